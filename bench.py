@@ -7,6 +7,10 @@ graph-evaluations/sec, whole job.  N > 1 (launched with torch.distributed.run):
 samples shard across ranks (weak scaling, no data-path collective); after the
 timed steps every rank accumulates its roots and ONE all-reduce (RCCL) combines
 the observable -- that reduce is inside the timed region.
+
+A plain run does only what the headline figure needs (set up, warm up, time --steps launches, print the line); --full adds
+every other measurement (ceilings, clock and power legs, cpu_baseline, accumulate, config 5, secondary rows, mc_step).
+--dump-outputs DIR writes what the last timed step computed (dump_outputs).
 """
 from __future__ import annotations
 
@@ -382,6 +386,29 @@ class Case:
         return bool(np.array_equal(got, want)), float(np.abs(got - want).max()) if n else 0.0, n
 
 
+DUMP_ROOT_BYTES = 48 << 20      # --dump-outputs: roots written per run (with the observable, well under 64 MB)
+DUMP_SEED = 20240917            # the sample of the batch whose roots are written: the same indices in every run with the same batch size
+
+
+def dump_outputs(path, case, acc):
+    """--dump-outputs DIR: what the timed path computed in its last step, as its caller receives it.  observable.npy: the column sums
+    of the roots after the one reduction, float64 [R].  roots_sample.npy: float64 [n, R], the roots of n samples of the batch (the
+    whole batch when 8 n R <= DUMP_ROOT_BYTES, otherwise n distinct sample indices drawn with DUMP_SEED, ascending), whatever the
+    layout.  The leaves are Philox-keyed by sample index, so the same arguments give the same inputs in every run."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "observable.npy"), acc.detach().to("cpu", torch.float64).numpy())
+    if DRY:
+        return
+    B, R, root = case.B, case.t.n_root, case.root
+    n = int(min(B, DUMP_ROOT_BYTES // (8 * R)))
+    idx = np.arange(B) if n == B else np.sort(np.random.default_rng(DUMP_SEED).choice(B, n, replace=False))
+    di = torch.from_numpy(idx).to(root.device)
+    got = root[di // 64, :, di % 64] if case.layout == "tile_major" else root[di]       # [n, R] either way
+    np.save(os.path.join(path, "roots_sample.npy"), got.to("cpu", torch.float64).numpy())
+
+
 def observable_sum(root):
     """Column sums of the root matrix, the observable of the final reduction.  For a Julia-layout matrix (R long rows)
     torch's reduction runs one workgroup per row -- 50 ms for 4 x 10^8 doubles -- so the rows are summed in two stages."""
@@ -734,6 +761,13 @@ def main():
     ap.add_argument("--secondary", default="", help="comma-separated workload:layout pairs to measure after the headline instead of the full list")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--power-seconds", type=float, default=1.5, help="per secondary row: seconds of back-to-back launches sampled with rocm-smi (socket power, sclk); 0 = off")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: measured copy / read ceilings, the probe clock and rocm-smi power next to the headline, "
+                         "cpu_baseline, the fused accumulation, config 5, the secondary rows and mc_step (a plain run sets up, warms up, times "
+                         "--steps launches and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float64): observable.npy, the reduced "
+                         "column sums of the roots [R], and roots_sample.npy, the roots of a fixed seeded sample of the batch [n, R] (dump_outputs)")
     ap.add_argument("--dry-run", action="store_true",
                     help="no device work: one process per rank on the CPU (gloo), the evaluator replaced by a stub that adds the shard's "
                          "sample count to the accumulator; checks sharding, the one collective and the stdout line (tests/test_bench_line.py)")
@@ -824,6 +858,8 @@ def main():
         elapsed = float(tt.item())
     kern_ms = ev.ms()
     avg_kernel_s = sum(kern_ms) / len(kern_ms) / 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, case, acc)
 
     total_evals = float(B) * args.steps * world
     value = total_evals / elapsed
@@ -881,19 +917,18 @@ def main():
                                                  "seconds": pi["seconds"], "seconds_settling": pi["seconds_settling"]}
         else:
             out["roofline"]["placement"] = "single allocation, as it came from the allocator (no trials)" + (f"; fdg_batch_alloc_pair failed: {case.pair_error}" if case.pair_error else "")
-        try:
-            if DRY:
-                raise RuntimeError("dry run")
-            copy_gbs = measured_copy(dev)
-            out["roofline"]["measured_copy_gbs"] = copy_gbs
-            out["roofline"]["measured_copy_kernel"] = "fdg_copy_device (16 B per lane, non-temporal loads and stores, 2 GiB, read + write counted)"
-            out["roofline"]["frac_of_measured_copy"] = achieved / copy_gbs
-            read_gbs = measured_read(dev)
-            out["roofline"]["measured_read_gbs"] = read_gbs            # (a read-only non-temporal stream: what the memory system gives the evaluator's kind of traffic)
-            out["roofline"]["frac_of_measured_read"] = achieved / read_gbs
-        except RuntimeError:
-            pass
-        if not DRY:
+        if not DRY and args.full:
+            try:
+                copy_gbs = measured_copy(dev)
+                out["roofline"]["measured_copy_gbs"] = copy_gbs
+                out["roofline"]["measured_copy_kernel"] = "fdg_copy_device (16 B per lane, non-temporal loads and stores, 2 GiB, read + write counted)"
+                out["roofline"]["frac_of_measured_copy"] = achieved / copy_gbs
+                read_gbs = measured_read(dev)
+                out["roofline"]["measured_read_gbs"] = read_gbs            # (a read-only non-temporal stream: what the memory system gives the evaluator's kind of traffic)
+                out["roofline"]["frac_of_measured_read"] = achieved / read_gbs
+            except RuntimeError:
+                pass
+        if not DRY and args.full:
             # the clock the chip sustains under the headline launch: ten more launches AFTER the contract's timed region, with the
             # probe wave on a side stream (the timed region itself runs without it)
             case.timed(min(10, max(2, args.steps)), 0)
@@ -901,7 +936,7 @@ def main():
                 out["roofline"]["clock_ghz"] = case.clock_ghz
                 if out["roofline"].get("frac_valu") is not None:
                     out["roofline"]["frac_valu_at_clock"] = out["roofline"]["valu_tops"] / (FP64_NOFMA_PEAK_TOPS * case.clock_ghz / SPEC_CLOCK_GHZ)
-        if not DRY and world == 1:
+        if not DRY and world == 1 and args.full:
             # what the package draws under the headline launch (rocm-smi; after and outside the timed region): the rows of this line run at the cap
             pw = power_leg(case.step)
             if pw:
@@ -912,9 +947,9 @@ def main():
                             "peak_tflops_fma": FP64_VALU_PEAK_TFLOPS,
                             "note": "secondary ceiling: add/mul only (no FMA contraction allowed), so the usable peak is half"}
         out["kernel_info"] = {k: info[k] for k in ("max_live", "spec_vgpr", "spec_lds_bytes", "spec_scratch_bytes")}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and not args.no_cpu_baseline and args.full:
             out["cpu_baseline"] = cpu_baseline(t, case, args.cpu_seconds)
-        if world == 1 and args.backend == "isa" and not DRY and not args.fast_math:
+        if world == 1 and args.backend == "isa" and not DRY and not args.fast_math and args.full:
             # The Monte-Carlo use of the same launch (after and outside the timed region, never part of `value`): weighted
             # accumulation inside the evaluator on the SAME resident batch -- fdg_accumulate_device: roots never reach HBM, so
             # the read stream has no stores in it.  Algorithmic bytes per sample: 8 L + 8 (the weight).
@@ -943,11 +978,11 @@ def main():
     freed = case.nbytes() + (8 * B if not DRY else 0)
     case.free()
     del case, leaf, root, f, step
-    if not DRY:
+    if not DRY and args.full:
         torch.cuda.empty_cache()
         settle_after_free(freed)
     # ---- after and outside the headline's timed region ---------------------------------------------------------
-    if args.backend == "isa" and not args.no_secondary and not args.fast_math:
+    if args.backend == "isa" and not args.no_secondary and not args.fast_math and args.full:
         # config 5 runs on every rank (its one collective needs them all); the rest on rank 0 at N = 1 only
         c5 = config5(dev, rank, world, dist if world > 1 or os.environ.get("FDG_BENCH_FORCE_DIST") else None, comm, steps=config5_steps(world), warm=30)
         if rank == 0:
@@ -975,7 +1010,7 @@ def main():
                                      "measured in this process after the headline's timed region (30 untimed + 20 timed launches each, HIP events on the "
                                      "launch stream); never part of `value`.  " + PARITY_NOTE)
     if rank == 0:
-        if world == 1 and not args.no_mc_step and args.backend == "isa":
+        if world == 1 and not args.no_mc_step and args.backend == "isa" and args.full:
             out["mc_step"] = mc_step(t, args.workload, min(B, 16_000_000), dev, args.fast_math)
         # the full objects go to bench_detail.json (and stderr); stdout gets ONE short line the driver can parse
         try:

@@ -14,7 +14,7 @@ Sigma2_0_0.diag.  This script computes the left side from the catalog text, buil
 writes (a) the 16 expected numbers and (b) the node table whose 16 roots are those Taylor coefficients, so that the CPU
 oracle and the device back ends can be held to the reference's own numbers without the reference present.
 
-Needs /root/reference (this container only).  Run: python tests/golden/make_gv_counterterm_kat.py
+Reads the catalogs stored in tests/golden/GV_diagrams.tar.xz (gv_catalogs.py).  Run: python tests/golden/make_gv_counterterm_kat.py
 """
 import json
 import os
@@ -25,7 +25,10 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
-RD = "/root/reference/src/frontend/GV_diagrams"
+sys.path.insert(0, HERE)
+import gv_catalogs  # noqa: E402
+
+RD = gv_catalogs.root()          # the reference's catalogs (src/frontend/GV_diagrams), the files this reads
 ORDERS = [(2, 0, 0), (2, 0, 1), (2, 0, 2), (2, 1, 0), (2, 1, 1), (2, 2, 0), (2, 1, 2), (2, 2, 2)]     # test/taylor.jl:98
 
 import oracle  # noqa: E402

@@ -83,7 +83,7 @@ def test_gpus_shard_and_reduce_through_the_c_abi(tmp_path, world):
 @pytest.mark.parametrize("comm", ["fdg", "torch"])
 def test_the_drivers_own_multi_gpu_command_line(world, comm):
     """the first multi-GPU node that runs the suite also runs the driver's exact command -- `python -m
-    torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W` --
+    torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W --full` --
     with both carriers of the one collective (RCCL through libfdg's fdg_comm_*, and torch.distributed's nccl backend), and reads the
     one stdout line: whole-job value, n_gpus, weak scaling, config 5's shards.  No scaling curve exists until this has run on such a node."""
     import json
@@ -100,7 +100,7 @@ def test_the_drivers_own_multi_gpu_command_line(world, comm):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1", "--comm", comm, "--samples", "4000000", "--no-mc-step",
-           "--secondary", "sigma2:tile_major"]
+           "--secondary", "sigma2:tile_major", "--full"]
     p = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

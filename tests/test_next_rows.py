@@ -5,6 +5,7 @@ catalogs; plus the optimizing back end's register-allocated program, replayed
 on the CPU against the oracle (no GPU needed)."""
 import json
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -19,7 +20,10 @@ from feynmandiagram_jl_amd.nodetable import NodeTable
 from feynmandiagram_jl_amd.producers.optimize import isequiv
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-REF_GV = "/root/reference/src/frontend/GV_diagrams"
+sys.path.insert(0, GOLD)
+import gv_catalogs  # noqa: E402
+
+REF_GV = gv_catalogs.root()          # the reference's GV catalogs that these tests read (src/frontend/GV_diagrams)
 
 
 class O(AbstractOperator):
@@ -122,7 +126,6 @@ def test_gv_tables_match_catalog_sums():
         assert oracle.eval_static(t, np.ones((1, t.n_leaf)))[0].tolist() == kat[str(order)]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_GV), reason="reference checkout not present (GPU box)")
 def test_gv_reader_reproduces_committed_tables():
     from feynmandiagram_jl_amd.producers import gv
     # leaf counts before/after optimize for sigma 2..4
@@ -142,7 +145,6 @@ def test_gv_reader_reproduces_committed_tables():
         assert np.array_equal(getattr(t.normalized(), a), getattr(w, a))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_GV), reason="reference checkout not present (GPU box)")
 def test_leafstates_on_gv_sigma3():
     """frontends.jl:178-232 over the leafmap of Compilers.compile-order lowering."""
     from feynmandiagram_jl_amd import FrontEnds
@@ -666,8 +668,6 @@ def test_taylor_ad_of_parquet_like_graph():
 def test_taylorAD_groups_by_order_and_evaluates_on_any_backend(libfdg):
     """taylorAD (utility.jl:48-93) on the real GV sigma_3 graphs, order 2 in the interaction: the
     enlarged graph set lowers through the same pipeline (config 4's shape: Power{2} nodes appear)."""
-    if not os.path.isdir(REF_GV):
-        pytest.skip("reference checkout not present (GPU box)")
     from feynmandiagram_jl_amd.producers import gv, taylor
     graphs = gv.diagsGV("sigma", 3, REF_GV)
     optimize.optimize_(graphs)
@@ -842,7 +842,6 @@ def test_mc_program_refuses_what_its_formulas_do_not_cover(libfdg):
         capi.GraphHandle(t).mc_program(tab)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_GV), reason="reference checkout not present (GPU box)")
 def test_taylor_coefficients_equal_the_counterterm_catalogs_orders_1_to_4():
     """The identity of test/taylor.jl:97-113 beyond the order the reference tests: for the 1st- to 4th-order GV self-energy and
     every counter-term catalog Sigma<n>_<VerOrder>_<GOrder>.diag with GOrder, VerOrder <= 2 that the reference ships (32 files),

@@ -2,6 +2,9 @@
 (test/front_end.jl:120-700: parameters, partitions, index helpers, filters, the diagram counts of the self-energy, the
 validity of Green's functions), by the optimized 2-loop graph the reference renders in assets/sigma_o2.svg (SURVEY.md
 Appendix A) and by value invariance under ``optimize!``.  No GPU."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
@@ -266,7 +269,10 @@ def test_taylor_expansion_of_the_parquet_self_energy_satisfies_the_series_identi
 
 
 # ---- the fully irreducible vertex from the GV catalogs (parquet.jl:216-231, vertex4.jl:112-120, operation.jl:178-257) -------
-REF_GV = "/root/reference/src/frontend/GV_diagrams"
+sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
+import gv_catalogs  # noqa: E402
+
+REF_GV = gv_catalogs.root()     # the reference's catalogs these tests read (src/frontend/GV_diagrams)
 
 
 def _catalog_sums(c):
@@ -287,9 +293,8 @@ def test_irreducible_vertex_catalogs(order, want):
     assert list(all_ones(graphs)) == want
     c = dict(np.load(os.path.join(workloads.DATA, f"vertex4I{order}.npz")))
     assert _catalog_sums(c) == want
-    if os.path.isdir(REF_GV):                   # the shipped arrays are the catalog's numbers
-        ref = gv.parse_vertex4_catalog(f"{REF_GV}/groups_vertex4/Vertex4I{order}_0_0.diag")
-        assert all(np.array_equal(ref[k], c[k]) for k in ref)
+    ref = gv.parse_vertex4_catalog(f"{REF_GV}/groups_vertex4/Vertex4I{order}_0_0.diag")      # the shipped arrays are the catalog's numbers
+    assert all(np.array_equal(ref[k], c[k]) for k in ref)
 
 
 def test_irreducible_vertex_enters_the_parquet_equations_with_the_right_multiplicity(monkeypatch):
@@ -391,9 +396,8 @@ def test_vertex_function_sums_agree_with_the_gv_vertex_catalogs(loops):
         t = workloads.get("gv_ver4_4")
         g = oracle.eval_static(t, np.ones((1, t.n_leaf)))[0]
         assert g[1::2].sum() == want and g[0::2].sum() == 0.0
-    if os.path.isdir(REF_GV):
-        c = gv.parse_vertex4_catalog(f"{REF_GV}/groups_vertex4/Vertex4{loops}_0_0.diag")
-        assert _catalog_sums(c) == [0.0, want]
+    c = gv.parse_vertex4_catalog(f"{REF_GV}/groups_vertex4/Vertex4{loops}_0_0.diag")
+    assert _catalog_sums(c) == [0.0, want]
 
 
 @pytest.mark.parametrize("loops", [1, 2, 3, 4, 5])
@@ -410,6 +414,5 @@ def test_polarization_sums_agree_with_the_gv_polarization_catalogs(loops):
     d = {r["response"]: float(x) for x, r in zip(all_ones([r["diagram"] for r in rows]), rows)}
     uu, ud = d.get(pq.UpUp, 0.0), d.get(pq.UpDown, 0.0)
     assert (2 * (uu + ud), 2 * (uu - ud)) == (charge, spin)
-    if os.path.isdir(REF_GV):
-        assert all_ones(gv.diagsGV("chargePolar", loops, REF_GV)).tolist() == [charge]
-        assert all_ones(gv.diagsGV("spinPolar", loops, REF_GV)).tolist() == [spin]
+    assert all_ones(gv.diagsGV("chargePolar", loops, REF_GV)).tolist() == [charge]
+    assert all_ones(gv.diagsGV("spinPolar", loops, REF_GV)).tolist() == [spin]

@@ -12,7 +12,7 @@ cd /tmp && export TMPDIR=/tmp
 # (a) the headline alone: the last 100 launches of fdg_isa_eval are bench.py's timed steps; (b) the whole default run
 timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/trace_headline" -o t -- python $R/bench.py --no-cpu-baseline --no-secondary --no-mc-step > "$OUT/bench_headline.json" 2> "$OUT/trace_headline.log"
 python $R/tools/rocpd_stats.py --last=100 $(find "$OUT/trace_headline" -name "*.db") > "$OUT/kernel_stats_headline.txt" 2>&1
-timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o t -- python $R/bench.py --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/trace.log"
+timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o t -- python $R/bench.py --full --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/trace.log"
 python $R/tools/rocpd_stats.py $(find "$OUT/trace" -name "*.db") > "$OUT/kernel_stats.txt" 2>&1
 [ "${PROF_TRACE_ONLY:-0}" = 1 ] && { cat "$OUT/kernel_stats_headline.txt" "$OUT/kernel_stats.txt"; exit 0; }
 SPECS=("parquet_sigma4 leaf_major" "parquet_sigma4 sample_major" "parquet_sigma4_dyn leaf_major" "parquet_sigma4_insdyn leaf_major" "parquet_sigma4_taylor2 leaf_major" "parquet_sigma5 leaf_major")
