@@ -41,7 +41,9 @@ EXPORTS = [
     "fdg_eval_device_tiled", "fdg_accumulate_device_tiled", "fdg_fill_uniform_device_tiled", "fdg_graph_set_association",
     "fdg_batch_alloc", "fdg_batch_free", "fdg_graph_pool_program", "fdg_batch_alloc_pair", "fdg_graph_set_option", "fdg_graph_get_option", "fdg_set_default_option", "fdg_get_default_option", "fdg_selftest_pair_search",
     "fdg_repack_tile_major", "fdg_unpack_tile_major",
+    "fdg_accumulate_device_binned", "fdg_mc_accumulate_device_binned",
 ]
+FDG_BIN_MAX = 16384     # fdg_accumulate_device_binned: largest n_bin
 COMM_ID_BYTES = 128
 
 
@@ -190,6 +192,9 @@ def lib():
     L.fdg_graph_specialize_fused.argtypes = [vp, C.POINTER(LeafTables), C.c_char_p, C.c_uint]
     L.fdg_mc_eval_device.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, i64, i64, i64, vp]
     L.fdg_mc_accumulate_device.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, dp, i64, vp]
+    L.fdg_accumulate_device_binned.argtypes = [vp, dp, i64, i64, i64, dp, C.c_int32, u32, dp, dp, i64, vp]
+    L.fdg_mc_accumulate_device_binned.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, C.c_int32, u32,
+                                                  dp, dp, i64, vp]
     L.fdg_comm_unique_id.argtypes = [C.c_void_p, C.c_size_t]
     L.fdg_comm_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(vp)]
     L.fdg_comm_destroy.argtypes = [vp]
@@ -395,6 +400,17 @@ class GraphHandle:
 
     def accumulate_device_tiled(self, d_leaf: int, ss: int, ls: int, lts: int, d_weight: int, d_acc: int, B: int, stream: int = 0):
         check(lib().fdg_accumulate_device_tiled(self._h, d_leaf, ss, ls, lts, d_weight or None, d_acc, B, stream))
+
+    # binned accumulation: d_acc[j * R + k] += w[b] root_k(b) for j = d_bin[b] - bin_base in [0, n_bin) (fdg.h) ---------------- #
+    def accumulate_device_binned(self, d_leaf: int, ss: int, ls: int, lts: int, d_bin: int, bin_base: int, n_bin: int, d_weight: int,
+                                 d_acc: int, B: int, stream: int = 0):
+        check(lib().fdg_accumulate_device_binned(self._h, d_leaf or None, ss, ls, lts, d_bin or None, bin_base,
+                                                 n_bin, d_weight or None, d_acc or None, B, stream))
+
+    def mc_accumulate_device_binned(self, d_K, ks, kc, d_T, ts, tc, kF, beta, lam, d_bin, bin_base, n_bin, d_weight, d_acc, B, stream=0):
+        check(lib().fdg_mc_accumulate_device_binned(self._h, d_K or None, ks, kc, d_T or None, ts, tc, kF, beta, lam,
+                                                    d_bin or None, bin_base, n_bin, d_weight or None,
+                                                    d_acc or None, B, stream))
 
     # fused Monte-Carlo step: leaves from (K, T) in registers, then the graph --------------------- #
     def specialize_fused(self, tables, cache_dir: Optional[str] = None, flags: int = 0):

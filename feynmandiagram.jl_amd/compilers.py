@@ -273,6 +273,54 @@ class GraphFunc:
             self.handle.accumulate_device_tiled(leaf.data_ptr(), leaf.stride(2), leaf.stride(1), leaf.stride(0), w, acc.data_ptr(), B, st)
         return acc
 
+    def accumulate_binned(self, leaf, bins, n_bin: int, weight=None, acc=None, bin_base: int = 0, n_sample: Optional[int] = None):
+        """The ``measure`` step of an observable that is a function of an external variable:
+        ``acc[j, k] += weight[b] * root_k(b)`` for every sample ``b`` with ``0 <= j = bins[b] - bin_base < n_bin`` (other samples add
+        nothing).  ``leaf`` is a float64 ``[B, L]`` CUDA tensor (any strides) or a tile-major ``(T, L, 64)`` batch (as
+        :meth:`accumulate_tiled` takes it); ``bins`` an int32 CUDA vector and ``weight`` a float64 one, both indexed by sample; ``acc`` a
+        contiguous float64 ``[n_bin, R]`` tensor (zeros when omitted), returned.  Deterministic: no float atomics (fdg_accumulate_device_binned)."""
+        import torch
+        tiled = _is_torch(leaf) and leaf.dim() == 3
+        if not (_is_torch(leaf) and leaf.is_cuda and leaf.dtype == torch.float64 and leaf.dim() in (2, 3)):
+            raise TypeError("leaf must be a float64 [B, L] CUDA tensor or a tile-major [tiles, L, 64] one")
+        if tiled:
+            self._check_tiled(leaf, self.n_leaf, "leaf")
+            cap = 64 * leaf.shape[0]
+        else:
+            if leaf.shape[1] < self.n_leaf:
+                raise IndexError("BoundsError: leafVal has fewer columns than the graph has leaves")
+            cap = leaf.shape[0]
+        B = cap if n_sample is None else int(n_sample)
+        if not (0 <= B <= cap):
+            raise ValueError("n_sample exceeds the batch")
+        n_bin = int(n_bin)
+        if not (1 <= n_bin <= capi.FDG_BIN_MAX):
+            raise ValueError(f"n_bin must lie in [1, {capi.FDG_BIN_MAX}]")
+        if not (_is_torch(bins) and bins.is_cuda):
+            raise TypeError("bins must be an int32 CUDA tensor")
+        if bins.dtype != torch.int32:
+            raise TypeError(f"bins must be an int32 CUDA tensor, not {bins.dtype}")
+        if bins.dim() != 1 or bins.shape[0] < B or bins.device != leaf.device:
+            raise ValueError("bins must be an int32 vector of at least n_sample elements on the leaves' device")
+        bins = bins.contiguous()
+        if acc is None:
+            acc = torch.zeros((n_bin, self.n_root), dtype=torch.float64, device=leaf.device)
+        if (not _is_torch(acc) or not acc.is_cuda or acc.device != leaf.device or acc.dtype != torch.float64 or not acc.is_contiguous()
+                or tuple(acc.shape) != (n_bin, self.n_root)):
+            raise ValueError(f"acc must be a contiguous float64 [{n_bin}, {self.n_root}] tensor on the leaves' device")
+        w = 0
+        if weight is not None:
+            if (not _is_torch(weight) or not weight.is_cuda or weight.device != leaf.device or weight.dtype != torch.float64
+                    or weight.dim() != 1 or weight.shape[0] < B):
+                raise ValueError("weight must be a float64 vector of at least n_sample elements on the leaves' device")
+            weight = weight.contiguous()
+            w = weight.data_ptr()
+        ss, ls, lts = (leaf.stride(2), leaf.stride(1), leaf.stride(0)) if tiled else (leaf.stride(0), leaf.stride(1), 0)
+        st = torch.cuda.current_stream(leaf.device).cuda_stream
+        with torch.cuda.device(leaf.device):
+            self.handle.accumulate_device_binned(leaf.data_ptr(), ss, ls, lts, bins.data_ptr(), int(bin_base), n_bin, w, acc.data_ptr(), B, st)
+        return acc
+
     def _call_numpy_typed(self, root, leaf):
         """Host arrays of an element type other than Float64: staged through the device (there is no CPU evaluator behind the ABI)."""
         import torch

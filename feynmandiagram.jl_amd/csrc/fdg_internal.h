@@ -229,6 +229,13 @@ int fdg_run_locked(fdg_graph *g, int mode, const double *d_leaf, int64_t ss, int
                    const double *d_weight, double *d_acc, int64_t B, hipStream_t st,
                    int64_t lts = 0, int64_t rts = 0);   // caller holds g->mu; lts / rts != 0: tile strides of a tile-major batch (fdg.h)
 int launch_reduce_partials(const double *partial, uint32_t nblk, uint32_t R, double *acc, hipStream_t st);
+int ensure_root_scratch(fdg_graph *g, size_t need);   // grows d_ws2 of the bound stream's scratch set (caller holds g->mu)
+int root_live_mask(fdg_graph *g, const uint8_t **out);  // device mask of the roots that exist (null: all of them); caller holds g->mu
+// the Monte-Carlo step of fdg_mc_eval_device / fdg_mc_accumulate_device after the argument checks (fdg_leaf.hip): the caller holds g->mu,
+// has bound the stream's scratch (fdg_bind_stream_ws) and has checked that fdg_graph_specialize_fused ran
+int fdg_mc_run_locked(fdg_graph *g, int mode, const double *d_K, int64_t ks, int64_t kc, const double *d_T, int64_t ts, int64_t tc,
+                      double kF, double beta, double lambda, double *d_root, int64_t rs, int64_t rk, const double *d_weight,
+                      double *d_acc, int64_t B, hipStream_t st);
 // Monte-Carlo step through one ISA kernel (fdg_runtime.hip); callers hold g->mu
 bool fdg_mc_isa_supported(fdg_graph *g, const fdg_leaf_tables *tab, std::string &why, bool *recommended);
 int fdg_mc_isa_build(fdg_graph *g);   // host-only (assembler); no-op when built

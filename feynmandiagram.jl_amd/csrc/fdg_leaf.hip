@@ -463,8 +463,16 @@ static int run_fused(fdg_graph *g, int mode, const double *d_K, int64_t ks, int6
   if (rc) return rc;
   rc = fdg_bind_stream_ws(g, stream);
   if (rc) return rc;
+  return fdg_mc_run_locked(g, mode, d_K, ks, kc, d_T, ts, tc, kF, beta, lambda, d_root, rs, rk, d_weight, d_acc, B, (hipStream_t)stream);
+}
+}  // extern "C"
+
+int fdg_mc_run_locked(fdg_graph *g, int mode, const double *d_K, int64_t ks, int64_t kc, const double *d_T, int64_t ts, int64_t tc,
+                      double kF, double beta, double lambda, double *d_root, int64_t rs, int64_t rk, const double *d_weight,
+                      double *d_acc, int64_t B, hipStream_t stream) {
+  int rc;
   if (g->mc_route == 3)
-    return fdg_mc_isa_run(g, mode, d_K, ks, kc, d_T, ts, tc, kF, beta, lambda, d_root, rs, rk, d_weight, d_acc, B, (hipStream_t)stream);
+    return fdg_mc_isa_run(g, mode, d_K, ks, kc, d_T, ts, tc, kF, beta, lambda, d_root, rs, rk, d_weight, d_acc, B, stream);
   if (g->mc_route == 2) {
     fdg_leaf_tables tab;
     tab.n_leaf = g->lt_hdr[0]; tab.n_basis = g->lt_hdr[1]; tab.n_loop = g->lt_hdr[2]; tab.dim = g->lt_hdr[3]; tab.n_tau = g->lt_hdr[4];
@@ -527,6 +535,7 @@ static int run_fused(fdg_graph *g, int mode, const double *d_K, int64_t ks, int6
   return FDG_OK;
 }
 
+extern "C" {
 int fdg_mc_eval_device(fdg_graph *g, const double *d_K, int64_t ks, int64_t kc, const double *d_T, int64_t ts, int64_t tc,
                        double kF, double beta, double lambda, double *d_root, int64_t rs, int64_t rk, int64_t B, void *stream) {
   return run_fused(g, 0, d_K, ks, kc, d_T, ts, tc, kF, beta, lambda, d_root, rs, rk, nullptr, nullptr, B, stream);

@@ -586,7 +586,7 @@ static int ensure_code(fdg_graph *g) {
 // Device mask of the roots that exist (root_slot[k] != FDG_NO_ROOT), for the passes over the column-major root scratch: null when every root
 // exists.  (the scratch's columns of missing roots are never written by the evaluator; copying or summing them would overwrite
 // root[k] / add garbage to acc[k], which fdg.h promises to leave alone.)
-static int root_live_mask(fdg_graph *g, const uint8_t **out) {
+int root_live_mask(fdg_graph *g, const uint8_t **out) {
   *out = nullptr;
   const Lowered &p = g->prog;
   bool any = false;
@@ -717,6 +717,7 @@ struct RunArgs {
   int64_t lts, rts;                 // tile strides of a tile-major batch (0: a plain strided matrix)
 };
 inline bool root_stride_ok(const RunArgs &a) { return !(a.rs < 0 || a.rs >= (1ll << 23)); }
+}  // namespace
 
 int ensure_root_scratch(fdg_graph *g, size_t need) {
   if (g->ws2_bytes >= need) return FDG_OK;
@@ -725,6 +726,8 @@ int ensure_root_scratch(fdg_graph *g, size_t need) {
   g->ws2_bytes = need;
   return FDG_OK;
 }
+
+namespace {
 
 // Roots into a ROW-MAJOR matrix (compile_Python's [B, R]) of a graph with many roots: a root store of the kernels is 64 lanes x 8 bytes, each in
 // another row -- with R = 180 (example/benchmark.jl's vertex function) the stores doubled the kernel's time.  Such calls evaluate chunk by chunk

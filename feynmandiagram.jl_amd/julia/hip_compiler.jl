@@ -239,6 +239,18 @@ function accumulate_device_tiled!(f::GraphFunc, d_acc::Ptr{Float64}, d_leaf::Ptr
         (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Cvoid}),
         f.handle, d_leaf, leaf_strides[1], leaf_strides[2], leaf_strides[3], d_weight, d_acc, B, stream))
 end
+# Binned accumulation (include/fdg.h: fdg_accumulate_device_binned), the `measure` step of an observable that depends on an external variable:
+# d_acc[k, j] += w[b] * root_k(b) for every sample b whose bin j = d_bin[b] (1-based: bin_base = 1) lies in 1:n_bin; other samples add nothing.
+# d_acc is an R x n_bin Matrix{Float64} on the device, d_bin a Vector{Int32}, d_weight a Vector{Float64} or C_NULL (weight 1), both indexed by
+# sample.  Leaves: a column-major B x L matrix (leaf_strides = (1, B), tile_stride = 0) or a tile-major batch (strides (1, 64), tile_stride
+# 64 L).  No float atomics: the same arguments give the same bits.
+function accumulate_device_binned!(f::GraphFunc, d_acc::Ptr{Float64}, d_leaf::Ptr{Float64}, d_bin::Ptr{Int32}, n_bin::Integer,
+    d_weight::Ptr{Float64}, B::Integer; leaf_strides=(1, B), tile_stride::Integer=0, bin_base::Integer=1, stream::Ptr{Cvoid}=C_NULL)
+    _fdg_check(ccall((:fdg_accumulate_device_binned, _libfdg), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Int64, Ptr{Int32}, Int32, UInt32, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Cvoid}),
+        f.handle, d_leaf, leaf_strides[1], leaf_strides[2], tile_stride, d_bin, bin_base, n_bin, d_weight, d_acc, B, stream))
+    return nothing
+end
 # device memory for a batch, backed by physical chunks of `chunk_bytes` (0: one allocation): fdg_batch_alloc / fdg_batch_free
 function batch_alloc(bytes::Integer; chunk_bytes::Integer=0)
     p = Ref{Ptr{Cvoid}}(C_NULL)
@@ -287,7 +299,7 @@ function accumulate_device!(f::GraphFunc, d_acc::Ptr{Float64}, d_leaf::Ptr{Float
         f.handle, d_leaf, leaf_strides[1], leaf_strides[2], d_weight, d_acc, B, stream))
 end
 
-export compile_hip, GraphFunc, eval_device!, accumulate_device!, eval_device_tiled!, accumulate_device_tiled!, batch_alloc, batch_free, tile_major!, from_tile_major!
+export compile_hip, GraphFunc, eval_device!, accumulate_device!, eval_device_tiled!, accumulate_device_tiled!, accumulate_device_binned!, mc_accumulate_device_binned!, batch_alloc, batch_free, tile_major!, from_tile_major!
 
 # ---- multi-GPU: one Julia process per GPU, ONE reduction of the accumulated observable ------------ #
 # (include/fdg.h, "multi-GPU").  Rank 0 calls `comm_unique_id()` and ships the 128 bytes to the other
@@ -368,6 +380,17 @@ function mc_accumulate_device!(f::GraphFunc, d_K::Ptr{Float64}, d_T::Ptr{Float64
     _fdg_check(ccall((:fdg_mc_accumulate_device, _libfdg), Cint,
         (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Int64, Float64, Float64, Float64, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Cvoid}),
         f.handle, d_K, k_strides[1], k_strides[2], d_T, t_strides[1], t_strides[2], kF, beta, lambda, d_weight, d_acc, B, stream))
+    return nothing
+end
+# the same into bins (fdg_mc_accumulate_device_binned): d_acc is R x n_bin, d_bin 1-based by default, as in accumulate_device_binned!
+function mc_accumulate_device_binned!(f::GraphFunc, d_K::Ptr{Float64}, d_T::Ptr{Float64}, d_bin::Ptr{Int32}, n_bin::Integer,
+    d_weight::Ptr{Float64}, d_acc::Ptr{Float64}, B::Integer; kF::Float64, beta::Float64, lambda::Float64, k_strides=(1, B), t_strides=(1, B),
+    bin_base::Integer=1, stream::Ptr{Cvoid}=C_NULL)
+    _fdg_check(ccall((:fdg_mc_accumulate_device_binned, _libfdg), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Int64, Float64, Float64, Float64, Ptr{Int32}, Int32, UInt32, Ptr{Float64},
+         Ptr{Float64}, Int64, Ptr{Cvoid}),
+        f.handle, d_K, k_strides[1], k_strides[2], d_T, t_strides[1], t_strides[2], kF, beta, lambda, d_bin, bin_base, n_bin, d_weight, d_acc,
+        B, stream))
     return nothing
 end
 

@@ -1,6 +1,8 @@
 """Multi-GPU decomposition of the evaluator: samples are independent, so they
 shard across ranks with no data-path collective; the only exchange is ONE
 all-reduce of the accumulated observable (R doubles) at the end.
+The observable may also be binned, R x n_bin doubles (``GraphFunc.accumulate_binned``,
+fdg_accumulate_device_binned): the same reduce over n_bin * R doubles, unchanged.
 The reference has no counterpart (single-threaded); downstream users do this
 reduce in MCIntegration.jl.
 

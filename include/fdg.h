@@ -348,6 +348,26 @@ int fdg_eval_device_tiled(fdg_graph *g, const double *d_leaf, int64_t leaf_sampl
                           int64_t root_tile_stride, int64_t n_sample, void *stream);
 int fdg_accumulate_device_tiled(fdg_graph *g, const double *d_leaf, int64_t leaf_sample_stride, int64_t leaf_leaf_stride,
                                 int64_t leaf_tile_stride, const double *d_weight, double *d_acc, int64_t n_sample, void *stream);
+/* Binned accumulation: the `measure` step of a Monte-Carlo integrand whose observable is a function of an
+ * external variable.  For every sample b with 0 <= j = d_bin[b] - bin_base < n_bin:
+ *     d_acc[j * R + k] += w[b] * root_k(b)          (w = d_weight[b], or 1 when d_weight is NULL)
+ * Samples whose bin falls outside [0, n_bin) add nothing.  d_acc holds n_bin x R doubles, bin-major
+ * (a Julia R x n_bin Matrix{Float64}; torch [n_bin, R]), and is added to, not overwritten.
+ * bin_base: 0 for C / Python indices, 1 for Julia's 1-based ones.
+ * Leaves as in fdg_eval_device_tiled: leaf_tile_stride 0 = a plain strided matrix (any back end);
+ * != 0 = a tile-major batch (needs FDG_SPEC_ISA, FDG_E_UNSUPPORTED otherwise).  d_bin and d_weight are
+ * plain vectors indexed by the sample number b in both cases.
+ * Roots that do not exist (FDG_NO_ROOT) leave their column of every bin untouched.
+ * No float atomics anywhere: bitwise reproducible for the same arguments on the same device.
+ * 1 <= n_bin <= FDG_BIN_MAX (FDG_E_INVALID for 0, FDG_E_UNSUPPORTED above).
+ * The roots of a chunk of samples (FDG_ROOT_SCRATCH_MB) go through the handle's column-major root scratch -- the same
+ * route and the same bits as fdg_eval_device --, a deterministic pass bins them (csrc/fdg_binned.hip). */
+#define FDG_BIN_MAX 16384
+int fdg_accumulate_device_binned(fdg_graph *g, const double *d_leaf, int64_t leaf_sample_stride,
+                                 int64_t leaf_leaf_stride, int64_t leaf_tile_stride,
+                                 const int32_t *d_bin, int32_t bin_base, uint32_t n_bin,
+                                 const double *d_weight, double *d_acc, int64_t n_sample, void *stream);
+
 /* harness: fdg_fill_uniform_device's values (same counters: sample_offset + b, i) written into a tile-major batch */
 int fdg_fill_uniform_device_tiled(double *d_leaf, int64_t n_sample, uint32_t n_leaf, int64_t leaf_sample_stride,
                                   int64_t leaf_leaf_stride, int64_t leaf_tile_stride, uint64_t seed, uint64_t sample_offset,
@@ -529,6 +549,13 @@ int fdg_mc_eval_device(fdg_graph *g, const double *d_K, int64_t k_sample_stride,
 int fdg_mc_accumulate_device(fdg_graph *g, const double *d_K, int64_t k_sample_stride, int64_t k_comp_stride, const double *d_T,
                              int64_t t_sample_stride, int64_t t_comp_stride, double kF, double beta, double lambda,
                              const double *d_weight, double *d_acc, int64_t n_sample, void *stream);
+/* fdg_accumulate_device_binned for the fused Monte-Carlo step (K, T, kF, beta, lambda as in fdg_mc_accumulate_device;
+ * every route: fused, split, one-kernel ISA). */
+int fdg_mc_accumulate_device_binned(fdg_graph *g, const double *d_K, int64_t k_sample_stride, int64_t k_comp_stride,
+                                    const double *d_T, int64_t t_sample_stride, int64_t t_comp_stride,
+                                    double kF, double beta, double lambda,
+                                    const int32_t *d_bin, int32_t bin_base, uint32_t n_bin,
+                                    const double *d_weight, double *d_acc, int64_t n_sample, void *stream);
 
 /* Device workspace control: the interpreter keeps per-sample overflow slots in
  * an HBM panel owned by the handle; it is sized on first use for the number of
