@@ -42,6 +42,7 @@ EXPORTS = [
     "fdg_batch_alloc", "fdg_batch_free", "fdg_graph_pool_program", "fdg_batch_alloc_pair", "fdg_graph_set_option", "fdg_graph_get_option", "fdg_set_default_option", "fdg_get_default_option", "fdg_selftest_pair_search",
     "fdg_repack_tile_major", "fdg_unpack_tile_major",
     "fdg_accumulate_device_binned", "fdg_mc_accumulate_device_binned",
+    "fdg_accumulate_device_moments", "fdg_mc_accumulate_device_moments",
 ]
 FDG_BIN_MAX = 16384     # fdg_accumulate_device_binned: largest n_bin
 COMM_ID_BYTES = 128
@@ -195,6 +196,9 @@ def lib():
     L.fdg_accumulate_device_binned.argtypes = [vp, dp, i64, i64, i64, dp, C.c_int32, u32, dp, dp, i64, vp]
     L.fdg_mc_accumulate_device_binned.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, C.c_int32, u32,
                                                   dp, dp, i64, vp]
+    L.fdg_accumulate_device_moments.argtypes = [vp, dp, i64, i64, i64, dp, C.c_int32, u32, dp, dp, dp, i64, vp]
+    L.fdg_mc_accumulate_device_moments.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, C.c_int32, u32,
+                                                   dp, dp, dp, i64, vp]
     L.fdg_comm_unique_id.argtypes = [C.c_void_p, C.c_size_t]
     L.fdg_comm_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(vp)]
     L.fdg_comm_destroy.argtypes = [vp]
@@ -411,6 +415,18 @@ class GraphHandle:
         check(lib().fdg_mc_accumulate_device_binned(self._h, d_K or None, ks, kc, d_T or None, ts, tc, kF, beta, lam,
                                                     d_bin or None, bin_base, n_bin, d_weight or None,
                                                     d_acc or None, B, stream))
+
+    # second moments as well: d_acc2[j * R + k] += (w[b] root_k(b))^2; d_bin 0 = every sample in bin 0 (n_bin 1) (fdg.h) ------- #
+    def accumulate_device_moments(self, d_leaf: int, ss: int, ls: int, lts: int, d_bin: int, bin_base: int, n_bin: int, d_weight: int,
+                                  d_acc: int, d_acc2: int, B: int, stream: int = 0):
+        check(lib().fdg_accumulate_device_moments(self._h, d_leaf or None, ss, ls, lts, d_bin or None, bin_base,
+                                                  n_bin, d_weight or None, d_acc or None, d_acc2 or None, B, stream))
+
+    def mc_accumulate_device_moments(self, d_K, ks, kc, d_T, ts, tc, kF, beta, lam, d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B,
+                                     stream=0):
+        check(lib().fdg_mc_accumulate_device_moments(self._h, d_K or None, ks, kc, d_T or None, ts, tc, kF, beta, lam,
+                                                     d_bin or None, bin_base, n_bin, d_weight or None,
+                                                     d_acc or None, d_acc2 or None, B, stream))
 
     # fused Monte-Carlo step: leaves from (K, T) in registers, then the graph --------------------- #
     def specialize_fused(self, tables, cache_dir: Optional[str] = None, flags: int = 0):

@@ -37,6 +37,32 @@ def _is_torch(x) -> bool:
     return type(x).__module__.split(".")[0] == "torch"
 
 
+def mc_estimate(acc, acc2, n_sample: int):
+    """Mean and standard error per (bin, root) from the moments of :meth:`GraphFunc.accumulate_moments` over ``n_sample`` samples:
+    ``mean = S1 / N`` and ``err = sqrt((S2 / N - mean**2) / (N - 1))``, with ``S1 = acc``, ``S2 = acc2`` and ``N = n_sample``.
+    ``N`` is the whole batch, every sample whether or not it fell into the bin (a sample outside a bin contributes 0 to it).
+    ``acc`` and ``acc2`` are torch tensors or numpy arrays of one shape; the results are of the same kind.  ``N < 2`` raises
+    ``ValueError``: one sample has no error bar.
+
+    Cancellation: ``S2 / N - mean**2`` subtracts two numbers of size ``mean**2``.  When ``|mean| >> std`` their difference keeps only
+    about ``16 - 2 log10(|mean| / std)`` significant digits, and at ``|mean| / std`` near 1e8 nothing of the variance is left.  A
+    difference that rounds below zero is reported as an error of 0, not as nan.  For such integrands shift the integrand by a known
+    estimate of its mean (or centre each batch) before accumulating."""
+    N = int(n_sample)
+    if N < 2:
+        raise ValueError(f"mc_estimate needs n_sample >= 2 (got {N}): the standard error of one sample is undefined")
+    if tuple(acc.shape) != tuple(acc2.shape):
+        raise ValueError("acc and acc2 must have the same shape")
+    mean = acc / N
+    var = (acc2 / N - mean * mean) / (N - 1)
+    if _is_torch(var):
+        err = var.clamp(min=0.0).sqrt()
+    else:
+        import numpy as np
+        err = np.sqrt(np.maximum(var, 0.0))
+    return mean, err
+
+
 class GraphFunc:
     """Callable evaluator bound to one lowered graph set (one ``fdg_graph``)."""
 
@@ -280,6 +306,38 @@ class GraphFunc:
         :meth:`accumulate_tiled` takes it); ``bins`` an int32 CUDA vector and ``weight`` a float64 one, both indexed by sample; ``acc`` a
         contiguous float64 ``[n_bin, R]`` tensor (zeros when omitted), returned.  Deterministic: no float atomics (fdg_accumulate_device_binned)."""
         import torch
+        B, n_bin, bins, weight, strides = self._binned_args(leaf, bins, n_bin, weight, n_sample)
+        w = 0 if weight is None else weight.data_ptr()
+        acc = self._bin_acc(acc, n_bin, leaf, "acc")
+        st = torch.cuda.current_stream(leaf.device).cuda_stream
+        with torch.cuda.device(leaf.device):
+            self.handle.accumulate_device_binned(leaf.data_ptr(), *strides, bins.data_ptr(), int(bin_base), n_bin, w, acc.data_ptr(), B, st)
+        return acc
+
+    def accumulate_moments(self, leaf, bins=None, n_bin: int = 1, weight=None, acc=None, acc2=None, bin_base: int = 0,
+                           n_sample: Optional[int] = None):
+        """:meth:`accumulate_binned` with the second moment, for Monte-Carlo error bars: with ``t = weight[b] * root_k(b)``,
+        ``acc[j, k] += t`` and ``acc2[j, k] += t * t`` for the samples in bin ``j``.  ``bins=None``: every sample is in bin 0 and
+        ``n_bin`` must be 1.  ``acc`` comes out with the bits :meth:`accumulate_binned` gives for the same arguments (an all-zero
+        ``bins`` for ``bins=None``).  Returns ``(acc, acc2)``, two float64 ``[n_bin, R]`` tensors (zeros when omitted), added to.
+        :func:`mc_estimate` turns them into a mean and a standard error (fdg_accumulate_device_moments)."""
+        import torch
+        B, n_bin, bins, weight, strides = self._binned_args(leaf, bins, n_bin, weight, n_sample, bins_optional=True)
+        w = 0 if weight is None else weight.data_ptr()
+        acc = self._bin_acc(acc, n_bin, leaf, "acc")
+        acc2 = self._bin_acc(acc2, n_bin, leaf, "acc2")
+        if acc.data_ptr() == acc2.data_ptr():
+            raise ValueError("acc and acc2 must be different tensors")
+        st = torch.cuda.current_stream(leaf.device).cuda_stream
+        with torch.cuda.device(leaf.device):
+            self.handle.accumulate_device_moments(leaf.data_ptr(), *strides, 0 if bins is None else bins.data_ptr(), int(bin_base), n_bin,
+                                                  w, acc.data_ptr(), acc2.data_ptr(), B, st)
+        return acc, acc2
+
+    def _binned_args(self, leaf, bins, n_bin, weight, n_sample, bins_optional=False):
+        """The checks of :meth:`accumulate_binned` / :meth:`accumulate_moments`: (n_sample, n_bin, bins, weight, leaf strides), bins and
+        weight contiguous (the caller holds them until the launch is queued)."""
+        import torch
         tiled = _is_torch(leaf) and leaf.dim() == 3
         if not (_is_torch(leaf) and leaf.is_cuda and leaf.dtype == torch.float64 and leaf.dim() in (2, 3)):
             raise TypeError("leaf must be a float64 [B, L] CUDA tensor or a tile-major [tiles, L, 64] one")
@@ -296,29 +354,32 @@ class GraphFunc:
         n_bin = int(n_bin)
         if not (1 <= n_bin <= capi.FDG_BIN_MAX):
             raise ValueError(f"n_bin must lie in [1, {capi.FDG_BIN_MAX}]")
-        if not (_is_torch(bins) and bins.is_cuda):
-            raise TypeError("bins must be an int32 CUDA tensor")
-        if bins.dtype != torch.int32:
-            raise TypeError(f"bins must be an int32 CUDA tensor, not {bins.dtype}")
-        if bins.dim() != 1 or bins.shape[0] < B or bins.device != leaf.device:
-            raise ValueError("bins must be an int32 vector of at least n_sample elements on the leaves' device")
-        bins = bins.contiguous()
-        if acc is None:
-            acc = torch.zeros((n_bin, self.n_root), dtype=torch.float64, device=leaf.device)
-        if (not _is_torch(acc) or not acc.is_cuda or acc.device != leaf.device or acc.dtype != torch.float64 or not acc.is_contiguous()
-                or tuple(acc.shape) != (n_bin, self.n_root)):
-            raise ValueError(f"acc must be a contiguous float64 [{n_bin}, {self.n_root}] tensor on the leaves' device")
-        w = 0
+        if bins is None and bins_optional:
+            if n_bin != 1:
+                raise ValueError("bins=None puts every sample in bin 0: n_bin must be 1")
+        else:
+            if not (_is_torch(bins) and bins.is_cuda):
+                raise TypeError("bins must be an int32 CUDA tensor")
+            if bins.dtype != torch.int32:
+                raise TypeError(f"bins must be an int32 CUDA tensor, not {bins.dtype}")
+            if bins.dim() != 1 or bins.shape[0] < B or bins.device != leaf.device:
+                raise ValueError("bins must be an int32 vector of at least n_sample elements on the leaves' device")
+            bins = bins.contiguous()
         if weight is not None:
             if (not _is_torch(weight) or not weight.is_cuda or weight.device != leaf.device or weight.dtype != torch.float64
                     or weight.dim() != 1 or weight.shape[0] < B):
                 raise ValueError("weight must be a float64 vector of at least n_sample elements on the leaves' device")
             weight = weight.contiguous()
-            w = weight.data_ptr()
-        ss, ls, lts = (leaf.stride(2), leaf.stride(1), leaf.stride(0)) if tiled else (leaf.stride(0), leaf.stride(1), 0)
-        st = torch.cuda.current_stream(leaf.device).cuda_stream
-        with torch.cuda.device(leaf.device):
-            self.handle.accumulate_device_binned(leaf.data_ptr(), ss, ls, lts, bins.data_ptr(), int(bin_base), n_bin, w, acc.data_ptr(), B, st)
+        strides = (leaf.stride(2), leaf.stride(1), leaf.stride(0)) if tiled else (leaf.stride(0), leaf.stride(1), 0)
+        return B, n_bin, bins, weight, strides
+
+    def _bin_acc(self, acc, n_bin, leaf, what):
+        import torch
+        if acc is None:
+            acc = torch.zeros((n_bin, self.n_root), dtype=torch.float64, device=leaf.device)
+        if (not _is_torch(acc) or not acc.is_cuda or acc.device != leaf.device or acc.dtype != torch.float64 or not acc.is_contiguous()
+                or tuple(acc.shape) != (n_bin, self.n_root)):
+            raise ValueError(f"{what} must be a contiguous float64 [{n_bin}, {self.n_root}] tensor on the leaves' device")
         return acc
 
     def _call_numpy_typed(self, root, leaf):

@@ -251,6 +251,18 @@ function accumulate_device_binned!(f::GraphFunc, d_acc::Ptr{Float64}, d_leaf::Pt
         f.handle, d_leaf, leaf_strides[1], leaf_strides[2], tile_stride, d_bin, bin_base, n_bin, d_weight, d_acc, B, stream))
     return nothing
 end
+# Second moments as well (fdg_accumulate_device_moments), for Monte-Carlo error bars: with t = w[b] * root_k(b), d_acc[k, j] += t and
+# d_acc2[k, j] += t * t.  d_acc and d_acc2 are two distinct R x n_bin matrices; d_acc gets the bits accumulate_device_binned! gives.
+# d_bin = C_NULL puts every sample in one bin (n_bin = 1, bin_base ignored): the plain sum with its error bar.  Mean and standard error per
+# (root, bin) over the B samples: m = S1 / B, err = sqrt((S2 / B - m^2) / (B - 1)).
+function accumulate_device_moments!(f::GraphFunc, d_acc::Ptr{Float64}, d_acc2::Ptr{Float64}, d_leaf::Ptr{Float64}, d_bin::Ptr{Int32},
+    n_bin::Integer, d_weight::Ptr{Float64}, B::Integer; leaf_strides=(1, B), tile_stride::Integer=0, bin_base::Integer=1,
+    stream::Ptr{Cvoid}=C_NULL)
+    _fdg_check(ccall((:fdg_accumulate_device_moments, _libfdg), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Int64, Ptr{Int32}, Int32, UInt32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Cvoid}),
+        f.handle, d_leaf, leaf_strides[1], leaf_strides[2], tile_stride, d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, stream))
+    return nothing
+end
 # device memory for a batch, backed by physical chunks of `chunk_bytes` (0: one allocation): fdg_batch_alloc / fdg_batch_free
 function batch_alloc(bytes::Integer; chunk_bytes::Integer=0)
     p = Ref{Ptr{Cvoid}}(C_NULL)
@@ -299,7 +311,7 @@ function accumulate_device!(f::GraphFunc, d_acc::Ptr{Float64}, d_leaf::Ptr{Float
         f.handle, d_leaf, leaf_strides[1], leaf_strides[2], d_weight, d_acc, B, stream))
 end
 
-export compile_hip, GraphFunc, eval_device!, accumulate_device!, eval_device_tiled!, accumulate_device_tiled!, accumulate_device_binned!, mc_accumulate_device_binned!, batch_alloc, batch_free, tile_major!, from_tile_major!
+export compile_hip, GraphFunc, eval_device!, accumulate_device!, eval_device_tiled!, accumulate_device_tiled!, accumulate_device_binned!, mc_accumulate_device_binned!, accumulate_device_moments!, mc_accumulate_device_moments!, batch_alloc, batch_free, tile_major!, from_tile_major!
 
 # ---- multi-GPU: one Julia process per GPU, ONE reduction of the accumulated observable ------------ #
 # (include/fdg.h, "multi-GPU").  Rank 0 calls `comm_unique_id()` and ships the 128 bytes to the other
@@ -391,6 +403,17 @@ function mc_accumulate_device_binned!(f::GraphFunc, d_K::Ptr{Float64}, d_T::Ptr{
          Ptr{Float64}, Int64, Ptr{Cvoid}),
         f.handle, d_K, k_strides[1], k_strides[2], d_T, t_strides[1], t_strides[2], kF, beta, lambda, d_bin, bin_base, n_bin, d_weight, d_acc,
         B, stream))
+    return nothing
+end
+# both moments for the fused step (fdg_mc_accumulate_device_moments): d_acc, d_acc2 and d_bin as in accumulate_device_moments!
+function mc_accumulate_device_moments!(f::GraphFunc, d_K::Ptr{Float64}, d_T::Ptr{Float64}, d_bin::Ptr{Int32}, n_bin::Integer,
+    d_weight::Ptr{Float64}, d_acc::Ptr{Float64}, d_acc2::Ptr{Float64}, B::Integer; kF::Float64, beta::Float64, lambda::Float64,
+    k_strides=(1, B), t_strides=(1, B), bin_base::Integer=1, stream::Ptr{Cvoid}=C_NULL)
+    _fdg_check(ccall((:fdg_mc_accumulate_device_moments, _libfdg), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Int64, Float64, Float64, Float64, Ptr{Int32}, Int32, UInt32, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Cvoid}),
+        f.handle, d_K, k_strides[1], k_strides[2], d_T, t_strides[1], t_strides[2], kF, beta, lambda, d_bin, bin_base, n_bin, d_weight, d_acc,
+        d_acc2, B, stream))
     return nothing
 end
 

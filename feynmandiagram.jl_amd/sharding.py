@@ -3,6 +3,11 @@ shard across ranks with no data-path collective; the only exchange is ONE
 all-reduce of the accumulated observable (R doubles) at the end.
 The observable may also be binned, R x n_bin doubles (``GraphFunc.accumulate_binned``,
 fdg_accumulate_device_binned): the same reduce over n_bin * R doubles, unchanged.
+Both moments of ``GraphFunc.accumulate_moments`` (fdg_accumulate_device_moments) are
+additive across ranks too: allocate ``acc`` and ``acc2`` as the two halves of one
+``[2, n_bin, R]`` tensor (``m = torch.zeros(2, n_bin, R); acc, acc2 = m[0], m[1]``), and one
+``reduce_observable`` call over its 2 * n_bin * R doubles covers both; ``mc_estimate`` then
+takes the reduced halves with N = the sum of the ranks' batch sizes.
 The reference has no counterpart (single-threaded); downstream users do this
 reduce in MCIntegration.jl.
 

@@ -367,6 +367,17 @@ int fdg_accumulate_device_binned(fdg_graph *g, const double *d_leaf, int64_t lea
                                  int64_t leaf_leaf_stride, int64_t leaf_tile_stride,
                                  const int32_t *d_bin, int32_t bin_base, uint32_t n_bin,
                                  const double *d_weight, double *d_acc, int64_t n_sample, void *stream);
+/* Second moments, for Monte-Carlo error bars: fdg_accumulate_device_binned plus, with t = w[b] * root_k(b),
+ *     d_acc2[j * R + k] += t * t                    (the square rounded to double before it is added)
+ * d_acc comes out bit for bit as fdg_accumulate_device_binned leaves it for the same arguments (the same
+ * chunks, segments and order of sums); d_acc2 is bitwise reproducible too.  Both arrays hold n_bin x R doubles
+ * and are added to; FDG_NO_ROOT columns stay untouched in both.  d_bin == NULL: every sample is in bin 0,
+ * n_bin must be 1 and bin_base is ignored (the plain sum with its error bar; the same bits as an all-zero d_bin).
+ * FDG_E_INVALID: d_acc or d_acc2 NULL, d_acc == d_acc2, d_bin NULL with n_bin != 1, and the binned call's cases;
+ * FDG_E_UNSUPPORTED: n_bin > FDG_BIN_MAX, or a tile-major batch without FDG_SPEC_ISA.  All before any device work. */
+int fdg_accumulate_device_moments(fdg_graph *g, const double *d_leaf, int64_t leaf_sample_stride, int64_t leaf_leaf_stride,
+                                  int64_t leaf_tile_stride, const int32_t *d_bin, int32_t bin_base, uint32_t n_bin,
+                                  const double *d_weight, double *d_acc, double *d_acc2, int64_t n_sample, void *stream);
 
 /* harness: fdg_fill_uniform_device's values (same counters: sample_offset + b, i) written into a tile-major batch */
 int fdg_fill_uniform_device_tiled(double *d_leaf, int64_t n_sample, uint32_t n_leaf, int64_t leaf_sample_stride,
@@ -556,6 +567,13 @@ int fdg_mc_accumulate_device_binned(fdg_graph *g, const double *d_K, int64_t k_s
                                     double kF, double beta, double lambda,
                                     const int32_t *d_bin, int32_t bin_base, uint32_t n_bin,
                                     const double *d_weight, double *d_acc, int64_t n_sample, void *stream);
+/* fdg_accumulate_device_moments for the fused Monte-Carlo step (every route; FDG_E_INVALID before
+ * fdg_graph_specialize_fused). */
+int fdg_mc_accumulate_device_moments(fdg_graph *g, const double *d_K, int64_t k_sample_stride, int64_t k_comp_stride,
+                                     const double *d_T, int64_t t_sample_stride, int64_t t_comp_stride,
+                                     double kF, double beta, double lambda,
+                                     const int32_t *d_bin, int32_t bin_base, uint32_t n_bin,
+                                     const double *d_weight, double *d_acc, double *d_acc2, int64_t n_sample, void *stream);
 
 /* Device workspace control: the interpreter keeps per-sample overflow slots in
  * an HBM panel owned by the handle; it is sized on first use for the number of
