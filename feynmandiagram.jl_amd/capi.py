@@ -43,8 +43,10 @@ EXPORTS = [
     "fdg_repack_tile_major", "fdg_unpack_tile_major",
     "fdg_accumulate_device_binned", "fdg_mc_accumulate_device_binned",
     "fdg_accumulate_device_moments", "fdg_mc_accumulate_device_moments",
+    "fdg_vegas_sample_device", "fdg_accumulate_device_vegas", "fdg_mc_accumulate_device_vegas", "fdg_vegas_refine",
 ]
 FDG_BIN_MAX = 16384     # fdg_accumulate_device_binned: largest n_bin
+FDG_VEGAS_DIM_MAX, FDG_VEGAS_GRID_MAX = 64, 1024     # the VEGAS map: most variables, most cells per variable
 COMM_ID_BYTES = 128
 
 
@@ -199,6 +201,11 @@ def lib():
     L.fdg_accumulate_device_moments.argtypes = [vp, dp, i64, i64, i64, dp, C.c_int32, u32, dp, dp, dp, i64, vp]
     L.fdg_mc_accumulate_device_moments.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, C.c_int32, u32,
                                                    dp, dp, dp, i64, vp]
+    L.fdg_vegas_sample_device.argtypes = [dp, u32, u32, C.c_void_p, u64, u64, dp, i64, i64, dp, dp, i64, vp]
+    L.fdg_accumulate_device_vegas.argtypes = [vp, dp, i64, i64, i64, dp, C.c_void_p, u64, u64, u32, u32, dp, dp, dp, i64, vp]
+    L.fdg_mc_accumulate_device_vegas.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, C.c_void_p, u64, u64,
+                                                 u32, u32, dp, dp, dp, i64, vp]
+    L.fdg_vegas_refine.argtypes = [C.c_void_p, C.c_void_p, u32, u32, C.c_double]
     L.fdg_comm_unique_id.argtypes = [C.c_void_p, C.c_size_t]
     L.fdg_comm_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(vp)]
     L.fdg_comm_destroy.argtypes = [vp]
@@ -428,6 +435,29 @@ class GraphHandle:
                                                      d_bin or None, bin_base, n_bin, d_weight or None,
                                                      d_acc or None, d_acc2 or None, B, stream))
 
+    # one VEGAS iteration's accumulate step: both moments (the bits of the moments calls with d_bin 0, n_bin 1) and the training histogram
+    # d_hist[d * n_grid + c] += (w[b] sum_k coef[k] root_k(b))^2, c = the cell of counter (sample_offset + b, d); coef: host vector or None (fdg.h)
+    def accumulate_device_vegas(self, d_leaf: int, ss: int, ls: int, lts: int, d_weight: int, coef, seed: int, sample_offset: int, n_dim: int,
+                                n_grid: int, d_acc: int, d_acc2: int, d_hist: int, B: int, stream: int = 0):
+        c = self._coef(coef)
+        check(lib().fdg_accumulate_device_vegas(self._h, d_leaf or None, ss, ls, lts, d_weight or None, None if c is None else c.ctypes.data,
+                                                seed, sample_offset, n_dim, n_grid, d_acc or None, d_acc2 or None, d_hist or None, B, stream))
+
+    def mc_accumulate_device_vegas(self, d_K, ks, kc, d_T, ts, tc, kF, beta, lam, d_weight, coef, seed, sample_offset, n_dim, n_grid, d_acc,
+                                   d_acc2, d_hist, B, stream=0):
+        c = self._coef(coef)
+        check(lib().fdg_mc_accumulate_device_vegas(self._h, d_K or None, ks, kc, d_T or None, ts, tc, kF, beta, lam, d_weight or None,
+                                                   None if c is None else c.ctypes.data, seed, sample_offset, n_dim, n_grid,
+                                                   d_acc or None, d_acc2 or None, d_hist or None, B, stream))
+
+    def _coef(self, coef):
+        if coef is None:
+            return None
+        c = np.ascontiguousarray(coef, dtype=np.float64)
+        if c.shape != (self.table.n_root,):
+            raise ValueError(f"coef must hold n_root = {self.table.n_root} factors")
+        return c
+
     # fused Monte-Carlo step: leaves from (K, T) in registers, then the graph --------------------- #
     def specialize_fused(self, tables, cache_dir: Optional[str] = None, flags: int = 0):
         """``tables`` = the struct returned by make_leaf_tables."""
@@ -469,6 +499,31 @@ def fill_uniform_device(d_leaf: int, B: int, L: int, ss: int, ls: int, seed: int
 def fill_uniform_device_tiled(d_leaf: int, B: int, L: int, ss: int, ls: int, lts: int, seed: int, sample_offset: int = 0,
                                stream: int = 0):
     check(lib().fdg_fill_uniform_device_tiled(d_leaf, B, L, ss, ls, lts, seed, sample_offset, stream))
+
+
+def vegas_sample_device(d_grid: int, n_dim: int, n_grid: int, col, seed: int, sample_offset: int, d_x: int, xs: int, xc: int, d_jac: int,
+                        d_cell: int, B: int, stream: int = 0):
+    """fdg_vegas_sample_device: ``x[b * xs + col[d] * xc]`` drawn through the map ``d_grid`` (device, ``[n_dim, n_grid + 1]`` edges),
+    ``jac[b]`` its weight, ``cell[d * B + b]`` when ``d_cell`` is not 0.  ``col``: host sequence of ``n_dim`` column numbers or None."""
+    c = None
+    if col is not None:
+        c = np.ascontiguousarray(col, dtype=np.uint32)
+        if c.shape != (n_dim,):
+            raise ValueError("col must name one column per variable")
+    check(lib().fdg_vegas_sample_device(d_grid or None, n_dim, n_grid, None if c is None else c.ctypes.data, seed, sample_offset,
+                                        d_x or None, xs, xc, d_jac or None, d_cell or None, B, stream))
+
+
+def vegas_refine(grid: np.ndarray, hist: np.ndarray, alpha: float = 0.5) -> np.ndarray:
+    """fdg_vegas_refine: moves the edges ``grid [n_dim, n_grid + 1]`` (float64, C-contiguous, in place) towards where the training
+    histogram ``hist [n_dim, n_grid]`` is large; returns ``grid``."""
+    if not (isinstance(grid, np.ndarray) and grid.dtype == np.float64 and grid.ndim == 2 and grid.flags.c_contiguous and grid.shape[1] >= 2):
+        raise ValueError("grid must be a C-contiguous float64 [n_dim, n_grid + 1] array")
+    h = np.ascontiguousarray(hist, dtype=np.float64)
+    if h.shape != (grid.shape[0], grid.shape[1] - 1):
+        raise ValueError("hist must be [n_dim, n_grid]")
+    check(lib().fdg_vegas_refine(grid.ctypes.data, h.ctypes.data, grid.shape[0], grid.shape[1] - 1, float(alpha)))
+    return grid
 
 
 def set_default_option(name: str, value=None):

@@ -334,6 +334,35 @@ class GraphFunc:
                                                   w, acc.data_ptr(), acc2.data_ptr(), B, st)
         return acc, acc2
 
+    def accumulate_vegas(self, leaf, weight, hist, seed: int, sample_offset: int, n_dim: int, n_grid: int, coef=None, acc=None, acc2=None,
+                         n_sample: Optional[int] = None):
+        """The accumulate step of one VEGAS iteration: :meth:`accumulate_moments` with ``bins=None`` (``acc``, ``acc2``: the same bits)
+        plus the training histogram ``hist[d, c] += (weight[b] * sum_k coef[k] * root_k(b))**2`` for every variable ``d < n_dim``, ``c``
+        the cell of sample ``b`` in ``d`` recomputed from the Philox counter ``(sample_offset + b, d)`` and ``seed`` -- the arguments
+        ``capi.vegas_sample_device`` drew the samples with.  ``hist``: a contiguous float64 ``[n_dim, n_grid]`` CUDA tensor, added to
+        (zeros when None); ``coef``: host sequence of ``n_root`` factors or None (the plain sum of the roots).  Returns
+        ``(acc, acc2, hist)``.  Deterministic: no float atomics (fdg_accumulate_device_vegas)."""
+        import torch
+        B, _, _, weight, strides = self._binned_args(leaf, None, 1, weight, n_sample, bins_optional=True)
+        n_dim, n_grid = int(n_dim), int(n_grid)
+        if not (1 <= n_dim <= capi.FDG_VEGAS_DIM_MAX and 1 <= n_grid <= capi.FDG_VEGAS_GRID_MAX):
+            raise ValueError(f"n_dim must lie in [1, {capi.FDG_VEGAS_DIM_MAX}] and n_grid in [1, {capi.FDG_VEGAS_GRID_MAX}]")
+        w = 0 if weight is None else weight.data_ptr()
+        acc = self._bin_acc(acc, 1, leaf, "acc")
+        acc2 = self._bin_acc(acc2, 1, leaf, "acc2")
+        if hist is None:
+            hist = torch.zeros((n_dim, n_grid), dtype=torch.float64, device=leaf.device)
+        if (not _is_torch(hist) or not hist.is_cuda or hist.device != leaf.device or hist.dtype != torch.float64 or not hist.is_contiguous()
+                or tuple(hist.shape) != (n_dim, n_grid)):
+            raise ValueError(f"hist must be a contiguous float64 [{n_dim}, {n_grid}] tensor on the leaves' device")
+        if len({acc.data_ptr(), acc2.data_ptr(), hist.data_ptr()}) != 3:
+            raise ValueError("acc, acc2 and hist must be different tensors")
+        st = torch.cuda.current_stream(leaf.device).cuda_stream
+        with torch.cuda.device(leaf.device):
+            self.handle.accumulate_device_vegas(leaf.data_ptr(), *strides, w, coef, int(seed), int(sample_offset), n_dim, n_grid,
+                                                acc.data_ptr(), acc2.data_ptr(), hist.data_ptr(), B, st)
+        return acc, acc2, hist
+
     def _binned_args(self, leaf, bins, n_bin, weight, n_sample, bins_optional=False):
         """The checks of :meth:`accumulate_binned` / :meth:`accumulate_moments`: (n_sample, n_bin, bins, weight, leaf strides), bins and
         weight contiguous (the caller holds them until the launch is queued)."""

@@ -21,10 +21,17 @@
 // with the binned call's bits.  A workgroup keeps both histograms (2 x n_bin x RS doubles) and scans t and t * t together; when even one
 // root does not fit twice (n_bin > 8192), every root slice gets two workgroups, one per moment, and the second reads the scratch columns again.
 // The slab is then [segment][moment][bin][root], and the reduce adds both moments in segment order.
+//
+// VEGAS importance sampling (fdg_vegas_sample_device, fdg_accumulate_device_vegas, fdg_mc_accumulate_device_vegas, fdg_vegas_refine):
+// the sampler draws through a piecewise-linear map per variable; the accumulate calls are the second-moment calls without a bin vector
+// plus one more pass per chunk over the same roots (fdg_vegas_partials below) that sums (w sum_k c_k root_k)^2 into a histogram per
+// variable and map cell, the cell recomputed from the sample's Philox counter; the refinement of the map is host code at the end.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <mutex>
+#include <vector>
 
 #define FDG_RUNTIME_TU 1
 #include "fdg_internal.h"
@@ -41,6 +48,35 @@ constexpr uint32_t kKeyInvalid = 0xFFFFFFC0u;             // (bin << 6 | lane) o
 __device__ inline void bin_barrier() {
   // LDS only: the pending global loads of the next round stay in flight across the barrier
   __asm__ volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
+// The wave-level pieces of the passes below.  key = (bin << 6 | lane), kKeyInvalid | lane for a lane that adds nothing; valid = the ballot of
+// key < kKeyInvalid (not zero).  Sorts the 64 keys ascending over the lanes -- a bitonic network; the keys are unique, the lane is part of
+// them -- unless every lane is valid and in one bin, and returns the lane this lane's key came from.
+__device__ inline uint32_t wave_sort_keys(uint32_t &key, uint32_t lane, uint64_t valid) {
+  const uint32_t key0 = __shfl(key, 0);
+  if (valid == ~0ull && __ballot((key >> 6) == (key0 >> 6)) == ~0ull) return lane;
+#pragma unroll
+  for (uint32_t kb = 2; kb <= 64; kb <<= 1)
+#pragma unroll
+    for (uint32_t jb = kb >> 1; jb > 0; jb >>= 1) {
+      const uint32_t other = __shfl_xor(key, (int)jb);
+      const bool keep_min = ((lane & kb) == 0) == ((lane & jb) == 0);
+      key = keep_min ? min(key, other) : max(key, other);
+    }
+  return key & 63u;
+}
+
+// The runs of equal bins among the sorted keys: j = this lane's bin, head = it is the first lane of a run of valid keys, end = the last
+// lane of its run (the lane itself where the key is invalid).
+__device__ inline void wave_runs(uint32_t key, uint32_t lane, uint32_t &j, bool &head, uint32_t &end) {
+  j = key >> 6;
+  const bool ok = key < kKeyInvalid;
+  const uint32_t j_prev = __shfl_up(j, 1);
+  const uint32_t j_next = __shfl_down(j, 1);
+  head = ok && (lane == 0 || j_prev != j);
+  const uint64_t tails = __ballot(!ok || lane == 63 || j_next != j);
+  end = ok ? (uint32_t)__builtin_ctzll(tails & (~0ull << lane)) : lane;
 }
 
 // What a workgroup of the pass accumulates: the first moment (the binned call), both moments in one LDS, or one moment per root slice
@@ -97,27 +133,9 @@ fdg_binned_partials(const double *__restrict__ root, long ld, long n, const int3
     bool head = false;
     uint32_t j = 0;
     if (valid) {
-      const uint32_t key0 = __shfl(key, 0);
-      uint32_t src = lane;
-      if (!(valid == ~0ull && __ballot((key >> 6) == (key0 >> 6)) == ~0ull)) {
-        // bitonic sort of the 64 keys (unique: the lane is part of the key), ascending over the lanes
-#pragma unroll
-        for (uint32_t kb = 2; kb <= 64; kb <<= 1)
-#pragma unroll
-          for (uint32_t jb = kb >> 1; jb > 0; jb >>= 1) {
-            const uint32_t other = __shfl_xor(key, (int)jb);
-            const bool keep_min = ((lane & kb) == 0) == ((lane & jb) == 0);
-            key = keep_min ? min(key, other) : max(key, other);
-          }
-        src = key & 63u;
-      }
-      j = key >> 6;
-      const bool ok = key < kKeyInvalid;
-      const uint32_t j_prev = __shfl_up(j, 1);
-      const uint32_t j_next = __shfl_down(j, 1);
-      head = ok && (lane == 0 || j_prev != j);
-      const uint64_t tails = __ballot(!ok || lane == 63 || j_next != j);
-      const uint32_t end = ok ? (uint32_t)__builtin_ctzll(tails & (~0ull << lane)) : lane;   // last lane of this lane's run
+      const uint32_t src = wave_sort_keys(key, lane, valid);
+      uint32_t end;
+      wave_runs(key, lane, j, head, end);
 #pragma unroll
       for (int kk = 0; kk < RS; ++kk) s[kk] = __shfl(v[kk], (int)src);
       // the square of the source lane's term (t * t, rounded, no fma: -ffp-contract=off); 0 where the term was selected away
@@ -189,6 +207,106 @@ fdg_binned_reduce(const double *__restrict__ partial, uint32_t n_seg, long seg_s
   }
 }
 
+// ---- VEGAS importance sampling: the map, the sampler, the training pass (include/fdg.h: fdg_vegas_sample_device, fdg_accumulate_device_vegas) ----
+// The cell of variable d that sample `sample` (a global index: the Philox counter) falls in, and y = u * G; every operation one rounded fp64
+// operation.  The sampler and the training pass both call this: the pass reads no cell array.
+__device__ __forceinline__ uint32_t vegas_cell(uint64_t sample, uint32_t d, uint64_t seed, uint32_t G, double &y) {
+  const double u = fdg_philox_u53(sample, d, seed);
+  y = u * (double)G;
+  return min((uint32_t)(int)y, G - 1u);
+}
+
+struct VegasCols { uint32_t c[FDG_VEGAS_DIM_MAX]; };   // the column of x each variable is written to (a kernel argument, by value)
+
+// One lane per sample, the variables in order (jac is a left fold over them).
+__global__ void __launch_bounds__(256)
+fdg_vegas_sample(const double *__restrict__ grid, uint32_t D, uint32_t G, VegasCols col, uint64_t seed, uint64_t off, double *__restrict__ x,
+                 long xs, long xc, double *__restrict__ jac, int32_t *__restrict__ cell, long n) {
+  for (long b = blockIdx.x * 256L + threadIdx.x; b < n; b += (long)gridDim.x * 256L) {
+    double jb = 0.0;
+    for (uint32_t d = 0; d < D; ++d) {
+      double y;
+      const uint32_t c = vegas_cell(off + (uint64_t)b, d, seed, G, y);
+      const double *e = grid + (size_t)d * (G + 1u) + c;
+      const double lo = e[0], wd = e[1] - lo, fr = y - (double)c;
+      x[b * xs + (long)col.c[d] * xc] = lo + fr * wd;
+      const double f = (double)G * wd;
+      jb = d ? jb * f : f;
+      if (cell) cell[(size_t)d * (size_t)n + (size_t)b] = (int32_t)c;
+    }
+    jac[b] = jb;
+  }
+}
+
+// The training pass over a chunk's roots (root k of sample b at root[k * ld + b], b < n): hist[d][c] += v(b) for every variable d, c = the
+// cell of sample off + b in d, v = (w (c_0 r_0 + c_1 r_1 + ...))^2 over the n_live roots kidx[] that exist (coef null: plain sum).
+// One workgroup per (segment of the chunk's tiles, slice of DS variables), the slice's histograms (DS x G doubles) in LDS.
+//  * In a round the four waves form v for one tile each (wave w the tile 4 r + w, as the binned pass deals them) and leave it in LDS.
+//  * Every wave then walks the round's tiles in tile order for ITS variables of the slice (dd = wave, wave + 4, ...): it recomputes
+//    the cell from the counter, sorts the lanes by (cell, lane), sums v over every run of equal cells (the binned pass's segmented scan,
+//    one value instead of RS) and the run heads add into the histogram.  A histogram word is only ever touched by one wave, in
+//    program order: per (variable, cell) the tiles are added in tile order, and there is nothing to wait for but the v exchange
+//    (two buffers, one barrier per round).
+//  * Chunks and segments chain as in the binned pass: partial [segment][variable][cell], summed in segment order by fdg_binned_reduce.
+// Lanes past n are selected away (key invalid, v = 0 never enters a sum); no float atomics.
+__global__ void __launch_bounds__(256)
+fdg_vegas_partials(const double *__restrict__ root, long ld, long n, const double *__restrict__ weight, const uint32_t *__restrict__ kidx,
+                   const double *__restrict__ coef, uint32_t n_live, uint64_t seed, uint64_t off, uint32_t D, uint32_t G, uint32_t DS,
+                   uint32_t n_slice, long seg_tiles, double *__restrict__ partial, int first) {
+  extern __shared__ double hist[];                        // [DS][G], then v of the round's tiles [2][kBinWaves][64]
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t slice = blockIdx.x % n_slice, seg = blockIdx.x / n_slice;
+  const uint32_t d0 = slice * DS, dn = min(DS, D - d0);
+  double *vbuf = hist + (size_t)DS * G;
+  double *slab = partial + ((size_t)seg * D + d0) * G;
+  for (uint32_t i = threadIdx.x; i < dn * G; i += 256) hist[i] = first ? 0.0 : slab[i];
+  __syncthreads();
+  const long ntile = (n + 63) / 64, t0 = (long)seg * seg_tiles, t1 = min(t0 + seg_tiles, ntile);
+  const long rounds = t1 > t0 ? (t1 - t0 + kBinWaves - 1) / kBinWaves : 0;
+  for (long r = 0; r < rounds; ++r) {
+    {
+      const long t = t0 + r * (long)kBinWaves + wave, b = t * 64 + lane;
+      const bool in = t < t1 && b < n;
+      const size_t bb = (size_t)min(b, n - 1);            // clamped into the chunk; what it loads is used only where `in`
+      double sum = 0.0;
+      for (uint32_t i = 0; i < n_live; ++i) {
+        const double rk = root[(size_t)kidx[i] * (size_t)ld + bb];
+        const double term = coef ? coef[i] * rk : rk;
+        sum = i ? sum + term : term;
+      }
+      const double tw = weight ? weight[bb] * sum : sum;
+      vbuf[(r & 1) * (kBinWaves * 64) + wave * 64 + lane] = in ? tw * tw : 0.0;
+    }
+    __syncthreads();
+    for (uint32_t tt = 0; tt < kBinWaves; ++tt) {
+      const long t = t0 + r * (long)kBinWaves + tt, b = t * 64 + lane;
+      if (t >= t1) break;
+      const double v = vbuf[(r & 1) * (kBinWaves * 64) + tt * 64 + lane];
+      for (uint32_t dd = wave; dd < dn; dd += kBinWaves) {
+        double y;
+        const uint32_t c = vegas_cell(off + (uint64_t)b, d0 + dd, seed, G, y);
+        uint32_t key = b < n ? (c << 6) | lane : kKeyInvalid | lane;
+        const uint64_t valid = __ballot(key < kKeyInvalid);
+        if (!valid) continue;
+        const uint32_t src = wave_sort_keys(key, lane, valid);
+        uint32_t j, end;
+        bool head;
+        wave_runs(key, lane, j, head, end);
+        double s = __shfl(v, (int)src);
+        for (uint32_t dist = 1; dist < 64; dist <<= 1) {   // segmented suffix scan, as in fdg_binned_partials
+          const bool take = lane + dist <= end;
+          if (!__ballot(take)) break;
+          const double up = __shfl_down(s, dist);
+          if (take) s = s + up;
+        }
+        if (head) hist[dd * G + j] = hist[dd * G + j] + s;
+      }
+    }
+  }
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < dn * G; i += 256) slab[i] = hist[i];
+}
+
 // How one call is cut: chunks of Bc samples through the root scratch, RS roots per slice, n_seg segments per chunk.  mode: what the
 // pass keeps (BinMode); n_slice counts the root slices of one moment.
 struct BinnedPlan {
@@ -234,6 +352,37 @@ BinnedPlan binned_plan(const fdg_graph *g, int64_t B, uint32_t R, uint32_t n_bin
     p.n_slice = (R + rs - 1) / rs;
   }
   return p;
+}
+
+// The training pass of one call: what the entry point was given, and how the pass is cut.  Variables per slice by the binned plan's LDS
+// budget (whole histograms of G cells), spread evenly over the slices; segments by the binned plan's three bounds with the histogram
+// [variable][cell] in the place of [bin][root].  A function of (n_sample, n_dim, n_grid, n_root, FDG_ROOT_SCRATCH_MB) only.
+struct VegasRun {
+  const double *coef = nullptr;      // host, [R] or null
+  uint64_t seed = 0, offset = 0;
+  uint32_t D = 0, G = 0;
+  double *d_hist = nullptr;
+};
+struct VegasPlan {
+  uint32_t ds = 1, n_slice = 1, n_seg = 1;
+  size_t lds = 0, slab_alloc = 0, list_bytes = 0;
+};
+
+VegasPlan vegas_plan(const BinnedPlan &p, const VegasRun &v, uint32_t R) {
+  VegasPlan q;
+  const uint32_t fit = (uint32_t)std::max<size_t>(1, kBinLdsBudget / ((size_t)v.G * 8u));
+  q.n_slice = (v.D + fit - 1) / fit;
+  q.ds = (v.D + q.n_slice - 1) / q.n_slice;
+  q.n_slice = (v.D + q.ds - 1) / q.ds;
+  q.lds = ((size_t)q.ds * v.G + 2u * kBinWaves * 64u) * 8u;
+  const size_t hist_bytes = (size_t)v.D * v.G * 8u;
+  const long by_size = std::max<long>(1, p.Bc / 64 / 16);
+  const long by_slab = std::max<long>(1, (long)(kBinSlabBytes / hist_bytes));
+  const long by_blocks = std::max<long>(1, 2048 / (long)q.n_slice);
+  q.n_seg = (uint32_t)std::min(std::min(by_size, by_slab), by_blocks);
+  q.slab_alloc = (std::max(hist_bytes, std::min(kBinSlabBytes, (size_t)by_size * hist_bytes)) + 4095) & ~(size_t)4095;
+  q.list_bytes = ((size_t)R * 12u + 4095) & ~(size_t)4095;      // coef[R] doubles, then kidx[R]
+  return q;
 }
 
 template <int RS, int MODE>
@@ -293,26 +442,75 @@ int check_moments(const fdg_graph *g, const int32_t *d_bin, uint32_t n_bin, cons
   return FDG_OK;
 }
 
+// ... and the VEGAS calls': the map's limits (every call), then the three output arrays of the accumulate calls.
+int check_vegas_map(uint32_t n_dim, uint32_t n_grid) {
+  if (n_dim == 0 || n_grid == 0) { set_error("n_dim == 0 or n_grid == 0"); return FDG_E_INVALID; }
+  if (n_dim > FDG_VEGAS_DIM_MAX) { set_error("n_dim > FDG_VEGAS_DIM_MAX"); return FDG_E_UNSUPPORTED; }
+  if (n_grid > FDG_VEGAS_GRID_MAX) { set_error("n_grid > FDG_VEGAS_GRID_MAX"); return FDG_E_UNSUPPORTED; }
+  return FDG_OK;
+}
+
+int check_vegas(const fdg_graph *g, uint32_t n_dim, uint32_t n_grid, const double *d_acc, const double *d_acc2, const double *d_hist, int64_t B) {
+  int rc = check_moments(g, nullptr, 1, d_acc, d_acc2, B);
+  if (rc) return rc;
+  if (!d_hist) { set_error("null device buffer"); return FDG_E_INVALID; }
+  if (d_hist == d_acc || d_hist == d_acc2) { set_error("d_hist is the same buffer as d_acc or d_acc2"); return FDG_E_INVALID; }
+  return check_vegas_map(n_dim, n_grid);
+}
+
 // The chunk loop shared by the entry points (caller holds g->mu, stream bound): eval(c0, n, roots, ld) writes the roots of samples
 // c0 .. c0 + n - 1 column-major into roots (root k of sample c0 + b at roots[k * ld + b]).  d_acc2 != null: the second moment too.
+// vg != null (the VEGAS calls): after a chunk's moments pass the training pass runs over the same roots, its partials behind the moments' slab.
 template <class Eval>
 int run_binned(fdg_graph *g, const int32_t *d_bin, int32_t bin_base, uint32_t n_bin, const double *d_weight, double *d_acc, double *d_acc2,
-               int64_t B, hipStream_t st, Eval eval) {
+               int64_t B, hipStream_t st, Eval eval, const VegasRun *vg = nullptr) {
   const uint32_t R = g->prog.R;
   const BinnedPlan p = binned_plan(g, B, R, n_bin, d_acc2 != nullptr);
   const size_t root_bytes = ((size_t)p.Bc * R * sizeof(double) + 4095) & ~(size_t)4095;
-  int rc = ensure_root_scratch(g, root_bytes + p.slab_alloc);
+  const size_t slab_bytes = (p.slab_alloc + 4095) & ~(size_t)4095;
+  VegasPlan q;
+  if (vg) q = vegas_plan(p, *vg, R);
+  int rc = ensure_root_scratch(g, vg ? root_bytes + slab_bytes + q.slab_alloc + q.list_bytes : root_bytes + p.slab_alloc);
   if (rc) return rc;
   double *roots = (double *)g->d_ws2, *partial = (double *)((char *)g->d_ws2 + root_bytes);
   const uint8_t *live = nullptr;
   rc = root_live_mask(g, &live);
   if (rc) return rc;
+  double *vpartial = nullptr, *d_coef = nullptr;
+  uint32_t *d_kidx = nullptr, n_live = 0;
+  if (vg) {
+    static std::once_flag lds_once;
+    std::call_once(lds_once, [] {
+      (void)hipFuncSetAttribute((const void *)fdg_vegas_partials, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kBinLdsBudget + 2u * kBinWaves * 64u * 8u));
+      (void)hipGetLastError();
+    });
+    // the roots that exist, ascending, and their factors: one small upload per call (pageable memory: staged before the call returns)
+    vpartial = (double *)((char *)partial + slab_bytes);
+    d_coef = (double *)((char *)vpartial + q.slab_alloc);
+    d_kidx = (uint32_t *)(d_coef + R);
+    std::vector<double> hc;
+    std::vector<uint32_t> hk;
+    for (uint32_t k = 0; k < R; ++k)
+      if (g->prog.root_slot[k] != FDG_NO_ROOT) { hk.push_back(k); hc.push_back(vg->coef ? vg->coef[k] : 1.0); }
+    n_live = (uint32_t)hk.size();
+    if (n_live) {
+      HIP_TRY(hipMemcpyAsync(d_coef, hc.data(), n_live * sizeof(double), hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(d_kidx, hk.data(), n_live * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    }
+  }
   for (long c0 = 0; c0 < (long)B; c0 += p.Bc) {
     const long n = std::min<long>(p.Bc, (long)B - c0);
     rc = eval(c0, n, roots, p.Bc);
     if (rc) return rc;
     rc = binned_pass(p, roots, n, d_bin ? d_bin + c0 : nullptr, bin_base, n_bin, d_weight ? d_weight + c0 : nullptr, R, partial, c0 == 0, st);
     if (rc) return rc;
+    if (vg) {
+      const long ntile = (n + 63) / 64, seg_tiles = (ntile + q.n_seg - 1) / q.n_seg;
+      hipLaunchKernelGGL(fdg_vegas_partials, dim3(q.n_seg * q.n_slice), dim3(256), q.lds, st, roots, (long)p.Bc, n,
+                         d_weight ? d_weight + c0 : nullptr, d_kidx, vg->coef ? d_coef : nullptr, n_live, vg->seed, vg->offset + (uint64_t)c0,
+                         vg->D, vg->G, q.ds, q.n_slice, seg_tiles, vpartial, c0 == 0);
+      HIP_TRY(hipGetLastError());
+    }
   }
   const long ncol = (long)n_bin * R;
   uint32_t C = 1;
@@ -321,12 +519,19 @@ int run_binned(fdg_graph *g, const int32_t *d_bin, int32_t bin_base, uint32_t n_
   hipLaunchKernelGGL(fdg_binned_reduce, dim3((unsigned)((ncol + C - 1) / C), n_mom), dim3(256), 0, st, partial, p.n_seg, ncol * n_mom, ncol,
                      R, C, d_acc, d_acc2, live);
   HIP_TRY(hipGetLastError());
+  if (vg) {                                               // hist[d][c] += the segments' partials, in segment order
+    const long hcol = (long)vg->D * vg->G;
+    hipLaunchKernelGGL(fdg_binned_reduce, dim3((unsigned)((hcol + 63) / 64), 1), dim3(256), 0, st, vpartial, q.n_seg, hcol, hcol, 1u, 64u,
+                       vg->d_hist, (double *)nullptr, (const uint8_t *)nullptr);
+    HIP_TRY(hipGetLastError());
+  }
   return FDG_OK;
 }
 
 // fdg_accumulate_device_binned / _moments after their own checks
 int accumulate_leaf(fdg_graph *g, const double *d_leaf, int64_t ss, int64_t ls, int64_t lts, const int32_t *d_bin, int32_t bin_base,
-                    uint32_t n_bin, const double *d_weight, double *d_acc, double *d_acc2, int64_t B, void *stream) {
+                    uint32_t n_bin, const double *d_weight, double *d_acc, double *d_acc2, int64_t B, void *stream,
+                    const VegasRun *vg = nullptr) {
   if (g->prog.L && !d_leaf) { set_error("null device buffer"); return FDG_E_INVALID; }
   if (B == 0 || g->prog.R == 0) return FDG_OK;
   std::lock_guard<std::mutex> lk(g->mu);
@@ -342,13 +547,13 @@ int accumulate_leaf(fdg_graph *g, const double *d_leaf, int64_t ss, int64_t ls, 
   return run_binned(g, d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, st, [&](long c0, long n, double *roots, long ld) {
     const double *lf = lts ? d_leaf + (size_t)(c0 / 64) * (size_t)lts : d_leaf + c0 * ss;
     return fdg_run_locked(g, 0, lf, ss, ls, roots, 1, ld, nullptr, nullptr, n, st, lts, 0);
-  });
+  }, vg);
 }
 
 // fdg_mc_accumulate_device_binned / _moments after their own checks
 int accumulate_mc(fdg_graph *g, const double *d_K, int64_t ks, int64_t kc, const double *d_T, int64_t ts, int64_t tc, double kF, double beta,
                   double lambda, const int32_t *d_bin, int32_t bin_base, uint32_t n_bin, const double *d_weight, double *d_acc, double *d_acc2,
-                  int64_t B, void *stream) {
+                  int64_t B, void *stream, const VegasRun *vg = nullptr) {
   if (!d_K || !d_T) { set_error("null device buffer"); return FDG_E_INVALID; }
   if (B == 0 || g->prog.R == 0) return FDG_OK;
   std::lock_guard<std::mutex> lk(g->mu);
@@ -361,7 +566,7 @@ int accumulate_mc(fdg_graph *g, const double *d_K, int64_t ks, int64_t kc, const
   const hipStream_t st = (hipStream_t)stream;
   return run_binned(g, d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, st, [&](long c0, long n, double *roots, long ld) {
     return fdg_mc_run_locked(g, 0, d_K + c0 * ks, ks, kc, d_T + c0 * ts, ts, tc, kF, beta, lambda, roots, 1, ld, nullptr, nullptr, n, st);
-  });
+  }, vg);
 }
 
 }  // namespace
@@ -397,6 +602,90 @@ int fdg_mc_accumulate_device_moments(fdg_graph *g, const double *d_K, int64_t ks
   const int rc = check_moments(g, d_bin, n_bin, d_acc, d_acc2, B);
   if (rc) return rc;
   return accumulate_mc(g, d_K, ks, kc, d_T, ts, tc, kF, beta, lambda, d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, stream);
+}
+
+int fdg_accumulate_device_vegas(fdg_graph *g, const double *d_leaf, int64_t ss, int64_t ls, int64_t lts, const double *d_weight,
+                                const double *coef, uint64_t seed, uint64_t sample_offset, uint32_t n_dim, uint32_t n_grid, double *d_acc,
+                                double *d_acc2, double *d_hist, int64_t B, void *stream) {
+  const int rc = check_vegas(g, n_dim, n_grid, d_acc, d_acc2, d_hist, B);
+  if (rc) return rc;
+  VegasRun vg;
+  vg.coef = coef; vg.seed = seed; vg.offset = sample_offset; vg.D = n_dim; vg.G = n_grid; vg.d_hist = d_hist;
+  return accumulate_leaf(g, d_leaf, ss, ls, lts, nullptr, 0, 1, d_weight, d_acc, d_acc2, B, stream, &vg);
+}
+
+int fdg_mc_accumulate_device_vegas(fdg_graph *g, const double *d_K, int64_t ks, int64_t kc, const double *d_T, int64_t ts, int64_t tc,
+                                   double kF, double beta, double lambda, const double *d_weight, const double *coef, uint64_t seed,
+                                   uint64_t sample_offset, uint32_t n_dim, uint32_t n_grid, double *d_acc, double *d_acc2, double *d_hist,
+                                   int64_t B, void *stream) {
+  const int rc = check_vegas(g, n_dim, n_grid, d_acc, d_acc2, d_hist, B);
+  if (rc) return rc;
+  VegasRun vg;
+  vg.coef = coef; vg.seed = seed; vg.offset = sample_offset; vg.D = n_dim; vg.G = n_grid; vg.d_hist = d_hist;
+  return accumulate_mc(g, d_K, ks, kc, d_T, ts, tc, kF, beta, lambda, nullptr, 0, 1, d_weight, d_acc, d_acc2, B, stream, &vg);
+}
+
+int fdg_vegas_sample_device(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, uint64_t seed, uint64_t sample_offset,
+                            double *d_x, int64_t x_sample_stride, int64_t x_col_stride, double *d_jac, int32_t *d_cell, int64_t B,
+                            void *stream) {
+  if (B < 0) { set_error("n_sample < 0"); return FDG_E_INVALID; }
+  if (!d_grid || !d_x || !d_jac) { set_error("null device buffer"); return FDG_E_INVALID; }
+  const int rc = check_vegas_map(n_dim, n_grid);
+  if (rc) return rc;
+  if (B == 0) return FDG_OK;
+  VegasCols cols;
+  for (uint32_t d = 0; d < FDG_VEGAS_DIM_MAX; ++d) cols.c[d] = d < n_dim ? (col ? col[d] : d) : 0u;
+  const long grid = std::min<long>(((long)B + 255) / 256, 256L * 16);
+  hipLaunchKernelGGL(fdg_vegas_sample, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, d_grid, n_dim, n_grid, cols, seed,
+                     sample_offset, d_x, (long)x_sample_stride, (long)x_col_stride, d_jac, d_cell, (long)B);
+  HIP_TRY(hipGetLastError());
+  return FDG_OK;
+}
+
+// Lepage's refinement of the map from the training histogram; host only, fp64, in the order include/fdg.h states.
+int fdg_vegas_refine(double *grid, const double *hist, uint32_t n_dim, uint32_t n_grid, double alpha) {
+  if (!grid || !hist) { set_error("null argument"); return FDG_E_INVALID; }
+  const int rc = check_vegas_map(n_dim, n_grid);
+  if (rc) return rc;
+  if (!(alpha >= 0.0 && alpha <= 2.0)) { set_error("alpha outside [0, 2]"); return FDG_E_INVALID; }
+  const uint32_t G = n_grid;
+  for (size_t i = 0; i < (size_t)n_dim * G; ++i)
+    if (!(hist[i] >= 0.0) || !std::isfinite(hist[i])) { set_error("histogram entry negative or not finite"); return FDG_E_INVALID; }
+  if (alpha == 0.0 || G == 1) return FDG_OK;
+  std::vector<double> out(grid, grid + (size_t)n_dim * (G + 1)), sm(G), w(G);
+  for (uint32_t d = 0; d < n_dim; ++d) {
+    const double *h = hist + (size_t)d * G, *e = grid + (size_t)d * (G + 1);
+    double *ne = out.data() + (size_t)d * (G + 1);
+    double total = 0.0;
+    for (uint32_t i = 0; i < G; ++i) total += h[i];
+    if (!(total > 0.0)) continue;
+    sm[0] = (7.0 * h[0] + h[1]) / 8.0;
+    sm[G - 1] = (h[G - 2] + 7.0 * h[G - 1]) / 8.0;
+    for (uint32_t i = 1; i + 1 < G; ++i) sm[i] = (h[i - 1] + 6.0 * h[i] + h[i + 1]) / 8.0;
+    double ssum = 0.0;
+    for (uint32_t i = 0; i < G; ++i) ssum += sm[i];
+    if (!(ssum > 0.0) || !std::isfinite(ssum)) { set_error("histogram sum overflows"); return FDG_E_INVALID; }
+    double wsum = 0.0;
+    for (uint32_t i = 0; i < G; ++i) {
+      const double x = sm[i] / ssum;
+      w[i] = x <= 0.0 ? 0.0 : x >= 1.0 ? 1.0 : std::pow((1.0 - x) / (-std::log(x)), alpha);
+      wsum += w[i];
+    }
+    if (!(wsum > 0.0)) continue;
+    const double delta = wsum / (double)G;
+    uint32_t j = 0;
+    double below = 0.0, cum = w[0];                       // sum of w before cell j, and through it
+    for (uint32_t i = 1; i < G; ++i) {
+      const double target = (double)i * delta;
+      while (cum < target && j + 1 < G) { below = cum; cum += w[++j]; }
+      const double frac = w[j] > 0.0 ? std::min(1.0, std::max(0.0, (target - below) / w[j])) : 1.0;
+      ne[i] = e[j] + frac * (e[j + 1] - e[j]);
+    }
+    for (uint32_t i = 0; i < G; ++i)
+      if (!(ne[i] < ne[i + 1])) { set_error("refined edges are not strictly increasing"); return FDG_E_INTERNAL; }
+  }
+  std::copy(out.begin(), out.end(), grid);
+  return FDG_OK;
 }
 
 }  // extern "C"

@@ -221,6 +221,31 @@ struct fdg_graph {
     }                                                                                   \
   } while (0)
 
+// Philox4x32-10 (Salmon et al., SC'11), key = seed, counter = (sample, leaf)
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
+                                              uint32_t k0, uint32_t k1, uint32_t out[4]) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+    const uint32_t n1 = (uint32_t)p1;
+    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    const uint32_t n3 = (uint32_t)p0;
+    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+// U[0,1) of counter (sample, column) and key seed, 53 random bits: what fdg_fill_uniform_device writes, and what the VEGAS map is drawn through
+__device__ __forceinline__ double fdg_philox_u53(uint64_t sample, uint32_t column, uint64_t seed) {
+  uint32_t o[4];
+  philox4x32_10((uint32_t)sample, (uint32_t)(sample >> 32), column, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), o);
+  const uint64_t m = ((uint64_t)(o[0] >> 5) << 26) | (uint64_t)(o[1] >> 6);
+  return (double)m * 0x1.0p-53;
+}
+
 void parse_launch_cfg(fdg_graph *g);             // g->knobs -> g->cfg
 int ensure_device(fdg_graph *g);                 // binds the handle to the current gfx950 device
 int fdg_bind_stream_ws(fdg_graph *g, void *stream);   // makes the scratch set of `stream` the current one (caller holds g->mu)

@@ -400,23 +400,7 @@ fdg_repack_transpose(double *__restrict__ mat, long ss, long cs, double *__restr
   }
 }
 
-// Philox4x32-10 (Salmon et al., SC'11), key = seed, counter = (sample, leaf)
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                              uint32_t k0, uint32_t k1, uint32_t out[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
-    const uint32_t n1 = (uint32_t)p1;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-    const uint32_t n3 = (uint32_t)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
+// (philox4x32_10, fdg_philox_u53: fdg_internal.h -- the VEGAS sampler and its training pass draw the same numbers)
 __global__ void __launch_bounds__(256)
 fdg_fill_uniform(double *__restrict__ leaf, long B, uint32_t L, long ss, long ls, uint64_t seed,
                  uint64_t off, int leaf_fastest) {
@@ -425,10 +409,7 @@ fdg_fill_uniform(double *__restrict__ leaf, long B, uint32_t L, long ss, long ls
     long b, i;
     if (leaf_fastest) { b = e / L; i = e - b * L; } else { i = e / B; b = e - i * B; }
     const uint64_t s = off + (uint64_t)b;
-    uint32_t o[4];
-    philox4x32_10((uint32_t)s, (uint32_t)(s >> 32), (uint32_t)i, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), o);
-    const uint64_t m = ((uint64_t)(o[0] >> 5) << 26) | (uint64_t)(o[1] >> 6);  // 53 random bits
-    leaf[b * ss + i * ls] = (double)m * 0x1.0p-53;
+    leaf[b * ss + i * ls] = fdg_philox_u53(s, (uint32_t)i, seed);
   }
 }
 
@@ -440,10 +421,7 @@ fdg_fill_uniform_tiled(double *__restrict__ leaf, long B, uint32_t L, long ss, l
     const long l = e & 63, ti = e >> 6, t = ti / L, i = ti - t * L, b = 64 * t + l;
     if (b >= B) continue;
     const uint64_t s = off + (uint64_t)b;
-    uint32_t o[4];
-    philox4x32_10((uint32_t)s, (uint32_t)(s >> 32), (uint32_t)i, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), o);
-    const uint64_t m = ((uint64_t)(o[0] >> 5) << 26) | (uint64_t)(o[1] >> 6);
-    leaf[t * lts + l * ss + i * ls] = (double)m * 0x1.0p-53;
+    leaf[t * lts + l * ss + i * ls] = fdg_philox_u53(s, (uint32_t)i, seed);
   }
 }
 

@@ -263,6 +263,40 @@ function accumulate_device_moments!(f::GraphFunc, d_acc::Ptr{Float64}, d_acc2::P
         f.handle, d_leaf, leaf_strides[1], leaf_strides[2], tile_stride, d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, stream))
     return nothing
 end
+# ---- VEGAS importance sampling (include/fdg.h; no counterpart in the reference: the caller side of example/benchmark.jl:46-51) ---- #
+# The map is a (G + 1) x D Matrix{Float64} of cell edges (column d: the edges of variable d, strictly increasing); d_grid is its copy on
+# the device.  vegas_sample_device! draws B samples through it: variable d goes to column col[d] (1-based; default d) of the matrix at
+# d_x (strides as a B x C column-major matrix by default, what the one-kernel Monte-Carlo route reads in place), d_jac[b] is the weight
+# 1/pdf of sample b, d_cell (B x D Int32, optional) the cells.  Counter-based: sample_offset + b is the global sample number.
+function vegas_sample_device!(d_x::Ptr{Float64}, d_jac::Ptr{Float64}, d_grid::Ptr{Float64}, n_dim::Integer, n_grid::Integer, B::Integer;
+    col::Union{Nothing,AbstractVector{<:Integer}}=nothing, seed::Integer=0, sample_offset::Integer=0, x_strides=(1, B),
+    d_cell::Ptr{Int32}=Ptr{Int32}(C_NULL), stream::Ptr{Cvoid}=C_NULL)
+    c = col === nothing ? nothing : UInt32.(col .- 1)
+    _fdg_check(ccall((:fdg_vegas_sample_device, _libfdg), Cint,
+        (Ptr{Float64}, UInt32, UInt32, Ptr{UInt32}, UInt64, UInt64, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Int32}, Int64, Ptr{Cvoid}),
+        d_grid, n_dim, n_grid, c === nothing ? C_NULL : c, seed, sample_offset, d_x, x_strides[1], x_strides[2], d_jac, d_cell, B, stream))
+    return nothing
+end
+# The accumulate step of an iteration (fdg_accumulate_device_vegas): d_acc, d_acc2 (R each) as accumulate_device_moments! with d_bin = C_NULL
+# leaves them, and the training histogram d_hist (G x D, added to): d_hist[c, d] += (w[b] * sum_k coef[k] * root_k(b))^2, c the cell of
+# sample b in variable d recomputed from (seed, sample_offset + b, d).  coef: host vector of R factors, or nothing for the plain sum.
+function accumulate_device_vegas!(f::GraphFunc, d_acc::Ptr{Float64}, d_acc2::Ptr{Float64}, d_hist::Ptr{Float64}, d_leaf::Ptr{Float64},
+    d_weight::Ptr{Float64}, n_dim::Integer, n_grid::Integer, B::Integer; coef::Union{Nothing,Vector{Float64}}=nothing, seed::Integer=0,
+    sample_offset::Integer=0, leaf_strides=(1, B), tile_stride::Integer=0, stream::Ptr{Cvoid}=C_NULL)
+    _fdg_check(ccall((:fdg_accumulate_device_vegas, _libfdg), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, UInt64, UInt64, UInt32, UInt32, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Int64, Ptr{Cvoid}),
+        f.handle, d_leaf, leaf_strides[1], leaf_strides[2], tile_stride, d_weight, coef === nothing ? C_NULL : coef, seed, sample_offset,
+        n_dim, n_grid, d_acc, d_acc2, d_hist, B, stream))
+    return nothing
+end
+# Lepage's refinement of the map from the training histogram, both on the host (fdg_vegas_refine): grid is (G + 1) x D, hist G x D.
+function vegas_refine!(grid::Matrix{Float64}, hist::Matrix{Float64}; alpha::Float64=0.5)
+    size(hist) == (size(grid, 1) - 1, size(grid, 2)) || error("hist must be (G, D) for a (G + 1, D) grid")
+    _fdg_check(ccall((:fdg_vegas_refine, _libfdg), Cint, (Ptr{Float64}, Ptr{Float64}, UInt32, UInt32, Float64),
+        grid, hist, size(grid, 2), size(hist, 1), alpha))
+    return grid
+end
 # device memory for a batch, backed by physical chunks of `chunk_bytes` (0: one allocation): fdg_batch_alloc / fdg_batch_free
 function batch_alloc(bytes::Integer; chunk_bytes::Integer=0)
     p = Ref{Ptr{Cvoid}}(C_NULL)
@@ -311,7 +345,7 @@ function accumulate_device!(f::GraphFunc, d_acc::Ptr{Float64}, d_leaf::Ptr{Float
         f.handle, d_leaf, leaf_strides[1], leaf_strides[2], d_weight, d_acc, B, stream))
 end
 
-export compile_hip, GraphFunc, eval_device!, accumulate_device!, eval_device_tiled!, accumulate_device_tiled!, accumulate_device_binned!, mc_accumulate_device_binned!, accumulate_device_moments!, mc_accumulate_device_moments!, batch_alloc, batch_free, tile_major!, from_tile_major!
+export compile_hip, GraphFunc, eval_device!, accumulate_device!, eval_device_tiled!, accumulate_device_tiled!, accumulate_device_binned!, mc_accumulate_device_binned!, accumulate_device_moments!, mc_accumulate_device_moments!, vegas_sample_device!, accumulate_device_vegas!, mc_accumulate_device_vegas!, vegas_refine!, batch_alloc, batch_free, tile_major!, from_tile_major!
 
 # ---- multi-GPU: one Julia process per GPU, ONE reduction of the accumulated observable ------------ #
 # (include/fdg.h, "multi-GPU").  Rank 0 calls `comm_unique_id()` and ships the 128 bytes to the other
@@ -414,6 +448,18 @@ function mc_accumulate_device_moments!(f::GraphFunc, d_K::Ptr{Float64}, d_T::Ptr
          Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Cvoid}),
         f.handle, d_K, k_strides[1], k_strides[2], d_T, t_strides[1], t_strides[2], kF, beta, lambda, d_bin, bin_base, n_bin, d_weight, d_acc,
         d_acc2, B, stream))
+    return nothing
+end
+# the VEGAS accumulate step for the fused step (fdg_mc_accumulate_device_vegas): d_acc, d_acc2, d_hist and coef as in accumulate_device_vegas!
+function mc_accumulate_device_vegas!(f::GraphFunc, d_K::Ptr{Float64}, d_T::Ptr{Float64}, d_weight::Ptr{Float64}, d_acc::Ptr{Float64},
+    d_acc2::Ptr{Float64}, d_hist::Ptr{Float64}, n_dim::Integer, n_grid::Integer, B::Integer; kF::Float64, beta::Float64, lambda::Float64,
+    coef::Union{Nothing,Vector{Float64}}=nothing, seed::Integer=0, sample_offset::Integer=0, k_strides=(1, B), t_strides=(1, B),
+    stream::Ptr{Cvoid}=C_NULL)
+    _fdg_check(ccall((:fdg_mc_accumulate_device_vegas, _libfdg), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Int64, Float64, Float64, Float64, Ptr{Float64}, Ptr{Float64}, UInt64,
+         UInt64, UInt32, UInt32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Cvoid}),
+        f.handle, d_K, k_strides[1], k_strides[2], d_T, t_strides[1], t_strides[2], kF, beta, lambda, d_weight,
+        coef === nothing ? C_NULL : coef, seed, sample_offset, n_dim, n_grid, d_acc, d_acc2, d_hist, B, stream))
     return nothing
 end
 

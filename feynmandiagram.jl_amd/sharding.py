@@ -8,6 +8,11 @@ additive across ranks too: allocate ``acc`` and ``acc2`` as the two halves of on
 ``[2, n_bin, R]`` tensor (``m = torch.zeros(2, n_bin, R); acc, acc2 = m[0], m[1]``), and one
 ``reduce_observable`` call over its 2 * n_bin * R doubles covers both; ``mc_estimate`` then
 takes the reduced halves with N = the sum of the ranks' batch sizes.
+VEGAS iterations (``vegas.vegas_integrate``, fdg_accumulate_device_vegas) shard the same way: a rank
+passes the start of its ``shard_range`` as part of ``sample_offset`` to the sampler and to the
+accumulate call (the cells are recomputed from the Philox counter = the global sample index), and the
+training histogram ``d_hist`` (n_dim * n_grid doubles) is summed over the ranks with the same
+``reduce_observable`` / ``fdg_reduce_device`` call as ``acc``, so every rank refines the same map.
 The reference has no counterpart (single-threaded); downstream users do this
 reduce in MCIntegration.jl.
 

@@ -1,0 +1,154 @@
+"""VEGAS importance sampling for the device Monte-Carlo step (include/fdg.h: fdg_vegas_sample_device, fdg_mc_accumulate_device_vegas,
+fdg_vegas_refine): a separable piecewise-linear map per integration variable, refined between iterations from a histogram of
+``(f * jacobian)**2`` per variable and grid cell.  The reference's examples hand their integrand to MCIntegration, whose default solver
+this is (example/benchmark.jl:46-51); MCIntegration is not part of the reference checkout, so nothing here has a counterpart in it.
+
+An iteration is "draw ``n_sample`` points through a fixed map, evaluate, accumulate": the sampler writes component-major ``(K, T)``
+columns, which the one-kernel Monte-Carlo route reads in place, and the accumulate call leaves the estimate, its second moment and the
+training histogram on the device.  Only the histogram (``n_dim * n_grid`` doubles) and the two moments come to the host per iteration.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass, field
+from typing import Callable, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import capi
+from .compilers import mc_estimate
+
+
+def uniform_grid(lo, hi, n_grid: int) -> np.ndarray:
+    """The flat map: edges ``lo + (hi - lo) * i / G`` for ``i = 0 .. G`` per variable, the last edge exactly ``hi``; ``[n_dim, G + 1]``."""
+    lo = np.atleast_1d(np.asarray(lo, dtype=np.float64))
+    hi = np.atleast_1d(np.asarray(hi, dtype=np.float64))
+    G = int(n_grid)
+    if lo.shape != hi.shape or lo.ndim != 1 or not (1 <= lo.shape[0] <= capi.FDG_VEGAS_DIM_MAX):
+        raise ValueError(f"lo and hi must be vectors of 1 .. {capi.FDG_VEGAS_DIM_MAX} limits")
+    if not (1 <= G <= capi.FDG_VEGAS_GRID_MAX):
+        raise ValueError(f"n_grid must lie in [1, {capi.FDG_VEGAS_GRID_MAX}]")
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (lo < hi).all()):
+        raise ValueError("every variable needs finite limits lo < hi")
+    g = lo[:, None] + (hi - lo)[:, None] * np.arange(G + 1, dtype=np.float64)[None, :] / G
+    g[:, G] = hi
+    if not (np.diff(g, axis=1) > 0).all():
+        raise ValueError("n_grid cells do not resolve [lo, hi] in float64")
+    return np.ascontiguousarray(g)
+
+
+class VegasMap:
+    """A map on the host (``.grid``, float64 ``[n_dim, n_grid + 1]``) and its copy on ``device`` (``.d_grid``, what the sampler reads)."""
+
+    def __init__(self, grid: np.ndarray, device):
+        import torch
+        g = np.ascontiguousarray(grid, dtype=np.float64)
+        if g.ndim != 2 or not (1 <= g.shape[0] <= capi.FDG_VEGAS_DIM_MAX) or not (2 <= g.shape[1] <= capi.FDG_VEGAS_GRID_MAX + 1):
+            raise ValueError("grid must be [n_dim, n_grid + 1] within the map's limits")
+        if not (np.diff(g, axis=1) > 0).all():
+            raise ValueError("the edges of every variable must be strictly increasing")
+        self.grid = g.copy()
+        self.device = torch.device(device)
+        self.d_grid = torch.from_numpy(self.grid).to(self.device)
+
+    @property
+    def n_dim(self) -> int:
+        return self.grid.shape[0]
+
+    @property
+    def n_grid(self) -> int:
+        return self.grid.shape[1] - 1
+
+    def refine(self, hist, alpha: float = 0.5) -> "VegasMap":
+        """Moves the edges by the training histogram ``hist [n_dim, n_grid]`` (a CUDA tensor or a host array) through
+        ``fdg_vegas_refine`` and uploads them; a failed refinement leaves both copies as they were."""
+        h = hist.detach().cpu().numpy() if hasattr(hist, "detach") else np.asarray(hist, dtype=np.float64)
+        capi.vegas_refine(self.grid, h, alpha)
+        self.d_grid.copy_(self.d_grid.new_tensor(self.grid))
+        return self
+
+
+@dataclass
+class VegasResult:
+    mean: np.ndarray                 # [R] inverse-variance combination of the iterations kept
+    stderr: np.ndarray               # [R]
+    chi2_dof: np.ndarray             # [R] consistency of the iterations kept (nan with fewer than two)
+    iterations: List[Tuple[np.ndarray, np.ndarray]] = field(default_factory=list)   # (mean [R], stderr [R]) of every iteration
+    map: Optional[VegasMap] = None   # the map after the last refinement
+    histograms: List[np.ndarray] = field(default_factory=list)                       # the training histogram of every iteration
+
+
+def combine(iterations: Sequence[Tuple[np.ndarray, np.ndarray]]):
+    """Inverse-variance combination per root of ``(mean, stderr)`` pairs: ``(mean, stderr, chi2 / dof)``.  A root whose error is 0 in
+    some iteration (a constant, or a root that does not exist) is averaged plainly and reports chi2/dof = nan."""
+    m = np.array([np.ravel(a) for a, _ in iterations], dtype=np.float64)
+    e = np.array([np.ravel(b) for _, b in iterations], dtype=np.float64)
+    n = m.shape[0]
+    ok = (e > 0).all(axis=0)
+    wgt = np.where(ok, 1.0 / np.where(e > 0, e, 1.0) ** 2, 1.0)
+    mean = (wgt * m).sum(axis=0) / wgt.sum(axis=0)
+    err = np.where(ok, 1.0 / np.sqrt(wgt.sum(axis=0)), 0.0)
+    chi2 = np.where(ok, (wgt * (m - mean) ** 2).sum(axis=0) / max(n - 1, 1), np.nan) if n > 1 else np.full(m.shape[1], np.nan)
+    return mean, err, chi2
+
+
+def vegas_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: float = 1.0, lam: float = 0.0, *, n_iter: int = 10,
+                    n_sample: int = 100_000, n_grid: int = 64, alpha: float = 0.5, seed: int = 0, n_discard: int = 0, fixed=None,
+                    coef=None, device="cuda", vmap: Optional[VegasMap] = None, specialize_fused: bool = True, n_total: Optional[int] = None,
+                    shard_start: int = 0, reduce: Optional[Callable] = None) -> VegasResult:
+    """Integrates the roots of a graph over the box ``[lo, hi]`` of ``len(col)`` of its Monte-Carlo variables.
+
+    ``func_or_handle``: a ``GraphFunc`` or ``capi.GraphHandle``; ``tables`` the ``fdg_leaf_tables`` struct of ``capi.make_leaf_tables``
+    (passed to ``specialize_fused`` unless ``specialize_fused=False``).  The variables live in one component-major array of
+    ``n_loop * dim + n_tau`` columns -- the momentum components, then the times -- and ``col[d]`` names the column variable ``d``
+    integrates; the other columns keep ``fixed`` (a vector of that many values, zeros by default: external momenta, ``T[1] = 0``).
+    Per iteration ``it``: sample with ``sample_offset = it * n_total + shard_start``, accumulate with weight = the map's jacobian,
+    ``mc_estimate``, refine with ``alpha``.  Iterations ``>= n_discard`` enter the inverse-variance combination.
+
+    Sharding: every rank passes its ``shard_range`` start and count as ``shard_start`` / ``n_sample``, the whole iteration as
+    ``n_total``, and ``reduce`` = a function that sums a CUDA tensor over the ranks in place (``sharding.reduce_observable``); it is
+    applied to the ``[2, 1, R]`` moments and to the histogram, so every rank refines the same map."""
+    import torch
+    handle = getattr(func_or_handle, "handle", func_or_handle)
+    device = torch.device(device)
+    n_col_k, n_tau = int(tables.n_loop) * int(tables.dim), int(tables.n_tau)
+    n_col, R = n_col_k + n_tau, handle.table.n_root
+    col = [int(c) for c in col]
+    if len(set(col)) != len(col) or not all(0 <= c < n_col for c in col):
+        raise ValueError(f"col must name distinct columns in [0, {n_col})")
+    if vmap is None:
+        vmap = VegasMap(uniform_grid(lo, hi, n_grid), device)
+    if vmap.n_dim != len(col):
+        raise ValueError("one column per variable of the map")
+    D, G = vmap.n_dim, vmap.n_grid
+    B = int(n_sample)
+    N = B if n_total is None else int(n_total)
+    if B < 1 or N < 2 or n_iter < 1 or not (0 <= n_discard < n_iter):
+        raise ValueError("need n_sample >= 1, n_total >= 2 and 0 <= n_discard < n_iter")
+    if specialize_fused:
+        handle.specialize_fused(tables)
+    fx = np.zeros(n_col) if fixed is None else np.asarray(fixed, dtype=np.float64)
+    if fx.shape != (n_col,):
+        raise ValueError(f"fixed must hold {n_col} column values")
+    with torch.cuda.device(device):
+        st = torch.cuda.current_stream(device).cuda_stream
+        x = torch.from_numpy(fx).to(device)[:, None].repeat(1, B).contiguous()          # [n_col, B]: sample stride 1
+        jac = torch.empty(B, dtype=torch.float64, device=device)
+        d_T = x.data_ptr() + 8 * n_col_k * B
+        out = VegasResult(np.zeros(R), np.zeros(R), np.full(R, np.nan), map=vmap)
+        for it in range(int(n_iter)):
+            off = it * N + int(shard_start)
+            capi.vegas_sample_device(vmap.d_grid.data_ptr(), D, G, col, seed, off, x.data_ptr(), 1, B, jac.data_ptr(), 0, B, st)
+            m = torch.zeros((2, 1, R), dtype=torch.float64, device=device)
+            hist = torch.zeros((D, G), dtype=torch.float64, device=device)
+            handle.mc_accumulate_device_vegas(x.data_ptr(), 1, B, d_T, 1, B, kF, beta, lam, jac.data_ptr(), coef, seed, off, D, G,
+                                              m[0].data_ptr(), m[1].data_ptr(), hist.data_ptr(), B, st)
+            if reduce is not None:
+                reduce(m)
+                reduce(hist)
+            mean, err = mc_estimate(m[0], m[1], N)
+            h = hist.cpu().numpy()
+            out.iterations.append((mean.cpu().numpy().reshape(R), err.cpu().numpy().reshape(R)))
+            out.histograms.append(h)
+            vmap.refine(h, alpha)
+    out.mean, out.stderr, out.chi2_dof = combine(out.iterations[int(n_discard):])
+    return out

@@ -575,6 +575,64 @@ int fdg_mc_accumulate_device_moments(fdg_graph *g, const double *d_K, int64_t k_
                                      const int32_t *d_bin, int32_t bin_base, uint32_t n_bin,
                                      const double *d_weight, double *d_acc, double *d_acc2, int64_t n_sample, void *stream);
 
+/* ---- VEGAS importance sampling (the front of the Monte-Carlo chain: where the samples and their weights come from) ----------------
+ * The reference's examples and tests hand their integrand to MCIntegration (example/benchmark.jl:46-51, test/ver4.jl:224-237), whose
+ * default solver is VEGAS: a separable piecewise-linear map per integration variable, refined between iterations from a histogram of
+ * (f * jacobian)^2 per variable and grid cell.  MCIntegration is not part of the reference checkout: no counterpart in the reference;
+ * the caller side of example/benchmark.jl:46-51.  One iteration = sample through a fixed map, evaluate, accumulate (estimate, error
+ * bar, training histogram), all on the device; fdg_vegas_refine then moves the map on the host (D * G numbers).
+ *
+ * The map is a caller-owned array grid[d * (G + 1) + i], 0 <= d < D = n_dim, 0 <= i <= G = n_grid: the G + 1 cell edges of variable d
+ * in physical units, strictly increasing.  1 <= D <= FDG_VEGAS_DIM_MAX, 1 <= G <= FDG_VEGAS_GRID_MAX (FDG_E_INVALID for 0,
+ * FDG_E_UNSUPPORTED above, in every call below, before any device work).
+ *
+ * fdg_vegas_sample_device: for sample b < n_sample and variable d, every operation one rounded fp64 operation,
+ *     u   = what fdg_fill_uniform_device writes for counter (sample_offset + b, d) and key seed (the same 53 bits)
+ *     y   = u * G,  c = min((int)y, G - 1),  fr = y - c,  wd = grid[d][c + 1] - grid[d][c]
+ *     x   = grid[d][c] + fr * wd        -> d_x[b * x_sample_stride + col[d] * x_col_stride]     (col NULL: col[d] = d)
+ *     jac = (..((G * wd_0) * (G * wd_1)) * ..)   -> d_jac[b]       (left fold over d: the weight 1/pdf of the sample)
+ *     c   -> d_cell[d * n_sample + b]   when d_cell is given (inspection; the accumulate calls do not need it)
+ * d_grid is the map in device memory; col a HOST array of n_dim column numbers.  Columns of d_x that col does not name are not touched
+ * (fixed external momenta, T[1] = 0 stay where they are); component-major x (sample stride 1) is what the one-kernel Monte-Carlo route
+ * reads in place.  The result is a function of the arguments only (counter-based: independent of launch shape and of how samples are
+ * sharded -- a rank passes the start of its range as part of sample_offset).  G = 1 on [0, 1] gives fdg_fill_uniform_device's bits and jac = 1. */
+#define FDG_VEGAS_DIM_MAX 64
+#define FDG_VEGAS_GRID_MAX 1024
+int fdg_vegas_sample_device(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, uint64_t seed,
+                            uint64_t sample_offset, double *d_x, int64_t x_sample_stride, int64_t x_col_stride, double *d_jac,
+                            int32_t *d_cell, int64_t n_sample, void *stream);
+/* The accumulate step of an iteration.  d_acc[k], d_acc2[k] (n_root doubles each, added to): bit for bit what
+ * fdg_accumulate_device_moments / fdg_mc_accumulate_device_moments leave for the same arguments with d_bin = NULL, n_bin = 1 (the same
+ * chunks, plan and pass): the estimate and its error bar.  d_hist[d * n_grid + c] (n_dim x n_grid doubles, added to) is the training
+ * histogram: for every sample b, with c the cell of variable d recomputed from the Philox counter (sample_offset + b, d) exactly as the
+ * sampler computes it (no cell array is read),
+ *     s = (c_k0 * r_k0) + (c_k1 * r_k1) + ...   over the roots that exist, ascending k, left fold; the factor only when coef != NULL
+ *     t = w_b * s   (d_weight NULL: t = s);   d_hist[d][c] += t * t
+ * coef is a HOST array of n_root factors: the combination of roots the map is trained on (NULL: their plain sum).  seed,
+ * sample_offset, n_dim, n_grid are the sampler's.  No float atomics: d_hist is bitwise reproducible for the same arguments on the same
+ * device, and the order of every sum depends on (n_sample, n_dim, n_grid, n_root, FDG_ROOT_SCRATCH_MB) only; lanes past n_sample are
+ * selected away, never multiplied by zero.  One more pass over the chunk's root scratch after the moments pass (csrc/fdg_binned.hip,
+ * DESIGN.md 8b).  FDG_E_INVALID: d_acc, d_acc2 or d_hist NULL, any two of them the same buffer, the moments calls' cases, n_dim or
+ * n_grid 0; FDG_E_UNSUPPORTED: the map's limits exceeded, a tile-major batch without FDG_SPEC_ISA; the Monte-Carlo form returns
+ * FDG_E_INVALID before fdg_graph_specialize_fused.  All before any device work. */
+int fdg_accumulate_device_vegas(fdg_graph *g, const double *d_leaf, int64_t leaf_sample_stride, int64_t leaf_leaf_stride,
+                                int64_t leaf_tile_stride, const double *d_weight, const double *coef, uint64_t seed,
+                                uint64_t sample_offset, uint32_t n_dim, uint32_t n_grid, double *d_acc, double *d_acc2, double *d_hist,
+                                int64_t n_sample, void *stream);
+int fdg_mc_accumulate_device_vegas(fdg_graph *g, const double *d_K, int64_t k_sample_stride, int64_t k_comp_stride, const double *d_T,
+                                   int64_t t_sample_stride, int64_t t_comp_stride, double kF, double beta, double lambda,
+                                   const double *d_weight, const double *coef, uint64_t seed, uint64_t sample_offset, uint32_t n_dim,
+                                   uint32_t n_grid, double *d_acc, double *d_acc2, double *d_hist, int64_t n_sample, void *stream);
+/* Lepage's refinement of the map from a training histogram (both HOST arrays; host only), per variable, in fp64, in this order:
+ *  1. h = hist[d].  sum(h) <= 0 or G == 1: the variable is left alone.  A negative or non-finite entry anywhere: FDG_E_INVALID.
+ *  2. smooth: s_0 = (7 h_0 + h_1) / 8, s_{G-1} = (h_{G-2} + 7 h_{G-1}) / 8, s_i = (h_{i-1} + 6 h_i + h_{i+1}) / 8; s /= sum(s).
+ *  3. damp: w_i = ((1 - s_i) / (-log s_i))^alpha for 0 < s_i < 1, 0 for s_i = 0, 1 for s_i = 1.
+ *  4. rebin: the new interior edge i (1 .. G - 1) lies where the running sum of w reaches i * sum(w) / G, linearly inside the old cell
+ *     it falls in; the two end edges are copied bit for bit.
+ *  5. the result is strictly increasing, or FDG_E_INTERNAL is returned.
+ * alpha in [0, 2] (0: the grid comes back unchanged; FDG_E_INVALID outside).  On any error the grid is untouched. */
+int fdg_vegas_refine(double *grid, const double *hist, uint32_t n_dim, uint32_t n_grid, double alpha);
+
 /* Device workspace control: the interpreter keeps per-sample overflow slots in
  * an HBM panel owned by the handle; it is sized on first use for the number of
  * resident waves.  This releases it (and any loaded module). */
