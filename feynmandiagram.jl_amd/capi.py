@@ -44,9 +44,12 @@ EXPORTS = [
     "fdg_accumulate_device_binned", "fdg_mc_accumulate_device_binned",
     "fdg_accumulate_device_moments", "fdg_mc_accumulate_device_moments",
     "fdg_vegas_sample_device", "fdg_accumulate_device_vegas", "fdg_mc_accumulate_device_vegas", "fdg_vegas_refine",
+    "fdg_vegas_sample_device_discrete", "fdg_accumulate_device_vegas_binned", "fdg_mc_accumulate_device_vegas_binned",
+    "fdg_vegas_refine_discrete",
 ]
 FDG_BIN_MAX = 16384     # fdg_accumulate_device_binned: largest n_bin
 FDG_VEGAS_DIM_MAX, FDG_VEGAS_GRID_MAX = 64, 1024     # the VEGAS map: most variables, most cells per variable
+FDG_VEGAS_EXT_MAX = 16  # the discrete variable's table: most columns per value
 COMM_ID_BYTES = 128
 
 
@@ -206,6 +209,13 @@ def lib():
     L.fdg_mc_accumulate_device_vegas.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, C.c_void_p, u64, u64,
                                                  u32, u32, dp, dp, dp, i64, vp]
     L.fdg_vegas_refine.argtypes = [C.c_void_p, C.c_void_p, u32, u32, C.c_double]
+    L.fdg_vegas_sample_device_discrete.argtypes = [dp, u32, u32, C.c_void_p, dp, u32, C.c_int32, dp, u32, C.c_void_p, u64, u64, dp, i64, i64,
+                                                   dp, dp, dp, i64, vp]
+    L.fdg_accumulate_device_vegas_binned.argtypes = [vp, dp, i64, i64, i64, dp, C.c_int32, u32, dp, C.c_void_p, u64, u64, u32, u32, dp, dp,
+                                                     dp, dp, i64, vp]
+    L.fdg_mc_accumulate_device_vegas_binned.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, C.c_int32,
+                                                        u32, dp, C.c_void_p, u64, u64, u32, u32, dp, dp, dp, dp, i64, vp]
+    L.fdg_vegas_refine_discrete.argtypes = [C.c_void_p, C.c_void_p, u32, C.c_double, C.c_double]
     L.fdg_comm_unique_id.argtypes = [C.c_void_p, C.c_size_t]
     L.fdg_comm_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(vp)]
     L.fdg_comm_destroy.argtypes = [vp]
@@ -450,6 +460,24 @@ class GraphHandle:
                                                    None if c is None else c.ctypes.data, seed, sample_offset, n_dim, n_grid,
                                                    d_acc or None, d_acc2 or None, d_hist or None, B, stream))
 
+    # the same with a discrete variable: binned moments (the bits of the moments calls with this d_bin), the training histogram over the
+    # samples whose bin is in range, and d_hist_bin[j] += (w[b] sum_k coef[k] root_k(b))^2 over the samples of bin j (0: not trained) (fdg.h)
+    def accumulate_device_vegas_binned(self, d_leaf: int, ss: int, ls: int, lts: int, d_bin: int, bin_base: int, n_bin: int, d_weight: int,
+                                       coef, seed: int, sample_offset: int, n_dim: int, n_grid: int, d_acc: int, d_acc2: int, d_hist: int,
+                                       d_hist_bin: int, B: int, stream: int = 0):
+        c = self._coef(coef)
+        check(lib().fdg_accumulate_device_vegas_binned(self._h, d_leaf or None, ss, ls, lts, d_bin or None, bin_base, n_bin, d_weight or None,
+                                                       None if c is None else c.ctypes.data, seed, sample_offset, n_dim, n_grid,
+                                                       d_acc or None, d_acc2 or None, d_hist or None, d_hist_bin or None, B, stream))
+
+    def mc_accumulate_device_vegas_binned(self, d_K, ks, kc, d_T, ts, tc, kF, beta, lam, d_bin, bin_base, n_bin, d_weight, coef, seed,
+                                          sample_offset, n_dim, n_grid, d_acc, d_acc2, d_hist, d_hist_bin, B, stream=0):
+        c = self._coef(coef)
+        check(lib().fdg_mc_accumulate_device_vegas_binned(self._h, d_K or None, ks, kc, d_T or None, ts, tc, kF, beta, lam, d_bin or None,
+                                                          bin_base, n_bin, d_weight or None, None if c is None else c.ctypes.data, seed,
+                                                          sample_offset, n_dim, n_grid, d_acc or None, d_acc2 or None, d_hist or None,
+                                                          d_hist_bin or None, B, stream))
+
     def _coef(self, coef):
         if coef is None:
             return None
@@ -512,6 +540,37 @@ def vegas_sample_device(d_grid: int, n_dim: int, n_grid: int, col, seed: int, sa
             raise ValueError("col must name one column per variable")
     check(lib().fdg_vegas_sample_device(d_grid or None, n_dim, n_grid, None if c is None else c.ctypes.data, seed, sample_offset,
                                         d_x or None, xs, xc, d_jac or None, d_cell or None, B, stream))
+
+
+def vegas_sample_device_discrete(d_grid: int, n_dim: int, n_grid: int, col, d_cdf: int, n_bin: int, bin_base: int, d_ext: int, ext_col,
+                                 seed: int, sample_offset: int, d_x: int, xs: int, xc: int, d_jac: int, d_bin: int, d_cell: int, B: int,
+                                 stream: int = 0):
+    """fdg_vegas_sample_device_discrete: :func:`vegas_sample_device` plus one discrete variable drawn by ``d_cdf`` (device,
+    ``n_bin + 1`` doubles): ``bin[b] = j + bin_base``, ``jac[b]`` divided by the value's probability, row ``j`` of ``d_ext`` (device,
+    ``[n_bin, len(ext_col)]``) copied into the columns ``ext_col`` (host sequence; empty or None with ``d_ext`` 0: no table)."""
+    c = None
+    if col is not None:
+        c = np.ascontiguousarray(col, dtype=np.uint32)
+        if c.shape != (n_dim,):
+            raise ValueError("col must name one column per variable")
+    e = np.ascontiguousarray([] if ext_col is None else ext_col, dtype=np.uint32)
+    if e.ndim != 1:
+        raise ValueError("ext_col must be a sequence of column numbers")
+    check(lib().fdg_vegas_sample_device_discrete(d_grid or None, n_dim, n_grid, None if c is None else c.ctypes.data, d_cdf or None, n_bin,
+                                                 bin_base, d_ext or None, e.shape[0], e.ctypes.data if e.shape[0] else None, seed,
+                                                 sample_offset, d_x or None, xs, xc, d_jac or None, d_bin or None, d_cell or None, B, stream))
+
+
+def vegas_refine_discrete(cdf: np.ndarray, hist_bin: np.ndarray, alpha: float = 0.5, floor: float = 0.05) -> np.ndarray:
+    """fdg_vegas_refine_discrete: moves the probabilities of the discrete variable ``cdf [n_bin + 1]`` (float64, C-contiguous, in place)
+    towards ``p_j ~ (hist_bin[j] * p_j) ** alpha``, every one at least ``floor / n_bin``; returns ``cdf``."""
+    if not (isinstance(cdf, np.ndarray) and cdf.dtype == np.float64 and cdf.ndim == 1 and cdf.flags.c_contiguous and cdf.shape[0] >= 2):
+        raise ValueError("cdf must be a C-contiguous float64 [n_bin + 1] array")
+    h = np.ascontiguousarray(hist_bin, dtype=np.float64)
+    if h.shape != (cdf.shape[0] - 1,):
+        raise ValueError("hist_bin must be [n_bin]")
+    check(lib().fdg_vegas_refine_discrete(cdf.ctypes.data, h.ctypes.data, cdf.shape[0] - 1, float(alpha), float(floor)))
+    return cdf
 
 
 def vegas_refine(grid: np.ndarray, hist: np.ndarray, alpha: float = 0.5) -> np.ndarray:

@@ -363,6 +363,42 @@ class GraphFunc:
                                                 acc.data_ptr(), acc2.data_ptr(), hist.data_ptr(), B, st)
         return acc, acc2, hist
 
+    def accumulate_vegas_binned(self, leaf, bins, n_bin: int, weight, hist, hist_bin, seed: int, sample_offset: int, n_dim: int, n_grid: int,
+                                coef=None, acc=None, acc2=None, bin_base: int = 0, n_sample: Optional[int] = None, train_bins: bool = True):
+        """The accumulate step of one VEGAS iteration with a discrete variable: :meth:`accumulate_moments` with ``bins`` (``acc``, ``acc2``
+        ``[n_bin, R]``: the same bits), the training histogram of :meth:`accumulate_vegas` over the samples whose bin is in range (the same
+        bits when every one is), and ``hist_bin[j] += (weight[b] * sum_k coef[k] * root_k(b))**2`` over the samples of bin ``j`` -- what
+        ``vegas.DiscreteMap.refine`` takes.  ``hist``: contiguous float64 ``[n_dim, n_grid]``, ``hist_bin``: contiguous float64 ``[n_bin]``,
+        both CUDA tensors, added to (zeros when None; ``train_bins=False``: no ``hist_bin``, None is returned for it).  The roots of a chunk
+        are evaluated once.  Returns ``(acc, acc2, hist, hist_bin)``.  Deterministic: no float atomics (fdg_accumulate_device_vegas_binned)."""
+        import torch
+        B, n_bin, bins, weight, strides = self._binned_args(leaf, bins, n_bin, weight, n_sample)
+        n_dim, n_grid = int(n_dim), int(n_grid)
+        if not (1 <= n_dim <= capi.FDG_VEGAS_DIM_MAX and 1 <= n_grid <= capi.FDG_VEGAS_GRID_MAX):
+            raise ValueError(f"n_dim must lie in [1, {capi.FDG_VEGAS_DIM_MAX}] and n_grid in [1, {capi.FDG_VEGAS_GRID_MAX}]")
+        w = 0 if weight is None else weight.data_ptr()
+        acc = self._bin_acc(acc, n_bin, leaf, "acc")
+        acc2 = self._bin_acc(acc2, n_bin, leaf, "acc2")
+        if hist is None:
+            hist = torch.zeros((n_dim, n_grid), dtype=torch.float64, device=leaf.device)
+        if hist_bin is None and train_bins:
+            hist_bin = torch.zeros(n_bin, dtype=torch.float64, device=leaf.device)
+        for h, shape, what in ((hist, (n_dim, n_grid), "hist"), (hist_bin, (n_bin,), "hist_bin")):
+            if h is not None and (not _is_torch(h) or not h.is_cuda or h.device != leaf.device or h.dtype != torch.float64
+                                  or not h.is_contiguous() or tuple(h.shape) != shape):
+                raise ValueError(f"{what} must be a contiguous float64 {list(shape)} tensor on the leaves' device")
+        if not train_bins:
+            hist_bin = None
+        outs = [acc, acc2, hist] + ([] if hist_bin is None else [hist_bin])
+        if len({o.data_ptr() for o in outs}) != len(outs):
+            raise ValueError("acc, acc2, hist and hist_bin must be different tensors")
+        st = torch.cuda.current_stream(leaf.device).cuda_stream
+        with torch.cuda.device(leaf.device):
+            self.handle.accumulate_device_vegas_binned(leaf.data_ptr(), *strides, bins.data_ptr(), int(bin_base), n_bin, w, coef, int(seed),
+                                                       int(sample_offset), n_dim, n_grid, acc.data_ptr(), acc2.data_ptr(), hist.data_ptr(),
+                                                       0 if hist_bin is None else hist_bin.data_ptr(), B, st)
+        return acc, acc2, hist, hist_bin
+
     def _binned_args(self, leaf, bins, n_bin, weight, n_sample, bins_optional=False):
         """The checks of :meth:`accumulate_binned` / :meth:`accumulate_moments`: (n_sample, n_bin, bins, weight, leaf strides), bins and
         weight contiguous (the caller holds them until the launch is queued)."""

@@ -26,6 +26,11 @@
 // the sampler draws through a piecewise-linear map per variable; the accumulate calls are the second-moment calls without a bin vector
 // plus one more pass per chunk over the same roots (fdg_vegas_partials below) that sums (w sum_k c_k root_k)^2 into a histogram per
 // variable and map cell, the cell recomputed from the sample's Philox counter; the refinement of the map is host code at the end.
+//
+// The discrete external variable (fdg_vegas_sample_device_discrete, fdg_[mc_]accumulate_device_vegas_binned, fdg_vegas_refine_discrete):
+// the sampler draws one of n_bin values by its cumulative distribution next to the continuous variables; the accumulate calls are the
+// moments calls WITH their bin vector plus the training pass above plus one more pass (fdg_vegas_bin_partials) that sums the same
+// (w sum_k c_k root_k)^2 per value of the discrete variable, the key read from the bin vector.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -238,6 +243,53 @@ fdg_vegas_sample(const double *__restrict__ grid, uint32_t D, uint32_t G, VegasC
   }
 }
 
+struct VegasExtCols { uint32_t c[FDG_VEGAS_EXT_MAX]; };   // the columns of x the rows of the discrete variable's table go to
+
+// fdg_vegas_sample with one discrete variable behind the continuous ones: its uniform is the Philox column D, its value j the number
+// of interior edges of cdf that are <= u (a binary search per lane: the cdf is at most 128 KiB and stays in L2).
+__global__ void __launch_bounds__(256)
+fdg_vegas_sample_discrete(const double *__restrict__ grid, uint32_t D, uint32_t G, VegasCols col, const double *__restrict__ cdf,
+                          uint32_t n_bin, int32_t bin_base, const double *__restrict__ ext, uint32_t n_ext, VegasExtCols ecol, uint64_t seed,
+                          uint64_t off, double *__restrict__ x, long xs, long xc, double *__restrict__ jac, int32_t *__restrict__ bin,
+                          int32_t *__restrict__ cell, long n) {
+  for (long b = blockIdx.x * 256L + threadIdx.x; b < n; b += (long)gridDim.x * 256L) {
+    double jb = 0.0;
+    for (uint32_t d = 0; d < D; ++d) {
+      double y;
+      const uint32_t c = vegas_cell(off + (uint64_t)b, d, seed, G, y);
+      const double *e = grid + (size_t)d * (G + 1u) + c;
+      const double lo = e[0], wd = e[1] - lo, fr = y - (double)c;
+      x[b * xs + (long)col.c[d] * xc] = lo + fr * wd;
+      const double f = (double)G * wd;
+      jb = d ? jb * f : f;
+      if (cell) cell[(size_t)d * (size_t)n + (size_t)b] = (int32_t)c;
+    }
+    const double u = fdg_philox_u53(off + (uint64_t)b, D, seed);
+    uint32_t lo = 0, hi = n_bin - 1u;                     // j in [lo, hi]: cdf[1 .. lo] <= u < cdf[hi + 1 ..]
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (cdf[mid + 1u] <= u) lo = mid + 1u; else hi = mid;
+    }
+    const double p = cdf[lo + 1u] - cdf[lo];
+    jac[b] = jb / p;
+    bin[b] = (int32_t)lo + bin_base;
+    for (uint32_t e = 0; e < n_ext; ++e) x[b * xs + (long)ecol.c[e] * xc] = ext[(size_t)lo * n_ext + e];
+  }
+}
+
+// t = w (c_0 r_0 + c_1 r_1 + ...) of the sample at bb of the chunk, over the n_live roots kidx[] that exist, a left fold (coef null: plain
+// sum; weight null: t = the sum).  What both training passes below square.
+__device__ __forceinline__ double vegas_term(const double *__restrict__ root, long ld, size_t bb, const double *__restrict__ weight,
+                                             const uint32_t *__restrict__ kidx, const double *__restrict__ coef, uint32_t n_live) {
+  double sum = 0.0;
+  for (uint32_t i = 0; i < n_live; ++i) {
+    const double rk = root[(size_t)kidx[i] * (size_t)ld + bb];
+    const double term = coef ? coef[i] * rk : rk;
+    sum = i ? sum + term : term;
+  }
+  return weight ? weight[bb] * sum : sum;
+}
+
 // The training pass over a chunk's roots (root k of sample b at root[k * ld + b], b < n): hist[d][c] += v(b) for every variable d, c = the
 // cell of sample off + b in d, v = (w (c_0 r_0 + c_1 r_1 + ...))^2 over the n_live roots kidx[] that exist (coef null: plain sum).
 // One workgroup per (segment of the chunk's tiles, slice of DS variables), the slice's histograms (DS x G doubles) in LDS.
@@ -249,10 +301,15 @@ fdg_vegas_sample(const double *__restrict__ grid, uint32_t D, uint32_t G, VegasC
 //    (two buffers, one barrier per round).
 //  * Chunks and segments chain as in the binned pass: partial [segment][variable][cell], summed in segment order by fdg_binned_reduce.
 // Lanes past n are selected away (key invalid, v = 0 never enters a sum); no float atomics.
+// BINNED (the calls with a discrete variable): a sample whose bin lies outside [bin_base, bin_base + n_bin) is selected away like a lane
+// past n.  The wave that forms v leaves -1 for it in the exchange buffer (v is a square: never negative), and the waves that walk the
+// tile give such a lane the invalid key.  With every bin in range no key changes: the sums are those of the unbinned instance.
+template <int BINNED>
 __global__ void __launch_bounds__(256)
 fdg_vegas_partials(const double *__restrict__ root, long ld, long n, const double *__restrict__ weight, const uint32_t *__restrict__ kidx,
                    const double *__restrict__ coef, uint32_t n_live, uint64_t seed, uint64_t off, uint32_t D, uint32_t G, uint32_t DS,
-                   uint32_t n_slice, long seg_tiles, double *__restrict__ partial, int first) {
+                   uint32_t n_slice, long seg_tiles, double *__restrict__ partial, int first, const int32_t *__restrict__ bins,
+                   int32_t bin_base, uint32_t n_bin) {
   extern __shared__ double hist[];                        // [DS][G], then v of the round's tiles [2][kBinWaves][64]
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   const uint32_t slice = blockIdx.x % n_slice, seg = blockIdx.x / n_slice;
@@ -266,16 +323,14 @@ fdg_vegas_partials(const double *__restrict__ root, long ld, long n, const doubl
   for (long r = 0; r < rounds; ++r) {
     {
       const long t = t0 + r * (long)kBinWaves + wave, b = t * 64 + lane;
-      const bool in = t < t1 && b < n;
+      bool in = t < t1 && b < n;
       const size_t bb = (size_t)min(b, n - 1);            // clamped into the chunk; what it loads is used only where `in`
-      double sum = 0.0;
-      for (uint32_t i = 0; i < n_live; ++i) {
-        const double rk = root[(size_t)kidx[i] * (size_t)ld + bb];
-        const double term = coef ? coef[i] * rk : rk;
-        sum = i ? sum + term : term;
+      if (BINNED) {
+        const int64_t jb = (int64_t)bins[bb] - (int64_t)bin_base;
+        in = in && jb >= 0 && jb < (int64_t)n_bin;
       }
-      const double tw = weight ? weight[bb] * sum : sum;
-      vbuf[(r & 1) * (kBinWaves * 64) + wave * 64 + lane] = in ? tw * tw : 0.0;
+      const double tw = vegas_term(root, ld, bb, weight, kidx, coef, n_live);
+      vbuf[(r & 1) * (kBinWaves * 64) + wave * 64 + lane] = in ? tw * tw : (BINNED && t < t1 && b < n) ? -1.0 : 0.0;
     }
     __syncthreads();
     for (uint32_t tt = 0; tt < kBinWaves; ++tt) {
@@ -285,7 +340,7 @@ fdg_vegas_partials(const double *__restrict__ root, long ld, long n, const doubl
       for (uint32_t dd = wave; dd < dn; dd += kBinWaves) {
         double y;
         const uint32_t c = vegas_cell(off + (uint64_t)b, d0 + dd, seed, G, y);
-        uint32_t key = b < n ? (c << 6) | lane : kKeyInvalid | lane;
+        uint32_t key = (b < n && !(BINNED && v < 0.0)) ? (c << 6) | lane : kKeyInvalid | lane;
         const uint64_t valid = __ballot(key < kKeyInvalid);
         if (!valid) continue;
         const uint32_t src = wave_sort_keys(key, lane, valid);
@@ -305,6 +360,66 @@ fdg_vegas_partials(const double *__restrict__ root, long ld, long n, const doubl
   }
   __syncthreads();
   for (uint32_t i = threadIdx.x; i < dn * G; i += 256) slab[i] = hist[i];
+}
+
+// The training pass of the discrete variable: hbin[j] += v(b) over the samples b of the chunk whose bin is j + bin_base, v as above.
+// The variable is one more key column of the pass above whose key is read from `bins`, but its histogram has up to FDG_BIN_MAX cells
+// (128 KiB), so it is a slice of its own: one workgroup per segment of the chunk's tiles, the whole histogram (n_bin doubles) in LDS,
+// and with one variable there is nothing to deal over the waves but the tiles, so the round is fdg_binned_partials': wave w forms v for
+// tile 4 r + w, sorts its lanes by (bin, lane), sums every run of equal bins, and the run heads add into the histogram in the waves'
+// turns, wave 0 first: per bin, tiles are added in tile order.  Chunks and segments chain through partial [segment][bin], summed in
+// segment order by fdg_binned_reduce.  Out-of-range bins and lanes past n are selected away (key invalid); no float atomics.
+__global__ void __launch_bounds__(256)
+fdg_vegas_bin_partials(const double *__restrict__ root, long ld, long n, const int32_t *__restrict__ bins, int32_t bin_base, uint32_t n_bin,
+                       const double *__restrict__ weight, const uint32_t *__restrict__ kidx, const double *__restrict__ coef, uint32_t n_live,
+                       long seg_tiles, double *__restrict__ partial, int first) {
+  extern __shared__ double hist[];                        // [n_bin]
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t seg = blockIdx.x;
+  double *slab = partial + (size_t)seg * n_bin;
+  for (uint32_t i = threadIdx.x; i < n_bin; i += 256) hist[i] = first ? 0.0 : slab[i];
+  __syncthreads();
+  const long ntile = (n + 63) / 64, t0 = (long)seg * seg_tiles, t1 = min(t0 + seg_tiles, ntile);
+  const long rounds = t1 > t0 ? (t1 - t0 + kBinWaves - 1) / kBinWaves : 0;
+  // this lane's sample of round r, formed one round ahead (indices clamped into the chunk; used only where the sample is `in`)
+  int32_t bin_n;
+  double t_n;
+  auto fetch = [&](long r) {
+    const size_t bb = (size_t)min((t0 + r * (long)kBinWaves + wave) * 64 + lane, n - 1);
+    bin_n = bins[bb];
+    t_n = vegas_term(root, ld, bb, weight, kidx, coef, n_live);
+  };
+  fetch(0);
+  for (long r = 0; r < rounds; ++r) {
+    const long t = t0 + r * (long)kBinWaves + wave, b = t * 64 + lane;
+    const int64_t jb = (int64_t)bin_n - (int64_t)bin_base;
+    const bool in = t < t1 && b < n && jb >= 0 && jb < (int64_t)n_bin;
+    uint32_t key = in ? ((uint32_t)jb << 6) | lane : kKeyInvalid | lane;
+    const double v = in ? t_n * t_n : 0.0;
+    fetch(r + 1);
+    const uint64_t valid = __ballot(key < kKeyInvalid);
+    double s = 0.0;
+    bool head = false;
+    uint32_t j = 0;
+    if (valid) {
+      const uint32_t src = wave_sort_keys(key, lane, valid);
+      uint32_t end;
+      wave_runs(key, lane, j, head, end);
+      s = __shfl(v, (int)src);
+      for (uint32_t dist = 1; dist < 64; dist <<= 1) {     // segmented suffix scan, as in fdg_binned_partials
+        const bool take = lane + dist <= end;
+        if (!__ballot(take)) break;
+        const double up = __shfl_down(s, dist);
+        if (take) s = s + up;
+      }
+    }
+    for (uint32_t w = 0; w < kBinWaves; ++w) {            // the waves' turns, in wave order
+      if (wave == w && head) hist[j] = hist[j] + s;
+      bin_barrier();
+    }
+  }
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < n_bin; i += 256) slab[i] = hist[i];
 }
 
 // How one call is cut: chunks of Bc samples through the root scratch, RS roots per slice, n_seg segments per chunk.  mode: what the
@@ -362,13 +477,17 @@ struct VegasRun {
   uint64_t seed = 0, offset = 0;
   uint32_t D = 0, G = 0;
   double *d_hist = nullptr;
+  bool binned = false;               // the calls with a discrete variable: d_bin selects the samples of the training pass too
+  double *d_hist_bin = nullptr;      // ... and, when given, the discrete variable is trained: [n_bin]
 };
+// bin_*: the discrete variable's slice (fdg_vegas_bin_partials), segments by the same three bounds with the histogram [bin]; a function
+// of (n_sample, n_bin, n_root, FDG_ROOT_SCRATCH_MB) that leaves the continuous variables' cut as it is.
 struct VegasPlan {
-  uint32_t ds = 1, n_slice = 1, n_seg = 1;
-  size_t lds = 0, slab_alloc = 0, list_bytes = 0;
+  uint32_t ds = 1, n_slice = 1, n_seg = 1, bin_seg = 1;
+  size_t lds = 0, slab_alloc = 0, list_bytes = 0, bin_slab_alloc = 0;
 };
 
-VegasPlan vegas_plan(const BinnedPlan &p, const VegasRun &v, uint32_t R) {
+VegasPlan vegas_plan(const BinnedPlan &p, const VegasRun &v, uint32_t R, uint32_t n_bin) {
   VegasPlan q;
   const uint32_t fit = (uint32_t)std::max<size_t>(1, kBinLdsBudget / ((size_t)v.G * 8u));
   q.n_slice = (v.D + fit - 1) / fit;
@@ -382,6 +501,11 @@ VegasPlan vegas_plan(const BinnedPlan &p, const VegasRun &v, uint32_t R) {
   q.n_seg = (uint32_t)std::min(std::min(by_size, by_slab), by_blocks);
   q.slab_alloc = (std::max(hist_bytes, std::min(kBinSlabBytes, (size_t)by_size * hist_bytes)) + 4095) & ~(size_t)4095;
   q.list_bytes = ((size_t)R * 12u + 4095) & ~(size_t)4095;      // coef[R] doubles, then kidx[R]
+  if (v.d_hist_bin) {
+    const size_t bin_bytes = (size_t)n_bin * 8u;
+    q.bin_seg = (uint32_t)std::min(std::min(by_size, std::max<long>(1, (long)(kBinSlabBytes / bin_bytes))), 2048l);
+    q.bin_slab_alloc = (std::max(bin_bytes, std::min(kBinSlabBytes, (size_t)by_size * bin_bytes)) + 4095) & ~(size_t)4095;
+  }
   return q;
 }
 
@@ -458,9 +582,24 @@ int check_vegas(const fdg_graph *g, uint32_t n_dim, uint32_t n_grid, const doubl
   return check_vegas_map(n_dim, n_grid);
 }
 
+// ... and the calls' with a discrete variable: the moments calls' cases with a bin vector, the map's, and four distinct output arrays.
+int check_vegas_binned(const fdg_graph *g, const int32_t *d_bin, uint32_t n_bin, uint32_t n_dim, uint32_t n_grid, const double *d_acc,
+                       const double *d_acc2, const double *d_hist, const double *d_hist_bin, int64_t B) {
+  if (g && !d_bin) { set_error("d_bin == NULL: use the call without a discrete variable"); return FDG_E_INVALID; }
+  int rc = check_moments(g, d_bin, n_bin, d_acc, d_acc2, B);
+  if (rc) return rc;
+  if (!d_hist) { set_error("null device buffer"); return FDG_E_INVALID; }
+  if (d_hist == d_acc || d_hist == d_acc2) { set_error("d_hist is the same buffer as d_acc or d_acc2"); return FDG_E_INVALID; }
+  if (d_hist_bin && (d_hist_bin == d_acc || d_hist_bin == d_acc2 || d_hist_bin == d_hist)) {
+    set_error("d_hist_bin is the same buffer as d_acc, d_acc2 or d_hist"); return FDG_E_INVALID;
+  }
+  return check_vegas_map(n_dim, n_grid);
+}
+
 // The chunk loop shared by the entry points (caller holds g->mu, stream bound): eval(c0, n, roots, ld) writes the roots of samples
 // c0 .. c0 + n - 1 column-major into roots (root k of sample c0 + b at roots[k * ld + b]).  d_acc2 != null: the second moment too.
-// vg != null (the VEGAS calls): after a chunk's moments pass the training pass runs over the same roots, its partials behind the moments' slab.
+// vg != null (the VEGAS calls): after a chunk's moments pass the training pass runs over the same roots, its partials behind the moments' slab;
+// with vg->d_hist_bin the discrete variable's pass follows, its partials behind the root list.
 template <class Eval>
 int run_binned(fdg_graph *g, const int32_t *d_bin, int32_t bin_base, uint32_t n_bin, const double *d_weight, double *d_acc, double *d_acc2,
                int64_t B, hipStream_t st, Eval eval, const VegasRun *vg = nullptr) {
@@ -469,25 +608,29 @@ int run_binned(fdg_graph *g, const int32_t *d_bin, int32_t bin_base, uint32_t n_
   const size_t root_bytes = ((size_t)p.Bc * R * sizeof(double) + 4095) & ~(size_t)4095;
   const size_t slab_bytes = (p.slab_alloc + 4095) & ~(size_t)4095;
   VegasPlan q;
-  if (vg) q = vegas_plan(p, *vg, R);
-  int rc = ensure_root_scratch(g, vg ? root_bytes + slab_bytes + q.slab_alloc + q.list_bytes : root_bytes + p.slab_alloc);
+  if (vg) q = vegas_plan(p, *vg, R, n_bin);
+  int rc = ensure_root_scratch(g, vg ? root_bytes + slab_bytes + q.slab_alloc + q.list_bytes + q.bin_slab_alloc : root_bytes + p.slab_alloc);
   if (rc) return rc;
   double *roots = (double *)g->d_ws2, *partial = (double *)((char *)g->d_ws2 + root_bytes);
   const uint8_t *live = nullptr;
   rc = root_live_mask(g, &live);
   if (rc) return rc;
-  double *vpartial = nullptr, *d_coef = nullptr;
+  double *vpartial = nullptr, *d_coef = nullptr, *bpartial = nullptr;
   uint32_t *d_kidx = nullptr, n_live = 0;
   if (vg) {
     static std::once_flag lds_once;
     std::call_once(lds_once, [] {
-      (void)hipFuncSetAttribute((const void *)fdg_vegas_partials, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kBinLdsBudget + 2u * kBinWaves * 64u * 8u));
+      const int lds = (int)(kBinLdsBudget + 2u * kBinWaves * 64u * 8u);
+      (void)hipFuncSetAttribute((const void *)fdg_vegas_partials<0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+      (void)hipFuncSetAttribute((const void *)fdg_vegas_partials<1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+      (void)hipFuncSetAttribute((const void *)fdg_vegas_bin_partials, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(FDG_BIN_MAX * 8));
       (void)hipGetLastError();
     });
     // the roots that exist, ascending, and their factors: one small upload per call (pageable memory: staged before the call returns)
     vpartial = (double *)((char *)partial + slab_bytes);
     d_coef = (double *)((char *)vpartial + q.slab_alloc);
     d_kidx = (uint32_t *)(d_coef + R);
+    bpartial = (double *)((char *)d_coef + q.list_bytes);
     std::vector<double> hc;
     std::vector<uint32_t> hk;
     for (uint32_t k = 0; k < R; ++k)
@@ -506,10 +649,22 @@ int run_binned(fdg_graph *g, const int32_t *d_bin, int32_t bin_base, uint32_t n_
     if (rc) return rc;
     if (vg) {
       const long ntile = (n + 63) / 64, seg_tiles = (ntile + q.n_seg - 1) / q.n_seg;
-      hipLaunchKernelGGL(fdg_vegas_partials, dim3(q.n_seg * q.n_slice), dim3(256), q.lds, st, roots, (long)p.Bc, n,
-                         d_weight ? d_weight + c0 : nullptr, d_kidx, vg->coef ? d_coef : nullptr, n_live, vg->seed, vg->offset + (uint64_t)c0,
-                         vg->D, vg->G, q.ds, q.n_slice, seg_tiles, vpartial, c0 == 0);
+      const double *w = d_weight ? d_weight + c0 : nullptr, *cf = vg->coef ? d_coef : nullptr;
+      if (vg->binned)
+        hipLaunchKernelGGL(fdg_vegas_partials<1>, dim3(q.n_seg * q.n_slice), dim3(256), q.lds, st, roots, (long)p.Bc, n, w, d_kidx, cf, n_live,
+                           vg->seed, vg->offset + (uint64_t)c0, vg->D, vg->G, q.ds, q.n_slice, seg_tiles, vpartial, c0 == 0, d_bin + c0, bin_base,
+                           n_bin);
+      else
+        hipLaunchKernelGGL(fdg_vegas_partials<0>, dim3(q.n_seg * q.n_slice), dim3(256), q.lds, st, roots, (long)p.Bc, n, w, d_kidx, cf, n_live,
+                           vg->seed, vg->offset + (uint64_t)c0, vg->D, vg->G, q.ds, q.n_slice, seg_tiles, vpartial, c0 == 0,
+                           (const int32_t *)nullptr, 0, 1u);
       HIP_TRY(hipGetLastError());
+      if (vg->d_hist_bin) {
+        const long bin_tiles = (ntile + q.bin_seg - 1) / q.bin_seg;
+        hipLaunchKernelGGL(fdg_vegas_bin_partials, dim3(q.bin_seg), dim3(256), (size_t)n_bin * 8u, st, roots, (long)p.Bc, n, d_bin + c0, bin_base,
+                           n_bin, w, d_kidx, cf, n_live, bin_tiles, bpartial, c0 == 0);
+        HIP_TRY(hipGetLastError());
+      }
     }
   }
   const long ncol = (long)n_bin * R;
@@ -524,6 +679,11 @@ int run_binned(fdg_graph *g, const int32_t *d_bin, int32_t bin_base, uint32_t n_
     hipLaunchKernelGGL(fdg_binned_reduce, dim3((unsigned)((hcol + 63) / 64), 1), dim3(256), 0, st, vpartial, q.n_seg, hcol, hcol, 1u, 64u,
                        vg->d_hist, (double *)nullptr, (const uint8_t *)nullptr);
     HIP_TRY(hipGetLastError());
+    if (vg->d_hist_bin) {                                 // hist_bin[j] += the segments' partials, in segment order
+      hipLaunchKernelGGL(fdg_binned_reduce, dim3((unsigned)((n_bin + 63u) / 64u), 1), dim3(256), 0, st, bpartial, q.bin_seg, (long)n_bin,
+                         (long)n_bin, 1u, 64u, vg->d_hist_bin, (double *)nullptr, (const uint8_t *)nullptr);
+      HIP_TRY(hipGetLastError());
+    }
   }
   return FDG_OK;
 }
@@ -625,6 +785,62 @@ int fdg_mc_accumulate_device_vegas(fdg_graph *g, const double *d_K, int64_t ks, 
   return accumulate_mc(g, d_K, ks, kc, d_T, ts, tc, kF, beta, lambda, nullptr, 0, 1, d_weight, d_acc, d_acc2, B, stream, &vg);
 }
 
+int fdg_accumulate_device_vegas_binned(fdg_graph *g, const double *d_leaf, int64_t ss, int64_t ls, int64_t lts, const int32_t *d_bin,
+                                       int32_t bin_base, uint32_t n_bin, const double *d_weight, const double *coef, uint64_t seed,
+                                       uint64_t sample_offset, uint32_t n_dim, uint32_t n_grid, double *d_acc, double *d_acc2, double *d_hist,
+                                       double *d_hist_bin, int64_t B, void *stream) {
+  const int rc = check_vegas_binned(g, d_bin, n_bin, n_dim, n_grid, d_acc, d_acc2, d_hist, d_hist_bin, B);
+  if (rc) return rc;
+  VegasRun vg;
+  vg.coef = coef; vg.seed = seed; vg.offset = sample_offset; vg.D = n_dim; vg.G = n_grid; vg.d_hist = d_hist;
+  vg.binned = true; vg.d_hist_bin = d_hist_bin;
+  return accumulate_leaf(g, d_leaf, ss, ls, lts, d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, stream, &vg);
+}
+
+int fdg_mc_accumulate_device_vegas_binned(fdg_graph *g, const double *d_K, int64_t ks, int64_t kc, const double *d_T, int64_t ts, int64_t tc,
+                                          double kF, double beta, double lambda, const int32_t *d_bin, int32_t bin_base, uint32_t n_bin,
+                                          const double *d_weight, const double *coef, uint64_t seed, uint64_t sample_offset, uint32_t n_dim,
+                                          uint32_t n_grid, double *d_acc, double *d_acc2, double *d_hist, double *d_hist_bin, int64_t B,
+                                          void *stream) {
+  const int rc = check_vegas_binned(g, d_bin, n_bin, n_dim, n_grid, d_acc, d_acc2, d_hist, d_hist_bin, B);
+  if (rc) return rc;
+  VegasRun vg;
+  vg.coef = coef; vg.seed = seed; vg.offset = sample_offset; vg.D = n_dim; vg.G = n_grid; vg.d_hist = d_hist;
+  vg.binned = true; vg.d_hist_bin = d_hist_bin;
+  return accumulate_mc(g, d_K, ks, kc, d_T, ts, tc, kF, beta, lambda, d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, stream, &vg);
+}
+
+int fdg_vegas_sample_device_discrete(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, const double *d_cdf,
+                                     uint32_t n_bin, int32_t bin_base, const double *d_ext, uint32_t n_ext, const uint32_t *ext_col,
+                                     uint64_t seed, uint64_t sample_offset, double *d_x, int64_t x_sample_stride, int64_t x_col_stride,
+                                     double *d_jac, int32_t *d_bin, int32_t *d_cell, int64_t B, void *stream) {
+  if (B < 0) { set_error("n_sample < 0"); return FDG_E_INVALID; }
+  if (!d_grid || !d_x || !d_jac || !d_cdf || !d_bin) { set_error("null device buffer"); return FDG_E_INVALID; }
+  const int rc = check_vegas_map(n_dim, n_grid);
+  if (rc) return rc;
+  if (n_bin == 0) { set_error("n_bin == 0"); return FDG_E_INVALID; }
+  if (n_bin > FDG_BIN_MAX) { set_error("n_bin > FDG_BIN_MAX"); return FDG_E_UNSUPPORTED; }
+  if (n_ext > FDG_VEGAS_EXT_MAX) { set_error("n_ext > FDG_VEGAS_EXT_MAX"); return FDG_E_UNSUPPORTED; }
+  if (n_ext && (!d_ext || !ext_col)) { set_error("n_ext > 0 needs d_ext and ext_col"); return FDG_E_INVALID; }
+  VegasCols cols;
+  for (uint32_t d = 0; d < FDG_VEGAS_DIM_MAX; ++d) cols.c[d] = d < n_dim ? (col ? col[d] : d) : 0u;
+  VegasExtCols ecols;
+  for (uint32_t e = 0; e < FDG_VEGAS_EXT_MAX; ++e) ecols.c[e] = e < n_ext ? ext_col[e] : 0u;
+  for (uint32_t e = 0; e < n_ext; ++e) {
+    for (uint32_t f = 0; f < e; ++f)
+      if (ecols.c[f] == ecols.c[e]) { set_error("ext_col names a column twice"); return FDG_E_INVALID; }
+    for (uint32_t d = 0; d < n_dim; ++d)
+      if (cols.c[d] == ecols.c[e]) { set_error("ext_col names a column of col"); return FDG_E_INVALID; }
+  }
+  if (B == 0) return FDG_OK;
+  const long grid = std::min<long>(((long)B + 255) / 256, 256L * 16);
+  hipLaunchKernelGGL(fdg_vegas_sample_discrete, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, d_grid, n_dim, n_grid, cols, d_cdf,
+                     n_bin, bin_base, d_ext, n_ext, ecols, seed, sample_offset, d_x, (long)x_sample_stride, (long)x_col_stride, d_jac, d_bin,
+                     d_cell, (long)B);
+  HIP_TRY(hipGetLastError());
+  return FDG_OK;
+}
+
 int fdg_vegas_sample_device(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, uint64_t seed, uint64_t sample_offset,
                             double *d_x, int64_t x_sample_stride, int64_t x_col_stride, double *d_jac, int32_t *d_cell, int64_t B,
                             void *stream) {
@@ -685,6 +901,43 @@ int fdg_vegas_refine(double *grid, const double *hist, uint32_t n_dim, uint32_t 
       if (!(ne[i] < ne[i + 1])) { set_error("refined edges are not strictly increasing"); return FDG_E_INTERNAL; }
   }
   std::copy(out.begin(), out.end(), grid);
+  return FDG_OK;
+}
+
+// The refinement of the discrete variable's probabilities; host only, fp64, in the order include/fdg.h states.
+int fdg_vegas_refine_discrete(double *cdf, const double *hist_bin, uint32_t n_bin, double alpha, double floor) {
+  if (!cdf || !hist_bin) { set_error("null argument"); return FDG_E_INVALID; }
+  if (n_bin == 0) { set_error("n_bin == 0"); return FDG_E_INVALID; }
+  if (n_bin > FDG_BIN_MAX) { set_error("n_bin > FDG_BIN_MAX"); return FDG_E_UNSUPPORTED; }
+  if (!(alpha >= 0.0 && alpha <= 2.0)) { set_error("alpha outside [0, 2]"); return FDG_E_INVALID; }
+  if (!(floor >= 0.0 && floor < 1.0)) { set_error("floor outside [0, 1)"); return FDG_E_INVALID; }
+  if (cdf[0] != 0.0 || cdf[n_bin] != 1.0) { set_error("cdf does not run from 0 to 1"); return FDG_E_INVALID; }
+  for (uint32_t j = 0; j < n_bin; ++j) {
+    if (!(cdf[j] < cdf[j + 1])) { set_error("cdf is not strictly increasing"); return FDG_E_INVALID; }
+    if (!(hist_bin[j] >= 0.0) || !std::isfinite(hist_bin[j])) { set_error("histogram entry negative or not finite"); return FDG_E_INVALID; }
+  }
+  if (alpha == 0.0 || n_bin == 1) return FDG_OK;
+  std::vector<double> w(n_bin), out(n_bin + 1);
+  double qsum = 0.0;
+  for (uint32_t j = 0; j < n_bin; ++j) {
+    w[j] = hist_bin[j] * (cdf[j + 1] - cdf[j]);
+    qsum += w[j];
+  }
+  if (!(qsum > 0.0)) return FDG_OK;
+  if (!std::isfinite(qsum)) { set_error("histogram sum overflows"); return FDG_E_INVALID; }
+  double wsum = 0.0;
+  for (uint32_t j = 0; j < n_bin; ++j) {
+    const double s = w[j] / qsum;
+    w[j] = s > 0.0 ? std::pow(s, alpha) : 0.0;
+    wsum += w[j];
+  }
+  const double keep = 1.0 - floor, base = floor / (double)n_bin;
+  out[0] = 0.0;
+  for (uint32_t j = 0; j < n_bin; ++j) out[j + 1] = out[j] + (keep * w[j] / wsum + base);
+  out[n_bin] = 1.0;
+  for (uint32_t j = 0; j < n_bin; ++j)
+    if (!(out[j] < out[j + 1])) { set_error("refined probabilities are not all positive"); return FDG_E_INTERNAL; }
+  std::copy(out.begin(), out.end(), cdf);
   return FDG_OK;
 }
 

@@ -297,6 +297,43 @@ function vegas_refine!(grid::Matrix{Float64}, hist::Matrix{Float64}; alpha::Floa
         grid, hist, size(grid, 2), size(hist, 1), alpha))
     return grid
 end
+# ---- a discrete external variable (include/fdg.h; no counterpart in the reference: the caller's side of test/ver4.jl:224-237) ---- #
+# ExtKidx = MCIntegration.Discrete(1, Nk): d_cdf (n_bin + 1, on the device) is the variable's cumulative distribution, d_ext (n_ext x n_bin,
+# column j = what value j means) goes to the columns ext_col (1-based) of x; d_bin[b] is the value drawn (1-based by default), d_jac[b] the
+# continuous weight divided by the value's probability.  n_bin = 1 is vegas_sample_device! bit for bit.
+function vegas_sample_device_discrete!(d_x::Ptr{Float64}, d_jac::Ptr{Float64}, d_bin::Ptr{Int32}, d_grid::Ptr{Float64}, n_dim::Integer,
+    n_grid::Integer, d_cdf::Ptr{Float64}, n_bin::Integer, B::Integer; col::Union{Nothing,AbstractVector{<:Integer}}=nothing,
+    d_ext::Ptr{Float64}=Ptr{Float64}(C_NULL), ext_col::AbstractVector{<:Integer}=Int[], bin_base::Integer=1, seed::Integer=0,
+    sample_offset::Integer=0, x_strides=(1, B), d_cell::Ptr{Int32}=Ptr{Int32}(C_NULL), stream::Ptr{Cvoid}=C_NULL)
+    c = col === nothing ? nothing : UInt32.(col .- 1)
+    e = UInt32.(ext_col .- 1)
+    _fdg_check(ccall((:fdg_vegas_sample_device_discrete, _libfdg), Cint,
+        (Ptr{Float64}, UInt32, UInt32, Ptr{UInt32}, Ptr{Float64}, UInt32, Int32, Ptr{Float64}, UInt32, Ptr{UInt32}, UInt64, UInt64,
+         Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Int64, Ptr{Cvoid}),
+        d_grid, n_dim, n_grid, c === nothing ? C_NULL : c, d_cdf, n_bin, bin_base, d_ext, length(e), isempty(e) ? C_NULL : e, seed,
+        sample_offset, d_x, x_strides[1], x_strides[2], d_jac, d_bin, d_cell, B, stream))
+    return nothing
+end
+# The accumulate step with the discrete variable (fdg_accumulate_device_vegas_binned): d_acc, d_acc2 (R x n_bin) as accumulate_device_moments!
+# leaves them, d_hist (G x D) as accumulate_device_vegas!, and d_hist_bin (n_bin, or C_NULL: not trained) the same squares summed per value.
+function accumulate_device_vegas_binned!(f::GraphFunc, d_acc::Ptr{Float64}, d_acc2::Ptr{Float64}, d_hist::Ptr{Float64},
+    d_hist_bin::Ptr{Float64}, d_leaf::Ptr{Float64}, d_bin::Ptr{Int32}, n_bin::Integer, d_weight::Ptr{Float64}, n_dim::Integer,
+    n_grid::Integer, B::Integer; coef::Union{Nothing,Vector{Float64}}=nothing, seed::Integer=0, sample_offset::Integer=0,
+    leaf_strides=(1, B), tile_stride::Integer=0, bin_base::Integer=1, stream::Ptr{Cvoid}=C_NULL)
+    _fdg_check(ccall((:fdg_accumulate_device_vegas_binned, _libfdg), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Int64, Ptr{Int32}, Int32, UInt32, Ptr{Float64}, Ptr{Float64}, UInt64, UInt64, UInt32, UInt32,
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Cvoid}),
+        f.handle, d_leaf, leaf_strides[1], leaf_strides[2], tile_stride, d_bin, bin_base, n_bin, d_weight, coef === nothing ? C_NULL : coef,
+        seed, sample_offset, n_dim, n_grid, d_acc, d_acc2, d_hist, d_hist_bin, B, stream))
+    return nothing
+end
+# The refinement of the probabilities, both on the host (fdg_vegas_refine_discrete): cdf is n_bin + 1, hist_bin n_bin.
+function vegas_refine_discrete!(cdf::Vector{Float64}, hist_bin::Vector{Float64}; alpha::Float64=0.5, floor::Float64=0.05)
+    length(hist_bin) == length(cdf) - 1 || error("hist_bin must hold n_bin entries for a cdf of n_bin + 1")
+    _fdg_check(ccall((:fdg_vegas_refine_discrete, _libfdg), Cint, (Ptr{Float64}, Ptr{Float64}, UInt32, Float64, Float64),
+        cdf, hist_bin, length(hist_bin), alpha, floor))
+    return cdf
+end
 # device memory for a batch, backed by physical chunks of `chunk_bytes` (0: one allocation): fdg_batch_alloc / fdg_batch_free
 function batch_alloc(bytes::Integer; chunk_bytes::Integer=0)
     p = Ref{Ptr{Cvoid}}(C_NULL)
@@ -345,7 +382,7 @@ function accumulate_device!(f::GraphFunc, d_acc::Ptr{Float64}, d_leaf::Ptr{Float
         f.handle, d_leaf, leaf_strides[1], leaf_strides[2], d_weight, d_acc, B, stream))
 end
 
-export compile_hip, GraphFunc, eval_device!, accumulate_device!, eval_device_tiled!, accumulate_device_tiled!, accumulate_device_binned!, mc_accumulate_device_binned!, accumulate_device_moments!, mc_accumulate_device_moments!, vegas_sample_device!, accumulate_device_vegas!, mc_accumulate_device_vegas!, vegas_refine!, batch_alloc, batch_free, tile_major!, from_tile_major!
+export compile_hip, GraphFunc, eval_device!, accumulate_device!, eval_device_tiled!, accumulate_device_tiled!, accumulate_device_binned!, mc_accumulate_device_binned!, accumulate_device_moments!, mc_accumulate_device_moments!, vegas_sample_device!, accumulate_device_vegas!, mc_accumulate_device_vegas!, vegas_refine!, vegas_sample_device_discrete!, accumulate_device_vegas_binned!, mc_accumulate_device_vegas_binned!, vegas_refine_discrete!, batch_alloc, batch_free, tile_major!, from_tile_major!
 
 # ---- multi-GPU: one Julia process per GPU, ONE reduction of the accumulated observable ------------ #
 # (include/fdg.h, "multi-GPU").  Rank 0 calls `comm_unique_id()` and ships the 128 bytes to the other
@@ -460,6 +497,19 @@ function mc_accumulate_device_vegas!(f::GraphFunc, d_K::Ptr{Float64}, d_T::Ptr{F
          UInt64, UInt32, UInt32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Cvoid}),
         f.handle, d_K, k_strides[1], k_strides[2], d_T, t_strides[1], t_strides[2], kF, beta, lambda, d_weight,
         coef === nothing ? C_NULL : coef, seed, sample_offset, n_dim, n_grid, d_acc, d_acc2, d_hist, B, stream))
+    return nothing
+end
+# the same for the fused step (fdg_mc_accumulate_device_vegas_binned)
+function mc_accumulate_device_vegas_binned!(f::GraphFunc, d_K::Ptr{Float64}, d_T::Ptr{Float64}, d_bin::Ptr{Int32}, n_bin::Integer,
+    d_weight::Ptr{Float64}, d_acc::Ptr{Float64}, d_acc2::Ptr{Float64}, d_hist::Ptr{Float64}, d_hist_bin::Ptr{Float64}, n_dim::Integer,
+    n_grid::Integer, B::Integer; kF::Float64, beta::Float64, lambda::Float64, coef::Union{Nothing,Vector{Float64}}=nothing,
+    seed::Integer=0, sample_offset::Integer=0, k_strides=(1, B), t_strides=(1, B), bin_base::Integer=1, stream::Ptr{Cvoid}=C_NULL)
+    _fdg_check(ccall((:fdg_mc_accumulate_device_vegas_binned, _libfdg), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Int64, Float64, Float64, Float64, Ptr{Int32}, Int32, UInt32,
+         Ptr{Float64}, Ptr{Float64}, UInt64, UInt64, UInt32, UInt32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64,
+         Ptr{Cvoid}),
+        f.handle, d_K, k_strides[1], k_strides[2], d_T, t_strides[1], t_strides[2], kF, beta, lambda, d_bin, bin_base, n_bin, d_weight,
+        coef === nothing ? C_NULL : coef, seed, sample_offset, n_dim, n_grid, d_acc, d_acc2, d_hist, d_hist_bin, B, stream))
     return nothing
 end
 

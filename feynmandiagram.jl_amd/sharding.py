@@ -13,6 +13,8 @@ passes the start of its ``shard_range`` as part of ``sample_offset`` to the samp
 accumulate call (the cells are recomputed from the Philox counter = the global sample index), and the
 training histogram ``d_hist`` (n_dim * n_grid doubles) is summed over the ranks with the same
 ``reduce_observable`` / ``fdg_reduce_device`` call as ``acc``, so every rank refines the same map.
+With a discrete variable (``vegas.vegas_integrate_binned``, fdg_accumulate_device_vegas_binned) the moments are
+``[2, n_bin, R]`` and the variable's histogram ``d_hist_bin`` (n_bin doubles) is reduced as well.
 The reference has no counterpart (single-threaded); downstream users do this
 reduce in MCIntegration.jl.
 

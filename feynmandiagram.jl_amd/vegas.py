@@ -6,6 +6,10 @@ this is (example/benchmark.jl:46-51); MCIntegration is not part of the reference
 An iteration is "draw ``n_sample`` points through a fixed map, evaluate, accumulate": the sampler writes component-major ``(K, T)``
 columns, which the one-kernel Monte-Carlo route reads in place, and the accumulate call leaves the estimate, its second moment and the
 training histogram on the device.  Only the histogram (``n_dim * n_grid`` doubles) and the two moments come to the host per iteration.
+
+A discrete variable (``DiscreteMap``, ``vegas_integrate_binned``; fdg_vegas_sample_device_discrete, fdg_mc_accumulate_device_vegas_binned,
+fdg_vegas_refine_discrete) picks one of ``n_bin`` external configurations per sample -- ``ExtKidx = MCIntegration.Discrete(1, Nk)`` of the
+reference's test/ver4.jl:221-250 -- so that one run fills an observable ``[n_bin, R]`` and trains the variable's probabilities with the map.
 """
 from __future__ import annotations
 
@@ -151,4 +155,145 @@ def vegas_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: 
             out.histograms.append(h)
             vmap.refine(h, alpha)
     out.mean, out.stderr, out.chi2_dof = combine(out.iterations[int(n_discard):])
+    return out
+
+
+def uniform_cdf(n_bin: int) -> np.ndarray:
+    """The flat discrete variable: ``cdf[j] = j / n_bin`` for ``j = 0 .. n_bin``, the last entry exactly 1; ``[n_bin + 1]``."""
+    n = int(n_bin)
+    if not (1 <= n <= capi.FDG_BIN_MAX):
+        raise ValueError(f"n_bin must lie in [1, {capi.FDG_BIN_MAX}]")
+    c = np.arange(n + 1, dtype=np.float64) / n
+    c[n] = 1.0
+    return c
+
+
+class DiscreteMap:
+    """A discrete variable on the host (``.cdf``, float64 ``[n_bin + 1]``: 0 .. 1, strictly increasing) and on ``device`` (``.d_cdf``),
+    with the table of what its values mean: ``ext [n_bin, n_ext]`` (``.ext`` / ``.d_ext``), row ``j`` going to the columns ``ext_col`` of
+    a sample that drew value ``j``."""
+
+    def __init__(self, cdf: np.ndarray, ext=None, ext_col: Sequence[int] = (), device="cuda"):
+        import torch
+        c = np.ascontiguousarray(cdf, dtype=np.float64)
+        if c.ndim != 1 or not (2 <= c.shape[0] <= capi.FDG_BIN_MAX + 1):
+            raise ValueError(f"cdf must be [n_bin + 1] with n_bin in [1, {capi.FDG_BIN_MAX}]")
+        if c[0] != 0.0 or c[-1] != 1.0 or not (np.diff(c) > 0).all():
+            raise ValueError("cdf must run from 0 to 1 exactly, strictly increasing")
+        self.cdf = c.copy()
+        self.ext_col = [int(e) for e in ext_col]
+        n_ext = len(self.ext_col)
+        if n_ext > capi.FDG_VEGAS_EXT_MAX or len(set(self.ext_col)) != n_ext or any(e < 0 for e in self.ext_col):
+            raise ValueError(f"ext_col must name at most {capi.FDG_VEGAS_EXT_MAX} distinct columns")
+        if (ext is None) != (n_ext == 0):
+            raise ValueError("ext and ext_col go together")
+        self.ext = None
+        if ext is not None:
+            e = np.ascontiguousarray(ext, dtype=np.float64)
+            if e.shape != (self.n_bin, n_ext):
+                raise ValueError(f"ext must be [{self.n_bin}, {n_ext}]: one row per value, one column per ext_col")
+            self.ext = e.copy()
+        self.device = torch.device(device)
+        self.d_cdf = torch.from_numpy(self.cdf).to(self.device)
+        self.d_ext = None if self.ext is None else torch.from_numpy(self.ext).to(self.device)
+
+    @property
+    def n_bin(self) -> int:
+        return self.cdf.shape[0] - 1
+
+    @property
+    def prob(self) -> np.ndarray:
+        """``p_j = cdf[j + 1] - cdf[j]``: what the sampler divides the weight by"""
+        return self.cdf[1:] - self.cdf[:-1]
+
+    def refine(self, hist_bin, alpha: float = 0.5, floor: float = 0.05) -> "DiscreteMap":
+        """Moves the probabilities by the training histogram ``hist_bin [n_bin]`` (a CUDA tensor or a host array) through
+        ``fdg_vegas_refine_discrete`` and uploads them; a failed refinement leaves both copies as they were."""
+        h = hist_bin.detach().cpu().numpy() if hasattr(hist_bin, "detach") else np.asarray(hist_bin, dtype=np.float64)
+        capi.vegas_refine_discrete(self.cdf, h, alpha, floor)
+        self.d_cdf.copy_(self.d_cdf.new_tensor(self.cdf))
+        return self
+
+
+@dataclass
+class VegasBinnedResult:
+    mean: np.ndarray                 # [n_bin, R] inverse-variance combination of the iterations kept, per (bin, root)
+    stderr: np.ndarray               # [n_bin, R]
+    chi2_dof: np.ndarray             # [n_bin, R]
+    iterations: List[Tuple[np.ndarray, np.ndarray]] = field(default_factory=list)   # (mean, stderr) [n_bin, R] of every iteration
+    map: Optional[VegasMap] = None
+    dmap: Optional[DiscreteMap] = None
+    histograms: List[np.ndarray] = field(default_factory=list)                       # [n_dim, n_grid] of every iteration
+    bin_histograms: List[np.ndarray] = field(default_factory=list)                   # [n_bin] of every iteration
+
+
+def vegas_integrate_binned(func_or_handle, tables, lo, hi, col, dmap: DiscreteMap, kF: float = 0.0, beta: float = 1.0, lam: float = 0.0, *,
+                           n_iter: int = 10, n_sample: int = 100_000, n_grid: int = 64, alpha: float = 0.5, floor: float = 0.05, seed: int = 0,
+                           n_discard: int = 0, fixed=None, coef=None, device="cuda", vmap: Optional[VegasMap] = None,
+                           specialize_fused: bool = True, n_total: Optional[int] = None, shard_start: int = 0,
+                           reduce: Optional[Callable] = None) -> VegasBinnedResult:
+    """:func:`vegas_integrate` with a discrete variable: every sample draws a value ``j`` of ``dmap`` next to its continuous variables,
+    the columns ``dmap.ext_col`` take row ``j`` of ``dmap.ext`` (external momenta), and the estimate is per value: arrays ``[n_bin, R]``,
+    bin ``j`` the integral over the continuous variables at configuration ``j`` (the weight carries ``1 / p_j``, and ``mc_estimate``
+    takes the whole batch as ``N``).  Per iteration: sample, accumulate (binned moments and both training histograms in one pass),
+    ``mc_estimate``, refine the map with ``alpha`` and the probabilities with ``alpha`` and ``floor``.  ``combine`` is per (bin, root).
+    Sharding as in :func:`vegas_integrate`; ``reduce`` is applied to the moments ``[2, n_bin, R]`` and to both histograms, so every rank
+    refines the same maps."""
+    import torch
+    handle = getattr(func_or_handle, "handle", func_or_handle)
+    device = torch.device(device)
+    n_col_k, n_tau = int(tables.n_loop) * int(tables.dim), int(tables.n_tau)
+    n_col, R = n_col_k + n_tau, handle.table.n_root
+    col = [int(c) for c in col]
+    if len(set(col)) != len(col) or not all(0 <= c < n_col for c in col):
+        raise ValueError(f"col must name distinct columns in [0, {n_col})")
+    if not all(0 <= e < n_col for e in dmap.ext_col) or set(dmap.ext_col) & set(col):
+        raise ValueError(f"dmap.ext_col must name columns in [0, {n_col}) that col does not")
+    if dmap.device != device:
+        raise ValueError("dmap lives on another device")
+    if vmap is None:
+        vmap = VegasMap(uniform_grid(lo, hi, n_grid), device)
+    if vmap.n_dim != len(col):
+        raise ValueError("one column per variable of the map")
+    D, G, NB = vmap.n_dim, vmap.n_grid, dmap.n_bin
+    B = int(n_sample)
+    N = B if n_total is None else int(n_total)
+    if B < 1 or N < 2 or n_iter < 1 or not (0 <= n_discard < n_iter):
+        raise ValueError("need n_sample >= 1, n_total >= 2 and 0 <= n_discard < n_iter")
+    if specialize_fused:
+        handle.specialize_fused(tables)
+    fx = np.zeros(n_col) if fixed is None else np.asarray(fixed, dtype=np.float64)
+    if fx.shape != (n_col,):
+        raise ValueError(f"fixed must hold {n_col} column values")
+    with torch.cuda.device(device):
+        st = torch.cuda.current_stream(device).cuda_stream
+        x = torch.from_numpy(fx).to(device)[:, None].repeat(1, B).contiguous()          # [n_col, B]: sample stride 1
+        jac = torch.empty(B, dtype=torch.float64, device=device)
+        bins = torch.empty(B, dtype=torch.int32, device=device)
+        d_T = x.data_ptr() + 8 * n_col_k * B
+        d_ext = 0 if dmap.d_ext is None else dmap.d_ext.data_ptr()
+        out = VegasBinnedResult(np.zeros((NB, R)), np.zeros((NB, R)), np.full((NB, R), np.nan), map=vmap, dmap=dmap)
+        for it in range(int(n_iter)):
+            off = it * N + int(shard_start)
+            capi.vegas_sample_device_discrete(vmap.d_grid.data_ptr(), D, G, col, dmap.d_cdf.data_ptr(), NB, 0, d_ext, dmap.ext_col, seed, off,
+                                              x.data_ptr(), 1, B, jac.data_ptr(), bins.data_ptr(), 0, B, st)
+            m = torch.zeros((2, NB, R), dtype=torch.float64, device=device)
+            hist = torch.zeros((D, G), dtype=torch.float64, device=device)
+            hist_bin = torch.zeros(NB, dtype=torch.float64, device=device)
+            handle.mc_accumulate_device_vegas_binned(x.data_ptr(), 1, B, d_T, 1, B, kF, beta, lam, bins.data_ptr(), 0, NB, jac.data_ptr(), coef,
+                                                     seed, off, D, G, m[0].data_ptr(), m[1].data_ptr(), hist.data_ptr(), hist_bin.data_ptr(),
+                                                     B, st)
+            if reduce is not None:
+                reduce(m)
+                reduce(hist)
+                reduce(hist_bin)
+            mean, err = mc_estimate(m[0], m[1], N)
+            h, hb = hist.cpu().numpy(), hist_bin.cpu().numpy()
+            out.iterations.append((mean.cpu().numpy(), err.cpu().numpy()))
+            out.histograms.append(h)
+            out.bin_histograms.append(hb)
+            vmap.refine(h, alpha)
+            dmap.refine(hb, alpha, floor)
+    mean, err, chi2 = combine(out.iterations[int(n_discard):])
+    out.mean, out.stderr, out.chi2_dof = mean.reshape(NB, R), err.reshape(NB, R), chi2.reshape(NB, R)
     return out

@@ -633,6 +633,74 @@ int fdg_mc_accumulate_device_vegas(fdg_graph *g, const double *d_K, int64_t k_sa
  * alpha in [0, 2] (0: the grid comes back unchanged; FDG_E_INVALID outside).  On any error the grid is untouched. */
 int fdg_vegas_refine(double *grid, const double *hist, uint32_t n_dim, uint32_t n_grid, double alpha);
 
+/* ---- A discrete external variable for VEGAS, and binned observables --------------------------------------------------------------
+ * The reference integrates its vertex function over (K, T, ExtKidx) with ExtKidx = MCIntegration.Discrete(1, Nk): the variable picks one
+ * of Nk external-momentum configurations, the external legs are looked up from it, the observable is one estimate per configuration,
+ * and the variable's probabilities are trained like the continuous map (test/ver4.jl:221-250; example/strong_coupling_expansion/).
+ * MCIntegration is not part of the reference checkout: no counterpart in the reference; the caller's side of test/ver4.jl:224-237.
+ *
+ * The variable has n_bin values, 1 <= n_bin <= FDG_BIN_MAX, a cumulative distribution cdf[0 .. n_bin] with cdf[0] == 0,
+ * cdf[n_bin] == 1 exactly and strictly increasing (every value has probability > 0), and an optional table ext[n_bin][n_ext],
+ * 0 <= n_ext <= FDG_VEGAS_EXT_MAX, of what the value means for the integrand: row j is copied into the columns ext_col[0 .. n_ext) of
+ * the sample's x (the components of the external momenta).
+ *
+ * fdg_vegas_sample_device_discrete: for sample b < n_sample, every step one rounded fp64 operation,
+ *     the continuous variables d < n_dim exactly as fdg_vegas_sample_device (the same x bits in the same columns, the same d_cell);
+ *     jc = the value that call writes to d_jac[b]
+ *     u  = the uniform of Philox counter (sample_offset + b, n_dim), key seed: the column behind the continuous ones, so adding the
+ *          discrete variable moves no continuous sample
+ *     j  = the number of interior edges cdf[1 .. n_bin - 1] that are <= u
+ *     p  = cdf[j + 1] - cdf[j];   jc / p -> d_jac[b];   j + bin_base -> d_bin[b];   ext[j][e] -> d_x[b * x_sample_stride + ext_col[e] * x_col_stride]
+ * d_cdf (n_bin + 1 doubles) and d_ext (n_bin x n_ext doubles, row-major) are device memory; ext_col a HOST array of n_ext column numbers;
+ * n_ext == 0: d_ext and ext_col may be NULL.  n_bin == 1 gives fdg_vegas_sample_device's x and jac bit for bit and d_bin = bin_base.
+ * FDG_E_INVALID: a NULL d_grid, d_cdf, d_x, d_jac or d_bin, n_sample < 0, n_dim, n_grid or n_bin 0, n_ext > 0 without d_ext or ext_col,
+ * an ext_col that repeats or names a column of col; FDG_E_UNSUPPORTED: the limits exceeded.  All before any device work.  The result is
+ * a function of the arguments only (counter-based), so shards reproduce the unsharded batch.  The cdf is not read on the host: what it
+ * must satisfy is the caller's to keep (fdg_vegas_refine_discrete does).  Neither is the width of x an argument: that every column
+ * col and ext_col name exists in d_x is the caller's to keep as well, as in fdg_vegas_sample_device. */
+#define FDG_VEGAS_EXT_MAX 16
+int fdg_vegas_sample_device_discrete(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, const double *d_cdf,
+                                     uint32_t n_bin, int32_t bin_base, const double *d_ext, uint32_t n_ext, const uint32_t *ext_col,
+                                     uint64_t seed, uint64_t sample_offset, double *d_x, int64_t x_sample_stride, int64_t x_col_stride,
+                                     double *d_jac, int32_t *d_bin, int32_t *d_cell, int64_t n_sample, void *stream);
+/* The accumulate step with the discrete variable: binned moments and the training of both maps in one pass over the roots (the roots
+ * of a chunk are evaluated once).
+ *   d_acc, d_acc2 (n_bin x n_root, added to): bit for bit what fdg_accumulate_device_moments / fdg_mc_accumulate_device_moments leave for
+ *     the same d_bin, bin_base, n_bin, weights and samples.
+ *   d_hist (n_dim x n_grid, added to): the continuous training histogram of fdg_accumulate_device_vegas over the samples whose bin lies
+ *     in [bin_base, bin_base + n_bin); when every sample's does, bit for bit what that call leaves for the same arguments (its cut
+ *     depends on n_root, not on n_bin).
+ *   d_hist_bin (n_bin doubles, added to; NULL: the discrete variable is not trained): d_hist_bin[j] += t * t over the samples of bin j,
+ *     t = w_b * ((c_k0 * r_k0) + (c_k1 * r_k1) + ...) exactly as fdg_accumulate_device_vegas forms it.
+ * A sample whose bin is out of range adds nothing to any of the four (it enters no sum: selected away, never multiplied by zero).  No float atomics:
+ * d_hist_bin is bitwise reproducible for the same arguments on the same device, and the order of its sums depends on (n_sample, n_bin,
+ * n_dim, n_grid, n_root, FDG_ROOT_SCRATCH_MB) only.  Errors: those of the moments calls and of the VEGAS calls; any two
+ * of the four output arrays the same buffer, d_bin NULL (use the call without a discrete variable): FDG_E_INVALID.  All before any
+ * device work. */
+int fdg_accumulate_device_vegas_binned(fdg_graph *g, const double *d_leaf, int64_t leaf_sample_stride, int64_t leaf_leaf_stride,
+                                       int64_t leaf_tile_stride, const int32_t *d_bin, int32_t bin_base, uint32_t n_bin,
+                                       const double *d_weight, const double *coef, uint64_t seed, uint64_t sample_offset, uint32_t n_dim,
+                                       uint32_t n_grid, double *d_acc, double *d_acc2, double *d_hist, double *d_hist_bin,
+                                       int64_t n_sample, void *stream);
+int fdg_mc_accumulate_device_vegas_binned(fdg_graph *g, const double *d_K, int64_t k_sample_stride, int64_t k_comp_stride,
+                                          const double *d_T, int64_t t_sample_stride, int64_t t_comp_stride, double kF, double beta,
+                                          double lambda, const int32_t *d_bin, int32_t bin_base, uint32_t n_bin, const double *d_weight,
+                                          const double *coef, uint64_t seed, uint64_t sample_offset, uint32_t n_dim, uint32_t n_grid,
+                                          double *d_acc, double *d_acc2, double *d_hist, double *d_hist_bin, int64_t n_sample,
+                                          void *stream);
+/* The refinement of the discrete variable's probabilities from its training histogram (both HOST arrays; host only), in fp64, in this order:
+ *  1. p_j = cdf[j + 1] - cdf[j].  A negative or non-finite histogram entry, alpha outside [0, 2], floor outside [0, 1), or a cdf that
+ *     does not run 0 .. 1 strictly increasing: FDG_E_INVALID.
+ *  2. q_j = hist_bin[j] * p_j; sum(q) (left fold) <= 0, alpha == 0 or n_bin == 1: the cdf comes back unchanged.
+ *  3. s_j = q_j / sum(q);  w_j = s_j ^ alpha, 0 for s_j = 0.
+ *  4. p'_j = ((1 - floor) * w_j) / sum(w) + floor / n_bin   (sum(w) a left fold).
+ *  5. cdf' = the left-fold running sum of p', cdf'[0] = 0, cdf'[n_bin] = 1 exactly.
+ *  6. cdf' is strictly increasing, or FDG_E_INTERNAL is returned.  On any error cdf is untouched.
+ * The expected hist_bin[j] is N * I2_j / p_j with I2_j the integral of (f_j * jac_c)^2, so q_j is proportional to I2_j whatever the
+ * current p: the iteration has one fixed point, at alpha = 1/2 p_j ~ sqrt(I2_j), which minimises the sum over the bins of the second
+ * moments I2_j / p_j.  floor keeps every bin sampled (a bin with p = 0 would silently lose its estimate). */
+int fdg_vegas_refine_discrete(double *cdf, const double *hist_bin, uint32_t n_bin, double alpha, double floor);
+
 /* Device workspace control: the interpreter keeps per-sample overflow slots in
  * an HBM panel owned by the handle; it is sized on first use for the number of
  * resident waves.  This releases it (and any loaded module). */
