@@ -19,6 +19,7 @@ reference itself returns a RuntimeGeneratedFunction.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import Dict, Optional, Sequence, Tuple
 
@@ -277,25 +278,14 @@ class GraphFunc:
 
     def accumulate_tiled(self, leaf, weight=None, acc=None, n_sample: Optional[int] = None):
         """``acc[k] += sum_b weight[b] * root_k(b)`` over a tile-major leaf batch (``weight``: plain vector indexed by sample)."""
-        import torch
         self._check_tiled(leaf, self.n_leaf, "leaf")
         B = 64 * leaf.shape[0] if n_sample is None else int(n_sample)
         if not (0 <= B <= 64 * leaf.shape[0]):
             raise ValueError("n_sample exceeds the batch")
-        if acc is None:
-            acc = torch.zeros(self.n_root, dtype=torch.float64, device=leaf.device)
-        if (not acc.is_cuda or acc.device != leaf.device or acc.dtype != torch.float64 or not acc.is_contiguous()
-                or acc.numel() < self.n_root):
-            raise ValueError("acc must be a contiguous float64 tensor of at least n_root elements on the leaves' device")
-        w = 0
-        if weight is not None:
-            if (not weight.is_cuda or weight.device != leaf.device or weight.dtype != torch.float64 or weight.dim() != 1
-                    or weight.shape[0] < B):
-                raise ValueError("weight must be a float64 vector of at least n_sample elements on the leaves' device")
-            weight = weight.contiguous()
-            w = weight.data_ptr()
-        st = torch.cuda.current_stream(leaf.device).cuda_stream
-        with torch.cuda.device(leaf.device):
+        acc = self._out(acc, (self.n_root,), leaf, "acc", at_least=True)
+        weight = self._weight(weight, B, leaf)
+        w = 0 if weight is None else weight.data_ptr()
+        with self._stream(leaf) as st:
             self.handle.accumulate_device_tiled(leaf.data_ptr(), leaf.stride(2), leaf.stride(1), leaf.stride(0), w, acc.data_ptr(), B, st)
         return acc
 
@@ -305,12 +295,10 @@ class GraphFunc:
         nothing).  ``leaf`` is a float64 ``[B, L]`` CUDA tensor (any strides) or a tile-major ``(T, L, 64)`` batch (as
         :meth:`accumulate_tiled` takes it); ``bins`` an int32 CUDA vector and ``weight`` a float64 one, both indexed by sample; ``acc`` a
         contiguous float64 ``[n_bin, R]`` tensor (zeros when omitted), returned.  Deterministic: no float atomics (fdg_accumulate_device_binned)."""
-        import torch
         B, n_bin, bins, weight, strides = self._binned_args(leaf, bins, n_bin, weight, n_sample)
         w = 0 if weight is None else weight.data_ptr()
-        acc = self._bin_acc(acc, n_bin, leaf, "acc")
-        st = torch.cuda.current_stream(leaf.device).cuda_stream
-        with torch.cuda.device(leaf.device):
+        acc = self._out(acc, (n_bin, self.n_root), leaf, "acc")
+        with self._stream(leaf) as st:
             self.handle.accumulate_device_binned(leaf.data_ptr(), *strides, bins.data_ptr(), int(bin_base), n_bin, w, acc.data_ptr(), B, st)
         return acc
 
@@ -321,15 +309,12 @@ class GraphFunc:
         ``n_bin`` must be 1.  ``acc`` comes out with the bits :meth:`accumulate_binned` gives for the same arguments (an all-zero
         ``bins`` for ``bins=None``).  Returns ``(acc, acc2)``, two float64 ``[n_bin, R]`` tensors (zeros when omitted), added to.
         :func:`mc_estimate` turns them into a mean and a standard error (fdg_accumulate_device_moments)."""
-        import torch
         B, n_bin, bins, weight, strides = self._binned_args(leaf, bins, n_bin, weight, n_sample, bins_optional=True)
         w = 0 if weight is None else weight.data_ptr()
-        acc = self._bin_acc(acc, n_bin, leaf, "acc")
-        acc2 = self._bin_acc(acc2, n_bin, leaf, "acc2")
-        if acc.data_ptr() == acc2.data_ptr():
-            raise ValueError("acc and acc2 must be different tensors")
-        st = torch.cuda.current_stream(leaf.device).cuda_stream
-        with torch.cuda.device(leaf.device):
+        acc = self._out(acc, (n_bin, self.n_root), leaf, "acc")
+        acc2 = self._out(acc2, (n_bin, self.n_root), leaf, "acc2")
+        self._distinct("acc and acc2", acc, acc2)
+        with self._stream(leaf) as st:
             self.handle.accumulate_device_moments(leaf.data_ptr(), *strides, 0 if bins is None else bins.data_ptr(), int(bin_base), n_bin,
                                                   w, acc.data_ptr(), acc2.data_ptr(), B, st)
         return acc, acc2
@@ -342,23 +327,14 @@ class GraphFunc:
         ``capi.vegas_sample_device`` drew the samples with.  ``hist``: a contiguous float64 ``[n_dim, n_grid]`` CUDA tensor, added to
         (zeros when None); ``coef``: host sequence of ``n_root`` factors or None (the plain sum of the roots).  Returns
         ``(acc, acc2, hist)``.  Deterministic: no float atomics (fdg_accumulate_device_vegas)."""
-        import torch
         B, _, _, weight, strides = self._binned_args(leaf, None, 1, weight, n_sample, bins_optional=True)
-        n_dim, n_grid = int(n_dim), int(n_grid)
-        if not (1 <= n_dim <= capi.FDG_VEGAS_DIM_MAX and 1 <= n_grid <= capi.FDG_VEGAS_GRID_MAX):
-            raise ValueError(f"n_dim must lie in [1, {capi.FDG_VEGAS_DIM_MAX}] and n_grid in [1, {capi.FDG_VEGAS_GRID_MAX}]")
+        n_dim, n_grid = self._vegas_map(n_dim, n_grid)
         w = 0 if weight is None else weight.data_ptr()
-        acc = self._bin_acc(acc, 1, leaf, "acc")
-        acc2 = self._bin_acc(acc2, 1, leaf, "acc2")
-        if hist is None:
-            hist = torch.zeros((n_dim, n_grid), dtype=torch.float64, device=leaf.device)
-        if (not _is_torch(hist) or not hist.is_cuda or hist.device != leaf.device or hist.dtype != torch.float64 or not hist.is_contiguous()
-                or tuple(hist.shape) != (n_dim, n_grid)):
-            raise ValueError(f"hist must be a contiguous float64 [{n_dim}, {n_grid}] tensor on the leaves' device")
-        if len({acc.data_ptr(), acc2.data_ptr(), hist.data_ptr()}) != 3:
-            raise ValueError("acc, acc2 and hist must be different tensors")
-        st = torch.cuda.current_stream(leaf.device).cuda_stream
-        with torch.cuda.device(leaf.device):
+        acc = self._out(acc, (1, self.n_root), leaf, "acc")
+        acc2 = self._out(acc2, (1, self.n_root), leaf, "acc2")
+        hist = self._out(hist, (n_dim, n_grid), leaf, "hist")
+        self._distinct("acc, acc2 and hist", acc, acc2, hist)
+        with self._stream(leaf) as st:
             self.handle.accumulate_device_vegas(leaf.data_ptr(), *strides, w, coef, int(seed), int(sample_offset), n_dim, n_grid,
                                                 acc.data_ptr(), acc2.data_ptr(), hist.data_ptr(), B, st)
         return acc, acc2, hist
@@ -371,29 +347,18 @@ class GraphFunc:
         ``vegas.DiscreteMap.refine`` takes.  ``hist``: contiguous float64 ``[n_dim, n_grid]``, ``hist_bin``: contiguous float64 ``[n_bin]``,
         both CUDA tensors, added to (zeros when None; ``train_bins=False``: no ``hist_bin``, None is returned for it).  The roots of a chunk
         are evaluated once.  Returns ``(acc, acc2, hist, hist_bin)``.  Deterministic: no float atomics (fdg_accumulate_device_vegas_binned)."""
-        import torch
         B, n_bin, bins, weight, strides = self._binned_args(leaf, bins, n_bin, weight, n_sample)
-        n_dim, n_grid = int(n_dim), int(n_grid)
-        if not (1 <= n_dim <= capi.FDG_VEGAS_DIM_MAX and 1 <= n_grid <= capi.FDG_VEGAS_GRID_MAX):
-            raise ValueError(f"n_dim must lie in [1, {capi.FDG_VEGAS_DIM_MAX}] and n_grid in [1, {capi.FDG_VEGAS_GRID_MAX}]")
+        n_dim, n_grid = self._vegas_map(n_dim, n_grid)
         w = 0 if weight is None else weight.data_ptr()
-        acc = self._bin_acc(acc, n_bin, leaf, "acc")
-        acc2 = self._bin_acc(acc2, n_bin, leaf, "acc2")
-        if hist is None:
-            hist = torch.zeros((n_dim, n_grid), dtype=torch.float64, device=leaf.device)
-        if hist_bin is None and train_bins:
-            hist_bin = torch.zeros(n_bin, dtype=torch.float64, device=leaf.device)
-        for h, shape, what in ((hist, (n_dim, n_grid), "hist"), (hist_bin, (n_bin,), "hist_bin")):
-            if h is not None and (not _is_torch(h) or not h.is_cuda or h.device != leaf.device or h.dtype != torch.float64
-                                  or not h.is_contiguous() or tuple(h.shape) != shape):
-                raise ValueError(f"{what} must be a contiguous float64 {list(shape)} tensor on the leaves' device")
+        acc = self._out(acc, (n_bin, self.n_root), leaf, "acc")
+        acc2 = self._out(acc2, (n_bin, self.n_root), leaf, "acc2")
+        hist = self._out(hist, (n_dim, n_grid), leaf, "hist")
+        if hist_bin is not None or train_bins:            # (a hist_bin given with train_bins=False is checked, then left alone)
+            hist_bin = self._out(hist_bin, (n_bin,), leaf, "hist_bin")
         if not train_bins:
             hist_bin = None
-        outs = [acc, acc2, hist] + ([] if hist_bin is None else [hist_bin])
-        if len({o.data_ptr() for o in outs}) != len(outs):
-            raise ValueError("acc, acc2, hist and hist_bin must be different tensors")
-        st = torch.cuda.current_stream(leaf.device).cuda_stream
-        with torch.cuda.device(leaf.device):
+        self._distinct("acc, acc2, hist and hist_bin", acc, acc2, hist, hist_bin)
+        with self._stream(leaf) as st:
             self.handle.accumulate_device_vegas_binned(leaf.data_ptr(), *strides, bins.data_ptr(), int(bin_base), n_bin, w, coef, int(seed),
                                                        int(sample_offset), n_dim, n_grid, acc.data_ptr(), acc2.data_ptr(), hist.data_ptr(),
                                                        0 if hist_bin is None else hist_bin.data_ptr(), B, st)
@@ -430,22 +395,55 @@ class GraphFunc:
             if bins.dim() != 1 or bins.shape[0] < B or bins.device != leaf.device:
                 raise ValueError("bins must be an int32 vector of at least n_sample elements on the leaves' device")
             bins = bins.contiguous()
-        if weight is not None:
-            if (not _is_torch(weight) or not weight.is_cuda or weight.device != leaf.device or weight.dtype != torch.float64
-                    or weight.dim() != 1 or weight.shape[0] < B):
-                raise ValueError("weight must be a float64 vector of at least n_sample elements on the leaves' device")
-            weight = weight.contiguous()
+        weight = self._weight(weight, B, leaf)
         strides = (leaf.stride(2), leaf.stride(1), leaf.stride(0)) if tiled else (leaf.stride(0), leaf.stride(1), 0)
         return B, n_bin, bins, weight, strides
 
-    def _bin_acc(self, acc, n_bin, leaf, what):
+    def _out(self, x, shape, leaf, what, at_least=False):
+        """An output of the ``accumulate_*`` methods: ``x`` checked as a contiguous float64 CUDA tensor of ``shape`` on the leaves'
+        device, zeros when None.  ``at_least`` (:meth:`accumulate_tiled`): any shape of at least ``n_root`` elements."""
         import torch
-        if acc is None:
-            acc = torch.zeros((n_bin, self.n_root), dtype=torch.float64, device=leaf.device)
-        if (not _is_torch(acc) or not acc.is_cuda or acc.device != leaf.device or acc.dtype != torch.float64 or not acc.is_contiguous()
-                or tuple(acc.shape) != (n_bin, self.n_root)):
-            raise ValueError(f"{what} must be a contiguous float64 [{n_bin}, {self.n_root}] tensor on the leaves' device")
-        return acc
+        if x is None:
+            x = torch.zeros(shape, dtype=torch.float64, device=leaf.device)
+        if (not _is_torch(x) or not x.is_cuda or x.device != leaf.device or x.dtype != torch.float64 or not x.is_contiguous()
+                or (x.numel() < self.n_root if at_least else tuple(x.shape) != shape)):
+            size = "tensor of at least n_root elements" if at_least else f"{list(shape)} tensor"
+            raise ValueError(f"{what} must be a contiguous float64 {size} on the leaves' device")
+        return x
+
+    @staticmethod
+    def _weight(weight, B, leaf):
+        """``weight`` checked as a float64 vector of at least ``B`` elements on the leaves' device and made contiguous (None stays None)."""
+        import torch
+        if weight is None:
+            return None
+        if (not _is_torch(weight) or not weight.is_cuda or weight.device != leaf.device or weight.dtype != torch.float64
+                or weight.dim() != 1 or weight.shape[0] < B):
+            raise ValueError("weight must be a float64 vector of at least n_sample elements on the leaves' device")
+        return weight.contiguous()
+
+    @staticmethod
+    def _vegas_map(n_dim, n_grid):
+        n_dim, n_grid = int(n_dim), int(n_grid)
+        if not (1 <= n_dim <= capi.FDG_VEGAS_DIM_MAX and 1 <= n_grid <= capi.FDG_VEGAS_GRID_MAX):
+            raise ValueError(f"n_dim must lie in [1, {capi.FDG_VEGAS_DIM_MAX}] and n_grid in [1, {capi.FDG_VEGAS_GRID_MAX}]")
+        return n_dim, n_grid
+
+    @staticmethod
+    def _distinct(names, *outs):
+        """No two of the output tensors (None: not given) may start at the same address."""
+        outs = [o for o in outs if o is not None]
+        if len({o.data_ptr() for o in outs}) != len(outs):
+            raise ValueError(f"{names} must be different tensors")
+
+    @staticmethod
+    @contextlib.contextmanager
+    def _stream(leaf):
+        """The leaves' device made current for the call; yields the raw handle of its current stream."""
+        import torch
+        st = torch.cuda.current_stream(leaf.device).cuda_stream
+        with torch.cuda.device(leaf.device):
+            yield st
 
     def _call_numpy_typed(self, root, leaf):
         """Host arrays of an element type other than Float64: staged through the device (there is no CPU evaluator behind the ABI)."""

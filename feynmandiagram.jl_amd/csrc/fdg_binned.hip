@@ -36,6 +36,7 @@
 #include <algorithm>
 #include <cmath>
 #include <mutex>
+#include <utility>
 #include <vector>
 
 #define FDG_RUNTIME_TU 1
@@ -84,6 +85,13 @@ __device__ inline void wave_runs(uint32_t key, uint32_t lane, uint32_t &j, bool 
   end = ok ? (uint32_t)__builtin_ctzll(tails & (~0ull << lane)) : lane;
 }
 
+// The tiles t0 .. t1 - 1 of a chunk of n samples that segment seg of seg_tiles tiles holds, and the rounds its four waves take them in.
+struct SegTiles { long t0, t1, rounds; };
+__device__ inline SegTiles seg_tiles_of(long n, uint32_t seg, long seg_tiles) {
+  const long ntile = (n + 63) / 64, t0 = (long)seg * seg_tiles, t1 = min(t0 + seg_tiles, ntile);
+  return {t0, t1, t1 > t0 ? (t1 - t0 + kBinWaves - 1) / kBinWaves : 0};
+}
+
 // What a workgroup of the pass accumulates: the first moment (the binned call), both moments in one LDS, or one moment per root slice
 // (slices n_slice .. 2 n_slice - 1 are the second moment's; the histograms of both do not fit the LDS).
 enum BinMode { kFirst = 0, kBoth = 1, kSplit = 2 };
@@ -107,8 +115,8 @@ fdg_binned_partials(const double *__restrict__ root, long ld, long n, const int3
     hist[i] = (first || kk >= kn) ? 0.0 : slab[(size_t)j * R + kk];
   }
   __syncthreads();
-  const long ntile = (n + 63) / 64, t0 = (long)seg * seg_tiles, t1 = min(t0 + seg_tiles, ntile);
-  const long rounds = t1 > t0 ? (t1 - t0 + kBinWaves - 1) / kBinWaves : 0;
+  const SegTiles sg = seg_tiles_of(n, seg, seg_tiles);
+  const long t0 = sg.t0, t1 = sg.t1, rounds = sg.rounds;
 
   // this lane's sample of round r, loaded one round ahead without a branch (indices clamped into the chunk: every load is issued at once
   // and stays in flight while the round before is binned); whether the sample adds anything is decided when it is used
@@ -223,22 +231,29 @@ __device__ __forceinline__ uint32_t vegas_cell(uint64_t sample, uint32_t d, uint
 
 struct VegasCols { uint32_t c[FDG_VEGAS_DIM_MAX]; };   // the column of x each variable is written to (a kernel argument, by value)
 
-// One lane per sample, the variables in order (jac is a left fold over them).
+// The continuous variables of sample b, in order: x and the cell of each, and the jacobian (a left fold over them), returned.
+__device__ __forceinline__ double vegas_draw(const double *__restrict__ grid, uint32_t D, uint32_t G, const VegasCols &col, uint64_t seed,
+                                             uint64_t off, double *__restrict__ x, long xs, long xc, int32_t *__restrict__ cell, long n, long b) {
+  double jb = 0.0;
+  for (uint32_t d = 0; d < D; ++d) {
+    double y;
+    const uint32_t c = vegas_cell(off + (uint64_t)b, d, seed, G, y);
+    const double *e = grid + (size_t)d * (G + 1u) + c;
+    const double lo = e[0], wd = e[1] - lo, fr = y - (double)c;
+    x[b * xs + (long)col.c[d] * xc] = lo + fr * wd;
+    const double f = (double)G * wd;
+    jb = d ? jb * f : f;
+    if (cell) cell[(size_t)d * (size_t)n + (size_t)b] = (int32_t)c;
+  }
+  return jb;
+}
+
+// One lane per sample.
 __global__ void __launch_bounds__(256)
 fdg_vegas_sample(const double *__restrict__ grid, uint32_t D, uint32_t G, VegasCols col, uint64_t seed, uint64_t off, double *__restrict__ x,
                  long xs, long xc, double *__restrict__ jac, int32_t *__restrict__ cell, long n) {
   for (long b = blockIdx.x * 256L + threadIdx.x; b < n; b += (long)gridDim.x * 256L) {
-    double jb = 0.0;
-    for (uint32_t d = 0; d < D; ++d) {
-      double y;
-      const uint32_t c = vegas_cell(off + (uint64_t)b, d, seed, G, y);
-      const double *e = grid + (size_t)d * (G + 1u) + c;
-      const double lo = e[0], wd = e[1] - lo, fr = y - (double)c;
-      x[b * xs + (long)col.c[d] * xc] = lo + fr * wd;
-      const double f = (double)G * wd;
-      jb = d ? jb * f : f;
-      if (cell) cell[(size_t)d * (size_t)n + (size_t)b] = (int32_t)c;
-    }
+    const double jb = vegas_draw(grid, D, G, col, seed, off, x, xs, xc, cell, n, b);
     jac[b] = jb;
   }
 }
@@ -253,17 +268,7 @@ fdg_vegas_sample_discrete(const double *__restrict__ grid, uint32_t D, uint32_t 
                           uint64_t off, double *__restrict__ x, long xs, long xc, double *__restrict__ jac, int32_t *__restrict__ bin,
                           int32_t *__restrict__ cell, long n) {
   for (long b = blockIdx.x * 256L + threadIdx.x; b < n; b += (long)gridDim.x * 256L) {
-    double jb = 0.0;
-    for (uint32_t d = 0; d < D; ++d) {
-      double y;
-      const uint32_t c = vegas_cell(off + (uint64_t)b, d, seed, G, y);
-      const double *e = grid + (size_t)d * (G + 1u) + c;
-      const double lo = e[0], wd = e[1] - lo, fr = y - (double)c;
-      x[b * xs + (long)col.c[d] * xc] = lo + fr * wd;
-      const double f = (double)G * wd;
-      jb = d ? jb * f : f;
-      if (cell) cell[(size_t)d * (size_t)n + (size_t)b] = (int32_t)c;
-    }
+    const double jb = vegas_draw(grid, D, G, col, seed, off, x, xs, xc, cell, n, b);
     const double u = fdg_philox_u53(off + (uint64_t)b, D, seed);
     uint32_t lo = 0, hi = n_bin - 1u;                     // j in [lo, hi]: cdf[1 .. lo] <= u < cdf[hi + 1 ..]
     while (lo < hi) {
@@ -318,8 +323,8 @@ fdg_vegas_partials(const double *__restrict__ root, long ld, long n, const doubl
   double *slab = partial + ((size_t)seg * D + d0) * G;
   for (uint32_t i = threadIdx.x; i < dn * G; i += 256) hist[i] = first ? 0.0 : slab[i];
   __syncthreads();
-  const long ntile = (n + 63) / 64, t0 = (long)seg * seg_tiles, t1 = min(t0 + seg_tiles, ntile);
-  const long rounds = t1 > t0 ? (t1 - t0 + kBinWaves - 1) / kBinWaves : 0;
+  const SegTiles sg = seg_tiles_of(n, seg, seg_tiles);
+  const long t0 = sg.t0, t1 = sg.t1, rounds = sg.rounds;
   for (long r = 0; r < rounds; ++r) {
     {
       const long t = t0 + r * (long)kBinWaves + wave, b = t * 64 + lane;
@@ -379,8 +384,8 @@ fdg_vegas_bin_partials(const double *__restrict__ root, long ld, long n, const i
   double *slab = partial + (size_t)seg * n_bin;
   for (uint32_t i = threadIdx.x; i < n_bin; i += 256) hist[i] = first ? 0.0 : slab[i];
   __syncthreads();
-  const long ntile = (n + 63) / 64, t0 = (long)seg * seg_tiles, t1 = min(t0 + seg_tiles, ntile);
-  const long rounds = t1 > t0 ? (t1 - t0 + kBinWaves - 1) / kBinWaves : 0;
+  const SegTiles sg = seg_tiles_of(n, seg, seg_tiles);
+  const long t0 = sg.t0, t1 = sg.t1, rounds = sg.rounds;
   // this lane's sample of round r, formed one round ahead (indices clamped into the chunk; used only where the sample is `in`)
   int32_t bin_n;
   double t_n;
@@ -422,6 +427,46 @@ fdg_vegas_bin_partials(const double *__restrict__ root, long ld, long n, const i
   for (uint32_t i = threadIdx.x; i < n_bin; i += 256) slab[i] = hist[i];
 }
 
+// The training pass of one call, as the entry point was given it (aggregate-initialised there, in this order).
+struct VegasRun {
+  const double *coef = nullptr;      // host, [R] or null
+  uint64_t seed = 0, offset = 0;
+  uint32_t D = 0, G = 0;
+  double *d_hist = nullptr;
+  bool binned = false;               // the calls with a discrete variable: d_bin selects the samples of the training pass too
+  double *d_hist_bin = nullptr;      // ... and, when given, the discrete variable is trained: [n_bin]
+};
+
+// One accumulate call, as the entry point was given it (aggregate-initialised there, in this order): what the checks, the shared body
+// and run_binned read.
+struct BinnedCall {
+  const int32_t *d_bin = nullptr;    // null: every sample in bin 0 (n_bin == 1)
+  int32_t bin_base = 0;
+  uint32_t n_bin = 1;
+  const double *d_weight = nullptr;
+  double *d_acc = nullptr, *d_acc2 = nullptr;     // d_acc2 != null: the second moment too
+  int64_t B = 0;
+  void *stream = nullptr;
+  const VegasRun *vg = nullptr;      // the VEGAS calls: the training pass runs too
+};
+
+constexpr size_t page_up(size_t bytes) { return (bytes + 4095) & ~(size_t)4095; }
+
+// How a chunk of Bc samples is cut into segments for a histogram of hist_bytes that n_grp workgroups per segment share the columns of:
+// at least 16 tiles (four rounds) per workgroup, the partial slab [segment][histogram] within kBinSlabBytes, at most 2048 workgroups.
+// These numbers fix the order of every sum.  slab_alloc: the slab's reservation; it grows with n_sample and the histogram only, so a
+// later call that is not larger allocates nothing.
+struct SegCut {
+  uint32_t n_seg;
+  size_t slab_alloc;
+};
+SegCut seg_cut(long Bc, size_t hist_bytes, long n_grp) {
+  const long by_size = std::max<long>(1, Bc / 64 / 16);
+  const long by_slab = std::max<long>(1, (long)(kBinSlabBytes / hist_bytes));
+  const long by_blocks = std::max<long>(1, 2048 / n_grp);
+  return {(uint32_t)std::min(std::min(by_size, by_slab), by_blocks), std::max(hist_bytes, std::min(kBinSlabBytes, (size_t)by_size * hist_bytes))};
+}
+
 // How one call is cut: chunks of Bc samples through the root scratch, RS roots per slice, n_seg segments per chunk.  mode: what the
 // pass keeps (BinMode); n_slice counts the root slices of one moment.
 struct BinnedPlan {
@@ -433,54 +478,42 @@ struct BinnedPlan {
 
 // moments: the plan of the second-moment call.  Bc and n_seg are the binned call's (its own slice count and slab size), so the first
 // moment is summed in the binned call's order; only the slices (two histograms per workgroup, or one moment per slice) differ.
-BinnedPlan binned_plan(const fdg_graph *g, int64_t B, uint32_t R, uint32_t n_bin, bool moments = false) {
+BinnedPlan binned_plan(const fdg_graph *g, int64_t B, uint32_t R, uint32_t n_bin, bool moments) {
   BinnedPlan p;
   p.Bc = std::max<long>(64, (long)((g->cfg.root_scratch_mb << 20) / (8ull * R)) & ~63l);
   p.Bc = std::min<long>(p.Bc, (long)((B + 63) & ~(int64_t)63));
-  uint32_t rs = 16;
-  while (rs > 1 && (size_t)n_bin * rs * 8u > kBinLdsBudget) rs >>= 1;
-  while (rs > 1 && rs / 2 >= R) rs >>= 1;
-  p.rs = rs;
-  p.n_slice = (R + rs - 1) / rs;
-  p.lds = (size_t)n_bin * rs * 8u;
-  const size_t hist_bytes = (size_t)n_bin * R * 8u;
-  const long by_size = std::max<long>(1, p.Bc / 64 / 16);            // at least 16 tiles (four rounds) per workgroup
-  const long by_slab = std::max<long>(1, (long)(kBinSlabBytes / hist_bytes));
-  const long by_blocks = std::max<long>(1, 2048 / (long)p.n_slice);
-  p.n_seg = (uint32_t)std::min(std::min(by_size, by_slab), by_blocks);
-  // the reservation grows with n_sample and n_bin only, so a later call that is not larger allocates nothing
-  p.slab_alloc = std::max(hist_bytes, std::min(kBinSlabBytes, (size_t)by_size * hist_bytes));
+  // the roots per slice by the LDS budget, for histograms of `bytes` per (bin, root)
+  auto slice = [&](size_t bytes) {
+    uint32_t rs = 16;
+    while (rs > 1 && (size_t)n_bin * rs * bytes > kBinLdsBudget) rs >>= 1;
+    while (rs > 1 && rs / 2 >= R) rs >>= 1;
+    p.rs = rs;
+    p.n_slice = (R + rs - 1) / rs;
+    p.lds = (size_t)n_bin * rs * bytes;
+  };
+  slice(8);
+  const SegCut cut = seg_cut(p.Bc, (size_t)n_bin * R * 8u, p.n_slice);
+  p.n_seg = cut.n_seg;
+  p.slab_alloc = cut.slab_alloc;
   if (moments) {
     p.slab_alloc *= 2;                                                 // [segment][moment][bin][root]
     if ((size_t)n_bin * 16u <= (size_t)FDG_BIN_MAX * 8u) {             // both histograms of one root fit: kBoth, the same budget rule
-      rs = 16;
-      while (rs > 1 && (size_t)n_bin * rs * 16u > kBinLdsBudget) rs >>= 1;
-      while (rs > 1 && rs / 2 >= R) rs >>= 1;
       p.mode = kBoth;
-      p.lds = (size_t)n_bin * rs * 16u;
+      slice(16);
     } else {                                                           // n_bin > 8192: one root of one moment per workgroup
-      rs = 1;
       p.mode = kSplit;
+      p.rs = 1;
+      p.n_slice = R;
       p.lds = (size_t)n_bin * 8u;
     }
-    p.rs = rs;
-    p.n_slice = (R + rs - 1) / rs;
   }
   return p;
 }
 
-// The training pass of one call: what the entry point was given, and how the pass is cut.  Variables per slice by the binned plan's LDS
-// budget (whole histograms of G cells), spread evenly over the slices; segments by the binned plan's three bounds with the histogram
-// [variable][cell] in the place of [bin][root].  A function of (n_sample, n_dim, n_grid, n_root, FDG_ROOT_SCRATCH_MB) only.
-struct VegasRun {
-  const double *coef = nullptr;      // host, [R] or null
-  uint64_t seed = 0, offset = 0;
-  uint32_t D = 0, G = 0;
-  double *d_hist = nullptr;
-  bool binned = false;               // the calls with a discrete variable: d_bin selects the samples of the training pass too
-  double *d_hist_bin = nullptr;      // ... and, when given, the discrete variable is trained: [n_bin]
-};
-// bin_*: the discrete variable's slice (fdg_vegas_bin_partials), segments by the same three bounds with the histogram [bin]; a function
+// How the training pass is cut.  Variables per slice by the binned plan's LDS budget (whole histograms of G cells), spread evenly over
+// the slices; segments by the binned plan's cut with the histogram [variable][cell] in the place of [bin][root].  A function of
+// (n_sample, n_dim, n_grid, n_root, FDG_ROOT_SCRATCH_MB) only.
+// bin_*: the discrete variable's slice (fdg_vegas_bin_partials), segments by the same cut with the histogram [bin]; a function
 // of (n_sample, n_bin, n_root, FDG_ROOT_SCRATCH_MB) that leaves the continuous variables' cut as it is.
 struct VegasPlan {
   uint32_t ds = 1, n_slice = 1, n_seg = 1, bin_seg = 1;
@@ -494,79 +527,82 @@ VegasPlan vegas_plan(const BinnedPlan &p, const VegasRun &v, uint32_t R, uint32_
   q.ds = (v.D + q.n_slice - 1) / q.n_slice;
   q.n_slice = (v.D + q.ds - 1) / q.ds;
   q.lds = ((size_t)q.ds * v.G + 2u * kBinWaves * 64u) * 8u;
-  const size_t hist_bytes = (size_t)v.D * v.G * 8u;
-  const long by_size = std::max<long>(1, p.Bc / 64 / 16);
-  const long by_slab = std::max<long>(1, (long)(kBinSlabBytes / hist_bytes));
-  const long by_blocks = std::max<long>(1, 2048 / (long)q.n_slice);
-  q.n_seg = (uint32_t)std::min(std::min(by_size, by_slab), by_blocks);
-  q.slab_alloc = (std::max(hist_bytes, std::min(kBinSlabBytes, (size_t)by_size * hist_bytes)) + 4095) & ~(size_t)4095;
-  q.list_bytes = ((size_t)R * 12u + 4095) & ~(size_t)4095;      // coef[R] doubles, then kidx[R]
+  const SegCut cut = seg_cut(p.Bc, (size_t)v.D * v.G * 8u, q.n_slice);
+  q.n_seg = cut.n_seg;
+  q.slab_alloc = page_up(cut.slab_alloc);
+  q.list_bytes = page_up((size_t)R * 12u);                       // coef[R] doubles, then kidx[R]
   if (v.d_hist_bin) {
-    const size_t bin_bytes = (size_t)n_bin * 8u;
-    q.bin_seg = (uint32_t)std::min(std::min(by_size, std::max<long>(1, (long)(kBinSlabBytes / bin_bytes))), 2048l);
-    q.bin_slab_alloc = (std::max(bin_bytes, std::min(kBinSlabBytes, (size_t)by_size * bin_bytes)) + 4095) & ~(size_t)4095;
+    const SegCut bin_cut = seg_cut(p.Bc, (size_t)n_bin * 8u, 1);
+    q.bin_seg = bin_cut.n_seg;
+    q.bin_slab_alloc = page_up(bin_cut.slab_alloc);
   }
   return q;
 }
 
-template <int RS, int MODE>
-int launch_partials(const BinnedPlan &p, const double *roots, long n, const int32_t *bins, int32_t bin_base, uint32_t n_bin,
-                    const double *weight, uint32_t R, double *partial, int first, hipStream_t st) {
-  static std::once_flag lds_once;           // (histograms above 64 KiB: one root of up to FDG_BIN_MAX bins, 128 KiB of the CU's 160)
-  std::call_once(lds_once, [] {
-    (void)hipFuncSetAttribute((const void *)fdg_binned_partials<RS, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(FDG_BIN_MAX * 8));
+// The instance of the binned pass a plan asks for.
+using PartialsKernel = void (*)(const double *, long, long, const int32_t *, int32_t, uint32_t, const double *, uint32_t, uint32_t, long,
+                                double *, int);
+
+template <int MODE>
+PartialsKernel partials_kernel_rs(uint32_t rs) {
+  switch (rs) {
+    case 1: return fdg_binned_partials<1, MODE>;
+    case 2: return fdg_binned_partials<2, MODE>;
+    case 4: return fdg_binned_partials<4, MODE>;
+    case 8: return fdg_binned_partials<8, MODE>;
+    default: return fdg_binned_partials<16, MODE>;
+  }
+}
+
+PartialsKernel partials_kernel(const BinnedPlan &p) {
+  if (p.mode == kBoth) return partials_kernel_rs<kBoth>(p.rs);
+  if (p.mode == kSplit) return fdg_binned_partials<1, kSplit>;
+  return partials_kernel_rs<kFirst>(p.rs);
+}
+
+// Lets every pass ask for more than the default 64 KiB of dynamic LDS: a histogram slice of one root of up to FDG_BIN_MAX bins
+// (128 KiB of the CU's 160), and the training pass's kBinLdsBudget plus its exchange buffers.
+void raise_lds_limits() {
+  static std::once_flag once;
+  std::call_once(once, [] {
+    const int hist = (int)(FDG_BIN_MAX * 8), train = (int)(kBinLdsBudget + 2u * kBinWaves * 64u * 8u);
+    std::vector<std::pair<const void *, int>> limits = {{(const void *)fdg_binned_partials<1, kSplit>, hist},
+                                                        {(const void *)fdg_vegas_bin_partials, hist},
+                                                        {(const void *)fdg_vegas_partials<0>, train},
+                                                        {(const void *)fdg_vegas_partials<1>, train}};
+    for (uint32_t rs = 1; rs <= 16; rs <<= 1) {
+      limits.push_back({(const void *)partials_kernel_rs<kFirst>(rs), hist});
+      limits.push_back({(const void *)partials_kernel_rs<kBoth>(rs), hist});
+    }
+    for (const auto &l : limits) (void)hipFuncSetAttribute(l.first, hipFuncAttributeMaxDynamicSharedMemorySize, l.second);
     (void)hipGetLastError();
   });
-  const long ntile = (n + 63) / 64, seg_tiles = (ntile + p.n_seg - 1) / p.n_seg;
-  const uint32_t n_grp = MODE == kSplit ? 2 * p.n_slice : p.n_slice;
-  hipLaunchKernelGGL((fdg_binned_partials<RS, MODE>), dim3(p.n_seg * n_grp), dim3(256), p.lds, st, roots, (long)p.Bc, n, bins, bin_base,
-                     n_bin, weight, R, p.n_slice, seg_tiles, partial, first);
+}
+
+// out[c] += the n_seg segments' partials [segment][moment][ncol], in segment order (fdg_binned_reduce; C columns per workgroup).
+int reduce_partials(const double *partial, uint32_t n_seg, long ncol, uint32_t R, uint32_t C, double *d_acc, double *d_acc2,
+                    const uint8_t *live, hipStream_t st) {
+  const uint32_t n_mom = d_acc2 ? 2 : 1;
+  hipLaunchKernelGGL(fdg_binned_reduce, dim3((unsigned)((ncol + C - 1) / C), n_mom), dim3(256), 0, st, partial, n_seg, ncol * n_mom, ncol, R,
+                     C, d_acc, d_acc2, live);
   HIP_TRY(hipGetLastError());
   return FDG_OK;
 }
 
-template <int MODE>
-int binned_pass_rs(const BinnedPlan &p, const double *roots, long n, const int32_t *bins, int32_t bin_base, uint32_t n_bin,
-                   const double *weight, uint32_t R, double *partial, int first, hipStream_t st) {
-  switch (p.rs) {
-    case 1: return launch_partials<1, MODE>(p, roots, n, bins, bin_base, n_bin, weight, R, partial, first, st);
-    case 2: return launch_partials<2, MODE>(p, roots, n, bins, bin_base, n_bin, weight, R, partial, first, st);
-    case 4: return launch_partials<4, MODE>(p, roots, n, bins, bin_base, n_bin, weight, R, partial, first, st);
-    case 8: return launch_partials<8, MODE>(p, roots, n, bins, bin_base, n_bin, weight, R, partial, first, st);
-    default: return launch_partials<16, MODE>(p, roots, n, bins, bin_base, n_bin, weight, R, partial, first, st);
-  }
-}
-
-int binned_pass(const BinnedPlan &p, const double *roots, long n, const int32_t *bins, int32_t bin_base, uint32_t n_bin, const double *weight,
-                uint32_t R, double *partial, int first, hipStream_t st) {
-  if (p.mode == kBoth) return binned_pass_rs<kBoth>(p, roots, n, bins, bin_base, n_bin, weight, R, partial, first, st);
-  if (p.mode == kSplit) return launch_partials<1, kSplit>(p, roots, n, bins, bin_base, n_bin, weight, R, partial, first, st);
-  return binned_pass_rs<kFirst>(p, roots, n, bins, bin_base, n_bin, weight, R, partial, first, st);
-}
-
-// The checks every binned entry point makes before any device work.
-int check_binned(const fdg_graph *g, const int32_t *d_bin, uint32_t n_bin, const double *d_acc, int64_t B) {
+// The checks every accumulate entry point makes before any device work.  The binned calls need d_bin; the moments calls need d_acc2
+// and take d_bin == NULL (every sample in bin 0, which needs n_bin == 1).
+int check_call(const fdg_graph *g, const BinnedCall &c, bool moments) {
   if (!g) { set_error("null handle"); return FDG_E_INVALID; }
-  if (B < 0) { set_error("n_sample < 0"); return FDG_E_INVALID; }
-  if (!d_bin || !d_acc) { set_error("null device buffer"); return FDG_E_INVALID; }
-  if (n_bin == 0) { set_error("n_bin == 0"); return FDG_E_INVALID; }
-  if (n_bin > FDG_BIN_MAX) { set_error("n_bin > FDG_BIN_MAX"); return FDG_E_UNSUPPORTED; }
+  if (c.B < 0) { set_error("n_sample < 0"); return FDG_E_INVALID; }
+  if (!c.d_acc || (moments ? !c.d_acc2 : !c.d_bin)) { set_error("null device buffer"); return FDG_E_INVALID; }
+  if (c.d_acc == c.d_acc2) { set_error("d_acc and d_acc2 are the same buffer"); return FDG_E_INVALID; }
+  if (c.n_bin == 0) { set_error("n_bin == 0"); return FDG_E_INVALID; }
+  if (!c.d_bin && c.n_bin != 1) { set_error("d_bin == NULL (one bin) needs n_bin == 1"); return FDG_E_INVALID; }
+  if (c.n_bin > FDG_BIN_MAX) { set_error("n_bin > FDG_BIN_MAX"); return FDG_E_UNSUPPORTED; }
   return FDG_OK;
 }
 
-// ... and the moments entry points' (d_bin == NULL: every sample in bin 0, which needs n_bin == 1).
-int check_moments(const fdg_graph *g, const int32_t *d_bin, uint32_t n_bin, const double *d_acc, const double *d_acc2, int64_t B) {
-  if (!g) { set_error("null handle"); return FDG_E_INVALID; }
-  if (B < 0) { set_error("n_sample < 0"); return FDG_E_INVALID; }
-  if (!d_acc || !d_acc2) { set_error("null device buffer"); return FDG_E_INVALID; }
-  if (d_acc == d_acc2) { set_error("d_acc and d_acc2 are the same buffer"); return FDG_E_INVALID; }
-  if (n_bin == 0) { set_error("n_bin == 0"); return FDG_E_INVALID; }
-  if (!d_bin && n_bin != 1) { set_error("d_bin == NULL (one bin) needs n_bin == 1"); return FDG_E_INVALID; }
-  if (n_bin > FDG_BIN_MAX) { set_error("n_bin > FDG_BIN_MAX"); return FDG_E_UNSUPPORTED; }
-  return FDG_OK;
-}
-
-// ... and the VEGAS calls': the map's limits (every call), then the three output arrays of the accumulate calls.
+// ... and the VEGAS calls': the map's limits (every call), then the output arrays of the accumulate calls.
 int check_vegas_map(uint32_t n_dim, uint32_t n_grid) {
   if (n_dim == 0 || n_grid == 0) { set_error("n_dim == 0 or n_grid == 0"); return FDG_E_INVALID; }
   if (n_dim > FDG_VEGAS_DIM_MAX) { set_error("n_dim > FDG_VEGAS_DIM_MAX"); return FDG_E_UNSUPPORTED; }
@@ -574,39 +610,31 @@ int check_vegas_map(uint32_t n_dim, uint32_t n_grid) {
   return FDG_OK;
 }
 
-int check_vegas(const fdg_graph *g, uint32_t n_dim, uint32_t n_grid, const double *d_acc, const double *d_acc2, const double *d_hist, int64_t B) {
-  int rc = check_moments(g, nullptr, 1, d_acc, d_acc2, B);
+// The moments calls' cases (with a bin vector where there is a discrete variable), distinct output arrays, the map's limits.
+int check_vegas(const fdg_graph *g, const BinnedCall &c) {
+  const VegasRun &v = *c.vg;
+  if (v.binned && g && !c.d_bin) { set_error("d_bin == NULL: use the call without a discrete variable"); return FDG_E_INVALID; }
+  const int rc = check_call(g, c, true);
   if (rc) return rc;
-  if (!d_hist) { set_error("null device buffer"); return FDG_E_INVALID; }
-  if (d_hist == d_acc || d_hist == d_acc2) { set_error("d_hist is the same buffer as d_acc or d_acc2"); return FDG_E_INVALID; }
-  return check_vegas_map(n_dim, n_grid);
-}
-
-// ... and the calls' with a discrete variable: the moments calls' cases with a bin vector, the map's, and four distinct output arrays.
-int check_vegas_binned(const fdg_graph *g, const int32_t *d_bin, uint32_t n_bin, uint32_t n_dim, uint32_t n_grid, const double *d_acc,
-                       const double *d_acc2, const double *d_hist, const double *d_hist_bin, int64_t B) {
-  if (g && !d_bin) { set_error("d_bin == NULL: use the call without a discrete variable"); return FDG_E_INVALID; }
-  int rc = check_moments(g, d_bin, n_bin, d_acc, d_acc2, B);
-  if (rc) return rc;
-  if (!d_hist) { set_error("null device buffer"); return FDG_E_INVALID; }
-  if (d_hist == d_acc || d_hist == d_acc2) { set_error("d_hist is the same buffer as d_acc or d_acc2"); return FDG_E_INVALID; }
-  if (d_hist_bin && (d_hist_bin == d_acc || d_hist_bin == d_acc2 || d_hist_bin == d_hist)) {
+  if (!v.d_hist) { set_error("null device buffer"); return FDG_E_INVALID; }
+  if (v.d_hist == c.d_acc || v.d_hist == c.d_acc2) { set_error("d_hist is the same buffer as d_acc or d_acc2"); return FDG_E_INVALID; }
+  if (v.d_hist_bin && (v.d_hist_bin == c.d_acc || v.d_hist_bin == c.d_acc2 || v.d_hist_bin == v.d_hist)) {
     set_error("d_hist_bin is the same buffer as d_acc, d_acc2 or d_hist"); return FDG_E_INVALID;
   }
-  return check_vegas_map(n_dim, n_grid);
+  return check_vegas_map(v.D, v.G);
 }
 
 // The chunk loop shared by the entry points (caller holds g->mu, stream bound): eval(c0, n, roots, ld) writes the roots of samples
-// c0 .. c0 + n - 1 column-major into roots (root k of sample c0 + b at roots[k * ld + b]).  d_acc2 != null: the second moment too.
-// vg != null (the VEGAS calls): after a chunk's moments pass the training pass runs over the same roots, its partials behind the moments' slab;
-// with vg->d_hist_bin the discrete variable's pass follows, its partials behind the root list.
+// c0 .. c0 + n - 1 column-major into roots (root k of sample c0 + b at roots[k * ld + b]).  c.d_acc2 != null: the second moment too.
+// c.vg != null (the VEGAS calls): after a chunk's moments pass the training pass runs over the same roots, its partials behind the
+// moments' slab; with vg->d_hist_bin the discrete variable's pass follows, its partials behind the root list.
 template <class Eval>
-int run_binned(fdg_graph *g, const int32_t *d_bin, int32_t bin_base, uint32_t n_bin, const double *d_weight, double *d_acc, double *d_acc2,
-               int64_t B, hipStream_t st, Eval eval, const VegasRun *vg = nullptr) {
-  const uint32_t R = g->prog.R;
-  const BinnedPlan p = binned_plan(g, B, R, n_bin, d_acc2 != nullptr);
-  const size_t root_bytes = ((size_t)p.Bc * R * sizeof(double) + 4095) & ~(size_t)4095;
-  const size_t slab_bytes = (p.slab_alloc + 4095) & ~(size_t)4095;
+int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
+  const uint32_t R = g->prog.R, n_bin = c.n_bin;
+  const VegasRun *vg = c.vg;
+  const hipStream_t st = (hipStream_t)c.stream;
+  const BinnedPlan p = binned_plan(g, c.B, R, n_bin, c.d_acc2 != nullptr);
+  const size_t root_bytes = page_up((size_t)p.Bc * R * sizeof(double)), slab_bytes = page_up(p.slab_alloc);
   VegasPlan q;
   if (vg) q = vegas_plan(p, *vg, R, n_bin);
   int rc = ensure_root_scratch(g, vg ? root_bytes + slab_bytes + q.slab_alloc + q.list_bytes + q.bin_slab_alloc : root_bytes + p.slab_alloc);
@@ -615,17 +643,10 @@ int run_binned(fdg_graph *g, const int32_t *d_bin, int32_t bin_base, uint32_t n_
   const uint8_t *live = nullptr;
   rc = root_live_mask(g, &live);
   if (rc) return rc;
+  raise_lds_limits();
   double *vpartial = nullptr, *d_coef = nullptr, *bpartial = nullptr;
   uint32_t *d_kidx = nullptr, n_live = 0;
   if (vg) {
-    static std::once_flag lds_once;
-    std::call_once(lds_once, [] {
-      const int lds = (int)(kBinLdsBudget + 2u * kBinWaves * 64u * 8u);
-      (void)hipFuncSetAttribute((const void *)fdg_vegas_partials<0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      (void)hipFuncSetAttribute((const void *)fdg_vegas_partials<1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      (void)hipFuncSetAttribute((const void *)fdg_vegas_bin_partials, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(FDG_BIN_MAX * 8));
-      (void)hipGetLastError();
-    });
     // the roots that exist, ascending, and their factors: one small upload per call (pageable memory: staged before the call returns)
     vpartial = (double *)((char *)partial + slab_bytes);
     d_coef = (double *)((char *)vpartial + q.slab_alloc);
@@ -641,28 +662,28 @@ int run_binned(fdg_graph *g, const int32_t *d_bin, int32_t bin_base, uint32_t n_
       HIP_TRY(hipMemcpyAsync(d_kidx, hk.data(), n_live * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     }
   }
-  for (long c0 = 0; c0 < (long)B; c0 += p.Bc) {
-    const long n = std::min<long>(p.Bc, (long)B - c0);
+  const PartialsKernel pass = partials_kernel(p);
+  const uint32_t n_grp = p.mode == kSplit ? 2 * p.n_slice : p.n_slice;
+  for (long c0 = 0; c0 < (long)c.B; c0 += p.Bc) {
+    const long n = std::min<long>(p.Bc, (long)c.B - c0), ntile = (n + 63) / 64;
+    const int first = c0 == 0;
+    const int32_t *bins = c.d_bin ? c.d_bin + c0 : nullptr;
+    const double *w = c.d_weight ? c.d_weight + c0 : nullptr;
     rc = eval(c0, n, roots, p.Bc);
     if (rc) return rc;
-    rc = binned_pass(p, roots, n, d_bin ? d_bin + c0 : nullptr, bin_base, n_bin, d_weight ? d_weight + c0 : nullptr, R, partial, c0 == 0, st);
-    if (rc) return rc;
+    hipLaunchKernelGGL(pass, dim3(p.n_seg * n_grp), dim3(256), p.lds, st, roots, (long)p.Bc, n, bins, c.bin_base, n_bin, w, R, p.n_slice,
+                       (ntile + p.n_seg - 1) / p.n_seg, partial, first);
+    HIP_TRY(hipGetLastError());
     if (vg) {
-      const long ntile = (n + 63) / 64, seg_tiles = (ntile + q.n_seg - 1) / q.n_seg;
-      const double *w = d_weight ? d_weight + c0 : nullptr, *cf = vg->coef ? d_coef : nullptr;
-      if (vg->binned)
-        hipLaunchKernelGGL(fdg_vegas_partials<1>, dim3(q.n_seg * q.n_slice), dim3(256), q.lds, st, roots, (long)p.Bc, n, w, d_kidx, cf, n_live,
-                           vg->seed, vg->offset + (uint64_t)c0, vg->D, vg->G, q.ds, q.n_slice, seg_tiles, vpartial, c0 == 0, d_bin + c0, bin_base,
-                           n_bin);
-      else
-        hipLaunchKernelGGL(fdg_vegas_partials<0>, dim3(q.n_seg * q.n_slice), dim3(256), q.lds, st, roots, (long)p.Bc, n, w, d_kidx, cf, n_live,
-                           vg->seed, vg->offset + (uint64_t)c0, vg->D, vg->G, q.ds, q.n_slice, seg_tiles, vpartial, c0 == 0,
-                           (const int32_t *)nullptr, 0, 1u);
+      const double *cf = vg->coef ? d_coef : nullptr;
+      // (the calls without a discrete variable carry no bin vector: null, base 0, one bin)
+      hipLaunchKernelGGL(vg->binned ? fdg_vegas_partials<1> : fdg_vegas_partials<0>, dim3(q.n_seg * q.n_slice), dim3(256), q.lds, st, roots,
+                         (long)p.Bc, n, w, d_kidx, cf, n_live, vg->seed, vg->offset + (uint64_t)c0, vg->D, vg->G, q.ds, q.n_slice,
+                         (ntile + q.n_seg - 1) / q.n_seg, vpartial, first, bins, c.bin_base, n_bin);
       HIP_TRY(hipGetLastError());
       if (vg->d_hist_bin) {
-        const long bin_tiles = (ntile + q.bin_seg - 1) / q.bin_seg;
-        hipLaunchKernelGGL(fdg_vegas_bin_partials, dim3(q.bin_seg), dim3(256), (size_t)n_bin * 8u, st, roots, (long)p.Bc, n, d_bin + c0, bin_base,
-                           n_bin, w, d_kidx, cf, n_live, bin_tiles, bpartial, c0 == 0);
+        hipLaunchKernelGGL(fdg_vegas_bin_partials, dim3(q.bin_seg), dim3(256), (size_t)n_bin * 8u, st, roots, (long)p.Bc, n, bins, c.bin_base,
+                           n_bin, w, d_kidx, cf, n_live, (ntile + q.bin_seg - 1) / q.bin_seg, bpartial, first);
         HIP_TRY(hipGetLastError());
       }
     }
@@ -670,63 +691,73 @@ int run_binned(fdg_graph *g, const int32_t *d_bin, int32_t bin_base, uint32_t n_
   const long ncol = (long)n_bin * R;
   uint32_t C = 1;
   while (C < 64 && (long)C < ncol) C <<= 1;
-  const uint32_t n_mom = d_acc2 ? 2 : 1;
-  hipLaunchKernelGGL(fdg_binned_reduce, dim3((unsigned)((ncol + C - 1) / C), n_mom), dim3(256), 0, st, partial, p.n_seg, ncol * n_mom, ncol,
-                     R, C, d_acc, d_acc2, live);
-  HIP_TRY(hipGetLastError());
-  if (vg) {                                               // hist[d][c] += the segments' partials, in segment order
-    const long hcol = (long)vg->D * vg->G;
-    hipLaunchKernelGGL(fdg_binned_reduce, dim3((unsigned)((hcol + 63) / 64), 1), dim3(256), 0, st, vpartial, q.n_seg, hcol, hcol, 1u, 64u,
-                       vg->d_hist, (double *)nullptr, (const uint8_t *)nullptr);
-    HIP_TRY(hipGetLastError());
-    if (vg->d_hist_bin) {                                 // hist_bin[j] += the segments' partials, in segment order
-      hipLaunchKernelGGL(fdg_binned_reduce, dim3((unsigned)((n_bin + 63u) / 64u), 1), dim3(256), 0, st, bpartial, q.bin_seg, (long)n_bin,
-                         (long)n_bin, 1u, 64u, vg->d_hist_bin, (double *)nullptr, (const uint8_t *)nullptr);
-      HIP_TRY(hipGetLastError());
-    }
-  }
-  return FDG_OK;
+  rc = reduce_partials(partial, p.n_seg, ncol, R, C, c.d_acc, c.d_acc2, live, st);
+  // hist[d][c] and hist_bin[j] += the segments' partials, in segment order
+  if (!rc && vg) rc = reduce_partials(vpartial, q.n_seg, (long)vg->D * vg->G, 1u, 64u, vg->d_hist, nullptr, nullptr, st);
+  if (!rc && vg && vg->d_hist_bin) rc = reduce_partials(bpartial, q.bin_seg, (long)n_bin, 1u, 64u, vg->d_hist_bin, nullptr, nullptr, st);
+  return rc;
 }
 
-// fdg_accumulate_device_binned / _moments after their own checks
-int accumulate_leaf(fdg_graph *g, const double *d_leaf, int64_t ss, int64_t ls, int64_t lts, const int32_t *d_bin, int32_t bin_base,
-                    uint32_t n_bin, const double *d_weight, double *d_acc, double *d_acc2, int64_t B, void *stream,
-                    const VegasRun *vg = nullptr) {
-  if (g->prog.L && !d_leaf) { set_error("null device buffer"); return FDG_E_INVALID; }
-  if (B == 0 || g->prog.R == 0) return FDG_OK;
+// The body every accumulate entry point shares after its own argument checks: null_input is the call's "an input array is missing",
+// locked_check() what only the handle can tell once it is locked, eval the chunk evaluator of run_binned.
+template <class Check, class Eval>
+int accumulate(fdg_graph *g, const BinnedCall &c, bool null_input, Check locked_check, Eval eval) {
+  if (null_input) { set_error("null device buffer"); return FDG_E_INVALID; }
+  if (c.B == 0 || g->prog.R == 0) return FDG_OK;
   std::lock_guard<std::mutex> lk(g->mu);
   fdg::KnobScope knob_scope(&g->knobs);
-  if (d_acc2 && lts && !(g->isa && !g->code_object.empty())) {     // (the binned call finds it in the first chunk's evaluation)
-    set_error("tile-major batches need a handle specialised with FDG_SPEC_ISA"); return FDG_E_UNSUPPORTED;
-  }
-  int rc = ensure_device(g);
+  int rc = locked_check();
   if (rc) return rc;
-  rc = fdg_bind_stream_ws(g, stream);
+  rc = ensure_device(g);
   if (rc) return rc;
-  const hipStream_t st = (hipStream_t)stream;
-  return run_binned(g, d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, st, [&](long c0, long n, double *roots, long ld) {
-    const double *lf = lts ? d_leaf + (size_t)(c0 / 64) * (size_t)lts : d_leaf + c0 * ss;
-    return fdg_run_locked(g, 0, lf, ss, ls, roots, 1, ld, nullptr, nullptr, n, st, lts, 0);
-  }, vg);
+  rc = fdg_bind_stream_ws(g, c.stream);
+  if (rc) return rc;
+  return run_binned(g, c, eval);
 }
 
-// fdg_mc_accumulate_device_binned / _moments after their own checks
+// The leaf form of the calls (fdg_accumulate_device_*), after their own checks
+int accumulate_leaf(fdg_graph *g, const double *d_leaf, int64_t ss, int64_t ls, int64_t lts, const BinnedCall &c) {
+  const hipStream_t st = (hipStream_t)c.stream;
+  return accumulate(
+      g, c, g->prog.L && !d_leaf,
+      [&] {
+        if (c.d_acc2 && lts && !(g->isa && !g->code_object.empty())) {     // (the binned call finds it in the first chunk's evaluation)
+          set_error("tile-major batches need a handle specialised with FDG_SPEC_ISA"); return FDG_E_UNSUPPORTED;
+        }
+        return FDG_OK;
+      },
+      [&](long c0, long n, double *roots, long ld) {
+        const double *lf = lts ? d_leaf + (size_t)(c0 / 64) * (size_t)lts : d_leaf + c0 * ss;
+        return fdg_run_locked(g, 0, lf, ss, ls, roots, 1, ld, nullptr, nullptr, n, st, lts, 0);
+      });
+}
+
+// The Monte-Carlo form (fdg_mc_accumulate_device_*), after their own checks
 int accumulate_mc(fdg_graph *g, const double *d_K, int64_t ks, int64_t kc, const double *d_T, int64_t ts, int64_t tc, double kF, double beta,
-                  double lambda, const int32_t *d_bin, int32_t bin_base, uint32_t n_bin, const double *d_weight, double *d_acc, double *d_acc2,
-                  int64_t B, void *stream, const VegasRun *vg = nullptr) {
-  if (!d_K || !d_T) { set_error("null device buffer"); return FDG_E_INVALID; }
-  if (B == 0 || g->prog.R == 0) return FDG_OK;
-  std::lock_guard<std::mutex> lk(g->mu);
-  fdg::KnobScope knob_scope(&g->knobs);
-  if (g->mc_route == 0) { set_error("fdg_graph_specialize_fused has not been called on this handle"); return FDG_E_INVALID; }
-  int rc = ensure_device(g);
-  if (rc) return rc;
-  rc = fdg_bind_stream_ws(g, stream);
-  if (rc) return rc;
-  const hipStream_t st = (hipStream_t)stream;
-  return run_binned(g, d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, st, [&](long c0, long n, double *roots, long ld) {
-    return fdg_mc_run_locked(g, 0, d_K + c0 * ks, ks, kc, d_T + c0 * ts, ts, tc, kF, beta, lambda, roots, 1, ld, nullptr, nullptr, n, st);
-  }, vg);
+                  double lambda, const BinnedCall &c) {
+  const hipStream_t st = (hipStream_t)c.stream;
+  return accumulate(
+      g, c, !d_K || !d_T,
+      [&] {
+        if (g->mc_route == 0) { set_error("fdg_graph_specialize_fused has not been called on this handle"); return FDG_E_INVALID; }
+        return FDG_OK;
+      },
+      [&](long c0, long n, double *roots, long ld) {
+        return fdg_mc_run_locked(g, 0, d_K + c0 * ks, ks, kc, d_T + c0 * ts, ts, tc, kF, beta, lambda, roots, 1, ld, nullptr, nullptr, n, st);
+      });
+}
+
+// The samplers' shared checks (null_buffer: one of the call's required arrays is missing) and column list.
+int check_sampler(int64_t B, bool null_buffer, uint32_t n_dim, uint32_t n_grid) {
+  if (B < 0) { set_error("n_sample < 0"); return FDG_E_INVALID; }
+  if (null_buffer) { set_error("null device buffer"); return FDG_E_INVALID; }
+  return check_vegas_map(n_dim, n_grid);
+}
+
+VegasCols vegas_cols(const uint32_t *col, uint32_t n_dim) {
+  VegasCols cols;
+  for (uint32_t d = 0; d < FDG_VEGAS_DIM_MAX; ++d) cols.c[d] = d < n_dim ? (col ? col[d] : d) : 0u;
+  return cols;
 }
 
 }  // namespace
@@ -735,66 +766,62 @@ extern "C" {
 
 int fdg_accumulate_device_binned(fdg_graph *g, const double *d_leaf, int64_t ss, int64_t ls, int64_t lts, const int32_t *d_bin, int32_t bin_base,
                                  uint32_t n_bin, const double *d_weight, double *d_acc, int64_t B, void *stream) {
-  const int rc = check_binned(g, d_bin, n_bin, d_acc, B);
-  if (rc) return rc;
-  return accumulate_leaf(g, d_leaf, ss, ls, lts, d_bin, bin_base, n_bin, d_weight, d_acc, nullptr, B, stream);
+  const BinnedCall c{d_bin, bin_base, n_bin, d_weight, d_acc, nullptr, B, stream, nullptr};
+  const int rc = check_call(g, c, false);
+  return rc ? rc : accumulate_leaf(g, d_leaf, ss, ls, lts, c);
 }
 
 int fdg_mc_accumulate_device_binned(fdg_graph *g, const double *d_K, int64_t ks, int64_t kc, const double *d_T, int64_t ts, int64_t tc,
                                     double kF, double beta, double lambda, const int32_t *d_bin, int32_t bin_base, uint32_t n_bin,
                                     const double *d_weight, double *d_acc, int64_t B, void *stream) {
-  const int rc = check_binned(g, d_bin, n_bin, d_acc, B);
-  if (rc) return rc;
-  return accumulate_mc(g, d_K, ks, kc, d_T, ts, tc, kF, beta, lambda, d_bin, bin_base, n_bin, d_weight, d_acc, nullptr, B, stream);
+  const BinnedCall c{d_bin, bin_base, n_bin, d_weight, d_acc, nullptr, B, stream, nullptr};
+  const int rc = check_call(g, c, false);
+  return rc ? rc : accumulate_mc(g, d_K, ks, kc, d_T, ts, tc, kF, beta, lambda, c);
 }
 
 int fdg_accumulate_device_moments(fdg_graph *g, const double *d_leaf, int64_t ss, int64_t ls, int64_t lts, const int32_t *d_bin,
                                   int32_t bin_base, uint32_t n_bin, const double *d_weight, double *d_acc, double *d_acc2, int64_t B,
                                   void *stream) {
-  const int rc = check_moments(g, d_bin, n_bin, d_acc, d_acc2, B);
-  if (rc) return rc;
-  return accumulate_leaf(g, d_leaf, ss, ls, lts, d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, stream);
+  const BinnedCall c{d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, stream, nullptr};
+  const int rc = check_call(g, c, true);
+  return rc ? rc : accumulate_leaf(g, d_leaf, ss, ls, lts, c);
 }
 
 int fdg_mc_accumulate_device_moments(fdg_graph *g, const double *d_K, int64_t ks, int64_t kc, const double *d_T, int64_t ts, int64_t tc,
                                      double kF, double beta, double lambda, const int32_t *d_bin, int32_t bin_base, uint32_t n_bin,
                                      const double *d_weight, double *d_acc, double *d_acc2, int64_t B, void *stream) {
-  const int rc = check_moments(g, d_bin, n_bin, d_acc, d_acc2, B);
-  if (rc) return rc;
-  return accumulate_mc(g, d_K, ks, kc, d_T, ts, tc, kF, beta, lambda, d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, stream);
+  const BinnedCall c{d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, stream, nullptr};
+  const int rc = check_call(g, c, true);
+  return rc ? rc : accumulate_mc(g, d_K, ks, kc, d_T, ts, tc, kF, beta, lambda, c);
 }
 
 int fdg_accumulate_device_vegas(fdg_graph *g, const double *d_leaf, int64_t ss, int64_t ls, int64_t lts, const double *d_weight,
                                 const double *coef, uint64_t seed, uint64_t sample_offset, uint32_t n_dim, uint32_t n_grid, double *d_acc,
                                 double *d_acc2, double *d_hist, int64_t B, void *stream) {
-  const int rc = check_vegas(g, n_dim, n_grid, d_acc, d_acc2, d_hist, B);
-  if (rc) return rc;
-  VegasRun vg;
-  vg.coef = coef; vg.seed = seed; vg.offset = sample_offset; vg.D = n_dim; vg.G = n_grid; vg.d_hist = d_hist;
-  return accumulate_leaf(g, d_leaf, ss, ls, lts, nullptr, 0, 1, d_weight, d_acc, d_acc2, B, stream, &vg);
+  const VegasRun vg{coef, seed, sample_offset, n_dim, n_grid, d_hist, false, nullptr};
+  const BinnedCall c{nullptr, 0, 1, d_weight, d_acc, d_acc2, B, stream, &vg};
+  const int rc = check_vegas(g, c);
+  return rc ? rc : accumulate_leaf(g, d_leaf, ss, ls, lts, c);
 }
 
 int fdg_mc_accumulate_device_vegas(fdg_graph *g, const double *d_K, int64_t ks, int64_t kc, const double *d_T, int64_t ts, int64_t tc,
                                    double kF, double beta, double lambda, const double *d_weight, const double *coef, uint64_t seed,
                                    uint64_t sample_offset, uint32_t n_dim, uint32_t n_grid, double *d_acc, double *d_acc2, double *d_hist,
                                    int64_t B, void *stream) {
-  const int rc = check_vegas(g, n_dim, n_grid, d_acc, d_acc2, d_hist, B);
-  if (rc) return rc;
-  VegasRun vg;
-  vg.coef = coef; vg.seed = seed; vg.offset = sample_offset; vg.D = n_dim; vg.G = n_grid; vg.d_hist = d_hist;
-  return accumulate_mc(g, d_K, ks, kc, d_T, ts, tc, kF, beta, lambda, nullptr, 0, 1, d_weight, d_acc, d_acc2, B, stream, &vg);
+  const VegasRun vg{coef, seed, sample_offset, n_dim, n_grid, d_hist, false, nullptr};
+  const BinnedCall c{nullptr, 0, 1, d_weight, d_acc, d_acc2, B, stream, &vg};
+  const int rc = check_vegas(g, c);
+  return rc ? rc : accumulate_mc(g, d_K, ks, kc, d_T, ts, tc, kF, beta, lambda, c);
 }
 
 int fdg_accumulate_device_vegas_binned(fdg_graph *g, const double *d_leaf, int64_t ss, int64_t ls, int64_t lts, const int32_t *d_bin,
                                        int32_t bin_base, uint32_t n_bin, const double *d_weight, const double *coef, uint64_t seed,
                                        uint64_t sample_offset, uint32_t n_dim, uint32_t n_grid, double *d_acc, double *d_acc2, double *d_hist,
                                        double *d_hist_bin, int64_t B, void *stream) {
-  const int rc = check_vegas_binned(g, d_bin, n_bin, n_dim, n_grid, d_acc, d_acc2, d_hist, d_hist_bin, B);
-  if (rc) return rc;
-  VegasRun vg;
-  vg.coef = coef; vg.seed = seed; vg.offset = sample_offset; vg.D = n_dim; vg.G = n_grid; vg.d_hist = d_hist;
-  vg.binned = true; vg.d_hist_bin = d_hist_bin;
-  return accumulate_leaf(g, d_leaf, ss, ls, lts, d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, stream, &vg);
+  const VegasRun vg{coef, seed, sample_offset, n_dim, n_grid, d_hist, true, d_hist_bin};
+  const BinnedCall c{d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, stream, &vg};
+  const int rc = check_vegas(g, c);
+  return rc ? rc : accumulate_leaf(g, d_leaf, ss, ls, lts, c);
 }
 
 int fdg_mc_accumulate_device_vegas_binned(fdg_graph *g, const double *d_K, int64_t ks, int64_t kc, const double *d_T, int64_t ts, int64_t tc,
@@ -802,28 +829,23 @@ int fdg_mc_accumulate_device_vegas_binned(fdg_graph *g, const double *d_K, int64
                                           const double *d_weight, const double *coef, uint64_t seed, uint64_t sample_offset, uint32_t n_dim,
                                           uint32_t n_grid, double *d_acc, double *d_acc2, double *d_hist, double *d_hist_bin, int64_t B,
                                           void *stream) {
-  const int rc = check_vegas_binned(g, d_bin, n_bin, n_dim, n_grid, d_acc, d_acc2, d_hist, d_hist_bin, B);
-  if (rc) return rc;
-  VegasRun vg;
-  vg.coef = coef; vg.seed = seed; vg.offset = sample_offset; vg.D = n_dim; vg.G = n_grid; vg.d_hist = d_hist;
-  vg.binned = true; vg.d_hist_bin = d_hist_bin;
-  return accumulate_mc(g, d_K, ks, kc, d_T, ts, tc, kF, beta, lambda, d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, stream, &vg);
+  const VegasRun vg{coef, seed, sample_offset, n_dim, n_grid, d_hist, true, d_hist_bin};
+  const BinnedCall c{d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, stream, &vg};
+  const int rc = check_vegas(g, c);
+  return rc ? rc : accumulate_mc(g, d_K, ks, kc, d_T, ts, tc, kF, beta, lambda, c);
 }
 
 int fdg_vegas_sample_device_discrete(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, const double *d_cdf,
                                      uint32_t n_bin, int32_t bin_base, const double *d_ext, uint32_t n_ext, const uint32_t *ext_col,
                                      uint64_t seed, uint64_t sample_offset, double *d_x, int64_t x_sample_stride, int64_t x_col_stride,
                                      double *d_jac, int32_t *d_bin, int32_t *d_cell, int64_t B, void *stream) {
-  if (B < 0) { set_error("n_sample < 0"); return FDG_E_INVALID; }
-  if (!d_grid || !d_x || !d_jac || !d_cdf || !d_bin) { set_error("null device buffer"); return FDG_E_INVALID; }
-  const int rc = check_vegas_map(n_dim, n_grid);
+  const int rc = check_sampler(B, !d_grid || !d_x || !d_jac || !d_cdf || !d_bin, n_dim, n_grid);
   if (rc) return rc;
   if (n_bin == 0) { set_error("n_bin == 0"); return FDG_E_INVALID; }
   if (n_bin > FDG_BIN_MAX) { set_error("n_bin > FDG_BIN_MAX"); return FDG_E_UNSUPPORTED; }
   if (n_ext > FDG_VEGAS_EXT_MAX) { set_error("n_ext > FDG_VEGAS_EXT_MAX"); return FDG_E_UNSUPPORTED; }
   if (n_ext && (!d_ext || !ext_col)) { set_error("n_ext > 0 needs d_ext and ext_col"); return FDG_E_INVALID; }
-  VegasCols cols;
-  for (uint32_t d = 0; d < FDG_VEGAS_DIM_MAX; ++d) cols.c[d] = d < n_dim ? (col ? col[d] : d) : 0u;
+  const VegasCols cols = vegas_cols(col, n_dim);
   VegasExtCols ecols;
   for (uint32_t e = 0; e < FDG_VEGAS_EXT_MAX; ++e) ecols.c[e] = e < n_ext ? ext_col[e] : 0u;
   for (uint32_t e = 0; e < n_ext; ++e) {
@@ -844,16 +866,12 @@ int fdg_vegas_sample_device_discrete(const double *d_grid, uint32_t n_dim, uint3
 int fdg_vegas_sample_device(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, uint64_t seed, uint64_t sample_offset,
                             double *d_x, int64_t x_sample_stride, int64_t x_col_stride, double *d_jac, int32_t *d_cell, int64_t B,
                             void *stream) {
-  if (B < 0) { set_error("n_sample < 0"); return FDG_E_INVALID; }
-  if (!d_grid || !d_x || !d_jac) { set_error("null device buffer"); return FDG_E_INVALID; }
-  const int rc = check_vegas_map(n_dim, n_grid);
+  const int rc = check_sampler(B, !d_grid || !d_x || !d_jac, n_dim, n_grid);
   if (rc) return rc;
   if (B == 0) return FDG_OK;
-  VegasCols cols;
-  for (uint32_t d = 0; d < FDG_VEGAS_DIM_MAX; ++d) cols.c[d] = d < n_dim ? (col ? col[d] : d) : 0u;
   const long grid = std::min<long>(((long)B + 255) / 256, 256L * 16);
-  hipLaunchKernelGGL(fdg_vegas_sample, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, d_grid, n_dim, n_grid, cols, seed,
-                     sample_offset, d_x, (long)x_sample_stride, (long)x_col_stride, d_jac, d_cell, (long)B);
+  hipLaunchKernelGGL(fdg_vegas_sample, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, d_grid, n_dim, n_grid, vegas_cols(col, n_dim),
+                     seed, sample_offset, d_x, (long)x_sample_stride, (long)x_col_stride, d_jac, d_cell, (long)B);
   HIP_TRY(hipGetLastError());
   return FDG_OK;
 }

@@ -95,6 +95,83 @@ def combine(iterations: Sequence[Tuple[np.ndarray, np.ndarray]]):
     return mean, err, chi2
 
 
+def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter, n_sample, n_grid, alpha, floor, seed, n_discard, fixed, coef,
+               device, vmap, specialize_fused, n_total, shard_start, reduce):
+    """The driver behind :func:`vegas_integrate` (``dmap`` None: results ``[R]``) and :func:`vegas_integrate_binned` (``[n_bin, R]``)."""
+    import torch
+    handle = getattr(func_or_handle, "handle", func_or_handle)
+    device = torch.device(device)
+    n_col_k, n_tau = int(tables.n_loop) * int(tables.dim), int(tables.n_tau)
+    n_col, R = n_col_k + n_tau, handle.table.n_root
+    col = [int(c) for c in col]
+    if len(set(col)) != len(col) or not all(0 <= c < n_col for c in col):
+        raise ValueError(f"col must name distinct columns in [0, {n_col})")
+    if dmap is not None:
+        if not all(0 <= e < n_col for e in dmap.ext_col) or set(dmap.ext_col) & set(col):
+            raise ValueError(f"dmap.ext_col must name columns in [0, {n_col}) that col does not")
+        if dmap.device != device:
+            raise ValueError("dmap lives on another device")
+    if vmap is None:
+        vmap = VegasMap(uniform_grid(lo, hi, n_grid), device)
+    if vmap.n_dim != len(col):
+        raise ValueError("one column per variable of the map")
+    D, G, NB = vmap.n_dim, vmap.n_grid, 1 if dmap is None else dmap.n_bin
+    B = int(n_sample)
+    N = B if n_total is None else int(n_total)
+    if B < 1 or N < 2 or n_iter < 1 or not (0 <= n_discard < n_iter):
+        raise ValueError("need n_sample >= 1, n_total >= 2 and 0 <= n_discard < n_iter")
+    if specialize_fused:
+        handle.specialize_fused(tables)
+    fx = np.zeros(n_col) if fixed is None else np.asarray(fixed, dtype=np.float64)
+    if fx.shape != (n_col,):
+        raise ValueError(f"fixed must hold {n_col} column values")
+    shape = (R,) if dmap is None else (NB, R)
+    if dmap is None:
+        out = VegasResult(np.zeros(shape), np.zeros(shape), np.full(shape, np.nan), map=vmap)
+    else:
+        out = VegasBinnedResult(np.zeros(shape), np.zeros(shape), np.full(shape, np.nan), map=vmap, dmap=dmap)
+    with torch.cuda.device(device):
+        st = torch.cuda.current_stream(device).cuda_stream
+        x = torch.from_numpy(fx).to(device)[:, None].repeat(1, B).contiguous()          # [n_col, B]: sample stride 1
+        jac = torch.empty(B, dtype=torch.float64, device=device)
+        d_T = x.data_ptr() + 8 * n_col_k * B
+        if dmap is not None:
+            bins = torch.empty(B, dtype=torch.int32, device=device)
+            d_ext = 0 if dmap.d_ext is None else dmap.d_ext.data_ptr()
+        for it in range(int(n_iter)):
+            off = it * N + int(shard_start)
+            m = torch.zeros((2, NB, R), dtype=torch.float64, device=device)
+            hist = torch.zeros((D, G), dtype=torch.float64, device=device)
+            if dmap is None:
+                capi.vegas_sample_device(vmap.d_grid.data_ptr(), D, G, col, seed, off, x.data_ptr(), 1, B, jac.data_ptr(), 0, B, st)
+                handle.mc_accumulate_device_vegas(x.data_ptr(), 1, B, d_T, 1, B, kF, beta, lam, jac.data_ptr(), coef, seed, off, D, G,
+                                                  m[0].data_ptr(), m[1].data_ptr(), hist.data_ptr(), B, st)
+                sums = [m, hist]
+            else:
+                capi.vegas_sample_device_discrete(vmap.d_grid.data_ptr(), D, G, col, dmap.d_cdf.data_ptr(), NB, 0, d_ext, dmap.ext_col, seed,
+                                                  off, x.data_ptr(), 1, B, jac.data_ptr(), bins.data_ptr(), 0, B, st)
+                hist_bin = torch.zeros(NB, dtype=torch.float64, device=device)
+                handle.mc_accumulate_device_vegas_binned(x.data_ptr(), 1, B, d_T, 1, B, kF, beta, lam, bins.data_ptr(), 0, NB, jac.data_ptr(),
+                                                         coef, seed, off, D, G, m[0].data_ptr(), m[1].data_ptr(), hist.data_ptr(),
+                                                         hist_bin.data_ptr(), B, st)
+                sums = [m, hist, hist_bin]
+            if reduce is not None:
+                for t in sums:
+                    reduce(t)
+            mean, err = mc_estimate(m[0], m[1], N)
+            out.iterations.append((mean.cpu().numpy().reshape(shape), err.cpu().numpy().reshape(shape)))
+            hs = [t.cpu().numpy() for t in sums[1:]]
+            out.histograms.append(hs[0])
+            if dmap is not None:
+                out.bin_histograms.append(hs[1])
+            vmap.refine(hs[0], alpha)
+            if dmap is not None:
+                dmap.refine(hs[1], alpha, floor)
+    mean, err, chi2 = combine(out.iterations[int(n_discard):])
+    out.mean, out.stderr, out.chi2_dof = mean.reshape(shape), err.reshape(shape), chi2.reshape(shape)
+    return out
+
+
 def vegas_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: float = 1.0, lam: float = 0.0, *, n_iter: int = 10,
                     n_sample: int = 100_000, n_grid: int = 64, alpha: float = 0.5, seed: int = 0, n_discard: int = 0, fixed=None,
                     coef=None, device="cuda", vmap: Optional[VegasMap] = None, specialize_fused: bool = True, n_total: Optional[int] = None,
@@ -111,51 +188,8 @@ def vegas_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: 
     Sharding: every rank passes its ``shard_range`` start and count as ``shard_start`` / ``n_sample``, the whole iteration as
     ``n_total``, and ``reduce`` = a function that sums a CUDA tensor over the ranks in place (``sharding.reduce_observable``); it is
     applied to the ``[2, 1, R]`` moments and to the histogram, so every rank refines the same map."""
-    import torch
-    handle = getattr(func_or_handle, "handle", func_or_handle)
-    device = torch.device(device)
-    n_col_k, n_tau = int(tables.n_loop) * int(tables.dim), int(tables.n_tau)
-    n_col, R = n_col_k + n_tau, handle.table.n_root
-    col = [int(c) for c in col]
-    if len(set(col)) != len(col) or not all(0 <= c < n_col for c in col):
-        raise ValueError(f"col must name distinct columns in [0, {n_col})")
-    if vmap is None:
-        vmap = VegasMap(uniform_grid(lo, hi, n_grid), device)
-    if vmap.n_dim != len(col):
-        raise ValueError("one column per variable of the map")
-    D, G = vmap.n_dim, vmap.n_grid
-    B = int(n_sample)
-    N = B if n_total is None else int(n_total)
-    if B < 1 or N < 2 or n_iter < 1 or not (0 <= n_discard < n_iter):
-        raise ValueError("need n_sample >= 1, n_total >= 2 and 0 <= n_discard < n_iter")
-    if specialize_fused:
-        handle.specialize_fused(tables)
-    fx = np.zeros(n_col) if fixed is None else np.asarray(fixed, dtype=np.float64)
-    if fx.shape != (n_col,):
-        raise ValueError(f"fixed must hold {n_col} column values")
-    with torch.cuda.device(device):
-        st = torch.cuda.current_stream(device).cuda_stream
-        x = torch.from_numpy(fx).to(device)[:, None].repeat(1, B).contiguous()          # [n_col, B]: sample stride 1
-        jac = torch.empty(B, dtype=torch.float64, device=device)
-        d_T = x.data_ptr() + 8 * n_col_k * B
-        out = VegasResult(np.zeros(R), np.zeros(R), np.full(R, np.nan), map=vmap)
-        for it in range(int(n_iter)):
-            off = it * N + int(shard_start)
-            capi.vegas_sample_device(vmap.d_grid.data_ptr(), D, G, col, seed, off, x.data_ptr(), 1, B, jac.data_ptr(), 0, B, st)
-            m = torch.zeros((2, 1, R), dtype=torch.float64, device=device)
-            hist = torch.zeros((D, G), dtype=torch.float64, device=device)
-            handle.mc_accumulate_device_vegas(x.data_ptr(), 1, B, d_T, 1, B, kF, beta, lam, jac.data_ptr(), coef, seed, off, D, G,
-                                              m[0].data_ptr(), m[1].data_ptr(), hist.data_ptr(), B, st)
-            if reduce is not None:
-                reduce(m)
-                reduce(hist)
-            mean, err = mc_estimate(m[0], m[1], N)
-            h = hist.cpu().numpy()
-            out.iterations.append((mean.cpu().numpy().reshape(R), err.cpu().numpy().reshape(R)))
-            out.histograms.append(h)
-            vmap.refine(h, alpha)
-    out.mean, out.stderr, out.chi2_dof = combine(out.iterations[int(n_discard):])
-    return out
+    return _integrate(func_or_handle, tables, lo, hi, col, None, kF, beta, lam, n_iter, n_sample, n_grid, alpha, 0.0, seed, n_discard, fixed, coef,
+                      device, vmap, specialize_fused, n_total, shard_start, reduce)
 
 
 def uniform_cdf(n_bin: int) -> np.ndarray:
@@ -239,61 +273,5 @@ def vegas_integrate_binned(func_or_handle, tables, lo, hi, col, dmap: DiscreteMa
     ``mc_estimate``, refine the map with ``alpha`` and the probabilities with ``alpha`` and ``floor``.  ``combine`` is per (bin, root).
     Sharding as in :func:`vegas_integrate`; ``reduce`` is applied to the moments ``[2, n_bin, R]`` and to both histograms, so every rank
     refines the same maps."""
-    import torch
-    handle = getattr(func_or_handle, "handle", func_or_handle)
-    device = torch.device(device)
-    n_col_k, n_tau = int(tables.n_loop) * int(tables.dim), int(tables.n_tau)
-    n_col, R = n_col_k + n_tau, handle.table.n_root
-    col = [int(c) for c in col]
-    if len(set(col)) != len(col) or not all(0 <= c < n_col for c in col):
-        raise ValueError(f"col must name distinct columns in [0, {n_col})")
-    if not all(0 <= e < n_col for e in dmap.ext_col) or set(dmap.ext_col) & set(col):
-        raise ValueError(f"dmap.ext_col must name columns in [0, {n_col}) that col does not")
-    if dmap.device != device:
-        raise ValueError("dmap lives on another device")
-    if vmap is None:
-        vmap = VegasMap(uniform_grid(lo, hi, n_grid), device)
-    if vmap.n_dim != len(col):
-        raise ValueError("one column per variable of the map")
-    D, G, NB = vmap.n_dim, vmap.n_grid, dmap.n_bin
-    B = int(n_sample)
-    N = B if n_total is None else int(n_total)
-    if B < 1 or N < 2 or n_iter < 1 or not (0 <= n_discard < n_iter):
-        raise ValueError("need n_sample >= 1, n_total >= 2 and 0 <= n_discard < n_iter")
-    if specialize_fused:
-        handle.specialize_fused(tables)
-    fx = np.zeros(n_col) if fixed is None else np.asarray(fixed, dtype=np.float64)
-    if fx.shape != (n_col,):
-        raise ValueError(f"fixed must hold {n_col} column values")
-    with torch.cuda.device(device):
-        st = torch.cuda.current_stream(device).cuda_stream
-        x = torch.from_numpy(fx).to(device)[:, None].repeat(1, B).contiguous()          # [n_col, B]: sample stride 1
-        jac = torch.empty(B, dtype=torch.float64, device=device)
-        bins = torch.empty(B, dtype=torch.int32, device=device)
-        d_T = x.data_ptr() + 8 * n_col_k * B
-        d_ext = 0 if dmap.d_ext is None else dmap.d_ext.data_ptr()
-        out = VegasBinnedResult(np.zeros((NB, R)), np.zeros((NB, R)), np.full((NB, R), np.nan), map=vmap, dmap=dmap)
-        for it in range(int(n_iter)):
-            off = it * N + int(shard_start)
-            capi.vegas_sample_device_discrete(vmap.d_grid.data_ptr(), D, G, col, dmap.d_cdf.data_ptr(), NB, 0, d_ext, dmap.ext_col, seed, off,
-                                              x.data_ptr(), 1, B, jac.data_ptr(), bins.data_ptr(), 0, B, st)
-            m = torch.zeros((2, NB, R), dtype=torch.float64, device=device)
-            hist = torch.zeros((D, G), dtype=torch.float64, device=device)
-            hist_bin = torch.zeros(NB, dtype=torch.float64, device=device)
-            handle.mc_accumulate_device_vegas_binned(x.data_ptr(), 1, B, d_T, 1, B, kF, beta, lam, bins.data_ptr(), 0, NB, jac.data_ptr(), coef,
-                                                     seed, off, D, G, m[0].data_ptr(), m[1].data_ptr(), hist.data_ptr(), hist_bin.data_ptr(),
-                                                     B, st)
-            if reduce is not None:
-                reduce(m)
-                reduce(hist)
-                reduce(hist_bin)
-            mean, err = mc_estimate(m[0], m[1], N)
-            h, hb = hist.cpu().numpy(), hist_bin.cpu().numpy()
-            out.iterations.append((mean.cpu().numpy(), err.cpu().numpy()))
-            out.histograms.append(h)
-            out.bin_histograms.append(hb)
-            vmap.refine(h, alpha)
-            dmap.refine(hb, alpha, floor)
-    mean, err, chi2 = combine(out.iterations[int(n_discard):])
-    out.mean, out.stderr, out.chi2_dof = mean.reshape(NB, R), err.reshape(NB, R), chi2.reshape(NB, R)
-    return out
+    return _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter, n_sample, n_grid, alpha, floor, seed, n_discard, fixed,
+                      coef, device, vmap, specialize_fused, n_total, shard_start, reduce)
