@@ -46,10 +46,12 @@ EXPORTS = [
     "fdg_vegas_sample_device", "fdg_accumulate_device_vegas", "fdg_mc_accumulate_device_vegas", "fdg_vegas_refine",
     "fdg_vegas_sample_device_discrete", "fdg_accumulate_device_vegas_binned", "fdg_mc_accumulate_device_vegas_binned",
     "fdg_vegas_refine_discrete",
+    "fdg_vegas_sample_device_polar", "fdg_sincos",
 ]
 FDG_BIN_MAX = 16384     # fdg_accumulate_device_binned: largest n_bin
 FDG_VEGAS_DIM_MAX, FDG_VEGAS_GRID_MAX = 64, 1024     # the VEGAS map: most variables, most cells per variable
 FDG_VEGAS_EXT_MAX = 16  # the discrete variable's table: most columns per value
+FDG_VEGAS_POLAR_MAX = 21  # fdg_vegas_sample_device_polar: most groups of polar variables
 COMM_ID_BYTES = 128
 
 
@@ -220,6 +222,10 @@ def lib():
     L.fdg_comm_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(vp)]
     L.fdg_comm_destroy.argtypes = [vp]
     L.fdg_reduce_device.argtypes = [vp, dp, u32, C.c_int, vp]
+    L.fdg_vegas_sample_device_polar.argtypes = [dp, u32, u32, C.c_void_p, dp, u32, C.c_int32, dp, u32, C.c_void_p, C.c_void_p, u32, u64, u64,
+                                                dp, i64, i64, dp, dp, dp, i64, vp]
+    L.fdg_sincos.argtypes = [C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.fdg_sincos.restype = None
     L.fdg_powi.argtypes = [C.c_double, C.c_int32]
     L.fdg_powi.restype = C.c_double
     _lib = L
@@ -561,6 +567,42 @@ def vegas_sample_device_discrete(d_grid: int, n_dim: int, n_grid: int, col, d_cd
                                                  sample_offset, d_x or None, xs, xc, d_jac or None, d_bin or None, d_cell or None, B, stream))
 
 
+class VegasPolar(C.Structure):
+    """fdg_vegas_polar: the variables ``var .. var + dim - 1`` are (k, phi) or (k, theta, phi); the components go to ``col[0 .. dim)``"""
+    _fields_ = [("var", C.c_uint32), ("dim", C.c_uint32), ("col", C.c_uint32 * 3)]
+
+
+def vegas_sample_device_polar(d_grid: int, n_dim: int, n_grid: int, col, d_cdf: int, n_bin: int, bin_base: int, d_ext: int, ext_col, polar,
+                              seed: int, sample_offset: int, d_x: int, xs: int, xc: int, d_jac: int, d_bin: int, d_cell: int, B: int,
+                              stream: int = 0):
+    """fdg_vegas_sample_device_polar: :func:`vegas_sample_device_discrete` (``d_cdf`` 0: :func:`vegas_sample_device`; the discrete
+    variable's arguments are then ignored) with groups of variables read as a modulus and a direction.  ``polar``: a sequence of
+    ``(var, cols)`` with ``len(cols)`` 2 -- variables ``var, var + 1`` are (k, phi) -- or 3 -- ``var .. var + 2`` are (k, theta, phi) --;
+    the Cartesian components go to the columns ``cols``.  ``col`` names a column per variable; the entry of a grouped variable is not
+    read (None stands for 0 there)."""
+    c = None
+    if col is not None:
+        c = np.ascontiguousarray([0 if v is None else v for v in col], dtype=np.uint32)
+        if c.shape != (n_dim,):
+            raise ValueError("col must name one column per variable")
+    e = np.ascontiguousarray([] if ext_col is None else ext_col, dtype=np.uint32)
+    if e.ndim != 1:
+        raise ValueError("ext_col must be a sequence of column numbers")
+    groups = [] if polar is None else list(polar)
+    arr = (VegasPolar * max(len(groups), 1))()
+    for g, (var, cols) in enumerate(groups):
+        cols = [int(v) for v in cols]
+        if len(cols) not in (2, 3):
+            raise ValueError("a polar group has 2 or 3 columns")
+        arr[g].var, arr[g].dim = int(var), len(cols)
+        for i, v in enumerate(cols):
+            arr[g].col[i] = v
+    check(lib().fdg_vegas_sample_device_polar(d_grid or None, n_dim, n_grid, None if c is None else c.ctypes.data, d_cdf or None, n_bin,
+                                              bin_base, d_ext or None, e.shape[0], e.ctypes.data if e.shape[0] else None,
+                                              C.addressof(arr) if groups else None, len(groups), seed, sample_offset, d_x or None, xs, xc,
+                                              d_jac or None, d_bin or None, d_cell or None, B, stream))
+
+
 def vegas_refine_discrete(cdf: np.ndarray, hist_bin: np.ndarray, alpha: float = 0.5, floor: float = 0.05) -> np.ndarray:
     """fdg_vegas_refine_discrete: moves the probabilities of the discrete variable ``cdf [n_bin + 1]`` (float64, C-contiguous, in place)
     towards ``p_j ~ (hist_bin[j] * p_j) ** alpha``, every one at least ``floor / n_bin``; returns ``cdf``."""
@@ -660,6 +702,13 @@ def clock_probe_device(seconds: float, d_ticks: int, stream: int):
 
 def powi(x: float, n: int) -> float:
     return float(lib().fdg_powi(x, n))
+
+
+def sincos(x: float):
+    """fdg_sincos: ``(sin x, cos x)`` for ``0 <= x <= 2 pi`` by the routine the polar sampler uses (csrc/fdg_sincos.h)"""
+    s, c = C.c_double(), C.c_double()
+    lib().fdg_sincos(float(x), C.byref(s), C.byref(c))
+    return s.value, c.value
 
 
 class Comm:

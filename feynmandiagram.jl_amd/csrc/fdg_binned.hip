@@ -31,6 +31,10 @@
 // the sampler draws one of n_bin values by its cumulative distribution next to the continuous variables; the accumulate calls are the
 // moments calls WITH their bin vector plus the training pass above plus one more pass (fdg_vegas_bin_partials) that sums the same
 // (w sum_k c_k root_k)^2 per value of the discrete variable, the key read from the bin vector.
+//
+// Spherical momentum variables (fdg_vegas_sample_device_polar): groups of 2 or 3 consecutive variables are (k, phi) or (k, theta, phi);
+// the sampler writes their Cartesian components and folds k (or k k sin theta) into the weight, the sine and cosine from fdg_sincos.h.
+// The accumulate side is untouched: the training pass recomputes cells from the Philox counters and never reads x.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -41,6 +45,7 @@
 
 #define FDG_RUNTIME_TU 1
 #include "fdg_internal.h"
+#include "fdg_sincos.h"
 
 using namespace fdg;
 
@@ -232,15 +237,22 @@ __device__ __forceinline__ uint32_t vegas_cell(uint64_t sample, uint32_t d, uint
 struct VegasCols { uint32_t c[FDG_VEGAS_DIM_MAX]; };   // the column of x each variable is written to (a kernel argument, by value)
 
 // The continuous variables of sample b, in order: x and the cell of each, and the jacobian (a left fold over them), returned.
+// kPolar (fdg_vegas_sample_polar): bit d of `grouped` set = variable d belongs to a polar group; its value goes to the lane's slot of
+// `stash` (LDS, [slot][256 lanes], slots in ascending d) instead of a column of x.
+template <bool kPolar = false>
 __device__ __forceinline__ double vegas_draw(const double *__restrict__ grid, uint32_t D, uint32_t G, const VegasCols &col, uint64_t seed,
-                                             uint64_t off, double *__restrict__ x, long xs, long xc, int32_t *__restrict__ cell, long n, long b) {
+                                             uint64_t off, double *__restrict__ x, long xs, long xc, int32_t *__restrict__ cell, long n, long b,
+                                             uint64_t grouped = 0, double *stash = nullptr) {
   double jb = 0.0;
+  uint32_t slot = 0;
   for (uint32_t d = 0; d < D; ++d) {
     double y;
     const uint32_t c = vegas_cell(off + (uint64_t)b, d, seed, G, y);
     const double *e = grid + (size_t)d * (G + 1u) + c;
     const double lo = e[0], wd = e[1] - lo, fr = y - (double)c;
-    x[b * xs + (long)col.c[d] * xc] = lo + fr * wd;
+    const double v = lo + fr * wd;
+    if (kPolar && ((grouped >> d) & 1u)) stash[(slot++) * 256u + threadIdx.x] = v;
+    else x[b * xs + (long)col.c[d] * xc] = v;
     const double f = (double)G * wd;
     jb = d ? jb * f : f;
     if (cell) cell[(size_t)d * (size_t)n + (size_t)b] = (int32_t)c;
@@ -260,8 +272,25 @@ fdg_vegas_sample(const double *__restrict__ grid, uint32_t D, uint32_t G, VegasC
 
 struct VegasExtCols { uint32_t c[FDG_VEGAS_EXT_MAX]; };   // the columns of x the rows of the discrete variable's table go to
 
-// fdg_vegas_sample with one discrete variable behind the continuous ones: its uniform is the Philox column D, its value j the number
-// of interior edges of cdf that are <= u (a binary search per lane: the cdf is at most 128 KiB and stays in L2).
+// The discrete variable of sample b behind D continuous ones whose jacobian is jb: its uniform is the Philox column D, its value j the
+// number of interior edges of cdf that are <= u (a binary search per lane: the cdf is at most 128 KiB and stays in L2).
+__device__ __forceinline__ void vegas_draw_discrete(const double *__restrict__ cdf, uint32_t n_bin, int32_t bin_base,
+                                                    const double *__restrict__ ext, uint32_t n_ext, const VegasExtCols &ecol, uint64_t seed,
+                                                    uint64_t off, uint32_t D, double *__restrict__ x, long xs, long xc,
+                                                    double *__restrict__ jac, int32_t *__restrict__ bin, long b, double jb) {
+  const double u = fdg_philox_u53(off + (uint64_t)b, D, seed);
+  uint32_t lo = 0, hi = n_bin - 1u;                     // j in [lo, hi]: cdf[1 .. lo] <= u < cdf[hi + 1 ..]
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (cdf[mid + 1u] <= u) lo = mid + 1u; else hi = mid;
+  }
+  const double p = cdf[lo + 1u] - cdf[lo];
+  jac[b] = jb / p;
+  bin[b] = (int32_t)lo + bin_base;
+  for (uint32_t e = 0; e < n_ext; ++e) x[b * xs + (long)ecol.c[e] * xc] = ext[(size_t)lo * n_ext + e];
+}
+
+// fdg_vegas_sample with one discrete variable behind the continuous ones (vegas_draw_discrete).
 __global__ void __launch_bounds__(256)
 fdg_vegas_sample_discrete(const double *__restrict__ grid, uint32_t D, uint32_t G, VegasCols col, const double *__restrict__ cdf,
                           uint32_t n_bin, int32_t bin_base, const double *__restrict__ ext, uint32_t n_ext, VegasExtCols ecol, uint64_t seed,
@@ -269,16 +298,57 @@ fdg_vegas_sample_discrete(const double *__restrict__ grid, uint32_t D, uint32_t 
                           int32_t *__restrict__ cell, long n) {
   for (long b = blockIdx.x * 256L + threadIdx.x; b < n; b += (long)gridDim.x * 256L) {
     const double jb = vegas_draw(grid, D, G, col, seed, off, x, xs, xc, cell, n, b);
-    const double u = fdg_philox_u53(off + (uint64_t)b, D, seed);
-    uint32_t lo = 0, hi = n_bin - 1u;                     // j in [lo, hi]: cdf[1 .. lo] <= u < cdf[hi + 1 ..]
-    while (lo < hi) {
-      const uint32_t mid = (lo + hi) >> 1;
-      if (cdf[mid + 1u] <= u) lo = mid + 1u; else hi = mid;
+    vegas_draw_discrete(cdf, n_bin, bin_base, ext, n_ext, ecol, seed, off, D, x, xs, xc, jac, bin, b, jb);
+  }
+}
+
+// The groups of polar variables (a kernel argument, by value): group g takes the variables var[g] .. var[g] + dim[g] - 1 and writes
+// the Cartesian components to the columns col[g][0 .. dim[g]).  grouped: bit d set = variable d belongs to a group.
+struct VegasPolar {
+  uint64_t grouped;
+  uint32_t n;
+  uint32_t var[FDG_VEGAS_POLAR_MAX], dim[FDG_VEGAS_POLAR_MAX];
+  uint32_t col[FDG_VEGAS_POLAR_MAX][3];
+};
+
+// fdg_vegas_sample / fdg_vegas_sample_discrete (cdf null: no discrete variable) with groups of variables read as (k, phi) or
+// (k, theta, phi): the drawn values of the grouped variables wait in LDS (one slot of 256 lanes per grouped variable, dynamic:
+// 2 KiB each) until the fold over all variables is done, then every group gives its columns and its factors of the jacobian, in
+// the order of the array.  One lane per sample; a lane touches its own LDS words only, so no barrier.
+__global__ void __launch_bounds__(256)
+fdg_vegas_sample_polar(const double *__restrict__ grid, uint32_t D, uint32_t G, VegasCols col, VegasPolar pol, const double *__restrict__ cdf,
+                       uint32_t n_bin, int32_t bin_base, const double *__restrict__ ext, uint32_t n_ext, VegasExtCols ecol, uint64_t seed,
+                       uint64_t off, double *__restrict__ x, long xs, long xc, double *__restrict__ jac, int32_t *__restrict__ bin,
+                       int32_t *__restrict__ cell, long n) {
+  extern __shared__ double polar_stash[];
+  for (long b = blockIdx.x * 256L + threadIdx.x; b < n; b += (long)gridDim.x * 256L) {
+    double jb = vegas_draw<true>(grid, D, G, col, seed, off, x, xs, xc, cell, n, b, pol.grouped, polar_stash);
+    for (uint32_t g = 0; g < pol.n; ++g) {
+      const uint32_t var = pol.var[g];
+      const double *v = polar_stash + (size_t)__popcll(pol.grouped & ((1ull << var) - 1ull)) * 256u + threadIdx.x;
+      double *xb = x + b * xs;
+      const double k = v[0];
+      double sp, cp;
+      if (pol.dim[g] == 3) {
+        double st, ct;
+        fdg_sincos_impl(v[256], st, ct);
+        fdg_sincos_impl(v[512], sp, cp);
+        const double ks = k * st;
+        xb[(long)pol.col[g][0] * xc] = ks * cp;
+        xb[(long)pol.col[g][1] * xc] = ks * sp;
+        xb[(long)pol.col[g][2] * xc] = k * ct;
+        jb = jb * k;
+        jb = jb * k;
+        jb = jb * st;
+      } else {
+        fdg_sincos_impl(v[256], sp, cp);
+        xb[(long)pol.col[g][0] * xc] = k * cp;
+        xb[(long)pol.col[g][1] * xc] = k * sp;
+        jb = jb * k;
+      }
     }
-    const double p = cdf[lo + 1u] - cdf[lo];
-    jac[b] = jb / p;
-    bin[b] = (int32_t)lo + bin_base;
-    for (uint32_t e = 0; e < n_ext; ++e) x[b * xs + (long)ecol.c[e] * xc] = ext[(size_t)lo * n_ext + e];
+    if (!cdf) { jac[b] = jb; continue; }
+    vegas_draw_discrete(cdf, n_bin, bin_base, ext, n_ext, ecol, seed, off, D, x, xs, xc, jac, bin, b, jb);
   }
 }
 
@@ -862,6 +932,66 @@ int fdg_vegas_sample_device_discrete(const double *d_grid, uint32_t n_dim, uint3
   HIP_TRY(hipGetLastError());
   return FDG_OK;
 }
+
+int fdg_vegas_sample_device_polar(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, const double *d_cdf,
+                                  uint32_t n_bin, int32_t bin_base, const double *d_ext, uint32_t n_ext, const uint32_t *ext_col,
+                                  const fdg_vegas_polar *polar, uint32_t n_polar, uint64_t seed, uint64_t sample_offset, double *d_x,
+                                  int64_t x_sample_stride, int64_t x_col_stride, double *d_jac, int32_t *d_bin, int32_t *d_cell, int64_t B,
+                                  void *stream) {
+  const int rc = check_sampler(B, !d_grid || !d_x || !d_jac || (d_cdf && !d_bin), n_dim, n_grid);
+  if (rc) return rc;
+  if (!d_cdf) n_bin = 1, n_ext = 0;                       // no discrete variable: its arguments are ignored
+  if (n_bin == 0) { set_error("n_bin == 0"); return FDG_E_INVALID; }
+  if (n_bin > FDG_BIN_MAX) { set_error("n_bin > FDG_BIN_MAX"); return FDG_E_UNSUPPORTED; }
+  if (n_ext > FDG_VEGAS_EXT_MAX) { set_error("n_ext > FDG_VEGAS_EXT_MAX"); return FDG_E_UNSUPPORTED; }
+  if (n_ext && (!d_ext || !ext_col)) { set_error("n_ext > 0 needs d_ext and ext_col"); return FDG_E_INVALID; }
+  if (n_polar > FDG_VEGAS_POLAR_MAX) { set_error("n_polar > FDG_VEGAS_POLAR_MAX"); return FDG_E_UNSUPPORTED; }
+  if (n_polar && !polar) { set_error("n_polar > 0 needs polar"); return FDG_E_INVALID; }
+  VegasPolar pol;
+  pol.grouped = 0;
+  pol.n = n_polar;
+  for (uint32_t g = 0; g < FDG_VEGAS_POLAR_MAX; ++g) {
+    const bool in = g < n_polar;
+    pol.var[g] = in ? polar[g].var : 0u;
+    pol.dim[g] = in ? polar[g].dim : 0u;
+    for (uint32_t i = 0; i < 3; ++i) pol.col[g][i] = in && i < polar[g].dim ? polar[g].col[i] : 0u;
+    if (!in) continue;
+    if (polar[g].dim != 2 && polar[g].dim != 3) { set_error("a polar group has 2 or 3 variables"); return FDG_E_INVALID; }
+    if (polar[g].var >= n_dim || polar[g].var + polar[g].dim > n_dim) { set_error("a polar group reaches past n_dim"); return FDG_E_INVALID; }
+    const uint64_t bits = ((1ull << polar[g].dim) - 1ull) << polar[g].var;
+    if (pol.grouped & bits) { set_error("two polar groups share a variable"); return FDG_E_INVALID; }
+    pol.grouped |= bits;
+  }
+  // every column written once: the variables of no group, the groups' components, the discrete variable's table
+  VegasCols cols = vegas_cols(col, n_dim);
+  VegasExtCols ecols;
+  for (uint32_t e = 0; e < FDG_VEGAS_EXT_MAX; ++e) ecols.c[e] = e < n_ext ? ext_col[e] : 0u;
+  std::vector<uint32_t> named;
+  for (uint32_t d = 0; d < n_dim; ++d) {
+    if ((pol.grouped >> d) & 1u) cols.c[d] = 0u;          // (not read)
+    else named.push_back(cols.c[d]);
+  }
+  for (uint32_t g = 0; g < n_polar; ++g) named.insert(named.end(), pol.col[g], pol.col[g] + pol.dim[g]);
+  named.insert(named.end(), ecols.c, ecols.c + n_ext);
+  std::sort(named.begin(), named.end());
+  if (std::adjacent_find(named.begin(), named.end()) != named.end()) { set_error("a column of x is named twice"); return FDG_E_INVALID; }
+  if (B == 0) return FDG_OK;
+  const size_t lds = (size_t)__builtin_popcountll(pol.grouped) * 256u * sizeof(double);
+  static std::once_flag once;
+  std::call_once(once, [] {
+    (void)hipFuncSetAttribute((const void *)fdg_vegas_sample_polar, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              FDG_VEGAS_DIM_MAX * 256 * (int)sizeof(double));
+    (void)hipGetLastError();
+  });
+  const long grid = std::min<long>(((long)B + 255) / 256, 256L * 16);
+  hipLaunchKernelGGL(fdg_vegas_sample_polar, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, d_grid, n_dim, n_grid, cols, pol, d_cdf,
+                     n_bin, bin_base, d_ext, n_ext, ecols, seed, sample_offset, d_x, (long)x_sample_stride, (long)x_col_stride, d_jac, d_bin,
+                     d_cell, (long)B);
+  HIP_TRY(hipGetLastError());
+  return FDG_OK;
+}
+
+void fdg_sincos(double x, double *s, double *c) { fdg_sincos_impl(x, *s, *c); }
 
 int fdg_vegas_sample_device(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, uint64_t seed, uint64_t sample_offset,
                             double *d_x, int64_t x_sample_stride, int64_t x_col_stride, double *d_jac, int32_t *d_cell, int64_t B,

@@ -334,6 +334,37 @@ function vegas_refine_discrete!(cdf::Vector{Float64}, hist_bin::Vector{Float64};
         cdf, hist_bin, length(hist_bin), alpha, floor))
     return cdf
 end
+# ---- spherical momentum variables (include/fdg.h; no counterpart in the reference: the caller's side of example/benchmark.jl:46) ---- #
+# K = MCIntegration.FermiK(dim, kF, 0.2 kF, 10 kF): a group of 2 or 3 consecutive VEGAS variables is (k, phi) or (k, theta, phi), and the
+# sampler writes the Cartesian components.  polar: a vector of (var, cols) with var the group's first variable (1-based) and cols its 2 or
+# 3 columns of x (1-based); a fdg_vegas_polar is five UInt32 (var, dim, col[3]).  d_cdf = C_NULL: no discrete variable (d_bin may be C_NULL).
+function vegas_sample_device_polar!(d_x::Ptr{Float64}, d_jac::Ptr{Float64}, d_grid::Ptr{Float64}, n_dim::Integer, n_grid::Integer, B::Integer,
+    polar::AbstractVector; col::Union{Nothing,AbstractVector{<:Integer}}=nothing, d_cdf::Ptr{Float64}=Ptr{Float64}(C_NULL), n_bin::Integer=1,
+    d_bin::Ptr{Int32}=Ptr{Int32}(C_NULL), d_ext::Ptr{Float64}=Ptr{Float64}(C_NULL), ext_col::AbstractVector{<:Integer}=Int[],
+    bin_base::Integer=1, seed::Integer=0, sample_offset::Integer=0, x_strides=(1, B), d_cell::Ptr{Int32}=Ptr{Int32}(C_NULL),
+    stream::Ptr{Cvoid}=C_NULL)
+    c = col === nothing ? nothing : UInt32.(col .- 1)
+    e = UInt32.(ext_col .- 1)
+    p = zeros(UInt32, 5 * max(length(polar), 1))
+    for (g, (var, cols)) in enumerate(polar)
+        length(cols) in (2, 3) || error("a polar group has 2 or 3 columns")
+        p[5g-4] = var - 1
+        p[5g-3] = length(cols)
+        p[5g-2:5g-3+length(cols)] .= UInt32.(cols .- 1)
+    end
+    _fdg_check(ccall((:fdg_vegas_sample_device_polar, _libfdg), Cint,
+        (Ptr{Float64}, UInt32, UInt32, Ptr{UInt32}, Ptr{Float64}, UInt32, Int32, Ptr{Float64}, UInt32, Ptr{UInt32}, Ptr{UInt32}, UInt32, UInt64,
+         UInt64, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Int64, Ptr{Cvoid}),
+        d_grid, n_dim, n_grid, c === nothing ? C_NULL : c, d_cdf, n_bin, bin_base, d_ext, length(e), isempty(e) ? C_NULL : e,
+        isempty(polar) ? C_NULL : p, length(polar), seed, sample_offset, d_x, x_strides[1], x_strides[2], d_jac, d_bin, d_cell, B, stream))
+    return nothing
+end
+# (sin x, cos x) for 0 <= x <= 2 pi by the routine the polar sampler uses (fdg_sincos): the same bits on host and device.
+function fdg_sincos(x::Float64)
+    s, c = Ref{Float64}(0.0), Ref{Float64}(0.0)
+    ccall((:fdg_sincos, _libfdg), Cvoid, (Float64, Ref{Float64}, Ref{Float64}), x, s, c)
+    return s[], c[]
+end
 # device memory for a batch, backed by physical chunks of `chunk_bytes` (0: one allocation): fdg_batch_alloc / fdg_batch_free
 function batch_alloc(bytes::Integer; chunk_bytes::Integer=0)
     p = Ref{Ptr{Cvoid}}(C_NULL)
@@ -382,7 +413,7 @@ function accumulate_device!(f::GraphFunc, d_acc::Ptr{Float64}, d_leaf::Ptr{Float
         f.handle, d_leaf, leaf_strides[1], leaf_strides[2], d_weight, d_acc, B, stream))
 end
 
-export compile_hip, GraphFunc, eval_device!, accumulate_device!, eval_device_tiled!, accumulate_device_tiled!, accumulate_device_binned!, mc_accumulate_device_binned!, accumulate_device_moments!, mc_accumulate_device_moments!, vegas_sample_device!, accumulate_device_vegas!, mc_accumulate_device_vegas!, vegas_refine!, vegas_sample_device_discrete!, accumulate_device_vegas_binned!, mc_accumulate_device_vegas_binned!, vegas_refine_discrete!, batch_alloc, batch_free, tile_major!, from_tile_major!
+export compile_hip, GraphFunc, eval_device!, accumulate_device!, eval_device_tiled!, accumulate_device_tiled!, accumulate_device_binned!, mc_accumulate_device_binned!, accumulate_device_moments!, mc_accumulate_device_moments!, vegas_sample_device!, accumulate_device_vegas!, mc_accumulate_device_vegas!, vegas_refine!, vegas_sample_device_discrete!, accumulate_device_vegas_binned!, mc_accumulate_device_vegas_binned!, vegas_refine_discrete!, vegas_sample_device_polar!, fdg_sincos, batch_alloc, batch_free, tile_major!, from_tile_major!
 
 # ---- multi-GPU: one Julia process per GPU, ONE reduction of the accumulated observable ------------ #
 # (include/fdg.h, "multi-GPU").  Rank 0 calls `comm_unique_id()` and ships the 128 bytes to the other

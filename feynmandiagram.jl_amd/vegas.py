@@ -10,9 +10,14 @@ training histogram on the device.  Only the histogram (``n_dim * n_grid`` double
 A discrete variable (``DiscreteMap``, ``vegas_integrate_binned``; fdg_vegas_sample_device_discrete, fdg_mc_accumulate_device_vegas_binned,
 fdg_vegas_refine_discrete) picks one of ``n_bin`` external configurations per sample -- ``ExtKidx = MCIntegration.Discrete(1, Nk)`` of the
 reference's test/ver4.jl:221-250 -- so that one run fills an observable ``[n_bin, R]`` and trains the variable's probabilities with the map.
+
+Spherical momentum variables (``PolarVar``, ``ball``, the keyword ``polar``; fdg_vegas_sample_device_polar): a group of 2 or 3
+consecutive variables is a modulus and a direction -- ``K = MCIntegration.FermiK(dim, kF, 0.2 kF, 10 kF)`` of the reference's
+example/benchmark.jl:46 -- and the sampler writes the Cartesian components; the accumulate calls and the refinement are the same.
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass, field
 from typing import Callable, List, Optional, Sequence, Tuple
 
@@ -95,19 +100,72 @@ def combine(iterations: Sequence[Tuple[np.ndarray, np.ndarray]]):
     return mean, err, chi2
 
 
+@dataclass(frozen=True)
+class PolarVar:
+    """A group of polar variables: the VEGAS variables ``var, var + 1`` are ``(k, phi)`` when ``cols`` names two columns, and
+    ``var, var + 1, var + 2`` are ``(k, theta, phi)`` when it names three; the sampler writes ``k cos(phi)``, ``k sin(phi)`` or
+    ``k sin(theta) cos(phi)``, ``k sin(theta) sin(phi)``, ``k cos(theta)`` into the columns ``cols`` and multiplies the weight by
+    ``k`` or ``k**2 sin(theta)``."""
+    var: int
+    cols: Tuple[int, ...]
+
+
+def ball(k_max: float, dim: int = 3, k_min: float = 0.0):
+    """``(lo, hi)`` of one group's variables for the ball (``k_min > 0``: the shell) ``k_min <= |K| <= k_max`` in ``dim`` = 2 or 3
+    dimensions: ``k`` in ``[k_min, k_max]``, ``theta`` in ``[0, pi]`` (3D only), ``phi`` in ``[0, 2 pi]``."""
+    if dim not in (2, 3):
+        raise ValueError("dim must be 2 or 3")
+    if not (0.0 <= k_min < k_max and math.isfinite(k_max)):
+        raise ValueError("need 0 <= k_min < k_max, finite")
+    angles = [math.pi, 2.0 * math.pi] if dim == 3 else [2.0 * math.pi]
+    return [float(k_min)] + [0.0] * (dim - 1), [float(k_max)] + angles
+
+
+def _check_polar(polar, col, vmap, n_col):
+    """The groups as ``(var, cols)`` pairs, after the checks of the driver: every group inside the map and apart from the others, no
+    column on a grouped variable, every column inside x, and the edges of the map within the domain of the sampler's sine and cosine."""
+    groups, grouped = [], set()
+    for p in polar:
+        var, cols = int(p.var), tuple(int(c) for c in p.cols)
+        if len(cols) not in (2, 3):
+            raise ValueError("a polar group names 2 or 3 columns")
+        mine = set(range(var, var + len(cols)))
+        if var < 0 or var + len(cols) > vmap.n_dim:
+            raise ValueError("a polar group reaches outside the map's variables")
+        if mine & grouped:
+            raise ValueError("two polar groups share a variable")
+        grouped |= mine
+        if not all(0 <= c < n_col for c in cols):
+            raise ValueError(f"a polar group must name columns in [0, {n_col})")
+        if any(col[d] is not None for d in mine):
+            raise ValueError("the col entry of a grouped variable must be None: the group writes its own columns")
+        g = vmap.grid
+        angles = [(var + 1, math.pi, "theta"), (var + 2, 2.0 * math.pi, "phi")] if len(cols) == 3 else [(var + 1, 2.0 * math.pi, "phi")]
+        if not g[var, 0] >= 0.0:
+            raise ValueError("the modulus of a polar group needs lo >= 0")
+        for d, top, what in angles:
+            if not (g[d, 0] >= 0.0 and g[d, -1] <= top):
+                raise ValueError(f"{what} of a polar group must stay within [0, {top}]")
+        groups.append((var, cols))
+    if len(groups) > capi.FDG_VEGAS_POLAR_MAX:
+        raise ValueError(f"at most {capi.FDG_VEGAS_POLAR_MAX} polar groups")
+    return groups
+
+
 def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter, n_sample, n_grid, alpha, floor, seed, n_discard, fixed, coef,
-               device, vmap, specialize_fused, n_total, shard_start, reduce):
+               device, vmap, specialize_fused, n_total, shard_start, reduce, polar=None):
     """The driver behind :func:`vegas_integrate` (``dmap`` None: results ``[R]``) and :func:`vegas_integrate_binned` (``[n_bin, R]``)."""
     import torch
     handle = getattr(func_or_handle, "handle", func_or_handle)
     device = torch.device(device)
     n_col_k, n_tau = int(tables.n_loop) * int(tables.dim), int(tables.n_tau)
     n_col, R = n_col_k + n_tau, handle.table.n_root
-    col = [int(c) for c in col]
-    if len(set(col)) != len(col) or not all(0 <= c < n_col for c in col):
+    col = [None if (c is None and polar) else int(c) for c in col]
+    written = [c for c in col if c is not None] + [c for p in (polar or ()) for c in p.cols]
+    if len(set(written)) != len(written) or not all(0 <= c < n_col for c in written):
         raise ValueError(f"col must name distinct columns in [0, {n_col})")
     if dmap is not None:
-        if not all(0 <= e < n_col for e in dmap.ext_col) or set(dmap.ext_col) & set(col):
+        if not all(0 <= e < n_col for e in dmap.ext_col) or set(dmap.ext_col) & set(written):
             raise ValueError(f"dmap.ext_col must name columns in [0, {n_col}) that col does not")
         if dmap.device != device:
             raise ValueError("dmap lives on another device")
@@ -115,6 +173,9 @@ def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter,
         vmap = VegasMap(uniform_grid(lo, hi, n_grid), device)
     if vmap.n_dim != len(col):
         raise ValueError("one column per variable of the map")
+    groups = _check_polar(polar, col, vmap, n_col) if polar else None
+    if polar and any(c is None for d, c in enumerate(col) if not any(v <= d < v + len(cs) for v, cs in groups)):
+        raise ValueError("only the variables of a polar group go without a column")
     D, G, NB = vmap.n_dim, vmap.n_grid, 1 if dmap is None else dmap.n_bin
     B = int(n_sample)
     N = B if n_total is None else int(n_total)
@@ -142,14 +203,20 @@ def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter,
             off = it * N + int(shard_start)
             m = torch.zeros((2, NB, R), dtype=torch.float64, device=device)
             hist = torch.zeros((D, G), dtype=torch.float64, device=device)
-            if dmap is None:
+            if groups:
+                capi.vegas_sample_device_polar(vmap.d_grid.data_ptr(), D, G, col, 0 if dmap is None else dmap.d_cdf.data_ptr(), NB, 0,
+                                               0 if dmap is None else d_ext, None if dmap is None else dmap.ext_col, groups, seed, off,
+                                               x.data_ptr(), 1, B, jac.data_ptr(), 0 if dmap is None else bins.data_ptr(), 0, B, st)
+            elif dmap is None:
                 capi.vegas_sample_device(vmap.d_grid.data_ptr(), D, G, col, seed, off, x.data_ptr(), 1, B, jac.data_ptr(), 0, B, st)
+            else:
+                capi.vegas_sample_device_discrete(vmap.d_grid.data_ptr(), D, G, col, dmap.d_cdf.data_ptr(), NB, 0, d_ext, dmap.ext_col, seed,
+                                                  off, x.data_ptr(), 1, B, jac.data_ptr(), bins.data_ptr(), 0, B, st)
+            if dmap is None:
                 handle.mc_accumulate_device_vegas(x.data_ptr(), 1, B, d_T, 1, B, kF, beta, lam, jac.data_ptr(), coef, seed, off, D, G,
                                                   m[0].data_ptr(), m[1].data_ptr(), hist.data_ptr(), B, st)
                 sums = [m, hist]
             else:
-                capi.vegas_sample_device_discrete(vmap.d_grid.data_ptr(), D, G, col, dmap.d_cdf.data_ptr(), NB, 0, d_ext, dmap.ext_col, seed,
-                                                  off, x.data_ptr(), 1, B, jac.data_ptr(), bins.data_ptr(), 0, B, st)
                 hist_bin = torch.zeros(NB, dtype=torch.float64, device=device)
                 handle.mc_accumulate_device_vegas_binned(x.data_ptr(), 1, B, d_T, 1, B, kF, beta, lam, bins.data_ptr(), 0, NB, jac.data_ptr(),
                                                          coef, seed, off, D, G, m[0].data_ptr(), m[1].data_ptr(), hist.data_ptr(),
@@ -175,7 +242,7 @@ def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter,
 def vegas_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: float = 1.0, lam: float = 0.0, *, n_iter: int = 10,
                     n_sample: int = 100_000, n_grid: int = 64, alpha: float = 0.5, seed: int = 0, n_discard: int = 0, fixed=None,
                     coef=None, device="cuda", vmap: Optional[VegasMap] = None, specialize_fused: bool = True, n_total: Optional[int] = None,
-                    shard_start: int = 0, reduce: Optional[Callable] = None) -> VegasResult:
+                    shard_start: int = 0, reduce: Optional[Callable] = None, polar: Optional[Sequence[PolarVar]] = None) -> VegasResult:
     """Integrates the roots of a graph over the box ``[lo, hi]`` of ``len(col)`` of its Monte-Carlo variables.
 
     ``func_or_handle``: a ``GraphFunc`` or ``capi.GraphHandle``; ``tables`` the ``fdg_leaf_tables`` struct of ``capi.make_leaf_tables``
@@ -187,9 +254,14 @@ def vegas_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: 
 
     Sharding: every rank passes its ``shard_range`` start and count as ``shard_start`` / ``n_sample``, the whole iteration as
     ``n_total``, and ``reduce`` = a function that sums a CUDA tensor over the ranks in place (``sharding.reduce_observable``); it is
-    applied to the ``[2, 1, R]`` moments and to the histogram, so every rank refines the same map."""
+    applied to the ``[2, 1, R]`` moments and to the histogram, so every rank refines the same map.
+
+    ``polar``: a sequence of :class:`PolarVar`.  The variables of a group are a modulus and a direction (``lo`` / ``hi`` rows as
+    :func:`ball` gives them), their ``col`` entries are None, and the group's own ``cols`` take the Cartesian components; the weight
+    carries ``k`` or ``k**2 sin(theta)``.  The limits (of ``lo`` / ``hi`` or of a ``vmap`` passed in) must keep ``k >= 0``, ``theta``
+    within ``[0, math.pi]`` and ``phi`` within ``[0, 2 * math.pi]``.  None or empty: the box, with the bits it always had."""
     return _integrate(func_or_handle, tables, lo, hi, col, None, kF, beta, lam, n_iter, n_sample, n_grid, alpha, 0.0, seed, n_discard, fixed, coef,
-                      device, vmap, specialize_fused, n_total, shard_start, reduce)
+                      device, vmap, specialize_fused, n_total, shard_start, reduce, polar)
 
 
 def uniform_cdf(n_bin: int) -> np.ndarray:
@@ -265,13 +337,13 @@ def vegas_integrate_binned(func_or_handle, tables, lo, hi, col, dmap: DiscreteMa
                            n_iter: int = 10, n_sample: int = 100_000, n_grid: int = 64, alpha: float = 0.5, floor: float = 0.05, seed: int = 0,
                            n_discard: int = 0, fixed=None, coef=None, device="cuda", vmap: Optional[VegasMap] = None,
                            specialize_fused: bool = True, n_total: Optional[int] = None, shard_start: int = 0,
-                           reduce: Optional[Callable] = None) -> VegasBinnedResult:
+                           reduce: Optional[Callable] = None, polar: Optional[Sequence[PolarVar]] = None) -> VegasBinnedResult:
     """:func:`vegas_integrate` with a discrete variable: every sample draws a value ``j`` of ``dmap`` next to its continuous variables,
     the columns ``dmap.ext_col`` take row ``j`` of ``dmap.ext`` (external momenta), and the estimate is per value: arrays ``[n_bin, R]``,
     bin ``j`` the integral over the continuous variables at configuration ``j`` (the weight carries ``1 / p_j``, and ``mc_estimate``
     takes the whole batch as ``N``).  Per iteration: sample, accumulate (binned moments and both training histograms in one pass),
     ``mc_estimate``, refine the map with ``alpha`` and the probabilities with ``alpha`` and ``floor``.  ``combine`` is per (bin, root).
     Sharding as in :func:`vegas_integrate`; ``reduce`` is applied to the moments ``[2, n_bin, R]`` and to both histograms, so every rank
-    refines the same maps."""
+    refines the same maps.  ``polar`` as in :func:`vegas_integrate`."""
     return _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter, n_sample, n_grid, alpha, floor, seed, n_discard, fixed,
-                      coef, device, vmap, specialize_fused, n_total, shard_start, reduce)
+                      coef, device, vmap, specialize_fused, n_total, shard_start, reduce, polar)

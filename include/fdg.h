@@ -701,6 +701,49 @@ int fdg_mc_accumulate_device_vegas_binned(fdg_graph *g, const double *d_K, int64
  * moments I2_j / p_j.  floor keeps every bin sampled (a bin with p = 0 would silently lose its estimate). */
 int fdg_vegas_refine_discrete(double *cdf, const double *hist_bin, uint32_t n_bin, double alpha, double floor);
 
+/* ---- Spherical momentum variables for VEGAS ---------------------------------------------------------------------------------------
+ * The reference integrates its loop momenta as MCIntegration.FermiK(dim, kF, 0.2 kF, 10 kF) (example/benchmark.jl:46,
+ * example/benchmark_GV.jl:47, test/ver4.jl:224): a vector with a modulus and a direction, over a ball with the measure
+ * k^(dim-1) dk dOmega.  MCIntegration is not part of the reference checkout: no counterpart in the reference; the caller's side of those
+ * lines.  Here a group of 2 or 3 consecutive VEGAS variables is read as (k, phi) or (k, theta, phi), and the sampler writes the
+ * Cartesian components into the columns of x the evaluator reads; the map stays separable in the polar variables, which is what
+ * follows a shell |K| ~ kF with one variable.
+ *
+ * Group g = polar[g] takes the variables var, var + 1 (dim 2: k, phi) or var, var + 1, var + 2 (dim 3: k, theta, phi) and writes
+ * the columns col[0 .. dim).  fdg_vegas_sample_device_polar: for sample b < n_sample, every step one rounded fp64 operation, in this order,
+ *   1. every variable d < n_dim exactly as fdg_vegas_sample_device draws it: v_d = grid[d][c] + fr * wd, jc the same left fold of
+ *      G * wd_d over ALL d, the same d_cell entries.  A variable of no group: v_d -> column col[d] as there.  A variable of a group is
+ *      written nowhere, and its col[d] is not read.
+ *   2. the groups, in the order of the array:
+ *        dim 3: (st, ct) = fdg_sincos(theta); (sp, cp) = fdg_sincos(phi); ks = k * st;
+ *               ks * cp -> col[0], ks * sp -> col[1], k * ct -> col[2];   jc = jc * k; jc = jc * k; jc = jc * st
+ *        dim 2: (sp, cp) = fdg_sincos(phi);   k * cp -> col[0], k * sp -> col[1];   jc = jc * k
+ *   3. d_cdf != NULL: the discrete variable exactly as fdg_vegas_sample_device_discrete (Philox column n_dim, jc / p -> d_jac[b], the
+ *      bin, the table's row).  d_cdf == NULL: no discrete variable; jc -> d_jac[b]; n_bin, bin_base, d_bin, d_ext, n_ext and ext_col are
+ *      ignored and d_bin may be NULL.
+ * n_polar == 0 gives the bits of fdg_vegas_sample_device (d_cdf NULL) or of fdg_vegas_sample_device_discrete.  polar is a HOST array.
+ * The result is a function of the arguments only (counter-based), so shards reproduce the unsharded batch.  The training pass of
+ * the accumulate calls recomputes a sample's cells from its Philox counters and never looks at x, so they serve unchanged with
+ * n_dim = the number of VEGAS variables.
+ * The edges live in device memory and are not read on the host: that k >= 0, theta lies in [0, pi] and phi in [0, 2 pi] (fdg_sincos'
+ * domain; a weight carries sin theta, which is >= 0 on [0, fl(pi)]) is the caller's to keep.
+ * FDG_E_INVALID: polar NULL with n_polar > 0, a dim that is not 2 or 3, var + dim > n_dim, two groups sharing a variable, a column
+ * named twice among the col[d] of the variables of no group, the groups' columns and (with d_cdf) ext_col, and the cases of
+ * fdg_vegas_sample_device / _discrete; FDG_E_UNSUPPORTED: n_polar > FDG_VEGAS_POLAR_MAX and those calls' limits.  All before any
+ * device work. */
+#define FDG_VEGAS_POLAR_MAX 21
+typedef struct fdg_vegas_polar { uint32_t var, dim, col[3]; } fdg_vegas_polar;
+int fdg_vegas_sample_device_polar(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, const double *d_cdf,
+                                  uint32_t n_bin, int32_t bin_base, const double *d_ext, uint32_t n_ext, const uint32_t *ext_col,
+                                  const fdg_vegas_polar *polar, uint32_t n_polar, uint64_t seed, uint64_t sample_offset, double *d_x,
+                                  int64_t x_sample_stride, int64_t x_col_stride, double *d_jac, int32_t *d_bin, int32_t *d_cell,
+                                  int64_t n_sample, void *stream);
+/* The sine and cosine the sampler uses, for 0 <= x <= 2 pi (the double nearest above included): Cody-Waite reduction to a quadrant,
+ * two Horner polynomials, selection; no FMA, the order of every operation and every constant in csrc/fdg_sincos.h, so a restatement
+ * in numpy gives the same bits.  |s - sin x|, |c - cos x| <= 4 * 2^-53; s >= 0 on [0, fl(pi)].  Exposed so host-side checkers can
+ * call the very same routine.  Pure host function. */
+void fdg_sincos(double x, double *s, double *c);
+
 /* Device workspace control: the interpreter keeps per-sample overflow slots in
  * an HBM panel owned by the handle; it is sized on first use for the number of
  * resident waves.  This releases it (and any loaded module). */
