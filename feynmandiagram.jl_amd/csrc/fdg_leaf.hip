@@ -119,6 +119,17 @@ fdg_leaf_kernel(const int32_t *__restrict__ ltype, const int32_t *__restrict__ l
   }
 }
 
+// Leaves without a formula (leaf_type 0) keep leafstates' initial value 1.0.  The leaf kernels above and below never write
+// their columns (fdg_leaf_eval_device's contract: the caller's buffer keeps what it held); the split Monte-Carlo route owns
+// its chunk of leaves and stores the constant with this kernel on every call, in the layout of that call.
+__global__ void __launch_bounds__(256)
+fdg_leaf_ones_kernel(const int32_t *__restrict__ idx, uint32_t n_idx, double *__restrict__ leaf, long ls, long n) {
+  for (uint32_t c = blockIdx.y; c < n_idx; c += gridDim.y) {
+    double *col = leaf + (long)idx[c] * ls;
+    for (long b = (long)blockIdx.x * 256 + threadIdx.x; b < n; b += (long)gridDim.x * 256) col[b] = 1.0;
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Leaf kernel specialised to one set of leafstates tables (the same JIT route as the graph kernels):
 // indices, the loop basis (almost all entries 0 / +-1) and the leaf order are compile-time constants, so
@@ -280,6 +291,8 @@ struct LeafPlan {
   hipFunction_t fn = nullptr;      // specialised kernel, or nullptr: table-driven kernel with d_tab
   char *d_tab = nullptr;
   size_t ib = 0, boff = 0, lds = 0;
+  int32_t *d_const = nullptr;      // the leaves without a formula (original indices), for the split Monte-Carlo route
+  uint32_t n_const = 0;
 };
 
 static int leaf_plan(const fdg_leaf_tables *tab, const LeafPlan **out) {
@@ -326,8 +339,27 @@ static int leaf_plan(const fdg_leaf_tables *tab, const LeafPlan **out) {
     }
     if (p->lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)fdg_leaf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds));
   }
+  std::vector<int32_t> h_const;
+  for (uint32_t i = 0; i < L; ++i) if (tab->leaf_type[i] == 0) h_const.push_back((int32_t)i);
+  if (!h_const.empty()) {
+    if (hipMalloc((void **)&p->d_const, h_const.size() * sizeof(int32_t)) != hipSuccess ||
+        hipMemcpy(p->d_const, h_const.data(), h_const.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
+      if (p->d_tab) (void)hipFree(p->d_tab);
+      delete p; set_error("leaf tables: device allocation / copy failed"); return FDG_E_NOMEM;
+    }
+    p->n_const = (uint32_t)h_const.size();
+  }
   cache.push_back(p);
   *out = p;
+  return FDG_OK;
+}
+
+// 1.0 into the columns of the leaves without a formula: leaf-major chunk, leaf stride ls, n samples
+static int leaf_launch_ones(const LeafPlan *p, double *d_leaf, int64_t ls, int64_t n, hipStream_t st) {
+  if (!p->n_const || n <= 0) return FDG_OK;
+  const unsigned gx = (unsigned)std::min<int64_t>((n + 255) / 256, 1024), gy = std::min<uint32_t>(p->n_const, 4096u);
+  hipLaunchKernelGGL(fdg_leaf_ones_kernel, dim3(gx, gy), dim3(256), 0, st, (const int32_t *)p->d_const, p->n_const, d_leaf, (long)ls, (long)n);
+  HIP_TRY(hipGetLastError());
   return FDG_OK;
 }
 
@@ -491,16 +523,16 @@ int fdg_mc_run_locked(fdg_graph *g, int mode, const double *d_K, int64_t ks, int
       if (g->d_ws4) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(g->d_ws4)); g->d_ws4 = nullptr; g->ws4_bytes = 0; }
       if (hipMalloc(&g->d_ws4, need) != hipSuccess) { set_error("hipMalloc(leaf chunk) failed"); return FDG_E_NOMEM; }
       g->ws4_bytes = need;
-      // leaves without a formula keep leafstates' initial value 1.0
-      std::vector<double> ones((size_t)Bc, 1.0);
-      for (uint32_t i = 0; i < g->prog.L; ++i)
-        if (tab.leaf_type[i] == 0) HIP_TRY(hipMemcpy((double *)g->d_ws4 + (size_t)i * Bc, ones.data(), (size_t)Bc * 8, hipMemcpyHostToDevice));
     }
+    // The chunk's leaf stride is this call's Bc and the buffer is shared with route 3 (packed K, T): nothing in it outlives a
+    // call, so the constant columns (leaves without a formula: 1.0) are stored next to the computed ones, chunk by chunk.
     hipStream_t st = (hipStream_t)stream;
     double *d_leaf = (double *)g->d_ws4;
     for (int64_t c0 = 0; c0 < B; c0 += Bc) {
       const int64_t n = std::min<int64_t>(Bc, B - c0);
       rc = leaf_launch(plan, &tab, d_K + c0 * ks, ks, kc, d_T + c0 * ts, ts, tc, d_leaf, 1, Bc, n, st);
+      if (rc) return rc;
+      rc = leaf_launch_ones(plan, d_leaf, Bc, n, st);
       if (rc) return rc;
       rc = fdg_run_locked(g, mode, d_leaf, 1, Bc, mode == 0 ? d_root + c0 * rs : nullptr, rs, rk, d_weight ? d_weight + c0 : nullptr, d_acc, n, st);
       if (rc) return rc;

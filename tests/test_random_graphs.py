@@ -244,9 +244,11 @@ def test_fuzz_isa_register_budgets_on_device(libfdg, cuda, tmp_path, monkeypatch
 # --------------------------------------------------------------------------- #
 # one-kernel Monte-Carlo step on random graphs over random leaf tables
 # --------------------------------------------------------------------------- #
-def random_leaf_tables(seed: int, L: int):
+def random_leaf_tables(seed: int, L: int, max_interaction_order=None):
     """A random partition in the shape FrontEnds.leafstates produces (frontends.jl:178-232): fermionic leaves with
-    green_derive orders 0..5 and interaction leaves with counter-term orders 0..6 over a random loop basis."""
+    green_derive orders 0..5 and interaction leaves with counter-term orders 0..6 over a random loop basis.
+    ``max_interaction_order``: the same tables with the interaction orders clipped to it (3: what the specialised leaf
+    kernel and the compiler-scheduled fused kernel cover)."""
     rng = np.random.default_rng(1000 + seed)
     n_loop, n_tau, n_basis = int(rng.integers(1, 5)), int(rng.integers(1, 6)), int(rng.integers(1, 9))
     basis = rng.choice([-1.0, 0.0, 0.0, 1.0, 1.0, 0.5], size=(n_basis, n_loop))
@@ -256,6 +258,8 @@ def random_leaf_tables(seed: int, L: int):
     ty = rng.choice([1, 1, 1, 2, 2, 0], size=L).astype(np.int32)     # 0: a leaf without a formula (value 1.0)
     order = np.where(ty == 1, rng.integers(0, 6, size=L), rng.integers(0, 7, size=L)).astype(np.int32)
     order[rng.random(L) < 0.5] = 0
+    if max_interaction_order is not None:
+        order = np.where(ty == 2, np.minimum(order, max_interaction_order), order).astype(np.int32)
     return dict(leaf_type=ty, leaf_order=order, tau_in=rng.integers(1, n_tau + 1, size=L).astype(np.int32),
                 tau_out=rng.integers(1, n_tau + 1, size=L).astype(np.int32), loop_index=rng.integers(1, n_basis + 1, size=L).astype(np.int32),
                 basis=basis, n_tau=n_tau, n_loop=n_loop)
