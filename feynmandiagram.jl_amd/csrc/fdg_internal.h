@@ -105,6 +105,21 @@ struct fdg_launch_cfg {
   long long eval_chunk = 0, mc_chunk = 0;  // host-buffer / Monte-Carlo chunk sizes in samples (0: the library's)
 };
 
+// The kernels one code object of the optimizing back end may hold, and what the launch path knows of each.  A kernel's symbol is the code
+// object's base name ("fdg_isa_eval", "fdg_isa_mc") + the suffix below; vgpr, lds_bytes and threads are what the emitter assembled
+// (fdg_opt.h: IsaKernelRecord), mem_slots the program's panel slots; fn is resolved when the module is loaded.
+enum { FDG_K_EVAL = 0, FDG_K_NT, FDG_K_W2, FDG_K_ACC, FDG_K_ACC_NT, FDG_K_RM, FDG_K_RM_ACC, FDG_K_RL, FDG_K_RL_ACC, FDG_K_COOP, FDG_K_POOL, FDG_K_COUNT };
+//   plain | streaming (non-temporal, line-aligned batches) | two samples per lane | fused accumulation | ... streaming | row-major (chunks staged in
+//   LDS) | ... accumulating | linear row-major (contiguous rows, LDS image) | ... accumulating | cooperative (a CU's waves on one tile) | pooled cooperative
+static const char *const FDG_ISA_KERNEL[FDG_K_COUNT] = {"fdg_isa_eval", "fdg_isa_eval_nt", "fdg_isa_eval_w2", "fdg_isa_eval_acc", "fdg_isa_eval_acc_nt",
+    "fdg_isa_eval_rm", "fdg_isa_eval_rm_acc", "fdg_isa_eval_rl", "fdg_isa_eval_rl_acc", "fdg_isa_eval_coop", "fdg_isa_eval_pool"};
+inline const char *fdg_isa_suffix(int k) { return FDG_ISA_KERNEL[k] + sizeof("fdg_isa_eval") - 1; }
+struct fdg_isa_kernel {
+  bool present = false;
+  void *fn = nullptr;              // hipFunction_t
+  uint32_t vgpr = 0, lds_bytes = 0, mem_slots = 0, threads = 64;
+};
+
 struct fdg_graph {
   fdg::Lowered prog;
   fdg::KnobMap knobs;              // this handle's options (starts as a copy of fdg::env_snapshot(); fdg_graph_set_option)
@@ -129,49 +144,19 @@ struct fdg_graph {
   size_t ws_bytes = 0;
   void *module = nullptr;          // hipModule_t
   void *fn_eval_sm = nullptr, *fn_eval_gen = nullptr;  // hipFunction_t
-  // ISA specialization (fdg_isa.cpp): one wave = 64 samples, persistent grid
+  // ISA specialization (fdg_isa.cpp): one wave = 64 samples, persistent grid; the kernels of the code object, [FDG_K_*]
   bool isa = false;
-  void *fn_isa = nullptr;
-  void *fn_isa_nt = nullptr, *fn_isa_acc_nt = nullptr;   // streaming variants (non-temporal leaf loads / root stores) for line-aligned batches
-  uint32_t isa_vgpr = 0, isa_lds_bytes = 0, isa_mem_slots = 0;
-  // optional two-samples-per-lane variant in the same code object (sample stride 1, full 128-sample tiles)
-  bool has_w2 = false;
-  void *fn_isa_w2 = nullptr;
-  uint32_t isa2_vgpr = 0, isa2_lds_bytes = 0, isa2_mem_slots = 0;
-  // fused accumulate variant (per-lane accumulators in VGPRs, roots never written)
-  bool has_acc = false;
   bool isa_fma = false;            // FDG_SPEC_FAST_MATH with FDG_SPEC_ISA: fused multiply-adds (not parity-exact)
-  void *fn_isa_acc = nullptr;
-  uint32_t isa3_vgpr = 0, isa3_lds_bytes = 0, isa3_mem_slots = 0;
-  // row-major variant (leaf stride 1: compile_Python's [B, L]): chunks of rows staged through LDS inside the evaluator
-  bool has_rm = false;
-  void *fn_isa_rm = nullptr;
-  uint32_t isa4_vgpr = 0, isa4_lds_bytes = 0, isa4_mem_slots = 0;
-  // ... and its fused-accumulate form (row-major leaves, roots never written)
-  bool has_rm_acc = false;
-  void *fn_isa_rm_acc = nullptr;
-  uint32_t isa5_vgpr = 0, isa5_lds_bytes = 0, isa5_mem_slots = 0;
+  fdg_isa_kernel kern[FDG_K_COUNT];
   // what the installed programs execute per evaluation (fdg_graph_kernel_info): [0] eval, [1] accumulate, [2] row-major
   uint64_t st_valu[3] = {0, 0, 0};
   uint32_t st_ld_leaf[3] = {0, 0, 0}, st_panel[3] = {0, 0, 0}, st_lds[3] = {0, 0, 0};
-  uint32_t rm_bufs = 0;
   const char *last_kernel = "";    // evaluator kernel of the last device call (guarded by mu)
-  // cooperative variant: the four waves of a CU evaluate one tile together (graphs whose live set overflows one lane)
-  bool has_coop = false, coop_enabled = false;
-  void *fn_isa_coop = nullptr;
-  uint32_t coop_panel_wg = 0, coop_lds_bytes = 0, coop_threads = 256;
-  // linear row-major variant: contiguous rows, the tile's block streamed into an LDS image
-  bool has_rl = false;
-  void *fn_isa_rl = nullptr;
-  uint32_t isa6_vgpr = 0, isa6_lds_bytes = 0, isa6_mem_slots = 0;
-  bool has_rl_acc = false;           // the linear row-major variant with fused accumulation
-  void *fn_isa_rl_acc = nullptr;
-  uint32_t isa7_vgpr = 0, isa7_lds_bytes = 0, isa7_mem_slots = 0;
-  uint64_t rl_valu = 0;
-  // pooled cooperative variant: the waves of a CU evaluate one tile, whole roots each, leaves through a shared LDS pool (full tiles, sample stride 1)
-  bool has_pool = false;
-  void *fn_isa_pool = nullptr;
-  uint32_t pool_panel_wg = 0, pool_threads = 256, pool_fetch = 0, pool_unit = 1;
+  uint32_t rm_bufs = 0;            // FDG_K_RM / _RM_ACC: LDS staging buffers
+  uint64_t rl_valu = 0;            // FDG_K_RL: fold steps per evaluation
+  bool coop_enabled = false;       // FDG_K_COOP: the tuner's verdict (a variant that is present but measured slower stays off)
+  uint32_t coop_panel_wg = 0;      // FDG_K_COOP / FDG_K_POOL: bytes of spill panel per workgroup (the sum over its waves)
+  uint32_t pool_panel_wg = 0, pool_fetch = 0, pool_unit = 1;
   uint64_t pool_valu = 0;
   // companion HIP-source kernels of an ISA-specialised handle, used for sample-major input (FDG_SPEC_ROW_MAJOR_COMPANION)
   std::vector<char> alt_code;
@@ -192,9 +177,9 @@ struct fdg_graph {
   uint32_t lt_hdr[5] = {0, 0, 0, 0, 0};   // n_leaf, n_basis, n_loop, dim, n_tau
   // ... or (route 3) ONE kernel of the optimizing back end whose leaves are computed in registers from (K, T)
   std::vector<char> mc_code;
-  void *mc_module = nullptr, *fn_mc = nullptr, *fn_mc_acc = nullptr;
-  bool mc_has_acc = false, mc_built = false;
-  uint32_t mc_vgpr[2] = {0, 0}, mc_lds[2] = {0, 0}, mc_mem[2] = {0, 0};   // [0] eval kernel, [1] accumulate kernel
+  void *mc_module = nullptr;
+  bool mc_built = false;
+  fdg_isa_kernel mc_kern[FDG_K_COUNT];   // fdg_isa_mc (FDG_K_EVAL) and fdg_isa_mc_acc (FDG_K_ACC)
   std::string mc_dir;
   unsigned mc_flags = 0;
   void *d_ws4 = nullptr;           // leaf-major chunk of leaves for route 2 / packed (K, T) columns for route 3

@@ -1641,11 +1641,13 @@ std::string isa_hazard_table() {
   return os.str();
 }
 
-// One code object: the W = 1 kernel `kname`, and, when prog2 is given, the two-samples-per-lane kernel
-// `kname`_w2 next to it.
-std::string emit_isa(const Lowered &p, const OptProgram &prog, const std::string &kname, const OptProgram *prog2,
-                     const OptProgram *prog_acc, const OptProgram *prog_rm, uint32_t rm_bufs, const CoopProgram *coop,
-                     const OptProgram *prog_rm_acc, const CoopProgram *pool, const OptProgram *prog_rl, const OptProgram *prog_rl_acc) {
+// One code object: the kernels of the programs in V (fdg_opt.h: IsaPrograms); `records`, when given, gets what was assembled for each.
+std::string emit_isa(const Lowered &p, const IsaPrograms &V, std::vector<IsaKernelRecord> *records) {
+  const OptProgram &prog = *V.main, *prog2 = V.w2_prog(), *prog_acc = V.acc_prog(), *prog_rm = V.rm_prog(), *prog_rm_acc = V.rm_acc_prog(), *prog_rl = V.rl_prog(),
+                   *prog_rl_acc = V.rl_acc_prog();
+  const CoopProgram *coop = V.coop_prog(), *pool = V.pool_prog();
+  const std::string &kname = V.kname;
+  const uint32_t rm_bufs = V.rm_bufs;
   Emit E;
   { const char *a = fdg::knob("FDG_ISA_ALIGN"); E.align = a && a[0] >= '0' && a[0] <= '2' ? a[0] - '0' : 1; }
   { const char *a = fdg::knob("FDG_ISA_SHIFT"); E.shift = a ? std::atoi(a) : 0; }
@@ -1676,12 +1678,12 @@ std::string emit_isa(const Lowered &p, const OptProgram &prog, const std::string
     if (prog_acc && prog_acc->ops.size() <= 60000) ks.push_back(emit_kernel(E, p, *prog_acc, kname + "_acc_nt", 1, true));
     E.streaming = false;
   }
-  if (prog_rm && rm_bufs) ks.push_back(emit_kernel(E, p, *prog_rm, kname + "_rm", 1, false, rm_bufs));
-  if (prog_rm_acc && rm_bufs) ks.push_back(emit_kernel(E, p, *prog_rm_acc, kname + "_rm_acc", 1, true, rm_bufs));
+  if (prog_rm) ks.push_back(emit_kernel(E, p, *prog_rm, kname + "_rm", 1, false, rm_bufs));
+  if (prog_rm_acc) ks.push_back(emit_kernel(E, p, *prog_rm_acc, kname + "_rm_acc", 1, true, rm_bufs));
   if (prog_rl) ks.push_back(emit_kernel(E, p, *prog_rl, kname + "_rl", 1, false, 0, nullptr, true));
-  if (prog_rl && prog_rl_acc) ks.push_back(emit_kernel(E, p, *prog_rl_acc, kname + "_rl_acc", 1, true, 0, nullptr, true));
-  if (coop && coop->supported) { ks.push_back(emit_coop(E, p, *coop, kname + "_coop")); ks.back().wg = 64 * coop->n_wave; }
-  if (pool && pool->supported) { ks.push_back(emit_coop(E, p, *pool, kname + "_pool")); ks.back().wg = 64 * pool->n_wave; }
+  if (prog_rl_acc) ks.push_back(emit_kernel(E, p, *prog_rl_acc, kname + "_rl_acc", 1, true, 0, nullptr, true));
+  if (coop) { ks.push_back(emit_coop(E, p, *coop, kname + "_coop")); ks.back().wg = 64 * coop->n_wave; }
+  if (pool) { ks.push_back(emit_coop(E, p, *pool, kname + "_pool")); ks.back().wg = 64 * pool->n_wave; }
   std::ostringstream &os = E.os;
   os << "\t.text\n\t.amdgpu_metadata\n---\namdhsa.kernels:\n";
   const char *kinds[18] = {"global_buffer", "by_value", "by_value", "global_buffer", "by_value", "by_value",
@@ -1700,6 +1702,7 @@ std::string emit_isa(const Lowered &p, const OptProgram &prog, const std::string
     os << "    .uniform_work_group_size: 1\n    .uses_dynamic_stack: false\n    .vgpr_count: " << (k.accum + k.n_agpr)
        << "\n    .vgpr_spill_count: 0\n    .wavefront_size: 64\n";
   }
+  if (records) for (const KernelMeta &k : ks) records->push_back(IsaKernelRecord{k.name, k.accum + k.n_agpr, k.lds_bytes, k.wg});
   os << "amdhsa.target: amdgcn-amd-amdhsa--gfx950\namdhsa.version:\n  - 1\n  - 2\n...\n\t.end_amdgpu_metadata\n";
   return os.str();
 }

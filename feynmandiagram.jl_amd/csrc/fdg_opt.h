@@ -141,12 +141,6 @@ void build_mc_program(const Lowered &p, const LeafSpec &ls, const OptParams &prm
 // (value << 1) | negate.  kind: M_MUL d = a*b, M_ADD d = a+b, M_MULC d = a*imm, M_ROOT root[d] = a.
 struct SchedOp { uint8_t kind; uint32_t d, a, b; double imm; };
 bool build_schedule(const Lowered &p, const OptParams &prm, std::vector<SchedOp> &ops, uint32_t &n_value, std::string &why);
-struct CoopProgram;
-std::string emit_isa(const Lowered &p, const OptProgram &prog, const std::string &kname, const OptProgram *prog2 = nullptr,
-                     const OptProgram *prog_acc = nullptr, const OptProgram *prog_rm = nullptr, uint32_t rm_bufs = 0,
-                     const CoopProgram *coop = nullptr, const OptProgram *prog_rm_acc = nullptr, const CoopProgram *pool = nullptr,
-                     const OptProgram *prog_rl = nullptr, const OptProgram *prog_rl_acc = nullptr);
-
 // Cooperative variant: the four waves of a CU (one per SIMD) evaluate ONE 64-sample tile together.  Each wave runs its own
 // straight-line program on its share of the graph with its own registers, AGPRs, private LDS slots and panel; a value
 // another wave needs is published into a shared LDS slot (M_SEND) and becomes readable after the next M_BARRIER (M_RECV).
@@ -182,6 +176,29 @@ void build_coop_program(const Lowered &p, const OptParams &prm, CoopProgram &out
 // leaves 2-3 times in the one-wave kernels because 324 on-chip values per sample cannot hold their 1000-1500 leaves; a CU's eight waves and the
 // pool together hold 1200.
 void build_pool_program(const Lowered &p, const OptParams &prm, CoopProgram &out, uint32_t n_wave = 8, uint32_t epoch_ops = 0, uint32_t ahead = 0);
+
+// The programs of one code object, owned here except the main one.  emit_isa prints them as `kname`, `kname`_w2, _acc, _rm, _rm_acc, _rl, _rl_acc,
+// _coop, _pool (and the streaming copies _nt / _acc_nt where they pay); the accessors say which of them the code object gets.
+struct IsaPrograms {
+  const OptProgram *main = nullptr;
+  std::string kname = "fdg_isa_eval";
+  OptProgram p2, pa, pr, pra, prl, prla;
+  CoopProgram coop, pool;
+  bool w2 = false, acc = false, rm_acc = false, rl = false, rl_acc = false;
+  uint32_t rm_bufs = 0;        // staging buffers of the row-major programs (0: none)
+  int coop_verdict = -1;       // a remembered measurement: 0 = the cooperative variant loses, 4 / 8 = it wins with that many waves; -1: none
+  const OptProgram *w2_prog() const { return w2 ? &p2 : nullptr; }
+  const OptProgram *acc_prog() const { return acc ? &pa : nullptr; }
+  const OptProgram *rm_prog() const { return rm_bufs ? &pr : nullptr; }
+  const OptProgram *rm_acc_prog() const { return rm_bufs && rm_acc ? &pra : nullptr; }
+  const OptProgram *rl_prog() const { return rl ? &prl : nullptr; }
+  const OptProgram *rl_acc_prog() const { return rl && rl_acc ? &prla : nullptr; }
+  const CoopProgram *coop_prog() const { return coop.supported ? &coop : nullptr; }
+  const CoopProgram *pool_prog() const { return pool.supported ? &pool : nullptr; }
+};
+// What the emitter assembled for one kernel, as its kernel descriptor states it: the launch plan sizes grids and occupancy from these
+struct IsaKernelRecord { std::string name; uint32_t vgpr = 0 /* accum offset + AGPRs */, lds_bytes = 0, threads = 64; };
+std::string emit_isa(const Lowered &p, const IsaPrograms &V, std::vector<IsaKernelRecord> *records = nullptr);
 
 void rm_plan_stats(const Lowered &p, const OptProgram &prog, uint32_t bufs, uint64_t &fetches, uint64_t &gathers);
 // gfx950 wait-state table of the emitter (fdg_isa.cpp): check of a finished listing, and the table as text

@@ -580,25 +580,36 @@ int root_live_mask(fdg_graph *g, const uint8_t **out) {
   return FDG_OK;
 }
 
+// Resident waves per CU of a one-wave kernel: bounded by its VGPRs (512 per SIMD, allocated in eights), its LDS (160 KB per CU) and 32 waves
+static uint32_t isa_waves_per_cu(uint32_t vgpr, uint32_t lds_bytes) {
+  const uint32_t valloc = std::max<uint32_t>(8, (vgpr + 7) & ~7u);
+  uint32_t per_cu = std::min<uint32_t>(8, 512 / valloc) * 4;
+  if (lds_bytes) per_cu = std::min<uint32_t>(per_cu, (160u * 1024u) / lds_bytes);
+  return std::max<uint32_t>(1, std::min<uint32_t>(per_cu, 32));
+}
+
+// The kernels a code object of the optimizing back end was assembled with, by name (`kname` + suffix): a missing one is an error
+static int resolve_isa_kernels(hipModule_t m, const std::string &kname, fdg_isa_kernel *kern) {
+  for (int k = 0; k < FDG_K_COUNT; ++k) {
+    if (!kern[k].present) continue;
+    hipFunction_t f;
+    const hipError_t e = hipModuleGetFunction(&f, m, (kname + fdg_isa_suffix(k)).c_str());
+    if (e != hipSuccess) { hipModuleUnload(m); set_error("kernel " + kname + fdg_isa_suffix(k) + " is missing from its code object: " + hipGetErrorString(e)); return FDG_E_NO_DEVICE; }
+    kern[k].fn = f;
+  }
+  return FDG_OK;
+}
+static void forget_isa_kernels(fdg_isa_kernel *kern) { for (int k = 0; k < FDG_K_COUNT; ++k) kern[k].fn = nullptr; }
+
 static int ensure_module(fdg_graph *g) {
   if (g->module || g->code_object.empty()) return FDG_OK;
   hipModule_t m;
   hipError_t e = hipModuleLoadData(&m, g->code_object.data());
   if (e != hipSuccess) { set_error("hipModuleLoadData failed: " + std::string(hipGetErrorString(e))); return FDG_E_JIT; }
   if (g->isa) {
-    hipFunction_t f;
-    HIP_TRY(hipModuleGetFunction(&f, m, "fdg_isa_eval"));
-    g->module = m; g->fn_isa = f;
-    { hipFunction_t fn; g->fn_isa_nt = hipModuleGetFunction(&fn, m, "fdg_isa_eval_nt") == hipSuccess ? (void *)fn : nullptr; (void)hipGetLastError(); }
-    { hipFunction_t fn; g->fn_isa_acc_nt = (g->has_acc && hipModuleGetFunction(&fn, m, "fdg_isa_eval_acc_nt") == hipSuccess) ? (void *)fn : nullptr; (void)hipGetLastError(); }
-    if (g->has_w2) { hipFunction_t f2; HIP_TRY(hipModuleGetFunction(&f2, m, "fdg_isa_eval_w2")); g->fn_isa_w2 = f2; }
-    if (g->has_acc) { hipFunction_t f3; HIP_TRY(hipModuleGetFunction(&f3, m, "fdg_isa_eval_acc")); g->fn_isa_acc = f3; }
-    if (g->has_rm) { hipFunction_t f4; HIP_TRY(hipModuleGetFunction(&f4, m, "fdg_isa_eval_rm")); g->fn_isa_rm = f4; }
-    if (g->has_rm_acc) { hipFunction_t f6; HIP_TRY(hipModuleGetFunction(&f6, m, "fdg_isa_eval_rm_acc")); g->fn_isa_rm_acc = f6; }
-    if (g->has_coop) { hipFunction_t f5; HIP_TRY(hipModuleGetFunction(&f5, m, "fdg_isa_eval_coop")); g->fn_isa_coop = f5; }
-    if (g->has_pool) { hipFunction_t f6; HIP_TRY(hipModuleGetFunction(&f6, m, "fdg_isa_eval_pool")); g->fn_isa_pool = f6; }
-    if (g->has_rl) { hipFunction_t f7; HIP_TRY(hipModuleGetFunction(&f7, m, "fdg_isa_eval_rl")); g->fn_isa_rl = f7; }
-    if (g->has_rl_acc) { hipFunction_t f8; HIP_TRY(hipModuleGetFunction(&f8, m, "fdg_isa_eval_rl_acc")); g->fn_isa_rl_acc = f8; }
+    const int rc = resolve_isa_kernels(m, "fdg_isa_eval", g->kern);
+    if (rc) return rc;
+    g->module = m;
     return FDG_OK;
   }
   hipFunction_t f1, f2;
@@ -790,6 +801,13 @@ int run_interpreter(fdg_graph *g, const RunArgs &a) {
 }
 
 // ---- the kernels of the optimizing back end (per-graph gfx950 assembly) ---------------------------------------------------------
+// what an accumulating kernel leaves behind: per-lane partial sums of its `nwg` workgroups at `part`; this adds them to acc
+static int launch_reduce_lane_partials(double *part, uint32_t nwg, uint32_t R, double *acc, hipStream_t st) {
+  hipLaunchKernelGGL(fdg_reduce_lane_partials, dim3(std::min<uint32_t>(R, 64u)), dim3(256), 0, st, part, nwg, R, acc);
+  HIP_TRY(hipGetLastError());
+  return FDG_OK;
+}
+
 // One call's launch plan: grids and workspace offsets of the variants the handle carries, then one method per variant.
 struct IsaRun {
   fdg_graph *g;
@@ -805,14 +823,10 @@ struct IsaRun {
 
   IsaRun(fdg_graph *g_, const RunArgs &a_) : g(g_), a(a_), p(g_->prog), R(g_->prog.R), tiled(a_.lts != 0 || a_.rts != 0) {}
 
-  // resident waves: one wave per workgroup; bounded by VGPRs, LDS and 32 waves/CU
-  uint32_t waves_per_cu(uint32_t vgpr, uint32_t lds_bytes) const {
-    const uint32_t valloc = std::max<uint32_t>(8, (vgpr + 7) & ~7u);
-    uint32_t per_cu = std::min<uint32_t>(8, 512 / valloc) * 4;
-    if (lds_bytes) per_cu = std::min<uint32_t>(per_cu, (160u * 1024u) / lds_bytes);
-    per_cu = std::max<uint32_t>(1, std::min<uint32_t>(per_cu, 32));
-    if (g->cfg.waves_per_cu > 0) per_cu = (uint32_t)g->cfg.waves_per_cu;
-    return per_cu;
+  const fdg_isa_kernel &K(int k) const { return g->kern[k]; }
+  // resident waves of kernel k (one wave per workgroup), or what FDG_ISA_WAVES_PER_CU forces
+  uint32_t waves_per_cu(const fdg_isa_kernel &k) const {
+    return g->cfg.waves_per_cu > 0 ? (uint32_t)g->cfg.waves_per_cu : isa_waves_per_cu(k.vgpr, k.lds_bytes);
   }
   // A persistent wave walks tiles w, w + n, ...  With several times as many workgroups as are resident at once the later ones
   // start as the first finish, which evens out waves that progress at different speeds (oversubscription x8: +2-3 % on the
@@ -828,8 +842,8 @@ struct IsaRun {
   // (one per SIMD) keep 4 x L x 512 bytes in flight per CU -- enough for the latency-bandwidth product -- and the memory system sees a
   // quarter of the concurrent streams (round 4, profiles/r04_log_waves.txt: headline +3-5 %, the 2-loop graph +6-15 %); the graphs at or
   // above the ridge want every wave they can get.  Options FDG_ISA_MEM_WAVES / FDG_ISA_MEM_OVERSUB / FDG_ISA_MEM_RATIO override (0 waves = off).
-  long shape(uint64_t valu, uint64_t bytes, uint32_t vgpr, uint32_t lds, size_t bytes_per_wg, bool accumulating = false) const {
-    const long full = (long)waves_per_cu(vgpr, lds);
+  long shape(uint64_t valu, uint64_t bytes, const fdg_isa_kernel &k, size_t bytes_per_wg, bool accumulating = false) const {
+    const long full = (long)waves_per_cu(k);
     // (a wave of a tiny graph keeps little in flight; without root stores more of them help: the 2-loop graph accumulates at 0.84 instead of
     //  0.73, profiles/r04_log_tiny_acc_waves.txt)
     const long mem_waves = g->cfg.mem_waves >= 0 ? g->cfg.mem_waves : (p.L >= 24 ? 4 : (accumulating ? 8 : 5));
@@ -848,22 +862,23 @@ struct IsaRun {
 
   int plan() {
     ntiles = (long)((a.B + 63) / 64);
-    grid = std::min<long>(ntiles, shape(g->st_valu[0], 8ull * (p.L + R), g->isa_vgpr, g->isa_lds_bytes, (size_t)g->isa_mem_slots * 512u));
-    grid2 = g->has_w2 ? (long)g->n_cu * waves_per_cu(g->isa2_vgpr, g->isa2_lds_bytes) : 0;
-    const size_t panel = std::max((size_t)std::max<uint32_t>(g->isa_mem_slots, 1) * 512u * (size_t)grid,
-                                  (size_t)std::max<uint32_t>(g->isa2_mem_slots, 1) * 1024u * (size_t)grid2);
+    const fdg_isa_kernel &ev = K(FDG_K_EVAL), &w2 = K(FDG_K_W2), &ac = K(FDG_K_ACC), &rm = K(FDG_K_RM), &rma = K(FDG_K_RM_ACC);
+    grid = std::min<long>(ntiles, shape(g->st_valu[0], 8ull * (p.L + R), ev, (size_t)ev.mem_slots * 512u));
+    grid2 = w2.present ? (long)g->n_cu * waves_per_cu(w2) : 0;
+    const size_t panel = std::max((size_t)std::max<uint32_t>(ev.mem_slots, 1) * 512u * (size_t)grid,
+                                  (size_t)std::max<uint32_t>(w2.mem_slots, 1) * 1024u * (size_t)grid2);
     // pooled cooperative variant: full tiles of batches whose samples of a leaf are contiguous and whose leaves lie within 2 GB of the tile's first
-    pool_ok = g->has_pool && g->fn_isa_pool && a.ss == 1 && a.ls > 0 && (g->pool_unit == 1 || a.ls == 64) &&
+    pool_ok = K(FDG_K_POOL).present && K(FDG_K_POOL).fn && a.ss == 1 && a.ls > 0 && (g->pool_unit == 1 || a.ls == 64) &&
               (uint64_t)a.ls * 8u * (uint64_t)std::max<uint32_t>(p.L, 1) < (1ull << 31) && a.B >= 64 && !g->cfg.no_pool;
     // (a graph that has the pooled variant accumulates through it and the root scratch: its fused-accumulation program, with R + 2 fewer value
     //  registers and no pool, runs the 4-loop GV vertex function at 0.87e8 samples/s where the pooled evaluation + the weighted sum do 1.3e8)
-    fused_acc = a.mode == 1 && g->has_acc && !g->cfg.no_fused_acc && !(pool_ok && !g->cfg.pool_no_acc);
-    grid3 = g->has_acc ? shape(g->st_valu[1], 8ull * p.L, g->isa3_vgpr, g->isa3_lds_bytes, ((size_t)g->isa3_mem_slots + R) * 512u, true) : 0;
-    const size_t panel3 = (size_t)std::max<uint32_t>(g->isa3_mem_slots, 1) * 512u * (size_t)grid3;
-    grid4 = g->has_rm ? (long)g->n_cu * waves_per_cu(g->isa4_vgpr, g->isa4_lds_bytes) : 0;
-    const size_t panel4 = (size_t)std::max<uint32_t>(g->isa4_mem_slots, 1) * 512u * (size_t)grid4;
-    grid5 = g->has_rm_acc ? (long)g->n_cu * waves_per_cu(g->isa5_vgpr, g->isa5_lds_bytes) : 0;
-    const size_t panel5 = (size_t)std::max<uint32_t>(g->isa5_mem_slots, 1) * 512u * (size_t)grid5;
+    fused_acc = a.mode == 1 && ac.present && !g->cfg.no_fused_acc && !(pool_ok && !g->cfg.pool_no_acc);
+    grid3 = ac.present ? shape(g->st_valu[1], 8ull * p.L, ac, ((size_t)ac.mem_slots + R) * 512u, true) : 0;
+    const size_t panel3 = (size_t)std::max<uint32_t>(ac.mem_slots, 1) * 512u * (size_t)grid3;
+    grid4 = rm.present ? (long)g->n_cu * waves_per_cu(rm) : 0;
+    const size_t panel4 = (size_t)std::max<uint32_t>(rm.mem_slots, 1) * 512u * (size_t)grid4;
+    grid5 = rma.present ? (long)g->n_cu * waves_per_cu(rma) : 0;
+    const size_t panel5 = (size_t)std::max<uint32_t>(rma.mem_slots, 1) * 512u * (size_t)grid5;
     panel_all = (std::max(std::max(panel, panel3), std::max(panel4, panel5)) + 4095) & ~(size_t)4095;
     int rc = ensure_ws(g, panel_all + (size_t)std::max(grid3, grid5) * R * 512u + 4096);
     if (rc) return rc;
@@ -879,47 +894,47 @@ struct IsaRun {
     return FDG_OK;
   }
 
+  // one launch of kernel k: its twelve arguments (leaves and their sample / leaf strides, roots and theirs, the panels, samples, workgroups,
+  // weights, the tile strides of leaves and roots), the workgroup size it was assembled for
+  int launch(int k, const double *lf, long lss, long lls, double *rt, long rrs, long rrk, long n, long nwg, const double *wt, long tls, long trs) {
+    void *a_wsp = g->d_ws;
+    void *args[] = {(void *)&lf, &lss, &lls, (void *)&rt, &rrs, &rrk, &a_wsp, &n, &nwg, (void *)&wt, &tls, &trs};
+    HIP_TRY(hipModuleLaunchKernel((hipFunction_t)K(k).fn, (unsigned)nwg, 1, 1, K(k).threads, 1, 1, 0, a.st, args, nullptr));
+    return FDG_OK;
+  }
+  // an accumulating kernel leaves per-lane partial sums of its workgroups at `part`; fdg_reduce_lane_partials adds them to acc
+  int launch_reduced(int k, const double *lf, long lss, long lls, double *part, long n, long nwg, const double *wt, long tls) {
+    const int rc = launch(k, lf, lss, lls, part, 0, 0, n, nwg, wt, tls, 0);
+    return rc ? rc : launch_reduce_lane_partials(part, (uint32_t)nwg, R, a.d_acc, a.st);
+  }
   // fused accumulation: acc[k] += sum_b w_b root_k(b) with per-lane accumulators inside the evaluator (fdg_isa_eval_acc[_nt])
   int launch_acc(const double *lf, long lss, long lls, const double *wt, long n, long tls = 0) {
-    void *a_wsp = g->d_ws;
     double *part = (double *)((char *)g->d_ws + panel_all);
-    long nwg = std::min<long>((n + 63) / 64, grid3), zero = 0;
     if (!tls) tls = 64 * lss;
-    void *args[] = {(void *)&lf, &lss, &lls, (void *)&part, &zero, &zero, &a_wsp, &n, &nwg, (void *)&wt, &tls, &zero};
-    void *fn = g->fn_isa_acc_nt && line_aligned(lf, lss, lls) && (tls & 15) == 0 ? g->fn_isa_acc_nt : g->fn_isa_acc;
-    if (!named) g->last_kernel = fn == g->fn_isa_acc ? "fdg_isa_eval_acc" : "fdg_isa_eval_acc_nt";
-    HIP_TRY(hipModuleLaunchKernel((hipFunction_t)fn, (unsigned)nwg, 1, 1, 64, 1, 1, 0, a.st, args, nullptr));
-    hipLaunchKernelGGL(fdg_reduce_lane_partials, dim3(std::min<uint32_t>(R, 64u)), dim3(256), 0, a.st, part, (uint32_t)nwg, R, a.d_acc);
-    HIP_TRY(hipGetLastError());
-    return FDG_OK;
+    const int k = K(FDG_K_ACC_NT).fn && line_aligned(lf, lss, lls) && (tls & 15) == 0 ? FDG_K_ACC_NT : FDG_K_ACC;
+    if (!named) g->last_kernel = FDG_ISA_KERNEL[k];
+    return launch_reduced(k, lf, lss, lls, part, n, std::min<long>((n + 63) / 64, grid3), wt, tls);
   }
   // one batch with sample stride `lss` (fdg_isa_eval[_nt]): full 128-sample tiles through the two-samples-per-lane kernel
   // when there is one and the samples of a leaf are contiguous, the rest through the W = 1 kernel
   int launch_isa(const double *lf, long lss, long lls, double *rt, long rrs, long rrk, long n, long tls = 0, long trs = 0) {
-    void *a_wsp = g->d_ws;
     long done = 0;
-    if (g->has_w2 && lss == 1 && n >= 128 && !tls && !trs && !g->cfg.no_w2) {
-      long n2 = n & ~127l;
-      long nwg = std::min<long>(n2 / 128, grid2);
-      const double *nowt = nullptr;
-      long tls2 = 128 * lss, trs2 = 128 * rrs;
-      void *args[] = {(void *)&lf, &lss, &lls, (void *)&rt, &rrs, &rrk, &a_wsp, &n2, &nwg, (void *)&nowt, &tls2, &trs2};
-      HIP_TRY(hipModuleLaunchKernel((hipFunction_t)g->fn_isa_w2, (unsigned)nwg, 1, 1, 64, 1, 1, 0, a.st, args, nullptr));
-      g->last_kernel = "fdg_isa_eval_w2";
+    if (K(FDG_K_W2).present && lss == 1 && n >= 128 && !tls && !trs && !g->cfg.no_w2) {
+      const long n2 = n & ~127l;
+      const int rc = launch(FDG_K_W2, lf, lss, lls, rt, rrs, rrk, n2, std::min<long>(n2 / 128, grid2), nullptr, 128 * lss, 128 * rrs);
+      if (rc) return rc;
+      g->last_kernel = FDG_ISA_KERNEL[FDG_K_W2];
       done = n2;
     }
     if (done < n) {
       const double *lf1 = lf + done * lss;
       double *rt1 = rt + done * rrs;
-      long n1 = n - done;
-      long nwg = std::min<long>((n1 + 63) / 64, grid);
-      const double *nowt = nullptr;
+      const long n1 = n - done;
       if (!tls) tls = 64 * lss;
       if (!trs) trs = 64 * rrs;
-      void *args[] = {(void *)&lf1, &lss, &lls, (void *)&rt1, &rrs, &rrk, &a_wsp, &n1, &nwg, (void *)&nowt, &tls, &trs};
-      void *fn = g->fn_isa_nt && line_aligned(lf1, lss, lls) && line_aligned(rt1, rrs, rrk) && ((tls | trs) & 15) == 0 ? g->fn_isa_nt : g->fn_isa;
-      if (!named && done == 0) g->last_kernel = fn == g->fn_isa ? "fdg_isa_eval" : "fdg_isa_eval_nt";
-      HIP_TRY(hipModuleLaunchKernel((hipFunction_t)fn, (unsigned)nwg, 1, 1, 64, 1, 1, 0, a.st, args, nullptr));
+      const int k = K(FDG_K_NT).fn && line_aligned(lf1, lss, lls) && line_aligned(rt1, rrs, rrk) && ((tls | trs) & 15) == 0 ? FDG_K_NT : FDG_K_EVAL;
+      if (!named && done == 0) g->last_kernel = FDG_ISA_KERNEL[k];
+      return launch(k, lf1, lss, lls, rt1, rrs, rrk, n1, std::min<long>((n1 + 63) / 64, grid), nullptr, tls, trs);
     }
     return FDG_OK;
   }
@@ -948,12 +963,10 @@ struct IsaRun {
     long nwg = std::min<long>(n4 / 64, (long)g->n_cu), lss = a.ss, lls = a.ls, rrs = mode == 0 ? a.rs : a_rs, rrk = mode == 0 ? a.rk : a_rk;
     int rc = ensure_ws(g, std::max(panel_all + (size_t)grid3 * R * 512u + 4096, (size_t)g->pool_panel_wg * (size_t)nwg + 4096));
     if (rc) return rc;
-    void *a_wsp = g->d_ws;
-    const double *nowt = nullptr;
-    long tls = a.lts ? (long)a.lts : 64 * lss, trs = (mode == 0 && a.rts) ? (long)a.rts : 64 * rrs, nn = n4;
-    void *args[] = {(void *)&lf, &lss, &lls, (void *)&rt0, &rrs, &rrk, &a_wsp, &nn, &nwg, (void *)&nowt, &tls, &trs};
-    HIP_TRY(hipModuleLaunchKernel((hipFunction_t)g->fn_isa_pool, (unsigned)nwg, 1, 1, g->pool_threads, 1, 1, 0, a.st, args, nullptr));
-    g->last_kernel = "fdg_isa_eval_pool";
+    long tls = a.lts ? (long)a.lts : 64 * lss, trs = (mode == 0 && a.rts) ? (long)a.rts : 64 * rrs;
+    rc = launch(FDG_K_POOL, lf, lss, lls, rt0, rrs, rrk, n4, nwg, nullptr, tls, trs);
+    if (rc) return rc;
+    g->last_kernel = FDG_ISA_KERNEL[FDG_K_POOL];
     named = true;
     if (tail) { rc = launch_isa(a.d_leaf + (size_t)(n4 / 64) * (size_t)tls, lss, lls, rt0 + (size_t)(n4 / 64) * (size_t)trs, rrs, rrk, tail, a.lts ? tls : 0, (mode == 0 && a.rts) ? trs : 0); if (rc) return rc; }
     return mode == 1 ? finish_scratch_acc() : FDG_OK;
@@ -961,19 +974,16 @@ struct IsaRun {
 
   // Cooperative variant (fdg_isa_eval_coop): one workgroup of four waves per CU, every workgroup walks tiles of 64 samples; leaf-major input.
   bool wants_coop() const {
-    return a.mode == 0 && g->has_coop && g->coop_enabled && g->fn_isa_coop && !(a.ls == 1 && a.ss != 1 && p.L > 1) && !wide_ss && root_stride_ok(a) && !g->cfg.no_coop;
+    return a.mode == 0 && K(FDG_K_COOP).present && g->coop_enabled && K(FDG_K_COOP).fn && !(a.ls == 1 && a.ss != 1 && p.L > 1) && !wide_ss && root_stride_ok(a) && !g->cfg.no_coop;
   }
   int run_coop() {
     const double *lf = a.d_leaf; double *rt = a.d_root;
     long nwg = std::min<long>((long)((a.B + 63) / 64), (long)g->n_cu), lss = a.ss, lls = a.ls, rrs = a.rs, rrk = a.rk, n = (long)a.B;
     int rc = ensure_ws(g, std::max(panel_all + (size_t)grid3 * R * 512u + 4096, (size_t)g->coop_panel_wg * (size_t)nwg + 4096));
     if (rc) return rc;
-    void *a_wsp = g->d_ws;
-    const double *nowt = nullptr;
-    long tls = a.lts ? (long)a.lts : 64 * lss, trs = a.rts ? (long)a.rts : 64 * rrs;
-    void *args[] = {(void *)&lf, &lss, &lls, (void *)&rt, &rrs, &rrk, &a_wsp, &n, &nwg, (void *)&nowt, &tls, &trs};
-    HIP_TRY(hipModuleLaunchKernel((hipFunction_t)g->fn_isa_coop, (unsigned)nwg, 1, 1, g->coop_threads, 1, 1, 0, a.st, args, nullptr));
-    g->last_kernel = "fdg_isa_eval_coop";
+    rc = launch(FDG_K_COOP, lf, lss, lls, rt, rrs, rrk, n, nwg, nullptr, a.lts ? (long)a.lts : 64 * lss, a.rts ? (long)a.rts : 64 * rrs);
+    if (rc) return rc;
+    g->last_kernel = FDG_ISA_KERNEL[FDG_K_COOP];
     return FDG_OK;
   }
 
@@ -981,20 +991,16 @@ struct IsaRun {
   // full tiles stream the tile's block into an LDS image, the last B % 64 rows go through launch_acc with the caller's strides
   int run_rl_acc() {
     const long n4 = (long)(a.B & ~(int64_t)63), tail = (long)a.B - n4;
-    const long grid7 = (long)g->n_cu * waves_per_cu(g->isa7_vgpr, g->isa7_lds_bytes);
-    const size_t panel7 = ((size_t)std::max<uint32_t>(g->isa7_mem_slots, 1) * 512u * (size_t)grid7 + 4095) & ~(size_t)4095;
+    const long grid7 = (long)g->n_cu * waves_per_cu(K(FDG_K_RL_ACC));
+    const size_t panel7 = ((size_t)std::max<uint32_t>(K(FDG_K_RL_ACC).mem_slots, 1) * 512u * (size_t)grid7 + 4095) & ~(size_t)4095;
     // (the partial sums of this launch and of the tail's launch_acc live behind the larger of the two panels)
     int rc = ensure_ws(g, std::max(panel_all, panel7) + (size_t)std::max(std::max(grid3, grid5), grid7) * R * 512u + 4096);
     if (rc) return rc;
-    void *a_wsp = g->d_ws;
     double *part = (double *)((char *)g->d_ws + std::max(panel_all, panel7));
-    const double *lf = a.d_leaf, *wt = a.d_weight;
-    long nwg = std::min<long>(n4 / 64, grid7), lss = a.ss, lls = a.ls, zero = 0, nn = n4, tls = 64 * lss;
-    void *args[] = {(void *)&lf, (void *)&lss, (void *)&lls, (void *)&part, &zero, &zero, &a_wsp, &nn, &nwg, (void *)&wt, &tls, &zero};
-    HIP_TRY(hipModuleLaunchKernel((hipFunction_t)g->fn_isa_rl_acc, (unsigned)nwg, 1, 1, 64, 1, 1, 0, a.st, args, nullptr));
-    hipLaunchKernelGGL(fdg_reduce_lane_partials, dim3(std::min<uint32_t>(R, 64u)), dim3(256), 0, a.st, part, (uint32_t)nwg, R, a.d_acc);
-    HIP_TRY(hipGetLastError());
-    g->last_kernel = "fdg_isa_eval_rl_acc";
+    const long lss = a.ss, lls = a.ls;
+    rc = launch_reduced(FDG_K_RL_ACC, a.d_leaf, lss, lls, part, n4, std::min<long>(n4 / 64, grid7), a.d_weight, 64 * lss);
+    if (rc) return rc;
+    g->last_kernel = FDG_ISA_KERNEL[FDG_K_RL_ACC];
     named = true;
     if (tail) { rc = launch_acc(a.d_leaf + (size_t)n4 * (size_t)a.ss, lss, lls, a.d_weight ? a.d_weight + n4 : nullptr, tail); if (rc) return rc; }
     return FDG_OK;
@@ -1002,16 +1008,13 @@ struct IsaRun {
   // ... and the evaluation (fdg_isa_eval_rl)
   int run_rl() {
     const long n4 = (long)(a.B & ~(int64_t)63), tail = (long)a.B - n4;
-    const long grid6 = (long)g->n_cu * waves_per_cu(g->isa6_vgpr, g->isa6_lds_bytes);
-    int rc = ensure_ws(g, std::max(panel_all + (size_t)std::max(grid3, grid5) * R * 512u + 4096, (size_t)std::max<uint32_t>(g->isa6_mem_slots, 1) * 512u * (size_t)grid6 + 4096));
+    const long grid6 = (long)g->n_cu * waves_per_cu(K(FDG_K_RL));
+    int rc = ensure_ws(g, std::max(panel_all + (size_t)std::max(grid3, grid5) * R * 512u + 4096, (size_t)std::max<uint32_t>(K(FDG_K_RL).mem_slots, 1) * 512u * (size_t)grid6 + 4096));
     if (rc) return rc;
-    void *a_wsp = g->d_ws;
-    const double *lf = a.d_leaf; double *rt = a.d_root;
-    long nwg = std::min<long>(n4 / 64, grid6), lss = a.ss, lls = a.ls, rrs = a.rs, rrk = a.rk, nn = n4, tls = 64 * lss, trs = 64 * rrs;
-    const double *nowt = nullptr;
-    void *args[] = {(void *)&lf, (void *)&lss, (void *)&lls, (void *)&rt, &rrs, &rrk, &a_wsp, &nn, &nwg, (void *)&nowt, &tls, &trs};
-    HIP_TRY(hipModuleLaunchKernel((hipFunction_t)g->fn_isa_rl, (unsigned)nwg, 1, 1, 64, 1, 1, 0, a.st, args, nullptr));
-    g->last_kernel = "fdg_isa_eval_rl";
+    const long lss = a.ss, lls = a.ls, rrs = a.rs, rrk = a.rk;
+    rc = launch(FDG_K_RL, a.d_leaf, lss, lls, a.d_root, rrs, rrk, n4, std::min<long>(n4 / 64, grid6), nullptr, 64 * lss, 64 * rrs);
+    if (rc) return rc;
+    g->last_kernel = FDG_ISA_KERNEL[FDG_K_RL];
     named = true;
     if (tail) { rc = launch_isa(a.d_leaf + (size_t)n4 * (size_t)a.ss, lss, lls, a.d_root + (size_t)n4 * (size_t)a.rs, rrs, rrk, tail); if (rc) return rc; }
     return FDG_OK;
@@ -1022,31 +1025,23 @@ struct IsaRun {
   // B % 64 rows go through the plain kernel with the caller's strides (its lanes gather their own rows: fine for under a tile).
   bool wants_rm() const {
     const bool rm_shape = a.ls == 1 && a.ss >= (int64_t)p.L && !wide_ss && p.L >= 16 && a.B >= 64 && !tiled && !g->cfg.no_rm;
-    return rm_shape && ((a.mode == 0 && g->has_rm && g->fn_isa_rm && root_stride_ok(a)) || (fused_acc && g->has_rm_acc && g->fn_isa_rm_acc));
+    return rm_shape && ((a.mode == 0 && K(FDG_K_RM).present && K(FDG_K_RM).fn && root_stride_ok(a)) || (fused_acc && K(FDG_K_RM_ACC).present && K(FDG_K_RM_ACC).fn));
   }
   int run_rm() {
     const long n4 = (long)(a.B & ~(int64_t)63), lss = a.ss, lls = a.ls, tail = (long)a.B - n4;
-    void *a_wsp = g->d_ws;
-    const double *lf = a.d_leaf;
     int rc;
     if (a.mode == 0) {
-      double *rt = a.d_root;
-      long nwg = std::min<long>(n4 / 64, grid4), rrs = a.rs, rrk = a.rk, nn = n4, tls = 64 * lss, trs = 64 * rrs;
-      const double *nowt = nullptr;
-      void *args[] = {(void *)&lf, (void *)&lss, (void *)&lls, (void *)&rt, &rrs, &rrk, &a_wsp, &nn, &nwg, (void *)&nowt, &tls, &trs};
-      HIP_TRY(hipModuleLaunchKernel((hipFunction_t)g->fn_isa_rm, (unsigned)nwg, 1, 1, 64, 1, 1, 0, a.st, args, nullptr));
-      g->last_kernel = "fdg_isa_eval_rm";
+      const long rrs = a.rs, rrk = a.rk;
+      rc = launch(FDG_K_RM, a.d_leaf, lss, lls, a.d_root, rrs, rrk, n4, std::min<long>(n4 / 64, grid4), nullptr, 64 * lss, 64 * rrs);
+      if (rc) return rc;
+      g->last_kernel = FDG_ISA_KERNEL[FDG_K_RM];
       named = true;                    // (the last B % 64 rows below do not rename the call)
       if (tail) { rc = launch_isa(a.d_leaf + (size_t)n4 * (size_t)a.ss, lss, lls, a.d_root + (size_t)n4 * (size_t)a.rs, rrs, rrk, tail); if (rc) return rc; }
     } else {
       double *part = (double *)((char *)g->d_ws + panel_all);
-      const double *wt = a.d_weight;
-      long nwg = std::min<long>(n4 / 64, grid5), zero = 0, nn = n4, tls = 64 * lss;
-      void *args[] = {(void *)&lf, (void *)&lss, (void *)&lls, (void *)&part, &zero, &zero, &a_wsp, &nn, &nwg, (void *)&wt, &tls, &zero};
-      HIP_TRY(hipModuleLaunchKernel((hipFunction_t)g->fn_isa_rm_acc, (unsigned)nwg, 1, 1, 64, 1, 1, 0, a.st, args, nullptr));
-      hipLaunchKernelGGL(fdg_reduce_lane_partials, dim3(std::min<uint32_t>(R, 64u)), dim3(256), 0, a.st, part, (uint32_t)nwg, R, a.d_acc);
-      HIP_TRY(hipGetLastError());
-      g->last_kernel = "fdg_isa_eval_rm_acc";
+      rc = launch_reduced(FDG_K_RM_ACC, a.d_leaf, lss, lls, part, n4, std::min<long>(n4 / 64, grid5), a.d_weight, 64 * lss);
+      if (rc) return rc;
+      g->last_kernel = FDG_ISA_KERNEL[FDG_K_RM_ACC];
       named = true;
       if (tail) { rc = launch_acc(a.d_leaf + (size_t)n4 * (size_t)a.ss, lss, lls, a.d_weight ? a.d_weight + n4 : nullptr, tail); if (rc) return rc; }
     }
@@ -1130,8 +1125,8 @@ int run_isa(fdg_graph *g, const RunArgs &a, bool rl_shape) {
   if (rc) return rc;
   if (r.wants_pool()) return r.run_pool();
   if (r.wants_coop()) return r.run_coop();
-  if (rl_shape && a.mode == 1 && g->fn_isa_rl_acc && !r.tiled) return r.run_rl_acc();
-  if (rl_shape && a.mode == 0 && g->fn_isa_rl && !r.tiled) return r.run_rl();
+  if (rl_shape && a.mode == 1 && g->kern[FDG_K_RL_ACC].fn && !r.tiled) return r.run_rl_acc();
+  if (rl_shape && a.mode == 0 && g->kern[FDG_K_RL].fn && !r.tiled) return r.run_rl();
   if (r.wants_rm()) return r.run_rm();
   if (a.mode == 0 && !root_stride_ok(a)) { set_error("root sample stride negative or of 2^23 elements or more is not supported by the ISA kernel"); return FDG_E_UNSUPPORTED; }
   rc = r.wants_transposition() ? r.run_transposed() : r.run_direct();
@@ -1158,10 +1153,10 @@ int fdg_run_locked(fdg_graph *g, int mode, const double *d_leaf, int64_t ss, int
     set_error("tile-major batch: negative strides or sample strides of 2^23 elements or more are not supported"); return FDG_E_UNSUPPORTED;
   }
   // contiguous rows ([B, L] with sample stride L): the linear row-major variant
-  const bool rl_rows = g->has_rl && ls == 1 && ss == (int64_t)p.L && p.L >= 2 && B >= 64 && ((uintptr_t)d_leaf & 15) == 0 && !g->cfg.no_rl;
-  const bool rl_shape = rl_rows && ((mode == 0 && root_stride_ok(a)) || (mode == 1 && g->has_rl_acc && g->has_acc && !g->cfg.no_fused_acc));
+  const bool rl_rows = g->kern[FDG_K_RL].present && ls == 1 && ss == (int64_t)p.L && p.L >= 2 && B >= 64 && ((uintptr_t)d_leaf & 15) == 0 && !g->cfg.no_rl;
+  const bool rl_shape = rl_rows && ((mode == 0 && root_stride_ok(a)) || (mode == 1 && g->kern[FDG_K_RL_ACC].present && g->kern[FDG_K_ACC].present && !g->cfg.no_fused_acc));
   if (mode == 0 && isa && g->cfg.root_scratch_min && R >= g->cfg.root_scratch_min && rk == 1 && rs >= (int64_t)R && (rts == 0 || rts == 64 * rs) && B >= 256 &&
-      !(ls == 1 && ss != 1 && (g->alt_code.size() || g->has_rm || rl_rows)))     // (the row-major variants write a tile's rows together: left alone)
+      !(ls == 1 && ss != 1 && (g->alt_code.size() || g->kern[FDG_K_RM].present || rl_rows)))     // (the row-major variants write a tile's rows together: left alone)
     return run_through_root_scratch(g, a);
   if (isa && !g->alt_code.empty() && ls == 1 && ss != 1 && p.L > 1 && !tiled && !rl_shape) return run_companion(g, a);
   if (isa) return run_isa(g, a, rl_shape);
@@ -1457,10 +1452,10 @@ int fdg_graph_release_device(fdg_graph *g) {
     g->ws_bound = true;
     g->ws_key = nullptr;
   }
-  if (g->module) { hipModuleUnload((hipModule_t)g->module); g->module = nullptr; g->fn_eval_sm = g->fn_eval_gen = nullptr; g->fn_isa = nullptr; g->fn_isa_nt = g->fn_isa_acc_nt = nullptr; }
+  if (g->module) { hipModuleUnload((hipModule_t)g->module); g->module = nullptr; g->fn_eval_sm = g->fn_eval_gen = nullptr; forget_isa_kernels(g->kern); }
   if (g->fused_module) { hipModuleUnload((hipModule_t)g->fused_module); g->fused_module = nullptr; g->fn_fused = nullptr; }
   if (g->alt_module) { hipModuleUnload((hipModule_t)g->alt_module); g->alt_module = nullptr; g->fn_alt_sm = g->fn_alt_gen = nullptr; }
-  if (g->mc_module) { hipModuleUnload((hipModule_t)g->mc_module); g->mc_module = nullptr; g->fn_mc = g->fn_mc_acc = nullptr; }
+  if (g->mc_module) { hipModuleUnload((hipModule_t)g->mc_module); g->mc_module = nullptr; forget_isa_kernels(g->mc_kern); }
   if (g->cx_twin) fdg_graph_release_device(g->cx_twin);
   for (int t = 0; t < 4; ++t) if (g->typed_module[t]) { hipModuleUnload((hipModule_t)g->typed_module[t]); g->typed_module[t] = nullptr; g->fn_typed[t] = nullptr; }
   return FDG_OK;
@@ -1494,19 +1489,12 @@ int fdg_graph_kernel_info(fdg_graph *g, fdg_kernel_info *o) {
   std::memset(o, 0, sizeof *o);
   std::snprintf(o->last_kernel, sizeof o->last_kernel, "%s", g->last_kernel ? g->last_kernel : "");
   if (!(g->isa && !g->code_object.empty())) return FDG_OK;
-  auto wpc = [](uint32_t vgpr, uint32_t lds_bytes) {      // the rule of fdg_run_locked (without its environment override)
-    const uint32_t valloc = std::max<uint32_t>(8, (vgpr + 7) & ~7u);
-    uint32_t per_cu = std::min<uint32_t>(8, 512 / valloc) * 4;
-    if (lds_bytes) per_cu = std::min<uint32_t>(per_cu, (160u * 1024u) / lds_bytes);
-    return std::max<uint32_t>(1, std::min<uint32_t>(per_cu, 32));
-  };
   for (int i = 0; i < 3; ++i) { o->n_valu[i] = g->st_valu[i]; o->n_ld_leaf[i] = g->st_ld_leaf[i]; o->n_panel[i] = g->st_panel[i]; o->n_lds[i] = g->st_lds[i]; }
-  o->waves_per_cu[0] = wpc(g->isa_vgpr, g->isa_lds_bytes);
-  if (g->has_acc) o->waves_per_cu[1] = wpc(g->isa3_vgpr, g->isa3_lds_bytes);
-  if (g->has_rm) o->waves_per_cu[2] = wpc(g->isa4_vgpr, g->isa4_lds_bytes);
-  o->has_acc = g->has_acc; o->has_rm = g->has_rm; o->has_coop = g->has_coop && g->coop_enabled; o->rm_bufs = g->rm_bufs;
-  o->has_pool = g->has_pool; o->pool_fetch = g->pool_fetch; o->pool_valu = g->pool_valu;
-  o->has_rl = g->has_rl; o->rl_reserved = 0; o->rl_valu = g->rl_valu;
+  const int slot[3] = {FDG_K_EVAL, FDG_K_ACC, FDG_K_RM};      // (the rule of the launch plan without its FDG_ISA_WAVES_PER_CU override)
+  for (int i = 0; i < 3; ++i) if (g->kern[slot[i]].present) o->waves_per_cu[i] = isa_waves_per_cu(g->kern[slot[i]].vgpr, g->kern[slot[i]].lds_bytes);
+  o->has_acc = g->kern[FDG_K_ACC].present; o->has_rm = g->kern[FDG_K_RM].present; o->has_coop = g->kern[FDG_K_COOP].present && g->coop_enabled; o->rm_bufs = g->rm_bufs;
+  o->has_pool = g->kern[FDG_K_POOL].present; o->pool_fetch = g->pool_fetch; o->pool_valu = g->pool_valu;
+  o->has_rl = g->kern[FDG_K_RL].present; o->rl_reserved = 0; o->rl_valu = g->rl_valu;
   return FDG_OK;
 }
 
@@ -1679,13 +1667,11 @@ int fdg_graph_mc_program(const fdg_graph *g, const fdg_leaf_tables *tab, const f
 
 static bool has_opt_params(const fdg_graph *g) { return g->has_opt; }
 
-static int assemble_isa(const fdg_graph *g, const fdg::OptProgram &prog, const std::string &dir, unsigned flags,
-                        std::vector<char> &co, std::string &hash, const fdg::OptProgram *prog2 = nullptr,
-                        const fdg::OptProgram *prog_acc = nullptr, const char *kname = "fdg_isa_eval",
-                        const fdg::OptProgram *prog_rm = nullptr, uint32_t rm_bufs = 0, const fdg::CoopProgram *coop = nullptr,
-                        const fdg::OptProgram *prog_rm_acc = nullptr, const fdg::CoopProgram *pool = nullptr,
-                        const fdg::OptProgram *prog_rl = nullptr, const fdg::OptProgram *prog_rl_acc = nullptr) {
-  const std::string src = fdg::emit_isa(g->prog, prog, kname, prog2, prog_acc, prog_rm, rm_bufs, coop, prog_rm_acc, pool, prog_rl, prog_rl_acc);
+// assembles the code object of the programs in V (or finds it in the cache); `records`: what the emitter assembled for each of its kernels
+static int assemble_isa(const fdg_graph *g, const fdg::IsaPrograms &V, const std::string &dir, unsigned flags, std::vector<char> &co, std::string &hash,
+                        std::vector<fdg::IsaKernelRecord> &records) {
+  records.clear();
+  const std::string src = fdg::emit_isa(g->prog, V, &records);
   char hbuf[40];
   std::snprintf(hbuf, sizeof hbuf, "%016llx", (unsigned long long)fnv1a(src, fnv1a("isa")));
   hash = hbuf;
@@ -1715,101 +1701,52 @@ static int assemble_isa(const fdg_graph *g, const fdg::OptProgram &prog, const s
   return FDG_OK;
 }
 
-static void install_isa(fdg_graph *g, const fdg::OptProgram &prog, std::vector<char> &co, const std::string &hash, unsigned flags,
-                        const fdg::OptProgram *prog2 = nullptr, const fdg::OptProgram *prog_acc = nullptr,
-                        const fdg::OptProgram *prog_rm = nullptr, uint32_t rm_bufs = 0, const fdg::CoopProgram *coop = nullptr,
-                        const fdg::OptProgram *prog_rm_acc = nullptr, const fdg::CoopProgram *pool = nullptr,
-                        const fdg::OptProgram *prog_rl = nullptr, const fdg::OptProgram *prog_rl_acc = nullptr) {
+// the kernel table of a code object: present, registers, LDS and workgroup size from the emitter's records; panel slots from the programs
+static void fill_isa_kernels(fdg_isa_kernel *kern, const fdg::IsaPrograms &V, const std::vector<fdg::IsaKernelRecord> &records) {
+  const fdg::OptProgram *prog[FDG_K_COUNT] = {V.main, V.main, V.w2_prog(), V.acc_prog(), V.acc_prog(), V.rm_prog(), V.rm_acc_prog(), V.rl_prog(), V.rl_acc_prog(), nullptr, nullptr};
+  for (int k = 0; k < FDG_K_COUNT; ++k) {
+    kern[k] = fdg_isa_kernel();
+    for (const fdg::IsaKernelRecord &r : records) {
+      if (r.name != V.kname + fdg_isa_suffix(k)) continue;
+      kern[k].present = true;
+      kern[k].vgpr = r.vgpr; kern[k].lds_bytes = r.lds_bytes; kern[k].threads = r.threads;
+      if (prog[k]) kern[k].mem_slots = prog[k]->n_mem_used;
+    }
+  }
+}
+static uint32_t panel_bytes_per_wg(const fdg::CoopProgram &cp) {
+  uint32_t bytes = 0;
+  for (uint32_t w = 0; w < cp.n_wave; ++w) bytes += std::max<uint32_t>(cp.wave[w].n_mem_used, 1) * 512u;
+  return bytes;
+}
+
+static void install_isa(fdg_graph *g, const fdg::IsaPrograms &V, std::vector<char> &co, const std::string &hash, unsigned flags,
+                        const std::vector<fdg::IsaKernelRecord> &records) {
   if (g->module) { hipModuleUnload((hipModule_t)g->module); g->module = nullptr; }
-  g->has_rl_acc = prog_rl != nullptr && prog_rl_acc != nullptr;
-  g->fn_isa_rl_acc = nullptr;
-  if (g->has_rl_acc) {
-    uint32_t t7 = 0;
-    for (const fdg::MOp &o : prog_rl_acc->ops) t7 = std::max(t7, fdg::mop_tmp_pairs(o.kind));
-    g->isa7_vgpr = ((6 + 2 * std::max<uint32_t>(prog_rl_acc->n_reg_used, 1) + 2 * (g->prog.R + 2) + 2 * t7 + 2 + 3) & ~3u) + 2 * prog_rl_acc->n_acc_used;
-    g->isa7_lds_bytes = ((prog_rl_acc->n_lds_used * 512u + 1023u) & ~1023u) + ((512u * g->prog.L + 1023u) & ~1023u);
-    g->isa7_mem_slots = prog_rl_acc->n_mem_used;
-  }
-  g->has_rl = prog_rl != nullptr;
-  g->fn_isa_rl = nullptr;
-  if (g->has_rl) {
-    uint32_t t = 0;
-    for (const fdg::MOp &o : prog_rl->ops) t = std::max(t, fdg::mop_tmp_pairs(o.kind));
-    g->isa6_vgpr = ((6 + 2 * std::max<uint32_t>(prog_rl->n_reg_used, 1) + 2 * t + 2 + 3) & ~3u) + 2 * prog_rl->n_acc_used;
-    g->isa6_lds_bytes = ((prog_rl->n_lds_used * 512u + 1023u) & ~1023u) + ((512u * g->prog.L + 1023u) & ~1023u);
-    g->isa6_mem_slots = prog_rl->n_mem_used;
-    g->rl_valu = prog_rl->n_valu;
-  }
-  g->has_pool = pool && pool->supported;
-  g->fn_isa_pool = nullptr;
-  if (g->has_pool) {
-    g->pool_panel_wg = 0;
-    for (uint32_t w = 0; w < pool->n_wave; ++w) g->pool_panel_wg += std::max<uint32_t>(pool->wave[w].n_mem_used, 1) * 512u;
-    g->pool_threads = 64 * pool->n_wave;
-    g->pool_fetch = (uint32_t)pool->n_transfer;      // leaves brought from memory per tile
-    g->pool_unit = pool->pool_unit;
+  fill_isa_kernels(g->kern, V, records);
+  const fdg_isa_kernel *K = g->kern;
+  if (K[FDG_K_RL].present) g->rl_valu = V.prl.n_valu;
+  if (K[FDG_K_POOL].present) {
+    g->pool_panel_wg = panel_bytes_per_wg(V.pool);
+    g->pool_fetch = (uint32_t)V.pool.n_transfer;      // leaves brought from memory per tile
+    g->pool_unit = V.pool.pool_unit;
     g->pool_valu = 0;
-    for (uint32_t w = 0; w < pool->n_wave; ++w) g->pool_valu += pool->wave[w].n_valu;
+    for (uint32_t w = 0; w < V.pool.n_wave; ++w) g->pool_valu += V.pool.wave[w].n_valu;
   }
-  g->has_coop = coop && coop->supported;
-  g->coop_enabled = g->has_coop;
-  g->fn_isa_coop = nullptr;
-  if (g->has_coop) {
-    g->coop_panel_wg = 0;
-    for (uint32_t w = 0; w < coop->n_wave; ++w) g->coop_panel_wg += std::max<uint32_t>(coop->wave[w].n_mem_used, 1) * 512u;
-    g->coop_lds_bytes = (coop->n_shared + coop->n_wave * coop->n_priv_lds) * 512u;
-    g->coop_threads = 64 * coop->n_wave;
-  }
+  g->coop_enabled = K[FDG_K_COOP].present;
+  if (K[FDG_K_COOP].present) g->coop_panel_wg = panel_bytes_per_wg(V.coop);
   g->code_object.swap(co);
   g->isa = true;
-  g->fn_isa = nullptr;
-  g->fn_isa_nt = g->fn_isa_acc_nt = nullptr;
-  g->fn_isa_w2 = nullptr;
-  g->fn_isa_acc = nullptr;
-  g->has_acc = prog_acc != nullptr;
-  auto tmp_vgprs = [](const fdg::OptProgram &q) { uint32_t t = 0; for (const fdg::MOp &o : q.ops) t = std::max(t, fdg::mop_tmp_pairs(o.kind)); return 2 * t; };
-  if (prog_acc) {
-    g->isa3_vgpr = prog_acc->params.acc_in_agpr
-                       ? ((6 + 2 * std::max<uint32_t>(prog_acc->n_reg_used, 1) + 2 * 3 + tmp_vgprs(*prog_acc) + 3) & ~3u) + 2 * (prog_acc->n_acc_used + g->prog.R)
-                       : ((6 + 2 * std::max<uint32_t>(prog_acc->n_reg_used, 1) + 2 * (g->prog.R + 2) + tmp_vgprs(*prog_acc) + 3) & ~3u) + 2 * prog_acc->n_acc_used;
-    g->isa3_lds_bytes = prog_acc->n_lds_used * 512u;
-    g->isa3_mem_slots = prog_acc->n_mem_used;
+  g->spec_vgpr = K[FDG_K_EVAL].vgpr; g->spec_lds = K[FDG_K_EVAL].lds_bytes; g->spec_scratch = 0;
+  const fdg::OptProgram *pp[3] = {V.main, V.acc_prog(), V.rm_prog()};
+  for (int i = 0; i < 3; ++i) {
+    g->st_valu[i] = pp[i] ? pp[i]->n_valu : 0;
+    g->st_ld_leaf[i] = pp[i] ? (uint32_t)pp[i]->n_ld_leaf : 0;
+    g->st_panel[i] = pp[i] ? (uint32_t)(pp[i]->n_ld_mem + pp[i]->n_st_mem) : 0;
+    g->st_lds[i] = pp[i] ? (uint32_t)(pp[i]->n_ld_lds + pp[i]->n_st_lds) : 0;
   }
-  g->has_rm = prog_rm != nullptr && rm_bufs > 0;
-  g->fn_isa_rm = nullptr;
-  if (g->has_rm) {
-    g->isa4_vgpr = ((6 + 2 * std::max<uint32_t>(prog_rm->n_reg_used, 1) + tmp_vgprs(*prog_rm) + 10 + 3) & ~3u) + 2 * prog_rm->n_acc_used;
-    g->isa4_lds_bytes = ((prog_rm->n_lds_used * 512u + 1023u) & ~1023u) + rm_bufs * 8192u;
-    g->isa4_mem_slots = prog_rm->n_mem_used;
-  }
-  g->has_rm_acc = g->has_rm && prog_rm_acc != nullptr;
-  g->fn_isa_rm_acc = nullptr;
-  if (g->has_rm_acc) {
-    g->isa5_vgpr = ((6 + 2 * std::max<uint32_t>(prog_rm_acc->n_reg_used, 1) + 2 * (g->prog.R + 2) + tmp_vgprs(*prog_rm_acc) + 10 + 3) & ~3u) + 2 * prog_rm_acc->n_acc_used;
-    g->isa5_lds_bytes = ((prog_rm_acc->n_lds_used * 512u + 1023u) & ~1023u) + rm_bufs * 8192u;
-    g->isa5_mem_slots = prog_rm_acc->n_mem_used;
-  }
-  g->has_w2 = prog2 != nullptr;
-  if (prog2) {
-    g->isa2_vgpr = ((6 + 4 * std::max<uint32_t>(prog2->n_reg_used, 1) + 3) & ~3u) + 4 * prog2->n_acc_used;
-    g->isa2_lds_bytes = prog2->n_lds_used * 1024u;
-    g->isa2_mem_slots = prog2->n_mem_used;
-  }
-  g->isa_vgpr = ((6 + 2 * std::max<uint32_t>(prog.n_reg_used, 1) + tmp_vgprs(prog) + 3) & ~3u) + 2 * prog.n_acc_used;
-  g->isa_lds_bytes = prog.n_lds_used * 512u;
-  g->isa_mem_slots = prog.n_mem_used;
-  g->spec_vgpr = g->isa_vgpr; g->spec_lds = g->isa_lds_bytes; g->spec_scratch = 0;
-  {
-    const fdg::OptProgram *pp[3] = {&prog, prog_acc, g->has_rm ? prog_rm : nullptr};
-    for (int i = 0; i < 3; ++i) {
-      g->st_valu[i] = pp[i] ? pp[i]->n_valu : 0;
-      g->st_ld_leaf[i] = pp[i] ? (uint32_t)pp[i]->n_ld_leaf : 0;
-      g->st_panel[i] = pp[i] ? (uint32_t)(pp[i]->n_ld_mem + pp[i]->n_st_mem) : 0;
-      g->st_lds[i] = pp[i] ? (uint32_t)(pp[i]->n_ld_lds + pp[i]->n_st_lds) : 0;
-    }
-    g->rm_bufs = g->has_rm ? rm_bufs : 0;
-    g->last_kernel = "";
-  }
+  g->rm_bufs = V.rm_bufs;
+  g->last_kernel = "";
   g->spec_source_hash = hash;
   g->spec_flags = flags;
 }
@@ -2039,6 +1976,7 @@ static uint32_t build_rm_program(const fdg_graph *g, const fdg::OptParams &chose
                                                   (unsigned long long)(cand.n_ld_lds + cand.n_st_lds), (unsigned long long)(cand.n_ld_acc + cand.n_st_acc), cost);
       if (cost < best_cost) { best_cost = cost; best_fetches = fetches; best_gathers = gathers; best_panel = cand.n_ld_mem + cand.n_st_mem; pr = std::move(cand); if (qsel) *qsel = q; }
     }
+    if (best_cost == 1e300) { if (pass == 1) return 0; break; }      // (every candidate unsupported: no row-major program, not a count with `pr` unset)
     const bool cheap = best_fetches * 4 <= (uint64_t)n_chunk * 5 + 4;
     if (pass == 0) { if (best_cost < 1e300 && cheap && best_panel == 0) return 4; break; }
     if (!cheap && bufs < 4 && !e) continue;
@@ -2051,17 +1989,9 @@ static uint32_t build_rm_program(const fdg_graph *g, const fdg::OptParams &chose
   return 0;
 }
 
-struct IsaVariants {
-  fdg::OptProgram p2, pa, pr, pra, prl, prla;
-  bool rl = false, rl_acc = false;
-  fdg::CoopProgram coop, pool;
-  bool w2 = false, acc = false, rm_acc = false;
-  uint32_t rm_bufs = 0;
-  int coop_verdict = -1;       // a remembered measurement: 0 = the cooperative variant loses, 4 / 8 = it wins with that many waves; -1: none
-};
 // The cooperative variant (four waves of a CU on one tile) is assembled for programs whose one-wave form
 // spills to the HBM panel in earnest (more than one panel access per 20 fold steps); FDG_ISA_COOP=1 / 0 forces / forbids.
-static void build_coop(const fdg_graph *g, const fdg::OptProgram &prog, IsaVariants &V) {
+static void build_coop(const fdg_graph *g, const fdg::OptProgram &prog, fdg::IsaPrograms &V) {
   const char *e = fdg::knob("FDG_ISA_COOP");
   if (e && e[0] == '0') return;
   (void)prog;
@@ -2083,7 +2013,7 @@ static void build_coop(const fdg_graph *g, const fdg::OptProgram &prog, IsaVaria
     if (V.coop.supported || V.coop_verdict > 0) break;
   }
 }
-static void build_variants(const fdg_graph *g, const fdg::OptParams &chosen, bool allow_w2, IsaVariants &V) {
+static void build_variants(const fdg_graph *g, const fdg::OptParams &chosen, bool allow_w2, fdg::IsaPrograms &V) {
   V.w2 = allow_w2 && !fdg::knob("FDG_ISA_NO_W2") && auto_program_w2(g, V.p2);
   V.acc = build_acc_program(g, chosen, V.pa);
   fdg::OptParams qrm;
@@ -2103,7 +2033,7 @@ static void build_variants(const fdg_graph *g, const fdg::OptParams &chosen, boo
 // The pooled cooperative variant (fdg_opt.h: build_pool_program) is assembled for graphs with at least two roots per wave whose one-wave
 // program goes back to memory for what it had already: leaf loads + panel accesses above twice the live leaves (the two vertex functions
 // of the reference's benchmark programs: 2.9 x and 1.1-1.4 x).  FDG_ISA_POOL=1 / 0 forces / forbids.
-static void build_pool(const fdg_graph *g, const fdg::OptProgram &prog, IsaVariants &V) {
+static void build_pool(const fdg_graph *g, const fdg::OptProgram &prog, fdg::IsaPrograms &V) {
   V.pool = fdg::CoopProgram();
   const char *e = fdg::knob("FDG_ISA_POOL");
   if (e && e[0] == '0') return;
@@ -2121,7 +2051,7 @@ static void build_pool(const fdg_graph *g, const fdg::OptProgram &prog, IsaVaria
 }
 // The linear row-major variant (csrc/fdg_isa.cpp: `rl`): contiguous rows (sample stride == L) of graphs whose 64-row tile, 512 L bytes, leaves
 // room for two waves per CU or more.  One wave per SIMD at most, so the AGPR level is there; a leaf comes back from the image by an LDS read.
-static void build_rl(const fdg_graph *g, const fdg::OptParams &chosen, IsaVariants &V) {
+static void build_rl(const fdg_graph *g, const fdg::OptParams &chosen, fdg::IsaPrograms &V) {
   V.rl = false;
   const char *e = fdg::knob("FDG_ISA_RL");
   // Three waves per CU or more (image + eight LDS slots three times into 160 KB: up to 98 leaves): with two, a wave that waits for its
@@ -2150,19 +2080,16 @@ static void build_rl(const fdg_graph *g, const fdg::OptParams &chosen, IsaVarian
                ((V.prla.n_lds_used * 512u + 1023u) & ~1023u) + ((512u * g->prog.L + 1023u) & ~1023u) <= 160u * 1024u / 3u;
   }
 }
-static int assemble_and_install(fdg_graph *g, const fdg::OptProgram &prog, const std::string &dir, unsigned flags, IsaVariants &V) {
+static int assemble_and_install(fdg_graph *g, const fdg::OptProgram &prog, const std::string &dir, unsigned flags, fdg::IsaPrograms &V) {
   std::vector<char> co; std::string hash;
+  std::vector<fdg::IsaKernelRecord> records;
+  V.main = &prog;
   if (V.coop_verdict != 0) build_coop(g, prog, V);
   build_pool(g, prog, V);
   build_rl(g, prog.params, V);
-  const fdg::CoopProgram *coop = V.coop.supported ? &V.coop : nullptr;
-  const fdg::CoopProgram *pool = V.pool.supported ? &V.pool : nullptr;
-  const int rc = assemble_isa(g, prog, dir, flags, co, hash, V.w2 ? &V.p2 : nullptr, V.acc ? &V.pa : nullptr, "fdg_isa_eval",
-                              V.rm_bufs ? &V.pr : nullptr, V.rm_bufs, coop, V.rm_acc ? &V.pra : nullptr, pool, V.rl ? &V.prl : nullptr,
-                              V.rl && V.rl_acc ? &V.prla : nullptr);
+  const int rc = assemble_isa(g, V, dir, flags, co, hash, records);
   if (rc) return rc;
-  install_isa(g, prog, co, hash, flags, V.w2 ? &V.p2 : nullptr, V.acc ? &V.pa : nullptr, V.rm_bufs ? &V.pr : nullptr, V.rm_bufs, coop,
-              V.rm_acc ? &V.pra : nullptr, pool, V.rl ? &V.prl : nullptr, V.rl && V.rl_acc ? &V.prla : nullptr);
+  install_isa(g, V, co, hash, flags, records);
   return FDG_OK;
 }
 
@@ -2193,7 +2120,7 @@ static int use_tuned(fdg_graph *g, const std::string &dir, unsigned flags) {
   fdg::OptProgram prog;
   build_prog(g, q, prog);
   if (!prog.supported) return 0;
-  IsaVariants V;
+  fdg::IsaPrograms V;
   build_variants(g, q, true, V);
   V.coop_verdict = tuned_coop;
   const int rc = assemble_and_install(g, prog, dir, flags, V);
@@ -2276,10 +2203,13 @@ static int autotune_isa(fdg_graph *g, const std::string &dir, unsigned flags) {
     if (!prog.supported) continue;
     if (c == 0 && !(prog.n_ld_leaf <= p.n_live_leaf && prog.n_ld_lds + prog.n_st_lds + prog.n_ld_mem + prog.n_st_mem == 0)) continue;
     std::vector<char> co; std::string hash;
-    if (assemble_isa(g, prog, dir, flags, co, hash) != FDG_OK) continue;
+    std::vector<fdg::IsaKernelRecord> records;
+    fdg::IsaPrograms one;              // (the candidate's one-wave kernels only)
+    one.main = &prog;
+    if (assemble_isa(g, one, dir, flags, co, hash, records) != FDG_OK) continue;
     if (seen.find(hash) != std::string::npos) continue;
     seen += hash + ";";
-    install_isa(g, prog, co, hash, flags);
+    install_isa(g, one, co, hash, flags, records);
     // warm-up: the first launches after a change of load run at transient clocks (power management settles
     // within a few tens of milliseconds); candidates are compared in the settled state
     bool ok_run = true;
@@ -2304,12 +2234,12 @@ static int autotune_isa(fdg_graph *g, const std::string &dir, unsigned flags) {
   if (best < 0) { hipEventDestroy(e0); hipEventDestroy(e1); hipFree(d_leaf); hipFree(d_root); set_error("autotune: no candidate configuration ran"); return FDG_E_JIT; }
   fdg::OptProgram prog;
   build_prog(g, cand[best], prog);
-  IsaVariants V;
+  fdg::IsaPrograms V;
   build_variants(g, cand[best], true, V);
   rc = assemble_and_install(g, prog, dir, flags, V);
   // the cooperative variant, when the graph gets one, with eight and with four waves against the best one-wave kernel
   int coop_best = 0;
-  const bool had_coop = rc == FDG_OK && g->has_coop;
+  const bool had_coop = rc == FDG_OK && g->kern[FDG_K_COOP].present;
   if (had_coop) {
     auto time_it = [&]() {
       float tm = 1e30f;
@@ -2329,19 +2259,19 @@ static int autotune_isa(fdg_graph *g, const std::string &dir, unsigned flags) {
     g->coop_enabled = false;
     float t_best = time_it();
     for (int nw : {8, 4}) {
-      IsaVariants Vw;
+      fdg::IsaPrograms Vw;
       build_variants(g, cand[best], true, Vw);
       Vw.coop_verdict = nw;
-      if (assemble_and_install(g, prog, dir, flags, Vw) != FDG_OK || !g->has_coop) continue;
+      if (assemble_and_install(g, prog, dir, flags, Vw) != FDG_OK || !g->kern[FDG_K_COOP].present) continue;
       g->coop_enabled = true;
       const float tw = time_it();
       if (tw < t_best) { t_best = tw; coop_best = nw; }
     }
-    IsaVariants Vf;
+    fdg::IsaPrograms Vf;
     build_variants(g, cand[best], true, Vf);
     Vf.coop_verdict = coop_best;
     rc = assemble_and_install(g, prog, dir, flags, Vf);
-    g->coop_enabled = g->has_coop;
+    g->coop_enabled = g->kern[FDG_K_COOP].present;
   }
   hipEventDestroy(e0); hipEventDestroy(e1);
   hipFree(d_leaf); hipFree(d_root);
@@ -2370,7 +2300,7 @@ static int specialize_isa(fdg_graph *g, const std::string &dir, unsigned flags) 
     chosen = auto_program(g, prog);
   }
   if (!prog.supported) { set_error("optimizing back end does not cover this graph: " + prog.why); return FDG_E_UNSUPPORTED; }
-  IsaVariants V;
+  fdg::IsaPrograms V;
   build_variants(g, chosen, !has_opt_params(g), V);
   return assemble_and_install(g, prog, dir, flags, V);
 }
@@ -2417,20 +2347,15 @@ bool fdg_mc_isa_supported(fdg_graph *g, const fdg_leaf_tables *tab, std::string 
   return prog.supported;
 }
 
-static uint32_t isa_waves_per_cu(uint32_t vgpr, uint32_t lds_bytes) {
-  const uint32_t valloc = std::max<uint32_t>(8, (vgpr + 7) & ~7u);
-  uint32_t per_cu = std::min<uint32_t>(8, 512 / valloc) * 4;
-  if (lds_bytes) per_cu = std::min<uint32_t>(per_cu, (160u * 1024u) / lds_bytes);
-  return std::max<uint32_t>(1, std::min<uint32_t>(per_cu, 32));
-}
-
 int fdg_mc_isa_build(fdg_graph *g) {
   if (g->mc_built) return FDG_OK;
   // (the parameter values only fill the ops' imm fields; the kernel reads them from its arguments)
   const fdg_leaf_tables tab = handle_tables(g, 1.0, 1.0, 1.0);
   fdg::LeafSpec ls; ls.tab = &tab; ls.kF = 1.0; ls.beta = 1.0; ls.lambda = 1.0;
   fdg::OptParams q = mc_params(g);
-  fdg::OptProgram pe, pa;
+  fdg::OptProgram pe;
+  fdg::IsaPrograms V;              // fdg_isa_mc and, for graphs whose accumulators fit next to the values, fdg_isa_mc_acc
+  V.main = &pe; V.kname = "fdg_isa_mc";
   fdg::build_mc_program(g->prog, ls, q, pe);
   if (pe.supported && !has_opt_params(g) && (pe.n_ld_mem + pe.n_st_mem) * 100 > pe.n_valu) {
     // values computed from (K, T) cannot be re-read from the input like leaves: what does not fit on chip goes through
@@ -2457,28 +2382,21 @@ int fdg_mc_isa_build(fdg_graph *g) {
   }
   if (!pe.supported) { set_error("the fused ISA step does not cover this graph / these leaves: " + pe.why); return FDG_E_UNSUPPORTED; }
   const uint32_t R = g->prog.R;
-  bool has_acc = R >= 1 && R <= 40 && q.n_reg >= R + 2 + 8 && (R <= 16 || q.n_reg >= R + 2 + 64);
-  if (has_acc) {
+  V.acc = R >= 1 && R <= 40 && q.n_reg >= R + 2 + 8 && (R <= 16 || q.n_reg >= R + 2 + 64);
+  if (V.acc) {
     fdg::OptParams qa = q;
     qa.reserve_pairs = R + 2;        // (build_mc_program takes the macro ops' temporaries off the value budget itself)
-    fdg::build_mc_program(g->prog, ls, qa, pa);
-    has_acc = pa.supported;
+    fdg::build_mc_program(g->prog, ls, qa, V.pa);
+    V.acc = V.pa.supported;
   }
   std::vector<char> co;
   std::string hash;
-  const int rc = assemble_isa(g, pe, g->mc_dir, g->mc_flags, co, hash, nullptr, has_acc ? &pa : nullptr, "fdg_isa_mc");
+  std::vector<fdg::IsaKernelRecord> records;
+  const int rc = assemble_isa(g, V, g->mc_dir, g->mc_flags, co, hash, records);
   if (rc) return rc;
   if (g->mc_module) { HIP_TRY(hipDeviceSynchronize()); hipModuleUnload((hipModule_t)g->mc_module); g->mc_module = nullptr; }
-  g->fn_mc = g->fn_mc_acc = nullptr;
   g->mc_code.swap(co);
-  g->mc_has_acc = has_acc;
-  auto tmp_vgprs = [](const fdg::OptProgram &q) { uint32_t t = 0; for (const fdg::MOp &o : q.ops) t = std::max(t, fdg::mop_tmp_pairs(o.kind)); return 2 * t; };
-  g->mc_vgpr[0] = ((6 + 2 * std::max<uint32_t>(pe.n_reg_used, 1) + tmp_vgprs(pe) + 3) & ~3u) + 2 * pe.n_acc_used;
-  g->mc_lds[0] = pe.n_lds_used * 512u; g->mc_mem[0] = pe.n_mem_used;
-  if (has_acc) {
-    g->mc_vgpr[1] = ((6 + 2 * std::max<uint32_t>(pa.n_reg_used, 1) + 2 * (R + 2) + tmp_vgprs(pa) + 3) & ~3u) + 2 * pa.n_acc_used;
-    g->mc_lds[1] = pa.n_lds_used * 512u; g->mc_mem[1] = pa.n_mem_used;
-  }
+  fill_isa_kernels(g->mc_kern, V, records);
   g->mc_built = true;
   return FDG_OK;
 }
@@ -2489,16 +2407,16 @@ int fdg_mc_isa_run(fdg_graph *g, int mode, const double *d_K, int64_t ks, int64_
   int rc = fdg_mc_isa_build(g);
   if (rc) return rc;
   if (!g->mc_module) {
-    hipModule_t m; hipFunction_t f;
+    hipModule_t m;
     hipError_t e = hipModuleLoadData(&m, g->mc_code.data());
     if (e != hipSuccess) { set_error("hipModuleLoadData failed: " + std::string(hipGetErrorString(e))); return FDG_E_JIT; }
-    HIP_TRY(hipModuleGetFunction(&f, m, "fdg_isa_mc"));
-    g->mc_module = m; g->fn_mc = f;
-    if (g->mc_has_acc) { HIP_TRY(hipModuleGetFunction(&f, m, "fdg_isa_mc_acc")); g->fn_mc_acc = f; }
+    rc = resolve_isa_kernels(m, "fdg_isa_mc", g->mc_kern);
+    if (rc) return rc;
+    g->mc_module = m;
   }
   const uint32_t R = g->prog.R;
   const uint32_t n_k = g->lt_hdr[2] * g->lt_hdr[3], n_tau = g->lt_hdr[4], n_in = n_k + n_tau;
-  const bool use_acc = mode == 1 && g->mc_has_acc;
+  const bool use_acc = mode == 1 && g->mc_kern[FDG_K_ACC].present;
   if (mode == 1 && !use_acc) {
     // more than 16 roots: no room for the accumulators next to the values -- roots to a scratch matrix, then the
     // deterministic weighted reduction the other back ends use
@@ -2523,9 +2441,9 @@ int fdg_mc_isa_run(fdg_graph *g, int mode, const double *d_K, int64_t ks, int64_
     return FDG_OK;
   }
   if (mode == 0 && (rs < 0 || rs >= (1ll << 23))) { set_error("root sample stride negative or of 2^23 elements or more is not supported by the ISA kernel"); return FDG_E_UNSUPPORTED; }
-  const int v = use_acc ? 1 : 0;
-  const long grid = (long)g->n_cu * isa_waves_per_cu(g->mc_vgpr[v], g->mc_lds[v]);
-  const size_t panel = (((size_t)std::max<uint32_t>(g->mc_mem[v], 1) * 512u * (size_t)grid) + 4095) & ~(size_t)4095;
+  const fdg_isa_kernel &kern = g->mc_kern[use_acc ? FDG_K_ACC : FDG_K_EVAL];
+  const long grid = (long)g->n_cu * isa_waves_per_cu(kern.vgpr, kern.lds_bytes);
+  const size_t panel = (((size_t)std::max<uint32_t>(kern.mem_slots, 1) * 512u * (size_t)grid) + 4095) & ~(size_t)4095;
   rc = ensure_ws(g, panel + (size_t)grid * std::max<uint32_t>(R, 1) * 512u + 4096);
   if (rc) return rc;
   // The kernel reads its inputs as columns: momentum component c at K[b*ss + c*kc], time i at T[b*ss + i*tc] (two
@@ -2567,21 +2485,17 @@ int fdg_mc_isa_run(fdg_graph *g, int mode, const double *d_K, int64_t ks, int64_
       x = X; x2 = X + (size_t)n_k * Bc; xls = xls2 = (long)Bc; xss = 1;
     }
     void *a_wsp = g->d_ws;
-    long nwg = std::min<long>((n + 63) / 64, grid), zero = 0, tls = 64 * xss;
+    long nwg = std::min<long>((n + 63) / 64, grid), tls = 64 * xss;
     double p_nkf2 = -(kF * kF), p_beta = beta, p_nbeta = -beta, p_lambda = lambda;     // MOp::param 1..4
+    // the eighteen arguments: the twelve of the evaluator kernels (fdg_isa_eval*) with T's base, its column stride and the four parameters in front of the tile strides
+    double *out = use_acc ? (double *)((char *)g->d_ws + panel) : d_root + c0 * rs;
+    const double *wt = use_acc && d_weight ? d_weight + c0 : nullptr;
+    long a_rs = use_acc ? 0 : (long)rs, a_rk = use_acc ? 0 : (long)rk, trs = 64 * a_rs;
+    void *args[] = {(void *)&x, &xss, &xls, (void *)&out, &a_rs, &a_rk, &a_wsp, &n, &nwg, (void *)&wt, (void *)&x2, &xls2, &p_nkf2, &p_beta, &p_nbeta, &p_lambda, &tls, &trs};
+    HIP_TRY(hipModuleLaunchKernel((hipFunction_t)kern.fn, (unsigned)nwg, 1, 1, kern.threads, 1, 1, 0, st, args, nullptr));
     if (use_acc) {
-      double *part = (double *)((char *)g->d_ws + panel);
-      const double *wt = d_weight ? d_weight + c0 : nullptr;
-      void *args[] = {(void *)&x, &xss, &xls, (void *)&part, &zero, &zero, &a_wsp, &n, &nwg, (void *)&wt, (void *)&x2, &xls2, &p_nkf2, &p_beta, &p_nbeta, &p_lambda, &tls, &zero};
-      HIP_TRY(hipModuleLaunchKernel((hipFunction_t)g->fn_mc_acc, (unsigned)nwg, 1, 1, 64, 1, 1, 0, st, args, nullptr));
-      hipLaunchKernelGGL(fdg_reduce_lane_partials, dim3(std::min<uint32_t>(R, 64u)), dim3(256), 0, st, part, (uint32_t)nwg, R, d_acc);
-      HIP_TRY(hipGetLastError());
-    } else {
-      double *rt = d_root + c0 * rs;
-      long a_rs = (long)rs, a_rk = (long)rk, trs = 64 * a_rs;
-      const double *nowt = nullptr;
-      void *args[] = {(void *)&x, &xss, &xls, (void *)&rt, &a_rs, &a_rk, &a_wsp, &n, &nwg, (void *)&nowt, (void *)&x2, &xls2, &p_nkf2, &p_beta, &p_nbeta, &p_lambda, &tls, &trs};
-      HIP_TRY(hipModuleLaunchKernel((hipFunction_t)g->fn_mc, (unsigned)nwg, 1, 1, 64, 1, 1, 0, st, args, nullptr));
+      rc = launch_reduce_lane_partials(out, (uint32_t)nwg, R, d_acc, st);
+      if (rc) return rc;
     }
   }
   return FDG_OK;
@@ -2638,9 +2552,8 @@ int fdg_graph_specialize(fdg_graph *g, const char *cache_dir, unsigned flags) {
   if (g->alt_module) { hipModuleUnload((hipModule_t)g->alt_module); g->alt_module = nullptr; }
   if (g->module) { hipModuleUnload((hipModule_t)g->module); g->module = nullptr; }
   g->isa = false;
-  g->fn_isa = g->fn_isa_w2 = g->fn_isa_acc = g->fn_isa_nt = g->fn_isa_acc_nt = nullptr;
+  for (int k = 0; k < FDG_K_COUNT; ++k) g->kern[k] = fdg_isa_kernel();
   g->fn_eval_sm = g->fn_eval_gen = nullptr;
-  g->has_w2 = g->has_acc = false;
   g->code_object.swap(co);
   g->spec_source_hash = hbuf;
   g->spec_flags = flags;
