@@ -47,11 +47,13 @@ EXPORTS = [
     "fdg_vegas_sample_device_discrete", "fdg_accumulate_device_vegas_binned", "fdg_mc_accumulate_device_vegas_binned",
     "fdg_vegas_refine_discrete",
     "fdg_vegas_sample_device_polar", "fdg_sincos",
+    "fdg_matsubara_phase", "fdg_accumulate_device_matsubara", "fdg_mc_accumulate_device_matsubara",
 ]
 FDG_BIN_MAX = 16384     # fdg_accumulate_device_binned: largest n_bin
 FDG_VEGAS_DIM_MAX, FDG_VEGAS_GRID_MAX = 64, 1024     # the VEGAS map: most variables, most cells per variable
 FDG_VEGAS_EXT_MAX = 16  # the discrete variable's table: most columns per value
 FDG_VEGAS_POLAR_MAX = 21  # fdg_vegas_sample_device_polar: most groups of polar variables
+FDG_MATSUBARA_FREQ_MAX = 64  # fdg_[mc_]accumulate_device_matsubara: most frequencies per call
 COMM_ID_BYTES = 128
 
 
@@ -97,6 +99,14 @@ class LeafTables(C.Structure):
                 ("n_tau", C.c_uint32), ("leaf_type", C.c_void_p), ("leaf_order", C.c_void_p), ("tau_in", C.c_void_p),
                 ("tau_out", C.c_void_p), ("loop_index", C.c_void_p), ("basis", C.c_void_p),
                 ("kF", C.c_double), ("beta", C.c_double), ("lambda_", C.c_double)]
+
+
+class Matsubara(C.Structure):
+    """fdg_matsubara (include/fdg.h)"""
+    _fields_ = [("n_freq", C.c_uint32), ("fermionic", C.c_int32), ("freq", C.c_void_p), ("root_tau_in", C.c_void_p),
+                ("root_tau_out", C.c_void_p), ("beta", C.c_double), ("d_T", C.c_void_p), ("t_sample_stride", C.c_int64),
+                ("t_comp_stride", C.c_int64), ("n_tau", C.c_uint32), ("d_acc_re", C.c_void_p), ("d_acc_im", C.c_void_p),
+                ("d_acc2_re", C.c_void_p), ("d_acc2_im", C.c_void_p)]
 
 
 class OptParams(C.Structure):
@@ -226,6 +236,12 @@ def lib():
                                                 dp, i64, i64, dp, dp, dp, i64, vp]
     L.fdg_sincos.argtypes = [C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.fdg_sincos.restype = None
+    L.fdg_matsubara_phase.argtypes = [C.c_double, C.c_double, C.c_int32, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.fdg_matsubara_phase.restype = None
+    L.fdg_accumulate_device_matsubara.argtypes = [vp, dp, i64, i64, i64, dp, C.c_int32, u32, dp, C.c_void_p, u64, u64, u32, u32, dp, dp,
+                                                  dp, dp, C.c_void_p, i64, vp]
+    L.fdg_mc_accumulate_device_matsubara.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, C.c_int32,
+                                                     u32, dp, C.c_void_p, u64, u64, u32, u32, dp, dp, dp, dp, C.c_void_p, i64, vp]
     L.fdg_powi.argtypes = [C.c_double, C.c_int32]
     L.fdg_powi.restype = C.c_double
     _lib = L
@@ -484,6 +500,25 @@ class GraphHandle:
                                                           sample_offset, n_dim, n_grid, d_acc or None, d_acc2 or None, d_hist or None,
                                                           d_hist_bin or None, B, stream))
 
+    # the projection onto Matsubara frequencies: desc = make_matsubara(...)[0]; d_bin 0: no discrete variable; d_acc and d_acc2 both 0: no
+    # unprojected moments; n_dim 0 and d_hist 0: no training, else the bits of the VEGAS calls in d_hist (and d_hist_bin) (fdg.h)
+    def accumulate_device_matsubara(self, d_leaf: int, ss: int, ls: int, lts: int, d_bin: int, bin_base: int, n_bin: int, d_weight: int,
+                                    desc, coef=None, seed: int = 0, sample_offset: int = 0, n_dim: int = 0, n_grid: int = 0, d_acc: int = 0,
+                                    d_acc2: int = 0, d_hist: int = 0, d_hist_bin: int = 0, B: int = 0, stream: int = 0):
+        c = self._coef(coef)
+        check(lib().fdg_accumulate_device_matsubara(self._h, d_leaf or None, ss, ls, lts, d_bin or None, bin_base, n_bin, d_weight or None,
+                                                    None if c is None else c.ctypes.data, seed, sample_offset, n_dim, n_grid,
+                                                    d_acc or None, d_acc2 or None, d_hist or None, d_hist_bin or None,
+                                                    None if desc is None else C.addressof(desc), B, stream))
+
+    def mc_accumulate_device_matsubara(self, d_K, ks, kc, d_T, ts, tc, kF, beta, lam, d_bin, bin_base, n_bin, d_weight, desc, coef=None,
+                                       seed=0, sample_offset=0, n_dim=0, n_grid=0, d_acc=0, d_acc2=0, d_hist=0, d_hist_bin=0, B=0, stream=0):
+        c = self._coef(coef)
+        check(lib().fdg_mc_accumulate_device_matsubara(self._h, d_K or None, ks, kc, d_T or None, ts, tc, kF, beta, lam, d_bin or None,
+                                                       bin_base, n_bin, d_weight or None, None if c is None else c.ctypes.data, seed,
+                                                       sample_offset, n_dim, n_grid, d_acc or None, d_acc2 or None, d_hist or None,
+                                                       d_hist_bin or None, None if desc is None else C.addressof(desc), B, stream))
+
     def _coef(self, coef):
         if coef is None:
             return None
@@ -709,6 +744,22 @@ def sincos(x: float):
     s, c = C.c_double(), C.c_double()
     lib().fdg_sincos(float(x), C.byref(s), C.byref(c))
     return s.value, c.value
+
+
+def matsubara_phase(tau: float, beta: float, n: int, fermionic: bool = True):
+    """``(sin, cos)`` of ``omega_n * tau`` by the routine the projection pass uses (fdg_matsubara_phase): the same bits on host and device."""
+    s, c = C.c_double(), C.c_double()
+    lib().fdg_matsubara_phase(tau, beta, int(n), 1 if fermionic else 0, C.byref(s), C.byref(c))
+    return s.value, c.value
+
+
+def make_matsubara(freq, fermionic, root_tau_in, root_tau_out, beta, n_tau, d_acc_re, d_acc_im, d_acc2_re, d_acc2_im, d_T=0, ts=0, tc=0):
+    """``(fdg_matsubara struct, keepalive)``: ``freq`` the n of every frequency, ``root_tau_in`` / ``root_tau_out`` 1-based per root (host
+    sequences); the four outputs and ``d_T`` device addresses (``d_T`` 0 in the Monte-Carlo form: the call's own T)."""
+    a = [np.ascontiguousarray(v, dtype=np.int32) for v in (freq, root_tau_in, root_tau_out)]
+    m = Matsubara(a[0].shape[0], 1 if fermionic else 0, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, float(beta), d_T or None,
+                  int(ts), int(tc), int(n_tau), d_acc_re or None, d_acc_im or None, d_acc2_re or None, d_acc2_im or None)
+    return m, a
 
 
 class Comm:

@@ -364,6 +364,36 @@ class GraphFunc:
                                                        0 if hist_bin is None else hist_bin.data_ptr(), B, st)
         return acc, acc2, hist, hist_bin
 
+    def accumulate_matsubara(self, leaf, T, freq, root_tau_in, root_tau_out, beta: float, fermionic: bool = True, bins=None, n_bin: int = 1,
+                             weight=None, sums=None, bin_base: int = 0, n_sample: Optional[int] = None):
+        """The ``measure`` step of Sigma(i omega_n) or a vertex at given frequencies: every root times the phase of ITS pair of external
+        times.  With ``t = weight[b] * root_k(b)``, ``tau = T[b, root_tau_out[k] - 1] - T[b, root_tau_in[k] - 1]`` and
+        ``(s, c) = capi.matsubara_phase(tau, beta, freq[f], fermionic)``, the samples of bin ``j`` add ``t * c``, ``t * s`` and the
+        squares of both to entry ``[j, f, k]`` of ``sums[0] .. sums[3]``.  ``T``: float64 ``[B, n_tau]`` CUDA tensor (any strides);
+        ``freq``: host sequence of at most ``capi.FDG_MATSUBARA_FREQ_MAX`` integers ``n``; the labels: host sequences of ``n_root``
+        1-based indices (``workloads.root_times``); ``bins=None``: every sample in bin 0.  ``sums``: a contiguous float64
+        ``[4, n_bin, n_freq, R]`` tensor, added to (zeros when None).  Returns ``(acc, acc2_re, acc2_im)``: ``acc`` the complex
+        ``[n_bin, n_freq, R]`` sums of ``t * e^{i omega_n tau}`` (a copy), the other two views of ``sums``; :func:`mc_estimate` on
+        ``(acc.real, acc2_re)`` and ``(acc.imag, acc2_im)`` gives the error bars.  Deterministic: no float atomics
+        (fdg_accumulate_device_matsubara)."""
+        import torch
+        B, n_bin, bins, weight, strides = self._binned_args(leaf, bins, n_bin, weight, n_sample, bins_optional=True)
+        if not (_is_torch(T) and T.is_cuda and T.device == leaf.device and T.dtype == torch.float64 and T.dim() == 2 and T.shape[0] >= B):
+            raise ValueError("T must be a float64 [B, n_tau] CUDA tensor on the leaves' device")
+        n_freq = len(freq)
+        if not (1 <= n_freq <= capi.FDG_MATSUBARA_FREQ_MAX and n_bin * n_freq <= capi.FDG_BIN_MAX):
+            raise ValueError(f"need 1 .. {capi.FDG_MATSUBARA_FREQ_MAX} frequencies and n_bin * n_freq <= {capi.FDG_BIN_MAX}")
+        if len(root_tau_in) != self.n_root or len(root_tau_out) != self.n_root:
+            raise ValueError("root_tau_in and root_tau_out hold one label per root")
+        sums = self._out(sums, (4, n_bin, n_freq, self.n_root), leaf, "sums")
+        p = [sums[i].data_ptr() for i in range(4)]
+        desc, _keep = capi.make_matsubara(freq, fermionic, root_tau_in, root_tau_out, beta, T.shape[1], p[0], p[1], p[2], p[3],
+                                          T.data_ptr(), T.stride(0), T.stride(1))
+        with self._stream(leaf) as st:
+            self.handle.accumulate_device_matsubara(leaf.data_ptr(), *strides, 0 if bins is None else bins.data_ptr(), int(bin_base), n_bin,
+                                                    0 if weight is None else weight.data_ptr(), desc, B=B, stream=st)
+        return torch.complex(sums[0], sums[1]), sums[2], sums[3]
+
     def _binned_args(self, leaf, bins, n_bin, weight, n_sample, bins_optional=False):
         """The checks of :meth:`accumulate_binned` / :meth:`accumulate_moments`: (n_sample, n_bin, bins, weight, leaf strides), bins and
         weight contiguous (the caller holds them until the launch is queued)."""

@@ -35,6 +35,10 @@
 // Spherical momentum variables (fdg_vegas_sample_device_polar): groups of 2 or 3 consecutive variables are (k, phi) or (k, theta, phi);
 // the sampler writes their Cartesian components and folds k (or k k sin theta) into the weight, the sine and cosine from fdg_sincos.h.
 // The accumulate side is untouched: the training pass recomputes cells from the Philox counters and never reads x.
+//
+// Matsubara projection (fdg_[mc_]accumulate_device_matsubara): one more pass per chunk over the same roots (fdg_matsubara_partials
+// below) that multiplies every root by the phase of its own pair of external times at every frequency and sums the real and imaginary
+// parts and their squares per (bin, frequency, root); the moments pass and the training passes run beside it when the call asks for them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -45,6 +49,7 @@
 
 #define FDG_RUNTIME_TU 1
 #include "fdg_internal.h"
+#include "fdg_matsubara.h"
 #include "fdg_sincos.h"
 
 using namespace fdg;
@@ -497,6 +502,142 @@ fdg_vegas_bin_partials(const double *__restrict__ root, long ld, long n, const i
   for (uint32_t i = threadIdx.x; i < n_bin; i += 256) slab[i] = hist[i];
 }
 
+// The projection pass over a chunk's roots (fdg_[mc_]accumulate_device_matsubara): for the samples b of bin j, the roots k and the
+// frequencies f, with t = w_b root_k(b), x = (T[b][tout_k] - T[b][tin_k]) / beta and (s, c) = matsubara_phase_of(x, mult[f]),
+//     hist[0][j][f][k] += t c;  hist[1] += t s;  hist[2] += (t c)(t c);  hist[3] += (t s)(t s).
+// One workgroup per (segment of the chunk's tiles, slice of RS roots, slice of FS frequencies), the slice's four histograms
+// (4 x n_bin x FS x RS doubles) in LDS.  The slice's (root, frequency) items are dealt over the waves, item kk + RS fl to wave
+// (kk + RS fl) % nw, and every wave walks ALL the segment's tiles in tile order for its items, as the training pass walks its
+// variables: a histogram word is only ever touched by one wave, in program order, so per (bin, frequency, root) the tiles are added
+// in tile order with no barrier inside the loop.  Per tile a wave sorts its lanes by (bin, lane) once for all its items (not at all
+// when the tile lies in one bin), forms t and x at the sample's own lane and moves them to the sorted position; then per item the
+// phase, the four terms, the binned pass's segmented scan over every run of equal bins, and the run heads add into the histograms.
+// Lanes past n or with a bin out of range carry the invalid key: they belong to no run and enter no sum.
+// HSPLIT (four histograms of one (root, frequency) do not fit the LDS: n_bin > 4096): RS = FS = 1 and every slice gets four
+// workgroups, one per histogram.  Chunks and segments chain through partial [segment][histogram][bin][frequency][root].
+// tab: mult[FDG_MATSUBARA_FREQ_MAX] doubles, then tin[R], tout[R] (0-based components of T) as int32.
+template <int KW, bool HSPLIT>
+__global__ void __launch_bounds__(256)
+fdg_matsubara_partials(const double *__restrict__ root, long ld, long n, const int32_t *__restrict__ bins, int32_t bin_base, uint32_t n_bin,
+                       const double *__restrict__ weight, const double *__restrict__ T, long ts, long tc, const double *__restrict__ tab,
+                       double beta, uint32_t n_freq, uint32_t R, uint32_t RS, uint32_t FS, uint32_t n_fslice, long seg_tiles,
+                       double *__restrict__ partial, int first) {
+  extern __shared__ double hist[];                        // [histogram][bin][FS][RS]
+  constexpr uint32_t NH = HSPLIT ? 1 : 4;
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const uint32_t n_rslice = (R + RS - 1) / RS, n_grp = n_rslice * n_fslice * (HSPLIT ? 4u : 1u);
+  const uint32_t grp = blockIdx.x % n_grp, seg = blockIdx.x / n_grp;
+  const uint32_t h0 = HSPLIT ? grp / (n_rslice * n_fslice) : 0u;            // HSPLIT: the histogram this workgroup sums
+  const uint32_t fslice = (grp / n_rslice) % n_fslice, rslice = grp % n_rslice;
+  const uint32_t k0 = rslice * RS, kn = min(RS, R - k0), fb = fslice * FS, fn = min(FS, n_freq - fb);
+  const size_t ncol = (size_t)n_bin * n_freq * R;
+  double *slab = partial + ((size_t)seg * 4u + h0) * ncol;
+  const uint32_t per = n_bin * FS * RS;                   // words of one histogram in LDS
+  // (hh, j, fl, kk) of LDS word i, and its place in the slab
+  auto slab_at = [&](uint32_t i, bool &live) {
+    const uint32_t kk = i % RS, fl = (i / RS) % FS, j = (i / (RS * FS)) % n_bin, hh = i / per;
+    live = kk < kn && fl < fn;
+    return (size_t)hh * ncol + ((size_t)j * n_freq + fb + fl) * R + k0 + kk;
+  };
+  for (uint32_t i = threadIdx.x; i < NH * per; i += blockDim.x) {
+    bool live;
+    const size_t at = slab_at(i, live);
+    hist[i] = (first || !live) ? 0.0 : slab[at];
+  }
+  __syncthreads();
+  const SegTiles sg = seg_tiles_of(n, seg, seg_tiles);
+  // this wave's items: the roots kk0 + nw m (m < KW) at every frequency when a slice has at least nw roots, else one root at the
+  // frequencies f0, f0 + fstep, ...
+  const uint32_t kk0 = RS >= nw ? wave : wave % RS, f0 = RS >= nw ? 0u : wave / RS, fstep = RS >= nw ? 1u : nw / RS;
+  const int32_t *tio = (const int32_t *)(tab + FDG_MATSUBARA_FREQ_MAX);
+  long off_in[KW], off_out[KW];
+  size_t col[KW];
+#pragma unroll
+  for (int m = 0; m < KW; ++m) {
+    const uint32_t k = min(k0 + kk0 + nw * (uint32_t)m, R - 1u);            // clamped: what it loads is used only for kk < kn
+    col[m] = (size_t)k * (size_t)ld;
+    off_in[m] = (long)tio[k] * tc;
+    off_out[m] = (long)tio[R + k] * tc;
+  }
+  if (kk0 < kn && f0 < fn) {
+    // this lane's sample of the next tile, loaded one tile ahead (indices clamped into the chunk; used only where the sample is `in`)
+    int32_t bin_n;
+    double w_n, r_n[KW], ti_n[KW], to_n[KW];
+    auto fetch = [&](long t) {
+      const size_t bb = (size_t)min(t * 64 + (long)lane, n - 1);
+      bin_n = bins ? bins[bb] : bin_base;
+      w_n = weight ? weight[bb] : 1.0;
+#pragma unroll
+      for (int m = 0; m < KW; ++m) {
+        r_n[m] = root[col[m] + bb];
+        ti_n[m] = T[(long)bb * ts + off_in[m]];
+        to_n[m] = T[(long)bb * ts + off_out[m]];
+      }
+    };
+    fetch(sg.t0);
+    for (long t = sg.t0; t < sg.t1; ++t) {
+      const long b = t * 64 + lane;
+      const int64_t jb = (int64_t)bin_n - (int64_t)bin_base;
+      const bool in = b < n && jb >= 0 && jb < (int64_t)n_bin;
+      uint32_t key = in ? ((uint32_t)jb << 6) | lane : kKeyInvalid | lane;
+      double tv[KW], xv[KW];
+#pragma unroll
+      for (int m = 0; m < KW; ++m) {
+        const double tau = to_n[m] - ti_n[m];
+        tv[m] = in ? w_n * r_n[m] : 0.0;                  // selected, never multiplied by 0
+        xv[m] = in ? tau / beta : 0.0;
+      }
+      fetch(min(t + 1, sg.t1 - 1));
+      const uint64_t valid = __ballot(key < kKeyInvalid);
+      if (!valid) continue;
+      const uint32_t src = wave_sort_keys(key, lane, valid);
+      uint32_t j, end;
+      bool head;
+      wave_runs(key, lane, j, head, end);
+#pragma unroll
+      for (int m = 0; m < KW; ++m) {
+        const uint32_t kk = kk0 + nw * (uint32_t)m;
+        if (kk >= kn) break;
+        const double ts_ = __shfl(tv[m], (int)src), xs = __shfl(xv[m], (int)src);
+        for (uint32_t fl = f0; fl < fn; fl += fstep) {
+          double s, c;
+          matsubara_phase_of(xs, tab[fb + fl], s, c);
+          const double tre = ts_ * c, tim = ts_ * s;
+          double v[NH];                                   // the squares rounded before they are added (no fma: -ffp-contract=off)
+          if constexpr (HSPLIT) {
+            v[0] = h0 == 0 ? tre : h0 == 1 ? tim : h0 == 2 ? tre * tre : tim * tim;
+          } else {
+            v[0] = tre;
+            v[1] = tim;
+            v[2] = tre * tre;
+            v[3] = tim * tim;
+          }
+          for (uint32_t d = 1; d < 64; d <<= 1) {         // segmented suffix scan, as in fdg_binned_partials
+            const bool take = lane + d <= end;
+            if (!__ballot(take)) break;
+#pragma unroll
+            for (uint32_t hh = 0; hh < NH; ++hh) {
+              const double up = __shfl_down(v[hh], d);
+              if (take) v[hh] = v[hh] + up;
+            }
+          }
+          if (head) {
+            double *hw = hist + ((size_t)j * FS + fl) * RS + kk;
+#pragma unroll
+            for (uint32_t hh = 0; hh < NH; ++hh) hw[(size_t)hh * per] = hw[(size_t)hh * per] + v[hh];
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < NH * per; i += blockDim.x) {
+    bool live;
+    const size_t at = slab_at(i, live);
+    if (live) slab[at] = hist[i];
+  }
+}
+
 // The training pass of one call, as the entry point was given it (aggregate-initialised there, in this order).
 struct VegasRun {
   const double *coef = nullptr;      // host, [R] or null
@@ -505,6 +646,14 @@ struct VegasRun {
   double *d_hist = nullptr;
   bool binned = false;               // the calls with a discrete variable: d_bin selects the samples of the training pass too
   double *d_hist_bin = nullptr;      // ... and, when given, the discrete variable is trained: [n_bin]
+};
+
+// The projection of one call (fdg_[mc_]accumulate_device_matsubara): the descriptor, and the T the pass reads (the descriptor's, or the
+// Monte-Carlo call's own).
+struct MatsubaraRun {
+  const fdg_matsubara *m = nullptr;
+  const double *d_T = nullptr;
+  int64_t ts = 0, tc = 0;
 };
 
 // One accumulate call, as the entry point was given it (aggregate-initialised there, in this order): what the checks, the shared body
@@ -518,6 +667,7 @@ struct BinnedCall {
   int64_t B = 0;
   void *stream = nullptr;
   const VegasRun *vg = nullptr;      // the VEGAS calls: the training pass runs too
+  const MatsubaraRun *mz = nullptr;  // the projection calls: the projection pass runs too; d_acc and d_acc2 may then both be null
 };
 
 constexpr size_t page_up(size_t bytes) { return (bytes + 4095) & ~(size_t)4095; }
@@ -609,6 +759,49 @@ VegasPlan vegas_plan(const BinnedPlan &p, const VegasRun &v, uint32_t R, uint32_
   return q;
 }
 
+// How the projection pass is cut.  Roots and frequencies per slice by the binned plan's LDS budget for four histograms (32 bytes per
+// (bin, frequency, root)): roots first, as the moments pass slices them, then as many frequencies as still fit, spread evenly over the
+// slices; when four histograms of one (root, frequency) do not fit in what one root of FDG_BIN_MAX bins takes, one histogram per
+// workgroup (hsplit).  nw: waves per workgroup, one per item up to four.  Segments by the binned plan's cut with the histogram
+// [4][bin][frequency][root].  A function of (n_sample, n_bin, n_freq, n_root, FDG_ROOT_SCRATCH_MB) only.
+struct MatsubaraPlan {
+  uint32_t rs = 1, fs = 1, n_fslice = 1, n_grp = 1, nw = 1, kw = 1, n_seg = 1;
+  bool hsplit = false;
+  size_t lds = 0, slab_alloc = 0, tab_bytes = 0;
+};
+
+MatsubaraPlan matsubara_plan(const BinnedPlan &p, uint32_t R, uint32_t n_bin, uint32_t n_freq) {
+  MatsubaraPlan q;
+  q.hsplit = (size_t)n_bin * 32u > (size_t)FDG_BIN_MAX * 8u;
+  if (!q.hsplit) {
+    uint32_t rs = 16;
+    while (rs > 1 && (size_t)n_bin * rs * 32u > kBinLdsBudget) rs >>= 1;
+    while (rs > 1 && rs / 2 >= R) rs >>= 1;
+    q.rs = rs;
+    const uint32_t fit = (uint32_t)std::max<size_t>(1, kBinLdsBudget / ((size_t)n_bin * rs * 32u));
+    q.n_fslice = (n_freq + fit - 1) / fit;
+    q.fs = (n_freq + q.n_fslice - 1) / q.n_fslice;
+  }
+  q.n_fslice = (n_freq + q.fs - 1) / q.fs;
+  q.n_grp = ((R + q.rs - 1) / q.rs) * q.n_fslice * (q.hsplit ? 4u : 1u);
+  while (q.nw < kBinWaves && q.nw * 2 <= q.rs * q.fs) q.nw <<= 1;
+  q.kw = std::max(1u, q.rs / q.nw);
+  q.lds = (size_t)(q.hsplit ? 1 : 4) * n_bin * q.fs * q.rs * 8u;
+  const SegCut cut = seg_cut(p.Bc, (size_t)n_bin * n_freq * R * 32u, q.n_grp);
+  q.n_seg = cut.n_seg;
+  q.slab_alloc = page_up(cut.slab_alloc);
+  q.tab_bytes = page_up(FDG_MATSUBARA_FREQ_MAX * 8u + (size_t)R * 8u);      // mult[], then tin[R], tout[R]
+  return q;
+}
+
+using MatsubaraKernel = void (*)(const double *, long, long, const int32_t *, int32_t, uint32_t, const double *, const double *, long, long,
+                                 const double *, double, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, long, double *, int);
+
+MatsubaraKernel matsubara_kernel(const MatsubaraPlan &q) {
+  if (q.hsplit) return fdg_matsubara_partials<1, true>;
+  return q.kw == 4 ? fdg_matsubara_partials<4, false> : q.kw == 2 ? fdg_matsubara_partials<2, false> : fdg_matsubara_partials<1, false>;
+}
+
 // The instance of the binned pass a plan asks for.
 using PartialsKernel = void (*)(const double *, long, long, const int32_t *, int32_t, uint32_t, const double *, uint32_t, uint32_t, long,
                                 double *, int);
@@ -639,7 +832,11 @@ void raise_lds_limits() {
     std::vector<std::pair<const void *, int>> limits = {{(const void *)fdg_binned_partials<1, kSplit>, hist},
                                                         {(const void *)fdg_vegas_bin_partials, hist},
                                                         {(const void *)fdg_vegas_partials<0>, train},
-                                                        {(const void *)fdg_vegas_partials<1>, train}};
+                                                        {(const void *)fdg_vegas_partials<1>, train},
+                                                        {(const void *)fdg_matsubara_partials<1, true>, hist},
+                                                        {(const void *)fdg_matsubara_partials<1, false>, hist},
+                                                        {(const void *)fdg_matsubara_partials<2, false>, hist},
+                                                        {(const void *)fdg_matsubara_partials<4, false>, hist}};
     for (uint32_t rs = 1; rs <= 16; rs <<= 1) {
       limits.push_back({(const void *)partials_kernel_rs<kFirst>(rs), hist});
       limits.push_back({(const void *)partials_kernel_rs<kBoth>(rs), hist});
@@ -694,6 +891,39 @@ int check_vegas(const fdg_graph *g, const BinnedCall &c) {
   return check_vegas_map(v.D, v.G);
 }
 
+// ... and the projection calls': the descriptor, then what the call asks for besides (moments: d_acc and d_acc2 together; training:
+// the VEGAS block, c.vg non-null).  mc_T: the Monte-Carlo form's own T, which a NULL d_T of the descriptor falls back on.
+int check_matsubara(const fdg_graph *g, const BinnedCall &c, const fdg_matsubara *m, const double *mc_T) {
+  if (!g) { set_error("null handle"); return FDG_E_INVALID; }
+  if (!m) { set_error("null descriptor"); return FDG_E_INVALID; }
+  if (c.B < 0) { set_error("n_sample < 0"); return FDG_E_INVALID; }
+  if (!m->d_acc_re || !m->d_acc_im || !m->d_acc2_re || !m->d_acc2_im) { set_error("null device buffer"); return FDG_E_INVALID; }
+  if (!m->freq || !m->root_tau_in || !m->root_tau_out) { set_error("null host array in the descriptor"); return FDG_E_INVALID; }
+  if (!m->d_T && !mc_T) { set_error("null device buffer"); return FDG_E_INVALID; }
+  if (!c.d_acc != !c.d_acc2) { set_error("d_acc and d_acc2 go together"); return FDG_E_INVALID; }
+  const VegasRun *v = c.vg;
+  if (v && !v->d_hist) { set_error("null device buffer"); return FDG_E_INVALID; }
+  if (!c.d_bin && v && v->d_hist_bin) { set_error("d_hist_bin needs d_bin"); return FDG_E_INVALID; }
+  const double *out[8] = {m->d_acc_re, m->d_acc_im, m->d_acc2_re, m->d_acc2_im, c.d_acc, c.d_acc2, v ? v->d_hist : nullptr,
+                          v ? v->d_hist_bin : nullptr};
+  for (int a = 0; a < 8; ++a)
+    for (int b = 0; b < a; ++b)
+      if (out[a] && out[a] == out[b]) { set_error("two output arrays are the same buffer"); return FDG_E_INVALID; }
+  if (c.n_bin == 0) { set_error("n_bin == 0"); return FDG_E_INVALID; }
+  if (!c.d_bin && c.n_bin != 1) { set_error("d_bin == NULL (one bin) needs n_bin == 1"); return FDG_E_INVALID; }
+  if (c.n_bin > FDG_BIN_MAX) { set_error("n_bin > FDG_BIN_MAX"); return FDG_E_UNSUPPORTED; }
+  if (m->n_freq == 0) { set_error("n_freq == 0"); return FDG_E_INVALID; }
+  if (m->n_freq > FDG_MATSUBARA_FREQ_MAX) { set_error("n_freq > FDG_MATSUBARA_FREQ_MAX"); return FDG_E_UNSUPPORTED; }
+  if ((uint64_t)c.n_bin * m->n_freq > FDG_BIN_MAX) { set_error("n_bin * n_freq > FDG_BIN_MAX"); return FDG_E_UNSUPPORTED; }
+  if (!(m->beta > 0.0)) { set_error("beta <= 0"); return FDG_E_INVALID; }
+  for (uint32_t k = 0; k < g->prog.R; ++k) {
+    if (g->prog.root_slot[k] == FDG_NO_ROOT) continue;
+    const int32_t ti = m->root_tau_in[k], to = m->root_tau_out[k];
+    if (ti < 1 || to < 1 || (uint32_t)ti > m->n_tau || (uint32_t)to > m->n_tau) { set_error("time label of a root outside [1, n_tau]"); return FDG_E_INVALID; }
+  }
+  return v ? check_vegas_map(v->D, v->G) : FDG_OK;
+}
+
 // The chunk loop shared by the entry points (caller holds g->mu, stream bound): eval(c0, n, roots, ld) writes the roots of samples
 // c0 .. c0 + n - 1 column-major into roots (root k of sample c0 + b at roots[k * ld + b]).  c.d_acc2 != null: the second moment too.
 // c.vg != null (the VEGAS calls): after a chunk's moments pass the training pass runs over the same roots, its partials behind the
@@ -707,7 +937,13 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
   const size_t root_bytes = page_up((size_t)p.Bc * R * sizeof(double)), slab_bytes = page_up(p.slab_alloc);
   VegasPlan q;
   if (vg) q = vegas_plan(p, *vg, R, n_bin);
-  int rc = ensure_root_scratch(g, vg ? root_bytes + slab_bytes + q.slab_alloc + q.list_bytes + q.bin_slab_alloc : root_bytes + p.slab_alloc);
+  const MatsubaraRun *mz = c.mz;
+  MatsubaraPlan mp;
+  if (mz) mp = matsubara_plan(p, R, n_bin, mz->m->n_freq);
+  // the projection's slab and table lie behind everything the call would reserve without it
+  const size_t base_bytes = vg ? root_bytes + slab_bytes + q.slab_alloc + q.list_bytes + q.bin_slab_alloc
+                               : mz ? root_bytes + slab_bytes : root_bytes + p.slab_alloc;
+  int rc = ensure_root_scratch(g, mz ? base_bytes + mp.slab_alloc + mp.tab_bytes : base_bytes);
   if (rc) return rc;
   double *roots = (double *)g->d_ws2, *partial = (double *)((char *)g->d_ws2 + root_bytes);
   const uint8_t *live = nullptr;
@@ -732,6 +968,23 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
       HIP_TRY(hipMemcpyAsync(d_kidx, hk.data(), n_live * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     }
   }
+  double *mpartial = nullptr, *d_mtab = nullptr;
+  if (mz) {
+    // the multipliers of the frequencies, then the roots' time components (0-based; 0 for a root that does not exist): one small upload
+    const fdg_matsubara &m = *mz->m;
+    mpartial = (double *)((char *)g->d_ws2 + base_bytes);
+    d_mtab = (double *)((char *)mpartial + mp.slab_alloc);
+    std::vector<double> hm(FDG_MATSUBARA_FREQ_MAX + R, 0.0);
+    int32_t *hio = (int32_t *)(hm.data() + FDG_MATSUBARA_FREQ_MAX);
+    for (uint32_t f = 0; f < m.n_freq; ++f) hm[f] = matsubara_multiplier(m.freq[f], m.fermionic);
+    for (uint32_t k = 0; k < R; ++k) {
+      const bool is = g->prog.root_slot[k] != FDG_NO_ROOT;
+      hio[k] = is ? m.root_tau_in[k] - 1 : 0;
+      hio[R + k] = is ? m.root_tau_out[k] - 1 : 0;
+    }
+    HIP_TRY(hipMemcpyAsync(d_mtab, hm.data(), hm.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  }
+  const MatsubaraKernel mpass = matsubara_kernel(mp);
   const PartialsKernel pass = partials_kernel(p);
   const uint32_t n_grp = p.mode == kSplit ? 2 * p.n_slice : p.n_slice;
   for (long c0 = 0; c0 < (long)c.B; c0 += p.Bc) {
@@ -741,9 +994,17 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
     const double *w = c.d_weight ? c.d_weight + c0 : nullptr;
     rc = eval(c0, n, roots, p.Bc);
     if (rc) return rc;
-    hipLaunchKernelGGL(pass, dim3(p.n_seg * n_grp), dim3(256), p.lds, st, roots, (long)p.Bc, n, bins, c.bin_base, n_bin, w, R, p.n_slice,
-                       (ntile + p.n_seg - 1) / p.n_seg, partial, first);
-    HIP_TRY(hipGetLastError());
+    if (c.d_acc) {
+      hipLaunchKernelGGL(pass, dim3(p.n_seg * n_grp), dim3(256), p.lds, st, roots, (long)p.Bc, n, bins, c.bin_base, n_bin, w, R, p.n_slice,
+                         (ntile + p.n_seg - 1) / p.n_seg, partial, first);
+      HIP_TRY(hipGetLastError());
+    }
+    if (mz) {
+      hipLaunchKernelGGL(mpass, dim3(mp.n_seg * mp.n_grp), dim3(64 * mp.nw), mp.lds, st, roots, (long)p.Bc, n, bins, c.bin_base, n_bin, w,
+                         mz->d_T + c0 * mz->ts, (long)mz->ts, (long)mz->tc, d_mtab, mz->m->beta, mz->m->n_freq, R, mp.rs, mp.fs, mp.n_fslice,
+                         (ntile + mp.n_seg - 1) / mp.n_seg, mpartial, first);
+      HIP_TRY(hipGetLastError());
+    }
     if (vg) {
       const double *cf = vg->coef ? d_coef : nullptr;
       // (the calls without a discrete variable carry no bin vector: null, base 0, one bin)
@@ -761,7 +1022,18 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
   const long ncol = (long)n_bin * R;
   uint32_t C = 1;
   while (C < 64 && (long)C < ncol) C <<= 1;
-  rc = reduce_partials(partial, p.n_seg, ncol, R, C, c.d_acc, c.d_acc2, live, st);
+  if (c.d_acc) rc = reduce_partials(partial, p.n_seg, ncol, R, C, c.d_acc, c.d_acc2, live, st);
+  if (!rc && mz) {
+    // the four arrays += the segments' partials [segment][4][bin][frequency][root], in segment order: first both first moments, then both second
+    const long mcol = ncol * mz->m->n_freq;
+    const fdg_matsubara &m = *mz->m;
+    double *out[2][2] = {{m.d_acc_re, m.d_acc_im}, {m.d_acc2_re, m.d_acc2_im}};
+    for (int h = 0; h < 2; ++h) {
+      hipLaunchKernelGGL(fdg_binned_reduce, dim3((unsigned)((mcol + 63) / 64), 2), dim3(256), 0, st, mpartial + (size_t)(2 * h) * mcol, mp.n_seg,
+                         4 * mcol, mcol, R, 64u, out[h][0], out[h][1], live);
+      HIP_TRY(hipGetLastError());
+    }
+  }
   // hist[d][c] and hist_bin[j] += the segments' partials, in segment order
   if (!rc && vg) rc = reduce_partials(vpartial, q.n_seg, (long)vg->D * vg->G, 1u, 64u, vg->d_hist, nullptr, nullptr, st);
   if (!rc && vg && vg->d_hist_bin) rc = reduce_partials(bpartial, q.bin_seg, (long)n_bin, 1u, 64u, vg->d_hist_bin, nullptr, nullptr, st);
@@ -791,7 +1063,7 @@ int accumulate_leaf(fdg_graph *g, const double *d_leaf, int64_t ss, int64_t ls, 
   return accumulate(
       g, c, g->prog.L && !d_leaf,
       [&] {
-        if (c.d_acc2 && lts && !(g->isa && !g->code_object.empty())) {     // (the binned call finds it in the first chunk's evaluation)
+        if ((c.d_acc2 || c.mz) && lts && !(g->isa && !g->code_object.empty())) {     // (the binned call finds it in the first chunk's evaluation)
           set_error("tile-major batches need a handle specialised with FDG_SPEC_ISA"); return FDG_E_UNSUPPORTED;
         }
         return FDG_OK;
@@ -902,6 +1174,36 @@ int fdg_mc_accumulate_device_vegas_binned(fdg_graph *g, const double *d_K, int64
   const VegasRun vg{coef, seed, sample_offset, n_dim, n_grid, d_hist, true, d_hist_bin};
   const BinnedCall c{d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, stream, &vg};
   const int rc = check_vegas(g, c);
+  return rc ? rc : accumulate_mc(g, d_K, ks, kc, d_T, ts, tc, kF, beta, lambda, c);
+}
+
+void fdg_matsubara_phase(double tau, double beta, int32_t n, int fermionic, double *s, double *c) {
+  fdg_matsubara_phase_impl(tau, beta, n, fermionic, *s, *c);
+}
+
+int fdg_accumulate_device_matsubara(fdg_graph *g, const double *d_leaf, int64_t ss, int64_t ls, int64_t lts, const int32_t *d_bin,
+                                    int32_t bin_base, uint32_t n_bin, const double *d_weight, const double *coef, uint64_t seed,
+                                    uint64_t sample_offset, uint32_t n_dim, uint32_t n_grid, double *d_acc, double *d_acc2, double *d_hist,
+                                    double *d_hist_bin, const fdg_matsubara *mz, int64_t B, void *stream) {
+  const bool train = n_dim != 0 || d_hist;
+  const VegasRun vg{coef, seed, sample_offset, n_dim, n_grid, d_hist, d_bin != nullptr, d_hist_bin};
+  const MatsubaraRun mr{mz, mz ? mz->d_T : nullptr, mz ? mz->t_sample_stride : 0, mz ? mz->t_comp_stride : 0};
+  const BinnedCall c{d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, stream, train ? &vg : nullptr, &mr};
+  const int rc = check_matsubara(g, c, mz, nullptr);
+  return rc ? rc : accumulate_leaf(g, d_leaf, ss, ls, lts, c);
+}
+
+int fdg_mc_accumulate_device_matsubara(fdg_graph *g, const double *d_K, int64_t ks, int64_t kc, const double *d_T, int64_t ts, int64_t tc,
+                                       double kF, double beta, double lambda, const int32_t *d_bin, int32_t bin_base, uint32_t n_bin,
+                                       const double *d_weight, const double *coef, uint64_t seed, uint64_t sample_offset, uint32_t n_dim,
+                                       uint32_t n_grid, double *d_acc, double *d_acc2, double *d_hist, double *d_hist_bin,
+                                       const fdg_matsubara *mz, int64_t B, void *stream) {
+  const bool train = n_dim != 0 || d_hist;
+  const VegasRun vg{coef, seed, sample_offset, n_dim, n_grid, d_hist, d_bin != nullptr, d_hist_bin};
+  const bool own_T = mz && mz->d_T;
+  const MatsubaraRun mr{mz, own_T ? mz->d_T : d_T, own_T ? mz->t_sample_stride : ts, own_T ? mz->t_comp_stride : tc};
+  const BinnedCall c{d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, stream, train ? &vg : nullptr, &mr};
+  const int rc = check_matsubara(g, c, mz, d_T);
   return rc ? rc : accumulate_mc(g, d_K, ks, kc, d_T, ts, tc, kF, beta, lambda, c);
 }
 

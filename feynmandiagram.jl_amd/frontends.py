@@ -114,3 +114,18 @@ def leafstates(leaf_maps: Sequence[Dict[int, Graph]], maxloopNum):
             leafOrders[ikey].append(leaf_orders)
             leafType[ikey].append(index(diag_id))
     return (leafValue, leafType, leafOrders, leafInTau, leafOutTau, leafLoopIndex), loopbasis
+
+
+def root_times(graphs: Sequence[Graph], pair=(0, 1)):
+    """``(tau_in, tau_out)``, one 1-based label per graph: the pair of external times a root's Matsubara phase is taken of,
+    ``tau = T[tau_out] - T[tau_in]`` (the reference's ``extT_labels``, example/benchmark.jl:26-31; ``phase(varT, ver4.Tpair[...])``,
+    test/ver4.jl:193).  The labels are entries ``pair`` of every graph's ``properties.extT``: ``(in, out)`` of a self-energy's two
+    times, as :func:`leafstates` reads a propagator's; for the four times of a vertex the caller names the two it projects."""
+    tin, tout = [], []
+    for g in graphs:
+        ext = tuple(g.properties.extT)
+        if max(pair) >= len(ext):
+            raise ValueError(f"a graph carries {len(ext)} external times: pair {pair} names none of them")
+        tin.append(int(ext[pair[0]]))
+        tout.append(int(ext[pair[1]]))
+    return tin, tout

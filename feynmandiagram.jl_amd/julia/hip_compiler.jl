@@ -365,6 +365,75 @@ function fdg_sincos(x::Float64)
     ccall((:fdg_sincos, _libfdg), Cvoid, (Float64, Ref{Float64}, Ref{Float64}), x, s, c)
     return s[], c[]
 end
+# ---- projection onto Matsubara frequencies (include/fdg.h; no counterpart in the reference: the caller's side of test/ver4.jl:193) ---- #
+# (sin, cos) of omega_n tau by the routine the projection pass uses (fdg_matsubara_phase): omega_n = (2n+1) pi / beta or 2n pi / beta.
+function fdg_matsubara_phase(tau::Float64, beta::Float64, n::Integer; fermionic::Bool=true)
+    s, c = Ref{Float64}(0.0), Ref{Float64}(0.0)
+    ccall((:fdg_matsubara_phase, _libfdg), Cvoid, (Float64, Float64, Int32, Cint, Ref{Float64}, Ref{Float64}), tau, beta, n, fermionic ? 1 : 0, s, c)
+    return s[], c[]
+end
+struct _FdgMatsubara
+    n_freq::UInt32
+    fermionic::Int32
+    freq::Ptr{Int32}
+    root_tau_in::Ptr{Int32}
+    root_tau_out::Ptr{Int32}
+    beta::Float64
+    d_T::Ptr{Float64}
+    t_sample_stride::Int64
+    t_comp_stride::Int64
+    n_tau::UInt32
+    d_acc_re::Ptr{Float64}
+    d_acc_im::Ptr{Float64}
+    d_acc2_re::Ptr{Float64}
+    d_acc2_im::Ptr{Float64}
+end
+# Root k times e^{i omega_n (T[tau_out[k]] - T[tau_in[k]])} summed per (root, frequency, bin): d_sums points at four R x n_freq x n_bin
+# arrays in a row (real parts, imaginary parts, their squares).  d_bin = C_NULL: one bin.  d_acc / d_acc2 (both or neither): the
+# unprojected moments as accumulate_device_moments! leaves them.  n_dim = 0 and d_hist = C_NULL: no training; otherwise d_hist (and
+# d_hist_bin) as accumulate_device_vegas[_binned]! leave them.  d_T is B x n_tau column-major by default.
+function accumulate_device_matsubara!(f::GraphFunc, d_sums::Ptr{Float64}, d_leaf::Ptr{Float64}, d_T::Ptr{Float64}, freq::Vector{Int},
+    root_tau_in::Vector{Int}, root_tau_out::Vector{Int}, B::Integer; beta::Float64, n_tau::Integer, fermionic::Bool=true,
+    d_bin::Ptr{Int32}=Ptr{Int32}(C_NULL), n_bin::Integer=1, bin_base::Integer=1, d_weight::Ptr{Float64}=Ptr{Float64}(C_NULL),
+    coef::Union{Nothing,Vector{Float64}}=nothing, seed::Integer=0, sample_offset::Integer=0, n_dim::Integer=0, n_grid::Integer=0,
+    d_acc::Ptr{Float64}=Ptr{Float64}(C_NULL), d_acc2::Ptr{Float64}=Ptr{Float64}(C_NULL), d_hist::Ptr{Float64}=Ptr{Float64}(C_NULL),
+    d_hist_bin::Ptr{Float64}=Ptr{Float64}(C_NULL), leaf_strides=(1, B), tile_stride::Integer=0, t_strides=(1, B),
+    stream::Ptr{Cvoid}=C_NULL)
+    a = [Int32.(v) for v in (freq, root_tau_in, root_tau_out)]
+    n = 8 * n_bin * length(freq) * length(root_tau_in)
+    GC.@preserve a begin
+        mz = _FdgMatsubara(length(freq), fermionic ? 1 : 0, pointer(a[1]), pointer(a[2]), pointer(a[3]), beta, d_T, t_strides[1], t_strides[2],
+            n_tau, d_sums, d_sums + n, d_sums + 2n, d_sums + 3n)
+        _fdg_check(ccall((:fdg_accumulate_device_matsubara, _libfdg), Cint,
+            (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Int64, Ptr{Int32}, Int32, UInt32, Ptr{Float64}, Ptr{Float64}, UInt64, UInt64, UInt32,
+             UInt32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{_FdgMatsubara}, Int64, Ptr{Cvoid}),
+            f.handle, d_leaf, leaf_strides[1], leaf_strides[2], tile_stride, d_bin, bin_base, n_bin, d_weight,
+            coef === nothing ? C_NULL : coef, seed, sample_offset, n_dim, n_grid, d_acc, d_acc2, d_hist, d_hist_bin, mz, B, stream))
+    end
+    return nothing
+end
+# the same for the fused step (fdg_mc_accumulate_device_matsubara): the phases are taken of the call's own T
+function mc_accumulate_device_matsubara!(f::GraphFunc, d_sums::Ptr{Float64}, d_K::Ptr{Float64}, d_T::Ptr{Float64}, freq::Vector{Int},
+    root_tau_in::Vector{Int}, root_tau_out::Vector{Int}, B::Integer; kF::Float64, beta::Float64, lambda::Float64, n_tau::Integer,
+    fermionic::Bool=true, d_bin::Ptr{Int32}=Ptr{Int32}(C_NULL), n_bin::Integer=1, bin_base::Integer=1,
+    d_weight::Ptr{Float64}=Ptr{Float64}(C_NULL), coef::Union{Nothing,Vector{Float64}}=nothing, seed::Integer=0, sample_offset::Integer=0,
+    n_dim::Integer=0, n_grid::Integer=0, d_acc::Ptr{Float64}=Ptr{Float64}(C_NULL), d_acc2::Ptr{Float64}=Ptr{Float64}(C_NULL),
+    d_hist::Ptr{Float64}=Ptr{Float64}(C_NULL), d_hist_bin::Ptr{Float64}=Ptr{Float64}(C_NULL), k_strides=(1, B), t_strides=(1, B),
+    stream::Ptr{Cvoid}=C_NULL)
+    a = [Int32.(v) for v in (freq, root_tau_in, root_tau_out)]
+    n = 8 * n_bin * length(freq) * length(root_tau_in)
+    GC.@preserve a begin
+        mz = _FdgMatsubara(length(freq), fermionic ? 1 : 0, pointer(a[1]), pointer(a[2]), pointer(a[3]), beta, Ptr{Float64}(C_NULL), 0, 0,
+            n_tau, d_sums, d_sums + n, d_sums + 2n, d_sums + 3n)
+        _fdg_check(ccall((:fdg_mc_accumulate_device_matsubara, _libfdg), Cint,
+            (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Int64, Float64, Float64, Float64, Ptr{Int32}, Int32, UInt32,
+             Ptr{Float64}, Ptr{Float64}, UInt64, UInt64, UInt32, UInt32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+             Ref{_FdgMatsubara}, Int64, Ptr{Cvoid}),
+            f.handle, d_K, k_strides[1], k_strides[2], d_T, t_strides[1], t_strides[2], kF, beta, lambda, d_bin, bin_base, n_bin, d_weight,
+            coef === nothing ? C_NULL : coef, seed, sample_offset, n_dim, n_grid, d_acc, d_acc2, d_hist, d_hist_bin, mz, B, stream))
+    end
+    return nothing
+end
 # device memory for a batch, backed by physical chunks of `chunk_bytes` (0: one allocation): fdg_batch_alloc / fdg_batch_free
 function batch_alloc(bytes::Integer; chunk_bytes::Integer=0)
     p = Ref{Ptr{Cvoid}}(C_NULL)
@@ -413,7 +482,7 @@ function accumulate_device!(f::GraphFunc, d_acc::Ptr{Float64}, d_leaf::Ptr{Float
         f.handle, d_leaf, leaf_strides[1], leaf_strides[2], d_weight, d_acc, B, stream))
 end
 
-export compile_hip, GraphFunc, eval_device!, accumulate_device!, eval_device_tiled!, accumulate_device_tiled!, accumulate_device_binned!, mc_accumulate_device_binned!, accumulate_device_moments!, mc_accumulate_device_moments!, vegas_sample_device!, accumulate_device_vegas!, mc_accumulate_device_vegas!, vegas_refine!, vegas_sample_device_discrete!, accumulate_device_vegas_binned!, mc_accumulate_device_vegas_binned!, vegas_refine_discrete!, vegas_sample_device_polar!, fdg_sincos, batch_alloc, batch_free, tile_major!, from_tile_major!
+export compile_hip, GraphFunc, eval_device!, accumulate_device!, eval_device_tiled!, accumulate_device_tiled!, accumulate_device_binned!, mc_accumulate_device_binned!, accumulate_device_moments!, mc_accumulate_device_moments!, vegas_sample_device!, accumulate_device_vegas!, mc_accumulate_device_vegas!, vegas_refine!, vegas_sample_device_discrete!, accumulate_device_vegas_binned!, mc_accumulate_device_vegas_binned!, vegas_refine_discrete!, vegas_sample_device_polar!, fdg_sincos, fdg_matsubara_phase, accumulate_device_matsubara!, mc_accumulate_device_matsubara!, batch_alloc, batch_free, tile_major!, from_tile_major!
 
 # ---- multi-GPU: one Julia process per GPU, ONE reduction of the accumulated observable ------------ #
 # (include/fdg.h, "multi-GPU").  Rank 0 calls `comm_unique_id()` and ships the 128 bytes to the other

@@ -14,6 +14,10 @@ reference's test/ver4.jl:221-250 -- so that one run fills an observable ``[n_bin
 Spherical momentum variables (``PolarVar``, ``ball``, the keyword ``polar``; fdg_vegas_sample_device_polar): a group of 2 or 3
 consecutive variables is a modulus and a direction -- ``K = MCIntegration.FermiK(dim, kF, 0.2 kF, 10 kF)`` of the reference's
 example/benchmark.jl:46 -- and the sampler writes the Cartesian components; the accumulate calls and the refinement are the same.
+
+Matsubara frequencies (``MatsubaraProjection``, the keyword ``matsubara``; fdg_mc_accumulate_device_matsubara): every root is multiplied
+by the phase of its own pair of external times before it is summed -- ``phase(varT, ver4.Tpair[...])`` of the reference's
+test/ver4.jl:193 -- so the estimate is complex, one number per frequency and root; the map is trained on the unprojected roots as before.
 """
 from __future__ import annotations
 
@@ -152,9 +156,22 @@ def _check_polar(polar, col, vmap, n_col):
     return groups
 
 
+@dataclass(frozen=True)
+class MatsubaraProjection:
+    """The frequencies an integration projects its roots onto: ``freq`` the integers ``n`` of ``omega_n = (2n+1) pi / beta``
+    (``fermionic``) or ``2n pi / beta``, ``root_tau_in`` / ``root_tau_out`` the 1-based labels of every root's pair of external times
+    (``workloads.root_times``).  Root ``k`` enters as ``root_k * e^{+i omega_n (T[tau_out] - T[tau_in])}``
+    (``capi.matsubara_phase``); for the other sign pass ``-n`` (fermions: ``-n - 1``)."""
+    freq: Tuple[int, ...]
+    fermionic: bool
+    root_tau_in: Tuple[int, ...]
+    root_tau_out: Tuple[int, ...]
+
+
 def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter, n_sample, n_grid, alpha, floor, seed, n_discard, fixed, coef,
-               device, vmap, specialize_fused, n_total, shard_start, reduce, polar=None):
-    """The driver behind :func:`vegas_integrate` (``dmap`` None: results ``[R]``) and :func:`vegas_integrate_binned` (``[n_bin, R]``)."""
+               device, vmap, specialize_fused, n_total, shard_start, reduce, polar=None, matsubara=None):
+    """The driver behind :func:`vegas_integrate` (``dmap`` None: results ``[R]``) and :func:`vegas_integrate_binned` (``[n_bin, R]``);
+    with ``matsubara`` the results are complex and carry a frequency axis in front of the roots."""
     import torch
     handle = getattr(func_or_handle, "handle", func_or_handle)
     device = torch.device(device)
@@ -187,6 +204,13 @@ def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter,
     if fx.shape != (n_col,):
         raise ValueError(f"fixed must hold {n_col} column values")
     shape = (R,) if dmap is None else (NB, R)
+    if matsubara is not None:
+        NF = len(matsubara.freq)
+        if not (1 <= NF <= capi.FDG_MATSUBARA_FREQ_MAX and NB * NF <= capi.FDG_BIN_MAX):
+            raise ValueError(f"need 1 .. {capi.FDG_MATSUBARA_FREQ_MAX} frequencies and n_bin * n_freq <= {capi.FDG_BIN_MAX}")
+        if len(matsubara.root_tau_in) != R or len(matsubara.root_tau_out) != R:
+            raise ValueError("matsubara.root_tau_in and root_tau_out hold one label per root")
+        shape = shape[:-1] + (NF, R)
     if dmap is None:
         out = VegasResult(np.zeros(shape), np.zeros(shape), np.full(shape, np.nan), map=vmap)
     else:
@@ -212,7 +236,17 @@ def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter,
             else:
                 capi.vegas_sample_device_discrete(vmap.d_grid.data_ptr(), D, G, col, dmap.d_cdf.data_ptr(), NB, 0, d_ext, dmap.ext_col, seed,
                                                   off, x.data_ptr(), 1, B, jac.data_ptr(), bins.data_ptr(), 0, B, st)
-            if dmap is None:
+            if matsubara is not None:
+                # (re, im, re^2, im^2) of the projected roots; the training histograms as the calls below leave them
+                m = torch.zeros((4, NB, NF, R), dtype=torch.float64, device=device)
+                hist_bin = None if dmap is None else torch.zeros(NB, dtype=torch.float64, device=device)
+                desc, _keep = capi.make_matsubara(matsubara.freq, matsubara.fermionic, matsubara.root_tau_in, matsubara.root_tau_out, beta,
+                                                  n_tau, *[m[i].data_ptr() for i in range(4)])
+                handle.mc_accumulate_device_matsubara(x.data_ptr(), 1, B, d_T, 1, B, kF, beta, lam, 0 if dmap is None else bins.data_ptr(), 0,
+                                                      NB, jac.data_ptr(), desc, coef, seed, off, D, G, 0, 0, hist.data_ptr(),
+                                                      0 if dmap is None else hist_bin.data_ptr(), B, st)
+                sums = [m, hist] if dmap is None else [m, hist, hist_bin]
+            elif dmap is None:
                 handle.mc_accumulate_device_vegas(x.data_ptr(), 1, B, d_T, 1, B, kF, beta, lam, jac.data_ptr(), coef, seed, off, D, G,
                                                   m[0].data_ptr(), m[1].data_ptr(), hist.data_ptr(), B, st)
                 sums = [m, hist]
@@ -225,7 +259,11 @@ def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter,
             if reduce is not None:
                 for t in sums:
                     reduce(t)
-            mean, err = mc_estimate(m[0], m[1], N)
+            if matsubara is not None:
+                (mr, er), (mi, ei) = mc_estimate(m[0], m[2], N), mc_estimate(m[1], m[3], N)
+                mean, err = torch.complex(mr, mi), torch.complex(er, ei)
+            else:
+                mean, err = mc_estimate(m[0], m[1], N)
             out.iterations.append((mean.cpu().numpy().reshape(shape), err.cpu().numpy().reshape(shape)))
             hs = [t.cpu().numpy() for t in sums[1:]]
             out.histograms.append(hs[0])
@@ -234,7 +272,13 @@ def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter,
             vmap.refine(hs[0], alpha)
             if dmap is not None:
                 dmap.refine(hs[1], alpha, floor)
-    mean, err, chi2 = combine(out.iterations[int(n_discard):])
+    kept = out.iterations[int(n_discard):]
+    if matsubara is not None:                 # the real and the imaginary parts are two estimates: combined each on its own
+        re = combine([(a.real, b.real) for a, b in kept])
+        im = combine([(a.imag, b.imag) for a, b in kept])
+        mean, err, chi2 = (r + 1j * i for r, i in zip(re, im))
+    else:
+        mean, err, chi2 = combine(kept)
     out.mean, out.stderr, out.chi2_dof = mean.reshape(shape), err.reshape(shape), chi2.reshape(shape)
     return out
 
@@ -242,7 +286,8 @@ def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter,
 def vegas_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: float = 1.0, lam: float = 0.0, *, n_iter: int = 10,
                     n_sample: int = 100_000, n_grid: int = 64, alpha: float = 0.5, seed: int = 0, n_discard: int = 0, fixed=None,
                     coef=None, device="cuda", vmap: Optional[VegasMap] = None, specialize_fused: bool = True, n_total: Optional[int] = None,
-                    shard_start: int = 0, reduce: Optional[Callable] = None, polar: Optional[Sequence[PolarVar]] = None) -> VegasResult:
+                    shard_start: int = 0, reduce: Optional[Callable] = None, polar: Optional[Sequence[PolarVar]] = None,
+                    matsubara: Optional[MatsubaraProjection] = None) -> VegasResult:
     """Integrates the roots of a graph over the box ``[lo, hi]`` of ``len(col)`` of its Monte-Carlo variables.
 
     ``func_or_handle``: a ``GraphFunc`` or ``capi.GraphHandle``; ``tables`` the ``fdg_leaf_tables`` struct of ``capi.make_leaf_tables``
@@ -259,9 +304,14 @@ def vegas_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: 
     ``polar``: a sequence of :class:`PolarVar`.  The variables of a group are a modulus and a direction (``lo`` / ``hi`` rows as
     :func:`ball` gives them), their ``col`` entries are None, and the group's own ``cols`` take the Cartesian components; the weight
     carries ``k`` or ``k**2 sin(theta)``.  The limits (of ``lo`` / ``hi`` or of a ``vmap`` passed in) must keep ``k >= 0``, ``theta``
-    within ``[0, math.pi]`` and ``phi`` within ``[0, 2 * math.pi]``.  None or empty: the box, with the bits it always had."""
+    within ``[0, math.pi]`` and ``phi`` within ``[0, 2 * math.pi]``.  None or empty: the box, with the bits it always had.
+
+    ``matsubara``: a :class:`MatsubaraProjection`.  Every root is multiplied by the phase of its own pair of times at every frequency
+    before it is summed: ``mean`` is complex ``[n_freq, R]``, ``stderr`` and ``chi2_dof`` carry the figures of the real parts in their
+    real parts and those of the imaginary parts in their imaginary parts (``mc_estimate`` and ``combine`` on each), and ``reduce`` is
+    applied to the ``[4, 1, n_freq, R]`` sums.  The map is trained on the unprojected roots: its histograms are those of a run without."""
     return _integrate(func_or_handle, tables, lo, hi, col, None, kF, beta, lam, n_iter, n_sample, n_grid, alpha, 0.0, seed, n_discard, fixed, coef,
-                      device, vmap, specialize_fused, n_total, shard_start, reduce, polar)
+                      device, vmap, specialize_fused, n_total, shard_start, reduce, polar, matsubara)
 
 
 def uniform_cdf(n_bin: int) -> np.ndarray:
@@ -337,13 +387,14 @@ def vegas_integrate_binned(func_or_handle, tables, lo, hi, col, dmap: DiscreteMa
                            n_iter: int = 10, n_sample: int = 100_000, n_grid: int = 64, alpha: float = 0.5, floor: float = 0.05, seed: int = 0,
                            n_discard: int = 0, fixed=None, coef=None, device="cuda", vmap: Optional[VegasMap] = None,
                            specialize_fused: bool = True, n_total: Optional[int] = None, shard_start: int = 0,
-                           reduce: Optional[Callable] = None, polar: Optional[Sequence[PolarVar]] = None) -> VegasBinnedResult:
+                           reduce: Optional[Callable] = None, polar: Optional[Sequence[PolarVar]] = None,
+                           matsubara: Optional[MatsubaraProjection] = None) -> VegasBinnedResult:
     """:func:`vegas_integrate` with a discrete variable: every sample draws a value ``j`` of ``dmap`` next to its continuous variables,
     the columns ``dmap.ext_col`` take row ``j`` of ``dmap.ext`` (external momenta), and the estimate is per value: arrays ``[n_bin, R]``,
     bin ``j`` the integral over the continuous variables at configuration ``j`` (the weight carries ``1 / p_j``, and ``mc_estimate``
     takes the whole batch as ``N``).  Per iteration: sample, accumulate (binned moments and both training histograms in one pass),
     ``mc_estimate``, refine the map with ``alpha`` and the probabilities with ``alpha`` and ``floor``.  ``combine`` is per (bin, root).
     Sharding as in :func:`vegas_integrate`; ``reduce`` is applied to the moments ``[2, n_bin, R]`` and to both histograms, so every rank
-    refines the same maps.  ``polar`` as in :func:`vegas_integrate`."""
+    refines the same maps.  ``polar`` and ``matsubara`` as in :func:`vegas_integrate` (complex ``[n_bin, n_freq, R]``)."""
     return _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter, n_sample, n_grid, alpha, floor, seed, n_discard, fixed,
-                      coef, device, vmap, specialize_fused, n_total, shard_start, reduce, polar)
+                      coef, device, vmap, specialize_fused, n_total, shard_start, reduce, polar, matsubara)

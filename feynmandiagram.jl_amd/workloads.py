@@ -87,6 +87,22 @@ def parquet_graphs(name: str):
     return graphs, rows
 
 
+def root_times(name: str, pair=(0, 1)):
+    """``(tau_in[R], tau_out[R])`` of a parquet workload, int32 and 1-based: the external times of every root, from the front end's
+    rows (``extT``; ``frontends.root_times`` on their graphs) -- what ``GraphFunc.accumulate_matsubara`` and
+    ``vegas.MatsubaraProjection`` take.  ``sigma2`` is the fixture of ``parquet_sigma2``'s two rows; a ``_taylor2`` workload repeats
+    the rows once per order (its roots are orders 0, 1, 2 x the rows)."""
+    from . import frontends
+    taylor2 = name.endswith("_taylor2")
+    base = name[:-len("_taylor2")] if taylor2 else name
+    graphs, _ = parquet_graphs("parquet_sigma2" if base == "sigma2" else base)
+    tin, tout = frontends.root_times(graphs, pair)
+    rep = get(name).n_root // len(tin)
+    if rep * len(tin) != get(name).n_root:
+        raise ValueError(f"{name}: {get(name).n_root} roots do not match {len(tin)} rows")
+    return np.array(tin * rep, np.int32), np.array(tout * rep, np.int32)
+
+
 @functools.lru_cache(maxsize=None)
 def _parquet_lowered(name: str):
     """(table, leafmap) of a parquet workload."""

@@ -744,6 +744,77 @@ int fdg_vegas_sample_device_polar(const double *d_grid, uint32_t n_dim, uint32_t
  * call the very same routine.  Pure host function. */
 void fdg_sincos(double x, double *s, double *c);
 
+/* ---- Projection of the roots onto Matsubara frequencies in the accumulate step -------------------------------------------------------
+ * Every root of a self-energy or vertex graph carries its own pair of external times (extT_labels, example/benchmark.jl:26-31), which
+ * are integration variables; the `measure` step of a real calculation multiplies root k by a phase of tau_k = T[t_out(k)] - T[t_in(k)]
+ * before it sums -- phase(varT, ver4.Tpair[...]) of test/ver4.jl:193 -- and so obtains Sigma(i omega_n) or Gamma at given frequencies:
+ * one complex number per root, frequency and external configuration.  That is the caller's side of test/ver4.jl:193 (the integrand
+ * handed to MCIntegration): no counterpart in the reference checkout.
+ *
+ * fdg_matsubara_phase: (s, c) = (sin, cos) of omega_n tau, omega_n = (2n+1) pi / beta (fermionic != 0) or 2n pi / beta, n of either
+ * sign; the convention is e^{+i omega_n tau} = c + i s (for the other sign pass -n, fermions: -n - 1).  Every line ONE rounded fp64
+ * operation, no FMA, in this order (csrc/fdg_matsubara.h, shared by host and device; a numpy restatement gives the same bits):
+ *     x  = tau / beta
+ *     m  = x * (double)(fermionic ? 2n+1 : 2n)
+ *     h  = m * 0.5;   fl = floor(h);   r = h - fl        (0 <= r <= 1)
+ *     th = r * 6.283185307179586                         (inside fdg_sincos' domain, its top end included)
+ *     (s, c) = fdg_sincos(th)
+ * |s - sin|, |c - cos| <= (4 pi |2n+1| + 16) * 2^-53 for |tau| <= beta.  A bosonic n = 0 gives exactly (0, 1).  Pure host function.
+ *
+ * The accumulate calls: for every sample b whose bin j = d_bin[b] - bin_base lies in [0, n_bin) (d_bin NULL: every sample in bin 0,
+ * n_bin must be 1), every root k that exists and every frequency f < n_freq,
+ *     t   = w_b * root_k(b)                               (the moments call's term; d_weight NULL: t = root)
+ *     tau = T[b][root_tau_out[k]] - T[b][root_tau_in[k]]
+ *     (s, c) = fdg_matsubara_phase(tau, beta, freq[f], fermionic)
+ *     tre = t * c;   tim = t * s
+ *     d_acc_re [(j * n_freq + f) * R + k] += tre;         d_acc_im [..] += tim
+ *     d_acc2_re[(j * n_freq + f) * R + k] += tre * tre;   d_acc2_im[..] += tim * tim      (squares rounded before they are added)
+ * The four arrays hold n_bin x n_freq x n_root doubles each (torch [n_bin, n_freq, R]) and are added to; FDG_NO_ROOT columns stay
+ * untouched in all four.  freq (n_freq int32), root_tau_in and root_tau_out (n_root int32 each, 1-based like fdg_leaf_tables) are HOST
+ * arrays.  T element (b, i), i 1-based: d_T[b * t_sample_stride + (i - 1) * t_comp_stride], as fdg_leaf_eval_device addresses it.  In
+ * the Monte-Carlo form a NULL d_T in the descriptor means the call's own T and strides.  beta is the descriptor's in both forms.
+ *
+ * Besides the descriptor each call takes what the _vegas_binned calls take, with more of it optional:
+ *   d_bin       NULL: no discrete variable (n_bin 1, d_hist_bin must be NULL): the arguments of the calls without one.
+ *   d_acc, d_acc2  both NULL: the unprojected moments are not wanted; both given: bit for bit what the moments calls leave.
+ *   the training block  n_dim == 0 and d_hist == NULL: no training.  Otherwise d_hist (and d_hist_bin, when given) come out bit for
+ *               bit as fdg_[mc_]accumulate_device_vegas[_binned] leave them for the same arguments: the training stays on the
+ *               unprojected (w sum_k c_k r_k)^2 and its plan does not change.
+ * The roots of a chunk are evaluated once for everything the call produces, through the handle's root scratch by the route of
+ * fdg_eval_device / fdg_mc_eval_device (every back end, layout, association and Monte-Carlo route).  No float atomics; samples past
+ * n_sample or with a bin out of range are selected away, never multiplied by zero; the order of every sum of the four arrays is a
+ * function of (n_sample, n_bin, n_freq, n_root, FDG_ROOT_SCRATCH_MB) only, so the same arguments give the same bits (csrc/fdg_binned.hip,
+ * DESIGN.md 8e).
+ * FDG_E_INVALID: a NULL descriptor, freq, root_tau_in, root_tau_out, T or one of the four arrays; any two output arrays of the call
+ * the same buffer; one of d_acc, d_acc2 without the other; n_freq == 0; beta <= 0; a time label of an existing root outside
+ * [1, n_tau]; d_hist_bin without d_bin; the cases of the moments and VEGAS calls.  FDG_E_UNSUPPORTED: n_freq > FDG_MATSUBARA_FREQ_MAX,
+ * n_bin * n_freq > FDG_BIN_MAX, and those calls' limits.  All before any device work. */
+#define FDG_MATSUBARA_FREQ_MAX 64
+typedef struct fdg_matsubara {
+  uint32_t n_freq;             /* 1 .. FDG_MATSUBARA_FREQ_MAX */
+  int32_t fermionic;           /* != 0: omega_n = (2n+1) pi / beta;  0: 2n pi / beta */
+  const int32_t *freq;         /* HOST [n_freq]: the n of every frequency */
+  const int32_t *root_tau_in;  /* HOST [n_root], 1-based index into T */
+  const int32_t *root_tau_out; /* HOST [n_root] */
+  double beta;
+  const double *d_T;           /* device; NULL in the Monte-Carlo form: the call's T */
+  int64_t t_sample_stride, t_comp_stride;
+  uint32_t n_tau;
+  double *d_acc_re, *d_acc_im, *d_acc2_re, *d_acc2_im;   /* device, [n_bin][n_freq][n_root] each */
+} fdg_matsubara;
+void fdg_matsubara_phase(double tau, double beta, int32_t n, int fermionic, double *s, double *c);
+int fdg_accumulate_device_matsubara(fdg_graph *g, const double *d_leaf, int64_t leaf_sample_stride, int64_t leaf_leaf_stride,
+                                    int64_t leaf_tile_stride, const int32_t *d_bin, int32_t bin_base, uint32_t n_bin,
+                                    const double *d_weight, const double *coef, uint64_t seed, uint64_t sample_offset, uint32_t n_dim,
+                                    uint32_t n_grid, double *d_acc, double *d_acc2, double *d_hist, double *d_hist_bin,
+                                    const fdg_matsubara *mz, int64_t n_sample, void *stream);
+int fdg_mc_accumulate_device_matsubara(fdg_graph *g, const double *d_K, int64_t k_sample_stride, int64_t k_comp_stride,
+                                       const double *d_T, int64_t t_sample_stride, int64_t t_comp_stride, double kF, double beta,
+                                       double lambda, const int32_t *d_bin, int32_t bin_base, uint32_t n_bin, const double *d_weight,
+                                       const double *coef, uint64_t seed, uint64_t sample_offset, uint32_t n_dim, uint32_t n_grid,
+                                       double *d_acc, double *d_acc2, double *d_hist, double *d_hist_bin, const fdg_matsubara *mz,
+                                       int64_t n_sample, void *stream);
+
 /* Device workspace control: the interpreter keeps per-sample overflow slots in
  * an HBM panel owned by the handle; it is sized on first use for the number of
  * resident waves.  This releases it (and any loaded module). */
