@@ -48,12 +48,14 @@ EXPORTS = [
     "fdg_vegas_refine_discrete",
     "fdg_vegas_sample_device_polar", "fdg_sincos",
     "fdg_matsubara_phase", "fdg_accumulate_device_matsubara", "fdg_mc_accumulate_device_matsubara",
+    "fdg_vegas_sample_device_grouped", "fdg_accumulate_device_grouped", "fdg_mc_accumulate_device_grouped",
 ]
 FDG_BIN_MAX = 16384     # fdg_accumulate_device_binned: largest n_bin
 FDG_VEGAS_DIM_MAX, FDG_VEGAS_GRID_MAX = 64, 1024     # the VEGAS map: most variables, most cells per variable
 FDG_VEGAS_EXT_MAX = 16  # the discrete variable's table: most columns per value
 FDG_VEGAS_POLAR_MAX = 21  # fdg_vegas_sample_device_polar: most groups of polar variables
 FDG_MATSUBARA_FREQ_MAX = 64  # fdg_[mc_]accumulate_device_matsubara: most frequencies per call
+FDG_WEIGHT_GROUP_MAX = 8  # fdg_weight_groups: most groups of roots with their own integration variables
 COMM_ID_BYTES = 128
 
 
@@ -107,6 +109,11 @@ class Matsubara(C.Structure):
                 ("root_tau_out", C.c_void_p), ("beta", C.c_double), ("d_T", C.c_void_p), ("t_sample_stride", C.c_int64),
                 ("t_comp_stride", C.c_int64), ("n_tau", C.c_uint32), ("d_acc_re", C.c_void_p), ("d_acc_im", C.c_void_p),
                 ("d_acc2_re", C.c_void_p), ("d_acc2_im", C.c_void_p)]
+
+
+class WeightGroups(C.Structure):
+    """fdg_weight_groups (include/fdg.h)"""
+    _fields_ = [("n_group", C.c_uint32), ("root_group", C.c_void_p), ("var_mask", C.c_void_p), ("weight_group_stride", C.c_int64)]
 
 
 class OptParams(C.Structure):
@@ -242,6 +249,12 @@ def lib():
                                                   dp, dp, C.c_void_p, i64, vp]
     L.fdg_mc_accumulate_device_matsubara.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, C.c_int32,
                                                      u32, dp, C.c_void_p, u64, u64, u32, u32, dp, dp, dp, dp, C.c_void_p, i64, vp]
+    L.fdg_vegas_sample_device_grouped.argtypes = [dp, u32, u32, C.c_void_p, dp, u32, C.c_int32, dp, u32, C.c_void_p, C.c_void_p, u32,
+                                                  C.c_void_p, u32, i64, u64, u64, dp, i64, i64, dp, dp, dp, i64, vp]
+    L.fdg_accumulate_device_grouped.argtypes = [vp, dp, i64, i64, i64, dp, C.c_int32, u32, dp, C.c_void_p, u64, u64, u32, u32, dp, dp,
+                                                dp, dp, C.c_void_p, C.c_void_p, i64, vp]
+    L.fdg_mc_accumulate_device_grouped.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, C.c_int32,
+                                                   u32, dp, C.c_void_p, u64, u64, u32, u32, dp, dp, dp, dp, C.c_void_p, C.c_void_p, i64, vp]
     L.fdg_powi.argtypes = [C.c_double, C.c_int32]
     L.fdg_powi.restype = C.c_double
     _lib = L
@@ -519,6 +532,28 @@ class GraphHandle:
                                                        sample_offset, n_dim, n_grid, d_acc or None, d_acc2 or None, d_hist or None,
                                                        d_hist_bin or None, None if desc is None else C.addressof(desc), B, stream))
 
+    # weight groups: groups = make_weight_groups(...)[0], d_weight [n_group, stride]; desc None: no projection; the rest as the
+    # projection calls take it (fdg.h)
+    def accumulate_device_grouped(self, d_leaf: int, ss: int, ls: int, lts: int, d_bin: int, bin_base: int, n_bin: int, d_weight: int,
+                                  groups, desc=None, coef=None, seed: int = 0, sample_offset: int = 0, n_dim: int = 0, n_grid: int = 0,
+                                  d_acc: int = 0, d_acc2: int = 0, d_hist: int = 0, d_hist_bin: int = 0, B: int = 0, stream: int = 0):
+        c = self._coef(coef)
+        check(lib().fdg_accumulate_device_grouped(self._h, d_leaf or None, ss, ls, lts, d_bin or None, bin_base, n_bin, d_weight or None,
+                                                  None if c is None else c.ctypes.data, seed, sample_offset, n_dim, n_grid,
+                                                  d_acc or None, d_acc2 or None, d_hist or None, d_hist_bin or None,
+                                                  None if desc is None else C.addressof(desc),
+                                                  None if groups is None else C.addressof(groups), B, stream))
+
+    def mc_accumulate_device_grouped(self, d_K, ks, kc, d_T, ts, tc, kF, beta, lam, d_bin, bin_base, n_bin, d_weight, groups, desc=None,
+                                     coef=None, seed=0, sample_offset=0, n_dim=0, n_grid=0, d_acc=0, d_acc2=0, d_hist=0, d_hist_bin=0, B=0,
+                                     stream=0):
+        c = self._coef(coef)
+        check(lib().fdg_mc_accumulate_device_grouped(self._h, d_K or None, ks, kc, d_T or None, ts, tc, kF, beta, lam, d_bin or None,
+                                                     bin_base, n_bin, d_weight or None, None if c is None else c.ctypes.data, seed,
+                                                     sample_offset, n_dim, n_grid, d_acc or None, d_acc2 or None, d_hist or None,
+                                                     d_hist_bin or None, None if desc is None else C.addressof(desc),
+                                                     None if groups is None else C.addressof(groups), B, stream))
+
     def _coef(self, coef):
         if coef is None:
             return None
@@ -623,6 +658,14 @@ def vegas_sample_device_polar(d_grid: int, n_dim: int, n_grid: int, col, d_cdf: 
     e = np.ascontiguousarray([] if ext_col is None else ext_col, dtype=np.uint32)
     if e.ndim != 1:
         raise ValueError("ext_col must be a sequence of column numbers")
+    arr, n_polar = _polar_array(polar)
+    check(lib().fdg_vegas_sample_device_polar(d_grid or None, n_dim, n_grid, None if c is None else c.ctypes.data, d_cdf or None, n_bin,
+                                              bin_base, d_ext or None, e.shape[0], e.ctypes.data if e.shape[0] else None,
+                                              C.addressof(arr) if n_polar else None, n_polar, seed, sample_offset, d_x or None, xs, xc,
+                                              d_jac or None, d_bin or None, d_cell or None, B, stream))
+
+
+def _polar_array(polar):
     groups = [] if polar is None else list(polar)
     arr = (VegasPolar * max(len(groups), 1))()
     for g, (var, cols) in enumerate(groups):
@@ -632,10 +675,78 @@ def vegas_sample_device_polar(d_grid: int, n_dim: int, n_grid: int, col, d_cdf: 
         arr[g].var, arr[g].dim = int(var), len(cols)
         for i, v in enumerate(cols):
             arr[g].col[i] = v
-    check(lib().fdg_vegas_sample_device_polar(d_grid or None, n_dim, n_grid, None if c is None else c.ctypes.data, d_cdf or None, n_bin,
-                                              bin_base, d_ext or None, e.shape[0], e.ctypes.data if e.shape[0] else None,
-                                              C.addressof(arr) if groups else None, len(groups), seed, sample_offset, d_x or None, xs, xc,
-                                              d_jac or None, d_bin or None, d_cell or None, B, stream))
+    return arr, len(groups)
+
+
+def var_masks(var_sets) -> np.ndarray:
+    """The ``var_mask`` words of ``fdg_weight_groups``: one uint64 per group, bit ``d`` set for every variable ``d`` of the group's set."""
+    out = np.zeros(len(var_sets), dtype=np.uint64)
+    for g, vs in enumerate(var_sets):
+        for d in vs:
+            if not 0 <= int(d) < FDG_VEGAS_DIM_MAX:
+                raise ValueError(f"a variable must lie in [0, {FDG_VEGAS_DIM_MAX})")
+            out[g] |= np.uint64(1) << np.uint64(int(d))
+    return out
+
+
+def make_weight_groups(root_group, var_sets, stride: int = 0):
+    """``(fdg_weight_groups struct, keepalive)``: ``root_group`` the group of every root, ``var_sets[g]`` the VEGAS variables of group
+    ``g`` (host sequences); ``stride`` the distance in doubles between the groups' weight columns."""
+    rg = np.ascontiguousarray(root_group, dtype=np.uint32)
+    vm = var_masks(var_sets)
+    if rg.ndim != 1 or vm.shape[0] < 1:
+        raise ValueError("root_group is a vector and there is at least one group")
+    return WeightGroups(vm.shape[0], rg.ctypes.data, vm.ctypes.data, int(stride)), (rg, vm)
+
+
+def vegas_sample_device_grouped(d_grid: int, n_dim: int, n_grid: int, col, d_cdf: int, n_bin: int, bin_base: int, d_ext: int, ext_col, polar,
+                                var_sets, jac_group_stride: int, seed: int, sample_offset: int, d_x: int, xs: int, xc: int, d_jac: int,
+                                d_bin: int, d_cell: int, B: int, stream: int = 0):
+    """fdg_vegas_sample_device_grouped: :func:`vegas_sample_device_polar` with one jacobian per weight group,
+    ``jac[g * jac_group_stride + b]`` the fold over the variables ``var_sets[g]`` only (``var_sets``: a sequence of sets of variables, or
+    the uint64 masks themselves)."""
+    c = None
+    if col is not None:
+        c = np.ascontiguousarray([0 if v is None else v for v in col], dtype=np.uint32)
+        if c.shape != (n_dim,):
+            raise ValueError("col must name one column per variable")
+    e = np.ascontiguousarray([] if ext_col is None else ext_col, dtype=np.uint32)
+    if e.ndim != 1:
+        raise ValueError("ext_col must be a sequence of column numbers")
+    arr, n_polar = _polar_array(polar)
+    vm = var_sets if isinstance(var_sets, np.ndarray) and var_sets.dtype == np.uint64 else var_masks(var_sets)
+    vm = np.ascontiguousarray(vm)
+    check(lib().fdg_vegas_sample_device_grouped(d_grid or None, n_dim, n_grid, None if c is None else c.ctypes.data, d_cdf or None, n_bin,
+                                                bin_base, d_ext or None, e.shape[0], e.ctypes.data if e.shape[0] else None,
+                                                C.addressof(arr) if n_polar else None, n_polar, vm.ctypes.data if vm.shape[0] else None,
+                                                vm.shape[0], jac_group_stride, seed, sample_offset, d_x or None, xs, xc, d_jac or None,
+                                                d_bin or None, d_cell or None, B, stream))
+
+
+def grouped_jacobian(factor, var_sets, polar=(), value=None, prob=None) -> np.ndarray:
+    """The numpy restatement of the grouped sampler's weights, ``[n_group, B]``, one numpy operation per rounded operation of the
+    kernel and in its order.  ``factor [B, D]``: ``G * wd_d`` of every sample's cell; ``polar``: ``(var, cols)`` groups, whose modulus
+    and polar angle are read from ``value [B, D]`` (the drawn values; the sine through :func:`sincos`); ``prob [B]``: the probability of
+    the discrete variable's value, None without one."""
+    f = np.asarray(factor, dtype=np.float64)
+    B, D = f.shape
+    sin_of = np.frompyfunc(lambda t: sincos(t)[0], 1, 1)
+    out = np.empty((len(var_sets), B))
+    for g, vs in enumerate(var_sets):
+        mine = {int(d) for d in vs}
+        j = np.ones(B)
+        for d in range(D):
+            if d in mine:
+                j = j * f[:, d]
+        for var, cols in polar:
+            if var in mine:
+                k = np.asarray(value, dtype=np.float64)[:, var]
+                j = j * k
+                if len(cols) == 3:
+                    j = j * k
+                    j = j * sin_of(np.asarray(value, dtype=np.float64)[:, var + 1]).astype(np.float64)
+        out[g] = j if prob is None else j / np.asarray(prob, dtype=np.float64)
+    return out
 
 
 def vegas_refine_discrete(cdf: np.ndarray, hist_bin: np.ndarray, alpha: float = 0.5, floor: float = 0.05) -> np.ndarray:

@@ -39,6 +39,12 @@
 // Matsubara projection (fdg_[mc_]accumulate_device_matsubara): one more pass per chunk over the same roots (fdg_matsubara_partials
 // below) that multiplies every root by the phase of its own pair of external times at every frequency and sums the real and imaginary
 // parts and their squares per (bin, frequency, root); the moments pass and the training passes run beside it when the call asks for them.
+//
+// Weight groups (fdg_vegas_sample_device_grouped, fdg_[mc_]accumulate_device_grouped): roots are assigned to groups, every group owns a
+// set of the VEGAS variables and has its own weight column.  Each kernel above carries a GRP template flag: the sampler folds every
+// variable into the jacobians of the groups that own it, the moments and projection passes read the weight column of a root's group,
+// and the training passes sum (w_g s_g)^2 over the groups that own a variable.  The ungrouped instantiations are the code they were;
+// a grouped call with one group and a full mask runs them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -107,10 +113,19 @@ __device__ inline SegTiles seg_tiles_of(long n, uint32_t seg, long seg_tiles) {
 enum BinMode { kFirst = 0, kBoth = 1, kSplit = 2 };
 
 // One workgroup per (segment, root slice); roots of the chunk at root[k * ld + b], b < n.  bins == null: every sample is in bin 0.
-template <int RS, int MODE>
+// GRP (the grouped calls with more than one group): the weight of root k is the column of its group, weight[g * wstride + b]; the
+// prefetch loads the distinct columns of the slice (gtab, below), one when its roots share a group, and the term picks its own by
+// wave-uniform selects.  Nothing else differs: the sorts, the scans and the order of every sum are those of the ungrouped instance.
+// gtab, one table per call as uint32: the group of every root [R] (a root that does not exist takes a neighbour's, so that it adds
+// no column to a slice), then per root slice of this pass kGrpEntry words -- the number of distinct groups among the slice's roots,
+// their numbers (the weight columns the slice loads), and for each of the slice's roots the place of its group in that list.
+constexpr uint32_t kGrpCols = FDG_WEIGHT_GROUP_MAX, kGrpEntry = 1u + kGrpCols + 16u;
+
+template <int RS, int MODE, bool GRP = false>
 __global__ void __launch_bounds__(256)
 fdg_binned_partials(const double *__restrict__ root, long ld, long n, const int32_t *__restrict__ bins, int32_t bin_base, uint32_t n_bin,
-                    const double *__restrict__ weight, uint32_t R, uint32_t n_slice, long seg_tiles, double *__restrict__ partial, int first) {
+                    const double *__restrict__ weight, uint32_t R, uint32_t n_slice, long seg_tiles, double *__restrict__ partial, int first,
+                    const uint32_t *__restrict__ gtab, long wstride) {
   extern __shared__ double hist[];                        // [moment][bin][RS]
   constexpr uint32_t NH = MODE == kBoth ? 2 : 1;          // histograms in LDS
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -130,12 +145,28 @@ fdg_binned_partials(const double *__restrict__ root, long ld, long n, const int3
 
   // this lane's sample of round r, loaded one round ahead without a branch (indices clamped into the chunk: every load is issued at once
   // and stays in flight while the round before is binned); whether the sample adds anything is decided when it is used
+  constexpr int WC = !GRP ? 1 : RS < (int)kGrpCols ? RS : (int)kGrpCols;   // the weight columns a slice can need
+  uint32_t n_wcol = 1, wcol[WC] = {}, widx[RS] = {};
+  if constexpr (GRP) {
+    const uint32_t *e = gtab + R + (size_t)slice * kGrpEntry;
+    n_wcol = e[0];
+#pragma unroll
+    for (int c = 0; c < WC; ++c) wcol[c] = e[1 + c];
+#pragma unroll
+    for (int kk = 0; kk < RS; ++kk) widx[kk] = e[1 + kGrpCols + kk];
+  }
   int32_t bin_n;
-  double w_n, r_n[RS];
+  double w_n[WC] = {}, r_n[RS];
   auto fetch = [&](long r) {
     const long b = min((t0 + r * (long)kBinWaves + wave) * 64 + lane, n - 1);
     bin_n = bins ? bins[b] : bin_base;
-    w_n = weight ? weight[b] : 1.0;
+    if constexpr (GRP) {
+#pragma unroll
+      for (int c = 0; c < WC; ++c)
+        if ((uint32_t)c < n_wcol) w_n[c] = weight[(size_t)wcol[c] * (size_t)wstride + (size_t)b];
+    } else {
+      w_n[0] = weight ? weight[b] : 1.0;
+    }
 #pragma unroll
     for (int kk = 0; kk < RS; ++kk) r_n[kk] = root[(size_t)min(k0 + kk, R - 1) * (size_t)ld + (size_t)b];
   };
@@ -148,8 +179,13 @@ fdg_binned_partials(const double *__restrict__ root, long ld, long n, const int3
     uint32_t key = in ? ((uint32_t)jb << 6) | lane : kKeyInvalid | lane;
     double v[RS];
 #pragma unroll
-    for (int kk = 0; kk < RS; ++kk) v[kk] = in ? w_n * r_n[kk] : 0.0;
-    fetch(r + 1);                                         // the next round's loads are in flight while this one is binned
+    for (int kk = 0; kk < RS; ++kk) {
+      double wk = w_n[0];
+#pragma unroll
+      for (int c = 1; c < WC; ++c) wk = widx[kk] == (uint32_t)c ? w_n[c] : wk;
+      v[kk] = in ? wk * r_n[kk] : 0.0;
+    }
+    fetch(r + 1);                                        // the next round's loads are in flight while this one is binned
 
     const uint64_t valid = __ballot(key < kKeyInvalid);
     double s[RS] = {}, s2[RS] = {};                       // s2: kBoth only
@@ -244,10 +280,12 @@ struct VegasCols { uint32_t c[FDG_VEGAS_DIM_MAX]; };   // the column of x each v
 // The continuous variables of sample b, in order: x and the cell of each, and the jacobian (a left fold over them), returned.
 // kPolar (fdg_vegas_sample_polar): bit d of `grouped` set = variable d belongs to a polar group; its value goes to the lane's slot of
 // `stash` (LDS, [slot][256 lanes], slots in ascending d) instead of a column of x.
-template <bool kPolar = false>
+// fold(d, f): called with every variable's factor f = G * wd_d of the jacobian, in order (the grouped sampler's per-group folds).
+struct VegasNoFold { __device__ void operator()(uint32_t, double) const {} };
+template <bool kPolar = false, class Fold = VegasNoFold>
 __device__ __forceinline__ double vegas_draw(const double *__restrict__ grid, uint32_t D, uint32_t G, const VegasCols &col, uint64_t seed,
                                              uint64_t off, double *__restrict__ x, long xs, long xc, int32_t *__restrict__ cell, long n, long b,
-                                             uint64_t grouped = 0, double *stash = nullptr) {
+                                             uint64_t grouped = 0, double *stash = nullptr, Fold fold = Fold()) {
   double jb = 0.0;
   uint32_t slot = 0;
   for (uint32_t d = 0; d < D; ++d) {
@@ -260,6 +298,7 @@ __device__ __forceinline__ double vegas_draw(const double *__restrict__ grid, ui
     else x[b * xs + (long)col.c[d] * xc] = v;
     const double f = (double)G * wd;
     jb = d ? jb * f : f;
+    fold(d, f);
     if (cell) cell[(size_t)d * (size_t)n + (size_t)b] = (int32_t)c;
   }
   return jb;
@@ -279,10 +318,11 @@ struct VegasExtCols { uint32_t c[FDG_VEGAS_EXT_MAX]; };   // the columns of x th
 
 // The discrete variable of sample b behind D continuous ones whose jacobian is jb: its uniform is the Philox column D, its value j the
 // number of interior edges of cdf that are <= u (a binary search per lane: the cdf is at most 128 KiB and stays in L2).
-__device__ __forceinline__ void vegas_draw_discrete(const double *__restrict__ cdf, uint32_t n_bin, int32_t bin_base,
-                                                    const double *__restrict__ ext, uint32_t n_ext, const VegasExtCols &ecol, uint64_t seed,
-                                                    uint64_t off, uint32_t D, double *__restrict__ x, long xs, long xc,
-                                                    double *__restrict__ jac, int32_t *__restrict__ bin, long b, double jb) {
+// vegas_pick_discrete: the value, its bin and the table's row written, its probability p returned (what every weight is divided by).
+__device__ __forceinline__ double vegas_pick_discrete(const double *__restrict__ cdf, uint32_t n_bin, int32_t bin_base,
+                                                      const double *__restrict__ ext, uint32_t n_ext, const VegasExtCols &ecol, uint64_t seed,
+                                                      uint64_t off, uint32_t D, double *__restrict__ x, long xs, long xc,
+                                                      int32_t *__restrict__ bin, long b) {
   const double u = fdg_philox_u53(off + (uint64_t)b, D, seed);
   uint32_t lo = 0, hi = n_bin - 1u;                     // j in [lo, hi]: cdf[1 .. lo] <= u < cdf[hi + 1 ..]
   while (lo < hi) {
@@ -290,9 +330,17 @@ __device__ __forceinline__ void vegas_draw_discrete(const double *__restrict__ c
     if (cdf[mid + 1u] <= u) lo = mid + 1u; else hi = mid;
   }
   const double p = cdf[lo + 1u] - cdf[lo];
-  jac[b] = jb / p;
   bin[b] = (int32_t)lo + bin_base;
   for (uint32_t e = 0; e < n_ext; ++e) x[b * xs + (long)ecol.c[e] * xc] = ext[(size_t)lo * n_ext + e];
+  return p;
+}
+
+__device__ __forceinline__ void vegas_draw_discrete(const double *__restrict__ cdf, uint32_t n_bin, int32_t bin_base,
+                                                    const double *__restrict__ ext, uint32_t n_ext, const VegasExtCols &ecol, uint64_t seed,
+                                                    uint64_t off, uint32_t D, double *__restrict__ x, long xs, long xc,
+                                                    double *__restrict__ jac, int32_t *__restrict__ bin, long b, double jb) {
+  const double p = vegas_pick_discrete(cdf, n_bin, bin_base, ext, n_ext, ecol, seed, off, D, x, xs, xc, bin, b);
+  jac[b] = jb / p;
 }
 
 // fdg_vegas_sample with one discrete variable behind the continuous ones (vegas_draw_discrete).
@@ -316,26 +364,48 @@ struct VegasPolar {
   uint32_t col[FDG_VEGAS_POLAR_MAX][3];
 };
 
+// The weight groups of the grouped sampler (a kernel argument, by value): bit d of m[g] set = variable d belongs to group g.
+struct VegasGroupMasks {
+  uint64_t m[FDG_WEIGHT_GROUP_MAX];
+  uint32_t n;
+};
+
 // fdg_vegas_sample / fdg_vegas_sample_discrete (cdf null: no discrete variable) with groups of variables read as (k, phi) or
 // (k, theta, phi): the drawn values of the grouped variables wait in LDS (one slot of 256 lanes per grouped variable, dynamic:
 // 2 KiB each) until the fold over all variables is done, then every group gives its columns and its factors of the jacobian, in
 // the order of the array.  One lane per sample; a lane touches its own LDS words only, so no barrier.
+// GRP (fdg_vegas_sample_device_grouped): one jacobian per weight group, jac[g * jstride + b], each the same fold over the variables
+// and polar groups of its mask only (1.0 * f = f exactly: a group's first factor enters as the plain fold's does).  Every variable is
+// drawn once, and x, bin and cell are written by the very statements of the ungrouped instance.
+template <bool GRP>
 __global__ void __launch_bounds__(256)
 fdg_vegas_sample_polar(const double *__restrict__ grid, uint32_t D, uint32_t G, VegasCols col, VegasPolar pol, const double *__restrict__ cdf,
                        uint32_t n_bin, int32_t bin_base, const double *__restrict__ ext, uint32_t n_ext, VegasExtCols ecol, uint64_t seed,
                        uint64_t off, double *__restrict__ x, long xs, long xc, double *__restrict__ jac, int32_t *__restrict__ bin,
-                       int32_t *__restrict__ cell, long n) {
+                       int32_t *__restrict__ cell, long n, VegasGroupMasks gm, long jstride) {
   extern __shared__ double polar_stash[];
+  constexpr int NG = GRP ? FDG_WEIGHT_GROUP_MAX : 1;
   for (long b = blockIdx.x * 256L + threadIdx.x; b < n; b += (long)gridDim.x * 256L) {
-    double jb = vegas_draw<true>(grid, D, G, col, seed, off, x, xs, xc, cell, n, b, pol.grouped, polar_stash);
+    double jg[NG];
+#pragma unroll
+    for (int g = 0; g < NG; ++g) jg[g] = 1.0;
+    // (f into the groups that own d; the ungrouped instance keeps vegas_draw's own fold)
+    auto fold = [&](uint32_t d, double f) {
+      if constexpr (GRP) {
+#pragma unroll
+        for (int g = 0; g < NG; ++g)
+          if ((uint32_t)g < gm.n && ((gm.m[g] >> d) & 1u)) jg[g] = jg[g] * f;
+      }
+    };
+    double jb = vegas_draw<true>(grid, D, G, col, seed, off, x, xs, xc, cell, n, b, pol.grouped, polar_stash, fold);
     for (uint32_t g = 0; g < pol.n; ++g) {
       const uint32_t var = pol.var[g];
       const double *v = polar_stash + (size_t)__popcll(pol.grouped & ((1ull << var) - 1ull)) * 256u + threadIdx.x;
       double *xb = x + b * xs;
       const double k = v[0];
-      double sp, cp;
+      double sp, cp, st = 0.0;
       if (pol.dim[g] == 3) {
-        double st, ct;
+        double ct;
         fdg_sincos_impl(v[256], st, ct);
         fdg_sincos_impl(v[512], sp, cp);
         const double ks = k * st;
@@ -351,9 +421,29 @@ fdg_vegas_sample_polar(const double *__restrict__ grid, uint32_t D, uint32_t G, 
         xb[(long)pol.col[g][1] * xc] = k * sp;
         jb = jb * k;
       }
+      if constexpr (GRP) {
+        // (a mask holds all of a polar group's variables or none: its first one decides)
+#pragma unroll
+        for (int h = 0; h < NG; ++h)
+          if ((uint32_t)h < gm.n && ((gm.m[h] >> var) & 1u)) {
+            jg[h] = jg[h] * k;
+            if (pol.dim[g] == 3) {
+              jg[h] = jg[h] * k;
+              jg[h] = jg[h] * st;
+            }
+          }
+      }
     }
-    if (!cdf) { jac[b] = jb; continue; }
-    vegas_draw_discrete(cdf, n_bin, bin_base, ext, n_ext, ecol, seed, off, D, x, xs, xc, jac, bin, b, jb);
+    if constexpr (GRP) {
+      // the discrete variable is shared by every group
+      const double p = cdf ? vegas_pick_discrete(cdf, n_bin, bin_base, ext, n_ext, ecol, seed, off, D, x, xs, xc, bin, b) : 1.0;
+#pragma unroll
+      for (int g = 0; g < NG; ++g)
+        if ((uint32_t)g < gm.n) jac[(size_t)g * (size_t)jstride + (size_t)b] = cdf ? jg[g] / p : jg[g];
+    } else {
+      if (!cdf) { jac[b] = jb; continue; }
+      vegas_draw_discrete(cdf, n_bin, bin_base, ext, n_ext, ecol, seed, off, D, x, xs, xc, jac, bin, b, jb);
+    }
   }
 }
 
@@ -370,6 +460,20 @@ __device__ __forceinline__ double vegas_term(const double *__restrict__ root, lo
   return weight ? weight[bb] * sum : sum;
 }
 
+// The training passes' view of the weight groups: the lists kidx / coef are sorted by (group, root) and gstart[g] .. gstart[g + 1]
+// bounds group g's part of them (empty: the group has no root that exists).  vegas_group_term: t_g = w_g s_g of the sample at bb,
+// s_g the left fold over the group's roots, ascending; the caller squares it.
+__device__ __forceinline__ double vegas_group_term(const double *__restrict__ root, long ld, size_t bb, const double *__restrict__ weight,
+                                                   long wstride, const uint32_t *__restrict__ kidx, const double *__restrict__ coef,
+                                                   const uint32_t *__restrict__ gstart, uint32_t g) {
+  const uint32_t i0 = gstart[g], i1 = gstart[g + 1u];
+  return vegas_term(root, ld, bb, weight + (size_t)g * (size_t)wstride, kidx + i0, coef ? coef + i0 : nullptr, i1 - i0);
+}
+
+// The groups that train each variable (a kernel argument, by value): bit g of g[d] set = variable d is in the mask of group g and
+// the group has a root that exists.
+struct VegasVarGroups { uint8_t g[FDG_VEGAS_DIM_MAX]; };
+
 // The training pass over a chunk's roots (root k of sample b at root[k * ld + b], b < n): hist[d][c] += v(b) for every variable d, c = the
 // cell of sample off + b in d, v = (w (c_0 r_0 + c_1 r_1 + ...))^2 over the n_live roots kidx[] that exist (coef null: plain sum).
 // One workgroup per (segment of the chunk's tiles, slice of DS variables), the slice's histograms (DS x G doubles) in LDS.
@@ -384,13 +488,18 @@ __device__ __forceinline__ double vegas_term(const double *__restrict__ root, lo
 // BINNED (the calls with a discrete variable): a sample whose bin lies outside [bin_base, bin_base + n_bin) is selected away like a lane
 // past n.  The wave that forms v leaves -1 for it in the exchange buffer (v is a square: never negative), and the waves that walk the
 // tile give such a lane the invalid key.  With every bin in range no key changes: the sums are those of the unbinned instance.
-template <int BINNED>
+// GRP (the grouped calls): the wave that forms v leaves q_g = (w_g s_g)^2 for each of the NG groups, the exchange buffer
+// [2][kBinWaves][NG][64] (the lanes innermost: a wave reads one group's 64 words at unit stride); a walking wave folds the q_g of its
+// variable's groups (vgm, ascending g) into v before the sort, and skips a variable that no group with a root owns.  The marker
+// survives the fold: the q_g of a lane are all -1 or all squares.
+template <int BINNED, bool GRP = false>
 __global__ void __launch_bounds__(256)
 fdg_vegas_partials(const double *__restrict__ root, long ld, long n, const double *__restrict__ weight, const uint32_t *__restrict__ kidx,
                    const double *__restrict__ coef, uint32_t n_live, uint64_t seed, uint64_t off, uint32_t D, uint32_t G, uint32_t DS,
                    uint32_t n_slice, long seg_tiles, double *__restrict__ partial, int first, const int32_t *__restrict__ bins,
-                   int32_t bin_base, uint32_t n_bin) {
-  extern __shared__ double hist[];                        // [DS][G], then v of the round's tiles [2][kBinWaves][64]
+                   int32_t bin_base, uint32_t n_bin, const uint32_t *__restrict__ gstart, uint32_t NG, long wstride, VegasVarGroups vgm) {
+  extern __shared__ double hist[];                        // [DS][G], then v of the round's tiles [2][kBinWaves][64] (GRP: x NG)
+  const uint32_t vtile = GRP ? NG * 64u : 64u;            // words of one tile in the exchange buffer
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   const uint32_t slice = blockIdx.x % n_slice, seg = blockIdx.x / n_slice;
   const uint32_t d0 = slice * DS, dn = min(DS, D - d0);
@@ -409,15 +518,36 @@ fdg_vegas_partials(const double *__restrict__ root, long ld, long n, const doubl
         const int64_t jb = (int64_t)bins[bb] - (int64_t)bin_base;
         in = in && jb >= 0 && jb < (int64_t)n_bin;
       }
-      const double tw = vegas_term(root, ld, bb, weight, kidx, coef, n_live);
-      vbuf[(r & 1) * (kBinWaves * 64) + wave * 64 + lane] = in ? tw * tw : (BINNED && t < t1 && b < n) ? -1.0 : 0.0;
+      const double out = (BINNED && t < t1 && b < n) ? -1.0 : 0.0;
+      double *vb = vbuf + ((r & 1) * kBinWaves + wave) * vtile + lane;
+      if constexpr (GRP) {
+        for (uint32_t g = 0; g < NG; ++g) {
+          const double tw = vegas_group_term(root, ld, bb, weight, wstride, kidx, coef, gstart, g);
+          vb[g * 64u] = in ? tw * tw : out;
+        }
+      } else {
+        const double tw = vegas_term(root, ld, bb, weight, kidx, coef, n_live);
+        vb[0] = in ? tw * tw : out;
+      }
     }
     __syncthreads();
     for (uint32_t tt = 0; tt < kBinWaves; ++tt) {
       const long t = t0 + r * (long)kBinWaves + tt, b = t * 64 + lane;
       if (t >= t1) break;
-      const double v = vbuf[(r & 1) * (kBinWaves * 64) + tt * 64 + lane];
+      const double *vb = vbuf + ((r & 1) * kBinWaves + tt) * vtile + lane;
+      double v = GRP ? 0.0 : vb[0];
       for (uint32_t dd = wave; dd < dn; dd += kBinWaves) {
+        if constexpr (GRP) {
+          const uint32_t owners = vgm.g[d0 + dd];
+          if (!owners) continue;
+          bool any = false;
+          for (uint32_t g = 0; g < NG; ++g)
+            if ((owners >> g) & 1u) {
+              const double q = vb[g * 64u];
+              v = any ? v + q : q;
+              any = true;
+            }
+        }
         double y;
         const uint32_t c = vegas_cell(off + (uint64_t)b, d0 + dd, seed, G, y);
         uint32_t key = (b < n && !(BINNED && v < 0.0)) ? (c << 6) | lane : kKeyInvalid | lane;
@@ -449,10 +579,13 @@ fdg_vegas_partials(const double *__restrict__ root, long ld, long n, const doubl
 // tile 4 r + w, sorts its lanes by (bin, lane), sums every run of equal bins, and the run heads add into the histogram in the waves'
 // turns, wave 0 first: per bin, tiles are added in tile order.  Chunks and segments chain through partial [segment][bin], summed in
 // segment order by fdg_binned_reduce.  Out-of-range bins and lanes past n are selected away (key invalid); no float atomics.
+// GRP (the grouped calls): v = the left fold, over the groups with a root that exists, ascending, of q_g = (w_g s_g)^2.
+template <bool GRP = false>
 __global__ void __launch_bounds__(256)
 fdg_vegas_bin_partials(const double *__restrict__ root, long ld, long n, const int32_t *__restrict__ bins, int32_t bin_base, uint32_t n_bin,
                        const double *__restrict__ weight, const uint32_t *__restrict__ kidx, const double *__restrict__ coef, uint32_t n_live,
-                       long seg_tiles, double *__restrict__ partial, int first) {
+                       long seg_tiles, double *__restrict__ partial, int first, const uint32_t *__restrict__ gstart, uint32_t NG,
+                       long wstride) {
   extern __shared__ double hist[];                        // [n_bin]
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   const uint32_t seg = blockIdx.x;
@@ -463,11 +596,21 @@ fdg_vegas_bin_partials(const double *__restrict__ root, long ld, long n, const i
   const long t0 = sg.t0, t1 = sg.t1, rounds = sg.rounds;
   // this lane's sample of round r, formed one round ahead (indices clamped into the chunk; used only where the sample is `in`)
   int32_t bin_n;
-  double t_n;
+  double t_n = 0.0;
   auto fetch = [&](long r) {
     const size_t bb = (size_t)min((t0 + r * (long)kBinWaves + wave) * 64 + lane, n - 1);
     bin_n = bins[bb];
-    t_n = vegas_term(root, ld, bb, weight, kidx, coef, n_live);
+    if constexpr (GRP) {                                  // (t_n holds the folded squares themselves)
+      bool any = false;
+      for (uint32_t g = 0; g < NG; ++g) {
+        if (gstart[g] == gstart[g + 1u]) continue;
+        const double tw = vegas_group_term(root, ld, bb, weight, wstride, kidx, coef, gstart, g), q = tw * tw;
+        t_n = any ? t_n + q : q;
+        any = true;
+      }
+    } else {
+      t_n = vegas_term(root, ld, bb, weight, kidx, coef, n_live);
+    }
   };
   fetch(0);
   for (long r = 0; r < rounds; ++r) {
@@ -475,7 +618,7 @@ fdg_vegas_bin_partials(const double *__restrict__ root, long ld, long n, const i
     const int64_t jb = (int64_t)bin_n - (int64_t)bin_base;
     const bool in = t < t1 && b < n && jb >= 0 && jb < (int64_t)n_bin;
     uint32_t key = in ? ((uint32_t)jb << 6) | lane : kKeyInvalid | lane;
-    const double v = in ? t_n * t_n : 0.0;
+    const double v = in ? (GRP ? t_n : t_n * t_n) : 0.0;
     fetch(r + 1);
     const uint64_t valid = __ballot(key < kKeyInvalid);
     double s = 0.0;
@@ -516,12 +659,14 @@ fdg_vegas_bin_partials(const double *__restrict__ root, long ld, long n, const i
 // HSPLIT (four histograms of one (root, frequency) do not fit the LDS: n_bin > 4096): RS = FS = 1 and every slice gets four
 // workgroups, one per histogram.  Chunks and segments chain through partial [segment][histogram][bin][frequency][root].
 // tab: mult[FDG_MATSUBARA_FREQ_MAX] doubles, then tin[R], tout[R] (0-based components of T) as int32.
-template <int KW, bool HSPLIT>
+// GRP (the grouped calls with more than one group): t = w_g(k) root_k, the weight column of the root's group (rgrp[k], the head of
+// gtab above); a wave loads one column per distinct group among its KW roots, so roots of one group load what the ungrouped pass does.
+template <int KW, bool HSPLIT, bool GRP = false>
 __global__ void __launch_bounds__(256)
 fdg_matsubara_partials(const double *__restrict__ root, long ld, long n, const int32_t *__restrict__ bins, int32_t bin_base, uint32_t n_bin,
                        const double *__restrict__ weight, const double *__restrict__ T, long ts, long tc, const double *__restrict__ tab,
                        double beta, uint32_t n_freq, uint32_t R, uint32_t RS, uint32_t FS, uint32_t n_fslice, long seg_tiles,
-                       double *__restrict__ partial, int first) {
+                       double *__restrict__ partial, int first, const uint32_t *__restrict__ rgrp, long wstride) {
   extern __shared__ double hist[];                        // [histogram][bin][FS][RS]
   constexpr uint32_t NH = HSPLIT ? 1 : 4;
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
@@ -551,24 +696,34 @@ fdg_matsubara_partials(const double *__restrict__ root, long ld, long n, const i
   const uint32_t kk0 = RS >= nw ? wave : wave % RS, f0 = RS >= nw ? 0u : wave / RS, fstep = RS >= nw ? 1u : nw / RS;
   const int32_t *tio = (const int32_t *)(tab + FDG_MATSUBARA_FREQ_MAX);
   long off_in[KW], off_out[KW];
-  size_t col[KW];
+  size_t col[KW], wcol[KW] = {};
+  int wfrom[KW] = {};                                      // GRP: the earliest of the wave's roots with root m's group (it loads the column)
 #pragma unroll
   for (int m = 0; m < KW; ++m) {
     const uint32_t k = min(k0 + kk0 + nw * (uint32_t)m, R - 1u);            // clamped: what it loads is used only for kk < kn
     col[m] = (size_t)k * (size_t)ld;
+    if constexpr (GRP) {
+      wcol[m] = (size_t)rgrp[k] * (size_t)wstride;
+      wfrom[m] = m;
+#pragma unroll
+      for (int e = m - 1; e >= 0; --e)
+        if (wcol[e] == wcol[m]) wfrom[m] = e;
+    }
     off_in[m] = (long)tio[k] * tc;
     off_out[m] = (long)tio[R + k] * tc;
   }
   if (kk0 < kn && f0 < fn) {
     // this lane's sample of the next tile, loaded one tile ahead (indices clamped into the chunk; used only where the sample is `in`)
     int32_t bin_n;
-    double w_n, r_n[KW], ti_n[KW], to_n[KW];
+    double w_n[GRP ? KW : 1] = {}, r_n[KW], ti_n[KW], to_n[KW];
     auto fetch = [&](long t) {
       const size_t bb = (size_t)min(t * 64 + (long)lane, n - 1);
       bin_n = bins ? bins[bb] : bin_base;
-      w_n = weight ? weight[bb] : 1.0;
+      if constexpr (!GRP) w_n[0] = weight ? weight[bb] : 1.0;
 #pragma unroll
       for (int m = 0; m < KW; ++m) {
+        if constexpr (GRP)
+          if (wfrom[m] == m) w_n[m] = weight[wcol[m] + bb];
         r_n[m] = root[col[m] + bb];
         ti_n[m] = T[(long)bb * ts + off_in[m]];
         to_n[m] = T[(long)bb * ts + off_out[m]];
@@ -584,7 +739,12 @@ fdg_matsubara_partials(const double *__restrict__ root, long ld, long n, const i
 #pragma unroll
       for (int m = 0; m < KW; ++m) {
         const double tau = to_n[m] - ti_n[m];
-        tv[m] = in ? w_n * r_n[m] : 0.0;                  // selected, never multiplied by 0
+        double wk = w_n[0];
+        if constexpr (GRP) {
+#pragma unroll
+          for (int e = 1; e <= m; ++e) wk = wfrom[m] == e ? w_n[e] : wk;
+        }
+        tv[m] = in ? wk * r_n[m] : 0.0;                   // selected, never multiplied by 0
         xv[m] = in ? tau / beta : 0.0;
       }
       fetch(min(t + 1, sg.t1 - 1));
@@ -668,6 +828,7 @@ struct BinnedCall {
   void *stream = nullptr;
   const VegasRun *vg = nullptr;      // the VEGAS calls: the training pass runs too
   const MatsubaraRun *mz = nullptr;  // the projection calls: the projection pass runs too; d_acc and d_acc2 may then both be null
+  const fdg_weight_groups *wg = nullptr;   // the grouped calls: d_weight holds one column per group
 };
 
 constexpr size_t page_up(size_t bytes) { return (bytes + 4095) & ~(size_t)4095; }
@@ -740,13 +901,14 @@ struct VegasPlan {
   size_t lds = 0, slab_alloc = 0, list_bytes = 0, bin_slab_alloc = 0;
 };
 
-VegasPlan vegas_plan(const BinnedPlan &p, const VegasRun &v, uint32_t R, uint32_t n_bin) {
+// n_group: the exchange buffer holds one value per group, on top of the histograms' budget (1: today's plan).
+VegasPlan vegas_plan(const BinnedPlan &p, const VegasRun &v, uint32_t R, uint32_t n_bin, uint32_t n_group) {
   VegasPlan q;
   const uint32_t fit = (uint32_t)std::max<size_t>(1, kBinLdsBudget / ((size_t)v.G * 8u));
   q.n_slice = (v.D + fit - 1) / fit;
   q.ds = (v.D + q.n_slice - 1) / q.n_slice;
   q.n_slice = (v.D + q.ds - 1) / q.ds;
-  q.lds = ((size_t)q.ds * v.G + 2u * kBinWaves * 64u) * 8u;
+  q.lds = ((size_t)q.ds * v.G + 2u * kBinWaves * 64u * n_group) * 8u;
   const SegCut cut = seg_cut(p.Bc, (size_t)v.D * v.G * 8u, q.n_slice);
   q.n_seg = cut.n_seg;
   q.slab_alloc = page_up(cut.slab_alloc);
@@ -795,31 +957,38 @@ MatsubaraPlan matsubara_plan(const BinnedPlan &p, uint32_t R, uint32_t n_bin, ui
 }
 
 using MatsubaraKernel = void (*)(const double *, long, long, const int32_t *, int32_t, uint32_t, const double *, const double *, long, long,
-                                 const double *, double, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, long, double *, int);
+                                 const double *, double, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, long, double *, int,
+                                 const uint32_t *, long);
 
-MatsubaraKernel matsubara_kernel(const MatsubaraPlan &q) {
-  if (q.hsplit) return fdg_matsubara_partials<1, true>;
-  return q.kw == 4 ? fdg_matsubara_partials<4, false> : q.kw == 2 ? fdg_matsubara_partials<2, false> : fdg_matsubara_partials<1, false>;
+template <bool GRP>
+MatsubaraKernel matsubara_kernel_of(const MatsubaraPlan &q) {
+  if (q.hsplit) return fdg_matsubara_partials<1, true, GRP>;
+  return q.kw == 4   ? fdg_matsubara_partials<4, false, GRP>
+         : q.kw == 2 ? fdg_matsubara_partials<2, false, GRP>
+                     : fdg_matsubara_partials<1, false, GRP>;
 }
+
+MatsubaraKernel matsubara_kernel(const MatsubaraPlan &q, bool grp) { return grp ? matsubara_kernel_of<true>(q) : matsubara_kernel_of<false>(q); }
 
 // The instance of the binned pass a plan asks for.
 using PartialsKernel = void (*)(const double *, long, long, const int32_t *, int32_t, uint32_t, const double *, uint32_t, uint32_t, long,
-                                double *, int);
+                                double *, int, const uint32_t *, long);
 
-template <int MODE>
+template <int MODE, bool GRP = false>
 PartialsKernel partials_kernel_rs(uint32_t rs) {
   switch (rs) {
-    case 1: return fdg_binned_partials<1, MODE>;
-    case 2: return fdg_binned_partials<2, MODE>;
-    case 4: return fdg_binned_partials<4, MODE>;
-    case 8: return fdg_binned_partials<8, MODE>;
-    default: return fdg_binned_partials<16, MODE>;
+    case 1: return fdg_binned_partials<1, MODE, GRP>;
+    case 2: return fdg_binned_partials<2, MODE, GRP>;
+    case 4: return fdg_binned_partials<4, MODE, GRP>;
+    case 8: return fdg_binned_partials<8, MODE, GRP>;
+    default: return fdg_binned_partials<16, MODE, GRP>;
   }
 }
 
-PartialsKernel partials_kernel(const BinnedPlan &p) {
-  if (p.mode == kBoth) return partials_kernel_rs<kBoth>(p.rs);
-  if (p.mode == kSplit) return fdg_binned_partials<1, kSplit>;
+// grp: the instance that reads one weight column per group (the grouped calls keep both moments: kBoth or kSplit)
+PartialsKernel partials_kernel(const BinnedPlan &p, bool grp) {
+  if (p.mode == kBoth) return grp ? partials_kernel_rs<kBoth, true>(p.rs) : partials_kernel_rs<kBoth>(p.rs);
+  if (p.mode == kSplit) return grp ? fdg_binned_partials<1, kSplit, true> : fdg_binned_partials<1, kSplit>;
   return partials_kernel_rs<kFirst>(p.rs);
 }
 
@@ -829,17 +998,26 @@ void raise_lds_limits() {
   static std::once_flag once;
   std::call_once(once, [] {
     const int hist = (int)(FDG_BIN_MAX * 8), train = (int)(kBinLdsBudget + 2u * kBinWaves * 64u * 8u);
+    const int train_grp = (int)(kBinLdsBudget + 2u * kBinWaves * 64u * 8u * FDG_WEIGHT_GROUP_MAX);
     std::vector<std::pair<const void *, int>> limits = {{(const void *)fdg_binned_partials<1, kSplit>, hist},
-                                                        {(const void *)fdg_vegas_bin_partials, hist},
+                                                        {(const void *)fdg_binned_partials<1, kSplit, true>, hist},
+                                                        {(const void *)fdg_vegas_bin_partials<false>, hist},
+                                                        {(const void *)fdg_vegas_bin_partials<true>, hist},
                                                         {(const void *)fdg_vegas_partials<0>, train},
                                                         {(const void *)fdg_vegas_partials<1>, train},
-                                                        {(const void *)fdg_matsubara_partials<1, true>, hist},
-                                                        {(const void *)fdg_matsubara_partials<1, false>, hist},
-                                                        {(const void *)fdg_matsubara_partials<2, false>, hist},
-                                                        {(const void *)fdg_matsubara_partials<4, false>, hist}};
+                                                        {(const void *)fdg_vegas_partials<0, true>, train_grp},
+                                                        {(const void *)fdg_vegas_partials<1, true>, train_grp}};
+    MatsubaraPlan mq;
+    for (int i = 0; i < 4; ++i) {                          // hsplit, then kw = 1, 2, 4
+      mq.hsplit = i == 0;
+      mq.kw = i ? 1u << (i - 1) : 1u;
+      limits.push_back({(const void *)matsubara_kernel(mq, false), hist});
+      limits.push_back({(const void *)matsubara_kernel(mq, true), hist});
+    }
     for (uint32_t rs = 1; rs <= 16; rs <<= 1) {
       limits.push_back({(const void *)partials_kernel_rs<kFirst>(rs), hist});
       limits.push_back({(const void *)partials_kernel_rs<kBoth>(rs), hist});
+      limits.push_back({(const void *)partials_kernel_rs<kBoth, true>(rs), hist});
     }
     for (const auto &l : limits) (void)hipFuncSetAttribute(l.first, hipFuncAttributeMaxDynamicSharedMemorySize, l.second);
     (void)hipGetLastError();
@@ -924,6 +1102,27 @@ int check_matsubara(const fdg_graph *g, const BinnedCall &c, const fdg_matsubara
   return v ? check_vegas_map(v->D, v->G) : FDG_OK;
 }
 
+// ... and the grouped calls': the weight groups first, then the cases of the call the arguments amount to (the projection calls'
+// with a descriptor, else the VEGAS calls' with a training block, else the moments calls').
+int check_grouped(const fdg_graph *g, const BinnedCall &c, const fdg_matsubara *m, const double *mc_T) {
+  const fdg_weight_groups *w = c.wg;
+  if (!g) { set_error("null handle"); return FDG_E_INVALID; }
+  if (!w || !w->root_group || !w->var_mask) { set_error("null weight groups, root_group or var_mask"); return FDG_E_INVALID; }
+  if (!c.d_weight) { set_error("the grouped calls need d_weight"); return FDG_E_INVALID; }
+  if (w->n_group == 0) { set_error("n_group == 0"); return FDG_E_INVALID; }
+  if (w->n_group > FDG_WEIGHT_GROUP_MAX) { set_error("n_group > FDG_WEIGHT_GROUP_MAX"); return FDG_E_UNSUPPORTED; }
+  for (uint32_t k = 0; k < g->prog.R; ++k)
+    if (g->prog.root_slot[k] != FDG_NO_ROOT && w->root_group[k] >= w->n_group) { set_error("root_group names a group >= n_group"); return FDG_E_INVALID; }
+  if (c.vg && c.vg->D < 64)
+    for (uint32_t gi = 0; gi < w->n_group; ++gi)
+      if (w->var_mask[gi] >> c.vg->D) { set_error("var_mask names a variable >= n_dim"); return FDG_E_INVALID; }
+  if (w->n_group > 1 && w->weight_group_stride < c.B) { set_error("weight_group_stride < n_sample"); return FDG_E_INVALID; }
+  if (m) return check_matsubara(g, c, m, mc_T);
+  if (!c.vg) return check_call(g, c, true);
+  if (!c.d_bin && c.vg->d_hist_bin) { set_error("d_hist_bin needs d_bin"); return FDG_E_INVALID; }
+  return check_vegas(g, c);
+}
+
 // The chunk loop shared by the entry points (caller holds g->mu, stream bound): eval(c0, n, roots, ld) writes the roots of samples
 // c0 .. c0 + n - 1 column-major into roots (root k of sample c0 + b at roots[k * ld + b]).  c.d_acc2 != null: the second moment too.
 // c.vg != null (the VEGAS calls): after a chunk's moments pass the training pass runs over the same roots, its partials behind the
@@ -935,21 +1134,75 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
   const hipStream_t st = (hipStream_t)c.stream;
   const BinnedPlan p = binned_plan(g, c.B, R, n_bin, c.d_acc2 != nullptr);
   const size_t root_bytes = page_up((size_t)p.Bc * R * sizeof(double)), slab_bytes = page_up(p.slab_alloc);
+  // The grouped calls take the grouped instances only where the groups do not reduce to "one weight, every variable": the weight
+  // columns with more than one group, the training passes also with one group whose mask leaves variables out.  Otherwise the call
+  // is the ungrouped one: the same kernels on the same plan.  Which instances run depends on n_group and the masks' coverage, the
+  // order of the sums on n_group alone.
+  const fdg_weight_groups *wg = c.wg;
+  const bool grp_w = wg && wg->n_group > 1;
+  const bool grp_t = wg && vg && (grp_w || (~wg->var_mask[0] & (vg->D == 64 ? ~0ull : (1ull << vg->D) - 1ull)) != 0);
+  const uint32_t NG = wg ? wg->n_group : 1u;
+  const long wstride = wg ? (long)wg->weight_group_stride : 0;
   VegasPlan q;
-  if (vg) q = vegas_plan(p, *vg, R, n_bin);
+  if (vg) q = vegas_plan(p, *vg, R, n_bin, grp_t ? NG : 1u);
   const MatsubaraRun *mz = c.mz;
   MatsubaraPlan mp;
   if (mz) mp = matsubara_plan(p, R, n_bin, mz->m->n_freq);
   // the projection's slab and table lie behind everything the call would reserve without it
   const size_t base_bytes = vg ? root_bytes + slab_bytes + q.slab_alloc + q.list_bytes + q.bin_slab_alloc
                                : mz ? root_bytes + slab_bytes : root_bytes + p.slab_alloc;
-  int rc = ensure_root_scratch(g, mz ? base_bytes + mp.slab_alloc + mp.tab_bytes : base_bytes);
+  // ... and the groups' table (gtab of fdg_binned_partials, then gstart[n_group + 1], then a byte per training histogram word:
+  // 0 = its variable is trained by no group) behind that
+  const size_t proj_bytes = mz ? base_bytes + mp.slab_alloc + mp.tab_bytes : base_bytes;
+  const size_t gtab_words = (size_t)R + (size_t)p.n_slice * kGrpEntry + kGrpCols + 1u;
+  const size_t grp_bytes = (grp_w || grp_t) ? page_up(gtab_words * 4u + (vg ? (size_t)vg->D * vg->G : 0)) : 0;
+  int rc = ensure_root_scratch(g, proj_bytes + grp_bytes);
   if (rc) return rc;
   double *roots = (double *)g->d_ws2, *partial = (double *)((char *)g->d_ws2 + root_bytes);
   const uint8_t *live = nullptr;
   rc = root_live_mask(g, &live);
   if (rc) return rc;
   raise_lds_limits();
+  uint32_t *d_gtab = nullptr, *d_gstart = nullptr;
+  const uint8_t *d_hlive = nullptr;
+  VegasVarGroups vgm = {};
+  std::vector<uint32_t> gstart(kGrpCols + 1u, 0u);         // bounds of every group's roots in the lists sorted by (group, root)
+  if (grp_w || grp_t) {
+    d_gtab = (uint32_t *)((char *)g->d_ws2 + proj_bytes);
+    d_gstart = d_gtab + R + (size_t)p.n_slice * kGrpEntry;
+    std::vector<uint32_t> hg(grp_bytes / 4u, 0u);
+    auto exists = [&](uint32_t k) { return g->prog.root_slot[k] != FDG_NO_ROOT; };
+    uint32_t near = 0;
+    for (uint32_t k = R; k-- > 0;)
+      if (exists(k)) near = wg->root_group[k];
+    for (uint32_t k = 0; k < R; ++k) hg[k] = near = exists(k) ? wg->root_group[k] : near;
+    for (uint32_t s = 0; s < p.n_slice; ++s) {
+      uint32_t *e = hg.data() + R + (size_t)s * kGrpEntry, &n_col = e[0];
+      for (uint32_t kk = 0; kk < p.rs && s * p.rs + kk < R; ++kk) {
+        const uint32_t gk = hg[s * p.rs + kk];
+        uint32_t at = 0;
+        while (at < n_col && e[1 + at] != gk) ++at;
+        if (at == n_col) e[1 + n_col++] = gk;
+        e[1 + kGrpCols + kk] = at;
+      }
+    }
+    for (uint32_t k = 0; k < R; ++k)
+      if (exists(k)) ++gstart[wg->root_group[k] + 1u];
+    for (uint32_t gi = 0; gi < NG; ++gi) gstart[gi + 1u] += gstart[gi];
+    std::copy(gstart.begin(), gstart.end(), hg.begin() + (d_gstart - d_gtab));
+    if (grp_t) {
+      uint8_t *hl = (uint8_t *)(hg.data() + gtab_words);
+      bool dead = false;
+      for (uint32_t d = 0; d < vg->D; ++d) {
+        for (uint32_t gi = 0; gi < NG; ++gi)
+          if (((wg->var_mask[gi] >> d) & 1u) && gstart[gi + 1u] > gstart[gi]) vgm.g[d] |= (uint8_t)(1u << gi);
+        dead = dead || !vgm.g[d];
+        std::fill(hl + (size_t)d * vg->G, hl + (size_t)(d + 1u) * vg->G, vgm.g[d] ? 1 : 0);
+      }
+      if (dead) d_hlive = (const uint8_t *)(d_gtab + gtab_words);
+    }
+    HIP_TRY(hipMemcpyAsync(d_gtab, hg.data(), grp_bytes, hipMemcpyHostToDevice, st));
+  }
   double *vpartial = nullptr, *d_coef = nullptr, *bpartial = nullptr;
   uint32_t *d_kidx = nullptr, n_live = 0;
   if (vg) {
@@ -960,8 +1213,10 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
     bpartial = (double *)((char *)d_coef + q.list_bytes);
     std::vector<double> hc;
     std::vector<uint32_t> hk;
-    for (uint32_t k = 0; k < R; ++k)
-      if (g->prog.root_slot[k] != FDG_NO_ROOT) { hk.push_back(k); hc.push_back(vg->coef ? vg->coef[k] : 1.0); }
+    // (the grouped training passes: sorted by (group, root), group gi's part at gstart[gi] .. gstart[gi + 1])
+    for (uint32_t gi = 0; gi < (grp_t ? NG : 1u); ++gi)
+      for (uint32_t k = 0; k < R; ++k)
+        if (g->prog.root_slot[k] != FDG_NO_ROOT && (!grp_t || wg->root_group[k] == gi)) { hk.push_back(k); hc.push_back(vg->coef ? vg->coef[k] : 1.0); }
     n_live = (uint32_t)hk.size();
     if (n_live) {
       HIP_TRY(hipMemcpyAsync(d_coef, hc.data(), n_live * sizeof(double), hipMemcpyHostToDevice, st));
@@ -984,8 +1239,8 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
     }
     HIP_TRY(hipMemcpyAsync(d_mtab, hm.data(), hm.size() * sizeof(double), hipMemcpyHostToDevice, st));
   }
-  const MatsubaraKernel mpass = matsubara_kernel(mp);
-  const PartialsKernel pass = partials_kernel(p);
+  const MatsubaraKernel mpass = matsubara_kernel(mp, grp_w);
+  const PartialsKernel pass = partials_kernel(p, grp_w);
   const uint32_t n_grp = p.mode == kSplit ? 2 * p.n_slice : p.n_slice;
   for (long c0 = 0; c0 < (long)c.B; c0 += p.Bc) {
     const long n = std::min<long>(p.Bc, (long)c.B - c0), ntile = (n + 63) / 64;
@@ -996,25 +1251,28 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
     if (rc) return rc;
     if (c.d_acc) {
       hipLaunchKernelGGL(pass, dim3(p.n_seg * n_grp), dim3(256), p.lds, st, roots, (long)p.Bc, n, bins, c.bin_base, n_bin, w, R, p.n_slice,
-                         (ntile + p.n_seg - 1) / p.n_seg, partial, first);
+                         (ntile + p.n_seg - 1) / p.n_seg, partial, first, d_gtab, wstride);
       HIP_TRY(hipGetLastError());
     }
     if (mz) {
       hipLaunchKernelGGL(mpass, dim3(mp.n_seg * mp.n_grp), dim3(64 * mp.nw), mp.lds, st, roots, (long)p.Bc, n, bins, c.bin_base, n_bin, w,
                          mz->d_T + c0 * mz->ts, (long)mz->ts, (long)mz->tc, d_mtab, mz->m->beta, mz->m->n_freq, R, mp.rs, mp.fs, mp.n_fslice,
-                         (ntile + mp.n_seg - 1) / mp.n_seg, mpartial, first);
+                         (ntile + mp.n_seg - 1) / mp.n_seg, mpartial, first, d_gtab, wstride);
       HIP_TRY(hipGetLastError());
     }
     if (vg) {
       const double *cf = vg->coef ? d_coef : nullptr;
       // (the calls without a discrete variable carry no bin vector: null, base 0, one bin)
-      hipLaunchKernelGGL(vg->binned ? fdg_vegas_partials<1> : fdg_vegas_partials<0>, dim3(q.n_seg * q.n_slice), dim3(256), q.lds, st, roots,
-                         (long)p.Bc, n, w, d_kidx, cf, n_live, vg->seed, vg->offset + (uint64_t)c0, vg->D, vg->G, q.ds, q.n_slice,
-                         (ntile + q.n_seg - 1) / q.n_seg, vpartial, first, bins, c.bin_base, n_bin);
+      const auto tpass = grp_t ? (vg->binned ? fdg_vegas_partials<1, true> : fdg_vegas_partials<0, true>)
+                               : (vg->binned ? fdg_vegas_partials<1> : fdg_vegas_partials<0>);
+      hipLaunchKernelGGL(tpass, dim3(q.n_seg * q.n_slice), dim3(256), q.lds, st, roots, (long)p.Bc, n, w, d_kidx, cf, n_live, vg->seed,
+                         vg->offset + (uint64_t)c0, vg->D, vg->G, q.ds, q.n_slice, (ntile + q.n_seg - 1) / q.n_seg, vpartial, first, bins,
+                         c.bin_base, n_bin, d_gstart, NG, wstride, vgm);
       HIP_TRY(hipGetLastError());
       if (vg->d_hist_bin) {
-        hipLaunchKernelGGL(fdg_vegas_bin_partials, dim3(q.bin_seg), dim3(256), (size_t)n_bin * 8u, st, roots, (long)p.Bc, n, bins, c.bin_base,
-                           n_bin, w, d_kidx, cf, n_live, (ntile + q.bin_seg - 1) / q.bin_seg, bpartial, first);
+        hipLaunchKernelGGL(grp_t ? fdg_vegas_bin_partials<true> : fdg_vegas_bin_partials<false>, dim3(q.bin_seg), dim3(256),
+                           (size_t)n_bin * 8u, st, roots, (long)p.Bc, n, bins, c.bin_base, n_bin, w, d_kidx, cf, n_live,
+                           (ntile + q.bin_seg - 1) / q.bin_seg, bpartial, first, d_gstart, NG, wstride);
         HIP_TRY(hipGetLastError());
       }
     }
@@ -1035,7 +1293,8 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
     }
   }
   // hist[d][c] and hist_bin[j] += the segments' partials, in segment order
-  if (!rc && vg) rc = reduce_partials(vpartial, q.n_seg, (long)vg->D * vg->G, 1u, 64u, vg->d_hist, nullptr, nullptr, st);
+  // (a variable that no group trains is not added to: the byte table stands in for the roots' mask, R = the histogram's size)
+  if (!rc && vg) rc = reduce_partials(vpartial, q.n_seg, (long)vg->D * vg->G, d_hlive ? vg->D * vg->G : 1u, 64u, vg->d_hist, nullptr, d_hlive, st);
   if (!rc && vg && vg->d_hist_bin) rc = reduce_partials(bpartial, q.bin_seg, (long)n_bin, 1u, 64u, vg->d_hist_bin, nullptr, nullptr, st);
   return rc;
 }
@@ -1207,6 +1466,32 @@ int fdg_mc_accumulate_device_matsubara(fdg_graph *g, const double *d_K, int64_t 
   return rc ? rc : accumulate_mc(g, d_K, ks, kc, d_T, ts, tc, kF, beta, lambda, c);
 }
 
+int fdg_accumulate_device_grouped(fdg_graph *g, const double *d_leaf, int64_t ss, int64_t ls, int64_t lts, const int32_t *d_bin,
+                                  int32_t bin_base, uint32_t n_bin, const double *d_weight, const double *coef, uint64_t seed,
+                                  uint64_t sample_offset, uint32_t n_dim, uint32_t n_grid, double *d_acc, double *d_acc2, double *d_hist,
+                                  double *d_hist_bin, const fdg_matsubara *mz, const fdg_weight_groups *wg, int64_t B, void *stream) {
+  const bool train = n_dim != 0 || d_hist;
+  const VegasRun vg{coef, seed, sample_offset, n_dim, n_grid, d_hist, d_bin != nullptr, d_hist_bin};
+  const MatsubaraRun mr{mz, mz ? mz->d_T : nullptr, mz ? mz->t_sample_stride : 0, mz ? mz->t_comp_stride : 0};
+  const BinnedCall c{d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, stream, train ? &vg : nullptr, mz ? &mr : nullptr, wg};
+  const int rc = check_grouped(g, c, mz, nullptr);
+  return rc ? rc : accumulate_leaf(g, d_leaf, ss, ls, lts, c);
+}
+
+int fdg_mc_accumulate_device_grouped(fdg_graph *g, const double *d_K, int64_t ks, int64_t kc, const double *d_T, int64_t ts, int64_t tc,
+                                     double kF, double beta, double lambda, const int32_t *d_bin, int32_t bin_base, uint32_t n_bin,
+                                     const double *d_weight, const double *coef, uint64_t seed, uint64_t sample_offset, uint32_t n_dim,
+                                     uint32_t n_grid, double *d_acc, double *d_acc2, double *d_hist, double *d_hist_bin,
+                                     const fdg_matsubara *mz, const fdg_weight_groups *wg, int64_t B, void *stream) {
+  const bool train = n_dim != 0 || d_hist;
+  const VegasRun vg{coef, seed, sample_offset, n_dim, n_grid, d_hist, d_bin != nullptr, d_hist_bin};
+  const bool own_T = mz && mz->d_T;
+  const MatsubaraRun mr{mz, own_T ? mz->d_T : d_T, own_T ? mz->t_sample_stride : ts, own_T ? mz->t_comp_stride : tc};
+  const BinnedCall c{d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, stream, train ? &vg : nullptr, mz ? &mr : nullptr, wg};
+  const int rc = check_grouped(g, c, mz, d_T);
+  return rc ? rc : accumulate_mc(g, d_K, ks, kc, d_T, ts, tc, kF, beta, lambda, c);
+}
+
 int fdg_vegas_sample_device_discrete(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, const double *d_cdf,
                                      uint32_t n_bin, int32_t bin_base, const double *d_ext, uint32_t n_ext, const uint32_t *ext_col,
                                      uint64_t seed, uint64_t sample_offset, double *d_x, int64_t x_sample_stride, int64_t x_col_stride,
@@ -1235,12 +1520,13 @@ int fdg_vegas_sample_device_discrete(const double *d_grid, uint32_t n_dim, uint3
   return FDG_OK;
 }
 
-int fdg_vegas_sample_device_polar(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, const double *d_cdf,
-                                  uint32_t n_bin, int32_t bin_base, const double *d_ext, uint32_t n_ext, const uint32_t *ext_col,
-                                  const fdg_vegas_polar *polar, uint32_t n_polar, uint64_t seed, uint64_t sample_offset, double *d_x,
-                                  int64_t x_sample_stride, int64_t x_col_stride, double *d_jac, int32_t *d_bin, int32_t *d_cell, int64_t B,
-                                  void *stream) {
-  const int rc = check_sampler(B, !d_grid || !d_x || !d_jac || (d_cdf && !d_bin), n_dim, n_grid);
+// fdg_vegas_sample_device_polar (grouped false; the last three arguments are not read) and fdg_vegas_sample_device_grouped.
+static int vegas_sample_polar(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, const double *d_cdf, uint32_t n_bin,
+                              int32_t bin_base, const double *d_ext, uint32_t n_ext, const uint32_t *ext_col, const fdg_vegas_polar *polar,
+                              uint32_t n_polar, uint64_t seed, uint64_t sample_offset, double *d_x, int64_t x_sample_stride,
+                              int64_t x_col_stride, double *d_jac, int32_t *d_bin, int32_t *d_cell, int64_t B, void *stream, bool grouped,
+                              const uint64_t *var_mask, uint32_t n_group, int64_t jac_group_stride) {
+  const int rc = check_sampler(B, !d_grid || !d_x || !d_jac || (d_cdf && !d_bin) || (grouped && !var_mask), n_dim, n_grid);
   if (rc) return rc;
   if (!d_cdf) n_bin = 1, n_ext = 0;                       // no discrete variable: its arguments are ignored
   if (n_bin == 0) { set_error("n_bin == 0"); return FDG_E_INVALID; }
@@ -1277,20 +1563,53 @@ int fdg_vegas_sample_device_polar(const double *d_grid, uint32_t n_dim, uint32_t
   named.insert(named.end(), ecols.c, ecols.c + n_ext);
   std::sort(named.begin(), named.end());
   if (std::adjacent_find(named.begin(), named.end()) != named.end()) { set_error("a column of x is named twice"); return FDG_E_INVALID; }
+  VegasGroupMasks gm = {};
+  if (grouped) {
+    if (n_group == 0) { set_error("n_group == 0"); return FDG_E_INVALID; }
+    if (n_group > FDG_WEIGHT_GROUP_MAX) { set_error("n_group > FDG_WEIGHT_GROUP_MAX"); return FDG_E_UNSUPPORTED; }
+    gm.n = n_group;
+    for (uint32_t g = 0; g < n_group; ++g) {
+      gm.m[g] = var_mask[g];
+      if (n_dim < 64 && (var_mask[g] >> n_dim)) { set_error("var_mask names a variable >= n_dim"); return FDG_E_INVALID; }
+      for (uint32_t pg = 0; pg < n_polar; ++pg) {
+        const uint64_t bits = ((1ull << pol.dim[pg]) - 1ull) << pol.var[pg], has = var_mask[g] & bits;
+        if (has && has != bits) { set_error("var_mask holds some but not all variables of a polar group"); return FDG_E_INVALID; }
+      }
+    }
+    if (n_group > 1 && jac_group_stride < B) { set_error("jac_group_stride < n_sample"); return FDG_E_INVALID; }
+  }
   if (B == 0) return FDG_OK;
   const size_t lds = (size_t)__builtin_popcountll(pol.grouped) * 256u * sizeof(double);
   static std::once_flag once;
   std::call_once(once, [] {
-    (void)hipFuncSetAttribute((const void *)fdg_vegas_sample_polar, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              FDG_VEGAS_DIM_MAX * 256 * (int)sizeof(double));
+    for (const void *k : {(const void *)fdg_vegas_sample_polar<false>, (const void *)fdg_vegas_sample_polar<true>})
+      (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, FDG_VEGAS_DIM_MAX * 256 * (int)sizeof(double));
     (void)hipGetLastError();
   });
   const long grid = std::min<long>(((long)B + 255) / 256, 256L * 16);
-  hipLaunchKernelGGL(fdg_vegas_sample_polar, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, d_grid, n_dim, n_grid, cols, pol, d_cdf,
-                     n_bin, bin_base, d_ext, n_ext, ecols, seed, sample_offset, d_x, (long)x_sample_stride, (long)x_col_stride, d_jac, d_bin,
-                     d_cell, (long)B);
+  hipLaunchKernelGGL(grouped ? fdg_vegas_sample_polar<true> : fdg_vegas_sample_polar<false>, dim3((unsigned)grid), dim3(256), lds,
+                     (hipStream_t)stream, d_grid, n_dim, n_grid, cols, pol, d_cdf, n_bin, bin_base, d_ext, n_ext, ecols, seed, sample_offset,
+                     d_x, (long)x_sample_stride, (long)x_col_stride, d_jac, d_bin, d_cell, (long)B, gm, (long)jac_group_stride);
   HIP_TRY(hipGetLastError());
   return FDG_OK;
+}
+
+int fdg_vegas_sample_device_polar(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, const double *d_cdf,
+                                  uint32_t n_bin, int32_t bin_base, const double *d_ext, uint32_t n_ext, const uint32_t *ext_col,
+                                  const fdg_vegas_polar *polar, uint32_t n_polar, uint64_t seed, uint64_t sample_offset, double *d_x,
+                                  int64_t x_sample_stride, int64_t x_col_stride, double *d_jac, int32_t *d_bin, int32_t *d_cell, int64_t B,
+                                  void *stream) {
+  return vegas_sample_polar(d_grid, n_dim, n_grid, col, d_cdf, n_bin, bin_base, d_ext, n_ext, ext_col, polar, n_polar, seed, sample_offset, d_x,
+                            x_sample_stride, x_col_stride, d_jac, d_bin, d_cell, B, stream, false, nullptr, 0, 0);
+}
+
+int fdg_vegas_sample_device_grouped(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, const double *d_cdf,
+                                    uint32_t n_bin, int32_t bin_base, const double *d_ext, uint32_t n_ext, const uint32_t *ext_col,
+                                    const fdg_vegas_polar *polar, uint32_t n_polar, const uint64_t *var_mask, uint32_t n_group,
+                                    int64_t jac_group_stride, uint64_t seed, uint64_t sample_offset, double *d_x, int64_t x_sample_stride,
+                                    int64_t x_col_stride, double *d_jac, int32_t *d_bin, int32_t *d_cell, int64_t B, void *stream) {
+  return vegas_sample_polar(d_grid, n_dim, n_grid, col, d_cdf, n_bin, bin_base, d_ext, n_ext, ext_col, polar, n_polar, seed, sample_offset, d_x,
+                            x_sample_stride, x_col_stride, d_jac, d_bin, d_cell, B, stream, true, var_mask, n_group, jac_group_stride);
 }
 
 void fdg_sincos(double x, double *s, double *c) { fdg_sincos_impl(x, *s, *c); }

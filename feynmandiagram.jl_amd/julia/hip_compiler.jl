@@ -434,6 +434,98 @@ function mc_accumulate_device_matsubara!(f::GraphFunc, d_sums::Ptr{Float64}, d_K
     end
     return nothing
 end
+# ---- weight groups (include/fdg.h; no counterpart in the reference: the caller's side of test/hubbard.jl:81-85) ---- #
+# MCIntegration's dof: root i is weighted by the jacobian of its own variables only.  dof[i][p] = how many leading elements of variable
+# pool p root i integrates, pools[p] = the VEGAS variables (1-based) of each element of the pool; roots with equal sets share a group.
+# Returns (root_group::Vector{UInt32} 0-based, var_mask::Vector{UInt64}).
+function weight_groups_from_dof(dof::AbstractVector, pools::AbstractVector)
+    masks = UInt64[]
+    root_group = UInt32[]
+    for row in dof
+        length(row) == length(pools) || error("dof holds one count per pool")
+        m = UInt64(0)
+        for (n, pool) in zip(row, pools)
+            0 <= n <= length(pool) || error("dof asks for more elements than the pool holds")
+            for element in pool[1:n], d in element
+                m |= UInt64(1) << (d - 1)
+            end
+        end
+        g = findfirst(==(m), masks)
+        if g === nothing
+            push!(masks, m)
+            g = length(masks)
+        end
+        push!(root_group, g - 1)
+    end
+    return root_group, masks
+end
+struct _FdgWeightGroups
+    n_group::UInt32
+    root_group::Ptr{UInt32}
+    var_mask::Ptr{UInt64}
+    weight_group_stride::Int64
+end
+# vegas_sample_device_polar! with one jacobian per weight group: d_jac is B x n_group column-major by default (jac_group_stride = B)
+function vegas_sample_device_grouped!(d_x::Ptr{Float64}, d_jac::Ptr{Float64}, d_grid::Ptr{Float64}, n_dim::Integer, n_grid::Integer, B::Integer,
+    polar::AbstractVector, var_mask::Vector{UInt64}; jac_group_stride::Integer=B, col::Union{Nothing,AbstractVector{<:Integer}}=nothing,
+    d_cdf::Ptr{Float64}=Ptr{Float64}(C_NULL), n_bin::Integer=1, d_bin::Ptr{Int32}=Ptr{Int32}(C_NULL), d_ext::Ptr{Float64}=Ptr{Float64}(C_NULL),
+    ext_col::AbstractVector{<:Integer}=Int[], bin_base::Integer=1, seed::Integer=0, sample_offset::Integer=0, x_strides=(1, B),
+    d_cell::Ptr{Int32}=Ptr{Int32}(C_NULL), stream::Ptr{Cvoid}=C_NULL)
+    c = col === nothing ? nothing : UInt32.(col .- 1)
+    e = UInt32.(ext_col .- 1)
+    p = zeros(UInt32, 5 * max(length(polar), 1))
+    for (g, (var, cols)) in enumerate(polar)
+        length(cols) in (2, 3) || error("a polar group has 2 or 3 columns")
+        p[5g-4] = var - 1
+        p[5g-3] = length(cols)
+        p[5g-2:5g-3+length(cols)] .= UInt32.(cols .- 1)
+    end
+    _fdg_check(ccall((:fdg_vegas_sample_device_grouped, _libfdg), Cint,
+        (Ptr{Float64}, UInt32, UInt32, Ptr{UInt32}, Ptr{Float64}, UInt32, Int32, Ptr{Float64}, UInt32, Ptr{UInt32}, Ptr{UInt32}, UInt32,
+         Ptr{UInt64}, UInt32, Int64, UInt64, UInt64, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Int64, Ptr{Cvoid}),
+        d_grid, n_dim, n_grid, c === nothing ? C_NULL : c, d_cdf, n_bin, bin_base, d_ext, length(e), isempty(e) ? C_NULL : e,
+        isempty(polar) ? C_NULL : p, length(polar), var_mask, length(var_mask), jac_group_stride, seed, sample_offset, d_x, x_strides[1],
+        x_strides[2], d_jac, d_bin, d_cell, B, stream))
+    return nothing
+end
+# The accumulate step with weight groups: d_weight is B x n_group column-major by default, dof / pools as weight_groups_from_dof takes
+# them.  Everything else as accumulate_device_matsubara! without a projection (these wrappers pass no descriptor): d_bin = C_NULL: one
+# bin; n_dim = 0 and d_hist = C_NULL: no training.
+function accumulate_device_grouped!(f::GraphFunc, d_acc::Ptr{Float64}, d_acc2::Ptr{Float64}, d_leaf::Ptr{Float64}, d_weight::Ptr{Float64},
+    B::Integer; dof::AbstractVector, pools::AbstractVector, weight_group_stride::Integer=B, d_bin::Ptr{Int32}=Ptr{Int32}(C_NULL),
+    n_bin::Integer=1, bin_base::Integer=1, coef::Union{Nothing,Vector{Float64}}=nothing, seed::Integer=0, sample_offset::Integer=0,
+    n_dim::Integer=0, n_grid::Integer=0, d_hist::Ptr{Float64}=Ptr{Float64}(C_NULL), d_hist_bin::Ptr{Float64}=Ptr{Float64}(C_NULL),
+    leaf_strides=(1, B), tile_stride::Integer=0, stream::Ptr{Cvoid}=C_NULL)
+    root_group, var_mask = weight_groups_from_dof(dof, pools)
+    GC.@preserve root_group var_mask begin
+        wg = _FdgWeightGroups(length(var_mask), pointer(root_group), pointer(var_mask), weight_group_stride)
+        _fdg_check(ccall((:fdg_accumulate_device_grouped, _libfdg), Cint,
+            (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Int64, Ptr{Int32}, Int32, UInt32, Ptr{Float64}, Ptr{Float64}, UInt64, UInt64, UInt32,
+             UInt32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}, Ref{_FdgWeightGroups}, Int64, Ptr{Cvoid}),
+            f.handle, d_leaf, leaf_strides[1], leaf_strides[2], tile_stride, d_bin, bin_base, n_bin, d_weight,
+            coef === nothing ? C_NULL : coef, seed, sample_offset, n_dim, n_grid, d_acc, d_acc2, d_hist, d_hist_bin, C_NULL, wg, B, stream))
+    end
+    return nothing
+end
+# the same for the fused step (fdg_mc_accumulate_device_grouped)
+function mc_accumulate_device_grouped!(f::GraphFunc, d_acc::Ptr{Float64}, d_acc2::Ptr{Float64}, d_K::Ptr{Float64}, d_T::Ptr{Float64},
+    d_weight::Ptr{Float64}, B::Integer; dof::AbstractVector, pools::AbstractVector, kF::Float64, beta::Float64, lambda::Float64,
+    weight_group_stride::Integer=B, d_bin::Ptr{Int32}=Ptr{Int32}(C_NULL), n_bin::Integer=1, bin_base::Integer=1,
+    coef::Union{Nothing,Vector{Float64}}=nothing, seed::Integer=0, sample_offset::Integer=0, n_dim::Integer=0, n_grid::Integer=0,
+    d_hist::Ptr{Float64}=Ptr{Float64}(C_NULL), d_hist_bin::Ptr{Float64}=Ptr{Float64}(C_NULL), k_strides=(1, B), t_strides=(1, B),
+    stream::Ptr{Cvoid}=C_NULL)
+    root_group, var_mask = weight_groups_from_dof(dof, pools)
+    GC.@preserve root_group var_mask begin
+        wg = _FdgWeightGroups(length(var_mask), pointer(root_group), pointer(var_mask), weight_group_stride)
+        _fdg_check(ccall((:fdg_mc_accumulate_device_grouped, _libfdg), Cint,
+            (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Int64, Float64, Float64, Float64, Ptr{Int32}, Int32, UInt32,
+             Ptr{Float64}, Ptr{Float64}, UInt64, UInt64, UInt32, UInt32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+             Ptr{Cvoid}, Ref{_FdgWeightGroups}, Int64, Ptr{Cvoid}),
+            f.handle, d_K, k_strides[1], k_strides[2], d_T, t_strides[1], t_strides[2], kF, beta, lambda, d_bin, bin_base, n_bin, d_weight,
+            coef === nothing ? C_NULL : coef, seed, sample_offset, n_dim, n_grid, d_acc, d_acc2, d_hist, d_hist_bin, C_NULL, wg, B, stream))
+    end
+    return nothing
+end
 # device memory for a batch, backed by physical chunks of `chunk_bytes` (0: one allocation): fdg_batch_alloc / fdg_batch_free
 function batch_alloc(bytes::Integer; chunk_bytes::Integer=0)
     p = Ref{Ptr{Cvoid}}(C_NULL)
@@ -482,7 +574,7 @@ function accumulate_device!(f::GraphFunc, d_acc::Ptr{Float64}, d_leaf::Ptr{Float
         f.handle, d_leaf, leaf_strides[1], leaf_strides[2], d_weight, d_acc, B, stream))
 end
 
-export compile_hip, GraphFunc, eval_device!, accumulate_device!, eval_device_tiled!, accumulate_device_tiled!, accumulate_device_binned!, mc_accumulate_device_binned!, accumulate_device_moments!, mc_accumulate_device_moments!, vegas_sample_device!, accumulate_device_vegas!, mc_accumulate_device_vegas!, vegas_refine!, vegas_sample_device_discrete!, accumulate_device_vegas_binned!, mc_accumulate_device_vegas_binned!, vegas_refine_discrete!, vegas_sample_device_polar!, fdg_sincos, fdg_matsubara_phase, accumulate_device_matsubara!, mc_accumulate_device_matsubara!, batch_alloc, batch_free, tile_major!, from_tile_major!
+export compile_hip, GraphFunc, eval_device!, accumulate_device!, eval_device_tiled!, accumulate_device_tiled!, accumulate_device_binned!, mc_accumulate_device_binned!, accumulate_device_moments!, mc_accumulate_device_moments!, vegas_sample_device!, accumulate_device_vegas!, mc_accumulate_device_vegas!, vegas_refine!, vegas_sample_device_discrete!, accumulate_device_vegas_binned!, mc_accumulate_device_vegas_binned!, vegas_refine_discrete!, vegas_sample_device_polar!, fdg_sincos, fdg_matsubara_phase, accumulate_device_matsubara!, mc_accumulate_device_matsubara!, weight_groups_from_dof, vegas_sample_device_grouped!, accumulate_device_grouped!, mc_accumulate_device_grouped!, batch_alloc, batch_free, tile_major!, from_tile_major!
 
 # ---- multi-GPU: one Julia process per GPU, ONE reduction of the accumulated observable ------------ #
 # (include/fdg.h, "multi-GPU").  Rank 0 calls `comm_unique_id()` and ships the 128 bytes to the other

@@ -18,6 +18,11 @@ example/benchmark.jl:46 -- and the sampler writes the Cartesian components; the 
 Matsubara frequencies (``MatsubaraProjection``, the keyword ``matsubara``; fdg_mc_accumulate_device_matsubara): every root is multiplied
 by the phase of its own pair of external times before it is summed -- ``phase(varT, ver4.Tpair[...])`` of the reference's
 test/ver4.jl:193 -- so the estimate is complex, one number per frequency and root; the map is trained on the unprojected roots as before.
+
+Weight groups (``WeightGroups``, ``groups_from_dof``, the keyword ``groups``; fdg_vegas_sample_device_grouped,
+fdg_mc_accumulate_device_grouped): roots that integrate different numbers of variables in one run -- MCIntegration's ``dof``, as in the
+reference's test/hubbard.jl:81-85 and example/strong_coupling_expansion/naive.jl:195 -- each weighted by the jacobian of its own
+variables, each variable's map trained by the roots that use it.
 """
 from __future__ import annotations
 
@@ -168,8 +173,40 @@ class MatsubaraProjection:
     root_tau_out: Tuple[int, ...]
 
 
+@dataclass(frozen=True)
+class WeightGroups:
+    """Roots with their own integration variables: root ``k`` belongs to group ``root_group[k]``, and group ``g`` integrates the VEGAS
+    variables ``var_sets[g]`` -- its roots are weighted by the jacobian of those variables only, and only they train those variables'
+    maps.  A polar group of variables belongs to a set whole or not at all."""
+    root_group: Tuple[int, ...]
+    var_sets: Tuple[Tuple[int, ...], ...]
+
+
+def groups_from_dof(dof, pools) -> WeightGroups:
+    """:class:`WeightGroups` in MCIntegration's call shape.  ``pools[p]`` lists, in order, the VEGAS variables of each element of
+    variable pool ``p`` (one ``K`` of a polar group: its three variables; one time: one variable); ``dof[i][p]`` says how many leading
+    elements of pool ``p`` root ``i`` integrates.  Roots with equal sets of variables share a group; the groups are numbered in the
+    order their first root appears."""
+    sets, root_group = [], []
+    for i, row in enumerate(dof):
+        if len(row) != len(pools):
+            raise ValueError(f"dof[{i}] must hold one count per pool")
+        mine = []
+        for n, pool in zip(row, pools):
+            if not 0 <= int(n) <= len(pool):
+                raise ValueError(f"dof[{i}] asks for {n} elements of a pool of {len(pool)}")
+            mine += [int(d) for element in pool[:int(n)] for d in element]
+        key = tuple(sorted(set(mine)))
+        if key not in sets:
+            sets.append(key)
+        root_group.append(sets.index(key))
+    if not 1 <= len(sets) <= capi.FDG_WEIGHT_GROUP_MAX:
+        raise ValueError(f"need 1 .. {capi.FDG_WEIGHT_GROUP_MAX} distinct sets of variables")
+    return WeightGroups(tuple(root_group), tuple(sets))
+
+
 def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter, n_sample, n_grid, alpha, floor, seed, n_discard, fixed, coef,
-               device, vmap, specialize_fused, n_total, shard_start, reduce, polar=None, matsubara=None):
+               device, vmap, specialize_fused, n_total, shard_start, reduce, polar=None, matsubara=None, wgroups=None):
     """The driver behind :func:`vegas_integrate` (``dmap`` None: results ``[R]``) and :func:`vegas_integrate_binned` (``[n_bin, R]``);
     with ``matsubara`` the results are complex and carry a frequency axis in front of the roots."""
     import torch
@@ -194,6 +231,14 @@ def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter,
     if polar and any(c is None for d, c in enumerate(col) if not any(v <= d < v + len(cs) for v, cs in groups)):
         raise ValueError("only the variables of a polar group go without a column")
     D, G, NB = vmap.n_dim, vmap.n_grid, 1 if dmap is None else dmap.n_bin
+    if wgroups is not None:
+        if len(wgroups.root_group) != R or not all(0 <= int(v) < len(wgroups.var_sets) for v in wgroups.root_group):
+            raise ValueError("groups.root_group names one group of groups.var_sets per root")
+        if not all(0 <= int(d) < D for vs in wgroups.var_sets for d in vs):
+            raise ValueError("groups.var_sets names variables of the map")
+        for var, cs in groups or ():
+            if any(0 < len(set(vs) & set(range(var, var + len(cs)))) < len(cs) for vs in wgroups.var_sets):
+                raise ValueError("a polar group belongs to a weight group whole or not at all")
     B = int(n_sample)
     N = B if n_total is None else int(n_total)
     if B < 1 or N < 2 or n_iter < 1 or not (0 <= n_discard < n_iter):
@@ -218,7 +263,9 @@ def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter,
     with torch.cuda.device(device):
         st = torch.cuda.current_stream(device).cuda_stream
         x = torch.from_numpy(fx).to(device)[:, None].repeat(1, B).contiguous()          # [n_col, B]: sample stride 1
-        jac = torch.empty(B, dtype=torch.float64, device=device)
+        jac = torch.empty(B if wgroups is None else (len(wgroups.var_sets), B), dtype=torch.float64, device=device)
+        if wgroups is not None:
+            wdesc, _wkeep = capi.make_weight_groups(wgroups.root_group, wgroups.var_sets, B)
         d_T = x.data_ptr() + 8 * n_col_k * B
         if dmap is not None:
             bins = torch.empty(B, dtype=torch.int32, device=device)
@@ -227,7 +274,12 @@ def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter,
             off = it * N + int(shard_start)
             m = torch.zeros((2, NB, R), dtype=torch.float64, device=device)
             hist = torch.zeros((D, G), dtype=torch.float64, device=device)
-            if groups:
+            if wgroups is not None:
+                capi.vegas_sample_device_grouped(vmap.d_grid.data_ptr(), D, G, col, 0 if dmap is None else dmap.d_cdf.data_ptr(), NB, 0,
+                                                 0 if dmap is None else d_ext, None if dmap is None else dmap.ext_col, groups,
+                                                 wgroups.var_sets, B, seed, off, x.data_ptr(), 1, B, jac.data_ptr(),
+                                                 0 if dmap is None else bins.data_ptr(), 0, B, st)
+            elif groups:
                 capi.vegas_sample_device_polar(vmap.d_grid.data_ptr(), D, G, col, 0 if dmap is None else dmap.d_cdf.data_ptr(), NB, 0,
                                                0 if dmap is None else d_ext, None if dmap is None else dmap.ext_col, groups, seed, off,
                                                x.data_ptr(), 1, B, jac.data_ptr(), 0 if dmap is None else bins.data_ptr(), 0, B, st)
@@ -236,7 +288,20 @@ def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter,
             else:
                 capi.vegas_sample_device_discrete(vmap.d_grid.data_ptr(), D, G, col, dmap.d_cdf.data_ptr(), NB, 0, d_ext, dmap.ext_col, seed,
                                                   off, x.data_ptr(), 1, B, jac.data_ptr(), bins.data_ptr(), 0, B, st)
-            if matsubara is not None:
+            if wgroups is not None:
+                # one call for every combination: the projection and the discrete variable are optional in it
+                desc, hist_bin = None, None if dmap is None else torch.zeros(NB, dtype=torch.float64, device=device)
+                if matsubara is not None:
+                    m = torch.zeros((4, NB, NF, R), dtype=torch.float64, device=device)
+                    desc, _keep = capi.make_matsubara(matsubara.freq, matsubara.fermionic, matsubara.root_tau_in, matsubara.root_tau_out,
+                                                      beta, n_tau, *[m[i].data_ptr() for i in range(4)])
+                handle.mc_accumulate_device_grouped(x.data_ptr(), 1, B, d_T, 1, B, kF, beta, lam, 0 if dmap is None else bins.data_ptr(), 0,
+                                                    NB, jac.data_ptr(), wdesc, desc, coef, seed, off, D, G,
+                                                    0 if matsubara is not None else m[0].data_ptr(),
+                                                    0 if matsubara is not None else m[1].data_ptr(), hist.data_ptr(),
+                                                    0 if dmap is None else hist_bin.data_ptr(), B, st)
+                sums = [m, hist] if dmap is None else [m, hist, hist_bin]
+            elif matsubara is not None:
                 # (re, im, re^2, im^2) of the projected roots; the training histograms as the calls below leave them
                 m = torch.zeros((4, NB, NF, R), dtype=torch.float64, device=device)
                 hist_bin = None if dmap is None else torch.zeros(NB, dtype=torch.float64, device=device)
@@ -287,7 +352,7 @@ def vegas_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: 
                     n_sample: int = 100_000, n_grid: int = 64, alpha: float = 0.5, seed: int = 0, n_discard: int = 0, fixed=None,
                     coef=None, device="cuda", vmap: Optional[VegasMap] = None, specialize_fused: bool = True, n_total: Optional[int] = None,
                     shard_start: int = 0, reduce: Optional[Callable] = None, polar: Optional[Sequence[PolarVar]] = None,
-                    matsubara: Optional[MatsubaraProjection] = None) -> VegasResult:
+                    matsubara: Optional[MatsubaraProjection] = None, groups: Optional[WeightGroups] = None) -> VegasResult:
     """Integrates the roots of a graph over the box ``[lo, hi]`` of ``len(col)`` of its Monte-Carlo variables.
 
     ``func_or_handle``: a ``GraphFunc`` or ``capi.GraphHandle``; ``tables`` the ``fdg_leaf_tables`` struct of ``capi.make_leaf_tables``
@@ -309,9 +374,14 @@ def vegas_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: 
     ``matsubara``: a :class:`MatsubaraProjection`.  Every root is multiplied by the phase of its own pair of times at every frequency
     before it is summed: ``mean`` is complex ``[n_freq, R]``, ``stderr`` and ``chi2_dof`` carry the figures of the real parts in their
     real parts and those of the imaginary parts in their imaginary parts (``mc_estimate`` and ``combine`` on each), and ``reduce`` is
-    applied to the ``[4, 1, n_freq, R]`` sums.  The map is trained on the unprojected roots: its histograms are those of a run without."""
+    applied to the ``[4, 1, n_freq, R]`` sums.  The map is trained on the unprojected roots: its histograms are those of a run without.
+
+    ``groups``: a :class:`WeightGroups` (:func:`groups_from_dof`).  Every root is weighted by the jacobian of its own group's variables
+    -- the integral over the others is not taken, as with MCIntegration's ``dof`` -- and a variable's histogram sums, over the groups
+    that own it, ``(w_g sum_k c_k r_k)**2`` of the group's roots; a variable of no group is not refined.  The sums, ``reduce`` and
+    ``combine`` are as without.  None: the calls made and their bits are what they are without this keyword."""
     return _integrate(func_or_handle, tables, lo, hi, col, None, kF, beta, lam, n_iter, n_sample, n_grid, alpha, 0.0, seed, n_discard, fixed, coef,
-                      device, vmap, specialize_fused, n_total, shard_start, reduce, polar, matsubara)
+                      device, vmap, specialize_fused, n_total, shard_start, reduce, polar, matsubara, groups)
 
 
 def uniform_cdf(n_bin: int) -> np.ndarray:
@@ -388,13 +458,15 @@ def vegas_integrate_binned(func_or_handle, tables, lo, hi, col, dmap: DiscreteMa
                            n_discard: int = 0, fixed=None, coef=None, device="cuda", vmap: Optional[VegasMap] = None,
                            specialize_fused: bool = True, n_total: Optional[int] = None, shard_start: int = 0,
                            reduce: Optional[Callable] = None, polar: Optional[Sequence[PolarVar]] = None,
-                           matsubara: Optional[MatsubaraProjection] = None) -> VegasBinnedResult:
+                           matsubara: Optional[MatsubaraProjection] = None,
+                           groups: Optional[WeightGroups] = None) -> VegasBinnedResult:
     """:func:`vegas_integrate` with a discrete variable: every sample draws a value ``j`` of ``dmap`` next to its continuous variables,
     the columns ``dmap.ext_col`` take row ``j`` of ``dmap.ext`` (external momenta), and the estimate is per value: arrays ``[n_bin, R]``,
     bin ``j`` the integral over the continuous variables at configuration ``j`` (the weight carries ``1 / p_j``, and ``mc_estimate``
     takes the whole batch as ``N``).  Per iteration: sample, accumulate (binned moments and both training histograms in one pass),
     ``mc_estimate``, refine the map with ``alpha`` and the probabilities with ``alpha`` and ``floor``.  ``combine`` is per (bin, root).
     Sharding as in :func:`vegas_integrate`; ``reduce`` is applied to the moments ``[2, n_bin, R]`` and to both histograms, so every rank
-    refines the same maps.  ``polar`` and ``matsubara`` as in :func:`vegas_integrate` (complex ``[n_bin, n_freq, R]``)."""
+    refines the same maps.  ``polar``, ``matsubara`` and ``groups`` as in :func:`vegas_integrate` (complex ``[n_bin, n_freq, R]``; the
+    discrete variable is shared by every group)."""
     return _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter, n_sample, n_grid, alpha, floor, seed, n_discard, fixed,
-                      coef, device, vmap, specialize_fused, n_total, shard_start, reduce, polar, matsubara)
+                      coef, device, vmap, specialize_fused, n_total, shard_start, reduce, polar, matsubara, groups)

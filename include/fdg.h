@@ -815,6 +815,70 @@ int fdg_mc_accumulate_device_matsubara(fdg_graph *g, const double *d_K, int64_t 
                                        double *d_acc, double *d_acc2, double *d_hist, double *d_hist_bin, const fdg_matsubara *mz,
                                        int64_t n_sample, void *stream);
 
+/* ---- Weight groups: per-root integration variables (MCIntegration's `dof`) --------------------------------------------------------------
+ * A diagrammatic series is integrated with all its orders at once, and every order has its own number of loop momenta and times:
+ * `dof = [[diagpara[o].totalTauNum - 1,] for o in 1:length(orders)]` (test/hubbard.jl:81-85), `dof = [[2, 2], [3, 3], ..., [9, 9]]`
+ * (example/strong_coupling_expansion/naive.jl:195), the same argument with one entry in test/ver4.jl:233.  Integrand i is then
+ * weighted by the jacobian of its own variables only, and every variable's map is trained by the integrands that use it.
+ * MCIntegration is not part of the reference checkout: no counterpart in the reference; the caller's side of those lines.
+ *
+ * Roots are assigned to groups and every group owns a set of the VEGAS variables: root k belongs to group root_group[k], bit d of
+ * var_mask[g] says that variable d belongs to group g, and the weight of group g for sample b is d_weight[g * weight_group_stride + b]
+ * (torch [n_group, n_sample]: stride n_sample).  root_group and var_mask are HOST arrays.
+ *
+ * fdg_vegas_sample_device_grouped: the arguments of fdg_vegas_sample_device_polar plus (var_mask, n_group, jac_group_stride).  x,
+ * d_bin, d_cell and the table's row come out bit for bit as that call writes them; every variable is drawn once.  For sample b and
+ * group g, every step one rounded fp64 operation, in this order,
+ *   1. j_g = the left fold, over ascending d with bit d in var_mask[g], of G * wd_d; an empty mask gives 1.0;
+ *   2. the polar groups, in the order of the array, whose variables belong to the mask: dim 3: j_g = j_g * k; * k; * st;  dim 2: j_g * k;
+ *   3. d_cdf != NULL: j_g / p (the discrete variable is shared by every group);
+ *   j_g -> d_jac[g * jac_group_stride + b].
+ * A group whose mask holds all n_dim variables reproduces the bits of fdg_vegas_sample_device_polar's d_jac.
+ * FDG_E_INVALID: var_mask NULL, n_group == 0, a mask bit at or above n_dim, a mask that holds some but not all variables of a polar
+ * group, jac_group_stride < n_sample with n_group > 1, and the cases of fdg_vegas_sample_device_polar; FDG_E_UNSUPPORTED:
+ * n_group > FDG_WEIGHT_GROUP_MAX and that call's limits.  All before any device work.
+ *
+ * fdg_[mc_]accumulate_device_grouped: the arguments of the _matsubara calls, where mz may now be NULL (no projection), plus wg.
+ * With g(k) = root_group[k] and w_g = d_weight[g * weight_group_stride + b]:
+ *   moments, binned moments and the projection: t = w_g(k) * root_k(b) wherever those calls form w_b * root_k(b); nothing else changes.
+ *   continuous training: for every group with a root that exists, s_g = the left fold over its existing roots, ascending k, of
+ *       c_k * r_k (the factor only with coef != NULL);  q_g = (w_g * s_g)^2, the product and the square each rounded;
+ *       d_hist[d][c] += v_d, v_d the left fold, over ascending g with bit d in var_mask[g] and a root that exists, of q_g.  A variable
+ *       of no such group is not added to at all.
+ *   discrete training: d_hist_bin[j] += the left fold of q_g over all groups that have a root that exists, ascending g.
+ * With n_group == 1, root_group all zero and a full mask every output carries the bits of the corresponding ungrouped call for the
+ * same arguments (_moments, _vegas, _vegas_binned, _matsubara): the same kernels on the same plan.  With several groups: no float
+ * atomics; samples past n_sample or out of range are selected away, never multiplied by zero; the order of every sum is a function of
+ * (n_sample, n_bin, n_freq, n_root, n_dim, n_grid, n_group, FDG_ROOT_SCRATCH_MB) only, not of the masks or of root_group
+ * (csrc/fdg_binned.hip).
+ * FDG_E_INVALID: wg or one of its arrays NULL, d_weight NULL, n_group == 0, root_group[k] >= n_group for a root that exists, a mask
+ * bit at or above n_dim when training is asked for, weight_group_stride < n_sample with n_group > 1, and the cases of the _matsubara
+ * calls except the NULL descriptor (without one: those of the VEGAS calls with a training block, else of the moments calls);
+ * FDG_E_UNSUPPORTED: n_group > FDG_WEIGHT_GROUP_MAX and those calls' limits.  All before any device work. */
+#define FDG_WEIGHT_GROUP_MAX 8
+typedef struct fdg_weight_groups {
+  uint32_t n_group;             /* 1 .. FDG_WEIGHT_GROUP_MAX */
+  const uint32_t *root_group;   /* HOST [n_root]: the group of root k (ignored for FDG_NO_ROOT roots) */
+  const uint64_t *var_mask;     /* HOST [n_group]: bit d set = VEGAS variable d belongs to the group (D <= 64 = FDG_VEGAS_DIM_MAX) */
+  int64_t weight_group_stride;  /* weight of group g, sample b: d_weight[g * weight_group_stride + b] */
+} fdg_weight_groups;
+int fdg_vegas_sample_device_grouped(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, const double *d_cdf,
+                                    uint32_t n_bin, int32_t bin_base, const double *d_ext, uint32_t n_ext, const uint32_t *ext_col,
+                                    const fdg_vegas_polar *polar, uint32_t n_polar, const uint64_t *var_mask, uint32_t n_group,
+                                    int64_t jac_group_stride, uint64_t seed, uint64_t sample_offset, double *d_x, int64_t x_sample_stride,
+                                    int64_t x_col_stride, double *d_jac, int32_t *d_bin, int32_t *d_cell, int64_t n_sample, void *stream);
+int fdg_accumulate_device_grouped(fdg_graph *g, const double *d_leaf, int64_t leaf_sample_stride, int64_t leaf_leaf_stride,
+                                  int64_t leaf_tile_stride, const int32_t *d_bin, int32_t bin_base, uint32_t n_bin, const double *d_weight,
+                                  const double *coef, uint64_t seed, uint64_t sample_offset, uint32_t n_dim, uint32_t n_grid, double *d_acc,
+                                  double *d_acc2, double *d_hist, double *d_hist_bin, const fdg_matsubara *mz, const fdg_weight_groups *wg,
+                                  int64_t n_sample, void *stream);
+int fdg_mc_accumulate_device_grouped(fdg_graph *g, const double *d_K, int64_t k_sample_stride, int64_t k_comp_stride, const double *d_T,
+                                     int64_t t_sample_stride, int64_t t_comp_stride, double kF, double beta, double lambda,
+                                     const int32_t *d_bin, int32_t bin_base, uint32_t n_bin, const double *d_weight, const double *coef,
+                                     uint64_t seed, uint64_t sample_offset, uint32_t n_dim, uint32_t n_grid, double *d_acc, double *d_acc2,
+                                     double *d_hist, double *d_hist_bin, const fdg_matsubara *mz, const fdg_weight_groups *wg,
+                                     int64_t n_sample, void *stream);
+
 /* Device workspace control: the interpreter keeps per-sample overflow slots in
  * an HBM panel owned by the handle; it is sized on first use for the number of
  * resident waves.  This releases it (and any loaded module). */
