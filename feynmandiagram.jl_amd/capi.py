@@ -49,6 +49,7 @@ EXPORTS = [
     "fdg_vegas_sample_device_polar", "fdg_sincos",
     "fdg_matsubara_phase", "fdg_accumulate_device_matsubara", "fdg_mc_accumulate_device_matsubara",
     "fdg_vegas_sample_device_grouped", "fdg_accumulate_device_grouped", "fdg_mc_accumulate_device_grouped",
+    "fdg_accumulate_device_observables", "fdg_mc_accumulate_device_observables",
 ]
 FDG_BIN_MAX = 16384     # fdg_accumulate_device_binned: largest n_bin
 FDG_VEGAS_DIM_MAX, FDG_VEGAS_GRID_MAX = 64, 1024     # the VEGAS map: most variables, most cells per variable
@@ -56,6 +57,7 @@ FDG_VEGAS_EXT_MAX = 16  # the discrete variable's table: most columns per value
 FDG_VEGAS_POLAR_MAX = 21  # fdg_vegas_sample_device_polar: most groups of polar variables
 FDG_MATSUBARA_FREQ_MAX = 64  # fdg_[mc_]accumulate_device_matsubara: most frequencies per call
 FDG_WEIGHT_GROUP_MAX = 8  # fdg_weight_groups: most groups of roots with their own integration variables
+FDG_OBS_MAX = 16  # fdg_observables: most linear combinations of the roots per call
 COMM_ID_BYTES = 128
 
 
@@ -114,6 +116,11 @@ class Matsubara(C.Structure):
 class WeightGroups(C.Structure):
     """fdg_weight_groups (include/fdg.h)"""
     _fields_ = [("n_group", C.c_uint32), ("root_group", C.c_void_p), ("var_mask", C.c_void_p), ("weight_group_stride", C.c_int64)]
+
+
+class Observables(C.Structure):
+    """fdg_observables (include/fdg.h)"""
+    _fields_ = [("n_obs", C.c_uint32), ("coef", C.c_void_p), ("d_obs", C.c_void_p), ("d_cov", C.c_void_p)]
 
 
 class OptParams(C.Structure):
@@ -255,6 +262,11 @@ def lib():
                                                 dp, dp, C.c_void_p, C.c_void_p, i64, vp]
     L.fdg_mc_accumulate_device_grouped.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, C.c_int32,
                                                    u32, dp, C.c_void_p, u64, u64, u32, u32, dp, dp, dp, dp, C.c_void_p, C.c_void_p, i64, vp]
+    L.fdg_accumulate_device_observables.argtypes = [vp, dp, i64, i64, i64, dp, C.c_int32, u32, dp, C.c_void_p, u64, u64, u32, u32, dp, dp,
+                                                    dp, dp, C.c_void_p, C.c_void_p, C.c_void_p, i64, vp]
+    L.fdg_mc_accumulate_device_observables.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, C.c_int32,
+                                                       u32, dp, C.c_void_p, u64, u64, u32, u32, dp, dp, dp, dp, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, i64, vp]
     L.fdg_powi.argtypes = [C.c_double, C.c_int32]
     L.fdg_powi.restype = C.c_double
     _lib = L
@@ -554,6 +566,31 @@ class GraphHandle:
                                                      d_hist_bin or None, None if desc is None else C.addressof(desc),
                                                      None if groups is None else C.addressof(groups), B, stream))
 
+    # observables: obs = make_observables(...)[0]; groups None: one weight column (or none with d_weight 0); d_acc and d_acc2 both 0:
+    # no per-root moments; the rest as the grouped calls take it (fdg.h)
+    def accumulate_device_observables(self, d_leaf: int, ss: int, ls: int, lts: int, d_bin: int, bin_base: int, n_bin: int, d_weight: int,
+                                      obs, groups=None, desc=None, coef=None, seed: int = 0, sample_offset: int = 0, n_dim: int = 0,
+                                      n_grid: int = 0, d_acc: int = 0, d_acc2: int = 0, d_hist: int = 0, d_hist_bin: int = 0, B: int = 0,
+                                      stream: int = 0):
+        c = self._coef(coef)
+        check(lib().fdg_accumulate_device_observables(self._h, d_leaf or None, ss, ls, lts, d_bin or None, bin_base, n_bin, d_weight or None,
+                                                      None if c is None else c.ctypes.data, seed, sample_offset, n_dim, n_grid,
+                                                      d_acc or None, d_acc2 or None, d_hist or None, d_hist_bin or None,
+                                                      None if desc is None else C.addressof(desc),
+                                                      None if groups is None else C.addressof(groups),
+                                                      None if obs is None else C.addressof(obs), B, stream))
+
+    def mc_accumulate_device_observables(self, d_K, ks, kc, d_T, ts, tc, kF, beta, lam, d_bin, bin_base, n_bin, d_weight, obs, groups=None,
+                                         desc=None, coef=None, seed=0, sample_offset=0, n_dim=0, n_grid=0, d_acc=0, d_acc2=0, d_hist=0,
+                                         d_hist_bin=0, B=0, stream=0):
+        c = self._coef(coef)
+        check(lib().fdg_mc_accumulate_device_observables(self._h, d_K or None, ks, kc, d_T or None, ts, tc, kF, beta, lam, d_bin or None,
+                                                         bin_base, n_bin, d_weight or None, None if c is None else c.ctypes.data, seed,
+                                                         sample_offset, n_dim, n_grid, d_acc or None, d_acc2 or None, d_hist or None,
+                                                         d_hist_bin or None, None if desc is None else C.addressof(desc),
+                                                         None if groups is None else C.addressof(groups),
+                                                         None if obs is None else C.addressof(obs), B, stream))
+
     def _coef(self, coef):
         if coef is None:
             return None
@@ -697,6 +734,66 @@ def make_weight_groups(root_group, var_sets, stride: int = 0):
     if rg.ndim != 1 or vm.shape[0] < 1:
         raise ValueError("root_group is a vector and there is at least one group")
     return WeightGroups(vm.shape[0], rg.ctypes.data, vm.ctypes.data, int(stride)), (rg, vm)
+
+
+def make_observables(coef, d_obs: int, d_cov: int):
+    """``(fdg_observables struct, keepalive)``: ``coef`` the ``[n_obs, n_root]`` coefficients (host), ``d_obs`` / ``d_cov`` the device
+    addresses of the ``[n_bin, n_obs]`` and ``[n_bin, n_obs, n_obs]`` sums.  The struct points into the keepalive array."""
+    c = np.ascontiguousarray(coef, dtype=np.float64)
+    if c.ndim != 2:
+        raise ValueError("coef must be [n_obs, n_root]")
+    return Observables(c.shape[0], c.ctypes.data, d_obs or None, d_cov or None), (c,)
+
+
+def observables_reference(roots, coef, weight=None, root_group=None, bins=None, n_bin: int = 1, bin_base: int = 0, exists=None):
+    """The numpy restatement of fdg_[mc_]accumulate_device_observables' definition: ``(obs [n_bin, n_obs], cov [n_bin, n_obs, n_obs],
+    scale_obs, scale_cov)`` from ``roots [B, R]``, ``coef [n_obs, R]``, ``weight`` None, ``[B]`` or ``[n_group, B]`` with
+    ``root_group [R]``, ``bins [B]`` or None (every sample in bin 0) and ``exists [R]`` (None: every root exists).  ``t_k = w_g(k) *
+    root_k``; ``o_m`` the left fold of ``coef[m, k] * t_k`` over ascending ``k`` with ``coef[m, k] != 0`` among the roots that exist,
+    the first product starting the fold; the samples of a bin are summed by numpy.  A row without a term leaves nan in its column of
+    ``obs`` and its rows and columns of ``cov`` (the call leaves them untouched).  ``scale_*``: the sums of ``|o_m|`` and
+    ``|o_a o_c|``, what a tolerance is measured against."""
+    r = np.asarray(roots, dtype=np.float64)
+    c = np.asarray(coef, dtype=np.float64)
+    B, R = r.shape
+    M = c.shape[0]
+    live = np.ones(R, bool) if exists is None else np.asarray(exists, bool)
+    if weight is None:
+        t = r
+    else:
+        w = np.asarray(weight, dtype=np.float64)
+        if w.ndim == 1:
+            t = w[:B, None] * r
+        else:
+            rg = np.zeros(R, np.int64) if root_group is None else np.asarray(root_group, np.int64)
+            t = w[np.where(live, rg, 0)][:, :B].T * r
+    j = np.zeros(B, np.int64) if bins is None else np.asarray(bins, np.int64)[:B] - int(bin_base)
+    ok = (j >= 0) & (j < n_bin)
+    o = np.zeros((B, M))
+    has = np.zeros(M, bool)
+    for m in range(M):
+        for k in range(R):
+            if live[k] and c[m, k] != 0.0:
+                p = c[m, k] * t[:, k]
+                o[:, m] = o[:, m] + p if has[m] else p
+                has[m] = True
+    obs = np.full((n_bin, M), np.nan)
+    cov = np.full((n_bin, M, M), np.nan)
+    s_obs, s_cov = np.zeros((n_bin, M)), np.zeros((n_bin, M, M))
+    jj = j[ok]
+    for m in range(M):
+        if not has[m]:
+            continue
+        om = o[ok, m]
+        obs[:, m] = np.bincount(jj, om, n_bin)
+        s_obs[:, m] = np.bincount(jj, np.abs(om), n_bin)
+        for m2 in range(m, M):
+            if not has[m2]:
+                continue
+            pr = om * o[ok, m2]
+            cov[:, m, m2] = cov[:, m2, m] = np.bincount(jj, pr, n_bin)
+            s_cov[:, m, m2] = s_cov[:, m2, m] = np.bincount(jj, np.abs(pr), n_bin)
+    return obs, cov, s_obs, s_cov
 
 
 def vegas_sample_device_grouped(d_grid: int, n_dim: int, n_grid: int, col, d_cdf: int, n_bin: int, bin_base: int, d_ext: int, ext_col, polar,

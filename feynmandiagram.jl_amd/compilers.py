@@ -64,6 +64,30 @@ def mc_estimate(acc, acc2, n_sample: int):
     return mean, err
 
 
+def mc_covariance(obs, cov, n_sample: int):
+    """Mean and covariance of the mean of the observables of :meth:`GraphFunc.accumulate_observables` over ``n_sample`` samples:
+    ``mean = S / N`` and ``C = (cov / N - mean (x) mean) / (N - 1)``, with ``S = obs [..., n_obs]``, ``cov [..., n_obs, n_obs]`` and
+    ``N = n_sample`` the whole batch, as in :func:`mc_estimate`.  The diagonal of ``C`` is clamped at 0 as ``mc_estimate`` clamps its
+    variance, so ``sqrt(diag(C))`` equals its error bar bit for bit; the off-diagonal entries are left as they come out.  The error of
+    ``a . o`` is ``sqrt(a^T C a)``.  torch tensors or numpy arrays; the results are of the same kind."""
+    N = int(n_sample)
+    if N < 2:
+        raise ValueError(f"mc_covariance needs n_sample >= 2 (got {N}): the covariance of one sample is undefined")
+    if tuple(cov.shape) != tuple(obs.shape) + (obs.shape[-1],):
+        raise ValueError("cov must have the shape of obs plus one more axis of n_obs")
+    mean = obs / N
+    C = (cov / N - mean[..., :, None] * mean[..., None, :]) / (N - 1)
+    if _is_torch(C):
+        import torch
+        d = torch.diagonal(C, dim1=-2, dim2=-1)
+        d.copy_(d.clamp(min=0.0))
+    else:
+        import numpy as np
+        i = np.arange(C.shape[-1])
+        C[..., i, i] = np.maximum(C[..., i, i], 0.0)
+    return mean, C
+
+
 class GraphFunc:
     """Callable evaluator bound to one lowered graph set (one ``fdg_graph``)."""
 
@@ -393,6 +417,37 @@ class GraphFunc:
             self.handle.accumulate_device_matsubara(leaf.data_ptr(), *strides, 0 if bins is None else bins.data_ptr(), int(bin_base), n_bin,
                                                     0 if weight is None else weight.data_ptr(), desc, B=B, stream=st)
         return torch.complex(sums[0], sums[1]), sums[2], sums[3]
+
+    def accumulate_observables(self, leaf, coef, bins=None, n_bin: int = 1, weight=None, obs=None, cov=None, acc=None, acc2=None,
+                               moments: bool = False, bin_base: int = 0, n_sample: Optional[int] = None):
+        """Linear combinations of the roots and their second moments, for the error bar of a sum, a difference or a series of
+        roots that share their samples: with ``t_k = weight[b] * root_k(b)`` and ``o_m = sum_k coef[m, k] * t_k`` (a left fold over
+        ascending ``k``, zero coefficients skipped), the samples of bin ``j`` add ``o_m`` to ``obs[j, m]`` and ``o_a * o_c`` to
+        ``cov[j, a, c]`` (symmetric, both triangles written).  ``coef``: host ``[n_obs, R]`` with ``n_obs <= capi.FDG_OBS_MAX``;
+        ``obs`` / ``cov``: contiguous float64 ``[n_bin, n_obs]`` / ``[n_bin, n_obs, n_obs]`` CUDA tensors, added to (zeros when None).
+        ``moments=True`` (or ``acc`` / ``acc2`` given): the per-root moments of :meth:`accumulate_moments` too, with its bits, from the
+        same evaluation of the roots.  Returns ``(obs, cov)`` or ``(obs, cov, acc, acc2)``; :func:`mc_covariance` turns the first two
+        into a mean and a covariance.  Real observables of unprojected roots only.  Deterministic: no float atomics
+        (fdg_accumulate_device_observables)."""
+        import numpy as np
+        B, n_bin, bins, weight, strides = self._binned_args(leaf, bins, n_bin, weight, n_sample, bins_optional=True)
+        c = np.ascontiguousarray(coef, dtype=np.float64)
+        if c.ndim != 2 or c.shape[1] != self.n_root or not (1 <= c.shape[0] <= capi.FDG_OBS_MAX):
+            raise ValueError(f"coef must be [n_obs, n_root = {self.n_root}] with 1 <= n_obs <= {capi.FDG_OBS_MAX}")
+        obs = self._out(obs, (n_bin, c.shape[0]), leaf, "obs")
+        cov = self._out(cov, (n_bin, c.shape[0], c.shape[0]), leaf, "cov")
+        moments = moments or acc is not None or acc2 is not None
+        if moments:
+            acc = self._out(acc, (n_bin, self.n_root), leaf, "acc")
+            acc2 = self._out(acc2, (n_bin, self.n_root), leaf, "acc2")
+        self._distinct("obs, cov, acc and acc2", obs, cov, acc, acc2)
+        desc, _keep = capi.make_observables(c, obs.data_ptr(), cov.data_ptr())
+        with self._stream(leaf) as st:
+            self.handle.accumulate_device_observables(leaf.data_ptr(), *strides, 0 if bins is None else bins.data_ptr(), int(bin_base),
+                                                      n_bin, 0 if weight is None else weight.data_ptr(), desc,
+                                                      d_acc=acc.data_ptr() if moments else 0, d_acc2=acc2.data_ptr() if moments else 0,
+                                                      B=B, stream=st)
+        return (obs, cov, acc, acc2) if moments else (obs, cov)
 
     def _binned_args(self, leaf, bins, n_bin, weight, n_sample, bins_optional=False):
         """The checks of :meth:`accumulate_binned` / :meth:`accumulate_moments`: (n_sample, n_bin, bins, weight, leaf strides), bins and

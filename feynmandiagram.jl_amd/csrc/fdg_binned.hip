@@ -45,6 +45,11 @@
 // variable into the jacobians of the groups that own it, the moments and projection passes read the weight column of a root's group,
 // and the training passes sum (w_g s_g)^2 over the groups that own a variable.  The ungrouped instantiations are the code they were;
 // a grouped call with one group and a full mask runs them.
+//
+// Observables (fdg_[mc_]accumulate_device_observables): one more pass per chunk over the same roots (fdg_obs_partials below) that
+// forms up to FDG_OBS_MAX linear combinations o_m of the weighted roots per sample and sums o_m and the products o_a o_c per bin: the
+// first moment and the covariance of sums, differences and series of roots, which the per-root acc2 cannot give because all roots
+// share their samples.  A kernel of its own: every instance above is the code it was.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -263,6 +268,174 @@ fdg_binned_reduce(const double *__restrict__ partial, uint32_t n_seg, long seg_s
     double t = sh[cl];
     for (uint32_t qq = 1; qq < Q && qq < n_seg; ++qq) t = t + sh[qq * C + cl];
     if (!live || live[c % R]) out[c] = out[c] + t;
+  }
+}
+
+// ---- Observables: linear combinations of the roots and their covariance (include/fdg.h: fdg_[mc_]accumulate_device_observables) ----
+// The value columns of a sample: o_0 .. o_{n_obs - 1}, then the products o_a o_c, a <= c, row by row of the upper triangle:
+// V = n_obs + n_obs (n_obs + 1) / 2 columns.  One workgroup per (segment of the chunk's tiles, slice of CS consecutive columns), the
+// slice's histogram (n_bin x CS doubles) in LDS; its four waves take the segment's tiles in rounds, wave w the tile 4 r + w, exactly
+// as fdg_binned_partials deals them.
+//  * A wave sorts its tile's lanes by (bin, lane) FIRST (the keys need the bin vector only), and every lane then forms the o_m of
+//    the sample whose key it holds: the root and weight columns are read at the sorted position, still inside the tile's 512 bytes of
+//    every column, so nothing has to cross lanes afterwards.
+//  * The slice's table (one upload per call, built on the host) lists the roots that the rows it needs use, ascending, each with the
+//    place of its weight column and its terms (row, coefficient), zero coefficients and roots that do not exist compacted away.  A
+//    root column is loaded once per tile, t = w_g(k) root_k formed as the moments pass forms it, and every term folds coef * t into its
+//    row's word of the lane's LDS stash ([row of the slice][256 lanes]: a lane only ever touches its own words).  The first term of a
+//    row starts the fold (flag in the table); the fold runs over ascending k.
+//  * The columns of the slice are then scanned kObsGroup at a time: a column is a stash word or the rounded product of two, 0.0
+//    selected where the key is invalid; the segmented suffix scan and the waves' turns are fdg_binned_partials' own, so per (bin,
+//    column) the tiles are added in tile order.
+//  * Chunks and segments chain through partial [segment][bin][V], summed in segment order by fdg_obs_reduce.
+// utab, per call: four words per slice {rows needed, root records, offset of the slice's words in utab, offset of its coefficients in
+// dtab}; the slice's words are colA[CS], colB[CS] (stash rows of a column's one or two factors; kObsNone: no second factor, or a
+// column of a row without terms, which stays 0), then four words per root record {root, place of its weight column, first term, end
+// of terms}, then a word per term (stash row, bit 31: the term starts its row's fold).  dtab: the terms' coefficients.
+constexpr uint32_t kObsGroup = 16;                        // columns a wave scans together
+constexpr uint32_t kObsNone = 0xFFFFFFFFu;
+constexpr uint32_t kObsFirst = 0x80000000u;
+
+__global__ void __launch_bounds__(256)
+fdg_obs_partials(const double *__restrict__ root, long ld, long n, const int32_t *__restrict__ bins, int32_t bin_base, uint32_t n_bin,
+                 const double *__restrict__ weight, long wstride, uint32_t n_wcol, uint32_t V, uint32_t CS, uint32_t n_slice, long seg_tiles,
+                 double *__restrict__ partial, int first, const uint32_t *__restrict__ utab, const double *__restrict__ dtab) {
+  extern __shared__ double hist[];                        // [bin][CS], then the stash [row][256]
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t slice = blockIdx.x % n_slice, seg = blockIdx.x / n_slice;
+  const uint32_t c0 = slice * CS, cn = min(CS, V - c0);
+  const uint32_t *hdr = utab + (size_t)slice * 4u;
+  const uint32_t n_rec = hdr[1];
+  const uint32_t *colA = utab + hdr[2], *colB = colA + CS, *rec = colB + CS, *tslot = rec + (size_t)n_rec * 4u;
+  const double *tcoef = dtab + hdr[3];
+  double *stash = hist + (size_t)n_bin * CS + threadIdx.x;
+  double *slab = partial + (size_t)seg * n_bin * V + c0;
+  for (uint32_t i = threadIdx.x; i < n_bin * CS; i += 256) {
+    const uint32_t j = i / CS, cl = i % CS;
+    hist[i] = (first || cl >= cn) ? 0.0 : slab[(size_t)j * V + cl];
+  }
+  __syncthreads();
+  const SegTiles sg = seg_tiles_of(n, seg, seg_tiles);
+  const long t0 = sg.t0, t1 = sg.t1, rounds = sg.rounds;
+  int32_t bin_n;
+  auto fetch = [&](long r) {                              // the bin of this lane's sample of round r, one round ahead (index clamped)
+    const long b = min((t0 + r * (long)kBinWaves + wave) * 64 + lane, n - 1);
+    bin_n = bins ? bins[b] : bin_base;
+  };
+  fetch(0);
+  for (long r = 0; r < rounds; ++r) {
+    const long t = t0 + r * (long)kBinWaves + wave, b = t * 64 + lane;
+    const int64_t jb = (int64_t)bin_n - (int64_t)bin_base;
+    const bool in = t < t1 && b < n && jb >= 0 && jb < (int64_t)n_bin;
+    uint32_t key = in ? ((uint32_t)jb << 6) | lane : kKeyInvalid | lane;
+    fetch(r + 1);
+    const uint64_t valid = __ballot(key < kKeyInvalid);
+    bool head = false, ok = false;
+    uint32_t j = 0, end = lane;
+    if (valid) {
+      const uint32_t src = wave_sort_keys(key, lane, valid);
+      wave_runs(key, lane, j, head, end);
+      ok = key < kKeyInvalid;
+      // the sample this lane now stands for (clamped into the chunk: what an invalid key loads is selected away below)
+      const size_t bs = (size_t)min(t * 64 + (long)src, n - 1);
+      double wv[kGrpCols] = {};
+#pragma unroll
+      for (uint32_t c = 0; c < kGrpCols; ++c)
+        if (c < n_wcol) wv[c] = weight[(size_t)c * (size_t)wstride + bs];
+      for (uint32_t i0 = 0; i0 < n_rec; i0 += 4) {
+        double rv[4];
+#pragma unroll
+        for (uint32_t u = 0; u < 4; ++u) rv[u] = root[(size_t)rec[(size_t)min(i0 + u, n_rec - 1u) * 4u] * (size_t)ld + bs];
+#pragma unroll
+        for (uint32_t u = 0; u < 4; ++u) {
+          if (i0 + u >= n_rec) break;
+          const uint32_t *e = rec + (size_t)(i0 + u) * 4u;
+          const uint32_t wc = e[1];
+          double wk = wv[0];
+#pragma unroll
+          for (uint32_t c = 1; c < kGrpCols; ++c) wk = wc == c ? wv[c] : wk;
+          const double tk = n_wcol ? wk * rv[u] : rv[u];
+          for (uint32_t ti = e[2]; ti < e[3]; ++ti) {
+            const uint32_t sl = tslot[ti];
+            double *o = stash + (size_t)(sl & ~kObsFirst) * 256u;
+            const double p = tcoef[ti] * tk;
+            *o = (sl & kObsFirst) ? p : *o + p;
+          }
+        }
+      }
+    }
+    for (uint32_t g0 = 0; g0 < cn; g0 += kObsGroup) {
+      double s[kObsGroup];
+      if (valid) {
+#pragma unroll
+        for (uint32_t i = 0; i < kObsGroup; ++i) {
+          const uint32_t cl = min(g0 + i, cn - 1u), a = colA[cl], c = colB[cl];
+          double v = 0.0;
+          if (a != kObsNone) {
+            v = stash[(size_t)a * 256u];
+            if (c != kObsNone) v = v * stash[(size_t)c * 256u];
+          }
+          s[i] = ok ? v : 0.0;                            // selected, never multiplied by 0
+        }
+        for (uint32_t d = 1; d < 64; d <<= 1) {           // segmented suffix scan, as in fdg_binned_partials
+          const bool take = lane + d <= end;
+          if (!__ballot(take)) break;
+#pragma unroll
+          for (uint32_t i = 0; i < kObsGroup; ++i) {
+            const double up = __shfl_down(s[i], d);
+            if (take) s[i] = s[i] + up;
+          }
+        }
+      }
+      for (uint32_t w = 0; w < kBinWaves; ++w) {          // the waves' turns, in wave order
+        if (wave == w && head) {
+#pragma unroll
+          for (uint32_t i = 0; i < kObsGroup; ++i)
+            if (g0 + i < cn) hist[(size_t)j * CS + g0 + i] = hist[(size_t)j * CS + g0 + i] + s[i];
+        }
+        bin_barrier();
+      }
+    }
+  }
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < n_bin * CS; i += 256) {
+    const uint32_t jj = i / CS, cl = i % CS;
+    if (cl < cn) slab[(size_t)jj * V + cl] = hist[i];
+  }
+}
+
+// d_obs[j][m] and d_cov[j][a][c] += the segments' partials [segment][bin][V], with fdg_binned_reduce's order (thread (q, c) adds the
+// segments q, q + Q, ..., then the Q sums are added q = 0, 1, ...; Q = 256 / C).  The column of a product goes to [a][c] and to its
+// mirror [c][a]; rows without a term (bit m of rowlive clear) leave their column of d_obs and their rows and columns of d_cov alone.
+__global__ void __launch_bounds__(256)
+fdg_obs_reduce(const double *__restrict__ partial, uint32_t n_seg, long ncol, uint32_t n_obs, uint32_t V, uint32_t C, uint32_t rowlive,
+               double *__restrict__ obs, double *__restrict__ cov) {
+  __shared__ double sh[256];
+  const uint32_t Q = 256u / C, q = threadIdx.x / C, cl = threadIdx.x % C;
+  const long c = (long)blockIdx.x * C + cl;
+  double s = 0.0;
+  if (c < ncol)
+    for (uint32_t sg = q; sg < n_seg; sg += Q) s = s + partial[(size_t)sg * (size_t)ncol + (size_t)c];
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  if (q == 0 && c < ncol) {
+    double t = sh[cl];
+    for (uint32_t qq = 1; qq < Q && qq < n_seg; ++qq) t = t + sh[qq * C + cl];
+    const size_t jb = (size_t)(c / V);
+    const uint32_t v = (uint32_t)(c % V);
+    if (v < n_obs) {
+      if ((rowlive >> v) & 1u) obs[jb * n_obs + v] = obs[jb * n_obs + v] + t;
+    } else {
+      uint32_t a = 0, p = v - n_obs;                      // the p-th entry of the upper triangle, row by row
+      while (p >= n_obs - a) { p -= n_obs - a; ++a; }
+      const uint32_t cc = a + p;
+      if (((rowlive >> a) & 1u) && ((rowlive >> cc) & 1u)) {
+        double *m = cov + jb * n_obs * n_obs;
+        const double up = m[a * n_obs + cc] + t;
+        m[a * n_obs + cc] = up;
+        if (cc != a) m[cc * n_obs + a] = m[cc * n_obs + a] + t;
+      }
+    }
   }
 }
 
@@ -816,6 +989,11 @@ struct MatsubaraRun {
   int64_t ts = 0, tc = 0;
 };
 
+// The observables of one call (fdg_[mc_]accumulate_device_observables): the descriptor as the entry point was given it.
+struct ObsRun {
+  const fdg_observables *ob = nullptr;
+};
+
 // One accumulate call, as the entry point was given it (aggregate-initialised there, in this order): what the checks, the shared body
 // and run_binned read.
 struct BinnedCall {
@@ -829,6 +1007,7 @@ struct BinnedCall {
   const VegasRun *vg = nullptr;      // the VEGAS calls: the training pass runs too
   const MatsubaraRun *mz = nullptr;  // the projection calls: the projection pass runs too; d_acc and d_acc2 may then both be null
   const fdg_weight_groups *wg = nullptr;   // the grouped calls: d_weight holds one column per group
+  const ObsRun *ob = nullptr;        // the observables calls: the observables pass runs too; d_acc and d_acc2 may then both be null
 };
 
 constexpr size_t page_up(size_t bytes) { return (bytes + 4095) & ~(size_t)4095; }
@@ -956,6 +1135,99 @@ MatsubaraPlan matsubara_plan(const BinnedPlan &p, uint32_t R, uint32_t n_bin, ui
   return q;
 }
 
+// How the observables pass is cut.  Columns per slice: as many of the V value columns as the binned plan's LDS budget holds (whole
+// columns of n_bin bins; one column of more than 8192 bins takes what one root of FDG_BIN_MAX bins takes), spread evenly over the
+// slices.  Segments: the binned call's own count whenever the slab [segment][bin][V] fits in 2 kBinSlabBytes (the moments call's
+// bound), so that a unit row sums in the moments call's order; else the largest count that fits.  A function of (n_sample, n_bin,
+// n_obs, n_root, FDG_ROOT_SCRATCH_MB) only.
+struct ObsPlan {
+  uint32_t V = 1, cs = 1, n_slice = 1, n_seg = 1;
+  size_t hist_bytes = 0, slab_alloc = 0;
+};
+
+ObsPlan obs_plan(const BinnedPlan &p, uint32_t n_bin, uint32_t n_obs) {
+  ObsPlan q;
+  q.V = n_obs + n_obs * (n_obs + 1u) / 2u;
+  const uint32_t fit = (uint32_t)std::max<size_t>(1, kBinLdsBudget / ((size_t)n_bin * 8u));
+  q.n_slice = (q.V + fit - 1) / fit;
+  q.cs = (q.V + q.n_slice - 1) / q.n_slice;
+  q.n_slice = (q.V + q.cs - 1) / q.cs;
+  q.hist_bytes = (size_t)n_bin * q.cs * 8u;
+  const size_t seg_bytes = (size_t)n_bin * q.V * 8u;
+  q.n_seg = (uint32_t)std::max<size_t>(1, std::min<size_t>(p.n_seg, 2u * kBinSlabBytes / seg_bytes));
+  q.slab_alloc = page_up((size_t)q.n_seg * seg_bytes);
+  return q;
+}
+
+// The tables of fdg_obs_partials for one call (the layout is stated there), built from the host coefficients: need = the most stash
+// rows a slice uses, rowlive = bit m set when row m has a term.
+struct ObsTables {
+  std::vector<uint32_t> u;
+  std::vector<double> d;
+  uint32_t need = 1, rowlive = 0;
+};
+
+ObsTables obs_tables(const fdg_graph *g, const ObsPlan &q, const fdg_observables &ob, const fdg_weight_groups *wg) {
+  const uint32_t R = g->prog.R, M = ob.n_obs;
+  ObsTables t;
+  auto term = [&](uint32_t m, uint32_t k) { return g->prog.root_slot[k] != FDG_NO_ROOT && ob.coef[(size_t)m * R + k] != 0.0; };
+  for (uint32_t m = 0; m < M; ++m)
+    for (uint32_t k = 0; k < R; ++k)
+      if (term(m, k)) { t.rowlive |= 1u << m; break; }
+  std::vector<uint32_t> pa, pc;                            // the factors of every value column
+  for (uint32_t m = 0; m < M; ++m) { pa.push_back(m); pc.push_back(kObsNone); }
+  for (uint32_t a = 0; a < M; ++a)
+    for (uint32_t c = a; c < M; ++c) { pa.push_back(a); pc.push_back(c); }
+  t.u.assign((size_t)q.n_slice * 4u, 0u);
+  for (uint32_t s = 0; s < q.n_slice; ++s) {
+    const uint32_t c0 = s * q.cs, cn = std::min(q.cs, q.V - c0);
+    std::vector<uint32_t> slot(M, kObsNone);               // the stash row of every row the slice needs, ascending
+    std::vector<uint32_t> colA(q.cs, kObsNone), colB(q.cs, kObsNone);
+    uint32_t used = 0;
+    for (uint32_t cl = 0; cl < cn; ++cl) {
+      const uint32_t a = pa[c0 + cl], c = pc[c0 + cl];
+      if (!((t.rowlive >> a) & 1u) || (c != kObsNone && !((t.rowlive >> c) & 1u))) continue;
+      used |= 1u << a;
+      if (c != kObsNone) used |= 1u << c;
+    }
+    uint32_t n_need = 0;
+    for (uint32_t m = 0; m < M; ++m)
+      if ((used >> m) & 1u) slot[m] = n_need++;
+    for (uint32_t cl = 0; cl < cn; ++cl) {
+      const uint32_t a = pa[c0 + cl], c = pc[c0 + cl];
+      if (slot[a] == kObsNone || (c != kObsNone && slot[c] == kObsNone)) continue;
+      colA[cl] = slot[a];
+      colB[cl] = c == kObsNone ? kObsNone : slot[c];
+    }
+    std::vector<uint32_t> recs, terms;
+    std::vector<bool> started(M, false);
+    const size_t d0 = t.d.size();
+    for (uint32_t k = 0; k < R; ++k) {
+      const uint32_t tb = (uint32_t)terms.size();
+      for (uint32_t m = 0; m < M; ++m)
+        if (slot[m] != kObsNone && term(m, k)) {
+          terms.push_back(slot[m] | (started[m] ? 0u : kObsFirst));
+          started[m] = true;
+          t.d.push_back(ob.coef[(size_t)m * R + k]);
+        }
+      if (terms.size() == tb) continue;
+      const uint32_t rk[4] = {k, wg && wg->n_group > 1 ? wg->root_group[k] : 0u, tb, (uint32_t)terms.size()};
+      recs.insert(recs.end(), rk, rk + 4);
+    }
+    uint32_t *hdr = t.u.data() + (size_t)s * 4u;
+    hdr[0] = n_need;
+    hdr[1] = (uint32_t)(recs.size() / 4u);
+    hdr[2] = (uint32_t)t.u.size();
+    hdr[3] = (uint32_t)d0;
+    t.need = std::max(t.need, n_need);
+    t.u.insert(t.u.end(), colA.begin(), colA.end());
+    t.u.insert(t.u.end(), colB.begin(), colB.end());
+    t.u.insert(t.u.end(), recs.begin(), recs.end());
+    t.u.insert(t.u.end(), terms.begin(), terms.end());
+  }
+  return t;
+}
+
 using MatsubaraKernel = void (*)(const double *, long, long, const int32_t *, int32_t, uint32_t, const double *, const double *, long, long,
                                  const double *, double, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, long, double *, int,
                                  const uint32_t *, long);
@@ -999,7 +1271,10 @@ void raise_lds_limits() {
   std::call_once(once, [] {
     const int hist = (int)(FDG_BIN_MAX * 8), train = (int)(kBinLdsBudget + 2u * kBinWaves * 64u * 8u);
     const int train_grp = (int)(kBinLdsBudget + 2u * kBinWaves * 64u * 8u * FDG_WEIGHT_GROUP_MAX);
-    std::vector<std::pair<const void *, int>> limits = {{(const void *)fdg_binned_partials<1, kSplit>, hist},
+    // the observables pass: a histogram slice and the stash, 2 KiB per row (every row beside kBinLdsBudget, two beside one column of FDG_BIN_MAX bins)
+    const int obs = (int)std::max<size_t>(kBinLdsBudget + FDG_OBS_MAX * 2048u, FDG_BIN_MAX * 8u + 2u * 2048u);
+    std::vector<std::pair<const void *, int>> limits = {{(const void *)fdg_obs_partials, obs},
+                                                        {(const void *)fdg_binned_partials<1, kSplit>, hist},
                                                         {(const void *)fdg_binned_partials<1, kSplit, true>, hist},
                                                         {(const void *)fdg_vegas_bin_partials<false>, hist},
                                                         {(const void *)fdg_vegas_bin_partials<true>, hist},
@@ -1039,8 +1314,9 @@ int reduce_partials(const double *partial, uint32_t n_seg, long ncol, uint32_t R
 int check_call(const fdg_graph *g, const BinnedCall &c, bool moments) {
   if (!g) { set_error("null handle"); return FDG_E_INVALID; }
   if (c.B < 0) { set_error("n_sample < 0"); return FDG_E_INVALID; }
-  if (!c.d_acc || (moments ? !c.d_acc2 : !c.d_bin)) { set_error("null device buffer"); return FDG_E_INVALID; }
-  if (c.d_acc == c.d_acc2) { set_error("d_acc and d_acc2 are the same buffer"); return FDG_E_INVALID; }
+  const bool no_acc = c.ob && moments && !c.d_acc && !c.d_acc2;    // the observables calls: no per-root moments asked for
+  if (!no_acc && (!c.d_acc || (moments ? !c.d_acc2 : !c.d_bin))) { set_error("null device buffer"); return FDG_E_INVALID; }
+  if (!no_acc && c.d_acc == c.d_acc2) { set_error("d_acc and d_acc2 are the same buffer"); return FDG_E_INVALID; }
   if (c.n_bin == 0) { set_error("n_bin == 0"); return FDG_E_INVALID; }
   if (!c.d_bin && c.n_bin != 1) { set_error("d_bin == NULL (one bin) needs n_bin == 1"); return FDG_E_INVALID; }
   if (c.n_bin > FDG_BIN_MAX) { set_error("n_bin > FDG_BIN_MAX"); return FDG_E_UNSUPPORTED; }
@@ -1102,11 +1378,21 @@ int check_matsubara(const fdg_graph *g, const BinnedCall &c, const fdg_matsubara
   return v ? check_vegas_map(v->D, v->G) : FDG_OK;
 }
 
+// What a call's blocks amount to once its weights are checked: the projection calls' cases with a descriptor, else the VEGAS calls'
+// with a training block, else the moments calls'.
+int check_blocks(const fdg_graph *g, const BinnedCall &c, const fdg_matsubara *m, const double *mc_T) {
+  if (m) return check_matsubara(g, c, m, mc_T);
+  if (!c.vg) return check_call(g, c, true);
+  if (!c.d_bin && c.vg->d_hist_bin) { set_error("d_hist_bin needs d_bin"); return FDG_E_INVALID; }
+  return check_vegas(g, c);
+}
+
 // ... and the grouped calls': the weight groups first, then the cases of the call the arguments amount to (the projection calls'
 // with a descriptor, else the VEGAS calls' with a training block, else the moments calls').
-int check_grouped(const fdg_graph *g, const BinnedCall &c, const fdg_matsubara *m, const double *mc_T) {
+int check_grouped(const fdg_graph *g, const BinnedCall &c, const fdg_matsubara *m, const double *mc_T, bool wg_optional = false) {
   const fdg_weight_groups *w = c.wg;
   if (!g) { set_error("null handle"); return FDG_E_INVALID; }
+  if (!w && wg_optional) return check_blocks(g, c, m, mc_T);
   if (!w || !w->root_group || !w->var_mask) { set_error("null weight groups, root_group or var_mask"); return FDG_E_INVALID; }
   if (!c.d_weight) { set_error("the grouped calls need d_weight"); return FDG_E_INVALID; }
   if (w->n_group == 0) { set_error("n_group == 0"); return FDG_E_INVALID; }
@@ -1117,10 +1403,25 @@ int check_grouped(const fdg_graph *g, const BinnedCall &c, const fdg_matsubara *
     for (uint32_t gi = 0; gi < w->n_group; ++gi)
       if (w->var_mask[gi] >> c.vg->D) { set_error("var_mask names a variable >= n_dim"); return FDG_E_INVALID; }
   if (w->n_group > 1 && w->weight_group_stride < c.B) { set_error("weight_group_stride < n_sample"); return FDG_E_INVALID; }
-  if (m) return check_matsubara(g, c, m, mc_T);
-  if (!c.vg) return check_call(g, c, true);
-  if (!c.d_bin && c.vg->d_hist_bin) { set_error("d_hist_bin needs d_bin"); return FDG_E_INVALID; }
-  return check_vegas(g, c);
+  return check_blocks(g, c, m, mc_T);
+}
+
+// ... and the observables calls': the descriptor first (the coefficients need the handle's n_root), then the grouped calls' cases
+// with wg optional and, through c.ob, d_acc and d_acc2 optional together.
+int check_observables(const fdg_graph *g, const BinnedCall &c, const fdg_matsubara *m, const double *mc_T) {
+  if (!g) { set_error("null handle"); return FDG_E_INVALID; }
+  const fdg_observables *o = c.ob ? c.ob->ob : nullptr;
+  if (!o) { set_error("null observables"); return FDG_E_INVALID; }
+  if (!o->coef || !o->d_obs || !o->d_cov) { set_error("null array in the observables"); return FDG_E_INVALID; }
+  if (o->n_obs == 0) { set_error("n_obs == 0"); return FDG_E_INVALID; }
+  if (o->n_obs > FDG_OBS_MAX) { set_error("n_obs > FDG_OBS_MAX"); return FDG_E_UNSUPPORTED; }
+  for (size_t i = 0; i < (size_t)o->n_obs * g->prog.R; ++i)
+    if (!std::isfinite(o->coef[i])) { set_error("a coefficient of the observables is not finite"); return FDG_E_INVALID; }
+  if (o->d_obs == o->d_cov) { set_error("d_obs and d_cov are the same buffer"); return FDG_E_INVALID; }
+  for (const double *out : {c.d_acc, c.d_acc2})
+    if (out && (out == o->d_obs || out == o->d_cov)) { set_error("d_obs or d_cov is the same buffer as d_acc or d_acc2"); return FDG_E_INVALID; }
+  if (!c.d_acc != !c.d_acc2) { set_error("d_acc and d_acc2 go together"); return FDG_E_INVALID; }
+  return check_grouped(g, c, m, mc_T, true);
 }
 
 // The chunk loop shared by the entry points (caller holds g->mu, stream bound): eval(c0, n, roots, ld) writes the roots of samples
@@ -1156,7 +1457,17 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
   const size_t proj_bytes = mz ? base_bytes + mp.slab_alloc + mp.tab_bytes : base_bytes;
   const size_t gtab_words = (size_t)R + (size_t)p.n_slice * kGrpEntry + kGrpCols + 1u;
   const size_t grp_bytes = (grp_w || grp_t) ? page_up(gtab_words * 4u + (vg ? (size_t)vg->D * vg->G : 0)) : 0;
-  int rc = ensure_root_scratch(g, proj_bytes + grp_bytes);
+  // ... and the observables' slab and tables behind that
+  const fdg_observables *ob = c.ob ? c.ob->ob : nullptr;
+  ObsPlan op;
+  ObsTables ot;
+  size_t obs_bytes = 0;
+  if (ob) {
+    op = obs_plan(p, n_bin, ob->n_obs);
+    ot = obs_tables(g, op, *ob, wg);
+    obs_bytes = op.slab_alloc + page_up(ot.d.size() * 8u) + page_up(ot.u.size() * 4u);
+  }
+  int rc = ensure_root_scratch(g, proj_bytes + grp_bytes + obs_bytes);
   if (rc) return rc;
   double *roots = (double *)g->d_ws2, *partial = (double *)((char *)g->d_ws2 + root_bytes);
   const uint8_t *live = nullptr;
@@ -1239,6 +1550,15 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
     }
     HIP_TRY(hipMemcpyAsync(d_mtab, hm.data(), hm.size() * sizeof(double), hipMemcpyHostToDevice, st));
   }
+  double *opartial = nullptr, *d_odtab = nullptr;
+  uint32_t *d_outab = nullptr;
+  if (ob) {
+    opartial = (double *)((char *)g->d_ws2 + proj_bytes + grp_bytes);
+    d_odtab = (double *)((char *)opartial + op.slab_alloc);
+    d_outab = (uint32_t *)((char *)d_odtab + page_up(ot.d.size() * 8u));
+    if (!ot.d.empty()) HIP_TRY(hipMemcpyAsync(d_odtab, ot.d.data(), ot.d.size() * 8u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_outab, ot.u.data(), ot.u.size() * 4u, hipMemcpyHostToDevice, st));
+  }
   const MatsubaraKernel mpass = matsubara_kernel(mp, grp_w);
   const PartialsKernel pass = partials_kernel(p, grp_w);
   const uint32_t n_grp = p.mode == kSplit ? 2 * p.n_slice : p.n_slice;
@@ -1252,6 +1572,13 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
     if (c.d_acc) {
       hipLaunchKernelGGL(pass, dim3(p.n_seg * n_grp), dim3(256), p.lds, st, roots, (long)p.Bc, n, bins, c.bin_base, n_bin, w, R, p.n_slice,
                          (ntile + p.n_seg - 1) / p.n_seg, partial, first, d_gtab, wstride);
+      HIP_TRY(hipGetLastError());
+    }
+    if (ob) {
+      // (one weight column per group; without groups one, or none when the call has no weights)
+      hipLaunchKernelGGL(fdg_obs_partials, dim3(op.n_seg * op.n_slice), dim3(256), op.hist_bytes + (size_t)ot.need * 2048u, st, roots,
+                         (long)p.Bc, n, bins, c.bin_base, n_bin, w, wstride, w ? (grp_w ? NG : 1u) : 0u, op.V, op.cs, op.n_slice,
+                         (ntile + op.n_seg - 1) / op.n_seg, opartial, first, d_outab, d_odtab);
       HIP_TRY(hipGetLastError());
     }
     if (mz) {
@@ -1281,6 +1608,13 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
   uint32_t C = 1;
   while (C < 64 && (long)C < ncol) C <<= 1;
   if (c.d_acc) rc = reduce_partials(partial, p.n_seg, ncol, R, C, c.d_acc, c.d_acc2, live, st);
+  if (!rc && ob) {
+    // (C, and with it the order of the segments' sum, is the moments reduce's own: a unit row then carries the moments call's bits)
+    const long ocol = (long)n_bin * op.V;
+    hipLaunchKernelGGL(fdg_obs_reduce, dim3((unsigned)((ocol + C - 1) / C)), dim3(256), 0, st, opartial, op.n_seg, ocol, ob->n_obs, op.V, C,
+                       ot.rowlive, ob->d_obs, ob->d_cov);
+    HIP_TRY(hipGetLastError());
+  }
   if (!rc && mz) {
     // the four arrays += the segments' partials [segment][4][bin][frequency][root], in segment order: first both first moments, then both second
     const long mcol = ncol * mz->m->n_freq;
@@ -1322,7 +1656,7 @@ int accumulate_leaf(fdg_graph *g, const double *d_leaf, int64_t ss, int64_t ls, 
   return accumulate(
       g, c, g->prog.L && !d_leaf,
       [&] {
-        if ((c.d_acc2 || c.mz) && lts && !(g->isa && !g->code_object.empty())) {     // (the binned call finds it in the first chunk's evaluation)
+        if ((c.d_acc2 || c.mz || c.ob) && lts && !(g->isa && !g->code_object.empty())) {     // (the binned call finds it in the first chunk's evaluation)
           set_error("tile-major batches need a handle specialised with FDG_SPEC_ISA"); return FDG_E_UNSUPPORTED;
         }
         return FDG_OK;
@@ -1489,6 +1823,36 @@ int fdg_mc_accumulate_device_grouped(fdg_graph *g, const double *d_K, int64_t ks
   const MatsubaraRun mr{mz, own_T ? mz->d_T : d_T, own_T ? mz->t_sample_stride : ts, own_T ? mz->t_comp_stride : tc};
   const BinnedCall c{d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, stream, train ? &vg : nullptr, mz ? &mr : nullptr, wg};
   const int rc = check_grouped(g, c, mz, d_T);
+  return rc ? rc : accumulate_mc(g, d_K, ks, kc, d_T, ts, tc, kF, beta, lambda, c);
+}
+
+int fdg_accumulate_device_observables(fdg_graph *g, const double *d_leaf, int64_t ss, int64_t ls, int64_t lts, const int32_t *d_bin,
+                                      int32_t bin_base, uint32_t n_bin, const double *d_weight, const double *coef, uint64_t seed,
+                                      uint64_t sample_offset, uint32_t n_dim, uint32_t n_grid, double *d_acc, double *d_acc2, double *d_hist,
+                                      double *d_hist_bin, const fdg_matsubara *mz, const fdg_weight_groups *wg, const fdg_observables *ob,
+                                      int64_t B, void *stream) {
+  const bool train = n_dim != 0 || d_hist;
+  const VegasRun vg{coef, seed, sample_offset, n_dim, n_grid, d_hist, d_bin != nullptr, d_hist_bin};
+  const MatsubaraRun mr{mz, mz ? mz->d_T : nullptr, mz ? mz->t_sample_stride : 0, mz ? mz->t_comp_stride : 0};
+  const ObsRun orun{ob};
+  const BinnedCall c{d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, stream, train ? &vg : nullptr, mz ? &mr : nullptr, wg, &orun};
+  const int rc = check_observables(g, c, mz, nullptr);
+  return rc ? rc : accumulate_leaf(g, d_leaf, ss, ls, lts, c);
+}
+
+int fdg_mc_accumulate_device_observables(fdg_graph *g, const double *d_K, int64_t ks, int64_t kc, const double *d_T, int64_t ts, int64_t tc,
+                                         double kF, double beta, double lambda, const int32_t *d_bin, int32_t bin_base, uint32_t n_bin,
+                                         const double *d_weight, const double *coef, uint64_t seed, uint64_t sample_offset, uint32_t n_dim,
+                                         uint32_t n_grid, double *d_acc, double *d_acc2, double *d_hist, double *d_hist_bin,
+                                         const fdg_matsubara *mz, const fdg_weight_groups *wg, const fdg_observables *ob, int64_t B,
+                                         void *stream) {
+  const bool train = n_dim != 0 || d_hist;
+  const VegasRun vg{coef, seed, sample_offset, n_dim, n_grid, d_hist, d_bin != nullptr, d_hist_bin};
+  const bool own_T = mz && mz->d_T;
+  const MatsubaraRun mr{mz, own_T ? mz->d_T : d_T, own_T ? mz->t_sample_stride : ts, own_T ? mz->t_comp_stride : tc};
+  const ObsRun orun{ob};
+  const BinnedCall c{d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, stream, train ? &vg : nullptr, mz ? &mr : nullptr, wg, &orun};
+  const int rc = check_observables(g, c, mz, d_T);
   return rc ? rc : accumulate_mc(g, d_K, ks, kc, d_T, ts, tc, kF, beta, lambda, c);
 }
 

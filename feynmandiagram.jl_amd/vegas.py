@@ -23,6 +23,11 @@ Weight groups (``WeightGroups``, ``groups_from_dof``, the keyword ``groups``; fd
 fdg_mc_accumulate_device_grouped): roots that integrate different numbers of variables in one run -- MCIntegration's ``dof``, as in the
 reference's test/hubbard.jl:81-85 and example/strong_coupling_expansion/naive.jl:195 -- each weighted by the jacobian of its own
 variables, each variable's map trained by the roots that use it.
+
+Observables (``Observables``, the keyword ``observables``; fdg_mc_accumulate_device_observables): what a caller reports is a sum of
+roots -- the direct and exchange components of the reference's test/ver4.jl:184-216, a series summed over its orders -- and its error
+bar needs the covariance of the roots, which share their samples.  The accumulate call sums the combinations and their products on
+the device; the results gain ``obs_mean``, ``obs_stderr``, ``obs_chi2_dof`` and ``obs_cov``.
 """
 from __future__ import annotations
 
@@ -33,7 +38,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import capi
-from .compilers import mc_estimate
+from .compilers import mc_covariance, mc_estimate
 
 
 def uniform_grid(lo, hi, n_grid: int) -> np.ndarray:
@@ -93,6 +98,11 @@ class VegasResult:
     iterations: List[Tuple[np.ndarray, np.ndarray]] = field(default_factory=list)   # (mean [R], stderr [R]) of every iteration
     map: Optional[VegasMap] = None   # the map after the last refinement
     histograms: List[np.ndarray] = field(default_factory=list)                       # the training histogram of every iteration
+    obs_mean: Optional[np.ndarray] = None       # with ``observables``: [n_obs] combination of the iterations kept, as ``mean``
+    obs_stderr: Optional[np.ndarray] = None     # [n_obs]
+    obs_chi2_dof: Optional[np.ndarray] = None   # [n_obs]
+    obs_cov: Optional[np.ndarray] = None        # [n_obs, n_obs] covariance of ``obs_mean`` (:func:`combine_covariance`)
+    obs_iterations: List[Tuple[np.ndarray, np.ndarray]] = field(default_factory=list)   # (mean [n_obs], C [n_obs, n_obs]) of every iteration
 
 
 def combine(iterations: Sequence[Tuple[np.ndarray, np.ndarray]]):
@@ -107,6 +117,26 @@ def combine(iterations: Sequence[Tuple[np.ndarray, np.ndarray]]):
     err = np.where(ok, 1.0 / np.sqrt(wgt.sum(axis=0)), 0.0)
     chi2 = np.where(ok, (wgt * (m - mean) ** 2).sum(axis=0) / max(n - 1, 1), np.nan) if n > 1 else np.full(m.shape[1], np.nan)
     return mean, err, chi2
+
+
+def combine_covariance(iterations: Sequence[Tuple[np.ndarray, np.ndarray]]):
+    """:func:`combine` for observables with a covariance: ``iterations`` holds ``(mean [..., M], C [..., M, M])`` pairs
+    (``mc_covariance``).  Every observable is combined on its own by :func:`combine` with ``stderr = sqrt(diag(C))``; the covariance of
+    the combined means is the exact propagation through those fixed weights, ``sum_i a[i, m] a[i, m'] C_i[m, m']`` with ``a[i, m]``
+    the normalised weights ``combine`` used for observable ``m`` in iteration ``i``.  With inverse-variance weights its diagonal is
+    ``stderr**2``; where ``combine`` averages plainly (an error of 0 in some iteration) the diagonal is the variance of that plain
+    average while ``stderr`` reports 0.  Returns ``(mean, stderr, chi2 / dof, cov)``."""
+    m = np.array([a for a, _ in iterations], dtype=np.float64)
+    c = np.array([b for _, b in iterations], dtype=np.float64)
+    shape = m.shape[1:]
+    M = shape[-1]
+    e = np.sqrt(np.maximum(np.diagonal(c, axis1=-2, axis2=-1), 0.0))
+    mean, err, chi2 = combine([(a.reshape(-1), b.reshape(-1)) for a, b in zip(m, e)])
+    ok = (e > 0).all(axis=0)
+    wgt = np.where(ok, 1.0 / np.where(e > 0, e, 1.0) ** 2, 1.0)
+    a = wgt / wgt.sum(axis=0)
+    cov = (a[..., :, None] * a[..., None, :] * c).sum(axis=0)
+    return mean.reshape(shape), err.reshape(shape), chi2.reshape(shape), cov.reshape(shape + (M,))
 
 
 @dataclass(frozen=True)
@@ -182,6 +212,14 @@ class WeightGroups:
     var_sets: Tuple[Tuple[int, ...], ...]
 
 
+@dataclass(frozen=True)
+class Observables:
+    """Linear combinations of the roots that an integration reports: ``coef[m][k]`` the factor of root ``k`` in observable ``m``, at
+    most ``capi.FDG_OBS_MAX`` rows of ``n_root`` finite numbers.  Every root enters with its own weight (its group's jacobian under
+    ``groups``), unprojected; complex observables (of Matsubara-projected roots) are not supported."""
+    coef: Tuple[Tuple[float, ...], ...]
+
+
 def groups_from_dof(dof, pools) -> WeightGroups:
     """:class:`WeightGroups` in MCIntegration's call shape.  ``pools[p]`` lists, in order, the VEGAS variables of each element of
     variable pool ``p`` (one ``K`` of a polar group: its three variables; one time: one variable); ``dof[i][p]`` says how many leading
@@ -206,7 +244,7 @@ def groups_from_dof(dof, pools) -> WeightGroups:
 
 
 def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter, n_sample, n_grid, alpha, floor, seed, n_discard, fixed, coef,
-               device, vmap, specialize_fused, n_total, shard_start, reduce, polar=None, matsubara=None, wgroups=None):
+               device, vmap, specialize_fused, n_total, shard_start, reduce, polar=None, matsubara=None, wgroups=None, observables=None):
     """The driver behind :func:`vegas_integrate` (``dmap`` None: results ``[R]``) and :func:`vegas_integrate_binned` (``[n_bin, R]``);
     with ``matsubara`` the results are complex and carry a frequency axis in front of the roots."""
     import torch
@@ -239,6 +277,11 @@ def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter,
         for var, cs in groups or ():
             if any(0 < len(set(vs) & set(range(var, var + len(cs)))) < len(cs) for vs in wgroups.var_sets):
                 raise ValueError("a polar group belongs to a weight group whole or not at all")
+    ocoef = None
+    if observables is not None:
+        ocoef = np.ascontiguousarray(observables.coef, dtype=np.float64)
+        if ocoef.ndim != 2 or ocoef.shape[1] != R or not (1 <= ocoef.shape[0] <= capi.FDG_OBS_MAX) or not np.isfinite(ocoef).all():
+            raise ValueError(f"observables.coef must be [n_obs, n_root = {R}], finite, with 1 <= n_obs <= {capi.FDG_OBS_MAX}")
     B = int(n_sample)
     N = B if n_total is None else int(n_total)
     if B < 1 or N < 2 or n_iter < 1 or not (0 <= n_discard < n_iter):
@@ -264,6 +307,7 @@ def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter,
         st = torch.cuda.current_stream(device).cuda_stream
         x = torch.from_numpy(fx).to(device)[:, None].repeat(1, B).contiguous()          # [n_col, B]: sample stride 1
         jac = torch.empty(B if wgroups is None else (len(wgroups.var_sets), B), dtype=torch.float64, device=device)
+        wdesc = None
         if wgroups is not None:
             wdesc, _wkeep = capi.make_weight_groups(wgroups.root_group, wgroups.var_sets, B)
         d_T = x.data_ptr() + 8 * n_col_k * B
@@ -288,18 +332,25 @@ def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter,
             else:
                 capi.vegas_sample_device_discrete(vmap.d_grid.data_ptr(), D, G, col, dmap.d_cdf.data_ptr(), NB, 0, d_ext, dmap.ext_col, seed,
                                                   off, x.data_ptr(), 1, B, jac.data_ptr(), bins.data_ptr(), 0, B, st)
-            if wgroups is not None:
-                # one call for every combination: the projection and the discrete variable are optional in it
+            osums = []
+            if wgroups is not None or ocoef is not None:
+                # one call for every combination: the projection, the discrete variable (and, beside observables, the groups) are optional in it
                 desc, hist_bin = None, None if dmap is None else torch.zeros(NB, dtype=torch.float64, device=device)
                 if matsubara is not None:
                     m = torch.zeros((4, NB, NF, R), dtype=torch.float64, device=device)
                     desc, _keep = capi.make_matsubara(matsubara.freq, matsubara.fermionic, matsubara.root_tau_in, matsubara.root_tau_out,
                                                       beta, n_tau, *[m[i].data_ptr() for i in range(4)])
-                handle.mc_accumulate_device_grouped(x.data_ptr(), 1, B, d_T, 1, B, kF, beta, lam, 0 if dmap is None else bins.data_ptr(), 0,
-                                                    NB, jac.data_ptr(), wdesc, desc, coef, seed, off, D, G,
-                                                    0 if matsubara is not None else m[0].data_ptr(),
-                                                    0 if matsubara is not None else m[1].data_ptr(), hist.data_ptr(),
-                                                    0 if dmap is None else hist_bin.data_ptr(), B, st)
+                blocks = (desc, coef, seed, off, D, G, 0 if matsubara is not None else m[0].data_ptr(),
+                          0 if matsubara is not None else m[1].data_ptr(), hist.data_ptr(), 0 if dmap is None else hist_bin.data_ptr(), B, st)
+                if ocoef is not None:
+                    M = ocoef.shape[0]
+                    osums = [torch.zeros((NB, M), dtype=torch.float64, device=device), torch.zeros((NB, M, M), dtype=torch.float64, device=device)]
+                    odesc, _okeep = capi.make_observables(ocoef, osums[0].data_ptr(), osums[1].data_ptr())
+                    handle.mc_accumulate_device_observables(x.data_ptr(), 1, B, d_T, 1, B, kF, beta, lam,
+                                                            0 if dmap is None else bins.data_ptr(), 0, NB, jac.data_ptr(), odesc, wdesc, *blocks)
+                else:
+                    handle.mc_accumulate_device_grouped(x.data_ptr(), 1, B, d_T, 1, B, kF, beta, lam, 0 if dmap is None else bins.data_ptr(), 0,
+                                                        NB, jac.data_ptr(), wdesc, *blocks)
                 sums = [m, hist] if dmap is None else [m, hist, hist_bin]
             elif matsubara is not None:
                 # (re, im, re^2, im^2) of the projected roots; the training histograms as the calls below leave them
@@ -322,8 +373,12 @@ def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter,
                                                          hist_bin.data_ptr(), B, st)
                 sums = [m, hist, hist_bin]
             if reduce is not None:
-                for t in sums:
+                for t in sums + osums:
                     reduce(t)
+            if osums:
+                om, oc = mc_covariance(osums[0], osums[1], N)
+                oshape = shape[:-1 if matsubara is None else -2] + (ocoef.shape[0],)
+                out.obs_iterations.append((om.cpu().numpy().reshape(oshape), oc.cpu().numpy().reshape(oshape + oshape[-1:])))
             if matsubara is not None:
                 (mr, er), (mi, ei) = mc_estimate(m[0], m[2], N), mc_estimate(m[1], m[3], N)
                 mean, err = torch.complex(mr, mi), torch.complex(er, ei)
@@ -345,6 +400,8 @@ def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter,
     else:
         mean, err, chi2 = combine(kept)
     out.mean, out.stderr, out.chi2_dof = mean.reshape(shape), err.reshape(shape), chi2.reshape(shape)
+    if ocoef is not None:
+        out.obs_mean, out.obs_stderr, out.obs_chi2_dof, out.obs_cov = combine_covariance(out.obs_iterations[int(n_discard):])
     return out
 
 
@@ -352,7 +409,8 @@ def vegas_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: 
                     n_sample: int = 100_000, n_grid: int = 64, alpha: float = 0.5, seed: int = 0, n_discard: int = 0, fixed=None,
                     coef=None, device="cuda", vmap: Optional[VegasMap] = None, specialize_fused: bool = True, n_total: Optional[int] = None,
                     shard_start: int = 0, reduce: Optional[Callable] = None, polar: Optional[Sequence[PolarVar]] = None,
-                    matsubara: Optional[MatsubaraProjection] = None, groups: Optional[WeightGroups] = None) -> VegasResult:
+                    matsubara: Optional[MatsubaraProjection] = None, groups: Optional[WeightGroups] = None,
+                    observables: Optional[Observables] = None) -> VegasResult:
     """Integrates the roots of a graph over the box ``[lo, hi]`` of ``len(col)`` of its Monte-Carlo variables.
 
     ``func_or_handle``: a ``GraphFunc`` or ``capi.GraphHandle``; ``tables`` the ``fdg_leaf_tables`` struct of ``capi.make_leaf_tables``
@@ -379,9 +437,16 @@ def vegas_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: 
     ``groups``: a :class:`WeightGroups` (:func:`groups_from_dof`).  Every root is weighted by the jacobian of its own group's variables
     -- the integral over the others is not taken, as with MCIntegration's ``dof`` -- and a variable's histogram sums, over the groups
     that own it, ``(w_g sum_k c_k r_k)**2`` of the group's roots; a variable of no group is not refined.  The sums, ``reduce`` and
-    ``combine`` are as without.  None: the calls made and their bits are what they are without this keyword."""
+    ``combine`` are as without.  None: the calls made and their bits are what they are without this keyword.
+
+    ``observables``: an :class:`Observables`.  The one accumulate call of an iteration is then fdg_mc_accumulate_device_observables,
+    which carries every other block and leaves their bits as they are; it also sums ``o_m = sum_k coef[m][k] w_g(k) root_k`` and the
+    products ``o_a o_c`` (``reduce`` is applied to both).  ``mc_covariance`` gives every iteration's ``(mean, C)``
+    (``obs_iterations``), and :func:`combine_covariance` the results ``obs_mean``, ``obs_stderr``, ``obs_chi2_dof`` ``[n_obs]`` and
+    ``obs_cov`` ``[n_obs, n_obs]``.  Real observables of the unprojected roots only, also beside ``matsubara``.  None: the calls made
+    and their bits are what they are without this keyword."""
     return _integrate(func_or_handle, tables, lo, hi, col, None, kF, beta, lam, n_iter, n_sample, n_grid, alpha, 0.0, seed, n_discard, fixed, coef,
-                      device, vmap, specialize_fused, n_total, shard_start, reduce, polar, matsubara, groups)
+                      device, vmap, specialize_fused, n_total, shard_start, reduce, polar, matsubara, groups, observables)
 
 
 def uniform_cdf(n_bin: int) -> np.ndarray:
@@ -451,6 +516,11 @@ class VegasBinnedResult:
     dmap: Optional[DiscreteMap] = None
     histograms: List[np.ndarray] = field(default_factory=list)                       # [n_dim, n_grid] of every iteration
     bin_histograms: List[np.ndarray] = field(default_factory=list)                   # [n_bin] of every iteration
+    obs_mean: Optional[np.ndarray] = None       # with ``observables``: [n_bin, n_obs], as ``mean``
+    obs_stderr: Optional[np.ndarray] = None     # [n_bin, n_obs]
+    obs_chi2_dof: Optional[np.ndarray] = None   # [n_bin, n_obs]
+    obs_cov: Optional[np.ndarray] = None        # [n_bin, n_obs, n_obs] (:func:`combine_covariance`)
+    obs_iterations: List[Tuple[np.ndarray, np.ndarray]] = field(default_factory=list)   # (mean [n_bin, n_obs], C [n_bin, n_obs, n_obs])
 
 
 def vegas_integrate_binned(func_or_handle, tables, lo, hi, col, dmap: DiscreteMap, kF: float = 0.0, beta: float = 1.0, lam: float = 0.0, *,
@@ -459,7 +529,7 @@ def vegas_integrate_binned(func_or_handle, tables, lo, hi, col, dmap: DiscreteMa
                            specialize_fused: bool = True, n_total: Optional[int] = None, shard_start: int = 0,
                            reduce: Optional[Callable] = None, polar: Optional[Sequence[PolarVar]] = None,
                            matsubara: Optional[MatsubaraProjection] = None,
-                           groups: Optional[WeightGroups] = None) -> VegasBinnedResult:
+                           groups: Optional[WeightGroups] = None, observables: Optional[Observables] = None) -> VegasBinnedResult:
     """:func:`vegas_integrate` with a discrete variable: every sample draws a value ``j`` of ``dmap`` next to its continuous variables,
     the columns ``dmap.ext_col`` take row ``j`` of ``dmap.ext`` (external momenta), and the estimate is per value: arrays ``[n_bin, R]``,
     bin ``j`` the integral over the continuous variables at configuration ``j`` (the weight carries ``1 / p_j``, and ``mc_estimate``
@@ -467,6 +537,6 @@ def vegas_integrate_binned(func_or_handle, tables, lo, hi, col, dmap: DiscreteMa
     ``mc_estimate``, refine the map with ``alpha`` and the probabilities with ``alpha`` and ``floor``.  ``combine`` is per (bin, root).
     Sharding as in :func:`vegas_integrate`; ``reduce`` is applied to the moments ``[2, n_bin, R]`` and to both histograms, so every rank
     refines the same maps.  ``polar``, ``matsubara`` and ``groups`` as in :func:`vegas_integrate` (complex ``[n_bin, n_freq, R]``; the
-    discrete variable is shared by every group)."""
+    discrete variable is shared by every group); ``observables`` too: ``obs_mean`` ``[n_bin, n_obs]``, ``obs_cov`` ``[n_bin, n_obs, n_obs]``."""
     return _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter, n_sample, n_grid, alpha, floor, seed, n_discard, fixed,
-                      coef, device, vmap, specialize_fused, n_total, shard_start, reduce, polar, matsubara, groups)
+                      coef, device, vmap, specialize_fused, n_total, shard_start, reduce, polar, matsubara, groups, observables)

@@ -879,6 +879,52 @@ int fdg_mc_accumulate_device_grouped(fdg_graph *g, const double *d_K, int64_t k_
                                      double *d_hist, double *d_hist_bin, const fdg_matsubara *mz, const fdg_weight_groups *wg,
                                      int64_t n_sample, void *stream);
 
+/* ---- Observables: linear combinations of the roots, with their covariance ----------------------------------------------------------------
+ * What a caller reports is rarely a root: the reference's own measurement sums a vertex function's roots into a direct and an exchange
+ * component per external configuration (test/ver4.jl:184-216, `obs = zeros(Nk, 2)`), a self-energy series is summed over its orders.
+ * All roots of a run are evaluated on the same samples, so the error bar of a sum, a difference or a ratio of roots cannot be formed
+ * from the per-root d_acc2: it needs the covariance.  MCIntegration is not part of the reference checkout: no counterpart in the
+ * reference; the caller's side of those lines.
+ *
+ * fdg_[mc_]accumulate_device_observables: the arguments of the _grouped calls plus ob.  Every optional block stays optional in the same
+ * way (the bin vector, d_acc / d_acc2, the training block, d_hist_bin, mz); wg may be NULL (one weight column d_weight[b], or no
+ * weights with d_weight == NULL); d_acc and d_acc2 may both be NULL.  coef is a HOST array, row-major [n_obs][n_root].
+ * For every sample b < n_sample whose bin j is in range, every step one rounded fp64 operation:
+ *   t_k = w_g(k) * root_k(b), as the moments pass forms it (root_k(b) without weights);
+ *   o_m = the left fold of coef[m][k] * t_k over ascending k, over the roots that exist with coef[m][k] != 0.0; the first product
+ *         starts the fold (no 0.0 + in front).  A row without a term contributes nothing: its column of d_obs and its rows and
+ *         columns of d_cov are left untouched, as the columns of FDG_NO_ROOT roots are;
+ *   d_obs[j][m] += o_m;   d_cov[j][a][c] += o_a * o_c for a <= c, and d_cov[j][c][a] receives the same increment.
+ * Samples past n_sample or out of range are selected away, never multiplied by zero.  No float atomics.  The order of every sum is a
+ * function of (n_sample, n_bin, n_obs, n_root, n_group, FDG_ROOT_SCRATCH_MB) and of the other blocks' own parameters, not of the
+ * values of coef.  Every other output of the call carries the bits of the same call without ob (with wg NULL: of the ungrouped
+ * call).  Whenever the pass keeps the binned call's segment count (its partials [segment][bin][V], V = n_obs + n_obs (n_obs + 1) / 2,
+ * fit in 128 MiB), a row coef[m] = e_k gives d_obs[:, m] the bits of the moments call's d_acc[:, k] and d_cov[:, m, m] those of
+ * d_acc2[:, k] (csrc/fdg_binned.hip).
+ * Observables combine UNPROJECTED roots only: the Matsubara block stays per root, and complex observables are not supported.
+ * FDG_E_INVALID: ob NULL, one of its arrays NULL, n_obs == 0, a coefficient that is not finite, d_obs or d_cov the same buffer as the
+ * other or as d_acc or d_acc2, one of d_acc and d_acc2 without the other, and the cases of the _grouped calls except those relaxed
+ * above; FDG_E_UNSUPPORTED: n_obs > FDG_OBS_MAX and those calls' limits.  All before any device work. */
+#define FDG_OBS_MAX 16
+typedef struct fdg_observables {
+  uint32_t n_obs;      /* 1 .. FDG_OBS_MAX */
+  const double *coef;  /* HOST [n_obs][n_root], row-major, finite */
+  double *d_obs;       /* device [n_bin][n_obs], added to */
+  double *d_cov;       /* device [n_bin][n_obs][n_obs], added to */
+} fdg_observables;
+int fdg_accumulate_device_observables(fdg_graph *g, const double *d_leaf, int64_t leaf_sample_stride, int64_t leaf_leaf_stride,
+                                      int64_t leaf_tile_stride, const int32_t *d_bin, int32_t bin_base, uint32_t n_bin,
+                                      const double *d_weight, const double *coef, uint64_t seed, uint64_t sample_offset, uint32_t n_dim,
+                                      uint32_t n_grid, double *d_acc, double *d_acc2, double *d_hist, double *d_hist_bin,
+                                      const fdg_matsubara *mz, const fdg_weight_groups *wg, const fdg_observables *ob, int64_t n_sample,
+                                      void *stream);
+int fdg_mc_accumulate_device_observables(fdg_graph *g, const double *d_K, int64_t k_sample_stride, int64_t k_comp_stride,
+                                         const double *d_T, int64_t t_sample_stride, int64_t t_comp_stride, double kF, double beta,
+                                         double lambda, const int32_t *d_bin, int32_t bin_base, uint32_t n_bin, const double *d_weight,
+                                         const double *coef, uint64_t seed, uint64_t sample_offset, uint32_t n_dim, uint32_t n_grid,
+                                         double *d_acc, double *d_acc2, double *d_hist, double *d_hist_bin, const fdg_matsubara *mz,
+                                         const fdg_weight_groups *wg, const fdg_observables *ob, int64_t n_sample, void *stream);
+
 /* Device workspace control: the interpreter keeps per-sample overflow slots in
  * an HBM panel owned by the handle; it is sized on first use for the number of
  * resident waves.  This releases it (and any loaded module). */
