@@ -50,6 +50,7 @@ EXPORTS = [
     "fdg_matsubara_phase", "fdg_accumulate_device_matsubara", "fdg_mc_accumulate_device_matsubara",
     "fdg_vegas_sample_device_grouped", "fdg_accumulate_device_grouped", "fdg_mc_accumulate_device_grouped",
     "fdg_accumulate_device_observables", "fdg_mc_accumulate_device_observables",
+    "fdg_vegas_sample_device_strat", "fdg_accumulate_device_strat", "fdg_mc_accumulate_device_strat", "fdg_strat_allocate",
 ]
 FDG_BIN_MAX = 16384     # fdg_accumulate_device_binned: largest n_bin
 FDG_VEGAS_DIM_MAX, FDG_VEGAS_GRID_MAX = 64, 1024     # the VEGAS map: most variables, most cells per variable
@@ -58,6 +59,7 @@ FDG_VEGAS_POLAR_MAX = 21  # fdg_vegas_sample_device_polar: most groups of polar 
 FDG_MATSUBARA_FREQ_MAX = 64  # fdg_[mc_]accumulate_device_matsubara: most frequencies per call
 FDG_WEIGHT_GROUP_MAX = 8  # fdg_weight_groups: most groups of roots with their own integration variables
 FDG_OBS_MAX = 16  # fdg_observables: most linear combinations of the roots per call
+FDG_STRAT_CUBE_MAX = 1 << 20  # the stratified calls: most hypercubes
 COMM_ID_BYTES = 128
 
 
@@ -267,6 +269,12 @@ def lib():
     L.fdg_mc_accumulate_device_observables.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, C.c_int32,
                                                        u32, dp, C.c_void_p, u64, u64, u32, u32, dp, dp, dp, dp, C.c_void_p, C.c_void_p,
                                                        C.c_void_p, i64, vp]
+    L.fdg_vegas_sample_device_strat.argtypes = [dp, u32, u32, C.c_void_p, C.c_void_p, dp, u64, u64, dp, i64, i64, dp, dp, dp, i64, vp]
+    L.fdg_accumulate_device_strat.argtypes = [vp, dp, i64, i64, i64, dp, C.c_void_p, u64, u64, u32, u32, dp, dp, dp, C.c_void_p, dp, dp, dp,
+                                              i64, vp]
+    L.fdg_mc_accumulate_device_strat.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, C.c_void_p, u64, u64,
+                                                 u32, u32, dp, dp, dp, C.c_void_p, dp, dp, dp, i64, vp]
+    L.fdg_strat_allocate.argtypes = [C.c_void_p, C.c_void_p, u32, u32, C.c_void_p, u32, i64, C.c_double, C.c_void_p]
     L.fdg_powi.argtypes = [C.c_double, C.c_int32]
     L.fdg_powi.restype = C.c_double
     _lib = L
@@ -591,6 +599,24 @@ class GraphHandle:
                                                          None if groups is None else C.addressof(groups),
                                                          None if obs is None else C.addressof(obs), B, stream))
 
+    # the stratified accumulate step: the _vegas calls plus the training cells by the stratified formula (d_cube: the sampler's
+    # hypercubes) and the per-hypercube moments d_cube_sum, d_cube_sum2 [H, n_root + 1]; strat: host sequence of n_dim counts (fdg.h)
+    def accumulate_device_strat(self, d_leaf: int, ss: int, ls: int, lts: int, d_weight: int, coef, seed: int, sample_offset: int, n_dim: int,
+                                n_grid: int, d_acc: int, d_acc2: int, d_hist: int, strat, d_cube: int, d_cube_sum: int, d_cube_sum2: int,
+                                B: int, stream: int = 0):
+        c, sv = self._coef(coef), _strat_array(strat, n_dim)
+        check(lib().fdg_accumulate_device_strat(self._h, d_leaf or None, ss, ls, lts, d_weight or None, None if c is None else c.ctypes.data,
+                                                seed, sample_offset, n_dim, n_grid, d_acc or None, d_acc2 or None, d_hist or None,
+                                                sv.ctypes.data, d_cube or None, d_cube_sum or None, d_cube_sum2 or None, B, stream))
+
+    def mc_accumulate_device_strat(self, d_K, ks, kc, d_T, ts, tc, kF, beta, lam, d_weight, coef, seed, sample_offset, n_dim, n_grid, d_acc,
+                                   d_acc2, d_hist, strat, d_cube, d_cube_sum, d_cube_sum2, B, stream=0):
+        c, sv = self._coef(coef), _strat_array(strat, n_dim)
+        check(lib().fdg_mc_accumulate_device_strat(self._h, d_K or None, ks, kc, d_T or None, ts, tc, kF, beta, lam, d_weight or None,
+                                                   None if c is None else c.ctypes.data, seed, sample_offset, n_dim, n_grid,
+                                                   d_acc or None, d_acc2 or None, d_hist or None, sv.ctypes.data, d_cube or None,
+                                                   d_cube_sum or None, d_cube_sum2 or None, B, stream))
+
     def _coef(self, coef):
         if coef is None:
             return None
@@ -653,6 +679,137 @@ def vegas_sample_device(d_grid: int, n_dim: int, n_grid: int, col, seed: int, sa
             raise ValueError("col must name one column per variable")
     check(lib().fdg_vegas_sample_device(d_grid or None, n_dim, n_grid, None if c is None else c.ctypes.data, seed, sample_offset,
                                         d_x or None, xs, xc, d_jac or None, d_cell or None, B, stream))
+
+
+def _strat_array(strat, n_dim: int) -> np.ndarray:
+    sv = np.ascontiguousarray(strat, dtype=np.uint32)
+    if sv.shape != (n_dim,):
+        raise ValueError("strat must hold one count per variable")
+    return sv
+
+
+def vegas_sample_device_strat(d_grid: int, n_dim: int, n_grid: int, col, strat, d_start: int, seed: int, sample_offset: int, d_x: int,
+                              xs: int, xc: int, d_jac: int, d_cube: int, d_cell: int, B: int, stream: int = 0):
+    """fdg_vegas_sample_device_strat: :func:`vegas_sample_device` inside the strata of the sample's hypercube.  ``strat``: host sequence
+    of ``n_dim`` counts; ``d_start``: device int64 ``[H + 1]`` prefix sums of the samples per hypercube (global indices);
+    ``d_cube[b]`` (int32) receives the hypercube, and ``jac`` carries ``n_total / (H n_h)``."""
+    c = None
+    if col is not None:
+        c = np.ascontiguousarray(col, dtype=np.uint32)
+        if c.shape != (n_dim,):
+            raise ValueError("col must name one column per variable")
+    sv = _strat_array(strat, n_dim)
+    check(lib().fdg_vegas_sample_device_strat(d_grid or None, n_dim, n_grid, None if c is None else c.ctypes.data, sv.ctypes.data,
+                                              d_start or None, seed, sample_offset, d_x or None, xs, xc, d_jac or None, d_cube or None,
+                                              d_cell or None, B, stream))
+
+
+def strat_allocate(cube_sum, cube_sum2, col: int, start_old, H: int, n_total: int, beta: float = 0.75) -> np.ndarray:
+    """fdg_strat_allocate: the prefix sums ``start_new [H + 1]`` (int64) of the next iteration's samples per hypercube, from column
+    ``col`` of the per-hypercube moments ``[H, ld]`` of an iteration drawn with ``start_old`` (None: no history, the uniform
+    allocation; the moments are then not read).  Every hypercube receives at least two samples."""
+    out = np.zeros(int(H) + 1, dtype=np.int64)
+    if start_old is None:
+        check(lib().fdg_strat_allocate(None, None, 0, 0, None, H, n_total, float(beta), out.ctypes.data))
+        return out
+    s1 = np.ascontiguousarray(cube_sum, dtype=np.float64)
+    s2 = np.ascontiguousarray(cube_sum2, dtype=np.float64)
+    so = np.ascontiguousarray(start_old, dtype=np.int64)
+    if s1.ndim != 2 or s1.shape != s2.shape or s1.shape[0] != H or so.shape != (H + 1,):
+        raise ValueError("the moments must be [H, ld] and start_old [H + 1]")
+    check(lib().fdg_strat_allocate(s1.ctypes.data, s2.ctypes.data, s1.shape[1], col, so.ctypes.data, H, n_total, float(beta), out.ctypes.data))
+    return out
+
+
+def strat_allocate_reference(cube_sum, cube_sum2, col: int, start_old, H: int, n_total: int, beta: float = 0.75) -> np.ndarray:
+    """Steps 1-5 of fdg_strat_allocate (include/fdg.h) restated in Python, valid arguments taken for granted: the same fp64
+    operations in the same order (``math.pow`` is the C library's ``pow``), so the result is the library's exactly."""
+    import math
+    H, n_total = int(H), int(n_total)
+    spare = n_total - 2 * H
+    dh, S = [0.0] * H, 0.0
+    if start_old is not None:
+        so = np.asarray(start_old, dtype=np.int64)
+        n_old = float(so[H])
+        for h in range(H):
+            nd = float(so[h + 1] - so[h])
+            s1, s2 = float(cube_sum[h][col]), float(cube_sum2[h][col])
+            fac = n_old / (float(H) * nd)
+            var = max(0.0, (s2 - s1 * s1 / nd) / (nd - 1.0)) / (fac * fac)
+            dh[h] = 0.0 if var == 0.0 else math.pow(var, beta / 2.0)
+            S = S + dh[h] if h else dh[h]
+    if start_old is None or not S > 0.0 or not math.isfinite(S) or beta == 0.0:
+        cnt = [2 + spare // H] * H
+    else:
+        cnt = [2 + int(math.floor(float(spare) * (dh[h] / S))) for h in range(H)]
+    have, h = sum(cnt), 0
+    while have < n_total:
+        cnt[h] += 1
+        have += 1
+        h = (h + 1) % H
+    h = H
+    while have > n_total:
+        h = h - 1 if h else H - 1
+        if cnt[h] > 2:
+            cnt[h] -= 1
+            have -= 1
+    return np.concatenate([[0], np.cumsum(np.array(cnt, dtype=np.int64))]).astype(np.int64)
+
+
+def strat_reference(grid, strat, start, u, sample_offset: int = 0, roots=None, weight=None, coef=None, exists=None, beta=None):
+    """The stratified calls restated in numpy (include/fdg.h, "Adaptive stratified sampling"), in the device's fp64 order, so that the
+    sampler compares bit for bit.  ``grid [D, G + 1]`` the map, ``strat [D]``, ``start [H + 1]`` the prefix sums in global indices,
+    ``u [B, D]`` the uniforms of the counters ``(sample_offset + b, d)``.  Returns a dict: ``cube [B]``, ``x [B, D]``, ``jac [B]``,
+    ``cell [B, D]``; with ``roots [B, R]`` also ``cube_sum`` / ``cube_sum2 [H, R + 1]`` of ``t_k = weight * root_k`` (``weight``
+    None: the roots themselves) and, in column ``R``, of ``weight * (left fold of coef_k * root_k over the roots that exist)``
+    (``exists``: bool per root, None: all) -- plain numpy sums, so these compare within rounding; with ``beta`` also ``start_new``,
+    :func:`strat_allocate_reference` of column ``R``."""
+    grid = np.asarray(grid, dtype=np.float64)
+    sv = np.asarray(strat, dtype=np.int64)
+    start = np.asarray(start, dtype=np.int64)
+    u = np.asarray(u, dtype=np.float64)
+    B, D = u.shape
+    G, H = grid.shape[1] - 1, int(np.prod(sv))
+    i = np.int64(sample_offset) + np.arange(B, dtype=np.int64)
+    cube = np.clip(np.searchsorted(start, i, side="right") - 1, 0, H - 1)
+    n_h = (start[cube + 1] - start[cube]).astype(np.float64)
+    rem = cube.copy()
+    x, cell = np.empty((B, D)), np.empty((B, D), dtype=np.int64)
+    jac = None
+    for d in range(D):
+        s_d = rem % sv[d]
+        rem = rem // sv[d]
+        v = (s_d.astype(np.float64) + u[:, d]) / np.float64(sv[d])
+        y = v * np.float64(G)
+        c = np.minimum(y.astype(np.int64), G - 1)
+        lo = grid[d, c]
+        wd = grid[d, c + 1] - lo
+        x[:, d] = lo + (y - c.astype(np.float64)) * wd
+        f = np.float64(G) * wd
+        jac = f if jac is None else jac * f
+        cell[:, d] = c
+    jac = jac * (np.float64(start[H]) / (np.float64(H) * n_h))
+    out = {"cube": cube.astype(np.int32), "x": x, "jac": jac, "cell": cell}
+    if roots is not None:
+        roots = np.asarray(roots, dtype=np.float64)
+        R = roots.shape[1]
+        live = [k for k in range(R) if exists is None or exists[k]]
+        s1, s2 = np.zeros((H, R + 1)), np.zeros((H, R + 1))
+        comb = None
+        for k in live:
+            term = roots[:, k] if coef is None else coef[k] * roots[:, k]
+            comb = term if comb is None else comb + term
+            t = roots[:, k] if weight is None else weight * roots[:, k]
+            s1[:, k] = np.bincount(cube, weights=t, minlength=H)
+            s2[:, k] = np.bincount(cube, weights=t * t, minlength=H)
+        if comb is not None:
+            t = comb if weight is None else weight * comb
+            s1[:, R] = np.bincount(cube, weights=t, minlength=H)
+            s2[:, R] = np.bincount(cube, weights=t * t, minlength=H)
+        out["cube_sum"], out["cube_sum2"] = s1, s2
+        if beta is not None:
+            out["start_new"] = strat_allocate_reference(s1, s2, R, start, H, int(start[H]), beta)
+    return out
 
 
 def vegas_sample_device_discrete(d_grid: int, n_dim: int, n_grid: int, col, d_cdf: int, n_bin: int, bin_base: int, d_ext: int, ext_col,

@@ -50,6 +50,12 @@
 // forms up to FDG_OBS_MAX linear combinations o_m of the weighted roots per sample and sums o_m and the products o_a o_c per bin: the
 // first moment and the covariance of sums, differences and series of roots, which the per-root acc2 cannot give because all roots
 // share their samples.  A kernel of its own: every instance above is the code it was.
+//
+// Adaptive stratified sampling (fdg_vegas_sample_device_strat, fdg_[mc_]accumulate_device_strat, fdg_strat_allocate): the unit cube of
+// the map's coordinates is cut into H hypercubes whose samples are contiguous; the sampler finds a sample's hypercube by a binary
+// search in the prefix sums and draws inside its strata; the training pass carries a STRAT flag that recomputes the cell by the same
+// formula; one more pass per chunk (fdg_strat_partials, fdg_strat_stitch below) sums w root_k and its square per hypercube, runs of
+// equal hypercubes inside a wave by the segmented scan above, runs that cross waves, tiles or chunks level by level from edge records.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -448,6 +454,18 @@ __device__ __forceinline__ uint32_t vegas_cell(uint64_t sample, uint32_t d, uint
   return min((uint32_t)(int)y, G - 1u);
 }
 
+// The strata of the stratified calls (a kernel argument, by value): n[d] strata of variable d, div[d] = n[0] * .. * n[d - 1] (the digit
+// of hypercube h in variable d is h / div[d] % n[d]; 1 and 1 past n_dim), H their product.
+struct VegasStrat { uint32_t n[FDG_VEGAS_DIM_MAX], div[FDG_VEGAS_DIM_MAX], H; };
+
+// vegas_cell inside stratum s of ns: v = (s + u) / ns in the place of u.  (0 + u) / 1 = u exactly: one stratum is vegas_cell.
+__device__ __forceinline__ uint32_t vegas_cell_strat(uint64_t sample, uint32_t d, uint64_t seed, uint32_t G, uint32_t s, uint32_t ns, double &y) {
+  const double u = fdg_philox_u53(sample, d, seed);
+  const double v = ((double)s + u) / (double)ns;
+  y = v * (double)G;
+  return min((uint32_t)(int)y, G - 1u);
+}
+
 struct VegasCols { uint32_t c[FDG_VEGAS_DIM_MAX]; };   // the column of x each variable is written to (a kernel argument, by value)
 
 // The continuous variables of sample b, in order: x and the cell of each, and the jacobian (a left fold over them), returned.
@@ -484,6 +502,43 @@ fdg_vegas_sample(const double *__restrict__ grid, uint32_t D, uint32_t G, VegasC
   for (long b = blockIdx.x * 256L + threadIdx.x; b < n; b += (long)gridDim.x * 256L) {
     const double jb = vegas_draw(grid, D, G, col, seed, off, x, xs, xc, cell, n, b);
     jac[b] = jb;
+  }
+}
+
+// The stratified sampler (fdg_vegas_sample_device_strat): one lane per sample.  The lane finds its hypercube h by a binary search in
+// start[0 .. H] (at most 20 steps; the table is at most 8 MiB and stays in L2), peels h's digits variable by variable and draws every
+// variable inside its stratum; the rest of a variable is vegas_draw's own arithmetic.  jac = jac_map * (n_total / (H * n_h)).
+__global__ void __launch_bounds__(256)
+fdg_vegas_sample_strat(const double *__restrict__ grid, uint32_t D, uint32_t G, VegasCols col, VegasStrat sv, const int64_t *__restrict__ start,
+                       uint64_t seed, uint64_t off, double *__restrict__ x, long xs, long xc, double *__restrict__ jac,
+                       int32_t *__restrict__ cube, int32_t *__restrict__ cell, long n) {
+  const uint32_t H = sv.H;
+  const int64_t n_total = start[H];
+  for (long b = blockIdx.x * 256L + threadIdx.x; b < n; b += (long)gridDim.x * 256L) {
+    const int64_t i = (int64_t)(off + (uint64_t)b);
+    uint32_t lo = 0, hi = H - 1u;                         // h in [lo, hi]: start[lo] <= i
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi + 1u) >> 1;
+      if (start[mid] <= i) lo = mid; else hi = mid - 1u;
+    }
+    const int64_t n_h = start[lo + 1u] - start[lo];
+    cube[b] = (int32_t)lo;
+    uint32_t rem = lo;
+    double jb = 0.0;
+    for (uint32_t d = 0; d < D; ++d) {
+      const uint32_t ns = sv.n[d], sd = rem % ns;
+      rem /= ns;
+      double y;
+      const uint32_t c = vegas_cell_strat(off + (uint64_t)b, d, seed, G, sd, ns, y);
+      const double *e = grid + (size_t)d * (G + 1u) + c;
+      const double el = e[0], wd = e[1] - el, fr = y - (double)c;
+      x[b * xs + (long)col.c[d] * xc] = el + fr * wd;
+      const double f = (double)G * wd;
+      jb = d ? jb * f : f;
+      if (cell) cell[(size_t)d * (size_t)n + (size_t)b] = (int32_t)c;
+    }
+    const double fac = (double)n_total / ((double)H * (double)n_h);
+    jac[b] = jb * fac;
   }
 }
 
@@ -665,12 +720,16 @@ struct VegasVarGroups { uint8_t g[FDG_VEGAS_DIM_MAX]; };
 // [2][kBinWaves][NG][64] (the lanes innermost: a wave reads one group's 64 words at unit stride); a walking wave folds the q_g of its
 // variable's groups (vgm, ascending g) into v before the sort, and skips a variable that no group with a root owns.  The marker
 // survives the fold: the q_g of a lane are all -1 or all squares.
-template <int BINNED, bool GRP = false>
+// STRAT (the stratified calls): the cell is vegas_cell_strat's, the stratum the digit of cube[b] in the variable; a sample whose
+// hypercube lies outside [0, H) is selected away like a lane past n.  Nothing else differs, and with one stratum per variable and
+// cube = 0 every key is the unstratified instance's.
+template <int BINNED, bool GRP = false, bool STRAT = false>
 __global__ void __launch_bounds__(256)
 fdg_vegas_partials(const double *__restrict__ root, long ld, long n, const double *__restrict__ weight, const uint32_t *__restrict__ kidx,
                    const double *__restrict__ coef, uint32_t n_live, uint64_t seed, uint64_t off, uint32_t D, uint32_t G, uint32_t DS,
                    uint32_t n_slice, long seg_tiles, double *__restrict__ partial, int first, const int32_t *__restrict__ bins,
-                   int32_t bin_base, uint32_t n_bin, const uint32_t *__restrict__ gstart, uint32_t NG, long wstride, VegasVarGroups vgm) {
+                   int32_t bin_base, uint32_t n_bin, const uint32_t *__restrict__ gstart, uint32_t NG, long wstride, VegasVarGroups vgm,
+                   const int32_t *__restrict__ cube, VegasStrat sv) {
   extern __shared__ double hist[];                        // [DS][G], then v of the round's tiles [2][kBinWaves][64] (GRP: x NG)
   const uint32_t vtile = GRP ? NG * 64u : 64u;            // words of one tile in the exchange buffer
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -709,6 +768,8 @@ fdg_vegas_partials(const double *__restrict__ root, long ld, long n, const doubl
       if (t >= t1) break;
       const double *vb = vbuf + ((r & 1) * kBinWaves + tt) * vtile + lane;
       double v = GRP ? 0.0 : vb[0];
+      uint32_t hc = 0;                                     // STRAT: this lane's hypercube (index clamped into the chunk)
+      if constexpr (STRAT) hc = (uint32_t)cube[(size_t)min(b, n - 1)];
       for (uint32_t dd = wave; dd < dn; dd += kBinWaves) {
         if constexpr (GRP) {
           const uint32_t owners = vgm.g[d0 + dd];
@@ -722,8 +783,10 @@ fdg_vegas_partials(const double *__restrict__ root, long ld, long n, const doubl
             }
         }
         double y;
-        const uint32_t c = vegas_cell(off + (uint64_t)b, d0 + dd, seed, G, y);
-        uint32_t key = (b < n && !(BINNED && v < 0.0)) ? (c << 6) | lane : kKeyInvalid | lane;
+        uint32_t c;
+        if constexpr (STRAT) c = vegas_cell_strat(off + (uint64_t)b, d0 + dd, seed, G, hc / sv.div[d0 + dd] % sv.n[d0 + dd], sv.n[d0 + dd], y);
+        else c = vegas_cell(off + (uint64_t)b, d0 + dd, seed, G, y);
+        uint32_t key = (b < n && !(STRAT && hc >= sv.H) && !(BINNED && v < 0.0)) ? (c << 6) | lane : kKeyInvalid | lane;
         const uint64_t valid = __ballot(key < kKeyInvalid);
         if (!valid) continue;
         const uint32_t src = wave_sort_keys(key, lane, valid);
@@ -971,6 +1034,140 @@ fdg_matsubara_partials(const double *__restrict__ root, long ld, long n, const i
   }
 }
 
+// ---- Per-hypercube moments of the stratified calls (include/fdg.h: fdg_[mc_]accumulate_device_strat) ----
+// sum[h][k] += t_k and sum2[h][k] += t_k t_k over the samples of hypercube h, t_k = w root_k for k < R and t_R = w (c_0 r_0 + ...), the
+// training pass's term.  The keys (cube[b]) are non-decreasing along the samples, so nothing is sorted and nothing is kept in LDS:
+//  * One wave per 64-sample tile and group of kStratCols columns (blockIdx.y): 2 kStratCols values per lane in registers, t and t t.
+//    A lane that adds nothing (past n, hypercube out of range) carries 0.0, selected, and the key of the nearest valid lane below it
+//    (above it where there is none), so that it never splits a run; wave_runs' logic on the filled keys and the binned pass's
+//    segmented suffix scan leave every run of equal keys summed in its first lane.
+//  * A run that touches neither end of the wave holds ALL samples of its hypercube (the keys are monotone): its head adds the sums
+//    into sum / sum2, the only writer of those words in the whole call.
+//  * The run at lane 0 and the run at lane 63 may go on in the neighbouring tiles: they leave the wave as two edge records
+//    (key, values) in slots 2 w and 2 w + 1 of the next level; a wave that is one run leaves it in the first slot and the same key
+//    with zeros in the second.  fdg_strat_stitch treats the records of a level as this kernel treats samples, 64 slots per wave:
+//    interior runs are written, edge runs go up, and every level is 32 times shorter.  The level that fits one wave leaves its two
+//    edge runs as the CHUNK's records; after the last chunk the chunks' records go through the same levels, and the last wave
+//    (final) writes every run.  A hypercube of 10^8 samples is thus summed by a tree of depth 6 + 6 levels, never by one lane.
+// The shape of every level follows from the chunk sizes alone -- (n_sample, n_root, FDG_ROOT_SCRATCH_MB) -- and every word of sum /
+// sum2 is written by exactly one lane of one launch: no atomics, bitwise repeatable.
+// Records of a level: keys [slot] (int32, -1: nothing), values [column][slot] with the columns 0 .. R of the first moment, then
+// R + 1 .. 2 R + 1 of the second.  wmask: bit j set = the column of value j is written to sum / sum2 (a root that exists).
+constexpr uint32_t kStratCols = 8, kStratVals = 2 * kStratCols;
+
+__device__ __forceinline__ uint32_t strat_wmask(uint32_t k0, uint32_t R, const uint8_t *__restrict__ live, uint32_t n_live) {
+  uint32_t m = 0;
+  for (uint32_t j = 0; j < kStratVals; ++j) {
+    const uint32_t kk = k0 + (j & (kStratCols - 1u));
+    const bool on = kk < R ? (!live || live[kk]) : (kk == R && n_live != 0);
+    m |= on ? 1u << j : 0u;
+  }
+  return m;
+}
+
+// The shared end of both kernels: s[] = this lane's values (0.0 where !ok), key its hypercube; slot = the wave's first output slot.
+__device__ __forceinline__ void strat_wave_reduce(int32_t key, bool ok, uint32_t lane, double (&s)[kStratVals], uint32_t k0, uint32_t C1,
+                                                  uint32_t wmask, double *__restrict__ sum, double *__restrict__ sum2, bool final,
+                                                  int32_t *__restrict__ rkey, double *__restrict__ rval, long rstride, long slot) {
+  const bool wkey = blockIdx.y == 0;                      // every column group sees the same keys: the first one records them
+  const uint64_t valid = __ballot(ok);
+  if (!valid) {
+    if (!final && wkey && lane < 2) rkey[slot + lane] = -1;
+    return;
+  }
+  const uint64_t upto = valid & (lane == 63 ? ~0ull : ((2ull << lane) - 1ull));
+  const int src = upto ? 63 - __builtin_clzll(upto) : __builtin_ctzll(valid);
+  const int32_t kf = __shfl(key, src);
+  const int32_t k_prev = __shfl_up(kf, 1), k_next = __shfl_down(kf, 1);
+  const bool head = lane == 0 || k_prev != kf;
+  const uint64_t tails = __ballot(lane == 63 || k_next != kf);
+  const uint32_t end = (uint32_t)__builtin_ctzll(tails & (~0ull << lane));
+  for (uint32_t d = 1; d < 64; d <<= 1) {                 // segmented suffix scan, as in fdg_binned_partials
+    const bool take = lane + d <= end;
+    if (!__ballot(take)) break;
+#pragma unroll
+    for (uint32_t j = 0; j < kStratVals; ++j) {
+      const double up = __shfl_down(s[j], d);
+      if (take) s[j] = s[j] + up;
+    }
+  }
+  if (!head) return;
+  const bool at0 = lane == 0, at63 = end == 63;
+  if (final || (!at0 && !at63)) {
+#pragma unroll
+    for (uint32_t j = 0; j < kStratVals; ++j)
+      if ((wmask >> j) & 1u) {
+        double *o = (j < kStratCols ? sum : sum2) + (size_t)kf * C1 + k0 + (j & (kStratCols - 1u));
+        *o = *o + s[j];
+      }
+    return;
+  }
+  const long at = slot + (at0 ? 0 : 1);
+  if (wkey) rkey[at] = kf;
+  if (wkey && at0 && at63) rkey[at + 1] = kf;
+#pragma unroll
+  for (uint32_t j = 0; j < kStratVals; ++j) {
+    const uint32_t kk = k0 + (j & (kStratCols - 1u));
+    if (kk >= C1) continue;
+    double *o = rval + (size_t)((j < kStratCols ? 0u : C1) + kk) * (size_t)rstride + (size_t)at;
+    o[0] = s[j];
+    if (at0 && at63) o[1] = 0.0;
+  }
+}
+
+// Level 0: the samples of a chunk (root k of sample b at root[k * ld + b], b < n).  The scratch columns are read for the last time
+// in the chunk: non-temporal loads.
+__global__ void __launch_bounds__(256)
+fdg_strat_partials(const double *__restrict__ root, long ld, long n, const int32_t *__restrict__ cube, uint32_t H,
+                   const double *__restrict__ weight, const uint32_t *__restrict__ kidx, const double *__restrict__ coef, uint32_t n_live,
+                   uint32_t R, const uint8_t *__restrict__ live, double *__restrict__ sum, double *__restrict__ sum2,
+                   int32_t *__restrict__ rkey, double *__restrict__ rval, long rstride, long slot_base) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const long t = (long)blockIdx.x * kBinWaves + wave;
+  if (t >= (n + 63) / 64) return;                          // (whole waves leave; the kernel has no barrier)
+  const uint32_t k0 = blockIdx.y * kStratCols, C1 = R + 1u;
+  const long b = t * 64 + lane;
+  const size_t bb = (size_t)min(b, n - 1);                 // clamped into the chunk; what it loads is used only where `ok`
+  const int32_t h = cube[bb];
+  const bool ok = b < n && (uint32_t)h < H;
+  const double w = weight ? weight[bb] : 1.0;
+  double s[kStratVals];
+#pragma unroll
+  for (uint32_t i = 0; i < kStratCols; ++i) {
+    const uint32_t kk = k0 + i;
+    double tk = 0.0;
+    if (kk < R) tk = w * __builtin_nontemporal_load(root + (size_t)kk * (size_t)ld + bb);
+    else if (kk == R) tk = vegas_term(root, ld, bb, weight, kidx, coef, n_live);
+    s[i] = ok ? tk : 0.0;                                  // selected, never multiplied by 0
+    s[kStratCols + i] = ok ? tk * tk : 0.0;
+  }
+  strat_wave_reduce(h, ok, lane, s, k0, C1, strat_wmask(k0, R, live, n_live), sum, sum2, false, rkey, rval, rstride, slot_base + 2 * t);
+}
+
+// Levels 1 ..: the n_slot records of the level below.
+__global__ void __launch_bounds__(256)
+fdg_strat_stitch(const int32_t *__restrict__ ikey, const double *__restrict__ ival, long istride, long n_slot, uint32_t R,
+                 const uint8_t *__restrict__ live, uint32_t n_live, double *__restrict__ sum, double *__restrict__ sum2, int final,
+                 int32_t *__restrict__ rkey, double *__restrict__ rval, long rstride, long slot_base) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const long wv = (long)blockIdx.x * kBinWaves + wave;
+  if (wv >= (n_slot + 63) / 64) return;
+  const uint32_t k0 = blockIdx.y * kStratCols, C1 = R + 1u;
+  const long i = wv * 64 + lane;
+  const size_t ii = (size_t)min(i, n_slot - 1);
+  const int32_t key = ikey[ii];
+  const bool ok = i < n_slot && key >= 0;
+  double s[kStratVals];
+#pragma unroll
+  for (uint32_t j = 0; j < kStratVals; ++j) {
+    const uint32_t kk = min(k0 + (j & (kStratCols - 1u)), R);      // clamped: a column past R is never written
+    const double v = ival[(size_t)((j < kStratCols ? 0u : C1) + kk) * (size_t)istride + ii];
+    s[j] = ok ? v : 0.0;
+  }
+  strat_wave_reduce(key, ok, lane, s, k0, C1, strat_wmask(k0, R, live, n_live), sum, sum2, final != 0, rkey, rval, rstride,
+                    slot_base + 2 * wv);
+}
+
 // The training pass of one call, as the entry point was given it (aggregate-initialised there, in this order).
 struct VegasRun {
   const double *coef = nullptr;      // host, [R] or null
@@ -994,6 +1191,13 @@ struct ObsRun {
   const fdg_observables *ob = nullptr;
 };
 
+// The stratification of one call (fdg_[mc_]accumulate_device_strat), as the entry point was given it.
+struct StratRun {
+  const uint32_t *strat = nullptr;   // host, [n_dim]
+  const int32_t *d_cube = nullptr;
+  double *d_sum = nullptr, *d_sum2 = nullptr;
+};
+
 // One accumulate call, as the entry point was given it (aggregate-initialised there, in this order): what the checks, the shared body
 // and run_binned read.
 struct BinnedCall {
@@ -1008,6 +1212,7 @@ struct BinnedCall {
   const MatsubaraRun *mz = nullptr;  // the projection calls: the projection pass runs too; d_acc and d_acc2 may then both be null
   const fdg_weight_groups *wg = nullptr;   // the grouped calls: d_weight holds one column per group
   const ObsRun *ob = nullptr;        // the observables calls: the observables pass runs too; d_acc and d_acc2 may then both be null
+  const StratRun *sr = nullptr;      // the stratified calls: the training pass reads the hypercubes, the per-hypercube pass runs too
 };
 
 constexpr size_t page_up(size_t bytes) { return (bytes + 4095) & ~(size_t)4095; }
@@ -1228,6 +1433,54 @@ ObsTables obs_tables(const fdg_graph *g, const ObsPlan &q, const fdg_observables
   return t;
 }
 
+// How the per-hypercube pass is cut: the record buffers of the levels (slots: two per wave of the level below).  A chunk's levels
+// alternate between a and b, the chunks' own records (two per chunk) lie in c and go through a and b again after the last chunk.
+// A function of (n_sample, n_root, FDG_ROOT_SCRATCH_MB) only.
+struct StratPlan {
+  uint32_t H = 1, n_grp = 1, V2 = 2;
+  long n_chunk = 1, cap_a = 2, cap_b = 2, cap_c = 2;
+  size_t bytes = 0;
+  static size_t buf_bytes(long cap, uint32_t V2) { return page_up((size_t)cap * 4u) + page_up((size_t)cap * V2 * 8u); }
+};
+
+StratPlan strat_plan(const BinnedPlan &p, int64_t B, uint32_t R, uint32_t H) {
+  StratPlan q;
+  q.H = H;
+  q.V2 = 2u * (R + 1u);
+  q.n_grp = (R + 1u + kStratCols - 1u) / kStratCols;
+  q.n_chunk = ((long)B + p.Bc - 1) / p.Bc;
+  q.cap_c = 2 * q.n_chunk;
+  q.cap_a = std::max(2 * ((p.Bc + 63) / 64), 2 * ((q.cap_c + 63) / 64));
+  q.cap_b = 2 * ((q.cap_a + 63) / 64);
+  q.bytes = StratPlan::buf_bytes(q.cap_a, q.V2) + StratPlan::buf_bytes(q.cap_b, q.V2) + StratPlan::buf_bytes(q.cap_c, q.V2);
+  return q;
+}
+
+// The strata of a call as the kernels take them (strat checked: every entry >= 1, the product within FDG_STRAT_CUBE_MAX).
+VegasStrat vegas_strat(const uint32_t *strat, uint32_t n_dim) {
+  VegasStrat sv;
+  uint32_t H = 1;
+  for (uint32_t d = 0; d < FDG_VEGAS_DIM_MAX; ++d) {
+    sv.n[d] = d < n_dim ? strat[d] : 1u;
+    sv.div[d] = H;
+    H *= sv.n[d];
+  }
+  sv.H = H;
+  return sv;
+}
+
+// The stratified calls' own checks, after the map's: H = prod strat[d] in *H.
+int check_strat(const uint32_t *strat, uint32_t n_dim, uint32_t *H) {
+  uint64_t h = 1;
+  for (uint32_t d = 0; d < n_dim; ++d) {
+    if (strat[d] == 0) { set_error("strat[d] == 0"); return FDG_E_INVALID; }
+    h *= strat[d];
+    if (h > FDG_STRAT_CUBE_MAX) { set_error("prod strat[d] > FDG_STRAT_CUBE_MAX"); return FDG_E_UNSUPPORTED; }
+  }
+  *H = (uint32_t)h;
+  return FDG_OK;
+}
+
 using MatsubaraKernel = void (*)(const double *, long, long, const int32_t *, int32_t, uint32_t, const double *, const double *, long, long,
                                  const double *, double, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, long, double *, int,
                                  const uint32_t *, long);
@@ -1281,7 +1534,8 @@ void raise_lds_limits() {
                                                         {(const void *)fdg_vegas_partials<0>, train},
                                                         {(const void *)fdg_vegas_partials<1>, train},
                                                         {(const void *)fdg_vegas_partials<0, true>, train_grp},
-                                                        {(const void *)fdg_vegas_partials<1, true>, train_grp}};
+                                                        {(const void *)fdg_vegas_partials<1, true>, train_grp},
+                                                        {(const void *)fdg_vegas_partials<0, false, true>, train}};
     MatsubaraPlan mq;
     for (int i = 0; i < 4; ++i) {                          // hsplit, then kw = 1, 2, 4
       mq.hsplit = i == 0;
@@ -1343,6 +1597,23 @@ int check_vegas(const fdg_graph *g, const BinnedCall &c) {
     set_error("d_hist_bin is the same buffer as d_acc, d_acc2 or d_hist"); return FDG_E_INVALID;
   }
   return check_vegas_map(v.D, v.G);
+}
+
+// ... and the stratified calls': the VEGAS calls' cases, then the strata and the per-hypercube arrays.
+int check_strat_call(const fdg_graph *g, const BinnedCall &c) {
+  const StratRun &s = *c.sr;
+  if (!s.strat || !s.d_cube || !s.d_sum || !s.d_sum2) { set_error("null strat, d_cube, d_cube_sum or d_cube_sum2"); return FDG_E_INVALID; }
+  int rc = check_vegas(g, c);
+  if (rc) return rc;
+  const double *out[5] = {s.d_sum, s.d_sum2, c.d_acc, c.d_acc2, c.vg->d_hist};
+  for (int a = 0; a < 2; ++a)
+    for (int b = a + 1; b < 5; ++b)
+      if (out[a] == out[b]) { set_error("d_cube_sum or d_cube_sum2 is the same buffer as another output"); return FDG_E_INVALID; }
+  uint32_t H;
+  rc = check_strat(s.strat, c.vg->D, &H);
+  if (rc) return rc;
+  if ((uint64_t)H * (g->prog.R + 1ull) > (1ull << 24)) { set_error("H * (n_root + 1) > 1 << 24"); return FDG_E_UNSUPPORTED; }
+  return FDG_OK;
 }
 
 // ... and the projection calls': the descriptor, then what the call asks for besides (moments: d_acc and d_acc2 together; training:
@@ -1467,7 +1738,15 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
     ot = obs_tables(g, op, *ob, wg);
     obs_bytes = op.slab_alloc + page_up(ot.d.size() * 8u) + page_up(ot.u.size() * 4u);
   }
-  int rc = ensure_root_scratch(g, proj_bytes + grp_bytes + obs_bytes);
+  // ... and the record buffers of the per-hypercube pass behind that
+  const StratRun *sr = c.sr;
+  StratPlan sp;
+  VegasStrat sv = {};
+  if (sr) {
+    sv = vegas_strat(sr->strat, vg->D);
+    sp = strat_plan(p, c.B, R, sv.H);
+  }
+  int rc = ensure_root_scratch(g, proj_bytes + grp_bytes + obs_bytes + sp.bytes);
   if (rc) return rc;
   double *roots = (double *)g->d_ws2, *partial = (double *)((char *)g->d_ws2 + root_bytes);
   const uint8_t *live = nullptr;
@@ -1559,6 +1838,31 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
     if (!ot.d.empty()) HIP_TRY(hipMemcpyAsync(d_odtab, ot.d.data(), ot.d.size() * 8u, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_outab, ot.u.data(), ot.u.size() * 4u, hipMemcpyHostToDevice, st));
   }
+  // the record buffers {keys, values, slots} a, b (the levels) and c (the chunks)
+  struct StratBuf { int32_t *key; double *val; long cap; } sa = {}, sb = {}, sc = {};
+  if (sr) {
+    char *at = (char *)g->d_ws2 + proj_bytes + grp_bytes + obs_bytes;
+    for (auto bc : {std::make_pair(&sa, sp.cap_a), std::make_pair(&sb, sp.cap_b), std::make_pair(&sc, sp.cap_c)}) {
+      *bc.first = {(int32_t *)at, (double *)(at + page_up((size_t)bc.second * 4u)), bc.second};
+      at += StratPlan::buf_bytes(bc.second, sp.V2);
+    }
+  }
+  // the levels above `in` (n_slot records): interior runs are written, edge runs go up until one wave is left; that wave writes
+  // everything (last) or leaves its two edge records in slots 2 c, 2 c + 1 of the chunks' buffer
+  auto strat_levels = [&](StratBuf in, long n_slot, bool last, long chunk) {
+    for (;;) {
+      const long nw = (n_slot + 63) / 64;
+      const bool top = nw == 1;
+      const StratBuf out = !top ? (in.key == sa.key ? sb : sa) : sc;
+      hipLaunchKernelGGL(fdg_strat_stitch, dim3((unsigned)((nw + kBinWaves - 1) / kBinWaves), sp.n_grp), dim3(256), 0, st, in.key, in.val,
+                         in.cap, n_slot, R, live, n_live, sr->d_sum, sr->d_sum2, (top && last) ? 1 : 0, out.key, out.val, out.cap,
+                         top ? 2 * chunk : 0L);
+      HIP_TRY(hipGetLastError());
+      if (top) return FDG_OK;
+      in = out;
+      n_slot = 2 * nw;
+    }
+  };
   const MatsubaraKernel mpass = matsubara_kernel(mp, grp_w);
   const PartialsKernel pass = partials_kernel(p, grp_w);
   const uint32_t n_grp = p.mode == kSplit ? 2 * p.n_slice : p.n_slice;
@@ -1590,12 +1894,26 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
     if (vg) {
       const double *cf = vg->coef ? d_coef : nullptr;
       // (the calls without a discrete variable carry no bin vector: null, base 0, one bin)
-      const auto tpass = grp_t ? (vg->binned ? fdg_vegas_partials<1, true> : fdg_vegas_partials<0, true>)
-                               : (vg->binned ? fdg_vegas_partials<1> : fdg_vegas_partials<0>);
+      const auto tpass = sr      ? fdg_vegas_partials<0, false, true>
+                         : grp_t ? (vg->binned ? fdg_vegas_partials<1, true> : fdg_vegas_partials<0, true>)
+                                 : (vg->binned ? fdg_vegas_partials<1> : fdg_vegas_partials<0>);
       hipLaunchKernelGGL(tpass, dim3(q.n_seg * q.n_slice), dim3(256), q.lds, st, roots, (long)p.Bc, n, w, d_kidx, cf, n_live, vg->seed,
                          vg->offset + (uint64_t)c0, vg->D, vg->G, q.ds, q.n_slice, (ntile + q.n_seg - 1) / q.n_seg, vpartial, first, bins,
-                         c.bin_base, n_bin, d_gstart, NG, wstride, vgm);
+                         c.bin_base, n_bin, d_gstart, NG, wstride, vgm, sr ? sr->d_cube + c0 : nullptr, sv);
       HIP_TRY(hipGetLastError());
+      if (sr) {
+        // the per-hypercube pass, the chunk's last reader of the roots: level 0 over the samples, then the levels over its records
+        const bool top = ntile == 1;
+        const StratBuf out = top ? sc : sa;
+        hipLaunchKernelGGL(fdg_strat_partials, dim3((unsigned)((ntile + kBinWaves - 1) / kBinWaves), sp.n_grp), dim3(256), 0, st, roots,
+                           (long)p.Bc, n, sr->d_cube + c0, sp.H, w, d_kidx, cf, n_live, R, live, sr->d_sum, sr->d_sum2, out.key, out.val,
+                           out.cap, top ? 2 * (c0 / p.Bc) : 0L);
+        HIP_TRY(hipGetLastError());
+        if (!top) {
+          rc = strat_levels(sa, 2 * ntile, false, c0 / p.Bc);
+          if (rc) return rc;
+        }
+      }
       if (vg->d_hist_bin) {
         hipLaunchKernelGGL(grp_t ? fdg_vegas_bin_partials<true> : fdg_vegas_bin_partials<false>, dim3(q.bin_seg), dim3(256),
                            (size_t)n_bin * 8u, st, roots, (long)p.Bc, n, bins, c.bin_base, n_bin, w, d_kidx, cf, n_live,
@@ -1630,6 +1948,8 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
   // (a variable that no group trains is not added to: the byte table stands in for the roots' mask, R = the histogram's size)
   if (!rc && vg) rc = reduce_partials(vpartial, q.n_seg, (long)vg->D * vg->G, d_hlive ? vg->D * vg->G : 1u, 64u, vg->d_hist, nullptr, d_hlive, st);
   if (!rc && vg && vg->d_hist_bin) rc = reduce_partials(bpartial, q.bin_seg, (long)n_bin, 1u, 64u, vg->d_hist_bin, nullptr, nullptr, st);
+  // the chunks' edge records through the same levels; the last wave writes every run
+  if (!rc && sr) rc = strat_levels(sc, 2 * sp.n_chunk, true, 0);
   return rc;
 }
 
@@ -1768,6 +2088,90 @@ int fdg_mc_accumulate_device_vegas_binned(fdg_graph *g, const double *d_K, int64
   const BinnedCall c{d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, stream, &vg};
   const int rc = check_vegas(g, c);
   return rc ? rc : accumulate_mc(g, d_K, ks, kc, d_T, ts, tc, kF, beta, lambda, c);
+}
+
+int fdg_accumulate_device_strat(fdg_graph *g, const double *d_leaf, int64_t ss, int64_t ls, int64_t lts, const double *d_weight,
+                                const double *coef, uint64_t seed, uint64_t sample_offset, uint32_t n_dim, uint32_t n_grid, double *d_acc,
+                                double *d_acc2, double *d_hist, const uint32_t *strat, const int32_t *d_cube, double *d_cube_sum,
+                                double *d_cube_sum2, int64_t B, void *stream) {
+  const VegasRun vg{coef, seed, sample_offset, n_dim, n_grid, d_hist, false, nullptr};
+  const StratRun sr{strat, d_cube, d_cube_sum, d_cube_sum2};
+  const BinnedCall c{nullptr, 0, 1, d_weight, d_acc, d_acc2, B, stream, &vg, nullptr, nullptr, nullptr, &sr};
+  const int rc = check_strat_call(g, c);
+  return rc ? rc : accumulate_leaf(g, d_leaf, ss, ls, lts, c);
+}
+
+int fdg_mc_accumulate_device_strat(fdg_graph *g, const double *d_K, int64_t ks, int64_t kc, const double *d_T, int64_t ts, int64_t tc,
+                                   double kF, double beta, double lambda, const double *d_weight, const double *coef, uint64_t seed,
+                                   uint64_t sample_offset, uint32_t n_dim, uint32_t n_grid, double *d_acc, double *d_acc2, double *d_hist,
+                                   const uint32_t *strat, const int32_t *d_cube, double *d_cube_sum, double *d_cube_sum2, int64_t B,
+                                   void *stream) {
+  const VegasRun vg{coef, seed, sample_offset, n_dim, n_grid, d_hist, false, nullptr};
+  const StratRun sr{strat, d_cube, d_cube_sum, d_cube_sum2};
+  const BinnedCall c{nullptr, 0, 1, d_weight, d_acc, d_acc2, B, stream, &vg, nullptr, nullptr, nullptr, &sr};
+  const int rc = check_strat_call(g, c);
+  return rc ? rc : accumulate_mc(g, d_K, ks, kc, d_T, ts, tc, kF, beta, lambda, c);
+}
+
+int fdg_vegas_sample_device_strat(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, const uint32_t *strat,
+                                  const int64_t *d_start, uint64_t seed, uint64_t sample_offset, double *d_x, int64_t x_sample_stride,
+                                  int64_t x_col_stride, double *d_jac, int32_t *d_cube, int32_t *d_cell, int64_t B, void *stream) {
+  int rc = check_sampler(B, !d_grid || !d_x || !d_jac, n_dim, n_grid);
+  if (rc) return rc;
+  if (!strat || !d_start || !d_cube) { set_error("null strat, d_start or d_cube"); return FDG_E_INVALID; }
+  uint32_t H;
+  rc = check_strat(strat, n_dim, &H);
+  if (rc) return rc;
+  if (B == 0) return FDG_OK;
+  const long grid = std::min<long>(((long)B + 255) / 256, 256L * 16);
+  hipLaunchKernelGGL(fdg_vegas_sample_strat, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, d_grid, n_dim, n_grid,
+                     vegas_cols(col, n_dim), vegas_strat(strat, n_dim), d_start, seed, sample_offset, d_x, (long)x_sample_stride,
+                     (long)x_col_stride, d_jac, d_cube, d_cell, (long)B);
+  HIP_TRY(hipGetLastError());
+  return FDG_OK;
+}
+
+// The allocation of the next iteration's samples to the hypercubes; host only, fp64, in the order include/fdg.h states.
+int fdg_strat_allocate(const double *cube_sum, const double *cube_sum2, uint32_t ld, uint32_t col, const int64_t *start_old, uint32_t H,
+                       int64_t n_total, double beta, int64_t *start_new) {
+  if (!start_new || (start_old && (!cube_sum || !cube_sum2))) { set_error("null argument"); return FDG_E_INVALID; }
+  if (H == 0) { set_error("H == 0"); return FDG_E_INVALID; }
+  if (H > FDG_STRAT_CUBE_MAX) { set_error("H > FDG_STRAT_CUBE_MAX"); return FDG_E_UNSUPPORTED; }
+  if (n_total < 2 * (int64_t)H) { set_error("n_total < 2 H"); return FDG_E_INVALID; }
+  if (!(beta >= 0.0 && beta <= 1.0)) { set_error("beta outside [0, 1]"); return FDG_E_INVALID; }
+  if (start_old && col >= ld) { set_error("col >= ld"); return FDG_E_INVALID; }
+  const int64_t spare = n_total - 2 * (int64_t)H;
+  std::vector<int64_t> cnt(H);
+  std::vector<double> dh(H, 0.0);
+  double S = 0.0;
+  if (start_old) {
+    const double n_old = (double)start_old[H];
+    for (uint32_t h = 0; h < H; ++h) {
+      const int64_t n_h = start_old[h + 1] - start_old[h];
+      if (n_h < 2) { set_error("an old count below 2"); return FDG_E_INVALID; }
+      const double s1 = cube_sum[(size_t)h * ld + col], s2 = cube_sum2[(size_t)h * ld + col];
+      if (!std::isfinite(s1) || !std::isfinite(s2)) { set_error("a moment is not finite"); return FDG_E_INVALID; }
+      const double nd = (double)n_h, fac = n_old / ((double)H * nd);
+      const double var = std::max(0.0, (s2 - s1 * s1 / nd) / (nd - 1.0)) / (fac * fac);
+      dh[h] = var == 0.0 ? 0.0 : std::pow(var, beta / 2.0);
+      S = h ? S + dh[h] : dh[h];
+    }
+  }
+  if (!start_old || !(S > 0.0) || !std::isfinite(S) || beta == 0.0) {
+    for (uint32_t h = 0; h < H; ++h) cnt[h] = 2 + spare / (int64_t)H;
+  } else {
+    for (uint32_t h = 0; h < H; ++h) cnt[h] = 2 + (int64_t)std::floor((double)spare * (dh[h] / S));
+  }
+  int64_t have = 0;
+  for (uint32_t h = 0; h < H; ++h) have += cnt[h];
+  for (uint32_t h = 0; have < n_total; h = (h + 1) % H) { ++cnt[h]; ++have; }
+  for (uint32_t h = H; have > n_total;) {
+    h = h ? h - 1 : H - 1;
+    if (cnt[h] > 2) { --cnt[h]; --have; }
+  }
+  start_new[0] = 0;
+  for (uint32_t h = 0; h < H; ++h) start_new[h + 1] = start_new[h] + cnt[h];
+  return FDG_OK;
 }
 
 void fdg_matsubara_phase(double tau, double beta, int32_t n, int fermionic, double *s, double *c) {

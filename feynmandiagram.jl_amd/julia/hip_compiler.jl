@@ -297,6 +297,64 @@ function vegas_refine!(grid::Matrix{Float64}, hist::Matrix{Float64}; alpha::Floa
         grid, hist, size(grid, 2), size(hist, 1), alpha))
     return grid
 end
+# ---- adaptive stratified sampling, VEGAS+ (include/fdg.h; no counterpart in the reference: MCIntegration is the caller's side) ---- #
+# strat: the strata per variable (a Vector, H = prod(strat) hypercubes, variable 1 fastest); d_start: H + 1 Int64 on the device, the
+# prefix sums of the samples per hypercube in global sample indices (0-based values); d_cube[b] receives the sample's hypercube
+# (0-based).  Unverified: there is no Julia in the image these wrappers were written in.
+function vegas_sample_device_strat!(d_x::Ptr{Float64}, d_jac::Ptr{Float64}, d_cube::Ptr{Int32}, d_grid::Ptr{Float64}, n_dim::Integer,
+    n_grid::Integer, strat::AbstractVector{<:Integer}, d_start::Ptr{Int64}, B::Integer;
+    col::Union{Nothing,AbstractVector{<:Integer}}=nothing, seed::Integer=0, sample_offset::Integer=0, x_strides=(1, B),
+    d_cell::Ptr{Int32}=Ptr{Int32}(C_NULL), stream::Ptr{Cvoid}=C_NULL)
+    c = col === nothing ? nothing : UInt32.(col .- 1)
+    sv = UInt32.(strat)
+    _fdg_check(ccall((:fdg_vegas_sample_device_strat, _libfdg), Cint,
+        (Ptr{Float64}, UInt32, UInt32, Ptr{UInt32}, Ptr{UInt32}, Ptr{Int64}, UInt64, UInt64, Ptr{Float64}, Int64, Int64, Ptr{Float64},
+         Ptr{Int32}, Ptr{Int32}, Int64, Ptr{Cvoid}),
+        d_grid, n_dim, n_grid, c === nothing ? C_NULL : c, sv, d_start, seed, sample_offset, d_x, x_strides[1], x_strides[2], d_jac,
+        d_cube, d_cell, B, stream))
+    return nothing
+end
+# accumulate_device_vegas! with the training cells by the stratified formula and the per-hypercube moments d_cube_sum, d_cube_sum2
+# ((R + 1) x H each, added to; row R + 1 the coef combination).
+function accumulate_device_strat!(f::GraphFunc, d_leaf::Ptr{Float64}, d_weight::Ptr{Float64}, d_acc::Ptr{Float64}, d_acc2::Ptr{Float64},
+    d_hist::Ptr{Float64}, strat::AbstractVector{<:Integer}, d_cube::Ptr{Int32}, d_cube_sum::Ptr{Float64}, d_cube_sum2::Ptr{Float64},
+    n_dim::Integer, n_grid::Integer, B::Integer; coef::Union{Nothing,Vector{Float64}}=nothing, seed::Integer=0,
+    sample_offset::Integer=0, leaf_strides=(1, B), tile_stride::Integer=0, stream::Ptr{Cvoid}=C_NULL)
+    sv = UInt32.(strat)
+    _fdg_check(ccall((:fdg_accumulate_device_strat, _libfdg), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, UInt64, UInt64, UInt32, UInt32, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{UInt32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Cvoid}),
+        f.handle, d_leaf, leaf_strides[1], leaf_strides[2], tile_stride, d_weight, coef === nothing ? C_NULL : coef, seed, sample_offset,
+        n_dim, n_grid, d_acc, d_acc2, d_hist, sv, d_cube, d_cube_sum, d_cube_sum2, B, stream))
+    return nothing
+end
+function mc_accumulate_device_strat!(f::GraphFunc, d_K::Ptr{Float64}, d_T::Ptr{Float64}, d_weight::Ptr{Float64}, d_acc::Ptr{Float64},
+    d_acc2::Ptr{Float64}, d_hist::Ptr{Float64}, strat::AbstractVector{<:Integer}, d_cube::Ptr{Int32}, d_cube_sum::Ptr{Float64},
+    d_cube_sum2::Ptr{Float64}, n_dim::Integer, n_grid::Integer, B::Integer; kF::Float64, beta::Float64, lambda::Float64,
+    coef::Union{Nothing,Vector{Float64}}=nothing, seed::Integer=0, sample_offset::Integer=0, k_strides=(1, B), t_strides=(1, B),
+    stream::Ptr{Cvoid}=C_NULL)
+    sv = UInt32.(strat)
+    _fdg_check(ccall((:fdg_mc_accumulate_device_strat, _libfdg), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Int64, Float64, Float64, Float64, Ptr{Float64}, Ptr{Float64}, UInt64,
+         UInt64, UInt32, UInt32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Int64,
+         Ptr{Cvoid}),
+        f.handle, d_K, k_strides[1], k_strides[2], d_T, t_strides[1], t_strides[2], kF, beta, lambda, d_weight,
+        coef === nothing ? C_NULL : coef, seed, sample_offset, n_dim, n_grid, d_acc, d_acc2, d_hist, sv, d_cube, d_cube_sum, d_cube_sum2,
+        B, stream))
+    return nothing
+end
+# The next iteration's allocation, on the host (fdg_strat_allocate): cube_sum, cube_sum2 are (R + 1) x H, col the 1-based row the
+# allocation follows, start_old H + 1 prefix sums (nothing: no history, the uniform allocation); start_new is filled and returned.
+function strat_allocate!(start_new::Vector{Int64}, cube_sum::Union{Nothing,Matrix{Float64}}, cube_sum2::Union{Nothing,Matrix{Float64}},
+    col::Integer, start_old::Union{Nothing,Vector{Int64}}, n_total::Integer; beta::Float64=0.75)
+    H = length(start_new) - 1
+    ld = cube_sum === nothing ? 0 : size(cube_sum, 1)
+    _fdg_check(ccall((:fdg_strat_allocate, _libfdg), Cint,
+        (Ptr{Float64}, Ptr{Float64}, UInt32, UInt32, Ptr{Int64}, UInt32, Int64, Float64, Ptr{Int64}),
+        cube_sum === nothing ? C_NULL : cube_sum, cube_sum2 === nothing ? C_NULL : cube_sum2, ld, max(col - 1, 0),
+        start_old === nothing ? C_NULL : start_old, H, n_total, beta, start_new))
+    return start_new
+end
 # ---- a discrete external variable (include/fdg.h; no counterpart in the reference: the caller's side of test/ver4.jl:224-237) ---- #
 # ExtKidx = MCIntegration.Discrete(1, Nk): d_cdf (n_bin + 1, on the device) is the variable's cumulative distribution, d_ext (n_ext x n_bin,
 # column j = what value j means) goes to the columns ext_col (1-based) of x; d_bin[b] is the value drawn (1-based by default), d_jac[b] the
@@ -620,7 +678,7 @@ function accumulate_device!(f::GraphFunc, d_acc::Ptr{Float64}, d_leaf::Ptr{Float
         f.handle, d_leaf, leaf_strides[1], leaf_strides[2], d_weight, d_acc, B, stream))
 end
 
-export compile_hip, GraphFunc, eval_device!, accumulate_device!, eval_device_tiled!, accumulate_device_tiled!, accumulate_device_binned!, mc_accumulate_device_binned!, accumulate_device_moments!, mc_accumulate_device_moments!, vegas_sample_device!, accumulate_device_vegas!, mc_accumulate_device_vegas!, vegas_refine!, vegas_sample_device_discrete!, accumulate_device_vegas_binned!, mc_accumulate_device_vegas_binned!, vegas_refine_discrete!, vegas_sample_device_polar!, fdg_sincos, fdg_matsubara_phase, accumulate_device_matsubara!, mc_accumulate_device_matsubara!, weight_groups_from_dof, vegas_sample_device_grouped!, accumulate_device_grouped!, mc_accumulate_device_grouped!, accumulate_device_observables!, mc_accumulate_device_observables!, batch_alloc, batch_free, tile_major!, from_tile_major!
+export compile_hip, GraphFunc, eval_device!, accumulate_device!, eval_device_tiled!, accumulate_device_tiled!, accumulate_device_binned!, mc_accumulate_device_binned!, accumulate_device_moments!, mc_accumulate_device_moments!, vegas_sample_device!, accumulate_device_vegas!, mc_accumulate_device_vegas!, vegas_refine!, vegas_sample_device_discrete!, accumulate_device_vegas_binned!, mc_accumulate_device_vegas_binned!, vegas_refine_discrete!, vegas_sample_device_polar!, fdg_sincos, fdg_matsubara_phase, accumulate_device_matsubara!, mc_accumulate_device_matsubara!, weight_groups_from_dof, vegas_sample_device_grouped!, accumulate_device_grouped!, mc_accumulate_device_grouped!, accumulate_device_observables!, mc_accumulate_device_observables!, batch_alloc, batch_free, tile_major!, from_tile_major!, vegas_sample_device_strat!, accumulate_device_strat!, mc_accumulate_device_strat!, strat_allocate!
 
 # ---- multi-GPU: one Julia process per GPU, ONE reduction of the accumulated observable ------------ #
 # (include/fdg.h, "multi-GPU").  Rank 0 calls `comm_unique_id()` and ships the 128 bytes to the other

@@ -28,6 +28,11 @@ Observables (``Observables``, the keyword ``observables``; fdg_mc_accumulate_dev
 roots -- the direct and exchange components of the reference's test/ver4.jl:184-216, a series summed over its orders -- and its error
 bar needs the covariance of the roots, which share their samples.  The accumulate call sums the combinations and their products on
 the device; the results gain ``obs_mean``, ``obs_stderr``, ``obs_chi2_dof`` and ``obs_cov``.
+
+Adaptive stratified sampling (``Stratification``, ``strat_for``, the keyword ``strat``; fdg_vegas_sample_device_strat,
+fdg_mc_accumulate_device_strat, fdg_strat_allocate): Lepage's VEGAS+ on top of the map.  The unit cube of the map's coordinates is cut
+into hypercubes, each receives at least two samples and the rest go where the integrand's standard deviation is largest -- what a
+separable map cannot do for a ridge along a diagonal (a propagator of ``k1 + k2`` or ``T[i] - T[j]``).
 """
 from __future__ import annotations
 
@@ -103,6 +108,7 @@ class VegasResult:
     obs_chi2_dof: Optional[np.ndarray] = None   # [n_obs]
     obs_cov: Optional[np.ndarray] = None        # [n_obs, n_obs] covariance of ``obs_mean`` (:func:`combine_covariance`)
     obs_iterations: List[Tuple[np.ndarray, np.ndarray]] = field(default_factory=list)   # (mean [n_obs], C [n_obs, n_obs]) of every iteration
+    cube_counts: List[np.ndarray] = field(default_factory=list)      # with ``strat``: the samples per hypercube [H] of every iteration
 
 
 def combine(iterations: Sequence[Tuple[np.ndarray, np.ndarray]]):
@@ -218,6 +224,121 @@ class Observables:
     most ``capi.FDG_OBS_MAX`` rows of ``n_root`` finite numbers.  Every root enters with its own weight (its group's jacobian under
     ``groups``), unprojected; complex observables (of Matsubara-projected roots) are not supported."""
     coef: Tuple[Tuple[float, ...], ...]
+
+
+@dataclass(frozen=True)
+class Stratification:
+    """Adaptive stratified sampling on top of the map: ``strat[d]`` strata of variable ``d`` (:func:`strat_for`), ``H = prod strat``
+    hypercubes of at most ``capi.FDG_STRAT_CUBE_MAX``; ``beta`` in ``[0, 1]`` damps the reallocation (0: every iteration uniform)."""
+    strat: Tuple[int, ...]
+    beta: float = 0.75
+
+
+def strat_for(n_sample: int, n_dim: int, max_cubes: int = capi.FDG_STRAT_CUBE_MAX) -> Tuple[int, ...]:
+    """Lepage's rule for the strata per variable: ``floor((n_sample / 4) ** (1 / n_dim))`` on every axis (at least 1; the root taken
+    in integers), then, while there are more than ``max_cubes`` hypercubes, one stratum less on one axis at a time, from the last
+    axis to the first and round again."""
+    n, D = int(n_sample), int(n_dim)
+    if n < 1 or D < 1 or max_cubes < 1:
+        raise ValueError("need n_sample, n_dim and max_cubes >= 1")
+    s = max(1, int((n / 4.0) ** (1.0 / D)))
+    while 4 * (s + 1) ** D <= n:
+        s += 1
+    while s > 1 and 4 * s ** D > n:
+        s -= 1
+    out = [s] * D
+    while math.prod(out) > max_cubes:
+        for d in range(D - 1, -1, -1):
+            if out[d] > 1 and math.prod(out) > max_cubes:
+                out[d] -= 1
+    return tuple(out)
+
+
+def strat_variance(cube_sum, cube_sum2, counts, n_total: int) -> np.ndarray:
+    """The variance of the stratified estimate per column of the per-hypercube moments ``[H, C]``:
+    ``sum_h n_h var_h / N**2`` with ``var_h = max(0, (sum2_h - sum_h**2 / n_h) / (n_h - 1))``."""
+    n = np.asarray(counts, dtype=np.float64)[:, None]
+    var = np.maximum(0.0, (cube_sum2 - cube_sum * cube_sum / n) / (n - 1.0))
+    return (n * var).sum(axis=0) / float(n_total) ** 2
+
+
+def _iteration_seed(seed: int, it: int) -> int:
+    """The Philox key of iteration ``it`` of a stratified run.  A sample's index places it in its hypercube, so the iterations cannot
+    be told apart by ``sample_offset`` as in the plain driver: each takes a key of its own."""
+    return (int(seed) + it * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+
+
+def _integrate_strat(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_iter, n_sample, n_grid, alpha, seed, n_discard, fixed, coef, device,
+                     vmap, specialize_fused, n_total, shard_start, reduce, strat):
+    """:func:`vegas_integrate` with ``strat``.  Per iteration: allocate, sample, accumulate, refine the map, fdg_strat_allocate."""
+    import torch
+    handle = getattr(func_or_handle, "handle", func_or_handle)
+    device = torch.device(device)
+    R = handle.table.n_root
+    if tables is None:
+        n_col_k, n_col = 0, handle.table.n_leaf          # the leaf form: the columns of x are the graph's leaves
+    else:
+        n_col_k = int(tables.n_loop) * int(tables.dim)
+        n_col = n_col_k + int(tables.n_tau)
+    col = [int(c) for c in col]
+    if len(set(col)) != len(col) or not all(0 <= c < n_col for c in col):
+        raise ValueError(f"col must name distinct columns in [0, {n_col})")
+    if vmap is None:
+        vmap = VegasMap(uniform_grid(lo, hi, n_grid), device)
+    if vmap.n_dim != len(col):
+        raise ValueError("one column per variable of the map")
+    D, G = vmap.n_dim, vmap.n_grid
+    sv = tuple(int(v) for v in strat.strat)
+    if len(sv) != D or not all(v >= 1 for v in sv):
+        raise ValueError("strat.strat holds one count >= 1 per variable of the map")
+    H = math.prod(sv)
+    B = int(n_sample)
+    N = B if n_total is None else int(n_total)
+    if not 0.0 <= strat.beta <= 1.0:
+        raise ValueError("strat.beta must lie in [0, 1]")
+    if H > capi.FDG_STRAT_CUBE_MAX or H * (R + 1) > 1 << 24 or N < 2 * H:
+        raise ValueError(f"need at most {capi.FDG_STRAT_CUBE_MAX} hypercubes, H * (n_root + 1) <= 2**24 and n_total >= 2 H")
+    if B < 1 or n_iter < 1 or not (0 <= n_discard < n_iter) or not 0 <= int(shard_start) <= N - B:
+        raise ValueError("need n_sample >= 1, 0 <= n_discard < n_iter and the shard inside n_total")
+    if specialize_fused and tables is not None:
+        handle.specialize_fused(tables)
+    fx = np.zeros(n_col) if fixed is None else np.asarray(fixed, dtype=np.float64)
+    if fx.shape != (n_col,):
+        raise ValueError(f"fixed must hold {n_col} column values")
+    out = VegasResult(np.zeros(R), np.zeros(R), np.full(R, np.nan), map=vmap)
+    start, sums = capi.strat_allocate(None, None, R, None, H, N, strat.beta), None
+    with torch.cuda.device(device):
+        st = torch.cuda.current_stream(device).cuda_stream
+        x = torch.from_numpy(fx).to(device)[:, None].repeat(1, B).contiguous()          # [n_col, B]: sample stride 1
+        jac = torch.empty(B, dtype=torch.float64, device=device)
+        cube = torch.empty(B, dtype=torch.int32, device=device)
+        for it in range(int(n_iter)):
+            key, off = _iteration_seed(seed, it), int(shard_start)
+            d_start = torch.from_numpy(start).to(device)
+            m = torch.zeros((2, 1, R), dtype=torch.float64, device=device)
+            hist = torch.zeros((D, G), dtype=torch.float64, device=device)
+            cs = torch.zeros((2, H, R + 1), dtype=torch.float64, device=device)
+            capi.vegas_sample_device_strat(vmap.d_grid.data_ptr(), D, G, col, sv, d_start.data_ptr(), key, off, x.data_ptr(), 1, B,
+                                           jac.data_ptr(), cube.data_ptr(), 0, B, st)
+            tail = (jac.data_ptr(), coef, key, off, D, G, m[0].data_ptr(), m[1].data_ptr(), hist.data_ptr(), sv, cube.data_ptr(),
+                    cs[0].data_ptr(), cs[1].data_ptr(), B, st)
+            if tables is None:
+                handle.accumulate_device_strat(x.data_ptr(), 1, B, 0, *tail)
+            else:
+                handle.mc_accumulate_device_strat(x.data_ptr(), 1, B, x.data_ptr() + 8 * n_col_k * B, 1, B, kF, beta, lam, *tail)
+            if reduce is not None:
+                for t in (m, hist, cs):
+                    reduce(t)
+            h_cs, counts = cs.cpu().numpy(), np.diff(start)
+            mean = m[0, 0].cpu().numpy() / N
+            err = np.sqrt(strat_variance(h_cs[0][:, :R], h_cs[1][:, :R], counts, N))
+            out.iterations.append((mean, err))
+            out.histograms.append(hist.cpu().numpy())
+            out.cube_counts.append(counts)
+            vmap.refine(out.histograms[-1], alpha)
+            start = capi.strat_allocate(h_cs[0], h_cs[1], R, start, H, N, strat.beta)
+    out.mean, out.stderr, out.chi2_dof = combine(out.iterations[int(n_discard):])
+    return out
 
 
 def groups_from_dof(dof, pools) -> WeightGroups:
@@ -410,7 +531,7 @@ def vegas_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: 
                     coef=None, device="cuda", vmap: Optional[VegasMap] = None, specialize_fused: bool = True, n_total: Optional[int] = None,
                     shard_start: int = 0, reduce: Optional[Callable] = None, polar: Optional[Sequence[PolarVar]] = None,
                     matsubara: Optional[MatsubaraProjection] = None, groups: Optional[WeightGroups] = None,
-                    observables: Optional[Observables] = None) -> VegasResult:
+                    observables: Optional[Observables] = None, strat: Optional[Stratification] = None) -> VegasResult:
     """Integrates the roots of a graph over the box ``[lo, hi]`` of ``len(col)`` of its Monte-Carlo variables.
 
     ``func_or_handle``: a ``GraphFunc`` or ``capi.GraphHandle``; ``tables`` the ``fdg_leaf_tables`` struct of ``capi.make_leaf_tables``
@@ -444,7 +565,24 @@ def vegas_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: 
     products ``o_a o_c`` (``reduce`` is applied to both).  ``mc_covariance`` gives every iteration's ``(mean, C)``
     (``obs_iterations``), and :func:`combine_covariance` the results ``obs_mean``, ``obs_stderr``, ``obs_chi2_dof`` ``[n_obs]`` and
     ``obs_cov`` ``[n_obs, n_obs]``.  Real observables of the unprojected roots only, also beside ``matsubara``.  None: the calls made
-    and their bits are what they are without this keyword."""
+    and their bits are what they are without this keyword.
+
+    ``strat``: a :class:`Stratification` (:func:`strat_for`): adaptive stratified sampling on top of the map.  Per iteration: sample
+    through fdg_vegas_sample_device_strat by the current allocation (the first is uniform), accumulate through
+    fdg_mc_accumulate_device_strat, refine the map, fdg_strat_allocate from column ``n_root`` of the per-hypercube moments (the
+    ``coef`` combination).  ``mean`` is ``acc / n_total`` and the reported variance per root ``sum_h n_h var_h(t_k) / n_total**2``;
+    the iterations combine through :func:`combine`, ``cube_counts`` keeps every iteration's samples per hypercube.  A sample's
+    index places it in its hypercube, so ``sample_offset`` is ``shard_start`` in every iteration and iteration ``it`` draws with the
+    Philox key ``seed + it * 0x9E3779B97F4A7C15`` (mod 2**64).  ``reduce`` is applied to the moments, the histogram and the
+    per-hypercube moments ``[2, H, n_root + 1]``.  ``tables`` may then be None: the leaf form, where the columns of ``x`` are the
+    graph's leaves themselves (fdg_accumulate_device_strat), ``col[d]`` the leaf that variable ``d`` fills and ``fixed`` the values
+    of the others.  Together with ``polar``, ``matsubara``, ``groups`` or ``observables`` (and with a discrete variable) it raises
+    ValueError: those combinations are not built yet.  None: the calls made and their bits are what they are without this keyword."""
+    if strat is not None:
+        if polar or matsubara is not None or groups is not None or observables is not None:
+            raise ValueError("strat cannot be combined with polar, matsubara, groups or observables")
+        return _integrate_strat(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_iter, n_sample, n_grid, alpha, seed, n_discard, fixed,
+                                coef, device, vmap, specialize_fused, n_total, shard_start, reduce, strat)
     return _integrate(func_or_handle, tables, lo, hi, col, None, kF, beta, lam, n_iter, n_sample, n_grid, alpha, 0.0, seed, n_discard, fixed, coef,
                       device, vmap, specialize_fused, n_total, shard_start, reduce, polar, matsubara, groups, observables)
 
@@ -529,7 +667,8 @@ def vegas_integrate_binned(func_or_handle, tables, lo, hi, col, dmap: DiscreteMa
                            specialize_fused: bool = True, n_total: Optional[int] = None, shard_start: int = 0,
                            reduce: Optional[Callable] = None, polar: Optional[Sequence[PolarVar]] = None,
                            matsubara: Optional[MatsubaraProjection] = None,
-                           groups: Optional[WeightGroups] = None, observables: Optional[Observables] = None) -> VegasBinnedResult:
+                           groups: Optional[WeightGroups] = None, observables: Optional[Observables] = None,
+                           strat: Optional[Stratification] = None) -> VegasBinnedResult:
     """:func:`vegas_integrate` with a discrete variable: every sample draws a value ``j`` of ``dmap`` next to its continuous variables,
     the columns ``dmap.ext_col`` take row ``j`` of ``dmap.ext`` (external momenta), and the estimate is per value: arrays ``[n_bin, R]``,
     bin ``j`` the integral over the continuous variables at configuration ``j`` (the weight carries ``1 / p_j``, and ``mc_estimate``
@@ -537,6 +676,9 @@ def vegas_integrate_binned(func_or_handle, tables, lo, hi, col, dmap: DiscreteMa
     ``mc_estimate``, refine the map with ``alpha`` and the probabilities with ``alpha`` and ``floor``.  ``combine`` is per (bin, root).
     Sharding as in :func:`vegas_integrate`; ``reduce`` is applied to the moments ``[2, n_bin, R]`` and to both histograms, so every rank
     refines the same maps.  ``polar``, ``matsubara`` and ``groups`` as in :func:`vegas_integrate` (complex ``[n_bin, n_freq, R]``; the
-    discrete variable is shared by every group); ``observables`` too: ``obs_mean`` ``[n_bin, n_obs]``, ``obs_cov`` ``[n_bin, n_obs, n_obs]``."""
+    discrete variable is shared by every group); ``observables`` too: ``obs_mean`` ``[n_bin, n_obs]``, ``obs_cov`` ``[n_bin, n_obs, n_obs]``.
+    ``strat`` is not built for a discrete variable yet: anything but None raises ValueError."""
+    if strat is not None:
+        raise ValueError("strat cannot be combined with a discrete variable (dmap)")
     return _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter, n_sample, n_grid, alpha, floor, seed, n_discard, fixed,
                       coef, device, vmap, specialize_fused, n_total, shard_start, reduce, polar, matsubara, groups, observables)

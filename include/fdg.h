@@ -925,6 +925,73 @@ int fdg_mc_accumulate_device_observables(fdg_graph *g, const double *d_K, int64_
                                          double *d_acc, double *d_acc2, double *d_hist, double *d_hist_bin, const fdg_matsubara *mz,
                                          const fdg_weight_groups *wg, const fdg_observables *ob, int64_t n_sample, void *stream);
 
+/* ---- Adaptive stratified sampling (VEGAS+) ------------------------------------------------------------------------------------------
+ * The map above is separable: a ridge along a diagonal (a propagator of k1 + k2, of T[i] - T[j]) is flat in every axis projection, the
+ * map stays uniform and the error falls as 1/sqrt(N).  Lepage's VEGAS+ (J. Comput. Phys. 439 (2021) 110386) cuts the unit cube of the
+ * map's coordinates into H hypercubes, gives each at least two samples and the rest to the hypercubes where the integrand's standard
+ * deviation is largest.  MCIntegration is not part of the reference checkout: no counterpart in the reference.
+ *
+ * strat[d] >= 1 (a HOST array of n_dim words) is the number of strata of variable d; H = prod strat[d], 1 <= H <= FDG_STRAT_CUBE_MAX;
+ * hypercube h has the mixed-radix digits s_d, variable 0 fastest: h = s_0 + strat[0] * (s_1 + strat[1] * (s_2 + ...)).
+ * d_start (DEVICE, H + 1 int64) holds the prefix sums of the samples per hypercube in GLOBAL sample indices: start[0] = 0,
+ * start[H] = n_total, and n_h = start[h + 1] - start[h] >= 1 (fdg_strat_allocate gives at least 2).  The samples of a hypercube are
+ * contiguous, so a sample's hypercube is a function of its index.
+ *
+ * fdg_vegas_sample_device_strat: for sample b with the global index i = sample_offset + b, every step one rounded fp64 operation,
+ *     h   = the hypercube with start[h] <= i < start[h + 1] (a binary search per lane)      -> d_cube[b]  (int32, required)
+ *     u   = the uniform of counter (i, d) and key seed, as fdg_vegas_sample_device draws it
+ *     v   = ((double)s_d + u) / (double)strat[d];   y = v * G;   c = min((int)y, G - 1)
+ *     fr, wd, x, the factor G * wd and the left fold jac_map exactly as in fdg_vegas_sample_device (v may round to 1.0 in the last
+ *     stratum: the clamp of c covers it, x is then the last edge)
+ *     jac = jac_map * fac_h,   fac_h = (double)n_total / ((double)H * (double)n_h)            -> d_jac[b]
+ * With every strat[d] == 1 and start = {0, n_total}, x, d_cell and d_jac carry the bits of fdg_vegas_sample_device ((0 + u) / 1 and
+ * * 1.0 are exact).  Counter-based: shards reproduce the unsharded batch.  FDG_E_INVALID: the sampler's cases, strat, d_start or
+ * d_cube NULL, strat[d] == 0; FDG_E_UNSUPPORTED: the map's limits, H > FDG_STRAT_CUBE_MAX.  All before any device work.
+ *
+ * fdg_[mc_]accumulate_device_strat: the arguments of the _vegas calls plus strat, d_cube (the sampler's, int32 [n_sample]) and the
+ * per-hypercube moments d_cube_sum, d_cube_sum2 (DEVICE, [H][n_root + 1] doubles each, added to).
+ *   d_acc, d_acc2: bit for bit those of the _vegas / moments calls (the same unchanged pass and plan).
+ *   d_hist: the training histogram with the cell of (sample, variable) recomputed by the STRATIFIED formula above from the digit of
+ *     d_cube[b] and the counter; a sample whose d_cube lies outside [0, H) is selected away from it.  With every strat[d] == 1 and an
+ *     all-zero d_cube it carries the bits of fdg_accumulate_device_vegas.
+ *   d_cube_sum[h][k] += t_k, d_cube_sum2[h][k] += t_k * t_k with t_k = w_b * root_k(b) (k < n_root; d_weight NULL: t_k = root_k), and
+ *     column n_root takes t = w_b * s and t * t, s the coef combination formed exactly as for d_hist.  The column of a root that does
+ *     not exist (FDG_NO_ROOT) is left untouched, and so is column n_root when no root exists.
+ * d_cube must be non-decreasing over its in-range values (the sampler's is).  Samples with d_cube outside [0, H) and lanes past n_sample
+ * enter no per-hypercube sum: selected away, never multiplied by zero.  No float atomics; the sums are bitwise repeatable, and their
+ * order is a function of (n_sample, n_root, FDG_ROOT_SCRATCH_MB) only (csrc/fdg_binned.hip).
+ * FDG_E_INVALID: the _vegas calls' cases, strat, d_cube, d_cube_sum or d_cube_sum2 NULL, the two the same buffer or one of them the
+ * same as d_acc, d_acc2 or d_hist, strat[d] == 0; FDG_E_UNSUPPORTED: H > FDG_STRAT_CUBE_MAX, H * (n_root + 1) > 1 << 24.
+ *
+ * fdg_strat_allocate (host only): the next iteration's allocation from the per-hypercube moments of column col (leading dimension
+ * ld, i.e. cube_sum[h * ld + col]), in fp64, in this order, with n_h and fac_h those of start_old (its own total start_old[H]):
+ *  1. var_h = max(0, (sum2_h - sum_h * sum_h / n_h) / (n_h - 1)) / (fac_h * fac_h)
+ *  2. d_h = pow(var_h, beta / 2), and 0 for var_h == 0
+ *  3. S = the left fold of d_h.  S <= 0, S not finite, beta == 0 or start_old == NULL ("no history"; the moments are then not
+ *     read): the allocation is uniform, n_h = 2 + (n_total - 2 H) div H in integers.
+ *  4. otherwise n_h = 2 + floor((double)(n_total - 2 H) * (d_h / S)).  The samples left over go one each to h = 0, 1, ... ascending
+ *     (wrapping) until the sum is exactly n_total; should rounding have handed out too many, they are taken back one each from
+ *     h = H - 1, H - 2, ... among the hypercubes that hold more than 2.
+ *  5. start_new[0] = 0, start_new[h + 1] = start_new[h] + n_h.
+ * FDG_E_INVALID: a NULL array (start_old may be NULL), H == 0, n_total < 2 H, beta outside [0, 1], col >= ld, a non-finite moment in column col, an old count
+ * below 2; FDG_E_UNSUPPORTED: H > FDG_STRAT_CUBE_MAX.  On error start_new is untouched. */
+#define FDG_STRAT_CUBE_MAX (1u << 20)
+int fdg_vegas_sample_device_strat(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, const uint32_t *strat,
+                                  const int64_t *d_start, uint64_t seed, uint64_t sample_offset, double *d_x, int64_t x_sample_stride,
+                                  int64_t x_col_stride, double *d_jac, int32_t *d_cube, int32_t *d_cell, int64_t n_sample, void *stream);
+int fdg_accumulate_device_strat(fdg_graph *g, const double *d_leaf, int64_t leaf_sample_stride, int64_t leaf_leaf_stride,
+                                int64_t leaf_tile_stride, const double *d_weight, const double *coef, uint64_t seed,
+                                uint64_t sample_offset, uint32_t n_dim, uint32_t n_grid, double *d_acc, double *d_acc2, double *d_hist,
+                                const uint32_t *strat, const int32_t *d_cube, double *d_cube_sum, double *d_cube_sum2, int64_t n_sample,
+                                void *stream);
+int fdg_mc_accumulate_device_strat(fdg_graph *g, const double *d_K, int64_t k_sample_stride, int64_t k_comp_stride, const double *d_T,
+                                   int64_t t_sample_stride, int64_t t_comp_stride, double kF, double beta, double lambda,
+                                   const double *d_weight, const double *coef, uint64_t seed, uint64_t sample_offset, uint32_t n_dim,
+                                   uint32_t n_grid, double *d_acc, double *d_acc2, double *d_hist, const uint32_t *strat,
+                                   const int32_t *d_cube, double *d_cube_sum, double *d_cube_sum2, int64_t n_sample, void *stream);
+int fdg_strat_allocate(const double *cube_sum, const double *cube_sum2, uint32_t ld, uint32_t col, const int64_t *start_old, uint32_t H,
+                       int64_t n_total, double beta, int64_t *start_new);
+
 /* Device workspace control: the interpreter keeps per-sample overflow slots in
  * an HBM panel owned by the handle; it is sized on first use for the number of
  * resident waves.  This releases it (and any loaded module). */
