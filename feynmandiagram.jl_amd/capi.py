@@ -50,6 +50,7 @@ EXPORTS = [
     "fdg_matsubara_phase", "fdg_accumulate_device_matsubara", "fdg_mc_accumulate_device_matsubara",
     "fdg_vegas_sample_device_grouped", "fdg_accumulate_device_grouped", "fdg_mc_accumulate_device_grouped",
     "fdg_accumulate_device_observables", "fdg_mc_accumulate_device_observables",
+    "fdg_accumulate_device_freq_observables", "fdg_mc_accumulate_device_freq_observables",
     "fdg_vegas_sample_device_strat", "fdg_accumulate_device_strat", "fdg_mc_accumulate_device_strat", "fdg_strat_allocate",
 ]
 FDG_BIN_MAX = 16384     # fdg_accumulate_device_binned: largest n_bin
@@ -59,6 +60,7 @@ FDG_VEGAS_POLAR_MAX = 21  # fdg_vegas_sample_device_polar: most groups of polar 
 FDG_MATSUBARA_FREQ_MAX = 64  # fdg_[mc_]accumulate_device_matsubara: most frequencies per call
 FDG_WEIGHT_GROUP_MAX = 8  # fdg_weight_groups: most groups of roots with their own integration variables
 FDG_OBS_MAX = 16  # fdg_observables: most linear combinations of the roots per call
+FDG_FREQ_OBS_MAX = 8  # fdg_freq_observables: most linear combinations of the projected roots per call
 FDG_STRAT_CUBE_MAX = 1 << 20  # the stratified calls: most hypercubes
 COMM_ID_BYTES = 128
 
@@ -123,6 +125,11 @@ class WeightGroups(C.Structure):
 class Observables(C.Structure):
     """fdg_observables (include/fdg.h)"""
     _fields_ = [("n_obs", C.c_uint32), ("coef", C.c_void_p), ("d_obs", C.c_void_p), ("d_cov", C.c_void_p)]
+
+
+class FreqObservables(C.Structure):
+    """fdg_freq_observables (include/fdg.h)"""
+    _fields_ = [("n_obs", C.c_uint32), ("coef", C.c_void_p), ("d_fobs", C.c_void_p), ("d_fcov", C.c_void_p)]
 
 
 class OptParams(C.Structure):
@@ -269,6 +276,11 @@ def lib():
     L.fdg_mc_accumulate_device_observables.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, C.c_int32,
                                                        u32, dp, C.c_void_p, u64, u64, u32, u32, dp, dp, dp, dp, C.c_void_p, C.c_void_p,
                                                        C.c_void_p, i64, vp]
+    L.fdg_accumulate_device_freq_observables.argtypes = [vp, dp, i64, i64, i64, dp, C.c_int32, u32, dp, C.c_void_p, u64, u64, u32, u32, dp,
+                                                         dp, dp, dp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, i64, vp]
+    L.fdg_mc_accumulate_device_freq_observables.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp,
+                                                            C.c_int32, u32, dp, C.c_void_p, u64, u64, u32, u32, dp, dp, dp, dp, C.c_void_p,
+                                                            C.c_void_p, C.c_void_p, C.c_void_p, i64, vp]
     L.fdg_vegas_sample_device_strat.argtypes = [dp, u32, u32, C.c_void_p, C.c_void_p, dp, u64, u64, dp, i64, i64, dp, dp, dp, i64, vp]
     L.fdg_accumulate_device_strat.argtypes = [vp, dp, i64, i64, i64, dp, C.c_void_p, u64, u64, u32, u32, dp, dp, dp, C.c_void_p, dp, dp, dp,
                                               i64, vp]
@@ -598,6 +610,33 @@ class GraphHandle:
                                                          d_hist_bin or None, None if desc is None else C.addressof(desc),
                                                          None if groups is None else C.addressof(groups),
                                                          None if obs is None else C.addressof(obs), B, stream))
+
+    # frequency observables: fobs = make_freq_observables(...)[0] and desc (required: the frequencies, time labels, beta, T; its four
+    # arrays all 0: no per-root projection); obs and groups may be None; the rest as the observables calls take it (fdg.h)
+    def accumulate_device_freq_observables(self, d_leaf: int, ss: int, ls: int, lts: int, d_bin: int, bin_base: int, n_bin: int,
+                                           d_weight: int, fobs, desc, obs=None, groups=None, coef=None, seed: int = 0, sample_offset: int = 0,
+                                           n_dim: int = 0, n_grid: int = 0, d_acc: int = 0, d_acc2: int = 0, d_hist: int = 0,
+                                           d_hist_bin: int = 0, B: int = 0, stream: int = 0):
+        c = self._coef(coef)
+        check(lib().fdg_accumulate_device_freq_observables(self._h, d_leaf or None, ss, ls, lts, d_bin or None, bin_base, n_bin,
+                                                           d_weight or None, None if c is None else c.ctypes.data, seed, sample_offset,
+                                                           n_dim, n_grid, d_acc or None, d_acc2 or None, d_hist or None, d_hist_bin or None,
+                                                           None if desc is None else C.addressof(desc),
+                                                           None if groups is None else C.addressof(groups),
+                                                           None if obs is None else C.addressof(obs),
+                                                           None if fobs is None else C.addressof(fobs), B, stream))
+
+    def mc_accumulate_device_freq_observables(self, d_K, ks, kc, d_T, ts, tc, kF, beta, lam, d_bin, bin_base, n_bin, d_weight, fobs, desc,
+                                              obs=None, groups=None, coef=None, seed=0, sample_offset=0, n_dim=0, n_grid=0, d_acc=0, d_acc2=0,
+                                              d_hist=0, d_hist_bin=0, B=0, stream=0):
+        c = self._coef(coef)
+        check(lib().fdg_mc_accumulate_device_freq_observables(self._h, d_K or None, ks, kc, d_T or None, ts, tc, kF, beta, lam, d_bin or None,
+                                                              bin_base, n_bin, d_weight or None, None if c is None else c.ctypes.data, seed,
+                                                              sample_offset, n_dim, n_grid, d_acc or None, d_acc2 or None, d_hist or None,
+                                                              d_hist_bin or None, None if desc is None else C.addressof(desc),
+                                                              None if groups is None else C.addressof(groups),
+                                                              None if obs is None else C.addressof(obs),
+                                                              None if fobs is None else C.addressof(fobs), B, stream))
 
     # the stratified accumulate step: the _vegas calls plus the training cells by the stratified formula (d_cube: the sampler's
     # hypercubes) and the per-hypercube moments d_cube_sum, d_cube_sum2 [H, n_root + 1]; strat: host sequence of n_dim counts (fdg.h)
@@ -951,6 +990,102 @@ def observables_reference(roots, coef, weight=None, root_group=None, bins=None, 
             cov[:, m, m2] = cov[:, m2, m] = np.bincount(jj, pr, n_bin)
             s_cov[:, m, m2] = s_cov[:, m2, m] = np.bincount(jj, np.abs(pr), n_bin)
     return obs, cov, s_obs, s_cov
+
+
+def make_freq_observables(coef, d_fobs: int, d_fcov: int):
+    """``(fdg_freq_observables struct, keepalive)``: ``coef`` the real ``[n_obs, n_root]`` coefficients (host), ``d_fobs`` / ``d_fcov``
+    the device addresses of the ``[n_bin, n_freq, 2 n_obs]`` and ``[n_bin, n_freq, 2 n_obs, 2 n_obs]`` sums.  The struct points into the
+    keepalive array."""
+    c = np.ascontiguousarray(coef, dtype=np.float64)
+    if c.ndim != 2:
+        raise ValueError("coef must be [n_obs, n_root]")
+    return FreqObservables(c.shape[0], c.ctypes.data, d_fobs or None, d_fcov or None), (c,)
+
+
+def matsubara_phase_table(tau, beta: float, freq, fermionic: bool = True):
+    """``(s, c)``, each ``[len(tau), len(freq)]``: fdg_matsubara_phase's bits for every (sample, frequency), one call of the library's
+    routine per entry (about a microsecond each)."""
+    tau = np.asarray(tau, dtype=np.float64)
+    s, c = np.empty((tau.shape[0], len(freq))), np.empty((tau.shape[0], len(freq)))
+    fn, vs, vc = lib().fdg_matsubara_phase, C.c_double(), C.c_double()
+    ps, pc, beta, fm = C.byref(vs), C.byref(vc), float(beta), 1 if fermionic else 0
+    taus = tau.tolist()
+    for f, n in enumerate(int(v) for v in freq):
+        for b, tb in enumerate(taus):
+            fn(tb, beta, n, fm, ps, pc)
+            s[b, f] = vs.value
+            c[b, f] = vc.value
+    return s, c
+
+
+def freq_observables_reference(roots, T, tin, tout, freq, beta, fermionic, coef, weight=None, root_group=None, bins=None, n_bin: int = 1,
+                               bin_base: int = 0, exists=None, phases=None):
+    """The numpy restatement of fdg_[mc_]accumulate_device_freq_observables' definition: ``(fobs [n_bin, F, 2 M], fcov [n_bin, F, 2 M,
+    2 M], scale_fobs, scale_fcov)`` from ``roots [B, R]``, ``T [B, n_tau]``, the 1-based time labels ``tin`` / ``tout`` ``[R]``, the
+    frequencies ``freq [F]`` and the real ``coef [M, R]``; ``weight``, ``root_group``, ``bins`` and ``exists`` as observables_reference
+    takes them.  ``t_k = w_g(k) * root_k``, ``(s, c) = fdg_matsubara_phase(T[b, tout_k] - T[b, tin_k], beta, freq[f], fermionic)``
+    (the library's routine through matsubara_phase_table; ``phases``: such tables ready-made, ``{(tin, tout): (s, c)}`` over ALL
+    samples), ``tre = t_k * c``, ``tim = t_k * s``; ``a_m`` / ``b_m`` the left folds of ``coef[m, k] * tre_k`` / ``* tim_k`` over
+    ascending ``k`` with ``coef[m, k] != 0`` among the roots that exist, the first product starting the fold; ``z = (a, b)``; the
+    samples of a bin are summed by numpy.  A row without a term leaves nan in its components ``m`` and ``M + m`` (the call leaves them
+    untouched).  ``scale_*``: the sums of ``|z_p|`` and ``|z_p z_q|``, what a tolerance is measured against."""
+    r = np.asarray(roots, dtype=np.float64)
+    c = np.asarray(coef, dtype=np.float64)
+    T = np.asarray(T, dtype=np.float64)
+    B, R = r.shape
+    M, F = c.shape[0], len(freq)
+    live = np.ones(R, bool) if exists is None else np.asarray(exists, bool)
+    if weight is None:
+        t = r
+    else:
+        w = np.asarray(weight, dtype=np.float64)
+        if w.ndim == 1:
+            t = w[:B, None] * r
+        else:
+            rg = np.zeros(R, np.int64) if root_group is None else np.asarray(root_group, np.int64)
+            t = w[np.where(live, rg, 0)][:, :B].T * r
+    j = np.zeros(B, np.int64) if bins is None else np.asarray(bins, np.int64)[:B] - int(bin_base)
+    ok = (j >= 0) & (j < n_bin)
+    jj = j[ok]
+    tables = {} if phases is None else phases
+    z = [np.zeros((int(ok.sum()), F)) for _ in range(2 * M)]                   # one contiguous [sample, frequency] array per component
+    has = np.zeros(M, bool)
+    for k in range(R):
+        if not live[k] or not (c[:, k] != 0.0).any():
+            continue
+        pair = (int(tin[k]), int(tout[k]))
+        if pair not in tables:
+            tau = np.where(ok, T[:B, pair[1] - 1] - T[:B, pair[0] - 1], 0.0)      # (samples out of range are not projected)
+            tables[pair] = matsubara_phase_table(tau, beta, freq, fermionic)
+        s, cs = (v[:B][ok] for v in tables[pair])
+        tre, tim = t[ok, k, None] * cs, t[ok, k, None] * s
+        for m in range(M):
+            if c[m, k] != 0.0:
+                pa, pb = c[m, k] * tre, c[m, k] * tim
+                z[m] = z[m] + pa if has[m] else pa
+                z[M + m] = z[M + m] + pb if has[m] else pb
+                has[m] = True
+    has2 = np.concatenate([has, has])
+    fobs = np.full((n_bin, F, 2 * M), np.nan)
+    fcov = np.full((n_bin, F, 2 * M, 2 * M), np.nan)
+    s_obs, s_cov = np.zeros((n_bin, F, 2 * M)), np.zeros((n_bin, F, 2 * M, 2 * M))
+    cell = (jj[:, None] * F + np.arange(F)[None, :]).ravel()                    # (bin, frequency) of every entry of a component
+
+    def per_bin(v):
+        return np.bincount(cell, v.ravel(), n_bin * F).reshape(n_bin, F)
+
+    for p in range(2 * M):
+        if not has2[p]:
+            continue
+        fobs[:, :, p] = per_bin(z[p])
+        s_obs[:, :, p] = per_bin(np.abs(z[p]))
+        for q in range(p, 2 * M):
+            if not has2[q]:
+                continue
+            pr = z[p] * z[q]
+            fcov[:, :, p, q] = fcov[:, :, q, p] = per_bin(pr)
+            s_cov[:, :, p, q] = s_cov[:, :, q, p] = per_bin(np.abs(pr))
+    return fobs, fcov, s_obs, s_cov
 
 
 def vegas_sample_device_grouped(d_grid: int, n_dim: int, n_grid: int, col, d_cdf: int, n_bin: int, bin_base: int, d_ext: int, ext_col, polar,

@@ -449,6 +449,49 @@ class GraphFunc:
                                                       B=B, stream=st)
         return (obs, cov, acc, acc2) if moments else (obs, cov)
 
+    def accumulate_freq_observables(self, leaf, T, freq, root_tau_in, root_tau_out, beta: float, coef, fermionic: bool = True, bins=None,
+                                    n_bin: int = 1, weight=None, fobs=None, fcov=None, sums=None, projection: bool = False,
+                                    bin_base: int = 0, n_sample: Optional[int] = None):
+        """Linear combinations of the PROJECTED roots and their second moments: the error bar of a frequency-resolved sum, difference
+        or series of roots that share their samples.  With ``tre_k`` / ``tim_k`` the real and imaginary parts of root ``k`` times the
+        phase of its own time pair at frequency ``f``, as :meth:`accumulate_matsubara` forms them, ``a_m = sum_k coef[m, k] * tre_k``
+        and ``b_m`` the same with ``tim_k`` (left folds over ascending ``k``, zero coefficients skipped) and ``z = (a_0 .., b_0 ..)``,
+        the samples of bin ``j`` add ``z_p`` to ``fobs[j, f, p]`` and ``z_p * z_q`` to ``fcov[j, f, p, q]`` (symmetric, both triangles
+        written).  ``coef``: host real ``[M, R]`` with ``M <= capi.FDG_FREQ_OBS_MAX``; ``fobs`` / ``fcov``: contiguous float64
+        ``[n_bin, n_freq, 2 M]`` / ``[n_bin, n_freq, 2 M, 2 M]`` CUDA tensors, added to (zeros when None).  ``projection=True`` (or
+        ``sums`` given): the per-root sums of :meth:`accumulate_matsubara` too, with its bits, from the same evaluation of the roots.
+        Returns ``(fobs, fcov)`` or ``(fobs, fcov, sums)``; :func:`mc_covariance` on ``fobs`` / ``fcov`` with the leading two axes
+        folded gives the mean and covariance of the ``2 M`` real components.  Deterministic: no float atomics
+        (fdg_accumulate_device_freq_observables)."""
+        import numpy as np
+        import torch
+        B, n_bin, bins, weight, strides = self._binned_args(leaf, bins, n_bin, weight, n_sample, bins_optional=True)
+        if not (_is_torch(T) and T.is_cuda and T.device == leaf.device and T.dtype == torch.float64 and T.dim() == 2 and T.shape[0] >= B):
+            raise ValueError("T must be a float64 [B, n_tau] CUDA tensor on the leaves' device")
+        n_freq = len(freq)
+        if not (1 <= n_freq <= capi.FDG_MATSUBARA_FREQ_MAX and n_bin * n_freq <= capi.FDG_BIN_MAX):
+            raise ValueError(f"need 1 .. {capi.FDG_MATSUBARA_FREQ_MAX} frequencies and n_bin * n_freq <= {capi.FDG_BIN_MAX}")
+        if len(root_tau_in) != self.n_root or len(root_tau_out) != self.n_root:
+            raise ValueError("root_tau_in and root_tau_out hold one label per root")
+        c = np.ascontiguousarray(coef, dtype=np.float64)
+        if c.ndim != 2 or c.shape[1] != self.n_root or not (1 <= c.shape[0] <= capi.FDG_FREQ_OBS_MAX):
+            raise ValueError(f"coef must be [n_obs, n_root = {self.n_root}] with 1 <= n_obs <= {capi.FDG_FREQ_OBS_MAX}")
+        P = 2 * c.shape[0]
+        fobs = self._out(fobs, (n_bin, n_freq, P), leaf, "fobs")
+        fcov = self._out(fcov, (n_bin, n_freq, P, P), leaf, "fcov")
+        projection = projection or sums is not None
+        if projection:
+            sums = self._out(sums, (4, n_bin, n_freq, self.n_root), leaf, "sums")
+        self._distinct("fobs, fcov and sums", fobs, fcov, sums)
+        p = [sums[i].data_ptr() if projection else 0 for i in range(4)]
+        desc, _keep = capi.make_matsubara(freq, fermionic, root_tau_in, root_tau_out, beta, T.shape[1], p[0], p[1], p[2], p[3],
+                                          T.data_ptr(), T.stride(0), T.stride(1))
+        fo, _keep_c = capi.make_freq_observables(c, fobs.data_ptr(), fcov.data_ptr())
+        with self._stream(leaf) as st:
+            self.handle.accumulate_device_freq_observables(leaf.data_ptr(), *strides, 0 if bins is None else bins.data_ptr(), int(bin_base),
+                                                           n_bin, 0 if weight is None else weight.data_ptr(), fo, desc, B=B, stream=st)
+        return (fobs, fcov, sums) if projection else (fobs, fcov)
+
     def _binned_args(self, leaf, bins, n_bin, weight, n_sample, bins_optional=False):
         """The checks of :meth:`accumulate_binned` / :meth:`accumulate_moments`: (n_sample, n_bin, bins, weight, leaf strides), bins and
         weight contiguous (the caller holds them until the launch is queued)."""

@@ -445,6 +445,199 @@ fdg_obs_reduce(const double *__restrict__ partial, uint32_t n_seg, long ncol, ui
   }
 }
 
+// ---- Frequency observables: linear combinations of the PROJECTED roots and their covariance (include/fdg.h:
+// fdg_[mc_]accumulate_device_freq_observables) ----
+// Per (sample, frequency) the components are z = (a_0 .. a_{M-1}, b_0 .. b_{M-1}), a_m and b_m the folds of coef[m][k] tre_k and
+// coef[m][k] tim_k; the value columns are the 2 M components, then the products z_p z_q, p <= q, row by row of the upper triangle:
+// V = 2 M + M (2 M + 1) columns.  fdg_obs_partials with 2 M rows and a histogram row per (bin, frequency): one workgroup per (segment of
+// the chunk's tiles, slice of FS consecutive frequencies, slice of CS consecutive columns), the slice's histogram (n_bin x FS x CS
+// doubles) in LDS, the tiles dealt to the four waves as there.
+//  * A wave sorts its tile's lanes by (bin, lane) once, before any root is touched; a lane then forms the values of the sample whose
+//    key it holds.  Unlike a bin, every frequency of the slice takes the sample: the frequencies are walked one after the other with
+//    the same keys and runs.
+//  * Per frequency the slice's root records are walked in ascending k: t = w_g(k) root_k as the moments pass forms it, x = tau / beta
+//    and (s, c) = matsubara_phase_of(x, mult[f]) as the projection pass forms them (a record whose pair of time labels is the record's
+//    before it keeps that phase: the same operands, the same bits), tre = t c, tim = t s; every term folds coef * tre or coef * tim
+//    into its component's word of the lane's LDS stash ([component of the slice][256 lanes]).
+//  * The columns are scanned kObsGroup at a time and the waves add their run heads in wave order, as in fdg_obs_partials.
+//  * Chunks and segments chain through partial [segment][bin][frequency][V], summed in segment order by fdg_fobs_reduce.
+// utab, per call: four words per COLUMN slice {components needed, root records, offset of the slice's words in utab, offset of its
+// coefficients in dtab}; the slice's words are colA[CS], colB[CS] (stash rows, as in fdg_obs_partials), then kFobsRec words per root
+// record {root, place of its weight column (bit 31: the time labels of the record before), first term, end of terms, tin, tout
+// (0-based components of T)}, then a word per term (stash row, bit 31: the term starts its component's fold, bit 30: the term takes
+// tim, else tre).  dtab: mult[FDG_MATSUBARA_FREQ_MAX], then the terms' coefficients.
+constexpr uint32_t kFobsRec = 6;
+constexpr uint32_t kFobsSame = 0x80000000u;
+constexpr uint32_t kFobsIm = 0x40000000u;
+
+__global__ void __launch_bounds__(256)
+fdg_fobs_partials(const double *__restrict__ root, long ld, long n, const int32_t *__restrict__ bins, int32_t bin_base, uint32_t n_bin,
+                  const double *__restrict__ weight, long wstride, uint32_t n_wcol, const double *__restrict__ T, long ts, long tc,
+                  double beta, uint32_t n_freq, uint32_t FS, uint32_t n_fslice, uint32_t V, uint32_t CS, uint32_t n_cslice, long seg_tiles,
+                  double *__restrict__ partial, int first, const uint32_t *__restrict__ utab, const double *__restrict__ dtab) {
+  extern __shared__ double hist[];                        // [bin][FS][CS], then the stash [row][256]
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t n_grp = n_fslice * n_cslice, grp = blockIdx.x % n_grp, seg = blockIdx.x / n_grp;
+  const uint32_t cslice = grp % n_cslice, fslice = grp / n_cslice;
+  const uint32_t c0 = cslice * CS, cn = min(CS, V - c0), fb = fslice * FS, fn = min(FS, n_freq - fb);
+  const uint32_t *hdr = utab + (size_t)cslice * 4u;
+  const uint32_t n_rec = hdr[1];
+  const uint32_t *colA = utab + hdr[2], *colB = colA + CS, *rec = colB + CS, *tslot = rec + (size_t)n_rec * kFobsRec;
+  const double *tcoef = dtab + hdr[3];
+  const uint32_t per = n_bin * FS * CS;                   // words of the histogram in LDS
+  double *stash = hist + per + threadIdx.x;
+  double *slab = partial + (size_t)seg * n_bin * n_freq * V;
+  // (j, fl, cl) of LDS word i, and its place in the slab
+  auto slab_at = [&](uint32_t i, bool &live) {
+    const uint32_t cl = i % CS, fl = (i / CS) % FS, j = i / (CS * FS);
+    live = cl < cn && fl < fn;
+    return ((size_t)j * n_freq + fb + fl) * V + c0 + cl;
+  };
+  for (uint32_t i = threadIdx.x; i < per; i += 256) {
+    bool live;
+    const size_t at = slab_at(i, live);
+    hist[i] = (first || !live) ? 0.0 : slab[at];
+  }
+  __syncthreads();
+  const SegTiles sg = seg_tiles_of(n, seg, seg_tiles);
+  const long t0 = sg.t0, t1 = sg.t1, rounds = sg.rounds;
+  int32_t bin_n;
+  auto fetch = [&](long r) {                              // the bin of this lane's sample of round r, one round ahead (index clamped)
+    const long b = min((t0 + r * (long)kBinWaves + wave) * 64 + lane, n - 1);
+    bin_n = bins ? bins[b] : bin_base;
+  };
+  fetch(0);
+  for (long r = 0; r < rounds; ++r) {
+    const long t = t0 + r * (long)kBinWaves + wave, b = t * 64 + lane;
+    const int64_t jb = (int64_t)bin_n - (int64_t)bin_base;
+    const bool in = t < t1 && b < n && jb >= 0 && jb < (int64_t)n_bin;
+    uint32_t key = in ? ((uint32_t)jb << 6) | lane : kKeyInvalid | lane;
+    fetch(r + 1);
+    const uint64_t valid = __ballot(key < kKeyInvalid);
+    bool head = false, ok = false;
+    uint32_t j = 0, end = lane;
+    size_t bs = 0;
+    double wv[kGrpCols] = {};
+    if (valid) {
+      const uint32_t src = wave_sort_keys(key, lane, valid);
+      wave_runs(key, lane, j, head, end);
+      ok = key < kKeyInvalid;
+      // the sample this lane now stands for (clamped into the chunk: what an invalid key loads is selected away below)
+      bs = (size_t)min(t * 64 + (long)src, n - 1);
+#pragma unroll
+      for (uint32_t c = 0; c < kGrpCols; ++c)
+        if (c < n_wcol) wv[c] = weight[(size_t)c * (size_t)wstride + bs];
+    }
+    for (uint32_t fl = 0; fl < fn; ++fl) {
+      if (valid) {
+        const double mult = dtab[fb + fl];
+        double ps = 0.0, pc = 0.0;                        // the phase of the last pair of time labels
+        for (uint32_t i0 = 0; i0 < n_rec; i0 += 4) {
+          double rv[4];
+#pragma unroll
+          for (uint32_t u = 0; u < 4; ++u) rv[u] = root[(size_t)rec[(size_t)min(i0 + u, n_rec - 1u) * kFobsRec] * (size_t)ld + bs];
+#pragma unroll
+          for (uint32_t u = 0; u < 4; ++u) {
+            if (i0 + u >= n_rec) break;
+            const uint32_t *e = rec + (size_t)(i0 + u) * kFobsRec;
+            const uint32_t wc = e[1] & ~kFobsSame;
+            double wk = wv[0];
+#pragma unroll
+            for (uint32_t c = 1; c < kGrpCols; ++c) wk = wc == c ? wv[c] : wk;
+            const double tk = n_wcol ? wk * rv[u] : rv[u];
+            if (!(e[1] & kFobsSame)) {
+              const double ti = T[(long)bs * ts + (long)e[4] * tc], to = T[(long)bs * ts + (long)e[5] * tc];
+              const double tau = to - ti;
+              const double x = ok ? tau / beta : 0.0;
+              matsubara_phase_of(x, mult, ps, pc);
+            }
+            const double tre = tk * pc, tim = tk * ps;
+            for (uint32_t tt = e[2]; tt < e[3]; ++tt) {
+              const uint32_t sl = tslot[tt];
+              double *o = stash + (size_t)(sl & ~(kObsFirst | kFobsIm)) * 256u;
+              const double p = tcoef[tt] * ((sl & kFobsIm) ? tim : tre);
+              *o = (sl & kObsFirst) ? p : *o + p;
+            }
+          }
+        }
+      }
+      for (uint32_t g0 = 0; g0 < cn; g0 += kObsGroup) {
+        double s[kObsGroup];
+        if (valid) {
+#pragma unroll
+          for (uint32_t i = 0; i < kObsGroup; ++i) {
+            const uint32_t cl = min(g0 + i, cn - 1u), a = colA[cl], c = colB[cl];
+            double v = 0.0;
+            if (a != kObsNone) {
+              v = stash[(size_t)a * 256u];
+              if (c != kObsNone) v = v * stash[(size_t)c * 256u];
+            }
+            s[i] = ok ? v : 0.0;                          // selected, never multiplied by 0
+          }
+          for (uint32_t d = 1; d < 64; d <<= 1) {         // segmented suffix scan, as in fdg_binned_partials
+            const bool take = lane + d <= end;
+            if (!__ballot(take)) break;
+#pragma unroll
+            for (uint32_t i = 0; i < kObsGroup; ++i) {
+              const double up = __shfl_down(s[i], d);
+              if (take) s[i] = s[i] + up;
+            }
+          }
+        }
+        for (uint32_t w = 0; w < kBinWaves; ++w) {        // the waves' turns, in wave order
+          if (wave == w && head) {
+            double *hw = hist + ((size_t)j * FS + fl) * CS + g0;
+#pragma unroll
+            for (uint32_t i = 0; i < kObsGroup; ++i)
+              if (g0 + i < cn) hw[i] = hw[i] + s[i];
+          }
+          bin_barrier();
+        }
+      }
+    }
+  }
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < per; i += 256) {
+    bool live;
+    const size_t at = slab_at(i, live);
+    if (live) slab[at] = hist[i];
+  }
+}
+
+// d_fobs[j][f][p] and d_fcov[j][f][p][q] += the segments' partials [segment][bin][frequency][V], with fdg_obs_reduce's order and
+// rules over the 2 M components: the column of a product goes to [p][q] and to its mirror [q][p]; components without a term (bit p of
+// live clear) leave their column of d_fobs and their rows and columns of d_fcov alone.
+__global__ void __launch_bounds__(256)
+fdg_fobs_reduce(const double *__restrict__ partial, uint32_t n_seg, long ncol, uint32_t n_comp, uint32_t V, uint32_t C, uint32_t live,
+                double *__restrict__ fobs, double *__restrict__ fcov) {
+  __shared__ double sh[256];
+  const uint32_t Q = 256u / C, q = threadIdx.x / C, cl = threadIdx.x % C;
+  const long c = (long)blockIdx.x * C + cl;
+  double s = 0.0;
+  if (c < ncol)
+    for (uint32_t sg = q; sg < n_seg; sg += Q) s = s + partial[(size_t)sg * (size_t)ncol + (size_t)c];
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  if (q == 0 && c < ncol) {
+    double t = sh[cl];
+    for (uint32_t qq = 1; qq < Q && qq < n_seg; ++qq) t = t + sh[qq * C + cl];
+    const size_t row = (size_t)(c / V);                   // bin * n_freq + frequency
+    const uint32_t v = (uint32_t)(c % V);
+    if (v < n_comp) {
+      if ((live >> v) & 1u) fobs[row * n_comp + v] = fobs[row * n_comp + v] + t;
+    } else {
+      uint32_t a = 0, p = v - n_comp;                     // the p-th entry of the upper triangle, row by row
+      while (p >= n_comp - a) { p -= n_comp - a; ++a; }
+      const uint32_t cc = a + p;
+      if (((live >> a) & 1u) && ((live >> cc) & 1u)) {
+        double *m = fcov + row * n_comp * n_comp;
+        m[a * n_comp + cc] = m[a * n_comp + cc] + t;
+        if (cc != a) m[cc * n_comp + a] = m[cc * n_comp + a] + t;
+      }
+    }
+  }
+}
+
 // ---- VEGAS importance sampling: the map, the sampler, the training pass (include/fdg.h: fdg_vegas_sample_device, fdg_accumulate_device_vegas) ----
 // The cell of variable d that sample `sample` (a global index: the Philox counter) falls in, and y = u * G; every operation one rounded fp64
 // operation.  The sampler and the training pass both call this: the pass reads no cell array.
@@ -1213,6 +1406,9 @@ struct BinnedCall {
   const fdg_weight_groups *wg = nullptr;   // the grouped calls: d_weight holds one column per group
   const ObsRun *ob = nullptr;        // the observables calls: the observables pass runs too; d_acc and d_acc2 may then both be null
   const StratRun *sr = nullptr;      // the stratified calls: the training pass reads the hypercubes, the per-hypercube pass runs too
+  // the frequency-observables calls: their pass runs too, with mz's frequencies, time labels, beta and T; mz's four arrays may then
+  // all be null (no per-root projection) and ob may be null
+  const fdg_freq_observables *fo = nullptr;
 };
 
 constexpr size_t page_up(size_t bytes) { return (bytes + 4095) & ~(size_t)4095; }
@@ -1433,6 +1629,118 @@ ObsTables obs_tables(const fdg_graph *g, const ObsPlan &q, const fdg_observables
   return t;
 }
 
+// How the frequency-observables pass is cut.  A histogram row is a (bin, frequency) pair of V = 2 M + M (2 M + 1) columns.
+// Frequencies are sliced first (a frequency slice forms only its own phases): as many whole frequencies of V columns as the binned
+// plan's LDS budget holds, spread evenly over the slices; only when not even one fits are the columns sliced too, as obs_plan slices
+// them (one column of more than 8192 bins takes what one root of FDG_BIN_MAX bins takes).  Segments: the binned call's own count
+// whenever the slab [segment][bin][frequency][V] fits in 2 kBinSlabBytes, else the largest count that fits.  A function of
+// (n_sample, n_bin, n_freq, n_obs, n_root, FDG_ROOT_SCRATCH_MB) only.
+struct FobsPlan {
+  uint32_t V = 1, fs = 1, n_fslice = 1, cs = 1, n_cslice = 1, n_seg = 1;
+  size_t hist_bytes = 0, slab_alloc = 0;
+};
+
+FobsPlan fobs_plan(const BinnedPlan &p, uint32_t n_bin, uint32_t n_freq, uint32_t n_obs) {
+  FobsPlan q;
+  q.V = 2u * n_obs + n_obs * (2u * n_obs + 1u);
+  const uint32_t fit = (uint32_t)std::max<size_t>(1, kBinLdsBudget / ((size_t)n_bin * 8u));     // words per bin
+  if (fit >= q.V) {
+    const uint32_t ffit = fit / q.V;
+    q.n_fslice = (n_freq + ffit - 1) / ffit;
+    q.fs = (n_freq + q.n_fslice - 1) / q.n_fslice;
+    q.cs = q.V;
+  } else {
+    q.n_cslice = (q.V + fit - 1) / fit;
+    q.cs = (q.V + q.n_cslice - 1) / q.n_cslice;
+  }
+  q.n_fslice = (n_freq + q.fs - 1) / q.fs;
+  q.n_cslice = (q.V + q.cs - 1) / q.cs;
+  q.hist_bytes = (size_t)n_bin * q.fs * q.cs * 8u;
+  const size_t seg_bytes = (size_t)n_bin * n_freq * q.V * 8u;
+  q.n_seg = (uint32_t)std::max<size_t>(1, std::min<size_t>(p.n_seg, 2u * kBinSlabBytes / seg_bytes));
+  q.slab_alloc = page_up((size_t)q.n_seg * seg_bytes);
+  return q;
+}
+
+// The tables of fdg_fobs_partials for one call (the layout is stated there), built from the host coefficients and the descriptor's
+// frequencies and time labels: need = the most stash rows a column slice uses, live = bit p set when component p (a_m: m, b_m:
+// M + m) has a term.
+struct FobsTables {
+  std::vector<uint32_t> u;
+  std::vector<double> d;
+  uint32_t need = 1, live = 0;
+};
+
+FobsTables fobs_tables(const fdg_graph *g, const FobsPlan &q, const fdg_freq_observables &fo, const fdg_matsubara &mz,
+                       const fdg_weight_groups *wg) {
+  const uint32_t R = g->prog.R, M = fo.n_obs, P = 2u * M;
+  FobsTables t;
+  auto term = [&](uint32_t p, uint32_t k) { return g->prog.root_slot[k] != FDG_NO_ROOT && fo.coef[(size_t)(p % M) * R + k] != 0.0; };
+  for (uint32_t p = 0; p < P; ++p)
+    for (uint32_t k = 0; k < R; ++k)
+      if (term(p, k)) { t.live |= 1u << p; break; }
+  t.d.assign(FDG_MATSUBARA_FREQ_MAX, 0.0);
+  for (uint32_t f = 0; f < mz.n_freq; ++f) t.d[f] = matsubara_multiplier(mz.freq[f], mz.fermionic);
+  std::vector<uint32_t> pa, pc;                            // the factors of every value column
+  for (uint32_t p = 0; p < P; ++p) { pa.push_back(p); pc.push_back(kObsNone); }
+  for (uint32_t a = 0; a < P; ++a)
+    for (uint32_t c = a; c < P; ++c) { pa.push_back(a); pc.push_back(c); }
+  t.u.assign((size_t)q.n_cslice * 4u, 0u);
+  for (uint32_t s = 0; s < q.n_cslice; ++s) {
+    const uint32_t c0 = s * q.cs, cn = std::min(q.cs, q.V - c0);
+    std::vector<uint32_t> slot(P, kObsNone);               // the stash row of every component the slice needs, ascending
+    std::vector<uint32_t> colA(q.cs, kObsNone), colB(q.cs, kObsNone);
+    uint32_t used = 0;
+    for (uint32_t cl = 0; cl < cn; ++cl) {
+      const uint32_t a = pa[c0 + cl], c = pc[c0 + cl];
+      if (!((t.live >> a) & 1u) || (c != kObsNone && !((t.live >> c) & 1u))) continue;
+      used |= 1u << a;
+      if (c != kObsNone) used |= 1u << c;
+    }
+    uint32_t n_need = 0;
+    for (uint32_t p = 0; p < P; ++p)
+      if ((used >> p) & 1u) slot[p] = n_need++;
+    for (uint32_t cl = 0; cl < cn; ++cl) {
+      const uint32_t a = pa[c0 + cl], c = pc[c0 + cl];
+      if (slot[a] == kObsNone || (c != kObsNone && slot[c] == kObsNone)) continue;
+      colA[cl] = slot[a];
+      colB[cl] = c == kObsNone ? kObsNone : slot[c];
+    }
+    std::vector<uint32_t> recs, terms;
+    std::vector<bool> started(P, false);
+    const size_t d0 = t.d.size();
+    int32_t last_in = -1, last_out = -1;
+    for (uint32_t k = 0; k < R; ++k) {
+      const uint32_t tb = (uint32_t)terms.size();
+      for (uint32_t p = 0; p < P; ++p)
+        if (slot[p] != kObsNone && term(p, k)) {
+          terms.push_back(slot[p] | (started[p] ? 0u : kObsFirst) | (p >= M ? kFobsIm : 0u));
+          started[p] = true;
+          t.d.push_back(fo.coef[(size_t)(p % M) * R + k]);
+        }
+      if (terms.size() == tb) continue;
+      const int32_t tin = mz.root_tau_in[k] - 1, tout = mz.root_tau_out[k] - 1;
+      const bool same = !recs.empty() && tin == last_in && tout == last_out;
+      const uint32_t rk[kFobsRec] = {k, (wg && wg->n_group > 1 ? wg->root_group[k] : 0u) | (same ? kFobsSame : 0u), tb,
+                                     (uint32_t)terms.size(), (uint32_t)tin, (uint32_t)tout};
+      recs.insert(recs.end(), rk, rk + kFobsRec);
+      last_in = tin;
+      last_out = tout;
+    }
+    uint32_t *hdr = t.u.data() + (size_t)s * 4u;
+    hdr[0] = n_need;
+    hdr[1] = (uint32_t)(recs.size() / kFobsRec);
+    hdr[2] = (uint32_t)t.u.size();
+    hdr[3] = (uint32_t)d0;
+    t.need = std::max(t.need, n_need);
+    t.u.insert(t.u.end(), colA.begin(), colA.end());
+    t.u.insert(t.u.end(), colB.begin(), colB.end());
+    t.u.insert(t.u.end(), recs.begin(), recs.end());
+    t.u.insert(t.u.end(), terms.begin(), terms.end());
+  }
+  return t;
+}
+
 // How the per-hypercube pass is cut: the record buffers of the levels (slots: two per wave of the level below).  A chunk's levels
 // alternate between a and b, the chunks' own records (two per chunk) lie in c and go through a and b again after the last chunk.
 // A function of (n_sample, n_root, FDG_ROOT_SCRATCH_MB) only.
@@ -1526,7 +1834,9 @@ void raise_lds_limits() {
     const int train_grp = (int)(kBinLdsBudget + 2u * kBinWaves * 64u * 8u * FDG_WEIGHT_GROUP_MAX);
     // the observables pass: a histogram slice and the stash, 2 KiB per row (every row beside kBinLdsBudget, two beside one column of FDG_BIN_MAX bins)
     const int obs = (int)std::max<size_t>(kBinLdsBudget + FDG_OBS_MAX * 2048u, FDG_BIN_MAX * 8u + 2u * 2048u);
+    static_assert(2 * FDG_FREQ_OBS_MAX <= FDG_OBS_MAX, "the frequency observables' stash is sized by the observables'");
     std::vector<std::pair<const void *, int>> limits = {{(const void *)fdg_obs_partials, obs},
+                                                        {(const void *)fdg_fobs_partials, obs},   // 2 M components in the place of the rows
                                                         {(const void *)fdg_binned_partials<1, kSplit>, hist},
                                                         {(const void *)fdg_binned_partials<1, kSplit, true>, hist},
                                                         {(const void *)fdg_vegas_bin_partials<false>, hist},
@@ -1622,7 +1932,11 @@ int check_matsubara(const fdg_graph *g, const BinnedCall &c, const fdg_matsubara
   if (!g) { set_error("null handle"); return FDG_E_INVALID; }
   if (!m) { set_error("null descriptor"); return FDG_E_INVALID; }
   if (c.B < 0) { set_error("n_sample < 0"); return FDG_E_INVALID; }
-  if (!m->d_acc_re || !m->d_acc_im || !m->d_acc2_re || !m->d_acc2_im) { set_error("null device buffer"); return FDG_E_INVALID; }
+  const bool no_sums = !m->d_acc_re && !m->d_acc_im && !m->d_acc2_re && !m->d_acc2_im;
+  if (c.fo && !no_sums && (!m->d_acc_re || !m->d_acc_im || !m->d_acc2_re || !m->d_acc2_im)) {
+    set_error("some but not all of the descriptor's four arrays are NULL"); return FDG_E_INVALID;
+  }
+  if (!c.fo && (!m->d_acc_re || !m->d_acc_im || !m->d_acc2_re || !m->d_acc2_im)) { set_error("null device buffer"); return FDG_E_INVALID; }
   if (!m->freq || !m->root_tau_in || !m->root_tau_out) { set_error("null host array in the descriptor"); return FDG_E_INVALID; }
   if (!m->d_T && !mc_T) { set_error("null device buffer"); return FDG_E_INVALID; }
   if (!c.d_acc != !c.d_acc2) { set_error("d_acc and d_acc2 go together"); return FDG_E_INVALID; }
@@ -1695,6 +2009,29 @@ int check_observables(const fdg_graph *g, const BinnedCall &c, const fdg_matsuba
   return check_grouped(g, c, m, mc_T, true);
 }
 
+// ... and the frequency-observables calls': the descriptor first, then the projection it stands on, then the observables calls'
+// cases with ob optional (without ob: the grouped calls' with wg optional).  check_matsubara lets the four per-root arrays be NULL
+// together when c.fo is set.
+int check_freq_observables(const fdg_graph *g, const BinnedCall &c, const fdg_matsubara *m, const double *mc_T) {
+  if (!g) { set_error("null handle"); return FDG_E_INVALID; }
+  const fdg_freq_observables *o = c.fo;
+  if (!o) { set_error("null frequency observables"); return FDG_E_INVALID; }
+  if (!o->coef || !o->d_fobs || !o->d_fcov) { set_error("null array in the frequency observables"); return FDG_E_INVALID; }
+  if (o->n_obs == 0) { set_error("n_obs == 0 in the frequency observables"); return FDG_E_INVALID; }
+  if (o->n_obs > FDG_FREQ_OBS_MAX) { set_error("n_obs > FDG_FREQ_OBS_MAX"); return FDG_E_UNSUPPORTED; }
+  for (size_t i = 0; i < (size_t)o->n_obs * g->prog.R; ++i)
+    if (!std::isfinite(o->coef[i])) { set_error("a coefficient of the frequency observables is not finite"); return FDG_E_INVALID; }
+  if (!m) { set_error("null descriptor: the frequency observables need mz"); return FDG_E_INVALID; }
+  const fdg_observables *ob = c.ob ? c.ob->ob : nullptr;
+  const double *out[11] = {o->d_fcov, c.d_acc, c.d_acc2, c.vg ? c.vg->d_hist : nullptr, c.vg ? c.vg->d_hist_bin : nullptr,
+                           m->d_acc_re, m->d_acc_im, m->d_acc2_re, m->d_acc2_im, ob ? ob->d_obs : nullptr, ob ? ob->d_cov : nullptr};
+  for (int a = 0; a < 11; ++a)
+    if (out[a] && (out[a] == o->d_fobs || (a && out[a] == o->d_fcov))) {
+      set_error("d_fobs or d_fcov is the same buffer as another output of the call"); return FDG_E_INVALID;
+    }
+  return ob ? check_observables(g, c, m, mc_T) : check_grouped(g, c, m, mc_T, true);
+}
+
 // The chunk loop shared by the entry points (caller holds g->mu, stream bound): eval(c0, n, roots, ld) writes the roots of samples
 // c0 .. c0 + n - 1 column-major into roots (root k of sample c0 + b at roots[k * ld + b]).  c.d_acc2 != null: the second moment too.
 // c.vg != null (the VEGAS calls): after a chunk's moments pass the training pass runs over the same roots, its partials behind the
@@ -1718,6 +2055,7 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
   VegasPlan q;
   if (vg) q = vegas_plan(p, *vg, R, n_bin, grp_t ? NG : 1u);
   const MatsubaraRun *mz = c.mz;
+  const bool proj = mz && mz->m->d_acc_re;      // (the frequency-observables calls may leave the four per-root arrays out)
   MatsubaraPlan mp;
   if (mz) mp = matsubara_plan(p, R, n_bin, mz->m->n_freq);
   // the projection's slab and table lie behind everything the call would reserve without it
@@ -1738,6 +2076,16 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
     ot = obs_tables(g, op, *ob, wg);
     obs_bytes = op.slab_alloc + page_up(ot.d.size() * 8u) + page_up(ot.u.size() * 4u);
   }
+  // ... and the frequency observables' slab and tables behind that
+  const fdg_freq_observables *fo = c.fo;
+  FobsPlan fp;
+  FobsTables ft;
+  size_t fobs_bytes = 0;
+  if (fo) {
+    fp = fobs_plan(p, n_bin, mz->m->n_freq, fo->n_obs);
+    ft = fobs_tables(g, fp, *fo, *mz->m, wg);
+    fobs_bytes = fp.slab_alloc + page_up(ft.d.size() * 8u) + page_up(ft.u.size() * 4u);
+  }
   // ... and the record buffers of the per-hypercube pass behind that
   const StratRun *sr = c.sr;
   StratPlan sp;
@@ -1746,7 +2094,7 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
     sv = vegas_strat(sr->strat, vg->D);
     sp = strat_plan(p, c.B, R, sv.H);
   }
-  int rc = ensure_root_scratch(g, proj_bytes + grp_bytes + obs_bytes + sp.bytes);
+  int rc = ensure_root_scratch(g, proj_bytes + grp_bytes + obs_bytes + fobs_bytes + sp.bytes);
   if (rc) return rc;
   double *roots = (double *)g->d_ws2, *partial = (double *)((char *)g->d_ws2 + root_bytes);
   const uint8_t *live = nullptr;
@@ -1838,10 +2186,19 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
     if (!ot.d.empty()) HIP_TRY(hipMemcpyAsync(d_odtab, ot.d.data(), ot.d.size() * 8u, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_outab, ot.u.data(), ot.u.size() * 4u, hipMemcpyHostToDevice, st));
   }
+  double *fpartial = nullptr, *d_fdtab = nullptr;
+  uint32_t *d_futab = nullptr;
+  if (fo) {
+    fpartial = (double *)((char *)g->d_ws2 + proj_bytes + grp_bytes + obs_bytes);
+    d_fdtab = (double *)((char *)fpartial + fp.slab_alloc);
+    d_futab = (uint32_t *)((char *)d_fdtab + page_up(ft.d.size() * 8u));
+    HIP_TRY(hipMemcpyAsync(d_fdtab, ft.d.data(), ft.d.size() * 8u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_futab, ft.u.data(), ft.u.size() * 4u, hipMemcpyHostToDevice, st));
+  }
   // the record buffers {keys, values, slots} a, b (the levels) and c (the chunks)
   struct StratBuf { int32_t *key; double *val; long cap; } sa = {}, sb = {}, sc = {};
   if (sr) {
-    char *at = (char *)g->d_ws2 + proj_bytes + grp_bytes + obs_bytes;
+    char *at = (char *)g->d_ws2 + proj_bytes + grp_bytes + obs_bytes + fobs_bytes;
     for (auto bc : {std::make_pair(&sa, sp.cap_a), std::make_pair(&sb, sp.cap_b), std::make_pair(&sc, sp.cap_c)}) {
       *bc.first = {(int32_t *)at, (double *)(at + page_up((size_t)bc.second * 4u)), bc.second};
       at += StratPlan::buf_bytes(bc.second, sp.V2);
@@ -1885,7 +2242,14 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
                          (ntile + op.n_seg - 1) / op.n_seg, opartial, first, d_outab, d_odtab);
       HIP_TRY(hipGetLastError());
     }
-    if (mz) {
+    if (fo) {
+      hipLaunchKernelGGL(fdg_fobs_partials, dim3(fp.n_seg * fp.n_fslice * fp.n_cslice), dim3(256), fp.hist_bytes + (size_t)ft.need * 2048u, st,
+                         roots, (long)p.Bc, n, bins, c.bin_base, n_bin, w, wstride, w ? (grp_w ? NG : 1u) : 0u, mz->d_T + c0 * mz->ts,
+                         (long)mz->ts, (long)mz->tc, mz->m->beta, mz->m->n_freq, fp.fs, fp.n_fslice, fp.V, fp.cs, fp.n_cslice,
+                         (ntile + fp.n_seg - 1) / fp.n_seg, fpartial, first, d_futab, d_fdtab);
+      HIP_TRY(hipGetLastError());
+    }
+    if (proj) {
       hipLaunchKernelGGL(mpass, dim3(mp.n_seg * mp.n_grp), dim3(64 * mp.nw), mp.lds, st, roots, (long)p.Bc, n, bins, c.bin_base, n_bin, w,
                          mz->d_T + c0 * mz->ts, (long)mz->ts, (long)mz->tc, d_mtab, mz->m->beta, mz->m->n_freq, R, mp.rs, mp.fs, mp.n_fslice,
                          (ntile + mp.n_seg - 1) / mp.n_seg, mpartial, first, d_gtab, wstride);
@@ -1933,7 +2297,15 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
                        ot.rowlive, ob->d_obs, ob->d_cov);
     HIP_TRY(hipGetLastError());
   }
-  if (!rc && mz) {
+  if (!rc && fo) {
+    const long fcol = (long)n_bin * mz->m->n_freq * fp.V;
+    uint32_t FC = 1;
+    while (FC < 64 && (long)FC < fcol) FC <<= 1;
+    hipLaunchKernelGGL(fdg_fobs_reduce, dim3((unsigned)((fcol + FC - 1) / FC)), dim3(256), 0, st, fpartial, fp.n_seg, fcol, 2u * fo->n_obs,
+                       fp.V, FC, ft.live, fo->d_fobs, fo->d_fcov);
+    HIP_TRY(hipGetLastError());
+  }
+  if (!rc && proj) {
     // the four arrays += the segments' partials [segment][4][bin][frequency][root], in segment order: first both first moments, then both second
     const long mcol = ncol * mz->m->n_freq;
     const fdg_matsubara &m = *mz->m;
@@ -2257,6 +2629,38 @@ int fdg_mc_accumulate_device_observables(fdg_graph *g, const double *d_K, int64_
   const ObsRun orun{ob};
   const BinnedCall c{d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, stream, train ? &vg : nullptr, mz ? &mr : nullptr, wg, &orun};
   const int rc = check_observables(g, c, mz, d_T);
+  return rc ? rc : accumulate_mc(g, d_K, ks, kc, d_T, ts, tc, kF, beta, lambda, c);
+}
+
+int fdg_accumulate_device_freq_observables(fdg_graph *g, const double *d_leaf, int64_t ss, int64_t ls, int64_t lts, const int32_t *d_bin,
+                                           int32_t bin_base, uint32_t n_bin, const double *d_weight, const double *coef, uint64_t seed,
+                                           uint64_t sample_offset, uint32_t n_dim, uint32_t n_grid, double *d_acc, double *d_acc2,
+                                           double *d_hist, double *d_hist_bin, const fdg_matsubara *mz, const fdg_weight_groups *wg,
+                                           const fdg_observables *ob, const fdg_freq_observables *fo, int64_t B, void *stream) {
+  const bool train = n_dim != 0 || d_hist;
+  const VegasRun vg{coef, seed, sample_offset, n_dim, n_grid, d_hist, d_bin != nullptr, d_hist_bin};
+  const MatsubaraRun mr{mz, mz ? mz->d_T : nullptr, mz ? mz->t_sample_stride : 0, mz ? mz->t_comp_stride : 0};
+  const ObsRun orun{ob};
+  const BinnedCall c{d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, stream, train ? &vg : nullptr, mz ? &mr : nullptr, wg,
+                     ob ? &orun : nullptr, nullptr, fo};
+  const int rc = check_freq_observables(g, c, mz, nullptr);
+  return rc ? rc : accumulate_leaf(g, d_leaf, ss, ls, lts, c);
+}
+
+int fdg_mc_accumulate_device_freq_observables(fdg_graph *g, const double *d_K, int64_t ks, int64_t kc, const double *d_T, int64_t ts,
+                                              int64_t tc, double kF, double beta, double lambda, const int32_t *d_bin, int32_t bin_base,
+                                              uint32_t n_bin, const double *d_weight, const double *coef, uint64_t seed,
+                                              uint64_t sample_offset, uint32_t n_dim, uint32_t n_grid, double *d_acc, double *d_acc2,
+                                              double *d_hist, double *d_hist_bin, const fdg_matsubara *mz, const fdg_weight_groups *wg,
+                                              const fdg_observables *ob, const fdg_freq_observables *fo, int64_t B, void *stream) {
+  const bool train = n_dim != 0 || d_hist;
+  const VegasRun vg{coef, seed, sample_offset, n_dim, n_grid, d_hist, d_bin != nullptr, d_hist_bin};
+  const bool own_T = mz && mz->d_T;
+  const MatsubaraRun mr{mz, own_T ? mz->d_T : d_T, own_T ? mz->t_sample_stride : ts, own_T ? mz->t_comp_stride : tc};
+  const ObsRun orun{ob};
+  const BinnedCall c{d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, stream, train ? &vg : nullptr, mz ? &mr : nullptr, wg,
+                     ob ? &orun : nullptr, nullptr, fo};
+  const int rc = check_freq_observables(g, c, mz, d_T);
   return rc ? rc : accumulate_mc(g, d_K, ks, kc, d_T, ts, tc, kF, beta, lambda, c);
 }
 

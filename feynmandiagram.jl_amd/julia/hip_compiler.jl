@@ -630,6 +630,66 @@ function mc_accumulate_device_observables!(f::GraphFunc, d_obs::Ptr{Float64}, d_
     end
     return nothing
 end
+# Frequency observables: linear combinations of the PROJECTED roots and their covariance (fdg_accumulate_device_freq_observables).
+# coef is n_root x M column-major (coef[k, m]: the real factor of root k in observable m); d_fobs is 2M x n_freq x n_bin and d_fcov
+# 2M x 2M x n_freq x n_bin column-major (the components Re o_1 .. Re o_M, Im o_1 .. Im o_M), both added to.  The frequencies, the
+# roots' time labels (1-based), beta and T as accumulate_device_matsubara! takes them; d_sums = C_NULL: no per-root projected sums,
+# else the four arrays in a row as there.  These wrappers pass one weight column (or none), no weight groups and no unprojected
+# observables.  Unverified: written against the header, never run.
+struct _FdgFreqObservables
+    n_obs::UInt32
+    coef::Ptr{Float64}
+    d_fobs::Ptr{Float64}
+    d_fcov::Ptr{Float64}
+end
+function accumulate_device_freq_observables!(f::GraphFunc, d_fobs::Ptr{Float64}, d_fcov::Ptr{Float64}, coef::Matrix{Float64},
+    d_leaf::Ptr{Float64}, d_T::Ptr{Float64}, freq::Vector{Int}, root_tau_in::Vector{Int}, root_tau_out::Vector{Int}, B::Integer;
+    beta::Float64, n_tau::Integer, fermionic::Bool=true, d_sums::Ptr{Float64}=Ptr{Float64}(C_NULL),
+    d_weight::Ptr{Float64}=Ptr{Float64}(C_NULL), d_acc::Ptr{Float64}=Ptr{Float64}(C_NULL), d_acc2::Ptr{Float64}=Ptr{Float64}(C_NULL),
+    d_bin::Ptr{Int32}=Ptr{Int32}(C_NULL), n_bin::Integer=1, bin_base::Integer=1, train_coef::Union{Nothing,Vector{Float64}}=nothing,
+    seed::Integer=0, sample_offset::Integer=0, n_dim::Integer=0, n_grid::Integer=0, d_hist::Ptr{Float64}=Ptr{Float64}(C_NULL),
+    d_hist_bin::Ptr{Float64}=Ptr{Float64}(C_NULL), leaf_strides=(1, B), tile_stride::Integer=0, t_strides=(1, B),
+    stream::Ptr{Cvoid}=C_NULL)
+    a = [Int32.(v) for v in (freq, root_tau_in, root_tau_out)]
+    n = d_sums == C_NULL ? 0 : 8 * n_bin * length(freq) * length(root_tau_in)
+    GC.@preserve a coef begin
+        mz = _FdgMatsubara(length(freq), fermionic ? 1 : 0, pointer(a[1]), pointer(a[2]), pointer(a[3]), beta, d_T, t_strides[1], t_strides[2],
+            n_tau, d_sums, d_sums + n, d_sums + 2n, d_sums + 3n)
+        fo = _FdgFreqObservables(size(coef, 2), pointer(coef), d_fobs, d_fcov)
+        _fdg_check(ccall((:fdg_accumulate_device_freq_observables, _libfdg), Cint,
+            (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Int64, Ptr{Int32}, Int32, UInt32, Ptr{Float64}, Ptr{Float64}, UInt64, UInt64, UInt32,
+             UInt32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{_FdgMatsubara}, Ptr{Cvoid}, Ptr{Cvoid},
+             Ref{_FdgFreqObservables}, Int64, Ptr{Cvoid}),
+            f.handle, d_leaf, leaf_strides[1], leaf_strides[2], tile_stride, d_bin, bin_base, n_bin, d_weight,
+            train_coef === nothing ? C_NULL : train_coef, seed, sample_offset, n_dim, n_grid, d_acc, d_acc2, d_hist, d_hist_bin, mz, C_NULL,
+            C_NULL, fo, B, stream))
+    end
+    return nothing
+end
+# the same for the fused step (fdg_mc_accumulate_device_freq_observables): the phases are taken of the call's own T
+function mc_accumulate_device_freq_observables!(f::GraphFunc, d_fobs::Ptr{Float64}, d_fcov::Ptr{Float64}, coef::Matrix{Float64},
+    d_K::Ptr{Float64}, d_T::Ptr{Float64}, freq::Vector{Int}, root_tau_in::Vector{Int}, root_tau_out::Vector{Int}, B::Integer;
+    kF::Float64, beta::Float64, lambda::Float64, n_tau::Integer, fermionic::Bool=true, d_sums::Ptr{Float64}=Ptr{Float64}(C_NULL),
+    d_weight::Ptr{Float64}=Ptr{Float64}(C_NULL), d_acc::Ptr{Float64}=Ptr{Float64}(C_NULL), d_acc2::Ptr{Float64}=Ptr{Float64}(C_NULL),
+    d_bin::Ptr{Int32}=Ptr{Int32}(C_NULL), n_bin::Integer=1, bin_base::Integer=1, train_coef::Union{Nothing,Vector{Float64}}=nothing,
+    seed::Integer=0, sample_offset::Integer=0, n_dim::Integer=0, n_grid::Integer=0, d_hist::Ptr{Float64}=Ptr{Float64}(C_NULL),
+    d_hist_bin::Ptr{Float64}=Ptr{Float64}(C_NULL), k_strides=(1, B), t_strides=(1, B), stream::Ptr{Cvoid}=C_NULL)
+    a = [Int32.(v) for v in (freq, root_tau_in, root_tau_out)]
+    n = d_sums == C_NULL ? 0 : 8 * n_bin * length(freq) * length(root_tau_in)
+    GC.@preserve a coef begin
+        mz = _FdgMatsubara(length(freq), fermionic ? 1 : 0, pointer(a[1]), pointer(a[2]), pointer(a[3]), beta, Ptr{Float64}(C_NULL), 0, 0,
+            n_tau, d_sums, d_sums + n, d_sums + 2n, d_sums + 3n)
+        fo = _FdgFreqObservables(size(coef, 2), pointer(coef), d_fobs, d_fcov)
+        _fdg_check(ccall((:fdg_mc_accumulate_device_freq_observables, _libfdg), Cint,
+            (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Int64, Float64, Float64, Float64, Ptr{Int32}, Int32, UInt32,
+             Ptr{Float64}, Ptr{Float64}, UInt64, UInt64, UInt32, UInt32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+             Ref{_FdgMatsubara}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{_FdgFreqObservables}, Int64, Ptr{Cvoid}),
+            f.handle, d_K, k_strides[1], k_strides[2], d_T, t_strides[1], t_strides[2], kF, beta, lambda, d_bin, bin_base, n_bin, d_weight,
+            train_coef === nothing ? C_NULL : train_coef, seed, sample_offset, n_dim, n_grid, d_acc, d_acc2, d_hist, d_hist_bin, mz, C_NULL,
+            C_NULL, fo, B, stream))
+    end
+    return nothing
+end
 # device memory for a batch, backed by physical chunks of `chunk_bytes` (0: one allocation): fdg_batch_alloc / fdg_batch_free
 function batch_alloc(bytes::Integer; chunk_bytes::Integer=0)
     p = Ref{Ptr{Cvoid}}(C_NULL)
@@ -678,7 +738,7 @@ function accumulate_device!(f::GraphFunc, d_acc::Ptr{Float64}, d_leaf::Ptr{Float
         f.handle, d_leaf, leaf_strides[1], leaf_strides[2], d_weight, d_acc, B, stream))
 end
 
-export compile_hip, GraphFunc, eval_device!, accumulate_device!, eval_device_tiled!, accumulate_device_tiled!, accumulate_device_binned!, mc_accumulate_device_binned!, accumulate_device_moments!, mc_accumulate_device_moments!, vegas_sample_device!, accumulate_device_vegas!, mc_accumulate_device_vegas!, vegas_refine!, vegas_sample_device_discrete!, accumulate_device_vegas_binned!, mc_accumulate_device_vegas_binned!, vegas_refine_discrete!, vegas_sample_device_polar!, fdg_sincos, fdg_matsubara_phase, accumulate_device_matsubara!, mc_accumulate_device_matsubara!, weight_groups_from_dof, vegas_sample_device_grouped!, accumulate_device_grouped!, mc_accumulate_device_grouped!, accumulate_device_observables!, mc_accumulate_device_observables!, batch_alloc, batch_free, tile_major!, from_tile_major!, vegas_sample_device_strat!, accumulate_device_strat!, mc_accumulate_device_strat!, strat_allocate!
+export compile_hip, GraphFunc, eval_device!, accumulate_device!, eval_device_tiled!, accumulate_device_tiled!, accumulate_device_binned!, mc_accumulate_device_binned!, accumulate_device_moments!, mc_accumulate_device_moments!, vegas_sample_device!, accumulate_device_vegas!, mc_accumulate_device_vegas!, vegas_refine!, vegas_sample_device_discrete!, accumulate_device_vegas_binned!, mc_accumulate_device_vegas_binned!, vegas_refine_discrete!, vegas_sample_device_polar!, fdg_sincos, fdg_matsubara_phase, accumulate_device_matsubara!, mc_accumulate_device_matsubara!, weight_groups_from_dof, vegas_sample_device_grouped!, accumulate_device_grouped!, mc_accumulate_device_grouped!, accumulate_device_observables!, mc_accumulate_device_observables!, accumulate_device_freq_observables!, mc_accumulate_device_freq_observables!, batch_alloc, batch_free, tile_major!, from_tile_major!, vegas_sample_device_strat!, accumulate_device_strat!, mc_accumulate_device_strat!, strat_allocate!
 
 # ---- multi-GPU: one Julia process per GPU, ONE reduction of the accumulated observable ------------ #
 # (include/fdg.h, "multi-GPU").  Rank 0 calls `comm_unique_id()` and ships the 128 bytes to the other

@@ -109,6 +109,11 @@ class VegasResult:
     obs_cov: Optional[np.ndarray] = None        # [n_obs, n_obs] covariance of ``obs_mean`` (:func:`combine_covariance`)
     obs_iterations: List[Tuple[np.ndarray, np.ndarray]] = field(default_factory=list)   # (mean [n_obs], C [n_obs, n_obs]) of every iteration
     cube_counts: List[np.ndarray] = field(default_factory=list)      # with ``strat``: the samples per hypercube [H] of every iteration
+    fobs_mean: Optional[np.ndarray] = None      # with ``freq_observables``: complex [n_freq, M], as ``mean`` under ``matsubara``
+    fobs_stderr: Optional[np.ndarray] = None    # complex [n_freq, M]: the real parts' figures in .real, the imaginary parts' in .imag
+    fobs_chi2_dof: Optional[np.ndarray] = None  # complex [n_freq, M], likewise
+    fobs_cov: Optional[np.ndarray] = None       # real [n_freq, 2 M, 2 M]: the components (Re o_0 .., Im o_0 ..) (:func:`combine_covariance`)
+    fobs_iterations: List[Tuple[np.ndarray, np.ndarray]] = field(default_factory=list)   # (mean [n_freq, 2 M], C [n_freq, 2 M, 2 M])
 
 
 def combine(iterations: Sequence[Tuple[np.ndarray, np.ndarray]]):
@@ -222,8 +227,26 @@ class WeightGroups:
 class Observables:
     """Linear combinations of the roots that an integration reports: ``coef[m][k]`` the factor of root ``k`` in observable ``m``, at
     most ``capi.FDG_OBS_MAX`` rows of ``n_root`` finite numbers.  Every root enters with its own weight (its group's jacobian under
-    ``groups``), unprojected; complex observables (of Matsubara-projected roots) are not supported."""
+    ``groups``), unprojected; the complex observables of Matsubara-projected roots are :class:`FrequencyObservables`."""
     coef: Tuple[Tuple[float, ...], ...]
+
+
+@dataclass(frozen=True)
+class FrequencyObservables:
+    """Linear combinations of the PROJECTED roots that an integration reports per frequency: ``coef[m][k]`` the real factor of root
+    ``k`` in observable ``m``, at most ``capi.FDG_FREQ_OBS_MAX`` rows of ``n_root`` finite numbers.  Every root enters with its own
+    weight (its group's jacobian under ``groups``) and the phase of its own pair of times (``matsubara``, which it needs)."""
+    coef: Tuple[Tuple[float, ...], ...]
+
+
+def complex_components(x) -> np.ndarray:
+    """The complex ``[..., M]`` array of ``[..., 2 M]`` real components ``(Re_0 .. Re_{M-1}, Im_0 .. Im_{M-1})``: what the frequency
+    observables' means, error bars and chi2/dof are reported as (the figures of the real parts in the real part)."""
+    x = np.asarray(x, dtype=np.float64)
+    M = x.shape[-1] // 2
+    out = np.empty(x.shape[:-1] + (M,), dtype=np.complex128)
+    out.real, out.imag = x[..., :M], x[..., M:]           # (not re + 1j * im: a nan of one part would spread to the other)
+    return out
 
 
 @dataclass(frozen=True)
@@ -365,9 +388,12 @@ def groups_from_dof(dof, pools) -> WeightGroups:
 
 
 def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter, n_sample, n_grid, alpha, floor, seed, n_discard, fixed, coef,
-               device, vmap, specialize_fused, n_total, shard_start, reduce, polar=None, matsubara=None, wgroups=None, observables=None):
+               device, vmap, specialize_fused, n_total, shard_start, reduce, polar=None, matsubara=None, wgroups=None, observables=None,
+               freq_observables=None):
     """The driver behind :func:`vegas_integrate` (``dmap`` None: results ``[R]``) and :func:`vegas_integrate_binned` (``[n_bin, R]``);
     with ``matsubara`` the results are complex and carry a frequency axis in front of the roots."""
+    if freq_observables is not None and matsubara is None:
+        raise ValueError("freq_observables needs matsubara: the frequencies and the roots' time labels")
     import torch
     handle = getattr(func_or_handle, "handle", func_or_handle)
     device = torch.device(device)
@@ -403,6 +429,11 @@ def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter,
         ocoef = np.ascontiguousarray(observables.coef, dtype=np.float64)
         if ocoef.ndim != 2 or ocoef.shape[1] != R or not (1 <= ocoef.shape[0] <= capi.FDG_OBS_MAX) or not np.isfinite(ocoef).all():
             raise ValueError(f"observables.coef must be [n_obs, n_root = {R}], finite, with 1 <= n_obs <= {capi.FDG_OBS_MAX}")
+    fcoef = None
+    if freq_observables is not None:
+        fcoef = np.ascontiguousarray(freq_observables.coef, dtype=np.float64)
+        if fcoef.ndim != 2 or fcoef.shape[1] != R or not (1 <= fcoef.shape[0] <= capi.FDG_FREQ_OBS_MAX) or not np.isfinite(fcoef).all():
+            raise ValueError(f"freq_observables.coef must be [n_obs, n_root = {R}], finite, with 1 <= n_obs <= {capi.FDG_FREQ_OBS_MAX}")
     B = int(n_sample)
     N = B if n_total is None else int(n_total)
     if B < 1 or N < 2 or n_iter < 1 or not (0 <= n_discard < n_iter):
@@ -453,8 +484,8 @@ def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter,
             else:
                 capi.vegas_sample_device_discrete(vmap.d_grid.data_ptr(), D, G, col, dmap.d_cdf.data_ptr(), NB, 0, d_ext, dmap.ext_col, seed,
                                                   off, x.data_ptr(), 1, B, jac.data_ptr(), bins.data_ptr(), 0, B, st)
-            osums = []
-            if wgroups is not None or ocoef is not None:
+            osums, fsums = [], []
+            if wgroups is not None or ocoef is not None or fcoef is not None:
                 # one call for every combination: the projection, the discrete variable (and, beside observables, the groups) are optional in it
                 desc, hist_bin = None, None if dmap is None else torch.zeros(NB, dtype=torch.float64, device=device)
                 if matsubara is not None:
@@ -463,10 +494,21 @@ def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter,
                                                       beta, n_tau, *[m[i].data_ptr() for i in range(4)])
                 blocks = (desc, coef, seed, off, D, G, 0 if matsubara is not None else m[0].data_ptr(),
                           0 if matsubara is not None else m[1].data_ptr(), hist.data_ptr(), 0 if dmap is None else hist_bin.data_ptr(), B, st)
+                odesc = None
                 if ocoef is not None:
                     M = ocoef.shape[0]
                     osums = [torch.zeros((NB, M), dtype=torch.float64, device=device), torch.zeros((NB, M, M), dtype=torch.float64, device=device)]
                     odesc, _okeep = capi.make_observables(ocoef, osums[0].data_ptr(), osums[1].data_ptr())
+                if fcoef is not None:
+                    # the one call that carries every other block: the projection (always: its results are reported), ob and wg optional
+                    P = 2 * fcoef.shape[0]
+                    fsums = [torch.zeros((NB, NF, P), dtype=torch.float64, device=device),
+                             torch.zeros((NB, NF, P, P), dtype=torch.float64, device=device)]
+                    fdesc, _fkeep = capi.make_freq_observables(fcoef, fsums[0].data_ptr(), fsums[1].data_ptr())
+                    handle.mc_accumulate_device_freq_observables(x.data_ptr(), 1, B, d_T, 1, B, kF, beta, lam,
+                                                                 0 if dmap is None else bins.data_ptr(), 0, NB, jac.data_ptr(), fdesc, blocks[0],
+                                                                 odesc, wdesc, *blocks[1:])
+                elif ocoef is not None:
                     handle.mc_accumulate_device_observables(x.data_ptr(), 1, B, d_T, 1, B, kF, beta, lam,
                                                             0 if dmap is None else bins.data_ptr(), 0, NB, jac.data_ptr(), odesc, wdesc, *blocks)
                 else:
@@ -494,12 +536,16 @@ def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter,
                                                          hist_bin.data_ptr(), B, st)
                 sums = [m, hist, hist_bin]
             if reduce is not None:
-                for t in sums + osums:
+                for t in sums + osums + fsums:
                     reduce(t)
             if osums:
                 om, oc = mc_covariance(osums[0], osums[1], N)
                 oshape = shape[:-1 if matsubara is None else -2] + (ocoef.shape[0],)
                 out.obs_iterations.append((om.cpu().numpy().reshape(oshape), oc.cpu().numpy().reshape(oshape + oshape[-1:])))
+            if fsums:
+                fm, fc = mc_covariance(fsums[0], fsums[1], N)
+                fshape = shape[:-1] + (2 * fcoef.shape[0],)
+                out.fobs_iterations.append((fm.cpu().numpy().reshape(fshape), fc.cpu().numpy().reshape(fshape + fshape[-1:])))
             if matsubara is not None:
                 (mr, er), (mi, ei) = mc_estimate(m[0], m[2], N), mc_estimate(m[1], m[3], N)
                 mean, err = torch.complex(mr, mi), torch.complex(er, ei)
@@ -523,6 +569,9 @@ def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter,
     out.mean, out.stderr, out.chi2_dof = mean.reshape(shape), err.reshape(shape), chi2.reshape(shape)
     if ocoef is not None:
         out.obs_mean, out.obs_stderr, out.obs_chi2_dof, out.obs_cov = combine_covariance(out.obs_iterations[int(n_discard):])
+    if fcoef is not None:
+        fmean, ferr, fchi2, out.fobs_cov = combine_covariance(out.fobs_iterations[int(n_discard):])
+        out.fobs_mean, out.fobs_stderr, out.fobs_chi2_dof = (complex_components(v) for v in (fmean, ferr, fchi2))
     return out
 
 
@@ -531,7 +580,8 @@ def vegas_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: 
                     coef=None, device="cuda", vmap: Optional[VegasMap] = None, specialize_fused: bool = True, n_total: Optional[int] = None,
                     shard_start: int = 0, reduce: Optional[Callable] = None, polar: Optional[Sequence[PolarVar]] = None,
                     matsubara: Optional[MatsubaraProjection] = None, groups: Optional[WeightGroups] = None,
-                    observables: Optional[Observables] = None, strat: Optional[Stratification] = None) -> VegasResult:
+                    observables: Optional[Observables] = None, strat: Optional[Stratification] = None,
+                    freq_observables: Optional[FrequencyObservables] = None) -> VegasResult:
     """Integrates the roots of a graph over the box ``[lo, hi]`` of ``len(col)`` of its Monte-Carlo variables.
 
     ``func_or_handle``: a ``GraphFunc`` or ``capi.GraphHandle``; ``tables`` the ``fdg_leaf_tables`` struct of ``capi.make_leaf_tables``
@@ -567,6 +617,14 @@ def vegas_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: 
     ``obs_cov`` ``[n_obs, n_obs]``.  Real observables of the unprojected roots only, also beside ``matsubara``.  None: the calls made
     and their bits are what they are without this keyword.
 
+    ``freq_observables``: a :class:`FrequencyObservables`; needs ``matsubara``.  The one accumulate call of an iteration is then
+    fdg_mc_accumulate_device_freq_observables, which carries every other block (the projection, ``groups``, ``observables``) and
+    leaves their bits as they are; per (bin,) frequency it also sums the ``2 M`` real components ``Re o_m``, ``Im o_m`` of
+    ``o_m = sum_k coef[m][k] w_g(k) root_k e^{i omega_n tau_k}`` and their products (``reduce`` is applied to both).  ``mc_covariance``
+    gives every iteration's ``(mean, C)`` on the components (``fobs_iterations``) and :func:`combine_covariance` the results:
+    ``fobs_mean`` complex ``[n_freq, M]``, ``fobs_stderr`` and ``fobs_chi2_dof`` complex as ``matsubara`` reports them,
+    ``fobs_cov`` real ``[n_freq, 2 M, 2 M]``.  None: the calls made and their bits are what they are without this keyword.
+
     ``strat``: a :class:`Stratification` (:func:`strat_for`): adaptive stratified sampling on top of the map.  Per iteration: sample
     through fdg_vegas_sample_device_strat by the current allocation (the first is uniform), accumulate through
     fdg_mc_accumulate_device_strat, refine the map, fdg_strat_allocate from column ``n_root`` of the per-hypercube moments (the
@@ -576,15 +634,15 @@ def vegas_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: 
     Philox key ``seed + it * 0x9E3779B97F4A7C15`` (mod 2**64).  ``reduce`` is applied to the moments, the histogram and the
     per-hypercube moments ``[2, H, n_root + 1]``.  ``tables`` may then be None: the leaf form, where the columns of ``x`` are the
     graph's leaves themselves (fdg_accumulate_device_strat), ``col[d]`` the leaf that variable ``d`` fills and ``fixed`` the values
-    of the others.  Together with ``polar``, ``matsubara``, ``groups`` or ``observables`` (and with a discrete variable) it raises
+    of the others.  Together with ``polar``, ``matsubara``, ``groups``, ``observables`` or ``freq_observables`` (and with a discrete variable) it raises
     ValueError: those combinations are not built yet.  None: the calls made and their bits are what they are without this keyword."""
     if strat is not None:
-        if polar or matsubara is not None or groups is not None or observables is not None:
-            raise ValueError("strat cannot be combined with polar, matsubara, groups or observables")
+        if polar or matsubara is not None or groups is not None or observables is not None or freq_observables is not None:
+            raise ValueError("strat cannot be combined with polar, matsubara, groups, observables or freq_observables")
         return _integrate_strat(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_iter, n_sample, n_grid, alpha, seed, n_discard, fixed,
                                 coef, device, vmap, specialize_fused, n_total, shard_start, reduce, strat)
     return _integrate(func_or_handle, tables, lo, hi, col, None, kF, beta, lam, n_iter, n_sample, n_grid, alpha, 0.0, seed, n_discard, fixed, coef,
-                      device, vmap, specialize_fused, n_total, shard_start, reduce, polar, matsubara, groups, observables)
+                      device, vmap, specialize_fused, n_total, shard_start, reduce, polar, matsubara, groups, observables, freq_observables)
 
 
 def uniform_cdf(n_bin: int) -> np.ndarray:
@@ -659,6 +717,11 @@ class VegasBinnedResult:
     obs_chi2_dof: Optional[np.ndarray] = None   # [n_bin, n_obs]
     obs_cov: Optional[np.ndarray] = None        # [n_bin, n_obs, n_obs] (:func:`combine_covariance`)
     obs_iterations: List[Tuple[np.ndarray, np.ndarray]] = field(default_factory=list)   # (mean [n_bin, n_obs], C [n_bin, n_obs, n_obs])
+    fobs_mean: Optional[np.ndarray] = None      # with ``freq_observables``: complex [n_bin, n_freq, M]
+    fobs_stderr: Optional[np.ndarray] = None    # complex [n_bin, n_freq, M]: the real parts' figures in .real, the imaginary parts' in .imag
+    fobs_chi2_dof: Optional[np.ndarray] = None  # complex [n_bin, n_freq, M], likewise
+    fobs_cov: Optional[np.ndarray] = None       # real [n_bin, n_freq, 2 M, 2 M]
+    fobs_iterations: List[Tuple[np.ndarray, np.ndarray]] = field(default_factory=list)   # (mean [n_bin, n_freq, 2 M], C [.., 2 M, 2 M])
 
 
 def vegas_integrate_binned(func_or_handle, tables, lo, hi, col, dmap: DiscreteMap, kF: float = 0.0, beta: float = 1.0, lam: float = 0.0, *,
@@ -668,7 +731,8 @@ def vegas_integrate_binned(func_or_handle, tables, lo, hi, col, dmap: DiscreteMa
                            reduce: Optional[Callable] = None, polar: Optional[Sequence[PolarVar]] = None,
                            matsubara: Optional[MatsubaraProjection] = None,
                            groups: Optional[WeightGroups] = None, observables: Optional[Observables] = None,
-                           strat: Optional[Stratification] = None) -> VegasBinnedResult:
+                           strat: Optional[Stratification] = None,
+                           freq_observables: Optional[FrequencyObservables] = None) -> VegasBinnedResult:
     """:func:`vegas_integrate` with a discrete variable: every sample draws a value ``j`` of ``dmap`` next to its continuous variables,
     the columns ``dmap.ext_col`` take row ``j`` of ``dmap.ext`` (external momenta), and the estimate is per value: arrays ``[n_bin, R]``,
     bin ``j`` the integral over the continuous variables at configuration ``j`` (the weight carries ``1 / p_j``, and ``mc_estimate``
@@ -676,9 +740,11 @@ def vegas_integrate_binned(func_or_handle, tables, lo, hi, col, dmap: DiscreteMa
     ``mc_estimate``, refine the map with ``alpha`` and the probabilities with ``alpha`` and ``floor``.  ``combine`` is per (bin, root).
     Sharding as in :func:`vegas_integrate`; ``reduce`` is applied to the moments ``[2, n_bin, R]`` and to both histograms, so every rank
     refines the same maps.  ``polar``, ``matsubara`` and ``groups`` as in :func:`vegas_integrate` (complex ``[n_bin, n_freq, R]``; the
-    discrete variable is shared by every group); ``observables`` too: ``obs_mean`` ``[n_bin, n_obs]``, ``obs_cov`` ``[n_bin, n_obs, n_obs]``.
+    discrete variable is shared by every group); ``observables`` too: ``obs_mean`` ``[n_bin, n_obs]``, ``obs_cov`` ``[n_bin, n_obs, n_obs]``;
+    ``freq_observables`` too: ``fobs_mean`` complex ``[n_bin, n_freq, M]``, ``fobs_cov`` ``[n_bin, n_freq, 2 M, 2 M]``.
     ``strat`` is not built for a discrete variable yet: anything but None raises ValueError."""
     if strat is not None:
         raise ValueError("strat cannot be combined with a discrete variable (dmap)")
     return _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter, n_sample, n_grid, alpha, floor, seed, n_discard, fixed,
-                      coef, device, vmap, specialize_fused, n_total, shard_start, reduce, polar, matsubara, groups, observables)
+                      coef, device, vmap, specialize_fused, n_total, shard_start, reduce, polar, matsubara, groups, observables,
+                      freq_observables)

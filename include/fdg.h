@@ -901,7 +901,8 @@ int fdg_mc_accumulate_device_grouped(fdg_graph *g, const double *d_K, int64_t k_
  * call).  Whenever the pass keeps the binned call's segment count (its partials [segment][bin][V], V = n_obs + n_obs (n_obs + 1) / 2,
  * fit in 128 MiB), a row coef[m] = e_k gives d_obs[:, m] the bits of the moments call's d_acc[:, k] and d_cov[:, m, m] those of
  * d_acc2[:, k] (csrc/fdg_binned.hip).
- * Observables combine UNPROJECTED roots only: the Matsubara block stays per root, and complex observables are not supported.
+ * These observables combine UNPROJECTED roots: the Matsubara block of this call stays per root.  Sums of PROJECTED roots -- the
+ * complex observables of a frequency-resolved measurement -- are the _freq_observables calls below (real coefficients).
  * FDG_E_INVALID: ob NULL, one of its arrays NULL, n_obs == 0, a coefficient that is not finite, d_obs or d_cov the same buffer as the
  * other or as d_acc or d_acc2, one of d_acc and d_acc2 without the other, and the cases of the _grouped calls except those relaxed
  * above; FDG_E_UNSUPPORTED: n_obs > FDG_OBS_MAX and those calls' limits.  All before any device work. */
@@ -924,6 +925,56 @@ int fdg_mc_accumulate_device_observables(fdg_graph *g, const double *d_K, int64_
                                          const double *coef, uint64_t seed, uint64_t sample_offset, uint32_t n_dim, uint32_t n_grid,
                                          double *d_acc, double *d_acc2, double *d_hist, double *d_hist_bin, const fdg_matsubara *mz,
                                          const fdg_weight_groups *wg, const fdg_observables *ob, int64_t n_sample, void *stream);
+
+/* ---- Frequency observables: linear combinations of the PROJECTED roots, with their covariance -------------------------------------------
+ * The reference's measurement multiplies every root's weight by the phase of its own pair of external times and THEN sums the roots
+ * into the direct and the exchange component (test/ver4.jl:184-216, `phase(varT, ver4.Tpair[map.ver])` in line 193); a self-energy
+ * Sigma(i omega_n) is the sum of its roots, each with its own time pair, over all orders of the series.  The projection above gives a
+ * mean and an error bar per (frequency, root); the roots share their samples, so the error of their sum needs the covariance, per
+ * frequency, of the real and imaginary parts.  MCIntegration is not part of the reference checkout: no counterpart in the reference;
+ * the caller's side of those lines.
+ *
+ * fdg_[mc_]accumulate_device_freq_observables: the arguments of the _observables calls plus fo, placed after ob.  ob and wg may be
+ * NULL.  mz is required: the frequencies, `fermionic`, the time labels, beta and d_T are its own.  In these two calls only, the four
+ * per-root arrays of mz may all be NULL (the per-root projected sums are not wanted) or all be given.  coef is a HOST array, row-major
+ * [n_obs][n_root], real.  With M = n_obs, for every sample b < n_sample whose bin j is in range, every frequency f and every root k
+ * that exists, every step one rounded fp64 operation:
+ *   t_k, tau_k, (s, c), tre_k = t_k * c, tim_k = t_k * s exactly as the _matsubara calls form them (t_k = w_g(k) * root_k(b) with wg);
+ *   a_m = the left fold of coef[m][k] * tre_k over ascending k, over the roots that exist with coef[m][k] != 0.0; the first product
+ *         starts the fold.  b_m = the same fold with tim_k;
+ *   z = (a_0 .. a_{M-1}, b_0 .. b_{M-1});   d_fobs[j][f][p] += z_p;   d_fcov[j][f][p][q] += z_p * z_q for p <= q, and
+ *         d_fcov[j][f][q][p] receives the same increment.
+ * A row without a term leaves its components m and M + m untouched in both arrays, as FDG_NO_ROOT columns are.  The complex
+ * observable m at (j, f) is d_fobs[j][f][m] + i d_fobs[j][f][M + m]; d_fcov holds the second moments of the 2 M real components, from
+ * which the covariance of the real and imaginary parts of any further real combination follows.
+ * No float atomics; samples past n_sample or out of range are selected away, never multiplied by zero; the order of every sum is a
+ * function of (n_sample, n_bin, n_freq, n_obs, n_root, n_group, FDG_ROOT_SCRATCH_MB) only, not of the values of coef.  Every other
+ * output of the call (d_acc, d_acc2, d_hist, d_hist_bin, the four arrays of mz, ob's arrays) carries the bits of the _observables call
+ * without fo (with ob NULL: of the _grouped call): those passes and their plans are not touched (csrc/fdg_binned.hip).
+ * FDG_E_INVALID: fo NULL or one of its arrays NULL, n_obs == 0, a coefficient that is not finite, mz NULL, some but not all of mz's
+ * four arrays NULL, d_fobs or d_fcov the same buffer as the other or as any other output of the call, and the cases of the
+ * _observables calls (ob given) or the _grouped calls with wg optional (ob NULL); FDG_E_UNSUPPORTED: n_obs > FDG_FREQ_OBS_MAX,
+ * n_bin * n_freq > FDG_BIN_MAX and those calls' limits.  All before any device work. */
+#define FDG_FREQ_OBS_MAX 8
+typedef struct fdg_freq_observables {
+  uint32_t n_obs;      /* M: 1 .. FDG_FREQ_OBS_MAX */
+  const double *coef;  /* HOST [n_obs][n_root], row-major, finite, real */
+  double *d_fobs;      /* device [n_bin][n_freq][2 M], added to */
+  double *d_fcov;      /* device [n_bin][n_freq][2 M][2 M], added to */
+} fdg_freq_observables;
+int fdg_accumulate_device_freq_observables(fdg_graph *g, const double *d_leaf, int64_t leaf_sample_stride, int64_t leaf_leaf_stride,
+                                           int64_t leaf_tile_stride, const int32_t *d_bin, int32_t bin_base, uint32_t n_bin,
+                                           const double *d_weight, const double *coef, uint64_t seed, uint64_t sample_offset,
+                                           uint32_t n_dim, uint32_t n_grid, double *d_acc, double *d_acc2, double *d_hist,
+                                           double *d_hist_bin, const fdg_matsubara *mz, const fdg_weight_groups *wg,
+                                           const fdg_observables *ob, const fdg_freq_observables *fo, int64_t n_sample, void *stream);
+int fdg_mc_accumulate_device_freq_observables(fdg_graph *g, const double *d_K, int64_t k_sample_stride, int64_t k_comp_stride,
+                                              const double *d_T, int64_t t_sample_stride, int64_t t_comp_stride, double kF, double beta,
+                                              double lambda, const int32_t *d_bin, int32_t bin_base, uint32_t n_bin,
+                                              const double *d_weight, const double *coef, uint64_t seed, uint64_t sample_offset,
+                                              uint32_t n_dim, uint32_t n_grid, double *d_acc, double *d_acc2, double *d_hist,
+                                              double *d_hist_bin, const fdg_matsubara *mz, const fdg_weight_groups *wg,
+                                              const fdg_observables *ob, const fdg_freq_observables *fo, int64_t n_sample, void *stream);
 
 /* ---- Adaptive stratified sampling (VEGAS+) ------------------------------------------------------------------------------------------
  * The map above is separable: a ridge along a diagonal (a propagator of k1 + k2, of T[i] - T[j]) is flat in every axis projection, the
