@@ -52,6 +52,8 @@ EXPORTS = [
     "fdg_accumulate_device_observables", "fdg_mc_accumulate_device_observables",
     "fdg_accumulate_device_freq_observables", "fdg_mc_accumulate_device_freq_observables",
     "fdg_vegas_sample_device_strat", "fdg_accumulate_device_strat", "fdg_mc_accumulate_device_strat", "fdg_strat_allocate",
+    "fdg_vegas_sample_device_strat_grouped", "fdg_accumulate_device_strat_grouped", "fdg_mc_accumulate_device_strat_grouped",
+    "fdg_strat_allocate_cols",
 ]
 FDG_BIN_MAX = 16384     # fdg_accumulate_device_binned: largest n_bin
 FDG_VEGAS_DIM_MAX, FDG_VEGAS_GRID_MAX = 64, 1024     # the VEGAS map: most variables, most cells per variable
@@ -287,6 +289,13 @@ def lib():
     L.fdg_mc_accumulate_device_strat.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, C.c_void_p, u64, u64,
                                                  u32, u32, dp, dp, dp, C.c_void_p, dp, dp, dp, i64, vp]
     L.fdg_strat_allocate.argtypes = [C.c_void_p, C.c_void_p, u32, u32, C.c_void_p, u32, i64, C.c_double, C.c_void_p]
+    L.fdg_vegas_sample_device_strat_grouped.argtypes = [dp, u32, u32, C.c_void_p, C.c_void_p, u32, C.c_void_p, u32, i64, C.c_void_p, dp, u64,
+                                                        u64, dp, i64, i64, dp, dp, dp, i64, vp]
+    L.fdg_accumulate_device_strat_grouped.argtypes = [vp, dp, i64, i64, i64, dp, C.c_void_p, u64, u64, u32, u32, dp, dp, dp, C.c_void_p, dp,
+                                                      dp, dp, C.c_void_p, i64, vp]
+    L.fdg_mc_accumulate_device_strat_grouped.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, C.c_void_p,
+                                                         u64, u64, u32, u32, dp, dp, dp, C.c_void_p, dp, dp, dp, C.c_void_p, i64, vp]
+    L.fdg_strat_allocate_cols.argtypes = [C.c_void_p, C.c_void_p, u32, C.c_void_p, u32, C.c_void_p, u32, i64, C.c_double, C.c_void_p]
     L.fdg_powi.argtypes = [C.c_double, C.c_int32]
     L.fdg_powi.restype = C.c_double
     _lib = L
@@ -656,6 +665,27 @@ class GraphHandle:
                                                    d_acc or None, d_acc2 or None, d_hist or None, sv.ctypes.data, d_cube or None,
                                                    d_cube_sum or None, d_cube_sum2 or None, B, stream))
 
+    # the stratified grouped accumulate step: the _strat calls plus groups = make_weight_groups(...)[0], d_weight [n_group, stride];
+    # d_cube_sum, d_cube_sum2 [H, n_root + n_group] (fdg.h)
+    def accumulate_device_strat_grouped(self, d_leaf: int, ss: int, ls: int, lts: int, d_weight: int, coef, seed: int, sample_offset: int,
+                                        n_dim: int, n_grid: int, d_acc: int, d_acc2: int, d_hist: int, strat, d_cube: int, d_cube_sum: int,
+                                        d_cube_sum2: int, groups, B: int, stream: int = 0):
+        c, sv = self._coef(coef), _strat_array(strat, n_dim)
+        check(lib().fdg_accumulate_device_strat_grouped(self._h, d_leaf or None, ss, ls, lts, d_weight or None,
+                                                        None if c is None else c.ctypes.data, seed, sample_offset, n_dim, n_grid,
+                                                        d_acc or None, d_acc2 or None, d_hist or None, sv.ctypes.data, d_cube or None,
+                                                        d_cube_sum or None, d_cube_sum2 or None,
+                                                        None if groups is None else C.addressof(groups), B, stream))
+
+    def mc_accumulate_device_strat_grouped(self, d_K, ks, kc, d_T, ts, tc, kF, beta, lam, d_weight, coef, seed, sample_offset, n_dim, n_grid,
+                                           d_acc, d_acc2, d_hist, strat, d_cube, d_cube_sum, d_cube_sum2, groups, B, stream=0):
+        c, sv = self._coef(coef), _strat_array(strat, n_dim)
+        check(lib().fdg_mc_accumulate_device_strat_grouped(self._h, d_K or None, ks, kc, d_T or None, ts, tc, kF, beta, lam, d_weight or None,
+                                                           None if c is None else c.ctypes.data, seed, sample_offset, n_dim, n_grid,
+                                                           d_acc or None, d_acc2 or None, d_hist or None, sv.ctypes.data, d_cube or None,
+                                                           d_cube_sum or None, d_cube_sum2 or None,
+                                                           None if groups is None else C.addressof(groups), B, stream))
+
     def _coef(self, coef):
         if coef is None:
             return None
@@ -763,21 +793,60 @@ def strat_allocate(cube_sum, cube_sum2, col: int, start_old, H: int, n_total: in
 def strat_allocate_reference(cube_sum, cube_sum2, col: int, start_old, H: int, n_total: int, beta: float = 0.75) -> np.ndarray:
     """Steps 1-5 of fdg_strat_allocate (include/fdg.h) restated in Python, valid arguments taken for granted: the same fp64
     operations in the same order (``math.pow`` is the C library's ``pow``), so the result is the library's exactly."""
+    return strat_allocate_cols_reference(cube_sum, cube_sum2, [col], start_old, H, n_total, beta)
+
+
+def strat_allocate_cols(cube_sum, cube_sum2, cols, start_old, H: int, n_total: int, beta: float = 0.75) -> np.ndarray:
+    """fdg_strat_allocate_cols: :func:`strat_allocate` from the columns ``cols`` (a sequence, in the order their variances are
+    folded) of the per-hypercube moments ``[H, ld]``."""
+    out = np.zeros(int(H) + 1, dtype=np.int64)
+    cv = np.ascontiguousarray(cols, dtype=np.uint32)
+    if cv.ndim != 1:
+        raise ValueError("cols must be a sequence of column numbers")
+    d_cols = cv.ctypes.data if cv.shape[0] else None
+    if start_old is None:
+        check(lib().fdg_strat_allocate_cols(None, None, 0, d_cols, cv.shape[0], None, H, n_total, float(beta), out.ctypes.data))
+        return out
+    s1 = np.ascontiguousarray(cube_sum, dtype=np.float64)
+    s2 = np.ascontiguousarray(cube_sum2, dtype=np.float64)
+    so = np.ascontiguousarray(start_old, dtype=np.int64)
+    if s1.ndim != 2 or s1.shape != s2.shape or s1.shape[0] != H or so.shape != (H + 1,):
+        raise ValueError("the moments must be [H, ld] and start_old [H + 1]")
+    check(lib().fdg_strat_allocate_cols(s1.ctypes.data, s2.ctypes.data, s1.shape[1], d_cols, cv.shape[0], so.ctypes.data, H, n_total,
+                                        float(beta), out.ctypes.data))
+    return out
+
+
+def strat_allocate_cols_reference(cube_sum, cube_sum2, cols, start_old, H: int, n_total: int, beta: float = 0.75) -> np.ndarray:
+    """Steps 1-5 of fdg_strat_allocate_cols (include/fdg.h) restated in Python, valid arguments taken for granted: step 1's ``var_h``
+    is the left fold over ``cols`` of each column's own; the same fp64 operations in the same order, so the result is the library's
+    exactly."""
+    H = int(H)
+    if start_old is None:
+        return _strat_allocate_from_var([0.0] * H, None, H, int(n_total), beta)
+    so = np.asarray(start_old, dtype=np.int64)
+    n_old = float(so[H])
+    var = [0.0] * H
+    for h in range(H):
+        nd = float(so[h + 1] - so[h])
+        fac = n_old / (float(H) * nd)
+        for i, col in enumerate(cols):
+            s1, s2 = float(cube_sum[h][col]), float(cube_sum2[h][col])
+            vc = max(0.0, (s2 - s1 * s1 / nd) / (nd - 1.0)) / (fac * fac)
+            var[h] = var[h] + vc if i else vc
+    return _strat_allocate_from_var(var, so, H, int(n_total), beta)
+
+
+def _strat_allocate_from_var(var, so, H: int, n_total: int, beta: float) -> np.ndarray:
+    """Steps 2-5 of fdg_strat_allocate from the ``var_h`` of step 1, in the library's order (``math.pow`` is the C library's
+    ``pow``); ``so`` None: no history."""
     import math
-    H, n_total = int(H), int(n_total)
     spare = n_total - 2 * H
     dh, S = [0.0] * H, 0.0
-    if start_old is not None:
-        so = np.asarray(start_old, dtype=np.int64)
-        n_old = float(so[H])
-        for h in range(H):
-            nd = float(so[h + 1] - so[h])
-            s1, s2 = float(cube_sum[h][col]), float(cube_sum2[h][col])
-            fac = n_old / (float(H) * nd)
-            var = max(0.0, (s2 - s1 * s1 / nd) / (nd - 1.0)) / (fac * fac)
-            dh[h] = 0.0 if var == 0.0 else math.pow(var, beta / 2.0)
-            S = S + dh[h] if h else dh[h]
-    if start_old is None or not S > 0.0 or not math.isfinite(S) or beta == 0.0:
+    for h in range(H):
+        dh[h] = 0.0 if var[h] == 0.0 else math.pow(var[h], beta / 2.0)
+        S = S + dh[h] if h else dh[h]
+    if so is None or not S > 0.0 or not math.isfinite(S) or beta == 0.0:
         cnt = [2 + spare // H] * H
     else:
         cnt = [2 + int(math.floor(float(spare) * (dh[h] / S))) for h in range(H)]
@@ -848,6 +917,103 @@ def strat_reference(grid, strat, start, u, sample_offset: int = 0, roots=None, w
         out["cube_sum"], out["cube_sum2"] = s1, s2
         if beta is not None:
             out["start_new"] = strat_allocate_reference(s1, s2, R, start, H, int(start[H]), beta)
+    return out
+
+
+def vegas_sample_device_strat_grouped(d_grid: int, n_dim: int, n_grid: int, col, polar, var_sets, jac_group_stride: int, strat, d_start: int,
+                                      seed: int, sample_offset: int, d_x: int, xs: int, xc: int, d_jac: int, d_cube: int, d_cell: int, B: int,
+                                      stream: int = 0):
+    """fdg_vegas_sample_device_strat_grouped: :func:`vegas_sample_device_grouped` without a discrete variable, every variable drawn
+    inside the stratum of the sample's hypercube (``strat``, ``d_start``, ``d_cube`` as :func:`vegas_sample_device_strat` takes them)
+    and every group's jacobian times ``n_total / (H n_h)``.  ``var_sets`` None: one jacobian ``jac[b]``, the full fold (polar without
+    groups)."""
+    c = None
+    if col is not None:
+        c = np.ascontiguousarray([0 if v is None else v for v in col], dtype=np.uint32)
+        if c.shape != (n_dim,):
+            raise ValueError("col must name one column per variable")
+    arr, n_polar = _polar_array(polar)
+    vm = None
+    if var_sets is not None:
+        vm = var_sets if isinstance(var_sets, np.ndarray) and var_sets.dtype == np.uint64 else var_masks(var_sets)
+        vm = np.ascontiguousarray(vm)
+    sv = _strat_array(strat, n_dim)
+    check(lib().fdg_vegas_sample_device_strat_grouped(d_grid or None, n_dim, n_grid, None if c is None else c.ctypes.data,
+                                                      C.addressof(arr) if n_polar else None, n_polar,
+                                                      vm.ctypes.data if vm is not None and vm.shape[0] else None,
+                                                      0 if vm is None else vm.shape[0], jac_group_stride, sv.ctypes.data, d_start or None,
+                                                      seed, sample_offset, d_x or None, xs, xc, d_jac or None, d_cube or None,
+                                                      d_cell or None, B, stream))
+
+
+def strat_grouped_reference(grid, strat, start, u, col, polar=(), var_sets=None, n_col=None, sample_offset: int = 0, fill: float = 0.0,
+                            roots=None, weight=None, coef=None, exists=None, root_group=None):
+    """The stratified grouped calls restated in numpy (include/fdg.h), composed of :func:`strat_reference` (the hypercubes, the
+    drawn values, the cells, the full fold times ``fac_h``), :func:`grouped_jacobian` (the per-group folds) and the polar sampler's
+    Cartesian statements with :func:`sincos`; one numpy operation per rounded operation of the kernel and in its order, so the
+    sampler compares bit for bit.  ``col[d]``: the column of variable ``d`` (None for a grouped one), ``polar``: ``(var, cols)``
+    pairs, ``var_sets``: the weight groups' sets of variables (None: one jacobian).  Returns a dict: ``cube [B]``, ``cell [B, D]``,
+    ``value [B, D]`` (the drawn variables), ``x [B, n_col]`` (the columns as the device writes them, ``fill`` elsewhere), ``jac``
+    (``[n_group, B]``, or ``[B]`` without groups); with ``roots [B, R]``, ``weight [n_group, B]`` and ``root_group [R]`` also
+    ``cube_sum`` / ``cube_sum2 [H, R + n_group]`` -- plain numpy sums, so these compare within rounding."""
+    grid = np.asarray(grid, dtype=np.float64)
+    start = np.asarray(start, dtype=np.int64)
+    base = strat_reference(grid, strat, start, u, sample_offset)
+    v, cell, cube = base["x"], base["cell"], base["cube"].astype(np.int64)
+    B, D = v.shape
+    G, H = grid.shape[1] - 1, int(np.prod(np.asarray(strat, dtype=np.int64)))
+    d_idx = np.arange(D)[None, :]
+    factor = np.float64(G) * (grid[d_idx, cell + 1] - grid[d_idx, cell])
+    fac_h = np.float64(start[H]) / (np.float64(H) * (start[cube + 1] - start[cube]).astype(np.float64))
+    polar = [(int(var), tuple(int(c) for c in cols)) for var, cols in polar]
+    if var_sets is None:
+        jac = grouped_jacobian(factor, [range(D)], polar, value=v)[0] * fac_h
+    else:
+        jac = grouped_jacobian(factor, var_sets, polar, value=v) * fac_h[None, :]
+    grouped = {d for var, cols in polar for d in range(var, var + len(cols))}
+    if n_col is None:
+        n_col = 1 + max([c for d, c in enumerate(col) if d not in grouped] + [c for _, cols in polar for c in cols])
+    x = np.full((B, n_col), fill)
+    for d in range(D):
+        if d not in grouped:
+            x[:, col[d]] = v[:, d]
+    sc = np.frompyfunc(sincos, 1, 2)
+    for var, cols in polar:
+        k = v[:, var]
+        if len(cols) == 3:
+            st, ct = (a.astype(np.float64) for a in sc(v[:, var + 1]))
+            sp, cp = (a.astype(np.float64) for a in sc(v[:, var + 2]))
+            ks = k * st
+            x[:, cols[0]], x[:, cols[1]], x[:, cols[2]] = ks * cp, ks * sp, k * ct
+        else:
+            sp, cp = (a.astype(np.float64) for a in sc(v[:, var + 1]))
+            x[:, cols[0]], x[:, cols[1]] = k * cp, k * sp
+    out = {"cube": base["cube"], "cell": cell, "value": v, "x": x, "jac": jac}
+    if roots is not None:
+        roots = np.asarray(roots, dtype=np.float64)
+        R = roots.shape[1]
+        w = np.asarray(weight, dtype=np.float64).reshape(-1, B)
+        NG = w.shape[0]
+        rg = np.zeros(R, dtype=np.int64) if root_group is None else np.asarray(root_group, dtype=np.int64)
+        inside = (cube >= 0) & (cube < H)
+        hc = cube[inside]
+        s1, s2 = np.zeros((H, R + NG)), np.zeros((H, R + NG))
+        comb = [None] * NG
+        for k in range(R):
+            if exists is not None and not exists[k]:
+                continue
+            g = int(rg[k])
+            term = roots[:, k] if coef is None else coef[k] * roots[:, k]
+            comb[g] = term if comb[g] is None else comb[g] + term
+            t = (w[g] * roots[:, k])[inside]
+            s1[:, k] = np.bincount(hc, weights=t, minlength=H)
+            s2[:, k] = np.bincount(hc, weights=t * t, minlength=H)
+        for g in range(NG):
+            if comb[g] is not None:
+                t = (w[g] * comb[g])[inside]
+                s1[:, R + g] = np.bincount(hc, weights=t, minlength=H)
+                s2[:, R + g] = np.bincount(hc, weights=t * t, minlength=H)
+        out["cube_sum"], out["cube_sum2"] = s1, s2
     return out
 
 

@@ -56,11 +56,14 @@
 // search in the prefix sums and draws inside its strata; the training pass carries a STRAT flag that recomputes the cell by the same
 // formula; one more pass per chunk (fdg_strat_partials, fdg_strat_stitch below) sums w root_k and its square per hypercube, runs of
 // equal hypercubes inside a wave by the segmented scan above, runs that cross waves, tiles or chunks level by level from edge records.
+// With polar groups and weight groups (the _strat_grouped calls): the polar sampler carries the same STRAT flag, the training pass runs
+// with STRAT beside GRP, and the per-hypercube pass takes one column per group behind the roots' in the place of the one.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <mutex>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -665,16 +668,32 @@ struct VegasCols { uint32_t c[FDG_VEGAS_DIM_MAX]; };   // the column of x each v
 // kPolar (fdg_vegas_sample_polar): bit d of `grouped` set = variable d belongs to a polar group; its value goes to the lane's slot of
 // `stash` (LDS, [slot][256 lanes], slots in ascending d) instead of a column of x.
 // fold(d, f): called with every variable's factor f = G * wd_d of the jacobian, in order (the grouped sampler's per-group folds).
+// pick(sample, d, seed, G, y): the cell of variable d and y, called once per variable in ascending d (VegasPlainCell: vegas_cell;
+// VegasStratCell: vegas_cell_strat in the stratum that the digits of the sample's hypercube name, peeled as the calls go).
 struct VegasNoFold { __device__ void operator()(uint32_t, double) const {} };
-template <bool kPolar = false, class Fold = VegasNoFold>
+struct VegasPlainCell {
+  __device__ __forceinline__ uint32_t operator()(uint64_t sample, uint32_t d, uint64_t seed, uint32_t G, double &y) const {
+    return vegas_cell(sample, d, seed, G, y);
+  }
+};
+struct VegasStratCell {
+  const VegasStrat *sv;
+  uint32_t rem;                                           // the hypercube's digits not yet peeled
+  __device__ __forceinline__ uint32_t operator()(uint64_t sample, uint32_t d, uint64_t seed, uint32_t G, double &y) {
+    const uint32_t ns = sv->n[d], sd = rem % ns;
+    rem /= ns;
+    return vegas_cell_strat(sample, d, seed, G, sd, ns, y);
+  }
+};
+template <bool kPolar = false, class Fold = VegasNoFold, class Cell = VegasPlainCell>
 __device__ __forceinline__ double vegas_draw(const double *__restrict__ grid, uint32_t D, uint32_t G, const VegasCols &col, uint64_t seed,
                                              uint64_t off, double *__restrict__ x, long xs, long xc, int32_t *__restrict__ cell, long n, long b,
-                                             uint64_t grouped = 0, double *stash = nullptr, Fold fold = Fold()) {
+                                             uint64_t grouped = 0, double *stash = nullptr, Fold fold = Fold(), Cell pick = Cell()) {
   double jb = 0.0;
   uint32_t slot = 0;
   for (uint32_t d = 0; d < D; ++d) {
     double y;
-    const uint32_t c = vegas_cell(off + (uint64_t)b, d, seed, G, y);
+    const uint32_t c = pick(off + (uint64_t)b, d, seed, G, y);
     const double *e = grid + (size_t)d * (G + 1u) + c;
     const double lo = e[0], wd = e[1] - lo, fr = y - (double)c;
     const double v = lo + fr * wd;
@@ -798,15 +817,40 @@ struct VegasGroupMasks {
 // GRP (fdg_vegas_sample_device_grouped): one jacobian per weight group, jac[g * jstride + b], each the same fold over the variables
 // and polar groups of its mask only (1.0 * f = f exactly: a group's first factor enters as the plain fold's does).  Every variable is
 // drawn once, and x, bin and cell are written by the very statements of the ungrouped instance.
-template <bool GRP>
+// STRAT (fdg_vegas_sample_device_strat_grouped; no discrete variable): the lane finds its hypercube as fdg_vegas_sample_strat does
+// (binary search in start[0 .. H], cube[b]), every variable is drawn by vegas_cell_strat in the stratum of the hypercube's digit, and
+// every jacobian is multiplied by fac_h = n_total / (H * n_h) last.  The instances without it take an empty argument in its place.
+struct VegasNoStrat {};
+struct VegasStratArgs {
+  VegasStrat sv;
+  const int64_t *start;
+  int32_t *cube;
+};
+template <bool GRP, bool STRAT = false>
 __global__ void __launch_bounds__(256)
 fdg_vegas_sample_polar(const double *__restrict__ grid, uint32_t D, uint32_t G, VegasCols col, VegasPolar pol, const double *__restrict__ cdf,
                        uint32_t n_bin, int32_t bin_base, const double *__restrict__ ext, uint32_t n_ext, VegasExtCols ecol, uint64_t seed,
                        uint64_t off, double *__restrict__ x, long xs, long xc, double *__restrict__ jac, int32_t *__restrict__ bin,
-                       int32_t *__restrict__ cell, long n, VegasGroupMasks gm, long jstride) {
+                       int32_t *__restrict__ cell, long n, VegasGroupMasks gm, long jstride,
+                       std::conditional_t<STRAT, VegasStratArgs, VegasNoStrat> sa) {
   extern __shared__ double polar_stash[];
   constexpr int NG = GRP ? FDG_WEIGHT_GROUP_MAX : 1;
   for (long b = blockIdx.x * 256L + threadIdx.x; b < n; b += (long)gridDim.x * 256L) {
+    [[maybe_unused]] double fac = 1.0;                     // STRAT: fac_h of this lane's hypercube
+    [[maybe_unused]] uint32_t hcube = 0;
+    if constexpr (STRAT) {
+      const uint32_t H = sa.sv.H;
+      const int64_t i = (int64_t)(off + (uint64_t)b);
+      uint32_t lo = 0, hi = H - 1u;                       // h in [lo, hi]: start[lo] <= i
+      while (lo < hi) {
+        const uint32_t mid = (lo + hi + 1u) >> 1;
+        if (sa.start[mid] <= i) lo = mid; else hi = mid - 1u;
+      }
+      const int64_t n_h = sa.start[lo + 1u] - sa.start[lo];
+      sa.cube[b] = (int32_t)lo;
+      hcube = lo;
+      fac = (double)sa.start[H] / ((double)H * (double)n_h);
+    }
     double jg[NG];
 #pragma unroll
     for (int g = 0; g < NG; ++g) jg[g] = 1.0;
@@ -818,7 +862,9 @@ fdg_vegas_sample_polar(const double *__restrict__ grid, uint32_t D, uint32_t G, 
           if ((uint32_t)g < gm.n && ((gm.m[g] >> d) & 1u)) jg[g] = jg[g] * f;
       }
     };
-    double jb = vegas_draw<true>(grid, D, G, col, seed, off, x, xs, xc, cell, n, b, pol.grouped, polar_stash, fold);
+    double jb;
+    if constexpr (STRAT) jb = vegas_draw<true>(grid, D, G, col, seed, off, x, xs, xc, cell, n, b, pol.grouped, polar_stash, fold, VegasStratCell{&sa.sv, hcube});
+    else jb = vegas_draw<true>(grid, D, G, col, seed, off, x, xs, xc, cell, n, b, pol.grouped, polar_stash, fold);
     for (uint32_t g = 0; g < pol.n; ++g) {
       const uint32_t var = pol.var[g];
       const double *v = polar_stash + (size_t)__popcll(pol.grouped & ((1ull << var) - 1ull)) * 256u + threadIdx.x;
@@ -855,7 +901,15 @@ fdg_vegas_sample_polar(const double *__restrict__ grid, uint32_t D, uint32_t G, 
           }
       }
     }
-    if constexpr (GRP) {
+    if constexpr (STRAT) {
+      if constexpr (GRP) {
+#pragma unroll
+        for (int g = 0; g < NG; ++g)
+          if ((uint32_t)g < gm.n) jac[(size_t)g * (size_t)jstride + (size_t)b] = jg[g] * fac;
+      } else {
+        jac[b] = jb * fac;
+      }
+    } else if constexpr (GRP) {
       // the discrete variable is shared by every group
       const double p = cdf ? vegas_pick_discrete(cdf, n_bin, bin_base, ext, n_ext, ecol, seed, off, D, x, xs, xc, bin, b) : 1.0;
 #pragma unroll
@@ -1244,15 +1298,17 @@ fdg_matsubara_partials(const double *__restrict__ root, long ld, long n, const i
 //    (final) writes every run.  A hypercube of 10^8 samples is thus summed by a tree of depth 6 + 6 levels, never by one lane.
 // The shape of every level follows from the chunk sizes alone -- (n_sample, n_root, FDG_ROOT_SCRATCH_MB) -- and every word of sum /
 // sum2 is written by exactly one lane of one launch: no atomics, bitwise repeatable.
-// Records of a level: keys [slot] (int32, -1: nothing), values [column][slot] with the columns 0 .. R of the first moment, then
-// R + 1 .. 2 R + 1 of the second.  wmask: bit j set = the column of value j is written to sum / sum2 (a root that exists).
+// Records of a level: keys [slot] (int32, -1: nothing), values [column][slot] with the C1 = R + E columns of the first moment, then
+// the C1 of the second (E = 1 but for the grouped calls with several groups: one column per group).  wmask: bit j set = the column of value j is written to sum / sum2 (a root that exists).
 constexpr uint32_t kStratCols = 8, kStratVals = 2 * kStratCols;
 
-__device__ __forceinline__ uint32_t strat_wmask(uint32_t k0, uint32_t R, const uint8_t *__restrict__ live, uint32_t n_live) {
+// E columns behind the roots' (1: the coef combination; the grouped calls: one per weight group); bit e of emask set = column R + e
+// has a root that exists behind it.
+__device__ __forceinline__ uint32_t strat_wmask(uint32_t k0, uint32_t R, uint32_t E, const uint8_t *__restrict__ live, uint32_t emask) {
   uint32_t m = 0;
   for (uint32_t j = 0; j < kStratVals; ++j) {
     const uint32_t kk = k0 + (j & (kStratCols - 1u));
-    const bool on = kk < R ? (!live || live[kk]) : (kk == R && n_live != 0);
+    const bool on = kk < R ? (!live || live[kk]) : (kk - R < E && ((emask >> (kk - R)) & 1u) != 0);
     m |= on ? 1u << j : 0u;
   }
   return m;
@@ -1310,42 +1366,59 @@ __device__ __forceinline__ void strat_wave_reduce(int32_t key, bool ok, uint32_t
 
 // Level 0: the samples of a chunk (root k of sample b at root[k * ld + b], b < n).  The scratch columns are read for the last time
 // in the chunk: non-temporal loads.
+// GRP (fdg_[mc_]accumulate_device_strat_grouped with more than one group): column k < R is weighted by the column of its root's group
+// (rgrp[k], the first R words of the groups' table: a root that does not exist carries a neighbour's group and is never written), and
+// NG columns follow, R + g = w_g s_g (vegas_group_term); bit g of emask: group g has a root that exists.  The lists kidx / coef are
+// then sorted by (group, root), as the grouped training pass takes them.
+template <bool GRP = false>
 __global__ void __launch_bounds__(256)
 fdg_strat_partials(const double *__restrict__ root, long ld, long n, const int32_t *__restrict__ cube, uint32_t H,
                    const double *__restrict__ weight, const uint32_t *__restrict__ kidx, const double *__restrict__ coef, uint32_t n_live,
                    uint32_t R, const uint8_t *__restrict__ live, double *__restrict__ sum, double *__restrict__ sum2,
-                   int32_t *__restrict__ rkey, double *__restrict__ rval, long rstride, long slot_base) {
+                   int32_t *__restrict__ rkey, double *__restrict__ rval, long rstride, long slot_base,
+                   const uint32_t *__restrict__ rgrp, const uint32_t *__restrict__ gstart, uint32_t NG, long wstride, uint32_t emask) {
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   const long t = (long)blockIdx.x * kBinWaves + wave;
   if (t >= (n + 63) / 64) return;                          // (whole waves leave; the kernel has no barrier)
-  const uint32_t k0 = blockIdx.y * kStratCols, C1 = R + 1u;
+  const uint32_t E = GRP ? NG : 1u;
+  const uint32_t k0 = blockIdx.y * kStratCols, C1 = R + E;
   const long b = t * 64 + lane;
   const size_t bb = (size_t)min(b, n - 1);                 // clamped into the chunk; what it loads is used only where `ok`
   const int32_t h = cube[bb];
   const bool ok = b < n && (uint32_t)h < H;
-  const double w = weight ? weight[bb] : 1.0;
+  double w = 1.0;
+  if constexpr (!GRP) w = weight ? weight[bb] : 1.0;
   double s[kStratVals];
 #pragma unroll
   for (uint32_t i = 0; i < kStratCols; ++i) {
     const uint32_t kk = k0 + i;
     double tk = 0.0;
-    if (kk < R) tk = w * __builtin_nontemporal_load(root + (size_t)kk * (size_t)ld + bb);
-    else if (kk == R) tk = vegas_term(root, ld, bb, weight, kidx, coef, n_live);
+    if constexpr (GRP) {
+      if (kk < R) tk = weight[(size_t)rgrp[kk] * (size_t)wstride + bb] * __builtin_nontemporal_load(root + (size_t)kk * (size_t)ld + bb);
+      else if (kk < C1) tk = vegas_group_term(root, ld, bb, weight, wstride, kidx, coef, gstart, kk - R);
+    } else {
+      if (kk < R) tk = w * __builtin_nontemporal_load(root + (size_t)kk * (size_t)ld + bb);
+      else if (kk == R) tk = vegas_term(root, ld, bb, weight, kidx, coef, n_live);
+    }
     s[i] = ok ? tk : 0.0;                                  // selected, never multiplied by 0
     s[kStratCols + i] = ok ? tk * tk : 0.0;
   }
-  strat_wave_reduce(h, ok, lane, s, k0, C1, strat_wmask(k0, R, live, n_live), sum, sum2, false, rkey, rval, rstride, slot_base + 2 * t);
+  const uint32_t em = GRP ? emask : (n_live != 0 ? 1u : 0u);
+  strat_wave_reduce(h, ok, lane, s, k0, C1, strat_wmask(k0, R, E, live, em), sum, sum2, false, rkey, rval, rstride, slot_base + 2 * t);
 }
 
 // Levels 1 ..: the n_slot records of the level below.
+// GRP: NG columns behind the roots' in the place of one (emask as in fdg_strat_partials).
+template <bool GRP = false>
 __global__ void __launch_bounds__(256)
 fdg_strat_stitch(const int32_t *__restrict__ ikey, const double *__restrict__ ival, long istride, long n_slot, uint32_t R,
                  const uint8_t *__restrict__ live, uint32_t n_live, double *__restrict__ sum, double *__restrict__ sum2, int final,
-                 int32_t *__restrict__ rkey, double *__restrict__ rval, long rstride, long slot_base) {
+                 int32_t *__restrict__ rkey, double *__restrict__ rval, long rstride, long slot_base, uint32_t NG, uint32_t emask) {
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   const long wv = (long)blockIdx.x * kBinWaves + wave;
   if (wv >= (n_slot + 63) / 64) return;
-  const uint32_t k0 = blockIdx.y * kStratCols, C1 = R + 1u;
+  const uint32_t E = GRP ? NG : 1u, em = GRP ? emask : (n_live != 0 ? 1u : 0u);
+  const uint32_t k0 = blockIdx.y * kStratCols, C1 = R + E;
   const long i = wv * 64 + lane;
   const size_t ii = (size_t)min(i, n_slot - 1);
   const int32_t key = ikey[ii];
@@ -1353,11 +1426,11 @@ fdg_strat_stitch(const int32_t *__restrict__ ikey, const double *__restrict__ iv
   double s[kStratVals];
 #pragma unroll
   for (uint32_t j = 0; j < kStratVals; ++j) {
-    const uint32_t kk = min(k0 + (j & (kStratCols - 1u)), R);      // clamped: a column past R is never written
+    const uint32_t kk = min(k0 + (j & (kStratCols - 1u)), C1 - 1u);   // clamped: a column past the last is never written
     const double v = ival[(size_t)((j < kStratCols ? 0u : C1) + kk) * (size_t)istride + ii];
     s[j] = ok ? v : 0.0;
   }
-  strat_wave_reduce(key, ok, lane, s, k0, C1, strat_wmask(k0, R, live, n_live), sum, sum2, final != 0, rkey, rval, rstride,
+  strat_wave_reduce(key, ok, lane, s, k0, C1, strat_wmask(k0, R, E, live, em), sum, sum2, final != 0, rkey, rval, rstride,
                     slot_base + 2 * wv);
 }
 
@@ -1743,7 +1816,7 @@ FobsTables fobs_tables(const fdg_graph *g, const FobsPlan &q, const fdg_freq_obs
 
 // How the per-hypercube pass is cut: the record buffers of the levels (slots: two per wave of the level below).  A chunk's levels
 // alternate between a and b, the chunks' own records (two per chunk) lie in c and go through a and b again after the last chunk.
-// A function of (n_sample, n_root, FDG_ROOT_SCRATCH_MB) only.
+// A function of (n_sample, n_root, the E columns behind the roots', FDG_ROOT_SCRATCH_MB) only.
 struct StratPlan {
   uint32_t H = 1, n_grp = 1, V2 = 2;
   long n_chunk = 1, cap_a = 2, cap_b = 2, cap_c = 2;
@@ -1751,11 +1824,11 @@ struct StratPlan {
   static size_t buf_bytes(long cap, uint32_t V2) { return page_up((size_t)cap * 4u) + page_up((size_t)cap * V2 * 8u); }
 };
 
-StratPlan strat_plan(const BinnedPlan &p, int64_t B, uint32_t R, uint32_t H) {
+StratPlan strat_plan(const BinnedPlan &p, int64_t B, uint32_t R, uint32_t H, uint32_t E) {
   StratPlan q;
   q.H = H;
-  q.V2 = 2u * (R + 1u);
-  q.n_grp = (R + 1u + kStratCols - 1u) / kStratCols;
+  q.V2 = 2u * (R + E);
+  q.n_grp = (R + E + kStratCols - 1u) / kStratCols;
   q.n_chunk = ((long)B + p.Bc - 1) / p.Bc;
   q.cap_c = 2 * q.n_chunk;
   q.cap_a = std::max(2 * ((p.Bc + 63) / 64), 2 * ((q.cap_c + 63) / 64));
@@ -1845,7 +1918,8 @@ void raise_lds_limits() {
                                                         {(const void *)fdg_vegas_partials<1>, train},
                                                         {(const void *)fdg_vegas_partials<0, true>, train_grp},
                                                         {(const void *)fdg_vegas_partials<1, true>, train_grp},
-                                                        {(const void *)fdg_vegas_partials<0, false, true>, train}};
+                                                        {(const void *)fdg_vegas_partials<0, false, true>, train},
+                                                        {(const void *)fdg_vegas_partials<0, true, true>, train_grp}};
     MatsubaraPlan mq;
     for (int i = 0; i < 4; ++i) {                          // hsplit, then kw = 1, 2, 4
       mq.hsplit = i == 0;
@@ -1910,20 +1984,26 @@ int check_vegas(const fdg_graph *g, const BinnedCall &c) {
 }
 
 // ... and the stratified calls': the VEGAS calls' cases, then the strata and the per-hypercube arrays.
-int check_strat_call(const fdg_graph *g, const BinnedCall &c) {
+int check_strat_arrays(const fdg_graph *g, const BinnedCall &c, uint32_t n_extra) {
   const StratRun &s = *c.sr;
-  if (!s.strat || !s.d_cube || !s.d_sum || !s.d_sum2) { set_error("null strat, d_cube, d_cube_sum or d_cube_sum2"); return FDG_E_INVALID; }
-  int rc = check_vegas(g, c);
-  if (rc) return rc;
   const double *out[5] = {s.d_sum, s.d_sum2, c.d_acc, c.d_acc2, c.vg->d_hist};
   for (int a = 0; a < 2; ++a)
     for (int b = a + 1; b < 5; ++b)
       if (out[a] == out[b]) { set_error("d_cube_sum or d_cube_sum2 is the same buffer as another output"); return FDG_E_INVALID; }
   uint32_t H;
-  rc = check_strat(s.strat, c.vg->D, &H);
+  const int rc = check_strat(s.strat, c.vg->D, &H);
   if (rc) return rc;
-  if ((uint64_t)H * (g->prog.R + 1ull) > (1ull << 24)) { set_error("H * (n_root + 1) > 1 << 24"); return FDG_E_UNSUPPORTED; }
+  if ((uint64_t)H * ((uint64_t)g->prog.R + n_extra) > (1ull << 24)) {
+    set_error(n_extra == 1 && !c.wg ? "H * (n_root + 1) > 1 << 24" : "H * (n_root + n_group) > 1 << 24"); return FDG_E_UNSUPPORTED;
+  }
   return FDG_OK;
+}
+
+int check_strat_call(const fdg_graph *g, const BinnedCall &c) {
+  const StratRun &s = *c.sr;
+  if (!s.strat || !s.d_cube || !s.d_sum || !s.d_sum2) { set_error("null strat, d_cube, d_cube_sum or d_cube_sum2"); return FDG_E_INVALID; }
+  const int rc = check_vegas(g, c);
+  return rc ? rc : check_strat_arrays(g, c, 1u);
 }
 
 // ... and the projection calls': the descriptor, then what the call asks for besides (moments: d_acc and d_acc2 together; training:
@@ -1989,6 +2069,15 @@ int check_grouped(const fdg_graph *g, const BinnedCall &c, const fdg_matsubara *
       if (w->var_mask[gi] >> c.vg->D) { set_error("var_mask names a variable >= n_dim"); return FDG_E_INVALID; }
   if (w->n_group > 1 && w->weight_group_stride < c.B) { set_error("weight_group_stride < n_sample"); return FDG_E_INVALID; }
   return check_blocks(g, c, m, mc_T);
+}
+
+// ... and the stratified grouped calls': the stratified calls' NULL arrays, the grouped calls' cases (which end in the VEGAS calls'),
+// then the strata and the per-hypercube arrays, [H][n_root + n_group].
+int check_strat_grouped_call(const fdg_graph *g, const BinnedCall &c) {
+  const StratRun &s = *c.sr;
+  if (!s.strat || !s.d_cube || !s.d_sum || !s.d_sum2) { set_error("null strat, d_cube, d_cube_sum or d_cube_sum2"); return FDG_E_INVALID; }
+  const int rc = check_grouped(g, c, nullptr, nullptr);
+  return rc ? rc : check_strat_arrays(g, c, c.wg->n_group);
 }
 
 // ... and the observables calls': the descriptor first (the coefficients need the handle's n_root), then the grouped calls' cases
@@ -2088,11 +2177,15 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
   }
   // ... and the record buffers of the per-hypercube pass behind that
   const StratRun *sr = c.sr;
+  // (with several groups one column per group behind the roots', the GRP instances; else the one coef column of the ungrouped call,
+  // whose root list a single group's is)
   StratPlan sp;
   VegasStrat sv = {};
+  const bool grp_s = sr && grp_w;
+  uint32_t semask = 0;                                     // grp_s: bit gi set = group gi has a root that exists
   if (sr) {
     sv = vegas_strat(sr->strat, vg->D);
-    sp = strat_plan(p, c.B, R, sv.H);
+    sp = strat_plan(p, c.B, R, sv.H, grp_s ? NG : 1u);
   }
   int rc = ensure_root_scratch(g, proj_bytes + grp_bytes + obs_bytes + fobs_bytes + sp.bytes);
   if (rc) return rc;
@@ -2128,6 +2221,8 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
       if (exists(k)) ++gstart[wg->root_group[k] + 1u];
     for (uint32_t gi = 0; gi < NG; ++gi) gstart[gi + 1u] += gstart[gi];
     std::copy(gstart.begin(), gstart.end(), hg.begin() + (d_gstart - d_gtab));
+    for (uint32_t gi = 0; gi < NG; ++gi)
+      if (gstart[gi + 1u] > gstart[gi]) semask |= 1u << gi;
     if (grp_t) {
       uint8_t *hl = (uint8_t *)(hg.data() + gtab_words);
       bool dead = false;
@@ -2211,9 +2306,9 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
       const long nw = (n_slot + 63) / 64;
       const bool top = nw == 1;
       const StratBuf out = !top ? (in.key == sa.key ? sb : sa) : sc;
-      hipLaunchKernelGGL(fdg_strat_stitch, dim3((unsigned)((nw + kBinWaves - 1) / kBinWaves), sp.n_grp), dim3(256), 0, st, in.key, in.val,
-                         in.cap, n_slot, R, live, n_live, sr->d_sum, sr->d_sum2, (top && last) ? 1 : 0, out.key, out.val, out.cap,
-                         top ? 2 * chunk : 0L);
+      hipLaunchKernelGGL(grp_s ? fdg_strat_stitch<true> : fdg_strat_stitch<false>, dim3((unsigned)((nw + kBinWaves - 1) / kBinWaves), sp.n_grp),
+                         dim3(256), 0, st, in.key, in.val, in.cap, n_slot, R, live, n_live, sr->d_sum, sr->d_sum2, (top && last) ? 1 : 0,
+                         out.key, out.val, out.cap, top ? 2 * chunk : 0L, NG, semask);
       HIP_TRY(hipGetLastError());
       if (top) return FDG_OK;
       in = out;
@@ -2258,7 +2353,7 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
     if (vg) {
       const double *cf = vg->coef ? d_coef : nullptr;
       // (the calls without a discrete variable carry no bin vector: null, base 0, one bin)
-      const auto tpass = sr      ? fdg_vegas_partials<0, false, true>
+      const auto tpass = sr      ? (grp_t ? fdg_vegas_partials<0, true, true> : fdg_vegas_partials<0, false, true>)
                          : grp_t ? (vg->binned ? fdg_vegas_partials<1, true> : fdg_vegas_partials<0, true>)
                                  : (vg->binned ? fdg_vegas_partials<1> : fdg_vegas_partials<0>);
       hipLaunchKernelGGL(tpass, dim3(q.n_seg * q.n_slice), dim3(256), q.lds, st, roots, (long)p.Bc, n, w, d_kidx, cf, n_live, vg->seed,
@@ -2269,9 +2364,10 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
         // the per-hypercube pass, the chunk's last reader of the roots: level 0 over the samples, then the levels over its records
         const bool top = ntile == 1;
         const StratBuf out = top ? sc : sa;
-        hipLaunchKernelGGL(fdg_strat_partials, dim3((unsigned)((ntile + kBinWaves - 1) / kBinWaves), sp.n_grp), dim3(256), 0, st, roots,
-                           (long)p.Bc, n, sr->d_cube + c0, sp.H, w, d_kidx, cf, n_live, R, live, sr->d_sum, sr->d_sum2, out.key, out.val,
-                           out.cap, top ? 2 * (c0 / p.Bc) : 0L);
+        hipLaunchKernelGGL(grp_s ? fdg_strat_partials<true> : fdg_strat_partials<false>,
+                           dim3((unsigned)((ntile + kBinWaves - 1) / kBinWaves), sp.n_grp), dim3(256), 0, st, roots, (long)p.Bc, n,
+                           sr->d_cube + c0, sp.H, w, d_kidx, cf, n_live, R, live, sr->d_sum, sr->d_sum2, out.key, out.val, out.cap,
+                           top ? 2 * (c0 / p.Bc) : 0L, d_gtab, d_gstart, NG, wstride, semask);
         HIP_TRY(hipGetLastError());
         if (!top) {
           rc = strat_levels(sa, 2 * ntile, false, c0 / p.Bc);
@@ -2485,6 +2581,29 @@ int fdg_mc_accumulate_device_strat(fdg_graph *g, const double *d_K, int64_t ks, 
   return rc ? rc : accumulate_mc(g, d_K, ks, kc, d_T, ts, tc, kF, beta, lambda, c);
 }
 
+int fdg_accumulate_device_strat_grouped(fdg_graph *g, const double *d_leaf, int64_t ss, int64_t ls, int64_t lts, const double *d_weight,
+                                        const double *coef, uint64_t seed, uint64_t sample_offset, uint32_t n_dim, uint32_t n_grid,
+                                        double *d_acc, double *d_acc2, double *d_hist, const uint32_t *strat, const int32_t *d_cube,
+                                        double *d_cube_sum, double *d_cube_sum2, const fdg_weight_groups *wg, int64_t B, void *stream) {
+  const VegasRun vg{coef, seed, sample_offset, n_dim, n_grid, d_hist, false, nullptr};
+  const StratRun sr{strat, d_cube, d_cube_sum, d_cube_sum2};
+  const BinnedCall c{nullptr, 0, 1, d_weight, d_acc, d_acc2, B, stream, &vg, nullptr, wg, nullptr, &sr};
+  const int rc = check_strat_grouped_call(g, c);
+  return rc ? rc : accumulate_leaf(g, d_leaf, ss, ls, lts, c);
+}
+
+int fdg_mc_accumulate_device_strat_grouped(fdg_graph *g, const double *d_K, int64_t ks, int64_t kc, const double *d_T, int64_t ts, int64_t tc,
+                                           double kF, double beta, double lambda, const double *d_weight, const double *coef, uint64_t seed,
+                                           uint64_t sample_offset, uint32_t n_dim, uint32_t n_grid, double *d_acc, double *d_acc2,
+                                           double *d_hist, const uint32_t *strat, const int32_t *d_cube, double *d_cube_sum,
+                                           double *d_cube_sum2, const fdg_weight_groups *wg, int64_t B, void *stream) {
+  const VegasRun vg{coef, seed, sample_offset, n_dim, n_grid, d_hist, false, nullptr};
+  const StratRun sr{strat, d_cube, d_cube_sum, d_cube_sum2};
+  const BinnedCall c{nullptr, 0, 1, d_weight, d_acc, d_acc2, B, stream, &vg, nullptr, wg, nullptr, &sr};
+  const int rc = check_strat_grouped_call(g, c);
+  return rc ? rc : accumulate_mc(g, d_K, ks, kc, d_T, ts, tc, kF, beta, lambda, c);
+}
+
 int fdg_vegas_sample_device_strat(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, const uint32_t *strat,
                                   const int64_t *d_start, uint64_t seed, uint64_t sample_offset, double *d_x, int64_t x_sample_stride,
                                   int64_t x_col_stride, double *d_jac, int32_t *d_cube, int32_t *d_cell, int64_t B, void *stream) {
@@ -2506,12 +2625,19 @@ int fdg_vegas_sample_device_strat(const double *d_grid, uint32_t n_dim, uint32_t
 // The allocation of the next iteration's samples to the hypercubes; host only, fp64, in the order include/fdg.h states.
 int fdg_strat_allocate(const double *cube_sum, const double *cube_sum2, uint32_t ld, uint32_t col, const int64_t *start_old, uint32_t H,
                        int64_t n_total, double beta, int64_t *start_new) {
-  if (!start_new || (start_old && (!cube_sum || !cube_sum2))) { set_error("null argument"); return FDG_E_INVALID; }
+  return fdg_strat_allocate_cols(cube_sum, cube_sum2, ld, &col, 1, start_old, H, n_total, beta, start_new);
+}
+
+int fdg_strat_allocate_cols(const double *cube_sum, const double *cube_sum2, uint32_t ld, const uint32_t *cols, uint32_t n_col,
+                            const int64_t *start_old, uint32_t H, int64_t n_total, double beta, int64_t *start_new) {
+  if (!start_new || !cols || (start_old && (!cube_sum || !cube_sum2))) { set_error("null argument"); return FDG_E_INVALID; }
+  if (n_col == 0) { set_error("n_col == 0"); return FDG_E_INVALID; }
   if (H == 0) { set_error("H == 0"); return FDG_E_INVALID; }
   if (H > FDG_STRAT_CUBE_MAX) { set_error("H > FDG_STRAT_CUBE_MAX"); return FDG_E_UNSUPPORTED; }
   if (n_total < 2 * (int64_t)H) { set_error("n_total < 2 H"); return FDG_E_INVALID; }
   if (!(beta >= 0.0 && beta <= 1.0)) { set_error("beta outside [0, 1]"); return FDG_E_INVALID; }
-  if (start_old && col >= ld) { set_error("col >= ld"); return FDG_E_INVALID; }
+  for (uint32_t i = 0; start_old && i < n_col; ++i)
+    if (cols[i] >= ld) { set_error("col >= ld"); return FDG_E_INVALID; }
   const int64_t spare = n_total - 2 * (int64_t)H;
   std::vector<int64_t> cnt(H);
   std::vector<double> dh(H, 0.0);
@@ -2521,10 +2647,14 @@ int fdg_strat_allocate(const double *cube_sum, const double *cube_sum2, uint32_t
     for (uint32_t h = 0; h < H; ++h) {
       const int64_t n_h = start_old[h + 1] - start_old[h];
       if (n_h < 2) { set_error("an old count below 2"); return FDG_E_INVALID; }
-      const double s1 = cube_sum[(size_t)h * ld + col], s2 = cube_sum2[(size_t)h * ld + col];
-      if (!std::isfinite(s1) || !std::isfinite(s2)) { set_error("a moment is not finite"); return FDG_E_INVALID; }
       const double nd = (double)n_h, fac = n_old / ((double)H * nd);
-      const double var = std::max(0.0, (s2 - s1 * s1 / nd) / (nd - 1.0)) / (fac * fac);
+      double var = 0.0;                                     // the left fold over cols of each column's own var_h
+      for (uint32_t i = 0; i < n_col; ++i) {
+        const double s1 = cube_sum[(size_t)h * ld + cols[i]], s2 = cube_sum2[(size_t)h * ld + cols[i]];
+        if (!std::isfinite(s1) || !std::isfinite(s2)) { set_error("a moment is not finite"); return FDG_E_INVALID; }
+        const double vc = std::max(0.0, (s2 - s1 * s1 / nd) / (nd - 1.0)) / (fac * fac);
+        var = i ? var + vc : vc;
+      }
       dh[h] = var == 0.0 ? 0.0 : std::pow(var, beta / 2.0);
       S = h ? S + dh[h] : dh[h];
     }
@@ -2692,13 +2822,16 @@ int fdg_vegas_sample_device_discrete(const double *d_grid, uint32_t n_dim, uint3
   return FDG_OK;
 }
 
-// fdg_vegas_sample_device_polar (grouped false; the last three arguments are not read) and fdg_vegas_sample_device_grouped.
+// fdg_vegas_sample_device_polar (grouped false; var_mask, n_group and jac_group_stride are not read), fdg_vegas_sample_device_grouped
+// and, with stratified, fdg_vegas_sample_device_strat_grouped (no discrete variable; strat, d_start and d_cube as the stratified
+// sampler takes them).
 static int vegas_sample_polar(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, const double *d_cdf, uint32_t n_bin,
                               int32_t bin_base, const double *d_ext, uint32_t n_ext, const uint32_t *ext_col, const fdg_vegas_polar *polar,
                               uint32_t n_polar, uint64_t seed, uint64_t sample_offset, double *d_x, int64_t x_sample_stride,
                               int64_t x_col_stride, double *d_jac, int32_t *d_bin, int32_t *d_cell, int64_t B, void *stream, bool grouped,
-                              const uint64_t *var_mask, uint32_t n_group, int64_t jac_group_stride) {
-  const int rc = check_sampler(B, !d_grid || !d_x || !d_jac || (d_cdf && !d_bin) || (grouped && !var_mask), n_dim, n_grid);
+                              const uint64_t *var_mask, uint32_t n_group, int64_t jac_group_stride, bool stratified = false,
+                              const uint32_t *strat = nullptr, const int64_t *d_start = nullptr, int32_t *d_cube = nullptr) {
+  int rc = check_sampler(B, !d_grid || !d_x || !d_jac || (d_cdf && !d_bin) || (grouped && !var_mask), n_dim, n_grid);
   if (rc) return rc;
   if (!d_cdf) n_bin = 1, n_ext = 0;                       // no discrete variable: its arguments are ignored
   if (n_bin == 0) { set_error("n_bin == 0"); return FDG_E_INVALID; }
@@ -2750,18 +2883,34 @@ static int vegas_sample_polar(const double *d_grid, uint32_t n_dim, uint32_t n_g
     }
     if (n_group > 1 && jac_group_stride < B) { set_error("jac_group_stride < n_sample"); return FDG_E_INVALID; }
   }
+  if (stratified) {
+    if (!strat || !d_start || !d_cube) { set_error("null strat, d_start or d_cube"); return FDG_E_INVALID; }
+    uint32_t H;
+    rc = check_strat(strat, n_dim, &H);
+    if (rc) return rc;
+  }
   if (B == 0) return FDG_OK;
   const size_t lds = (size_t)__builtin_popcountll(pol.grouped) * 256u * sizeof(double);
   static std::once_flag once;
   std::call_once(once, [] {
-    for (const void *k : {(const void *)fdg_vegas_sample_polar<false>, (const void *)fdg_vegas_sample_polar<true>})
+    for (const void *k : {(const void *)fdg_vegas_sample_polar<false>, (const void *)fdg_vegas_sample_polar<true>,
+                          (const void *)fdg_vegas_sample_polar<false, true>, (const void *)fdg_vegas_sample_polar<true, true>})
       (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, FDG_VEGAS_DIM_MAX * 256 * (int)sizeof(double));
     (void)hipGetLastError();
   });
   const long grid = std::min<long>(((long)B + 255) / 256, 256L * 16);
-  hipLaunchKernelGGL(grouped ? fdg_vegas_sample_polar<true> : fdg_vegas_sample_polar<false>, dim3((unsigned)grid), dim3(256), lds,
-                     (hipStream_t)stream, d_grid, n_dim, n_grid, cols, pol, d_cdf, n_bin, bin_base, d_ext, n_ext, ecols, seed, sample_offset,
-                     d_x, (long)x_sample_stride, (long)x_col_stride, d_jac, d_bin, d_cell, (long)B, gm, (long)jac_group_stride);
+  if (stratified) {
+    // (the kernel arguments -- cols, pol, ecols, gm and the strata by value -- come to about 1.6 KiB of the 4 KiB segment)
+    const VegasStratArgs sa{vegas_strat(strat, n_dim), d_start, d_cube};
+    hipLaunchKernelGGL((grouped ? fdg_vegas_sample_polar<true, true> : fdg_vegas_sample_polar<false, true>), dim3((unsigned)grid), dim3(256),
+                       lds, (hipStream_t)stream, d_grid, n_dim, n_grid, cols, pol, nullptr, 1u, 0, nullptr, 0u, ecols, seed, sample_offset,
+                       d_x, (long)x_sample_stride, (long)x_col_stride, d_jac, nullptr, d_cell, (long)B, gm, (long)jac_group_stride, sa);
+  } else {
+    hipLaunchKernelGGL(grouped ? fdg_vegas_sample_polar<true> : fdg_vegas_sample_polar<false>, dim3((unsigned)grid), dim3(256), lds,
+                       (hipStream_t)stream, d_grid, n_dim, n_grid, cols, pol, d_cdf, n_bin, bin_base, d_ext, n_ext, ecols, seed,
+                       sample_offset, d_x, (long)x_sample_stride, (long)x_col_stride, d_jac, d_bin, d_cell, (long)B, gm,
+                       (long)jac_group_stride, VegasNoStrat{});
+  }
   HIP_TRY(hipGetLastError());
   return FDG_OK;
 }
@@ -2782,6 +2931,17 @@ int fdg_vegas_sample_device_grouped(const double *d_grid, uint32_t n_dim, uint32
                                     int64_t x_col_stride, double *d_jac, int32_t *d_bin, int32_t *d_cell, int64_t B, void *stream) {
   return vegas_sample_polar(d_grid, n_dim, n_grid, col, d_cdf, n_bin, bin_base, d_ext, n_ext, ext_col, polar, n_polar, seed, sample_offset, d_x,
                             x_sample_stride, x_col_stride, d_jac, d_bin, d_cell, B, stream, true, var_mask, n_group, jac_group_stride);
+}
+
+int fdg_vegas_sample_device_strat_grouped(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col,
+                                          const fdg_vegas_polar *polar, uint32_t n_polar, const uint64_t *var_mask, uint32_t n_group,
+                                          int64_t jac_group_stride, const uint32_t *strat, const int64_t *d_start, uint64_t seed,
+                                          uint64_t sample_offset, double *d_x, int64_t x_sample_stride, int64_t x_col_stride, double *d_jac,
+                                          int32_t *d_cube, int32_t *d_cell, int64_t B, void *stream) {
+  const bool grouped = var_mask || n_group;               // neither: one jacobian, the full fold (polar without groups)
+  return vegas_sample_polar(d_grid, n_dim, n_grid, col, nullptr, 1, 0, nullptr, 0, nullptr, polar, n_polar, seed, sample_offset, d_x,
+                            x_sample_stride, x_col_stride, d_jac, nullptr, d_cell, B, stream, grouped, var_mask, n_group, jac_group_stride,
+                            true, strat, d_start, d_cube);
 }
 
 void fdg_sincos(double x, double *s, double *c) { fdg_sincos_impl(x, *s, *c); }

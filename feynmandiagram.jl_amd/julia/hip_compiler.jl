@@ -355,6 +355,18 @@ function strat_allocate!(start_new::Vector{Int64}, cube_sum::Union{Nothing,Matri
         start_old === nothing ? C_NULL : start_old, H, n_total, beta, start_new))
     return start_new
 end
+# The allocation from several rows (fdg_strat_allocate_cols): cols the 1-based rows whose variances are added up, in that order.
+function strat_allocate_cols!(start_new::Vector{Int64}, cube_sum::Union{Nothing,Matrix{Float64}}, cube_sum2::Union{Nothing,Matrix{Float64}},
+    cols::AbstractVector{<:Integer}, start_old::Union{Nothing,Vector{Int64}}, n_total::Integer; beta::Float64=0.75)
+    H = length(start_new) - 1
+    ld = cube_sum === nothing ? 0 : size(cube_sum, 1)
+    cv = UInt32.(cols .- 1)
+    _fdg_check(ccall((:fdg_strat_allocate_cols, _libfdg), Cint,
+        (Ptr{Float64}, Ptr{Float64}, UInt32, Ptr{UInt32}, UInt32, Ptr{Int64}, UInt32, Int64, Float64, Ptr{Int64}),
+        cube_sum === nothing ? C_NULL : cube_sum, cube_sum2 === nothing ? C_NULL : cube_sum2, ld, cv, length(cv),
+        start_old === nothing ? C_NULL : start_old, H, n_total, beta, start_new))
+    return start_new
+end
 # ---- a discrete external variable (include/fdg.h; no counterpart in the reference: the caller's side of test/ver4.jl:224-237) ---- #
 # ExtKidx = MCIntegration.Discrete(1, Nk): d_cdf (n_bin + 1, on the device) is the variable's cumulative distribution, d_ext (n_ext x n_bin,
 # column j = what value j means) goes to the columns ext_col (1-based) of x; d_bin[b] is the value drawn (1-based by default), d_jac[b] the
@@ -584,6 +596,70 @@ function mc_accumulate_device_grouped!(f::GraphFunc, d_acc::Ptr{Float64}, d_acc2
     end
     return nothing
 end
+# ---- stratified sampling with polar groups and weight groups (include/fdg.h: the _strat_grouped calls) ---- #
+# vegas_sample_device_grouped! without a discrete variable, inside the strata of the sample's hypercube (strat, d_start, d_cube as
+# vegas_sample_device_strat! takes them); every group's jacobian carries n_total / (H n_h).  var_mask empty: one jacobian, the full
+# fold.  Unverified: there is no Julia in the image these wrappers were written in.
+function vegas_sample_device_strat_grouped!(d_x::Ptr{Float64}, d_jac::Ptr{Float64}, d_cube::Ptr{Int32}, d_grid::Ptr{Float64},
+    n_dim::Integer, n_grid::Integer, B::Integer, polar::AbstractVector, var_mask::Vector{UInt64}, strat::AbstractVector{<:Integer},
+    d_start::Ptr{Int64}; jac_group_stride::Integer=B, col::Union{Nothing,AbstractVector{<:Integer}}=nothing, seed::Integer=0,
+    sample_offset::Integer=0, x_strides=(1, B), d_cell::Ptr{Int32}=Ptr{Int32}(C_NULL), stream::Ptr{Cvoid}=C_NULL)
+    c = col === nothing ? nothing : UInt32.(col .- 1)
+    sv = UInt32.(strat)
+    p = zeros(UInt32, 5 * max(length(polar), 1))
+    for (g, (var, cols)) in enumerate(polar)
+        length(cols) in (2, 3) || error("a polar group has 2 or 3 columns")
+        p[5g-4] = var - 1
+        p[5g-3] = length(cols)
+        p[5g-2:5g-3+length(cols)] .= UInt32.(cols .- 1)
+    end
+    _fdg_check(ccall((:fdg_vegas_sample_device_strat_grouped, _libfdg), Cint,
+        (Ptr{Float64}, UInt32, UInt32, Ptr{UInt32}, Ptr{UInt32}, UInt32, Ptr{UInt64}, UInt32, Int64, Ptr{UInt32}, Ptr{Int64}, UInt64,
+         UInt64, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Int64, Ptr{Cvoid}),
+        d_grid, n_dim, n_grid, c === nothing ? C_NULL : c, isempty(polar) ? C_NULL : p, length(polar),
+        isempty(var_mask) ? C_NULL : var_mask, length(var_mask), jac_group_stride, sv, d_start, seed, sample_offset, d_x, x_strides[1],
+        x_strides[2], d_jac, d_cube, d_cell, B, stream))
+    return nothing
+end
+# accumulate_device_strat! with weight groups: d_weight is B x n_group column-major by default, d_cube_sum, d_cube_sum2
+# ((R + n_group) x H each, added to; row R + g the combination of group g's roots).
+function accumulate_device_strat_grouped!(f::GraphFunc, d_leaf::Ptr{Float64}, d_weight::Ptr{Float64}, d_acc::Ptr{Float64},
+    d_acc2::Ptr{Float64}, d_hist::Ptr{Float64}, strat::AbstractVector{<:Integer}, d_cube::Ptr{Int32}, d_cube_sum::Ptr{Float64},
+    d_cube_sum2::Ptr{Float64}, n_dim::Integer, n_grid::Integer, B::Integer; dof::AbstractVector, pools::AbstractVector,
+    weight_group_stride::Integer=B, coef::Union{Nothing,Vector{Float64}}=nothing, seed::Integer=0, sample_offset::Integer=0,
+    leaf_strides=(1, B), tile_stride::Integer=0, stream::Ptr{Cvoid}=C_NULL)
+    sv = UInt32.(strat)
+    root_group, var_mask = weight_groups_from_dof(dof, pools)
+    GC.@preserve root_group var_mask begin
+        wg = _FdgWeightGroups(length(var_mask), pointer(root_group), pointer(var_mask), weight_group_stride)
+        _fdg_check(ccall((:fdg_accumulate_device_strat_grouped, _libfdg), Cint,
+            (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, UInt64, UInt64, UInt32, UInt32, Ptr{Float64},
+             Ptr{Float64}, Ptr{Float64}, Ptr{UInt32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ref{_FdgWeightGroups}, Int64, Ptr{Cvoid}),
+            f.handle, d_leaf, leaf_strides[1], leaf_strides[2], tile_stride, d_weight, coef === nothing ? C_NULL : coef, seed,
+            sample_offset, n_dim, n_grid, d_acc, d_acc2, d_hist, sv, d_cube, d_cube_sum, d_cube_sum2, wg, B, stream))
+    end
+    return nothing
+end
+function mc_accumulate_device_strat_grouped!(f::GraphFunc, d_K::Ptr{Float64}, d_T::Ptr{Float64}, d_weight::Ptr{Float64},
+    d_acc::Ptr{Float64}, d_acc2::Ptr{Float64}, d_hist::Ptr{Float64}, strat::AbstractVector{<:Integer}, d_cube::Ptr{Int32},
+    d_cube_sum::Ptr{Float64}, d_cube_sum2::Ptr{Float64}, n_dim::Integer, n_grid::Integer, B::Integer; dof::AbstractVector,
+    pools::AbstractVector, kF::Float64, beta::Float64, lambda::Float64, weight_group_stride::Integer=B,
+    coef::Union{Nothing,Vector{Float64}}=nothing, seed::Integer=0, sample_offset::Integer=0, k_strides=(1, B), t_strides=(1, B),
+    stream::Ptr{Cvoid}=C_NULL)
+    sv = UInt32.(strat)
+    root_group, var_mask = weight_groups_from_dof(dof, pools)
+    GC.@preserve root_group var_mask begin
+        wg = _FdgWeightGroups(length(var_mask), pointer(root_group), pointer(var_mask), weight_group_stride)
+        _fdg_check(ccall((:fdg_mc_accumulate_device_strat_grouped, _libfdg), Cint,
+            (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Int64, Float64, Float64, Float64, Ptr{Float64}, Ptr{Float64},
+             UInt64, UInt64, UInt32, UInt32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64},
+             Ref{_FdgWeightGroups}, Int64, Ptr{Cvoid}),
+            f.handle, d_K, k_strides[1], k_strides[2], d_T, t_strides[1], t_strides[2], kF, beta, lambda, d_weight,
+            coef === nothing ? C_NULL : coef, seed, sample_offset, n_dim, n_grid, d_acc, d_acc2, d_hist, sv, d_cube, d_cube_sum,
+            d_cube_sum2, wg, B, stream))
+    end
+    return nothing
+end
 # Observables: linear combinations of the roots and their covariance (fdg_accumulate_device_observables).  coef is n_root x n_obs
 # column-major (coef[k, m]: the factor of root k in observable m -- the C side's row-major [n_obs][n_root]); d_obs is n_obs x n_bin and
 # d_cov n_obs x n_obs x n_bin column-major, both added to.  d_acc = d_acc2 = C_NULL: no per-root moments.  These wrappers pass one
@@ -738,7 +814,7 @@ function accumulate_device!(f::GraphFunc, d_acc::Ptr{Float64}, d_leaf::Ptr{Float
         f.handle, d_leaf, leaf_strides[1], leaf_strides[2], d_weight, d_acc, B, stream))
 end
 
-export compile_hip, GraphFunc, eval_device!, accumulate_device!, eval_device_tiled!, accumulate_device_tiled!, accumulate_device_binned!, mc_accumulate_device_binned!, accumulate_device_moments!, mc_accumulate_device_moments!, vegas_sample_device!, accumulate_device_vegas!, mc_accumulate_device_vegas!, vegas_refine!, vegas_sample_device_discrete!, accumulate_device_vegas_binned!, mc_accumulate_device_vegas_binned!, vegas_refine_discrete!, vegas_sample_device_polar!, fdg_sincos, fdg_matsubara_phase, accumulate_device_matsubara!, mc_accumulate_device_matsubara!, weight_groups_from_dof, vegas_sample_device_grouped!, accumulate_device_grouped!, mc_accumulate_device_grouped!, accumulate_device_observables!, mc_accumulate_device_observables!, accumulate_device_freq_observables!, mc_accumulate_device_freq_observables!, batch_alloc, batch_free, tile_major!, from_tile_major!, vegas_sample_device_strat!, accumulate_device_strat!, mc_accumulate_device_strat!, strat_allocate!
+export compile_hip, GraphFunc, eval_device!, accumulate_device!, eval_device_tiled!, accumulate_device_tiled!, accumulate_device_binned!, mc_accumulate_device_binned!, accumulate_device_moments!, mc_accumulate_device_moments!, vegas_sample_device!, accumulate_device_vegas!, mc_accumulate_device_vegas!, vegas_refine!, vegas_sample_device_discrete!, accumulate_device_vegas_binned!, mc_accumulate_device_vegas_binned!, vegas_refine_discrete!, vegas_sample_device_polar!, fdg_sincos, fdg_matsubara_phase, accumulate_device_matsubara!, mc_accumulate_device_matsubara!, weight_groups_from_dof, vegas_sample_device_grouped!, accumulate_device_grouped!, mc_accumulate_device_grouped!, accumulate_device_observables!, mc_accumulate_device_observables!, accumulate_device_freq_observables!, mc_accumulate_device_freq_observables!, batch_alloc, batch_free, tile_major!, from_tile_major!, vegas_sample_device_strat!, accumulate_device_strat!, mc_accumulate_device_strat!, strat_allocate!, strat_allocate_cols!, vegas_sample_device_strat_grouped!, accumulate_device_strat_grouped!, mc_accumulate_device_strat_grouped!
 
 # ---- multi-GPU: one Julia process per GPU, ONE reduction of the accumulated observable ------------ #
 # (include/fdg.h, "multi-GPU").  Rank 0 calls `comm_unique_id()` and ships the 128 bytes to the other

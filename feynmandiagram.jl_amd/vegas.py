@@ -32,7 +32,9 @@ the device; the results gain ``obs_mean``, ``obs_stderr``, ``obs_chi2_dof`` and 
 Adaptive stratified sampling (``Stratification``, ``strat_for``, the keyword ``strat``; fdg_vegas_sample_device_strat,
 fdg_mc_accumulate_device_strat, fdg_strat_allocate): Lepage's VEGAS+ on top of the map.  The unit cube of the map's coordinates is cut
 into hypercubes, each receives at least two samples and the rest go where the integrand's standard deviation is largest -- what a
-separable map cannot do for a ridge along a diagonal (a propagator of ``k1 + k2`` or ``T[i] - T[j]``).
+separable map cannot do for a ridge along a diagonal (a propagator of ``k1 + k2`` or ``T[i] - T[j]``).  Together with spherical
+momentum variables and weight groups: ``vegas_integrate_stratified`` (fdg_vegas_sample_device_strat_grouped,
+fdg_[mc_]accumulate_device_strat_grouped, fdg_strat_allocate_cols).
 """
 from __future__ import annotations
 
@@ -292,9 +294,11 @@ def _iteration_seed(seed: int, it: int) -> int:
 
 
 def _integrate_strat(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_iter, n_sample, n_grid, alpha, seed, n_discard, fixed, coef, device,
-                     vmap, specialize_fused, n_total, shard_start, reduce, strat):
-    """:func:`vegas_integrate` with ``strat``.  Per iteration: allocate, sample, accumulate, refine the map, fdg_strat_allocate."""
+                     vmap, specialize_fused, n_total, shard_start, reduce, strat, polar=None, wgroups=None, alloc_cols=None):
+    """:func:`vegas_integrate` with ``strat`` and :func:`vegas_integrate_stratified`.  Per iteration: allocate, sample, accumulate,
+    refine the map, fdg_strat_allocate_cols.  Without ``polar`` and ``wgroups`` the device calls are the plain stratified ones."""
     import torch
+    from .nodetable import FDG_NO_ROOT
     handle = getattr(func_or_handle, "handle", func_or_handle)
     device = torch.device(device)
     R = handle.table.n_root
@@ -303,14 +307,29 @@ def _integrate_strat(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_iter,
     else:
         n_col_k = int(tables.n_loop) * int(tables.dim)
         n_col = n_col_k + int(tables.n_tau)
-    col = [int(c) for c in col]
-    if len(set(col)) != len(col) or not all(0 <= c < n_col for c in col):
+    col = [None if (c is None and polar) else int(c) for c in col]
+    written = [c for c in col if c is not None] + [int(c) for p in (polar or ()) for c in p.cols]
+    if len(set(written)) != len(written) or not all(0 <= c < n_col for c in written):
         raise ValueError(f"col must name distinct columns in [0, {n_col})")
     if vmap is None:
         vmap = VegasMap(uniform_grid(lo, hi, n_grid), device)
     if vmap.n_dim != len(col):
         raise ValueError("one column per variable of the map")
+    groups = _check_polar(polar, col, vmap, n_col) if polar else None
+    if polar and any(c is None for d, c in enumerate(col) if not any(v <= d < v + len(cs) for v, cs in groups)):
+        raise ValueError("only the variables of a polar group go without a column")
     D, G = vmap.n_dim, vmap.n_grid
+    if wgroups is not None:
+        if len(wgroups.root_group) != R or not all(0 <= int(v) < len(wgroups.var_sets) for v in wgroups.root_group):
+            raise ValueError("groups.root_group names one group of groups.var_sets per root")
+        if not 1 <= len(wgroups.var_sets) <= capi.FDG_WEIGHT_GROUP_MAX:
+            raise ValueError(f"need 1 .. {capi.FDG_WEIGHT_GROUP_MAX} weight groups")
+        if not all(0 <= int(d) < D for vs in wgroups.var_sets for d in vs):
+            raise ValueError("groups.var_sets names variables of the map")
+        for var, cs in groups or ():
+            if any(0 < len(set(vs) & set(range(var, var + len(cs)))) < len(cs) for vs in wgroups.var_sets):
+                raise ValueError("a polar group belongs to a weight group whole or not at all")
+    NG = 1 if wgroups is None else len(wgroups.var_sets)      # the columns behind the roots' in the per-hypercube moments
     sv = tuple(int(v) for v in strat.strat)
     if len(sv) != D or not all(v >= 1 for v in sv):
         raise ValueError("strat.strat holds one count >= 1 per variable of the map")
@@ -319,36 +338,55 @@ def _integrate_strat(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_iter,
     N = B if n_total is None else int(n_total)
     if not 0.0 <= strat.beta <= 1.0:
         raise ValueError("strat.beta must lie in [0, 1]")
-    if H > capi.FDG_STRAT_CUBE_MAX or H * (R + 1) > 1 << 24 or N < 2 * H:
-        raise ValueError(f"need at most {capi.FDG_STRAT_CUBE_MAX} hypercubes, H * (n_root + 1) <= 2**24 and n_total >= 2 H")
+    if H > capi.FDG_STRAT_CUBE_MAX or H * (R + NG) > 1 << 24 or N < 2 * H:
+        raise ValueError(f"need at most {capi.FDG_STRAT_CUBE_MAX} hypercubes, H * (n_root + {'n_group' if wgroups is not None else '1'}) "
+                         f"<= 2**24 and n_total >= 2 H")
     if B < 1 or n_iter < 1 or not (0 <= n_discard < n_iter) or not 0 <= int(shard_start) <= N - B:
         raise ValueError("need n_sample >= 1, 0 <= n_discard < n_iter and the shard inside n_total")
+    if alloc_cols is None:
+        # every column behind the roots' that has a root that exists behind it (without groups: the coef column)
+        rs = np.asarray(handle.table.root_slot)
+        have = {0 if wgroups is None else int(wgroups.root_group[k]) for k in range(R) if int(rs[k]) != FDG_NO_ROOT}
+        alloc_cols = [R + g for g in range(NG) if g in have] or [R]
+    alloc_cols = [int(c) for c in alloc_cols]
+    if not alloc_cols or not all(0 <= c < R + NG for c in alloc_cols):
+        raise ValueError(f"alloc_cols names at least one column in [0, {R + NG}) of the per-hypercube moments")
     if specialize_fused and tables is not None:
         handle.specialize_fused(tables)
     fx = np.zeros(n_col) if fixed is None else np.asarray(fixed, dtype=np.float64)
     if fx.shape != (n_col,):
         raise ValueError(f"fixed must hold {n_col} column values")
     out = VegasResult(np.zeros(R), np.zeros(R), np.full(R, np.nan), map=vmap)
-    start, sums = capi.strat_allocate(None, None, R, None, H, N, strat.beta), None
+    start = capi.strat_allocate_cols(None, None, alloc_cols, None, H, N, strat.beta)
     with torch.cuda.device(device):
         st = torch.cuda.current_stream(device).cuda_stream
         x = torch.from_numpy(fx).to(device)[:, None].repeat(1, B).contiguous()          # [n_col, B]: sample stride 1
-        jac = torch.empty(B, dtype=torch.float64, device=device)
+        jac = torch.empty(B if wgroups is None else (NG, B), dtype=torch.float64, device=device)
         cube = torch.empty(B, dtype=torch.int32, device=device)
+        wdesc = None
+        if wgroups is not None:
+            wdesc, _wkeep = capi.make_weight_groups(wgroups.root_group, wgroups.var_sets, B)
         for it in range(int(n_iter)):
             key, off = _iteration_seed(seed, it), int(shard_start)
             d_start = torch.from_numpy(start).to(device)
             m = torch.zeros((2, 1, R), dtype=torch.float64, device=device)
             hist = torch.zeros((D, G), dtype=torch.float64, device=device)
-            cs = torch.zeros((2, H, R + 1), dtype=torch.float64, device=device)
-            capi.vegas_sample_device_strat(vmap.d_grid.data_ptr(), D, G, col, sv, d_start.data_ptr(), key, off, x.data_ptr(), 1, B,
-                                           jac.data_ptr(), cube.data_ptr(), 0, B, st)
-            tail = (jac.data_ptr(), coef, key, off, D, G, m[0].data_ptr(), m[1].data_ptr(), hist.data_ptr(), sv, cube.data_ptr(),
-                    cs[0].data_ptr(), cs[1].data_ptr(), B, st)
-            if tables is None:
-                handle.accumulate_device_strat(x.data_ptr(), 1, B, 0, *tail)
+            cs = torch.zeros((2, H, R + NG), dtype=torch.float64, device=device)
+            if groups or wgroups is not None:
+                capi.vegas_sample_device_strat_grouped(vmap.d_grid.data_ptr(), D, G, col, groups, None if wgroups is None else wgroups.var_sets,
+                                                       B, sv, d_start.data_ptr(), key, off, x.data_ptr(), 1, B, jac.data_ptr(),
+                                                       cube.data_ptr(), 0, B, st)
             else:
-                handle.mc_accumulate_device_strat(x.data_ptr(), 1, B, x.data_ptr() + 8 * n_col_k * B, 1, B, kF, beta, lam, *tail)
+                capi.vegas_sample_device_strat(vmap.d_grid.data_ptr(), D, G, col, sv, d_start.data_ptr(), key, off, x.data_ptr(), 1, B,
+                                               jac.data_ptr(), cube.data_ptr(), 0, B, st)
+            tail = (jac.data_ptr(), coef, key, off, D, G, m[0].data_ptr(), m[1].data_ptr(), hist.data_ptr(), sv, cube.data_ptr(),
+                    cs[0].data_ptr(), cs[1].data_ptr()) + (() if wgroups is None else (wdesc,)) + (B, st)
+            leaf_call = handle.accumulate_device_strat if wgroups is None else handle.accumulate_device_strat_grouped
+            mc_call = handle.mc_accumulate_device_strat if wgroups is None else handle.mc_accumulate_device_strat_grouped
+            if tables is None:
+                leaf_call(x.data_ptr(), 1, B, 0, *tail)
+            else:
+                mc_call(x.data_ptr(), 1, B, x.data_ptr() + 8 * n_col_k * B, 1, B, kF, beta, lam, *tail)
             if reduce is not None:
                 for t in (m, hist, cs):
                     reduce(t)
@@ -359,9 +397,37 @@ def _integrate_strat(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_iter,
             out.histograms.append(hist.cpu().numpy())
             out.cube_counts.append(counts)
             vmap.refine(out.histograms[-1], alpha)
-            start = capi.strat_allocate(h_cs[0], h_cs[1], R, start, H, N, strat.beta)
+            start = capi.strat_allocate_cols(h_cs[0], h_cs[1], alloc_cols, start, H, N, strat.beta)
     out.mean, out.stderr, out.chi2_dof = combine(out.iterations[int(n_discard):])
     return out
+
+
+def vegas_integrate_stratified(func_or_handle, tables, lo, hi, col, strat: Stratification, kF: float = 0.0, beta: float = 1.0, lam: float = 0.0,
+                               *, n_iter: int = 10, n_sample: int = 100_000, n_grid: int = 64, alpha: float = 0.5, seed: int = 0,
+                               n_discard: int = 0, fixed=None, coef=None, device="cuda", vmap: Optional[VegasMap] = None,
+                               specialize_fused: bool = True, n_total: Optional[int] = None, shard_start: int = 0,
+                               reduce: Optional[Callable] = None, polar: Optional[Sequence[PolarVar]] = None,
+                               groups: Optional[WeightGroups] = None, alloc_cols: Optional[Sequence[int]] = None) -> VegasResult:
+    """Adaptive stratified sampling (:class:`Stratification`) together with spherical momentum variables (``polar``) and weight
+    groups (``groups``), which :func:`vegas_integrate` refuses beside ``strat``.  The arguments and the result are those of
+    ``vegas_integrate(..., strat=strat)``; ``tables`` None is the leaf form.
+
+    Per iteration: sample through fdg_vegas_sample_device_strat_grouped by the current allocation (the first is uniform) -- the
+    strata cut the map's own coordinates, a polar group's ``(k, theta, phi)`` --, accumulate through
+    fdg_[mc_]accumulate_device_strat_grouped (with ``polar`` alone: the _strat call on the one jacobian), ``reduce`` on the moments,
+    the histogram and the per-hypercube moments ``[2, H, n_root + n_group]``, refine the map, fdg_strat_allocate_cols.  Every group's
+    weight carries the hypercube's ``n_total / (H n_h)``, also that of a group which does not own every variable.  ``mean`` and
+    ``stderr`` come per root from :func:`strat_variance` on the roots' columns; iteration ``it`` draws with the Philox key of
+    ``vegas_integrate``'s stratified run.
+
+    ``alloc_cols``: the columns of the per-hypercube moments whose variances, added up, steer the next allocation; by default the
+    groups' columns ``n_root + g`` of every group with a root that exists (without ``groups``: column ``n_root``, the ``coef``
+    combination).  With ``polar`` and ``groups`` None the device calls and the result are ``vegas_integrate(strat=...)``'s, bit for
+    bit."""
+    if strat is None:
+        raise ValueError("vegas_integrate_stratified needs a Stratification")
+    return _integrate_strat(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_iter, n_sample, n_grid, alpha, seed, n_discard, fixed,
+                            coef, device, vmap, specialize_fused, n_total, shard_start, reduce, strat, polar, groups, alloc_cols)
 
 
 def groups_from_dof(dof, pools) -> WeightGroups:
@@ -635,10 +701,11 @@ def vegas_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: 
     per-hypercube moments ``[2, H, n_root + 1]``.  ``tables`` may then be None: the leaf form, where the columns of ``x`` are the
     graph's leaves themselves (fdg_accumulate_device_strat), ``col[d]`` the leaf that variable ``d`` fills and ``fixed`` the values
     of the others.  Together with ``polar``, ``matsubara``, ``groups``, ``observables`` or ``freq_observables`` (and with a discrete variable) it raises
-    ValueError: those combinations are not built yet.  None: the calls made and their bits are what they are without this keyword."""
+    ValueError: ``polar`` and ``groups`` go through :func:`vegas_integrate_stratified`, the others are not built yet.  None: the calls made and their bits are what they are without this keyword."""
     if strat is not None:
         if polar or matsubara is not None or groups is not None or observables is not None or freq_observables is not None:
-            raise ValueError("strat cannot be combined with polar, matsubara, groups, observables or freq_observables")
+            raise ValueError("strat cannot be combined with polar, matsubara, groups, observables or freq_observables here "
+                             "(polar and groups: vegas_integrate_stratified)")
         return _integrate_strat(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_iter, n_sample, n_grid, alpha, seed, n_discard, fixed,
                                 coef, device, vmap, specialize_fused, n_total, shard_start, reduce, strat)
     return _integrate(func_or_handle, tables, lo, hi, col, None, kF, beta, lam, n_iter, n_sample, n_grid, alpha, 0.0, seed, n_discard, fixed, coef,

@@ -1043,6 +1043,68 @@ int fdg_mc_accumulate_device_strat(fdg_graph *g, const double *d_K, int64_t k_sa
 int fdg_strat_allocate(const double *cube_sum, const double *cube_sum2, uint32_t ld, uint32_t col, const int64_t *start_old, uint32_t H,
                        int64_t n_total, double beta, int64_t *start_new);
 
+/* ---- Stratified sampling for spherical momenta and weight groups ------------------------------------------------------------------
+ * The two halves of the Monte-Carlo step together: loop momenta in a ball (fdg_vegas_sample_device_polar) and several orders per run
+ * (the weight groups) under the hypercubes above.  The discrete variable, the projection and the observables stay outside these
+ * calls.  MCIntegration is not part of the reference checkout: no counterpart in the reference.
+ *
+ * fdg_vegas_sample_device_strat_grouped: the arguments of fdg_vegas_sample_device_grouped without the discrete variable, plus strat,
+ * d_start and d_cube as fdg_vegas_sample_device_strat takes them.  For sample b with the global index i = sample_offset + b, every
+ * step one rounded fp64 operation, in this order,
+ *   1. the hypercube h (-> d_cube[b]) and its digits s_d exactly as in fdg_vegas_sample_device_strat;
+ *   2. every variable d < n_dim: u the uniform of counter (i, d);  v = ((double)s_d + u) / (double)strat[d];  y = v * G;
+ *      c = min((int)y, G - 1);  fr, wd, the value lo + fr * wd and the factor G * wd as everywhere; a polar group's variables are
+ *      stratified in (k, theta, phi), the coordinates of the map;
+ *   3. the variables of a polar group come out as Cartesian columns by the very statements of fdg_vegas_sample_device_polar;
+ *   4. j_g by steps 1-2 of fdg_vegas_sample_device_grouped (the fold over the mask's variables, then its polar groups' factors);
+ *   5. j_g * fac_h -> d_jac[g * jac_group_stride + b],  fac_h = (double)n_total / ((double)H * (double)n_h).
+ * EVERY group takes fac_h, also a group whose mask leaves variables out: the samples are drawn with the density
+ * prod_d (1 / (G wd_d)) / fac_h over all n_dim variables, and an integrand that does not depend on a variable sees that variable's
+ * marginal, whose factors cancel between the strata only together with fac_h (stratifying over a variable an integrand does not
+ * depend on leaves its estimate unbiased; dropping fac_h for such a group would not).
+ * var_mask == NULL with n_group == 0: one jacobian, the full fold (fdg_vegas_sample_device_polar's) times fac_h -> d_jac[b].
+ * Identities: with n_polar == 0 and no groups, d_x, d_jac, d_cube and d_cell carry the bits of fdg_vegas_sample_device_strat; with
+ * every strat[d] == 1 and start = {0, n_total}, d_x, d_jac and d_cell carry the bits of fdg_vegas_sample_device_grouped (of _polar
+ * without groups) with d_cdf == NULL ((0 + u) / 1 and * 1.0 are exact).  Counter-based: shards reproduce the unsharded batch.
+ * FDG_E_INVALID / FDG_E_UNSUPPORTED: the cases of fdg_vegas_sample_device_grouped (var_mask NULL with n_group > 0 among them), then
+ * those of fdg_vegas_sample_device_strat.  All before any device work.
+ *
+ * fdg_[mc_]accumulate_device_strat_grouped: the arguments of the _strat calls plus wg.  With g(k) = root_group[k]:
+ *   d_acc, d_acc2: bit for bit those of the _grouped calls (the same unchanged moments pass and plan).
+ *   d_hist: the grouped training rule (q_g = (w_g s_g)^2, a variable's fold over its owning groups, ascending g) with the cell
+ *     recomputed by the stratified formula from d_cube; a sample whose d_cube lies outside [0, H) is selected away.
+ *   d_cube_sum, d_cube_sum2 (DEVICE, [H][n_root + n_group] doubles each, added to): column k < n_root takes t_k = w_g(k) * root_k and
+ *     t_k * t_k; column n_root + g takes t_g = w_g * s_g and t_g * t_g, s_g the left fold of c_k * r_k over the group's existing
+ *     roots, ascending.  Untouched: the column of an FDG_NO_ROOT root and the column of a group with no root that exists.
+ * With n_group == 1, root_group all zero and a full mask every output carries the bits of the _strat call, d_cube_sum
+ * [H][n_root + 1] included.  No float atomics; samples are selected away, never multiplied by zero; bitwise repeatable; the order of
+ * every sum is a function of (n_sample, n_root, n_group, FDG_ROOT_SCRATCH_MB) only.
+ * FDG_E_INVALID / FDG_E_UNSUPPORTED: the cases of the _strat calls and of the _grouped calls; H * (n_root + n_group) > 1 << 24 is
+ * FDG_E_UNSUPPORTED.  All before any device work.
+ *
+ * fdg_strat_allocate_cols (host only): fdg_strat_allocate from several columns.  Step 1 gives var_h = the left fold, over cols in the
+ * order given, of each column's own var_h, each formed exactly as there; steps 2-5 are unchanged.  n_col == 1 gives the bits of
+ * fdg_strat_allocate, which is this call with one column.  FDG_E_INVALID: cols NULL, n_col == 0, a cols[i] >= ld (with start_old),
+ * and that call's cases.  On error start_new is untouched. */
+int fdg_vegas_sample_device_strat_grouped(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col,
+                                          const fdg_vegas_polar *polar, uint32_t n_polar, const uint64_t *var_mask, uint32_t n_group,
+                                          int64_t jac_group_stride, const uint32_t *strat, const int64_t *d_start, uint64_t seed,
+                                          uint64_t sample_offset, double *d_x, int64_t x_sample_stride, int64_t x_col_stride, double *d_jac,
+                                          int32_t *d_cube, int32_t *d_cell, int64_t n_sample, void *stream);
+int fdg_accumulate_device_strat_grouped(fdg_graph *g, const double *d_leaf, int64_t leaf_sample_stride, int64_t leaf_leaf_stride,
+                                        int64_t leaf_tile_stride, const double *d_weight, const double *coef, uint64_t seed,
+                                        uint64_t sample_offset, uint32_t n_dim, uint32_t n_grid, double *d_acc, double *d_acc2,
+                                        double *d_hist, const uint32_t *strat, const int32_t *d_cube, double *d_cube_sum,
+                                        double *d_cube_sum2, const fdg_weight_groups *wg, int64_t n_sample, void *stream);
+int fdg_mc_accumulate_device_strat_grouped(fdg_graph *g, const double *d_K, int64_t k_sample_stride, int64_t k_comp_stride,
+                                           const double *d_T, int64_t t_sample_stride, int64_t t_comp_stride, double kF, double beta,
+                                           double lambda, const double *d_weight, const double *coef, uint64_t seed,
+                                           uint64_t sample_offset, uint32_t n_dim, uint32_t n_grid, double *d_acc, double *d_acc2,
+                                           double *d_hist, const uint32_t *strat, const int32_t *d_cube, double *d_cube_sum,
+                                           double *d_cube_sum2, const fdg_weight_groups *wg, int64_t n_sample, void *stream);
+int fdg_strat_allocate_cols(const double *cube_sum, const double *cube_sum2, uint32_t ld, const uint32_t *cols, uint32_t n_col,
+                            const int64_t *start_old, uint32_t H, int64_t n_total, double beta, int64_t *start_new);
+
 /* Device workspace control: the interpreter keeps per-sample overflow slots in
  * an HBM panel owned by the handle; it is sized on first use for the number of
  * resident waves.  This releases it (and any loaded module). */
