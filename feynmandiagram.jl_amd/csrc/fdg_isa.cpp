@@ -57,7 +57,13 @@ static_assert(S_LT2 + 2 == S_END && S_PARAM % 4 == 0 && S_LEAF2 % 4 == 0, "SGPR 
 
 // exp(x), x <= 0 in practice: n = rint(x log2 e), r = x - n ln2 (two-part), exp(r) by a degree-11 polynomial
 // (Chebyshev-node interpolant of exp on |r| <= 0.3467, coefficients rounded to double: 1.6e-17 relative, computed with
-// 60-digit arithmetic), scaled by 2^n with v_ldexp_f64 (flushes to 0 / denormals correctly far below)
+// 60-digit arithmetic), scaled by 2^n with v_ldexp_f64 (flushes to 0 / denormals correctly far below).
+// Domain: finite arguments.  Within 2 * 2^-53 relative where exp(x) is normal, within one unit of 2^-1074 where it is
+// subnormal, exactly 0 from -745.14 down to -4e15 (n saturates in v_cvt_i32_f64, the remainder stays small).  Far below,
+// from about -1e44, the remainder is no longer reduced and its polynomial overflows: +-inf for a finite argument, and NaN
+// for +-inf, where the other routes' library exp gives 0 or inf.  No physical sample comes near (|w a| <= |w| beta); there is
+// no clamp.  tests/test_leaf_edges.py restates this sequence in numpy, pins it by 60-digit values and ties the listing and
+// the device's results to the restatement.
 const double kLog2e = 0x1.71547652b82fep+0, kLn2Hi = 0x1.62e42fefa39efp-1, kLn2Lo = 0x1.abc9e3b39803fp-56;
 constexpr int kExpDeg = 11;
 const double kExpC[kExpDeg + 1] = {0x1.0000000000000p+0, 0x1.0000000000000p+0, 0x1.0000000000011p-1, 0x1.555555555555ap-3,
