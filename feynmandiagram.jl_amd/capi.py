@@ -54,6 +54,7 @@ EXPORTS = [
     "fdg_vegas_sample_device_strat", "fdg_accumulate_device_strat", "fdg_mc_accumulate_device_strat", "fdg_strat_allocate",
     "fdg_vegas_sample_device_strat_grouped", "fdg_accumulate_device_strat_grouped", "fdg_mc_accumulate_device_strat_grouped",
     "fdg_strat_allocate_cols",
+    "fdg_chain_propose_device", "fdg_chain_step_device", "fdg_mc_chain_step_device", "fdg_chain_reduce_device",
 ]
 FDG_BIN_MAX = 16384     # fdg_accumulate_device_binned: largest n_bin
 FDG_VEGAS_DIM_MAX, FDG_VEGAS_GRID_MAX = 64, 1024     # the VEGAS map: most variables, most cells per variable
@@ -64,6 +65,7 @@ FDG_WEIGHT_GROUP_MAX = 8  # fdg_weight_groups: most groups of roots with their o
 FDG_OBS_MAX = 16  # fdg_observables: most linear combinations of the roots per call
 FDG_FREQ_OBS_MAX = 8  # fdg_freq_observables: most linear combinations of the projected roots per call
 FDG_STRAT_CUBE_MAX = 1 << 20  # the stratified calls: most hypercubes
+FDG_CHAIN_INIT, FDG_CHAIN_MEASURE = 1, 2  # flags of fdg_[mc_]chain_step_device
 COMM_ID_BYTES = 128
 
 
@@ -296,6 +298,12 @@ def lib():
     L.fdg_mc_accumulate_device_strat_grouped.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, C.c_void_p,
                                                          u64, u64, u32, u32, dp, dp, dp, C.c_void_p, dp, dp, dp, C.c_void_p, i64, vp]
     L.fdg_strat_allocate_cols.argtypes = [C.c_void_p, C.c_void_p, u32, C.c_void_p, u32, C.c_void_p, u32, i64, C.c_double, C.c_void_p]
+    L.fdg_chain_propose_device.argtypes = [dp, u32, u32, C.c_void_p, u32, u64, u64, u64, dp, i64, dp, dp, i64, dp, i64, vp]
+    L.fdg_chain_step_device.argtypes = [vp, dp, i64, dp, u32, u32, C.c_void_p, C.c_double, u64, u64, C.c_uint, dp, i64, dp, dp, dp, dp, dp,
+                                        i64, vp]
+    L.fdg_mc_chain_step_device.argtypes = [vp, dp, i64, C.c_double, C.c_double, C.c_double, dp, u32, u32, C.c_void_p, C.c_double, u64, u64,
+                                           C.c_uint, dp, i64, dp, dp, dp, dp, dp, i64, vp]
+    L.fdg_chain_reduce_device.argtypes = [dp, u32, i64, dp, vp]
     L.fdg_powi.argtypes = [C.c_double, C.c_int32]
     L.fdg_powi.restype = C.c_double
     _lib = L
@@ -686,6 +694,24 @@ class GraphHandle:
                                                            d_cube_sum or None, d_cube_sum2 or None,
                                                            None if groups is None else C.addressof(groups), B, stream))
 
+    # one step of the Markov chain on the VEGAS map after fdg_chain_propose_device: evaluate the proposals (d_xp: [n_col, B] with column
+    # stride xpc), fold, accept, select into the state (x, fac, root, a), measure into sum [n_root + 1, B] with FDG_CHAIN_MEASURE (fdg.h)
+    def chain_step_device(self, d_xp: int, xpc: int, d_facp: int, n_col: int, n_dim: int, coef, gamma: float, seed: int, sample_offset: int,
+                          flags: int, d_x: int, xc: int, d_fac: int, d_root: int, d_a: int, d_sum: int, d_n_accept: int, B: int,
+                          stream: int = 0):
+        c = self._coef(coef)
+        check(lib().fdg_chain_step_device(self._h, d_xp or None, xpc, d_facp or None, n_col, n_dim, None if c is None else c.ctypes.data,
+                                          gamma, seed, sample_offset, flags, d_x or None, xc, d_fac or None, d_root or None, d_a or None,
+                                          d_sum or None, d_n_accept or None, B, stream))
+
+    def mc_chain_step_device(self, d_xp: int, xpc: int, kF, beta, lam, d_facp: int, n_col: int, n_dim: int, coef, gamma: float, seed: int,
+                             sample_offset: int, flags: int, d_x: int, xc: int, d_fac: int, d_root: int, d_a: int, d_sum: int,
+                             d_n_accept: int, B: int, stream: int = 0):
+        c = self._coef(coef)
+        check(lib().fdg_mc_chain_step_device(self._h, d_xp or None, xpc, kF, beta, lam, d_facp or None, n_col, n_dim,
+                                             None if c is None else c.ctypes.data, gamma, seed, sample_offset, flags, d_x or None, xc,
+                                             d_fac or None, d_root or None, d_a or None, d_sum or None, d_n_accept or None, B, stream))
+
     def _coef(self, coef):
         if coef is None:
             return None
@@ -748,6 +774,94 @@ def vegas_sample_device(d_grid: int, n_dim: int, n_grid: int, col, seed: int, sa
             raise ValueError("col must name one column per variable")
     check(lib().fdg_vegas_sample_device(d_grid or None, n_dim, n_grid, None if c is None else c.ctypes.data, seed, sample_offset,
                                         d_x or None, xs, xc, d_jac or None, d_cell or None, B, stream))
+
+
+def chain_propose_device(d_grid: int, n_dim: int, n_grid: int, col, n_col: int, mask: int, seed: int, sample_offset: int, d_x: int, xc: int,
+                         d_fac: int, d_xp: int, xpc: int, d_facp: int, B: int, stream: int = 0):
+    """fdg_chain_propose_device: the proposal ``xp [n_col, B]`` / ``facp [n_dim, B]`` of every walker -- the variables of ``mask`` redrawn
+    through the map for counter ``(sample_offset + b, d)``, everything else copied from ``x`` / ``fac``."""
+    c = None
+    if col is not None:
+        c = np.ascontiguousarray(col, dtype=np.uint32)
+        if c.shape != (n_dim,):
+            raise ValueError("col must name one column per variable")
+    check(lib().fdg_chain_propose_device(d_grid or None, n_dim, n_grid, None if c is None else c.ctypes.data, n_col, mask, seed, sample_offset,
+                                         d_x or None, xc, d_fac or None, d_xp or None, xpc, d_facp or None, B, stream))
+
+
+def chain_reduce_device(d_sum: int, n_root: int, B: int, d_out: int, stream: int = 0):
+    """fdg_chain_reduce_device: ``out [3 R + 2] +=`` (S [R + 1], Q [R + 1], X [R]) of the walkers' sums ``[n_root + 1, B]``."""
+    check(lib().fdg_chain_reduce_device(d_sum or None, n_root, B, d_out or None, stream))
+
+
+def chain_reduce_reference(total) -> np.ndarray:
+    """fdg_chain_reduce_device restated: ``(S, Q, X)`` of ``total [R + 1, B]`` as one ``[3 R + 2]`` vector.  The products are formed in
+    fp64 as on the device; the sums over the walkers are exact (math.fsum), so the device's agree within its own rounding."""
+    import math
+    A = np.asarray(total, dtype=np.float64)
+    R = A.shape[0] - 1
+    out = [math.fsum(A[c]) for c in range(R + 1)] + [math.fsum(A[c] * A[c]) for c in range(R + 1)] + [math.fsum(A[k] * A[R]) for k in range(R)]
+    return np.array(out, dtype=np.float64)
+
+
+def chain_reference(grid, col, state, mask: int, u, u_acc, gamma: float, flags: int, eval_roots, coef=None, exists=None):
+    """One chain step restated in numpy (include/fdg.h, "Markov-chain sampling on the VEGAS map"): fdg_chain_propose_device, then
+    fdg_[mc_]chain_step_device, in the device's fp64 order, so that the state compares bit for bit.
+
+    ``grid [D, G + 1]`` the map; ``col [D]`` the column of each variable (None: ``d``); ``state`` a dict of ``x [n_col, B]``,
+    ``fac [D, B]``, ``root [R, B]``, ``a [B]``, ``sum [R + 1, B]``, ``n_accept [B]`` (int32); ``u [B, D]`` the uniforms of the counters
+    ``(sample_offset + b, d)`` (only the columns of ``mask`` are read); ``u_acc [B]`` those of ``(sample_offset + b, FDG_VEGAS_DIM_MAX)``
+    (not read with FDG_CHAIN_INIT); ``eval_roots(xp) -> [R, B]`` the roots of the proposals ``xp [n_col, B]``; ``exists`` a bool per
+    root (None: all).  Returns the new state (new arrays; columns of roots that do not exist are carried over) with ``xp``, ``facp``
+    (the proposal) and ``accept [B]`` beside it.  :func:`chain_reduce_reference` restates the reduction."""
+    grid = np.asarray(grid, dtype=np.float64)
+    D, G = grid.shape[0], grid.shape[1] - 1
+    x, fac, root, a = (np.array(state[k], dtype=np.float64) for k in ("x", "fac", "root", "a"))
+    total, n_acc = np.array(state["sum"], dtype=np.float64), np.array(state["n_accept"], dtype=np.int32)
+    B, R = x.shape[1], root.shape[0]
+    cols = list(range(D)) if col is None else [int(c) for c in col]
+    live = [k for k in range(R) if exists is None or exists[k]]
+    xp, facp = x.copy(), fac.copy()
+    for d in range(D):
+        if (mask >> d) & 1:
+            y = np.asarray(u, dtype=np.float64)[:, d] * np.float64(G)
+            c = np.minimum(y.astype(np.int64), G - 1)
+            lo = grid[d, c]
+            wd = grid[d, c + 1] - lo
+            xp[cols[d]] = lo + (y - c.astype(np.float64)) * wd
+            facp[d] = np.float64(G) * wd
+    with np.errstate(all="ignore"):
+        rp = np.asarray(eval_roots(xp), dtype=np.float64) if live else np.zeros((R, B))
+        jp = facp[0].copy()
+        for d in range(1, D):
+            jp = jp * facp[d]
+        s, bad = None, np.zeros(B, dtype=bool)
+        for k in live:
+            bad |= ~np.isfinite(rp[k])
+            term = rp[k] if coef is None else np.float64(coef[k]) * rp[k]
+            s = term if s is None else s + term
+        if s is None:
+            s = np.zeros(B)
+        tp = jp * s
+        bad |= ~np.isfinite(tp)
+        ap = np.where(bad, 0.0, np.abs(tp))
+        if flags & FDG_CHAIN_INIT:
+            acc = np.ones(B, dtype=bool)
+        else:
+            acc = np.asarray(u_acc, dtype=np.float64) * (a + gamma) < (ap + gamma)
+    x, fac, a = np.where(acc, xp, x), np.where(acc, facp, fac), np.where(acc, ap, a)
+    for k in live:
+        root[k] = np.where(acc, np.where(bad, 0.0, rp[k]), root[k])
+    n_acc = n_acc + acc.astype(np.int32)
+    if flags & FDG_CHAIN_MEASURE:
+        jac = fac[0].copy()
+        for d in range(1, D):
+            jac = jac * fac[d]
+        dd = 1.0 / (a + gamma)
+        for k in live:
+            total[k] = total[k] + (jac * root[k]) * dd
+        total[R] = total[R] + dd
+    return {"x": x, "fac": fac, "root": root, "a": a, "sum": total, "n_accept": n_acc, "xp": xp, "facp": facp, "accept": acc}
 
 
 def _strat_array(strat, n_dim: int) -> np.ndarray:

@@ -1,0 +1,328 @@
+// Markov-chain sampling on the VEGAS map (include/fdg.h: fdg_chain_propose_device, fdg_chain_step_device, fdg_mc_chain_step_device,
+// fdg_chain_reduce_device).  One walker per lane, every access with sample stride 1.  A step is: propose (redraw the
+// variables of a mask through the map, copy the rest), evaluate the proposals chunk by chunk into the handle's root scratch by the
+// route of fdg_eval_device / fdg_mc_eval_device, then fdg_chain_select per chunk: fold, accept rule, selection, measurement.  No
+// kernel here holds a per-lane array: the select kernel walks the root columns twice (fold, then select), the variables' factors
+// likewise, so n_root = 180 and n_dim = 64 cost loads, not registers.  Nothing here touches the kernels of fdg_binned.hip: the
+// sampler's arithmetic of one variable is restated below (chain_draw), the same operations in the same order, so the bits are its.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <mutex>
+#include <vector>
+
+#define FDG_RUNTIME_TU 1
+#include "fdg_internal.h"
+
+using namespace fdg;
+
+namespace {
+
+struct ChainCols { uint32_t c[FDG_VEGAS_DIM_MAX]; };      // the column of x each variable is written to (a kernel argument, by value)
+
+// Variable d of walker `sample` (a global index: the Philox counter) through the map: fdg_vegas_sample's statements for one variable.
+__device__ __forceinline__ double chain_draw(const double *__restrict__ grid, uint32_t d, uint32_t G, uint64_t sample, uint64_t seed, double &f) {
+  const double u = fdg_philox_u53(sample, d, seed);
+  const double y = u * (double)G;
+  const uint32_t c = min((uint32_t)(int)y, G - 1u);
+  const double *e = grid + (size_t)d * (G + 1u) + c;
+  const double lo = e[0], wd = e[1] - lo, fr = y - (double)c;
+  f = (double)G * wd;
+  return lo + fr * wd;
+}
+
+// xp, facp = the proposal of every walker: the variables of `mask` redrawn, everything else copied from x, fac.  A masked variable's
+// column is first copied and then overwritten by the same lane, in program order.
+__global__ void __launch_bounds__(256)
+fdg_chain_propose(const double *__restrict__ grid, uint32_t D, uint32_t G, ChainCols col, uint32_t n_col, uint64_t mask, uint64_t seed,
+                  uint64_t off, const double *__restrict__ x, long xc, const double *__restrict__ fac, double *__restrict__ xp, long xpc,
+                  double *__restrict__ facp, long n) {
+  const long b = blockIdx.x * 256L + threadIdx.x;
+  if (b >= n) return;
+  for (uint32_t c = 0; c < n_col; ++c) xp[(long)c * xpc + b] = x[(long)c * xc + b];
+  for (uint32_t d = 0; d < D; ++d) {
+    const size_t at = (size_t)d * (size_t)n + (size_t)b;
+    if ((mask >> d) & 1u) {
+      double f;
+      const double v = chain_draw(grid, d, G, off + (uint64_t)b, seed, f);
+      xp[(long)col.c[d] * xpc + b] = v;
+      facp[at] = f;
+    } else {
+      facp[at] = fac[at];
+    }
+  }
+}
+
+// One chunk of n walkers whose proposals' roots lie column-major in `roots` (leading dimension ld).  Every array pointer is already
+// moved to the chunk's first walker; nw = n_walker is the column stride of fac, root and sum; off = sample_offset + the chunk's start.
+// kidx[0 .. n_live) are the roots that exist, ascending, cf their factors (null: 1).
+__global__ void __launch_bounds__(256)
+fdg_chain_select(const double *__restrict__ roots, long ld, long n, const uint32_t *__restrict__ kidx, const double *__restrict__ cf,
+                 uint32_t n_live, const double *__restrict__ xp, long xpc, const double *__restrict__ facp, uint32_t n_col, uint32_t D,
+                 long nw, double gamma, uint64_t seed, uint64_t off, uint32_t flags, double *__restrict__ x, long xc,
+                 double *__restrict__ fac, double *__restrict__ root, double *__restrict__ a, double *__restrict__ sum, uint32_t R,
+                 int32_t *__restrict__ n_accept) {
+  const long b = blockIdx.x * 256L + threadIdx.x;
+  if (b >= n) return;
+  const bool init = (flags & FDG_CHAIN_INIT) != 0, meas = (flags & FDG_CHAIN_MEASURE) != 0;
+  // the fold: jac', s', t', a'
+  double jp = 0.0;
+  for (uint32_t d = 0; d < D; ++d) {
+    const double f = facp[(size_t)d * (size_t)nw + (size_t)b];
+    jp = d ? jp * f : f;
+  }
+  double s = 0.0;
+  bool bad = false;
+  for (uint32_t j = 0; j < n_live; ++j) {
+    const double r = roots[(size_t)kidx[j] * (size_t)ld + (size_t)b];
+    bad = bad || !std::isfinite(r);
+    const double term = cf ? cf[j] * r : r;
+    s = j ? s + term : term;
+  }
+  const double tp = jp * s;
+  bad = bad || !std::isfinite(tp);
+  const double ap = bad ? 0.0 : fabs(tp);
+  // the accept rule
+  const double a0 = init ? 0.0 : a[b];
+  bool acc = true;
+  if (!init) {
+    const double u = fdg_philox_u53(off + (uint64_t)b, FDG_VEGAS_DIM_MAX, seed);
+    acc = u * (a0 + gamma) < (ap + gamma);
+  }
+  // the selection
+  double jac = jp;
+  if (acc) {
+    for (uint32_t c = 0; c < n_col; ++c) x[(long)c * xc + b] = xp[(long)c * xpc + b];
+    for (uint32_t d = 0; d < D; ++d) {
+      const size_t at = (size_t)d * (size_t)nw + (size_t)b;
+      fac[at] = facp[at];
+    }
+    a[b] = ap;
+    if (n_accept) n_accept[b] = n_accept[b] + 1;
+  } else if (meas) {
+    for (uint32_t d = 0; d < D; ++d) {
+      const double f = fac[(size_t)d * (size_t)nw + (size_t)b];
+      jac = d ? jac * f : f;
+    }
+  }
+  if (!acc && !meas) return;
+  // the second walk over the roots: select, and measure on the state after the selection
+  const double dd = 1.0 / ((acc ? ap : a0) + gamma);
+  for (uint32_t j = 0; j < n_live; ++j) {
+    const uint32_t k = kidx[j];
+    const size_t at = (size_t)k * (size_t)nw + (size_t)b;
+    double r;
+    if (acc) {
+      const double rp = roots[(size_t)k * (size_t)ld + (size_t)b];
+      r = bad ? 0.0 : rp;
+      root[at] = r;
+    } else {
+      r = root[at];
+    }
+    if (meas) {
+      const double w = jac * r;
+      sum[at] = sum[at] + w * dd;
+    }
+  }
+  if (meas) {
+    const size_t at = (size_t)R * (size_t)nw + (size_t)b;
+    sum[at] = sum[at] + dd;
+  }
+}
+
+// out[c] += the sum over the walkers of column c's term (include/fdg.h: S, Q, X); one workgroup per output.
+__global__ void __launch_bounds__(256)
+fdg_chain_reduce(const double *__restrict__ sum, uint32_t R, long n, double *__restrict__ out) {
+  __shared__ double sh[256];
+  const uint32_t c = blockIdx.x;
+  const double *p, *q;                                     // the term of walker b is p[b] * q[b], or p[b] where q is null
+  if (c <= R) { p = sum + (size_t)c * (size_t)n; q = nullptr; }
+  else if (c <= 2u * R + 1u) { p = q = sum + (size_t)(c - R - 1u) * (size_t)n; }
+  else { p = sum + (size_t)(c - 2u * R - 2u) * (size_t)n; q = sum + (size_t)R * (size_t)n; }
+  double t = 0.0;
+  for (long b = threadIdx.x; b < n; b += 256) {
+    const double v = p[b];
+    t = t + (q ? v * q[b] : v);
+  }
+  sh[threadIdx.x] = t;
+  __syncthreads();
+  for (uint32_t h = 128; h; h >>= 1) {
+    if (threadIdx.x < h) sh[threadIdx.x] = sh[threadIdx.x] + sh[threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[c] = out[c] + sh[0];
+}
+
+constexpr size_t page_up(size_t bytes) { return (bytes + 4095) & ~(size_t)4095; }
+
+struct ChainCall {
+  const double *d_xp;
+  int64_t xpc;
+  const double *d_facp;
+  uint32_t n_col, n_dim;
+  const double *coef;
+  double gamma;
+  uint64_t seed, offset;
+  unsigned flags;
+  double *d_x;
+  int64_t xc;
+  double *d_fac, *d_root, *d_a, *d_sum;
+  int32_t *d_n_accept;
+  int64_t B;
+  void *stream;
+};
+
+// The checks of both step calls that need no lock.
+int check_chain(const fdg_graph *g, const ChainCall &c) {
+  if (!g) { set_error("null handle"); return FDG_E_INVALID; }
+  if (c.B < 0) { set_error("n_walker < 0"); return FDG_E_INVALID; }
+  if (c.flags & ~(FDG_CHAIN_INIT | FDG_CHAIN_MEASURE)) { set_error("unknown flags"); return FDG_E_INVALID; }
+  const bool meas = (c.flags & FDG_CHAIN_MEASURE) != 0;
+  if (!c.d_xp || !c.d_facp || !c.d_x || !c.d_fac || !c.d_root || !c.d_a || (meas && !c.d_sum)) { set_error("null device buffer"); return FDG_E_INVALID; }
+  const void *arr[7] = {c.d_x, c.d_fac, c.d_root, c.d_a, c.d_sum, c.d_xp, c.d_facp};
+  for (int i = 0; i < 7; ++i)
+    for (int j = 0; j < i; ++j)
+      if (arr[i] && arr[i] == arr[j]) { set_error("two of the state, proposal and sum arrays are the same buffer"); return FDG_E_INVALID; }
+  if ((const void *)c.d_n_accept && std::find(arr, arr + 7, (const void *)c.d_n_accept) != arr + 7) {
+    set_error("d_n_accept is the same buffer as another array"); return FDG_E_INVALID;
+  }
+  if (!(std::isfinite(c.gamma) && c.gamma > 0.0)) { set_error("gamma must be finite and > 0"); return FDG_E_INVALID; }
+  if (c.n_dim == 0) { set_error("n_dim == 0"); return FDG_E_INVALID; }
+  if (c.n_dim > FDG_VEGAS_DIM_MAX) { set_error("n_dim > FDG_VEGAS_DIM_MAX"); return FDG_E_UNSUPPORTED; }
+  if (c.xc < c.B || c.xpc < c.B) { set_error("a column stride < n_walker"); return FDG_E_INVALID; }
+  if (c.coef)
+    for (uint32_t k = 0; k < g->prog.R; ++k)
+      if (!std::isfinite(c.coef[k])) { set_error("a coefficient is not finite"); return FDG_E_INVALID; }
+  return FDG_OK;
+}
+
+// The body of both step calls (caller holds g->mu, stream bound): eval(c0, n, roots, ld) writes the roots of the proposals of walkers
+// c0 .. c0 + n - 1 column-major into roots.  The chunk is the accumulate calls' (FDG_ROOT_SCRATCH_MB); no result depends on it.
+template <class Eval>
+int run_chain(fdg_graph *g, const ChainCall &c, Eval eval) {
+  const uint32_t R = g->prog.R;
+  const hipStream_t st = (hipStream_t)c.stream;
+  long Bc = std::max<long>(64, (long)((g->cfg.root_scratch_mb << 20) / (8ull * std::max<uint32_t>(R, 1u))) & ~63l);
+  Bc = std::min<long>(Bc, (long)((c.B + 63) & ~(int64_t)63));
+  const size_t root_bytes = page_up((size_t)Bc * std::max<uint32_t>(R, 1u) * sizeof(double));
+  int rc = ensure_root_scratch(g, root_bytes + page_up((size_t)std::max<uint32_t>(R, 1u) * 12u));
+  if (rc) return rc;
+  double *roots = (double *)g->d_ws2;
+  // the roots that exist, ascending, and their factors: one small upload per call (pageable memory: staged before the call returns)
+  double *d_coef = (double *)((char *)g->d_ws2 + root_bytes);
+  uint32_t *d_kidx = (uint32_t *)(d_coef + std::max<uint32_t>(R, 1u));
+  std::vector<double> hc;
+  std::vector<uint32_t> hk;
+  for (uint32_t k = 0; k < R; ++k)
+    if (g->prog.root_slot[k] != FDG_NO_ROOT) { hk.push_back(k); hc.push_back(c.coef ? c.coef[k] : 1.0); }
+  const uint32_t n_live = (uint32_t)hk.size();
+  if (n_live) {
+    HIP_TRY(hipMemcpyAsync(d_coef, hc.data(), n_live * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_kidx, hk.data(), n_live * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  }
+  for (long c0 = 0; c0 < (long)c.B; c0 += Bc) {
+    const long n = std::min<long>(Bc, (long)c.B - c0);
+    if (n_live) {
+      rc = eval(c0, n, roots, Bc);
+      if (rc) return rc;
+    }
+    hipLaunchKernelGGL(fdg_chain_select, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, roots, Bc, n, d_kidx, c.coef ? d_coef : nullptr,
+                       n_live, c.d_xp + c0, (long)c.xpc, c.d_facp + c0, c.n_col, c.n_dim, (long)c.B, c.gamma, c.seed,
+                       c.offset + (uint64_t)c0, (uint32_t)c.flags, c.d_x + c0, (long)c.xc, c.d_fac + c0, c.d_root + c0, c.d_a + c0,
+                       c.d_sum ? c.d_sum + c0 : nullptr, R, c.d_n_accept ? c.d_n_accept + c0 : nullptr);
+    HIP_TRY(hipGetLastError());
+  }
+  return FDG_OK;
+}
+
+template <class Check, class Eval>
+int chain_step(fdg_graph *g, const ChainCall &c, Check locked_check, Eval eval) {
+  std::lock_guard<std::mutex> lk(g->mu);
+  fdg::KnobScope knob_scope(&g->knobs);
+  int rc = locked_check();
+  if (rc) return rc;
+  if (c.B == 0) return FDG_OK;
+  rc = ensure_device(g);
+  if (rc) return rc;
+  rc = fdg_bind_stream_ws(g, c.stream);
+  if (rc) return rc;
+  return run_chain(g, c, eval);
+}
+
+}  // namespace
+
+extern "C" {
+
+int fdg_chain_propose_device(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, uint32_t n_col, uint64_t mask,
+                             uint64_t seed, uint64_t sample_offset, const double *d_x, int64_t x_col_stride, const double *d_fac,
+                             double *d_xp, int64_t xp_col_stride, double *d_facp, int64_t B, void *stream) {
+  if (B < 0) { set_error("n_walker < 0"); return FDG_E_INVALID; }
+  if (!d_grid || !d_x || !d_fac || !d_xp || !d_facp) { set_error("null device buffer"); return FDG_E_INVALID; }
+  if (n_dim == 0 || n_grid == 0) { set_error("n_dim == 0 or n_grid == 0"); return FDG_E_INVALID; }
+  if (n_dim > FDG_VEGAS_DIM_MAX) { set_error("n_dim > FDG_VEGAS_DIM_MAX"); return FDG_E_UNSUPPORTED; }
+  if (n_grid > FDG_VEGAS_GRID_MAX) { set_error("n_grid > FDG_VEGAS_GRID_MAX"); return FDG_E_UNSUPPORTED; }
+  if (d_x == d_xp || d_fac == d_facp) { set_error("the state and the proposal are the same buffer"); return FDG_E_INVALID; }
+  if (n_dim < 64 && (mask >> n_dim)) { set_error("mask names a variable >= n_dim"); return FDG_E_INVALID; }
+  if (x_col_stride < B || xp_col_stride < B) { set_error("a column stride < n_walker"); return FDG_E_INVALID; }
+  ChainCols cols;
+  for (uint32_t d = 0; d < FDG_VEGAS_DIM_MAX; ++d) cols.c[d] = d < n_dim ? (col ? col[d] : d) : 0u;
+  for (uint32_t d = 0; d < n_dim; ++d)
+    if (cols.c[d] >= n_col) { set_error("col names a column >= n_col"); return FDG_E_INVALID; }
+  if (B == 0) return FDG_OK;
+  hipLaunchKernelGGL(fdg_chain_propose, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_grid, n_dim, n_grid, cols, n_col,
+                     mask, seed, sample_offset, d_x, (long)x_col_stride, d_fac, d_xp, (long)xp_col_stride, d_facp, (long)B);
+  HIP_TRY(hipGetLastError());
+  return FDG_OK;
+}
+
+int fdg_chain_step_device(fdg_graph *g, const double *d_xp, int64_t xp_col_stride, const double *d_facp, uint32_t n_col, uint32_t n_dim,
+                          const double *coef, double gamma, uint64_t seed, uint64_t sample_offset, unsigned flags, double *d_x,
+                          int64_t x_col_stride, double *d_fac, double *d_root, double *d_a, double *d_sum, int32_t *d_n_accept, int64_t B,
+                          void *stream) {
+  const ChainCall c{d_xp, xp_col_stride, d_facp, n_col, n_dim, coef, gamma, seed, sample_offset, flags, d_x, x_col_stride, d_fac,
+                    d_root, d_a, d_sum, d_n_accept, B, stream};
+  const int rc = check_chain(g, c);
+  if (rc) return rc;
+  if (n_col != g->prog.L) { set_error("n_col is not the graph's number of leaves"); return FDG_E_INVALID; }
+  const hipStream_t st = (hipStream_t)stream;
+  return chain_step(
+      g, c, [] { return FDG_OK; },
+      [&](long c0, long n, double *roots, long ld) {
+        return fdg_run_locked(g, 0, d_xp + c0, 1, xp_col_stride, roots, 1, ld, nullptr, nullptr, n, st, 0, 0);
+      });
+}
+
+int fdg_mc_chain_step_device(fdg_graph *g, const double *d_xp, int64_t xp_col_stride, double kF, double beta, double lambda,
+                             const double *d_facp, uint32_t n_col, uint32_t n_dim, const double *coef, double gamma, uint64_t seed,
+                             uint64_t sample_offset, unsigned flags, double *d_x, int64_t x_col_stride, double *d_fac, double *d_root,
+                             double *d_a, double *d_sum, int32_t *d_n_accept, int64_t B, void *stream) {
+  const ChainCall c{d_xp, xp_col_stride, d_facp, n_col, n_dim, coef, gamma, seed, sample_offset, flags, d_x, x_col_stride, d_fac,
+                    d_root, d_a, d_sum, d_n_accept, B, stream};
+  const int rc = check_chain(g, c);
+  if (rc) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  return chain_step(
+      g, c,
+      [&] {
+        if (g->mc_route == 0) { set_error("fdg_graph_specialize_fused has not been called on this handle"); return FDG_E_INVALID; }
+        if (n_col != g->lt_hdr[2] * g->lt_hdr[3] + g->lt_hdr[4]) { set_error("n_col is not the tables' n_loop * dim + n_tau"); return FDG_E_INVALID; }
+        return FDG_OK;
+      },
+      [&](long c0, long n, double *roots, long ld) {
+        const double *K = d_xp + c0, *T = d_xp + (int64_t)(g->lt_hdr[2] * g->lt_hdr[3]) * xp_col_stride + c0;
+        return fdg_mc_run_locked(g, 0, K, 1, xp_col_stride, T, 1, xp_col_stride, kF, beta, lambda, roots, 1, ld, nullptr, nullptr, n, st);
+      });
+}
+
+int fdg_chain_reduce_device(const double *d_sum, uint32_t n_root, int64_t B, double *d_out, void *stream) {
+  if (B < 0) { set_error("n_walker < 0"); return FDG_E_INVALID; }
+  if (!d_sum || !d_out) { set_error("null device buffer"); return FDG_E_INVALID; }
+  if (d_sum == d_out) { set_error("d_sum and d_out are the same buffer"); return FDG_E_INVALID; }
+  if (B == 0) return FDG_OK;
+  hipLaunchKernelGGL(fdg_chain_reduce, dim3(3u * n_root + 2u), dim3(256), 0, (hipStream_t)stream, d_sum, n_root, (long)B, d_out);
+  HIP_TRY(hipGetLastError());
+  return FDG_OK;
+}
+
+}  // extern "C"

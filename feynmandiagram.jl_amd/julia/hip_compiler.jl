@@ -816,6 +816,59 @@ end
 
 export compile_hip, GraphFunc, eval_device!, accumulate_device!, eval_device_tiled!, accumulate_device_tiled!, accumulate_device_binned!, mc_accumulate_device_binned!, accumulate_device_moments!, mc_accumulate_device_moments!, vegas_sample_device!, accumulate_device_vegas!, mc_accumulate_device_vegas!, vegas_refine!, vegas_sample_device_discrete!, accumulate_device_vegas_binned!, mc_accumulate_device_vegas_binned!, vegas_refine_discrete!, vegas_sample_device_polar!, fdg_sincos, fdg_matsubara_phase, accumulate_device_matsubara!, mc_accumulate_device_matsubara!, weight_groups_from_dof, vegas_sample_device_grouped!, accumulate_device_grouped!, mc_accumulate_device_grouped!, accumulate_device_observables!, mc_accumulate_device_observables!, accumulate_device_freq_observables!, mc_accumulate_device_freq_observables!, batch_alloc, batch_free, tile_major!, from_tile_major!, vegas_sample_device_strat!, accumulate_device_strat!, mc_accumulate_device_strat!, strat_allocate!, strat_allocate_cols!, vegas_sample_device_strat_grouped!, accumulate_device_strat_grouped!, mc_accumulate_device_strat_grouped!
 
+# ---- Markov-chain sampling on the VEGAS map (include/fdg.h; no counterpart in the reference: the caller's side of test/hubbard.jl:85) ---- #
+# The state of B walkers is caller-owned device memory, every array a column-major Julia matrix with the walker as its first index:
+# d_x (B x n_col), d_fac (B x n_dim), d_root (B x R), d_a (B), d_sum (B x (R + 1)), d_n_accept (B Int32, optional).
+# chain_propose_device! writes the proposal d_xp, d_facp: the variables of `mask` (bit d - 1 = variable d) redrawn through the map for the
+# counters (sample_offset + b, d), everything else copied from the state.  col is 1-based (default d).
+const FDG_CHAIN_INIT = Cuint(1)
+const FDG_CHAIN_MEASURE = Cuint(2)
+function chain_propose_device!(d_xp::Ptr{Float64}, d_facp::Ptr{Float64}, d_x::Ptr{Float64}, d_fac::Ptr{Float64}, d_grid::Ptr{Float64},
+    n_dim::Integer, n_grid::Integer, n_col::Integer, mask::Integer, B::Integer; col::Union{Nothing,AbstractVector{<:Integer}}=nothing,
+    seed::Integer=0, sample_offset::Integer=0, x_col_stride::Integer=B, xp_col_stride::Integer=B, stream::Ptr{Cvoid}=C_NULL)
+    c = col === nothing ? nothing : UInt32.(col .- 1)
+    _fdg_check(ccall((:fdg_chain_propose_device, _libfdg), Cint,
+        (Ptr{Float64}, UInt32, UInt32, Ptr{UInt32}, UInt32, UInt64, UInt64, UInt64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Int64,
+         Ptr{Float64}, Int64, Ptr{Cvoid}),
+        d_grid, n_dim, n_grid, c === nothing ? C_NULL : c, n_col, mask, seed, sample_offset, d_x, x_col_stride, d_fac, d_xp, xp_col_stride,
+        d_facp, B, stream))
+    return nothing
+end
+# One step after the proposal (fdg_chain_step_device, the leaf form: the columns of d_xp are the graph's leaves): the roots of the
+# proposals, the fold, the accept rule u * (a + gamma) < (a' + gamma), the selection into the state and, with FDG_CHAIN_MEASURE, the
+# walker's sums d_sum[b, k] += (jac * r_k) / (a + gamma), d_sum[b, R + 1] += 1 / (a + gamma).  FDG_CHAIN_INIT accepts unconditionally.
+function chain_step_device!(f::GraphFunc, d_xp::Ptr{Float64}, d_facp::Ptr{Float64}, d_x::Ptr{Float64}, d_fac::Ptr{Float64},
+    d_root::Ptr{Float64}, d_a::Ptr{Float64}, d_sum::Ptr{Float64}, n_col::Integer, n_dim::Integer, gamma::Float64, B::Integer;
+    flags::Integer=0, coef::Union{Nothing,Vector{Float64}}=nothing, seed::Integer=0, sample_offset::Integer=0,
+    d_n_accept::Ptr{Int32}=Ptr{Int32}(C_NULL), x_col_stride::Integer=B, xp_col_stride::Integer=B, stream::Ptr{Cvoid}=C_NULL)
+    _fdg_check(ccall((:fdg_chain_step_device, _libfdg), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, UInt32, UInt32, Ptr{Float64}, Float64, UInt64, UInt64, Cuint, Ptr{Float64}, Int64,
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Int64, Ptr{Cvoid}),
+        f.handle, d_xp, xp_col_stride, d_facp, n_col, n_dim, coef === nothing ? C_NULL : coef, gamma, seed, sample_offset, flags, d_x,
+        x_col_stride, d_fac, d_root, d_a, d_sum, d_n_accept, B, stream))
+    return nothing
+end
+# The Monte-Carlo form (fdg_mc_chain_step_device): d_xp is one B x (n_loop * dim + n_tau) matrix, momentum components first, then the times.
+function mc_chain_step_device!(f::GraphFunc, d_xp::Ptr{Float64}, d_facp::Ptr{Float64}, d_x::Ptr{Float64}, d_fac::Ptr{Float64},
+    d_root::Ptr{Float64}, d_a::Ptr{Float64}, d_sum::Ptr{Float64}, n_col::Integer, n_dim::Integer, gamma::Float64, B::Integer;
+    kF::Float64, beta::Float64, lambda::Float64, flags::Integer=0, coef::Union{Nothing,Vector{Float64}}=nothing, seed::Integer=0,
+    sample_offset::Integer=0, d_n_accept::Ptr{Int32}=Ptr{Int32}(C_NULL), x_col_stride::Integer=B, xp_col_stride::Integer=B,
+    stream::Ptr{Cvoid}=C_NULL)
+    _fdg_check(ccall((:fdg_mc_chain_step_device, _libfdg), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Int64, Float64, Float64, Float64, Ptr{Float64}, UInt32, UInt32, Ptr{Float64}, Float64, UInt64, UInt64,
+         Cuint, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Int64, Ptr{Cvoid}),
+        f.handle, d_xp, xp_col_stride, kF, beta, lambda, d_facp, n_col, n_dim, coef === nothing ? C_NULL : coef, gamma, seed,
+        sample_offset, flags, d_x, x_col_stride, d_fac, d_root, d_a, d_sum, d_n_accept, B, stream))
+    return nothing
+end
+# d_out (3 R + 2, added to) = the sums over the walkers S_c, Q_c = sum A_c^2 (R + 1 each) and X_k = sum A_k A_{R+1} (R) of d_sum.
+function chain_reduce_device!(d_out::Ptr{Float64}, d_sum::Ptr{Float64}, n_root::Integer, B::Integer; stream::Ptr{Cvoid}=C_NULL)
+    _fdg_check(ccall((:fdg_chain_reduce_device, _libfdg), Cint, (Ptr{Float64}, UInt32, Int64, Ptr{Float64}, Ptr{Cvoid}),
+        d_sum, n_root, B, d_out, stream))
+    return nothing
+end
+export chain_propose_device!, chain_step_device!, mc_chain_step_device!, chain_reduce_device!, FDG_CHAIN_INIT, FDG_CHAIN_MEASURE
+
 # ---- multi-GPU: one Julia process per GPU, ONE reduction of the accumulated observable ------------ #
 # (include/fdg.h, "multi-GPU").  Rank 0 calls `comm_unique_id()` and ships the 128 bytes to the other
 # ranks (MPI.jl `MPI.bcast`, a shared file, ...); every rank then builds its communicator with its own

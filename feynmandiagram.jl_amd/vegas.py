@@ -35,6 +35,12 @@ into hypercubes, each receives at least two samples and the rest go where the in
 separable map cannot do for a ridge along a diagonal (a propagator of ``k1 + k2`` or ``T[i] - T[j]``).  Together with spherical
 momentum variables and weight groups: ``vegas_integrate_stratified`` (fdg_vegas_sample_device_strat_grouped,
 fdg_[mc_]accumulate_device_strat_grouped, fdg_strat_allocate_cols).
+
+Markov-chain sampling (``chain_integrate``, ``chain_estimate``, ``ChainResult``; fdg_chain_propose_device, fdg_[mc_]chain_step_device,
+fdg_chain_reduce_device): a Metropolis chain whose proposals are fresh draws through the map for a subset of the variables, one
+walker per lane -- what ``integrate(...; solver=:mcmc)`` of the reference's test/hubbard.jl:85 asks MCIntegration for -- for weights
+that no separable map follows.  The stationary density ``|s| + gamma q`` carries the map's own density ``q``, whose known integral
+normalises the result; the error bar comes from the spread across the independent walkers.
 """
 from __future__ import annotations
 
@@ -815,3 +821,172 @@ def vegas_integrate_binned(func_or_handle, tables, lo, hi, col, dmap: DiscreteMa
     return _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter, n_sample, n_grid, alpha, floor, seed, n_discard, fixed,
                       coef, device, vmap, specialize_fused, n_total, shard_start, reduce, polar, matsubara, groups, observables,
                       freq_observables)
+
+
+# ---- Markov-chain sampling on the VEGAS map (include/fdg.h: fdg_chain_propose_device, fdg_[mc_]chain_step_device, fdg_chain_reduce_device) ---- #
+@dataclass
+class ChainResult:
+    mean: np.ndarray                 # [R] S_k / S_R: the integral of every root
+    stderr: np.ndarray               # [R] from the spread across the walkers (:func:`chain_estimate`)
+    acceptance: float                # mean over the walkers of n_accept / n_step
+    gamma: float                     # the weight of the map's own density in the stationary density
+    map: Optional[VegasMap] = None   # the map the chain drew its proposals through
+    S: Optional[np.ndarray] = None   # [R + 1] sum over the walkers of their sums A_c(b); A_R is the normalisation
+    Q: Optional[np.ndarray] = None   # [R + 1] sum over the walkers of A_c(b)**2
+    X: Optional[np.ndarray] = None   # [R] sum over the walkers of A_k(b) A_R(b)
+
+
+def chain_estimate(S, Q, X, n_walker: int):
+    """``(mean, stderr)`` per root from the reduced sums of a chain run (fdg_chain_reduce_device): with ``B = n_walker`` independent
+    walkers whose sums are ``A_c(b)``, ``m_k = S_k / S_R``, ``V_cd = B / (B - 1) (sum_b A_c A_d - S_c S_d / B)`` for the pairs the sums
+    provide, and ``var(m_k) = (V_kk - 2 m_k V_kR + m_k**2 V_RR) / S_R**2``: the delta method for a ratio over independent walkers.
+    ``B = 1`` has no spread to measure: every stderr is nan.  ``S_R = 0`` (nothing was measured) raises ValueError; a variance that
+    rounding leaves below zero is reported as 0."""
+    S, Q, X = (np.asarray(v, dtype=np.float64) for v in (S, Q, X))
+    R, B = X.shape[0], int(n_walker)
+    if S.shape != (R + 1,) or Q.shape != (R + 1,) or B < 1:
+        raise ValueError("need S, Q of n_root + 1 sums, X of n_root and n_walker >= 1")
+    if not S[R] > 0.0:
+        raise ValueError("S_R, the sum of the normalisation, is not positive: no step was measured")
+    mean = S[:R] / S[R]
+    if B == 1:
+        return mean, np.full(R, np.nan)
+    f = B / (B - 1.0)
+    Vkk = f * (Q[:R] - S[:R] * S[:R] / B)
+    VkR = f * (X - S[:R] * S[R] / B)
+    VRR = f * (Q[R] - S[R] * S[R] / B)
+    var = (Vkk - 2.0 * mean * VkR + mean * mean * VRR) / (S[R] * S[R])
+    return mean, np.sqrt(np.maximum(var, 0.0))
+
+
+def chain_moves(n_dim: int) -> List[int]:
+    """The default moves of :func:`chain_integrate`: the mask of all variables, then one mask per variable."""
+    D = int(n_dim)
+    return [(1 << D) - 1] + [1 << d for d in range(D)]
+
+
+_CHAIN_EXCLUDED = ("polar", "groups", "dmap", "matsubara", "observables", "freq_observables", "strat")
+_CHAIN_TRAIN_KEY = 0x632BE59BD9B4E019       # added to ``seed`` for the map's training: the chain's counters are used once
+
+
+def chain_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: float = 1.0, lam: float = 0.0, *, n_walker: int,
+                    n_step: int, n_therm: int, moves: Optional[Sequence[int]] = None, gamma_rel: float = 1.0, gamma: Optional[float] = None,
+                    n_warm: int = 5, n_warm_sample: Optional[int] = None, n_grid: int = 64, alpha: float = 0.5, seed: int = 0, fixed=None,
+                    coef=None, vmap: Optional[VegasMap] = None, specialize_fused: bool = True, n_total: Optional[int] = None,
+                    shard_start: int = 0, reduce: Optional[Callable] = None, device="cuda", **excluded) -> ChainResult:
+    """Integrates the roots of a graph over the box ``[lo, hi]`` with a Metropolis chain whose proposals are fresh draws through the
+    VEGAS map for a subset of the variables (MCIntegration's ``:vegasmc``; no counterpart in the reference: the caller's side of
+    test/hubbard.jl:85).  ``n_walker`` independent walkers, one per lane; the stationary density is ``|s| + gamma q`` with ``s`` the
+    ``coef`` combination of the roots and ``q`` the map's own density, whose known integral 1 normalises the result (include/fdg.h).
+
+    The arguments up to ``lam``, ``fixed``, ``coef``, ``vmap``, ``specialize_fused`` and ``device`` are :func:`vegas_integrate`'s;
+    ``tables`` None is the leaf form (the columns of ``x`` are the graph's leaves).  Procedure:
+
+    1. the map is trained by ``n_warm`` plain ``vegas_integrate`` iterations of ``n_warm_sample`` (default ``n_walker``) samples, on
+       a Philox key of its own; skipped with ``n_warm = 0`` (then ``vmap``, or the uniform map, is used as it is).  The leaf form
+       trains through the stratified driver with one stratum per variable, which is the plain step;
+    2. FDG_CHAIN_INIT places the walkers with all variables drawn (``sample_offset = shard_start``);
+    3. ``gamma = gamma_rel * mean(a)`` unless ``gamma`` is given: the mean over the walkers (all of them: ``reduce`` is applied to
+       the sum) of ``a = |jac s|`` is the map's estimate of the integral of ``|s|``;
+    4. ``n_step`` steps; step ``t`` redraws the variables of ``moves[t % len(moves)]`` (bit ``d`` = variable ``d``; default
+       :func:`chain_moves`) with ``sample_offset = (t + 1) * n_total + shard_start`` and ``seed``, and measures from step
+       ``n_therm`` on;
+    5. fdg_chain_reduce_device, ``reduce`` on the ``3 R + 2`` sums, :func:`chain_estimate` with ``n_total`` walkers.
+
+    Sharding is :func:`vegas_integrate`'s: a rank passes its range as ``shard_start`` / ``n_walker`` and the whole as ``n_total``;
+    a walker's chain does not depend on the split.
+
+    Out of scope here, refused with ValueError: ``polar``, ``groups``, a discrete variable (``dmap``), ``matsubara``,
+    ``observables``, ``freq_observables`` and ``strat`` together with the chain.  Not built either: training the map from the
+    chain's own samples, local (shift) proposals, reweighting between orders.  The target these lead to is ``Sigma(i omega_0)`` of
+    the Hubbard atom in the reference's test/hubbard.jl, which the chain, ``matsubara`` and ``groups`` together would reach."""
+    import torch
+    for name, value in excluded.items():
+        if name not in _CHAIN_EXCLUDED:
+            raise TypeError(f"chain_integrate() got an unexpected keyword argument '{name}'")
+        if value is not None and not (name == "polar" and not value):
+            raise ValueError(f"{name} cannot be combined with the chain yet")
+    handle = getattr(func_or_handle, "handle", func_or_handle)
+    device = torch.device(device)
+    R = handle.table.n_root
+    if tables is None:
+        n_col = handle.table.n_leaf
+    else:
+        n_col = int(tables.n_loop) * int(tables.dim) + int(tables.n_tau)
+    col = [int(c) for c in col]
+    if len(set(col)) != len(col) or not all(0 <= c < n_col for c in col):
+        raise ValueError(f"col must name distinct columns in [0, {n_col})")
+    B, n_step, n_therm, n_warm = int(n_walker), int(n_step), int(n_therm), int(n_warm)
+    N = B if n_total is None else int(n_total)
+    if B < 1 or n_step < 1 or not 0 <= n_therm < n_step or n_warm < 0 or not 0 <= int(shard_start) <= N - B:
+        raise ValueError("need n_walker >= 1, 0 <= n_therm < n_step, n_warm >= 0 and the shard inside n_total")
+    if gamma is not None and not (math.isfinite(gamma) and gamma > 0.0):
+        raise ValueError("gamma must be finite and > 0")
+    if gamma is None and not (math.isfinite(gamma_rel) and gamma_rel > 0.0):
+        raise ValueError("gamma_rel must be finite and > 0")
+    if vmap is None:
+        vmap = VegasMap(uniform_grid(lo, hi, n_grid), device)
+    if vmap.n_dim != len(col):
+        raise ValueError("one column per variable of the map")
+    D, G = vmap.n_dim, vmap.n_grid
+    moves = chain_moves(D) if moves is None else [int(m) for m in moves]
+    if not moves or not all(0 <= m < (1 << D) for m in moves):
+        raise ValueError("moves holds masks over the variables of the map")
+    fx = np.zeros(n_col) if fixed is None else np.asarray(fixed, dtype=np.float64)
+    if fx.shape != (n_col,):
+        raise ValueError(f"fixed must hold {n_col} column values")
+    if n_warm:
+        kw = dict(n_iter=n_warm, n_grid=G, alpha=alpha, seed=(int(seed) + _CHAIN_TRAIN_KEY) & 0xFFFFFFFFFFFFFFFF, fixed=fixed, coef=coef,
+                  device=device, vmap=vmap, specialize_fused=specialize_fused, reduce=reduce)
+        if n_warm_sample is None:
+            kw.update(n_sample=B, n_total=n_total, shard_start=shard_start)
+        else:
+            kw.update(n_sample=int(n_warm_sample))
+        if tables is None:
+            kw["strat"] = Stratification((1,) * D)
+        vegas_integrate(func_or_handle, tables, lo, hi, col, kF, beta, lam, **kw)
+    elif specialize_fused and tables is not None:
+        handle.specialize_fused(tables)
+    all_mask = (1 << D) - 1
+    with torch.cuda.device(device):
+        st = torch.cuda.current_stream(device).cuda_stream
+        f64 = dict(dtype=torch.float64, device=device)
+        x = torch.from_numpy(fx).to(device)[:, None].repeat(1, B).contiguous()            # [n_col, B]: sample stride 1
+        xp = torch.empty_like(x)
+        fac, facp = torch.ones((D, B), **f64), torch.empty((D, B), **f64)
+        root, a = torch.zeros((R, B), **f64), torch.zeros(B, **f64)
+        total = torch.zeros((R + 1, B), **f64)
+        n_acc = torch.zeros(B, dtype=torch.int32, device=device)
+
+        def step(mask, off, g, flags):
+            capi.chain_propose_device(vmap.d_grid.data_ptr(), D, G, col, n_col, mask, seed, off, x.data_ptr(), B, fac.data_ptr(),
+                                      xp.data_ptr(), B, facp.data_ptr(), B, st)
+            tail = (facp.data_ptr(), n_col, D, coef, g, seed, off, flags, x.data_ptr(), B, fac.data_ptr(), root.data_ptr(), a.data_ptr(),
+                    total.data_ptr(), n_acc.data_ptr(), B, st)
+            if tables is None:
+                handle.chain_step_device(xp.data_ptr(), B, *tail)
+            else:
+                handle.mc_chain_step_device(xp.data_ptr(), B, kF, beta, lam, *tail)
+
+        step(all_mask, int(shard_start), 1.0, capi.FDG_CHAIN_INIT)                       # (gamma enters no result of the placement)
+        if gamma is None:
+            sa = a.sum().reshape(1)
+            if reduce is not None:
+                reduce(sa)
+            gamma = float(gamma_rel) * float(sa.item()) / N
+            if not (math.isfinite(gamma) and gamma > 0.0):
+                raise ValueError("the map's estimate of the integral of |s| is not positive: pass gamma")
+        n_acc.zero_()
+        for t in range(n_step):
+            step(moves[t % len(moves)], (t + 1) * N + int(shard_start), float(gamma),
+                 capi.FDG_CHAIN_MEASURE if t >= n_therm else 0)
+        out = torch.zeros(3 * R + 2, **f64)
+        capi.chain_reduce_device(total.data_ptr(), R, B, out.data_ptr(), st)
+        acc_sum = n_acc.sum(dtype=torch.float64).reshape(1)
+        if reduce is not None:
+            reduce(out)
+            reduce(acc_sum)
+        h = out.cpu().numpy()
+    S, Q, X = h[:R + 1].copy(), h[R + 1:2 * R + 2].copy(), h[2 * R + 2:].copy()
+    mean, err = chain_estimate(S, Q, X, N)                # (a root that does not exist has sums of 0: mean 0, stderr 0)
+    return ChainResult(mean, err, float(acc_sum.item()) / (N * n_step), float(gamma), vmap, S, Q, X)

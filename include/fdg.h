@@ -1105,6 +1105,88 @@ int fdg_mc_accumulate_device_strat_grouped(fdg_graph *g, const double *d_K, int6
 int fdg_strat_allocate_cols(const double *cube_sum, const double *cube_sum2, uint32_t ld, const uint32_t *cols, uint32_t n_col,
                             const int64_t *start_old, uint32_t H, int64_t n_total, double beta, int64_t *start_new);
 
+/* ---- Markov-chain sampling on the VEGAS map ----------------------------------------------------------------------------------------------
+ * The reference's callers of this path sample with a Markov chain: test/hubbard.jl:85 calls integrate(...; solver=:mcmc), and the
+ * `measure` of test/ver4.jl:77-92,236-237 and example/strong_coupling_expansion adds weight / abs(weight) / reweight, the estimator of a
+ * chain whose stationary density is |integrand|.  A diagram's weight is not separable (propagators tie loop momenta and times together),
+ * so a separable map cannot follow it; a chain can.  This is the scheme of MCIntegration's :vegasmc: a Metropolis chain whose proposals
+ * are fresh draws through the VEGAS map for a subset of the variables.  MCIntegration is not part of the reference checkout: no
+ * counterpart in the reference; the caller's side of test/hubbard.jl:85.
+ *
+ * One walker per lane, n_walker independent chains, every step one batched evaluation of the proposals.  The walkers are independent,
+ * so the error bar comes from the spread across walkers (fdg_chain_reduce_device); no autocorrelation analysis is needed.
+ *
+ * The walker quantities, every operation one rounded fp64 operation (the library builds with -ffp-contract=off):
+ *     x      the point, all n_col columns
+ *     fac_d  = G * wd_d, the per-variable jacobian factor of its current value (fdg_vegas_sample_device's factor)
+ *     jac    = (..(fac_0 * fac_1) * ..), the left fold over d, as fdg_vegas_sample_device forms it
+ *     r_k    the roots at x
+ *     s      = (c_k0 * r_k0) + (c_k1 * r_k1) + ...  over the roots that exist, ascending k, left fold; the factor only when coef != NULL
+ *              (the training pass's s; 0.0 when no root exists)
+ *     t      = jac * s,   a = |t|
+ * The stationary density in physical coordinates is p(x) = |s(x)| + gamma q(x), where q = 1 / jac is the map's own normalised density
+ * and gamma > 0 an argument.  The gamma q term keeps the chain ergodic wherever the map has support, and its integral is known to be 1,
+ * which normalises the result with no reference diagram:
+ *     I_k = < r_k / p > / < q / p > = sum (jac * r_k) * d / sum d,     d = 1 / (a + gamma)
+ * A move redraws the variables of a mask S through the map and keeps the others.  The Metropolis ratio is (a' + gamma) / (a + gamma)
+ * for every mask: the factors of the unchanged variables cancel, the redrawn ones cancel against the proposal density.
+ * The accept rule is   u * (a + gamma) < (a' + gamma),   each side one rounded operation, with u = what fdg_fill_uniform_device writes
+ * for counter (sample_offset + b, FDG_VEGAS_DIM_MAX) and the step's key: a variable index that no sampler uses.
+ * A proposal at which any existing root is non-finite, or whose t' is non-finite, counts as f = 0 there: its roots are taken as 0.0
+ * and a' = 0.  The value is selected, never multiplied, so an inf or nan poisons nothing; the normal rule applies to it.
+ * Roots that do not exist (FDG_NO_ROOT) are skipped in s, and their columns of the state and of the sums are never written.  Lanes
+ * past n_walker write nothing.
+ *
+ * fdg_chain_propose_device: d_x, d_xp are component-major (sample stride 1) with column strides x_col_stride, xp_col_stride
+ * (>= n_walker), n_col columns each; d_fac, d_facp are [n_dim][n_walker].  For walker b:
+ *     variable d in mask:      xp[col[d]][b] and facp[d][b] are what fdg_vegas_sample_device computes for counter (sample_offset + b, d)
+ *                              and key seed: x the same bits, fac = G * wd_d
+ *     variable d not in mask:  xp[col[d]][b] = x[col[d]][b], facp[d][b] = fac[d][b]
+ *     a column col does not name: copied from d_x
+ * so d_xp is a complete input of the evaluator.  d_grid is the map on the device, read where the sampler reads it; col a HOST array
+ * (NULL: col[d] = d).  FDG_E_INVALID: a NULL array, d_x == d_xp or d_fac == d_facp, a col[d] >= n_col, a column stride < n_walker, mask
+ * with a bit at or above n_dim, n_dim or n_grid 0; FDG_E_UNSUPPORTED: the map's limits exceeded.  n_dim = 64 is allowed.
+ *
+ * fdg_chain_step_device (leaf form: the n_col = n_leaf columns of d_xp are the graph's leaves, as in fdg_accumulate_device_strat's leaf
+ * form) and fdg_mc_chain_step_device (Monte-Carlo form: d_xp is one [n_loop * dim + n_tau][n_walker] array, momentum components first
+ * and then the times; kF, beta, lambda as in fdg_mc_eval_device): the roots of the proposals are evaluated chunk by chunk into the
+ * handle's root scratch by the route fdg_eval_device / fdg_mc_eval_device takes (the same root bits on every back end and layout), then
+ * one kernel does, per walker: the fold s', t', a'; the accept rule (FDG_CHAIN_INIT: accepted unconditionally, no u is drawn: the first
+ * placement of the walkers); the selection of x, fac, root, a from the proposal, or they are kept; and
+ *     FDG_CHAIN_MEASURE:  sum[k][b] += (jac * r_k) * d  for k < R,  sum[R][b] += d     on the state AFTER the selection (the product is
+ *                         rounded before the addition);
+ *     n_accept[b] += 1 on acceptance (int32; d_n_accept may be NULL).
+ * The state is caller-owned device memory: x [n_col][n_walker] (column stride x_col_stride), fac [n_dim][n_walker], root
+ * [n_root][n_walker], a [n_walker], sum [n_root + 1][n_walker] (may be NULL without FDG_CHAIN_MEASURE).  coef is a HOST array of n_root
+ * finite factors or NULL.  The result is a function of the arguments only: every word is written by one lane, a walker's sums are
+ * added in step order, and nothing depends on FDG_ROOT_SCRATCH_MB, the launch shape or how the walkers are sharded (a shard passes the
+ * start of its range as part of sample_offset).  FDG_E_INVALID: a NULL handle or array, any two of the state, proposal and sum arrays
+ * the same buffer, gamma not finite or <= 0, a coef that is not finite, unknown flags, n_dim 0, n_col that does not match the graph's
+ * leaves (leaf form) or the tables' n_loop * dim + n_tau (Monte-Carlo form), a column stride < n_walker, n_walker < 0; the Monte-Carlo
+ * form before fdg_graph_specialize_fused; FDG_E_UNSUPPORTED: n_dim > FDG_VEGAS_DIM_MAX.  All before any device work.
+ *
+ * fdg_chain_reduce_device: from d_sum [n_root + 1][n_walker], with A_c(b) = sum[c][b] and R = n_root, adds into d_out (3 R + 2 doubles)
+ *     d_out[c]             += S_c = sum_b A_c(b)            c = 0 .. R
+ *     d_out[R + 1 + c]     += Q_c = sum_b A_c(b)^2          c = 0 .. R
+ *     d_out[2 R + 2 + k]   += X_k = sum_b A_k(b) * A_R(b)   k = 0 .. R - 1
+ * No float atomics; bitwise reproducible; the order of every sum is a function of (n_walker, n_root) only: one workgroup per output,
+ * lane t of 256 adds the terms b = t, t + 256, .. in ascending b, the 256 partials are added pairwise (stride 128, 64, .., 1).  Every
+ * column of d_sum is read, also a root's that does not exist (the caller zeroes d_sum before the first measured step). */
+#define FDG_CHAIN_INIT 1u
+#define FDG_CHAIN_MEASURE 2u
+int fdg_chain_propose_device(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, uint32_t n_col, uint64_t mask,
+                             uint64_t seed, uint64_t sample_offset, const double *d_x, int64_t x_col_stride, const double *d_fac,
+                             double *d_xp, int64_t xp_col_stride, double *d_facp, int64_t n_walker, void *stream);
+int fdg_chain_step_device(fdg_graph *g, const double *d_xp, int64_t xp_col_stride, const double *d_facp, uint32_t n_col, uint32_t n_dim,
+                          const double *coef, double gamma, uint64_t seed, uint64_t sample_offset, unsigned flags, double *d_x,
+                          int64_t x_col_stride, double *d_fac, double *d_root, double *d_a, double *d_sum, int32_t *d_n_accept,
+                          int64_t n_walker, void *stream);
+int fdg_mc_chain_step_device(fdg_graph *g, const double *d_xp, int64_t xp_col_stride, double kF, double beta, double lambda,
+                             const double *d_facp, uint32_t n_col, uint32_t n_dim, const double *coef, double gamma, uint64_t seed,
+                             uint64_t sample_offset, unsigned flags, double *d_x, int64_t x_col_stride, double *d_fac, double *d_root,
+                             double *d_a, double *d_sum, int32_t *d_n_accept, int64_t n_walker, void *stream);
+int fdg_chain_reduce_device(const double *d_sum, uint32_t n_root, int64_t n_walker, double *d_out, void *stream);
+
 /* Device workspace control: the interpreter keeps per-sample overflow slots in
  * an HBM panel owned by the handle; it is sized on first use for the number of
  * resident waves.  This releases it (and any loaded module). */

@@ -1,0 +1,418 @@
+"""Markov-chain sampling on the VEGAS map on the device (include/fdg.h: fdg_chain_propose_device, fdg_chain_step_device,
+fdg_mc_chain_step_device, fdg_chain_reduce_device; feynmandiagram.jl_amd/vegas.py: chain_integrate).  The leaf form, whose graph part
+is bit-exact against the CPU oracle, is compared bit for bit with the numpy mirror (capi.chain_reference) after every step: x, fac,
+root, a, sum, n_accept; the reduced sums with the mirror's exact ones (math.fsum), |d| <= 1e-12 sum |term|.  The statistical
+conditions are the ones the mirror alone meets in tests/test_chain_host.py."""
+import math
+import os
+
+import numpy as np
+import pytest
+
+import oracle
+import feynmandiagram_jl_amd as fd
+from feynmandiagram_jl_amd import capi, vegas, workloads
+from feynmandiagram_jl_amd.lowering import lower
+from feynmandiagram_jl_amd.nodetable import FDG_NO_ROOT
+from test_chain_host import (CHI2_HI, CHI2_LO, INIT, KNOWN, MEASURE, fresh_state, known_chi2, known_graph, known_mirror, oracle_roots,
+                             step_uniforms)
+from test_strat_accumulate import assert_bits, random_program, refined_grid
+
+pytestmark = pytest.mark.gpu
+
+GOLD = os.path.join(os.path.dirname(__file__), "golden")
+TOL = 1e-12
+SENT = -7.25                                               # what the lanes past n_walker hold
+PAD = 5                                                    # lanes past n_walker in the over-allocated arrays
+STATE = ("x", "fac", "root", "a", "sum", "n_accept")
+
+
+class DeviceChain:
+    """The state of B walkers on the device, every array over-allocated by PAD sentinel lanes behind its last word (x and xp: PAD
+    lanes behind every column, column stride B + PAD), and the raw calls of one step."""
+
+    def __init__(self, handle, cuda, grid, col, fixed, B, coef=None, shard_start=0):
+        import torch
+        self.h, self.cuda, self.B, self.col, self.coef, self.off0 = handle, cuda, B, col, coef, shard_start
+        self.D, self.G, self.R, self.C = grid.shape[0], grid.shape[1] - 1, handle.table.n_root, len(fixed)
+        self.d_grid = torch.from_numpy(np.ascontiguousarray(grid)).to(cuda)
+        self.xc = B + PAD
+        D, R, C = self.D, self.R, self.C
+
+        def flat(n, dtype=torch.float64):
+            return torch.full((n + PAD,), SENT, dtype=dtype, device=cuda)
+        self.x = torch.full((C, self.xc), SENT, dtype=torch.float64, device=cuda)
+        self.x[:, :B] = torch.from_numpy(np.asarray(fixed, dtype=np.float64)).to(cuda)[:, None]
+        self.xp = torch.full((C, self.xc), SENT, dtype=torch.float64, device=cuda)
+        self.fac, self.facp, self.root, self.a, self.total = flat(D * B), flat(D * B), flat(R * B), flat(B), flat((R + 1) * B)
+        self.n_acc = flat(B, torch.int32)
+        self.fac[:D * B], self.root[:R * B], self.a[:B], self.total[:(R + 1) * B], self.n_acc[:B] = 1.0, 0.0, 0.0, 0.0, 0
+        self.st = torch.cuda.current_stream().cuda_stream
+
+    def propose(self, mask, seed, off):
+        capi.chain_propose_device(self.d_grid.data_ptr(), self.D, self.G, self.col, self.C, mask, seed, off, self.x.data_ptr(), self.xc,
+                                  self.fac.data_ptr(), self.xp.data_ptr(), self.xc, self.facp.data_ptr(), self.B, self.st)
+
+    def select(self, gamma, seed, off, flags, mc=None):
+        tail = (self.facp.data_ptr(), self.C, self.D, self.coef, gamma, seed, off, flags, self.x.data_ptr(), self.xc, self.fac.data_ptr(),
+                self.root.data_ptr(), self.a.data_ptr(), self.total.data_ptr(), self.n_acc.data_ptr(), self.B, self.st)
+        if mc is None:
+            self.h.chain_step_device(self.xp.data_ptr(), self.xc, *tail)
+        else:
+            self.h.mc_chain_step_device(self.xp.data_ptr(), self.xc, *mc, *tail)
+
+    def step(self, mask, gamma, seed, off, flags, mc=None):
+        self.propose(mask, seed, off)
+        self.select(gamma, seed, off, flags, mc)
+
+    def reduced(self):
+        import torch
+        out = torch.zeros(3 * self.R + 2, dtype=torch.float64, device=self.cuda)
+        capi.chain_reduce_device(self.total.data_ptr(), self.R, self.B, out.data_ptr(), self.st)
+        torch.cuda.synchronize()
+        return out.cpu().numpy()
+
+    def state(self):
+        """the state as the mirror holds it, after checking that no lane past n_walker was written"""
+        import torch
+        torch.cuda.synchronize()
+        B, D, R = self.B, self.D, self.R
+        x, xp = self.x.cpu().numpy(), self.xp.cpu().numpy()
+        assert (x[:, B:] == SENT).all() and (xp[:, B:] == SENT).all(), "a lane past n_walker of x or xp was written"
+        out = {"x": x[:, :B].copy(), "xp": xp[:, :B].copy()}
+        for name, t, n in (("fac", self.fac, D * B), ("facp", self.facp, D * B), ("root", self.root, R * B), ("a", self.a, B),
+                           ("sum", self.total, (R + 1) * B), ("n_accept", self.n_acc, B)):
+            h = t.cpu().numpy()
+            assert (h[n:] == (SENT if h.dtype == np.float64 else int(SENT))).all(), name + ": a word past the array was written"
+            out[name] = h[:n].reshape(-1, B).copy() if n != B else h[:n].copy()
+        return out
+
+
+def assert_state(got, want, what):
+    for k in STATE:
+        assert_bits(got[k], want[k], f"{what}: {k}")
+
+
+def assert_reduced(got, total, what):
+    want = capi.chain_reduce_reference(total)
+    R = total.shape[0] - 1
+    scale = np.array([math.fsum(np.abs(total[c])) for c in range(R + 1)] + [math.fsum(total[c] * total[c]) for c in range(R + 1)]
+                     + [math.fsum(np.abs(total[k] * total[R])) for k in range(R)])
+    d = np.abs(got - want)
+    assert (d <= TOL * scale).all(), (what, np.argwhere(~(d <= TOL * scale))[:4], d.max())
+
+
+def random_case(cuda, options=None):
+    t = random_program(21)
+    f = fd.compile_table(t, specialize="isa", options=options)
+    rng = np.random.default_rng(8)
+    col = [5, 0, 3]                                         # three of the seven leaves are variables, in no particular order
+    fixed = rng.uniform(-1.0, 1.0, size=t.n_leaf)
+    grid = refined_grid(rng, len(col), 6)
+    coef = rng.uniform(-1.0, 1.0, size=t.n_root)
+    exists = [int(s) != FDG_NO_ROOT for s in t.root_slot]
+    assert sum(exists) == t.n_root - 1 and t.n_root == 10
+    return t, f, col, fixed, grid, coef, exists
+
+
+MASKS = [0b111, 0b010, 0b101, 0, 0b111, 0b001, 0b110, 0b100, 0, 0b111, 0b011, 0b111]       # all / one / two / empty, 12 steps
+
+
+def run_both(chain, table, grid, col, fixed, coef, exists, B, seed, gamma, n_total, shard_start=0, n_therm=3, check=True, lanes=None):
+    """INIT and the 12 steps on the device and on the mirror (``lanes``: the mirror's slice of a larger run); every state compared"""
+    D, R = grid.shape[0], table.n_root
+    ev = oracle_roots(table)
+    m = fresh_state(fixed, D, R, B)
+    steps = [(0b111, shard_start, 1.0, INIT)] + [(mask, (t + 1) * n_total + shard_start, gamma, MEASURE if t >= n_therm else 0)
+                                                  for t, mask in enumerate(MASKS)]
+    trace = []
+    for i, (mask, off, g, flags) in enumerate(steps):
+        chain.step(mask, g, seed, off, flags)
+        got = chain.state()
+        if check:
+            u, ua = step_uniforms(B, D, mask, seed, off)
+            m = capi.chain_reference(grid, col, m, mask, u, ua, g, flags, ev, coef, exists)
+            assert_bits(got["xp"], m["xp"], f"step {i}: xp")
+            assert_bits(got["facp"], m["facp"], f"step {i}: facp")
+            assert_state(got, m, f"step {i}")
+            assert_reduced(chain.reduced(), m["sum"], f"step {i}: reduced sums")
+        trace.append(got)
+    return trace
+
+
+@pytest.mark.parametrize("B", [1, 63, 64, 65])
+def test_every_step_matches_the_mirror_bit_for_bit(libfdg, cuda, B):
+    t, f, col, fixed, grid, coef, exists = random_case(cuda)
+    trace = run_both(DeviceChain(f.handle, cuda, grid, col, fixed, B, coef), t, grid, col, fixed, coef, exists, B, 11, 0.37, B)
+    acc = trace[-1]["n_accept"]
+    assert acc.min() >= 3 and (B < 63 or acc.max() > acc.min())     # the INIT and the two empty masks; some proposals were refused
+    # the empty mask: the state unchanged bit for bit, one more acceptance everywhere
+    for i in (4, 9):
+        for k in ("x", "fac", "root", "a"):
+            assert_bits(trace[i][k], trace[i - 1][k], f"empty mask: {k}")
+        assert (trace[i]["n_accept"] == trace[i - 1]["n_accept"] + 1).all()
+    # a second run gives the same bits
+    again = run_both(DeviceChain(f.handle, cuda, grid, col, fixed, B, coef), t, grid, col, fixed, coef, exists, B, 11, 0.37, B, check=False)
+    assert_state(again[-1], trace[-1], "second run")
+
+
+def test_walkers_over_several_chunks_with_a_short_last_one(libfdg, cuda):
+    """70 003 walkers with FDG_ROOT_SCRATCH_MB = 1: chunks of 13 056 walkers, the last one of 4 723.  The same bits with the default
+    scratch (one chunk), and from two shards."""
+    B, seed, gamma = 70_003, 12, 0.37
+    t, f1, col, fixed, grid, coef, exists = random_case(cuda, options={"FDG_ROOT_SCRATCH_MB": "1"})
+    trace = run_both(DeviceChain(f1.handle, cuda, grid, col, fixed, B, coef), t, grid, col, fixed, coef, exists, B, seed, gamma, B)
+    red = DeviceChain(f1.handle, cuda, grid, col, fixed, B, coef)
+    run_both(red, t, grid, col, fixed, coef, exists, B, seed, gamma, B, check=False)
+    f = fd.compile_table(t, specialize="isa")
+    whole = DeviceChain(f.handle, cuda, grid, col, fixed, B, coef)
+    other = run_both(whole, t, grid, col, fixed, coef, exists, B, seed, gamma, B, check=False)
+    assert_state(other[-1], trace[-1], "FDG_ROOT_SCRATCH_MB changed")
+    assert_bits(whole.reduced(), red.reduced(), "reduced sums, FDG_ROOT_SCRATCH_MB changed")
+    cut = 30_001
+    for lo, n in ((0, cut), (cut, B - cut)):
+        part = run_both(DeviceChain(f1.handle, cuda, grid, col, fixed, n, coef, lo), t, grid, col, fixed, coef, exists, n, seed, gamma, B,
+                        shard_start=lo, check=False)
+        for k in STATE:
+            assert_bits(part[-1][k], trace[-1][k][..., lo:lo + n], f"shard at {lo}: {k}")
+
+
+def test_zero_coefficients_tie_the_chain_to_the_plain_pipeline(libfdg, cuda):
+    """coef = 0, gamma = 1, every variable redrawn: a = a' = 0, so every step is accepted; x after step t is fdg_vegas_sample_device's
+    output for that sample_offset; d = 1, so the walkers' sums add up to the fdg_accumulate_device_moments calls with weight jac."""
+    import torch
+    B, seed, n_step = 1000, 5, 4
+    t, f, col, fixed, grid, _, exists = random_case(cuda)
+    D, R, L = len(col), t.n_root, t.n_leaf
+    chain = DeviceChain(f.handle, cuda, grid, col, fixed, B, np.zeros(R))
+    chain.step(0b111, 1.0, seed, 0, INIT)
+    xs = torch.from_numpy(fixed).to(cuda)[:, None].repeat(1, B).contiguous()
+    jac = torch.zeros(B, dtype=torch.float64, device=cuda)
+    acc, acc2 = torch.zeros(R, dtype=torch.float64, device=cuda), torch.zeros(R, dtype=torch.float64, device=cuda)
+    terms = np.zeros((R, 0))
+    for s in range(n_step):
+        off = (s + 1) * B
+        chain.step(0b111, 1.0, seed, off, MEASURE)
+        got = chain.state()
+        capi.vegas_sample_device(chain.d_grid.data_ptr(), D, chain.G, col, seed, off, xs.data_ptr(), 1, B, jac.data_ptr(), 0, B, chain.st)
+        f.handle.accumulate_device_moments(xs.data_ptr(), 1, B, 0, 0, 0, 1, jac.data_ptr(), acc.data_ptr(), acc2.data_ptr(), B, chain.st)
+        torch.cuda.synchronize()
+        assert_bits(got["x"], xs.cpu().numpy(), f"step {s}: x")
+        assert (got["n_accept"] == s + 2).all() and (got["a"] == 0.0).all()
+        assert_bits(np.prod(got["fac"], axis=0) if D == 1 else (got["fac"][0] * got["fac"][1]) * got["fac"][2], jac.cpu().numpy(), "jac")
+        terms = np.concatenate([terms, got["root"] * jac.cpu().numpy()[None, :]], axis=1)
+    total = chain.state()["sum"]
+    assert (total[R] == float(n_step)).all()
+    live = [k for k in range(R) if exists[k]]
+    want, scale = acc.cpu().numpy(), np.array([math.fsum(np.abs(terms[k])) for k in range(R)])
+    got = np.array([math.fsum(total[k]) for k in range(R)])
+    assert (np.abs(got - want)[live] <= TOL * scale[live]).all(), (got, want)
+    assert (total[[k for k in range(R) if not exists[k]]] == 0.0).all()                  # the column of the root that does not exist
+
+
+def poison_graph():
+    """r_0 = (2e154 x)^2 is inf for x > 0.67, r_1 = r_0 - (2e154 y)^2 nan where both overflow, r_2 = x y finite everywhere, over [0, 1]^2
+    (the uniform map's jacobian is 1 there, so a finite root stays finite under it)"""
+    x, y = fd.Graph([]), fd.Graph([])
+    bx = fd.Graph([fd.Graph([x], subgraph_factors=[2e154], operator=fd.Sum())], operator=fd.Power(2))
+    by = fd.Graph([fd.Graph([y], subgraph_factors=[2e154], operator=fd.Sum())], operator=fd.Power(2))
+    r1 = fd.Graph([bx, by], subgraph_factors=[1.0, -1.0], operator=fd.Sum())
+    r2 = fd.Graph([x, y], operator=fd.Prod())
+    t, leafmap, _ = lower([bx, r1, r2])
+    at = {g.id: i - 1 for i, g in leafmap.items()}
+    assert t.n_leaf == 2 and t.n_root == 3
+    return t, [at[x.id], at[y.id]]
+
+
+def test_poisoned_proposals_count_as_zero(libfdg, cuda):
+    """Proposals whose roots are inf or nan (here: where x or y > 0.67, about half of them) have a' = 0 and roots 0.0: they are
+    accepted or refused by the normal rule, and nothing that is not finite reaches the state or a sum."""
+    t, col = poison_graph()
+    f = fd.compile_table(t, specialize="isa")
+    B, seed, gamma = 300, 4, 0.5
+    grid = vegas.uniform_grid([0, 0], [1, 1], 4)
+    coef = np.array([1e-300, 1.0, 1.0])
+    ev = oracle_roots(t)
+    chain = DeviceChain(f.handle, cuda, grid, col, np.zeros(2), B, coef)
+    m = fresh_state(np.zeros(2), 2, 3, B)
+    n_bad = 0
+    for i, (mask, flags) in enumerate([(3, INIT)] + [(mask, MEASURE) for mask in (3, 1, 2, 3, 0, 3, 1)]):
+        off = i * B
+        chain.step(mask, gamma, seed, off, flags)
+        got = chain.state()
+        u, ua = step_uniforms(B, 2, mask, seed, off)
+        m = capi.chain_reference(grid, col, m, mask, u, ua, gamma, flags, ev, coef, None)
+        bad = ~np.isfinite(ev(m["xp"])).all(axis=0)
+        n_bad += int(bad.sum())
+        assert (m["root"][:, bad & m["accept"]] == 0.0).all() and (m["a"][bad & m["accept"]] == 0.0).all()
+        assert_state(got, m, f"step {i}")
+        assert all(np.isfinite(got[k]).all() for k in ("x", "fac", "root", "a", "sum"))
+    assert n_bad > B and 0 < (m["a"] == 0.0).sum() < B                                    # poisoned proposals were met, and accepted
+    assert_reduced(chain.reduced(), m["sum"], "reduced sums")
+
+
+# ---- the driver --------------------------------------------------------------------------------------------------------------------------- #
+def known_device(f, col, fixed, cuda, seed, n_therm=None):
+    k = KNOWN
+    return vegas.chain_integrate(f, None, [0, 0], [1, 1], col, n_walker=k["n_walker"], n_step=k["n_step"],
+                                 n_therm=k["n_therm"] if n_therm is None else n_therm, moves=[3, 1, 2], gamma=k["gamma"], n_warm=0,
+                                 n_grid=k["n_grid"], seed=seed, fixed=fixed, coef=[1.0, 1.0], device=cuda)
+
+
+def test_known_answer_on_a_sign_changing_pair(libfdg, cuda):
+    """r_0 = (x - 0.3)(1 - y)^3 and r_1 = x y over the unit square, exact 0.05 and 0.25 (the graph model has no exp: the polynomial
+    pair of tests/test_chain_host.py): within 5 sigma at seed 0, and the sum over seeds 0 .. 31 of ((mean - exact) / sigma)^2 inside
+    [10.3, 70.6], the 1e-4 and 1 - 1e-4 quantiles of chi^2 with 32 degrees of freedom.  The mirror gives 31.57 and 40.61, and the
+    device the mirror's figures."""
+    t, col, fixed = known_graph()
+    f = fd.compile_table(t, specialize="isa")
+    chi2, first = known_chi2(lambda seed: vars(known_device(f, col, fixed, cuda, seed)))
+    mirror = known_mirror(0, table=(t, col, fixed))
+    print("seed 0: mean", first["mean"], "stderr", first["stderr"], "acceptance", first["acceptance"], "chi2 over 32 seeds", chi2)
+    print("mirror: mean", mirror["mean"], "stderr", mirror["stderr"], "acceptance", mirror["acceptance"])
+    assert (np.abs(first["mean"] - KNOWN["exact"]) < 5.0 * first["stderr"]).all()
+    assert ((CHI2_LO <= chi2) & (chi2 <= CHI2_HI)).all()
+    assert np.allclose(first["mean"], mirror["mean"], rtol=1e-11, atol=0) and np.allclose(first["stderr"], mirror["stderr"], rtol=1e-9, atol=0)
+    assert first["acceptance"] == mirror["acceptance"] and first["gamma"] == KNOWN["gamma"]
+    assert np.allclose(first["S"], mirror["S"], rtol=1e-12, atol=0)
+
+
+# ---- the diagram -------------------------------------------------------------------------------------------------------------------------- #
+def gv_sigma4_case():
+    z = dict(np.load(os.path.join(GOLD, "gv_sigma4_leafstates.npz")))
+    t = workloads.get("gv_sigma4")
+    dim, n_loop, n_tau = 3, int(z["basis"].shape[1]), int(z["n_tau"])
+    kF, beta, lam = 1.919, 3.0, 1.2
+    nk, C = n_loop * dim, n_loop * dim + n_tau
+    col = list(range(dim, nk)) + list(range(nk + 1, C))                     # the external momentum and T[1] stay fixed
+    lo = np.array([-2.0] * (nk - dim) + [0.0] * (n_tau - 1))
+    hi = np.array([2.0] * (nk - dim) + [beta] * (n_tau - 1))
+    fixed = np.zeros(C)
+    fixed[0] = kF
+    args = (z["leaf_type"], z["leaf_order"], z["tau_in"], z["tau_out"], z["loop_index"], z["basis"], dim, n_tau)
+    return t, args, (kF, beta, lam), nk, C, col, lo, hi, fixed
+
+
+def test_init_of_both_forms_on_gv_sigma4(libfdg, cuda):
+    """The Monte-Carlo form's first placement against the leaf form's on the leaves of the same proposals (fdg_leaf_eval_device):
+    the leaves of the one-kernel route differ from those in the last ulps, so the roots agree within the leaf tolerance of DESIGN 8
+    carried through the graph, not bit for bit.  Both sets of leaves lie within d = 1e-13 relative of the oracle's (the bar the leaf
+    kernels are tested at), so within 2 d of each other; a root of the fourth-order self-energy is a sum of products of at most 11
+    leaves (7 propagators, 4 interaction lines), so to first order |d root_k| <= 11 * 2 d * A_k with A_k the graph on |leaf| and
+    |factor| (oracle.abs_graph_scale; the bound of tests/test_gpu_parity.py::test_mc_step_in_one_isa_kernel): 2.2e-12 max(1, A_k).
+    a = |jac s| then agrees within |jac| times the sum of those bars."""
+    import torch
+    t, args, (kF, beta, lam), nk, C, col, lo, hi, fixed = gv_sigma4_case()
+    B, D, G, seed = 4099, len(col), 12, 3
+    grid = capi.vegas_refine(vegas.uniform_grid(lo, hi, G), np.random.default_rng(2).random((D, G)) + 0.05, 1.0)
+    tab, _keep = capi.make_leaf_tables(*args)
+    f = fd.compile_table(t, specialize="isa")
+    f.handle.specialize_fused(tab)
+    mc = DeviceChain(f.handle, cuda, grid, col, fixed, B)
+    mc.step((1 << D) - 1, 1.0, seed, 0, INIT, mc=(kF, beta, lam))
+    got = mc.state()
+    # the leaf form: the same proposal's leaves as the columns of xp
+    leaf = DeviceChain(f.handle, cuda, grid, list(range(D)), np.ones(t.n_leaf), B)
+    leaf.facp[:D * B] = mc.facp[:D * B]
+    leaf.xp[:, :B] = 1.0                                    # (leaves without a formula are 1.0 and are not written)
+    capi.leaf_eval_device(*args, kF, beta, lam, mc.xp.data_ptr(), 1, mc.xc, mc.xp.data_ptr() + 8 * nk * mc.xc, 1, mc.xc,
+                          leaf.xp.data_ptr(), 1, leaf.xc, B, mc.st)
+    leaf.select(1.0, seed, 0, INIT)
+    want = leaf.state()
+    assert_bits(got["fac"], want["fac"], "fac")
+    bar = 11 * 2e-13 * np.maximum(1.0, oracle.abs_graph_scale(t, np.ascontiguousarray(want["xp"].T))).T          # [R, B]
+    d, jac = np.abs(got["root"] - want["root"]), np.prod(want["fac"], axis=0)
+    da = np.abs(got["a"] - want["a"])
+    print("max |d root| / bar =", (d / bar).max(), " max |d a| / bar =", (da / (np.abs(jac) * bar.sum(axis=0))).max())
+    assert (d <= bar).all() and (da <= np.abs(jac) * bar.sum(axis=0) * (1.0 + 1e-9)).all()
+    assert (got["n_accept"] == 1).all() and np.isfinite(got["root"]).all()
+    u, _ = step_uniforms(B, D, (1 << D) - 1, seed, 0)
+    m = capi.chain_reference(grid, col, fresh_state(fixed, D, t.n_root, B), (1 << D) - 1, u, None, 1.0, INIT,
+                             lambda xp: np.zeros((t.n_root, B)))
+    assert_bits(got["x"], m["x"], "x of the first placement")
+
+
+DIAGRAM = dict(n_walker=20_000, n_step=40, n_therm=16, gamma_rel=16.0, n_warm=3, n_warm_sample=100_000, n_grid=16)
+
+
+def test_chain_agrees_with_vegas_on_gv_sigma4_in_both_forms(libfdg, cuda):
+    """The GV self-energy of order 4 over its internal momenta and times (the box of tests/test_strat_accumulate.py): the chain's two
+    roots against vegas_integrate's on the same integrand, |d| < 5 sqrt(sigma_chain^2 + sigma_vegas^2) per root, for the Monte-Carlo
+    form (chain_integrate) and for the leaf form (the same proposals' leaves from fdg_leaf_eval_device as the columns of xp).
+
+    The sizes were chosen on the CPU mirror (oracle.leaf_values + the oracle's graph, a map trained by three iterations), where a
+    reference of 6e5 plain samples gives root 1 = -8.54e13 +- 0.39e13.  This integrand cancels (the mean of |jac s| is 7e14, six times
+    the integral) and its large values are rare under the map, so a walker needs many proposals to find them: with gamma_rel = 1 the
+    mirror's chain of 40 steps (16 discarded) reads -6.2e13 .. -4.7e13 +- 0.3e13 on root 1, 5 to 8 sigma low, and 120 steps (40
+    discarded) still -7.5e13, 2.2 sigma low: it is not thermalised, and its error bar cannot know.  gamma_rel = 16 mixes at once
+    (acceptance 0.97): 40 steps give -8.35e13 +- 0.62e13, and root 0 within 0.4 sigma.  Hence gamma_rel = 16 here; both findings
+    are written up in DESIGN 8k."""
+    import torch
+    t, args, (kF, beta, lam), nk, C, col, lo, hi, fixed = gv_sigma4_case()
+    k = DIAGRAM
+    tab, _keep = capi.make_leaf_tables(*args)
+    f = fd.compile_table(t, specialize="isa")
+    ref = vegas.vegas_integrate(f, tab, lo, hi, col, kF, beta, lam, n_iter=6, n_discard=3, n_sample=200_000, n_grid=k["n_grid"], seed=999,
+                                fixed=fixed, device=cuda)
+    res = vegas.chain_integrate(f, tab, lo, hi, col, kF, beta, lam, n_walker=k["n_walker"], n_step=k["n_step"], n_therm=k["n_therm"],
+                                gamma_rel=k["gamma_rel"], n_warm=k["n_warm"], n_warm_sample=k["n_warm_sample"], n_grid=k["n_grid"], seed=0,
+                                fixed=fixed, device=cuda)
+    pull = (res.mean - ref.mean) / np.sqrt(res.stderr ** 2 + ref.stderr ** 2)
+    print("vegas", ref.mean, ref.stderr, "chain (Monte-Carlo form)", res.mean, res.stderr, "acceptance", res.acceptance, "pull", pull)
+    n_chain, n_vegas = k["n_walker"] * (k["n_step"] + 1), 3 * 200_000
+    print("variance per evaluation, chain / vegas:", (res.stderr ** 2 * n_chain) / (ref.stderr ** 2 * n_vegas))
+    assert (np.abs(pull) < 5.0).all() and 0.5 < res.acceptance <= 1.0
+    # the leaf form on the map the chain trained: proposals in (K, T), their leaves as the columns of xp, the selection of (K, T)
+    # from the step's own acceptances
+    B, D, seed = k["n_walker"], len(col), 1
+    grid = res.map.grid
+    kt = DeviceChain(f.handle, cuda, grid, col, fixed, B)
+    leaf = DeviceChain(f.handle, cuda, grid, list(range(D)), np.ones(t.n_leaf), B)
+    leaf.xp[:, :B] = 1.0
+    moves, gamma = vegas.chain_moves(D), 1.0
+    for s in range(-1, k["n_step"]):
+        off = (s + 1) * B
+        kt.propose((1 << D) - 1 if s < 0 else moves[s % len(moves)], seed, off)
+        leaf.facp[:D * B] = kt.facp[:D * B]
+        capi.leaf_eval_device(*args, kF, beta, lam, kt.xp.data_ptr(), 1, kt.xc, kt.xp.data_ptr() + 8 * nk * kt.xc, 1, kt.xc,
+                              leaf.xp.data_ptr(), 1, leaf.xc, B, kt.st)
+        before = leaf.n_acc[:B].clone()
+        leaf.select(gamma, seed, off, INIT if s < 0 else (MEASURE if s >= k["n_therm"] else 0))
+        acc = leaf.n_acc[:B] != before
+        kt.x[:, :B] = torch.where(acc[None, :], kt.xp[:, :B], kt.x[:, :B])
+        kt.fac[:D * B] = torch.where(acc.repeat(D), kt.facp[:D * B], kt.fac[:D * B])
+        if s < 0:
+            gamma = k["gamma_rel"] * float(leaf.a[:B].mean().item())
+    R = t.n_root
+    red = leaf.reduced()
+    mean, err = vegas.chain_estimate(red[:R + 1], red[R + 1:2 * R + 2], red[2 * R + 2:], B)
+    pull = (mean - ref.mean) / np.sqrt(err ** 2 + ref.stderr ** 2)
+    print("chain (leaf form)", mean, err, "gamma", gamma, "against", res.gamma, "pull", pull)
+    assert (np.abs(pull) < 5.0).all()
+    assert abs(gamma / res.gamma - 1.0) < 0.1                        # two estimates of 16 times the integral of |s| on the same map
+
+
+def test_180_roots_and_64_variables(libfdg, cuda):
+    """parquet_ver4_4 (180 roots) in the leaf form with 64 of its leaves as variables, the most a map holds: the accept rule's uniform
+    is then the Philox column right behind the last variable's.  Two chunks (FDG_ROOT_SCRATCH_MB = 1 holds 704 walkers of 180 roots,
+    the second has 66).  On the mirror 202 of the 770 walkers refuse at least one proposal."""
+    t = workloads.get("parquet_ver4_4")
+    f = fd.compile_table(t, specialize="isa", options={"FDG_ROOT_SCRATCH_MB": "1"})
+    B, D, G, seed, gamma = 770, capi.FDG_VEGAS_DIM_MAX, 3, 9, 2.0 ** -22       # (gamma: about the mean of a = |jac s| on this map, 1.9e-7)
+    rng = np.random.default_rng(6)
+    col = [int(c) for c in rng.permutation(t.n_leaf)[:D]]
+    fixed = rng.uniform(0.2, 1.0, size=t.n_leaf)
+    grid = capi.vegas_refine(vegas.uniform_grid([0.2] * D, [1.0] * D, G), rng.random((D, G)) + 0.5, 1.0)
+    coef = rng.uniform(-1.0, 1.0, size=t.n_root)
+    ev = oracle_roots(t)
+    chain = DeviceChain(f.handle, cuda, grid, col, fixed, B, coef)
+    m = fresh_state(fixed, D, t.n_root, B)
+    full = (1 << D) - 1
+    for i, (mask, flags) in enumerate([(full, INIT), (full, MEASURE), (1 << 63, MEASURE), (0x8000000000000001, MEASURE), (full, MEASURE)]):
+        off = i * B + (1 << 32)                              # a counter whose high word is not zero
+        chain.step(mask, gamma, seed, off, flags)
+        u, ua = step_uniforms(B, D, mask, seed, off)
+        m = capi.chain_reference(grid, col, m, mask, u, ua, gamma, flags, ev, coef, None)
+        assert_state(chain.state(), m, f"step {i}")
+    assert 0 < (m["n_accept"] < 5).sum()                     # some proposals were refused
+    assert_reduced(chain.reduced(), m["sum"], "reduced sums")
