@@ -55,6 +55,7 @@ EXPORTS = [
     "fdg_vegas_sample_device_strat_grouped", "fdg_accumulate_device_strat_grouped", "fdg_mc_accumulate_device_strat_grouped",
     "fdg_strat_allocate_cols",
     "fdg_chain_propose_device", "fdg_chain_step_device", "fdg_mc_chain_step_device", "fdg_chain_reduce_device",
+    "fdg_chain_step_device_matsubara", "fdg_mc_chain_step_device_matsubara",
 ]
 FDG_BIN_MAX = 16384     # fdg_accumulate_device_binned: largest n_bin
 FDG_VEGAS_DIM_MAX, FDG_VEGAS_GRID_MAX = 64, 1024     # the VEGAS map: most variables, most cells per variable
@@ -119,6 +120,12 @@ class Matsubara(C.Structure):
                 ("root_tau_out", C.c_void_p), ("beta", C.c_double), ("d_T", C.c_void_p), ("t_sample_stride", C.c_int64),
                 ("t_comp_stride", C.c_int64), ("n_tau", C.c_uint32), ("d_acc_re", C.c_void_p), ("d_acc_im", C.c_void_p),
                 ("d_acc2_re", C.c_void_p), ("d_acc2_im", C.c_void_p)]
+
+
+class ChainMatsubara(C.Structure):
+    """fdg_chain_matsubara (include/fdg.h)"""
+    _fields_ = [("n_freq", C.c_uint32), ("fermionic", C.c_int32), ("freq", C.c_void_p), ("weight_freq", C.c_uint32),
+                ("root_col_in", C.c_void_p), ("root_col_out", C.c_void_p), ("beta", C.c_double)]
 
 
 class WeightGroups(C.Structure):
@@ -304,6 +311,8 @@ def lib():
     L.fdg_mc_chain_step_device.argtypes = [vp, dp, i64, C.c_double, C.c_double, C.c_double, dp, u32, u32, C.c_void_p, C.c_double, u64, u64,
                                            C.c_uint, dp, i64, dp, dp, dp, dp, dp, i64, vp]
     L.fdg_chain_reduce_device.argtypes = [dp, u32, i64, dp, vp]
+    L.fdg_chain_step_device_matsubara.argtypes = L.fdg_chain_step_device.argtypes[:-2] + [C.c_void_p, i64, vp]
+    L.fdg_mc_chain_step_device_matsubara.argtypes = L.fdg_mc_chain_step_device.argtypes[:-2] + [C.c_void_p, i64, vp]
     L.fdg_powi.argtypes = [C.c_double, C.c_int32]
     L.fdg_powi.restype = C.c_double
     _lib = L
@@ -712,6 +721,26 @@ class GraphHandle:
                                              None if c is None else c.ctypes.data, gamma, seed, sample_offset, flags, d_x or None, xc,
                                              d_fac or None, d_root or None, d_a or None, d_sum or None, d_n_accept or None, B, stream))
 
+    # the same steps with the Matsubara projection in the weight and in the measurement: desc = make_chain_matsubara(...)[0], d_sum
+    # [2 n_freq n_root + 1, B] (fdg.h, "Markov chain with a Matsubara-projected weight and measurement")
+    def chain_step_device_matsubara(self, d_xp: int, xpc: int, d_facp: int, n_col: int, n_dim: int, coef, gamma: float, seed: int,
+                                    sample_offset: int, flags: int, d_x: int, xc: int, d_fac: int, d_root: int, d_a: int, d_sum: int,
+                                    d_n_accept: int, desc, B: int, stream: int = 0):
+        c = self._coef(coef)
+        check(lib().fdg_chain_step_device_matsubara(self._h, d_xp or None, xpc, d_facp or None, n_col, n_dim,
+                                                    None if c is None else c.ctypes.data, gamma, seed, sample_offset, flags, d_x or None, xc,
+                                                    d_fac or None, d_root or None, d_a or None, d_sum or None, d_n_accept or None,
+                                                    None if desc is None else C.addressof(desc), B, stream))
+
+    def mc_chain_step_device_matsubara(self, d_xp: int, xpc: int, kF, beta, lam, d_facp: int, n_col: int, n_dim: int, coef, gamma: float,
+                                       seed: int, sample_offset: int, flags: int, d_x: int, xc: int, d_fac: int, d_root: int, d_a: int,
+                                       d_sum: int, d_n_accept: int, desc, B: int, stream: int = 0):
+        c = self._coef(coef)
+        check(lib().fdg_mc_chain_step_device_matsubara(self._h, d_xp or None, xpc, kF, beta, lam, d_facp or None, n_col, n_dim,
+                                                       None if c is None else c.ctypes.data, gamma, seed, sample_offset, flags,
+                                                       d_x or None, xc, d_fac or None, d_root or None, d_a or None, d_sum or None,
+                                                       d_n_accept or None, None if desc is None else C.addressof(desc), B, stream))
+
     def _coef(self, coef):
         if coef is None:
             return None
@@ -861,6 +890,100 @@ def chain_reference(grid, col, state, mask: int, u, u_acc, gamma: float, flags: 
         for k in live:
             total[k] = total[k] + (jac * root[k]) * dd
         total[R] = total[R] + dd
+    return {"x": x, "fac": fac, "root": root, "a": a, "sum": total, "n_accept": n_acc, "xp": xp, "facp": facp, "accept": acc}
+
+
+def make_chain_matsubara(freq, fermionic, weight_freq: int, root_col_in, root_col_out, beta: float):
+    """``(fdg_chain_matsubara struct, keepalive)``: ``freq`` the n of every frequency, ``weight_freq`` the index of the one the chain's
+    weight is projected onto, ``root_col_in`` / ``root_col_out`` the 0-based columns of ``x`` that hold every root's two times."""
+    f = np.ascontiguousarray(freq, dtype=np.int32)
+    cin, cout = (np.ascontiguousarray(v, dtype=np.uint32) for v in (root_col_in, root_col_out))
+    if f.ndim != 1 or cin.ndim != 1 or cin.shape != cout.shape:
+        raise ValueError("freq must be a sequence, root_col_in and root_col_out one column per root each")
+    m = ChainMatsubara(f.shape[0], 1 if fermionic else 0, f.ctypes.data, int(weight_freq), cin.ctypes.data, cout.ctypes.data, float(beta))
+    return m, (f, cin, cout)
+
+
+def chain_matsubara_reference(grid, col, state, mask: int, u, u_acc, gamma: float, flags: int, eval_roots, freq, fermionic, weight_freq: int,
+                              root_col_in, root_col_out, beta: float, coef=None, exists=None, phase_table=None):
+    """One step of the projected chain restated in numpy (include/fdg.h, "Markov chain with a Matsubara-projected weight and
+    measurement"): fdg_chain_propose_device, then fdg_[mc_]chain_step_device_matsubara, in the device's fp64 order, so that the state
+    and the sums compare bit for bit.  The arguments of :func:`chain_reference`, with ``state["sum"]`` ``[2 F R + 1, B]``, and the
+    descriptor's: ``freq [F]``, ``fermionic``, ``weight_freq``, the 0-based time columns ``root_col_in`` / ``root_col_out [R]`` and
+    ``beta``.  The phases are the library's own (fdg_matsubara_phase through :func:`matsubara_phase_table`), one table per distinct
+    pair of columns; ``phase_table(tau, beta, freq, fermionic) -> (s, c) [B, F]`` replaces that routine by a faster one with the
+    same bits."""
+    table = matsubara_phase_table if phase_table is None else phase_table
+    grid = np.asarray(grid, dtype=np.float64)
+    D, G = grid.shape[0], grid.shape[1] - 1
+    x, fac, root, a = (np.array(state[k], dtype=np.float64) for k in ("x", "fac", "root", "a"))
+    total, n_acc = np.array(state["sum"], dtype=np.float64), np.array(state["n_accept"], dtype=np.int32)
+    B, R, F, wf = x.shape[1], root.shape[0], len(freq), int(weight_freq)
+    if total.shape != (2 * F * R + 1, B) or not 0 <= wf < F:
+        raise ValueError("sum must be [2 n_freq n_root + 1, n_walker] and weight_freq an index into freq")
+    cols = list(range(D)) if col is None else [int(c) for c in col]
+    live = [k for k in range(R) if exists is None or exists[k]]
+    pairs = {k: (int(root_col_in[k]), int(root_col_out[k])) for k in live}
+
+    def phases(p, fs):
+        out = {}
+        for pair in set(pairs.values()):
+            tau = p[pair[1]] - p[pair[0]]
+            out[pair] = table(tau, beta, fs, fermionic)
+        return out
+
+    xp, facp = x.copy(), fac.copy()
+    for d in range(D):
+        if (mask >> d) & 1:
+            y = np.asarray(u, dtype=np.float64)[:, d] * np.float64(G)
+            c = np.minimum(y.astype(np.int64), G - 1)
+            lo = grid[d, c]
+            wd = grid[d, c + 1] - lo
+            xp[cols[d]] = lo + (y - c.astype(np.float64)) * wd
+            facp[d] = np.float64(G) * wd
+    with np.errstate(all="ignore"):
+        rp = np.asarray(eval_roots(xp), dtype=np.float64) if live else np.zeros((R, B))
+        jp = facp[0].copy()
+        for d in range(1, D):
+            jp = jp * facp[d]
+        ph = phases(xp, [freq[wf]])
+        re, im, bad = None, None, np.zeros(B, dtype=bool)
+        for k in live:
+            bad |= ~np.isfinite(rp[k])
+            term = rp[k] if coef is None else np.float64(coef[k]) * rp[k]
+            s, c = ph[pairs[k]]
+            pr, pi = term * c[:, 0], term * s[:, 0]
+            re, im = (pr, pi) if re is None else (re + pr, im + pi)
+        if re is None:
+            re, im = np.zeros(B), np.zeros(B)
+        tre, tim = jp * re, jp * im
+        bad |= ~np.isfinite(tre) | ~np.isfinite(tim)
+        q0, q1 = tre * tre, tim * tim
+        q = q0 + q1
+        bad |= ~np.isfinite(q)
+        ap = np.where(bad, 0.0, np.sqrt(np.where(bad, 0.0, q)))
+        if flags & FDG_CHAIN_INIT:
+            acc = np.ones(B, dtype=bool)
+        else:
+            acc = np.asarray(u_acc, dtype=np.float64) * (a + gamma) < (ap + gamma)
+    x, fac, a = np.where(acc, xp, x), np.where(acc, facp, fac), np.where(acc, ap, a)
+    for k in live:
+        root[k] = np.where(acc, np.where(bad, 0.0, rp[k]), root[k])
+    n_acc = n_acc + acc.astype(np.int32)
+    if flags & FDG_CHAIN_MEASURE:
+        jac = fac[0].copy()
+        for d in range(1, D):
+            jac = jac * fac[d]
+        dd = 1.0 / (a + gamma)
+        ph = phases(x, list(freq))
+        for k in live:
+            w = (jac * root[k]) * dd
+            s, c = ph[pairs[k]]
+            for f in range(F):
+                o = 2 * (f * R + k)
+                total[o] = total[o] + w * c[:, f]
+                total[o + 1] = total[o + 1] + w * s[:, f]
+        total[2 * F * R] = total[2 * F * R] + dd
     return {"x": x, "fac": fac, "root": root, "a": a, "sum": total, "n_accept": n_acc, "xp": xp, "facp": facp, "accept": acc}
 
 

@@ -5,6 +5,11 @@
 // kernel here holds a per-lane array: the select kernel walks the root columns twice (fold, then select), the variables' factors
 // likewise, so n_root = 180 and n_dim = 64 cost loads, not registers.  Nothing here touches the kernels of fdg_binned.hip: the
 // sampler's arithmetic of one variable is restated below (chain_draw), the same operations in the same order, so the bits are its.
+//
+// The Matsubara-projected step (fdg_[mc_]chain_step_device_matsubara) reuses propose, the evaluation and reduce; its
+// select kernel fdg_chain_select_mz folds the roots with the phase of the weight frequency (a' = |jac' sum_k c_k r_k e^{i w tau_k}|)
+// and measures every root at every frequency.  Roots outside, frequencies inside, x = tau / beta once per root; the phase is
+// fdg_matsubara.h's, so a numpy restatement gives the same bits.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -14,6 +19,7 @@
 
 #define FDG_RUNTIME_TU 1
 #include "fdg_internal.h"
+#include "fdg_matsubara.h"
 
 using namespace fdg;
 
@@ -131,6 +137,107 @@ fdg_chain_select(const double *__restrict__ roots, long ld, long n, const uint32
   }
 }
 
+// fdg_chain_select with the Matsubara projection in the weight and in the measurement.  cin[j], cout[j] are the columns of xp / x
+// that hold the two times of live root j, mult[f] the multiplier of frequency f (matsubara_multiplier, formed on the host), wf the
+// frequency of the weight.  sum is [2 F R + 1][nw]: column 2 (f R + k) the real part of root k at frequency f, the next one the
+// imaginary part, the last one d.  Everything indexed by j or f is wave-uniform.
+__global__ void __launch_bounds__(256)
+fdg_chain_select_mz(const double *__restrict__ roots, long ld, long n, const uint32_t *__restrict__ kidx, const double *__restrict__ cf,
+                    uint32_t n_live, const uint32_t *__restrict__ cin, const uint32_t *__restrict__ cout, const double *__restrict__ mult,
+                    uint32_t F, uint32_t wf, double beta, const double *__restrict__ xp, long xpc, const double *__restrict__ facp,
+                    uint32_t n_col, uint32_t D, long nw, double gamma, uint64_t seed, uint64_t off, uint32_t flags, double *__restrict__ x,
+                    long xc, double *__restrict__ fac, double *__restrict__ root, double *__restrict__ a, double *__restrict__ sum, uint32_t R,
+                    int32_t *__restrict__ n_accept) {
+  const long b = blockIdx.x * 256L + threadIdx.x;
+  if (b >= n) return;
+  const bool init = (flags & FDG_CHAIN_INIT) != 0, meas = (flags & FDG_CHAIN_MEASURE) != 0;
+  // the fold: jac', (re', im') at the weight frequency, a'
+  double jp = 0.0;
+  for (uint32_t d = 0; d < D; ++d) {
+    const double f = facp[(size_t)d * (size_t)nw + (size_t)b];
+    jp = d ? jp * f : f;
+  }
+  const double mw = mult[wf];
+  double re = 0.0, im = 0.0;
+  bool bad = false;
+  for (uint32_t j = 0; j < n_live; ++j) {
+    const double r = roots[(size_t)kidx[j] * (size_t)ld + (size_t)b];
+    bad = bad || !std::isfinite(r);
+    const double tau = xp[(long)cout[j] * xpc + b] - xp[(long)cin[j] * xpc + b];
+    const double xt = tau / beta;
+    double sn, cs;
+    matsubara_phase_of(xt, mw, sn, cs);
+    const double term = cf ? cf[j] * r : r;
+    const double pr = term * cs, pi = term * sn;
+    re = j ? re + pr : pr;
+    im = j ? im + pi : pi;
+  }
+  const double tre = jp * re, tim = jp * im;
+  bad = bad || !std::isfinite(tre) || !std::isfinite(tim);
+  const double q0 = tre * tre, q1 = tim * tim;
+  const double q = q0 + q1;
+  bad = bad || !std::isfinite(q);
+  const double ap = bad ? 0.0 : sqrt(q);
+  // the accept rule
+  const double a0 = init ? 0.0 : a[b];
+  bool acc = true;
+  if (!init) {
+    const double u = fdg_philox_u53(off + (uint64_t)b, FDG_VEGAS_DIM_MAX, seed);
+    acc = u * (a0 + gamma) < (ap + gamma);
+  }
+  // the selection
+  double jac = jp;
+  if (acc) {
+    for (uint32_t c = 0; c < n_col; ++c) x[(long)c * xc + b] = xp[(long)c * xpc + b];
+    for (uint32_t d = 0; d < D; ++d) {
+      const size_t at = (size_t)d * (size_t)nw + (size_t)b;
+      fac[at] = facp[at];
+    }
+    a[b] = ap;
+    if (n_accept) n_accept[b] = n_accept[b] + 1;
+  } else if (meas) {
+    for (uint32_t d = 0; d < D; ++d) {
+      const double f = fac[(size_t)d * (size_t)nw + (size_t)b];
+      jac = d ? jac * f : f;
+    }
+  }
+  if (!acc && !meas) return;
+  // the second walk over the roots: select, and measure every frequency on the state after the selection (whose times are the
+  // proposal's after an acceptance: the same bits, read where they were not just written)
+  const double dd = 1.0 / ((acc ? ap : a0) + gamma);
+  const double *tp = acc ? xp : x;
+  const long tpc = acc ? xpc : xc;
+  for (uint32_t j = 0; j < n_live; ++j) {
+    const uint32_t k = kidx[j];
+    const size_t at = (size_t)k * (size_t)nw + (size_t)b;
+    double r;
+    if (acc) {
+      const double rp = roots[(size_t)k * (size_t)ld + (size_t)b];
+      r = bad ? 0.0 : rp;
+      root[at] = r;
+    } else {
+      r = root[at];
+    }
+    if (meas) {
+      const double jr = jac * r;
+      const double w = jr * dd;
+      const double tau = tp[(long)cout[j] * tpc + b] - tp[(long)cin[j] * tpc + b];
+      const double xt = tau / beta;
+      for (uint32_t f = 0; f < F; ++f) {
+        double sn, cs;
+        matsubara_phase_of(xt, mult[f], sn, cs);
+        const size_t o = (size_t)(2u * (f * R + k)) * (size_t)nw + (size_t)b;
+        sum[o] = sum[o] + w * cs;
+        sum[o + (size_t)nw] = sum[o + (size_t)nw] + w * sn;
+      }
+    }
+  }
+  if (meas) {
+    const size_t at = (size_t)(2u * F * R) * (size_t)nw + (size_t)b;
+    sum[at] = sum[at] + dd;
+  }
+}
+
 // out[c] += the sum over the walkers of column c's term (include/fdg.h: S, Q, X); one workgroup per output.
 __global__ void __launch_bounds__(256)
 fdg_chain_reduce(const double *__restrict__ sum, uint32_t R, long n, double *__restrict__ out) {
@@ -197,16 +304,34 @@ int check_chain(const fdg_graph *g, const ChainCall &c) {
   return FDG_OK;
 }
 
-// The body of both step calls (caller holds g->mu, stream bound): eval(c0, n, roots, ld) writes the roots of the proposals of walkers
+// The checks of the projected step calls on their descriptor, after check_chain.
+int check_chain_mz(const fdg_graph *g, const ChainCall &c, const fdg_chain_matsubara *mz) {
+  if (!mz) { set_error("null Matsubara descriptor"); return FDG_E_INVALID; }
+  if (!mz->freq || !mz->root_col_in || !mz->root_col_out) { set_error("null array in the Matsubara descriptor"); return FDG_E_INVALID; }
+  if (mz->n_freq == 0) { set_error("n_freq == 0"); return FDG_E_INVALID; }
+  if (mz->n_freq > FDG_MATSUBARA_FREQ_MAX) { set_error("n_freq > FDG_MATSUBARA_FREQ_MAX"); return FDG_E_UNSUPPORTED; }
+  if (mz->weight_freq >= mz->n_freq) { set_error("weight_freq >= n_freq"); return FDG_E_INVALID; }
+  if (!(std::isfinite(mz->beta) && mz->beta > 0.0)) { set_error("beta must be finite and > 0"); return FDG_E_INVALID; }
+  for (uint32_t k = 0; k < g->prog.R; ++k)
+    if (g->prog.root_slot[k] != FDG_NO_ROOT && (mz->root_col_in[k] >= c.n_col || mz->root_col_out[k] >= c.n_col)) {
+      set_error("a time column of an existing root >= n_col"); return FDG_E_INVALID;
+    }
+  return FDG_OK;
+}
+
+// The body of all step calls (caller holds g->mu, stream bound): eval(c0, n, roots, ld) writes the roots of the proposals of walkers
 // c0 .. c0 + n - 1 column-major into roots.  The chunk is the accumulate calls' (FDG_ROOT_SCRATCH_MB); no result depends on it.
+// mz: the projected step (fdg_chain_select_mz); its multipliers and time columns lie behind the plain step's uploads.
 template <class Eval>
-int run_chain(fdg_graph *g, const ChainCall &c, Eval eval) {
+int run_chain(fdg_graph *g, const ChainCall &c, Eval eval, const fdg_chain_matsubara *mz) {
   const uint32_t R = g->prog.R;
   const hipStream_t st = (hipStream_t)c.stream;
   long Bc = std::max<long>(64, (long)((g->cfg.root_scratch_mb << 20) / (8ull * std::max<uint32_t>(R, 1u))) & ~63l);
   Bc = std::min<long>(Bc, (long)((c.B + 63) & ~(int64_t)63));
   const size_t root_bytes = page_up((size_t)Bc * std::max<uint32_t>(R, 1u) * sizeof(double));
-  int rc = ensure_root_scratch(g, root_bytes + page_up((size_t)std::max<uint32_t>(R, 1u) * 12u));
+  const size_t plain_bytes = page_up((size_t)std::max<uint32_t>(R, 1u) * 12u);
+  const size_t mz_bytes = mz ? page_up((size_t)FDG_MATSUBARA_FREQ_MAX * sizeof(double) + (size_t)std::max<uint32_t>(R, 1u) * 8u) : 0;
+  int rc = ensure_root_scratch(g, root_bytes + plain_bytes + mz_bytes);
   if (rc) return rc;
   double *roots = (double *)g->d_ws2;
   // the roots that exist, ascending, and their factors: one small upload per call (pageable memory: staged before the call returns)
@@ -221,23 +346,44 @@ int run_chain(fdg_graph *g, const ChainCall &c, Eval eval) {
     HIP_TRY(hipMemcpyAsync(d_coef, hc.data(), n_live * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_kidx, hk.data(), n_live * sizeof(uint32_t), hipMemcpyHostToDevice, st));
   }
+  // the projected step: the multiplier of every frequency, then the two time columns of every root that exists
+  double *d_mult = (double *)((char *)g->d_ws2 + root_bytes + plain_bytes);
+  uint32_t *d_cin = (uint32_t *)(d_mult + FDG_MATSUBARA_FREQ_MAX), *d_cout = d_cin + std::max<uint32_t>(R, 1u);
+  if (mz) {
+    std::vector<double> hm(mz->n_freq);
+    std::vector<uint32_t> hin, hout;
+    for (uint32_t f = 0; f < mz->n_freq; ++f) hm[f] = matsubara_multiplier(mz->freq[f], mz->fermionic);
+    for (uint32_t k : hk) { hin.push_back(mz->root_col_in[k]); hout.push_back(mz->root_col_out[k]); }
+    HIP_TRY(hipMemcpyAsync(d_mult, hm.data(), hm.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    if (n_live) {
+      HIP_TRY(hipMemcpyAsync(d_cin, hin.data(), n_live * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(d_cout, hout.data(), n_live * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    }
+  }
   for (long c0 = 0; c0 < (long)c.B; c0 += Bc) {
     const long n = std::min<long>(Bc, (long)c.B - c0);
     if (n_live) {
       rc = eval(c0, n, roots, Bc);
       if (rc) return rc;
     }
-    hipLaunchKernelGGL(fdg_chain_select, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, roots, Bc, n, d_kidx, c.coef ? d_coef : nullptr,
-                       n_live, c.d_xp + c0, (long)c.xpc, c.d_facp + c0, c.n_col, c.n_dim, (long)c.B, c.gamma, c.seed,
-                       c.offset + (uint64_t)c0, (uint32_t)c.flags, c.d_x + c0, (long)c.xc, c.d_fac + c0, c.d_root + c0, c.d_a + c0,
-                       c.d_sum ? c.d_sum + c0 : nullptr, R, c.d_n_accept ? c.d_n_accept + c0 : nullptr);
+    if (mz)
+      hipLaunchKernelGGL(fdg_chain_select_mz, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, roots, Bc, n, d_kidx,
+                         c.coef ? d_coef : nullptr, n_live, d_cin, d_cout, d_mult, mz->n_freq, mz->weight_freq, mz->beta, c.d_xp + c0,
+                         (long)c.xpc, c.d_facp + c0, c.n_col, c.n_dim, (long)c.B, c.gamma, c.seed, c.offset + (uint64_t)c0,
+                         (uint32_t)c.flags, c.d_x + c0, (long)c.xc, c.d_fac + c0, c.d_root + c0, c.d_a + c0,
+                         c.d_sum ? c.d_sum + c0 : nullptr, R, c.d_n_accept ? c.d_n_accept + c0 : nullptr);
+    else
+      hipLaunchKernelGGL(fdg_chain_select, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, roots, Bc, n, d_kidx, c.coef ? d_coef : nullptr,
+                         n_live, c.d_xp + c0, (long)c.xpc, c.d_facp + c0, c.n_col, c.n_dim, (long)c.B, c.gamma, c.seed,
+                         c.offset + (uint64_t)c0, (uint32_t)c.flags, c.d_x + c0, (long)c.xc, c.d_fac + c0, c.d_root + c0, c.d_a + c0,
+                         c.d_sum ? c.d_sum + c0 : nullptr, R, c.d_n_accept ? c.d_n_accept + c0 : nullptr);
     HIP_TRY(hipGetLastError());
   }
   return FDG_OK;
 }
 
 template <class Check, class Eval>
-int chain_step(fdg_graph *g, const ChainCall &c, Check locked_check, Eval eval) {
+int chain_step(fdg_graph *g, const ChainCall &c, Check locked_check, Eval eval, const fdg_chain_matsubara *mz = nullptr) {
   std::lock_guard<std::mutex> lk(g->mu);
   fdg::KnobScope knob_scope(&g->knobs);
   int rc = locked_check();
@@ -247,7 +393,7 @@ int chain_step(fdg_graph *g, const ChainCall &c, Check locked_check, Eval eval) 
   if (rc) return rc;
   rc = fdg_bind_stream_ws(g, c.stream);
   if (rc) return rc;
-  return run_chain(g, c, eval);
+  return run_chain(g, c, eval, mz);
 }
 
 }  // namespace
@@ -313,6 +459,52 @@ int fdg_mc_chain_step_device(fdg_graph *g, const double *d_xp, int64_t xp_col_st
         const double *K = d_xp + c0, *T = d_xp + (int64_t)(g->lt_hdr[2] * g->lt_hdr[3]) * xp_col_stride + c0;
         return fdg_mc_run_locked(g, 0, K, 1, xp_col_stride, T, 1, xp_col_stride, kF, beta, lambda, roots, 1, ld, nullptr, nullptr, n, st);
       });
+}
+
+int fdg_chain_step_device_matsubara(fdg_graph *g, const double *d_xp, int64_t xp_col_stride, const double *d_facp, uint32_t n_col,
+                                    uint32_t n_dim, const double *coef, double gamma, uint64_t seed, uint64_t sample_offset, unsigned flags,
+                                    double *d_x, int64_t x_col_stride, double *d_fac, double *d_root, double *d_a, double *d_sum,
+                                    int32_t *d_n_accept, const fdg_chain_matsubara *mz, int64_t B, void *stream) {
+  const ChainCall c{d_xp, xp_col_stride, d_facp, n_col, n_dim, coef, gamma, seed, sample_offset, flags, d_x, x_col_stride, d_fac,
+                    d_root, d_a, d_sum, d_n_accept, B, stream};
+  int rc = check_chain(g, c);
+  if (rc) return rc;
+  if (n_col != g->prog.L) { set_error("n_col is not the graph's number of leaves"); return FDG_E_INVALID; }
+  rc = check_chain_mz(g, c, mz);
+  if (rc) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  return chain_step(
+      g, c, [] { return FDG_OK; },
+      [&](long c0, long n, double *roots, long ld) {
+        return fdg_run_locked(g, 0, d_xp + c0, 1, xp_col_stride, roots, 1, ld, nullptr, nullptr, n, st, 0, 0);
+      },
+      mz);
+}
+
+int fdg_mc_chain_step_device_matsubara(fdg_graph *g, const double *d_xp, int64_t xp_col_stride, double kF, double beta, double lambda,
+                                       const double *d_facp, uint32_t n_col, uint32_t n_dim, const double *coef, double gamma,
+                                       uint64_t seed, uint64_t sample_offset, unsigned flags, double *d_x, int64_t x_col_stride,
+                                       double *d_fac, double *d_root, double *d_a, double *d_sum, int32_t *d_n_accept,
+                                       const fdg_chain_matsubara *mz, int64_t B, void *stream) {
+  const ChainCall c{d_xp, xp_col_stride, d_facp, n_col, n_dim, coef, gamma, seed, sample_offset, flags, d_x, x_col_stride, d_fac,
+                    d_root, d_a, d_sum, d_n_accept, B, stream};
+  int rc = check_chain(g, c);
+  if (rc) return rc;
+  rc = check_chain_mz(g, c, mz);
+  if (rc) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  return chain_step(
+      g, c,
+      [&] {
+        if (g->mc_route == 0) { set_error("fdg_graph_specialize_fused has not been called on this handle"); return FDG_E_INVALID; }
+        if (n_col != g->lt_hdr[2] * g->lt_hdr[3] + g->lt_hdr[4]) { set_error("n_col is not the tables' n_loop * dim + n_tau"); return FDG_E_INVALID; }
+        return FDG_OK;
+      },
+      [&](long c0, long n, double *roots, long ld) {
+        const double *K = d_xp + c0, *T = d_xp + (int64_t)(g->lt_hdr[2] * g->lt_hdr[3]) * xp_col_stride + c0;
+        return fdg_mc_run_locked(g, 0, K, 1, xp_col_stride, T, 1, xp_col_stride, kF, beta, lambda, roots, 1, ld, nullptr, nullptr, n, st);
+      },
+      mz);
 }
 
 int fdg_chain_reduce_device(const double *d_sum, uint32_t n_root, int64_t B, double *d_out, void *stream) {

@@ -861,6 +861,52 @@ function mc_chain_step_device!(f::GraphFunc, d_xp::Ptr{Float64}, d_facp::Ptr{Flo
         sample_offset, flags, d_x, x_col_stride, d_fac, d_root, d_a, d_sum, d_n_accept, B, stream))
     return nothing
 end
+# The same two steps with the Matsubara projection inside the chain (fdg_[mc_]chain_step_device_matsubara): the weight is
+# |jac sum_k c_k r_k e^{i omega tau_k}| at freq[weight_freq] (1-based here), and every root is measured at every frequency into d_sum,
+# B x (2 F R + 1): column 2 ((f - 1) R + k - 1) + 1 the real part, the next one the imaginary part, the last one 1 / (a + gamma).
+# root_col_in / root_col_out: the 1-based columns of d_x that hold the two times of every root.
+struct _FdgChainMatsubara
+    n_freq::UInt32
+    fermionic::Int32
+    freq::Ptr{Int32}
+    weight_freq::UInt32
+    root_col_in::Ptr{UInt32}
+    root_col_out::Ptr{UInt32}
+    beta::Float64
+end
+function chain_step_device_matsubara!(f::GraphFunc, d_xp::Ptr{Float64}, d_facp::Ptr{Float64}, d_x::Ptr{Float64}, d_fac::Ptr{Float64},
+    d_root::Ptr{Float64}, d_a::Ptr{Float64}, d_sum::Ptr{Float64}, n_col::Integer, n_dim::Integer, gamma::Float64, freq::Vector{Int},
+    root_col_in::Vector{Int}, root_col_out::Vector{Int}, B::Integer; beta::Float64, fermionic::Bool=true, weight_freq::Integer=1,
+    flags::Integer=0, coef::Union{Nothing,Vector{Float64}}=nothing, seed::Integer=0, sample_offset::Integer=0,
+    d_n_accept::Ptr{Int32}=Ptr{Int32}(C_NULL), x_col_stride::Integer=B, xp_col_stride::Integer=B, stream::Ptr{Cvoid}=C_NULL)
+    fr, cin, cout = Int32.(freq), UInt32.(root_col_in .- 1), UInt32.(root_col_out .- 1)
+    GC.@preserve fr cin cout begin
+        mz = _FdgChainMatsubara(length(fr), fermionic ? 1 : 0, pointer(fr), weight_freq - 1, pointer(cin), pointer(cout), beta)
+        _fdg_check(ccall((:fdg_chain_step_device_matsubara, _libfdg), Cint,
+            (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, UInt32, UInt32, Ptr{Float64}, Float64, UInt64, UInt64, Cuint, Ptr{Float64}, Int64,
+             Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ref{_FdgChainMatsubara}, Int64, Ptr{Cvoid}),
+            f.handle, d_xp, xp_col_stride, d_facp, n_col, n_dim, coef === nothing ? C_NULL : coef, gamma, seed, sample_offset, flags, d_x,
+            x_col_stride, d_fac, d_root, d_a, d_sum, d_n_accept, mz, B, stream))
+    end
+    return nothing
+end
+function mc_chain_step_device_matsubara!(f::GraphFunc, d_xp::Ptr{Float64}, d_facp::Ptr{Float64}, d_x::Ptr{Float64}, d_fac::Ptr{Float64},
+    d_root::Ptr{Float64}, d_a::Ptr{Float64}, d_sum::Ptr{Float64}, n_col::Integer, n_dim::Integer, gamma::Float64, freq::Vector{Int},
+    root_col_in::Vector{Int}, root_col_out::Vector{Int}, B::Integer; kF::Float64, beta::Float64, lambda::Float64, fermionic::Bool=true,
+    weight_freq::Integer=1, flags::Integer=0, coef::Union{Nothing,Vector{Float64}}=nothing, seed::Integer=0, sample_offset::Integer=0,
+    d_n_accept::Ptr{Int32}=Ptr{Int32}(C_NULL), x_col_stride::Integer=B, xp_col_stride::Integer=B, stream::Ptr{Cvoid}=C_NULL)
+    fr, cin, cout = Int32.(freq), UInt32.(root_col_in .- 1), UInt32.(root_col_out .- 1)
+    GC.@preserve fr cin cout begin
+        mz = _FdgChainMatsubara(length(fr), fermionic ? 1 : 0, pointer(fr), weight_freq - 1, pointer(cin), pointer(cout), beta)
+        _fdg_check(ccall((:fdg_mc_chain_step_device_matsubara, _libfdg), Cint,
+            (Ptr{Cvoid}, Ptr{Float64}, Int64, Float64, Float64, Float64, Ptr{Float64}, UInt32, UInt32, Ptr{Float64}, Float64, UInt64, UInt64,
+             Cuint, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ref{_FdgChainMatsubara}, Int64,
+             Ptr{Cvoid}),
+            f.handle, d_xp, xp_col_stride, kF, beta, lambda, d_facp, n_col, n_dim, coef === nothing ? C_NULL : coef, gamma, seed,
+            sample_offset, flags, d_x, x_col_stride, d_fac, d_root, d_a, d_sum, d_n_accept, mz, B, stream))
+    end
+    return nothing
+end
 # d_out (3 R + 2, added to) = the sums over the walkers S_c, Q_c = sum A_c^2 (R + 1 each) and X_k = sum A_k A_{R+1} (R) of d_sum.
 function chain_reduce_device!(d_out::Ptr{Float64}, d_sum::Ptr{Float64}, n_root::Integer, B::Integer; stream::Ptr{Cvoid}=C_NULL)
     _fdg_check(ccall((:fdg_chain_reduce_device, _libfdg), Cint, (Ptr{Float64}, UInt32, Int64, Ptr{Float64}, Ptr{Cvoid}),
@@ -868,6 +914,7 @@ function chain_reduce_device!(d_out::Ptr{Float64}, d_sum::Ptr{Float64}, n_root::
     return nothing
 end
 export chain_propose_device!, chain_step_device!, mc_chain_step_device!, chain_reduce_device!, FDG_CHAIN_INIT, FDG_CHAIN_MEASURE
+export chain_step_device_matsubara!, mc_chain_step_device_matsubara!
 
 # ---- multi-GPU: one Julia process per GPU, ONE reduction of the accumulated observable ------------ #
 # (include/fdg.h, "multi-GPU").  Rank 0 calls `comm_unique_id()` and ships the 128 bytes to the other

@@ -40,7 +40,9 @@ Markov-chain sampling (``chain_integrate``, ``chain_estimate``, ``ChainResult``;
 fdg_chain_reduce_device): a Metropolis chain whose proposals are fresh draws through the map for a subset of the variables, one
 walker per lane -- what ``integrate(...; solver=:mcmc)`` of the reference's test/hubbard.jl:85 asks MCIntegration for -- for weights
 that no separable map follows.  The stationary density ``|s| + gamma q`` carries the map's own density ``q``, whose known integral
-normalises the result; the error bar comes from the spread across the independent walkers.
+normalises the result; the error bar comes from the spread across the independent walkers.  With ``matsubara`` the projection
+runs inside the chain (fdg_[mc_]chain_step_device_matsubara): the weight is the modulus of the projected sum at one frequency, and
+every root is measured at every frequency.
 """
 from __future__ import annotations
 
@@ -826,12 +828,14 @@ def vegas_integrate_binned(func_or_handle, tables, lo, hi, col, dmap: DiscreteMa
 # ---- Markov-chain sampling on the VEGAS map (include/fdg.h: fdg_chain_propose_device, fdg_[mc_]chain_step_device, fdg_chain_reduce_device) ---- #
 @dataclass
 class ChainResult:
-    mean: np.ndarray                 # [R] S_k / S_R: the integral of every root
-    stderr: np.ndarray               # [R] from the spread across the walkers (:func:`chain_estimate`)
+    mean: np.ndarray                 # [R] S_k / S_R: the integral of every root; with ``matsubara`` complex [n_freq, R]
+    stderr: np.ndarray               # [R] from the spread across the walkers (:func:`chain_estimate`); with ``matsubara`` complex
+                                     # [n_freq, R]: the error of the real part in the real part, of the imaginary part in the imaginary
     acceptance: float                # mean over the walkers of n_accept / n_step
     gamma: float                     # the weight of the map's own density in the stationary density
     map: Optional[VegasMap] = None   # the map the chain drew its proposals through
-    S: Optional[np.ndarray] = None   # [R + 1] sum over the walkers of their sums A_c(b); A_R is the normalisation
+    S: Optional[np.ndarray] = None   # [R + 1] sum over the walkers of their sums A_c(b); A_R is the normalisation.  With ``matsubara``
+                                     # S, Q, X are raw over the 2 n_freq R columns 2 (f R + k) (real part), + 1 (imaginary part)
     Q: Optional[np.ndarray] = None   # [R + 1] sum over the walkers of A_c(b)**2
     X: Optional[np.ndarray] = None   # [R] sum over the walkers of A_k(b) A_R(b)
 
@@ -859,13 +863,22 @@ def chain_estimate(S, Q, X, n_walker: int):
     return mean, np.sqrt(np.maximum(var, 0.0))
 
 
+def chain_complex(v, n_freq: int, n_root: int) -> np.ndarray:
+    """The complex ``[n_freq, R]`` array of the ``2 n_freq R`` figures that the projected chain keeps per column ``2 (f R + k)`` (real
+    part) and ``2 (f R + k) + 1`` (imaginary part): means, or error bars with each part's own error in that part."""
+    v = np.asarray(v, dtype=np.float64).reshape(int(n_freq), int(n_root), 2)
+    out = np.empty(v.shape[:2], dtype=np.complex128)
+    out.real, out.imag = v[..., 0], v[..., 1]               # (not re + 1j * im: a nan of one part would spread to the other)
+    return out
+
+
 def chain_moves(n_dim: int) -> List[int]:
     """The default moves of :func:`chain_integrate`: the mask of all variables, then one mask per variable."""
     D = int(n_dim)
     return [(1 << D) - 1] + [1 << d for d in range(D)]
 
 
-_CHAIN_EXCLUDED = ("polar", "groups", "dmap", "matsubara", "observables", "freq_observables", "strat")
+_CHAIN_EXCLUDED = ("polar", "groups", "dmap", "observables", "freq_observables", "strat")
 _CHAIN_TRAIN_KEY = 0x632BE59BD9B4E019       # added to ``seed`` for the map's training: the chain's counters are used once
 
 
@@ -873,7 +886,8 @@ def chain_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: 
                     n_step: int, n_therm: int, moves: Optional[Sequence[int]] = None, gamma_rel: float = 1.0, gamma: Optional[float] = None,
                     n_warm: int = 5, n_warm_sample: Optional[int] = None, n_grid: int = 64, alpha: float = 0.5, seed: int = 0, fixed=None,
                     coef=None, vmap: Optional[VegasMap] = None, specialize_fused: bool = True, n_total: Optional[int] = None,
-                    shard_start: int = 0, reduce: Optional[Callable] = None, device="cuda", **excluded) -> ChainResult:
+                    shard_start: int = 0, reduce: Optional[Callable] = None, device="cuda",
+                    matsubara: Optional[MatsubaraProjection] = None, weight_freq: int = 0, **excluded) -> ChainResult:
     """Integrates the roots of a graph over the box ``[lo, hi]`` with a Metropolis chain whose proposals are fresh draws through the
     VEGAS map for a subset of the variables (MCIntegration's ``:vegasmc``; no counterpart in the reference: the caller's side of
     test/hubbard.jl:85).  ``n_walker`` independent walkers, one per lane; the stationary density is ``|s| + gamma q`` with ``s`` the
@@ -896,10 +910,18 @@ def chain_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: 
     Sharding is :func:`vegas_integrate`'s: a rank passes its range as ``shard_start`` / ``n_walker`` and the whole as ``n_total``;
     a walker's chain does not depend on the split.
 
-    Out of scope here, refused with ValueError: ``polar``, ``groups``, a discrete variable (``dmap``), ``matsubara``,
-    ``observables``, ``freq_observables`` and ``strat`` together with the chain.  Not built either: training the map from the
-    chain's own samples, local (shift) proposals, reweighting between orders.  The target these lead to is ``Sigma(i omega_0)`` of
-    the Hubbard atom in the reference's test/hubbard.jl, which the chain, ``matsubara`` and ``groups`` together would reach."""
+    ``matsubara`` (a :class:`MatsubaraProjection`) projects the roots onto its frequencies INSIDE the chain
+    (fdg_[mc_]chain_step_device_matsubara): the walkers' weight is ``a = |jac sum_k c_k r_k e^{i omega tau_k}|`` at the frequency
+    ``freq[weight_freq]``, and every root is measured at every frequency, so ``mean`` and ``stderr`` are complex ``[n_freq, R]``
+    (the errors of the two parts kept apart, as ``vegas_integrate(matsubara=...)`` reports them) and ``S``, ``Q``, ``X`` the raw sums
+    over the ``2 n_freq R`` columns.  The projection's 1-based time label ``i`` names column ``t0 + i - 1`` of ``x``: ``t0 = n_loop *
+    dim`` in the Monte-Carlo form, and ``t0 = 0`` in the leaf form, where a "time" is a leaf column (of use to tests).  The warm-up
+    still trains the map on the unprojected ``s``, and ``gamma = gamma_rel * mean(a)`` is taken of the projected ``a``.
+
+    Out of scope here, refused with ValueError: ``polar``, ``groups``, a discrete variable (``dmap``), ``observables``,
+    ``freq_observables`` and ``strat`` together with the chain.  Not built either: training the map from the chain's own samples,
+    local (shift) proposals, reweighting between orders.  The target these lead to is ``Sigma(i omega_0)`` of the Hubbard atom in
+    the reference's test/hubbard.jl: its single-order case is what ``matsubara`` reaches; several orders at once need ``groups``."""
     import torch
     for name, value in excluded.items():
         if name not in _CHAIN_EXCLUDED:
@@ -916,6 +938,31 @@ def chain_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: 
     col = [int(c) for c in col]
     if len(set(col)) != len(col) or not all(0 <= c < n_col for c in col):
         raise ValueError(f"col must name distinct columns in [0, {n_col})")
+    F, desc = 0, None
+    if matsubara is not None:
+        if not isinstance(matsubara, MatsubaraProjection):
+            raise ValueError("matsubara must be a MatsubaraProjection")
+        F = len(matsubara.freq)
+        t0, n_time = (0, n_col) if tables is None else (int(tables.n_loop) * int(tables.dim), int(tables.n_tau))
+        if not 1 <= F <= capi.FDG_MATSUBARA_FREQ_MAX:
+            raise ValueError(f"matsubara needs 1 .. {capi.FDG_MATSUBARA_FREQ_MAX} frequencies")
+        if not 0 <= int(weight_freq) < F:
+            raise ValueError("weight_freq must be an index into matsubara.freq")
+        if len(matsubara.root_tau_in) != R or len(matsubara.root_tau_out) != R:
+            raise ValueError(f"matsubara must name the two times of each of the {R} roots")
+        if not (math.isfinite(beta) and beta > 0.0):
+            raise ValueError("beta must be finite and > 0")
+        from .nodetable import FDG_NO_ROOT
+        live = [int(v) != FDG_NO_ROOT for v in handle.table.root_slot]
+        cin, cout = [], []
+        for k in range(R):
+            i, o = int(matsubara.root_tau_in[k]), int(matsubara.root_tau_out[k])
+            if live[k] and not (1 <= i <= n_time and 1 <= o <= n_time):
+                raise ValueError(f"matsubara: a time label of root {k} lies outside [1, {n_time}]")
+            cin.append(t0 + i - 1 if live[k] else 0)
+            cout.append(t0 + o - 1 if live[k] else 0)
+        desc, _keep = capi.make_chain_matsubara(matsubara.freq, matsubara.fermionic, int(weight_freq), cin, cout, beta)
+    C = 2 * F * R if F else R                               # the columns of the walkers' sums before the normalisation's
     B, n_step, n_therm, n_warm = int(n_walker), int(n_step), int(n_therm), int(n_warm)
     N = B if n_total is None else int(n_total)
     if B < 1 or n_step < 1 or not 0 <= n_therm < n_step or n_warm < 0 or not 0 <= int(shard_start) <= N - B:
@@ -955,7 +1002,7 @@ def chain_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: 
         xp = torch.empty_like(x)
         fac, facp = torch.ones((D, B), **f64), torch.empty((D, B), **f64)
         root, a = torch.zeros((R, B), **f64), torch.zeros(B, **f64)
-        total = torch.zeros((R + 1, B), **f64)
+        total = torch.zeros((C + 1, B), **f64)
         n_acc = torch.zeros(B, dtype=torch.int32, device=device)
 
         def step(mask, off, g, flags):
@@ -963,7 +1010,13 @@ def chain_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: 
                                       xp.data_ptr(), B, facp.data_ptr(), B, st)
             tail = (facp.data_ptr(), n_col, D, coef, g, seed, off, flags, x.data_ptr(), B, fac.data_ptr(), root.data_ptr(), a.data_ptr(),
                     total.data_ptr(), n_acc.data_ptr(), B, st)
-            if tables is None:
+            if desc is not None:
+                tail = tail[:-2] + (desc,) + tail[-2:]
+                if tables is None:
+                    handle.chain_step_device_matsubara(xp.data_ptr(), B, *tail)
+                else:
+                    handle.mc_chain_step_device_matsubara(xp.data_ptr(), B, kF, beta, lam, *tail)
+            elif tables is None:
                 handle.chain_step_device(xp.data_ptr(), B, *tail)
             else:
                 handle.mc_chain_step_device(xp.data_ptr(), B, kF, beta, lam, *tail)
@@ -980,13 +1033,15 @@ def chain_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: 
         for t in range(n_step):
             step(moves[t % len(moves)], (t + 1) * N + int(shard_start), float(gamma),
                  capi.FDG_CHAIN_MEASURE if t >= n_therm else 0)
-        out = torch.zeros(3 * R + 2, **f64)
-        capi.chain_reduce_device(total.data_ptr(), R, B, out.data_ptr(), st)
+        out = torch.zeros(3 * C + 2, **f64)
+        capi.chain_reduce_device(total.data_ptr(), C, B, out.data_ptr(), st)
         acc_sum = n_acc.sum(dtype=torch.float64).reshape(1)
         if reduce is not None:
             reduce(out)
             reduce(acc_sum)
         h = out.cpu().numpy()
-    S, Q, X = h[:R + 1].copy(), h[R + 1:2 * R + 2].copy(), h[2 * R + 2:].copy()
+    S, Q, X = h[:C + 1].copy(), h[C + 1:2 * C + 2].copy(), h[2 * C + 2:].copy()
     mean, err = chain_estimate(S, Q, X, N)                # (a root that does not exist has sums of 0: mean 0, stderr 0)
+    if F:
+        mean, err = chain_complex(mean, F, R), chain_complex(err, F, R)
     return ChainResult(mean, err, float(acc_sum.item()) / (N * n_step), float(gamma), vmap, S, Q, X)

@@ -1187,6 +1187,67 @@ int fdg_mc_chain_step_device(fdg_graph *g, const double *d_xp, int64_t xp_col_st
                              double *d_a, double *d_sum, int32_t *d_n_accept, int64_t n_walker, void *stream);
 int fdg_chain_reduce_device(const double *d_sum, uint32_t n_root, int64_t n_walker, double *d_out, void *stream);
 
+/* ---- Markov chain with a Matsubara-projected weight and measurement ----------------------------------------------------------------------
+ * The integrand of the chain's own target, Sigma(i omega_n) of test/hubbard.jl, is complex:
+ *     w = sum_k c_k r_k e^{i omega (T[out_k] - T[in_k])}
+ * The chain walks on |w| at ONE frequency (weight_freq) and measures every root at every frequency of the descriptor.  The phase has to
+ * be part of the weight: a chain on the unprojected |s| with the phases multiplied in afterwards is another, worse estimator, and none
+ * at all where the unprojected sum cancels.  MCIntegration is not part of the reference checkout: no counterpart in the reference; the
+ * caller's side of test/hubbard.jl:85 with the measure of test/ver4.jl:193.
+ *
+ * fdg_chain_propose_device and fdg_chain_reduce_device serve as they are, and the state (x, fac, root, a) keeps its layout; only d_sum
+ * grows.  Per walker, every line one rounded fp64 operation (no FMA), in this order:
+ *
+ * The phase of root k at frequency f for a point p (the proposal xp, or the state x):
+ *     tau = p[root_col_out[k]] - p[root_col_in[k]];   x = tau / beta
+ *     (s, c) = the phase of fdg_matsubara_phase from x on, with the multiplier of (freq[f], fermionic)      (csrc/fdg_matsubara.h)
+ * The weight of a proposal, over the roots j that exist in ascending order, (s_j, c_j) at weight_freq from the proposal's own times:
+ *     term = coef ? coef_j * r_j : r_j;   pr = term * c_j;   pi = term * s_j
+ *     re = re + pr;   im = im + pi                   (left folds; the first term is assigned, not added to 0; no root: 0.0)
+ *     tre = jac' * re;   tim = jac' * im
+ *     q   = tre * tre + tim * tim;   a' = sqrt(q)    (the two squares, their sum and the root each rounded once; fp64 sqrt is
+ *                                                     correctly rounded on host and device)
+ * A proposal at which an existing root, tre, tim or q is not finite counts as f = 0: its roots are taken as 0.0 and a' = 0, selected
+ * and never multiplied.  (q is in the list because a finite tre or tim above 1.3e154 squares to inf: a walker with a = inf would be
+ * accepted and never leave.  The plain step's a = |t| has no such range.)
+ * The accept rule, FDG_CHAIN_INIT, n_accept and the selection of x, fac, root, a are the plain step's, on the same Philox counter.
+ * FDG_CHAIN_MEASURE, on the state AFTER the selection, with R = n_root and F = n_freq:
+ *     d = 1 / (a + gamma)
+ *     for every root k that exists:   w = (jac * r_k) * d;   for every f, (s, c) from the state's times:
+ *         sum[2 (f R + k)][b]     += w * c
+ *         sum[2 (f R + k) + 1][b] += w * s
+ *     sum[2 F R][b] += d
+ * d_sum is [2 F R + 1][n_walker]; fdg_chain_reduce_device(d_sum, 2 F R, ..) reduces it, one ratio per (frequency, root, component).
+ * The columns of a root that does not exist are never written, in root and in sum; its time columns are not read and may be anything.
+ * The times are columns of x that the map draws or the caller fixes: they are taken as finite.  With fermionic = 0 and freq = {0} the
+ * phase is exactly (0, 1) and the state is the plain step's bit for bit (wherever tre * tre neither overflows nor underflows: 1e-154 < |tre| < 1.3e154).
+ *
+ * The Metropolis ratio stays (a' + gamma) / (a + gamma): the stationary density is |w(x)| + gamma q(x) with the same q, and the
+ * argument of the plain step needs of the weight only that it is a non-negative function of the point.
+ *
+ * The result is a function of the arguments only, as for the plain step (FDG_ROOT_SCRATCH_MB, launch shape, shards).
+ * FDG_E_INVALID: everything the plain step refuses; a NULL descriptor, freq, root_col_in or root_col_out; n_freq == 0;
+ * weight_freq >= n_freq; beta not finite or <= 0; a time column >= n_col of a root that exists.  FDG_E_UNSUPPORTED: the plain step's
+ * case, n_freq > FDG_MATSUBARA_FREQ_MAX.  All before any device work. */
+typedef struct fdg_chain_matsubara {
+  uint32_t n_freq;              /* 1 .. FDG_MATSUBARA_FREQ_MAX */
+  int32_t fermionic;            /* != 0: omega_n = (2n+1) pi / beta;  0: 2n pi / beta */
+  const int32_t *freq;          /* HOST [n_freq]: the n of every frequency */
+  uint32_t weight_freq;         /* index into freq: the frequency whose projected sum is the chain's weight */
+  const uint32_t *root_col_in;  /* HOST [n_root]: 0-based column of x / xp that holds t_in of root k */
+  const uint32_t *root_col_out; /* HOST [n_root] */
+  double beta;                  /* > 0 */
+} fdg_chain_matsubara;
+int fdg_chain_step_device_matsubara(fdg_graph *g, const double *d_xp, int64_t xp_col_stride, const double *d_facp, uint32_t n_col,
+                                    uint32_t n_dim, const double *coef, double gamma, uint64_t seed, uint64_t sample_offset,
+                                    unsigned flags, double *d_x, int64_t x_col_stride, double *d_fac, double *d_root, double *d_a,
+                                    double *d_sum, int32_t *d_n_accept, const fdg_chain_matsubara *mz, int64_t n_walker, void *stream);
+int fdg_mc_chain_step_device_matsubara(fdg_graph *g, const double *d_xp, int64_t xp_col_stride, double kF, double beta, double lambda,
+                                       const double *d_facp, uint32_t n_col, uint32_t n_dim, const double *coef, double gamma,
+                                       uint64_t seed, uint64_t sample_offset, unsigned flags, double *d_x, int64_t x_col_stride,
+                                       double *d_fac, double *d_root, double *d_a, double *d_sum, int32_t *d_n_accept,
+                                       const fdg_chain_matsubara *mz, int64_t n_walker, void *stream);
+
 /* Device workspace control: the interpreter keeps per-sample overflow slots in
  * an HBM panel owned by the handle; it is sized on first use for the number of
  * resident waves.  This releases it (and any loaded module). */
