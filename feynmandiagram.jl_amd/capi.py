@@ -56,6 +56,7 @@ EXPORTS = [
     "fdg_strat_allocate_cols",
     "fdg_chain_propose_device", "fdg_chain_step_device", "fdg_mc_chain_step_device", "fdg_chain_reduce_device",
     "fdg_chain_step_device_matsubara", "fdg_mc_chain_step_device_matsubara",
+    "fdg_chain_step_device_grouped", "fdg_mc_chain_step_device_grouped",
 ]
 FDG_BIN_MAX = 16384     # fdg_accumulate_device_binned: largest n_bin
 FDG_VEGAS_DIM_MAX, FDG_VEGAS_GRID_MAX = 64, 1024     # the VEGAS map: most variables, most cells per variable
@@ -126,6 +127,11 @@ class ChainMatsubara(C.Structure):
     """fdg_chain_matsubara (include/fdg.h)"""
     _fields_ = [("n_freq", C.c_uint32), ("fermionic", C.c_int32), ("freq", C.c_void_p), ("weight_freq", C.c_uint32),
                 ("root_col_in", C.c_void_p), ("root_col_out", C.c_void_p), ("beta", C.c_double)]
+
+
+class ChainGroups(C.Structure):
+    """fdg_chain_groups (include/fdg.h)"""
+    _fields_ = [("n_group", C.c_uint32), ("root_group", C.c_void_p), ("var_mask", C.c_void_p), ("reweight", C.c_void_p)]
 
 
 class WeightGroups(C.Structure):
@@ -313,6 +319,8 @@ def lib():
     L.fdg_chain_reduce_device.argtypes = [dp, u32, i64, dp, vp]
     L.fdg_chain_step_device_matsubara.argtypes = L.fdg_chain_step_device.argtypes[:-2] + [C.c_void_p, i64, vp]
     L.fdg_mc_chain_step_device_matsubara.argtypes = L.fdg_mc_chain_step_device.argtypes[:-2] + [C.c_void_p, i64, vp]
+    L.fdg_chain_step_device_grouped.argtypes = L.fdg_chain_step_device.argtypes[:-2] + [C.c_void_p, C.c_void_p, i64, vp]
+    L.fdg_mc_chain_step_device_grouped.argtypes = L.fdg_mc_chain_step_device.argtypes[:-2] + [C.c_void_p, C.c_void_p, i64, vp]
     L.fdg_powi.argtypes = [C.c_double, C.c_int32]
     L.fdg_powi.restype = C.c_double
     _lib = L
@@ -741,6 +749,28 @@ class GraphHandle:
                                                        d_x or None, xc, d_fac or None, d_root or None, d_a or None, d_sum or None,
                                                        d_n_accept or None, None if desc is None else C.addressof(desc), B, stream))
 
+    # the same steps with weight groups: groups = make_chain_groups(...)[0]; desc = make_chain_matsubara(...)[0] or None (no projection),
+    # d_sum as in the plain or the projected step (fdg.h, "Markov chain with weight groups and reweighting between orders")
+    def chain_step_device_grouped(self, d_xp: int, xpc: int, d_facp: int, n_col: int, n_dim: int, coef, gamma: float, seed: int,
+                                  sample_offset: int, flags: int, d_x: int, xc: int, d_fac: int, d_root: int, d_a: int, d_sum: int,
+                                  d_n_accept: int, desc, groups, B: int, stream: int = 0):
+        c = self._coef(coef)
+        check(lib().fdg_chain_step_device_grouped(self._h, d_xp or None, xpc, d_facp or None, n_col, n_dim,
+                                                  None if c is None else c.ctypes.data, gamma, seed, sample_offset, flags, d_x or None, xc,
+                                                  d_fac or None, d_root or None, d_a or None, d_sum or None, d_n_accept or None,
+                                                  None if desc is None else C.addressof(desc),
+                                                  None if groups is None else C.addressof(groups), B, stream))
+
+    def mc_chain_step_device_grouped(self, d_xp: int, xpc: int, kF, beta, lam, d_facp: int, n_col: int, n_dim: int, coef, gamma: float,
+                                     seed: int, sample_offset: int, flags: int, d_x: int, xc: int, d_fac: int, d_root: int, d_a: int,
+                                     d_sum: int, d_n_accept: int, desc, groups, B: int, stream: int = 0):
+        c = self._coef(coef)
+        check(lib().fdg_mc_chain_step_device_grouped(self._h, d_xp or None, xpc, kF, beta, lam, d_facp or None, n_col, n_dim,
+                                                     None if c is None else c.ctypes.data, gamma, seed, sample_offset, flags,
+                                                     d_x or None, xc, d_fac or None, d_root or None, d_a or None, d_sum or None,
+                                                     d_n_accept or None, None if desc is None else C.addressof(desc),
+                                                     None if groups is None else C.addressof(groups), B, stream))
+
     def _coef(self, coef):
         if coef is None:
             return None
@@ -984,6 +1014,128 @@ def chain_matsubara_reference(grid, col, state, mask: int, u, u_acc, gamma: floa
                 total[o] = total[o] + w * c[:, f]
                 total[o + 1] = total[o + 1] + w * s[:, f]
         total[2 * F * R] = total[2 * F * R] + dd
+    return {"x": x, "fac": fac, "root": root, "a": a, "sum": total, "n_accept": n_acc, "xp": xp, "facp": facp, "accept": acc}
+
+
+def make_chain_groups(root_group, var_sets, reweight=None):
+    """``(fdg_chain_groups struct, keepalive)``: ``root_group`` the group of every root, ``var_sets[g]`` the variables of group ``g``
+    (an empty set is allowed), ``reweight`` one factor per group or None (no factor is applied).  Host sequences."""
+    rg = np.ascontiguousarray(root_group, dtype=np.uint32)
+    vm = var_masks(var_sets)
+    rw = None if reweight is None else np.ascontiguousarray(reweight, dtype=np.float64)
+    if rg.ndim != 1 or vm.shape[0] < 1 or (rw is not None and rw.shape != vm.shape):
+        raise ValueError("root_group is a vector, there is at least one group, and reweight holds one factor per group")
+    return ChainGroups(vm.shape[0], rg.ctypes.data, vm.ctypes.data, None if rw is None else rw.ctypes.data), (rg, vm, rw)
+
+
+def chain_grouped_reference(grid, col, state, mask: int, u, u_acc, gamma: float, flags: int, eval_roots, root_group, var_sets,
+                            reweight=None, coef=None, exists=None, matsubara=None, phase_table=None):
+    """One step of the grouped chain restated in numpy (include/fdg.h, "Markov chain with weight groups and reweighting between
+    orders"): fdg_chain_propose_device, then fdg_[mc_]chain_step_device_grouped, in the device's fp64 order, so that the state and the
+    sums compare bit for bit.  The arguments of :func:`chain_reference` with ``root_group [R]``, ``var_sets[g]`` the variables of group
+    ``g`` and ``reweight [n_group]`` or None.  ``matsubara``: None (``state["sum"]`` is ``[R + 1, B]``), or a dict of the projected
+    step's descriptor -- ``freq``, ``fermionic``, ``weight_freq``, ``root_col_in``, ``root_col_out``, ``beta`` -- with
+    ``state["sum"]`` ``[2 F R + 1, B]``; the phases are the library's own (fdg_matsubara_phase through
+    :func:`matsubara_phase_table`, or ``phase_table`` as in :func:`chain_matsubara_reference`)."""
+    table = matsubara_phase_table if phase_table is None else phase_table
+    grid = np.asarray(grid, dtype=np.float64)
+    D, G = grid.shape[0], grid.shape[1] - 1
+    x, fac, root, a = (np.array(state[k], dtype=np.float64) for k in ("x", "fac", "root", "a"))
+    total, n_acc = np.array(state["sum"], dtype=np.float64), np.array(state["n_accept"], dtype=np.int32)
+    B, R, n_group = x.shape[1], root.shape[0], len(var_sets)
+    cols = list(range(D)) if col is None else [int(c) for c in col]
+    live = [k for k in range(R) if exists is None or exists[k]]
+    members = [[k for k in live if int(root_group[k]) == g] for g in range(n_group)]
+    if any(not 0 <= int(root_group[k]) < n_group for k in live) or any(not 0 <= int(d) < D for vs in var_sets for d in vs):
+        raise ValueError("root_group names a group >= n_group, or a variable set a variable >= n_dim")
+    mz = matsubara
+    if mz is not None:
+        freq, fermionic, wf, beta = list(mz["freq"]), mz["fermionic"], int(mz["weight_freq"]), float(mz["beta"])
+        F = len(freq)
+        pairs = {k: (int(mz["root_col_in"][k]), int(mz["root_col_out"][k])) for k in live}
+        if total.shape != (2 * F * R + 1, B) or not 0 <= wf < F:
+            raise ValueError("sum must be [2 n_freq n_root + 1, n_walker] and weight_freq an index into freq")
+
+    def phases(p, fs):
+        return {pair: table(p[pair[1]] - p[pair[0]], beta, fs, fermionic) for pair in set(pairs.values())}
+
+    def group_jac(f, g):
+        j = None
+        for d in sorted(set(int(d) for d in var_sets[g])):
+            j = f[d].copy() if j is None else j * f[d]
+        return np.ones(B) if j is None else j
+
+    xp, facp = x.copy(), fac.copy()
+    for d in range(D):
+        if (mask >> d) & 1:
+            y = np.asarray(u, dtype=np.float64)[:, d] * np.float64(G)
+            c = np.minimum(y.astype(np.int64), G - 1)
+            lo = grid[d, c]
+            wd = grid[d, c + 1] - lo
+            xp[cols[d]] = lo + (y - c.astype(np.float64)) * wd
+            facp[d] = np.float64(G) * wd
+    with np.errstate(all="ignore"):
+        rp = np.asarray(eval_roots(xp), dtype=np.float64) if live else np.zeros((R, B))
+        ph = phases(xp, [freq[wf]]) if mz is not None else None
+        asum, bad = None, np.zeros(B, dtype=bool)
+        for g in range(n_group):
+            if not members[g]:
+                continue
+            jg = group_jac(facp, g)
+            s = re = im = None
+            for k in members[g]:
+                bad |= ~np.isfinite(rp[k])
+                term = rp[k] if coef is None else np.float64(coef[k]) * rp[k]
+                if mz is None:
+                    s = term if s is None else s + term
+                else:
+                    sn, cs = ph[pairs[k]]
+                    pr, pi = term * cs[:, 0], term * sn[:, 0]
+                    re, im = (pr, pi) if re is None else (re + pr, im + pi)
+            if mz is None:
+                tg = jg * s
+                bad |= ~np.isfinite(tg)
+                ag = np.abs(tg)
+            else:
+                tre, tim = jg * re, jg * im
+                bad |= ~np.isfinite(tre) | ~np.isfinite(tim)
+                q0, q1 = tre * tre, tim * tim
+                q = q0 + q1
+                bad |= ~np.isfinite(q)
+                ag = np.sqrt(q)
+            wa = ag if reweight is None else np.float64(reweight[g]) * ag
+            asum = wa if asum is None else asum + wa
+        if asum is None:
+            asum = np.zeros(B)
+        bad |= ~np.isfinite(asum)
+        ap = np.where(bad, 0.0, asum)
+        if flags & FDG_CHAIN_INIT:
+            acc = np.ones(B, dtype=bool)
+        else:
+            acc = np.asarray(u_acc, dtype=np.float64) * (a + gamma) < (ap + gamma)
+    x, fac, a = np.where(acc, xp, x), np.where(acc, facp, fac), np.where(acc, ap, a)
+    for k in live:
+        root[k] = np.where(acc, np.where(bad, 0.0, rp[k]), root[k])
+    n_acc = n_acc + acc.astype(np.int32)
+    if flags & FDG_CHAIN_MEASURE:
+        dd = 1.0 / (a + gamma)
+        ph = phases(x, freq) if mz is not None else None
+        for g in range(n_group):
+            if not members[g]:
+                continue
+            jac = group_jac(fac, g)
+            for k in members[g]:
+                w = (jac * root[k]) * dd
+                if mz is None:
+                    total[k] = total[k] + w
+                    continue
+                sn, cs = ph[pairs[k]]
+                for f in range(F):
+                    o = 2 * (f * R + k)
+                    total[o] = total[o] + w * cs[:, f]
+                    total[o + 1] = total[o + 1] + w * sn[:, f]
+        last = R if mz is None else 2 * F * R
+        total[last] = total[last] + dd
     return {"x": x, "fac": fac, "root": root, "a": a, "sum": total, "n_accept": n_acc, "xp": xp, "facp": facp, "accept": acc}
 
 

@@ -10,6 +10,12 @@
 // select kernel fdg_chain_select_mz folds the roots with the phase of the weight frequency (a' = |jac' sum_k c_k r_k e^{i w tau_k}|)
 // and measures every root at every frequency.  Roots outside, frequencies inside, x = tau / beta once per root; the phase is
 // fdg_matsubara.h's, so a numpy restatement gives the same bits.
+//
+// The grouped step (fdg_[mc_]chain_step_device_grouped) gives every group of roots the jacobian of its own variables and
+// a reweight factor: a' = sum_g rho_g |jac_g s_g|.  Its select kernel fdg_chain_select_grp<MZ> walks the groups outside and a group's
+// roots inside: the lists of the roots are uploaded sorted by (group, root), so a group is one contiguous range, and the groups'
+// ranges, masks and factors are a kernel argument by value (ChainGroups).  jac_g is one pass over the group's variables, made anew
+// for every group: a product per group in a register, not an array of them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -26,6 +32,15 @@ using namespace fdg;
 namespace {
 
 struct ChainCols { uint32_t c[FDG_VEGAS_DIM_MAX]; };      // the column of x each variable is written to (a kernel argument, by value)
+
+// The groups of the grouped step (a kernel argument, by value): the live roots of group g are the entries start[g] .. start[g + 1] - 1
+// of the sorted lists, mask[g] its variables, rho[g] its reweight factor (read only where the call has one).
+struct ChainGroups {
+  uint32_t n;
+  uint32_t start[FDG_WEIGHT_GROUP_MAX + 1];
+  uint64_t mask[FDG_WEIGHT_GROUP_MAX];
+  double rho[FDG_WEIGHT_GROUP_MAX];
+};
 
 // Variable d of walker `sample` (a global index: the Philox counter) through the map: fdg_vegas_sample's statements for one variable.
 __device__ __forceinline__ double chain_draw(const double *__restrict__ grid, uint32_t d, uint32_t G, uint64_t sample, uint64_t seed, double &f) {
@@ -238,6 +253,146 @@ fdg_chain_select_mz(const double *__restrict__ roots, long ld, long n, const uin
   }
 }
 
+// The jacobian of one group for walker b: the left fold of f[d][b] over ascending d with bit d in mask; an empty mask gives 1.0.
+__device__ __forceinline__ double chain_group_jac(const double *__restrict__ f, uint64_t mask, uint32_t D, long nw, long b) {
+  double j = 1.0;
+  bool first = true;
+  for (uint32_t d = 0; d < D; ++d) {
+    if (!((mask >> d) & 1u)) continue;
+    const double v = f[(size_t)d * (size_t)nw + (size_t)b];
+    j = first ? v : j * v;
+    first = false;
+  }
+  return j;
+}
+
+// fdg_chain_select / fdg_chain_select_mz (MZ) with weight groups.  kidx, cf, cin, cout are sorted by (group, root); a group without a
+// live root is skipped altogether.  The arguments of the projection are not read without MZ.  Everything indexed by g, j or f is
+// wave-uniform; the only per-lane values that live across a group are ap and bad.
+template <bool MZ>
+__global__ void __launch_bounds__(256)
+fdg_chain_select_grp(const double *__restrict__ roots, long ld, long n, const uint32_t *__restrict__ kidx, const double *__restrict__ cf,
+                     ChainGroups cg, uint32_t has_rho, const uint32_t *__restrict__ cin, const uint32_t *__restrict__ cout,
+                     const double *__restrict__ mult, uint32_t F, uint32_t wf, double beta, const double *__restrict__ xp, long xpc,
+                     const double *__restrict__ facp, uint32_t n_col, uint32_t D, long nw, double gamma, uint64_t seed, uint64_t off,
+                     uint32_t flags, double *__restrict__ x, long xc, double *__restrict__ fac, double *__restrict__ root,
+                     double *__restrict__ a, double *__restrict__ sum, uint32_t R, int32_t *__restrict__ n_accept) {
+  const long b = blockIdx.x * 256L + threadIdx.x;
+  if (b >= n) return;
+  const bool init = (flags & FDG_CHAIN_INIT) != 0, meas = (flags & FDG_CHAIN_MEASURE) != 0;
+  // the fold, group by group: jac_g', s_g' (or re_g', im_g' at the weight frequency), a_g', and a' = the fold of rho_g a_g'
+  double mw = 0.0;
+  if (MZ) mw = mult[wf];
+  double asum = 0.0;
+  bool bad = false, first_group = true;
+  for (uint32_t g = 0; g < cg.n; ++g) {
+    const uint32_t j0 = cg.start[g], j1 = cg.start[g + 1];
+    if (j0 == j1) continue;
+    const double jg = chain_group_jac(facp, cg.mask[g], D, nw, b);
+    double ag;
+    if (MZ) {
+      double re = 0.0, im = 0.0;
+      for (uint32_t j = j0; j < j1; ++j) {
+        const double r = roots[(size_t)kidx[j] * (size_t)ld + (size_t)b];
+        bad = bad || !std::isfinite(r);
+        const double tau = xp[(long)cout[j] * xpc + b] - xp[(long)cin[j] * xpc + b];
+        const double xt = tau / beta;
+        double sn, cs;
+        matsubara_phase_of(xt, mw, sn, cs);
+        const double term = cf ? cf[j] * r : r;
+        const double pr = term * cs, pi = term * sn;
+        re = j != j0 ? re + pr : pr;
+        im = j != j0 ? im + pi : pi;
+      }
+      const double tre = jg * re, tim = jg * im;
+      bad = bad || !std::isfinite(tre) || !std::isfinite(tim);
+      const double q0 = tre * tre, q1 = tim * tim;
+      const double q = q0 + q1;
+      bad = bad || !std::isfinite(q);
+      ag = sqrt(q);
+    } else {
+      double s = 0.0;
+      for (uint32_t j = j0; j < j1; ++j) {
+        const double r = roots[(size_t)kidx[j] * (size_t)ld + (size_t)b];
+        bad = bad || !std::isfinite(r);
+        const double term = cf ? cf[j] * r : r;
+        s = j != j0 ? s + term : term;
+      }
+      const double tg = jg * s;
+      bad = bad || !std::isfinite(tg);
+      ag = fabs(tg);
+    }
+    const double wa = has_rho ? cg.rho[g] * ag : ag;
+    asum = first_group ? wa : asum + wa;
+    first_group = false;
+  }
+  bad = bad || !std::isfinite(asum);
+  const double ap = bad ? 0.0 : asum;
+  // the accept rule
+  const double a0 = init ? 0.0 : a[b];
+  bool acc = true;
+  if (!init) {
+    const double u = fdg_philox_u53(off + (uint64_t)b, FDG_VEGAS_DIM_MAX, seed);
+    acc = u * (a0 + gamma) < (ap + gamma);
+  }
+  // the selection
+  if (acc) {
+    for (uint32_t c = 0; c < n_col; ++c) x[(long)c * xc + b] = xp[(long)c * xpc + b];
+    for (uint32_t d = 0; d < D; ++d) {
+      const size_t at = (size_t)d * (size_t)nw + (size_t)b;
+      fac[at] = facp[at];
+    }
+    a[b] = ap;
+    if (n_accept) n_accept[b] = n_accept[b] + 1;
+  }
+  if (!acc && !meas) return;
+  // the second walk over the groups and their roots: select, and measure on the state after the selection (whose factors and times
+  // are the proposal's after an acceptance: the same bits, read where they were not just written)
+  const double dd = 1.0 / ((acc ? ap : a0) + gamma);
+  const double *fs = acc ? facp : fac;
+  const double *tp = acc ? xp : x;
+  const long tpc = acc ? xpc : xc;
+  for (uint32_t g = 0; g < cg.n; ++g) {
+    const uint32_t j0 = cg.start[g], j1 = cg.start[g + 1];
+    if (j0 == j1) continue;
+    double jac = 0.0;
+    if (meas) jac = chain_group_jac(fs, cg.mask[g], D, nw, b);
+    for (uint32_t j = j0; j < j1; ++j) {
+      const uint32_t k = kidx[j];
+      const size_t at = (size_t)k * (size_t)nw + (size_t)b;
+      double r;
+      if (acc) {
+        const double rp = roots[(size_t)k * (size_t)ld + (size_t)b];
+        r = bad ? 0.0 : rp;
+        root[at] = r;
+      } else {
+        r = root[at];
+      }
+      if (meas) {
+        const double jr = jac * r;
+        const double w = jr * dd;
+        if (MZ) {
+          const double tau = tp[(long)cout[j] * tpc + b] - tp[(long)cin[j] * tpc + b];
+          const double xt = tau / beta;
+          for (uint32_t f = 0; f < F; ++f) {
+            double sn, cs;
+            matsubara_phase_of(xt, mult[f], sn, cs);
+            const size_t o = (size_t)(2u * (f * R + k)) * (size_t)nw + (size_t)b;
+            sum[o] = sum[o] + w * cs;
+            sum[o + (size_t)nw] = sum[o + (size_t)nw] + w * sn;
+          }
+        } else {
+          sum[at] = sum[at] + w;
+        }
+      }
+    }
+  }
+  if (meas) {
+    const size_t at = (size_t)(MZ ? 2u * F * R : R) * (size_t)nw + (size_t)b;
+    sum[at] = sum[at] + dd;
+  }
+}
+
 // out[c] += the sum over the walkers of column c's term (include/fdg.h: S, Q, X); one workgroup per output.
 __global__ void __launch_bounds__(256)
 fdg_chain_reduce(const double *__restrict__ sum, uint32_t R, long n, double *__restrict__ out) {
@@ -319,11 +474,31 @@ int check_chain_mz(const fdg_graph *g, const ChainCall &c, const fdg_chain_matsu
   return FDG_OK;
 }
 
+// The checks of the grouped step calls on their descriptor, after check_chain (and check_chain_mz where there is a projection).
+int check_chain_groups(const fdg_graph *g, const ChainCall &c, const fdg_chain_groups *cg) {
+  if (!cg) { set_error("null groups descriptor"); return FDG_E_INVALID; }
+  if (!cg->root_group || !cg->var_mask) { set_error("null array in the groups descriptor"); return FDG_E_INVALID; }
+  if (cg->n_group == 0) { set_error("n_group == 0"); return FDG_E_INVALID; }
+  if (cg->n_group > FDG_WEIGHT_GROUP_MAX) { set_error("n_group > FDG_WEIGHT_GROUP_MAX"); return FDG_E_UNSUPPORTED; }
+  for (uint32_t k = 0; k < g->prog.R; ++k)
+    if (g->prog.root_slot[k] != FDG_NO_ROOT && cg->root_group[k] >= cg->n_group) {
+      set_error("root_group of an existing root >= n_group"); return FDG_E_INVALID;
+    }
+  for (uint32_t q = 0; q < cg->n_group; ++q) {
+    if (c.n_dim < 64 && (cg->var_mask[q] >> c.n_dim)) { set_error("var_mask names a variable >= n_dim"); return FDG_E_INVALID; }
+    if (cg->reweight && !(std::isfinite(cg->reweight[q]) && cg->reweight[q] > 0.0)) {
+      set_error("a reweight factor is not finite or <= 0"); return FDG_E_INVALID;
+    }
+  }
+  return FDG_OK;
+}
+
 // The body of all step calls (caller holds g->mu, stream bound): eval(c0, n, roots, ld) writes the roots of the proposals of walkers
 // c0 .. c0 + n - 1 column-major into roots.  The chunk is the accumulate calls' (FDG_ROOT_SCRATCH_MB); no result depends on it.
 // mz: the projected step (fdg_chain_select_mz); its multipliers and time columns lie behind the plain step's uploads.
+// cg: the grouped step (fdg_chain_select_grp, with or without mz); the lists are then sorted by (group, root).
 template <class Eval>
-int run_chain(fdg_graph *g, const ChainCall &c, Eval eval, const fdg_chain_matsubara *mz) {
+int run_chain(fdg_graph *g, const ChainCall &c, Eval eval, const fdg_chain_matsubara *mz, const fdg_chain_groups *cg) {
   const uint32_t R = g->prog.R;
   const hipStream_t st = (hipStream_t)c.stream;
   long Bc = std::max<long>(64, (long)((g->cfg.root_scratch_mb << 20) / (8ull * std::max<uint32_t>(R, 1u))) & ~63l);
@@ -340,7 +515,19 @@ int run_chain(fdg_graph *g, const ChainCall &c, Eval eval, const fdg_chain_matsu
   std::vector<double> hc;
   std::vector<uint32_t> hk;
   for (uint32_t k = 0; k < R; ++k)
-    if (g->prog.root_slot[k] != FDG_NO_ROOT) { hk.push_back(k); hc.push_back(c.coef ? c.coef[k] : 1.0); }
+    if (g->prog.root_slot[k] != FDG_NO_ROOT) hk.push_back(k);
+  ChainGroups grp{};
+  if (cg) {
+    std::stable_sort(hk.begin(), hk.end(), [&](uint32_t p, uint32_t q) { return cg->root_group[p] < cg->root_group[q]; });
+    grp.n = cg->n_group;
+    for (uint32_t k : hk) ++grp.start[cg->root_group[k] + 1u];
+    for (uint32_t q = 0; q < cg->n_group; ++q) {
+      grp.start[q + 1u] += grp.start[q];
+      grp.mask[q] = cg->var_mask[q];
+      grp.rho[q] = cg->reweight ? cg->reweight[q] : 1.0;
+    }
+  }
+  for (uint32_t k : hk) hc.push_back(c.coef ? c.coef[k] : 1.0);
   const uint32_t n_live = (uint32_t)hk.size();
   if (n_live) {
     HIP_TRY(hipMemcpyAsync(d_coef, hc.data(), n_live * sizeof(double), hipMemcpyHostToDevice, st));
@@ -366,7 +553,19 @@ int run_chain(fdg_graph *g, const ChainCall &c, Eval eval, const fdg_chain_matsu
       rc = eval(c0, n, roots, Bc);
       if (rc) return rc;
     }
-    if (mz)
+    if (cg && mz)
+      hipLaunchKernelGGL(fdg_chain_select_grp<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, roots, Bc, n, d_kidx,
+                         c.coef ? d_coef : nullptr, grp, cg->reweight ? 1u : 0u, d_cin, d_cout, d_mult, mz->n_freq, mz->weight_freq, mz->beta,
+                         c.d_xp + c0, (long)c.xpc, c.d_facp + c0, c.n_col, c.n_dim, (long)c.B, c.gamma, c.seed, c.offset + (uint64_t)c0,
+                         (uint32_t)c.flags, c.d_x + c0, (long)c.xc, c.d_fac + c0, c.d_root + c0, c.d_a + c0,
+                         c.d_sum ? c.d_sum + c0 : nullptr, R, c.d_n_accept ? c.d_n_accept + c0 : nullptr);
+    else if (cg)
+      hipLaunchKernelGGL(fdg_chain_select_grp<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, roots, Bc, n, d_kidx,
+                         c.coef ? d_coef : nullptr, grp, cg->reweight ? 1u : 0u, nullptr, nullptr, nullptr, 0u, 0u, 1.0, c.d_xp + c0,
+                         (long)c.xpc, c.d_facp + c0, c.n_col, c.n_dim, (long)c.B, c.gamma, c.seed, c.offset + (uint64_t)c0,
+                         (uint32_t)c.flags, c.d_x + c0, (long)c.xc, c.d_fac + c0, c.d_root + c0, c.d_a + c0,
+                         c.d_sum ? c.d_sum + c0 : nullptr, R, c.d_n_accept ? c.d_n_accept + c0 : nullptr);
+    else if (mz)
       hipLaunchKernelGGL(fdg_chain_select_mz, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, roots, Bc, n, d_kidx,
                          c.coef ? d_coef : nullptr, n_live, d_cin, d_cout, d_mult, mz->n_freq, mz->weight_freq, mz->beta, c.d_xp + c0,
                          (long)c.xpc, c.d_facp + c0, c.n_col, c.n_dim, (long)c.B, c.gamma, c.seed, c.offset + (uint64_t)c0,
@@ -383,7 +582,8 @@ int run_chain(fdg_graph *g, const ChainCall &c, Eval eval, const fdg_chain_matsu
 }
 
 template <class Check, class Eval>
-int chain_step(fdg_graph *g, const ChainCall &c, Check locked_check, Eval eval, const fdg_chain_matsubara *mz = nullptr) {
+int chain_step(fdg_graph *g, const ChainCall &c, Check locked_check, Eval eval, const fdg_chain_matsubara *mz = nullptr,
+               const fdg_chain_groups *cg = nullptr) {
   std::lock_guard<std::mutex> lk(g->mu);
   fdg::KnobScope knob_scope(&g->knobs);
   int rc = locked_check();
@@ -393,7 +593,7 @@ int chain_step(fdg_graph *g, const ChainCall &c, Check locked_check, Eval eval, 
   if (rc) return rc;
   rc = fdg_bind_stream_ws(g, c.stream);
   if (rc) return rc;
-  return run_chain(g, c, eval, mz);
+  return run_chain(g, c, eval, mz, cg);
 }
 
 }  // namespace
@@ -505,6 +705,61 @@ int fdg_mc_chain_step_device_matsubara(fdg_graph *g, const double *d_xp, int64_t
         return fdg_mc_run_locked(g, 0, K, 1, xp_col_stride, T, 1, xp_col_stride, kF, beta, lambda, roots, 1, ld, nullptr, nullptr, n, st);
       },
       mz);
+}
+
+int fdg_chain_step_device_grouped(fdg_graph *g, const double *d_xp, int64_t xp_col_stride, const double *d_facp, uint32_t n_col,
+                                  uint32_t n_dim, const double *coef, double gamma, uint64_t seed, uint64_t sample_offset, unsigned flags,
+                                  double *d_x, int64_t x_col_stride, double *d_fac, double *d_root, double *d_a, double *d_sum,
+                                  int32_t *d_n_accept, const fdg_chain_matsubara *mz, const fdg_chain_groups *cg, int64_t B,
+                                  void *stream) {
+  const ChainCall c{d_xp, xp_col_stride, d_facp, n_col, n_dim, coef, gamma, seed, sample_offset, flags, d_x, x_col_stride, d_fac,
+                    d_root, d_a, d_sum, d_n_accept, B, stream};
+  int rc = check_chain(g, c);
+  if (rc) return rc;
+  if (n_col != g->prog.L) { set_error("n_col is not the graph's number of leaves"); return FDG_E_INVALID; }
+  if (mz) {
+    rc = check_chain_mz(g, c, mz);
+    if (rc) return rc;
+  }
+  rc = check_chain_groups(g, c, cg);
+  if (rc) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  return chain_step(
+      g, c, [] { return FDG_OK; },
+      [&](long c0, long n, double *roots, long ld) {
+        return fdg_run_locked(g, 0, d_xp + c0, 1, xp_col_stride, roots, 1, ld, nullptr, nullptr, n, st, 0, 0);
+      },
+      mz, cg);
+}
+
+int fdg_mc_chain_step_device_grouped(fdg_graph *g, const double *d_xp, int64_t xp_col_stride, double kF, double beta, double lambda,
+                                     const double *d_facp, uint32_t n_col, uint32_t n_dim, const double *coef, double gamma, uint64_t seed,
+                                     uint64_t sample_offset, unsigned flags, double *d_x, int64_t x_col_stride, double *d_fac,
+                                     double *d_root, double *d_a, double *d_sum, int32_t *d_n_accept, const fdg_chain_matsubara *mz,
+                                     const fdg_chain_groups *cg, int64_t B, void *stream) {
+  const ChainCall c{d_xp, xp_col_stride, d_facp, n_col, n_dim, coef, gamma, seed, sample_offset, flags, d_x, x_col_stride, d_fac,
+                    d_root, d_a, d_sum, d_n_accept, B, stream};
+  int rc = check_chain(g, c);
+  if (rc) return rc;
+  if (mz) {
+    rc = check_chain_mz(g, c, mz);
+    if (rc) return rc;
+  }
+  rc = check_chain_groups(g, c, cg);
+  if (rc) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  return chain_step(
+      g, c,
+      [&] {
+        if (g->mc_route == 0) { set_error("fdg_graph_specialize_fused has not been called on this handle"); return FDG_E_INVALID; }
+        if (n_col != g->lt_hdr[2] * g->lt_hdr[3] + g->lt_hdr[4]) { set_error("n_col is not the tables' n_loop * dim + n_tau"); return FDG_E_INVALID; }
+        return FDG_OK;
+      },
+      [&](long c0, long n, double *roots, long ld) {
+        const double *K = d_xp + c0, *T = d_xp + (int64_t)(g->lt_hdr[2] * g->lt_hdr[3]) * xp_col_stride + c0;
+        return fdg_mc_run_locked(g, 0, K, 1, xp_col_stride, T, 1, xp_col_stride, kF, beta, lambda, roots, 1, ld, nullptr, nullptr, n, st);
+      },
+      mz, cg);
 }
 
 int fdg_chain_reduce_device(const double *d_sum, uint32_t n_root, int64_t B, double *d_out, void *stream) {

@@ -907,6 +907,52 @@ function mc_chain_step_device_matsubara!(f::GraphFunc, d_xp::Ptr{Float64}, d_fac
     end
     return nothing
 end
+# The same two steps with weight groups (fdg_[mc_]chain_step_device_grouped): the weight is a = sum_g rho_g |jac_g s_g| with jac_g the
+# jacobian of the variables of group g only, and root k is measured with the jacobian of its own group.  dof / pools as
+# weight_groups_from_dof takes them; reweight: one factor > 0 per group, or nothing (no factor is applied).  These wrappers pass no
+# projection (mz = C_NULL), so d_sum is B x (R + 1).  Unverified: written against the header, never run.
+struct _FdgChainGroups
+    n_group::UInt32
+    root_group::Ptr{UInt32}
+    var_mask::Ptr{UInt64}
+    reweight::Ptr{Float64}
+end
+function chain_step_device_grouped!(f::GraphFunc, d_xp::Ptr{Float64}, d_facp::Ptr{Float64}, d_x::Ptr{Float64}, d_fac::Ptr{Float64},
+    d_root::Ptr{Float64}, d_a::Ptr{Float64}, d_sum::Ptr{Float64}, n_col::Integer, n_dim::Integer, gamma::Float64, B::Integer;
+    dof::AbstractVector, pools::AbstractVector, reweight::Union{Nothing,Vector{Float64}}=nothing, flags::Integer=0,
+    coef::Union{Nothing,Vector{Float64}}=nothing, seed::Integer=0, sample_offset::Integer=0,
+    d_n_accept::Ptr{Int32}=Ptr{Int32}(C_NULL), x_col_stride::Integer=B, xp_col_stride::Integer=B, stream::Ptr{Cvoid}=C_NULL)
+    root_group, var_mask = weight_groups_from_dof(dof, pools)
+    rw = reweight === nothing ? Float64[] : reweight
+    GC.@preserve root_group var_mask rw begin
+        cg = _FdgChainGroups(length(var_mask), pointer(root_group), pointer(var_mask), reweight === nothing ? Ptr{Float64}(C_NULL) : pointer(rw))
+        _fdg_check(ccall((:fdg_chain_step_device_grouped, _libfdg), Cint,
+            (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, UInt32, UInt32, Ptr{Float64}, Float64, UInt64, UInt64, Cuint, Ptr{Float64}, Int64,
+             Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Cvoid}, Ref{_FdgChainGroups}, Int64, Ptr{Cvoid}),
+            f.handle, d_xp, xp_col_stride, d_facp, n_col, n_dim, coef === nothing ? C_NULL : coef, gamma, seed, sample_offset, flags, d_x,
+            x_col_stride, d_fac, d_root, d_a, d_sum, d_n_accept, C_NULL, cg, B, stream))
+    end
+    return nothing
+end
+function mc_chain_step_device_grouped!(f::GraphFunc, d_xp::Ptr{Float64}, d_facp::Ptr{Float64}, d_x::Ptr{Float64}, d_fac::Ptr{Float64},
+    d_root::Ptr{Float64}, d_a::Ptr{Float64}, d_sum::Ptr{Float64}, n_col::Integer, n_dim::Integer, gamma::Float64, B::Integer;
+    dof::AbstractVector, pools::AbstractVector, kF::Float64, beta::Float64, lambda::Float64,
+    reweight::Union{Nothing,Vector{Float64}}=nothing, flags::Integer=0, coef::Union{Nothing,Vector{Float64}}=nothing, seed::Integer=0,
+    sample_offset::Integer=0, d_n_accept::Ptr{Int32}=Ptr{Int32}(C_NULL), x_col_stride::Integer=B, xp_col_stride::Integer=B,
+    stream::Ptr{Cvoid}=C_NULL)
+    root_group, var_mask = weight_groups_from_dof(dof, pools)
+    rw = reweight === nothing ? Float64[] : reweight
+    GC.@preserve root_group var_mask rw begin
+        cg = _FdgChainGroups(length(var_mask), pointer(root_group), pointer(var_mask), reweight === nothing ? Ptr{Float64}(C_NULL) : pointer(rw))
+        _fdg_check(ccall((:fdg_mc_chain_step_device_grouped, _libfdg), Cint,
+            (Ptr{Cvoid}, Ptr{Float64}, Int64, Float64, Float64, Float64, Ptr{Float64}, UInt32, UInt32, Ptr{Float64}, Float64, UInt64, UInt64,
+             Cuint, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Cvoid}, Ref{_FdgChainGroups},
+             Int64, Ptr{Cvoid}),
+            f.handle, d_xp, xp_col_stride, kF, beta, lambda, d_facp, n_col, n_dim, coef === nothing ? C_NULL : coef, gamma, seed,
+            sample_offset, flags, d_x, x_col_stride, d_fac, d_root, d_a, d_sum, d_n_accept, C_NULL, cg, B, stream))
+    end
+    return nothing
+end
 # d_out (3 R + 2, added to) = the sums over the walkers S_c, Q_c = sum A_c^2 (R + 1 each) and X_k = sum A_k A_{R+1} (R) of d_sum.
 function chain_reduce_device!(d_out::Ptr{Float64}, d_sum::Ptr{Float64}, n_root::Integer, B::Integer; stream::Ptr{Cvoid}=C_NULL)
     _fdg_check(ccall((:fdg_chain_reduce_device, _libfdg), Cint, (Ptr{Float64}, UInt32, Int64, Ptr{Float64}, Ptr{Cvoid}),
@@ -915,6 +961,7 @@ function chain_reduce_device!(d_out::Ptr{Float64}, d_sum::Ptr{Float64}, n_root::
 end
 export chain_propose_device!, chain_step_device!, mc_chain_step_device!, chain_reduce_device!, FDG_CHAIN_INIT, FDG_CHAIN_MEASURE
 export chain_step_device_matsubara!, mc_chain_step_device_matsubara!
+export chain_step_device_grouped!, mc_chain_step_device_grouped!
 
 # ---- multi-GPU: one Julia process per GPU, ONE reduction of the accumulated observable ------------ #
 # (include/fdg.h, "multi-GPU").  Rank 0 calls `comm_unique_id()` and ships the 128 bytes to the other

@@ -42,7 +42,8 @@ walker per lane -- what ``integrate(...; solver=:mcmc)`` of the reference's test
 that no separable map follows.  The stationary density ``|s| + gamma q`` carries the map's own density ``q``, whose known integral
 normalises the result; the error bar comes from the spread across the independent walkers.  With ``matsubara`` the projection
 runs inside the chain (fdg_[mc_]chain_step_device_matsubara): the weight is the modulus of the projected sum at one frequency, and
-every root is measured at every frequency.
+every root is measured at every frequency.  With weight groups (``chain_integrate_grouped``; fdg_[mc_]chain_step_device_grouped)
+several orders of a series walk in one chain: every group carries the jacobian of its own variables and a reweight factor.
 """
 from __future__ import annotations
 
@@ -838,6 +839,7 @@ class ChainResult:
                                      # S, Q, X are raw over the 2 n_freq R columns 2 (f R + k) (real part), + 1 (imaginary part)
     Q: Optional[np.ndarray] = None   # [R + 1] sum over the walkers of A_c(b)**2
     X: Optional[np.ndarray] = None   # [R] sum over the walkers of A_k(b) A_R(b)
+    reweight: Optional[np.ndarray] = None   # [n_group] the factor of every weight group (:func:`chain_integrate_grouped`)
 
 
 def chain_estimate(S, Q, X, n_walker: int):
@@ -921,13 +923,61 @@ def chain_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: 
     Out of scope here, refused with ValueError: ``polar``, ``groups``, a discrete variable (``dmap``), ``observables``,
     ``freq_observables`` and ``strat`` together with the chain.  Not built either: training the map from the chain's own samples,
     local (shift) proposals, reweighting between orders.  The target these lead to is ``Sigma(i omega_0)`` of the Hubbard atom in
-    the reference's test/hubbard.jl: its single-order case is what ``matsubara`` reaches; several orders at once need ``groups``."""
-    import torch
+    the reference's test/hubbard.jl: its single-order case is what ``matsubara`` reaches; several orders at once need ``groups``,
+    which :func:`chain_integrate_grouped` takes (with the reweighting between orders)."""
     for name, value in excluded.items():
         if name not in _CHAIN_EXCLUDED:
             raise TypeError(f"chain_integrate() got an unexpected keyword argument '{name}'")
         if value is not None and not (name == "polar" and not value):
             raise ValueError(f"{name} cannot be combined with the chain yet")
+    return _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step, n_therm, moves, gamma_rel, gamma, n_warm,
+                  n_warm_sample, n_grid, alpha, seed, fixed, coef, vmap, specialize_fused, n_total, shard_start, reduce, device, matsubara,
+                  weight_freq)
+
+
+def chain_integrate_grouped(func_or_handle, tables, lo, hi, col, groups: WeightGroups, kF: float = 0.0, beta: float = 1.0, lam: float = 0.0, *,
+                            n_walker: int, n_step: int, n_therm: int, moves: Optional[Sequence[int]] = None, gamma_rel: float = 1.0,
+                            gamma: Optional[float] = None, n_warm: int = 5, n_warm_sample: Optional[int] = None, n_grid: int = 64,
+                            alpha: float = 0.5, seed: int = 0, fixed=None, coef=None, vmap: Optional[VegasMap] = None,
+                            specialize_fused: bool = True, n_total: Optional[int] = None, shard_start: int = 0,
+                            reduce: Optional[Callable] = None, device="cuda", reweight=None,
+                            matsubara: Optional[MatsubaraProjection] = None, weight_freq: int = 0, **excluded) -> ChainResult:
+    """:func:`chain_integrate` with weight groups (``groups``: a :class:`WeightGroups`, :func:`groups_from_dof`), which that function
+    refuses: several orders of a series in one run, every order with its own variables, MCIntegration's ``:vegasmc`` with several
+    integrands (fdg_[mc_]chain_step_device_grouped; include/fdg.h).  The walkers' weight is ``a = sum_g rho_g |jac_g s_g|`` with
+    ``jac_g`` the jacobian of the variables of group ``g`` only, ``s_g`` the ``coef`` combination of the group's roots and ``rho_g``
+    the reweight factor that balances the orders; root ``k`` is measured with the jacobian of its own group.  With ``matsubara`` the
+    group's sum is projected at ``freq[weight_freq]`` as in :func:`chain_integrate`.  Every other argument and the result are that
+    function's; ``ChainResult.reweight`` holds the factors used.  Procedure:
+
+    1. the map is trained by the grouped direct sampler: ``vegas_integrate(groups=...)`` in the Monte-Carlo form,
+       ``vegas_integrate_stratified(..., Stratification((1,) * D), groups=...)`` in the leaf form; skipped with ``n_warm = 0``;
+    2. unless ``reweight`` is given, FDG_CHAIN_INIT places the walkers without factors, and ``rho_g = 1 / mean_b |jac_g s_g|`` is
+       taken from the placed ``fac`` and ``root`` (all walkers: ``reduce`` is applied to the sums), so that every group carries the
+       same share of the density.  This is the UNPROJECTED ``s_g``, also under ``matsubara``.  A group with a root that exists whose
+       mean is 0 or not finite raises ValueError asking for ``reweight``; a group without such a root gets the factor 1;
+    3. FDG_CHAIN_INIT places the walkers on the same counters with ``rho``; ``gamma = gamma_rel * mean(a)``;
+    4. the steps, the reduction and :func:`chain_estimate` as in :func:`chain_integrate`.
+
+    ``reweight``: one finite factor > 0 per group.  Refused with ValueError: ``polar``, ``dmap``, ``observables``,
+    ``freq_observables`` and ``strat``."""
+    for name, value in excluded.items():
+        if name not in _CHAIN_EXCLUDED or name == "groups":
+            raise TypeError(f"chain_integrate_grouped() got an unexpected keyword argument '{name}'")
+        if value is not None and not (name == "polar" and not value):
+            raise ValueError(f"{name} cannot be combined with the chain yet")
+    if not isinstance(groups, WeightGroups):
+        raise ValueError("groups must be a WeightGroups")
+    return _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step, n_therm, moves, gamma_rel, gamma, n_warm,
+                  n_warm_sample, n_grid, alpha, seed, fixed, coef, vmap, specialize_fused, n_total, shard_start, reduce, device, matsubara,
+                  weight_freq, groups, reweight)
+
+
+def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step, n_therm, moves, gamma_rel, gamma, n_warm, n_warm_sample,
+           n_grid, alpha, seed, fixed, coef, vmap, specialize_fused, n_total, shard_start, reduce, device, matsubara, weight_freq,
+           wgroups=None, reweight=None) -> ChainResult:
+    """The body of :func:`chain_integrate` and, with ``wgroups``, of :func:`chain_integrate_grouped`."""
+    import torch
     handle = getattr(func_or_handle, "handle", func_or_handle)
     device = torch.device(device)
     R = handle.table.n_root
@@ -982,6 +1032,21 @@ def chain_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: 
     fx = np.zeros(n_col) if fixed is None else np.asarray(fixed, dtype=np.float64)
     if fx.shape != (n_col,):
         raise ValueError(f"fixed must hold {n_col} column values")
+    rho = None
+    if wgroups is not None:
+        NG = len(wgroups.var_sets)
+        if len(wgroups.root_group) != R or not all(0 <= int(v) < NG for v in wgroups.root_group):
+            raise ValueError("groups.root_group names one group of groups.var_sets per root")
+        if not 1 <= NG <= capi.FDG_WEIGHT_GROUP_MAX:
+            raise ValueError(f"need 1 .. {capi.FDG_WEIGHT_GROUP_MAX} weight groups")
+        if not all(0 <= int(d) < D for vs in wgroups.var_sets for d in vs):
+            raise ValueError("groups.var_sets names variables of the map")
+        if coef is not None and np.shape(coef) != (R,):
+            raise ValueError(f"coef must hold n_root = {R} factors")
+        if reweight is not None:
+            rho = np.array(reweight, dtype=np.float64)
+            if rho.shape != (NG,) or not (np.isfinite(rho) & (rho > 0.0)).all():
+                raise ValueError("reweight must hold one finite factor > 0 per group")
     if n_warm:
         kw = dict(n_iter=n_warm, n_grid=G, alpha=alpha, seed=(int(seed) + _CHAIN_TRAIN_KEY) & 0xFFFFFFFFFFFFFFFF, fixed=fixed, coef=coef,
                   device=device, vmap=vmap, specialize_fused=specialize_fused, reduce=reduce)
@@ -989,9 +1054,14 @@ def chain_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: 
             kw.update(n_sample=B, n_total=n_total, shard_start=shard_start)
         else:
             kw.update(n_sample=int(n_warm_sample))
-        if tables is None:
-            kw["strat"] = Stratification((1,) * D)
-        vegas_integrate(func_or_handle, tables, lo, hi, col, kF, beta, lam, **kw)
+        if wgroups is not None and tables is None:
+            vegas_integrate_stratified(func_or_handle, tables, lo, hi, col, Stratification((1,) * D), kF, beta, lam, groups=wgroups, **kw)
+        else:
+            if wgroups is not None:
+                kw["groups"] = wgroups
+            elif tables is None:
+                kw["strat"] = Stratification((1,) * D)
+            vegas_integrate(func_or_handle, tables, lo, hi, col, kF, beta, lam, **kw)
     elif specialize_fused and tables is not None:
         handle.specialize_fused(tables)
     all_mask = (1 << D) - 1
@@ -1010,7 +1080,14 @@ def chain_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: 
                                       xp.data_ptr(), B, facp.data_ptr(), B, st)
             tail = (facp.data_ptr(), n_col, D, coef, g, seed, off, flags, x.data_ptr(), B, fac.data_ptr(), root.data_ptr(), a.data_ptr(),
                     total.data_ptr(), n_acc.data_ptr(), B, st)
-            if desc is not None:
+            if wgroups is not None:
+                gdesc, _gkeep = capi.make_chain_groups(wgroups.root_group, wgroups.var_sets, rho)
+                tail = tail[:-2] + (desc, gdesc) + tail[-2:]
+                if tables is None:
+                    handle.chain_step_device_grouped(xp.data_ptr(), B, *tail)
+                else:
+                    handle.mc_chain_step_device_grouped(xp.data_ptr(), B, kF, beta, lam, *tail)
+            elif desc is not None:
                 tail = tail[:-2] + (desc,) + tail[-2:]
                 if tables is None:
                     handle.chain_step_device_matsubara(xp.data_ptr(), B, *tail)
@@ -1022,6 +1099,27 @@ def chain_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: 
                 handle.mc_chain_step_device(xp.data_ptr(), B, kF, beta, lam, *tail)
 
         step(all_mask, int(shard_start), 1.0, capi.FDG_CHAIN_INIT)                       # (gamma enters no result of the placement)
+        if wgroups is not None and rho is None:
+            # rho_g = 1 / mean_b |jac_g s_g| of the placement, then the placement again on the same counters with rho
+            from .nodetable import FDG_NO_ROOT
+            members = [[k for k in range(R) if int(handle.table.root_slot[k]) != FDG_NO_ROOT and int(wgroups.root_group[k]) == g]
+                       for g in range(NG)]
+            sg = torch.zeros(NG, **f64)
+            for g, ks in enumerate(members):
+                if ks:
+                    c = torch.ones(len(ks), **f64) if coef is None else torch.as_tensor(np.asarray(coef, dtype=np.float64)[ks], **f64)
+                    jg = fac[sorted(set(int(d) for d in wgroups.var_sets[g]))].prod(0)       # (an empty set: 1)
+                    sg[g] = (jg * (c[:, None] * root[ks]).sum(0)).abs().sum()
+            if reduce is not None:
+                reduce(sg)
+            mean_g = sg.cpu().numpy() / N
+            rho = np.ones(NG)
+            for g, ks in enumerate(members):
+                if ks:
+                    if not (math.isfinite(mean_g[g]) and mean_g[g] > 0.0 and math.isfinite(1.0 / mean_g[g])):
+                        raise ValueError(f"the map's estimate of the integral of |s_g| of group {g} is not positive and finite: pass reweight")
+                    rho[g] = 1.0 / mean_g[g]
+            step(all_mask, int(shard_start), 1.0, capi.FDG_CHAIN_INIT)
         if gamma is None:
             sa = a.sum().reshape(1)
             if reduce is not None:
@@ -1044,4 +1142,4 @@ def chain_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: 
     mean, err = chain_estimate(S, Q, X, N)                # (a root that does not exist has sums of 0: mean 0, stderr 0)
     if F:
         mean, err = chain_complex(mean, F, R), chain_complex(err, F, R)
-    return ChainResult(mean, err, float(acc_sum.item()) / (N * n_step), float(gamma), vmap, S, Q, X)
+    return ChainResult(mean, err, float(acc_sum.item()) / (N * n_step), float(gamma), vmap, S, Q, X, rho)

@@ -1248,6 +1248,66 @@ int fdg_mc_chain_step_device_matsubara(fdg_graph *g, const double *d_xp, int64_t
                                        double *d_fac, double *d_root, double *d_a, double *d_sum, int32_t *d_n_accept,
                                        const fdg_chain_matsubara *mz, int64_t n_walker, void *stream);
 
+/* ---- Markov chain with weight groups and reweighting between orders ---------------------------------------------------------------------
+ * A diagram series integrated with all its orders at once gives every order its own variables (MCIntegration's dof; "Weight groups"
+ * above).  This is MCIntegration's :vegasmc with several integrands: group g has the variables of var_mask[g], jac_g is the jacobian of
+ * those variables only, s_g the coef combination of the group's roots and rho_g > 0 a reweight factor that balances the orders.  The
+ * stationary density in physical coordinates is
+ *     p(x) = sum_g rho_g |s_g(x)| q_notg(x) + gamma q(x),     q_notg = prod_{d not in g} 1 / fac_d
+ * (the map's density of the variables the group does not integrate), in the map's coordinates pi(y) = a(y) + gamma with
+ * a = sum_g rho_g |jac_g s_g|.  The Metropolis ratio stays (a' + gamma) / (a + gamma) for every move mask: the argument of the plain
+ * step needs of a only that it is a non-negative function of the point.  The estimate is
+ *     I_k = sum (jac_g(k) * r_k) * d / sum d,     d = 1 / (a + gamma)
+ * since the variables outside the group integrate to 1 under q.  MCIntegration is not part of the reference checkout: no counterpart
+ * in the reference; the caller's side of test/hubbard.jl:81-85 with more than one order.
+ *
+ * fdg_chain_propose_device and fdg_chain_reduce_device serve as they are; the state (x, fac, root, a) and d_sum keep the layout of the
+ * plain step (mz == NULL) or of the projected step (mz != NULL).  Per walker, every line one rounded fp64 operation (no FMA), the first
+ * term of every fold assigned, not added to 0, in this order:
+ *     jac_g = the left fold of fac_d over ascending d with bit d in var_mask[g]; an empty mask gives 1.0
+ *   mz == NULL:
+ *     s_g = (c_k0 * r_k0) + (c_k1 * r_k1) + ...  over the group's roots that exist, ascending k; the factor only with coef != NULL
+ *     t_g = jac_g * s_g;   a_g = |t_g|
+ *   mz != NULL, (s_k, c_k) the phase of root k at weight_freq from the proposal's own times, as in the projected step:
+ *     term = coef ? coef_k * r_k : r_k;   re_g = re_g + term * c_k;   im_g = im_g + term * s_k      (left folds over the group's roots)
+ *     tre_g = jac_g * re_g;   tim_g = jac_g * im_g;   q_g = tre_g * tre_g + tim_g * tim_g;   a_g = sqrt(q_g)
+ *   a' = the left fold of rho_g * a_g over ascending g among the groups that have a root that exists (reweight == NULL: of a_g, no
+ *        product is formed); no root at all: 0.0.  A group without such a root takes no part anywhere.
+ * A proposal at which an existing root, any t_g (any tre_g, tim_g or q_g) or a' is not finite counts as f = 0: all its roots are taken
+ * as 0.0 and a' = 0, selected and never multiplied.
+ * The accept rule, FDG_CHAIN_INIT, n_accept and the selection of x, fac, root, a are the plain step's, on the same Philox counter.
+ * FDG_CHAIN_MEASURE, on the state AFTER the selection, jac_g from the state's fac:
+ *     d = 1 / (a + gamma)
+ *   mz == NULL:  sum[k][b] += (jac_g(k) * r_k) * d  for every root k that exists,  sum[R][b] += d
+ *   mz != NULL:  w = (jac_g(k) * r_k) * d;  sum[2 (f R + k)][b] += w * c,  sum[2 (f R + k) + 1][b] += w * s  for every f, the phases
+ *                from the state's times;  sum[2 F R][b] += d
+ * The columns of a root that does not exist are never written.  A variable of no group moves and is copied like any other and enters
+ * no jacobian.
+ *
+ * With n_group == 1, a mask of all n_dim variables and reweight == NULL the state and the sums are bit for bit those of
+ * fdg_[mc_]chain_step_device (mz == NULL) or of fdg_[mc_]chain_step_device_matsubara (mz != NULL).
+ * The result is a function of the arguments only, as for the plain step (FDG_ROOT_SCRATCH_MB, launch shape, shards).
+ * FDG_E_INVALID: everything the plain step refuses and, with mz != NULL, everything the projected step refuses of its descriptor; a
+ * NULL cg, root_group or var_mask; n_group == 0; root_group[k] >= n_group for a root that exists; a mask bit at or above n_dim; a
+ * reweight that is not finite or <= 0.  FDG_E_UNSUPPORTED: those calls' cases, n_group > FDG_WEIGHT_GROUP_MAX.  All before any device
+ * work. */
+typedef struct fdg_chain_groups {
+  uint32_t n_group;             /* 1 .. FDG_WEIGHT_GROUP_MAX */
+  const uint32_t *root_group;   /* HOST [n_root]: the group of root k (ignored for FDG_NO_ROOT roots) */
+  const uint64_t *var_mask;     /* HOST [n_group]: bit d set = variable d belongs to the group; an empty mask is allowed */
+  const double *reweight;       /* HOST [n_group], finite and > 0, or NULL: no factor is applied */
+} fdg_chain_groups;
+int fdg_chain_step_device_grouped(fdg_graph *g, const double *d_xp, int64_t xp_col_stride, const double *d_facp, uint32_t n_col,
+                                  uint32_t n_dim, const double *coef, double gamma, uint64_t seed, uint64_t sample_offset, unsigned flags,
+                                  double *d_x, int64_t x_col_stride, double *d_fac, double *d_root, double *d_a, double *d_sum,
+                                  int32_t *d_n_accept, const fdg_chain_matsubara *mz, const fdg_chain_groups *cg, int64_t n_walker,
+                                  void *stream);
+int fdg_mc_chain_step_device_grouped(fdg_graph *g, const double *d_xp, int64_t xp_col_stride, double kF, double beta, double lambda,
+                                     const double *d_facp, uint32_t n_col, uint32_t n_dim, const double *coef, double gamma, uint64_t seed,
+                                     uint64_t sample_offset, unsigned flags, double *d_x, int64_t x_col_stride, double *d_fac,
+                                     double *d_root, double *d_a, double *d_sum, int32_t *d_n_accept, const fdg_chain_matsubara *mz,
+                                     const fdg_chain_groups *cg, int64_t n_walker, void *stream);
+
 /* Device workspace control: the interpreter keeps per-sample overflow slots in
  * an HBM panel owned by the handle; it is sized on first use for the number of
  * resident waves.  This releases it (and any loaded module). */
