@@ -716,60 +716,53 @@ class GraphHandle:
     def chain_step_device(self, d_xp: int, xpc: int, d_facp: int, n_col: int, n_dim: int, coef, gamma: float, seed: int, sample_offset: int,
                           flags: int, d_x: int, xc: int, d_fac: int, d_root: int, d_a: int, d_sum: int, d_n_accept: int, B: int,
                           stream: int = 0):
-        c = self._coef(coef)
-        check(lib().fdg_chain_step_device(self._h, d_xp or None, xpc, d_facp or None, n_col, n_dim, None if c is None else c.ctypes.data,
-                                          gamma, seed, sample_offset, flags, d_x or None, xc, d_fac or None, d_root or None, d_a or None,
-                                          d_sum or None, d_n_accept or None, B, stream))
+        self._chain_step("", None, d_xp, xpc, d_facp, n_col, n_dim, coef, gamma, seed, sample_offset, flags, d_x, xc, d_fac, d_root, d_a, d_sum,
+                         d_n_accept, B, stream)
 
     def mc_chain_step_device(self, d_xp: int, xpc: int, kF, beta, lam, d_facp: int, n_col: int, n_dim: int, coef, gamma: float, seed: int,
                              sample_offset: int, flags: int, d_x: int, xc: int, d_fac: int, d_root: int, d_a: int, d_sum: int,
                              d_n_accept: int, B: int, stream: int = 0):
-        c = self._coef(coef)
-        check(lib().fdg_mc_chain_step_device(self._h, d_xp or None, xpc, kF, beta, lam, d_facp or None, n_col, n_dim,
-                                             None if c is None else c.ctypes.data, gamma, seed, sample_offset, flags, d_x or None, xc,
-                                             d_fac or None, d_root or None, d_a or None, d_sum or None, d_n_accept or None, B, stream))
+        self._chain_step("", (kF, beta, lam), d_xp, xpc, d_facp, n_col, n_dim, coef, gamma, seed, sample_offset, flags, d_x, xc, d_fac, d_root,
+                         d_a, d_sum, d_n_accept, B, stream)
 
     # the same steps with the Matsubara projection in the weight and in the measurement: desc = make_chain_matsubara(...)[0], d_sum
     # [2 n_freq n_root + 1, B] (fdg.h, "Markov chain with a Matsubara-projected weight and measurement")
     def chain_step_device_matsubara(self, d_xp: int, xpc: int, d_facp: int, n_col: int, n_dim: int, coef, gamma: float, seed: int,
                                     sample_offset: int, flags: int, d_x: int, xc: int, d_fac: int, d_root: int, d_a: int, d_sum: int,
                                     d_n_accept: int, desc, B: int, stream: int = 0):
-        c = self._coef(coef)
-        check(lib().fdg_chain_step_device_matsubara(self._h, d_xp or None, xpc, d_facp or None, n_col, n_dim,
-                                                    None if c is None else c.ctypes.data, gamma, seed, sample_offset, flags, d_x or None, xc,
-                                                    d_fac or None, d_root or None, d_a or None, d_sum or None, d_n_accept or None,
-                                                    None if desc is None else C.addressof(desc), B, stream))
+        self._chain_step("_matsubara", None, d_xp, xpc, d_facp, n_col, n_dim, coef, gamma, seed, sample_offset, flags, d_x, xc, d_fac, d_root,
+                         d_a, d_sum, d_n_accept, B, stream, desc)
 
     def mc_chain_step_device_matsubara(self, d_xp: int, xpc: int, kF, beta, lam, d_facp: int, n_col: int, n_dim: int, coef, gamma: float,
                                        seed: int, sample_offset: int, flags: int, d_x: int, xc: int, d_fac: int, d_root: int, d_a: int,
                                        d_sum: int, d_n_accept: int, desc, B: int, stream: int = 0):
-        c = self._coef(coef)
-        check(lib().fdg_mc_chain_step_device_matsubara(self._h, d_xp or None, xpc, kF, beta, lam, d_facp or None, n_col, n_dim,
-                                                       None if c is None else c.ctypes.data, gamma, seed, sample_offset, flags,
-                                                       d_x or None, xc, d_fac or None, d_root or None, d_a or None, d_sum or None,
-                                                       d_n_accept or None, None if desc is None else C.addressof(desc), B, stream))
+        self._chain_step("_matsubara", (kF, beta, lam), d_xp, xpc, d_facp, n_col, n_dim, coef, gamma, seed, sample_offset, flags, d_x, xc, d_fac,
+                         d_root, d_a, d_sum, d_n_accept, B, stream, desc)
 
     # the same steps with weight groups: groups = make_chain_groups(...)[0]; desc = make_chain_matsubara(...)[0] or None (no projection),
     # d_sum as in the plain or the projected step (fdg.h, "Markov chain with weight groups and reweighting between orders")
     def chain_step_device_grouped(self, d_xp: int, xpc: int, d_facp: int, n_col: int, n_dim: int, coef, gamma: float, seed: int,
                                   sample_offset: int, flags: int, d_x: int, xc: int, d_fac: int, d_root: int, d_a: int, d_sum: int,
                                   d_n_accept: int, desc, groups, B: int, stream: int = 0):
-        c = self._coef(coef)
-        check(lib().fdg_chain_step_device_grouped(self._h, d_xp or None, xpc, d_facp or None, n_col, n_dim,
-                                                  None if c is None else c.ctypes.data, gamma, seed, sample_offset, flags, d_x or None, xc,
-                                                  d_fac or None, d_root or None, d_a or None, d_sum or None, d_n_accept or None,
-                                                  None if desc is None else C.addressof(desc),
-                                                  None if groups is None else C.addressof(groups), B, stream))
+        self._chain_step("_grouped", None, d_xp, xpc, d_facp, n_col, n_dim, coef, gamma, seed, sample_offset, flags, d_x, xc, d_fac, d_root,
+                         d_a, d_sum, d_n_accept, B, stream, desc, groups)
 
     def mc_chain_step_device_grouped(self, d_xp: int, xpc: int, kF, beta, lam, d_facp: int, n_col: int, n_dim: int, coef, gamma: float,
                                      seed: int, sample_offset: int, flags: int, d_x: int, xc: int, d_fac: int, d_root: int, d_a: int,
                                      d_sum: int, d_n_accept: int, desc, groups, B: int, stream: int = 0):
+        self._chain_step("_grouped", (kF, beta, lam), d_xp, xpc, d_facp, n_col, n_dim, coef, gamma, seed, sample_offset, flags, d_x, xc, d_fac,
+                         d_root, d_a, d_sum, d_n_accept, B, stream, desc, groups)
+
+    def _chain_step(self, entry: str, mc, d_xp, xpc, d_facp, n_col, n_dim, coef, gamma, seed, sample_offset, flags, d_x, xc, d_fac, d_root, d_a,
+                    d_sum, d_n_accept, B, stream=0, desc=None, groups=None):
+        """fdg_[mc_]chain_step_device + ``entry``: ``mc`` None (the leaf form) or ``(kF, beta, lam)``; ``entry`` "" takes no descriptor,
+        "_matsubara" ``desc`` and "_grouped" ``desc`` and ``groups`` (each None: a null pointer)."""
         c = self._coef(coef)
-        check(lib().fdg_mc_chain_step_device_grouped(self._h, d_xp or None, xpc, kF, beta, lam, d_facp or None, n_col, n_dim,
-                                                     None if c is None else c.ctypes.data, gamma, seed, sample_offset, flags,
-                                                     d_x or None, xc, d_fac or None, d_root or None, d_a or None, d_sum or None,
-                                                     d_n_accept or None, None if desc is None else C.addressof(desc),
-                                                     None if groups is None else C.addressof(groups), B, stream))
+        fn = getattr(lib(), ("fdg_chain_step_device" if mc is None else "fdg_mc_chain_step_device") + entry)
+        descs = {"": (), "_matsubara": (desc,), "_grouped": (desc, groups)}[entry]
+        check(fn(self._h, d_xp or None, xpc, *(mc or ()), d_facp or None, n_col, n_dim, None if c is None else c.ctypes.data, gamma, seed,
+                 sample_offset, flags, d_x or None, xc, d_fac or None, d_root or None, d_a or None, d_sum or None, d_n_accept or None,
+                 *(None if d is None else C.addressof(d) for d in descs), B, stream))
 
     def _coef(self, coef):
         if coef is None:

@@ -6,16 +6,17 @@
 // likewise, so n_root = 180 and n_dim = 64 cost loads, not registers.  Nothing here touches the kernels of fdg_binned.hip: the
 // sampler's arithmetic of one variable is restated below (chain_draw), the same operations in the same order, so the bits are its.
 //
-// The Matsubara-projected step (fdg_[mc_]chain_step_device_matsubara) reuses propose, the evaluation and reduce; its
-// select kernel fdg_chain_select_mz folds the roots with the phase of the weight frequency (a' = |jac' sum_k c_k r_k e^{i w tau_k}|)
-// and measures every root at every frequency.  Roots outside, frequencies inside, x = tau / beta once per root; the phase is
-// fdg_matsubara.h's, so a numpy restatement gives the same bits.
+// All six step entries run the one select kernel fdg_chain_select<MZ>.  It gives every group of roots the jacobian of its own
+// variables and a reweight factor: a' = sum_g rho_g |jac_g s_g| (fdg_[mc_]chain_step_device_grouped).  It walks the
+// groups outside and a group's roots inside: the lists of the roots are uploaded sorted by (group, root), so a group is one contiguous
+// range, and the groups' ranges, masks and factors are a kernel argument by value (ChainGroups).  jac_g is one pass over the group's
+// variables, made anew for every group: a product per group in a register, not an array of them.  A call without groups is one
+// group of every live root and every variable without a factor, built on the host: a' = |jac' s'|, the same bits.
 //
-// The grouped step (fdg_[mc_]chain_step_device_grouped) gives every group of roots the jacobian of its own variables and
-// a reweight factor: a' = sum_g rho_g |jac_g s_g|.  Its select kernel fdg_chain_select_grp<MZ> walks the groups outside and a group's
-// roots inside: the lists of the roots are uploaded sorted by (group, root), so a group is one contiguous range, and the groups'
-// ranges, masks and factors are a kernel argument by value (ChainGroups).  jac_g is one pass over the group's variables, made anew
-// for every group: a product per group in a register, not an array of them.
+// With MZ (fdg_[mc_]chain_step_device_matsubara, or a grouped call with a projection) a group's roots are folded with
+// the phase of the weight frequency (s_g = sum_k c_k r_k e^{i w tau_k}) and every root is measured at every frequency.  Roots
+// outside, frequencies inside, x = tau / beta once per root; the phase is fdg_matsubara.h's, so a numpy restatement gives the same
+// bits.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,7 +34,7 @@ namespace {
 
 struct ChainCols { uint32_t c[FDG_VEGAS_DIM_MAX]; };      // the column of x each variable is written to (a kernel argument, by value)
 
-// The groups of the grouped step (a kernel argument, by value): the live roots of group g are the entries start[g] .. start[g + 1] - 1
+// The groups of a step (a kernel argument, by value): the live roots of group g are the entries start[g] .. start[g + 1] - 1
 // of the sorted lists, mask[g] its variables, rho[g] its reweight factor (read only where the call has one).
 struct ChainGroups {
   uint32_t n;
@@ -75,184 +76,6 @@ fdg_chain_propose(const double *__restrict__ grid, uint32_t D, uint32_t G, Chain
   }
 }
 
-// One chunk of n walkers whose proposals' roots lie column-major in `roots` (leading dimension ld).  Every array pointer is already
-// moved to the chunk's first walker; nw = n_walker is the column stride of fac, root and sum; off = sample_offset + the chunk's start.
-// kidx[0 .. n_live) are the roots that exist, ascending, cf their factors (null: 1).
-__global__ void __launch_bounds__(256)
-fdg_chain_select(const double *__restrict__ roots, long ld, long n, const uint32_t *__restrict__ kidx, const double *__restrict__ cf,
-                 uint32_t n_live, const double *__restrict__ xp, long xpc, const double *__restrict__ facp, uint32_t n_col, uint32_t D,
-                 long nw, double gamma, uint64_t seed, uint64_t off, uint32_t flags, double *__restrict__ x, long xc,
-                 double *__restrict__ fac, double *__restrict__ root, double *__restrict__ a, double *__restrict__ sum, uint32_t R,
-                 int32_t *__restrict__ n_accept) {
-  const long b = blockIdx.x * 256L + threadIdx.x;
-  if (b >= n) return;
-  const bool init = (flags & FDG_CHAIN_INIT) != 0, meas = (flags & FDG_CHAIN_MEASURE) != 0;
-  // the fold: jac', s', t', a'
-  double jp = 0.0;
-  for (uint32_t d = 0; d < D; ++d) {
-    const double f = facp[(size_t)d * (size_t)nw + (size_t)b];
-    jp = d ? jp * f : f;
-  }
-  double s = 0.0;
-  bool bad = false;
-  for (uint32_t j = 0; j < n_live; ++j) {
-    const double r = roots[(size_t)kidx[j] * (size_t)ld + (size_t)b];
-    bad = bad || !std::isfinite(r);
-    const double term = cf ? cf[j] * r : r;
-    s = j ? s + term : term;
-  }
-  const double tp = jp * s;
-  bad = bad || !std::isfinite(tp);
-  const double ap = bad ? 0.0 : fabs(tp);
-  // the accept rule
-  const double a0 = init ? 0.0 : a[b];
-  bool acc = true;
-  if (!init) {
-    const double u = fdg_philox_u53(off + (uint64_t)b, FDG_VEGAS_DIM_MAX, seed);
-    acc = u * (a0 + gamma) < (ap + gamma);
-  }
-  // the selection
-  double jac = jp;
-  if (acc) {
-    for (uint32_t c = 0; c < n_col; ++c) x[(long)c * xc + b] = xp[(long)c * xpc + b];
-    for (uint32_t d = 0; d < D; ++d) {
-      const size_t at = (size_t)d * (size_t)nw + (size_t)b;
-      fac[at] = facp[at];
-    }
-    a[b] = ap;
-    if (n_accept) n_accept[b] = n_accept[b] + 1;
-  } else if (meas) {
-    for (uint32_t d = 0; d < D; ++d) {
-      const double f = fac[(size_t)d * (size_t)nw + (size_t)b];
-      jac = d ? jac * f : f;
-    }
-  }
-  if (!acc && !meas) return;
-  // the second walk over the roots: select, and measure on the state after the selection
-  const double dd = 1.0 / ((acc ? ap : a0) + gamma);
-  for (uint32_t j = 0; j < n_live; ++j) {
-    const uint32_t k = kidx[j];
-    const size_t at = (size_t)k * (size_t)nw + (size_t)b;
-    double r;
-    if (acc) {
-      const double rp = roots[(size_t)k * (size_t)ld + (size_t)b];
-      r = bad ? 0.0 : rp;
-      root[at] = r;
-    } else {
-      r = root[at];
-    }
-    if (meas) {
-      const double w = jac * r;
-      sum[at] = sum[at] + w * dd;
-    }
-  }
-  if (meas) {
-    const size_t at = (size_t)R * (size_t)nw + (size_t)b;
-    sum[at] = sum[at] + dd;
-  }
-}
-
-// fdg_chain_select with the Matsubara projection in the weight and in the measurement.  cin[j], cout[j] are the columns of xp / x
-// that hold the two times of live root j, mult[f] the multiplier of frequency f (matsubara_multiplier, formed on the host), wf the
-// frequency of the weight.  sum is [2 F R + 1][nw]: column 2 (f R + k) the real part of root k at frequency f, the next one the
-// imaginary part, the last one d.  Everything indexed by j or f is wave-uniform.
-__global__ void __launch_bounds__(256)
-fdg_chain_select_mz(const double *__restrict__ roots, long ld, long n, const uint32_t *__restrict__ kidx, const double *__restrict__ cf,
-                    uint32_t n_live, const uint32_t *__restrict__ cin, const uint32_t *__restrict__ cout, const double *__restrict__ mult,
-                    uint32_t F, uint32_t wf, double beta, const double *__restrict__ xp, long xpc, const double *__restrict__ facp,
-                    uint32_t n_col, uint32_t D, long nw, double gamma, uint64_t seed, uint64_t off, uint32_t flags, double *__restrict__ x,
-                    long xc, double *__restrict__ fac, double *__restrict__ root, double *__restrict__ a, double *__restrict__ sum, uint32_t R,
-                    int32_t *__restrict__ n_accept) {
-  const long b = blockIdx.x * 256L + threadIdx.x;
-  if (b >= n) return;
-  const bool init = (flags & FDG_CHAIN_INIT) != 0, meas = (flags & FDG_CHAIN_MEASURE) != 0;
-  // the fold: jac', (re', im') at the weight frequency, a'
-  double jp = 0.0;
-  for (uint32_t d = 0; d < D; ++d) {
-    const double f = facp[(size_t)d * (size_t)nw + (size_t)b];
-    jp = d ? jp * f : f;
-  }
-  const double mw = mult[wf];
-  double re = 0.0, im = 0.0;
-  bool bad = false;
-  for (uint32_t j = 0; j < n_live; ++j) {
-    const double r = roots[(size_t)kidx[j] * (size_t)ld + (size_t)b];
-    bad = bad || !std::isfinite(r);
-    const double tau = xp[(long)cout[j] * xpc + b] - xp[(long)cin[j] * xpc + b];
-    const double xt = tau / beta;
-    double sn, cs;
-    matsubara_phase_of(xt, mw, sn, cs);
-    const double term = cf ? cf[j] * r : r;
-    const double pr = term * cs, pi = term * sn;
-    re = j ? re + pr : pr;
-    im = j ? im + pi : pi;
-  }
-  const double tre = jp * re, tim = jp * im;
-  bad = bad || !std::isfinite(tre) || !std::isfinite(tim);
-  const double q0 = tre * tre, q1 = tim * tim;
-  const double q = q0 + q1;
-  bad = bad || !std::isfinite(q);
-  const double ap = bad ? 0.0 : sqrt(q);
-  // the accept rule
-  const double a0 = init ? 0.0 : a[b];
-  bool acc = true;
-  if (!init) {
-    const double u = fdg_philox_u53(off + (uint64_t)b, FDG_VEGAS_DIM_MAX, seed);
-    acc = u * (a0 + gamma) < (ap + gamma);
-  }
-  // the selection
-  double jac = jp;
-  if (acc) {
-    for (uint32_t c = 0; c < n_col; ++c) x[(long)c * xc + b] = xp[(long)c * xpc + b];
-    for (uint32_t d = 0; d < D; ++d) {
-      const size_t at = (size_t)d * (size_t)nw + (size_t)b;
-      fac[at] = facp[at];
-    }
-    a[b] = ap;
-    if (n_accept) n_accept[b] = n_accept[b] + 1;
-  } else if (meas) {
-    for (uint32_t d = 0; d < D; ++d) {
-      const double f = fac[(size_t)d * (size_t)nw + (size_t)b];
-      jac = d ? jac * f : f;
-    }
-  }
-  if (!acc && !meas) return;
-  // the second walk over the roots: select, and measure every frequency on the state after the selection (whose times are the
-  // proposal's after an acceptance: the same bits, read where they were not just written)
-  const double dd = 1.0 / ((acc ? ap : a0) + gamma);
-  const double *tp = acc ? xp : x;
-  const long tpc = acc ? xpc : xc;
-  for (uint32_t j = 0; j < n_live; ++j) {
-    const uint32_t k = kidx[j];
-    const size_t at = (size_t)k * (size_t)nw + (size_t)b;
-    double r;
-    if (acc) {
-      const double rp = roots[(size_t)k * (size_t)ld + (size_t)b];
-      r = bad ? 0.0 : rp;
-      root[at] = r;
-    } else {
-      r = root[at];
-    }
-    if (meas) {
-      const double jr = jac * r;
-      const double w = jr * dd;
-      const double tau = tp[(long)cout[j] * tpc + b] - tp[(long)cin[j] * tpc + b];
-      const double xt = tau / beta;
-      for (uint32_t f = 0; f < F; ++f) {
-        double sn, cs;
-        matsubara_phase_of(xt, mult[f], sn, cs);
-        const size_t o = (size_t)(2u * (f * R + k)) * (size_t)nw + (size_t)b;
-        sum[o] = sum[o] + w * cs;
-        sum[o + (size_t)nw] = sum[o + (size_t)nw] + w * sn;
-      }
-    }
-  }
-  if (meas) {
-    const size_t at = (size_t)(2u * F * R) * (size_t)nw + (size_t)b;
-    sum[at] = sum[at] + dd;
-  }
-}
-
 // The jacobian of one group for walker b: the left fold of f[d][b] over ascending d with bit d in mask; an empty mask gives 1.0.
 __device__ __forceinline__ double chain_group_jac(const double *__restrict__ f, uint64_t mask, uint32_t D, long nw, long b) {
   double j = 1.0;
@@ -266,17 +89,22 @@ __device__ __forceinline__ double chain_group_jac(const double *__restrict__ f, 
   return j;
 }
 
-// fdg_chain_select / fdg_chain_select_mz (MZ) with weight groups.  kidx, cf, cin, cout are sorted by (group, root); a group without a
-// live root is skipped altogether.  The arguments of the projection are not read without MZ.  Everything indexed by g, j or f is
-// wave-uniform; the only per-lane values that live across a group are ap and bad.
+// One chunk of n walkers whose proposals' roots lie column-major in `roots` (leading dimension ld).  Every array pointer is already
+// moved to the chunk's first walker; nw = n_walker is the column stride of fac, root and sum; off = sample_offset + the chunk's start.
+// kidx are the roots that exist, cf their factors (null: 1), both sorted by (group, root); a group without a live root is skipped
+// altogether.  Without MZ sum is [R + 1][nw], column k root k's, the last one d, and the arguments of the projection are not read.
+// With MZ cin[j], cout[j] are the columns of xp / x that hold the two times of live root j, mult[f] the multiplier of frequency f
+// (matsubara_multiplier, formed on the host), wf the frequency of the weight, and sum is [2 F R + 1][nw]: column 2 (f R + k) the real
+// part of root k at frequency f, the next one the imaginary part, the last one d.  Everything indexed by g, j or f is wave-uniform;
+// the only per-lane values that live across a group are ap and bad.
 template <bool MZ>
 __global__ void __launch_bounds__(256)
-fdg_chain_select_grp(const double *__restrict__ roots, long ld, long n, const uint32_t *__restrict__ kidx, const double *__restrict__ cf,
-                     ChainGroups cg, uint32_t has_rho, const uint32_t *__restrict__ cin, const uint32_t *__restrict__ cout,
-                     const double *__restrict__ mult, uint32_t F, uint32_t wf, double beta, const double *__restrict__ xp, long xpc,
-                     const double *__restrict__ facp, uint32_t n_col, uint32_t D, long nw, double gamma, uint64_t seed, uint64_t off,
-                     uint32_t flags, double *__restrict__ x, long xc, double *__restrict__ fac, double *__restrict__ root,
-                     double *__restrict__ a, double *__restrict__ sum, uint32_t R, int32_t *__restrict__ n_accept) {
+fdg_chain_select(const double *__restrict__ roots, long ld, long n, const uint32_t *__restrict__ kidx, const double *__restrict__ cf,
+                 ChainGroups cg, uint32_t has_rho, const uint32_t *__restrict__ cin, const uint32_t *__restrict__ cout,
+                 const double *__restrict__ mult, uint32_t F, uint32_t wf, double beta, const double *__restrict__ xp, long xpc,
+                 const double *__restrict__ facp, uint32_t n_col, uint32_t D, long nw, double gamma, uint64_t seed, uint64_t off,
+                 uint32_t flags, double *__restrict__ x, long xc, double *__restrict__ fac, double *__restrict__ root,
+                 double *__restrict__ a, double *__restrict__ sum, uint32_t R, int32_t *__restrict__ n_accept) {
   const long b = blockIdx.x * 256L + threadIdx.x;
   if (b >= n) return;
   const bool init = (flags & FDG_CHAIN_INIT) != 0, meas = (flags & FDG_CHAIN_MEASURE) != 0;
@@ -493,12 +321,14 @@ int check_chain_groups(const fdg_graph *g, const ChainCall &c, const fdg_chain_g
   return FDG_OK;
 }
 
-// The body of all step calls (caller holds g->mu, stream bound): eval(c0, n, roots, ld) writes the roots of the proposals of walkers
-// c0 .. c0 + n - 1 column-major into roots.  The chunk is the accumulate calls' (FDG_ROOT_SCRATCH_MB); no result depends on it.
-// mz: the projected step (fdg_chain_select_mz); its multipliers and time columns lie behind the plain step's uploads.
-// cg: the grouped step (fdg_chain_select_grp, with or without mz); the lists are then sorted by (group, root).
-template <class Eval>
-int run_chain(fdg_graph *g, const ChainCall &c, Eval eval, const fdg_chain_matsubara *mz, const fdg_chain_groups *cg) {
+struct ChainMc { double kF, beta, lambda; };               // the parameters of the Monte-Carlo form's leaves
+
+// The work of all step calls (caller holds g->mu, stream bound), chunk by chunk: the roots of the proposals column-major into the
+// root scratch, by fdg_run_locked or, with mc, fdg_mc_run_locked, then fdg_chain_select.  The chunk is the accumulate calls'
+// (FDG_ROOT_SCRATCH_MB); no result depends on it.
+// mz: the projected step; its multipliers and time columns lie behind the plain step's uploads.
+// cg: the grouped step; the lists are then sorted by (group, root).  Without cg the roots are one group of every variable.
+int run_chain(fdg_graph *g, const ChainCall &c, const ChainMc *mc, const fdg_chain_matsubara *mz, const fdg_chain_groups *cg) {
   const uint32_t R = g->prog.R;
   const hipStream_t st = (hipStream_t)c.stream;
   long Bc = std::max<long>(64, (long)((g->cfg.root_scratch_mb << 20) / (8ull * std::max<uint32_t>(R, 1u))) & ~63l);
@@ -526,6 +356,10 @@ int run_chain(fdg_graph *g, const ChainCall &c, Eval eval, const fdg_chain_matsu
       grp.mask[q] = cg->var_mask[q];
       grp.rho[q] = cg->reweight ? cg->reweight[q] : 1.0;
     }
+  } else {
+    grp.n = 1;
+    grp.start[1] = (uint32_t)hk.size();
+    grp.mask[0] = c.n_dim < 64 ? (1ull << c.n_dim) - 1ull : ~0ull;
   }
   for (uint32_t k : hk) hc.push_back(c.coef ? c.coef[k] : 1.0);
   const uint32_t n_live = (uint32_t)hk.size();
@@ -533,10 +367,14 @@ int run_chain(fdg_graph *g, const ChainCall &c, Eval eval, const fdg_chain_matsu
     HIP_TRY(hipMemcpyAsync(d_coef, hc.data(), n_live * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_kidx, hk.data(), n_live * sizeof(uint32_t), hipMemcpyHostToDevice, st));
   }
-  // the projected step: the multiplier of every frequency, then the two time columns of every root that exists
-  double *d_mult = (double *)((char *)g->d_ws2 + root_bytes + plain_bytes);
-  uint32_t *d_cin = (uint32_t *)(d_mult + FDG_MATSUBARA_FREQ_MAX), *d_cout = d_cin + std::max<uint32_t>(R, 1u);
+  // the projected step: the multiplier of every frequency, then the two time columns of every root that exists; without a
+  // projection the kernel reads none of them
+  double *d_mult = nullptr;
+  uint32_t *d_cin = nullptr, *d_cout = nullptr;
   if (mz) {
+    d_mult = (double *)((char *)g->d_ws2 + root_bytes + plain_bytes);
+    d_cin = (uint32_t *)(d_mult + FDG_MATSUBARA_FREQ_MAX);
+    d_cout = d_cin + std::max<uint32_t>(R, 1u);
     std::vector<double> hm(mz->n_freq);
     std::vector<uint32_t> hin, hout;
     for (uint32_t f = 0; f < mz->n_freq; ++f) hm[f] = matsubara_multiplier(mz->freq[f], mz->fermionic);
@@ -550,50 +388,56 @@ int run_chain(fdg_graph *g, const ChainCall &c, Eval eval, const fdg_chain_matsu
   for (long c0 = 0; c0 < (long)c.B; c0 += Bc) {
     const long n = std::min<long>(Bc, (long)c.B - c0);
     if (n_live) {
-      rc = eval(c0, n, roots, Bc);
+      const double *xp = c.d_xp + c0;
+      if (mc) {
+        const double *T = xp + (int64_t)(g->lt_hdr[2] * g->lt_hdr[3]) * c.xpc;
+        rc = fdg_mc_run_locked(g, 0, xp, 1, c.xpc, T, 1, c.xpc, mc->kF, mc->beta, mc->lambda, roots, 1, Bc, nullptr, nullptr, n, st);
+      } else {
+        rc = fdg_run_locked(g, 0, xp, 1, c.xpc, roots, 1, Bc, nullptr, nullptr, n, st, 0, 0);
+      }
       if (rc) return rc;
     }
-    if (cg && mz)
-      hipLaunchKernelGGL(fdg_chain_select_grp<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, roots, Bc, n, d_kidx,
-                         c.coef ? d_coef : nullptr, grp, cg->reweight ? 1u : 0u, d_cin, d_cout, d_mult, mz->n_freq, mz->weight_freq, mz->beta,
-                         c.d_xp + c0, (long)c.xpc, c.d_facp + c0, c.n_col, c.n_dim, (long)c.B, c.gamma, c.seed, c.offset + (uint64_t)c0,
-                         (uint32_t)c.flags, c.d_x + c0, (long)c.xc, c.d_fac + c0, c.d_root + c0, c.d_a + c0,
-                         c.d_sum ? c.d_sum + c0 : nullptr, R, c.d_n_accept ? c.d_n_accept + c0 : nullptr);
-    else if (cg)
-      hipLaunchKernelGGL(fdg_chain_select_grp<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, roots, Bc, n, d_kidx,
-                         c.coef ? d_coef : nullptr, grp, cg->reweight ? 1u : 0u, nullptr, nullptr, nullptr, 0u, 0u, 1.0, c.d_xp + c0,
-                         (long)c.xpc, c.d_facp + c0, c.n_col, c.n_dim, (long)c.B, c.gamma, c.seed, c.offset + (uint64_t)c0,
-                         (uint32_t)c.flags, c.d_x + c0, (long)c.xc, c.d_fac + c0, c.d_root + c0, c.d_a + c0,
-                         c.d_sum ? c.d_sum + c0 : nullptr, R, c.d_n_accept ? c.d_n_accept + c0 : nullptr);
-    else if (mz)
-      hipLaunchKernelGGL(fdg_chain_select_mz, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, roots, Bc, n, d_kidx,
-                         c.coef ? d_coef : nullptr, n_live, d_cin, d_cout, d_mult, mz->n_freq, mz->weight_freq, mz->beta, c.d_xp + c0,
-                         (long)c.xpc, c.d_facp + c0, c.n_col, c.n_dim, (long)c.B, c.gamma, c.seed, c.offset + (uint64_t)c0,
-                         (uint32_t)c.flags, c.d_x + c0, (long)c.xc, c.d_fac + c0, c.d_root + c0, c.d_a + c0,
-                         c.d_sum ? c.d_sum + c0 : nullptr, R, c.d_n_accept ? c.d_n_accept + c0 : nullptr);
-    else
-      hipLaunchKernelGGL(fdg_chain_select, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, roots, Bc, n, d_kidx, c.coef ? d_coef : nullptr,
-                         n_live, c.d_xp + c0, (long)c.xpc, c.d_facp + c0, c.n_col, c.n_dim, (long)c.B, c.gamma, c.seed,
-                         c.offset + (uint64_t)c0, (uint32_t)c.flags, c.d_x + c0, (long)c.xc, c.d_fac + c0, c.d_root + c0, c.d_a + c0,
-                         c.d_sum ? c.d_sum + c0 : nullptr, R, c.d_n_accept ? c.d_n_accept + c0 : nullptr);
+    hipLaunchKernelGGL((mz ? fdg_chain_select<true> : fdg_chain_select<false>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, roots,
+                       Bc, n, d_kidx, c.coef ? d_coef : nullptr, grp, cg && cg->reweight ? 1u : 0u, d_cin, d_cout, d_mult,
+                       mz ? mz->n_freq : 0u, mz ? mz->weight_freq : 0u, mz ? mz->beta : 1.0, c.d_xp + c0, (long)c.xpc, c.d_facp + c0,
+                       c.n_col, c.n_dim, (long)c.B, c.gamma, c.seed, c.offset + (uint64_t)c0, (uint32_t)c.flags, c.d_x + c0, (long)c.xc,
+                       c.d_fac + c0, c.d_root + c0, c.d_a + c0, c.d_sum ? c.d_sum + c0 : nullptr, R,
+                       c.d_n_accept ? c.d_n_accept + c0 : nullptr);
     HIP_TRY(hipGetLastError());
   }
   return FDG_OK;
 }
 
-template <class Check, class Eval>
-int chain_step(fdg_graph *g, const ChainCall &c, Check locked_check, Eval eval, const fdg_chain_matsubara *mz = nullptr,
-               const fdg_chain_groups *cg = nullptr) {
+// Which of the three pairs of entries a call came through: what its descriptors may be.
+enum ChainEntry { CHAIN_PLAIN, CHAIN_MATSUBARA, CHAIN_GROUPED };   // no descriptor; mz required; cg required, mz optional
+
+// The body of the six step entries: the leaf form, or with mc the Monte-Carlo form.  The checks run in this order in every entry,
+// so a call that is wrong in two ways is refused with the same message through each of them.
+int chain_step(fdg_graph *g, const ChainCall &c, const ChainMc *mc, ChainEntry entry, const fdg_chain_matsubara *mz,
+               const fdg_chain_groups *cg) {
+  int rc = check_chain(g, c);
+  if (rc) return rc;
+  if (!mc && c.n_col != g->prog.L) { set_error("n_col is not the graph's number of leaves"); return FDG_E_INVALID; }
+  if (mz || entry == CHAIN_MATSUBARA) {
+    rc = check_chain_mz(g, c, mz);
+    if (rc) return rc;
+  }
+  if (entry == CHAIN_GROUPED) {
+    rc = check_chain_groups(g, c, cg);
+    if (rc) return rc;
+  }
   std::lock_guard<std::mutex> lk(g->mu);
   fdg::KnobScope knob_scope(&g->knobs);
-  int rc = locked_check();
-  if (rc) return rc;
+  if (mc) {
+    if (g->mc_route == 0) { set_error("fdg_graph_specialize_fused has not been called on this handle"); return FDG_E_INVALID; }
+    if (c.n_col != g->lt_hdr[2] * g->lt_hdr[3] + g->lt_hdr[4]) { set_error("n_col is not the tables' n_loop * dim + n_tau"); return FDG_E_INVALID; }
+  }
   if (c.B == 0) return FDG_OK;
   rc = ensure_device(g);
   if (rc) return rc;
   rc = fdg_bind_stream_ws(g, c.stream);
   if (rc) return rc;
-  return run_chain(g, c, eval, mz, cg);
+  return run_chain(g, c, mc, mz, cg);
 }
 
 }  // namespace
@@ -628,15 +472,7 @@ int fdg_chain_step_device(fdg_graph *g, const double *d_xp, int64_t xp_col_strid
                           void *stream) {
   const ChainCall c{d_xp, xp_col_stride, d_facp, n_col, n_dim, coef, gamma, seed, sample_offset, flags, d_x, x_col_stride, d_fac,
                     d_root, d_a, d_sum, d_n_accept, B, stream};
-  const int rc = check_chain(g, c);
-  if (rc) return rc;
-  if (n_col != g->prog.L) { set_error("n_col is not the graph's number of leaves"); return FDG_E_INVALID; }
-  const hipStream_t st = (hipStream_t)stream;
-  return chain_step(
-      g, c, [] { return FDG_OK; },
-      [&](long c0, long n, double *roots, long ld) {
-        return fdg_run_locked(g, 0, d_xp + c0, 1, xp_col_stride, roots, 1, ld, nullptr, nullptr, n, st, 0, 0);
-      });
+  return chain_step(g, c, nullptr, CHAIN_PLAIN, nullptr, nullptr);
 }
 
 int fdg_mc_chain_step_device(fdg_graph *g, const double *d_xp, int64_t xp_col_stride, double kF, double beta, double lambda,
@@ -645,20 +481,8 @@ int fdg_mc_chain_step_device(fdg_graph *g, const double *d_xp, int64_t xp_col_st
                              double *d_a, double *d_sum, int32_t *d_n_accept, int64_t B, void *stream) {
   const ChainCall c{d_xp, xp_col_stride, d_facp, n_col, n_dim, coef, gamma, seed, sample_offset, flags, d_x, x_col_stride, d_fac,
                     d_root, d_a, d_sum, d_n_accept, B, stream};
-  const int rc = check_chain(g, c);
-  if (rc) return rc;
-  const hipStream_t st = (hipStream_t)stream;
-  return chain_step(
-      g, c,
-      [&] {
-        if (g->mc_route == 0) { set_error("fdg_graph_specialize_fused has not been called on this handle"); return FDG_E_INVALID; }
-        if (n_col != g->lt_hdr[2] * g->lt_hdr[3] + g->lt_hdr[4]) { set_error("n_col is not the tables' n_loop * dim + n_tau"); return FDG_E_INVALID; }
-        return FDG_OK;
-      },
-      [&](long c0, long n, double *roots, long ld) {
-        const double *K = d_xp + c0, *T = d_xp + (int64_t)(g->lt_hdr[2] * g->lt_hdr[3]) * xp_col_stride + c0;
-        return fdg_mc_run_locked(g, 0, K, 1, xp_col_stride, T, 1, xp_col_stride, kF, beta, lambda, roots, 1, ld, nullptr, nullptr, n, st);
-      });
+  const ChainMc mc{kF, beta, lambda};
+  return chain_step(g, c, &mc, CHAIN_PLAIN, nullptr, nullptr);
 }
 
 int fdg_chain_step_device_matsubara(fdg_graph *g, const double *d_xp, int64_t xp_col_stride, const double *d_facp, uint32_t n_col,
@@ -667,18 +491,7 @@ int fdg_chain_step_device_matsubara(fdg_graph *g, const double *d_xp, int64_t xp
                                     int32_t *d_n_accept, const fdg_chain_matsubara *mz, int64_t B, void *stream) {
   const ChainCall c{d_xp, xp_col_stride, d_facp, n_col, n_dim, coef, gamma, seed, sample_offset, flags, d_x, x_col_stride, d_fac,
                     d_root, d_a, d_sum, d_n_accept, B, stream};
-  int rc = check_chain(g, c);
-  if (rc) return rc;
-  if (n_col != g->prog.L) { set_error("n_col is not the graph's number of leaves"); return FDG_E_INVALID; }
-  rc = check_chain_mz(g, c, mz);
-  if (rc) return rc;
-  const hipStream_t st = (hipStream_t)stream;
-  return chain_step(
-      g, c, [] { return FDG_OK; },
-      [&](long c0, long n, double *roots, long ld) {
-        return fdg_run_locked(g, 0, d_xp + c0, 1, xp_col_stride, roots, 1, ld, nullptr, nullptr, n, st, 0, 0);
-      },
-      mz);
+  return chain_step(g, c, nullptr, CHAIN_MATSUBARA, mz, nullptr);
 }
 
 int fdg_mc_chain_step_device_matsubara(fdg_graph *g, const double *d_xp, int64_t xp_col_stride, double kF, double beta, double lambda,
@@ -688,23 +501,8 @@ int fdg_mc_chain_step_device_matsubara(fdg_graph *g, const double *d_xp, int64_t
                                        const fdg_chain_matsubara *mz, int64_t B, void *stream) {
   const ChainCall c{d_xp, xp_col_stride, d_facp, n_col, n_dim, coef, gamma, seed, sample_offset, flags, d_x, x_col_stride, d_fac,
                     d_root, d_a, d_sum, d_n_accept, B, stream};
-  int rc = check_chain(g, c);
-  if (rc) return rc;
-  rc = check_chain_mz(g, c, mz);
-  if (rc) return rc;
-  const hipStream_t st = (hipStream_t)stream;
-  return chain_step(
-      g, c,
-      [&] {
-        if (g->mc_route == 0) { set_error("fdg_graph_specialize_fused has not been called on this handle"); return FDG_E_INVALID; }
-        if (n_col != g->lt_hdr[2] * g->lt_hdr[3] + g->lt_hdr[4]) { set_error("n_col is not the tables' n_loop * dim + n_tau"); return FDG_E_INVALID; }
-        return FDG_OK;
-      },
-      [&](long c0, long n, double *roots, long ld) {
-        const double *K = d_xp + c0, *T = d_xp + (int64_t)(g->lt_hdr[2] * g->lt_hdr[3]) * xp_col_stride + c0;
-        return fdg_mc_run_locked(g, 0, K, 1, xp_col_stride, T, 1, xp_col_stride, kF, beta, lambda, roots, 1, ld, nullptr, nullptr, n, st);
-      },
-      mz);
+  const ChainMc mc{kF, beta, lambda};
+  return chain_step(g, c, &mc, CHAIN_MATSUBARA, mz, nullptr);
 }
 
 int fdg_chain_step_device_grouped(fdg_graph *g, const double *d_xp, int64_t xp_col_stride, const double *d_facp, uint32_t n_col,
@@ -714,22 +512,7 @@ int fdg_chain_step_device_grouped(fdg_graph *g, const double *d_xp, int64_t xp_c
                                   void *stream) {
   const ChainCall c{d_xp, xp_col_stride, d_facp, n_col, n_dim, coef, gamma, seed, sample_offset, flags, d_x, x_col_stride, d_fac,
                     d_root, d_a, d_sum, d_n_accept, B, stream};
-  int rc = check_chain(g, c);
-  if (rc) return rc;
-  if (n_col != g->prog.L) { set_error("n_col is not the graph's number of leaves"); return FDG_E_INVALID; }
-  if (mz) {
-    rc = check_chain_mz(g, c, mz);
-    if (rc) return rc;
-  }
-  rc = check_chain_groups(g, c, cg);
-  if (rc) return rc;
-  const hipStream_t st = (hipStream_t)stream;
-  return chain_step(
-      g, c, [] { return FDG_OK; },
-      [&](long c0, long n, double *roots, long ld) {
-        return fdg_run_locked(g, 0, d_xp + c0, 1, xp_col_stride, roots, 1, ld, nullptr, nullptr, n, st, 0, 0);
-      },
-      mz, cg);
+  return chain_step(g, c, nullptr, CHAIN_GROUPED, mz, cg);
 }
 
 int fdg_mc_chain_step_device_grouped(fdg_graph *g, const double *d_xp, int64_t xp_col_stride, double kF, double beta, double lambda,
@@ -739,28 +522,10 @@ int fdg_mc_chain_step_device_grouped(fdg_graph *g, const double *d_xp, int64_t x
                                      const fdg_chain_groups *cg, int64_t B, void *stream) {
   const ChainCall c{d_xp, xp_col_stride, d_facp, n_col, n_dim, coef, gamma, seed, sample_offset, flags, d_x, x_col_stride, d_fac,
                     d_root, d_a, d_sum, d_n_accept, B, stream};
-  int rc = check_chain(g, c);
-  if (rc) return rc;
-  if (mz) {
-    rc = check_chain_mz(g, c, mz);
-    if (rc) return rc;
-  }
-  rc = check_chain_groups(g, c, cg);
-  if (rc) return rc;
-  const hipStream_t st = (hipStream_t)stream;
-  return chain_step(
-      g, c,
-      [&] {
-        if (g->mc_route == 0) { set_error("fdg_graph_specialize_fused has not been called on this handle"); return FDG_E_INVALID; }
-        if (n_col != g->lt_hdr[2] * g->lt_hdr[3] + g->lt_hdr[4]) { set_error("n_col is not the tables' n_loop * dim + n_tau"); return FDG_E_INVALID; }
-        return FDG_OK;
-      },
-      [&](long c0, long n, double *roots, long ld) {
-        const double *K = d_xp + c0, *T = d_xp + (int64_t)(g->lt_hdr[2] * g->lt_hdr[3]) * xp_col_stride + c0;
-        return fdg_mc_run_locked(g, 0, K, 1, xp_col_stride, T, 1, xp_col_stride, kF, beta, lambda, roots, 1, ld, nullptr, nullptr, n, st);
-      },
-      mz, cg);
+  const ChainMc mc{kF, beta, lambda};
+  return chain_step(g, c, &mc, CHAIN_GROUPED, mz, cg);
 }
+
 
 int fdg_chain_reduce_device(const double *d_sum, uint32_t n_root, int64_t B, double *d_out, void *stream) {
   if (B < 0) { set_error("n_walker < 0"); return FDG_E_INVALID; }

@@ -1078,26 +1078,14 @@ def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step,
         def step(mask, off, g, flags):
             capi.chain_propose_device(vmap.d_grid.data_ptr(), D, G, col, n_col, mask, seed, off, x.data_ptr(), B, fac.data_ptr(),
                                       xp.data_ptr(), B, facp.data_ptr(), B, st)
-            tail = (facp.data_ptr(), n_col, D, coef, g, seed, off, flags, x.data_ptr(), B, fac.data_ptr(), root.data_ptr(), a.data_ptr(),
-                    total.data_ptr(), n_acc.data_ptr(), B, st)
-            if wgroups is not None:
-                gdesc, _gkeep = capi.make_chain_groups(wgroups.root_group, wgroups.var_sets, rho)
-                tail = tail[:-2] + (desc, gdesc) + tail[-2:]
-                if tables is None:
-                    handle.chain_step_device_grouped(xp.data_ptr(), B, *tail)
-                else:
-                    handle.mc_chain_step_device_grouped(xp.data_ptr(), B, kF, beta, lam, *tail)
-            elif desc is not None:
-                tail = tail[:-2] + (desc,) + tail[-2:]
-                if tables is None:
-                    handle.chain_step_device_matsubara(xp.data_ptr(), B, *tail)
-                else:
-                    handle.mc_chain_step_device_matsubara(xp.data_ptr(), B, kF, beta, lam, *tail)
-            elif tables is None:
-                handle.chain_step_device(xp.data_ptr(), B, *tail)
-            else:
-                handle.mc_chain_step_device(xp.data_ptr(), B, kF, beta, lam, *tail)
+            handle._chain_step(entry, mc, xp.data_ptr(), B, facp.data_ptr(), n_col, D, coef, g, seed, off, flags, x.data_ptr(), B,
+                               fac.data_ptr(), root.data_ptr(), a.data_ptr(), total.data_ptr(), n_acc.data_ptr(), B, st, desc, gdesc)
 
+        entry = "_grouped" if wgroups is not None else "_matsubara" if desc is not None else ""
+        mc = None if tables is None else (kF, beta, lam)
+        gdesc = None
+        if wgroups is not None:
+            gdesc, _gkeep = capi.make_chain_groups(wgroups.root_group, wgroups.var_sets, rho)
         step(all_mask, int(shard_start), 1.0, capi.FDG_CHAIN_INIT)                       # (gamma enters no result of the placement)
         if wgroups is not None and rho is None:
             # rho_g = 1 / mean_b |jac_g s_g| of the placement, then the placement again on the same counters with rho
@@ -1119,6 +1107,7 @@ def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step,
                     if not (math.isfinite(mean_g[g]) and mean_g[g] > 0.0 and math.isfinite(1.0 / mean_g[g])):
                         raise ValueError(f"the map's estimate of the integral of |s_g| of group {g} is not positive and finite: pass reweight")
                     rho[g] = 1.0 / mean_g[g]
+            gdesc, _gkeep = capi.make_chain_groups(wgroups.root_group, wgroups.var_sets, rho)
             step(all_mask, int(shard_start), 1.0, capi.FDG_CHAIN_INIT)
         if gamma is None:
             sa = a.sum().reshape(1)

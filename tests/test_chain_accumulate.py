@@ -84,7 +84,7 @@ class DeviceChain:
                            ("sum", self.total, (R + 1) * B), ("n_accept", self.n_acc, B)):
             h = t.cpu().numpy()
             assert (h[n:] == (SENT if h.dtype == np.float64 else int(SENT))).all(), name + ": a word past the array was written"
-            out[name] = h[:n].reshape(-1, B).copy() if n != B else h[:n].copy()
+            out[name] = h[:n].reshape(-1, B).copy() if name not in ("a", "n_accept") else h[:n].copy()     # (one row where D or R is 1)
         return out
 
 
@@ -154,6 +154,39 @@ def test_every_step_matches_the_mirror_bit_for_bit(libfdg, cuda, B):
     # a second run gives the same bits
     again = run_both(DeviceChain(f.handle, cuda, grid, col, fixed, B, coef), t, grid, col, fixed, coef, exists, B, 11, 0.37, B, check=False)
     assert_state(again[-1], trace[-1], "second run")
+
+
+def test_one_variable_and_one_root_plain_and_projected(libfdg, cuda):
+    """n_dim = 1, the other end of the variables' masks from the 64 of test_180_roots_and_64_variables: r = (x - 0.3 c) s with x the
+    variable, s = 0.4 and c = 1 fixed, 65 walkers.  INIT and three steps, the first of them not measured, in the leaf form, plain
+    against capi.chain_reference and projected (two frequencies, tau = x - s) against capi.chain_matsubara_reference."""
+    from test_chain_matsubara_accumulate import DeviceChainMz, mirror_state, mirror_step   # (that module imports this one)
+    x, s, c = fd.Graph([]), fd.Graph([]), fd.Graph([])
+    r = fd.Graph([fd.Graph([x, c], subgraph_factors=[1.0, -0.3], operator=fd.Sum()), s], operator=fd.Prod())
+    t, leafmap, _ = lower([r])
+    at = {g.id: i - 1 for i, g in leafmap.items()}
+    assert t.n_leaf == 3 and t.n_root == 1
+    col, fixed = [at[x.id]], np.zeros(3)
+    fixed[at[s.id]], fixed[at[c.id]] = 0.4, 1.0
+    f = fd.compile_table(t, specialize="isa")
+    B, seed, gamma = 65, 13, 0.05
+    grid = refined_grid(np.random.default_rng(3), 1, 5)
+    ev = oracle_roots(t)
+    steps = [(1, 0, 1.0, INIT), (1, B, gamma, 0), (1, 2 * B, gamma, MEASURE), (1, 3 * B, gamma, MEASURE)]
+    chain, m = DeviceChain(f.handle, cuda, grid, col, fixed, B), fresh_state(fixed, 1, 1, B)
+    for i, (mask, off, g, flags) in enumerate(steps):
+        chain.step(mask, g, seed, off, flags)
+        u, ua = step_uniforms(B, 1, mask, seed, off)
+        m = capi.chain_reference(grid, col, m, mask, u, ua, g, flags, ev)
+        assert_state(chain.state(), m, f"plain, step {i}")
+    assert 0 < (m["n_accept"] < 4).sum() and (m["sum"][1] > 0.0).all()      # proposals were refused; both measured steps counted
+    mz = ((1, -2), True, 1, [at[s.id]], [at[x.id]], 1.7)
+    chain, m = DeviceChainMz(f.handle, cuda, grid, col, fixed, B, mz), mirror_state(fixed, 1, 1, B, 2)
+    for i, (mask, off, g, flags) in enumerate(steps):
+        chain.step(mask, g, seed, off, flags)
+        m = mirror_step(m, grid, col, mask, seed, off, g, flags, ev, mz, None, None)
+        assert_state(chain.state(), m, f"projected, step {i}")
+    assert 0 < (m["n_accept"] < 4).sum() and np.abs(m["sum"][1:-1:2]).min() > 0.0   # proposals were refused; imaginary parts were measured
 
 
 def test_walkers_over_several_chunks_with_a_short_last_one(libfdg, cuda):

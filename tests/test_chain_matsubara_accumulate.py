@@ -63,7 +63,7 @@ class DeviceChainMz(DeviceChain):
                            ("sum", self.total, self.n_sum * B), ("n_accept", self.n_acc, B)):
             h = t.cpu().numpy()
             assert (h[n:] == (SENT if h.dtype == np.float64 else int(SENT))).all(), name + ": a word past the array was written"
-            out[name] = h[:n].reshape(-1, B).copy() if n != B else h[:n].copy()
+            out[name] = h[:n].reshape(-1, B).copy() if name not in ("a", "n_accept") else h[:n].copy()     # (one row where D or R is 1)
         return out
 
 
