@@ -57,6 +57,7 @@ EXPORTS = [
     "fdg_chain_propose_device", "fdg_chain_step_device", "fdg_mc_chain_step_device", "fdg_chain_reduce_device",
     "fdg_chain_step_device_matsubara", "fdg_mc_chain_step_device_matsubara",
     "fdg_chain_step_device_grouped", "fdg_mc_chain_step_device_grouped",
+    "fdg_chain_propose_device_discrete", "fdg_chain_step_device_binned", "fdg_mc_chain_step_device_binned",
 ]
 FDG_BIN_MAX = 16384     # fdg_accumulate_device_binned: largest n_bin
 FDG_VEGAS_DIM_MAX, FDG_VEGAS_GRID_MAX = 64, 1024     # the VEGAS map: most variables, most cells per variable
@@ -68,6 +69,7 @@ FDG_OBS_MAX = 16  # fdg_observables: most linear combinations of the roots per c
 FDG_FREQ_OBS_MAX = 8  # fdg_freq_observables: most linear combinations of the projected roots per call
 FDG_STRAT_CUBE_MAX = 1 << 20  # the stratified calls: most hypercubes
 FDG_CHAIN_INIT, FDG_CHAIN_MEASURE = 1, 2  # flags of fdg_[mc_]chain_step_device
+FDG_CHAIN_BIN_MAX = 64  # fdg_[mc_]chain_step_device_binned: most values of the chain's discrete variable
 COMM_ID_BYTES = 128
 
 
@@ -321,6 +323,9 @@ def lib():
     L.fdg_mc_chain_step_device_matsubara.argtypes = L.fdg_mc_chain_step_device.argtypes[:-2] + [C.c_void_p, i64, vp]
     L.fdg_chain_step_device_grouped.argtypes = L.fdg_chain_step_device.argtypes[:-2] + [C.c_void_p, C.c_void_p, i64, vp]
     L.fdg_mc_chain_step_device_grouped.argtypes = L.fdg_mc_chain_step_device.argtypes[:-2] + [C.c_void_p, C.c_void_p, i64, vp]
+    L.fdg_chain_propose_device_discrete.argtypes = L.fdg_chain_propose_device.argtypes[:-2] + [C.c_int, dp, u32, dp, u32, C.c_void_p, vp, vp, i64, vp]
+    L.fdg_chain_step_device_binned.argtypes = L.fdg_chain_step_device.argtypes[:-2] + [C.c_void_p, C.c_void_p, u32, vp, vp, i64, vp]
+    L.fdg_mc_chain_step_device_binned.argtypes = L.fdg_mc_chain_step_device.argtypes[:-2] + [C.c_void_p, C.c_void_p, u32, vp, vp, i64, vp]
     L.fdg_powi.argtypes = [C.c_double, C.c_int32]
     L.fdg_powi.restype = C.c_double
     _lib = L
@@ -753,16 +758,33 @@ class GraphHandle:
         self._chain_step("_grouped", (kF, beta, lam), d_xp, xpc, d_facp, n_col, n_dim, coef, gamma, seed, sample_offset, flags, d_x, xc, d_fac,
                          d_root, d_a, d_sum, d_n_accept, B, stream, desc, groups)
 
+    # the same steps with one discrete variable behind the continuous ones: desc and groups as in the grouped step, each may be None;
+    # d_fac / d_facp [n_dim + 1, B], d_bin / d_binp int32 [B], d_sum [n_bin n_root + 1, B] or [2 n_bin n_freq n_root + 1, B]
+    # (fdg.h, "Markov chain with a discrete external variable and per-bin measurement")
+    def chain_step_device_binned(self, d_xp: int, xpc: int, d_facp: int, n_col: int, n_dim: int, coef, gamma: float, seed: int,
+                                 sample_offset: int, flags: int, d_x: int, xc: int, d_fac: int, d_root: int, d_a: int, d_sum: int,
+                                 d_n_accept: int, desc, groups, n_bin: int, d_binp: int, d_bin: int, B: int, stream: int = 0):
+        self._chain_step("_binned", None, d_xp, xpc, d_facp, n_col, n_dim, coef, gamma, seed, sample_offset, flags, d_x, xc, d_fac, d_root,
+                         d_a, d_sum, d_n_accept, B, stream, desc, groups, (n_bin, d_binp, d_bin))
+
+    def mc_chain_step_device_binned(self, d_xp: int, xpc: int, kF, beta, lam, d_facp: int, n_col: int, n_dim: int, coef, gamma: float,
+                                    seed: int, sample_offset: int, flags: int, d_x: int, xc: int, d_fac: int, d_root: int, d_a: int,
+                                    d_sum: int, d_n_accept: int, desc, groups, n_bin: int, d_binp: int, d_bin: int, B: int, stream: int = 0):
+        self._chain_step("_binned", (kF, beta, lam), d_xp, xpc, d_facp, n_col, n_dim, coef, gamma, seed, sample_offset, flags, d_x, xc, d_fac,
+                         d_root, d_a, d_sum, d_n_accept, B, stream, desc, groups, (n_bin, d_binp, d_bin))
+
     def _chain_step(self, entry: str, mc, d_xp, xpc, d_facp, n_col, n_dim, coef, gamma, seed, sample_offset, flags, d_x, xc, d_fac, d_root, d_a,
-                    d_sum, d_n_accept, B, stream=0, desc=None, groups=None):
+                    d_sum, d_n_accept, B, stream=0, desc=None, groups=None, binned=None):
         """fdg_[mc_]chain_step_device + ``entry``: ``mc`` None (the leaf form) or ``(kF, beta, lam)``; ``entry`` "" takes no descriptor,
-        "_matsubara" ``desc`` and "_grouped" ``desc`` and ``groups`` (each None: a null pointer)."""
+        "_matsubara" ``desc``, "_grouped" ``desc`` and ``groups`` (each None: a null pointer), "_binned" those two and
+        ``binned = (n_bin, d_binp, d_bin)``."""
         c = self._coef(coef)
         fn = getattr(lib(), ("fdg_chain_step_device" if mc is None else "fdg_mc_chain_step_device") + entry)
-        descs = {"": (), "_matsubara": (desc,), "_grouped": (desc, groups)}[entry]
+        descs = {"": (), "_matsubara": (desc,), "_grouped": (desc, groups), "_binned": (desc, groups)}[entry]
+        bins = (binned[0], binned[1] or None, binned[2] or None) if entry == "_binned" else ()
         check(fn(self._h, d_xp or None, xpc, *(mc or ()), d_facp or None, n_col, n_dim, None if c is None else c.ctypes.data, gamma, seed,
                  sample_offset, flags, d_x or None, xc, d_fac or None, d_root or None, d_a or None, d_sum or None, d_n_accept or None,
-                 *(None if d is None else C.addressof(d) for d in descs), B, stream))
+                 *(None if d is None else C.addressof(d) for d in descs), *bins, B, stream))
 
     def _coef(self, coef):
         if coef is None:
@@ -839,6 +861,26 @@ def chain_propose_device(d_grid: int, n_dim: int, n_grid: int, col, n_col: int, 
             raise ValueError("col must name one column per variable")
     check(lib().fdg_chain_propose_device(d_grid or None, n_dim, n_grid, None if c is None else c.ctypes.data, n_col, mask, seed, sample_offset,
                                          d_x or None, xc, d_fac or None, d_xp or None, xpc, d_facp or None, B, stream))
+
+
+def chain_propose_device_discrete(d_grid: int, n_dim: int, n_grid: int, col, n_col: int, mask: int, seed: int, sample_offset: int, d_x: int,
+                                  xc: int, d_fac: int, d_xp: int, xpc: int, d_facp: int, move_discrete: bool, d_cdf: int, n_bin: int, d_ext: int,
+                                  ext_col, d_bin: int, d_binp: int, B: int, stream: int = 0):
+    """fdg_chain_propose_device_discrete: :func:`chain_propose_device` and, with ``move_discrete``, the discrete variable redrawn from
+    ``d_cdf [n_bin + 1]`` for counter ``(sample_offset + b, n_dim)``: ``binp [B]`` (int32) its value, ``facp[n_dim]`` the factor
+    ``1 / p_j``, the columns ``ext_col`` (a host sequence) of ``xp`` row ``j`` of ``d_ext [n_bin, len(ext_col)]``; otherwise copied."""
+    c = None
+    if col is not None:
+        c = np.ascontiguousarray(col, dtype=np.uint32)
+        if c.shape != (n_dim,):
+            raise ValueError("col must name one column per variable")
+    ec = np.ascontiguousarray(ext_col if ext_col is not None else [], dtype=np.uint32)
+    if ec.ndim != 1:
+        raise ValueError("ext_col must be a sequence of columns")
+    check(lib().fdg_chain_propose_device_discrete(d_grid or None, n_dim, n_grid, None if c is None else c.ctypes.data, n_col, mask, seed,
+                                                  sample_offset, d_x or None, xc, d_fac or None, d_xp or None, xpc, d_facp or None,
+                                                  1 if move_discrete else 0, d_cdf or None, n_bin, d_ext or None, ec.shape[0],
+                                                  ec.ctypes.data if ec.shape[0] else None, d_bin or None, d_binp or None, B, stream))
 
 
 def chain_reduce_device(d_sum: int, n_root: int, B: int, d_out: int, stream: int = 0):
@@ -1030,12 +1072,46 @@ def chain_grouped_reference(grid, col, state, mask: int, u, u_acc, gamma: float,
     step's descriptor -- ``freq``, ``fermionic``, ``weight_freq``, ``root_col_in``, ``root_col_out``, ``beta`` -- with
     ``state["sum"]`` ``[2 F R + 1, B]``; the phases are the library's own (fdg_matsubara_phase through
     :func:`matsubara_phase_table`, or ``phase_table`` as in :func:`chain_matsubara_reference`)."""
+    return _chain_grouped_step(grid, col, state, mask, u, u_acc, gamma, flags, eval_roots, root_group, var_sets, reweight, coef, exists,
+                               matsubara, phase_table, None)
+
+
+def chain_binned_reference(grid, col, state, mask: int, u, u_acc, gamma: float, flags: int, eval_roots, cdf, ext=None, ext_col=(),
+                           move_discrete: bool = True, u_disc=None, root_group=None, var_sets=None, reweight=None, coef=None, exists=None,
+                           matsubara=None, phase_table=None):
+    """One step of the chain with a discrete variable restated in numpy (include/fdg.h, "Markov chain with a discrete external variable
+    and per-bin measurement"): fdg_chain_propose_device_discrete, then fdg_[mc_]chain_step_device_binned, in the device's fp64 order,
+    so that the state and the sums compare bit for bit.  These are :func:`chain_grouped_reference`'s statements, run by the same body,
+    with the discrete variable's beside them; its arguments, and ``cdf [n_bin + 1]``, ``ext [n_bin, n_ext]`` / ``ext_col`` the table
+    and its columns of ``x``, ``move_discrete`` whether the variable is redrawn, ``u_disc [B]`` the uniforms of the counters
+    ``(sample_offset + b, n_dim)`` (read only then).  ``root_group`` and ``var_sets`` None: one group of every root and every variable
+    (a NULL ``cg``).  ``state`` holds ``fac [D + 1, B]`` (row ``D``: ``1 / p_j``), ``bin [B]`` (int32) and ``sum``
+    ``[n_bin R + 1, B]`` or ``[2 n_bin F R + 1, B]``; the result has ``bin`` and ``binp`` too."""
+    D, R = np.asarray(grid).shape[0], np.asarray(state["root"]).shape[0]
+    if root_group is None and var_sets is None:
+        root_group, var_sets = [0] * R, [tuple(range(D))]
+    binned = dict(cdf=np.asarray(cdf, dtype=np.float64), ext=None if ext is None else np.asarray(ext, dtype=np.float64),
+                  ext_col=[int(e) for e in ext_col], move=bool(move_discrete), u=u_disc)
+    return _chain_grouped_step(grid, col, state, mask, u, u_acc, gamma, flags, eval_roots, root_group, var_sets, reweight, coef, exists,
+                               matsubara, phase_table, binned)
+
+
+def _chain_grouped_step(grid, col, state, mask, u, u_acc, gamma, flags, eval_roots, root_group, var_sets, reweight, coef, exists, matsubara,
+                        phase_table, binned):
+    """The body of :func:`chain_grouped_reference` (``binned`` None) and :func:`chain_binned_reference`: where ``binned`` is None no
+    statement of the discrete variable runs."""
     table = matsubara_phase_table if phase_table is None else phase_table
     grid = np.asarray(grid, dtype=np.float64)
     D, G = grid.shape[0], grid.shape[1] - 1
     x, fac, root, a = (np.array(state[k], dtype=np.float64) for k in ("x", "fac", "root", "a"))
     total, n_acc = np.array(state["sum"], dtype=np.float64), np.array(state["n_accept"], dtype=np.int32)
     B, R, n_group = x.shape[1], root.shape[0], len(var_sets)
+    n_bin, lanes = 1, np.arange(x.shape[1])
+    if binned is not None:
+        cdf, n_bin = binned["cdf"], binned["cdf"].shape[0] - 1
+        bins = np.array(state["bin"], dtype=np.int32)
+        if fac.shape != (D + 1, B) or bins.shape != (B,):
+            raise ValueError("fac must be [n_dim + 1, n_walker] and bin [n_walker]")
     cols = list(range(D)) if col is None else [int(c) for c in col]
     live = [k for k in range(R) if exists is None or exists[k]]
     members = [[k for k in live if int(root_group[k]) == g] for g in range(n_group)]
@@ -1046,8 +1122,11 @@ def chain_grouped_reference(grid, col, state, mask: int, u, u_acc, gamma: float,
         freq, fermionic, wf, beta = list(mz["freq"]), mz["fermionic"], int(mz["weight_freq"]), float(mz["beta"])
         F = len(freq)
         pairs = {k: (int(mz["root_col_in"][k]), int(mz["root_col_out"][k])) for k in live}
-        if total.shape != (2 * F * R + 1, B) or not 0 <= wf < F:
+        if (binned is None and total.shape != (2 * F * R + 1, B)) or not 0 <= wf < F:
             raise ValueError("sum must be [2 n_freq n_root + 1, n_walker] and weight_freq an index into freq")
+    n_sum = R if mz is None else 2 * F * R                  # the columns of one bin
+    if binned is not None and total.shape != (n_bin * n_sum + 1, B):
+        raise ValueError("sum must be [n_bin n_root + 1, n_walker], or [2 n_bin n_freq n_root + 1, n_walker] with a projection")
 
     def phases(p, fs):
         return {pair: table(p[pair[1]] - p[pair[0]], beta, fs, fermionic) for pair in set(pairs.values())}
@@ -1056,7 +1135,8 @@ def chain_grouped_reference(grid, col, state, mask: int, u, u_acc, gamma: float,
         j = None
         for d in sorted(set(int(d) for d in var_sets[g])):
             j = f[d].copy() if j is None else j * f[d]
-        return np.ones(B) if j is None else j
+        j = np.ones(B) if j is None else j
+        return j if binned is None else j * f[D]
 
     xp, facp = x.copy(), fac.copy()
     for d in range(D):
@@ -1067,6 +1147,16 @@ def chain_grouped_reference(grid, col, state, mask: int, u, u_acc, gamma: float,
             wd = grid[d, c + 1] - lo
             xp[cols[d]] = lo + (y - c.astype(np.float64)) * wd
             facp[d] = np.float64(G) * wd
+    if binned is not None:
+        binp = bins.copy()
+        if binned["move"]:
+            ud = np.asarray(binned["u"], dtype=np.float64)
+            jp = np.searchsorted(cdf[1:n_bin], ud, side="right")        # the number of interior edges <= u
+            with np.errstate(all="ignore"):
+                facp[D] = 1.0 / (cdf[jp + 1] - cdf[jp])
+            binp = jp.astype(np.int32)
+            for e, c in enumerate(binned["ext_col"]):
+                xp[c] = binned["ext"][jp, e]
     with np.errstate(all="ignore"):
         rp = np.asarray(eval_roots(xp), dtype=np.float64) if live else np.zeros((R, B))
         ph = phases(xp, [freq[wf]]) if mz is not None else None
@@ -1110,6 +1200,10 @@ def chain_grouped_reference(grid, col, state, mask: int, u, u_acc, gamma: float,
     for k in live:
         root[k] = np.where(acc, np.where(bad, 0.0, rp[k]), root[k])
     n_acc = n_acc + acc.astype(np.int32)
+    base = 0                                                 # the first column of the walker's bin: per walker with a discrete variable
+    if binned is not None:
+        bins = np.where(acc, binp, bins)
+        base = bins.astype(np.int64) * n_sum
     if flags & FDG_CHAIN_MEASURE:
         dd = 1.0 / (a + gamma)
         ph = phases(x, freq) if mz is not None else None
@@ -1120,16 +1214,19 @@ def chain_grouped_reference(grid, col, state, mask: int, u, u_acc, gamma: float,
             for k in members[g]:
                 w = (jac * root[k]) * dd
                 if mz is None:
-                    total[k] = total[k] + w
+                    total[base + k, lanes] = total[base + k, lanes] + w
                     continue
                 sn, cs = ph[pairs[k]]
                 for f in range(F):
-                    o = 2 * (f * R + k)
-                    total[o] = total[o] + w * cs[:, f]
-                    total[o + 1] = total[o + 1] + w * sn[:, f]
-        last = R if mz is None else 2 * F * R
+                    o = base + 2 * (f * R + k)
+                    total[o, lanes] = total[o, lanes] + w * cs[:, f]
+                    total[o + 1, lanes] = total[o + 1, lanes] + w * sn[:, f]
+        last = n_bin * n_sum
         total[last] = total[last] + dd
-    return {"x": x, "fac": fac, "root": root, "a": a, "sum": total, "n_accept": n_acc, "xp": xp, "facp": facp, "accept": acc}
+    out = {"x": x, "fac": fac, "root": root, "a": a, "sum": total, "n_accept": n_acc, "xp": xp, "facp": facp, "accept": acc}
+    if binned is not None:
+        out.update(bin=bins, binp=binp)
+    return out
 
 
 def _strat_array(strat, n_dim: int) -> np.ndarray:

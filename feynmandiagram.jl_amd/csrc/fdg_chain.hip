@@ -6,7 +6,7 @@
 // likewise, so n_root = 180 and n_dim = 64 cost loads, not registers.  Nothing here touches the kernels of fdg_binned.hip: the
 // sampler's arithmetic of one variable is restated below (chain_draw), the same operations in the same order, so the bits are its.
 //
-// All six step entries run the one select kernel fdg_chain_select<MZ>.  It gives every group of roots the jacobian of its own
+// All step entries run the one select kernel fdg_chain_select<MZ, BIN>.  It gives every group of roots the jacobian of its own
 // variables and a reweight factor: a' = sum_g rho_g |jac_g s_g| (fdg_[mc_]chain_step_device_grouped).  It walks the
 // groups outside and a group's roots inside: the lists of the roots are uploaded sorted by (group, root), so a group is one contiguous
 // range, and the groups' ranges, masks and factors are a kernel argument by value (ChainGroups).  jac_g is one pass over the group's
@@ -17,6 +17,11 @@
 // the phase of the weight frequency (s_g = sum_k c_k r_k e^{i w tau_k}) and every root is measured at every frequency.  Roots
 // outside, frequencies inside, x = tau / beta once per root; the phase is fdg_matsubara.h's, so a numpy restatement gives the same
 // bits.
+//
+// With BIN (fdg_chain_propose_device_discrete, fdg_[mc_]chain_step_device_binned) the walker carries one discrete
+// variable behind the continuous ones: its value in bin / binp, its factor 1 / p_j in row n_dim of fac / facp.  Every group's jacobian
+// takes that factor as its last product, and a walker measures into the columns of its own bin through a row address of its own:
+// no loop over the bins, nothing multiplied by zero, every word still one lane's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -76,6 +81,49 @@ fdg_chain_propose(const double *__restrict__ grid, uint32_t D, uint32_t G, Chain
   }
 }
 
+struct ChainExtCols { uint32_t c[FDG_VEGAS_EXT_MAX]; };   // the columns of x the rows of the discrete variable's table go to
+
+// fdg_chain_propose with the discrete variable behind the D continuous ones.  move: its uniform is the Philox column D, its value j the
+// number of interior edges of cdf that are <= u (fdg_vegas_sample_device_discrete's search), row j of ext goes to the columns ecol and
+// 1 / p_j to row D of facp; otherwise the value and its factor are copied (the columns ecol were copied with all the others).
+__global__ void __launch_bounds__(256)
+fdg_chain_propose_discrete(const double *__restrict__ grid, uint32_t D, uint32_t G, ChainCols col, uint32_t n_col, uint64_t mask, uint64_t seed,
+                           uint64_t off, const double *__restrict__ x, long xc, const double *__restrict__ fac, double *__restrict__ xp, long xpc,
+                           double *__restrict__ facp, uint32_t move, const double *__restrict__ cdf, uint32_t n_bin,
+                           const double *__restrict__ ext, uint32_t n_ext, ChainExtCols ecol, const int32_t *__restrict__ bin,
+                           int32_t *__restrict__ binp, long n) {
+  const long b = blockIdx.x * 256L + threadIdx.x;
+  if (b >= n) return;
+  for (uint32_t c = 0; c < n_col; ++c) xp[(long)c * xpc + b] = x[(long)c * xc + b];
+  for (uint32_t d = 0; d < D; ++d) {
+    const size_t at = (size_t)d * (size_t)n + (size_t)b;
+    if ((mask >> d) & 1u) {
+      double f;
+      const double v = chain_draw(grid, d, G, off + (uint64_t)b, seed, f);
+      xp[(long)col.c[d] * xpc + b] = v;
+      facp[at] = f;
+    } else {
+      facp[at] = fac[at];
+    }
+  }
+  const size_t at = (size_t)D * (size_t)n + (size_t)b;
+  if (move) {
+    const double u = fdg_philox_u53(off + (uint64_t)b, D, seed);
+    uint32_t lo = 0, hi = n_bin - 1u;                     // j in [lo, hi]: cdf[1 .. lo] <= u < cdf[hi + 1 ..]
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (cdf[mid + 1u] <= u) lo = mid + 1u; else hi = mid;
+    }
+    const double p = cdf[lo + 1u] - cdf[lo];
+    binp[b] = (int32_t)lo;
+    for (uint32_t e = 0; e < n_ext; ++e) xp[(long)ecol.c[e] * xpc + b] = ext[(size_t)lo * n_ext + e];
+    facp[at] = 1.0 / p;
+  } else {
+    binp[b] = bin[b];
+    facp[at] = fac[at];
+  }
+}
+
 // The jacobian of one group for walker b: the left fold of f[d][b] over ascending d with bit d in mask; an empty mask gives 1.0.
 __device__ __forceinline__ double chain_group_jac(const double *__restrict__ f, uint64_t mask, uint32_t D, long nw, long b) {
   double j = 1.0;
@@ -97,14 +145,18 @@ __device__ __forceinline__ double chain_group_jac(const double *__restrict__ f, 
 // (matsubara_multiplier, formed on the host), wf the frequency of the weight, and sum is [2 F R + 1][nw]: column 2 (f R + k) the real
 // part of root k at frequency f, the next one the imaginary part, the last one d.  Everything indexed by g, j or f is wave-uniform;
 // the only per-lane values that live across a group are ap and bad.
-template <bool MZ>
+// With BIN fac and facp have the row D (the discrete variable's factor: the last product of every jac_g), binp / bin hold the value of
+// the proposal / the state, and sum is [n_bin R + 1][nw] or [2 n_bin F R + 1][nw]: the walker's columns are those of its bin j, root k
+// at j R + k, or at 2 ((j F + f) R + k).  A bin outside [0, n_bin), which the proposal never writes, measures nothing.
+template <bool MZ, bool BIN>
 __global__ void __launch_bounds__(256)
 fdg_chain_select(const double *__restrict__ roots, long ld, long n, const uint32_t *__restrict__ kidx, const double *__restrict__ cf,
                  ChainGroups cg, uint32_t has_rho, const uint32_t *__restrict__ cin, const uint32_t *__restrict__ cout,
                  const double *__restrict__ mult, uint32_t F, uint32_t wf, double beta, const double *__restrict__ xp, long xpc,
                  const double *__restrict__ facp, uint32_t n_col, uint32_t D, long nw, double gamma, uint64_t seed, uint64_t off,
                  uint32_t flags, double *__restrict__ x, long xc, double *__restrict__ fac, double *__restrict__ root,
-                 double *__restrict__ a, double *__restrict__ sum, uint32_t R, int32_t *__restrict__ n_accept) {
+                 double *__restrict__ a, double *__restrict__ sum, uint32_t R, int32_t *__restrict__ n_accept, uint32_t n_bin,
+                 const int32_t *__restrict__ binp, int32_t *__restrict__ bin) {
   const long b = blockIdx.x * 256L + threadIdx.x;
   if (b >= n) return;
   const bool init = (flags & FDG_CHAIN_INIT) != 0, meas = (flags & FDG_CHAIN_MEASURE) != 0;
@@ -113,10 +165,13 @@ fdg_chain_select(const double *__restrict__ roots, long ld, long n, const uint32
   if (MZ) mw = mult[wf];
   double asum = 0.0;
   bool bad = false, first_group = true;
+  double fdp = 1.0;
+  if (BIN) fdp = facp[(size_t)D * (size_t)nw + (size_t)b];
   for (uint32_t g = 0; g < cg.n; ++g) {
     const uint32_t j0 = cg.start[g], j1 = cg.start[g + 1];
     if (j0 == j1) continue;
-    const double jg = chain_group_jac(facp, cg.mask[g], D, nw, b);
+    double jg = chain_group_jac(facp, cg.mask[g], D, nw, b);
+    if (BIN) jg = jg * fdp;
     double ag;
     if (MZ) {
       double re = 0.0, im = 0.0;
@@ -170,6 +225,11 @@ fdg_chain_select(const double *__restrict__ roots, long ld, long n, const uint32
       const size_t at = (size_t)d * (size_t)nw + (size_t)b;
       fac[at] = facp[at];
     }
+    if (BIN) {
+      const size_t at = (size_t)D * (size_t)nw + (size_t)b;
+      fac[at] = facp[at];
+      bin[b] = binp[b];
+    }
     a[b] = ap;
     if (n_accept) n_accept[b] = n_accept[b] + 1;
   }
@@ -180,11 +240,20 @@ fdg_chain_select(const double *__restrict__ roots, long ld, long n, const uint32
   const double *fs = acc ? facp : fac;
   const double *tp = acc ? xp : x;
   const long tpc = acc ? xpc : xc;
+  uint32_t jb = 0;
+  double fds = 1.0;
+  bool jin = true;
+  if (BIN && meas) {
+    jb = (uint32_t)(acc ? binp[b] : bin[b]);
+    jin = jb < n_bin;
+    fds = fs[(size_t)D * (size_t)nw + (size_t)b];
+  }
   for (uint32_t g = 0; g < cg.n; ++g) {
     const uint32_t j0 = cg.start[g], j1 = cg.start[g + 1];
     if (j0 == j1) continue;
     double jac = 0.0;
     if (meas) jac = chain_group_jac(fs, cg.mask[g], D, nw, b);
+    if (BIN && meas) jac = jac * fds;
     for (uint32_t j = j0; j < j1; ++j) {
       const uint32_t k = kidx[j];
       const size_t at = (size_t)k * (size_t)nw + (size_t)b;
@@ -196,7 +265,7 @@ fdg_chain_select(const double *__restrict__ roots, long ld, long n, const uint32
       } else {
         r = root[at];
       }
-      if (meas) {
+      if (meas && (!BIN || jin)) {
         const double jr = jac * r;
         const double w = jr * dd;
         if (MZ) {
@@ -205,18 +274,21 @@ fdg_chain_select(const double *__restrict__ roots, long ld, long n, const uint32
           for (uint32_t f = 0; f < F; ++f) {
             double sn, cs;
             matsubara_phase_of(xt, mult[f], sn, cs);
-            const size_t o = (size_t)(2u * (f * R + k)) * (size_t)nw + (size_t)b;
+            const size_t o = (size_t)(2u * ((BIN ? jb * F + f : f) * R + k)) * (size_t)nw + (size_t)b;
             sum[o] = sum[o] + w * cs;
             sum[o + (size_t)nw] = sum[o + (size_t)nw] + w * sn;
           }
+        } else if (BIN) {
+          const size_t o = ((size_t)jb * R + k) * (size_t)nw + (size_t)b;
+          sum[o] = sum[o] + w;
         } else {
           sum[at] = sum[at] + w;
         }
       }
     }
   }
-  if (meas) {
-    const size_t at = (size_t)(MZ ? 2u * F * R : R) * (size_t)nw + (size_t)b;
+  if (meas && (!BIN || jin)) {
+    const size_t at = (size_t)((BIN ? n_bin : 1u) * (MZ ? 2u * F * R : R)) * (size_t)nw + (size_t)b;
     sum[at] = sum[at] + dd;
   }
 }
@@ -261,6 +333,9 @@ struct ChainCall {
   int32_t *d_n_accept;
   int64_t B;
   void *stream;
+  uint32_t n_bin = 0;                                      // the binned step: the discrete variable's values, 0 for every other entry
+  const int32_t *d_binp = nullptr;
+  int32_t *d_bin = nullptr;
 };
 
 // The checks of both step calls that need no lock.
@@ -318,6 +393,20 @@ int check_chain_groups(const fdg_graph *g, const ChainCall &c, const fdg_chain_g
       set_error("a reweight factor is not finite or <= 0"); return FDG_E_INVALID;
     }
   }
+  return FDG_OK;
+}
+
+// The checks of the binned step calls on the discrete variable's arguments, after all the others.
+int check_chain_binned(const ChainCall &c) {
+  if (c.n_bin == 0) { set_error("n_bin == 0"); return FDG_E_INVALID; }
+  if (c.n_bin > FDG_CHAIN_BIN_MAX) { set_error("n_bin > FDG_CHAIN_BIN_MAX"); return FDG_E_UNSUPPORTED; }
+  if (!c.d_binp || !c.d_bin) { set_error("null device buffer"); return FDG_E_INVALID; }
+  if (c.d_binp == c.d_bin) { set_error("d_bin and d_binp are the same buffer"); return FDG_E_INVALID; }
+  const void *arr[8] = {c.d_x, c.d_fac, c.d_root, c.d_a, c.d_sum, c.d_xp, c.d_facp, c.d_n_accept};
+  for (int i = 0; i < 8; ++i)
+    if (arr[i] && (arr[i] == (const void *)c.d_binp || arr[i] == (const void *)c.d_bin)) {
+      set_error("d_bin or d_binp is the same buffer as another array"); return FDG_E_INVALID;
+    }
   return FDG_OK;
 }
 
@@ -385,6 +474,8 @@ int run_chain(fdg_graph *g, const ChainCall &c, const ChainMc *mc, const fdg_cha
       HIP_TRY(hipMemcpyAsync(d_cout, hout.data(), n_live * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     }
   }
+  const auto select = c.n_bin ? (mz ? fdg_chain_select<true, true> : fdg_chain_select<false, true>)
+                              : (mz ? fdg_chain_select<true, false> : fdg_chain_select<false, false>);
   for (long c0 = 0; c0 < (long)c.B; c0 += Bc) {
     const long n = std::min<long>(Bc, (long)c.B - c0);
     if (n_live) {
@@ -397,21 +488,23 @@ int run_chain(fdg_graph *g, const ChainCall &c, const ChainMc *mc, const fdg_cha
       }
       if (rc) return rc;
     }
-    hipLaunchKernelGGL((mz ? fdg_chain_select<true> : fdg_chain_select<false>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, roots,
+    hipLaunchKernelGGL(select, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, roots,
                        Bc, n, d_kidx, c.coef ? d_coef : nullptr, grp, cg && cg->reweight ? 1u : 0u, d_cin, d_cout, d_mult,
                        mz ? mz->n_freq : 0u, mz ? mz->weight_freq : 0u, mz ? mz->beta : 1.0, c.d_xp + c0, (long)c.xpc, c.d_facp + c0,
                        c.n_col, c.n_dim, (long)c.B, c.gamma, c.seed, c.offset + (uint64_t)c0, (uint32_t)c.flags, c.d_x + c0, (long)c.xc,
                        c.d_fac + c0, c.d_root + c0, c.d_a + c0, c.d_sum ? c.d_sum + c0 : nullptr, R,
-                       c.d_n_accept ? c.d_n_accept + c0 : nullptr);
+                       c.d_n_accept ? c.d_n_accept + c0 : nullptr, c.n_bin, c.n_bin ? c.d_binp + c0 : nullptr,
+                       c.n_bin ? c.d_bin + c0 : nullptr);
     HIP_TRY(hipGetLastError());
   }
   return FDG_OK;
 }
 
-// Which of the three pairs of entries a call came through: what its descriptors may be.
-enum ChainEntry { CHAIN_PLAIN, CHAIN_MATSUBARA, CHAIN_GROUPED };   // no descriptor; mz required; cg required, mz optional
+// Which of the four pairs of entries a call came through: what its descriptors may be.
+// no descriptor; mz required; cg required, mz optional; both optional (with the discrete variable's arguments in the call)
+enum ChainEntry { CHAIN_PLAIN, CHAIN_MATSUBARA, CHAIN_GROUPED, CHAIN_BINNED };
 
-// The body of the six step entries: the leaf form, or with mc the Monte-Carlo form.  The checks run in this order in every entry,
+// The body of the eight step entries: the leaf form, or with mc the Monte-Carlo form.  The checks run in this order in every entry,
 // so a call that is wrong in two ways is refused with the same message through each of them.
 int chain_step(fdg_graph *g, const ChainCall &c, const ChainMc *mc, ChainEntry entry, const fdg_chain_matsubara *mz,
                const fdg_chain_groups *cg) {
@@ -422,8 +515,12 @@ int chain_step(fdg_graph *g, const ChainCall &c, const ChainMc *mc, ChainEntry e
     rc = check_chain_mz(g, c, mz);
     if (rc) return rc;
   }
-  if (entry == CHAIN_GROUPED) {
+  if (entry == CHAIN_GROUPED || (entry == CHAIN_BINNED && cg)) {
     rc = check_chain_groups(g, c, cg);
+    if (rc) return rc;
+  }
+  if (entry == CHAIN_BINNED) {
+    rc = check_chain_binned(c);
     if (rc) return rc;
   }
   std::lock_guard<std::mutex> lk(g->mu);
@@ -440,13 +537,9 @@ int chain_step(fdg_graph *g, const ChainCall &c, const ChainMc *mc, ChainEntry e
   return run_chain(g, c, mc, mz, cg);
 }
 
-}  // namespace
-
-extern "C" {
-
-int fdg_chain_propose_device(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, uint32_t n_col, uint64_t mask,
-                             uint64_t seed, uint64_t sample_offset, const double *d_x, int64_t x_col_stride, const double *d_fac,
-                             double *d_xp, int64_t xp_col_stride, double *d_facp, int64_t B, void *stream) {
+// The checks of both propose calls, in one order; cols = the column of every variable.
+int check_propose(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, uint32_t n_col, uint64_t mask, const double *d_x,
+                  int64_t x_col_stride, const double *d_fac, double *d_xp, int64_t xp_col_stride, double *d_facp, int64_t B, ChainCols &cols) {
   if (B < 0) { set_error("n_walker < 0"); return FDG_E_INVALID; }
   if (!d_grid || !d_x || !d_fac || !d_xp || !d_facp) { set_error("null device buffer"); return FDG_E_INVALID; }
   if (n_dim == 0 || n_grid == 0) { set_error("n_dim == 0 or n_grid == 0"); return FDG_E_INVALID; }
@@ -455,10 +548,22 @@ int fdg_chain_propose_device(const double *d_grid, uint32_t n_dim, uint32_t n_gr
   if (d_x == d_xp || d_fac == d_facp) { set_error("the state and the proposal are the same buffer"); return FDG_E_INVALID; }
   if (n_dim < 64 && (mask >> n_dim)) { set_error("mask names a variable >= n_dim"); return FDG_E_INVALID; }
   if (x_col_stride < B || xp_col_stride < B) { set_error("a column stride < n_walker"); return FDG_E_INVALID; }
-  ChainCols cols;
   for (uint32_t d = 0; d < FDG_VEGAS_DIM_MAX; ++d) cols.c[d] = d < n_dim ? (col ? col[d] : d) : 0u;
   for (uint32_t d = 0; d < n_dim; ++d)
     if (cols.c[d] >= n_col) { set_error("col names a column >= n_col"); return FDG_E_INVALID; }
+  return FDG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fdg_chain_propose_device(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, uint32_t n_col, uint64_t mask,
+                             uint64_t seed, uint64_t sample_offset, const double *d_x, int64_t x_col_stride, const double *d_fac,
+                             double *d_xp, int64_t xp_col_stride, double *d_facp, int64_t B, void *stream) {
+  ChainCols cols;
+  const int rc = check_propose(d_grid, n_dim, n_grid, col, n_col, mask, d_x, x_col_stride, d_fac, d_xp, xp_col_stride, d_facp, B, cols);
+  if (rc) return rc;
   if (B == 0) return FDG_OK;
   hipLaunchKernelGGL(fdg_chain_propose, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_grid, n_dim, n_grid, cols, n_col,
                      mask, seed, sample_offset, d_x, (long)x_col_stride, d_fac, d_xp, (long)xp_col_stride, d_facp, (long)B);
@@ -526,6 +631,59 @@ int fdg_mc_chain_step_device_grouped(fdg_graph *g, const double *d_xp, int64_t x
   return chain_step(g, c, &mc, CHAIN_GROUPED, mz, cg);
 }
 
+int fdg_chain_propose_device_discrete(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, uint32_t n_col,
+                                      uint64_t mask, uint64_t seed, uint64_t sample_offset, const double *d_x, int64_t x_col_stride,
+                                      const double *d_fac, double *d_xp, int64_t xp_col_stride, double *d_facp, int move_discrete,
+                                      const double *d_cdf, uint32_t n_bin, const double *d_ext, uint32_t n_ext, const uint32_t *ext_col,
+                                      const int32_t *d_bin, int32_t *d_binp, int64_t B, void *stream) {
+  ChainCols cols;
+  const int rc = check_propose(d_grid, n_dim, n_grid, col, n_col, mask, d_x, x_col_stride, d_fac, d_xp, xp_col_stride, d_facp, B, cols);
+  if (rc) return rc;
+  if (n_dim == FDG_VEGAS_DIM_MAX) { set_error("n_dim == FDG_VEGAS_DIM_MAX: the discrete variable's counter is the accept rule's"); return FDG_E_UNSUPPORTED; }
+  if (!d_cdf || !d_bin || !d_binp) { set_error("null device buffer"); return FDG_E_INVALID; }
+  if (d_bin == d_binp) { set_error("d_bin and d_binp are the same buffer"); return FDG_E_INVALID; }
+  if (n_bin == 0) { set_error("n_bin == 0"); return FDG_E_INVALID; }
+  if (n_bin > FDG_CHAIN_BIN_MAX) { set_error("n_bin > FDG_CHAIN_BIN_MAX"); return FDG_E_UNSUPPORTED; }
+  if (n_ext > FDG_VEGAS_EXT_MAX) { set_error("n_ext > FDG_VEGAS_EXT_MAX"); return FDG_E_UNSUPPORTED; }
+  if (n_ext && (!d_ext || !ext_col)) { set_error("n_ext > 0 needs d_ext and ext_col"); return FDG_E_INVALID; }
+  ChainExtCols ecols;
+  for (uint32_t e = 0; e < FDG_VEGAS_EXT_MAX; ++e) ecols.c[e] = e < n_ext ? ext_col[e] : 0u;
+  for (uint32_t e = 0; e < n_ext; ++e) {
+    if (ecols.c[e] >= n_col) { set_error("ext_col names a column >= n_col"); return FDG_E_INVALID; }
+    for (uint32_t f = 0; f < e; ++f)
+      if (ecols.c[f] == ecols.c[e]) { set_error("ext_col names a column twice"); return FDG_E_INVALID; }
+    for (uint32_t d = 0; d < n_dim; ++d)
+      if (cols.c[d] == ecols.c[e]) { set_error("ext_col names a column of col"); return FDG_E_INVALID; }
+  }
+  if (B == 0) return FDG_OK;
+  hipLaunchKernelGGL(fdg_chain_propose_discrete, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_grid, n_dim, n_grid,
+                     cols, n_col, mask, seed, sample_offset, d_x, (long)x_col_stride, d_fac, d_xp, (long)xp_col_stride, d_facp,
+                     move_discrete ? 1u : 0u, d_cdf, n_bin, d_ext, n_ext, ecols, d_bin, d_binp, (long)B);
+  HIP_TRY(hipGetLastError());
+  return FDG_OK;
+}
+
+int fdg_chain_step_device_binned(fdg_graph *g, const double *d_xp, int64_t xp_col_stride, const double *d_facp, uint32_t n_col,
+                                 uint32_t n_dim, const double *coef, double gamma, uint64_t seed, uint64_t sample_offset, unsigned flags,
+                                 double *d_x, int64_t x_col_stride, double *d_fac, double *d_root, double *d_a, double *d_sum,
+                                 int32_t *d_n_accept, const fdg_chain_matsubara *mz, const fdg_chain_groups *cg, uint32_t n_bin,
+                                 const int32_t *d_binp, int32_t *d_bin, int64_t B, void *stream) {
+  const ChainCall c{d_xp, xp_col_stride, d_facp, n_col, n_dim, coef, gamma, seed, sample_offset, flags, d_x, x_col_stride, d_fac,
+                    d_root, d_a, d_sum, d_n_accept, B, stream, n_bin, d_binp, d_bin};
+  return chain_step(g, c, nullptr, CHAIN_BINNED, mz, cg);
+}
+
+int fdg_mc_chain_step_device_binned(fdg_graph *g, const double *d_xp, int64_t xp_col_stride, double kF, double beta, double lambda,
+                                    const double *d_facp, uint32_t n_col, uint32_t n_dim, const double *coef, double gamma, uint64_t seed,
+                                    uint64_t sample_offset, unsigned flags, double *d_x, int64_t x_col_stride, double *d_fac,
+                                    double *d_root, double *d_a, double *d_sum, int32_t *d_n_accept, const fdg_chain_matsubara *mz,
+                                    const fdg_chain_groups *cg, uint32_t n_bin, const int32_t *d_binp, int32_t *d_bin, int64_t B,
+                                    void *stream) {
+  const ChainCall c{d_xp, xp_col_stride, d_facp, n_col, n_dim, coef, gamma, seed, sample_offset, flags, d_x, x_col_stride, d_fac,
+                    d_root, d_a, d_sum, d_n_accept, B, stream, n_bin, d_binp, d_bin};
+  const ChainMc mc{kF, beta, lambda};
+  return chain_step(g, c, &mc, CHAIN_BINNED, mz, cg);
+}
 
 int fdg_chain_reduce_device(const double *d_sum, uint32_t n_root, int64_t B, double *d_out, void *stream) {
   if (B < 0) { set_error("n_walker < 0"); return FDG_E_INVALID; }

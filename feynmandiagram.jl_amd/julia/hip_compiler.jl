@@ -962,6 +962,68 @@ end
 export chain_propose_device!, chain_step_device!, mc_chain_step_device!, chain_reduce_device!, FDG_CHAIN_INIT, FDG_CHAIN_MEASURE
 export chain_step_device_matsubara!, mc_chain_step_device_matsubara!
 export chain_step_device_grouped!, mc_chain_step_device_grouped!
+# The chain with one discrete external variable behind the continuous ones (fdg_chain_propose_device_discrete,
+# fdg_[mc_]chain_step_device_binned): d_fac / d_facp are B x (n_dim + 1), the last column the factor 1 / p_j of the walker's value j,
+# d_bin / d_binp (B Int32) hold the 0-based j, and d_sum is B x (n_bin R + 1): column j R + k root k at value j, the last one
+# 1 / (a + gamma).  d_cdf (n_bin + 1) and d_ext (n_ext x n_bin, row j of the C table a column here) lie on the device; ext_col is
+# 1-based.  dof / pools nothing: one group of every root and every variable.  These wrappers pass no projection (mz = C_NULL).
+# Unverified: written against the header, never run.
+function chain_propose_device_discrete!(d_xp::Ptr{Float64}, d_facp::Ptr{Float64}, d_binp::Ptr{Int32}, d_x::Ptr{Float64}, d_fac::Ptr{Float64},
+    d_bin::Ptr{Int32}, d_grid::Ptr{Float64}, d_cdf::Ptr{Float64}, n_dim::Integer, n_grid::Integer, n_bin::Integer, n_col::Integer,
+    mask::Integer, move_discrete::Bool, B::Integer; col::Union{Nothing,AbstractVector{<:Integer}}=nothing,
+    d_ext::Ptr{Float64}=Ptr{Float64}(C_NULL), ext_col::AbstractVector{<:Integer}=Int[], seed::Integer=0, sample_offset::Integer=0,
+    x_col_stride::Integer=B, xp_col_stride::Integer=B, stream::Ptr{Cvoid}=C_NULL)
+    c = col === nothing ? nothing : UInt32.(col .- 1)
+    ec = UInt32.(ext_col .- 1)
+    _fdg_check(ccall((:fdg_chain_propose_device_discrete, _libfdg), Cint,
+        (Ptr{Float64}, UInt32, UInt32, Ptr{UInt32}, UInt32, UInt64, UInt64, UInt64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Int64,
+         Ptr{Float64}, Cint, Ptr{Float64}, UInt32, Ptr{Float64}, UInt32, Ptr{UInt32}, Ptr{Int32}, Ptr{Int32}, Int64, Ptr{Cvoid}),
+        d_grid, n_dim, n_grid, c === nothing ? C_NULL : c, n_col, mask, seed, sample_offset, d_x, x_col_stride, d_fac, d_xp, xp_col_stride,
+        d_facp, move_discrete ? 1 : 0, d_cdf, n_bin, d_ext, length(ec), isempty(ec) ? C_NULL : ec, d_bin, d_binp, B, stream))
+    return nothing
+end
+function chain_step_device_binned!(f::GraphFunc, d_xp::Ptr{Float64}, d_facp::Ptr{Float64}, d_binp::Ptr{Int32}, d_x::Ptr{Float64},
+    d_fac::Ptr{Float64}, d_bin::Ptr{Int32}, d_root::Ptr{Float64}, d_a::Ptr{Float64}, d_sum::Ptr{Float64}, n_col::Integer, n_dim::Integer,
+    n_bin::Integer, gamma::Float64, B::Integer; dof::Union{Nothing,AbstractVector}=nothing, pools::Union{Nothing,AbstractVector}=nothing,
+    reweight::Union{Nothing,Vector{Float64}}=nothing, flags::Integer=0, coef::Union{Nothing,Vector{Float64}}=nothing, seed::Integer=0,
+    sample_offset::Integer=0, d_n_accept::Ptr{Int32}=Ptr{Int32}(C_NULL), x_col_stride::Integer=B, xp_col_stride::Integer=B,
+    stream::Ptr{Cvoid}=C_NULL)
+    root_group, var_mask = dof === nothing ? (UInt32[], UInt64[]) : weight_groups_from_dof(dof, pools)
+    rw = reweight === nothing ? Float64[] : reweight
+    GC.@preserve root_group var_mask rw begin
+        cg = Ref(_FdgChainGroups(length(var_mask), pointer(root_group), pointer(var_mask), reweight === nothing ? Ptr{Float64}(C_NULL) : pointer(rw)))
+        _fdg_check(ccall((:fdg_chain_step_device_binned, _libfdg), Cint,
+            (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, UInt32, UInt32, Ptr{Float64}, Float64, UInt64, UInt64, Cuint, Ptr{Float64}, Int64,
+             Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Ptr{Int32}, Ptr{Int32}, Int64,
+             Ptr{Cvoid}),
+            f.handle, d_xp, xp_col_stride, d_facp, n_col, n_dim, coef === nothing ? C_NULL : coef, gamma, seed, sample_offset, flags, d_x,
+            x_col_stride, d_fac, d_root, d_a, d_sum, d_n_accept, C_NULL, dof === nothing ? C_NULL : cg, n_bin, d_binp, d_bin, B, stream))
+    end
+    return nothing
+end
+function mc_chain_step_device_binned!(f::GraphFunc, d_xp::Ptr{Float64}, d_facp::Ptr{Float64}, d_binp::Ptr{Int32}, d_x::Ptr{Float64},
+    d_fac::Ptr{Float64}, d_bin::Ptr{Int32}, d_root::Ptr{Float64}, d_a::Ptr{Float64}, d_sum::Ptr{Float64}, n_col::Integer, n_dim::Integer,
+    n_bin::Integer, gamma::Float64, B::Integer; kF::Float64, beta::Float64, lambda::Float64,
+    dof::Union{Nothing,AbstractVector}=nothing, pools::Union{Nothing,AbstractVector}=nothing,
+    reweight::Union{Nothing,Vector{Float64}}=nothing, flags::Integer=0, coef::Union{Nothing,Vector{Float64}}=nothing, seed::Integer=0,
+    sample_offset::Integer=0, d_n_accept::Ptr{Int32}=Ptr{Int32}(C_NULL), x_col_stride::Integer=B, xp_col_stride::Integer=B,
+    stream::Ptr{Cvoid}=C_NULL)
+    root_group, var_mask = dof === nothing ? (UInt32[], UInt64[]) : weight_groups_from_dof(dof, pools)
+    rw = reweight === nothing ? Float64[] : reweight
+    GC.@preserve root_group var_mask rw begin
+        cg = Ref(_FdgChainGroups(length(var_mask), pointer(root_group), pointer(var_mask), reweight === nothing ? Ptr{Float64}(C_NULL) : pointer(rw)))
+        _fdg_check(ccall((:fdg_mc_chain_step_device_binned, _libfdg), Cint,
+            (Ptr{Cvoid}, Ptr{Float64}, Int64, Float64, Float64, Float64, Ptr{Float64}, UInt32, UInt32, Ptr{Float64}, Float64, UInt64, UInt64,
+             Cuint, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Cvoid}, Ptr{Cvoid}, UInt32,
+             Ptr{Int32}, Ptr{Int32}, Int64, Ptr{Cvoid}),
+            f.handle, d_xp, xp_col_stride, kF, beta, lambda, d_facp, n_col, n_dim, coef === nothing ? C_NULL : coef, gamma, seed,
+            sample_offset, flags, d_x, x_col_stride, d_fac, d_root, d_a, d_sum, d_n_accept, C_NULL, dof === nothing ? C_NULL : cg, n_bin,
+            d_binp, d_bin, B, stream))
+    end
+    return nothing
+end
+const FDG_CHAIN_BIN_MAX = 64
+export chain_propose_device_discrete!, chain_step_device_binned!, mc_chain_step_device_binned!, FDG_CHAIN_BIN_MAX
 
 # ---- multi-GPU: one Julia process per GPU, ONE reduction of the accumulated observable ------------ #
 # (include/fdg.h, "multi-GPU").  Rank 0 calls `comm_unique_id()` and ships the 128 bytes to the other

@@ -973,10 +973,52 @@ def chain_integrate_grouped(func_or_handle, tables, lo, hi, col, groups: WeightG
                   weight_freq, groups, reweight)
 
 
+def chain_integrate_binned(func_or_handle, tables, lo, hi, col, dmap: DiscreteMap, kF: float = 0.0, beta: float = 1.0, lam: float = 0.0, *,
+                           n_walker: int, n_step: int, n_therm: int, moves: Optional[Sequence[int]] = None, gamma_rel: float = 1.0,
+                           gamma: Optional[float] = None, n_warm: int = 5, n_warm_sample: Optional[int] = None, n_grid: int = 64,
+                           alpha: float = 0.5, floor: float = 0.05, seed: int = 0, fixed=None, coef=None, vmap: Optional[VegasMap] = None,
+                           specialize_fused: bool = True, n_total: Optional[int] = None, shard_start: int = 0,
+                           reduce: Optional[Callable] = None, device="cuda", groups: Optional[WeightGroups] = None, reweight=None,
+                           matsubara: Optional[MatsubaraProjection] = None, weight_freq: int = 0, **excluded) -> ChainResult:
+    """:func:`chain_integrate` with a discrete variable (``dmap``: a :class:`DiscreteMap` of at most ``FDG_CHAIN_BIN_MAX`` values),
+    which that function refuses: the walkers move over ``(x, j)``, the columns ``dmap.ext_col`` take row ``j`` of ``dmap.ext``
+    (external momenta), and every root is measured per value (fdg_chain_propose_device_discrete, fdg_[mc_]chain_step_device_binned;
+    include/fdg.h).  ``mean`` and ``stderr`` are ``[n_bin, R]``, with ``matsubara`` complex ``[n_bin, n_freq, R]``: entry ``j`` is the
+    integral over the continuous variables at configuration ``j`` (the weight carries ``1 / p_j``, as in
+    :func:`vegas_integrate_binned`), with its own error bar; ``S``, ``Q``, ``X`` are raw over the ``n_bin R`` (``2 n_bin n_freq R``)
+    columns.  This is the sampler's side of the reference's test/ver4.jl: ``ExtKidx = Discrete(1, Nk)`` and an observable per value.
+
+    A move is an int whose bit ``d < D`` names variable ``d`` and whose bit ``D`` names the discrete variable; the default is
+    ``chain_moves(D + 1)``.  ``groups`` (with ``reweight``), ``matsubara`` and ``weight_freq`` as in :func:`chain_integrate_grouped`
+    and :func:`chain_integrate`; the discrete variable is shared by every group, and ``rho_g`` is taken of ``|jac_g s_g|`` with the
+    factor ``1 / p_j`` in ``jac_g``.  ``gamma``, ``sample_offset`` and sharding as there.  The warm-up of the Monte-Carlo form is
+    ``n_warm`` iterations of ``vegas_integrate_binned(..., groups=groups)``, which train the map and ``dmap`` (in place, with
+    ``alpha`` and ``floor``); the leaf form has no such driver, so there ``n_warm > 0`` raises ValueError and ``vmap`` / ``dmap``
+    are used as given.
+
+    Refused with ValueError: ``polar``, ``observables``, ``freq_observables`` and ``strat``; more than ``FDG_VEGAS_DIM_MAX - 1``
+    continuous variables (the discrete variable's Philox column would be the accept rule's)."""
+    for name, value in excluded.items():
+        if name not in _CHAIN_EXCLUDED or name in ("groups", "dmap"):
+            raise TypeError(f"chain_integrate_binned() got an unexpected keyword argument '{name}'")
+        if value is not None and not (name == "polar" and not value):
+            raise ValueError(f"{name} cannot be combined with the chain yet")
+    if not isinstance(dmap, DiscreteMap):
+        raise ValueError("dmap must be a DiscreteMap")
+    if groups is not None and not isinstance(groups, WeightGroups):
+        raise ValueError("groups must be a WeightGroups")
+    if groups is None and reweight is not None:
+        raise ValueError("reweight goes with groups")
+    return _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step, n_therm, moves, gamma_rel, gamma, n_warm,
+                  n_warm_sample, n_grid, alpha, seed, fixed, coef, vmap, specialize_fused, n_total, shard_start, reduce, device, matsubara,
+                  weight_freq, groups, reweight, dmap, floor)
+
+
 def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step, n_therm, moves, gamma_rel, gamma, n_warm, n_warm_sample,
            n_grid, alpha, seed, fixed, coef, vmap, specialize_fused, n_total, shard_start, reduce, device, matsubara, weight_freq,
-           wgroups=None, reweight=None) -> ChainResult:
-    """The body of :func:`chain_integrate` and, with ``wgroups``, of :func:`chain_integrate_grouped`."""
+           wgroups=None, reweight=None, dmap=None, floor=0.05) -> ChainResult:
+    """The body of :func:`chain_integrate`, with ``wgroups`` of :func:`chain_integrate_grouped`, and with ``dmap`` of
+    :func:`chain_integrate_binned`."""
     import torch
     handle = getattr(func_or_handle, "handle", func_or_handle)
     device = torch.device(device)
@@ -1012,7 +1054,20 @@ def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step,
             cin.append(t0 + i - 1 if live[k] else 0)
             cout.append(t0 + o - 1 if live[k] else 0)
         desc, _keep = capi.make_chain_matsubara(matsubara.freq, matsubara.fermionic, int(weight_freq), cin, cout, beta)
-    C = 2 * F * R if F else R                               # the columns of the walkers' sums before the normalisation's
+    n_bin = 0
+    if dmap is not None:
+        if not isinstance(dmap, DiscreteMap):
+            raise ValueError("dmap must be a DiscreteMap")
+        n_bin = dmap.n_bin
+        if n_bin > capi.FDG_CHAIN_BIN_MAX:
+            raise ValueError(f"the chain takes at most {capi.FDG_CHAIN_BIN_MAX} values of the discrete variable")
+        if not all(0 <= e < n_col for e in dmap.ext_col) or set(dmap.ext_col) & set(col):
+            raise ValueError(f"dmap.ext_col must name columns in [0, {n_col}) that col does not name")
+        if len(col) >= capi.FDG_VEGAS_DIM_MAX:
+            raise ValueError(f"a discrete variable leaves room for {capi.FDG_VEGAS_DIM_MAX - 1} continuous ones")
+        if tables is None and int(n_warm) > 0:
+            raise ValueError("the leaf form has no warm-up with a discrete variable: pass n_warm=0 (vmap and dmap are used as given)")
+    C = max(n_bin, 1) * (2 * F * R if F else R)            # the columns of the walkers' sums before the normalisation's
     B, n_step, n_therm, n_warm = int(n_walker), int(n_step), int(n_therm), int(n_warm)
     N = B if n_total is None else int(n_total)
     if B < 1 or n_step < 1 or not 0 <= n_therm < n_step or n_warm < 0 or not 0 <= int(shard_start) <= N - B:
@@ -1026,9 +1081,10 @@ def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step,
     if vmap.n_dim != len(col):
         raise ValueError("one column per variable of the map")
     D, G = vmap.n_dim, vmap.n_grid
-    moves = chain_moves(D) if moves is None else [int(m) for m in moves]
-    if not moves or not all(0 <= m < (1 << D) for m in moves):
-        raise ValueError("moves holds masks over the variables of the map")
+    DV = D + 1 if dmap is not None else D                   # the variables a move can name: bit D is the discrete one
+    moves = chain_moves(DV) if moves is None else [int(m) for m in moves]
+    if not moves or not all(0 <= m < (1 << DV) for m in moves):
+        raise ValueError("moves holds masks over the variables of the map" + (" and the discrete variable" if dmap is not None else ""))
     fx = np.zeros(n_col) if fixed is None else np.asarray(fixed, dtype=np.float64)
     if fx.shape != (n_col,):
         raise ValueError(f"fixed must hold {n_col} column values")
@@ -1054,7 +1110,9 @@ def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step,
             kw.update(n_sample=B, n_total=n_total, shard_start=shard_start)
         else:
             kw.update(n_sample=int(n_warm_sample))
-        if wgroups is not None and tables is None:
+        if dmap is not None:
+            vegas_integrate_binned(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, floor=floor, groups=wgroups, **kw)
+        elif wgroups is not None and tables is None:
             vegas_integrate_stratified(func_or_handle, tables, lo, hi, col, Stratification((1,) * D), kF, beta, lam, groups=wgroups, **kw)
         else:
             if wgroups is not None:
@@ -1070,23 +1128,34 @@ def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step,
         f64 = dict(dtype=torch.float64, device=device)
         x = torch.from_numpy(fx).to(device)[:, None].repeat(1, B).contiguous()            # [n_col, B]: sample stride 1
         xp = torch.empty_like(x)
-        fac, facp = torch.ones((D, B), **f64), torch.empty((D, B), **f64)
+        fac, facp = torch.ones((DV, B), **f64), torch.empty((DV, B), **f64)          # (row D: the discrete variable's 1 / p_j)
+        bins = binp = None
+        if dmap is not None:
+            bins, binp = (torch.zeros(B, dtype=torch.int32, device=device) for _ in range(2))
         root, a = torch.zeros((R, B), **f64), torch.zeros(B, **f64)
         total = torch.zeros((C + 1, B), **f64)
         n_acc = torch.zeros(B, dtype=torch.int32, device=device)
 
         def step(mask, off, g, flags):
-            capi.chain_propose_device(vmap.d_grid.data_ptr(), D, G, col, n_col, mask, seed, off, x.data_ptr(), B, fac.data_ptr(),
-                                      xp.data_ptr(), B, facp.data_ptr(), B, st)
+            if dmap is None:
+                capi.chain_propose_device(vmap.d_grid.data_ptr(), D, G, col, n_col, mask, seed, off, x.data_ptr(), B, fac.data_ptr(),
+                                          xp.data_ptr(), B, facp.data_ptr(), B, st)
+            else:
+                capi.chain_propose_device_discrete(vmap.d_grid.data_ptr(), D, G, col, n_col, mask & all_mask, seed, off, x.data_ptr(), B,
+                                                   fac.data_ptr(), xp.data_ptr(), B, facp.data_ptr(), bool((mask >> D) & 1),
+                                                   dmap.d_cdf.data_ptr(), n_bin, 0 if dmap.d_ext is None else dmap.d_ext.data_ptr(),
+                                                   dmap.ext_col, bins.data_ptr(), binp.data_ptr(), B, st)
             handle._chain_step(entry, mc, xp.data_ptr(), B, facp.data_ptr(), n_col, D, coef, g, seed, off, flags, x.data_ptr(), B,
-                               fac.data_ptr(), root.data_ptr(), a.data_ptr(), total.data_ptr(), n_acc.data_ptr(), B, st, desc, gdesc)
+                               fac.data_ptr(), root.data_ptr(), a.data_ptr(), total.data_ptr(), n_acc.data_ptr(), B, st, desc, gdesc,
+                               None if dmap is None else (n_bin, binp.data_ptr(), bins.data_ptr()))
 
-        entry = "_grouped" if wgroups is not None else "_matsubara" if desc is not None else ""
+        entry = "_binned" if dmap is not None else "_grouped" if wgroups is not None else "_matsubara" if desc is not None else ""
         mc = None if tables is None else (kF, beta, lam)
         gdesc = None
         if wgroups is not None:
             gdesc, _gkeep = capi.make_chain_groups(wgroups.root_group, wgroups.var_sets, rho)
-        step(all_mask, int(shard_start), 1.0, capi.FDG_CHAIN_INIT)                       # (gamma enters no result of the placement)
+        place = (1 << DV) - 1                                                            # every variable, the discrete one too
+        step(place, int(shard_start), 1.0, capi.FDG_CHAIN_INIT)                          # (gamma enters no result of the placement)
         if wgroups is not None and rho is None:
             # rho_g = 1 / mean_b |jac_g s_g| of the placement, then the placement again on the same counters with rho
             from .nodetable import FDG_NO_ROOT
@@ -1097,6 +1166,8 @@ def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step,
                 if ks:
                     c = torch.ones(len(ks), **f64) if coef is None else torch.as_tensor(np.asarray(coef, dtype=np.float64)[ks], **f64)
                     jg = fac[sorted(set(int(d) for d in wgroups.var_sets[g]))].prod(0)       # (an empty set: 1)
+                    if dmap is not None:
+                        jg = jg * fac[D]
                     sg[g] = (jg * (c[:, None] * root[ks]).sum(0)).abs().sum()
             if reduce is not None:
                 reduce(sg)
@@ -1108,7 +1179,7 @@ def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step,
                         raise ValueError(f"the map's estimate of the integral of |s_g| of group {g} is not positive and finite: pass reweight")
                     rho[g] = 1.0 / mean_g[g]
             gdesc, _gkeep = capi.make_chain_groups(wgroups.root_group, wgroups.var_sets, rho)
-            step(all_mask, int(shard_start), 1.0, capi.FDG_CHAIN_INIT)
+            step(place, int(shard_start), 1.0, capi.FDG_CHAIN_INIT)
         if gamma is None:
             sa = a.sum().reshape(1)
             if reduce is not None:
@@ -1130,5 +1201,7 @@ def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step,
     S, Q, X = h[:C + 1].copy(), h[C + 1:2 * C + 2].copy(), h[2 * C + 2:].copy()
     mean, err = chain_estimate(S, Q, X, N)                # (a root that does not exist has sums of 0: mean 0, stderr 0)
     if F:
-        mean, err = chain_complex(mean, F, R), chain_complex(err, F, R)
+        mean, err = chain_complex(mean, max(n_bin, 1) * F, R), chain_complex(err, max(n_bin, 1) * F, R)
+    if dmap is not None:
+        mean, err = (v.reshape((n_bin, F, R) if F else (n_bin, R)) for v in (mean, err))
     return ChainResult(mean, err, float(acc_sum.item()) / (N * n_step), float(gamma), vmap, S, Q, X, rho)

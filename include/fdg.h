@@ -1308,6 +1308,74 @@ int fdg_mc_chain_step_device_grouped(fdg_graph *g, const double *d_xp, int64_t x
                                      double *d_root, double *d_a, double *d_sum, int32_t *d_n_accept, const fdg_chain_matsubara *mz,
                                      const fdg_chain_groups *cg, int64_t n_walker, void *stream);
 
+/* ---- Markov chain with a discrete external variable and per-bin measurement ---------------------------------------------------------------
+ * The vertex-function caller of this path samples over (K, T, ExtKidx) with ExtKidx = MCIntegration.Discrete(1, Nk), and its `measure`
+ * adds weight / |weight| * factor into observable[extKidx, :] (test/ver4.jl:77-92, 224-237; example/strong_coupling_expansion does the
+ * same).  One chain run then yields the roots on a grid of external momenta, every grid point with its own error bar.  MCIntegration
+ * is not part of the reference checkout: no counterpart in the reference; the caller's side of test/ver4.jl.
+ *
+ * The discrete variable is one more coordinate of the map, the one of "A discrete external variable" above: in the map's coordinates
+ * a uniform u, its value j = the number of interior edges cdf[1 .. n_bin - 1] that are <= u (fdg_vegas_sample_device_discrete's rule),
+ * p_j = cdf[j + 1] - cdf[j], and its jacobian factor fd = 1.0 / p_j, one rounded division.  It is shared by every weight group, as in
+ * the direct sampler's binned calls.  The state grows by it:
+ *     d_fac, d_facp   [n_dim + 1][n_walker]; row n_dim holds fd
+ *     d_bin, d_binp   int32 [n_walker]: the 0-based j of the state and of the proposal
+ * x, root and a keep their layout.
+ *
+ * fdg_chain_propose_device_discrete: fdg_chain_propose_device's arguments and results (the continuous variables and the copied
+ * columns, the same bits), and then
+ *     move_discrete != 0:  u = what fdg_fill_uniform_device writes for counter (sample_offset + b, n_dim), the direct sampler's counter;
+ *                          binp[b] = j', facp[n_dim][b] = 1.0 / p_j', xp[ext_col[e]][b] = ext[j'][e] for e < n_ext
+ *     move_discrete == 0:  binp[b] = bin[b], facp[n_dim][b] = fac[n_dim][b]; the ext_col columns are copied from d_x like any column
+ *                          col does not name
+ * d_cdf [n_bin + 1] and d_ext [n_bin][n_ext] lie on the device, ext_col is a HOST array of n_ext columns.  FDG_E_INVALID: everything
+ * fdg_chain_propose_device refuses; a NULL d_cdf, d_bin or d_binp; d_bin == d_binp; n_bin 0; n_ext > 0 without d_ext or ext_col; an
+ * ext_col that repeats, names a column of col or one >= n_col.  FDG_E_UNSUPPORTED: that call's cases; n_dim == FDG_VEGAS_DIM_MAX (that
+ * counter belongs to the accept rule); n_bin > FDG_CHAIN_BIN_MAX; n_ext > FDG_VEGAS_EXT_MAX.  All before any device work.
+ *
+ * fdg_chain_step_device_binned and fdg_mc_chain_step_device_binned: the grouped entries' arguments plus n_bin, d_binp, d_bin.  mz and
+ * cg may each be NULL; a NULL cg is one group holding every root that exists and every variable, without a factor, as the plain
+ * entries build it.  Per walker the statements are the grouped step's, in its order, with
+ *     jac_g = the left fold of fac_d over the group's mask (an empty mask: 1.0), then one more rounded product jac_g * fd, applied
+ *             last; for every group, in the weight of the proposal (facp) and in the measurement (the state's fac)
+ * The weight a, the poison rules (an overflowing fd * jac_g s_g poisons like any non-finite t_g), the accept rule
+ * u * (a + gamma) < (a' + gamma) on counter (sample_offset + b, FDG_VEGAS_DIM_MAX), FDG_CHAIN_INIT and n_accept are unchanged.  The
+ * Metropolis ratio stays (a' + gamma) / (a + gamma): a is still a non-negative function of the point in the map's coordinates, and the
+ * proposal of the discrete coordinate is uniform both ways.  On acceptance bin[b] = binp[b] and the rows 0 .. n_dim of fac are copied.
+ * FDG_CHAIN_MEASURE, on the state AFTER the selection, with j = bin[b], R = n_root, F = n_freq, d = 1 / (a + gamma):
+ *     mz == NULL:  d_sum is [n_bin R + 1][n_walker];      sum[j R + k][b] += (jac_g(k) * r_k) * d;   sum[n_bin R][b] += d
+ *     mz != NULL:  d_sum is [2 n_bin F R + 1][n_walker];  w = (jac_g(k) * r_k) * d;  sum[2 ((j F + f) R + k)][b] += w * c,  the next
+ *                  column += w * s  for every f;  sum[2 n_bin F R][b] += d
+ * A walker writes only the columns of its current bin, through a row address of its own: no loop over the bins, nothing multiplied by
+ * zero, no atomics; every word belongs to one lane.  The columns of a root that does not exist and of every other bin are never
+ * written.  A bin outside [0, n_bin), which fdg_chain_propose_device_discrete never writes, measures nothing in that step.
+ * fdg_chain_reduce_device(d_sum, n_bin R [2 n_bin F R], ..) reduces it, and I_{j,k} = S_{j R + k} / S_last is the integral over the
+ * continuous variables at configuration j: the weight carries 1 / p_j, as in the direct sampler's binned calls.
+ *
+ * With n_bin = 1, cdf = {0, 1} and n_ext = 0, fd = 1.0 and x, fac rows 0 .. n_dim - 1, root, a, sum and n_accept are bit for bit those
+ * of fdg_[mc_]chain_step_device, .._matsubara or .._grouped with the same descriptors.
+ * The result is a function of the arguments only, as for the plain step (FDG_ROOT_SCRATCH_MB, launch shape, shards).
+ * FDG_E_INVALID: everything the plain step refuses and, of a descriptor that is given, everything the projected and the grouped step
+ * refuse; n_bin 0; a NULL d_bin or d_binp; d_bin == d_binp, or either the same buffer as another array.  FDG_E_UNSUPPORTED: those
+ * calls' cases, n_bin > FDG_CHAIN_BIN_MAX.  All before any device work. */
+#define FDG_CHAIN_BIN_MAX 64
+int fdg_chain_propose_device_discrete(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, uint32_t n_col,
+                                      uint64_t mask, uint64_t seed, uint64_t sample_offset, const double *d_x, int64_t x_col_stride,
+                                      const double *d_fac, double *d_xp, int64_t xp_col_stride, double *d_facp, int move_discrete,
+                                      const double *d_cdf, uint32_t n_bin, const double *d_ext, uint32_t n_ext, const uint32_t *ext_col,
+                                      const int32_t *d_bin, int32_t *d_binp, int64_t n_walker, void *stream);
+int fdg_chain_step_device_binned(fdg_graph *g, const double *d_xp, int64_t xp_col_stride, const double *d_facp, uint32_t n_col,
+                                 uint32_t n_dim, const double *coef, double gamma, uint64_t seed, uint64_t sample_offset, unsigned flags,
+                                 double *d_x, int64_t x_col_stride, double *d_fac, double *d_root, double *d_a, double *d_sum,
+                                 int32_t *d_n_accept, const fdg_chain_matsubara *mz, const fdg_chain_groups *cg, uint32_t n_bin,
+                                 const int32_t *d_binp, int32_t *d_bin, int64_t n_walker, void *stream);
+int fdg_mc_chain_step_device_binned(fdg_graph *g, const double *d_xp, int64_t xp_col_stride, double kF, double beta, double lambda,
+                                    const double *d_facp, uint32_t n_col, uint32_t n_dim, const double *coef, double gamma, uint64_t seed,
+                                    uint64_t sample_offset, unsigned flags, double *d_x, int64_t x_col_stride, double *d_fac,
+                                    double *d_root, double *d_a, double *d_sum, int32_t *d_n_accept, const fdg_chain_matsubara *mz,
+                                    const fdg_chain_groups *cg, uint32_t n_bin, const int32_t *d_binp, int32_t *d_bin, int64_t n_walker,
+                                    void *stream);
+
 /* Device workspace control: the interpreter keeps per-sample overflow slots in
  * an HBM panel owned by the handle; it is sized on first use for the number of
  * resident waves.  This releases it (and any loaded module). */
