@@ -58,6 +58,7 @@ EXPORTS = [
     "fdg_chain_step_device_matsubara", "fdg_mc_chain_step_device_matsubara",
     "fdg_chain_step_device_grouped", "fdg_mc_chain_step_device_grouped",
     "fdg_chain_propose_device_discrete", "fdg_chain_step_device_binned", "fdg_mc_chain_step_device_binned",
+    "fdg_chain_propose_device_polar",
 ]
 FDG_BIN_MAX = 16384     # fdg_accumulate_device_binned: largest n_bin
 FDG_VEGAS_DIM_MAX, FDG_VEGAS_GRID_MAX = 64, 1024     # the VEGAS map: most variables, most cells per variable
@@ -326,6 +327,7 @@ def lib():
     L.fdg_chain_propose_device_discrete.argtypes = L.fdg_chain_propose_device.argtypes[:-2] + [C.c_int, dp, u32, dp, u32, C.c_void_p, vp, vp, i64, vp]
     L.fdg_chain_step_device_binned.argtypes = L.fdg_chain_step_device.argtypes[:-2] + [C.c_void_p, C.c_void_p, u32, vp, vp, i64, vp]
     L.fdg_mc_chain_step_device_binned.argtypes = L.fdg_mc_chain_step_device.argtypes[:-2] + [C.c_void_p, C.c_void_p, u32, vp, vp, i64, vp]
+    L.fdg_chain_propose_device_polar.argtypes = L.fdg_chain_propose_device_discrete.argtypes[:-2] + [C.c_void_p, u32, i64, vp]
     L.fdg_powi.argtypes = [C.c_double, C.c_int32]
     L.fdg_powi.restype = C.c_double
     _lib = L
@@ -883,6 +885,113 @@ def chain_propose_device_discrete(d_grid: int, n_dim: int, n_grid: int, col, n_c
                                                   ec.ctypes.data if ec.shape[0] else None, d_bin or None, d_binp or None, B, stream))
 
 
+def chain_propose_device_polar(d_grid: int, n_dim: int, n_grid: int, col, n_col: int, mask: int, seed: int, sample_offset: int, d_x: int,
+                               xc: int, d_fac: int, d_xp: int, xpc: int, d_facp: int, move_discrete: bool, d_cdf: int, n_bin: int, d_ext: int,
+                               ext_col, d_bin: int, d_binp: int, polar, B: int, stream: int = 0):
+    """fdg_chain_propose_device_polar: :func:`chain_propose_device_discrete` (``d_cdf`` 0: :func:`chain_propose_device`; the discrete
+    variable's arguments are then ignored and ``fac`` / ``facp`` have ``n_dim`` rows) with groups of variables read as a modulus and a
+    direction.  ``polar``: a sequence of ``(var, cols)`` as :func:`vegas_sample_device_polar` takes it; a group is redrawn whole (every
+    one of its bits in ``mask``) or kept, and the factors of the polar measure go to the group's own rows of ``facp``.  The ``col``
+    entry of a grouped variable is not read (None stands for 0 there)."""
+    c = None
+    if col is not None:
+        c = np.ascontiguousarray([0 if v is None else v for v in col], dtype=np.uint32)
+        if c.shape != (n_dim,):
+            raise ValueError("col must name one column per variable")
+    ec = np.ascontiguousarray(ext_col if ext_col is not None else [], dtype=np.uint32)
+    if ec.ndim != 1:
+        raise ValueError("ext_col must be a sequence of columns")
+    arr, n_polar = _polar_array(polar)
+    check(lib().fdg_chain_propose_device_polar(d_grid or None, n_dim, n_grid, None if c is None else c.ctypes.data, n_col, mask, seed,
+                                               sample_offset, d_x or None, xc, d_fac or None, d_xp or None, xpc, d_facp or None,
+                                               1 if move_discrete else 0, d_cdf or None, n_bin, d_ext or None, ec.shape[0],
+                                               ec.ctypes.data if ec.shape[0] else None, d_bin or None, d_binp or None,
+                                               C.addressof(arr) if n_polar else None, n_polar, B, stream))
+
+
+def sincos_table(x):
+    """``(s, c)`` of fdg_sincos for an array of doubles in ``[0, 2 pi]``: one call of the library's routine per entry."""
+    x = np.asarray(x, dtype=np.float64)
+    s, c = np.empty(x.shape), np.empty(x.shape)
+    fn, vs, vc = lib().fdg_sincos, C.c_double(), C.c_double()
+    ps, pc = C.byref(vs), C.byref(vc)
+    for i, v in enumerate(x.ravel().tolist()):
+        fn(v, ps, pc)
+        s.flat[i], c.flat[i] = vs.value, vc.value
+    return s, c
+
+
+def chain_propose_polar_reference(grid, col, polar, state, mask: int, u, cdf=None, ext=None, ext_col=(), move_discrete: bool = False,
+                                  u_disc=None, sincos=None):
+    """fdg_chain_propose_device_polar restated in numpy, in the device's fp64 order: ``(xp, facp, binp)`` of the state's ``x``, ``fac``
+    (and ``bin``), ``binp`` None without a discrete variable (``cdf`` None).  The variables of no group and the discrete variable are
+    drawn by the statements of the chain mirrors' proposal (:func:`chain_reference`, :func:`chain_binned_reference`); ``polar`` holds
+    ``(var, cols)`` pairs; ``u [B, D]`` the uniforms of the counters ``(sample_offset + b, d)`` (only the columns of ``mask`` are
+    read), ``u_disc [B]`` those of column ``n_dim``.  ``sincos(x) -> (s, c)`` replaces :func:`sincos_table`, the library's own routine
+    entry by entry, by a faster one with the same bits.  The step mirrors take the result as their ``proposal``."""
+    sc = sincos_table if sincos is None else sincos
+    grid = np.asarray(grid, dtype=np.float64)
+    D, G = grid.shape[0], grid.shape[1] - 1
+    x, fac = np.array(state["x"], dtype=np.float64), np.array(state["fac"], dtype=np.float64)
+    B = x.shape[1]
+    groups = [(int(var), tuple(int(c) for c in cols)) for var, cols in (polar or ())]
+    grouped = set()
+    for var, cols in groups:
+        mine = set(range(var, var + len(cols)))
+        if len(cols) not in (2, 3) or var < 0 or var + len(cols) > D or mine & grouped:
+            raise ValueError("a polar group has 2 or 3 variables inside the map, apart from every other group's")
+        has = [(mask >> d) & 1 for d in sorted(mine)]
+        if any(has) and not all(has):
+            raise ValueError("mask names some but not all variables of a polar group")
+        grouped |= mine
+    if fac.shape != (D + (cdf is not None), B):
+        raise ValueError("fac must be [n_dim, n_walker], or [n_dim + 1, n_walker] with a discrete variable")
+    cols_of = list(range(D)) if col is None else [None if c is None else int(c) for c in col]
+    xp, facp = x.copy(), fac.copy()
+
+    def draw(d):
+        y = np.asarray(u, dtype=np.float64)[:, d] * np.float64(G)
+        c = np.minimum(y.astype(np.int64), G - 1)
+        lo = grid[d, c]
+        wd = grid[d, c + 1] - lo
+        return lo + (y - c.astype(np.float64)) * wd, np.float64(G) * wd
+
+    for d in range(D):
+        if d not in grouped and (mask >> d) & 1:
+            xp[cols_of[d]], facp[d] = draw(d)
+    for var, cols in groups:
+        if not (mask >> var) & 1:
+            continue
+        k, fk = draw(var)
+        va, fa = draw(var + 1)
+        if len(cols) == 3:
+            vp, fp = draw(var + 2)
+            st, ct = sc(va)
+            sp, cp = sc(vp)
+            ks = k * st
+            xp[cols[0]], xp[cols[1]], xp[cols[2]] = ks * cp, ks * sp, k * ct
+            f0 = fk * k
+            facp[var], facp[var + 1], facp[var + 2] = f0 * k, fa * st, fp
+        else:
+            sp, cp = sc(va)
+            xp[cols[0]], xp[cols[1]] = k * cp, k * sp
+            facp[var], facp[var + 1] = fk * k, fa
+    binp = None
+    if cdf is not None:
+        cdf = np.asarray(cdf, dtype=np.float64)
+        n_bin = cdf.shape[0] - 1
+        binp = np.array(state["bin"], dtype=np.int32)
+        if move_discrete:
+            ud = np.asarray(u_disc, dtype=np.float64)
+            jp = np.searchsorted(cdf[1:n_bin], ud, side="right")        # the number of interior edges <= u
+            with np.errstate(all="ignore"):
+                facp[D] = 1.0 / (cdf[jp + 1] - cdf[jp])
+            binp = jp.astype(np.int32)
+            for e, c in enumerate(ext_col):
+                xp[int(c)] = np.asarray(ext, dtype=np.float64)[jp, e]
+    return xp, facp, binp
+
+
 def chain_reduce_device(d_sum: int, n_root: int, B: int, d_out: int, stream: int = 0):
     """fdg_chain_reduce_device: ``out [3 R + 2] +=`` (S [R + 1], Q [R + 1], X [R]) of the walkers' sums ``[n_root + 1, B]``."""
     check(lib().fdg_chain_reduce_device(d_sum or None, n_root, B, d_out or None, stream))
@@ -1064,21 +1173,23 @@ def make_chain_groups(root_group, var_sets, reweight=None):
 
 
 def chain_grouped_reference(grid, col, state, mask: int, u, u_acc, gamma: float, flags: int, eval_roots, root_group, var_sets,
-                            reweight=None, coef=None, exists=None, matsubara=None, phase_table=None):
+                            reweight=None, coef=None, exists=None, matsubara=None, phase_table=None, proposal=None):
     """One step of the grouped chain restated in numpy (include/fdg.h, "Markov chain with weight groups and reweighting between
     orders"): fdg_chain_propose_device, then fdg_[mc_]chain_step_device_grouped, in the device's fp64 order, so that the state and the
     sums compare bit for bit.  The arguments of :func:`chain_reference` with ``root_group [R]``, ``var_sets[g]`` the variables of group
     ``g`` and ``reweight [n_group]`` or None.  ``matsubara``: None (``state["sum"]`` is ``[R + 1, B]``), or a dict of the projected
     step's descriptor -- ``freq``, ``fermionic``, ``weight_freq``, ``root_col_in``, ``root_col_out``, ``beta`` -- with
     ``state["sum"]`` ``[2 F R + 1, B]``; the phases are the library's own (fdg_matsubara_phase through
-    :func:`matsubara_phase_table`, or ``phase_table`` as in :func:`chain_matsubara_reference`)."""
+    :func:`matsubara_phase_table`, or ``phase_table`` as in :func:`chain_matsubara_reference`).  ``proposal``: None, or ``(xp, facp,
+    binp)`` made elsewhere (:func:`chain_propose_polar_reference`), which the step then takes in place of its own; ``mask`` and ``u``
+    are not read."""
     return _chain_grouped_step(grid, col, state, mask, u, u_acc, gamma, flags, eval_roots, root_group, var_sets, reweight, coef, exists,
-                               matsubara, phase_table, None)
+                               matsubara, phase_table, None, proposal)
 
 
 def chain_binned_reference(grid, col, state, mask: int, u, u_acc, gamma: float, flags: int, eval_roots, cdf, ext=None, ext_col=(),
                            move_discrete: bool = True, u_disc=None, root_group=None, var_sets=None, reweight=None, coef=None, exists=None,
-                           matsubara=None, phase_table=None):
+                           matsubara=None, phase_table=None, proposal=None):
     """One step of the chain with a discrete variable restated in numpy (include/fdg.h, "Markov chain with a discrete external variable
     and per-bin measurement"): fdg_chain_propose_device_discrete, then fdg_[mc_]chain_step_device_binned, in the device's fp64 order,
     so that the state and the sums compare bit for bit.  These are :func:`chain_grouped_reference`'s statements, run by the same body,
@@ -1086,20 +1197,25 @@ def chain_binned_reference(grid, col, state, mask: int, u, u_acc, gamma: float, 
     and its columns of ``x``, ``move_discrete`` whether the variable is redrawn, ``u_disc [B]`` the uniforms of the counters
     ``(sample_offset + b, n_dim)`` (read only then).  ``root_group`` and ``var_sets`` None: one group of every root and every variable
     (a NULL ``cg``).  ``state`` holds ``fac [D + 1, B]`` (row ``D``: ``1 / p_j``), ``bin [B]`` (int32) and ``sum``
-    ``[n_bin R + 1, B]`` or ``[2 n_bin F R + 1, B]``; the result has ``bin`` and ``binp`` too."""
+    ``[n_bin R + 1, B]`` or ``[2 n_bin F R + 1, B]``; the result has ``bin`` and ``binp`` too.  ``proposal`` as in
+    :func:`chain_grouped_reference` (``move_discrete`` and ``u_disc`` are then not read either)."""
     D, R = np.asarray(grid).shape[0], np.asarray(state["root"]).shape[0]
     if root_group is None and var_sets is None:
         root_group, var_sets = [0] * R, [tuple(range(D))]
     binned = dict(cdf=np.asarray(cdf, dtype=np.float64), ext=None if ext is None else np.asarray(ext, dtype=np.float64),
                   ext_col=[int(e) for e in ext_col], move=bool(move_discrete), u=u_disc)
     return _chain_grouped_step(grid, col, state, mask, u, u_acc, gamma, flags, eval_roots, root_group, var_sets, reweight, coef, exists,
-                               matsubara, phase_table, binned)
+                               matsubara, phase_table, binned, proposal)
 
 
 def _chain_grouped_step(grid, col, state, mask, u, u_acc, gamma, flags, eval_roots, root_group, var_sets, reweight, coef, exists, matsubara,
-                        phase_table, binned):
+                        phase_table, binned, proposal=None):
     """The body of :func:`chain_grouped_reference` (``binned`` None) and :func:`chain_binned_reference`: where ``binned`` is None no
-    statement of the discrete variable runs."""
+    statement of the discrete variable runs.  With ``proposal`` the step's own proposal is not made."""
+    if proposal is not None:
+        mask = 0
+        if binned is not None:
+            binned = dict(binned, move=False)
     table = matsubara_phase_table if phase_table is None else phase_table
     grid = np.asarray(grid, dtype=np.float64)
     D, G = grid.shape[0], grid.shape[1] - 1
@@ -1157,6 +1273,12 @@ def _chain_grouped_step(grid, col, state, mask, u, u_acc, gamma, flags, eval_roo
             binp = jp.astype(np.int32)
             for e, c in enumerate(binned["ext_col"]):
                 xp[c] = binned["ext"][jp, e]
+    if proposal is not None:
+        xp, facp = (np.array(v, dtype=np.float64) for v in proposal[:2])
+        if xp.shape != x.shape or facp.shape != fac.shape:
+            raise ValueError("the proposal's xp and facp have the shapes of the state's x and fac")
+        if binned is not None:
+            binp = np.array(proposal[2], dtype=np.int32)
     with np.errstate(all="ignore"):
         rp = np.asarray(eval_roots(xp), dtype=np.float64) if live else np.zeros((R, B))
         ph = phases(xp, [freq[wf]]) if mz is not None else None

@@ -124,6 +124,102 @@ fdg_chain_propose_discrete(const double *__restrict__ grid, uint32_t D, uint32_t
   }
 }
 
+// The groups of polar variables of fdg_chain_propose_polar (a kernel argument, by value; fdg_binned.hip's VegasPolar): group g takes the
+// variables var[g] .. var[g] + dim[g] - 1 and writes the Cartesian components to the columns col[g][0 .. dim[g]).  grouped: bit d set
+// = variable d belongs to a group.
+struct ChainPolar {
+  uint64_t grouped;
+  uint32_t n;
+  uint32_t var[FDG_VEGAS_POLAR_MAX], dim[FDG_VEGAS_POLAR_MAX];
+  uint32_t col[FDG_VEGAS_POLAR_MAX][3];
+};
+
+// fdg_chain_propose / fdg_chain_propose_discrete (cdf null: no discrete variable, fac and facp have D rows) with groups of variables
+// read as (k, phi) or (k, theta, phi) (fdg_chain_propose_device_polar).  The ungrouped variables first, by the plain
+// kernel's statements; then group by group, in the order of the array.  A group moves whole or not at all (the host has refused a mask
+// that names part of one: the bit of its first variable decides): moved, its two or three values are drawn on their own counters,
+// stay in registers, and give the group's columns and the measure's factors, each factor in the row of its own variable
+//     3D:  facp[var] = ((G wd_k) k) k,  facp[var + 1] = (G wd_theta) sin(theta),  facp[var + 2] = G wd_phi
+//     2D:  facp[var] = (G wd_k) k,      facp[var + 1] = G wd_phi
+// so that the select kernel's left fold over a mask is the jacobian of the polar measure with no change to it; kept, its rows of fac
+// are copied (its columns were copied with all the others).  No per-lane array, no LDS: everything indexed by g is wave-uniform.
+__global__ void __launch_bounds__(256)
+fdg_chain_propose_polar(const double *__restrict__ grid, uint32_t D, uint32_t G, ChainCols col, uint32_t n_col, uint64_t mask, uint64_t seed,
+                        uint64_t off, const double *__restrict__ x, long xc, const double *__restrict__ fac, double *__restrict__ xp, long xpc,
+                        double *__restrict__ facp, ChainPolar pol, uint32_t move, const double *__restrict__ cdf, uint32_t n_bin,
+                        const double *__restrict__ ext, uint32_t n_ext, ChainExtCols ecol, const int32_t *__restrict__ bin,
+                        int32_t *__restrict__ binp, long n) {
+  const long b = blockIdx.x * 256L + threadIdx.x;
+  if (b >= n) return;
+  for (uint32_t c = 0; c < n_col; ++c) xp[(long)c * xpc + b] = x[(long)c * xc + b];
+  for (uint32_t d = 0; d < D; ++d) {
+    if ((pol.grouped >> d) & 1u) continue;
+    const size_t at = (size_t)d * (size_t)n + (size_t)b;
+    if ((mask >> d) & 1u) {
+      double f;
+      const double v = chain_draw(grid, d, G, off + (uint64_t)b, seed, f);
+      xp[(long)col.c[d] * xpc + b] = v;
+      facp[at] = f;
+    } else {
+      facp[at] = fac[at];
+    }
+  }
+  for (uint32_t g = 0; g < pol.n; ++g) {
+    const uint32_t var = pol.var[g];
+    const bool three = pol.dim[g] == 3;
+    const size_t at = (size_t)var * (size_t)n + (size_t)b;
+    if (!((mask >> var) & 1u)) {
+      facp[at] = fac[at];
+      facp[at + (size_t)n] = fac[at + (size_t)n];
+      if (three) facp[at + 2u * (size_t)n] = fac[at + 2u * (size_t)n];
+      continue;
+    }
+    double fk, fa;
+    const double k = chain_draw(grid, var, G, off + (uint64_t)b, seed, fk);
+    const double va = chain_draw(grid, var + 1u, G, off + (uint64_t)b, seed, fa);
+    if (three) {
+      double fp;
+      const double vp = chain_draw(grid, var + 2u, G, off + (uint64_t)b, seed, fp);
+      double st, ct, sp, cp;
+      fdg_sincos_impl(va, st, ct);
+      fdg_sincos_impl(vp, sp, cp);
+      const double ks = k * st;
+      xp[(long)pol.col[g][0] * xpc + b] = ks * cp;
+      xp[(long)pol.col[g][1] * xpc + b] = ks * sp;
+      xp[(long)pol.col[g][2] * xpc + b] = k * ct;
+      double f0 = fk * k;
+      f0 = f0 * k;
+      facp[at] = f0;
+      facp[at + (size_t)n] = fa * st;
+      facp[at + 2u * (size_t)n] = fp;
+    } else {
+      double sp, cp;
+      fdg_sincos_impl(va, sp, cp);
+      xp[(long)pol.col[g][0] * xpc + b] = k * cp;
+      xp[(long)pol.col[g][1] * xpc + b] = k * sp;
+      facp[at] = fk * k;
+      facp[at + (size_t)n] = fa;
+    }
+  }
+  if (!cdf) return;
+  const size_t at = (size_t)D * (size_t)n + (size_t)b;
+  if (move) {
+    const double u = fdg_philox_u53(off + (uint64_t)b, D, seed);
+    uint32_t lo = 0, hi = n_bin - 1u;                     // j in [lo, hi]: cdf[1 .. lo] <= u < cdf[hi + 1 ..]
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (cdf[mid + 1u] <= u) lo = mid + 1u; else hi = mid;
+    }
+    const double p = cdf[lo + 1u] - cdf[lo];
+    binp[b] = (int32_t)lo;
+    for (uint32_t e = 0; e < n_ext; ++e) xp[(long)ecol.c[e] * xpc + b] = ext[(size_t)lo * n_ext + e];
+    facp[at] = 1.0 / p;
+  } else {
+    binp[b] = bin[b];
+    facp[at] = fac[at];
+  }
+}
+
 // The jacobian of one group for walker b: the left fold of f[d][b] over ascending d with bit d in mask; an empty mask gives 1.0.
 __device__ __forceinline__ double chain_group_jac(const double *__restrict__ f, uint64_t mask, uint32_t D, long nw, long b) {
   double j = 1.0;
@@ -554,6 +650,40 @@ int check_propose(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const u
   return FDG_OK;
 }
 
+// The checks of the discrete variable's arguments in the propose calls that take one, after check_propose, in one order; ecols = the
+// columns of its table.  skip: bit d set = col[d] is not read (a variable of a polar group).
+int check_propose_discrete(uint32_t n_dim, const ChainCols &cols, uint64_t skip, uint32_t n_col, const double *d_cdf, uint32_t n_bin,
+                           const double *d_ext, uint32_t n_ext, const uint32_t *ext_col, const int32_t *d_bin, const int32_t *d_binp,
+                           ChainExtCols &ecols) {
+  if (n_dim == FDG_VEGAS_DIM_MAX) { set_error("n_dim == FDG_VEGAS_DIM_MAX: the discrete variable's counter is the accept rule's"); return FDG_E_UNSUPPORTED; }
+  if (!d_cdf || !d_bin || !d_binp) { set_error("null device buffer"); return FDG_E_INVALID; }
+  if (d_bin == d_binp) { set_error("d_bin and d_binp are the same buffer"); return FDG_E_INVALID; }
+  if (n_bin == 0) { set_error("n_bin == 0"); return FDG_E_INVALID; }
+  if (n_bin > FDG_CHAIN_BIN_MAX) { set_error("n_bin > FDG_CHAIN_BIN_MAX"); return FDG_E_UNSUPPORTED; }
+  if (n_ext > FDG_VEGAS_EXT_MAX) { set_error("n_ext > FDG_VEGAS_EXT_MAX"); return FDG_E_UNSUPPORTED; }
+  if (n_ext && (!d_ext || !ext_col)) { set_error("n_ext > 0 needs d_ext and ext_col"); return FDG_E_INVALID; }
+  for (uint32_t e = 0; e < FDG_VEGAS_EXT_MAX; ++e) ecols.c[e] = e < n_ext ? ext_col[e] : 0u;
+  for (uint32_t e = 0; e < n_ext; ++e) {
+    if (ecols.c[e] >= n_col) { set_error("ext_col names a column >= n_col"); return FDG_E_INVALID; }
+    for (uint32_t f = 0; f < e; ++f)
+      if (ecols.c[f] == ecols.c[e]) { set_error("ext_col names a column twice"); return FDG_E_INVALID; }
+    for (uint32_t d = 0; d < n_dim; ++d)
+      if (!((skip >> d) & 1u) && cols.c[d] == ecols.c[e]) { set_error("ext_col names a column of col"); return FDG_E_INVALID; }
+  }
+  return FDG_OK;
+}
+
+// The variables that the groups of `polar` hold, as far as the groups are well formed (dim 2 or 3, inside n_dim): what the checks
+// that run before the groups' own need, since the col entry of a grouped variable is not read.
+uint64_t polar_vars(const fdg_vegas_polar *polar, uint32_t n_polar, uint32_t n_dim) {
+  uint64_t grouped = 0;
+  if (!polar) return 0;
+  for (uint32_t g = 0; g < std::min<uint32_t>(n_polar, FDG_VEGAS_POLAR_MAX); ++g)
+    if ((polar[g].dim == 2 || polar[g].dim == 3) && polar[g].var < n_dim && polar[g].var + polar[g].dim <= n_dim)
+      grouped |= ((1ull << polar[g].dim) - 1ull) << polar[g].var;
+  return grouped;
+}
+
 }  // namespace
 
 extern "C" {
@@ -639,22 +769,9 @@ int fdg_chain_propose_device_discrete(const double *d_grid, uint32_t n_dim, uint
   ChainCols cols;
   const int rc = check_propose(d_grid, n_dim, n_grid, col, n_col, mask, d_x, x_col_stride, d_fac, d_xp, xp_col_stride, d_facp, B, cols);
   if (rc) return rc;
-  if (n_dim == FDG_VEGAS_DIM_MAX) { set_error("n_dim == FDG_VEGAS_DIM_MAX: the discrete variable's counter is the accept rule's"); return FDG_E_UNSUPPORTED; }
-  if (!d_cdf || !d_bin || !d_binp) { set_error("null device buffer"); return FDG_E_INVALID; }
-  if (d_bin == d_binp) { set_error("d_bin and d_binp are the same buffer"); return FDG_E_INVALID; }
-  if (n_bin == 0) { set_error("n_bin == 0"); return FDG_E_INVALID; }
-  if (n_bin > FDG_CHAIN_BIN_MAX) { set_error("n_bin > FDG_CHAIN_BIN_MAX"); return FDG_E_UNSUPPORTED; }
-  if (n_ext > FDG_VEGAS_EXT_MAX) { set_error("n_ext > FDG_VEGAS_EXT_MAX"); return FDG_E_UNSUPPORTED; }
-  if (n_ext && (!d_ext || !ext_col)) { set_error("n_ext > 0 needs d_ext and ext_col"); return FDG_E_INVALID; }
   ChainExtCols ecols;
-  for (uint32_t e = 0; e < FDG_VEGAS_EXT_MAX; ++e) ecols.c[e] = e < n_ext ? ext_col[e] : 0u;
-  for (uint32_t e = 0; e < n_ext; ++e) {
-    if (ecols.c[e] >= n_col) { set_error("ext_col names a column >= n_col"); return FDG_E_INVALID; }
-    for (uint32_t f = 0; f < e; ++f)
-      if (ecols.c[f] == ecols.c[e]) { set_error("ext_col names a column twice"); return FDG_E_INVALID; }
-    for (uint32_t d = 0; d < n_dim; ++d)
-      if (cols.c[d] == ecols.c[e]) { set_error("ext_col names a column of col"); return FDG_E_INVALID; }
-  }
+  const int rd = check_propose_discrete(n_dim, cols, 0, n_col, d_cdf, n_bin, d_ext, n_ext, ext_col, d_bin, d_binp, ecols);
+  if (rd) return rd;
   if (B == 0) return FDG_OK;
   hipLaunchKernelGGL(fdg_chain_propose_discrete, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_grid, n_dim, n_grid,
                      cols, n_col, mask, seed, sample_offset, d_x, (long)x_col_stride, d_fac, d_xp, (long)xp_col_stride, d_facp,
@@ -663,7 +780,64 @@ int fdg_chain_propose_device_discrete(const double *d_grid, uint32_t n_dim, uint
   return FDG_OK;
 }
 
-int fdg_chain_step_device_binned(fdg_graph *g, const double *d_xp, int64_t xp_col_stride, const double *d_facp, uint32_t n_col,
+int fdg_chain_propose_device_polar(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, uint32_t n_col, uint64_t mask,
+                                   uint64_t seed, uint64_t sample_offset, const double *d_x, int64_t x_col_stride, const double *d_fac,
+                                   double *d_xp, int64_t xp_col_stride, double *d_facp, int move_discrete, const double *d_cdf,
+                                   uint32_t n_bin, const double *d_ext, uint32_t n_ext, const uint32_t *ext_col, const int32_t *d_bin,
+                                   int32_t *d_binp, const fdg_vegas_polar *polar, uint32_t n_polar, int64_t B, void *stream) {
+  // the col entry of a grouped variable is not read: 0 stands in for it in the checks that come before the groups' own
+  const uint64_t skip = polar_vars(polar, n_polar, n_dim);
+  uint32_t lcol[FDG_VEGAS_DIM_MAX];
+  for (uint32_t d = 0; d < std::min<uint32_t>(n_dim, FDG_VEGAS_DIM_MAX); ++d) lcol[d] = ((skip >> d) & 1u) ? 0u : (col ? col[d] : d);
+  ChainCols cols;
+  int rc = check_propose(d_grid, n_dim, n_grid, lcol, n_col, mask, d_x, x_col_stride, d_fac, d_xp, xp_col_stride, d_facp, B, cols);
+  if (rc) return rc;
+  ChainExtCols ecols = {};
+  if (d_cdf) {
+    rc = check_propose_discrete(n_dim, cols, skip, n_col, d_cdf, n_bin, d_ext, n_ext, ext_col, d_bin, d_binp, ecols);
+    if (rc) return rc;
+  } else {
+    n_bin = 1, n_ext = 0;                                  // no discrete variable: its arguments are ignored
+  }
+  if (n_polar > FDG_VEGAS_POLAR_MAX) { set_error("n_polar > FDG_VEGAS_POLAR_MAX"); return FDG_E_UNSUPPORTED; }
+  if (n_polar && !polar) { set_error("n_polar > 0 needs polar"); return FDG_E_INVALID; }
+  ChainPolar pol = {};
+  pol.n = n_polar;
+  for (uint32_t g = 0; g < n_polar; ++g) {
+    if (polar[g].dim != 2 && polar[g].dim != 3) { set_error("a polar group has 2 or 3 variables"); return FDG_E_INVALID; }
+    if (polar[g].var >= n_dim || polar[g].var + polar[g].dim > n_dim) { set_error("a polar group reaches past n_dim"); return FDG_E_INVALID; }
+    const uint64_t bits = ((1ull << polar[g].dim) - 1ull) << polar[g].var;
+    if (pol.grouped & bits) { set_error("two polar groups share a variable"); return FDG_E_INVALID; }
+    pol.grouped |= bits;
+    pol.var[g] = polar[g].var;
+    pol.dim[g] = polar[g].dim;
+    for (uint32_t i = 0; i < polar[g].dim; ++i) pol.col[g][i] = polar[g].col[i];
+  }
+  // every column written once: the variables of no group, the groups' components, the discrete variable's table
+  std::vector<uint32_t> named;
+  for (uint32_t d = 0; d < n_dim; ++d)
+    if (!((pol.grouped >> d) & 1u)) named.push_back(cols.c[d]);
+  for (uint32_t g = 0; g < n_polar; ++g)
+    for (uint32_t i = 0; i < pol.dim[g]; ++i) {
+      if (pol.col[g][i] >= n_col) { set_error("a polar group names a column >= n_col"); return FDG_E_INVALID; }
+      named.push_back(pol.col[g][i]);
+    }
+  named.insert(named.end(), ecols.c, ecols.c + n_ext);
+  std::sort(named.begin(), named.end());
+  if (std::adjacent_find(named.begin(), named.end()) != named.end()) { set_error("a column of x is named twice"); return FDG_E_INVALID; }
+  for (uint32_t g = 0; g < n_polar; ++g) {
+    const uint64_t bits = ((1ull << pol.dim[g]) - 1ull) << pol.var[g], has = mask & bits;
+    if (has && has != bits) { set_error("mask names some but not all variables of a polar group"); return FDG_E_INVALID; }
+  }
+  if (B == 0) return FDG_OK;
+  hipLaunchKernelGGL(fdg_chain_propose_polar, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_grid, n_dim, n_grid, cols,
+                     n_col, mask, seed, sample_offset, d_x, (long)x_col_stride, d_fac, d_xp, (long)xp_col_stride, d_facp, pol,
+                     move_discrete ? 1u : 0u, d_cdf, n_bin, d_ext, n_ext, ecols, d_bin, d_binp, (long)B);
+  HIP_TRY(hipGetLastError());
+  return FDG_OK;
+}
+
+int fdg_chain_step_device_binned(fdg_graph *g,const double *d_xp, int64_t xp_col_stride, const double *d_facp, uint32_t n_col,
                                  uint32_t n_dim, const double *coef, double gamma, uint64_t seed, uint64_t sample_offset, unsigned flags,
                                  double *d_x, int64_t x_col_stride, double *d_fac, double *d_root, double *d_a, double *d_sum,
                                  int32_t *d_n_accept, const fdg_chain_matsubara *mz, const fdg_chain_groups *cg, uint32_t n_bin,

@@ -44,6 +44,9 @@ normalises the result; the error bar comes from the spread across the independen
 runs inside the chain (fdg_[mc_]chain_step_device_matsubara): the weight is the modulus of the projected sum at one frequency, and
 every root is measured at every frequency.  With weight groups (``chain_integrate_grouped``; fdg_[mc_]chain_step_device_grouped)
 several orders of a series walk in one chain: every group carries the jacobian of its own variables and a reweight factor.
+With spherical momentum variables (``chain_integrate_polar``, ``chain_moves_polar``; fdg_chain_propose_device_polar) the proposal
+draws a group's modulus and direction and writes the Cartesian columns; the measure's factors ride in the group's own rows of the
+per-variable factors, so every step serves as it is.  A group is redrawn whole or not at all.
 """
 from __future__ import annotations
 
@@ -880,6 +883,23 @@ def chain_moves(n_dim: int) -> List[int]:
     return [(1 << D) - 1] + [1 << d for d in range(D)]
 
 
+def chain_moves_polar(n_dim: int, polar) -> List[int]:
+    """The default moves of :func:`chain_integrate_polar`: the mask of all ``n_dim`` variables (the discrete one counted, where there
+    is one), then one mask per unit in the order of the units' first variables: a polar group (``polar``: :class:`PolarVar` or
+    ``(var, cols)`` pairs) with all its variables, a variable of no group, the discrete variable."""
+    D = int(n_dim)
+    first = {}
+    for p in polar:
+        var, cols = (p.var, p.cols) if isinstance(p, PolarVar) else p
+        first[int(var)] = len(cols)
+    out, d = [(1 << D) - 1], 0
+    while d < D:
+        n = first.get(d, 1)
+        out.append(((1 << n) - 1) << d)
+        d += n
+    return out
+
+
 _CHAIN_EXCLUDED = ("polar", "groups", "dmap", "observables", "freq_observables", "strat")
 _CHAIN_TRAIN_KEY = 0x632BE59BD9B4E019       # added to ``seed`` for the map's training: the chain's counters are used once
 
@@ -1014,11 +1034,58 @@ def chain_integrate_binned(func_or_handle, tables, lo, hi, col, dmap: DiscreteMa
                   weight_freq, groups, reweight, dmap, floor)
 
 
+def chain_integrate_polar(func_or_handle, tables, lo, hi, col, polar: Sequence[PolarVar], kF: float = 0.0, beta: float = 1.0, lam: float = 0.0, *,
+                          n_walker: int, n_step: int, n_therm: int, moves: Optional[Sequence[int]] = None, gamma_rel: float = 1.0,
+                          gamma: Optional[float] = None, n_warm: int = 5, n_warm_sample: Optional[int] = None, n_grid: int = 64,
+                          alpha: float = 0.5, floor: float = 0.05, seed: int = 0, fixed=None, coef=None, vmap: Optional[VegasMap] = None,
+                          specialize_fused: bool = True, n_total: Optional[int] = None, shard_start: int = 0,
+                          reduce: Optional[Callable] = None, device="cuda", groups: Optional[WeightGroups] = None, reweight=None,
+                          dmap: Optional[DiscreteMap] = None, matsubara: Optional[MatsubaraProjection] = None, weight_freq: int = 0,
+                          **excluded) -> ChainResult:
+    """The chain with spherical momentum variables (``polar``: a sequence of :class:`PolarVar`, as in :func:`vegas_integrate`), which
+    the other chain drivers refuse: the loop momenta are a modulus and a direction over a ball (:func:`ball`), MCIntegration's
+    ``FermiK``, the way every caller of the chain in the reference draws them (test/hubbard.jl:85, test/ver4.jl:77-92;
+    fdg_chain_propose_device_polar, include/fdg.h).  The ``col`` entry of a grouped variable is None; the group writes its own columns.
+
+    The factors of the polar measure -- ``k**2`` and ``sin(theta)``, or ``k`` -- are kept per variable in the rows of ``fac`` the chain
+    already carries, so the step is the one of :func:`chain_integrate`, :func:`chain_integrate_grouped` (``groups``, ``reweight``) or
+    :func:`chain_integrate_binned` (``dmap``), with ``matsubara`` and ``weight_freq`` as there; the result has that driver's shapes.
+    A polar group belongs to a weight group whole or not at all.
+
+    A move redraws a polar group whole or not at all: the state holds the Cartesian columns, not ``(k, theta, phi)``, which moving the
+    modulus or the direction alone would need.  A move naming part of a group raises ValueError; the default is
+    :func:`chain_moves_polar`: everything, then one move per unit (a polar group, a variable of no group, the discrete variable).
+
+    The warm-up is the direct sampler's with the same groups: ``vegas_integrate(polar=..., groups=...)`` in the Monte-Carlo form,
+    ``vegas_integrate_binned(polar=..., groups=...)`` with ``dmap``, ``vegas_integrate_stratified(..., Stratification((1,) * D),
+    polar=..., groups=...)`` in the leaf form; the leaf form with ``dmap`` has none (``n_warm > 0`` raises ValueError).
+
+    Refused with ValueError: ``observables``, ``freq_observables`` and ``strat``.  Not built: moving the modulus or the direction of a
+    group alone."""
+    for name, value in excluded.items():
+        if name not in _CHAIN_EXCLUDED or name in ("polar", "groups", "dmap"):
+            raise TypeError(f"chain_integrate_polar() got an unexpected keyword argument '{name}'")
+        if value is not None:
+            raise ValueError(f"{name} cannot be combined with the chain yet")
+    polar = list(polar) if polar is not None else None
+    if polar is None or not all(isinstance(p, PolarVar) for p in polar):
+        raise ValueError("polar must be a sequence of PolarVar")
+    if dmap is not None and not isinstance(dmap, DiscreteMap):
+        raise ValueError("dmap must be a DiscreteMap")
+    if groups is not None and not isinstance(groups, WeightGroups):
+        raise ValueError("groups must be a WeightGroups")
+    if groups is None and reweight is not None:
+        raise ValueError("reweight goes with groups")
+    return _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step, n_therm, moves, gamma_rel, gamma, n_warm,
+                  n_warm_sample, n_grid, alpha, seed, fixed, coef, vmap, specialize_fused, n_total, shard_start, reduce, device, matsubara,
+                  weight_freq, groups, reweight, dmap, floor, polar)
+
+
 def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step, n_therm, moves, gamma_rel, gamma, n_warm, n_warm_sample,
            n_grid, alpha, seed, fixed, coef, vmap, specialize_fused, n_total, shard_start, reduce, device, matsubara, weight_freq,
-           wgroups=None, reweight=None, dmap=None, floor=0.05) -> ChainResult:
-    """The body of :func:`chain_integrate`, with ``wgroups`` of :func:`chain_integrate_grouped`, and with ``dmap`` of
-    :func:`chain_integrate_binned`."""
+           wgroups=None, reweight=None, dmap=None, floor=0.05, polar=None) -> ChainResult:
+    """The body of :func:`chain_integrate`, with ``wgroups`` of :func:`chain_integrate_grouped`, with ``dmap`` of
+    :func:`chain_integrate_binned`, and with ``polar`` of :func:`chain_integrate_polar`."""
     import torch
     handle = getattr(func_or_handle, "handle", func_or_handle)
     device = torch.device(device)
@@ -1027,8 +1094,9 @@ def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step,
         n_col = handle.table.n_leaf
     else:
         n_col = int(tables.n_loop) * int(tables.dim) + int(tables.n_tau)
-    col = [int(c) for c in col]
-    if len(set(col)) != len(col) or not all(0 <= c < n_col for c in col):
+    col = [None if (c is None and polar is not None) else int(c) for c in col]
+    written = [c for c in col if c is not None] + [int(c) for p in (polar or ()) for c in p.cols]
+    if len(set(written)) != len(written) or not all(0 <= c < n_col for c in written):
         raise ValueError(f"col must name distinct columns in [0, {n_col})")
     F, desc = 0, None
     if matsubara is not None:
@@ -1061,7 +1129,7 @@ def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step,
         n_bin = dmap.n_bin
         if n_bin > capi.FDG_CHAIN_BIN_MAX:
             raise ValueError(f"the chain takes at most {capi.FDG_CHAIN_BIN_MAX} values of the discrete variable")
-        if not all(0 <= e < n_col for e in dmap.ext_col) or set(dmap.ext_col) & set(col):
+        if not all(0 <= e < n_col for e in dmap.ext_col) or set(dmap.ext_col) & set(written):
             raise ValueError(f"dmap.ext_col must name columns in [0, {n_col}) that col does not name")
         if len(col) >= capi.FDG_VEGAS_DIM_MAX:
             raise ValueError(f"a discrete variable leaves room for {capi.FDG_VEGAS_DIM_MAX - 1} continuous ones")
@@ -1082,9 +1150,19 @@ def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step,
         raise ValueError("one column per variable of the map")
     D, G = vmap.n_dim, vmap.n_grid
     DV = D + 1 if dmap is not None else D                   # the variables a move can name: bit D is the discrete one
+    pgroups = None
+    if polar is not None:
+        pgroups = _check_polar(polar, col, vmap, n_col)
+        if any(c is None for d, c in enumerate(col) if not any(v <= d < v + len(cs) for v, cs in pgroups)):
+            raise ValueError("only the variables of a polar group go without a column")
+        pbits = [((1 << len(cs)) - 1) << v for v, cs in pgroups]
+        if moves is None:
+            moves = chain_moves_polar(DV, pgroups)
     moves = chain_moves(DV) if moves is None else [int(m) for m in moves]
     if not moves or not all(0 <= m < (1 << DV) for m in moves):
         raise ValueError("moves holds masks over the variables of the map" + (" and the discrete variable" if dmap is not None else ""))
+    if polar is not None and any((m & bits) not in (0, bits) for m in moves for bits in pbits):
+        raise ValueError("a move redraws a polar group whole or not at all: the state does not hold (k, theta, phi)")
     fx = np.zeros(n_col) if fixed is None else np.asarray(fixed, dtype=np.float64)
     if fx.shape != (n_col,):
         raise ValueError(f"fixed must hold {n_col} column values")
@@ -1097,6 +1175,9 @@ def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step,
             raise ValueError(f"need 1 .. {capi.FDG_WEIGHT_GROUP_MAX} weight groups")
         if not all(0 <= int(d) < D for vs in wgroups.var_sets for d in vs):
             raise ValueError("groups.var_sets names variables of the map")
+        for var, cs in pgroups or ():
+            if any(0 < len(set(int(d) for d in vs) & set(range(var, var + len(cs)))) < len(cs) for vs in wgroups.var_sets):
+                raise ValueError("a polar group belongs to a weight group whole or not at all")
         if coef is not None and np.shape(coef) != (R,):
             raise ValueError(f"coef must hold n_root = {R} factors")
         if reweight is not None:
@@ -1110,9 +1191,11 @@ def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step,
             kw.update(n_sample=B, n_total=n_total, shard_start=shard_start)
         else:
             kw.update(n_sample=int(n_warm_sample))
+        if polar is not None:
+            kw["polar"] = polar
         if dmap is not None:
             vegas_integrate_binned(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, floor=floor, groups=wgroups, **kw)
-        elif wgroups is not None and tables is None:
+        elif (wgroups is not None or polar is not None) and tables is None:
             vegas_integrate_stratified(func_or_handle, tables, lo, hi, col, Stratification((1,) * D), kF, beta, lam, groups=wgroups, **kw)
         else:
             if wgroups is not None:
@@ -1137,7 +1220,14 @@ def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step,
         n_acc = torch.zeros(B, dtype=torch.int32, device=device)
 
         def step(mask, off, g, flags):
-            if dmap is None:
+            if polar is not None:
+                capi.chain_propose_device_polar(vmap.d_grid.data_ptr(), D, G, col, n_col, mask & all_mask, seed, off, x.data_ptr(), B,
+                                                fac.data_ptr(), xp.data_ptr(), B, facp.data_ptr(), bool((mask >> D) & 1),
+                                                0 if dmap is None else dmap.d_cdf.data_ptr(), n_bin,
+                                                0 if dmap is None or dmap.d_ext is None else dmap.d_ext.data_ptr(),
+                                                None if dmap is None else dmap.ext_col, 0 if dmap is None else bins.data_ptr(),
+                                                0 if dmap is None else binp.data_ptr(), pgroups, B, st)
+            elif dmap is None:
                 capi.chain_propose_device(vmap.d_grid.data_ptr(), D, G, col, n_col, mask, seed, off, x.data_ptr(), B, fac.data_ptr(),
                                           xp.data_ptr(), B, facp.data_ptr(), B, st)
             else:

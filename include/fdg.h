@@ -1376,6 +1376,44 @@ int fdg_mc_chain_step_device_binned(fdg_graph *g, const double *d_xp, int64_t xp
                                     const fdg_chain_groups *cg, uint32_t n_bin, const int32_t *d_binp, int32_t *d_bin, int64_t n_walker,
                                     void *stream);
 
+/* ---- Markov chain with spherical momentum variables --------------------------------------------------------------------------------------
+ * Every caller of the chain in the reference draws its loop momenta as MCIntegration.FermiK, a modulus and a direction over a ball
+ * (test/hubbard.jl:85, test/ver4.jl:77-92, 224-237, example/benchmark.jl:46).  This is "Spherical momentum variables" above in the
+ * chain's proposal.  MCIntegration is not part of the reference checkout: no counterpart in the reference.
+ *
+ * Unlike the direct sampler, which folds the polar measure into its one jacobian, the chain keeps the measure's factors PER VARIABLE
+ * in the rows of fac that it already carries, each row a function of its own variable alone, so that the step's left fold over a
+ * group's mask is the jacobian of the polar measure: no step entry, and nothing of the state's layout, changes.
+ *
+ * fdg_chain_propose_device_polar: fdg_chain_propose_device_discrete's arguments and results, plus the groups polar[0 .. n_polar) of
+ * fdg_vegas_sample_device_polar (HOST array).  d_cdf == NULL: no discrete variable; move_discrete, n_bin, d_ext, n_ext, ext_col, d_bin
+ * and d_binp are ignored, d_fac and d_facp have n_dim rows and n_dim = 64 is allowed.  A variable of no group behaves as in
+ * fdg_chain_propose_device, the discrete variable as in fdg_chain_propose_device_discrete.  For a group {var, dim, col[]} whose
+ * variables the mask names, with k, theta, phi the values drawn through the map for the variables var, var + 1, var + 2 (dim 2:
+ * k, phi), each by fdg_vegas_sample_device's statements on counter (sample_offset + b, d) -- the direct sampler's counters -- and
+ * f_d = G * wd_d, every line one rounded fp64 operation (no FMA), in this order:
+ *     (st, ct) = fdg_sincos(theta);   (sp, cp) = fdg_sincos(phi)
+ *   dim 3:  ks = k * st;   xp[col[0]] = ks * cp;   xp[col[1]] = ks * sp;   xp[col[2]] = k * ct
+ *           facp[var] = (f_k * k) * k;   facp[var + 1] = f_theta * st;   facp[var + 2] = f_phi
+ *   dim 2:  xp[col[0]] = k * cp;   xp[col[1]] = k * sp;   facp[var] = f_k * k;   facp[var + 1] = f_phi
+ * so a full proposal's xp is fdg_vegas_sample_device_polar's x bit for bit, and the product of the rows of facp its jac up to the
+ * order of the products.  st >= 0 on [0, fl(pi)], so no factor is negative; k = 0 gives the factor 0, hence a' = 0, which is finite
+ * and no poison.  A group whose variables the mask does not name is kept: its rows of fac are copied, and its columns with all the
+ * columns nobody redraws.  A move redraws a group whole or not at all: the state does not hold (k, theta, phi), which moving the
+ * modulus or the direction alone would need.  The col entry of a grouped variable is not read.
+ * With n_polar == 0 the results are bit for bit those of fdg_chain_propose_device (d_cdf == NULL) or of
+ * fdg_chain_propose_device_discrete.
+ * FDG_E_INVALID / FDG_E_UNSUPPORTED, in this order: everything fdg_chain_propose_device refuses; with d_cdf != NULL everything
+ * fdg_chain_propose_device_discrete refuses of the discrete variable's arguments; n_polar > FDG_VEGAS_POLAR_MAX (unsupported); a NULL
+ * polar with n_polar > 0; a dim that is not 2 or 3, a group that reaches past n_dim, two groups that share a variable; a group's
+ * column >= n_col, a column named twice among the col entries of the variables of no group, the groups' columns and ext_col; a mask
+ * that names some but not all variables of a group.  All before any device work. */
+int fdg_chain_propose_device_polar(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, uint32_t n_col, uint64_t mask,
+                                   uint64_t seed, uint64_t sample_offset, const double *d_x, int64_t x_col_stride, const double *d_fac,
+                                   double *d_xp, int64_t xp_col_stride, double *d_facp, int move_discrete, const double *d_cdf,
+                                   uint32_t n_bin, const double *d_ext, uint32_t n_ext, const uint32_t *ext_col, const int32_t *d_bin,
+                                   int32_t *d_binp, const fdg_vegas_polar *polar, uint32_t n_polar, int64_t n_walker, void *stream);
+
 /* Device workspace control: the interpreter keeps per-sample overflow slots in
  * an HBM panel owned by the handle; it is sized on first use for the number of
  * resident waves.  This releases it (and any loaded module). */
