@@ -108,7 +108,7 @@ class KernelInfo(C.Structure):
                 ("n_panel", C.c_uint32 * 3), ("n_lds", C.c_uint32 * 3), ("waves_per_cu", C.c_uint32 * 3),
                 ("has_acc", C.c_uint32), ("has_rm", C.c_uint32), ("has_coop", C.c_uint32), ("rm_bufs", C.c_uint32),
                 ("has_pool", C.c_uint32), ("pool_fetch", C.c_uint32), ("pool_valu", C.c_uint64),
-                ("has_rl", C.c_uint32), ("rl_reserved", C.c_uint32), ("rl_valu", C.c_uint64)]
+                ("has_rl", C.c_uint32), ("last_launch", C.c_uint32), ("rl_valu", C.c_uint64)]
 
 
 class LeafTables(C.Structure):
@@ -430,6 +430,9 @@ class GraphHandle:
             out[k] = [int(x) for x in getattr(ki, k)]
         for k in ("has_acc", "has_rm", "has_coop", "rm_bufs", "has_pool", "pool_fetch", "pool_valu", "has_rl", "rl_valu"):
             out[k] = int(getattr(ki, k))
+        # the last evaluator launch: its workgroups, and whether its waves claimed their tiles from a counter (FDG_ISA_TILE_CLAIM) or walked w, w + n, ...
+        out["last_grid"] = int(ki.last_launch) & 0x7FFFFFFF
+        out["tile_walk"] = "claimed" if int(ki.last_launch) >> 31 else "static"
         return out
 
     def emit_source(self, flags: int = 0) -> str:

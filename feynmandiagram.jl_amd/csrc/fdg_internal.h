@@ -101,6 +101,8 @@ struct fdg_launch_cfg {
   long mem_waves = -1;                     // >= 0: resident waves per CU of memory-bound graphs (0: rule off); -1: the library's rule
   long mem_oversub = 1;
   double mem_ratio = 2.5;
+  int tile_claim = -1;                     // memory-bound launches of the root-writing one-wave kernels: waves claim their next tiles from a counter (FDG_ISA_TILE_CLAIM):
+                                           // 0 never, 1 always, -1 the library's rule: launches of 256 rounds and more
   uint64_t sm_chunk_bytes = 1ull << 29;    // row-major input without an in-place variant: bytes of leaves transposed per chunk
   long long eval_chunk = 0, mc_chunk = 0;  // host-buffer / Monte-Carlo chunk sizes in samples (0: the library's)
 };
@@ -108,11 +110,12 @@ struct fdg_launch_cfg {
 // The kernels one code object of the optimizing back end may hold, and what the launch path knows of each.  A kernel's symbol is the code
 // object's base name ("fdg_isa_eval", "fdg_isa_mc") + the suffix below; vgpr, lds_bytes and threads are what the emitter assembled
 // (fdg_opt.h: IsaKernelRecord), mem_slots the program's panel slots; fn is resolved when the module is loaded.
-enum { FDG_K_EVAL = 0, FDG_K_NT, FDG_K_W2, FDG_K_ACC, FDG_K_ACC_NT, FDG_K_RM, FDG_K_RM_ACC, FDG_K_RL, FDG_K_RL_ACC, FDG_K_COOP, FDG_K_POOL, FDG_K_COUNT };
+enum { FDG_K_EVAL = 0, FDG_K_NT, FDG_K_W2, FDG_K_ACC, FDG_K_ACC_NT, FDG_K_RM, FDG_K_RM_ACC, FDG_K_RL, FDG_K_RL_ACC, FDG_K_COOP, FDG_K_POOL, FDG_K_EVAL_CL, FDG_K_NT_CL, FDG_K_COUNT };
 //   plain | streaming (non-temporal, line-aligned batches) | two samples per lane | fused accumulation | ... streaming | row-major (chunks staged in
-//   LDS) | ... accumulating | linear row-major (contiguous rows, LDS image) | ... accumulating | cooperative (a CU's waves on one tile) | pooled cooperative
+//   LDS) | ... accumulating | linear row-major (contiguous rows, LDS image) | ... accumulating | cooperative (a CU's waves on one tile) | pooled cooperative |
+//   plain, tiles claimed from a shared counter (FDG_ISA_TILE_CLAIM) | ... streaming
 static const char *const FDG_ISA_KERNEL[FDG_K_COUNT] = {"fdg_isa_eval", "fdg_isa_eval_nt", "fdg_isa_eval_w2", "fdg_isa_eval_acc", "fdg_isa_eval_acc_nt",
-    "fdg_isa_eval_rm", "fdg_isa_eval_rm_acc", "fdg_isa_eval_rl", "fdg_isa_eval_rl_acc", "fdg_isa_eval_coop", "fdg_isa_eval_pool"};
+    "fdg_isa_eval_rm", "fdg_isa_eval_rm_acc", "fdg_isa_eval_rl", "fdg_isa_eval_rl_acc", "fdg_isa_eval_coop", "fdg_isa_eval_pool", "fdg_isa_eval_cl", "fdg_isa_eval_nt_cl"};
 inline const char *fdg_isa_suffix(int k) { return FDG_ISA_KERNEL[k] + sizeof("fdg_isa_eval") - 1; }
 struct fdg_isa_kernel {
   bool present = false;
@@ -152,6 +155,8 @@ struct fdg_graph {
   uint64_t st_valu[3] = {0, 0, 0};
   uint32_t st_ld_leaf[3] = {0, 0, 0}, st_panel[3] = {0, 0, 0}, st_lds[3] = {0, 0, 0};
   const char *last_kernel = "";    // evaluator kernel of the last device call (guarded by mu)
+  uint32_t claim_run = 0;          // FDG_K_EVAL_CL / _NT_CL: log2 of the tiles per claim they were printed with (fdg_opt.h: isa_claim_run_log2)
+  uint32_t last_launch = 0;        // ... workgroups of the last launch of a kernel of the optimizing back end | FDG_LAUNCH_CLAIMED
   uint32_t rm_bufs = 0;            // FDG_K_RM / _RM_ACC: LDS staging buffers
   uint64_t rl_valu = 0;            // FDG_K_RL: fold steps per evaluation
   bool coop_enabled = false;       // FDG_K_COOP: the tuner's verdict (a variant that is present but measured slower stays off)

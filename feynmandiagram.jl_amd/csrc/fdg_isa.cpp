@@ -34,6 +34,13 @@
 #include "fdg_opt.h"
 
 namespace fdg {
+int isa_claim_run_log2() {
+  const char *e = fdg::knob("FDG_ISA_CLAIM_RUN");
+  const long tiles = e ? std::atol(e) : 4;
+  int r = 0;
+  while (r < 6 && (1l << (r + 1)) <= tiles) ++r;
+  return r;
+}
 namespace {
 
 constexpr int V_LANE8 = 1, V_LEAFOFF = 2, V_ROOTOFF = 3, V_TMP = 4, V_BASE = 6;
@@ -177,7 +184,8 @@ static HzInst hz_decode(const std::string &line) {
     if (hz_starts(op, "s_addc") || hz_starts(op, "s_subb") || hz_starts(op, "s_cselect")) {}   // SCC is not tracked (SALU only)
     return I;
   }
-  if (hz_starts(op, "global_load") || hz_starts(op, "global_store") || hz_starts(op, "buffer_") || hz_starts(op, "flat_")) {
+  // (global_atomic_*: only the returning form is printed -- operand 0 is the VGPR the old value lands in, like a load's)
+  if (hz_starts(op, "global_load") || hz_starts(op, "global_store") || hz_starts(op, "global_atomic") || hz_starts(op, "buffer_") || hz_starts(op, "flat_")) {
     I.vmem = true;
     I.store = op.find("store") != std::string::npos;
     if (op.find("_lds_") != std::string::npos) {      // LDS-direct: no VGPR destination, M0 is the LDS base
@@ -529,7 +537,7 @@ struct CoopSec { uint32_t wave, n_shared, priv_base_bytes, panel_wg_bytes, panel
 // tile's 64 rows are one block of 512 L bytes, streamed linearly into an LDS image by LDS-direct loads (1 KB per instruction, every cache
 // line of the matrix requested exactly once, non-temporal), and leaf i of lane = row r is read from image[r * 8 L + 8 i].
 static KernelMeta emit_kernel(Emit &E, const Lowered &p, const OptProgram &prog, const std::string &kname, int W, bool accumulate = false,
-                              uint32_t rm_bufs = 0, const CoopSec *cs = nullptr, bool rl = false) {
+                              uint32_t rm_bufs = 0, const CoopSec *cs = nullptr, bool rl = false, bool claim_tiles = false) {
   E.vm_issued = E.lg_issued = E.vm_done = E.lg_done = 0;
   E.pend.assign(std::max<uint32_t>(prog.n_reg_used, 1), {0, 0});
   const uint32_t SLOT = 512u * W;                 // bytes of one LDS / panel slot of a wave
@@ -611,6 +619,19 @@ static KernelMeta emit_kernel(Emit &E, const Lowered &p, const OptProgram &prog,
   int tile_rot = 0;
   if (dbg && std::strstr(dbg, "rot") && !cs && !tile_run && !tile_xcd) tile_rot = std::max(0, std::atoi(std::strstr(dbg, "rot") + 3));
   const int S_ROTB = S_POOL + 2 * (N_POOL - 1), S_ROTS = S_ROTB + 1;
+  // Claimed tiles (the `_cl` kernels, one more argument: a 32-bit counter the host zeroes in front of the launch).  A wave's first tile is its
+  // workgroup id; at the head of every tile lane 0 adds 1 to the counter (returning atomic), and at the back edge the value that came back,
+  // + nwg, is the next tile.  Nothing waits for another wave: a wave that loses a race gets a larger index, and the claim that returns
+  // >= ntiles ends it -- so the tiles being read at any moment are the most recent ones however far the waves' speeds differ, where the
+  // static walk (tile += nwg) lets the fast waves run ahead for the whole launch.  Every tile is claimed exactly once whatever
+  // order the workgroups start in.  The counter's address lives in the constant pool's last pair, which such a kernel leaves free.
+  const bool claim = claim_tiles && W == 1 && !cs && !accumulate && !rm_bufs && !rl && prog.mc_n_k == 0 && prog.mc_n_t == 0 && !tile_run && !tile_xcd && !tile_rot;
+  // One claim is good for a RUN of 2^claim_run consecutive tiles (isa_claim_run_log2: four): all claims of a launch go to one address and are
+  // served one after the other, about 12.6 ns each on MI355X -- a claim per tile is 1.56e6 of them in the headline launch, 19.7 ms where the whole
+  // launch takes 10.6 (profiles/log_tile_claim_ab_run1.txt); runs of 2 ... 8 tiles cost the static walk nothing (profiles/r04_log_tile_runs.txt).
+  const int claim_run = claim ? isa_claim_run_log2() : 0;
+  const int S_CLAIM = S_POOL + 2 * (N_POOL - 1);
+  uint64_t claim_seq = 0;
   E.vm_slack = (dbg && std::strstr(dbg, "noackwait") && !accumulate) ? p.R : 0;
   E.no_vm_wait = dbg && std::strstr(dbg, "novmwait");
   // ---- prologue ------------------------------------------------------------
@@ -626,6 +647,7 @@ static KernelMeta emit_kernel(Emit &E, const Lowered &p, const OptProgram &prog,
   const int tile_arg = mc ? 0x80 : 0x50;          // lts, rts follow the other arguments
   E.ins("s_load_dwordx2 " + S2(S_LTS) + ", s[0:1], " + hex32((uint32_t)tile_arg));
   if (!accumulate) E.ins("s_load_dwordx2 " + S2(S_RTS) + ", s[0:1], " + hex32((uint32_t)tile_arg + 8));
+  if (claim) E.ins("s_load_dwordx2 " + S2(S_CLAIM) + ", s[0:1], " + hex32((uint32_t)tile_arg + 16));      // the counter follows lts, rts
   if (mc) {
     E.ins("s_load_dwordx4 s[" + std::to_string(S_LEAF2) + ":" + std::to_string(S_LEAF2 + 3) + "], s[0:1], 0x50");
     E.ins("s_load_dwordx8 s[" + std::to_string(S_PARAM) + ":" + std::to_string(S_PARAM + 7) + "], s[0:1], 0x60");
@@ -778,7 +800,7 @@ static KernelMeta emit_kernel(Emit &E, const Lowered &p, const OptProgram &prog,
     std::vector<std::pair<int, uint64_t>> v;
     for (auto &kv : hist) v.push_back({kv.second, kv.first});
     std::sort(v.begin(), v.end(), [](const auto &x, const auto &y) { return x.first > y.first || (x.first == y.first && x.second < y.second); });
-    for (size_t i = 0; i < v.size() && i < (size_t)(mc ? N_POOL_MC : (has_macro ? N_POOL : 16)); ++i) pool.push_back(v[i].second);
+    for (size_t i = 0; i < v.size() && i < (size_t)(mc ? N_POOL_MC : (has_macro ? N_POOL - (claim ? 1 : 0) : 16)); ++i) pool.push_back(v[i].second);
   }
   for (size_t k = 0; k < pool.size(); ++k) {
     E.ins("s_mov_b32 " + S(S_POOL + 2 * (int)k) + ", " + hex32((uint32_t)pool[k]));
@@ -800,6 +822,7 @@ static KernelMeta emit_kernel(Emit &E, const Lowered &p, const OptProgram &prog,
     E.ins("s_add_u32 " + S(S_A) + ", " + S(S_A) + ", " + S(S_T));
     E.ins("s_min_u32 " + S(S_NTILES) + ", " + S(S_A) + ", " + S(S_NTILES));        // end of the range (the loop's bound from here on)
   }
+  else if (claim_run) E.ins("s_lshl_b32 " + S(S_TILE) + ", s2, " + std::to_string(claim_run));      // the first run: the workgroup id's
   else {
     E.ins("s_mov_b32 " + S(S_TILE) + ", s2");
     if (tile_rot) { E.ins("s_mov_b32 " + S(S_ROTB) + ", 0"); E.ins("s_mov_b32 " + S(S_ROTS) + ", s2"); }
@@ -827,7 +850,7 @@ static KernelMeta emit_kernel(Emit &E, const Lowered &p, const OptProgram &prog,
     std::vector<std::pair<uint64_t, uint32_t>> v;
     for (auto &kv : hist) v.push_back({kv.second, kv.first});
     std::sort(v.begin(), v.end(), [](const auto &x, const auto &y) { return x.first > y.first || (x.first == y.first && x.second < y.second); });
-    for (size_t i = 0; i < v.size() && pool.size() + i < (size_t)N_POOL; ++i) {
+    for (size_t i = 0; i < v.size() && pool.size() + i < (size_t)(N_POOL - (claim ? 1 : 0)); ++i) {
       const int r = S_POOL + 2 * (int)(pool.size() + i);
       panel_base[v[i].second] = r;
       E.ins("s_add_u32 " + S(r) + ", " + S(S_PANEL) + ", " + hex32(v[i].second * 8192u));
@@ -839,6 +862,20 @@ static KernelMeta emit_kernel(Emit &E, const Lowered &p, const OptProgram &prog,
   E.ins("s_endpgm");   // (the host never launches more waves than tiles)
   os << ".Ltile" << sfx << ":\n";
   if (cs && cs->slack) E.ins("s_mov_b32 " + S(S_DELTA + 7) + ", " + S(S_DELTA + 6));      // S_G0: the progress count at the start of this tile
+  const int v_claim = (int)(tmp0 + 2 * n_tmp_pairs);      // above everything the register allocator and the temporaries own (counted in next_vgpr)
+  if (claim) {
+    // the claim for the NEXT run goes out at the head of a run's first tile: a whole run's time to come back.  One lane; the tile's own exec
+    // mask is set right below
+    if (claim_run) {
+      E.ins("s_and_b32 " + S(S_X) + ", " + S(S_TILE) + ", " + std::to_string((1 << claim_run) - 1));
+      E.ins("s_cbranch_scc1 .Lheld" + sfx);
+    }
+    E.ins("s_mov_b64 exec, 1");
+    E.ins("v_mov_b32_e32 " + V(V_TMP) + ", 1");
+    E.ins("global_atomic_add " + V(v_claim) + ", " + V(V_LANE8) + ", " + V(V_TMP) + ", " + S2(S_CLAIM) + " sc0");      // (lane 0's offset, lane * 8, is 0)
+    if (claim_run) os << ".Lheld" << sfx << ":\n";
+    claim_seq = ++E.vm_issued;     // counted on both paths: a phantom older operation only makes later waits conservative
+  }
   E.ins("s_mov_b32 " + S(S_X + 1) + ", 0");
   E.ins("s_mov_b32 " + S(S_X) + ", " + S(S_TILE));
   E.ins("s_lshl_b64 " + S2(S_X) + ", " + S2(S_X) + ", " + std::to_string(TSH));                 // b0
@@ -1464,6 +1501,25 @@ static KernelMeta emit_kernel(Emit &E, const Lowered &p, const OptProgram &prog,
     E.ins("s_sub_u32 " + S(S_X) + ", " + S(S_NWG) + ", 1");
     E.ins("s_and_b32 " + S(S_ROTS) + ", " + S(S_ROTS) + ", " + S(S_X));
     E.ins("s_add_u32 " + S(S_TILE) + ", " + S(S_ROTB) + ", " + S(S_ROTS));
+  } else if (claim) {
+    if (claim_run) {      // inside a run: the next tile
+      E.ins("s_add_u32 " + S(S_TILE) + ", " + S(S_TILE) + ", 1");
+      E.ins("s_and_b32 " + S(S_X) + ", " + S(S_TILE) + ", " + std::to_string((1 << claim_run) - 1));
+      E.ins("s_cbranch_scc1 .Lrun" + sfx);
+    }
+    // (the run's first memory operation: every wait for a leaf has covered it already.  Not through wait_vm: the timing experiments that
+    //  drop or loosen waits must not touch this one -- the loop's bound depends on the value)
+    if (claim_seq > E.vm_done) {
+      const uint64_t n = std::min<uint64_t>(E.vm_issued - claim_seq, 63);
+      E.ins("s_waitcnt vmcnt(" + std::to_string(n) + ")");
+      E.vm_done = std::max(std::max(E.vm_done, E.vm_issued - n), claim_seq);
+    }
+    E.ins("v_readfirstlane_b32 " + S(S_TILE) + ", " + V(v_claim));      // lane 0 is active in every tile, the ragged last one included
+    E.ins("s_add_u32 " + S(S_TILE) + ", " + S(S_TILE) + ", " + S(S_NWG));
+    if (claim_run) {
+      E.ins("s_lshl_b32 " + S(S_TILE) + ", " + S(S_TILE) + ", " + std::to_string(claim_run));      // the claimed run's first tile
+      os << ".Lrun" << sfx << ":\n";
+    }
   } else {
     E.ins("s_add_u32 " + S(S_TILE) + ", " + S(S_TILE) + ", " + S(S_NWG));
   }
@@ -1520,16 +1576,16 @@ static KernelMeta emit_kernel(Emit &E, const Lowered &p, const OptProgram &prog,
   E.ins("s_endpgm");
 
   // ---- kernel descriptor -------------------------------------------------------
-  const uint32_t next_vgpr = std::max<uint32_t>(V_BASE + RW * std::max<uint32_t>(prog.n_reg_used, 1) + 2 * acc_pairs_v + 2 * n_tmp_pairs + (rm_bufs ? 10 : 0) + (cs ? (cs->slack ? 7 : 4) : 0) + (rl ? 2 : 0), 8);
+  const uint32_t next_vgpr = std::max<uint32_t>(V_BASE + RW * std::max<uint32_t>(prog.n_reg_used, 1) + 2 * acc_pairs_v + 2 * n_tmp_pairs + (rm_bufs ? 10 : 0) + (cs ? (cs->slack ? 7 : 4) : 0) + (rl ? 2 : 0) + (claim ? 1 : 0), 8);
   const uint32_t accum = (next_vgpr + 3) & ~3u;
   const uint32_t n_agpr = RW * prog.n_acc_used + (aa ? 2 * p.R : 0);
   if (cs) return KernelMeta{kname, lds_bytes, accum, n_agpr, 12, (mc || has_macro) ? S_END : S_POOL + 2 * 16};
   os << "\t.section\t.rodata,\"a\",@progbits\n\t.p2align\t6, 0x0\n\t.amdhsa_kernel " << kname << "\n";
   os << "\t\t.amdhsa_group_segment_fixed_size " << lds_bytes << "\n";
-  os << "\t\t.amdhsa_private_segment_fixed_size 0\n\t\t.amdhsa_kernarg_size " << (mc ? 144 : 96) << "\n\t\t.amdhsa_user_sgpr_count 2\n";
+  os << "\t\t.amdhsa_private_segment_fixed_size 0\n\t\t.amdhsa_kernarg_size " << (mc ? 144 : (claim ? 104 : 96)) << "\n\t\t.amdhsa_user_sgpr_count 2\n";
   os << "\t\t.amdhsa_user_sgpr_kernarg_segment_ptr 1\n\t\t.amdhsa_system_sgpr_workgroup_id_x 1\n";
   os << "\t\t.amdhsa_system_vgpr_workitem_id 0\n";
-  const int n_sgpr = (mc || has_macro) ? S_END : S_POOL + 2 * 16;   // programs without leaf formulas: the 16-entry pool ends the map
+  const int n_sgpr = (mc || has_macro || claim) ? S_END : S_POOL + 2 * 16;   // programs without leaf formulas: the 16-entry pool ends the map
   os << "\t\t.amdhsa_next_free_vgpr " << (accum + n_agpr) << "\n\t\t.amdhsa_next_free_sgpr " << n_sgpr << "\n";
   os << "\t\t.amdhsa_accum_offset " << accum << "\n\t\t.amdhsa_reserve_vcc 1\n";
   os << "\t\t.amdhsa_float_round_mode_32 0\n\t\t.amdhsa_float_round_mode_16_64 0\n";
@@ -1537,7 +1593,7 @@ static KernelMeta emit_kernel(Emit &E, const Lowered &p, const OptProgram &prog,
   os << "\t\t.amdhsa_dx10_clamp 1\n\t\t.amdhsa_ieee_mode 1\n";
   os << "\t.end_amdhsa_kernel\n";
   (void)p;
-  return KernelMeta{kname, lds_bytes, accum, n_agpr, mc ? 18 : 12, n_sgpr};
+  return KernelMeta{kname, lds_bytes, accum, n_agpr, mc ? 18 : (claim ? 13 : 12), n_sgpr};
 }
 
 }  // namespace
@@ -1647,6 +1703,10 @@ std::string isa_hazard_table() {
   return os.str();
 }
 
+static bool isa_has_claimed(const Lowered &p, const OptProgram &prog) {
+  return prog.mc_n_k == 0 && prog.mc_n_t == 0 && prog.ops.size() <= 60000 && (double)prog.n_valu < 10.0 * 8.0 * (double)(p.L + p.R);
+}
+
 // One code object: the kernels of the programs in V (fdg_opt.h: IsaPrograms); `records`, when given, gets what was assembled for each.
 std::string emit_isa(const Lowered &p, const IsaPrograms &V, std::vector<IsaKernelRecord> *records) {
   const OptProgram &prog = *V.main, *prog2 = V.w2_prog(), *prog_acc = V.acc_prog(), *prog_rm = V.rm_prog(), *prog_rm_acc = V.rm_acc_prog(), *prog_rl = V.rl_prog(),
@@ -1690,6 +1750,17 @@ std::string emit_isa(const Lowered &p, const IsaPrograms &V, std::vector<IsaKern
   if (prog_rl_acc) ks.push_back(emit_kernel(E, p, *prog_rl_acc, kname + "_rl_acc", 1, true, 0, nullptr, true));
   if (coop) { ks.push_back(emit_coop(E, p, *coop, kname + "_coop")); ks.back().wg = 64 * coop->n_wave; }
   if (pool) { ks.push_back(emit_coop(E, p, *pool, kname + "_pool")); ks.back().wg = 64 * pool->n_wave; }
+  // The root-writing one-wave kernels once more with claimed tiles (see `claim` in emit_kernel), for the graphs a launch plan can find bound by
+  // memory (fdg_runtime.hip: IsaRun::shape; four times its default ratio leaves FDG_ISA_MEM_RATIO room).  Behind every other kernel: the text
+  // in front of them is what it is without them.
+  if (isa_has_claimed(p, prog)) {
+    ks.push_back(emit_kernel(E, p, prog, kname + "_cl", 1, false, 0, nullptr, false, true));
+    if (!fdg::knob("FDG_ISA_NO_STREAMING")) {
+      E.streaming = true;
+      ks.push_back(emit_kernel(E, p, prog, kname + "_nt_cl", 1, false, 0, nullptr, false, true));
+      E.streaming = false;
+    }
+  }
   std::ostringstream &os = E.os;
   os << "\t.text\n\t.amdgpu_metadata\n---\namdhsa.kernels:\n";
   const char *kinds[18] = {"global_buffer", "by_value", "by_value", "global_buffer", "by_value", "by_value",
@@ -1698,7 +1769,7 @@ std::string emit_isa(const Lowered &p, const IsaPrograms &V, std::vector<IsaKern
   for (const KernelMeta &k : ks) {
     os << "  - .agpr_count: " << k.n_agpr << "\n    .args:\n";
     for (int i = 0; i < k.n_args; ++i) {
-      const char *kind = (k.n_args == 12 && i >= 10) ? "by_value" : kinds[i];      // (lts, rts end every argument list)
+      const char *kind = (k.n_args <= 13 && i >= 10) ? (i == 12 ? "global_buffer" : "by_value") : kinds[i];      // (lts, rts end every argument list; the claimed kernels' counter follows them)
       os << "      - .offset: " << i * 8 << "\n        .size: 8\n        .value_kind: " << kind << "\n";
       if (std::strcmp(kind, "global_buffer") == 0) os << "        .address_space: global\n";
     }

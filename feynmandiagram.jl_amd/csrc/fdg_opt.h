@@ -199,6 +199,9 @@ struct IsaPrograms {
 // What the emitter assembled for one kernel, as its kernel descriptor states it: the launch plan sizes grids and occupancy from these
 struct IsaKernelRecord { std::string name; uint32_t vgpr = 0 /* accum offset + AGPRs */, lds_bytes = 0, threads = 64; };
 std::string emit_isa(const Lowered &p, const IsaPrograms &V, std::vector<IsaKernelRecord> *records = nullptr);
+// log2 of the consecutive tiles one claim of the `_cl` kernels is good for, under the options in scope (FDG_ISA_CLAIM_RUN = 1, 2, 4, ... 64 tiles;
+// default 4): the emitter prints it into the kernels, the launch plan sizes their grid by it (at most one workgroup per run)
+int isa_claim_run_log2();
 
 void rm_plan_stats(const Lowered &p, const OptProgram &prog, uint32_t bufs, uint64_t &fetches, uint64_t &gathers);
 // gfx950 wait-state table of the emitter (fdg_isa.cpp): check of a finished listing, and the table as text

@@ -643,6 +643,7 @@ void parse_launch_cfg(fdg_graph *g) {
   if (const char *e = get("FDG_ISA_MEM_WAVES")) c.mem_waves = std::max(0l, std::atol(e));
   if (const char *e = get("FDG_ISA_MEM_OVERSUB")) c.mem_oversub = std::max(1l, std::atol(e));
   if (const char *e = get("FDG_ISA_MEM_RATIO")) c.mem_ratio = std::atof(e);
+  if (const char *e = get("FDG_ISA_TILE_CLAIM")) c.tile_claim = e[0] != '0' ? 1 : 0;
   if (const char *e = get("FDG_SM_CHUNK_MB")) c.sm_chunk_bytes = (uint64_t)std::max(1, std::atoi(e)) << 20;
   if (const char *e = get("FDG_EVAL_CHUNK")) c.eval_chunk = std::atoll(e);
   if (const char *e = get("FDG_MC_CHUNK")) c.mc_chunk = std::atoll(e);
@@ -817,7 +818,8 @@ struct IsaRun {
   const bool tiled;
   long ntiles = 0, grid = 0, grid2 = 0, grid3 = 0, grid4 = 0, grid5 = 0;
   size_t panel_all = 0;
-  bool pool_ok = false, fused_acc = false, wide_ss = false, named = false;
+  bool pool_ok = false, fused_acc = false, wide_ss = false, named = false, claim = false;
+  size_t claim_off = 0;             // the tile counter of the claimed kernels: byte offset in the workspace
   double *roots = nullptr;          // where mode 1 without fused accumulation puts the roots: the column-major scratch (roots[k * a_rk + b])
   long a_rs = 0, a_rk = 0;
 
@@ -842,12 +844,17 @@ struct IsaRun {
   // (one per SIMD) keep 4 x L x 512 bytes in flight per CU -- enough for the latency-bandwidth product -- and the memory system sees a
   // quarter of the concurrent streams (round 4, profiles/r04_log_waves.txt: headline +3-5 %, the 2-loop graph +6-15 %); the graphs at or
   // above the ridge want every wave they can get.  Options FDG_ISA_MEM_WAVES / FDG_ISA_MEM_OVERSUB / FDG_ISA_MEM_RATIO override (0 waves = off).
+  long mem_waves_of(bool accumulating) const { return g->cfg.mem_waves >= 0 ? g->cfg.mem_waves : (p.L >= 24 ? 4 : (accumulating ? 8 : 5)); }
+  bool mem_bound(uint64_t valu, uint64_t bytes, const fdg_isa_kernel &k, bool accumulating) const {
+    return mem_waves_of(accumulating) > 0 && g->cfg.waves_per_cu <= 0 && g->cfg.oversub <= 0 && bytes && (double)valu < g->cfg.mem_ratio * (double)bytes &&
+           (long)waves_per_cu(k) > mem_waves_of(accumulating);
+  }
   long shape(uint64_t valu, uint64_t bytes, const fdg_isa_kernel &k, size_t bytes_per_wg, bool accumulating = false) const {
     const long full = (long)waves_per_cu(k);
     // (a wave of a tiny graph keeps little in flight; without root stores more of them help: the 2-loop graph accumulates at 0.84 instead of
     //  0.73, profiles/r04_log_tiny_acc_waves.txt)
-    const long mem_waves = g->cfg.mem_waves >= 0 ? g->cfg.mem_waves : (p.L >= 24 ? 4 : (accumulating ? 8 : 5));
-    if (mem_waves > 0 && g->cfg.waves_per_cu <= 0 && g->cfg.oversub <= 0 && bytes && (double)valu < g->cfg.mem_ratio * (double)bytes && full > mem_waves) {
+    const long mem_waves = mem_waves_of(accumulating);
+    if (mem_bound(valu, bytes, k, accumulating)) {
       long f = g->cfg.mem_oversub;
       while (f > 1 && ntiles < (long)g->n_cu * mem_waves * f * 4) f >>= 1;
       return (long)g->n_cu * mem_waves * f;
@@ -880,7 +887,13 @@ struct IsaRun {
     grid5 = rma.present ? (long)g->n_cu * waves_per_cu(rma) : 0;
     const size_t panel5 = (size_t)std::max<uint32_t>(rma.mem_slots, 1) * 512u * (size_t)grid5;
     panel_all = (std::max(std::max(panel, panel3), std::max(panel4, panel5)) + 4095) & ~(size_t)4095;
-    int rc = ensure_ws(g, panel_all + (size_t)std::max(grid3, grid5) * R * 512u + 4096);
+    // Claimed tiles (FDG_ISA_TILE_CLAIM; fdg_isa.cpp: `claim`): where the plan above took its memory-bound branch the root-writing one-wave
+    // kernels are launched in the variant whose waves take their next tile from a counter.  The counter lives behind everything else in this
+    // stream's workspace (one workspace per caller stream: two streams on one handle never share it) and is zeroed on the launch stream in
+    // front of every launch -- a memset node like any other under stream capture, nothing allocated, nothing waited for.
+    claim = g->cfg.tile_claim != 0 && K(FDG_K_EVAL_CL).present && mem_bound(g->st_valu[0], 8ull * (p.L + R), ev, false);
+    claim_off = panel_all + (size_t)std::max(grid3, grid5) * R * 512u + 4096;
+    int rc = ensure_ws(g, claim_off + 256);
     if (rc) return rc;
     roots = a.d_root; a_rs = (long)a.rs; a_rk = (long)a.rk;
     if (a.mode == 1 && !fused_acc) {
@@ -898,8 +911,11 @@ struct IsaRun {
   // weights, the tile strides of leaves and roots), the workgroup size it was assembled for
   int launch(int k, const double *lf, long lss, long lls, double *rt, long rrs, long rrk, long n, long nwg, const double *wt, long tls, long trs) {
     void *a_wsp = g->d_ws;
-    void *args[] = {(void *)&lf, &lss, &lls, (void *)&rt, &rrs, &rrk, &a_wsp, &n, &nwg, (void *)&wt, &tls, &trs};
+    void *a_cnt = (char *)g->d_ws + claim_off;      // (read by the claimed kernels only: their thirteenth argument)
+    void *args[] = {(void *)&lf, &lss, &lls, (void *)&rt, &rrs, &rrk, &a_wsp, &n, &nwg, (void *)&wt, &tls, &trs, &a_cnt};
+    if (k == FDG_K_EVAL_CL || k == FDG_K_NT_CL) HIP_TRY(hipMemsetAsync(a_cnt, 0, 4, a.st));
     HIP_TRY(hipModuleLaunchKernel((hipFunction_t)K(k).fn, (unsigned)nwg, 1, 1, K(k).threads, 1, 1, 0, a.st, args, nullptr));
+    g->last_launch = (uint32_t)nwg | ((k == FDG_K_EVAL_CL || k == FDG_K_NT_CL) ? FDG_LAUNCH_CLAIMED : 0u);
     return FDG_OK;
   }
   // an accumulating kernel leaves per-lane partial sums of its workgroups at `part`; fdg_reduce_lane_partials adds them to acc
@@ -932,9 +948,15 @@ struct IsaRun {
       const long n1 = n - done;
       if (!tls) tls = 64 * lss;
       if (!trs) trs = 64 * rrs;
-      const int k = K(FDG_K_NT).fn && line_aligned(lf1, lss, lls) && line_aligned(rt1, rrs, rrk) && ((tls | trs) & 15) == 0 ? FDG_K_NT : FDG_K_EVAL;
-      if (!named && done == 0) g->last_kernel = FDG_ISA_KERNEL[k];
-      return launch(k, lf1, lss, lls, rt1, rrs, rrk, n1, std::min<long>((n1 + 63) / 64, grid), nullptr, tls, trs);
+      int k = K(FDG_K_NT).fn && line_aligned(lf1, lss, lls) && line_aligned(rt1, rrs, rrk) && ((tls | trs) & 15) == 0 ? FDG_K_NT : FDG_K_EVAL;
+      if (!named && done == 0) g->last_kernel = FDG_ISA_KERNEL[k];      // (the variant's name whichever walk: fdg_kernel_info::last_launch tells the walk)
+      long run = 1;      // tiles a workgroup starts with: at most one workgroup per run of the claimed kernels
+      // (a short launch has no time to drift apart, and a run is a coarser unit to end on than a tile: the rule claims from 256 rounds on, where a
+      //  run is at most 1/64 of a wave's work.  Claimed at 49 rounds, the 2 GB windows fdg_batch_alloc_pair times ran 0.80 instead of 0.86 -- 12.2
+      //  runs per wave take the time of 13 -- and the allocator matched 22-28 windows of 32 instead of all; FDG_ISA_TILE_CLAIM=1
+      //  claims at every size)
+      if (claim && (g->cfg.tile_claim > 0 || (n1 + 63) / 64 >= 256 * grid) && K(k == FDG_K_NT ? FDG_K_NT_CL : FDG_K_EVAL_CL).fn) { k = k == FDG_K_NT ? FDG_K_NT_CL : FDG_K_EVAL_CL; run = 1l << g->claim_run; }
+      return launch(k, lf1, lss, lls, rt1, rrs, rrk, n1, std::min<long>(((n1 + 63) / 64 + run - 1) / run, grid), nullptr, tls, trs);
     }
     return FDG_OK;
   }
@@ -1494,7 +1516,7 @@ int fdg_graph_kernel_info(fdg_graph *g, fdg_kernel_info *o) {
   for (int i = 0; i < 3; ++i) if (g->kern[slot[i]].present) o->waves_per_cu[i] = isa_waves_per_cu(g->kern[slot[i]].vgpr, g->kern[slot[i]].lds_bytes);
   o->has_acc = g->kern[FDG_K_ACC].present; o->has_rm = g->kern[FDG_K_RM].present; o->has_coop = g->kern[FDG_K_COOP].present && g->coop_enabled; o->rm_bufs = g->rm_bufs;
   o->has_pool = g->kern[FDG_K_POOL].present; o->pool_fetch = g->pool_fetch; o->pool_valu = g->pool_valu;
-  o->has_rl = g->kern[FDG_K_RL].present; o->rl_reserved = 0; o->rl_valu = g->rl_valu;
+  o->has_rl = g->kern[FDG_K_RL].present; o->last_launch = g->last_launch; o->rl_valu = g->rl_valu;
   return FDG_OK;
 }
 
@@ -1703,7 +1725,7 @@ static int assemble_isa(const fdg_graph *g, const fdg::IsaPrograms &V, const std
 
 // the kernel table of a code object: present, registers, LDS and workgroup size from the emitter's records; panel slots from the programs
 static void fill_isa_kernels(fdg_isa_kernel *kern, const fdg::IsaPrograms &V, const std::vector<fdg::IsaKernelRecord> &records) {
-  const fdg::OptProgram *prog[FDG_K_COUNT] = {V.main, V.main, V.w2_prog(), V.acc_prog(), V.acc_prog(), V.rm_prog(), V.rm_acc_prog(), V.rl_prog(), V.rl_acc_prog(), nullptr, nullptr};
+  const fdg::OptProgram *prog[FDG_K_COUNT] = {V.main, V.main, V.w2_prog(), V.acc_prog(), V.acc_prog(), V.rm_prog(), V.rm_acc_prog(), V.rl_prog(), V.rl_acc_prog(), nullptr, nullptr, V.main, V.main};
   for (int k = 0; k < FDG_K_COUNT; ++k) {
     kern[k] = fdg_isa_kernel();
     for (const fdg::IsaKernelRecord &r : records) {
@@ -1733,6 +1755,7 @@ static void install_isa(fdg_graph *g, const fdg::IsaPrograms &V, std::vector<cha
     g->pool_valu = 0;
     for (uint32_t w = 0; w < V.pool.n_wave; ++w) g->pool_valu += V.pool.wave[w].n_valu;
   }
+  g->claim_run = (uint32_t)fdg::isa_claim_run_log2();
   g->coop_enabled = K[FDG_K_COOP].present;
   if (K[FDG_K_COOP].present) g->coop_panel_wg = panel_bytes_per_wg(V.coop);
   g->code_object.swap(co);

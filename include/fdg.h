@@ -157,8 +157,13 @@ int fdg_graph_set_association(fdg_graph *g, int assoc);
  * fdg_graph_set_option changes one (value NULL: removes it) -- the same names, plus the variant selectors and tuning knobs the tests and dev
  * tools use (FDG_ISA_W2, FDG_ISA_COOP, FDG_COOP_WAVES, FDG_ISA_NO_FUSED_ACC, FDG_ROOT_SCRATCH_MB, ...).  Options that shape
  * a kernel must be set before the fdg_graph_specialize* call that builds it; options of the launch path (FDG_ISA_NO_*, FDG_*_CHUNK*,
- * FDG_ROOT_SCRATCH_*, FDG_ISA_WAVES_PER_CU, FDG_ISA_OVERSUB, FDG_ISA_MEM_*) take effect with the next call: they are parsed into the
- * handle here, and between an evaluation entry point and hipModuleLaunchKernel nothing is looked up by name.  Thread-safe against
+ * FDG_ROOT_SCRATCH_*, FDG_ISA_WAVES_PER_CU, FDG_ISA_OVERSUB, FDG_ISA_MEM_*, FDG_ISA_TILE_CLAIM) take effect with the next call: they are
+ * parsed into the handle here, and between an evaluation entry point and hipModuleLaunchKernel nothing is looked up by name.
+ * FDG_ISA_TILE_CLAIM = "1" / "0": launches of the root-writing one-wave kernels that the plan finds bound by memory always / never use
+ * the twin whose waves claim their next run of tiles from a counter in the stream's workspace (fdg_isa_eval_cl / fdg_isa_eval_nt_cl: the
+ * same bits, the waves stay together however long the launch) instead of walking tiles w, w + n, ...; unset, launches of 256 rounds and
+ * more do.  fdg_kernel_info::last_launch tells which walk a call used.  (FDG_ISA_CLAIM_RUN, at specialisation: tiles per claim, 4.)
+ * Thread-safe against
  * concurrent launches of the same handle (taken under the handle's mutex).  Names must start with "FDG_".  fdg_graph_get_option returns
  * the value (owned by the handle, valid until the option changes) or NULL.  No counterpart in the reference. */
 int fdg_graph_set_option(fdg_graph *g, const char *name, const char *value);
@@ -173,6 +178,7 @@ const char *fdg_get_default_option(const char *name);   /* valid until the calli
  * guessing on the host side which variant the library picked.  Counts are per sample (one lane); slot 0 = the evaluator
  * (fdg_isa_eval[_nt]), 1 = fused accumulation (fdg_isa_eval_acc[_nt]), 2 = the row-major variant (fdg_isa_eval_rm).
  * All zero for handles that are not specialised with FDG_SPEC_ISA.  No counterpart in the reference. */
+#define FDG_LAUNCH_CLAIMED 0x80000000u
 typedef struct fdg_kernel_info {
   char last_kernel[48];       /* name of the evaluator kernel the last device call on this handle launched ("" = none yet) */
   uint64_t n_valu[3];         /* vector-ALU fold steps executed per evaluation (after value numbering / recomputation) */
@@ -185,8 +191,10 @@ typedef struct fdg_kernel_info {
   uint32_t pool_fetch;        /* ... leaf fetches from memory per evaluation (>= the live leaves) */
   uint64_t pool_valu;         /* ... fold steps executed per evaluation, all waves together */
   uint32_t has_rl;            /* the linear row-major variant (fdg_isa_eval_rl) is installed: contiguous rows, full tiles */
-  uint32_t rl_reserved;
-  uint64_t rl_valu;           /* ... fold steps it executes per evaluation */
+  uint32_t last_launch;       /* bits 0-30: workgroups of the last launch of an evaluator kernel of the optimizing back end (0 = none yet);
+                               * bit 31 (FDG_LAUNCH_CLAIMED): its waves claimed their tiles from a counter (FDG_ISA_TILE_CLAIM) -- the kernel
+                               * launched was the `_cl` twin of the variant last_kernel names */
+  uint64_t rl_valu;          /* ... fold steps it executes per evaluation */
 } fdg_kernel_info;
 int fdg_graph_kernel_info(fdg_graph *g, fdg_kernel_info *info);
 
