@@ -842,15 +842,30 @@ def fill_uniform_device_tiled(d_leaf: int, B: int, L: int, ss: int, ls: int, lts
     check(lib().fdg_fill_uniform_device_tiled(d_leaf, B, L, ss, ls, lts, seed, sample_offset, stream))
 
 
+def _col_arg(col, n_dim: int, none_ok: bool = False):
+    """The ``col`` argument of the samplers and proposals as a uint32 array, or None.  ``none_ok``: None entries stand for 0 (the
+    polar wrappers: the entry of a grouped variable is not read)."""
+    if col is None:
+        return None
+    c = np.ascontiguousarray([0 if v is None else v for v in col] if none_ok else col, dtype=np.uint32)
+    if c.shape != (n_dim,):
+        raise ValueError("col must name one column per variable")
+    return c
+
+
+def _ext_col_arg(ext_col) -> np.ndarray:
+    """The ``ext_col`` argument of the discrete variable's table as a uint32 array (None: empty)."""
+    e = np.ascontiguousarray([] if ext_col is None else ext_col, dtype=np.uint32)
+    if e.ndim != 1:
+        raise ValueError("ext_col must be a sequence of column numbers")
+    return e
+
+
 def vegas_sample_device(d_grid: int, n_dim: int, n_grid: int, col, seed: int, sample_offset: int, d_x: int, xs: int, xc: int, d_jac: int,
                         d_cell: int, B: int, stream: int = 0):
     """fdg_vegas_sample_device: ``x[b * xs + col[d] * xc]`` drawn through the map ``d_grid`` (device, ``[n_dim, n_grid + 1]`` edges),
     ``jac[b]`` its weight, ``cell[d * B + b]`` when ``d_cell`` is not 0.  ``col``: host sequence of ``n_dim`` column numbers or None."""
-    c = None
-    if col is not None:
-        c = np.ascontiguousarray(col, dtype=np.uint32)
-        if c.shape != (n_dim,):
-            raise ValueError("col must name one column per variable")
+    c = _col_arg(col, n_dim)
     check(lib().fdg_vegas_sample_device(d_grid or None, n_dim, n_grid, None if c is None else c.ctypes.data, seed, sample_offset,
                                         d_x or None, xs, xc, d_jac or None, d_cell or None, B, stream))
 
@@ -859,11 +874,7 @@ def chain_propose_device(d_grid: int, n_dim: int, n_grid: int, col, n_col: int, 
                          d_fac: int, d_xp: int, xpc: int, d_facp: int, B: int, stream: int = 0):
     """fdg_chain_propose_device: the proposal ``xp [n_col, B]`` / ``facp [n_dim, B]`` of every walker -- the variables of ``mask`` redrawn
     through the map for counter ``(sample_offset + b, d)``, everything else copied from ``x`` / ``fac``."""
-    c = None
-    if col is not None:
-        c = np.ascontiguousarray(col, dtype=np.uint32)
-        if c.shape != (n_dim,):
-            raise ValueError("col must name one column per variable")
+    c = _col_arg(col, n_dim)
     check(lib().fdg_chain_propose_device(d_grid or None, n_dim, n_grid, None if c is None else c.ctypes.data, n_col, mask, seed, sample_offset,
                                          d_x or None, xc, d_fac or None, d_xp or None, xpc, d_facp or None, B, stream))
 
@@ -874,14 +885,8 @@ def chain_propose_device_discrete(d_grid: int, n_dim: int, n_grid: int, col, n_c
     """fdg_chain_propose_device_discrete: :func:`chain_propose_device` and, with ``move_discrete``, the discrete variable redrawn from
     ``d_cdf [n_bin + 1]`` for counter ``(sample_offset + b, n_dim)``: ``binp [B]`` (int32) its value, ``facp[n_dim]`` the factor
     ``1 / p_j``, the columns ``ext_col`` (a host sequence) of ``xp`` row ``j`` of ``d_ext [n_bin, len(ext_col)]``; otherwise copied."""
-    c = None
-    if col is not None:
-        c = np.ascontiguousarray(col, dtype=np.uint32)
-        if c.shape != (n_dim,):
-            raise ValueError("col must name one column per variable")
-    ec = np.ascontiguousarray(ext_col if ext_col is not None else [], dtype=np.uint32)
-    if ec.ndim != 1:
-        raise ValueError("ext_col must be a sequence of columns")
+    c = _col_arg(col, n_dim)
+    ec = _ext_col_arg(ext_col)
     check(lib().fdg_chain_propose_device_discrete(d_grid or None, n_dim, n_grid, None if c is None else c.ctypes.data, n_col, mask, seed,
                                                   sample_offset, d_x or None, xc, d_fac or None, d_xp or None, xpc, d_facp or None,
                                                   1 if move_discrete else 0, d_cdf or None, n_bin, d_ext or None, ec.shape[0],
@@ -896,14 +901,8 @@ def chain_propose_device_polar(d_grid: int, n_dim: int, n_grid: int, col, n_col:
     direction.  ``polar``: a sequence of ``(var, cols)`` as :func:`vegas_sample_device_polar` takes it; a group is redrawn whole (every
     one of its bits in ``mask``) or kept, and the factors of the polar measure go to the group's own rows of ``facp``.  The ``col``
     entry of a grouped variable is not read (None stands for 0 there)."""
-    c = None
-    if col is not None:
-        c = np.ascontiguousarray([0 if v is None else v for v in col], dtype=np.uint32)
-        if c.shape != (n_dim,):
-            raise ValueError("col must name one column per variable")
-    ec = np.ascontiguousarray(ext_col if ext_col is not None else [], dtype=np.uint32)
-    if ec.ndim != 1:
-        raise ValueError("ext_col must be a sequence of columns")
+    c = _col_arg(col, n_dim, none_ok=True)
+    ec = _ext_col_arg(ext_col)
     arr, n_polar = _polar_array(polar)
     check(lib().fdg_chain_propose_device_polar(d_grid or None, n_dim, n_grid, None if c is None else c.ctypes.data, n_col, mask, seed,
                                                sample_offset, d_x or None, xc, d_fac or None, d_xp or None, xpc, d_facp or None,
@@ -1366,11 +1365,7 @@ def vegas_sample_device_strat(d_grid: int, n_dim: int, n_grid: int, col, strat, 
     """fdg_vegas_sample_device_strat: :func:`vegas_sample_device` inside the strata of the sample's hypercube.  ``strat``: host sequence
     of ``n_dim`` counts; ``d_start``: device int64 ``[H + 1]`` prefix sums of the samples per hypercube (global indices);
     ``d_cube[b]`` (int32) receives the hypercube, and ``jac`` carries ``n_total / (H n_h)``."""
-    c = None
-    if col is not None:
-        c = np.ascontiguousarray(col, dtype=np.uint32)
-        if c.shape != (n_dim,):
-            raise ValueError("col must name one column per variable")
+    c = _col_arg(col, n_dim)
     sv = _strat_array(strat, n_dim)
     check(lib().fdg_vegas_sample_device_strat(d_grid or None, n_dim, n_grid, None if c is None else c.ctypes.data, sv.ctypes.data,
                                               d_start or None, seed, sample_offset, d_x or None, xs, xc, d_jac or None, d_cube or None,
@@ -1531,11 +1526,7 @@ def vegas_sample_device_strat_grouped(d_grid: int, n_dim: int, n_grid: int, col,
     inside the stratum of the sample's hypercube (``strat``, ``d_start``, ``d_cube`` as :func:`vegas_sample_device_strat` takes them)
     and every group's jacobian times ``n_total / (H n_h)``.  ``var_sets`` None: one jacobian ``jac[b]``, the full fold (polar without
     groups)."""
-    c = None
-    if col is not None:
-        c = np.ascontiguousarray([0 if v is None else v for v in col], dtype=np.uint32)
-        if c.shape != (n_dim,):
-            raise ValueError("col must name one column per variable")
+    c = _col_arg(col, n_dim, none_ok=True)
     arr, n_polar = _polar_array(polar)
     vm = None
     if var_sets is not None:
@@ -1627,14 +1618,8 @@ def vegas_sample_device_discrete(d_grid: int, n_dim: int, n_grid: int, col, d_cd
     """fdg_vegas_sample_device_discrete: :func:`vegas_sample_device` plus one discrete variable drawn by ``d_cdf`` (device,
     ``n_bin + 1`` doubles): ``bin[b] = j + bin_base``, ``jac[b]`` divided by the value's probability, row ``j`` of ``d_ext`` (device,
     ``[n_bin, len(ext_col)]``) copied into the columns ``ext_col`` (host sequence; empty or None with ``d_ext`` 0: no table)."""
-    c = None
-    if col is not None:
-        c = np.ascontiguousarray(col, dtype=np.uint32)
-        if c.shape != (n_dim,):
-            raise ValueError("col must name one column per variable")
-    e = np.ascontiguousarray([] if ext_col is None else ext_col, dtype=np.uint32)
-    if e.ndim != 1:
-        raise ValueError("ext_col must be a sequence of column numbers")
+    c = _col_arg(col, n_dim)
+    e = _ext_col_arg(ext_col)
     check(lib().fdg_vegas_sample_device_discrete(d_grid or None, n_dim, n_grid, None if c is None else c.ctypes.data, d_cdf or None, n_bin,
                                                  bin_base, d_ext or None, e.shape[0], e.ctypes.data if e.shape[0] else None, seed,
                                                  sample_offset, d_x or None, xs, xc, d_jac or None, d_bin or None, d_cell or None, B, stream))
@@ -1653,14 +1638,8 @@ def vegas_sample_device_polar(d_grid: int, n_dim: int, n_grid: int, col, d_cdf: 
     ``(var, cols)`` with ``len(cols)`` 2 -- variables ``var, var + 1`` are (k, phi) -- or 3 -- ``var .. var + 2`` are (k, theta, phi) --;
     the Cartesian components go to the columns ``cols``.  ``col`` names a column per variable; the entry of a grouped variable is not
     read (None stands for 0 there)."""
-    c = None
-    if col is not None:
-        c = np.ascontiguousarray([0 if v is None else v for v in col], dtype=np.uint32)
-        if c.shape != (n_dim,):
-            raise ValueError("col must name one column per variable")
-    e = np.ascontiguousarray([] if ext_col is None else ext_col, dtype=np.uint32)
-    if e.ndim != 1:
-        raise ValueError("ext_col must be a sequence of column numbers")
+    c = _col_arg(col, n_dim, none_ok=True)
+    e = _ext_col_arg(ext_col)
     arr, n_polar = _polar_array(polar)
     check(lib().fdg_vegas_sample_device_polar(d_grid or None, n_dim, n_grid, None if c is None else c.ctypes.data, d_cdf or None, n_bin,
                                               bin_base, d_ext or None, e.shape[0], e.ctypes.data if e.shape[0] else None,
@@ -1864,14 +1843,8 @@ def vegas_sample_device_grouped(d_grid: int, n_dim: int, n_grid: int, col, d_cdf
     """fdg_vegas_sample_device_grouped: :func:`vegas_sample_device_polar` with one jacobian per weight group,
     ``jac[g * jac_group_stride + b]`` the fold over the variables ``var_sets[g]`` only (``var_sets``: a sequence of sets of variables, or
     the uint64 masks themselves)."""
-    c = None
-    if col is not None:
-        c = np.ascontiguousarray([0 if v is None else v for v in col], dtype=np.uint32)
-        if c.shape != (n_dim,):
-            raise ValueError("col must name one column per variable")
-    e = np.ascontiguousarray([] if ext_col is None else ext_col, dtype=np.uint32)
-    if e.ndim != 1:
-        raise ValueError("ext_col must be a sequence of column numbers")
+    c = _col_arg(col, n_dim, none_ok=True)
+    e = _ext_col_arg(ext_col)
     arr, n_polar = _polar_array(polar)
     vm = var_sets if isinstance(var_sets, np.ndarray) and var_sets.dtype == np.uint64 else var_masks(var_sets)
     vm = np.ascontiguousarray(vm)

@@ -71,6 +71,7 @@
 #include "fdg_internal.h"
 #include "fdg_matsubara.h"
 #include "fdg_sincos.h"
+#include "fdg_sampler.h"
 
 using namespace fdg;
 
@@ -641,283 +642,141 @@ fdg_fobs_reduce(const double *__restrict__ partial, uint32_t n_seg, long ncol, u
   }
 }
 
-// ---- VEGAS importance sampling: the map, the sampler, the training pass (include/fdg.h: fdg_vegas_sample_device, fdg_accumulate_device_vegas) ----
-// The cell of variable d that sample `sample` (a global index: the Philox counter) falls in, and y = u * G; every operation one rounded fp64
-// operation.  The sampler and the training pass both call this: the pass reads no cell array.
-__device__ __forceinline__ uint32_t vegas_cell(uint64_t sample, uint32_t d, uint64_t seed, uint32_t G, double &y) {
-  const double u = fdg_philox_u53(sample, d, seed);
-  y = u * (double)G;
-  return min((uint32_t)(int)y, G - 1u);
-}
+// ---- VEGAS importance sampling: the sampler, the training pass (include/fdg.h: fdg_vegas_sample_device, fdg_accumulate_device_vegas) ----
+// The map's statements (vegas_cell, vegas_draw, discrete_pick, strat_cube, polar_point) are fdg_sampler.h's.
 
-// The strata of the stratified calls (a kernel argument, by value): n[d] strata of variable d, div[d] = n[0] * .. * n[d - 1] (the digit
-// of hypercube h in variable d is h / div[d] % n[d]; 1 and 1 past n_dim), H their product.
-struct VegasStrat { uint32_t n[FDG_VEGAS_DIM_MAX], div[FDG_VEGAS_DIM_MAX], H; };
-
-// vegas_cell inside stratum s of ns: v = (s + u) / ns in the place of u.  (0 + u) / 1 = u exactly: one stratum is vegas_cell.
-__device__ __forceinline__ uint32_t vegas_cell_strat(uint64_t sample, uint32_t d, uint64_t seed, uint32_t G, uint32_t s, uint32_t ns, double &y) {
-  const double u = fdg_philox_u53(sample, d, seed);
-  const double v = ((double)s + u) / (double)ns;
-  y = v * (double)G;
-  return min((uint32_t)(int)y, G - 1u);
-}
-
-struct VegasCols { uint32_t c[FDG_VEGAS_DIM_MAX]; };   // the column of x each variable is written to (a kernel argument, by value)
-
-// The continuous variables of sample b, in order: x and the cell of each, and the jacobian (a left fold over them), returned.
-// kPolar (fdg_vegas_sample_polar): bit d of `grouped` set = variable d belongs to a polar group; its value goes to the lane's slot of
-// `stash` (LDS, [slot][256 lanes], slots in ascending d) instead of a column of x.
-// fold(d, f): called with every variable's factor f = G * wd_d of the jacobian, in order (the grouped sampler's per-group folds).
-// pick(sample, d, seed, G, y): the cell of variable d and y, called once per variable in ascending d (VegasPlainCell: vegas_cell;
-// VegasStratCell: vegas_cell_strat in the stratum that the digits of the sample's hypercube name, peeled as the calls go).
-struct VegasNoFold { __device__ void operator()(uint32_t, double) const {} };
-struct VegasPlainCell {
-  __device__ __forceinline__ uint32_t operator()(uint64_t sample, uint32_t d, uint64_t seed, uint32_t G, double &y) const {
-    return vegas_cell(sample, d, seed, G, y);
-  }
+// What the instances of the sampler take beside the map and the outputs, each only where its flag is set (kernel arguments, by value).
+// The discrete variable: its cdf, the base of bin[], its table ext [n_bin][n_ext] and the table's columns.
+struct VegasDiscArgs {
+  const double *cdf;
+  uint32_t n_bin;
+  int32_t bin_base;
+  const double *ext;
+  uint32_t n_ext;
+  SamplerExtCols ecol;
+  int32_t *bin;
 };
-struct VegasStratCell {
-  const VegasStrat *sv;
-  uint32_t rem;                                           // the hypercube's digits not yet peeled
-  __device__ __forceinline__ uint32_t operator()(uint64_t sample, uint32_t d, uint64_t seed, uint32_t G, double &y) {
-    const uint32_t ns = sv->n[d], sd = rem % ns;
-    rem /= ns;
-    return vegas_cell_strat(sample, d, seed, G, sd, ns, y);
-  }
-};
-template <bool kPolar = false, class Fold = VegasNoFold, class Cell = VegasPlainCell>
-__device__ __forceinline__ double vegas_draw(const double *__restrict__ grid, uint32_t D, uint32_t G, const VegasCols &col, uint64_t seed,
-                                             uint64_t off, double *__restrict__ x, long xs, long xc, int32_t *__restrict__ cell, long n, long b,
-                                             uint64_t grouped = 0, double *stash = nullptr, Fold fold = Fold(), Cell pick = Cell()) {
-  double jb = 0.0;
-  uint32_t slot = 0;
-  for (uint32_t d = 0; d < D; ++d) {
-    double y;
-    const uint32_t c = pick(off + (uint64_t)b, d, seed, G, y);
-    const double *e = grid + (size_t)d * (G + 1u) + c;
-    const double lo = e[0], wd = e[1] - lo, fr = y - (double)c;
-    const double v = lo + fr * wd;
-    if (kPolar && ((grouped >> d) & 1u)) stash[(slot++) * 256u + threadIdx.x] = v;
-    else x[b * xs + (long)col.c[d] * xc] = v;
-    const double f = (double)G * wd;
-    jb = d ? jb * f : f;
-    fold(d, f);
-    if (cell) cell[(size_t)d * (size_t)n + (size_t)b] = (int32_t)c;
-  }
-  return jb;
-}
-
-// One lane per sample.
-__global__ void __launch_bounds__(256)
-fdg_vegas_sample(const double *__restrict__ grid, uint32_t D, uint32_t G, VegasCols col, uint64_t seed, uint64_t off, double *__restrict__ x,
-                 long xs, long xc, double *__restrict__ jac, int32_t *__restrict__ cell, long n) {
-  for (long b = blockIdx.x * 256L + threadIdx.x; b < n; b += (long)gridDim.x * 256L) {
-    const double jb = vegas_draw(grid, D, G, col, seed, off, x, xs, xc, cell, n, b);
-    jac[b] = jb;
-  }
-}
-
-// The stratified sampler (fdg_vegas_sample_device_strat): one lane per sample.  The lane finds its hypercube h by a binary search in
-// start[0 .. H] (at most 20 steps; the table is at most 8 MiB and stays in L2), peels h's digits variable by variable and draws every
-// variable inside its stratum; the rest of a variable is vegas_draw's own arithmetic.  jac = jac_map * (n_total / (H * n_h)).
-__global__ void __launch_bounds__(256)
-fdg_vegas_sample_strat(const double *__restrict__ grid, uint32_t D, uint32_t G, VegasCols col, VegasStrat sv, const int64_t *__restrict__ start,
-                       uint64_t seed, uint64_t off, double *__restrict__ x, long xs, long xc, double *__restrict__ jac,
-                       int32_t *__restrict__ cube, int32_t *__restrict__ cell, long n) {
-  const uint32_t H = sv.H;
-  const int64_t n_total = start[H];
-  for (long b = blockIdx.x * 256L + threadIdx.x; b < n; b += (long)gridDim.x * 256L) {
-    const int64_t i = (int64_t)(off + (uint64_t)b);
-    uint32_t lo = 0, hi = H - 1u;                         // h in [lo, hi]: start[lo] <= i
-    while (lo < hi) {
-      const uint32_t mid = (lo + hi + 1u) >> 1;
-      if (start[mid] <= i) lo = mid; else hi = mid - 1u;
-    }
-    const int64_t n_h = start[lo + 1u] - start[lo];
-    cube[b] = (int32_t)lo;
-    uint32_t rem = lo;
-    double jb = 0.0;
-    for (uint32_t d = 0; d < D; ++d) {
-      const uint32_t ns = sv.n[d], sd = rem % ns;
-      rem /= ns;
-      double y;
-      const uint32_t c = vegas_cell_strat(off + (uint64_t)b, d, seed, G, sd, ns, y);
-      const double *e = grid + (size_t)d * (G + 1u) + c;
-      const double el = e[0], wd = e[1] - el, fr = y - (double)c;
-      x[b * xs + (long)col.c[d] * xc] = el + fr * wd;
-      const double f = (double)G * wd;
-      jb = d ? jb * f : f;
-      if (cell) cell[(size_t)d * (size_t)n + (size_t)b] = (int32_t)c;
-    }
-    const double fac = (double)n_total / ((double)H * (double)n_h);
-    jac[b] = jb * fac;
-  }
-}
-
-struct VegasExtCols { uint32_t c[FDG_VEGAS_EXT_MAX]; };   // the columns of x the rows of the discrete variable's table go to
-
-// The discrete variable of sample b behind D continuous ones whose jacobian is jb: its uniform is the Philox column D, its value j the
-// number of interior edges of cdf that are <= u (a binary search per lane: the cdf is at most 128 KiB and stays in L2).
-// vegas_pick_discrete: the value, its bin and the table's row written, its probability p returned (what every weight is divided by).
-__device__ __forceinline__ double vegas_pick_discrete(const double *__restrict__ cdf, uint32_t n_bin, int32_t bin_base,
-                                                      const double *__restrict__ ext, uint32_t n_ext, const VegasExtCols &ecol, uint64_t seed,
-                                                      uint64_t off, uint32_t D, double *__restrict__ x, long xs, long xc,
-                                                      int32_t *__restrict__ bin, long b) {
-  const double u = fdg_philox_u53(off + (uint64_t)b, D, seed);
-  uint32_t lo = 0, hi = n_bin - 1u;                     // j in [lo, hi]: cdf[1 .. lo] <= u < cdf[hi + 1 ..]
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (cdf[mid + 1u] <= u) lo = mid + 1u; else hi = mid;
-  }
-  const double p = cdf[lo + 1u] - cdf[lo];
-  bin[b] = (int32_t)lo + bin_base;
-  for (uint32_t e = 0; e < n_ext; ++e) x[b * xs + (long)ecol.c[e] * xc] = ext[(size_t)lo * n_ext + e];
-  return p;
-}
-
-__device__ __forceinline__ void vegas_draw_discrete(const double *__restrict__ cdf, uint32_t n_bin, int32_t bin_base,
-                                                    const double *__restrict__ ext, uint32_t n_ext, const VegasExtCols &ecol, uint64_t seed,
-                                                    uint64_t off, uint32_t D, double *__restrict__ x, long xs, long xc,
-                                                    double *__restrict__ jac, int32_t *__restrict__ bin, long b, double jb) {
-  const double p = vegas_pick_discrete(cdf, n_bin, bin_base, ext, n_ext, ecol, seed, off, D, x, xs, xc, bin, b);
-  jac[b] = jb / p;
-}
-
-// fdg_vegas_sample with one discrete variable behind the continuous ones (vegas_draw_discrete).
-__global__ void __launch_bounds__(256)
-fdg_vegas_sample_discrete(const double *__restrict__ grid, uint32_t D, uint32_t G, VegasCols col, const double *__restrict__ cdf,
-                          uint32_t n_bin, int32_t bin_base, const double *__restrict__ ext, uint32_t n_ext, VegasExtCols ecol, uint64_t seed,
-                          uint64_t off, double *__restrict__ x, long xs, long xc, double *__restrict__ jac, int32_t *__restrict__ bin,
-                          int32_t *__restrict__ cell, long n) {
-  for (long b = blockIdx.x * 256L + threadIdx.x; b < n; b += (long)gridDim.x * 256L) {
-    const double jb = vegas_draw(grid, D, G, col, seed, off, x, xs, xc, cell, n, b);
-    vegas_draw_discrete(cdf, n_bin, bin_base, ext, n_ext, ecol, seed, off, D, x, xs, xc, jac, bin, b, jb);
-  }
-}
-
-// The groups of polar variables (a kernel argument, by value): group g takes the variables var[g] .. var[g] + dim[g] - 1 and writes
-// the Cartesian components to the columns col[g][0 .. dim[g]).  grouped: bit d set = variable d belongs to a group.
-struct VegasPolar {
-  uint64_t grouped;
-  uint32_t n;
-  uint32_t var[FDG_VEGAS_POLAR_MAX], dim[FDG_VEGAS_POLAR_MAX];
-  uint32_t col[FDG_VEGAS_POLAR_MAX][3];
-};
-
-// The weight groups of the grouped sampler (a kernel argument, by value): bit d of m[g] set = variable d belongs to group g.
-struct VegasGroupMasks {
+// The weight groups: bit d of m[g] set = variable d belongs to group g; group g's jacobian goes to jac[g * jstride + b].
+struct VegasGroupArgs {
   uint64_t m[FDG_WEIGHT_GROUP_MAX];
   uint32_t n;
+  long jstride;
 };
-
-// fdg_vegas_sample / fdg_vegas_sample_discrete (cdf null: no discrete variable) with groups of variables read as (k, phi) or
-// (k, theta, phi): the drawn values of the grouped variables wait in LDS (one slot of 256 lanes per grouped variable, dynamic:
-// 2 KiB each) until the fold over all variables is done, then every group gives its columns and its factors of the jacobian, in
-// the order of the array.  One lane per sample; a lane touches its own LDS words only, so no barrier.
-// GRP (fdg_vegas_sample_device_grouped): one jacobian per weight group, jac[g * jstride + b], each the same fold over the variables
-// and polar groups of its mask only (1.0 * f = f exactly: a group's first factor enters as the plain fold's does).  Every variable is
-// drawn once, and x, bin and cell are written by the very statements of the ungrouped instance.
-// STRAT (fdg_vegas_sample_device_strat_grouped; no discrete variable): the lane finds its hypercube as fdg_vegas_sample_strat does
-// (binary search in start[0 .. H], cube[b]), every variable is drawn by vegas_cell_strat in the stratum of the hypercube's digit, and
-// every jacobian is multiplied by fac_h = n_total / (H * n_h) last.  The instances without it take an empty argument in its place.
-struct VegasNoStrat {};
+// The strata, the prefix sums start[0 .. H] of the samples per hypercube, and cube[b] to write.
 struct VegasStratArgs {
   VegasStrat sv;
   const int64_t *start;
   int32_t *cube;
 };
-template <bool GRP, bool STRAT = false>
+
+// The one sampler, one lane per sample in a grid-stride loop.  The continuous variables of sample b in order: each through the map
+// (vegas_draw), its value to its column of x, its factor f = G * wd into the jacobian (a left fold), its cell to cell[] when given.
+// DISC: one discrete variable behind them (discrete_pick): bin[b], row j of ext to the columns ecol, every jacobian divided by p.
+// POLAR: groups of variables read as (k, phi) or (k, theta, phi).  The drawn values of the grouped variables wait in LDS (one slot of
+//   256 lanes per grouped variable, in ascending d, dynamic: 2 KiB each) until the fold over all variables is done, then every group
+//   gives its columns and its factors of the jacobian (k, or k k sin theta), in the order of the array.  A lane touches its own LDS
+//   words only, so no barrier.
+// GRP: one jacobian per weight group, each the same fold over the variables and polar groups of its mask only (1.0 * f = f exactly:
+//   a group's first factor enters as the plain fold's does; a mask holds all of a polar group's variables or none: its first one
+//   decides).  Every variable is drawn once, and x, bin and cell are written by the very statements of the ungrouped instances.
+// STRAT (no discrete variable): the lane finds its hypercube h (strat_cube, cube[b]), peels h's digits variable by variable and draws
+//   every variable inside its stratum; every jacobian is multiplied by fac_h = n_total / (H * n_h) last.
+template <bool POLAR, bool GRP, bool STRAT, bool DISC>
 __global__ void __launch_bounds__(256)
-fdg_vegas_sample_polar(const double *__restrict__ grid, uint32_t D, uint32_t G, VegasCols col, VegasPolar pol, const double *__restrict__ cdf,
-                       uint32_t n_bin, int32_t bin_base, const double *__restrict__ ext, uint32_t n_ext, VegasExtCols ecol, uint64_t seed,
-                       uint64_t off, double *__restrict__ x, long xs, long xc, double *__restrict__ jac, int32_t *__restrict__ bin,
-                       int32_t *__restrict__ cell, long n, VegasGroupMasks gm, long jstride,
-                       std::conditional_t<STRAT, VegasStratArgs, VegasNoStrat> sa) {
-  extern __shared__ double polar_stash[];
+fdg_vegas_sample(const double *__restrict__ grid, uint32_t D, uint32_t G, SamplerCols col, uint64_t seed, uint64_t off, double *__restrict__ x,
+                 long xs, long xc, double *__restrict__ jac, int32_t *__restrict__ cell, long n, ArgIf<DISC, VegasDiscArgs> da,
+                 ArgIf<POLAR, SamplerPolar> pol, ArgIf<GRP, VegasGroupArgs> ga, ArgIf<STRAT, VegasStratArgs> sa) {
+  static_assert(!(STRAT && DISC), "the stratified calls take no discrete variable");
   constexpr int NG = GRP ? FDG_WEIGHT_GROUP_MAX : 1;
+  [[maybe_unused]] double *stash = nullptr;
+  if constexpr (POLAR) {
+    extern __shared__ double polar_stash[];
+    stash = polar_stash;
+  }
+  [[maybe_unused]] double n_total = 0.0;
+  if constexpr (STRAT) n_total = (double)sa.start[sa.sv.H];
   for (long b = blockIdx.x * 256L + threadIdx.x; b < n; b += (long)gridDim.x * 256L) {
+    const uint64_t sample = off + (uint64_t)b;
     [[maybe_unused]] double fac = 1.0;                     // STRAT: fac_h of this lane's hypercube
-    [[maybe_unused]] uint32_t hcube = 0;
+    [[maybe_unused]] uint32_t rem = 0;                     // STRAT: the hypercube's digits not yet peeled
     if constexpr (STRAT) {
-      const uint32_t H = sa.sv.H;
-      const int64_t i = (int64_t)(off + (uint64_t)b);
-      uint32_t lo = 0, hi = H - 1u;                       // h in [lo, hi]: start[lo] <= i
-      while (lo < hi) {
-        const uint32_t mid = (lo + hi + 1u) >> 1;
-        if (sa.start[mid] <= i) lo = mid; else hi = mid - 1u;
-      }
-      const int64_t n_h = sa.start[lo + 1u] - sa.start[lo];
-      sa.cube[b] = (int32_t)lo;
-      hcube = lo;
-      fac = (double)sa.start[H] / ((double)H * (double)n_h);
+      int64_t n_h;
+      rem = strat_cube(sa.start, sa.sv.H, (int64_t)sample, n_h);
+      sa.cube[b] = (int32_t)rem;
+      fac = n_total / ((double)sa.sv.H * (double)n_h);
     }
-    double jg[NG];
+    double jb = 0.0;
+    [[maybe_unused]] double jg[NG];
+    if constexpr (GRP) {
 #pragma unroll
-    for (int g = 0; g < NG; ++g) jg[g] = 1.0;
-    // (f into the groups that own d; the ungrouped instance keeps vegas_draw's own fold)
-    auto fold = [&](uint32_t d, double f) {
+      for (int g = 0; g < NG; ++g) jg[g] = 1.0;
+    }
+    [[maybe_unused]] uint32_t slot = 0;
+    for (uint32_t d = 0; d < D; ++d) {
+      uint32_t s = 0, ns = 1;
+      if constexpr (STRAT) {
+        ns = sa.sv.n[d];
+        s = rem % ns;
+        rem /= ns;
+      }
+      uint32_t c;
+      double f;
+      const double v = vegas_draw<STRAT>(grid, d, G, sample, seed, s, ns, c, f);
+      bool stashed = false;
+      if constexpr (POLAR) stashed = (pol.grouped >> d) & 1u;
+      if (stashed) stash[(slot++) * 256u + threadIdx.x] = v;
+      else x[b * xs + (long)col.c[d] * xc] = v;
+      jb = d ? jb * f : f;
       if constexpr (GRP) {
 #pragma unroll
         for (int g = 0; g < NG; ++g)
-          if ((uint32_t)g < gm.n && ((gm.m[g] >> d) & 1u)) jg[g] = jg[g] * f;
+          if ((uint32_t)g < ga.n && ((ga.m[g] >> d) & 1u)) jg[g] = jg[g] * f;
       }
-    };
-    double jb;
-    if constexpr (STRAT) jb = vegas_draw<true>(grid, D, G, col, seed, off, x, xs, xc, cell, n, b, pol.grouped, polar_stash, fold, VegasStratCell{&sa.sv, hcube});
-    else jb = vegas_draw<true>(grid, D, G, col, seed, off, x, xs, xc, cell, n, b, pol.grouped, polar_stash, fold);
-    for (uint32_t g = 0; g < pol.n; ++g) {
-      const uint32_t var = pol.var[g];
-      const double *v = polar_stash + (size_t)__popcll(pol.grouped & ((1ull << var) - 1ull)) * 256u + threadIdx.x;
-      double *xb = x + b * xs;
-      const double k = v[0];
-      double sp, cp, st = 0.0;
-      if (pol.dim[g] == 3) {
-        double ct;
-        fdg_sincos_impl(v[256], st, ct);
-        fdg_sincos_impl(v[512], sp, cp);
-        const double ks = k * st;
-        xb[(long)pol.col[g][0] * xc] = ks * cp;
-        xb[(long)pol.col[g][1] * xc] = ks * sp;
-        xb[(long)pol.col[g][2] * xc] = k * ct;
+      if (cell) cell[(size_t)d * (size_t)n + (size_t)b] = (int32_t)c;
+    }
+    if constexpr (POLAR) {
+      for (uint32_t g = 0; g < pol.n; ++g) {
+        const uint32_t var = pol.var[g];
+        const bool three = pol.dim[g] == 3;
+        const double *v = stash + (size_t)__popcll(pol.grouped & ((1ull << var) - 1ull)) * 256u + threadIdx.x;
+        double *xb = x + b * xs;
+        const double k = v[0];
+        double c0, c1, c2, st;
+        polar_point(three, k, v[256], v[three ? 512 : 256], c0, c1, c2, st);
+        xb[(long)pol.col[g][0] * xc] = c0;
+        xb[(long)pol.col[g][1] * xc] = c1;
+        if (three) xb[(long)pol.col[g][2] * xc] = c2;
         jb = jb * k;
-        jb = jb * k;
-        jb = jb * st;
-      } else {
-        fdg_sincos_impl(v[256], sp, cp);
-        xb[(long)pol.col[g][0] * xc] = k * cp;
-        xb[(long)pol.col[g][1] * xc] = k * sp;
-        jb = jb * k;
-      }
-      if constexpr (GRP) {
-        // (a mask holds all of a polar group's variables or none: its first one decides)
+        if (three) {
+          jb = jb * k;
+          jb = jb * st;
+        }
+        if constexpr (GRP) {
 #pragma unroll
-        for (int h = 0; h < NG; ++h)
-          if ((uint32_t)h < gm.n && ((gm.m[h] >> var) & 1u)) {
-            jg[h] = jg[h] * k;
-            if (pol.dim[g] == 3) {
+          for (int h = 0; h < NG; ++h)
+            if ((uint32_t)h < ga.n && ((ga.m[h] >> var) & 1u)) {
               jg[h] = jg[h] * k;
-              jg[h] = jg[h] * st;
+              if (three) {
+                jg[h] = jg[h] * k;
+                jg[h] = jg[h] * st;
+              }
             }
-          }
+        }
       }
     }
-    if constexpr (STRAT) {
-      if constexpr (GRP) {
-#pragma unroll
-        for (int g = 0; g < NG; ++g)
-          if ((uint32_t)g < gm.n) jac[(size_t)g * (size_t)jstride + (size_t)b] = jg[g] * fac;
-      } else {
-        jac[b] = jb * fac;
-      }
-    } else if constexpr (GRP) {
-      // the discrete variable is shared by every group
-      const double p = cdf ? vegas_pick_discrete(cdf, n_bin, bin_base, ext, n_ext, ecol, seed, off, D, x, xs, xc, bin, b) : 1.0;
+    [[maybe_unused]] double p = 1.0;                       // DISC: the probability of the value drawn; shared by every group
+    if constexpr (DISC) {
+      const uint32_t j = discrete_pick(da.cdf, da.n_bin, sample, D, seed, p);
+      da.bin[b] = (int32_t)j + da.bin_base;
+      for (uint32_t e = 0; e < da.n_ext; ++e) x[b * xs + (long)da.ecol.c[e] * xc] = da.ext[(size_t)j * da.n_ext + e];
+    }
+    auto out = [&](double j) { return DISC ? j / p : STRAT ? j * fac : j; };
+    if constexpr (GRP) {
 #pragma unroll
       for (int g = 0; g < NG; ++g)
-        if ((uint32_t)g < gm.n) jac[(size_t)g * (size_t)jstride + (size_t)b] = cdf ? jg[g] / p : jg[g];
+        if ((uint32_t)g < ga.n) jac[(size_t)g * (size_t)ga.jstride + (size_t)b] = out(jg[g]);
     } else {
-      if (!cdf) { jac[b] = jb; continue; }
-      vegas_draw_discrete(cdf, n_bin, bin_base, ext, n_ext, ecol, seed, off, D, x, xs, xc, jac, bin, b, jb);
+      jac[b] = out(jb);
     }
   }
 }
@@ -2477,10 +2336,102 @@ int check_sampler(int64_t B, bool null_buffer, uint32_t n_dim, uint32_t n_grid) 
   return check_vegas_map(n_dim, n_grid);
 }
 
-VegasCols vegas_cols(const uint32_t *col, uint32_t n_dim) {
-  VegasCols cols;
-  for (uint32_t d = 0; d < FDG_VEGAS_DIM_MAX; ++d) cols.c[d] = d < n_dim ? (col ? col[d] : d) : 0u;
-  return cols;
+// What a sampler entry carries beside the map and the outputs; an entry leaves what it does not take at these defaults.
+struct VegasSampleCall {
+  // the discrete variable; d_cdf null: none, and the rest is ignored.  need_discrete (fdg_vegas_sample_device_discrete): d_cdf and
+  // d_bin are required
+  const double *d_cdf = nullptr;
+  uint32_t n_bin = 1;
+  int32_t bin_base = 0;
+  const double *d_ext = nullptr;
+  uint32_t n_ext = 0;
+  const uint32_t *ext_col = nullptr;
+  int32_t *d_bin = nullptr;
+  bool need_discrete = false;
+  // the polar groups.  takes_polar (the _polar, _grouped and _strat_grouped entries): every written column is to be named once
+  const fdg_vegas_polar *polar = nullptr;
+  uint32_t n_polar = 0;
+  bool takes_polar = false;
+  // the weight groups: one jacobian per group
+  bool grouped = false;
+  const uint64_t *var_mask = nullptr;
+  uint32_t n_group = 0;
+  int64_t jac_group_stride = 0;
+  // the strata
+  bool stratified = false;
+  const uint32_t *strat = nullptr;
+  const int64_t *d_start = nullptr;
+  int32_t *d_cube = nullptr;
+};
+
+// Every fdg_vegas_sample_device* entry: the checks in one order, then the instance of the sampler that reads what the call carries
+// and nothing else (no polar group: no LDS and no group list, whichever entry was called).
+int vegas_sample(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, uint64_t seed, uint64_t sample_offset, double *d_x,
+                 int64_t x_sample_stride, int64_t x_col_stride, double *d_jac, int32_t *d_cell, int64_t B, void *stream, VegasSampleCall c) {
+  const bool bad_discrete = c.need_discrete ? !c.d_cdf || !c.d_bin : c.d_cdf && !c.d_bin;
+  int rc = check_sampler(B, !d_grid || !d_x || !d_jac || bad_discrete || (c.grouped && !c.var_mask), n_dim, n_grid);
+  if (rc) return rc;
+  if (!c.d_cdf) c.n_bin = 1, c.n_ext = 0;                 // no discrete variable: its arguments are ignored
+  VegasDiscArgs da{c.d_cdf, c.n_bin, c.bin_base, c.d_ext, c.n_ext, {}, c.d_bin};
+  rc = check_discrete_table(c.n_bin, FDG_BIN_MAX, "FDG_BIN_MAX", c.d_ext, c.n_ext, c.ext_col, da.ecol);
+  if (rc) return rc;
+  SamplerPolar pol;
+  rc = parse_polar(c.polar, c.n_polar, n_dim, -1, pol);
+  if (rc) return rc;
+  const SamplerCols cols = sampler_cols(col, n_dim, pol.grouped);
+  rc = c.takes_polar ? check_cols_once(cols, n_dim, pol, da.ecol, c.n_ext) : check_ext_cols(da.ecol, c.n_ext, cols, n_dim, 0, -1);
+  if (rc) return rc;
+  VegasGroupArgs ga = {};
+  if (c.grouped) {
+    if (c.n_group == 0) { set_error("n_group == 0"); return FDG_E_INVALID; }
+    if (c.n_group > FDG_WEIGHT_GROUP_MAX) { set_error("n_group > FDG_WEIGHT_GROUP_MAX"); return FDG_E_UNSUPPORTED; }
+    ga.n = c.n_group;
+    ga.jstride = (long)c.jac_group_stride;
+    for (uint32_t g = 0; g < c.n_group; ++g) {
+      ga.m[g] = c.var_mask[g];
+      if (n_dim < 64 && (c.var_mask[g] >> n_dim)) { set_error("var_mask names a variable >= n_dim"); return FDG_E_INVALID; }
+      for (uint32_t pg = 0; pg < pol.n; ++pg) {
+        const uint64_t bits = ((1ull << pol.dim[pg]) - 1ull) << pol.var[pg], has = c.var_mask[g] & bits;
+        if (has && has != bits) { set_error("var_mask holds some but not all variables of a polar group"); return FDG_E_INVALID; }
+      }
+    }
+    if (c.n_group > 1 && c.jac_group_stride < B) { set_error("jac_group_stride < n_sample"); return FDG_E_INVALID; }
+  }
+  VegasStratArgs sa = {};
+  if (c.stratified) {
+    if (!c.strat || !c.d_start || !c.d_cube) { set_error("null strat, d_start or d_cube"); return FDG_E_INVALID; }
+    uint32_t H;
+    rc = check_strat(c.strat, n_dim, &H);
+    if (rc) return rc;
+    sa = VegasStratArgs{vegas_strat(c.strat, n_dim), c.d_start, c.d_cube};
+  }
+  if (B == 0) return FDG_OK;
+  const long grid = std::min<long>(((long)B + 255) / 256, 256L * 16);
+  const size_t lds = (size_t)__builtin_popcountll(pol.grouped) * 256u * sizeof(double);
+  auto launch = [&](auto polar, auto grp, auto stratified, auto disc) {
+    constexpr bool P = decltype(polar)::value, Gr = decltype(grp)::value, S = decltype(stratified)::value, Dc = decltype(disc)::value;
+    if constexpr (!(S && Dc)) {                            // (a stratified call has no discrete variable)
+      const auto kernel = fdg_vegas_sample<P, Gr, S, Dc>;
+      if constexpr (P) {
+        static std::once_flag once;
+        std::call_once(once, [&] {
+          (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, FDG_VEGAS_DIM_MAX * 256 * (int)sizeof(double));
+          (void)hipGetLastError();
+        });
+      }
+      // (the by-value arguments of the fullest instance -- cols, pol, the group masks and the strata -- come to about 1.4 KiB of the 4 KiB segment)
+      hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, d_grid, n_dim, n_grid, cols, seed, sample_offset,
+                         d_x, (long)x_sample_stride, (long)x_col_stride, d_jac, d_cell, (long)B, arg_if<Dc>(da), arg_if<P>(pol),
+                         arg_if<Gr>(ga), arg_if<S>(sa));
+    }
+  };
+  with_flag(pol.n != 0, [&](auto p) {
+    with_flag(c.grouped, [&](auto g) {
+      with_flag(c.stratified, [&](auto s) { with_flag(c.d_cdf != nullptr, [&](auto d) { launch(p, g, s, d); }); });
+    });
+  });
+  HIP_TRY(hipGetLastError());
+  return FDG_OK;
 }
 
 }  // namespace
@@ -2602,24 +2553,6 @@ int fdg_mc_accumulate_device_strat_grouped(fdg_graph *g, const double *d_K, int6
   const BinnedCall c{nullptr, 0, 1, d_weight, d_acc, d_acc2, B, stream, &vg, nullptr, wg, nullptr, &sr};
   const int rc = check_strat_grouped_call(g, c);
   return rc ? rc : accumulate_mc(g, d_K, ks, kc, d_T, ts, tc, kF, beta, lambda, c);
-}
-
-int fdg_vegas_sample_device_strat(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, const uint32_t *strat,
-                                  const int64_t *d_start, uint64_t seed, uint64_t sample_offset, double *d_x, int64_t x_sample_stride,
-                                  int64_t x_col_stride, double *d_jac, int32_t *d_cube, int32_t *d_cell, int64_t B, void *stream) {
-  int rc = check_sampler(B, !d_grid || !d_x || !d_jac, n_dim, n_grid);
-  if (rc) return rc;
-  if (!strat || !d_start || !d_cube) { set_error("null strat, d_start or d_cube"); return FDG_E_INVALID; }
-  uint32_t H;
-  rc = check_strat(strat, n_dim, &H);
-  if (rc) return rc;
-  if (B == 0) return FDG_OK;
-  const long grid = std::min<long>(((long)B + 255) / 256, 256L * 16);
-  hipLaunchKernelGGL(fdg_vegas_sample_strat, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, d_grid, n_dim, n_grid,
-                     vegas_cols(col, n_dim), vegas_strat(strat, n_dim), d_start, seed, sample_offset, d_x, (long)x_sample_stride,
-                     (long)x_col_stride, d_jac, d_cube, d_cell, (long)B);
-  HIP_TRY(hipGetLastError());
-  return FDG_OK;
 }
 
 // The allocation of the next iteration's samples to the hypercubes; host only, fp64, in the order include/fdg.h states.
@@ -2794,125 +2727,28 @@ int fdg_mc_accumulate_device_freq_observables(fdg_graph *g, const double *d_K, i
   return rc ? rc : accumulate_mc(g, d_K, ks, kc, d_T, ts, tc, kF, beta, lambda, c);
 }
 
+// The six sampler entries: each names what it carries and goes through vegas_sample.
+int fdg_vegas_sample_device(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, uint64_t seed, uint64_t sample_offset,
+                            double *d_x, int64_t x_sample_stride, int64_t x_col_stride, double *d_jac, int32_t *d_cell, int64_t B,
+                            void *stream) {
+  return vegas_sample(d_grid, n_dim, n_grid, col, seed, sample_offset, d_x, x_sample_stride, x_col_stride, d_jac, d_cell, B, stream, {});
+}
+
+int fdg_vegas_sample_device_strat(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, const uint32_t *strat,
+                                  const int64_t *d_start, uint64_t seed, uint64_t sample_offset, double *d_x, int64_t x_sample_stride,
+                                  int64_t x_col_stride, double *d_jac, int32_t *d_cube, int32_t *d_cell, int64_t B, void *stream) {
+  VegasSampleCall c;
+  c.stratified = true, c.strat = strat, c.d_start = d_start, c.d_cube = d_cube;
+  return vegas_sample(d_grid, n_dim, n_grid, col, seed, sample_offset, d_x, x_sample_stride, x_col_stride, d_jac, d_cell, B, stream, c);
+}
+
 int fdg_vegas_sample_device_discrete(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, const double *d_cdf,
                                      uint32_t n_bin, int32_t bin_base, const double *d_ext, uint32_t n_ext, const uint32_t *ext_col,
                                      uint64_t seed, uint64_t sample_offset, double *d_x, int64_t x_sample_stride, int64_t x_col_stride,
                                      double *d_jac, int32_t *d_bin, int32_t *d_cell, int64_t B, void *stream) {
-  const int rc = check_sampler(B, !d_grid || !d_x || !d_jac || !d_cdf || !d_bin, n_dim, n_grid);
-  if (rc) return rc;
-  if (n_bin == 0) { set_error("n_bin == 0"); return FDG_E_INVALID; }
-  if (n_bin > FDG_BIN_MAX) { set_error("n_bin > FDG_BIN_MAX"); return FDG_E_UNSUPPORTED; }
-  if (n_ext > FDG_VEGAS_EXT_MAX) { set_error("n_ext > FDG_VEGAS_EXT_MAX"); return FDG_E_UNSUPPORTED; }
-  if (n_ext && (!d_ext || !ext_col)) { set_error("n_ext > 0 needs d_ext and ext_col"); return FDG_E_INVALID; }
-  const VegasCols cols = vegas_cols(col, n_dim);
-  VegasExtCols ecols;
-  for (uint32_t e = 0; e < FDG_VEGAS_EXT_MAX; ++e) ecols.c[e] = e < n_ext ? ext_col[e] : 0u;
-  for (uint32_t e = 0; e < n_ext; ++e) {
-    for (uint32_t f = 0; f < e; ++f)
-      if (ecols.c[f] == ecols.c[e]) { set_error("ext_col names a column twice"); return FDG_E_INVALID; }
-    for (uint32_t d = 0; d < n_dim; ++d)
-      if (cols.c[d] == ecols.c[e]) { set_error("ext_col names a column of col"); return FDG_E_INVALID; }
-  }
-  if (B == 0) return FDG_OK;
-  const long grid = std::min<long>(((long)B + 255) / 256, 256L * 16);
-  hipLaunchKernelGGL(fdg_vegas_sample_discrete, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, d_grid, n_dim, n_grid, cols, d_cdf,
-                     n_bin, bin_base, d_ext, n_ext, ecols, seed, sample_offset, d_x, (long)x_sample_stride, (long)x_col_stride, d_jac, d_bin,
-                     d_cell, (long)B);
-  HIP_TRY(hipGetLastError());
-  return FDG_OK;
-}
-
-// fdg_vegas_sample_device_polar (grouped false; var_mask, n_group and jac_group_stride are not read), fdg_vegas_sample_device_grouped
-// and, with stratified, fdg_vegas_sample_device_strat_grouped (no discrete variable; strat, d_start and d_cube as the stratified
-// sampler takes them).
-static int vegas_sample_polar(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, const double *d_cdf, uint32_t n_bin,
-                              int32_t bin_base, const double *d_ext, uint32_t n_ext, const uint32_t *ext_col, const fdg_vegas_polar *polar,
-                              uint32_t n_polar, uint64_t seed, uint64_t sample_offset, double *d_x, int64_t x_sample_stride,
-                              int64_t x_col_stride, double *d_jac, int32_t *d_bin, int32_t *d_cell, int64_t B, void *stream, bool grouped,
-                              const uint64_t *var_mask, uint32_t n_group, int64_t jac_group_stride, bool stratified = false,
-                              const uint32_t *strat = nullptr, const int64_t *d_start = nullptr, int32_t *d_cube = nullptr) {
-  int rc = check_sampler(B, !d_grid || !d_x || !d_jac || (d_cdf && !d_bin) || (grouped && !var_mask), n_dim, n_grid);
-  if (rc) return rc;
-  if (!d_cdf) n_bin = 1, n_ext = 0;                       // no discrete variable: its arguments are ignored
-  if (n_bin == 0) { set_error("n_bin == 0"); return FDG_E_INVALID; }
-  if (n_bin > FDG_BIN_MAX) { set_error("n_bin > FDG_BIN_MAX"); return FDG_E_UNSUPPORTED; }
-  if (n_ext > FDG_VEGAS_EXT_MAX) { set_error("n_ext > FDG_VEGAS_EXT_MAX"); return FDG_E_UNSUPPORTED; }
-  if (n_ext && (!d_ext || !ext_col)) { set_error("n_ext > 0 needs d_ext and ext_col"); return FDG_E_INVALID; }
-  if (n_polar > FDG_VEGAS_POLAR_MAX) { set_error("n_polar > FDG_VEGAS_POLAR_MAX"); return FDG_E_UNSUPPORTED; }
-  if (n_polar && !polar) { set_error("n_polar > 0 needs polar"); return FDG_E_INVALID; }
-  VegasPolar pol;
-  pol.grouped = 0;
-  pol.n = n_polar;
-  for (uint32_t g = 0; g < FDG_VEGAS_POLAR_MAX; ++g) {
-    const bool in = g < n_polar;
-    pol.var[g] = in ? polar[g].var : 0u;
-    pol.dim[g] = in ? polar[g].dim : 0u;
-    for (uint32_t i = 0; i < 3; ++i) pol.col[g][i] = in && i < polar[g].dim ? polar[g].col[i] : 0u;
-    if (!in) continue;
-    if (polar[g].dim != 2 && polar[g].dim != 3) { set_error("a polar group has 2 or 3 variables"); return FDG_E_INVALID; }
-    if (polar[g].var >= n_dim || polar[g].var + polar[g].dim > n_dim) { set_error("a polar group reaches past n_dim"); return FDG_E_INVALID; }
-    const uint64_t bits = ((1ull << polar[g].dim) - 1ull) << polar[g].var;
-    if (pol.grouped & bits) { set_error("two polar groups share a variable"); return FDG_E_INVALID; }
-    pol.grouped |= bits;
-  }
-  // every column written once: the variables of no group, the groups' components, the discrete variable's table
-  VegasCols cols = vegas_cols(col, n_dim);
-  VegasExtCols ecols;
-  for (uint32_t e = 0; e < FDG_VEGAS_EXT_MAX; ++e) ecols.c[e] = e < n_ext ? ext_col[e] : 0u;
-  std::vector<uint32_t> named;
-  for (uint32_t d = 0; d < n_dim; ++d) {
-    if ((pol.grouped >> d) & 1u) cols.c[d] = 0u;          // (not read)
-    else named.push_back(cols.c[d]);
-  }
-  for (uint32_t g = 0; g < n_polar; ++g) named.insert(named.end(), pol.col[g], pol.col[g] + pol.dim[g]);
-  named.insert(named.end(), ecols.c, ecols.c + n_ext);
-  std::sort(named.begin(), named.end());
-  if (std::adjacent_find(named.begin(), named.end()) != named.end()) { set_error("a column of x is named twice"); return FDG_E_INVALID; }
-  VegasGroupMasks gm = {};
-  if (grouped) {
-    if (n_group == 0) { set_error("n_group == 0"); return FDG_E_INVALID; }
-    if (n_group > FDG_WEIGHT_GROUP_MAX) { set_error("n_group > FDG_WEIGHT_GROUP_MAX"); return FDG_E_UNSUPPORTED; }
-    gm.n = n_group;
-    for (uint32_t g = 0; g < n_group; ++g) {
-      gm.m[g] = var_mask[g];
-      if (n_dim < 64 && (var_mask[g] >> n_dim)) { set_error("var_mask names a variable >= n_dim"); return FDG_E_INVALID; }
-      for (uint32_t pg = 0; pg < n_polar; ++pg) {
-        const uint64_t bits = ((1ull << pol.dim[pg]) - 1ull) << pol.var[pg], has = var_mask[g] & bits;
-        if (has && has != bits) { set_error("var_mask holds some but not all variables of a polar group"); return FDG_E_INVALID; }
-      }
-    }
-    if (n_group > 1 && jac_group_stride < B) { set_error("jac_group_stride < n_sample"); return FDG_E_INVALID; }
-  }
-  if (stratified) {
-    if (!strat || !d_start || !d_cube) { set_error("null strat, d_start or d_cube"); return FDG_E_INVALID; }
-    uint32_t H;
-    rc = check_strat(strat, n_dim, &H);
-    if (rc) return rc;
-  }
-  if (B == 0) return FDG_OK;
-  const size_t lds = (size_t)__builtin_popcountll(pol.grouped) * 256u * sizeof(double);
-  static std::once_flag once;
-  std::call_once(once, [] {
-    for (const void *k : {(const void *)fdg_vegas_sample_polar<false>, (const void *)fdg_vegas_sample_polar<true>,
-                          (const void *)fdg_vegas_sample_polar<false, true>, (const void *)fdg_vegas_sample_polar<true, true>})
-      (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, FDG_VEGAS_DIM_MAX * 256 * (int)sizeof(double));
-    (void)hipGetLastError();
-  });
-  const long grid = std::min<long>(((long)B + 255) / 256, 256L * 16);
-  if (stratified) {
-    // (the kernel arguments -- cols, pol, ecols, gm and the strata by value -- come to about 1.6 KiB of the 4 KiB segment)
-    const VegasStratArgs sa{vegas_strat(strat, n_dim), d_start, d_cube};
-    hipLaunchKernelGGL((grouped ? fdg_vegas_sample_polar<true, true> : fdg_vegas_sample_polar<false, true>), dim3((unsigned)grid), dim3(256),
-                       lds, (hipStream_t)stream, d_grid, n_dim, n_grid, cols, pol, nullptr, 1u, 0, nullptr, 0u, ecols, seed, sample_offset,
-                       d_x, (long)x_sample_stride, (long)x_col_stride, d_jac, nullptr, d_cell, (long)B, gm, (long)jac_group_stride, sa);
-  } else {
-    hipLaunchKernelGGL(grouped ? fdg_vegas_sample_polar<true> : fdg_vegas_sample_polar<false>, dim3((unsigned)grid), dim3(256), lds,
-                       (hipStream_t)stream, d_grid, n_dim, n_grid, cols, pol, d_cdf, n_bin, bin_base, d_ext, n_ext, ecols, seed,
-                       sample_offset, d_x, (long)x_sample_stride, (long)x_col_stride, d_jac, d_bin, d_cell, (long)B, gm,
-                       (long)jac_group_stride, VegasNoStrat{});
-  }
-  HIP_TRY(hipGetLastError());
-  return FDG_OK;
+  VegasSampleCall c{d_cdf, n_bin, bin_base, d_ext, n_ext, ext_col, d_bin};
+  c.need_discrete = true;
+  return vegas_sample(d_grid, n_dim, n_grid, col, seed, sample_offset, d_x, x_sample_stride, x_col_stride, d_jac, d_cell, B, stream, c);
 }
 
 int fdg_vegas_sample_device_polar(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, const double *d_cdf,
@@ -2920,8 +2756,9 @@ int fdg_vegas_sample_device_polar(const double *d_grid, uint32_t n_dim, uint32_t
                                   const fdg_vegas_polar *polar, uint32_t n_polar, uint64_t seed, uint64_t sample_offset, double *d_x,
                                   int64_t x_sample_stride, int64_t x_col_stride, double *d_jac, int32_t *d_bin, int32_t *d_cell, int64_t B,
                                   void *stream) {
-  return vegas_sample_polar(d_grid, n_dim, n_grid, col, d_cdf, n_bin, bin_base, d_ext, n_ext, ext_col, polar, n_polar, seed, sample_offset, d_x,
-                            x_sample_stride, x_col_stride, d_jac, d_bin, d_cell, B, stream, false, nullptr, 0, 0);
+  VegasSampleCall c{d_cdf, n_bin, bin_base, d_ext, n_ext, ext_col, d_bin};
+  c.polar = polar, c.n_polar = n_polar, c.takes_polar = true;
+  return vegas_sample(d_grid, n_dim, n_grid, col, seed, sample_offset, d_x, x_sample_stride, x_col_stride, d_jac, d_cell, B, stream, c);
 }
 
 int fdg_vegas_sample_device_grouped(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, const double *d_cdf,
@@ -2929,8 +2766,10 @@ int fdg_vegas_sample_device_grouped(const double *d_grid, uint32_t n_dim, uint32
                                     const fdg_vegas_polar *polar, uint32_t n_polar, const uint64_t *var_mask, uint32_t n_group,
                                     int64_t jac_group_stride, uint64_t seed, uint64_t sample_offset, double *d_x, int64_t x_sample_stride,
                                     int64_t x_col_stride, double *d_jac, int32_t *d_bin, int32_t *d_cell, int64_t B, void *stream) {
-  return vegas_sample_polar(d_grid, n_dim, n_grid, col, d_cdf, n_bin, bin_base, d_ext, n_ext, ext_col, polar, n_polar, seed, sample_offset, d_x,
-                            x_sample_stride, x_col_stride, d_jac, d_bin, d_cell, B, stream, true, var_mask, n_group, jac_group_stride);
+  VegasSampleCall c{d_cdf, n_bin, bin_base, d_ext, n_ext, ext_col, d_bin};
+  c.polar = polar, c.n_polar = n_polar, c.takes_polar = true;
+  c.grouped = true, c.var_mask = var_mask, c.n_group = n_group, c.jac_group_stride = jac_group_stride;
+  return vegas_sample(d_grid, n_dim, n_grid, col, seed, sample_offset, d_x, x_sample_stride, x_col_stride, d_jac, d_cell, B, stream, c);
 }
 
 int fdg_vegas_sample_device_strat_grouped(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col,
@@ -2938,26 +2777,15 @@ int fdg_vegas_sample_device_strat_grouped(const double *d_grid, uint32_t n_dim, 
                                           int64_t jac_group_stride, const uint32_t *strat, const int64_t *d_start, uint64_t seed,
                                           uint64_t sample_offset, double *d_x, int64_t x_sample_stride, int64_t x_col_stride, double *d_jac,
                                           int32_t *d_cube, int32_t *d_cell, int64_t B, void *stream) {
-  const bool grouped = var_mask || n_group;               // neither: one jacobian, the full fold (polar without groups)
-  return vegas_sample_polar(d_grid, n_dim, n_grid, col, nullptr, 1, 0, nullptr, 0, nullptr, polar, n_polar, seed, sample_offset, d_x,
-                            x_sample_stride, x_col_stride, d_jac, nullptr, d_cell, B, stream, grouped, var_mask, n_group, jac_group_stride,
-                            true, strat, d_start, d_cube);
+  VegasSampleCall c;
+  c.polar = polar, c.n_polar = n_polar, c.takes_polar = true;
+  c.grouped = var_mask || n_group;                        // neither: one jacobian, the full fold (polar without groups)
+  c.var_mask = var_mask, c.n_group = n_group, c.jac_group_stride = jac_group_stride;
+  c.stratified = true, c.strat = strat, c.d_start = d_start, c.d_cube = d_cube;
+  return vegas_sample(d_grid, n_dim, n_grid, col, seed, sample_offset, d_x, x_sample_stride, x_col_stride, d_jac, d_cell, B, stream, c);
 }
 
 void fdg_sincos(double x, double *s, double *c) { fdg_sincos_impl(x, *s, *c); }
-
-int fdg_vegas_sample_device(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, uint64_t seed, uint64_t sample_offset,
-                            double *d_x, int64_t x_sample_stride, int64_t x_col_stride, double *d_jac, int32_t *d_cell, int64_t B,
-                            void *stream) {
-  const int rc = check_sampler(B, !d_grid || !d_x || !d_jac, n_dim, n_grid);
-  if (rc) return rc;
-  if (B == 0) return FDG_OK;
-  const long grid = std::min<long>(((long)B + 255) / 256, 256L * 16);
-  hipLaunchKernelGGL(fdg_vegas_sample, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, d_grid, n_dim, n_grid, vegas_cols(col, n_dim),
-                     seed, sample_offset, d_x, (long)x_sample_stride, (long)x_col_stride, d_jac, d_cell, (long)B);
-  HIP_TRY(hipGetLastError());
-  return FDG_OK;
-}
 
 // Lepage's refinement of the map from the training histogram; host only, fp64, in the order include/fdg.h states.
 int fdg_vegas_refine(double *grid, const double *hist, uint32_t n_dim, uint32_t n_grid, double alpha) {

@@ -4,7 +4,7 @@
 // route of fdg_eval_device / fdg_mc_eval_device, then fdg_chain_select per chunk: fold, accept rule, selection, measurement.  No
 // kernel here holds a per-lane array: the select kernel walks the root columns twice (fold, then select), the variables' factors
 // likewise, so n_root = 180 and n_dim = 64 cost loads, not registers.  Nothing here touches the kernels of fdg_binned.hip: the
-// sampler's arithmetic of one variable is restated below (chain_draw), the same operations in the same order, so the bits are its.
+// proposal calls the sampler's own statements of one variable, of the discrete pick and of the polar point (fdg_sampler.h), so the bits are its.
 //
 // All step entries run the one select kernel fdg_chain_select<MZ, BIN>.  It gives every group of roots the jacobian of its own
 // variables and a reweight factor: a' = sum_g rho_g |jac_g s_g| (fdg_[mc_]chain_step_device_grouped).  It walks the
@@ -32,12 +32,11 @@
 #define FDG_RUNTIME_TU 1
 #include "fdg_internal.h"
 #include "fdg_matsubara.h"
+#include "fdg_sampler.h"
 
 using namespace fdg;
 
 namespace {
-
-struct ChainCols { uint32_t c[FDG_VEGAS_DIM_MAX]; };      // the column of x each variable is written to (a kernel argument, by value)
 
 // The groups of a step (a kernel argument, by value): the live roots of group g are the entries start[g] .. start[g + 1] - 1
 // of the sorted lists, mask[g] its variables, rho[g] its reweight factor (read only where the call has one).
@@ -48,175 +47,97 @@ struct ChainGroups {
   double rho[FDG_WEIGHT_GROUP_MAX];
 };
 
-// Variable d of walker `sample` (a global index: the Philox counter) through the map: fdg_vegas_sample's statements for one variable.
-__device__ __forceinline__ double chain_draw(const double *__restrict__ grid, uint32_t d, uint32_t G, uint64_t sample, uint64_t seed, double &f) {
-  const double u = fdg_philox_u53(sample, d, seed);
-  const double y = u * (double)G;
-  const uint32_t c = min((uint32_t)(int)y, G - 1u);
-  const double *e = grid + (size_t)d * (G + 1u) + c;
-  const double lo = e[0], wd = e[1] - lo, fr = y - (double)c;
-  f = (double)G * wd;
-  return lo + fr * wd;
-}
-
-// xp, facp = the proposal of every walker: the variables of `mask` redrawn, everything else copied from x, fac.  A masked variable's
-// column is first copied and then overwritten by the same lane, in program order.
-__global__ void __launch_bounds__(256)
-fdg_chain_propose(const double *__restrict__ grid, uint32_t D, uint32_t G, ChainCols col, uint32_t n_col, uint64_t mask, uint64_t seed,
-                  uint64_t off, const double *__restrict__ x, long xc, const double *__restrict__ fac, double *__restrict__ xp, long xpc,
-                  double *__restrict__ facp, long n) {
-  const long b = blockIdx.x * 256L + threadIdx.x;
-  if (b >= n) return;
-  for (uint32_t c = 0; c < n_col; ++c) xp[(long)c * xpc + b] = x[(long)c * xc + b];
-  for (uint32_t d = 0; d < D; ++d) {
-    const size_t at = (size_t)d * (size_t)n + (size_t)b;
-    if ((mask >> d) & 1u) {
-      double f;
-      const double v = chain_draw(grid, d, G, off + (uint64_t)b, seed, f);
-      xp[(long)col.c[d] * xpc + b] = v;
-      facp[at] = f;
-    } else {
-      facp[at] = fac[at];
-    }
-  }
-}
-
-struct ChainExtCols { uint32_t c[FDG_VEGAS_EXT_MAX]; };   // the columns of x the rows of the discrete variable's table go to
-
-// fdg_chain_propose with the discrete variable behind the D continuous ones.  move: its uniform is the Philox column D, its value j the
-// number of interior edges of cdf that are <= u (fdg_vegas_sample_device_discrete's search), row j of ext goes to the columns ecol and
-// 1 / p_j to row D of facp; otherwise the value and its factor are copied (the columns ecol were copied with all the others).
-__global__ void __launch_bounds__(256)
-fdg_chain_propose_discrete(const double *__restrict__ grid, uint32_t D, uint32_t G, ChainCols col, uint32_t n_col, uint64_t mask, uint64_t seed,
-                           uint64_t off, const double *__restrict__ x, long xc, const double *__restrict__ fac, double *__restrict__ xp, long xpc,
-                           double *__restrict__ facp, uint32_t move, const double *__restrict__ cdf, uint32_t n_bin,
-                           const double *__restrict__ ext, uint32_t n_ext, ChainExtCols ecol, const int32_t *__restrict__ bin,
-                           int32_t *__restrict__ binp, long n) {
-  const long b = blockIdx.x * 256L + threadIdx.x;
-  if (b >= n) return;
-  for (uint32_t c = 0; c < n_col; ++c) xp[(long)c * xpc + b] = x[(long)c * xc + b];
-  for (uint32_t d = 0; d < D; ++d) {
-    const size_t at = (size_t)d * (size_t)n + (size_t)b;
-    if ((mask >> d) & 1u) {
-      double f;
-      const double v = chain_draw(grid, d, G, off + (uint64_t)b, seed, f);
-      xp[(long)col.c[d] * xpc + b] = v;
-      facp[at] = f;
-    } else {
-      facp[at] = fac[at];
-    }
-  }
-  const size_t at = (size_t)D * (size_t)n + (size_t)b;
-  if (move) {
-    const double u = fdg_philox_u53(off + (uint64_t)b, D, seed);
-    uint32_t lo = 0, hi = n_bin - 1u;                     // j in [lo, hi]: cdf[1 .. lo] <= u < cdf[hi + 1 ..]
-    while (lo < hi) {
-      const uint32_t mid = (lo + hi) >> 1;
-      if (cdf[mid + 1u] <= u) lo = mid + 1u; else hi = mid;
-    }
-    const double p = cdf[lo + 1u] - cdf[lo];
-    binp[b] = (int32_t)lo;
-    for (uint32_t e = 0; e < n_ext; ++e) xp[(long)ecol.c[e] * xpc + b] = ext[(size_t)lo * n_ext + e];
-    facp[at] = 1.0 / p;
-  } else {
-    binp[b] = bin[b];
-    facp[at] = fac[at];
-  }
-}
-
-// The groups of polar variables of fdg_chain_propose_polar (a kernel argument, by value; fdg_binned.hip's VegasPolar): group g takes the
-// variables var[g] .. var[g] + dim[g] - 1 and writes the Cartesian components to the columns col[g][0 .. dim[g]).  grouped: bit d set
-// = variable d belongs to a group.
-struct ChainPolar {
-  uint64_t grouped;
-  uint32_t n;
-  uint32_t var[FDG_VEGAS_POLAR_MAX], dim[FDG_VEGAS_POLAR_MAX];
-  uint32_t col[FDG_VEGAS_POLAR_MAX][3];
+// The discrete variable of a proposal (a kernel argument, by value; only the instances with one take it): move = redraw it, cdf and
+// the table ext [n_bin][n_ext] with its columns as the VEGAS sampler takes them, bin / binp its value in the state / the proposal.
+struct ChainDiscArgs {
+  uint32_t move;
+  const double *cdf;
+  uint32_t n_bin;
+  const double *ext;
+  uint32_t n_ext;
+  SamplerExtCols ecol;
+  const int32_t *bin;
+  int32_t *binp;
 };
 
-// fdg_chain_propose / fdg_chain_propose_discrete (cdf null: no discrete variable, fac and facp have D rows) with groups of variables
-// read as (k, phi) or (k, theta, phi) (fdg_chain_propose_device_polar).  The ungrouped variables first, by the plain
-// kernel's statements; then group by group, in the order of the array.  A group moves whole or not at all (the host has refused a mask
-// that names part of one: the bit of its first variable decides): moved, its two or three values are drawn on their own counters,
-// stay in registers, and give the group's columns and the measure's factors, each factor in the row of its own variable
+// xp, facp = the proposal of every walker, one lane per walker: the variables of `mask` redrawn through the map (vegas_draw, the
+// sampler's statements: the counter is the walker's global index), everything else copied from x, fac.  A redrawn variable's column is
+// first copied and then overwritten by the same lane, in program order.
+// POLAR: groups of variables read as (k, phi) or (k, theta, phi).  The ungrouped variables first; then group by group,
+// in the order of the array.  A group moves whole or not at all (the host has refused a mask that names part of one: the bit of its
+// first variable decides): moved, its two or three values are drawn on their own counters, stay in registers, and give the group's
+// columns and the measure's factors, each factor in the row of its own variable
 //     3D:  facp[var] = ((G wd_k) k) k,  facp[var + 1] = (G wd_theta) sin(theta),  facp[var + 2] = G wd_phi
 //     2D:  facp[var] = (G wd_k) k,      facp[var + 1] = G wd_phi
 // so that the select kernel's left fold over a mask is the jacobian of the polar measure with no change to it; kept, its rows of fac
 // are copied (its columns were copied with all the others).  No per-lane array, no LDS: everything indexed by g is wave-uniform.
+// DISC: the discrete variable behind the D continuous ones, fac and facp have the row D.  move: its value j by
+// discrete_pick, row j of ext to the columns ecol and 1 / p_j to row D of facp; otherwise the value and its factor are copied (the
+// columns ecol were copied with all the others).
+template <bool POLAR, bool DISC>
 __global__ void __launch_bounds__(256)
-fdg_chain_propose_polar(const double *__restrict__ grid, uint32_t D, uint32_t G, ChainCols col, uint32_t n_col, uint64_t mask, uint64_t seed,
-                        uint64_t off, const double *__restrict__ x, long xc, const double *__restrict__ fac, double *__restrict__ xp, long xpc,
-                        double *__restrict__ facp, ChainPolar pol, uint32_t move, const double *__restrict__ cdf, uint32_t n_bin,
-                        const double *__restrict__ ext, uint32_t n_ext, ChainExtCols ecol, const int32_t *__restrict__ bin,
-                        int32_t *__restrict__ binp, long n) {
+fdg_chain_propose(const double *__restrict__ grid, uint32_t D, uint32_t G, SamplerCols col, uint32_t n_col, uint64_t mask, uint64_t seed,
+                  uint64_t off, const double *__restrict__ x, long xc, const double *__restrict__ fac, double *__restrict__ xp, long xpc,
+                  double *__restrict__ facp, long n, ArgIf<POLAR, SamplerPolar> pol, ArgIf<DISC, ChainDiscArgs> da) {
   const long b = blockIdx.x * 256L + threadIdx.x;
   if (b >= n) return;
+  const uint64_t sample = off + (uint64_t)b;
   for (uint32_t c = 0; c < n_col; ++c) xp[(long)c * xpc + b] = x[(long)c * xc + b];
   for (uint32_t d = 0; d < D; ++d) {
-    if ((pol.grouped >> d) & 1u) continue;
+    if constexpr (POLAR) {
+      if ((pol.grouped >> d) & 1u) continue;
+    }
     const size_t at = (size_t)d * (size_t)n + (size_t)b;
     if ((mask >> d) & 1u) {
+      uint32_t c;
       double f;
-      const double v = chain_draw(grid, d, G, off + (uint64_t)b, seed, f);
+      const double v = vegas_draw(grid, d, G, sample, seed, 0, 1, c, f);
       xp[(long)col.c[d] * xpc + b] = v;
       facp[at] = f;
     } else {
       facp[at] = fac[at];
     }
   }
-  for (uint32_t g = 0; g < pol.n; ++g) {
-    const uint32_t var = pol.var[g];
-    const bool three = pol.dim[g] == 3;
-    const size_t at = (size_t)var * (size_t)n + (size_t)b;
-    if (!((mask >> var) & 1u)) {
-      facp[at] = fac[at];
-      facp[at + (size_t)n] = fac[at + (size_t)n];
-      if (three) facp[at + 2u * (size_t)n] = fac[at + 2u * (size_t)n];
-      continue;
-    }
-    double fk, fa;
-    const double k = chain_draw(grid, var, G, off + (uint64_t)b, seed, fk);
-    const double va = chain_draw(grid, var + 1u, G, off + (uint64_t)b, seed, fa);
-    if (three) {
-      double fp;
-      const double vp = chain_draw(grid, var + 2u, G, off + (uint64_t)b, seed, fp);
-      double st, ct, sp, cp;
-      fdg_sincos_impl(va, st, ct);
-      fdg_sincos_impl(vp, sp, cp);
-      const double ks = k * st;
-      xp[(long)pol.col[g][0] * xpc + b] = ks * cp;
-      xp[(long)pol.col[g][1] * xpc + b] = ks * sp;
-      xp[(long)pol.col[g][2] * xpc + b] = k * ct;
+  if constexpr (POLAR) {
+    for (uint32_t g = 0; g < pol.n; ++g) {
+      const uint32_t var = pol.var[g];
+      const bool three = pol.dim[g] == 3;
+      const size_t at = (size_t)var * (size_t)n + (size_t)b;
+      if (!((mask >> var) & 1u)) {
+        facp[at] = fac[at];
+        facp[at + (size_t)n] = fac[at + (size_t)n];
+        if (three) facp[at + 2u * (size_t)n] = fac[at + 2u * (size_t)n];
+        continue;
+      }
+      uint32_t c;
+      double fk, fa, fp = 0.0;
+      const double k = vegas_draw(grid, var, G, sample, seed, 0, 1, c, fk);
+      const double va = vegas_draw(grid, var + 1u, G, sample, seed, 0, 1, c, fa);      // theta, or phi in two dimensions
+      const double vp = three ? vegas_draw(grid, var + 2u, G, sample, seed, 0, 1, c, fp) : va;
+      double c0, c1, c2, st;
+      polar_point(three, k, va, vp, c0, c1, c2, st);
+      xp[(long)pol.col[g][0] * xpc + b] = c0;
+      xp[(long)pol.col[g][1] * xpc + b] = c1;
+      if (three) xp[(long)pol.col[g][2] * xpc + b] = c2;
       double f0 = fk * k;
-      f0 = f0 * k;
+      if (three) f0 = f0 * k;
       facp[at] = f0;
-      facp[at + (size_t)n] = fa * st;
-      facp[at + 2u * (size_t)n] = fp;
-    } else {
-      double sp, cp;
-      fdg_sincos_impl(va, sp, cp);
-      xp[(long)pol.col[g][0] * xpc + b] = k * cp;
-      xp[(long)pol.col[g][1] * xpc + b] = k * sp;
-      facp[at] = fk * k;
-      facp[at + (size_t)n] = fa;
+      facp[at + (size_t)n] = three ? fa * st : fa;
+      if (three) facp[at + 2u * (size_t)n] = fp;
     }
   }
-  if (!cdf) return;
-  const size_t at = (size_t)D * (size_t)n + (size_t)b;
-  if (move) {
-    const double u = fdg_philox_u53(off + (uint64_t)b, D, seed);
-    uint32_t lo = 0, hi = n_bin - 1u;                     // j in [lo, hi]: cdf[1 .. lo] <= u < cdf[hi + 1 ..]
-    while (lo < hi) {
-      const uint32_t mid = (lo + hi) >> 1;
-      if (cdf[mid + 1u] <= u) lo = mid + 1u; else hi = mid;
+  if constexpr (DISC) {
+    const size_t at = (size_t)D * (size_t)n + (size_t)b;
+    if (da.move) {
+      double p;
+      const uint32_t j = discrete_pick(da.cdf, da.n_bin, sample, D, seed, p);
+      da.binp[b] = (int32_t)j;
+      for (uint32_t e = 0; e < da.n_ext; ++e) xp[(long)da.ecol.c[e] * xpc + b] = da.ext[(size_t)j * da.n_ext + e];
+      facp[at] = 1.0 / p;
+    } else {
+      da.binp[b] = da.bin[b];
+      facp[at] = fac[at];
     }
-    const double p = cdf[lo + 1u] - cdf[lo];
-    binp[b] = (int32_t)lo;
-    for (uint32_t e = 0; e < n_ext; ++e) xp[(long)ecol.c[e] * xpc + b] = ext[(size_t)lo * n_ext + e];
-    facp[at] = 1.0 / p;
-  } else {
-    binp[b] = bin[b];
-    facp[at] = fac[at];
   }
 }
 
@@ -633,9 +554,30 @@ int chain_step(fdg_graph *g, const ChainCall &c, const ChainMc *mc, ChainEntry e
   return run_chain(g, c, mc, mz, cg);
 }
 
-// The checks of both propose calls, in one order; cols = the column of every variable.
-int check_propose(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, uint32_t n_col, uint64_t mask, const double *d_x,
-                  int64_t x_col_stride, const double *d_fac, double *d_xp, int64_t xp_col_stride, double *d_facp, int64_t B, ChainCols &cols) {
+// The discrete variable of a propose call as the host takes it; d_cdf null (fdg_chain_propose_device, or the polar entry without
+// one): none, and the rest is ignored.  required (fdg_chain_propose_device_discrete): d_cdf null is refused.
+struct ChainProposeDiscrete {
+  bool required;
+  int move;
+  const double *d_cdf;
+  uint32_t n_bin;
+  const double *d_ext;
+  uint32_t n_ext;
+  const uint32_t *ext_col;
+  const int32_t *d_bin;
+  int32_t *d_binp;
+};
+
+// Every fdg_chain_propose_device* entry: the checks in one order, then the instance of the proposal that reads what the call carries.
+// takes_polar (the _polar entry): every written column is to be named once.
+int chain_propose(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, uint32_t n_col, uint64_t mask, uint64_t seed,
+                  uint64_t sample_offset, const double *d_x, int64_t x_col_stride, const double *d_fac, double *d_xp, int64_t xp_col_stride,
+                  double *d_facp, int64_t B, void *stream, const ChainProposeDiscrete &dv, bool takes_polar, const fdg_vegas_polar *polar,
+                  uint32_t n_polar) {
+  // The groups first, for pol.grouped: the col entry of a grouped variable is not read, and 0 stands in for it in the checks below.
+  // A refusal of theirs is returned at its own rank, behind those checks; nothing sets a message in between unless it refuses.
+  SamplerPolar pol;
+  const int rc_polar = parse_polar(polar, n_polar, n_dim, n_col, pol);
   if (B < 0) { set_error("n_walker < 0"); return FDG_E_INVALID; }
   if (!d_grid || !d_x || !d_fac || !d_xp || !d_facp) { set_error("null device buffer"); return FDG_E_INVALID; }
   if (n_dim == 0 || n_grid == 0) { set_error("n_dim == 0 or n_grid == 0"); return FDG_E_INVALID; }
@@ -644,62 +586,45 @@ int check_propose(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const u
   if (d_x == d_xp || d_fac == d_facp) { set_error("the state and the proposal are the same buffer"); return FDG_E_INVALID; }
   if (n_dim < 64 && (mask >> n_dim)) { set_error("mask names a variable >= n_dim"); return FDG_E_INVALID; }
   if (x_col_stride < B || xp_col_stride < B) { set_error("a column stride < n_walker"); return FDG_E_INVALID; }
-  for (uint32_t d = 0; d < FDG_VEGAS_DIM_MAX; ++d) cols.c[d] = d < n_dim ? (col ? col[d] : d) : 0u;
+  const SamplerCols cols = sampler_cols(col, n_dim, pol.grouped);
   for (uint32_t d = 0; d < n_dim; ++d)
     if (cols.c[d] >= n_col) { set_error("col names a column >= n_col"); return FDG_E_INVALID; }
-  return FDG_OK;
-}
-
-// The checks of the discrete variable's arguments in the propose calls that take one, after check_propose, in one order; ecols = the
-// columns of its table.  skip: bit d set = col[d] is not read (a variable of a polar group).
-int check_propose_discrete(uint32_t n_dim, const ChainCols &cols, uint64_t skip, uint32_t n_col, const double *d_cdf, uint32_t n_bin,
-                           const double *d_ext, uint32_t n_ext, const uint32_t *ext_col, const int32_t *d_bin, const int32_t *d_binp,
-                           ChainExtCols &ecols) {
-  if (n_dim == FDG_VEGAS_DIM_MAX) { set_error("n_dim == FDG_VEGAS_DIM_MAX: the discrete variable's counter is the accept rule's"); return FDG_E_UNSUPPORTED; }
-  if (!d_cdf || !d_bin || !d_binp) { set_error("null device buffer"); return FDG_E_INVALID; }
-  if (d_bin == d_binp) { set_error("d_bin and d_binp are the same buffer"); return FDG_E_INVALID; }
-  if (n_bin == 0) { set_error("n_bin == 0"); return FDG_E_INVALID; }
-  if (n_bin > FDG_CHAIN_BIN_MAX) { set_error("n_bin > FDG_CHAIN_BIN_MAX"); return FDG_E_UNSUPPORTED; }
-  if (n_ext > FDG_VEGAS_EXT_MAX) { set_error("n_ext > FDG_VEGAS_EXT_MAX"); return FDG_E_UNSUPPORTED; }
-  if (n_ext && (!d_ext || !ext_col)) { set_error("n_ext > 0 needs d_ext and ext_col"); return FDG_E_INVALID; }
-  for (uint32_t e = 0; e < FDG_VEGAS_EXT_MAX; ++e) ecols.c[e] = e < n_ext ? ext_col[e] : 0u;
-  for (uint32_t e = 0; e < n_ext; ++e) {
-    if (ecols.c[e] >= n_col) { set_error("ext_col names a column >= n_col"); return FDG_E_INVALID; }
-    for (uint32_t f = 0; f < e; ++f)
-      if (ecols.c[f] == ecols.c[e]) { set_error("ext_col names a column twice"); return FDG_E_INVALID; }
-    for (uint32_t d = 0; d < n_dim; ++d)
-      if (!((skip >> d) & 1u) && cols.c[d] == ecols.c[e]) { set_error("ext_col names a column of col"); return FDG_E_INVALID; }
+  const bool discrete = dv.required || dv.d_cdf;
+  ChainDiscArgs da = {};
+  if (discrete) {
+    if (n_dim == FDG_VEGAS_DIM_MAX) { set_error("n_dim == FDG_VEGAS_DIM_MAX: the discrete variable's counter is the accept rule's"); return FDG_E_UNSUPPORTED; }
+    if (!dv.d_cdf || !dv.d_bin || !dv.d_binp) { set_error("null device buffer"); return FDG_E_INVALID; }
+    if (dv.d_bin == dv.d_binp) { set_error("d_bin and d_binp are the same buffer"); return FDG_E_INVALID; }
+    da = ChainDiscArgs{dv.move ? 1u : 0u, dv.d_cdf, dv.n_bin, dv.d_ext, dv.n_ext, {}, dv.d_bin, dv.d_binp};
+    int rc = check_discrete_table(dv.n_bin, FDG_CHAIN_BIN_MAX, "FDG_CHAIN_BIN_MAX", dv.d_ext, dv.n_ext, dv.ext_col, da.ecol);
+    if (!rc) rc = check_ext_cols(da.ecol, dv.n_ext, cols, n_dim, pol.grouped, n_col);
+    if (rc) return rc;
   }
+  if (rc_polar) return rc_polar;
+  if (takes_polar) {
+    const int rc = check_cols_once(cols, n_dim, pol, da.ecol, da.n_ext);
+    if (rc) return rc;
+  }
+  for (uint32_t g = 0; g < pol.n; ++g) {
+    const uint64_t bits = ((1ull << pol.dim[g]) - 1ull) << pol.var[g], has = mask & bits;
+    if (has && has != bits) { set_error("mask names some but not all variables of a polar group"); return FDG_E_INVALID; }
+  }
+  if (B == 0) return FDG_OK;
+  with_flag(pol.n != 0, [&](auto p) {
+    with_flag(discrete, [&](auto d) {
+      constexpr bool P = decltype(p)::value, Dc = decltype(d)::value;
+      hipLaunchKernelGGL((fdg_chain_propose<P, Dc>), dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_grid, n_dim, n_grid,
+                         cols, n_col, mask, seed, sample_offset, d_x, (long)x_col_stride, d_fac, d_xp, (long)xp_col_stride, d_facp, (long)B,
+                         arg_if<P>(pol), arg_if<Dc>(da));
+    });
+  });
+  HIP_TRY(hipGetLastError());
   return FDG_OK;
-}
-
-// The variables that the groups of `polar` hold, as far as the groups are well formed (dim 2 or 3, inside n_dim): what the checks
-// that run before the groups' own need, since the col entry of a grouped variable is not read.
-uint64_t polar_vars(const fdg_vegas_polar *polar, uint32_t n_polar, uint32_t n_dim) {
-  uint64_t grouped = 0;
-  if (!polar) return 0;
-  for (uint32_t g = 0; g < std::min<uint32_t>(n_polar, FDG_VEGAS_POLAR_MAX); ++g)
-    if ((polar[g].dim == 2 || polar[g].dim == 3) && polar[g].var < n_dim && polar[g].var + polar[g].dim <= n_dim)
-      grouped |= ((1ull << polar[g].dim) - 1ull) << polar[g].var;
-  return grouped;
 }
 
 }  // namespace
 
 extern "C" {
-
-int fdg_chain_propose_device(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, uint32_t n_col, uint64_t mask,
-                             uint64_t seed, uint64_t sample_offset, const double *d_x, int64_t x_col_stride, const double *d_fac,
-                             double *d_xp, int64_t xp_col_stride, double *d_facp, int64_t B, void *stream) {
-  ChainCols cols;
-  const int rc = check_propose(d_grid, n_dim, n_grid, col, n_col, mask, d_x, x_col_stride, d_fac, d_xp, xp_col_stride, d_facp, B, cols);
-  if (rc) return rc;
-  if (B == 0) return FDG_OK;
-  hipLaunchKernelGGL(fdg_chain_propose, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_grid, n_dim, n_grid, cols, n_col,
-                     mask, seed, sample_offset, d_x, (long)x_col_stride, d_fac, d_xp, (long)xp_col_stride, d_facp, (long)B);
-  HIP_TRY(hipGetLastError());
-  return FDG_OK;
-}
 
 int fdg_chain_step_device(fdg_graph *g, const double *d_xp, int64_t xp_col_stride, const double *d_facp, uint32_t n_col, uint32_t n_dim,
                           const double *coef, double gamma, uint64_t seed, uint64_t sample_offset, unsigned flags, double *d_x,
@@ -761,23 +686,20 @@ int fdg_mc_chain_step_device_grouped(fdg_graph *g, const double *d_xp, int64_t x
   return chain_step(g, c, &mc, CHAIN_GROUPED, mz, cg);
 }
 
+int fdg_chain_propose_device(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, uint32_t n_col, uint64_t mask,
+                             uint64_t seed, uint64_t sample_offset, const double *d_x, int64_t x_col_stride, const double *d_fac,
+                             double *d_xp, int64_t xp_col_stride, double *d_facp, int64_t B, void *stream) {
+  return chain_propose(d_grid, n_dim, n_grid, col, n_col, mask, seed, sample_offset, d_x, x_col_stride, d_fac, d_xp, xp_col_stride, d_facp, B,
+                       stream, ChainProposeDiscrete{}, false, nullptr, 0);
+}
+
 int fdg_chain_propose_device_discrete(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, uint32_t n_col,
                                       uint64_t mask, uint64_t seed, uint64_t sample_offset, const double *d_x, int64_t x_col_stride,
                                       const double *d_fac, double *d_xp, int64_t xp_col_stride, double *d_facp, int move_discrete,
                                       const double *d_cdf, uint32_t n_bin, const double *d_ext, uint32_t n_ext, const uint32_t *ext_col,
                                       const int32_t *d_bin, int32_t *d_binp, int64_t B, void *stream) {
-  ChainCols cols;
-  const int rc = check_propose(d_grid, n_dim, n_grid, col, n_col, mask, d_x, x_col_stride, d_fac, d_xp, xp_col_stride, d_facp, B, cols);
-  if (rc) return rc;
-  ChainExtCols ecols;
-  const int rd = check_propose_discrete(n_dim, cols, 0, n_col, d_cdf, n_bin, d_ext, n_ext, ext_col, d_bin, d_binp, ecols);
-  if (rd) return rd;
-  if (B == 0) return FDG_OK;
-  hipLaunchKernelGGL(fdg_chain_propose_discrete, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_grid, n_dim, n_grid,
-                     cols, n_col, mask, seed, sample_offset, d_x, (long)x_col_stride, d_fac, d_xp, (long)xp_col_stride, d_facp,
-                     move_discrete ? 1u : 0u, d_cdf, n_bin, d_ext, n_ext, ecols, d_bin, d_binp, (long)B);
-  HIP_TRY(hipGetLastError());
-  return FDG_OK;
+  return chain_propose(d_grid, n_dim, n_grid, col, n_col, mask, seed, sample_offset, d_x, x_col_stride, d_fac, d_xp, xp_col_stride, d_facp, B,
+                       stream, ChainProposeDiscrete{true, move_discrete, d_cdf, n_bin, d_ext, n_ext, ext_col, d_bin, d_binp}, false, nullptr, 0);
 }
 
 int fdg_chain_propose_device_polar(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, uint32_t n_col, uint64_t mask,
@@ -785,56 +707,9 @@ int fdg_chain_propose_device_polar(const double *d_grid, uint32_t n_dim, uint32_
                                    double *d_xp, int64_t xp_col_stride, double *d_facp, int move_discrete, const double *d_cdf,
                                    uint32_t n_bin, const double *d_ext, uint32_t n_ext, const uint32_t *ext_col, const int32_t *d_bin,
                                    int32_t *d_binp, const fdg_vegas_polar *polar, uint32_t n_polar, int64_t B, void *stream) {
-  // the col entry of a grouped variable is not read: 0 stands in for it in the checks that come before the groups' own
-  const uint64_t skip = polar_vars(polar, n_polar, n_dim);
-  uint32_t lcol[FDG_VEGAS_DIM_MAX];
-  for (uint32_t d = 0; d < std::min<uint32_t>(n_dim, FDG_VEGAS_DIM_MAX); ++d) lcol[d] = ((skip >> d) & 1u) ? 0u : (col ? col[d] : d);
-  ChainCols cols;
-  int rc = check_propose(d_grid, n_dim, n_grid, lcol, n_col, mask, d_x, x_col_stride, d_fac, d_xp, xp_col_stride, d_facp, B, cols);
-  if (rc) return rc;
-  ChainExtCols ecols = {};
-  if (d_cdf) {
-    rc = check_propose_discrete(n_dim, cols, skip, n_col, d_cdf, n_bin, d_ext, n_ext, ext_col, d_bin, d_binp, ecols);
-    if (rc) return rc;
-  } else {
-    n_bin = 1, n_ext = 0;                                  // no discrete variable: its arguments are ignored
-  }
-  if (n_polar > FDG_VEGAS_POLAR_MAX) { set_error("n_polar > FDG_VEGAS_POLAR_MAX"); return FDG_E_UNSUPPORTED; }
-  if (n_polar && !polar) { set_error("n_polar > 0 needs polar"); return FDG_E_INVALID; }
-  ChainPolar pol = {};
-  pol.n = n_polar;
-  for (uint32_t g = 0; g < n_polar; ++g) {
-    if (polar[g].dim != 2 && polar[g].dim != 3) { set_error("a polar group has 2 or 3 variables"); return FDG_E_INVALID; }
-    if (polar[g].var >= n_dim || polar[g].var + polar[g].dim > n_dim) { set_error("a polar group reaches past n_dim"); return FDG_E_INVALID; }
-    const uint64_t bits = ((1ull << polar[g].dim) - 1ull) << polar[g].var;
-    if (pol.grouped & bits) { set_error("two polar groups share a variable"); return FDG_E_INVALID; }
-    pol.grouped |= bits;
-    pol.var[g] = polar[g].var;
-    pol.dim[g] = polar[g].dim;
-    for (uint32_t i = 0; i < polar[g].dim; ++i) pol.col[g][i] = polar[g].col[i];
-  }
-  // every column written once: the variables of no group, the groups' components, the discrete variable's table
-  std::vector<uint32_t> named;
-  for (uint32_t d = 0; d < n_dim; ++d)
-    if (!((pol.grouped >> d) & 1u)) named.push_back(cols.c[d]);
-  for (uint32_t g = 0; g < n_polar; ++g)
-    for (uint32_t i = 0; i < pol.dim[g]; ++i) {
-      if (pol.col[g][i] >= n_col) { set_error("a polar group names a column >= n_col"); return FDG_E_INVALID; }
-      named.push_back(pol.col[g][i]);
-    }
-  named.insert(named.end(), ecols.c, ecols.c + n_ext);
-  std::sort(named.begin(), named.end());
-  if (std::adjacent_find(named.begin(), named.end()) != named.end()) { set_error("a column of x is named twice"); return FDG_E_INVALID; }
-  for (uint32_t g = 0; g < n_polar; ++g) {
-    const uint64_t bits = ((1ull << pol.dim[g]) - 1ull) << pol.var[g], has = mask & bits;
-    if (has && has != bits) { set_error("mask names some but not all variables of a polar group"); return FDG_E_INVALID; }
-  }
-  if (B == 0) return FDG_OK;
-  hipLaunchKernelGGL(fdg_chain_propose_polar, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_grid, n_dim, n_grid, cols,
-                     n_col, mask, seed, sample_offset, d_x, (long)x_col_stride, d_fac, d_xp, (long)xp_col_stride, d_facp, pol,
-                     move_discrete ? 1u : 0u, d_cdf, n_bin, d_ext, n_ext, ecols, d_bin, d_binp, (long)B);
-  HIP_TRY(hipGetLastError());
-  return FDG_OK;
+  return chain_propose(d_grid, n_dim, n_grid, col, n_col, mask, seed, sample_offset, d_x, x_col_stride, d_fac, d_xp, xp_col_stride, d_facp, B,
+                       stream, ChainProposeDiscrete{false, move_discrete, d_cdf, n_bin, d_ext, n_ext, ext_col, d_bin, d_binp}, true, polar,
+                       n_polar);
 }
 
 int fdg_chain_step_device_binned(fdg_graph *g,const double *d_xp, int64_t xp_col_stride, const double *d_facp, uint32_t n_col,
