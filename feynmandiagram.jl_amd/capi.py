@@ -58,7 +58,7 @@ EXPORTS = [
     "fdg_chain_step_device_matsubara", "fdg_mc_chain_step_device_matsubara",
     "fdg_chain_step_device_grouped", "fdg_mc_chain_step_device_grouped",
     "fdg_chain_propose_device_discrete", "fdg_chain_step_device_binned", "fdg_mc_chain_step_device_binned",
-    "fdg_chain_propose_device_polar",
+    "fdg_chain_propose_device_polar", "fdg_chain_propose_device_local",
 ]
 FDG_BIN_MAX = 16384     # fdg_accumulate_device_binned: largest n_bin
 FDG_VEGAS_DIM_MAX, FDG_VEGAS_GRID_MAX = 64, 1024     # the VEGAS map: most variables, most cells per variable
@@ -328,6 +328,8 @@ def lib():
     L.fdg_chain_step_device_binned.argtypes = L.fdg_chain_step_device.argtypes[:-2] + [C.c_void_p, C.c_void_p, u32, vp, vp, i64, vp]
     L.fdg_mc_chain_step_device_binned.argtypes = L.fdg_mc_chain_step_device.argtypes[:-2] + [C.c_void_p, C.c_void_p, u32, vp, vp, i64, vp]
     L.fdg_chain_propose_device_polar.argtypes = L.fdg_chain_propose_device_discrete.argtypes[:-2] + [C.c_void_p, u32, i64, vp]
+    L.fdg_chain_propose_device_local.argtypes = (L.fdg_chain_propose_device_polar.argtypes[:6] + [u64, C.c_void_p]
+                                                 + L.fdg_chain_propose_device_polar.argtypes[6:])
     L.fdg_powi.argtypes = [C.c_double, C.c_int32]
     L.fdg_powi.restype = C.c_double
     _lib = L
@@ -991,6 +993,104 @@ def chain_propose_polar_reference(grid, col, polar, state, mask: int, u, cdf=Non
             binp = jp.astype(np.int32)
             for e, c in enumerate(ext_col):
                 xp[int(c)] = np.asarray(ext, dtype=np.float64)[jp, e]
+    return xp, facp, binp
+
+
+def _width_arg(width, n_dim: int, local_mask: int):
+    """The ``width`` argument of the shifted proposal as a float64 array ``[n_dim]`` (a scalar stands for every variable), or None
+    where no variable is shifted and none is given."""
+    if width is None:
+        if local_mask:
+            raise ValueError("a shift mask needs width")
+        return None
+    w = np.asarray(width, dtype=np.float64)
+    w = np.full(n_dim, float(w)) if w.ndim == 0 else np.ascontiguousarray(w)
+    if w.shape != (n_dim,):
+        raise ValueError("width must be one number or one per variable")
+    return w
+
+
+def chain_propose_device_local(d_grid: int, n_dim: int, n_grid: int, col, n_col: int, mask: int, local_mask: int, width, seed: int,
+                               sample_offset: int, d_x: int, xc: int, d_fac: int, d_xp: int, xpc: int, d_facp: int, move_discrete: bool = False,
+                               d_cdf: int = 0, n_bin: int = 0, d_ext: int = 0, ext_col=None, d_bin: int = 0, d_binp: int = 0, polar=(),
+                               B: int = 0, stream: int = 0):
+    """fdg_chain_propose_device_local: :func:`chain_propose_device_polar` with the variables of ``local_mask`` SHIFTED in the map's
+    coordinate, ``y' = y + t h (mod 1)`` with ``t`` uniform in ``[-1, 1)`` on the counter a redraw of the variable would use and
+    ``h = width[d]`` in ``(0, 0.5]`` (``width``: a host sequence of ``n_dim`` numbers, or one number for all; read only where
+    ``local_mask`` has a bit).  ``mask`` and ``local_mask`` share no bit.  Only variables of no polar group can be shifted; the groups
+    and the discrete variable are redrawn or kept.  ``local_mask = 0`` is :func:`chain_propose_device_polar` bit for bit."""
+    c = _col_arg(col, n_dim, none_ok=True)
+    ec = _ext_col_arg(ext_col)
+    arr, n_polar = _polar_array(polar)
+    w = _width_arg(width, n_dim, local_mask)
+    check(lib().fdg_chain_propose_device_local(d_grid or None, n_dim, n_grid, None if c is None else c.ctypes.data, n_col, mask, local_mask,
+                                               None if w is None else w.ctypes.data, seed, sample_offset, d_x or None, xc, d_fac or None,
+                                               d_xp or None, xpc, d_facp or None, 1 if move_discrete else 0, d_cdf or None, n_bin,
+                                               d_ext or None, ec.shape[0], ec.ctypes.data if ec.shape[0] else None, d_bin or None,
+                                               d_binp or None, C.addressof(arr) if n_polar else None, n_polar, B, stream))
+
+
+def vegas_invert_reference(grid, d: int, xv):
+    """The inverse of the map for variable ``d`` restated in numpy, in the device's fp64 order (include/fdg.h, "Markov chain with local
+    shift moves"): ``(c, fr)`` of the values ``xv``, with ``yy = c + fr`` the coordinate in cells.  ``c`` is the number of interior
+    edges ``<= xv``; ``fr`` is clamped into ``[0, 1]``, 0 for a cell without width and for a nan."""
+    e = np.asarray(grid, dtype=np.float64)[d]
+    G = e.shape[0] - 1
+    xv = np.asarray(xv, dtype=np.float64)
+    c = np.searchsorted(e[1:G], xv, side="right")            # the number of interior edges <= xv (a nan sorts behind them all ...)
+    c = np.where(np.isnan(xv), 0, c)                         # ... but compares false with every edge on the device
+    lo = e[c]
+    wd = e[c + 1] - lo
+    with np.errstate(all="ignore"):
+        fr = (xv - lo) / wd
+    fr = np.where((wd == 0.0) | ~(fr >= 0.0), 0.0, fr)
+    fr = np.where(fr > 1.0, 1.0, fr)
+    return c, fr
+
+
+def chain_propose_local_reference(grid, col, polar, state, mask: int, local_mask: int, width, u, cdf=None, ext=None, ext_col=(),
+                                  move_discrete: bool = False, u_disc=None, sincos=None):
+    """fdg_chain_propose_device_local restated in numpy, in the device's fp64 order: :func:`chain_propose_polar_reference` for ``mask``,
+    the groups and the discrete variable, then every variable of ``local_mask`` shifted from the state's value: the inverse of the map
+    (:func:`vegas_invert_reference`), ``y1 = yy + ((u + u) - 1) * (width[d] * G)`` wrapped once into ``[0, G)``, the map again.
+    ``u [B, D]`` holds the uniforms of the counters ``(sample_offset + b, d)``; the columns of ``mask`` and of ``local_mask`` are read.
+    ``width``: one number or one per variable.  The step mirrors take the result as their ``proposal``, so stepping through
+    :func:`chain_grouped_reference` or :func:`chain_binned_reference` works unchanged behind it."""
+    grid = np.asarray(grid, dtype=np.float64)
+    D, G = grid.shape[0], grid.shape[1] - 1
+    mask, local_mask = int(mask), int(local_mask)
+    if local_mask >> D:
+        raise ValueError("local_mask names a variable >= n_dim")
+    if mask & local_mask:
+        raise ValueError("mask and local_mask name the same variable")
+    for var, cols in (polar or ()):
+        if local_mask & (((1 << len(cols)) - 1) << int(var)):
+            raise ValueError("local_mask names a variable of a polar group")
+    xp, facp, binp = chain_propose_polar_reference(grid, col, polar, state, mask, u, cdf, ext, ext_col, move_discrete, u_disc, sincos)
+    if not local_mask:
+        return xp, facp, binp
+    w = _width_arg(width, D, local_mask)
+    x = np.asarray(state["x"], dtype=np.float64)
+    cols_of = list(range(D)) if col is None else [None if c is None else int(c) for c in col]
+    g = np.float64(G)
+    for d in range(D):
+        if not (local_mask >> d) & 1:
+            continue
+        if not (np.isfinite(w[d]) and 0.0 < w[d] <= 0.5):
+            raise ValueError("a width of a shifted variable is not in (0, 0.5]")
+        hG = w[d] * g
+        c, fr = vegas_invert_reference(grid, d, x[cols_of[d]])
+        yy = c.astype(np.float64) + fr
+        ud = np.asarray(u, dtype=np.float64)[:, d]
+        t = (ud + ud) - 1.0
+        y1 = yy + t * hG
+        y1 = np.where(y1 < 0.0, y1 + g, y1)
+        y1 = np.where(y1 >= g, y1 - g, y1)
+        c1 = np.minimum(y1.astype(np.int64), G - 1)
+        lo = grid[d, c1]
+        wd = grid[d, c1 + 1] - lo
+        xp[cols_of[d]] = lo + (y1 - c1.astype(np.float64)) * wd
+        facp[d] = g * wd
     return xp, facp, binp
 
 

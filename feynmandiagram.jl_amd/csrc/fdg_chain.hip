@@ -22,6 +22,10 @@
 // variable behind the continuous ones: its value in bin / binp, its factor 1 / p_j in row n_dim of fac / facp.  Every group's jacobian
 // takes that factor as its last product, and a walker measures into the columns of its own bin through a row address of its own:
 // no loop over the bins, nothing multiplied by zero, every word still one lane's.
+//
+// Local moves (fdg_chain_propose_device_local) are a matter of the proposal alone: in the map's uniform coordinate y the
+// stationary density is a + gamma, so the select kernel's rule is the Metropolis rule of every proposal that is symmetric in y, and
+// a shift y' = y + t h (mod 1) is one.  The proposal kernel has an instance that shifts; no step, select or reduce kernel changes.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -60,6 +64,13 @@ struct ChainDiscArgs {
   int32_t *binp;
 };
 
+// The shifted variables of a proposal (a kernel argument, by value; only the instances with one take it): mask = the variables moved by
+// a shift in the map's coordinate, hG[d] = width[d] * n_grid the half width of variable d's shift in cells.
+struct ChainLocalArgs {
+  uint64_t mask;
+  double hG[FDG_VEGAS_DIM_MAX];
+};
+
 // xp, facp = the proposal of every walker, one lane per walker: the variables of `mask` redrawn through the map (vegas_draw, the
 // sampler's statements: the counter is the walker's global index), everything else copied from x, fac.  A redrawn variable's column is
 // first copied and then overwritten by the same lane, in program order.
@@ -74,11 +85,16 @@ struct ChainDiscArgs {
 // DISC: the discrete variable behind the D continuous ones, fac and facp have the row D.  move: its value j by
 // discrete_pick, row j of ext to the columns ecol and 1 / p_j to row D of facp; otherwise the value and its factor are copied (the
 // columns ecol were copied with all the others).
-template <bool POLAR, bool DISC>
+// LOCAL: a variable of no group whose bit is set in loc.mask, and not in mask, is SHIFTED in the map's coordinate
+// (vegas_shift: the inverse of the map at the state's value, y' = y + t h mod 1, the map again), on the Philox column a redraw of it
+// would use.  loc.hG[d] = width[d] * G is read only for those variables; d is wave-uniform, so it is a scalar load of the argument.
+// The discrete variable and the polar groups are only ever redrawn: the state holds Cartesian columns and no (k, theta, phi).
+template <bool POLAR, bool DISC, bool LOCAL>
 __global__ void __launch_bounds__(256)
 fdg_chain_propose(const double *__restrict__ grid, uint32_t D, uint32_t G, SamplerCols col, uint32_t n_col, uint64_t mask, uint64_t seed,
                   uint64_t off, const double *__restrict__ x, long xc, const double *__restrict__ fac, double *__restrict__ xp, long xpc,
-                  double *__restrict__ facp, long n, ArgIf<POLAR, SamplerPolar> pol, ArgIf<DISC, ChainDiscArgs> da) {
+                  double *__restrict__ facp, long n, ArgIf<POLAR, SamplerPolar> pol, ArgIf<DISC, ChainDiscArgs> da,
+                  ArgIf<LOCAL, ChainLocalArgs> loc) {
   const long b = blockIdx.x * 256L + threadIdx.x;
   if (b >= n) return;
   const uint64_t sample = off + (uint64_t)b;
@@ -95,6 +111,15 @@ fdg_chain_propose(const double *__restrict__ grid, uint32_t D, uint32_t G, Sampl
       xp[(long)col.c[d] * xpc + b] = v;
       facp[at] = f;
     } else {
+      if constexpr (LOCAL) {
+        if ((loc.mask >> d) & 1u) {
+          double f;
+          const double v = vegas_shift(grid, d, G, sample, seed, loc.hG[d], x[(long)col.c[d] * xc + b], f);
+          xp[(long)col.c[d] * xpc + b] = v;
+          facp[at] = f;
+          continue;
+        }
+      }
       facp[at] = fac[at];
     }
   }
@@ -573,7 +598,7 @@ struct ChainProposeDiscrete {
 int chain_propose(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, uint32_t n_col, uint64_t mask, uint64_t seed,
                   uint64_t sample_offset, const double *d_x, int64_t x_col_stride, const double *d_fac, double *d_xp, int64_t xp_col_stride,
                   double *d_facp, int64_t B, void *stream, const ChainProposeDiscrete &dv, bool takes_polar, const fdg_vegas_polar *polar,
-                  uint32_t n_polar) {
+                  uint32_t n_polar, uint64_t local_mask = 0, const double *width = nullptr) {
   // The groups first, for pol.grouped: the col entry of a grouped variable is not read, and 0 stands in for it in the checks below.
   // A refusal of theirs is returned at its own rank, behind those checks; nothing sets a message in between unless it refuses.
   SamplerPolar pol;
@@ -609,13 +634,31 @@ int chain_propose(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const u
     const uint64_t bits = ((1ull << pol.dim[g]) - 1ull) << pol.var[g], has = mask & bits;
     if (has && has != bits) { set_error("mask names some but not all variables of a polar group"); return FDG_E_INVALID; }
   }
+  // the shifted variables (fdg_chain_propose_device_local), behind everything the other entries refuse
+  ChainLocalArgs loc = {};
+  if (local_mask) {
+    if (n_dim < 64 && (local_mask >> n_dim)) { set_error("local_mask names a variable >= n_dim"); return FDG_E_INVALID; }
+    if (mask & local_mask) { set_error("mask and local_mask name the same variable: it is redrawn or shifted, not both"); return FDG_E_INVALID; }
+    if (local_mask & pol.grouped) {
+      set_error("local_mask names a variable of a polar group: the state does not hold (k, theta, phi)"); return FDG_E_UNSUPPORTED;
+    }
+    if (!width) { set_error("local_mask != 0 needs width"); return FDG_E_INVALID; }
+    loc.mask = local_mask;
+    for (uint32_t d = 0; d < n_dim; ++d) {
+      if (!((local_mask >> d) & 1u)) continue;
+      if (!(std::isfinite(width[d]) && width[d] > 0.0 && width[d] <= 0.5)) { set_error("a width of a shifted variable is not in (0, 0.5]"); return FDG_E_INVALID; }
+      loc.hG[d] = width[d] * (double)n_grid;
+    }
+  }
   if (B == 0) return FDG_OK;
   with_flag(pol.n != 0, [&](auto p) {
     with_flag(discrete, [&](auto d) {
-      constexpr bool P = decltype(p)::value, Dc = decltype(d)::value;
-      hipLaunchKernelGGL((fdg_chain_propose<P, Dc>), dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_grid, n_dim, n_grid,
-                         cols, n_col, mask, seed, sample_offset, d_x, (long)x_col_stride, d_fac, d_xp, (long)xp_col_stride, d_facp, (long)B,
-                         arg_if<P>(pol), arg_if<Dc>(da));
+      with_flag(local_mask != 0, [&](auto l) {
+        constexpr bool P = decltype(p)::value, Dc = decltype(d)::value, Lc = decltype(l)::value;
+        hipLaunchKernelGGL((fdg_chain_propose<P, Dc, Lc>), dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_grid, n_dim,
+                           n_grid, cols, n_col, mask, seed, sample_offset, d_x, (long)x_col_stride, d_fac, d_xp, (long)xp_col_stride, d_facp,
+                           (long)B, arg_if<P>(pol), arg_if<Dc>(da), arg_if<Lc>(loc));
+      });
     });
   });
   HIP_TRY(hipGetLastError());
@@ -710,6 +753,17 @@ int fdg_chain_propose_device_polar(const double *d_grid, uint32_t n_dim, uint32_
   return chain_propose(d_grid, n_dim, n_grid, col, n_col, mask, seed, sample_offset, d_x, x_col_stride, d_fac, d_xp, xp_col_stride, d_facp, B,
                        stream, ChainProposeDiscrete{false, move_discrete, d_cdf, n_bin, d_ext, n_ext, ext_col, d_bin, d_binp}, true, polar,
                        n_polar);
+}
+
+int fdg_chain_propose_device_local(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, uint32_t n_col, uint64_t mask,
+                                   uint64_t local_mask, const double *width, uint64_t seed, uint64_t sample_offset, const double *d_x,
+                                   int64_t x_col_stride, const double *d_fac, double *d_xp, int64_t xp_col_stride, double *d_facp,
+                                   int move_discrete, const double *d_cdf, uint32_t n_bin, const double *d_ext, uint32_t n_ext,
+                                   const uint32_t *ext_col, const int32_t *d_bin, int32_t *d_binp, const fdg_vegas_polar *polar, uint32_t n_polar,
+                                   int64_t B, void *stream) {
+  return chain_propose(d_grid, n_dim, n_grid, col, n_col, mask, seed, sample_offset, d_x, x_col_stride, d_fac, d_xp, xp_col_stride, d_facp, B,
+                       stream, ChainProposeDiscrete{false, move_discrete, d_cdf, n_bin, d_ext, n_ext, ext_col, d_bin, d_binp}, true, polar,
+                       n_polar, local_mask, width);
 }
 
 int fdg_chain_step_device_binned(fdg_graph *g,const double *d_xp, int64_t xp_col_stride, const double *d_facp, uint32_t n_col,

@@ -1,5 +1,5 @@
 // What the VEGAS samplers (fdg_binned.hip) and the chain's proposals (fdg_chain.hip) share, written once: the by-value kernel arguments,
-// the device statements of one variable, of the discrete pick, of the hypercube search and of the polar point, and the host checks of
+// the device statements of one variable (drawn, inverted, shifted), of the discrete pick, of the hypercube search and of the polar point, and the host checks of
 // the polar groups, the discrete variable's table and the column lists.  Every device function is one fixed sequence of rounded fp64
 // operations (the build has no FMA contraction): a kernel that calls one has the bits of every other that does.
 // Include after fdg_internal.h with FDG_RUNTIME_TU defined.
@@ -69,6 +69,44 @@ __device__ __forceinline__ double vegas_draw(const double *__restrict__ grid, ui
   else c = vegas_cell(sample, d, seed, G, y);
   const double *e = grid + (size_t)d * (G + 1u) + c;
   const double lo = e[0], wd = e[1] - lo, fr = y - (double)c;
+  f = (double)G * wd;
+  return lo + fr * wd;
+}
+
+// The inverse of the map for variable d: the coordinate yy in cells, 0 <= yy <= G, of the value xv.  c = the number of interior edges
+// e[1 .. G - 1] that are <= xv (a binary search per lane like discrete_pick's: a row is at most a few KiB and stays in cache; G = 1
+// searches nothing), then fr = (xv - e[c]) / (e[c + 1] - e[c]) clamped into [0, 1] (0 for a cell without width and for a nan), and
+// yy = c + fr.  A value outside the row is clamped, never faulted on: every index lies in [0, G].
+__device__ __forceinline__ double vegas_invert(const double *__restrict__ grid, uint32_t d, uint32_t G, double xv) {
+  const double *e = grid + (size_t)d * (G + 1u);
+  uint32_t lo = 0, hi = G - 1u;                           // c in [lo, hi]: e[1 .. lo] <= xv < e[hi + 1 ..]
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (e[mid + 1u] <= xv) lo = mid + 1u; else hi = mid;
+  }
+  const double l = e[lo], wd = e[lo + 1u] - l;
+  double fr = (xv - l) / wd;
+  if (wd == 0.0 || !(fr >= 0.0)) fr = 0.0;
+  if (fr > 1.0) fr = 1.0;
+  return (double)lo + fr;
+}
+
+// Variable d of `sample` moved from the value xv by a shift in the map's coordinate: y' = y + t h (mod 1) with t = 2 u - 1 uniform in
+// [-1, 1), u the Philox column d (the one a redraw of d would use: a variable is redrawn or shifted in one step, never both) and
+// hG = h * G the half width in cells, formed on the host.  One wrap suffices because h <= 0.5.  The new value is returned and f = G * wd
+// of its cell: the tail of vegas_draw.  The proposal is symmetric in y, so the chain's accept rule needs no factor for it.
+__device__ __forceinline__ double vegas_shift(const double *__restrict__ grid, uint32_t d, uint32_t G, uint64_t sample, uint64_t seed, double hG,
+                                              double xv, double &f) {
+  const double yy = vegas_invert(grid, d, G, xv);
+  const double u = fdg_philox_u53(sample, d, seed);
+  const double t = (u + u) - 1.0;
+  const double s = t * hG;
+  double y1 = yy + s;
+  if (y1 < 0.0) y1 = y1 + (double)G;
+  if (y1 >= (double)G) y1 = y1 - (double)G;
+  const uint32_t c = min((uint32_t)(int)y1, G - 1u);
+  const double *e = grid + (size_t)d * (G + 1u) + c;
+  const double lo = e[0], wd = e[1] - lo, fr = y1 - (double)c;
   f = (double)G * wd;
   return lo + fr * wd;
 }

@@ -1053,6 +1053,36 @@ function chain_propose_device_polar!(d_xp::Ptr{Float64}, d_facp::Ptr{Float64}, d
     return nothing
 end
 export chain_propose_device_polar!
+# The chain's proposal with local shift moves (fdg_chain_propose_device_local): chain_propose_device_polar! with the variables of local_mask
+# shifted in the map's coordinate, y' = y + t h (mod 1), h = width[d] in (0, 0.5] (width: one number per variable, read where local_mask has
+# a bit).  mask and local_mask share no bit; a variable of a polar group and the discrete variable cannot be shifted.  The proposal is
+# symmetric in y, so every step wrapper above serves as it is.  Unverified: written against the header, never run.
+function chain_propose_device_local!(d_xp::Ptr{Float64}, d_facp::Ptr{Float64}, d_x::Ptr{Float64}, d_fac::Ptr{Float64}, d_grid::Ptr{Float64},
+    n_dim::Integer, n_grid::Integer, n_col::Integer, mask::Integer, local_mask::Integer, width::Vector{Float64}, B::Integer;
+    polar::AbstractVector=[], col::Union{Nothing,AbstractVector{<:Integer}}=nothing, move_discrete::Bool=false,
+    d_cdf::Ptr{Float64}=Ptr{Float64}(C_NULL), n_bin::Integer=1, d_ext::Ptr{Float64}=Ptr{Float64}(C_NULL),
+    ext_col::AbstractVector{<:Integer}=Int[], d_bin::Ptr{Int32}=Ptr{Int32}(C_NULL), d_binp::Ptr{Int32}=Ptr{Int32}(C_NULL), seed::Integer=0,
+    sample_offset::Integer=0, x_col_stride::Integer=B, xp_col_stride::Integer=B, stream::Ptr{Cvoid}=C_NULL)
+    length(width) == n_dim || error("width holds one number per variable")
+    c = col === nothing ? nothing : UInt32.(col .- 1)
+    ec = UInt32.(ext_col .- 1)
+    p = zeros(UInt32, 5 * max(length(polar), 1))
+    for (g, (var, cols)) in enumerate(polar)
+        length(cols) in (2, 3) || error("a polar group has 2 or 3 columns")
+        p[5g-4] = var - 1
+        p[5g-3] = length(cols)
+        p[5g-2:5g-3+length(cols)] .= UInt32.(cols .- 1)
+    end
+    _fdg_check(ccall((:fdg_chain_propose_device_local, _libfdg), Cint,
+        (Ptr{Float64}, UInt32, UInt32, Ptr{UInt32}, UInt32, UInt64, UInt64, Ptr{Float64}, UInt64, UInt64, Ptr{Float64}, Int64, Ptr{Float64},
+         Ptr{Float64}, Int64, Ptr{Float64}, Cint, Ptr{Float64}, UInt32, Ptr{Float64}, UInt32, Ptr{UInt32}, Ptr{Int32}, Ptr{Int32}, Ptr{UInt32},
+         UInt32, Int64, Ptr{Cvoid}),
+        d_grid, n_dim, n_grid, c === nothing ? C_NULL : c, n_col, mask, local_mask, width, seed, sample_offset, d_x, x_col_stride, d_fac, d_xp,
+        xp_col_stride, d_facp, move_discrete ? 1 : 0, d_cdf, n_bin, d_ext, length(ec), isempty(ec) ? C_NULL : ec, d_bin, d_binp,
+        isempty(polar) ? C_NULL : p, length(polar), B, stream))
+    return nothing
+end
+export chain_propose_device_local!
 
 # ---- multi-GPU: one Julia process per GPU, ONE reduction of the accumulated observable ------------ #
 # (include/fdg.h, "multi-GPU").  Rank 0 calls `comm_unique_id()` and ships the 128 bytes to the other

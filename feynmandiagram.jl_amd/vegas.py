@@ -47,6 +47,9 @@ several orders of a series walk in one chain: every group carries the jacobian o
 With spherical momentum variables (``chain_integrate_polar``, ``chain_moves_polar``; fdg_chain_propose_device_polar) the proposal
 draws a group's modulus and direction and writes the Cartesian columns; the measure's factors ride in the group's own rows of the
 per-variable factors, so every step serves as it is.  A group is redrawn whole or not at all.
+With local moves (``chain_integrate_shift``, ``ChainShift``, ``chain_moves_shift``; fdg_chain_propose_device_local) a variable is
+displaced in the map's uniform coordinate, ``y' = y + t h (mod 1)``, instead of being redrawn whole: the stationary density in ``y`` is
+``a + gamma``, so the step's rule is the Metropolis rule of every proposal symmetric in ``y``, and every step serves as it is.
 """
 from __future__ import annotations
 
@@ -842,6 +845,7 @@ class ChainResult:
                                      # S, Q, X are raw over the 2 n_freq R columns 2 (f R + k) (real part), + 1 (imaginary part)
     Q: Optional[np.ndarray] = None   # [R + 1] sum over the walkers of A_c(b)**2
     X: Optional[np.ndarray] = None   # [R] sum over the walkers of A_k(b) A_R(b)
+    shift_width: Optional[np.ndarray] = None   # [D] the half widths of the shifts of the measured steps (:func:`chain_integrate_shift`)
     reweight: Optional[np.ndarray] = None   # [n_group] the factor of every weight group (:func:`chain_integrate_grouped`)
 
 
@@ -900,6 +904,45 @@ def chain_moves_polar(n_dim: int, polar) -> List[int]:
     return out
 
 
+@dataclass
+class ChainShift:
+    """The local moves of :func:`chain_integrate_shift`: a variable is displaced in the map's uniform coordinate, ``y' = y + t h
+    (mod 1)`` with ``t`` uniform in ``[-1, 1)``.  ``width``: the half width ``h`` in ``(0, 0.5]``, one number or one per variable.
+    ``moves``: pairs ``(redraw_mask, shift_mask)``, one per step in turn (None: :func:`chain_moves_shift`).  ``tune``: adapt the widths
+    towards the acceptance ``target`` during the discarded steps."""
+    width: object = 0.1
+    moves: Optional[Sequence[Tuple[int, int]]] = None
+    tune: bool = False
+    target: float = 0.44
+
+
+def chain_moves_shift(n_dim: int, polar=(), discrete: bool = False) -> List[Tuple[int, int]]:
+    """The default moves of :func:`chain_integrate_shift`, pairs ``(redraw_mask, shift_mask)`` over ``n_dim`` continuous variables:
+    everything redrawn (the discrete variable, bit ``n_dim``, too), then one move per unit in the order of the units' first variables:
+    a variable of no group shifted, a polar group (``polar``: :class:`PolarVar` or ``(var, cols)`` pairs) redrawn whole, the discrete
+    variable redrawn.  The one whole redraw stays because a cycle of shifts alone thermalises slowly from the map's placement."""
+    D = int(n_dim)
+    first = {}
+    for p in polar:
+        var, cols = (p.var, p.cols) if isinstance(p, PolarVar) else p
+        first[int(var)] = len(cols)
+    out, d = [((1 << (D + bool(discrete))) - 1, 0)], 0
+    while d < D:
+        n = first.get(d, 0)
+        out.append(((((1 << n) - 1) << d), 0) if n else (0, 1 << d))
+        d += max(n, 1)
+    if discrete:
+        out.append((1 << D, 0))
+    return out
+
+
+def chain_tune_width(h: float, n_accepted, n_total: int, target: float) -> float:
+    """The width of a one-variable shift after a tuned step: ``r`` = the step's acceptances over the walkers,
+    ``h <- clip(h r / target, h / 2, 2 h)``, then into ``[2**-20, 0.5]``."""
+    r = float(n_accepted) / int(n_total)
+    return min(max(min(max(h * r / target, h / 2.0), 2.0 * h), 2.0 ** -20), 0.5)
+
+
 _CHAIN_EXCLUDED = ("polar", "groups", "dmap", "observables", "freq_observables", "strat")
 _CHAIN_TRAIN_KEY = 0x632BE59BD9B4E019       # added to ``seed`` for the map's training: the chain's counters are used once
 
@@ -942,7 +985,7 @@ def chain_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: 
 
     Out of scope here, refused with ValueError: ``polar``, ``groups``, a discrete variable (``dmap``), ``observables``,
     ``freq_observables`` and ``strat`` together with the chain.  Not built either: training the map from the chain's own samples,
-    local (shift) proposals, reweighting between orders.  The target these lead to is ``Sigma(i omega_0)`` of the Hubbard atom in
+    reweighting between orders; local (shift) proposals are :func:`chain_integrate_shift`'s.  The target these lead to is ``Sigma(i omega_0)`` of the Hubbard atom in
     the reference's test/hubbard.jl: its single-order case is what ``matsubara`` reaches; several orders at once need ``groups``,
     which :func:`chain_integrate_grouped` takes (with the reweighting between orders)."""
     for name, value in excluded.items():
@@ -1081,11 +1124,68 @@ def chain_integrate_polar(func_or_handle, tables, lo, hi, col, polar: Sequence[P
                   weight_freq, groups, reweight, dmap, floor, polar)
 
 
+def chain_integrate_shift(func_or_handle, tables, lo, hi, col, shift: ChainShift, kF: float = 0.0, beta: float = 1.0, lam: float = 0.0, *,
+                          n_walker: int, n_step: int, n_therm: int, gamma_rel: float = 1.0, gamma: Optional[float] = None, n_warm: int = 5,
+                          n_warm_sample: Optional[int] = None, n_grid: int = 64, alpha: float = 0.5, floor: float = 0.05, seed: int = 0,
+                          fixed=None, coef=None, vmap: Optional[VegasMap] = None, specialize_fused: bool = True,
+                          n_total: Optional[int] = None, shard_start: int = 0, reduce: Optional[Callable] = None, device="cuda",
+                          groups: Optional[WeightGroups] = None, reweight=None, dmap: Optional[DiscreteMap] = None,
+                          polar: Optional[Sequence[PolarVar]] = None, matsubara: Optional[MatsubaraProjection] = None, weight_freq: int = 0,
+                          **excluded) -> ChainResult:
+    """The chain with LOCAL moves (``shift``: a :class:`ChainShift`), which the other chain drivers lack: a variable is displaced by a
+    small step instead of being redrawn whole -- the way ``integrate(...; solver=:mcmc)`` of the reference's test/hubbard.jl:85 walks
+    (fdg_chain_propose_device_local, include/fdg.h).  Diagram weights depend on differences of times and momenta; a separable map
+    cannot adapt to such a ridge, and a whole redraw of a variable then lands off it most of the time.
+
+    With ``x = map(y)`` the stationary density in the map's uniform coordinate ``y`` is exactly ``a + gamma``, so the step's rule
+    ``u (a + gamma) < a' + gamma`` is the Metropolis rule of every proposal that is symmetric in ``y``.  A redraw is the uniform one;
+    the shift ``y' = y + t h (mod 1)``, ``t`` uniform in ``[-1, 1)``, is another.  So the step entries are those of
+    :func:`chain_integrate_polar` -- ``groups`` (with ``reweight``), ``dmap``, ``polar``, ``matsubara`` and ``weight_freq`` as there,
+    with the same warm-up, placement, ``gamma``, sharding and result -- and only the proposal call differs.  FDG_CHAIN_INIT redraws
+    everything, as in every driver.
+
+    A move is a pair ``(redraw_mask, shift_mask)``: the variables of the first are redrawn through the map, those of the second
+    shifted by their own ``shift.width``, the rest kept.  The default, :func:`chain_moves_shift`, is one whole redraw, then one move
+    per unit: a shift of a variable of no group, a redraw of a polar group, a redraw of the discrete variable.
+
+    ``shift.tune``: during the first ``n_therm`` steps only, after a step whose move shifts exactly one variable ``d`` and does nothing
+    else, ``r`` = the step's acceptances over all walkers (``reduce`` is applied to the count, so every rank holds the same widths)
+    and ``h_d <- clip(h_d r / target, h_d / 2, 2 h_d)``, then into ``[2**-20, 0.5]``.  From step ``n_therm`` on the widths are
+    frozen, so the measured chain is stationary; ``ChainResult.shift_width`` holds them.  This is host arithmetic on integer counts:
+    deterministic and independent of the split into shards.
+
+    Refused with ValueError: a move whose two masks overlap; a shift of a variable of a polar group or of the discrete variable (the
+    state holds Cartesian columns and no ``(k, theta, phi)``; inverting that is out of scope, as are local moves of the discrete
+    variable); a width outside ``(0, 0.5]``; ``observables``, ``freq_observables`` and ``strat``.  Not built: training the map from
+    the chain.  Whether shifts lower the error on a given workload has not been measured."""
+    for name, value in excluded.items():
+        if name not in _CHAIN_EXCLUDED or name in ("polar", "groups", "dmap"):
+            raise TypeError(f"chain_integrate_shift() got an unexpected keyword argument '{name}'")
+        if value is not None:
+            raise ValueError(f"{name} cannot be combined with the chain yet")
+    if not isinstance(shift, ChainShift):
+        raise ValueError("shift must be a ChainShift")
+    if polar is not None:
+        polar = list(polar)
+        if not all(isinstance(p, PolarVar) for p in polar):
+            raise ValueError("polar must be a sequence of PolarVar")
+    if dmap is not None and not isinstance(dmap, DiscreteMap):
+        raise ValueError("dmap must be a DiscreteMap")
+    if groups is not None and not isinstance(groups, WeightGroups):
+        raise ValueError("groups must be a WeightGroups")
+    if groups is None and reweight is not None:
+        raise ValueError("reweight goes with groups")
+    return _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step, n_therm, None, gamma_rel, gamma, n_warm,
+                  n_warm_sample, n_grid, alpha, seed, fixed, coef, vmap, specialize_fused, n_total, shard_start, reduce, device, matsubara,
+                  weight_freq, groups, reweight, dmap, floor, polar or None, shift)
+
+
 def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step, n_therm, moves, gamma_rel, gamma, n_warm, n_warm_sample,
            n_grid, alpha, seed, fixed, coef, vmap, specialize_fused, n_total, shard_start, reduce, device, matsubara, weight_freq,
-           wgroups=None, reweight=None, dmap=None, floor=0.05, polar=None) -> ChainResult:
+           wgroups=None, reweight=None, dmap=None, floor=0.05, polar=None, shift=None) -> ChainResult:
     """The body of :func:`chain_integrate`, with ``wgroups`` of :func:`chain_integrate_grouped`, with ``dmap`` of
-    :func:`chain_integrate_binned`, and with ``polar`` of :func:`chain_integrate_polar`."""
+    :func:`chain_integrate_binned`, with ``polar`` of :func:`chain_integrate_polar`, and with ``shift`` of
+    :func:`chain_integrate_shift` (the moves are then its pairs, and ``moves`` is None)."""
     import torch
     handle = getattr(func_or_handle, "handle", func_or_handle)
     device = torch.device(device)
@@ -1156,8 +1256,27 @@ def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step,
         if any(c is None for d, c in enumerate(col) if not any(v <= d < v + len(cs) for v, cs in pgroups)):
             raise ValueError("only the variables of a polar group go without a column")
         pbits = [((1 << len(cs)) - 1) << v for v, cs in pgroups]
-        if moves is None:
+        if moves is None and shift is None:
             moves = chain_moves_polar(DV, pgroups)
+    lmoves = width = None                                   # the shift masks of the moves and the widths, with ``shift`` only
+    if shift is not None:
+        width = np.array(shift.width, dtype=np.float64)
+        width = np.full(D, float(width)) if width.ndim == 0 else width
+        if width.shape != (D,) or not (np.isfinite(width) & (width > 0.0) & (width <= 0.5)).all():
+            raise ValueError("shift.width holds one half width in (0, 0.5], or one per variable of the map")
+        if shift.tune and not (math.isfinite(shift.target) and 0.0 < shift.target < 1.0):
+            raise ValueError("shift.target must lie in (0, 1)")
+        pairs = chain_moves_shift(D, pgroups or (), dmap is not None) if shift.moves is None else [(int(r), int(s)) for r, s in shift.moves]
+        for r, s in pairs:
+            if not 0 <= s < (1 << DV):
+                raise ValueError("moves holds pairs of masks over the variables of the map")
+            if r & s:
+                raise ValueError("a move redraws or shifts a variable, not both: its two masks overlap")
+            if s >> D:
+                raise ValueError("the discrete variable can only be redrawn, not shifted")
+            if polar is not None and any(s & bits for bits in pbits):
+                raise ValueError("a variable of a polar group can only be redrawn with its group: the state does not hold (k, theta, phi)")
+        moves, lmoves = [r for r, _ in pairs], [s for _, s in pairs]
     moves = chain_moves(DV) if moves is None else [int(m) for m in moves]
     if not moves or not all(0 <= m < (1 << DV) for m in moves):
         raise ValueError("moves holds masks over the variables of the map" + (" and the discrete variable" if dmap is not None else ""))
@@ -1219,8 +1338,15 @@ def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step,
         total = torch.zeros((C + 1, B), **f64)
         n_acc = torch.zeros(B, dtype=torch.int32, device=device)
 
-        def step(mask, off, g, flags):
-            if polar is not None:
+        def step(mask, off, g, flags, lmask=0):
+            if shift is not None:
+                capi.chain_propose_device_local(vmap.d_grid.data_ptr(), D, G, col, n_col, mask & all_mask, lmask, width, seed, off, x.data_ptr(),
+                                                B, fac.data_ptr(), xp.data_ptr(), B, facp.data_ptr(), bool((mask >> D) & 1),
+                                                0 if dmap is None else dmap.d_cdf.data_ptr(), n_bin,
+                                                0 if dmap is None or dmap.d_ext is None else dmap.d_ext.data_ptr(),
+                                                None if dmap is None else dmap.ext_col, 0 if dmap is None else bins.data_ptr(),
+                                                0 if dmap is None else binp.data_ptr(), pgroups or (), B, st)
+            elif polar is not None:
                 capi.chain_propose_device_polar(vmap.d_grid.data_ptr(), D, G, col, n_col, mask & all_mask, seed, off, x.data_ptr(), B,
                                                 fac.data_ptr(), xp.data_ptr(), B, facp.data_ptr(), bool((mask >> D) & 1),
                                                 0 if dmap is None else dmap.d_cdf.data_ptr(), n_bin,
@@ -1278,9 +1404,23 @@ def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step,
             if not (math.isfinite(gamma) and gamma > 0.0):
                 raise ValueError("the map's estimate of the integral of |s| is not positive: pass gamma")
         n_acc.zero_()
+
+        def accepted():                                       # the acceptances of all walkers so far: an integer, exact in fp64
+            s = n_acc.sum(dtype=torch.float64).reshape(1)
+            if reduce is not None:
+                reduce(s)
+            return float(s.item())
+
         for t in range(n_step):
-            step(moves[t % len(moves)], (t + 1) * N + int(shard_start), float(gamma),
-                 capi.FDG_CHAIN_MEASURE if t >= n_therm else 0)
+            i = t % len(moves)
+            lm = 0 if lmoves is None else lmoves[i]
+            # tuning, in the discarded steps only: after a move that shifts exactly one variable and does nothing else
+            tuned = shift is not None and shift.tune and t < n_therm and moves[i] == 0 and lm != 0 and lm & (lm - 1) == 0
+            before = accepted() if tuned else 0.0
+            step(moves[i], (t + 1) * N + int(shard_start), float(gamma), capi.FDG_CHAIN_MEASURE if t >= n_therm else 0, lm)
+            if tuned:
+                d = lm.bit_length() - 1
+                width[d] = chain_tune_width(float(width[d]), accepted() - before, N, float(shift.target))
         out = torch.zeros(3 * C + 2, **f64)
         capi.chain_reduce_device(total.data_ptr(), C, B, out.data_ptr(), st)
         acc_sum = n_acc.sum(dtype=torch.float64).reshape(1)
@@ -1294,4 +1434,5 @@ def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step,
         mean, err = chain_complex(mean, max(n_bin, 1) * F, R), chain_complex(err, max(n_bin, 1) * F, R)
     if dmap is not None:
         mean, err = (v.reshape((n_bin, F, R) if F else (n_bin, R)) for v in (mean, err))
-    return ChainResult(mean, err, float(acc_sum.item()) / (N * n_step), float(gamma), vmap, S, Q, X, rho)
+    return ChainResult(mean, err, float(acc_sum.item()) / (N * n_step), float(gamma), vmap, S, Q, X,
+                       shift_width=None if width is None else width.copy(), reweight=rho)

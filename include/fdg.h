@@ -1422,6 +1422,50 @@ int fdg_chain_propose_device_polar(const double *d_grid, uint32_t n_dim, uint32_
                                    uint32_t n_bin, const double *d_ext, uint32_t n_ext, const uint32_t *ext_col, const int32_t *d_bin,
                                    int32_t *d_binp, const fdg_vegas_polar *polar, uint32_t n_polar, int64_t n_walker, void *stream);
 
+/* ---- Markov chain with local shift moves in the map's coordinate -----------------------------------------------------------------------
+ * The solver that the reference's test/hubbard.jl:85 asks for (integrate(...; solver=:mcmc)) walks by local moves: small displacements
+ * of one variable at a time, not independent fresh draws.  Diagram weights depend on differences of times and momenta; a separable map
+ * cannot follow such a ridge, and a whole-variable redraw lands off it most of the time.  MCIntegration is not part of the reference
+ * checkout: no counterpart in the reference.
+ *
+ * With x = map(y), the stationary density of the chain in the map's uniform coordinate y is exactly a + gamma, where
+ * a = sum_g rho_g |jac_g s_g| is pi / q as before.  So the step's rule u (a + gamma) < a' + gamma is the correct Metropolis rule for ANY
+ * proposal that is symmetric in y.  A redraw is the uniform, symmetric proposal in y; the shift y' = y + t h (mod 1), t uniform in
+ * [-1, 1), is another one: the density of y' given y depends on (y' - y) mod 1 only, and is even in it.  Weight groups, the Matsubara
+ * weight and the per-bin measurement stay valid: a group's density is uniform in the y of the variables it does not own.  No step,
+ * select or reduce entry changes; only the proposal does.
+ *
+ * fdg_chain_propose_device_local: fdg_chain_propose_device_polar's arguments and results, with local_mask and width behind mask.  A
+ * variable of local_mask is SHIFTED; a variable of mask is redrawn as before; every other one is copied.  width is a HOST array of
+ * [n_dim] entries, the half width h_d of the shift of variable d as a fraction of the map's unit interval, read only where local_mask
+ * has a bit; hG_d = width[d] * (double)n_grid is formed on the host.  For a shifted variable d, with e[0 .. G] row d of the grid,
+ * xv = x[col[d]] the walker's value and u the uniform of counter (sample_offset + b, d) -- the column a redraw of d would use; a variable
+ * is redrawn or shifted in one step, never both -- every line one rounded fp64 operation (no FMA), in this order:
+ *   the inverse of the map:
+ *     c  = the number of interior edges e[1 .. G - 1] that are <= xv (a binary search per lane; G = 1 searches nothing)
+ *     lo = e[c];   wd = e[c + 1] - lo;   fr = (xv - lo) / wd;   fr = 0 when wd == 0 or fr is not >= 0;   fr = 1 when fr > 1
+ *     yy = (double)c + fr                                        in cells: 0 <= yy <= G
+ *   the shift:
+ *     t = (u + u) - 1.0;   y1 = yy + t * hG_d
+ *     if y1 < 0: y1 = y1 + G;   if y1 >= G: y1 = y1 - G           one wrap suffices because width <= 0.5
+ *     c' = min((uint32_t)(int)y1, G - 1);   fr' = y1 - c'
+ *   the map again, the tail of fdg_vegas_sample_device's statements:
+ *     xp[col[d]] = lo' + fr' * wd';   facp[d] = G * wd'
+ * A shift is meant for a placed walker: after FDG_CHAIN_INIT a value lies inside its row.  A value outside it (or a nan) is clamped
+ * to the row's ends by the statements above and not faulted on: every index into the grid lies in [0, G].
+ * The discrete variable and the polar groups can only be redrawn.  The state holds Cartesian columns and no (k, theta, phi); inverting
+ * that with pinned bits is out of scope here, as are local moves of the discrete variable.
+ * With local_mask == 0 the results are bit for bit those of fdg_chain_propose_device_polar (width is not read and may be NULL).
+ * FDG_E_INVALID / FDG_E_UNSUPPORTED, in this order: everything fdg_chain_propose_device_polar refuses; a bit of local_mask at or above
+ * n_dim (invalid); mask & local_mask != 0 (invalid); local_mask naming a variable of a polar group (unsupported); width == NULL with
+ * local_mask != 0 (invalid); a named width[d] that is not finite or not in (0, 0.5] (invalid).  All before any device work. */
+int fdg_chain_propose_device_local(const double *d_grid, uint32_t n_dim, uint32_t n_grid, const uint32_t *col, uint32_t n_col, uint64_t mask,
+                                   uint64_t local_mask, const double *width, uint64_t seed, uint64_t sample_offset, const double *d_x,
+                                   int64_t x_col_stride, const double *d_fac, double *d_xp, int64_t xp_col_stride, double *d_facp,
+                                   int move_discrete, const double *d_cdf, uint32_t n_bin, const double *d_ext, uint32_t n_ext,
+                                   const uint32_t *ext_col, const int32_t *d_bin, int32_t *d_binp, const fdg_vegas_polar *polar,
+                                   uint32_t n_polar, int64_t n_walker, void *stream);
+
 /* Device workspace control: the interpreter keeps per-sample overflow slots in
  * an HBM panel owned by the handle; it is sized on first use for the number of
  * resident waves.  This releases it (and any loaded module). */
