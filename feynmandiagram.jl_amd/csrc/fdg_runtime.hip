@@ -816,7 +816,7 @@ struct IsaRun {
   const Lowered &p;
   const uint32_t R;
   const bool tiled;
-  long ntiles = 0, grid = 0, grid2 = 0, grid3 = 0, grid4 = 0, grid5 = 0;
+  long ntiles = 0, grid = 0, grid_cl = 0, grid2 = 0, grid3 = 0, grid4 = 0, grid5 = 0;      // (grid_cl: the claimed walk of the kernels that `grid` launches)
   size_t panel_all = 0;
   bool pool_ok = false, fused_acc = false, wide_ss = false, named = false, claim = false;
   size_t claim_off = 0;             // the tile counter of the claimed kernels: byte offset in the workspace
@@ -844,7 +844,12 @@ struct IsaRun {
   // (one per SIMD) keep 4 x L x 512 bytes in flight per CU -- enough for the latency-bandwidth product -- and the memory system sees a
   // quarter of the concurrent streams (round 4, profiles/r04_log_waves.txt: headline +3-5 %, the 2-loop graph +6-15 %); the graphs at or
   // above the ridge want every wave they can get.  Options FDG_ISA_MEM_WAVES / FDG_ISA_MEM_OVERSUB / FDG_ISA_MEM_RATIO override (0 waves = off).
-  long mem_waves_of(bool accumulating) const { return g->cfg.mem_waves >= 0 ? g->cfg.mem_waves : (p.L >= 24 ? 4 : (accumulating ? 8 : 5)); }
+  // The claimed walk of the graphs with 24 leaves or more runs from THREE: its waves cannot drift apart, which is what a fourth wave was
+  // covering for in the static walk, where three only equalled four (headline, one process, one allocation: 10.05 against 10.20 ms paired,
+  // 10.54 against 10.82 ms plain, every alternation; two waves lose 3.5 %; profiles/log_tile_prefetch_bound*.txt).
+  long mem_waves_of(bool accumulating, bool claimed = false) const {
+    return g->cfg.mem_waves >= 0 ? g->cfg.mem_waves : (p.L >= 24 ? (claimed ? 3 : 4) : (accumulating ? 8 : 5));
+  }
   bool mem_bound(uint64_t valu, uint64_t bytes, const fdg_isa_kernel &k, bool accumulating) const {
     return mem_waves_of(accumulating) > 0 && g->cfg.waves_per_cu <= 0 && g->cfg.oversub <= 0 && bytes && (double)valu < g->cfg.mem_ratio * (double)bytes &&
            (long)waves_per_cu(k) > mem_waves_of(accumulating);
@@ -853,13 +858,14 @@ struct IsaRun {
     const long full = (long)waves_per_cu(k);
     // (a wave of a tiny graph keeps little in flight; without root stores more of them help: the 2-loop graph accumulates at 0.84 instead of
     //  0.73, profiles/r04_log_tiny_acc_waves.txt)
-    const long mem_waves = mem_waves_of(accumulating);
-    if (mem_bound(valu, bytes, k, accumulating)) {
-      long f = g->cfg.mem_oversub;
-      while (f > 1 && ntiles < (long)g->n_cu * mem_waves * f * 4) f >>= 1;
-      return (long)g->n_cu * mem_waves * f;
-    }
+    if (mem_bound(valu, bytes, k, accumulating)) return mem_grid(mem_waves_of(accumulating));
     return oversub((long)g->n_cu * full, bytes_per_wg);
+  }
+  // the grid of a memory-bound launch with `mem_waves` resident waves per CU
+  long mem_grid(long mem_waves) const {
+    long f = g->cfg.mem_oversub;
+    while (f > 1 && ntiles < (long)g->n_cu * mem_waves * f * 4) f >>= 1;
+    return (long)g->n_cu * mem_waves * f;
   }
   // a matrix whose 64-sample tiles are whole 128-byte lines (samples of a column contiguous, column stride a multiple of 16
   // doubles, base on a line): the streaming variants may be used (non-temporal accesses would fetch a shared line twice)
@@ -892,6 +898,7 @@ struct IsaRun {
     // stream's workspace (one workspace per caller stream: two streams on one handle never share it) and is zeroed on the launch stream in
     // front of every launch -- a memset node like any other under stream capture, nothing allocated, nothing waited for.
     claim = g->cfg.tile_claim != 0 && K(FDG_K_EVAL_CL).present && mem_bound(g->st_valu[0], 8ull * (p.L + R), ev, false);
+    grid_cl = claim ? std::min<long>(grid, mem_grid(mem_waves_of(false, true))) : 0;      // (never more workgroups than the panels were sized for)
     claim_off = panel_all + (size_t)std::max(grid3, grid5) * R * 512u + 4096;
     int rc = ensure_ws(g, claim_off + 256);
     if (rc) return rc;
@@ -950,13 +957,13 @@ struct IsaRun {
       if (!trs) trs = 64 * rrs;
       int k = K(FDG_K_NT).fn && line_aligned(lf1, lss, lls) && line_aligned(rt1, rrs, rrk) && ((tls | trs) & 15) == 0 ? FDG_K_NT : FDG_K_EVAL;
       if (!named && done == 0) g->last_kernel = FDG_ISA_KERNEL[k];      // (the variant's name whichever walk: fdg_kernel_info::last_launch tells the walk)
-      long run = 1;      // tiles a workgroup starts with: at most one workgroup per run of the claimed kernels
+      long run = 1, nwg = grid;      // tiles a workgroup starts with: at most one workgroup per run of the claimed kernels
       // (a short launch has no time to drift apart, and a run is a coarser unit to end on than a tile: the rule claims from 256 rounds on, where a
       //  run is at most 1/64 of a wave's work.  Claimed at 49 rounds, the 2 GB windows fdg_batch_alloc_pair times ran 0.80 instead of 0.86 -- 12.2
       //  runs per wave take the time of 13 -- and the allocator matched 22-28 windows of 32 instead of all; FDG_ISA_TILE_CLAIM=1
-      //  claims at every size)
-      if (claim && (g->cfg.tile_claim > 0 || (n1 + 63) / 64 >= 256 * grid) && K(k == FDG_K_NT ? FDG_K_NT_CL : FDG_K_EVAL_CL).fn) { k = k == FDG_K_NT ? FDG_K_NT_CL : FDG_K_EVAL_CL; run = 1l << g->claim_run; }
-      return launch(k, lf1, lss, lls, rt1, rrs, rrk, n1, std::min<long>(((n1 + 63) / 64 + run - 1) / run, grid), nullptr, tls, trs);
+      //  claims at every size.  The rule counts its rounds on the static walk's grid; the claimed walk then starts from its own, grid_cl)
+      if (claim && (g->cfg.tile_claim > 0 || (n1 + 63) / 64 >= 256 * grid) && K(k == FDG_K_NT ? FDG_K_NT_CL : FDG_K_EVAL_CL).fn) { k = k == FDG_K_NT ? FDG_K_NT_CL : FDG_K_EVAL_CL; run = 1l << g->claim_run; nwg = grid_cl; }
+      return launch(k, lf1, lss, lls, rt1, rrs, rrk, n1, std::min<long>(((n1 + 63) / 64 + run - 1) / run, nwg), nullptr, tls, trs);
     }
     return FDG_OK;
   }
