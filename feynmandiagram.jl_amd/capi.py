@@ -253,23 +253,10 @@ def lib():
     L.fdg_graph_specialize_fused.argtypes = [vp, C.POINTER(LeafTables), C.c_char_p, C.c_uint]
     L.fdg_mc_eval_device.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, i64, i64, i64, vp]
     L.fdg_mc_accumulate_device.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, dp, i64, vp]
-    L.fdg_accumulate_device_binned.argtypes = [vp, dp, i64, i64, i64, dp, C.c_int32, u32, dp, dp, i64, vp]
-    L.fdg_mc_accumulate_device_binned.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, C.c_int32, u32,
-                                                  dp, dp, i64, vp]
-    L.fdg_accumulate_device_moments.argtypes = [vp, dp, i64, i64, i64, dp, C.c_int32, u32, dp, dp, dp, i64, vp]
-    L.fdg_mc_accumulate_device_moments.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, C.c_int32, u32,
-                                                   dp, dp, dp, i64, vp]
     L.fdg_vegas_sample_device.argtypes = [dp, u32, u32, C.c_void_p, u64, u64, dp, i64, i64, dp, dp, i64, vp]
-    L.fdg_accumulate_device_vegas.argtypes = [vp, dp, i64, i64, i64, dp, C.c_void_p, u64, u64, u32, u32, dp, dp, dp, i64, vp]
-    L.fdg_mc_accumulate_device_vegas.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, C.c_void_p, u64, u64,
-                                                 u32, u32, dp, dp, dp, i64, vp]
     L.fdg_vegas_refine.argtypes = [C.c_void_p, C.c_void_p, u32, u32, C.c_double]
     L.fdg_vegas_sample_device_discrete.argtypes = [dp, u32, u32, C.c_void_p, dp, u32, C.c_int32, dp, u32, C.c_void_p, u64, u64, dp, i64, i64,
                                                    dp, dp, dp, i64, vp]
-    L.fdg_accumulate_device_vegas_binned.argtypes = [vp, dp, i64, i64, i64, dp, C.c_int32, u32, dp, C.c_void_p, u64, u64, u32, u32, dp, dp,
-                                                     dp, dp, i64, vp]
-    L.fdg_mc_accumulate_device_vegas_binned.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, C.c_int32,
-                                                        u32, dp, C.c_void_p, u64, u64, u32, u32, dp, dp, dp, dp, i64, vp]
     L.fdg_vegas_refine_discrete.argtypes = [C.c_void_p, C.c_void_p, u32, C.c_double, C.c_double]
     L.fdg_comm_unique_id.argtypes = [C.c_void_p, C.c_size_t]
     L.fdg_comm_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(vp)]
@@ -281,39 +268,27 @@ def lib():
     L.fdg_sincos.restype = None
     L.fdg_matsubara_phase.argtypes = [C.c_double, C.c_double, C.c_int32, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.fdg_matsubara_phase.restype = None
-    L.fdg_accumulate_device_matsubara.argtypes = [vp, dp, i64, i64, i64, dp, C.c_int32, u32, dp, C.c_void_p, u64, u64, u32, u32, dp, dp,
-                                                  dp, dp, C.c_void_p, i64, vp]
-    L.fdg_mc_accumulate_device_matsubara.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, C.c_int32,
-                                                     u32, dp, C.c_void_p, u64, u64, u32, u32, dp, dp, dp, dp, C.c_void_p, i64, vp]
     L.fdg_vegas_sample_device_grouped.argtypes = [dp, u32, u32, C.c_void_p, dp, u32, C.c_int32, dp, u32, C.c_void_p, C.c_void_p, u32,
                                                   C.c_void_p, u32, i64, u64, u64, dp, i64, i64, dp, dp, dp, i64, vp]
-    L.fdg_accumulate_device_grouped.argtypes = [vp, dp, i64, i64, i64, dp, C.c_int32, u32, dp, C.c_void_p, u64, u64, u32, u32, dp, dp,
-                                                dp, dp, C.c_void_p, C.c_void_p, i64, vp]
-    L.fdg_mc_accumulate_device_grouped.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, C.c_int32,
-                                                   u32, dp, C.c_void_p, u64, u64, u32, u32, dp, dp, dp, dp, C.c_void_p, C.c_void_p, i64, vp]
-    L.fdg_accumulate_device_observables.argtypes = [vp, dp, i64, i64, i64, dp, C.c_int32, u32, dp, C.c_void_p, u64, u64, u32, u32, dp, dp,
-                                                    dp, dp, C.c_void_p, C.c_void_p, C.c_void_p, i64, vp]
-    L.fdg_mc_accumulate_device_observables.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, C.c_int32,
-                                                       u32, dp, C.c_void_p, u64, u64, u32, u32, dp, dp, dp, dp, C.c_void_p, C.c_void_p,
-                                                       C.c_void_p, i64, vp]
-    L.fdg_accumulate_device_freq_observables.argtypes = [vp, dp, i64, i64, i64, dp, C.c_int32, u32, dp, C.c_void_p, u64, u64, u32, u32, dp,
-                                                         dp, dp, dp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, i64, vp]
-    L.fdg_mc_accumulate_device_freq_observables.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp,
-                                                            C.c_int32, u32, dp, C.c_void_p, u64, u64, u32, u32, dp, dp, dp, dp, C.c_void_p,
-                                                            C.c_void_p, C.c_void_p, C.c_void_p, i64, vp]
     L.fdg_vegas_sample_device_strat.argtypes = [dp, u32, u32, C.c_void_p, C.c_void_p, dp, u64, u64, dp, i64, i64, dp, dp, dp, i64, vp]
-    L.fdg_accumulate_device_strat.argtypes = [vp, dp, i64, i64, i64, dp, C.c_void_p, u64, u64, u32, u32, dp, dp, dp, C.c_void_p, dp, dp, dp,
-                                              i64, vp]
-    L.fdg_mc_accumulate_device_strat.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, C.c_void_p, u64, u64,
-                                                 u32, u32, dp, dp, dp, C.c_void_p, dp, dp, dp, i64, vp]
     L.fdg_strat_allocate.argtypes = [C.c_void_p, C.c_void_p, u32, u32, C.c_void_p, u32, i64, C.c_double, C.c_void_p]
     L.fdg_vegas_sample_device_strat_grouped.argtypes = [dp, u32, u32, C.c_void_p, C.c_void_p, u32, C.c_void_p, u32, i64, C.c_void_p, dp, u64,
                                                         u64, dp, i64, i64, dp, dp, dp, i64, vp]
-    L.fdg_accumulate_device_strat_grouped.argtypes = [vp, dp, i64, i64, i64, dp, C.c_void_p, u64, u64, u32, u32, dp, dp, dp, C.c_void_p, dp,
-                                                      dp, dp, C.c_void_p, i64, vp]
-    L.fdg_mc_accumulate_device_strat_grouped.argtypes = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double, dp, C.c_void_p,
-                                                         u64, u64, u32, u32, dp, dp, dp, C.c_void_p, dp, dp, dp, C.c_void_p, i64, vp]
     L.fdg_strat_allocate_cols.argtypes = [C.c_void_p, C.c_void_p, u32, C.c_void_p, u32, C.c_void_p, u32, i64, C.c_double, C.c_void_p]
+    # the accumulate entries: the leaf or the Monte-Carlo prefix, then one tail for both, composed of the pieces fdg.h names
+    leaf = [vp, dp, i64, i64, i64]                                                       # g, d_leaf, ss, ls, lts
+    mc = [vp, dp, i64, i64, dp, i64, i64, C.c_double, C.c_double, C.c_double]            # g, d_K, ks, kc, d_T, ts, tc, kF, beta, lam
+    bins, w, end = [dp, C.c_int32, u32], [dp], [i64, vp]                                 # d_bin, bin_base, n_bin; d_weight; B, stream
+    train = [vp, u64, u64, u32, u32]                                                     # coef, seed, sample_offset, n_dim, n_grid
+    vegas = w + train + [dp, dp, dp]                                                     # .. d_acc, d_acc2, d_hist
+    vegas_binned = bins + vegas + [dp]                                                   # .. d_hist_bin
+    strat = vegas + [vp, dp, dp, dp]                                                     # .. strat, d_cube, d_cube_sum, d_cube_sum2
+    tails = {"binned": bins + w + [dp], "moments": bins + w + [dp, dp], "vegas": vegas, "vegas_binned": vegas_binned,
+             "matsubara": vegas_binned + [vp], "grouped": vegas_binned + [vp] * 2, "observables": vegas_binned + [vp] * 3,
+             "freq_observables": vegas_binned + [vp] * 4, "strat": strat, "strat_grouped": strat + [vp]}      # (the descriptors)
+    for entry, tail in tails.items():
+        getattr(L, "fdg_accumulate_device_" + entry).argtypes = leaf + tail + end
+        getattr(L, "fdg_mc_accumulate_device_" + entry).argtypes = mc + tail + end
     L.fdg_chain_propose_device.argtypes = [dp, u32, u32, C.c_void_p, u32, u64, u64, u64, dp, i64, dp, dp, i64, dp, i64, vp]
     L.fdg_chain_step_device.argtypes = [vp, dp, i64, dp, u32, u32, C.c_void_p, C.c_double, u64, u64, C.c_uint, dp, i64, dp, dp, dp, dp, dp,
                                         i64, vp]
@@ -344,6 +319,23 @@ def lib():
 def check(rc: int):
     if rc != 0:
         raise FdgError(rc, lib().fdg_last_error().decode("utf-8", "replace"))
+
+
+def _ptr(v):
+    """One Python value as what a ``c_void_p`` parameter takes: None and 0 are the null pointer, any other int is an address, a ctypes
+    structure (a descriptor) stands for its own address and a numpy array (a host vector) for its data."""
+    if v is None:
+        return None
+    if isinstance(v, int):
+        return v or None
+    if isinstance(v, C.Structure):
+        return C.addressof(v)
+    if isinstance(v, np.ndarray):
+        return v.ctypes.data
+    raise TypeError(f"a pointer argument must be None, an int, a ctypes structure or a numpy array, not {type(v).__name__}")
+
+
+_POINTERS = {}      # GraphHandle._accumulate: entry -> (function, number of arguments, positions of the c_void_p arguments behind the graph)
 
 
 class GraphHandle:
@@ -535,102 +527,90 @@ class GraphHandle:
     def accumulate_device_tiled(self, d_leaf: int, ss: int, ls: int, lts: int, d_weight: int, d_acc: int, B: int, stream: int = 0):
         check(lib().fdg_accumulate_device_tiled(self._h, d_leaf, ss, ls, lts, d_weight or None, d_acc, B, stream))
 
+    def _accumulate(self, entry: str, src, *tail):
+        """fdg_[mc_]accumulate_device_ + ``entry``: ``src`` is ``(d_leaf, ss, ls, lts)`` (the leaf form) or
+        ``(d_K, ks, kc, d_T, ts, tc, kF, beta, lam)`` (the Monte-Carlo form), ``tail`` the rest in the order of fdg.h.  Every pointer
+        argument goes through :func:`_ptr`: 0 and None are null, a descriptor stands for its address, a host array for its data."""
+        name = ("fdg_accumulate_device_" if len(src) == 4 else "fdg_mc_accumulate_device_") + entry
+        if name not in _POINTERS:                   # the entry's function, its argument count and its pointer positions, looked up once
+            fn = getattr(lib(), name)
+            _POINTERS[name] = (fn, len(fn.argtypes), [i for i, t in enumerate(fn.argtypes) if i and t is C.c_void_p])
+        fn, n, pointers = _POINTERS[name]
+        args = [self._h, *src, *tail]
+        if len(args) != n:
+            raise TypeError(f"{name} takes {n - 1} arguments behind the graph ({len(args) - 1} given)")
+        for i in pointers:
+            args[i] = _ptr(args[i])
+        check(fn(*args))
+
     # binned accumulation: d_acc[j * R + k] += w[b] root_k(b) for j = d_bin[b] - bin_base in [0, n_bin) (fdg.h) ---------------- #
     def accumulate_device_binned(self, d_leaf: int, ss: int, ls: int, lts: int, d_bin: int, bin_base: int, n_bin: int, d_weight: int,
                                  d_acc: int, B: int, stream: int = 0):
-        check(lib().fdg_accumulate_device_binned(self._h, d_leaf or None, ss, ls, lts, d_bin or None, bin_base,
-                                                 n_bin, d_weight or None, d_acc or None, B, stream))
+        self._accumulate("binned", (d_leaf, ss, ls, lts), d_bin, bin_base, n_bin, d_weight, d_acc, B, stream)
 
     def mc_accumulate_device_binned(self, d_K, ks, kc, d_T, ts, tc, kF, beta, lam, d_bin, bin_base, n_bin, d_weight, d_acc, B, stream=0):
-        check(lib().fdg_mc_accumulate_device_binned(self._h, d_K or None, ks, kc, d_T or None, ts, tc, kF, beta, lam,
-                                                    d_bin or None, bin_base, n_bin, d_weight or None,
-                                                    d_acc or None, B, stream))
+        self._accumulate("binned", (d_K, ks, kc, d_T, ts, tc, kF, beta, lam), d_bin, bin_base, n_bin, d_weight, d_acc, B, stream)
 
     # second moments as well: d_acc2[j * R + k] += (w[b] root_k(b))^2; d_bin 0 = every sample in bin 0 (n_bin 1) (fdg.h) ------- #
     def accumulate_device_moments(self, d_leaf: int, ss: int, ls: int, lts: int, d_bin: int, bin_base: int, n_bin: int, d_weight: int,
                                   d_acc: int, d_acc2: int, B: int, stream: int = 0):
-        check(lib().fdg_accumulate_device_moments(self._h, d_leaf or None, ss, ls, lts, d_bin or None, bin_base,
-                                                  n_bin, d_weight or None, d_acc or None, d_acc2 or None, B, stream))
+        self._accumulate("moments", (d_leaf, ss, ls, lts), d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, stream)
 
     def mc_accumulate_device_moments(self, d_K, ks, kc, d_T, ts, tc, kF, beta, lam, d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B,
                                      stream=0):
-        check(lib().fdg_mc_accumulate_device_moments(self._h, d_K or None, ks, kc, d_T or None, ts, tc, kF, beta, lam,
-                                                     d_bin or None, bin_base, n_bin, d_weight or None,
-                                                     d_acc or None, d_acc2 or None, B, stream))
+        self._accumulate("moments", (d_K, ks, kc, d_T, ts, tc, kF, beta, lam), d_bin, bin_base, n_bin, d_weight, d_acc, d_acc2, B, stream)
 
     # one VEGAS iteration's accumulate step: both moments (the bits of the moments calls with d_bin 0, n_bin 1) and the training histogram
     # d_hist[d * n_grid + c] += (w[b] sum_k coef[k] root_k(b))^2, c = the cell of counter (sample_offset + b, d); coef: host vector or None (fdg.h)
     def accumulate_device_vegas(self, d_leaf: int, ss: int, ls: int, lts: int, d_weight: int, coef, seed: int, sample_offset: int, n_dim: int,
                                 n_grid: int, d_acc: int, d_acc2: int, d_hist: int, B: int, stream: int = 0):
-        c = self._coef(coef)
-        check(lib().fdg_accumulate_device_vegas(self._h, d_leaf or None, ss, ls, lts, d_weight or None, None if c is None else c.ctypes.data,
-                                                seed, sample_offset, n_dim, n_grid, d_acc or None, d_acc2 or None, d_hist or None, B, stream))
+        self._accumulate("vegas", (d_leaf, ss, ls, lts), d_weight, self._coef(coef), seed, sample_offset, n_dim, n_grid, d_acc, d_acc2,
+                         d_hist, B, stream)
 
     def mc_accumulate_device_vegas(self, d_K, ks, kc, d_T, ts, tc, kF, beta, lam, d_weight, coef, seed, sample_offset, n_dim, n_grid, d_acc,
                                    d_acc2, d_hist, B, stream=0):
-        c = self._coef(coef)
-        check(lib().fdg_mc_accumulate_device_vegas(self._h, d_K or None, ks, kc, d_T or None, ts, tc, kF, beta, lam, d_weight or None,
-                                                   None if c is None else c.ctypes.data, seed, sample_offset, n_dim, n_grid,
-                                                   d_acc or None, d_acc2 or None, d_hist or None, B, stream))
+        self._accumulate("vegas", (d_K, ks, kc, d_T, ts, tc, kF, beta, lam), d_weight, self._coef(coef), seed, sample_offset, n_dim, n_grid,
+                         d_acc, d_acc2, d_hist, B, stream)
 
     # the same with a discrete variable: binned moments (the bits of the moments calls with this d_bin), the training histogram over the
     # samples whose bin is in range, and d_hist_bin[j] += (w[b] sum_k coef[k] root_k(b))^2 over the samples of bin j (0: not trained) (fdg.h)
     def accumulate_device_vegas_binned(self, d_leaf: int, ss: int, ls: int, lts: int, d_bin: int, bin_base: int, n_bin: int, d_weight: int,
                                        coef, seed: int, sample_offset: int, n_dim: int, n_grid: int, d_acc: int, d_acc2: int, d_hist: int,
                                        d_hist_bin: int, B: int, stream: int = 0):
-        c = self._coef(coef)
-        check(lib().fdg_accumulate_device_vegas_binned(self._h, d_leaf or None, ss, ls, lts, d_bin or None, bin_base, n_bin, d_weight or None,
-                                                       None if c is None else c.ctypes.data, seed, sample_offset, n_dim, n_grid,
-                                                       d_acc or None, d_acc2 or None, d_hist or None, d_hist_bin or None, B, stream))
+        self._accumulate("vegas_binned", (d_leaf, ss, ls, lts), d_bin, bin_base, n_bin, d_weight, self._coef(coef), seed, sample_offset,
+                         n_dim, n_grid, d_acc, d_acc2, d_hist, d_hist_bin, B, stream)
 
     def mc_accumulate_device_vegas_binned(self, d_K, ks, kc, d_T, ts, tc, kF, beta, lam, d_bin, bin_base, n_bin, d_weight, coef, seed,
                                           sample_offset, n_dim, n_grid, d_acc, d_acc2, d_hist, d_hist_bin, B, stream=0):
-        c = self._coef(coef)
-        check(lib().fdg_mc_accumulate_device_vegas_binned(self._h, d_K or None, ks, kc, d_T or None, ts, tc, kF, beta, lam, d_bin or None,
-                                                          bin_base, n_bin, d_weight or None, None if c is None else c.ctypes.data, seed,
-                                                          sample_offset, n_dim, n_grid, d_acc or None, d_acc2 or None, d_hist or None,
-                                                          d_hist_bin or None, B, stream))
+        self._accumulate("vegas_binned", (d_K, ks, kc, d_T, ts, tc, kF, beta, lam), d_bin, bin_base, n_bin, d_weight, self._coef(coef),
+                         seed, sample_offset, n_dim, n_grid, d_acc, d_acc2, d_hist, d_hist_bin, B, stream)
 
     # the projection onto Matsubara frequencies: desc = make_matsubara(...)[0]; d_bin 0: no discrete variable; d_acc and d_acc2 both 0: no
     # unprojected moments; n_dim 0 and d_hist 0: no training, else the bits of the VEGAS calls in d_hist (and d_hist_bin) (fdg.h)
     def accumulate_device_matsubara(self, d_leaf: int, ss: int, ls: int, lts: int, d_bin: int, bin_base: int, n_bin: int, d_weight: int,
                                     desc, coef=None, seed: int = 0, sample_offset: int = 0, n_dim: int = 0, n_grid: int = 0, d_acc: int = 0,
                                     d_acc2: int = 0, d_hist: int = 0, d_hist_bin: int = 0, B: int = 0, stream: int = 0):
-        c = self._coef(coef)
-        check(lib().fdg_accumulate_device_matsubara(self._h, d_leaf or None, ss, ls, lts, d_bin or None, bin_base, n_bin, d_weight or None,
-                                                    None if c is None else c.ctypes.data, seed, sample_offset, n_dim, n_grid,
-                                                    d_acc or None, d_acc2 or None, d_hist or None, d_hist_bin or None,
-                                                    None if desc is None else C.addressof(desc), B, stream))
+        self._accumulate("matsubara", (d_leaf, ss, ls, lts), d_bin, bin_base, n_bin, d_weight, self._coef(coef), seed, sample_offset,
+                         n_dim, n_grid, d_acc, d_acc2, d_hist, d_hist_bin, desc, B, stream)
 
     def mc_accumulate_device_matsubara(self, d_K, ks, kc, d_T, ts, tc, kF, beta, lam, d_bin, bin_base, n_bin, d_weight, desc, coef=None,
                                        seed=0, sample_offset=0, n_dim=0, n_grid=0, d_acc=0, d_acc2=0, d_hist=0, d_hist_bin=0, B=0, stream=0):
-        c = self._coef(coef)
-        check(lib().fdg_mc_accumulate_device_matsubara(self._h, d_K or None, ks, kc, d_T or None, ts, tc, kF, beta, lam, d_bin or None,
-                                                       bin_base, n_bin, d_weight or None, None if c is None else c.ctypes.data, seed,
-                                                       sample_offset, n_dim, n_grid, d_acc or None, d_acc2 or None, d_hist or None,
-                                                       d_hist_bin or None, None if desc is None else C.addressof(desc), B, stream))
+        self._accumulate("matsubara", (d_K, ks, kc, d_T, ts, tc, kF, beta, lam), d_bin, bin_base, n_bin, d_weight, self._coef(coef), seed,
+                         sample_offset, n_dim, n_grid, d_acc, d_acc2, d_hist, d_hist_bin, desc, B, stream)
 
     # weight groups: groups = make_weight_groups(...)[0], d_weight [n_group, stride]; desc None: no projection; the rest as the
     # projection calls take it (fdg.h)
     def accumulate_device_grouped(self, d_leaf: int, ss: int, ls: int, lts: int, d_bin: int, bin_base: int, n_bin: int, d_weight: int,
                                   groups, desc=None, coef=None, seed: int = 0, sample_offset: int = 0, n_dim: int = 0, n_grid: int = 0,
                                   d_acc: int = 0, d_acc2: int = 0, d_hist: int = 0, d_hist_bin: int = 0, B: int = 0, stream: int = 0):
-        c = self._coef(coef)
-        check(lib().fdg_accumulate_device_grouped(self._h, d_leaf or None, ss, ls, lts, d_bin or None, bin_base, n_bin, d_weight or None,
-                                                  None if c is None else c.ctypes.data, seed, sample_offset, n_dim, n_grid,
-                                                  d_acc or None, d_acc2 or None, d_hist or None, d_hist_bin or None,
-                                                  None if desc is None else C.addressof(desc),
-                                                  None if groups is None else C.addressof(groups), B, stream))
+        self._accumulate("grouped", (d_leaf, ss, ls, lts), d_bin, bin_base, n_bin, d_weight, self._coef(coef), seed, sample_offset, n_dim,
+                         n_grid, d_acc, d_acc2, d_hist, d_hist_bin, desc, groups, B, stream)
 
     def mc_accumulate_device_grouped(self, d_K, ks, kc, d_T, ts, tc, kF, beta, lam, d_bin, bin_base, n_bin, d_weight, groups, desc=None,
                                      coef=None, seed=0, sample_offset=0, n_dim=0, n_grid=0, d_acc=0, d_acc2=0, d_hist=0, d_hist_bin=0, B=0,
                                      stream=0):
-        c = self._coef(coef)
-        check(lib().fdg_mc_accumulate_device_grouped(self._h, d_K or None, ks, kc, d_T or None, ts, tc, kF, beta, lam, d_bin or None,
-                                                     bin_base, n_bin, d_weight or None, None if c is None else c.ctypes.data, seed,
-                                                     sample_offset, n_dim, n_grid, d_acc or None, d_acc2 or None, d_hist or None,
-                                                     d_hist_bin or None, None if desc is None else C.addressof(desc),
-                                                     None if groups is None else C.addressof(groups), B, stream))
+        self._accumulate("grouped", (d_K, ks, kc, d_T, ts, tc, kF, beta, lam), d_bin, bin_base, n_bin, d_weight, self._coef(coef), seed,
+                         sample_offset, n_dim, n_grid, d_acc, d_acc2, d_hist, d_hist_bin, desc, groups, B, stream)
 
     # observables: obs = make_observables(...)[0]; groups None: one weight column (or none with d_weight 0); d_acc and d_acc2 both 0:
     # no per-root moments; the rest as the grouped calls take it (fdg.h)
@@ -638,24 +618,14 @@ class GraphHandle:
                                       obs, groups=None, desc=None, coef=None, seed: int = 0, sample_offset: int = 0, n_dim: int = 0,
                                       n_grid: int = 0, d_acc: int = 0, d_acc2: int = 0, d_hist: int = 0, d_hist_bin: int = 0, B: int = 0,
                                       stream: int = 0):
-        c = self._coef(coef)
-        check(lib().fdg_accumulate_device_observables(self._h, d_leaf or None, ss, ls, lts, d_bin or None, bin_base, n_bin, d_weight or None,
-                                                      None if c is None else c.ctypes.data, seed, sample_offset, n_dim, n_grid,
-                                                      d_acc or None, d_acc2 or None, d_hist or None, d_hist_bin or None,
-                                                      None if desc is None else C.addressof(desc),
-                                                      None if groups is None else C.addressof(groups),
-                                                      None if obs is None else C.addressof(obs), B, stream))
+        self._accumulate("observables", (d_leaf, ss, ls, lts), d_bin, bin_base, n_bin, d_weight, self._coef(coef), seed, sample_offset,
+                         n_dim, n_grid, d_acc, d_acc2, d_hist, d_hist_bin, desc, groups, obs, B, stream)
 
     def mc_accumulate_device_observables(self, d_K, ks, kc, d_T, ts, tc, kF, beta, lam, d_bin, bin_base, n_bin, d_weight, obs, groups=None,
                                          desc=None, coef=None, seed=0, sample_offset=0, n_dim=0, n_grid=0, d_acc=0, d_acc2=0, d_hist=0,
                                          d_hist_bin=0, B=0, stream=0):
-        c = self._coef(coef)
-        check(lib().fdg_mc_accumulate_device_observables(self._h, d_K or None, ks, kc, d_T or None, ts, tc, kF, beta, lam, d_bin or None,
-                                                         bin_base, n_bin, d_weight or None, None if c is None else c.ctypes.data, seed,
-                                                         sample_offset, n_dim, n_grid, d_acc or None, d_acc2 or None, d_hist or None,
-                                                         d_hist_bin or None, None if desc is None else C.addressof(desc),
-                                                         None if groups is None else C.addressof(groups),
-                                                         None if obs is None else C.addressof(obs), B, stream))
+        self._accumulate("observables", (d_K, ks, kc, d_T, ts, tc, kF, beta, lam), d_bin, bin_base, n_bin, d_weight, self._coef(coef), seed,
+                         sample_offset, n_dim, n_grid, d_acc, d_acc2, d_hist, d_hist_bin, desc, groups, obs, B, stream)
 
     # frequency observables: fobs = make_freq_observables(...)[0] and desc (required: the frequencies, time labels, beta, T; its four
     # arrays all 0: no per-root projection); obs and groups may be None; the rest as the observables calls take it (fdg.h)
@@ -663,65 +633,40 @@ class GraphHandle:
                                            d_weight: int, fobs, desc, obs=None, groups=None, coef=None, seed: int = 0, sample_offset: int = 0,
                                            n_dim: int = 0, n_grid: int = 0, d_acc: int = 0, d_acc2: int = 0, d_hist: int = 0,
                                            d_hist_bin: int = 0, B: int = 0, stream: int = 0):
-        c = self._coef(coef)
-        check(lib().fdg_accumulate_device_freq_observables(self._h, d_leaf or None, ss, ls, lts, d_bin or None, bin_base, n_bin,
-                                                           d_weight or None, None if c is None else c.ctypes.data, seed, sample_offset,
-                                                           n_dim, n_grid, d_acc or None, d_acc2 or None, d_hist or None, d_hist_bin or None,
-                                                           None if desc is None else C.addressof(desc),
-                                                           None if groups is None else C.addressof(groups),
-                                                           None if obs is None else C.addressof(obs),
-                                                           None if fobs is None else C.addressof(fobs), B, stream))
+        self._accumulate("freq_observables", (d_leaf, ss, ls, lts), d_bin, bin_base, n_bin, d_weight, self._coef(coef), seed, sample_offset,
+                         n_dim, n_grid, d_acc, d_acc2, d_hist, d_hist_bin, desc, groups, obs, fobs, B, stream)
 
     def mc_accumulate_device_freq_observables(self, d_K, ks, kc, d_T, ts, tc, kF, beta, lam, d_bin, bin_base, n_bin, d_weight, fobs, desc,
                                               obs=None, groups=None, coef=None, seed=0, sample_offset=0, n_dim=0, n_grid=0, d_acc=0, d_acc2=0,
                                               d_hist=0, d_hist_bin=0, B=0, stream=0):
-        c = self._coef(coef)
-        check(lib().fdg_mc_accumulate_device_freq_observables(self._h, d_K or None, ks, kc, d_T or None, ts, tc, kF, beta, lam, d_bin or None,
-                                                              bin_base, n_bin, d_weight or None, None if c is None else c.ctypes.data, seed,
-                                                              sample_offset, n_dim, n_grid, d_acc or None, d_acc2 or None, d_hist or None,
-                                                              d_hist_bin or None, None if desc is None else C.addressof(desc),
-                                                              None if groups is None else C.addressof(groups),
-                                                              None if obs is None else C.addressof(obs),
-                                                              None if fobs is None else C.addressof(fobs), B, stream))
+        self._accumulate("freq_observables", (d_K, ks, kc, d_T, ts, tc, kF, beta, lam), d_bin, bin_base, n_bin, d_weight, self._coef(coef),
+                         seed, sample_offset, n_dim, n_grid, d_acc, d_acc2, d_hist, d_hist_bin, desc, groups, obs, fobs, B, stream)
 
     # the stratified accumulate step: the _vegas calls plus the training cells by the stratified formula (d_cube: the sampler's
     # hypercubes) and the per-hypercube moments d_cube_sum, d_cube_sum2 [H, n_root + 1]; strat: host sequence of n_dim counts (fdg.h)
     def accumulate_device_strat(self, d_leaf: int, ss: int, ls: int, lts: int, d_weight: int, coef, seed: int, sample_offset: int, n_dim: int,
                                 n_grid: int, d_acc: int, d_acc2: int, d_hist: int, strat, d_cube: int, d_cube_sum: int, d_cube_sum2: int,
                                 B: int, stream: int = 0):
-        c, sv = self._coef(coef), _strat_array(strat, n_dim)
-        check(lib().fdg_accumulate_device_strat(self._h, d_leaf or None, ss, ls, lts, d_weight or None, None if c is None else c.ctypes.data,
-                                                seed, sample_offset, n_dim, n_grid, d_acc or None, d_acc2 or None, d_hist or None,
-                                                sv.ctypes.data, d_cube or None, d_cube_sum or None, d_cube_sum2 or None, B, stream))
+        self._accumulate("strat", (d_leaf, ss, ls, lts), d_weight, self._coef(coef), seed, sample_offset, n_dim, n_grid, d_acc, d_acc2,
+                         d_hist, _strat_array(strat, n_dim), d_cube, d_cube_sum, d_cube_sum2, B, stream)
 
     def mc_accumulate_device_strat(self, d_K, ks, kc, d_T, ts, tc, kF, beta, lam, d_weight, coef, seed, sample_offset, n_dim, n_grid, d_acc,
                                    d_acc2, d_hist, strat, d_cube, d_cube_sum, d_cube_sum2, B, stream=0):
-        c, sv = self._coef(coef), _strat_array(strat, n_dim)
-        check(lib().fdg_mc_accumulate_device_strat(self._h, d_K or None, ks, kc, d_T or None, ts, tc, kF, beta, lam, d_weight or None,
-                                                   None if c is None else c.ctypes.data, seed, sample_offset, n_dim, n_grid,
-                                                   d_acc or None, d_acc2 or None, d_hist or None, sv.ctypes.data, d_cube or None,
-                                                   d_cube_sum or None, d_cube_sum2 or None, B, stream))
+        self._accumulate("strat", (d_K, ks, kc, d_T, ts, tc, kF, beta, lam), d_weight, self._coef(coef), seed, sample_offset, n_dim, n_grid,
+                         d_acc, d_acc2, d_hist, _strat_array(strat, n_dim), d_cube, d_cube_sum, d_cube_sum2, B, stream)
 
     # the stratified grouped accumulate step: the _strat calls plus groups = make_weight_groups(...)[0], d_weight [n_group, stride];
     # d_cube_sum, d_cube_sum2 [H, n_root + n_group] (fdg.h)
     def accumulate_device_strat_grouped(self, d_leaf: int, ss: int, ls: int, lts: int, d_weight: int, coef, seed: int, sample_offset: int,
                                         n_dim: int, n_grid: int, d_acc: int, d_acc2: int, d_hist: int, strat, d_cube: int, d_cube_sum: int,
                                         d_cube_sum2: int, groups, B: int, stream: int = 0):
-        c, sv = self._coef(coef), _strat_array(strat, n_dim)
-        check(lib().fdg_accumulate_device_strat_grouped(self._h, d_leaf or None, ss, ls, lts, d_weight or None,
-                                                        None if c is None else c.ctypes.data, seed, sample_offset, n_dim, n_grid,
-                                                        d_acc or None, d_acc2 or None, d_hist or None, sv.ctypes.data, d_cube or None,
-                                                        d_cube_sum or None, d_cube_sum2 or None,
-                                                        None if groups is None else C.addressof(groups), B, stream))
+        self._accumulate("strat_grouped", (d_leaf, ss, ls, lts), d_weight, self._coef(coef), seed, sample_offset, n_dim, n_grid, d_acc,
+                         d_acc2, d_hist, _strat_array(strat, n_dim), d_cube, d_cube_sum, d_cube_sum2, groups, B, stream)
 
     def mc_accumulate_device_strat_grouped(self, d_K, ks, kc, d_T, ts, tc, kF, beta, lam, d_weight, coef, seed, sample_offset, n_dim, n_grid,
                                            d_acc, d_acc2, d_hist, strat, d_cube, d_cube_sum, d_cube_sum2, groups, B, stream=0):
-        c, sv = self._coef(coef), _strat_array(strat, n_dim)
-        check(lib().fdg_mc_accumulate_device_strat_grouped(self._h, d_K or None, ks, kc, d_T or None, ts, tc, kF, beta, lam, d_weight or None,
-                                                           None if c is None else c.ctypes.data, seed, sample_offset, n_dim, n_grid,
-                                                           d_acc or None, d_acc2 or None, d_hist or None, sv.ctypes.data, d_cube or None,
-                                                           d_cube_sum or None, d_cube_sum2 or None,
-                                                           None if groups is None else C.addressof(groups), B, stream))
+        self._accumulate("strat_grouped", (d_K, ks, kc, d_T, ts, tc, kF, beta, lam), d_weight, self._coef(coef), seed, sample_offset, n_dim,
+                         n_grid, d_acc, d_acc2, d_hist, _strat_array(strat, n_dim), d_cube, d_cube_sum, d_cube_sum2, groups, B, stream)
 
     # one step of the Markov chain on the VEGAS map after fdg_chain_propose_device: evaluate the proposals (d_xp: [n_col, B] with column
     # stride xpc), fold, accept, select into the state (x, fac, root, a), measure into sum [n_root + 1, B] with FDG_CHAIN_MEASURE (fdg.h)
@@ -788,10 +733,9 @@ class GraphHandle:
         c = self._coef(coef)
         fn = getattr(lib(), ("fdg_chain_step_device" if mc is None else "fdg_mc_chain_step_device") + entry)
         descs = {"": (), "_matsubara": (desc,), "_grouped": (desc, groups), "_binned": (desc, groups)}[entry]
-        bins = (binned[0], binned[1] or None, binned[2] or None) if entry == "_binned" else ()
-        check(fn(self._h, d_xp or None, xpc, *(mc or ()), d_facp or None, n_col, n_dim, None if c is None else c.ctypes.data, gamma, seed,
-                 sample_offset, flags, d_x or None, xc, d_fac or None, d_root or None, d_a or None, d_sum or None, d_n_accept or None,
-                 *(None if d is None else C.addressof(d) for d in descs), *bins, B, stream))
+        bins = (binned[0], _ptr(binned[1]), _ptr(binned[2])) if entry == "_binned" else ()
+        check(fn(self._h, _ptr(d_xp), xpc, *(mc or ()), _ptr(d_facp), n_col, n_dim, _ptr(c), gamma, seed, sample_offset, flags, _ptr(d_x), xc,
+                 _ptr(d_fac), _ptr(d_root), _ptr(d_a), _ptr(d_sum), _ptr(d_n_accept), *(_ptr(d) for d in descs), *bins, B, stream))
 
     def _coef(self, coef):
         if coef is None:

@@ -55,7 +55,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass, field
-from typing import Callable, List, Optional, Sequence, Tuple
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -219,6 +219,96 @@ def _check_polar(polar, col, vmap, n_col):
     return groups
 
 
+# ---- the set-up the drivers share: each helper is called where its checks stand in that driver's sequence of refusals ---------------- #
+def _columns(func_or_handle, tables, col, polar, none_ok: bool):
+    """``(handle, n_col_k, n_col, col, written)``: the columns of ``x`` -- ``n_col_k`` momentum components, then the times; with
+    ``tables`` None (the leaf form) the graph's leaves --, ``col`` as ints (None kept where ``none_ok``: a grouped variable's entry)
+    and the columns the sampler writes, which must be distinct and inside ``x``."""
+    handle = getattr(func_or_handle, "handle", func_or_handle)
+    if tables is None:
+        n_col_k, n_col = 0, handle.table.n_leaf
+    else:
+        n_col_k = int(tables.n_loop) * int(tables.dim)
+        n_col = n_col_k + int(tables.n_tau)
+    col = [None if (c is None and none_ok) else int(c) for c in col]
+    written = [c for c in col if c is not None] + [int(c) for p in (polar or ()) for c in p.cols]
+    if len(set(written)) != len(written) or not all(0 <= c < n_col for c in written):
+        raise ValueError(f"col must name distinct columns in [0, {n_col})")
+    return handle, n_col_k, n_col, col, written
+
+
+def _check_ext_col(dmap, n_col: int, written, that_col: str):
+    """The discrete variable's columns lie inside ``x`` and apart from the sampler's; ``that_col``: the driver's own end of the message."""
+    if not all(0 <= e < n_col for e in dmap.ext_col) or set(dmap.ext_col) & set(written):
+        raise ValueError(f"dmap.ext_col must name columns in [0, {n_col}) {that_col}")
+
+
+def _map_for(vmap, lo, hi, n_grid, device, col) -> "VegasMap":
+    """``vmap``, or the flat map over ``[lo, hi]``; one variable per entry of ``col``."""
+    if vmap is None:
+        vmap = VegasMap(uniform_grid(lo, hi, n_grid), device)
+    if vmap.n_dim != len(col):
+        raise ValueError("one column per variable of the map")
+    return vmap
+
+
+def _polar_groups(polar, col, vmap, n_col):
+    """:func:`_check_polar`, and no variable outside the groups without a column."""
+    groups = _check_polar(polar, col, vmap, n_col)
+    if any(c is None for d, c in enumerate(col) if not any(v <= d < v + len(cs) for v, cs in groups)):
+        raise ValueError("only the variables of a polar group go without a column")
+    return groups
+
+
+def _check_weight_groups(wgroups, R: int, D: int, pgroups, limit: bool = True) -> int:
+    """The checks of a :class:`WeightGroups` against ``R`` roots, ``D`` variables and the polar groups; returns the number of groups.
+    ``limit`` False leaves FDG_WEIGHT_GROUP_MAX to the library (``vegas_integrate``, which never checked it on this side)."""
+    NG = len(wgroups.var_sets)
+    if len(wgroups.root_group) != R or not all(0 <= int(v) < NG for v in wgroups.root_group):
+        raise ValueError("groups.root_group names one group of groups.var_sets per root")
+    if limit and not 1 <= NG <= capi.FDG_WEIGHT_GROUP_MAX:
+        raise ValueError(f"need 1 .. {capi.FDG_WEIGHT_GROUP_MAX} weight groups")
+    if not all(0 <= int(d) < D for vs in wgroups.var_sets for d in vs):
+        raise ValueError("groups.var_sets names variables of the map")
+    for var, cs in pgroups or ():
+        if any(0 < len(set(int(d) for d in vs) & set(range(var, var + len(cs)))) < len(cs) for vs in wgroups.var_sets):
+            raise ValueError("a polar group belongs to a weight group whole or not at all")
+    return NG
+
+
+def _fixed(fixed, n_col: int) -> np.ndarray:
+    fx = np.zeros(n_col) if fixed is None else np.asarray(fixed, dtype=np.float64)
+    if fx.shape != (n_col,):
+        raise ValueError(f"fixed must hold {n_col} column values")
+    return fx
+
+
+def _state(fx, B: int, device):
+    """``x [n_col, B]`` on the device, sample stride 1: every column at its fixed value."""
+    import torch
+    return torch.from_numpy(fx).to(device)[:, None].repeat(1, B).contiguous()
+
+
+class _Discrete(NamedTuple):
+    """The discrete variable's arguments of the samplers, proposals and steps.  The defaults are what those calls take without one."""
+    d_cdf: int = 0
+    n_bin: int = 0
+    bin_base: int = 0
+    d_ext: int = 0
+    ext_col: Optional[Sequence[int]] = None
+    d_bin: int = 0
+    d_binp: int = 0
+
+
+def _discrete(dmap, none_bins: int, bins=None, binp=None) -> _Discrete:
+    """The pack of ``dmap`` with the walkers' or samples' values in ``bins`` (and the proposals' in ``binp``); ``dmap`` None: the
+    defaults with ``n_bin = none_bins`` (the direct sampler counts one bin then, the chain none)."""
+    if dmap is None:
+        return _Discrete(n_bin=none_bins)
+    return _Discrete(dmap.d_cdf.data_ptr(), dmap.n_bin, 0, 0 if dmap.d_ext is None else dmap.d_ext.data_ptr(), dmap.ext_col,
+                     bins.data_ptr(), 0 if binp is None else binp.data_ptr())
+
+
 @dataclass(frozen=True)
 class MatsubaraProjection:
     """The frequencies an integration projects its roots onto: ``freq`` the integers ``n`` of ``omega_n = (2n+1) pi / beta``
@@ -314,37 +404,13 @@ def _integrate_strat(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_iter,
     refine the map, fdg_strat_allocate_cols.  Without ``polar`` and ``wgroups`` the device calls are the plain stratified ones."""
     import torch
     from .nodetable import FDG_NO_ROOT
-    handle = getattr(func_or_handle, "handle", func_or_handle)
     device = torch.device(device)
+    handle, n_col_k, n_col, col, _ = _columns(func_or_handle, tables, col, polar, bool(polar))
     R = handle.table.n_root
-    if tables is None:
-        n_col_k, n_col = 0, handle.table.n_leaf          # the leaf form: the columns of x are the graph's leaves
-    else:
-        n_col_k = int(tables.n_loop) * int(tables.dim)
-        n_col = n_col_k + int(tables.n_tau)
-    col = [None if (c is None and polar) else int(c) for c in col]
-    written = [c for c in col if c is not None] + [int(c) for p in (polar or ()) for c in p.cols]
-    if len(set(written)) != len(written) or not all(0 <= c < n_col for c in written):
-        raise ValueError(f"col must name distinct columns in [0, {n_col})")
-    if vmap is None:
-        vmap = VegasMap(uniform_grid(lo, hi, n_grid), device)
-    if vmap.n_dim != len(col):
-        raise ValueError("one column per variable of the map")
-    groups = _check_polar(polar, col, vmap, n_col) if polar else None
-    if polar and any(c is None for d, c in enumerate(col) if not any(v <= d < v + len(cs) for v, cs in groups)):
-        raise ValueError("only the variables of a polar group go without a column")
+    vmap = _map_for(vmap, lo, hi, n_grid, device, col)
+    groups = _polar_groups(polar, col, vmap, n_col) if polar else None
     D, G = vmap.n_dim, vmap.n_grid
-    if wgroups is not None:
-        if len(wgroups.root_group) != R or not all(0 <= int(v) < len(wgroups.var_sets) for v in wgroups.root_group):
-            raise ValueError("groups.root_group names one group of groups.var_sets per root")
-        if not 1 <= len(wgroups.var_sets) <= capi.FDG_WEIGHT_GROUP_MAX:
-            raise ValueError(f"need 1 .. {capi.FDG_WEIGHT_GROUP_MAX} weight groups")
-        if not all(0 <= int(d) < D for vs in wgroups.var_sets for d in vs):
-            raise ValueError("groups.var_sets names variables of the map")
-        for var, cs in groups or ():
-            if any(0 < len(set(vs) & set(range(var, var + len(cs)))) < len(cs) for vs in wgroups.var_sets):
-                raise ValueError("a polar group belongs to a weight group whole or not at all")
-    NG = 1 if wgroups is None else len(wgroups.var_sets)      # the columns behind the roots' in the per-hypercube moments
+    NG = 1 if wgroups is None else _check_weight_groups(wgroups, R, D, groups)      # the columns behind the roots' in the per-hypercube moments
     sv = tuple(int(v) for v in strat.strat)
     if len(sv) != D or not all(v >= 1 for v in sv):
         raise ValueError("strat.strat holds one count >= 1 per variable of the map")
@@ -368,14 +434,13 @@ def _integrate_strat(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_iter,
         raise ValueError(f"alloc_cols names at least one column in [0, {R + NG}) of the per-hypercube moments")
     if specialize_fused and tables is not None:
         handle.specialize_fused(tables)
-    fx = np.zeros(n_col) if fixed is None else np.asarray(fixed, dtype=np.float64)
-    if fx.shape != (n_col,):
-        raise ValueError(f"fixed must hold {n_col} column values")
+    fx = _fixed(fixed, n_col)
     out = VegasResult(np.zeros(R), np.zeros(R), np.full(R, np.nan), map=vmap)
     start = capi.strat_allocate_cols(None, None, alloc_cols, None, H, N, strat.beta)
     with torch.cuda.device(device):
         st = torch.cuda.current_stream(device).cuda_stream
-        x = torch.from_numpy(fx).to(device)[:, None].repeat(1, B).contiguous()          # [n_col, B]: sample stride 1
+        x = _state(fx, B, device)
+        src = (x.data_ptr(), 1, B, 0) if tables is None else (x.data_ptr(), 1, B, x.data_ptr() + 8 * n_col_k * B, 1, B, kF, beta, lam)
         jac = torch.empty(B if wgroups is None else (NG, B), dtype=torch.float64, device=device)
         cube = torch.empty(B, dtype=torch.int32, device=device)
         wdesc = None
@@ -394,14 +459,9 @@ def _integrate_strat(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_iter,
             else:
                 capi.vegas_sample_device_strat(vmap.d_grid.data_ptr(), D, G, col, sv, d_start.data_ptr(), key, off, x.data_ptr(), 1, B,
                                                jac.data_ptr(), cube.data_ptr(), 0, B, st)
-            tail = (jac.data_ptr(), coef, key, off, D, G, m[0].data_ptr(), m[1].data_ptr(), hist.data_ptr(), sv, cube.data_ptr(),
-                    cs[0].data_ptr(), cs[1].data_ptr()) + (() if wgroups is None else (wdesc,)) + (B, st)
-            leaf_call = handle.accumulate_device_strat if wgroups is None else handle.accumulate_device_strat_grouped
-            mc_call = handle.mc_accumulate_device_strat if wgroups is None else handle.mc_accumulate_device_strat_grouped
-            if tables is None:
-                leaf_call(x.data_ptr(), 1, B, 0, *tail)
-            else:
-                mc_call(x.data_ptr(), 1, B, x.data_ptr() + 8 * n_col_k * B, 1, B, kF, beta, lam, *tail)
+            handle._accumulate("strat" if wgroups is None else "strat_grouped", src, jac.data_ptr(), handle._coef(coef), key, off, D, G,
+                               m[0].data_ptr(), m[1].data_ptr(), hist.data_ptr(), capi._strat_array(sv, D), cube.data_ptr(),
+                               cs[0].data_ptr(), cs[1].data_ptr(), *(() if wgroups is None else (wdesc,)), B, st)
             if reduce is not None:
                 for t in (m, hist, cs):
                     reduce(t)
@@ -476,35 +536,19 @@ def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter,
     if freq_observables is not None and matsubara is None:
         raise ValueError("freq_observables needs matsubara: the frequencies and the roots' time labels")
     import torch
-    handle = getattr(func_or_handle, "handle", func_or_handle)
     device = torch.device(device)
-    n_col_k, n_tau = int(tables.n_loop) * int(tables.dim), int(tables.n_tau)
-    n_col, R = n_col_k + n_tau, handle.table.n_root
-    col = [None if (c is None and polar) else int(c) for c in col]
-    written = [c for c in col if c is not None] + [c for p in (polar or ()) for c in p.cols]
-    if len(set(written)) != len(written) or not all(0 <= c < n_col for c in written):
-        raise ValueError(f"col must name distinct columns in [0, {n_col})")
+    n_tau = int(tables.n_tau)                              # (tables is required: this driver has no leaf form)
+    handle, n_col_k, n_col, col, written = _columns(func_or_handle, tables, col, polar, bool(polar))
+    R = handle.table.n_root
     if dmap is not None:
-        if not all(0 <= e < n_col for e in dmap.ext_col) or set(dmap.ext_col) & set(written):
-            raise ValueError(f"dmap.ext_col must name columns in [0, {n_col}) that col does not")
+        _check_ext_col(dmap, n_col, written, "that col does not")
         if dmap.device != device:
             raise ValueError("dmap lives on another device")
-    if vmap is None:
-        vmap = VegasMap(uniform_grid(lo, hi, n_grid), device)
-    if vmap.n_dim != len(col):
-        raise ValueError("one column per variable of the map")
-    groups = _check_polar(polar, col, vmap, n_col) if polar else None
-    if polar and any(c is None for d, c in enumerate(col) if not any(v <= d < v + len(cs) for v, cs in groups)):
-        raise ValueError("only the variables of a polar group go without a column")
+    vmap = _map_for(vmap, lo, hi, n_grid, device, col)
+    groups = _polar_groups(polar, col, vmap, n_col) if polar else None
     D, G, NB = vmap.n_dim, vmap.n_grid, 1 if dmap is None else dmap.n_bin
     if wgroups is not None:
-        if len(wgroups.root_group) != R or not all(0 <= int(v) < len(wgroups.var_sets) for v in wgroups.root_group):
-            raise ValueError("groups.root_group names one group of groups.var_sets per root")
-        if not all(0 <= int(d) < D for vs in wgroups.var_sets for d in vs):
-            raise ValueError("groups.var_sets names variables of the map")
-        for var, cs in groups or ():
-            if any(0 < len(set(vs) & set(range(var, var + len(cs)))) < len(cs) for vs in wgroups.var_sets):
-                raise ValueError("a polar group belongs to a weight group whole or not at all")
+        _check_weight_groups(wgroups, R, D, groups, limit=False)
     ocoef = None
     if observables is not None:
         ocoef = np.ascontiguousarray(observables.coef, dtype=np.float64)
@@ -521,9 +565,7 @@ def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter,
         raise ValueError("need n_sample >= 1, n_total >= 2 and 0 <= n_discard < n_iter")
     if specialize_fused:
         handle.specialize_fused(tables)
-    fx = np.zeros(n_col) if fixed is None else np.asarray(fixed, dtype=np.float64)
-    if fx.shape != (n_col,):
-        raise ValueError(f"fixed must hold {n_col} column values")
+    fx = _fixed(fixed, n_col)
     shape = (R,) if dmap is None else (NB, R)
     if matsubara is not None:
         NF = len(matsubara.freq)
@@ -538,84 +580,65 @@ def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter,
         out = VegasBinnedResult(np.zeros(shape), np.zeros(shape), np.full(shape, np.nan), map=vmap, dmap=dmap)
     with torch.cuda.device(device):
         st = torch.cuda.current_stream(device).cuda_stream
-        x = torch.from_numpy(fx).to(device)[:, None].repeat(1, B).contiguous()          # [n_col, B]: sample stride 1
+        x = _state(fx, B, device)
         jac = torch.empty(B if wgroups is None else (len(wgroups.var_sets), B), dtype=torch.float64, device=device)
         wdesc = None
         if wgroups is not None:
             wdesc, _wkeep = capi.make_weight_groups(wgroups.root_group, wgroups.var_sets, B)
-        d_T = x.data_ptr() + 8 * n_col_k * B
-        if dmap is not None:
-            bins = torch.empty(B, dtype=torch.int32, device=device)
-            d_ext = 0 if dmap.d_ext is None else dmap.d_ext.data_ptr()
+        src = (x.data_ptr(), 1, B, x.data_ptr() + 8 * n_col_k * B, 1, B, kF, beta, lam)
+        bins = None if dmap is None else torch.empty(B, dtype=torch.int32, device=device)
+        dv = _discrete(dmap, 1, bins)
+        f64 = dict(dtype=torch.float64, device=device)
         for it in range(int(n_iter)):
             off = it * N + int(shard_start)
-            m = torch.zeros((2, NB, R), dtype=torch.float64, device=device)
-            hist = torch.zeros((D, G), dtype=torch.float64, device=device)
+            # the moments, or (re, im, re^2, im^2) of the projected roots; the training histograms are the same with and without a projection
+            m = torch.zeros((2, NB, R) if matsubara is None else (4, NB, NF, R), **f64)
+            hist = torch.zeros((D, G), **f64)
+            hist_bin = None if dmap is None else torch.zeros(NB, **f64)
+            sample = (seed, off, x.data_ptr(), 1, B, jac.data_ptr(), dv.d_bin, 0, B, st)
             if wgroups is not None:
-                capi.vegas_sample_device_grouped(vmap.d_grid.data_ptr(), D, G, col, 0 if dmap is None else dmap.d_cdf.data_ptr(), NB, 0,
-                                                 0 if dmap is None else d_ext, None if dmap is None else dmap.ext_col, groups,
-                                                 wgroups.var_sets, B, seed, off, x.data_ptr(), 1, B, jac.data_ptr(),
-                                                 0 if dmap is None else bins.data_ptr(), 0, B, st)
+                capi.vegas_sample_device_grouped(vmap.d_grid.data_ptr(), D, G, col, dv.d_cdf, dv.n_bin, dv.bin_base, dv.d_ext, dv.ext_col, groups,
+                                                 wgroups.var_sets, B, *sample)
             elif groups:
-                capi.vegas_sample_device_polar(vmap.d_grid.data_ptr(), D, G, col, 0 if dmap is None else dmap.d_cdf.data_ptr(), NB, 0,
-                                               0 if dmap is None else d_ext, None if dmap is None else dmap.ext_col, groups, seed, off,
-                                               x.data_ptr(), 1, B, jac.data_ptr(), 0 if dmap is None else bins.data_ptr(), 0, B, st)
+                capi.vegas_sample_device_polar(vmap.d_grid.data_ptr(), D, G, col, dv.d_cdf, dv.n_bin, dv.bin_base, dv.d_ext, dv.ext_col, groups,
+                                               *sample)
             elif dmap is None:
                 capi.vegas_sample_device(vmap.d_grid.data_ptr(), D, G, col, seed, off, x.data_ptr(), 1, B, jac.data_ptr(), 0, B, st)
             else:
-                capi.vegas_sample_device_discrete(vmap.d_grid.data_ptr(), D, G, col, dmap.d_cdf.data_ptr(), NB, 0, d_ext, dmap.ext_col, seed,
-                                                  off, x.data_ptr(), 1, B, jac.data_ptr(), bins.data_ptr(), 0, B, st)
+                capi.vegas_sample_device_discrete(vmap.d_grid.data_ptr(), D, G, col, dv.d_cdf, dv.n_bin, dv.bin_base, dv.d_ext, dv.ext_col, *sample)
+            desc = odesc = fdesc = None
             osums, fsums = [], []
-            if wgroups is not None or ocoef is not None or fcoef is not None:
-                # one call for every combination: the projection, the discrete variable (and, beside observables, the groups) are optional in it
-                desc, hist_bin = None, None if dmap is None else torch.zeros(NB, dtype=torch.float64, device=device)
-                if matsubara is not None:
-                    m = torch.zeros((4, NB, NF, R), dtype=torch.float64, device=device)
-                    desc, _keep = capi.make_matsubara(matsubara.freq, matsubara.fermionic, matsubara.root_tau_in, matsubara.root_tau_out,
-                                                      beta, n_tau, *[m[i].data_ptr() for i in range(4)])
-                blocks = (desc, coef, seed, off, D, G, 0 if matsubara is not None else m[0].data_ptr(),
-                          0 if matsubara is not None else m[1].data_ptr(), hist.data_ptr(), 0 if dmap is None else hist_bin.data_ptr(), B, st)
-                odesc = None
-                if ocoef is not None:
-                    M = ocoef.shape[0]
-                    osums = [torch.zeros((NB, M), dtype=torch.float64, device=device), torch.zeros((NB, M, M), dtype=torch.float64, device=device)]
-                    odesc, _okeep = capi.make_observables(ocoef, osums[0].data_ptr(), osums[1].data_ptr())
-                if fcoef is not None:
-                    # the one call that carries every other block: the projection (always: its results are reported), ob and wg optional
-                    P = 2 * fcoef.shape[0]
-                    fsums = [torch.zeros((NB, NF, P), dtype=torch.float64, device=device),
-                             torch.zeros((NB, NF, P, P), dtype=torch.float64, device=device)]
-                    fdesc, _fkeep = capi.make_freq_observables(fcoef, fsums[0].data_ptr(), fsums[1].data_ptr())
-                    handle.mc_accumulate_device_freq_observables(x.data_ptr(), 1, B, d_T, 1, B, kF, beta, lam,
-                                                                 0 if dmap is None else bins.data_ptr(), 0, NB, jac.data_ptr(), fdesc, blocks[0],
-                                                                 odesc, wdesc, *blocks[1:])
-                elif ocoef is not None:
-                    handle.mc_accumulate_device_observables(x.data_ptr(), 1, B, d_T, 1, B, kF, beta, lam,
-                                                            0 if dmap is None else bins.data_ptr(), 0, NB, jac.data_ptr(), odesc, wdesc, *blocks)
-                else:
-                    handle.mc_accumulate_device_grouped(x.data_ptr(), 1, B, d_T, 1, B, kF, beta, lam, 0 if dmap is None else bins.data_ptr(), 0,
-                                                        NB, jac.data_ptr(), wdesc, *blocks)
-                sums = [m, hist] if dmap is None else [m, hist, hist_bin]
-            elif matsubara is not None:
-                # (re, im, re^2, im^2) of the projected roots; the training histograms as the calls below leave them
-                m = torch.zeros((4, NB, NF, R), dtype=torch.float64, device=device)
-                hist_bin = None if dmap is None else torch.zeros(NB, dtype=torch.float64, device=device)
+            if matsubara is not None:
                 desc, _keep = capi.make_matsubara(matsubara.freq, matsubara.fermionic, matsubara.root_tau_in, matsubara.root_tau_out, beta,
                                                   n_tau, *[m[i].data_ptr() for i in range(4)])
-                handle.mc_accumulate_device_matsubara(x.data_ptr(), 1, B, d_T, 1, B, kF, beta, lam, 0 if dmap is None else bins.data_ptr(), 0,
-                                                      NB, jac.data_ptr(), desc, coef, seed, off, D, G, 0, 0, hist.data_ptr(),
-                                                      0 if dmap is None else hist_bin.data_ptr(), B, st)
-                sums = [m, hist] if dmap is None else [m, hist, hist_bin]
-            elif dmap is None:
-                handle.mc_accumulate_device_vegas(x.data_ptr(), 1, B, d_T, 1, B, kF, beta, lam, jac.data_ptr(), coef, seed, off, D, G,
-                                                  m[0].data_ptr(), m[1].data_ptr(), hist.data_ptr(), B, st)
-                sums = [m, hist]
+            if ocoef is not None:
+                M = ocoef.shape[0]
+                osums = [torch.zeros((NB, M), **f64), torch.zeros((NB, M, M), **f64)]
+                odesc, _okeep = capi.make_observables(ocoef, osums[0].data_ptr(), osums[1].data_ptr())
+            if fcoef is not None:
+                P = 2 * fcoef.shape[0]
+                fsums = [torch.zeros((NB, NF, P), **f64), torch.zeros((NB, NF, P, P), **f64)]
+                fdesc, _fkeep = capi.make_freq_observables(fcoef, fsums[0].data_ptr(), fsums[1].data_ptr())
+            # the narrowest entry that carries what was asked for.  Each of these takes the blocks of the ones below it, every one
+            # optional in it (a null descriptor, d_bin 0), and leaves their bits as they are; with a projection the unprojected
+            # moments are not taken (d_acc, d_acc2 0)
+            if fcoef is not None:
+                entry, descs = "freq_observables", (desc, wdesc, odesc, fdesc)
+            elif ocoef is not None:
+                entry, descs = "observables", (desc, wdesc, odesc)
+            elif wgroups is not None:
+                entry, descs = "grouped", (desc, wdesc)
+            elif matsubara is not None:
+                entry, descs = "matsubara", (desc,)
             else:
-                hist_bin = torch.zeros(NB, dtype=torch.float64, device=device)
-                handle.mc_accumulate_device_vegas_binned(x.data_ptr(), 1, B, d_T, 1, B, kF, beta, lam, bins.data_ptr(), 0, NB, jac.data_ptr(),
-                                                         coef, seed, off, D, G, m[0].data_ptr(), m[1].data_ptr(), hist.data_ptr(),
-                                                         hist_bin.data_ptr(), B, st)
-                sums = [m, hist, hist_bin]
+                entry, descs = "vegas" if dmap is None else "vegas_binned", ()
+            head = (dv.d_bin, dv.bin_base, NB, jac.data_ptr())
+            block = (handle._coef(coef), seed, off, D, G, 0 if matsubara is not None else m[0].data_ptr(),
+                     0 if matsubara is not None else m[1].data_ptr(), hist.data_ptr(), 0 if dmap is None else hist_bin.data_ptr())
+            if entry == "vegas":                             # the one entry without the discrete variable's arguments
+                head, block = head[3:], block[:-1]
+            handle._accumulate(entry, src, *head, *block, *descs, B, st)
+            sums = [m, hist] if dmap is None else [m, hist, hist_bin]
             if reduce is not None:
                 for t in sums + osums + fsums:
                     reduce(t)
@@ -1187,23 +1210,15 @@ def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step,
     :func:`chain_integrate_binned`, with ``polar`` of :func:`chain_integrate_polar`, and with ``shift`` of
     :func:`chain_integrate_shift` (the moves are then its pairs, and ``moves`` is None)."""
     import torch
-    handle = getattr(func_or_handle, "handle", func_or_handle)
     device = torch.device(device)
+    handle, n_col_k, n_col, col, written = _columns(func_or_handle, tables, col, polar, polar is not None)
     R = handle.table.n_root
-    if tables is None:
-        n_col = handle.table.n_leaf
-    else:
-        n_col = int(tables.n_loop) * int(tables.dim) + int(tables.n_tau)
-    col = [None if (c is None and polar is not None) else int(c) for c in col]
-    written = [c for c in col if c is not None] + [int(c) for p in (polar or ()) for c in p.cols]
-    if len(set(written)) != len(written) or not all(0 <= c < n_col for c in written):
-        raise ValueError(f"col must name distinct columns in [0, {n_col})")
     F, desc = 0, None
     if matsubara is not None:
         if not isinstance(matsubara, MatsubaraProjection):
             raise ValueError("matsubara must be a MatsubaraProjection")
         F = len(matsubara.freq)
-        t0, n_time = (0, n_col) if tables is None else (int(tables.n_loop) * int(tables.dim), int(tables.n_tau))
+        t0, n_time = n_col_k, n_col - n_col_k                # (the leaf form: every column counts as a time)
         if not 1 <= F <= capi.FDG_MATSUBARA_FREQ_MAX:
             raise ValueError(f"matsubara needs 1 .. {capi.FDG_MATSUBARA_FREQ_MAX} frequencies")
         if not 0 <= int(weight_freq) < F:
@@ -1229,8 +1244,7 @@ def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step,
         n_bin = dmap.n_bin
         if n_bin > capi.FDG_CHAIN_BIN_MAX:
             raise ValueError(f"the chain takes at most {capi.FDG_CHAIN_BIN_MAX} values of the discrete variable")
-        if not all(0 <= e < n_col for e in dmap.ext_col) or set(dmap.ext_col) & set(written):
-            raise ValueError(f"dmap.ext_col must name columns in [0, {n_col}) that col does not name")
+        _check_ext_col(dmap, n_col, written, "that col does not name")
         if len(col) >= capi.FDG_VEGAS_DIM_MAX:
             raise ValueError(f"a discrete variable leaves room for {capi.FDG_VEGAS_DIM_MAX - 1} continuous ones")
         if tables is None and int(n_warm) > 0:
@@ -1244,17 +1258,12 @@ def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step,
         raise ValueError("gamma must be finite and > 0")
     if gamma is None and not (math.isfinite(gamma_rel) and gamma_rel > 0.0):
         raise ValueError("gamma_rel must be finite and > 0")
-    if vmap is None:
-        vmap = VegasMap(uniform_grid(lo, hi, n_grid), device)
-    if vmap.n_dim != len(col):
-        raise ValueError("one column per variable of the map")
+    vmap = _map_for(vmap, lo, hi, n_grid, device, col)
     D, G = vmap.n_dim, vmap.n_grid
     DV = D + 1 if dmap is not None else D                   # the variables a move can name: bit D is the discrete one
     pgroups = None
     if polar is not None:
-        pgroups = _check_polar(polar, col, vmap, n_col)
-        if any(c is None for d, c in enumerate(col) if not any(v <= d < v + len(cs) for v, cs in pgroups)):
-            raise ValueError("only the variables of a polar group go without a column")
+        pgroups = _polar_groups(polar, col, vmap, n_col)
         pbits = [((1 << len(cs)) - 1) << v for v, cs in pgroups]
         if moves is None and shift is None:
             moves = chain_moves_polar(DV, pgroups)
@@ -1282,21 +1291,10 @@ def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step,
         raise ValueError("moves holds masks over the variables of the map" + (" and the discrete variable" if dmap is not None else ""))
     if polar is not None and any((m & bits) not in (0, bits) for m in moves for bits in pbits):
         raise ValueError("a move redraws a polar group whole or not at all: the state does not hold (k, theta, phi)")
-    fx = np.zeros(n_col) if fixed is None else np.asarray(fixed, dtype=np.float64)
-    if fx.shape != (n_col,):
-        raise ValueError(f"fixed must hold {n_col} column values")
+    fx = _fixed(fixed, n_col)
     rho = None
     if wgroups is not None:
-        NG = len(wgroups.var_sets)
-        if len(wgroups.root_group) != R or not all(0 <= int(v) < NG for v in wgroups.root_group):
-            raise ValueError("groups.root_group names one group of groups.var_sets per root")
-        if not 1 <= NG <= capi.FDG_WEIGHT_GROUP_MAX:
-            raise ValueError(f"need 1 .. {capi.FDG_WEIGHT_GROUP_MAX} weight groups")
-        if not all(0 <= int(d) < D for vs in wgroups.var_sets for d in vs):
-            raise ValueError("groups.var_sets names variables of the map")
-        for var, cs in pgroups or ():
-            if any(0 < len(set(int(d) for d in vs) & set(range(var, var + len(cs)))) < len(cs) for vs in wgroups.var_sets):
-                raise ValueError("a polar group belongs to a weight group whole or not at all")
+        NG = _check_weight_groups(wgroups, R, D, pgroups)
         if coef is not None and np.shape(coef) != (R,):
             raise ValueError(f"coef must hold n_root = {R} factors")
         if reweight is not None:
@@ -1328,42 +1326,32 @@ def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step,
     with torch.cuda.device(device):
         st = torch.cuda.current_stream(device).cuda_stream
         f64 = dict(dtype=torch.float64, device=device)
-        x = torch.from_numpy(fx).to(device)[:, None].repeat(1, B).contiguous()            # [n_col, B]: sample stride 1
+        x = _state(fx, B, device)
         xp = torch.empty_like(x)
         fac, facp = torch.ones((DV, B), **f64), torch.empty((DV, B), **f64)          # (row D: the discrete variable's 1 / p_j)
         bins = binp = None
         if dmap is not None:
             bins, binp = (torch.zeros(B, dtype=torch.int32, device=device) for _ in range(2))
+        dv = _discrete(dmap, 0, bins, binp)
         root, a = torch.zeros((R, B), **f64), torch.zeros(B, **f64)
         total = torch.zeros((C + 1, B), **f64)
         n_acc = torch.zeros(B, dtype=torch.int32, device=device)
 
         def step(mask, off, g, flags, lmask=0):
+            grid = (vmap.d_grid.data_ptr(), D, G, col, n_col)
+            walk = (seed, off, x.data_ptr(), B, fac.data_ptr(), xp.data_ptr(), B, facp.data_ptr())
+            disc = (bool((mask >> D) & 1), dv.d_cdf, dv.n_bin, dv.d_ext, dv.ext_col, dv.d_bin, dv.d_binp)
             if shift is not None:
-                capi.chain_propose_device_local(vmap.d_grid.data_ptr(), D, G, col, n_col, mask & all_mask, lmask, width, seed, off, x.data_ptr(),
-                                                B, fac.data_ptr(), xp.data_ptr(), B, facp.data_ptr(), bool((mask >> D) & 1),
-                                                0 if dmap is None else dmap.d_cdf.data_ptr(), n_bin,
-                                                0 if dmap is None or dmap.d_ext is None else dmap.d_ext.data_ptr(),
-                                                None if dmap is None else dmap.ext_col, 0 if dmap is None else bins.data_ptr(),
-                                                0 if dmap is None else binp.data_ptr(), pgroups or (), B, st)
+                capi.chain_propose_device_local(*grid, mask & all_mask, lmask, width, *walk, *disc, pgroups or (), B, st)
             elif polar is not None:
-                capi.chain_propose_device_polar(vmap.d_grid.data_ptr(), D, G, col, n_col, mask & all_mask, seed, off, x.data_ptr(), B,
-                                                fac.data_ptr(), xp.data_ptr(), B, facp.data_ptr(), bool((mask >> D) & 1),
-                                                0 if dmap is None else dmap.d_cdf.data_ptr(), n_bin,
-                                                0 if dmap is None or dmap.d_ext is None else dmap.d_ext.data_ptr(),
-                                                None if dmap is None else dmap.ext_col, 0 if dmap is None else bins.data_ptr(),
-                                                0 if dmap is None else binp.data_ptr(), pgroups, B, st)
+                capi.chain_propose_device_polar(*grid, mask & all_mask, *walk, *disc, pgroups, B, st)
             elif dmap is None:
-                capi.chain_propose_device(vmap.d_grid.data_ptr(), D, G, col, n_col, mask, seed, off, x.data_ptr(), B, fac.data_ptr(),
-                                          xp.data_ptr(), B, facp.data_ptr(), B, st)
+                capi.chain_propose_device(*grid, mask, *walk, B, st)
             else:
-                capi.chain_propose_device_discrete(vmap.d_grid.data_ptr(), D, G, col, n_col, mask & all_mask, seed, off, x.data_ptr(), B,
-                                                   fac.data_ptr(), xp.data_ptr(), B, facp.data_ptr(), bool((mask >> D) & 1),
-                                                   dmap.d_cdf.data_ptr(), n_bin, 0 if dmap.d_ext is None else dmap.d_ext.data_ptr(),
-                                                   dmap.ext_col, bins.data_ptr(), binp.data_ptr(), B, st)
+                capi.chain_propose_device_discrete(*grid, mask & all_mask, *walk, *disc, B, st)
             handle._chain_step(entry, mc, xp.data_ptr(), B, facp.data_ptr(), n_col, D, coef, g, seed, off, flags, x.data_ptr(), B,
                                fac.data_ptr(), root.data_ptr(), a.data_ptr(), total.data_ptr(), n_acc.data_ptr(), B, st, desc, gdesc,
-                               None if dmap is None else (n_bin, binp.data_ptr(), bins.data_ptr()))
+                               None if dmap is None else (dv.n_bin, dv.d_binp, dv.d_bin))
 
         entry = "_binned" if dmap is not None else "_grouped" if wgroups is not None else "_matsubara" if desc is not None else ""
         mc = None if tables is None else (kF, beta, lam)
