@@ -51,6 +51,10 @@
 // first moment and the covariance of sums, differences and series of roots, which the per-root acc2 cannot give because all roots
 // share their samples.  A kernel of its own: every instance above is the code it was.
 //
+// Frequency observables (fdg_[mc_]accumulate_device_freq_observables): the same over the PROJECTED roots (fdg_fobs_partials below), 2 M
+// components per frequency in the place of the rows.  The two passes share everything but their partials kernels: one plan
+// (obs_plan), one table builder (obs_tables), one reduce (fdg_obs_reduce) and one host path (ObsPass).
+//
 // Adaptive stratified sampling (fdg_vegas_sample_device_strat, fdg_[mc_]accumulate_device_strat, fdg_strat_allocate): the unit cube of
 // the map's coordinates is cut into H hypercubes whose samples are contiguous; the sampler finds a sample's hypercube by a binary
 // search in the prefix sums and draws inside its strata; the training pass carries a STRAT flag that recomputes the cell by the same
@@ -298,10 +302,13 @@ fdg_binned_reduce(const double *__restrict__ partial, uint32_t n_seg, long seg_s
 //    selected where the key is invalid; the segmented suffix scan and the waves' turns are fdg_binned_partials' own, so per (bin,
 //    column) the tiles are added in tile order.
 //  * Chunks and segments chain through partial [segment][bin][V], summed in segment order by fdg_obs_reduce.
-// utab, per call: four words per slice {rows needed, root records, offset of the slice's words in utab, offset of its coefficients in
+// The tables (obs_tables builds them for this pass and for the frequency observables', which adds what is in brackets).  utab, per
+// call: four words per column slice {rows needed, root records, offset of the slice's words in utab, offset of its coefficients in
 // dtab}; the slice's words are colA[CS], colB[CS] (stash rows of a column's one or two factors; kObsNone: no second factor, or a
-// column of a row without terms, which stays 0), then four words per root record {root, place of its weight column, first term, end
-// of terms}, then a word per term (stash row, bit 31: the term starts its row's fold).  dtab: the terms' coefficients.
+// column of a row without terms, which stays 0), then four [kFobsRec] words per root record {root, place of its weight column [bit
+// 31: the time labels of the record before], first term, end of terms [, tin, tout: 0-based components of T]}, then a word per term
+// (stash row, bit 31: the term starts its row's fold [bit 30: the term takes tim, else tre]).  dtab: [mult[FDG_MATSUBARA_FREQ_MAX],
+// then] the terms' coefficients.
 constexpr uint32_t kObsGroup = 16;                        // columns a wave scans together
 constexpr uint32_t kObsNone = 0xFFFFFFFFu;
 constexpr uint32_t kObsFirst = 0x80000000u;
@@ -414,9 +421,11 @@ fdg_obs_partials(const double *__restrict__ root, long ld, long n, const int32_t
   }
 }
 
-// d_obs[j][m] and d_cov[j][a][c] += the segments' partials [segment][bin][V], with fdg_binned_reduce's order (thread (q, c) adds the
-// segments q, q + Q, ..., then the Q sums are added q = 0, 1, ...; Q = 256 / C).  The column of a product goes to [a][c] and to its
-// mirror [c][a]; rows without a term (bit m of rowlive clear) leave their column of d_obs and their rows and columns of d_cov alone.
+// The reduce of both passes, over n_obs rows (the observables) or components (2 M, the frequency observables) and histogram rows jb
+// (a bin, or bin * n_freq + frequency): d_obs[jb][m] and d_cov[jb][a][c] += the segments' partials [segment][jb][V], with
+// fdg_binned_reduce's order (thread (q, c) adds the segments q, q + Q, ..., then the Q sums are added q = 0, 1, ...; Q = 256 / C).
+// The column of a product goes to [a][c] and to its mirror [c][a]; rows or components without a term (bit m of rowlive clear) leave
+// their column of d_obs and their rows and columns of d_cov alone.
 __global__ void __launch_bounds__(256)
 fdg_obs_reduce(const double *__restrict__ partial, uint32_t n_seg, long ncol, uint32_t n_obs, uint32_t V, uint32_t C, uint32_t rowlive,
                double *__restrict__ obs, double *__restrict__ cov) {
@@ -464,12 +473,9 @@ fdg_obs_reduce(const double *__restrict__ partial, uint32_t n_seg, long ncol, ui
 //    before it keeps that phase: the same operands, the same bits), tre = t c, tim = t s; every term folds coef * tre or coef * tim
 //    into its component's word of the lane's LDS stash ([component of the slice][256 lanes]).
 //  * The columns are scanned kObsGroup at a time and the waves add their run heads in wave order, as in fdg_obs_partials.
-//  * Chunks and segments chain through partial [segment][bin][frequency][V], summed in segment order by fdg_fobs_reduce.
-// utab, per call: four words per COLUMN slice {components needed, root records, offset of the slice's words in utab, offset of its
-// coefficients in dtab}; the slice's words are colA[CS], colB[CS] (stash rows, as in fdg_obs_partials), then kFobsRec words per root
-// record {root, place of its weight column (bit 31: the time labels of the record before), first term, end of terms, tin, tout
-// (0-based components of T)}, then a word per term (stash row, bit 31: the term starts its component's fold, bit 30: the term takes
-// tim, else tre).  dtab: mult[FDG_MATSUBARA_FREQ_MAX], then the terms' coefficients.
+//  * Chunks and segments chain through partial [segment][bin][frequency][V], summed in segment order by fdg_obs_reduce over the
+//    2 M components.
+// utab and dtab: the observables' tables with the bracketed parts (stated there), a header per COLUMN slice.
 constexpr uint32_t kFobsRec = 6;
 constexpr uint32_t kFobsSame = 0x80000000u;
 constexpr uint32_t kFobsIm = 0x40000000u;
@@ -605,40 +611,6 @@ fdg_fobs_partials(const double *__restrict__ root, long ld, long n, const int32_
     bool live;
     const size_t at = slab_at(i, live);
     if (live) slab[at] = hist[i];
-  }
-}
-
-// d_fobs[j][f][p] and d_fcov[j][f][p][q] += the segments' partials [segment][bin][frequency][V], with fdg_obs_reduce's order and
-// rules over the 2 M components: the column of a product goes to [p][q] and to its mirror [q][p]; components without a term (bit p of
-// live clear) leave their column of d_fobs and their rows and columns of d_fcov alone.
-__global__ void __launch_bounds__(256)
-fdg_fobs_reduce(const double *__restrict__ partial, uint32_t n_seg, long ncol, uint32_t n_comp, uint32_t V, uint32_t C, uint32_t live,
-                double *__restrict__ fobs, double *__restrict__ fcov) {
-  __shared__ double sh[256];
-  const uint32_t Q = 256u / C, q = threadIdx.x / C, cl = threadIdx.x % C;
-  const long c = (long)blockIdx.x * C + cl;
-  double s = 0.0;
-  if (c < ncol)
-    for (uint32_t sg = q; sg < n_seg; sg += Q) s = s + partial[(size_t)sg * (size_t)ncol + (size_t)c];
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  if (q == 0 && c < ncol) {
-    double t = sh[cl];
-    for (uint32_t qq = 1; qq < Q && qq < n_seg; ++qq) t = t + sh[qq * C + cl];
-    const size_t row = (size_t)(c / V);                   // bin * n_freq + frequency
-    const uint32_t v = (uint32_t)(c % V);
-    if (v < n_comp) {
-      if ((live >> v) & 1u) fobs[row * n_comp + v] = fobs[row * n_comp + v] + t;
-    } else {
-      uint32_t a = 0, p = v - n_comp;                     // the p-th entry of the upper triangle, row by row
-      while (p >= n_comp - a) { p -= n_comp - a; ++a; }
-      const uint32_t cc = a + p;
-      if (((live >> a) & 1u) && ((live >> cc) & 1u)) {
-        double *m = fcov + row * n_comp * n_comp;
-        m[a * n_comp + cc] = m[a * n_comp + cc] + t;
-        if (cc != a) m[cc * n_comp + a] = m[cc * n_comp + a] + t;
-      }
-    }
   }
 }
 
@@ -1468,113 +1440,22 @@ MatsubaraPlan matsubara_plan(const BinnedPlan &p, uint32_t R, uint32_t n_bin, ui
   return q;
 }
 
-// How the observables pass is cut.  Columns per slice: as many of the V value columns as the binned plan's LDS budget holds (whole
-// columns of n_bin bins; one column of more than 8192 bins takes what one root of FDG_BIN_MAX bins takes), spread evenly over the
-// slices.  Segments: the binned call's own count whenever the slab [segment][bin][V] fits in 2 kBinSlabBytes (the moments call's
-// bound), so that a unit row sums in the moments call's order; else the largest count that fits.  A function of (n_sample, n_bin,
-// n_obs, n_root, FDG_ROOT_SCRATCH_MB) only.
+// How the two observables passes are cut.  A histogram row is a (bin, frequency) pair of V value columns (the observables: one
+// frequency, V = M + M (M + 1) / 2; the frequency observables: V = 2 M + M (2 M + 1)).  Frequencies are sliced first (a frequency
+// slice forms only its own phases): as many whole frequencies of V columns as the binned plan's LDS budget holds, spread evenly over
+// the slices; only when not even one fits are the columns sliced too: as many as the budget holds (whole columns of n_bin bins; one
+// column of more than 8192 bins takes what one root of FDG_BIN_MAX bins takes), spread evenly over the slices.  Segments: the binned
+// call's own count whenever the slab [segment][bin][frequency][V] fits in 2 kBinSlabBytes (the moments call's bound), so that a unit
+// row sums in the moments call's order; else the largest count that fits.  A function of (n_sample, n_bin, n_freq, n_obs, n_root,
+// FDG_ROOT_SCRATCH_MB) only.
 struct ObsPlan {
-  uint32_t V = 1, cs = 1, n_slice = 1, n_seg = 1;
-  size_t hist_bytes = 0, slab_alloc = 0;
-};
-
-ObsPlan obs_plan(const BinnedPlan &p, uint32_t n_bin, uint32_t n_obs) {
-  ObsPlan q;
-  q.V = n_obs + n_obs * (n_obs + 1u) / 2u;
-  const uint32_t fit = (uint32_t)std::max<size_t>(1, kBinLdsBudget / ((size_t)n_bin * 8u));
-  q.n_slice = (q.V + fit - 1) / fit;
-  q.cs = (q.V + q.n_slice - 1) / q.n_slice;
-  q.n_slice = (q.V + q.cs - 1) / q.cs;
-  q.hist_bytes = (size_t)n_bin * q.cs * 8u;
-  const size_t seg_bytes = (size_t)n_bin * q.V * 8u;
-  q.n_seg = (uint32_t)std::max<size_t>(1, std::min<size_t>(p.n_seg, 2u * kBinSlabBytes / seg_bytes));
-  q.slab_alloc = page_up((size_t)q.n_seg * seg_bytes);
-  return q;
-}
-
-// The tables of fdg_obs_partials for one call (the layout is stated there), built from the host coefficients: need = the most stash
-// rows a slice uses, rowlive = bit m set when row m has a term.
-struct ObsTables {
-  std::vector<uint32_t> u;
-  std::vector<double> d;
-  uint32_t need = 1, rowlive = 0;
-};
-
-ObsTables obs_tables(const fdg_graph *g, const ObsPlan &q, const fdg_observables &ob, const fdg_weight_groups *wg) {
-  const uint32_t R = g->prog.R, M = ob.n_obs;
-  ObsTables t;
-  auto term = [&](uint32_t m, uint32_t k) { return g->prog.root_slot[k] != FDG_NO_ROOT && ob.coef[(size_t)m * R + k] != 0.0; };
-  for (uint32_t m = 0; m < M; ++m)
-    for (uint32_t k = 0; k < R; ++k)
-      if (term(m, k)) { t.rowlive |= 1u << m; break; }
-  std::vector<uint32_t> pa, pc;                            // the factors of every value column
-  for (uint32_t m = 0; m < M; ++m) { pa.push_back(m); pc.push_back(kObsNone); }
-  for (uint32_t a = 0; a < M; ++a)
-    for (uint32_t c = a; c < M; ++c) { pa.push_back(a); pc.push_back(c); }
-  t.u.assign((size_t)q.n_slice * 4u, 0u);
-  for (uint32_t s = 0; s < q.n_slice; ++s) {
-    const uint32_t c0 = s * q.cs, cn = std::min(q.cs, q.V - c0);
-    std::vector<uint32_t> slot(M, kObsNone);               // the stash row of every row the slice needs, ascending
-    std::vector<uint32_t> colA(q.cs, kObsNone), colB(q.cs, kObsNone);
-    uint32_t used = 0;
-    for (uint32_t cl = 0; cl < cn; ++cl) {
-      const uint32_t a = pa[c0 + cl], c = pc[c0 + cl];
-      if (!((t.rowlive >> a) & 1u) || (c != kObsNone && !((t.rowlive >> c) & 1u))) continue;
-      used |= 1u << a;
-      if (c != kObsNone) used |= 1u << c;
-    }
-    uint32_t n_need = 0;
-    for (uint32_t m = 0; m < M; ++m)
-      if ((used >> m) & 1u) slot[m] = n_need++;
-    for (uint32_t cl = 0; cl < cn; ++cl) {
-      const uint32_t a = pa[c0 + cl], c = pc[c0 + cl];
-      if (slot[a] == kObsNone || (c != kObsNone && slot[c] == kObsNone)) continue;
-      colA[cl] = slot[a];
-      colB[cl] = c == kObsNone ? kObsNone : slot[c];
-    }
-    std::vector<uint32_t> recs, terms;
-    std::vector<bool> started(M, false);
-    const size_t d0 = t.d.size();
-    for (uint32_t k = 0; k < R; ++k) {
-      const uint32_t tb = (uint32_t)terms.size();
-      for (uint32_t m = 0; m < M; ++m)
-        if (slot[m] != kObsNone && term(m, k)) {
-          terms.push_back(slot[m] | (started[m] ? 0u : kObsFirst));
-          started[m] = true;
-          t.d.push_back(ob.coef[(size_t)m * R + k]);
-        }
-      if (terms.size() == tb) continue;
-      const uint32_t rk[4] = {k, wg && wg->n_group > 1 ? wg->root_group[k] : 0u, tb, (uint32_t)terms.size()};
-      recs.insert(recs.end(), rk, rk + 4);
-    }
-    uint32_t *hdr = t.u.data() + (size_t)s * 4u;
-    hdr[0] = n_need;
-    hdr[1] = (uint32_t)(recs.size() / 4u);
-    hdr[2] = (uint32_t)t.u.size();
-    hdr[3] = (uint32_t)d0;
-    t.need = std::max(t.need, n_need);
-    t.u.insert(t.u.end(), colA.begin(), colA.end());
-    t.u.insert(t.u.end(), colB.begin(), colB.end());
-    t.u.insert(t.u.end(), recs.begin(), recs.end());
-    t.u.insert(t.u.end(), terms.begin(), terms.end());
-  }
-  return t;
-}
-
-// How the frequency-observables pass is cut.  A histogram row is a (bin, frequency) pair of V = 2 M + M (2 M + 1) columns.
-// Frequencies are sliced first (a frequency slice forms only its own phases): as many whole frequencies of V columns as the binned
-// plan's LDS budget holds, spread evenly over the slices; only when not even one fits are the columns sliced too, as obs_plan slices
-// them (one column of more than 8192 bins takes what one root of FDG_BIN_MAX bins takes).  Segments: the binned call's own count
-// whenever the slab [segment][bin][frequency][V] fits in 2 kBinSlabBytes, else the largest count that fits.  A function of
-// (n_sample, n_bin, n_freq, n_obs, n_root, FDG_ROOT_SCRATCH_MB) only.
-struct FobsPlan {
   uint32_t V = 1, fs = 1, n_fslice = 1, cs = 1, n_cslice = 1, n_seg = 1;
   size_t hist_bytes = 0, slab_alloc = 0;
 };
 
-FobsPlan fobs_plan(const BinnedPlan &p, uint32_t n_bin, uint32_t n_freq, uint32_t n_obs) {
-  FobsPlan q;
-  q.V = 2u * n_obs + n_obs * (2u * n_obs + 1u);
+ObsPlan obs_plan(const BinnedPlan &p, uint32_t n_bin, uint32_t n_freq, uint32_t V) {
+  ObsPlan q;
+  q.V = V;
   const uint32_t fit = (uint32_t)std::max<size_t>(1, kBinLdsBudget / ((size_t)n_bin * 8u));     // words per bin
   if (fit >= q.V) {
     const uint32_t ffit = fit / q.V;
@@ -1594,25 +1475,30 @@ FobsPlan fobs_plan(const BinnedPlan &p, uint32_t n_bin, uint32_t n_freq, uint32_
   return q;
 }
 
-// The tables of fdg_fobs_partials for one call (the layout is stated there), built from the host coefficients and the descriptor's
-// frequencies and time labels: need = the most stash rows a column slice uses, live = bit p set when component p (a_m: m, b_m:
-// M + m) has a term.
-struct FobsTables {
+// The tables of fdg_obs_partials or fdg_fobs_partials for one call (the layout is stated at fdg_obs_partials), built from the M rows
+// of host coefficients: need = the most stash rows a column slice uses, live = bit p set when row p has a term.  mz == null: the
+// observables, the rows are the M rows.  Else the frequency observables: 2 M rows, the components a_m (p = m) and b_m (p = M + m),
+// both reading row p % M of coef; dtab starts with the descriptor's multipliers, a record carries its root's time labels, a term of
+// b_m the bit kFobsIm.
+struct ObsTables {
   std::vector<uint32_t> u;
   std::vector<double> d;
   uint32_t need = 1, live = 0;
 };
 
-FobsTables fobs_tables(const fdg_graph *g, const FobsPlan &q, const fdg_freq_observables &fo, const fdg_matsubara &mz,
-                       const fdg_weight_groups *wg) {
-  const uint32_t R = g->prog.R, M = fo.n_obs, P = 2u * M;
-  FobsTables t;
-  auto term = [&](uint32_t p, uint32_t k) { return g->prog.root_slot[k] != FDG_NO_ROOT && fo.coef[(size_t)(p % M) * R + k] != 0.0; };
+ObsTables obs_tables(const fdg_graph *g, const ObsPlan &q, const double *coef, uint32_t M, const fdg_matsubara *mz,
+                     const fdg_weight_groups *wg) {
+  const uint32_t R = g->prog.R, P = mz ? 2u * M : M, W = mz ? kFobsRec : 4u;
+  ObsTables t;
+  auto coef_of = [&](uint32_t p, uint32_t k) { return coef[(size_t)(p % M) * R + k]; };
+  auto term = [&](uint32_t p, uint32_t k) { return g->prog.root_slot[k] != FDG_NO_ROOT && coef_of(p, k) != 0.0; };
   for (uint32_t p = 0; p < P; ++p)
     for (uint32_t k = 0; k < R; ++k)
       if (term(p, k)) { t.live |= 1u << p; break; }
-  t.d.assign(FDG_MATSUBARA_FREQ_MAX, 0.0);
-  for (uint32_t f = 0; f < mz.n_freq; ++f) t.d[f] = matsubara_multiplier(mz.freq[f], mz.fermionic);
+  if (mz) {
+    t.d.assign(FDG_MATSUBARA_FREQ_MAX, 0.0);
+    for (uint32_t f = 0; f < mz->n_freq; ++f) t.d[f] = matsubara_multiplier(mz->freq[f], mz->fermionic);
+  }
   std::vector<uint32_t> pa, pc;                            // the factors of every value column
   for (uint32_t p = 0; p < P; ++p) { pa.push_back(p); pc.push_back(kObsNone); }
   for (uint32_t a = 0; a < P; ++a)
@@ -1620,7 +1506,7 @@ FobsTables fobs_tables(const fdg_graph *g, const FobsPlan &q, const fdg_freq_obs
   t.u.assign((size_t)q.n_cslice * 4u, 0u);
   for (uint32_t s = 0; s < q.n_cslice; ++s) {
     const uint32_t c0 = s * q.cs, cn = std::min(q.cs, q.V - c0);
-    std::vector<uint32_t> slot(P, kObsNone);               // the stash row of every component the slice needs, ascending
+    std::vector<uint32_t> slot(P, kObsNone);               // the stash row of every row the slice needs, ascending
     std::vector<uint32_t> colA(q.cs, kObsNone), colB(q.cs, kObsNone);
     uint32_t used = 0;
     for (uint32_t cl = 0; cl < cn; ++cl) {
@@ -1648,20 +1534,23 @@ FobsTables fobs_tables(const fdg_graph *g, const FobsPlan &q, const fdg_freq_obs
         if (slot[p] != kObsNone && term(p, k)) {
           terms.push_back(slot[p] | (started[p] ? 0u : kObsFirst) | (p >= M ? kFobsIm : 0u));
           started[p] = true;
-          t.d.push_back(fo.coef[(size_t)(p % M) * R + k]);
+          t.d.push_back(coef_of(p, k));
         }
       if (terms.size() == tb) continue;
-      const int32_t tin = mz.root_tau_in[k] - 1, tout = mz.root_tau_out[k] - 1;
-      const bool same = !recs.empty() && tin == last_in && tout == last_out;
-      const uint32_t rk[kFobsRec] = {k, (wg && wg->n_group > 1 ? wg->root_group[k] : 0u) | (same ? kFobsSame : 0u), tb,
-                                     (uint32_t)terms.size(), (uint32_t)tin, (uint32_t)tout};
-      recs.insert(recs.end(), rk, rk + kFobsRec);
-      last_in = tin;
-      last_out = tout;
+      uint32_t rk[kFobsRec] = {k, wg && wg->n_group > 1 ? wg->root_group[k] : 0u, tb, (uint32_t)terms.size(), 0u, 0u};
+      if (mz) {
+        const int32_t tin = mz->root_tau_in[k] - 1, tout = mz->root_tau_out[k] - 1;
+        if (!recs.empty() && tin == last_in && tout == last_out) rk[1] |= kFobsSame;
+        rk[4] = (uint32_t)tin;
+        rk[5] = (uint32_t)tout;
+        last_in = tin;
+        last_out = tout;
+      }
+      recs.insert(recs.end(), rk, rk + W);
     }
     uint32_t *hdr = t.u.data() + (size_t)s * 4u;
     hdr[0] = n_need;
-    hdr[1] = (uint32_t)(recs.size() / kFobsRec);
+    hdr[1] = (uint32_t)(recs.size() / W);
     hdr[2] = (uint32_t)t.u.size();
     hdr[3] = (uint32_t)d0;
     t.need = std::max(t.need, n_need);
@@ -1672,6 +1561,50 @@ FobsTables fobs_tables(const fdg_graph *g, const FobsPlan &q, const fdg_freq_obs
   }
   return t;
 }
+
+// What run_binned keeps of one of the two passes: P rows (the 2 M components of the frequency observables; 0: the call has no such
+// pass) over n_freq frequencies (one for the observables), the plan, the tables, and its region of the workspace: the partial slab,
+// then dtab, then utab, each from a page boundary.
+struct ObsPass {
+  uint32_t P = 0, n_freq = 1;
+  bool freq = false;                                       // the frequency observables' pass
+  ObsPlan q;
+  ObsTables t;
+  size_t bytes = 0;
+  double *partial = nullptr, *d_dtab = nullptr;
+  uint32_t *d_utab = nullptr;
+
+  // mz: the descriptor of the frequency observables' pass, null for the observables'
+  void set_up(const fdg_graph *g, const BinnedPlan &p, uint32_t n_bin, const double *coef, uint32_t M, const fdg_matsubara *mz,
+              const fdg_weight_groups *wg) {
+    freq = mz != nullptr;
+    P = mz ? 2u * M : M;
+    n_freq = mz ? mz->n_freq : 1u;
+    q = obs_plan(p, n_bin, n_freq, P + P * (P + 1u) / 2u);
+    t = obs_tables(g, q, coef, M, mz, wg);
+    bytes = q.slab_alloc + page_up(t.d.size() * 8u) + page_up(t.u.size() * 4u);
+  }
+  // the region starts at `at`: one upload per table (the observables' dtab is empty when no row has a term)
+  int place(char *at, hipStream_t st) {
+    partial = (double *)at;
+    d_dtab = (double *)(at + q.slab_alloc);
+    d_utab = (uint32_t *)((char *)d_dtab + page_up(t.d.size() * 8u));
+    if (!t.d.empty()) HIP_TRY(hipMemcpyAsync(d_dtab, t.d.data(), t.d.size() * 8u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_utab, t.u.data(), t.u.size() * 4u, hipMemcpyHostToDevice, st));
+    return FDG_OK;
+  }
+  // d_o and d_c += the segments' partials, C columns per workgroup: C fixes the order of the segments' sum (0: by the moments
+  // reduce's rule from the pass's own columns)
+  int reduce(uint32_t n_bin, uint32_t C, double *d_o, double *d_c, hipStream_t st) const {
+    const long ncol = (long)n_bin * n_freq * q.V;
+    if (!C)
+      for (C = 1; C < 64 && (long)C < ncol;) C <<= 1;
+    hipLaunchKernelGGL(fdg_obs_reduce, dim3((unsigned)((ncol + C - 1) / C)), dim3(256), 0, st, partial, q.n_seg, ncol, P, q.V, C, t.live, d_o,
+                       d_c);
+    HIP_TRY(hipGetLastError());
+    return FDG_OK;
+  }
+};
 
 // How the per-hypercube pass is cut: the record buffers of the levels (slots: two per wave of the level below).  A chunk's levels
 // alternate between a and b, the chunks' own records (two per chunk) lie in c and go through a and b again after the last chunk.
@@ -1806,6 +1739,14 @@ int reduce_partials(const double *partial, uint32_t n_seg, long ncol, uint32_t R
   return FDG_OK;
 }
 
+// The bin count of a call against its bin vector and FDG_BIN_MAX: three refusals that every call makes, in this order.
+int check_n_bin(const BinnedCall &c) {
+  if (c.n_bin == 0) { set_error("n_bin == 0"); return FDG_E_INVALID; }
+  if (!c.d_bin && c.n_bin != 1) { set_error("d_bin == NULL (one bin) needs n_bin == 1"); return FDG_E_INVALID; }
+  if (c.n_bin > FDG_BIN_MAX) { set_error("n_bin > FDG_BIN_MAX"); return FDG_E_UNSUPPORTED; }
+  return FDG_OK;
+}
+
 // The checks every accumulate entry point makes before any device work.  The binned calls need d_bin; the moments calls need d_acc2
 // and take d_bin == NULL (every sample in bin 0, which needs n_bin == 1).
 int check_call(const fdg_graph *g, const BinnedCall &c, bool moments) {
@@ -1814,10 +1755,7 @@ int check_call(const fdg_graph *g, const BinnedCall &c, bool moments) {
   const bool no_acc = c.ob && moments && !c.d_acc && !c.d_acc2;    // the observables calls: no per-root moments asked for
   if (!no_acc && (!c.d_acc || (moments ? !c.d_acc2 : !c.d_bin))) { set_error("null device buffer"); return FDG_E_INVALID; }
   if (!no_acc && c.d_acc == c.d_acc2) { set_error("d_acc and d_acc2 are the same buffer"); return FDG_E_INVALID; }
-  if (c.n_bin == 0) { set_error("n_bin == 0"); return FDG_E_INVALID; }
-  if (!c.d_bin && c.n_bin != 1) { set_error("d_bin == NULL (one bin) needs n_bin == 1"); return FDG_E_INVALID; }
-  if (c.n_bin > FDG_BIN_MAX) { set_error("n_bin > FDG_BIN_MAX"); return FDG_E_UNSUPPORTED; }
-  return FDG_OK;
+  return check_n_bin(c);
 }
 
 // ... and the VEGAS calls': the map's limits (every call), then the output arrays of the accumulate calls.
@@ -1887,9 +1825,8 @@ int check_matsubara(const fdg_graph *g, const BinnedCall &c, const fdg_matsubara
   for (int a = 0; a < 8; ++a)
     for (int b = 0; b < a; ++b)
       if (out[a] && out[a] == out[b]) { set_error("two output arrays are the same buffer"); return FDG_E_INVALID; }
-  if (c.n_bin == 0) { set_error("n_bin == 0"); return FDG_E_INVALID; }
-  if (!c.d_bin && c.n_bin != 1) { set_error("d_bin == NULL (one bin) needs n_bin == 1"); return FDG_E_INVALID; }
-  if (c.n_bin > FDG_BIN_MAX) { set_error("n_bin > FDG_BIN_MAX"); return FDG_E_UNSUPPORTED; }
+  const int rc = check_n_bin(c);
+  if (rc) return rc;
   if (m->n_freq == 0) { set_error("n_freq == 0"); return FDG_E_INVALID; }
   if (m->n_freq > FDG_MATSUBARA_FREQ_MAX) { set_error("n_freq > FDG_MATSUBARA_FREQ_MAX"); return FDG_E_UNSUPPORTED; }
   if ((uint64_t)c.n_bin * m->n_freq > FDG_BIN_MAX) { set_error("n_bin * n_freq > FDG_BIN_MAX"); return FDG_E_UNSUPPORTED; }
@@ -1939,17 +1876,27 @@ int check_strat_grouped_call(const fdg_graph *g, const BinnedCall &c) {
   return rc ? rc : check_strat_arrays(g, c, c.wg->n_group);
 }
 
+// What the descriptors of the observables and of the frequency observables are both checked for, in this order, each refusal in
+// its caller's words: the three arrays, the number of rows against 1 .. n_max, every coefficient finite.
+struct RowTexts { const char *null_array, *none, *many, *not_finite; };
+int check_rows(const fdg_graph *g, const double *coef, const double *d_o, const double *d_c, uint32_t n_obs, uint32_t n_max, const RowTexts &t) {
+  if (!coef || !d_o || !d_c) { set_error(t.null_array); return FDG_E_INVALID; }
+  if (n_obs == 0) { set_error(t.none); return FDG_E_INVALID; }
+  if (n_obs > n_max) { set_error(t.many); return FDG_E_UNSUPPORTED; }
+  for (size_t i = 0; i < (size_t)n_obs * g->prog.R; ++i)
+    if (!std::isfinite(coef[i])) { set_error(t.not_finite); return FDG_E_INVALID; }
+  return FDG_OK;
+}
+
 // ... and the observables calls': the descriptor first (the coefficients need the handle's n_root), then the grouped calls' cases
 // with wg optional and, through c.ob, d_acc and d_acc2 optional together.
 int check_observables(const fdg_graph *g, const BinnedCall &c, const fdg_matsubara *m, const double *mc_T) {
   if (!g) { set_error("null handle"); return FDG_E_INVALID; }
   const fdg_observables *o = c.ob ? c.ob->ob : nullptr;
   if (!o) { set_error("null observables"); return FDG_E_INVALID; }
-  if (!o->coef || !o->d_obs || !o->d_cov) { set_error("null array in the observables"); return FDG_E_INVALID; }
-  if (o->n_obs == 0) { set_error("n_obs == 0"); return FDG_E_INVALID; }
-  if (o->n_obs > FDG_OBS_MAX) { set_error("n_obs > FDG_OBS_MAX"); return FDG_E_UNSUPPORTED; }
-  for (size_t i = 0; i < (size_t)o->n_obs * g->prog.R; ++i)
-    if (!std::isfinite(o->coef[i])) { set_error("a coefficient of the observables is not finite"); return FDG_E_INVALID; }
+  const int rc = check_rows(g, o->coef, o->d_obs, o->d_cov, o->n_obs, FDG_OBS_MAX,
+                            {"null array in the observables", "n_obs == 0", "n_obs > FDG_OBS_MAX", "a coefficient of the observables is not finite"});
+  if (rc) return rc;
   if (o->d_obs == o->d_cov) { set_error("d_obs and d_cov are the same buffer"); return FDG_E_INVALID; }
   for (const double *out : {c.d_acc, c.d_acc2})
     if (out && (out == o->d_obs || out == o->d_cov)) { set_error("d_obs or d_cov is the same buffer as d_acc or d_acc2"); return FDG_E_INVALID; }
@@ -1964,11 +1911,10 @@ int check_freq_observables(const fdg_graph *g, const BinnedCall &c, const fdg_ma
   if (!g) { set_error("null handle"); return FDG_E_INVALID; }
   const fdg_freq_observables *o = c.fo;
   if (!o) { set_error("null frequency observables"); return FDG_E_INVALID; }
-  if (!o->coef || !o->d_fobs || !o->d_fcov) { set_error("null array in the frequency observables"); return FDG_E_INVALID; }
-  if (o->n_obs == 0) { set_error("n_obs == 0 in the frequency observables"); return FDG_E_INVALID; }
-  if (o->n_obs > FDG_FREQ_OBS_MAX) { set_error("n_obs > FDG_FREQ_OBS_MAX"); return FDG_E_UNSUPPORTED; }
-  for (size_t i = 0; i < (size_t)o->n_obs * g->prog.R; ++i)
-    if (!std::isfinite(o->coef[i])) { set_error("a coefficient of the frequency observables is not finite"); return FDG_E_INVALID; }
+  const int rc = check_rows(g, o->coef, o->d_fobs, o->d_fcov, o->n_obs, FDG_FREQ_OBS_MAX,
+                            {"null array in the frequency observables", "n_obs == 0 in the frequency observables", "n_obs > FDG_FREQ_OBS_MAX",
+                             "a coefficient of the frequency observables is not finite"});
+  if (rc) return rc;
   if (!m) { set_error("null descriptor: the frequency observables need mz"); return FDG_E_INVALID; }
   const fdg_observables *ob = c.ob ? c.ob->ob : nullptr;
   const double *out[11] = {o->d_fcov, c.d_acc, c.d_acc2, c.vg ? c.vg->d_hist : nullptr, c.vg ? c.vg->d_hist_bin : nullptr,
@@ -2014,26 +1960,12 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
   const size_t proj_bytes = mz ? base_bytes + mp.slab_alloc + mp.tab_bytes : base_bytes;
   const size_t gtab_words = (size_t)R + (size_t)p.n_slice * kGrpEntry + kGrpCols + 1u;
   const size_t grp_bytes = (grp_w || grp_t) ? page_up(gtab_words * 4u + (vg ? (size_t)vg->D * vg->G : 0)) : 0;
-  // ... and the observables' slab and tables behind that
+  // ... and the observables' slab and tables behind that, the frequency observables' behind those
   const fdg_observables *ob = c.ob ? c.ob->ob : nullptr;
-  ObsPlan op;
-  ObsTables ot;
-  size_t obs_bytes = 0;
-  if (ob) {
-    op = obs_plan(p, n_bin, ob->n_obs);
-    ot = obs_tables(g, op, *ob, wg);
-    obs_bytes = op.slab_alloc + page_up(ot.d.size() * 8u) + page_up(ot.u.size() * 4u);
-  }
-  // ... and the frequency observables' slab and tables behind that
   const fdg_freq_observables *fo = c.fo;
-  FobsPlan fp;
-  FobsTables ft;
-  size_t fobs_bytes = 0;
-  if (fo) {
-    fp = fobs_plan(p, n_bin, mz->m->n_freq, fo->n_obs);
-    ft = fobs_tables(g, fp, *fo, *mz->m, wg);
-    fobs_bytes = fp.slab_alloc + page_up(ft.d.size() * 8u) + page_up(ft.u.size() * 4u);
-  }
+  ObsPass op, fp;
+  if (ob) op.set_up(g, p, n_bin, ob->coef, ob->n_obs, nullptr, wg);
+  if (fo) fp.set_up(g, p, n_bin, fo->coef, fo->n_obs, mz->m, wg);
   // ... and the record buffers of the per-hypercube pass behind that
   const StratRun *sr = c.sr;
   // (with several groups one column per group behind the roots', the GRP instances; else the one coef column of the ungrouped call,
@@ -2046,7 +1978,7 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
     sv = vegas_strat(sr->strat, vg->D);
     sp = strat_plan(p, c.B, R, sv.H, grp_s ? NG : 1u);
   }
-  int rc = ensure_root_scratch(g, proj_bytes + grp_bytes + obs_bytes + fobs_bytes + sp.bytes);
+  int rc = ensure_root_scratch(g, proj_bytes + grp_bytes + op.bytes + fp.bytes + sp.bytes);
   if (rc) return rc;
   double *roots = (double *)g->d_ws2, *partial = (double *)((char *)g->d_ws2 + root_bytes);
   const uint8_t *live = nullptr;
@@ -2131,28 +2063,30 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
     }
     HIP_TRY(hipMemcpyAsync(d_mtab, hm.data(), hm.size() * sizeof(double), hipMemcpyHostToDevice, st));
   }
-  double *opartial = nullptr, *d_odtab = nullptr;
-  uint32_t *d_outab = nullptr;
-  if (ob) {
-    opartial = (double *)((char *)g->d_ws2 + proj_bytes + grp_bytes);
-    d_odtab = (double *)((char *)opartial + op.slab_alloc);
-    d_outab = (uint32_t *)((char *)d_odtab + page_up(ot.d.size() * 8u));
-    if (!ot.d.empty()) HIP_TRY(hipMemcpyAsync(d_odtab, ot.d.data(), ot.d.size() * 8u, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_outab, ot.u.data(), ot.u.size() * 4u, hipMemcpyHostToDevice, st));
-  }
-  double *fpartial = nullptr, *d_fdtab = nullptr;
-  uint32_t *d_futab = nullptr;
-  if (fo) {
-    fpartial = (double *)((char *)g->d_ws2 + proj_bytes + grp_bytes + obs_bytes);
-    d_fdtab = (double *)((char *)fpartial + fp.slab_alloc);
-    d_futab = (uint32_t *)((char *)d_fdtab + page_up(ft.d.size() * 8u));
-    HIP_TRY(hipMemcpyAsync(d_fdtab, ft.d.data(), ft.d.size() * 8u, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_futab, ft.u.data(), ft.u.size() * 4u, hipMemcpyHostToDevice, st));
-  }
+  if (op.P) rc = op.place((char *)g->d_ws2 + proj_bytes + grp_bytes, st);
+  if (!rc && fp.P) rc = fp.place((char *)g->d_ws2 + proj_bytes + grp_bytes + op.bytes, st);
+  if (rc) return rc;
+  // a chunk's launch of either pass (one weight column per group; without groups one, or none when the call has no weights)
+  auto obs_launch = [&](const ObsPass &o, long c0, long n, long ntile, const int32_t *bins, const double *w, int first) {
+    const ObsPlan &q = o.q;
+    const dim3 grid(q.n_seg * q.n_fslice * q.n_cslice);
+    const size_t lds = q.hist_bytes + (size_t)o.t.need * 2048u;
+    const uint32_t n_wcol = w ? (grp_w ? NG : 1u) : 0u;
+    const long seg_tiles = (ntile + q.n_seg - 1) / q.n_seg;
+    if (!o.freq)
+      hipLaunchKernelGGL(fdg_obs_partials, grid, dim3(256), lds, st, roots, (long)p.Bc, n, bins, c.bin_base, n_bin, w, wstride, n_wcol, q.V, q.cs,
+                         q.n_cslice, seg_tiles, o.partial, first, o.d_utab, o.d_dtab);
+    else
+      hipLaunchKernelGGL(fdg_fobs_partials, grid, dim3(256), lds, st, roots, (long)p.Bc, n, bins, c.bin_base, n_bin, w, wstride, n_wcol,
+                         mz->d_T + c0 * mz->ts, (long)mz->ts, (long)mz->tc, mz->m->beta, o.n_freq, q.fs, q.n_fslice, q.V, q.cs, q.n_cslice,
+                         seg_tiles, o.partial, first, o.d_utab, o.d_dtab);
+    HIP_TRY(hipGetLastError());
+    return FDG_OK;
+  };
   // the record buffers {keys, values, slots} a, b (the levels) and c (the chunks)
   struct StratBuf { int32_t *key; double *val; long cap; } sa = {}, sb = {}, sc = {};
   if (sr) {
-    char *at = (char *)g->d_ws2 + proj_bytes + grp_bytes + obs_bytes + fobs_bytes;
+    char *at = (char *)g->d_ws2 + proj_bytes + grp_bytes + op.bytes + fp.bytes;
     for (auto bc : {std::make_pair(&sa, sp.cap_a), std::make_pair(&sb, sp.cap_b), std::make_pair(&sc, sp.cap_c)}) {
       *bc.first = {(int32_t *)at, (double *)(at + page_up((size_t)bc.second * 4u)), bc.second};
       at += StratPlan::buf_bytes(bc.second, sp.V2);
@@ -2189,20 +2123,11 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
                          (ntile + p.n_seg - 1) / p.n_seg, partial, first, d_gtab, wstride);
       HIP_TRY(hipGetLastError());
     }
-    if (ob) {
-      // (one weight column per group; without groups one, or none when the call has no weights)
-      hipLaunchKernelGGL(fdg_obs_partials, dim3(op.n_seg * op.n_slice), dim3(256), op.hist_bytes + (size_t)ot.need * 2048u, st, roots,
-                         (long)p.Bc, n, bins, c.bin_base, n_bin, w, wstride, w ? (grp_w ? NG : 1u) : 0u, op.V, op.cs, op.n_slice,
-                         (ntile + op.n_seg - 1) / op.n_seg, opartial, first, d_outab, d_odtab);
-      HIP_TRY(hipGetLastError());
-    }
-    if (fo) {
-      hipLaunchKernelGGL(fdg_fobs_partials, dim3(fp.n_seg * fp.n_fslice * fp.n_cslice), dim3(256), fp.hist_bytes + (size_t)ft.need * 2048u, st,
-                         roots, (long)p.Bc, n, bins, c.bin_base, n_bin, w, wstride, w ? (grp_w ? NG : 1u) : 0u, mz->d_T + c0 * mz->ts,
-                         (long)mz->ts, (long)mz->tc, mz->m->beta, mz->m->n_freq, fp.fs, fp.n_fslice, fp.V, fp.cs, fp.n_cslice,
-                         (ntile + fp.n_seg - 1) / fp.n_seg, fpartial, first, d_futab, d_fdtab);
-      HIP_TRY(hipGetLastError());
-    }
+    for (const ObsPass *o : {&op, &fp})
+      if (o->P) {
+        rc = obs_launch(*o, c0, n, ntile, bins, w, first);
+        if (rc) return rc;
+      }
     if (proj) {
       hipLaunchKernelGGL(mpass, dim3(mp.n_seg * mp.n_grp), dim3(64 * mp.nw), mp.lds, st, roots, (long)p.Bc, n, bins, c.bin_base, n_bin, w,
                          mz->d_T + c0 * mz->ts, (long)mz->ts, (long)mz->tc, d_mtab, mz->m->beta, mz->m->n_freq, R, mp.rs, mp.fs, mp.n_fslice,
@@ -2245,21 +2170,10 @@ int run_binned(fdg_graph *g, const BinnedCall &c, Eval eval) {
   uint32_t C = 1;
   while (C < 64 && (long)C < ncol) C <<= 1;
   if (c.d_acc) rc = reduce_partials(partial, p.n_seg, ncol, R, C, c.d_acc, c.d_acc2, live, st);
-  if (!rc && ob) {
-    // (C, and with it the order of the segments' sum, is the moments reduce's own: a unit row then carries the moments call's bits)
-    const long ocol = (long)n_bin * op.V;
-    hipLaunchKernelGGL(fdg_obs_reduce, dim3((unsigned)((ocol + C - 1) / C)), dim3(256), 0, st, opartial, op.n_seg, ocol, ob->n_obs, op.V, C,
-                       ot.rowlive, ob->d_obs, ob->d_cov);
-    HIP_TRY(hipGetLastError());
-  }
-  if (!rc && fo) {
-    const long fcol = (long)n_bin * mz->m->n_freq * fp.V;
-    uint32_t FC = 1;
-    while (FC < 64 && (long)FC < fcol) FC <<= 1;
-    hipLaunchKernelGGL(fdg_fobs_reduce, dim3((unsigned)((fcol + FC - 1) / FC)), dim3(256), 0, st, fpartial, fp.n_seg, fcol, 2u * fo->n_obs,
-                       fp.V, FC, ft.live, fo->d_fobs, fo->d_fcov);
-    HIP_TRY(hipGetLastError());
-  }
+  // (the observables: C, and with it the order of the segments' sum, is the moments reduce's own: a unit row then carries the moments
+  // call's bits; the frequency observables: C by the same rule from their own columns)
+  if (!rc && ob) rc = op.reduce(n_bin, C, ob->d_obs, ob->d_cov, st);
+  if (!rc && fo) rc = fp.reduce(n_bin, 0u, fo->d_fobs, fo->d_fcov, st);
   if (!rc && proj) {
     // the four arrays += the segments' partials [segment][4][bin][frequency][root], in segment order: first both first moments, then both second
     const long mcol = ncol * mz->m->n_freq;

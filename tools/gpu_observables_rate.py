@@ -2,8 +2,9 @@
 (the headline, L = 84, R = 4) at 1e8 samples in one box; n_obs = 2 and 16 dense random rows, n_bin = 1 (no bin vector) and 64 (uniform
 bins).  Per n_bin, in one process: accumulate_moments (the yardstick), the grouped call with one group and no observables (the same
 call without ob: the ungrouped kernels on the ungrouped plan), the observables call alone (no per-root moments), and the observables
-call beside the per-root moments.  One warm-up call, then the median of --reps timed calls (events around each call).  Prints ONE
-JSON line: ms per call, their spread, the ratios to the moments call.
+call beside the per-root moments; then the frequency-observables call alone (fdg_accumulate_device_freq_observables, no per-root sums;
+external times (1,1) (1,2) (1,3) (1,4)) for M = 2 and 8 dense random rows at n_freq = 1 and 8.  One warm-up call, then the median of
+--reps timed calls (events around each call).  Prints ONE JSON line: ms per call, their spread, the ratios to the moments call.
 
     python tools/gpu_observables_rate.py [--samples 1e8] [--reps 7]
 """
@@ -36,6 +37,10 @@ def main():
     leaf = torch.empty((B // 64, t.n_leaf, 64), dtype=torch.float64, device=dev)
     capi.fill_uniform_device_tiled(leaf.data_ptr(), B, t.n_leaf, 1, 64, 64 * t.n_leaf, 1234, 0, st)
     w = torch.rand(B, dtype=torch.float64, device=dev)
+    beta = 3.0
+    tin, tout = workloads.root_times(name)
+    T = torch.rand((4, B), dtype=torch.float64, device=dev).mul_(beta).t()           # component-major, as the sampler writes it
+    T[:, 0] = 0.0
     rng = np.random.default_rng(1)
     rows = {"samples": B}
     wg, _keep = capi.make_weight_groups([0] * R, [(0,)], B)
@@ -60,6 +65,13 @@ def main():
             coef = rng.uniform(-1.0, 1.0, size=(n_obs, R))
             put(f"obs{n_obs}", lambda: f.accumulate_observables(leaf, coef, bins, n_bin, w, obs, cov, n_sample=B))
             put(f"obs{n_obs}_and_moments", lambda: f.accumulate_observables(leaf, coef, bins, n_bin, w, obs, cov, acc, acc2, n_sample=B))
+        for M, n_freq in ((2, 1), (2, 8), (8, 1), (8, 8)):
+            freq = list(range(-(n_freq // 2), n_freq - n_freq // 2))
+            fobs = torch.zeros((n_bin, n_freq, 2 * M), dtype=torch.float64, device=dev)
+            fcov = torch.zeros((n_bin, n_freq, 2 * M, 2 * M), dtype=torch.float64, device=dev)
+            coef = rng.uniform(-1.0, 1.0, size=(M, R))
+            put(f"fobs{M}_freq{n_freq}", lambda: f.accumulate_freq_observables(leaf, T, freq, tin, tout, beta, coef, True, bins, n_bin, w, fobs, fcov,
+                                                                               n_sample=B))
     print(json.dumps({"tool": "gpu_observables_rate", "device": torch.cuda.get_device_name(0), name: rows}), flush=True)
 
 
