@@ -59,6 +59,7 @@ EXPORTS = [
     "fdg_chain_step_device_grouped", "fdg_mc_chain_step_device_grouped",
     "fdg_chain_propose_device_discrete", "fdg_chain_step_device_binned", "fdg_mc_chain_step_device_binned",
     "fdg_chain_propose_device_polar", "fdg_chain_propose_device_local",
+    "fdg_chain_reduce_observables_work_bytes", "fdg_chain_reduce_device_observables",
 ]
 FDG_BIN_MAX = 16384     # fdg_accumulate_device_binned: largest n_bin
 FDG_VEGAS_DIM_MAX, FDG_VEGAS_GRID_MAX = 64, 1024     # the VEGAS map: most variables, most cells per variable
@@ -71,6 +72,8 @@ FDG_FREQ_OBS_MAX = 8  # fdg_freq_observables: most linear combinations of the pr
 FDG_STRAT_CUBE_MAX = 1 << 20  # the stratified calls: most hypercubes
 FDG_CHAIN_INIT, FDG_CHAIN_MEASURE = 1, 2  # flags of fdg_[mc_]chain_step_device
 FDG_CHAIN_BIN_MAX = 64  # fdg_[mc_]chain_step_device_binned: most values of the chain's discrete variable
+# fdg_chain_reduce_device_observables: most rows per call, most columns of the window, the workgroups of the first stage
+FDG_CHAIN_OBS_MAX, FDG_CHAIN_OBS_COL_MAX, FDG_CHAIN_OBS_GROUPS = 16, 1024, 1024
 COMM_ID_BYTES = 128
 
 
@@ -305,6 +308,9 @@ def lib():
     L.fdg_chain_propose_device_polar.argtypes = L.fdg_chain_propose_device_discrete.argtypes[:-2] + [C.c_void_p, u32, i64, vp]
     L.fdg_chain_propose_device_local.argtypes = (L.fdg_chain_propose_device_polar.argtypes[:6] + [u64, C.c_void_p]
                                                  + L.fdg_chain_propose_device_polar.argtypes[6:])
+    L.fdg_chain_reduce_observables_work_bytes.argtypes = [u32, u32]
+    L.fdg_chain_reduce_observables_work_bytes.restype = C.c_size_t
+    L.fdg_chain_reduce_device_observables.argtypes = [dp, i64, u32, u32, u32, C.c_void_p, u32, dp, vp, vp]
     L.fdg_powi.argtypes = [C.c_double, C.c_int32]
     L.fdg_powi.restype = C.c_double
     _lib = L
@@ -1051,6 +1057,79 @@ def chain_reduce_reference(total) -> np.ndarray:
     R = A.shape[0] - 1
     out = [math.fsum(A[c]) for c in range(R + 1)] + [math.fsum(A[c] * A[c]) for c in range(R + 1)] + [math.fsum(A[k] * A[R]) for k in range(R)]
     return np.array(out, dtype=np.float64)
+
+
+def chain_reduce_observables_work_bytes(n_obs: int, n_use: int) -> int:
+    """fdg_chain_reduce_observables_work_bytes: the bytes of ``d_work`` for a call with these sizes, 0 where the call is refused."""
+    return int(lib().fdg_chain_reduce_observables_work_bytes(n_obs, n_use))
+
+
+def chain_reduce_observables_device(d_sum: int, B: int, col_base: int, n_use: int, norm_col: int, coef, d_out: int, d_work: int,
+                                    stream: int = 0):
+    """fdg_chain_reduce_device_observables: ``out [(M + 1) + (M + 1) (M + 2) / 2] +=`` (S, P packed) of the rows ``coef [M, n_use]``
+    (host) over the window ``col_base .. col_base + n_use - 1`` of the walkers' sums, with the column ``norm_col`` as row ``M``;
+    ``d_work`` holds :func:`chain_reduce_observables_work_bytes` bytes."""
+    c = np.ascontiguousarray(coef, dtype=np.float64)
+    if c.ndim != 2 or c.shape[1] != n_use:
+        raise ValueError(f"coef must be [n_obs, n_use = {n_use}]")
+    check(lib().fdg_chain_reduce_device_observables(d_sum or None, B, col_base, n_use, norm_col, c.ctypes.data, c.shape[0], d_out or None,
+                                                    d_work or None, stream))
+
+
+def _chain_obs_sum(x, W: int) -> float:
+    """``x [n]`` added in the order of fdg_chain_reduce_device_observables with ``W`` workgroups: strided lane sums, the pairwise tree
+    of a workgroup, the strided sums of the workgroups' partials, the tree again."""
+    def tree(v):                                            # v [.., 256]: stride 128, 64, .., 1
+        h = 128
+        while h:
+            v = v[..., :h] + v[..., h:2 * h]
+            h >>= 1
+        return v[..., 0]
+
+    def strided(v, step):                                   # v [n] -> [step]: entry s adds v[s], v[s + step], .. ascending from +0.0
+        k = -(-v.shape[0] // step)
+        pad = np.zeros(k * step)
+        pad[:v.shape[0]] = v                                 # (a missing term: nothing is added there -- + 0.0 keeps every bit but
+        acc = np.zeros(step)                                 # -0.0's sign, which a sum begun at +0.0 cannot hold)
+        for i in range(k):
+            acc = acc + pad[i * step:(i + 1) * step]
+        return acc
+    part = tree(strided(np.asarray(x, dtype=np.float64), 256 * W).reshape(W, 256))
+    return float(tree(strided(part, 256)))
+
+
+def chain_reduce_observables_reference(total, col_base: int, n_use: int, norm_col: int, coef, out=None) -> np.ndarray:
+    """fdg_chain_reduce_device_observables restated in the device's order, bit for bit: ``out`` (None: zeros) with the ``V = (M + 1) +
+    (M + 1) (M + 2) / 2`` sums ``(S, P packed)`` of ``total [n_columns, B]`` added to it, as a new array.  The outputs of a row
+    without a term are left as they are, as on the device."""
+    A = np.asarray(total, dtype=np.float64)
+    c = np.asarray(coef, dtype=np.float64)
+    M, B = c.shape[0], A.shape[1]
+    W = min(max(-(-B // 256), 1), FDG_CHAIN_OBS_GROUPS)
+    O = []
+    for m in range(M):
+        o = None
+        for k in range(n_use):
+            if c[m, k] != 0.0:
+                term = c[m, k] * A[col_base + k]
+                o = term if o is None else o + term
+        O.append(o)
+    O.append(A[norm_col])
+    V = (M + 1) + (M + 1) * (M + 2) // 2
+    out = np.zeros(V) if out is None else np.array(out, dtype=np.float64)
+    if out.shape != (V,):
+        raise ValueError(f"out must hold {V} doubles")
+    if B == 0:
+        return out
+    at = M + 1
+    for p in range(M + 1):
+        if O[p] is not None:
+            out[p] = out[p] + _chain_obs_sum(O[p], W)
+        for q in range(p, M + 1):
+            if O[p] is not None and O[q] is not None:
+                out[at] = out[at] + _chain_obs_sum(O[p] * O[q], W)
+            at += 1
+    return out
 
 
 def chain_reference(grid, col, state, mask: int, u, u_acc, gamma: float, flags: int, eval_roots, coef=None, exists=None):

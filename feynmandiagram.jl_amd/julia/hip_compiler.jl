@@ -960,6 +960,26 @@ function chain_reduce_device!(d_out::Ptr{Float64}, d_sum::Ptr{Float64}, n_root::
     return nothing
 end
 export chain_propose_device!, chain_step_device!, mc_chain_step_device!, chain_reduce_device!, FDG_CHAIN_INIT, FDG_CHAIN_MEASURE
+# Observables of the chain (fdg_chain_reduce_device_observables): d_out ((M + 1) + (M + 1)(M + 2) / 2, added to) = the sums S_p and the
+# packed upper triangle P_pq of the rows coef (M x n_use, HOST, row m the factors of observable m) over the window of n_use columns of
+# d_sum that starts at the 0-based column col_base, with the 0-based column norm_col as row M.  d_work holds
+# chain_reduce_observables_work_bytes(M, n_use) bytes of device memory.  (The size query returns a size_t: it is bound with @ccall.)
+const FDG_CHAIN_OBS_MAX = 16
+const FDG_CHAIN_OBS_COL_MAX = 1024
+const FDG_CHAIN_OBS_GROUPS = 1024
+function chain_reduce_observables_work_bytes(n_obs::Integer, n_use::Integer)
+    return Int(@ccall _libfdg.fdg_chain_reduce_observables_work_bytes(n_obs::UInt32, n_use::UInt32)::Csize_t)
+end
+function chain_reduce_device_observables!(d_out::Ptr{Float64}, d_sum::Ptr{Float64}, B::Integer, col_base::Integer, norm_col::Integer,
+    coef::Matrix{Float64}, d_work::Ptr{Cvoid}; stream::Ptr{Cvoid}=C_NULL)
+    n_obs, n_use = size(coef)
+    rows = permutedims(coef)                                 # row-major [n_obs][n_use] for the C side
+    _fdg_check(ccall((:fdg_chain_reduce_device_observables, _libfdg), Cint,
+        (Ptr{Float64}, Int64, UInt32, UInt32, UInt32, Ptr{Float64}, UInt32, Ptr{Float64}, Ptr{Cvoid}, Ptr{Cvoid}),
+        d_sum, B, col_base, n_use, norm_col, rows, n_obs, d_out, d_work, stream))
+    return nothing
+end
+export chain_reduce_observables_work_bytes, chain_reduce_device_observables!, FDG_CHAIN_OBS_MAX, FDG_CHAIN_OBS_COL_MAX, FDG_CHAIN_OBS_GROUPS
 export chain_step_device_matsubara!, mc_chain_step_device_matsubara!
 export chain_step_device_grouped!, mc_chain_step_device_grouped!
 # The chain with one discrete external variable behind the continuous ones (fdg_chain_propose_device_discrete,

@@ -50,6 +50,9 @@ per-variable factors, so every step serves as it is.  A group is redrawn whole o
 With local moves (``chain_integrate_shift``, ``ChainShift``, ``chain_moves_shift``; fdg_chain_propose_device_local) a variable is
 displaced in the map's uniform coordinate, ``y' = y + t h (mod 1)``, instead of being redrawn whole: the stationary density in ``y`` is
 ``a + gamma``, so the step's rule is the Metropolis rule of every proposal symmetric in ``y``, and every step serves as it is.
+With observables (``chain_integrate_observables``, ``chain_estimate_observables``, ``ChainObservablesResult``;
+fdg_chain_reduce_device_observables) the chain reports sums of roots, or of projected roots per frequency, with their covariance
+over the walkers: one reduction behind the chain forms the cross moments between the roots, which share their walkers.
 """
 from __future__ import annotations
 
@@ -872,6 +875,21 @@ class ChainResult:
     reweight: Optional[np.ndarray] = None   # [n_group] the factor of every weight group (:func:`chain_integrate_grouped`)
 
 
+@dataclass
+class ChainObservablesResult(ChainResult):
+    """What :func:`chain_integrate_observables` returns: a :class:`ChainResult` (whose own last field stays ``reweight``) with the
+    observables behind it, in the shapes and conventions of VegasResult's; with ``dmap`` every array has a leading n_bin axis."""
+    obs_mean: Optional[np.ndarray] = None    # with ``observables``: [n_obs] the combinations of the roots
+    obs_cov: Optional[np.ndarray] = None     # [n_obs, n_obs] their covariance over the walkers (:func:`chain_estimate_observables`)
+    obs_stderr: Optional[np.ndarray] = None  # [n_obs] sqrt of its diagonal
+    fobs_mean: Optional[np.ndarray] = None   # with ``freq_observables``: complex [n_freq, M]
+    fobs_stderr: Optional[np.ndarray] = None  # complex [n_freq, M]: the real parts' figures in .real, the imaginary parts' in .imag
+    fobs_cov: Optional[np.ndarray] = None    # real [n_freq, 2 M, 2 M]: the components (Re o_0 .., Im o_0 ..)
+    obs_sums: Optional[np.ndarray] = None    # [V] the raw sums (S, P packed) of fdg_chain_reduce_device_observables, additive over shards
+    fobs_sums: Optional[np.ndarray] = None   # [n_freq, V] those of every frequency's block, over the 2 M components
+    walker_sums: object = None               # with ``keep_sums``: the walkers' sums [n_columns, n_walker] of this shard, on the device
+
+
 def chain_estimate(S, Q, X, n_walker: int):
     """``(mean, stderr)`` per root from the reduced sums of a chain run (fdg_chain_reduce_device): with ``B = n_walker`` independent
     walkers whose sums are ``A_c(b)``, ``m_k = S_k / S_R``, ``V_cd = B / (B - 1) (sum_b A_c A_d - S_c S_d / B)`` for the pairs the sums
@@ -893,6 +911,36 @@ def chain_estimate(S, Q, X, n_walker: int):
     VRR = f * (Q[R] - S[R] * S[R] / B)
     var = (Vkk - 2.0 * mean * VkR + mean * mean * VRR) / (S[R] * S[R])
     return mean, np.sqrt(np.maximum(var, 0.0))
+
+
+def chain_estimate_observables(S, P, n_walker: int):
+    """``(mean [M], cov [M, M])`` of ``M`` observables from the sums of fdg_chain_reduce_device_observables: ``S [M + 1]`` with the
+    normalisation last, ``P`` the sums of products, packed upper triangle ``[(M + 1) (M + 2) / 2]`` row-major as the device writes
+    it, or the full symmetric ``[M + 1, M + 1]``.  With ``B = n_walker`` independent walkers ``m_p = S_p / S_M``, ``V_pq = B / (B - 1)
+    (P_pq - S_p S_q / B)`` and ``cov(m_p, m_q) = (V_pq - m_q V_pM - m_p V_qM + m_p m_q V_MM) / S_M**2``: the delta method for ratios
+    that share their walkers and their denominator.  The diagonal for a unit row is :func:`chain_estimate`'s variance.  ``B = 1``
+    gives nan covariances; ``S_M`` not positive raises ValueError; a diagonal that rounding leaves below zero is reported as 0."""
+    S, P = np.asarray(S, dtype=np.float64), np.asarray(P, dtype=np.float64)
+    M, B = S.shape[0] - 1 if S.ndim == 1 else -1, int(n_walker)
+    if M < 1 or B < 1:
+        raise ValueError("need S of n_obs + 1 >= 2 sums and n_walker >= 1")
+    if P.shape == ((M + 1) * (M + 2) // 2,):
+        full = np.zeros((M + 1, M + 1))
+        full[np.triu_indices(M + 1)] = P
+        P = full + np.triu(full, 1).T
+    elif P.shape != (M + 1, M + 1):
+        raise ValueError("P must be the packed upper triangle [(M + 1) (M + 2) / 2] or [M + 1, M + 1]")
+    if not S[M] > 0.0:
+        raise ValueError("S_M, the sum of the normalisation, is not positive: no step was measured")
+    mean = S[:M] / S[M]
+    if B == 1:
+        return mean, np.full((M, M), np.nan)
+    V = (B / (B - 1.0)) * (P - np.outer(S, S) / B)
+    t = mean[None, :] * V[:M, M][:, None]                   # [p, q] = m_q V_pM
+    cov = (V[:M, :M] - (t + t.T) + np.outer(mean, mean) * V[M, M]) / (S[M] * S[M])
+    d = np.arange(M)
+    cov[d, d] = np.maximum(cov[d, d], 0.0)
+    return mean, cov
 
 
 def chain_complex(v, n_freq: int, n_root: int) -> np.ndarray:
@@ -1007,7 +1055,7 @@ def chain_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: 
     still trains the map on the unprojected ``s``, and ``gamma = gamma_rel * mean(a)`` is taken of the projected ``a``.
 
     Out of scope here, refused with ValueError: ``polar``, ``groups``, a discrete variable (``dmap``), ``observables``,
-    ``freq_observables`` and ``strat`` together with the chain.  Not built either: training the map from the chain's own samples,
+    ``freq_observables`` (both are :func:`chain_integrate_observables`'s) and ``strat`` together with the chain.  Not built either: training the map from the chain's own samples,
     reweighting between orders; local (shift) proposals are :func:`chain_integrate_shift`'s.  The target these lead to is ``Sigma(i omega_0)`` of the Hubbard atom in
     the reference's test/hubbard.jl: its single-order case is what ``matsubara`` reaches; several orders at once need ``groups``,
     which :func:`chain_integrate_grouped` takes (with the reweighting between orders)."""
@@ -1046,7 +1094,7 @@ def chain_integrate_grouped(func_or_handle, tables, lo, hi, col, groups: WeightG
     4. the steps, the reduction and :func:`chain_estimate` as in :func:`chain_integrate`.
 
     ``reweight``: one finite factor > 0 per group.  Refused with ValueError: ``polar``, ``dmap``, ``observables``,
-    ``freq_observables`` and ``strat``."""
+    ``freq_observables`` (:func:`chain_integrate_observables` takes both) and ``strat``."""
     for name, value in excluded.items():
         if name not in _CHAIN_EXCLUDED or name == "groups":
             raise TypeError(f"chain_integrate_grouped() got an unexpected keyword argument '{name}'")
@@ -1082,7 +1130,8 @@ def chain_integrate_binned(func_or_handle, tables, lo, hi, col, dmap: DiscreteMa
     ``alpha`` and ``floor``); the leaf form has no such driver, so there ``n_warm > 0`` raises ValueError and ``vmap`` / ``dmap``
     are used as given.
 
-    Refused with ValueError: ``polar``, ``observables``, ``freq_observables`` and ``strat``; more than ``FDG_VEGAS_DIM_MAX - 1``
+    Refused with ValueError: ``polar``, ``observables``, ``freq_observables`` (:func:`chain_integrate_observables` takes both) and
+    ``strat``; more than ``FDG_VEGAS_DIM_MAX - 1``
     continuous variables (the discrete variable's Philox column would be the accept rule's)."""
     for name, value in excluded.items():
         if name not in _CHAIN_EXCLUDED or name in ("groups", "dmap"):
@@ -1126,8 +1175,8 @@ def chain_integrate_polar(func_or_handle, tables, lo, hi, col, polar: Sequence[P
     ``vegas_integrate_binned(polar=..., groups=...)`` with ``dmap``, ``vegas_integrate_stratified(..., Stratification((1,) * D),
     polar=..., groups=...)`` in the leaf form; the leaf form with ``dmap`` has none (``n_warm > 0`` raises ValueError).
 
-    Refused with ValueError: ``observables``, ``freq_observables`` and ``strat``.  Not built: moving the modulus or the direction of a
-    group alone."""
+    Refused with ValueError: ``observables``, ``freq_observables`` (:func:`chain_integrate_observables` takes both) and ``strat``.  Not
+    built: moving the modulus or the direction of a group alone."""
     for name, value in excluded.items():
         if name not in _CHAIN_EXCLUDED or name in ("polar", "groups", "dmap"):
             raise TypeError(f"chain_integrate_polar() got an unexpected keyword argument '{name}'")
@@ -1179,7 +1228,8 @@ def chain_integrate_shift(func_or_handle, tables, lo, hi, col, shift: ChainShift
 
     Refused with ValueError: a move whose two masks overlap; a shift of a variable of a polar group or of the discrete variable (the
     state holds Cartesian columns and no ``(k, theta, phi)``; inverting that is out of scope, as are local moves of the discrete
-    variable); a width outside ``(0, 0.5]``; ``observables``, ``freq_observables`` and ``strat``.  Not built: training the map from
+    variable); a width outside ``(0, 0.5]``; ``observables``, ``freq_observables`` (:func:`chain_integrate_observables` takes both,
+    with ``shift``) and ``strat``.  Not built: training the map from
     the chain.  Whether shifts lower the error on a given workload has not been measured."""
     for name, value in excluded.items():
         if name not in _CHAIN_EXCLUDED or name in ("polar", "groups", "dmap"):
@@ -1203,16 +1253,117 @@ def chain_integrate_shift(func_or_handle, tables, lo, hi, col, shift: ChainShift
                   weight_freq, groups, reweight, dmap, floor, polar or None, shift)
 
 
+def chain_integrate_observables(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: float = 1.0, lam: float = 0.0, *,
+                                n_walker: int, n_step: int, n_therm: int, observables: Optional[Observables] = None,
+                                freq_observables: Optional[FrequencyObservables] = None, shift: Optional[ChainShift] = None,
+                                moves: Optional[Sequence[int]] = None, gamma_rel: float = 1.0, gamma: Optional[float] = None,
+                                n_warm: int = 5, n_warm_sample: Optional[int] = None, n_grid: int = 64, alpha: float = 0.5,
+                                floor: float = 0.05, seed: int = 0, fixed=None, coef=None, vmap: Optional[VegasMap] = None,
+                                specialize_fused: bool = True, n_total: Optional[int] = None, shard_start: int = 0,
+                                reduce: Optional[Callable] = None, device="cuda", groups: Optional[WeightGroups] = None, reweight=None,
+                                dmap: Optional[DiscreteMap] = None, polar: Optional[Sequence[PolarVar]] = None,
+                                matsubara: Optional[MatsubaraProjection] = None, weight_freq: int = 0, keep_sums: bool = False,
+                                **excluded) -> ChainObservablesResult:
+    """The chain with OBSERVABLES, which the other chain drivers refuse: linear combinations of the roots with their covariance over
+    the walkers -- what every caller of the chain in the reference reports (test/ver4.jl:184-216: a direct and an exchange sum;
+    Sigma(i omega_n) of test/hubbard.jl: the sum over all orders).  All roots share their walkers, so the error of a sum is not the
+    quadrature of the roots' errors (fdg_chain_reduce_device_observables, include/fdg.h).
+
+    The chain is that of :func:`chain_integrate_shift` with the same keywords -- ``groups`` (with ``reweight``), ``dmap``, ``polar``,
+    ``matsubara``, ``weight_freq`` -- except that ``shift`` is optional: without it the moves are redraws (``moves``, default as in
+    the driver that takes the same keywords); with it ``moves`` must be None.  An observable is linear in the walkers' sums, so no
+    step changes: ``mean``, ``stderr``, ``S``, ``Q``, ``X``, ``acceptance``, ``gamma`` and the widths are bit for bit those of the
+    existing driver on the same arguments.  After its reduction the new entry runs once per block of the walkers' sums:
+
+    ``observables`` (an :class:`Observables`, rows of ``n_root`` factors): per value of the discrete variable the window of its ``R``
+    columns.  ``obs_mean [n_obs]``, ``obs_cov [n_obs, n_obs]``, ``obs_stderr``; with ``dmap`` a leading ``n_bin`` axis.  Refused with
+    ``matsubara``: the chain's sums are then projected, and the unprojected combination does not exist.
+
+    ``freq_observables`` (a :class:`FrequencyObservables`, needs ``matsubara``): per (value, frequency) the window of its ``2 R``
+    interleaved columns, with ``2 M`` rows in the component order ``(Re o_0 .., Im o_0 ..)``.  ``fobs_mean`` and ``fobs_stderr`` complex
+    ``[n_freq, M]`` (:func:`complex_components`), ``fobs_cov`` real ``[n_freq, 2 M, 2 M]``; with ``dmap`` a leading ``n_bin`` axis.
+
+    At least one of the two must be given.  ``reduce`` is applied to the arrays of raw sums (``obs_sums``, ``fobs_sums``), which are
+    additive over shards, as it is to the sums of the roots.  ``keep_sums``: ``walker_sums`` holds this shard's sums on the device.
+    Covariances between blocks -- between values of the discrete variable, or between frequencies -- are not formed.  Refused with
+    ValueError: ``strat``; everything :func:`chain_integrate_shift` refuses."""
+    for name, value in excluded.items():
+        if name != "strat":
+            raise TypeError(f"chain_integrate_observables() got an unexpected keyword argument '{name}'")
+        if value is not None:
+            raise ValueError(f"{name} cannot be combined with the chain yet")
+    if observables is None and freq_observables is None:
+        raise ValueError("chain_integrate_observables needs observables or freq_observables")
+    if observables is not None and not isinstance(observables, Observables):
+        raise ValueError("observables must be an Observables")
+    if freq_observables is not None and not isinstance(freq_observables, FrequencyObservables):
+        raise ValueError("freq_observables must be a FrequencyObservables")
+    if freq_observables is not None and matsubara is None:
+        raise ValueError("freq_observables needs matsubara: the projection whose frequencies they are reported at")
+    if observables is not None and matsubara is not None:
+        raise ValueError("observables cannot be combined with matsubara in the chain: its sums are then projected, and the unprojected "
+                         "combination does not exist")
+    if shift is not None and not isinstance(shift, ChainShift):
+        raise ValueError("shift must be a ChainShift")
+    if shift is not None and moves is not None:
+        raise ValueError("with shift the moves are shift.moves: moves must be None")
+    if polar is not None:
+        polar = list(polar)
+        if not all(isinstance(p, PolarVar) for p in polar):
+            raise ValueError("polar must be a sequence of PolarVar")
+    if dmap is not None and not isinstance(dmap, DiscreteMap):
+        raise ValueError("dmap must be a DiscreteMap")
+    if groups is not None and not isinstance(groups, WeightGroups):
+        raise ValueError("groups must be a WeightGroups")
+    if groups is None and reweight is not None:
+        raise ValueError("reweight goes with groups")
+    return _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step, n_therm, moves, gamma_rel, gamma, n_warm,
+                  n_warm_sample, n_grid, alpha, seed, fixed, coef, vmap, specialize_fused, n_total, shard_start, reduce, device, matsubara,
+                  weight_freq, groups, reweight, dmap, floor, polar or None, shift, observables, freq_observables, bool(keep_sums))
+
+
+def _chain_observable_rows(observables, freq_observables, R: int):
+    """The rows of the two kinds of observables as the new reduction takes them, checked: ``(ocoef [n_obs, R] or None, frows [2 M, 2 R]
+    or None)``; the frequency rows hold the real parts' factors at the window positions ``2 k`` and the imaginary parts' at ``2 k + 1``,
+    in the component order ``(Re o_0 .., Im o_0 ..)``."""
+    ocoef = frows = None
+    if observables is not None:
+        try:
+            ocoef = np.ascontiguousarray(observables.coef, dtype=np.float64)
+        except (TypeError, ValueError):                      # (rows of unequal lengths)
+            ocoef = np.zeros(0)
+        if ocoef.ndim != 2 or ocoef.shape[1] != R or not (1 <= ocoef.shape[0] <= capi.FDG_OBS_MAX) or not np.isfinite(ocoef).all():
+            raise ValueError(f"observables.coef must be [n_obs, n_root = {R}], finite, with 1 <= n_obs <= {capi.FDG_OBS_MAX}")
+        if R > capi.FDG_CHAIN_OBS_COL_MAX:
+            raise ValueError(f"the chain's observables take at most {capi.FDG_CHAIN_OBS_COL_MAX} roots")
+    if freq_observables is not None:
+        try:
+            fcoef = np.ascontiguousarray(freq_observables.coef, dtype=np.float64)
+        except (TypeError, ValueError):
+            fcoef = np.zeros(0)
+        if fcoef.ndim != 2 or fcoef.shape[1] != R or not (1 <= fcoef.shape[0] <= capi.FDG_FREQ_OBS_MAX) or not np.isfinite(fcoef).all():
+            raise ValueError(f"freq_observables.coef must be [n_obs, n_root = {R}], finite, with 1 <= n_obs <= {capi.FDG_FREQ_OBS_MAX}")
+        if 2 * R > capi.FDG_CHAIN_OBS_COL_MAX:
+            raise ValueError(f"the chain's frequency observables take at most {capi.FDG_CHAIN_OBS_COL_MAX // 2} roots")
+        M = fcoef.shape[0]
+        frows = np.zeros((2 * M, 2 * R))
+        frows[:M, 0::2], frows[M:, 1::2] = fcoef, fcoef
+    return ocoef, frows
+
+
 def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step, n_therm, moves, gamma_rel, gamma, n_warm, n_warm_sample,
            n_grid, alpha, seed, fixed, coef, vmap, specialize_fused, n_total, shard_start, reduce, device, matsubara, weight_freq,
-           wgroups=None, reweight=None, dmap=None, floor=0.05, polar=None, shift=None) -> ChainResult:
+           wgroups=None, reweight=None, dmap=None, floor=0.05, polar=None, shift=None, observables=None, freq_observables=None,
+           keep_sums=False) -> ChainResult:
     """The body of :func:`chain_integrate`, with ``wgroups`` of :func:`chain_integrate_grouped`, with ``dmap`` of
-    :func:`chain_integrate_binned`, with ``polar`` of :func:`chain_integrate_polar`, and with ``shift`` of
-    :func:`chain_integrate_shift` (the moves are then its pairs, and ``moves`` is None)."""
+    :func:`chain_integrate_binned`, with ``polar`` of :func:`chain_integrate_polar`, with ``shift`` of
+    :func:`chain_integrate_shift` (the moves are then its pairs, and ``moves`` is None), and with ``observables`` /
+    ``freq_observables`` of :func:`chain_integrate_observables` (calls behind the reduction; without them none is made)."""
     import torch
     device = torch.device(device)
     handle, n_col_k, n_col, col, written = _columns(func_or_handle, tables, col, polar, polar is not None)
     R = handle.table.n_root
+    ocoef, frows = _chain_observable_rows(observables, freq_observables, R)
     F, desc = 0, None
     if matsubara is not None:
         if not isinstance(matsubara, MatsubaraProjection):
@@ -1415,12 +1566,53 @@ def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step,
         if reduce is not None:
             reduce(out)
             reduce(acc_sum)
+        # the observables: one call per block of the sums, behind the reduction and on its stream
+        osum = fsum = None
+        NB = max(n_bin, 1)
+        if ocoef is not None or frows is not None:
+            work = torch.empty(max(capi.chain_reduce_observables_work_bytes(c.shape[0], c.shape[1]) for c in (ocoef, frows) if c is not None),
+                               dtype=torch.uint8, device=device)
+            if ocoef is not None:
+                Mo = ocoef.shape[0]
+                osum = torch.zeros((NB, (Mo + 1) + (Mo + 1) * (Mo + 2) // 2), **f64)
+                for j in range(NB):
+                    capi.chain_reduce_observables_device(total.data_ptr(), B, j * R, R, C, ocoef, osum[j].data_ptr(), work.data_ptr(), st)
+                if reduce is not None:
+                    reduce(osum)
+            if frows is not None:
+                Mf = frows.shape[0]
+                fsum = torch.zeros((NB * F, (Mf + 1) + (Mf + 1) * (Mf + 2) // 2), **f64)
+                for jf in range(NB * F):
+                    capi.chain_reduce_observables_device(total.data_ptr(), B, 2 * jf * R, 2 * R, C, frows, fsum[jf].data_ptr(),
+                                                         work.data_ptr(), st)
+                if reduce is not None:
+                    reduce(fsum)
         h = out.cpu().numpy()
+        osum, fsum = (None if v is None else v.cpu().numpy() for v in (osum, fsum))
     S, Q, X = h[:C + 1].copy(), h[C + 1:2 * C + 2].copy(), h[2 * C + 2:].copy()
     mean, err = chain_estimate(S, Q, X, N)                # (a root that does not exist has sums of 0: mean 0, stderr 0)
     if F:
         mean, err = chain_complex(mean, max(n_bin, 1) * F, R), chain_complex(err, max(n_bin, 1) * F, R)
     if dmap is not None:
         mean, err = (v.reshape((n_bin, F, R) if F else (n_bin, R)) for v in (mean, err))
-    return ChainResult(mean, err, float(acc_sum.item()) / (N * n_step), float(gamma), vmap, S, Q, X,
-                       shift_width=None if width is None else width.copy(), reweight=rho)
+    res = (ChainResult if osum is None and fsum is None else ChainObservablesResult)(
+        mean, err, float(acc_sum.item()) / (N * n_step), float(gamma), vmap, S, Q, X, shift_width=None if width is None else width.copy(),
+        reweight=rho)
+    if keep_sums:
+        res.walker_sums = total
+    lead = (n_bin,) if dmap is not None else ()
+    if osum is not None:
+        Mo = ocoef.shape[0]
+        est = [chain_estimate_observables(v[:Mo + 1], v[Mo + 1:], N) for v in osum]
+        res.obs_mean = np.stack([m for m, _ in est]).reshape(lead + (Mo,))
+        res.obs_cov = np.stack([c for _, c in est]).reshape(lead + (Mo, Mo))
+        res.obs_stderr = np.sqrt(np.stack([np.diag(c) for _, c in est])).reshape(lead + (Mo,))
+        res.obs_sums = osum.reshape(lead + osum.shape[1:])
+    if fsum is not None:
+        Mf = frows.shape[0]
+        est = [chain_estimate_observables(v[:Mf + 1], v[Mf + 1:], N) for v in fsum]
+        res.fobs_mean = complex_components(np.stack([m for m, _ in est])).reshape(lead + (F, Mf // 2))
+        res.fobs_stderr = complex_components(np.sqrt(np.stack([np.diag(c) for _, c in est]))).reshape(lead + (F, Mf // 2))
+        res.fobs_cov = np.stack([c for _, c in est]).reshape(lead + (F, Mf, Mf))
+        res.fobs_sums = fsum.reshape(lead + (F,) + fsum.shape[1:])
+    return res

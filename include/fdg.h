@@ -1466,6 +1466,42 @@ int fdg_chain_propose_device_local(const double *d_grid, uint32_t n_dim, uint32_
                                    const uint32_t *ext_col, const int32_t *d_bin, int32_t *d_binp, const fdg_vegas_polar *polar,
                                    uint32_t n_polar, int64_t n_walker, void *stream);
 
+/* ---- Observables of the chain: sums of roots with their covariance -------------------------------------------------------
+ * Every caller of the chain in the reference reports a SUM of roots (test/ver4.jl:184-216: a direct and an exchange component;
+ * Sigma(i omega_n) of test/hubbard.jl: the sum over all orders).  All roots share their walkers, so the error of a sum is not the
+ * quadrature of the roots' errors: it needs the cross moments sum_b A_k(b) A_l(b), which fdg_chain_reduce_device does not form.  An
+ * observable is linear in the walkers' sums, so one reduction behind the chain provides them; no step changes.
+ *
+ * d_sum is any chain's d_sum: [n_columns][n_walker], stride n_walker.  The window is the columns col_base .. col_base + n_use - 1,
+ * norm_col the normalisation's column (the last one of every layout), outside the window.  The layouts with bins and frequencies are
+ * blocks -- R columns at j R for bin j; 2 R interleaved real / imaginary columns at 2 (j F + f) R for bin j, frequency f -- and an
+ * observable lives in one block: one call per block.  coef is a HOST array [n_obs][n_use], copied before the call returns.
+ *
+ * With M = n_obs and A_c(b) = d_sum[c][b], every line one rounded fp64 operation, no FMA:
+ *     O_m(b) = the left fold of coef[m][c] * A_{col_base + c}(b) over ascending c, over the c with coef[m][c] != 0.0; the first product
+ *              starts the fold (no 0.0 + in front).                O_M(b) = A_{norm_col}(b)
+ *     d_out[p]                 += S_p  = sum_b O_p(b)              p = 0 .. M
+ *     d_out[M + 1 + idx(p, q)] += P_pq = sum_b O_p(b) * O_q(b)     p <= q,   idx(p, q) = p (M + 1) - p (p - 1) / 2 + (q - p)
+ * V = (M + 1) + (M + 1) (M + 2) / 2 doubles, the upper triangle packed row-major.  A column whose coefficient is zero in every row is
+ * never read: a nan there reaches no output (zeros are selected away, never multiplied).  A row without a term leaves its S entry
+ * and its row and column of P untouched in d_out.
+ * No float atomics; bitwise reproducible; the order of every sum is a function of n_walker alone, not of coef, n_obs or the kernel's
+ * instance: with W = min(max(ceil(n_walker / 256), 1), FDG_CHAIN_OBS_GROUPS), lane t of workgroup w adds from +0.0 the terms of the
+ * walkers b = 256 w + t + 256 W i, i = 0, 1, .. ascending; the 256 lane partials of a workgroup are added pairwise (stride 128, 64,
+ * .., 1); per output, lane t of 256 adds the workgroup partials w = t, t + 256, .. ascending from +0.0, then the same pairwise tree,
+ * then d_out[v] = d_out[v] + total (fdg_chain_reduce_device's scheme on [V][W] partials).
+ * The partials and the table of the live columns lie in d_work, which the caller provides: fdg_chain_reduce_observables_work_bytes
+ * (n_obs, n_use) bytes, 0 for arguments the entry refuses.  The entry takes no graph handle and allocates nothing.
+ * In this order, all before any device work.  FDG_E_INVALID: NULL d_sum, d_out or d_work; NULL coef; two of d_sum, d_out and d_work the
+ * same buffer; n_walker < 0; n_obs == 0; n_use == 0.  FDG_E_UNSUPPORTED: n_obs > FDG_CHAIN_OBS_MAX; n_use > FDG_CHAIN_OBS_COL_MAX.
+ * FDG_E_INVALID: a coefficient that is not finite; norm_col inside the window.  n_walker == 0 returns FDG_OK and writes nothing. */
+#define FDG_CHAIN_OBS_MAX 16       /* rows per call */
+#define FDG_CHAIN_OBS_COL_MAX 1024 /* columns of the window */
+#define FDG_CHAIN_OBS_GROUPS 1024  /* workgroups of the first stage */
+size_t fdg_chain_reduce_observables_work_bytes(uint32_t n_obs, uint32_t n_use);
+int fdg_chain_reduce_device_observables(const double *d_sum, int64_t n_walker, uint32_t col_base, uint32_t n_use, uint32_t norm_col,
+                                        const double *coef, uint32_t n_obs, double *d_out, void *d_work, void *stream);
+
 /* Device workspace control: the interpreter keeps per-sample overflow slots in
  * an HBM panel owned by the handle; it is sized on first use for the number of
  * resident waves.  This releases it (and any loaded module). */
