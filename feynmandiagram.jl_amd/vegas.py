@@ -57,6 +57,7 @@ over the walkers: one reduction behind the chain forms the cross moments between
 from __future__ import annotations
 
 import math
+from collections import namedtuple
 from dataclasses import dataclass, field
 from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 
@@ -401,8 +402,8 @@ def _iteration_seed(seed: int, it: int) -> int:
     return (int(seed) + it * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
 
 
-def _integrate_strat(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_iter, n_sample, n_grid, alpha, seed, n_discard, fixed, coef, device,
-                     vmap, specialize_fused, n_total, shard_start, reduce, strat, polar=None, wgroups=None, alloc_cols=None):
+def _integrate_strat(func_or_handle, tables, lo, hi, col, kF, beta, lam, *, n_iter, n_sample, n_grid, alpha, seed, n_discard, fixed, coef,
+                     device, vmap, specialize_fused, n_total, shard_start, reduce, strat, polar=None, wgroups=None, alloc_cols=None):
     """:func:`vegas_integrate` with ``strat`` and :func:`vegas_integrate_stratified`.  Per iteration: allocate, sample, accumulate,
     refine the map, fdg_strat_allocate_cols.  Without ``polar`` and ``wgroups`` the device calls are the plain stratified ones."""
     import torch
@@ -504,8 +505,10 @@ def vegas_integrate_stratified(func_or_handle, tables, lo, hi, col, strat: Strat
     bit."""
     if strat is None:
         raise ValueError("vegas_integrate_stratified needs a Stratification")
-    return _integrate_strat(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_iter, n_sample, n_grid, alpha, seed, n_discard, fixed,
-                            coef, device, vmap, specialize_fused, n_total, shard_start, reduce, strat, polar, groups, alloc_cols)
+    return _integrate_strat(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_iter=n_iter, n_sample=n_sample, n_grid=n_grid, alpha=alpha,
+                            seed=seed, n_discard=n_discard, fixed=fixed, coef=coef, device=device, vmap=vmap,
+                            specialize_fused=specialize_fused, n_total=n_total, shard_start=shard_start, reduce=reduce, strat=strat,
+                            polar=polar, wgroups=groups, alloc_cols=alloc_cols)
 
 
 def groups_from_dof(dof, pools) -> WeightGroups:
@@ -531,7 +534,18 @@ def groups_from_dof(dof, pools) -> WeightGroups:
     return WeightGroups(tuple(root_group), tuple(sets))
 
 
-def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter, n_sample, n_grid, alpha, floor, seed, n_discard, fixed, coef,
+def _coef_table(table, what: str, R: int, limit: int) -> np.ndarray:
+    """``table.coef`` (``what``: ``observables`` or ``freq_observables``) as float64 ``[n_obs, R]``: finite, ``1 <= n_obs <= limit``."""
+    try:
+        c = np.ascontiguousarray(table.coef, dtype=np.float64)
+    except (TypeError, ValueError):                          # (rows of unequal lengths)
+        c = np.zeros(0)
+    if c.ndim != 2 or c.shape[1] != R or not (1 <= c.shape[0] <= limit) or not np.isfinite(c).all():
+        raise ValueError(f"{what}.coef must be [n_obs, n_root = {R}], finite, with 1 <= n_obs <= {limit}")
+    return c
+
+
+def _integrate(func_or_handle, tables, lo, hi, col, kF, beta, lam, *, dmap, n_iter, n_sample, n_grid, alpha, floor, seed, n_discard, fixed, coef,
                device, vmap, specialize_fused, n_total, shard_start, reduce, polar=None, matsubara=None, wgroups=None, observables=None,
                freq_observables=None):
     """The driver behind :func:`vegas_integrate` (``dmap`` None: results ``[R]``) and :func:`vegas_integrate_binned` (``[n_bin, R]``);
@@ -552,16 +566,8 @@ def _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter,
     D, G, NB = vmap.n_dim, vmap.n_grid, 1 if dmap is None else dmap.n_bin
     if wgroups is not None:
         _check_weight_groups(wgroups, R, D, groups, limit=False)
-    ocoef = None
-    if observables is not None:
-        ocoef = np.ascontiguousarray(observables.coef, dtype=np.float64)
-        if ocoef.ndim != 2 or ocoef.shape[1] != R or not (1 <= ocoef.shape[0] <= capi.FDG_OBS_MAX) or not np.isfinite(ocoef).all():
-            raise ValueError(f"observables.coef must be [n_obs, n_root = {R}], finite, with 1 <= n_obs <= {capi.FDG_OBS_MAX}")
-    fcoef = None
-    if freq_observables is not None:
-        fcoef = np.ascontiguousarray(freq_observables.coef, dtype=np.float64)
-        if fcoef.ndim != 2 or fcoef.shape[1] != R or not (1 <= fcoef.shape[0] <= capi.FDG_FREQ_OBS_MAX) or not np.isfinite(fcoef).all():
-            raise ValueError(f"freq_observables.coef must be [n_obs, n_root = {R}], finite, with 1 <= n_obs <= {capi.FDG_FREQ_OBS_MAX}")
+    ocoef = None if observables is None else _coef_table(observables, "observables", R, capi.FDG_OBS_MAX)
+    fcoef = None if freq_observables is None else _coef_table(freq_observables, "freq_observables", R, capi.FDG_FREQ_OBS_MAX)
     B = int(n_sample)
     N = B if n_total is None else int(n_total)
     if B < 1 or N < 2 or n_iter < 1 or not (0 <= n_discard < n_iter):
@@ -743,14 +749,15 @@ def vegas_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: 
     graph's leaves themselves (fdg_accumulate_device_strat), ``col[d]`` the leaf that variable ``d`` fills and ``fixed`` the values
     of the others.  Together with ``polar``, ``matsubara``, ``groups``, ``observables`` or ``freq_observables`` (and with a discrete variable) it raises
     ValueError: ``polar`` and ``groups`` go through :func:`vegas_integrate_stratified`, the others are not built yet.  None: the calls made and their bits are what they are without this keyword."""
+    shared = dict(n_iter=n_iter, n_sample=n_sample, n_grid=n_grid, alpha=alpha, seed=seed, n_discard=n_discard, fixed=fixed, coef=coef,
+                  device=device, vmap=vmap, specialize_fused=specialize_fused, n_total=n_total, shard_start=shard_start, reduce=reduce)
     if strat is not None:
         if polar or matsubara is not None or groups is not None or observables is not None or freq_observables is not None:
             raise ValueError("strat cannot be combined with polar, matsubara, groups, observables or freq_observables here "
                              "(polar and groups: vegas_integrate_stratified)")
-        return _integrate_strat(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_iter, n_sample, n_grid, alpha, seed, n_discard, fixed,
-                                coef, device, vmap, specialize_fused, n_total, shard_start, reduce, strat)
-    return _integrate(func_or_handle, tables, lo, hi, col, None, kF, beta, lam, n_iter, n_sample, n_grid, alpha, 0.0, seed, n_discard, fixed, coef,
-                      device, vmap, specialize_fused, n_total, shard_start, reduce, polar, matsubara, groups, observables, freq_observables)
+        return _integrate_strat(func_or_handle, tables, lo, hi, col, kF, beta, lam, strat=strat, **shared)
+    return _integrate(func_or_handle, tables, lo, hi, col, kF, beta, lam, dmap=None, floor=0.0, polar=polar, matsubara=matsubara, wgroups=groups,
+                      observables=observables, freq_observables=freq_observables, **shared)
 
 
 def uniform_cdf(n_bin: int) -> np.ndarray:
@@ -853,9 +860,10 @@ def vegas_integrate_binned(func_or_handle, tables, lo, hi, col, dmap: DiscreteMa
     ``strat`` is not built for a discrete variable yet: anything but None raises ValueError."""
     if strat is not None:
         raise ValueError("strat cannot be combined with a discrete variable (dmap)")
-    return _integrate(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, n_iter, n_sample, n_grid, alpha, floor, seed, n_discard, fixed,
-                      coef, device, vmap, specialize_fused, n_total, shard_start, reduce, polar, matsubara, groups, observables,
-                      freq_observables)
+    return _integrate(func_or_handle, tables, lo, hi, col, kF, beta, lam, dmap=dmap, floor=floor, n_iter=n_iter, n_sample=n_sample, n_grid=n_grid,
+                      alpha=alpha, seed=seed, n_discard=n_discard, fixed=fixed, coef=coef, device=device, vmap=vmap,
+                      specialize_fused=specialize_fused, n_total=n_total, shard_start=shard_start, reduce=reduce, polar=polar,
+                      matsubara=matsubara, wgroups=groups, observables=observables, freq_observables=freq_observables)
 
 
 # ---- Markov-chain sampling on the VEGAS map (include/fdg.h: fdg_chain_propose_device, fdg_[mc_]chain_step_device, fdg_chain_reduce_device) ---- #
@@ -1018,6 +1026,31 @@ _CHAIN_EXCLUDED = ("polar", "groups", "dmap", "observables", "freq_observables",
 _CHAIN_TRAIN_KEY = 0x632BE59BD9B4E019       # added to ``seed`` for the map's training: the chain's counters are used once
 
 
+def _refuse_excluded(driver: str, excluded) -> None:
+    """The keywords a chain driver has no parameter for: a name outside ``_CHAIN_EXCLUDED`` is unknown to ``driver``, a value of one
+    inside it is refused (an empty ``polar`` is none)."""
+    for name, value in excluded.items():
+        if name not in _CHAIN_EXCLUDED:
+            raise TypeError(f"{driver}() got an unexpected keyword argument '{name}'")
+        if value is not None and not (name == "polar" and not value):
+            raise ValueError(f"{name} cannot be combined with the chain yet")
+
+
+def _check_kinds(polar, dmap, groups, reweight):
+    """The kinds of the optional keywords the later chain drivers share, behind each driver's own checks; returns ``polar`` as a list."""
+    if polar is not None:
+        polar = list(polar)
+        if not all(isinstance(p, PolarVar) for p in polar):
+            raise ValueError("polar must be a sequence of PolarVar")
+    if dmap is not None and not isinstance(dmap, DiscreteMap):
+        raise ValueError("dmap must be a DiscreteMap")
+    if groups is not None and not isinstance(groups, WeightGroups):
+        raise ValueError("groups must be a WeightGroups")
+    if groups is None and reweight is not None:
+        raise ValueError("reweight goes with groups")
+    return polar
+
+
 def chain_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: float = 1.0, lam: float = 0.0, *, n_walker: int,
                     n_step: int, n_therm: int, moves: Optional[Sequence[int]] = None, gamma_rel: float = 1.0, gamma: Optional[float] = None,
                     n_warm: int = 5, n_warm_sample: Optional[int] = None, n_grid: int = 64, alpha: float = 0.5, seed: int = 0, fixed=None,
@@ -1059,14 +1092,11 @@ def chain_integrate(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: 
     reweighting between orders; local (shift) proposals are :func:`chain_integrate_shift`'s.  The target these lead to is ``Sigma(i omega_0)`` of the Hubbard atom in
     the reference's test/hubbard.jl: its single-order case is what ``matsubara`` reaches; several orders at once need ``groups``,
     which :func:`chain_integrate_grouped` takes (with the reweighting between orders)."""
-    for name, value in excluded.items():
-        if name not in _CHAIN_EXCLUDED:
-            raise TypeError(f"chain_integrate() got an unexpected keyword argument '{name}'")
-        if value is not None and not (name == "polar" and not value):
-            raise ValueError(f"{name} cannot be combined with the chain yet")
-    return _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step, n_therm, moves, gamma_rel, gamma, n_warm,
-                  n_warm_sample, n_grid, alpha, seed, fixed, coef, vmap, specialize_fused, n_total, shard_start, reduce, device, matsubara,
-                  weight_freq)
+    _refuse_excluded("chain_integrate", excluded)
+    return _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker=n_walker, n_step=n_step, n_therm=n_therm, moves=moves,
+                  gamma_rel=gamma_rel, gamma=gamma, n_warm=n_warm, n_warm_sample=n_warm_sample, n_grid=n_grid, alpha=alpha, seed=seed,
+                  fixed=fixed, coef=coef, vmap=vmap, specialize_fused=specialize_fused, n_total=n_total, shard_start=shard_start,
+                  reduce=reduce, device=device, matsubara=matsubara, weight_freq=weight_freq)
 
 
 def chain_integrate_grouped(func_or_handle, tables, lo, hi, col, groups: WeightGroups, kF: float = 0.0, beta: float = 1.0, lam: float = 0.0, *,
@@ -1095,16 +1125,13 @@ def chain_integrate_grouped(func_or_handle, tables, lo, hi, col, groups: WeightG
 
     ``reweight``: one finite factor > 0 per group.  Refused with ValueError: ``polar``, ``dmap``, ``observables``,
     ``freq_observables`` (:func:`chain_integrate_observables` takes both) and ``strat``."""
-    for name, value in excluded.items():
-        if name not in _CHAIN_EXCLUDED or name == "groups":
-            raise TypeError(f"chain_integrate_grouped() got an unexpected keyword argument '{name}'")
-        if value is not None and not (name == "polar" and not value):
-            raise ValueError(f"{name} cannot be combined with the chain yet")
+    _refuse_excluded("chain_integrate_grouped", excluded)
     if not isinstance(groups, WeightGroups):
         raise ValueError("groups must be a WeightGroups")
-    return _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step, n_therm, moves, gamma_rel, gamma, n_warm,
-                  n_warm_sample, n_grid, alpha, seed, fixed, coef, vmap, specialize_fused, n_total, shard_start, reduce, device, matsubara,
-                  weight_freq, groups, reweight)
+    return _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker=n_walker, n_step=n_step, n_therm=n_therm, moves=moves,
+                  gamma_rel=gamma_rel, gamma=gamma, n_warm=n_warm, n_warm_sample=n_warm_sample, n_grid=n_grid, alpha=alpha, seed=seed,
+                  fixed=fixed, coef=coef, vmap=vmap, specialize_fused=specialize_fused, n_total=n_total, shard_start=shard_start,
+                  reduce=reduce, device=device, matsubara=matsubara, weight_freq=weight_freq, wgroups=groups, reweight=reweight)
 
 
 def chain_integrate_binned(func_or_handle, tables, lo, hi, col, dmap: DiscreteMap, kF: float = 0.0, beta: float = 1.0, lam: float = 0.0, *,
@@ -1133,20 +1160,15 @@ def chain_integrate_binned(func_or_handle, tables, lo, hi, col, dmap: DiscreteMa
     Refused with ValueError: ``polar``, ``observables``, ``freq_observables`` (:func:`chain_integrate_observables` takes both) and
     ``strat``; more than ``FDG_VEGAS_DIM_MAX - 1``
     continuous variables (the discrete variable's Philox column would be the accept rule's)."""
-    for name, value in excluded.items():
-        if name not in _CHAIN_EXCLUDED or name in ("groups", "dmap"):
-            raise TypeError(f"chain_integrate_binned() got an unexpected keyword argument '{name}'")
-        if value is not None and not (name == "polar" and not value):
-            raise ValueError(f"{name} cannot be combined with the chain yet")
+    _refuse_excluded("chain_integrate_binned", excluded)
     if not isinstance(dmap, DiscreteMap):
         raise ValueError("dmap must be a DiscreteMap")
-    if groups is not None and not isinstance(groups, WeightGroups):
-        raise ValueError("groups must be a WeightGroups")
-    if groups is None and reweight is not None:
-        raise ValueError("reweight goes with groups")
-    return _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step, n_therm, moves, gamma_rel, gamma, n_warm,
-                  n_warm_sample, n_grid, alpha, seed, fixed, coef, vmap, specialize_fused, n_total, shard_start, reduce, device, matsubara,
-                  weight_freq, groups, reweight, dmap, floor)
+    _check_kinds(None, dmap, groups, reweight)
+    return _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker=n_walker, n_step=n_step, n_therm=n_therm, moves=moves,
+                  gamma_rel=gamma_rel, gamma=gamma, n_warm=n_warm, n_warm_sample=n_warm_sample, n_grid=n_grid, alpha=alpha, seed=seed,
+                  fixed=fixed, coef=coef, vmap=vmap, specialize_fused=specialize_fused, n_total=n_total, shard_start=shard_start,
+                  reduce=reduce, device=device, matsubara=matsubara, weight_freq=weight_freq, wgroups=groups, reweight=reweight, dmap=dmap,
+                  floor=floor)
 
 
 def chain_integrate_polar(func_or_handle, tables, lo, hi, col, polar: Sequence[PolarVar], kF: float = 0.0, beta: float = 1.0, lam: float = 0.0, *,
@@ -1177,23 +1199,15 @@ def chain_integrate_polar(func_or_handle, tables, lo, hi, col, polar: Sequence[P
 
     Refused with ValueError: ``observables``, ``freq_observables`` (:func:`chain_integrate_observables` takes both) and ``strat``.  Not
     built: moving the modulus or the direction of a group alone."""
-    for name, value in excluded.items():
-        if name not in _CHAIN_EXCLUDED or name in ("polar", "groups", "dmap"):
-            raise TypeError(f"chain_integrate_polar() got an unexpected keyword argument '{name}'")
-        if value is not None:
-            raise ValueError(f"{name} cannot be combined with the chain yet")
-    polar = list(polar) if polar is not None else None
-    if polar is None or not all(isinstance(p, PolarVar) for p in polar):
+    _refuse_excluded("chain_integrate_polar", excluded)
+    if polar is None:
         raise ValueError("polar must be a sequence of PolarVar")
-    if dmap is not None and not isinstance(dmap, DiscreteMap):
-        raise ValueError("dmap must be a DiscreteMap")
-    if groups is not None and not isinstance(groups, WeightGroups):
-        raise ValueError("groups must be a WeightGroups")
-    if groups is None and reweight is not None:
-        raise ValueError("reweight goes with groups")
-    return _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step, n_therm, moves, gamma_rel, gamma, n_warm,
-                  n_warm_sample, n_grid, alpha, seed, fixed, coef, vmap, specialize_fused, n_total, shard_start, reduce, device, matsubara,
-                  weight_freq, groups, reweight, dmap, floor, polar)
+    polar = _check_kinds(polar, dmap, groups, reweight)
+    return _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker=n_walker, n_step=n_step, n_therm=n_therm, moves=moves,
+                  gamma_rel=gamma_rel, gamma=gamma, n_warm=n_warm, n_warm_sample=n_warm_sample, n_grid=n_grid, alpha=alpha, seed=seed,
+                  fixed=fixed, coef=coef, vmap=vmap, specialize_fused=specialize_fused, n_total=n_total, shard_start=shard_start,
+                  reduce=reduce, device=device, matsubara=matsubara, weight_freq=weight_freq, wgroups=groups, reweight=reweight, dmap=dmap,
+                  floor=floor, polar=polar)
 
 
 def chain_integrate_shift(func_or_handle, tables, lo, hi, col, shift: ChainShift, kF: float = 0.0, beta: float = 1.0, lam: float = 0.0, *,
@@ -1231,26 +1245,15 @@ def chain_integrate_shift(func_or_handle, tables, lo, hi, col, shift: ChainShift
     variable); a width outside ``(0, 0.5]``; ``observables``, ``freq_observables`` (:func:`chain_integrate_observables` takes both,
     with ``shift``) and ``strat``.  Not built: training the map from
     the chain.  Whether shifts lower the error on a given workload has not been measured."""
-    for name, value in excluded.items():
-        if name not in _CHAIN_EXCLUDED or name in ("polar", "groups", "dmap"):
-            raise TypeError(f"chain_integrate_shift() got an unexpected keyword argument '{name}'")
-        if value is not None:
-            raise ValueError(f"{name} cannot be combined with the chain yet")
+    _refuse_excluded("chain_integrate_shift", excluded)
     if not isinstance(shift, ChainShift):
         raise ValueError("shift must be a ChainShift")
-    if polar is not None:
-        polar = list(polar)
-        if not all(isinstance(p, PolarVar) for p in polar):
-            raise ValueError("polar must be a sequence of PolarVar")
-    if dmap is not None and not isinstance(dmap, DiscreteMap):
-        raise ValueError("dmap must be a DiscreteMap")
-    if groups is not None and not isinstance(groups, WeightGroups):
-        raise ValueError("groups must be a WeightGroups")
-    if groups is None and reweight is not None:
-        raise ValueError("reweight goes with groups")
-    return _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step, n_therm, None, gamma_rel, gamma, n_warm,
-                  n_warm_sample, n_grid, alpha, seed, fixed, coef, vmap, specialize_fused, n_total, shard_start, reduce, device, matsubara,
-                  weight_freq, groups, reweight, dmap, floor, polar or None, shift)
+    polar = _check_kinds(polar, dmap, groups, reweight)
+    return _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker=n_walker, n_step=n_step, n_therm=n_therm, moves=None,
+                  gamma_rel=gamma_rel, gamma=gamma, n_warm=n_warm, n_warm_sample=n_warm_sample, n_grid=n_grid, alpha=alpha, seed=seed,
+                  fixed=fixed, coef=coef, vmap=vmap, specialize_fused=specialize_fused, n_total=n_total, shard_start=shard_start,
+                  reduce=reduce, device=device, matsubara=matsubara, weight_freq=weight_freq, wgroups=groups, reweight=reweight, dmap=dmap,
+                  floor=floor, polar=polar or None, shift=shift)
 
 
 def chain_integrate_observables(func_or_handle, tables, lo, hi, col, kF: float = 0.0, beta: float = 1.0, lam: float = 0.0, *,
@@ -1287,11 +1290,7 @@ def chain_integrate_observables(func_or_handle, tables, lo, hi, col, kF: float =
     additive over shards, as it is to the sums of the roots.  ``keep_sums``: ``walker_sums`` holds this shard's sums on the device.
     Covariances between blocks -- between values of the discrete variable, or between frequencies -- are not formed.  Refused with
     ValueError: ``strat``; everything :func:`chain_integrate_shift` refuses."""
-    for name, value in excluded.items():
-        if name != "strat":
-            raise TypeError(f"chain_integrate_observables() got an unexpected keyword argument '{name}'")
-        if value is not None:
-            raise ValueError(f"{name} cannot be combined with the chain yet")
+    _refuse_excluded("chain_integrate_observables", excluded)
     if observables is None and freq_observables is None:
         raise ValueError("chain_integrate_observables needs observables or freq_observables")
     if observables is not None and not isinstance(observables, Observables):
@@ -1307,19 +1306,13 @@ def chain_integrate_observables(func_or_handle, tables, lo, hi, col, kF: float =
         raise ValueError("shift must be a ChainShift")
     if shift is not None and moves is not None:
         raise ValueError("with shift the moves are shift.moves: moves must be None")
-    if polar is not None:
-        polar = list(polar)
-        if not all(isinstance(p, PolarVar) for p in polar):
-            raise ValueError("polar must be a sequence of PolarVar")
-    if dmap is not None and not isinstance(dmap, DiscreteMap):
-        raise ValueError("dmap must be a DiscreteMap")
-    if groups is not None and not isinstance(groups, WeightGroups):
-        raise ValueError("groups must be a WeightGroups")
-    if groups is None and reweight is not None:
-        raise ValueError("reweight goes with groups")
-    return _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step, n_therm, moves, gamma_rel, gamma, n_warm,
-                  n_warm_sample, n_grid, alpha, seed, fixed, coef, vmap, specialize_fused, n_total, shard_start, reduce, device, matsubara,
-                  weight_freq, groups, reweight, dmap, floor, polar or None, shift, observables, freq_observables, bool(keep_sums))
+    polar = _check_kinds(polar, dmap, groups, reweight)
+    return _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker=n_walker, n_step=n_step, n_therm=n_therm, moves=moves,
+                  gamma_rel=gamma_rel, gamma=gamma, n_warm=n_warm, n_warm_sample=n_warm_sample, n_grid=n_grid, alpha=alpha, seed=seed,
+                  fixed=fixed, coef=coef, vmap=vmap, specialize_fused=specialize_fused, n_total=n_total, shard_start=shard_start,
+                  reduce=reduce, device=device, matsubara=matsubara, weight_freq=weight_freq, wgroups=groups, reweight=reweight, dmap=dmap,
+                  floor=floor, polar=polar or None, shift=shift, observables=observables, freq_observables=freq_observables,
+                  keep_sums=bool(keep_sums))
 
 
 def _chain_observable_rows(observables, freq_observables, R: int):
@@ -1328,21 +1321,11 @@ def _chain_observable_rows(observables, freq_observables, R: int):
     in the component order ``(Re o_0 .., Im o_0 ..)``."""
     ocoef = frows = None
     if observables is not None:
-        try:
-            ocoef = np.ascontiguousarray(observables.coef, dtype=np.float64)
-        except (TypeError, ValueError):                      # (rows of unequal lengths)
-            ocoef = np.zeros(0)
-        if ocoef.ndim != 2 or ocoef.shape[1] != R or not (1 <= ocoef.shape[0] <= capi.FDG_OBS_MAX) or not np.isfinite(ocoef).all():
-            raise ValueError(f"observables.coef must be [n_obs, n_root = {R}], finite, with 1 <= n_obs <= {capi.FDG_OBS_MAX}")
+        ocoef = _coef_table(observables, "observables", R, capi.FDG_OBS_MAX)
         if R > capi.FDG_CHAIN_OBS_COL_MAX:
             raise ValueError(f"the chain's observables take at most {capi.FDG_CHAIN_OBS_COL_MAX} roots")
     if freq_observables is not None:
-        try:
-            fcoef = np.ascontiguousarray(freq_observables.coef, dtype=np.float64)
-        except (TypeError, ValueError):
-            fcoef = np.zeros(0)
-        if fcoef.ndim != 2 or fcoef.shape[1] != R or not (1 <= fcoef.shape[0] <= capi.FDG_FREQ_OBS_MAX) or not np.isfinite(fcoef).all():
-            raise ValueError(f"freq_observables.coef must be [n_obs, n_root = {R}], finite, with 1 <= n_obs <= {capi.FDG_FREQ_OBS_MAX}")
+        fcoef = _coef_table(freq_observables, "freq_observables", R, capi.FDG_FREQ_OBS_MAX)
         if 2 * R > capi.FDG_CHAIN_OBS_COL_MAX:
             raise ValueError(f"the chain's frequency observables take at most {capi.FDG_CHAIN_OBS_COL_MAX // 2} roots")
         M = fcoef.shape[0]
@@ -1351,20 +1334,35 @@ def _chain_observable_rows(observables, freq_observables, R: int):
     return ocoef, frows
 
 
-def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step, n_therm, moves, gamma_rel, gamma, n_warm, n_warm_sample,
-           n_grid, alpha, seed, fixed, coef, vmap, specialize_fused, n_total, shard_start, reduce, device, matsubara, weight_freq,
-           wgroups=None, reweight=None, dmap=None, floor=0.05, polar=None, shift=None, observables=None, freq_observables=None,
-           keep_sums=False) -> ChainResult:
-    """The body of :func:`chain_integrate`, with ``wgroups`` of :func:`chain_integrate_grouped`, with ``dmap`` of
-    :func:`chain_integrate_binned`, with ``polar`` of :func:`chain_integrate_polar`, with ``shift`` of
-    :func:`chain_integrate_shift` (the moves are then its pairs, and ``moves`` is None), and with ``observables`` /
-    ``freq_observables`` of :func:`chain_integrate_observables` (calls behind the reduction; without them none is made)."""
+class _ChainPlan(namedtuple("_ChainPlan", "handle entry desc keep col n_col fx R F n_bin C B N n_step n_therm n_warm shard_start vmap D G DV "
+                            "pgroups moves lmoves width ocoef frows NG rho mc coef gamma gamma_rel wgroups dmap shift device")):
+    """What :func:`_chain_plan` decides of a chain run, and the arguments it checked that the later stages read as given.
+
+    ``handle``; ``entry``: the step entry, "", "_matsubara", "_grouped" or "_binned"; ``desc``, ``keep``: the projection's descriptor
+    (None without ``matsubara``) and what keeps its arrays alive; ``col``: as ints, None at a polar group's variables; ``n_col``,
+    ``fx [n_col]``: the columns of ``x`` and their fixed values; ``R`` roots, ``F`` frequencies (0 without ``matsubara``), ``n_bin``
+    values of the discrete variable (0 without ``dmap``); ``C``: the columns of the walkers' sums before the normalisation's; ``B``
+    walkers of this shard, of ``N`` in all, from ``shard_start``; ``n_step``, ``n_therm``, ``n_warm`` as ints; ``vmap`` with its
+    ``D`` variables and ``G`` cells; ``DV``: the variables a move can name, bit ``D`` the discrete one; ``pgroups``: the polar groups
+    as ``(var, cols)`` pairs (None without ``polar``); ``moves``: the redraw mask of every move; ``lmoves``, ``width``: the moves'
+    shift masks and the ``D`` half widths (None without ``shift``; the walk tunes ``width`` in place); ``ocoef``, ``frows``:
+    :func:`_chain_observable_rows`; ``NG`` weight groups (0 without ``wgroups``) and ``rho``, ``reweight`` as given.
+    As given: ``mc`` = ``(kF, beta, lam)`` (None: the leaf form), ``coef``, ``gamma``, ``gamma_rel``, ``wgroups``, ``dmap``,
+    ``shift``, ``device`` (a ``torch.device``)."""
+    __slots__ = ()
+
+
+def _chain_plan(func_or_handle, tables, lo, hi, col, kF, beta, lam, *, n_walker, n_step, n_therm, n_warm, gamma_rel, n_grid, shard_start,
+                weight_freq, device, moves=None, gamma=None, fixed=None, coef=None, vmap=None, n_total=None, matsubara=None, wgroups=None,
+                reweight=None, dmap=None, polar=None, shift=None, observables=None, freq_observables=None) -> _ChainPlan:
+    """The first stage of :func:`_chain`: every check of the arguments, in the order of the drivers' refusals, and every quantity the
+    later stages derive from them.  Host work only: it runs with ``device="cpu"`` on a machine without a GPU."""
     import torch
     device = torch.device(device)
     handle, n_col_k, n_col, col, written = _columns(func_or_handle, tables, col, polar, polar is not None)
     R = handle.table.n_root
     ocoef, frows = _chain_observable_rows(observables, freq_observables, R)
-    F, desc = 0, None
+    F, desc, keep = 0, None, None
     if matsubara is not None:
         if not isinstance(matsubara, MatsubaraProjection):
             raise ValueError("matsubara must be a MatsubaraProjection")
@@ -1387,7 +1385,7 @@ def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step,
                 raise ValueError(f"matsubara: a time label of root {k} lies outside [1, {n_time}]")
             cin.append(t0 + i - 1 if live[k] else 0)
             cout.append(t0 + o - 1 if live[k] else 0)
-        desc, _keep = capi.make_chain_matsubara(matsubara.freq, matsubara.fermionic, int(weight_freq), cin, cout, beta)
+        desc, keep = capi.make_chain_matsubara(matsubara.freq, matsubara.fermionic, int(weight_freq), cin, cout, beta)
     n_bin = 0
     if dmap is not None:
         if not isinstance(dmap, DiscreteMap):
@@ -1443,7 +1441,7 @@ def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step,
     if polar is not None and any((m & bits) not in (0, bits) for m in moves for bits in pbits):
         raise ValueError("a move redraws a polar group whole or not at all: the state does not hold (k, theta, phi)")
     fx = _fixed(fixed, n_col)
-    rho = None
+    NG, rho = 0, None
     if wgroups is not None:
         NG = _check_weight_groups(wgroups, R, D, pgroups)
         if coef is not None and np.shape(coef) != (R,):
@@ -1452,167 +1450,223 @@ def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, n_walker, n_step,
             rho = np.array(reweight, dtype=np.float64)
             if rho.shape != (NG,) or not (np.isfinite(rho) & (rho > 0.0)).all():
                 raise ValueError("reweight must hold one finite factor > 0 per group")
-    if n_warm:
-        kw = dict(n_iter=n_warm, n_grid=G, alpha=alpha, seed=(int(seed) + _CHAIN_TRAIN_KEY) & 0xFFFFFFFFFFFFFFFF, fixed=fixed, coef=coef,
-                  device=device, vmap=vmap, specialize_fused=specialize_fused, reduce=reduce)
+    entry = "_binned" if dmap is not None else "_grouped" if wgroups is not None else "_matsubara" if desc is not None else ""
+    return _ChainPlan(handle=handle, entry=entry, desc=desc, keep=keep, col=col, n_col=n_col, fx=fx, R=R, F=F, n_bin=n_bin, C=C, B=B, N=N,
+                      n_step=n_step, n_therm=n_therm, n_warm=n_warm, shard_start=int(shard_start), vmap=vmap, D=D, G=G, DV=DV,
+                      pgroups=pgroups, moves=moves, lmoves=lmoves, width=width, ocoef=ocoef, frows=frows, NG=NG, rho=rho,
+                      mc=None if tables is None else (kF, beta, lam), coef=coef, gamma=gamma, gamma_rel=gamma_rel, wgroups=wgroups,
+                      dmap=dmap, shift=shift, device=device)
+
+
+def _chain_warm(p: _ChainPlan, func_or_handle, tables, lo, hi, kF, beta, lam, *, n_warm_sample, alpha, floor, seed, fixed, polar,
+                specialize_fused, n_total, shard_start, reduce) -> None:
+    """The map's training: ``p.n_warm`` iterations of the direct driver that takes the chain's keywords, on a Philox key of its own;
+    without a warm-up, the fused kernel's specialisation that such a driver would have asked for."""
+    if p.n_warm:
+        kw = dict(n_iter=p.n_warm, n_grid=p.G, alpha=alpha, seed=(int(seed) + _CHAIN_TRAIN_KEY) & 0xFFFFFFFFFFFFFFFF, fixed=fixed,
+                  coef=p.coef, device=p.device, vmap=p.vmap, specialize_fused=specialize_fused, reduce=reduce)
         if n_warm_sample is None:
-            kw.update(n_sample=B, n_total=n_total, shard_start=shard_start)
+            kw.update(n_sample=p.B, n_total=n_total, shard_start=shard_start)
         else:
             kw.update(n_sample=int(n_warm_sample))
         if polar is not None:
             kw["polar"] = polar
-        if dmap is not None:
-            vegas_integrate_binned(func_or_handle, tables, lo, hi, col, dmap, kF, beta, lam, floor=floor, groups=wgroups, **kw)
-        elif (wgroups is not None or polar is not None) and tables is None:
-            vegas_integrate_stratified(func_or_handle, tables, lo, hi, col, Stratification((1,) * D), kF, beta, lam, groups=wgroups, **kw)
+        if p.dmap is not None:
+            vegas_integrate_binned(func_or_handle, tables, lo, hi, p.col, p.dmap, kF, beta, lam, floor=floor, groups=p.wgroups, **kw)
+        elif (p.wgroups is not None or polar is not None) and tables is None:
+            vegas_integrate_stratified(func_or_handle, tables, lo, hi, p.col, Stratification((1,) * p.D), kF, beta, lam, groups=p.wgroups, **kw)
         else:
-            if wgroups is not None:
-                kw["groups"] = wgroups
+            if p.wgroups is not None:
+                kw["groups"] = p.wgroups
             elif tables is None:
-                kw["strat"] = Stratification((1,) * D)
-            vegas_integrate(func_or_handle, tables, lo, hi, col, kF, beta, lam, **kw)
+                kw["strat"] = Stratification((1,) * p.D)
+            vegas_integrate(func_or_handle, tables, lo, hi, p.col, kF, beta, lam, **kw)
     elif specialize_fused and tables is not None:
-        handle.specialize_fused(tables)
+        p.handle.specialize_fused(tables)
+
+
+class _ChainWalkers(namedtuple("_ChainWalkers", "step total n_acc gamma rho keep")):
+    """The placed walkers, what :func:`_chain_place` hands to the walk and to the results: ``step(mask, sample_offset, gamma, flags,
+    shift_mask=0)`` makes one proposal and one step of every walker; ``total [C + 1, B]`` the walkers' sums and ``n_acc [B]`` their
+    acceptances, on the device; ``gamma``; ``rho``: the reweight factors in use; ``keep``: what ``step`` holds
+    only addresses of -- the arrays of the groups' descriptor and the walkers' values of the discrete variable."""
+    __slots__ = ()
+
+
+def _chain_place(p: _ChainPlan, st, *, seed, reduce) -> _ChainWalkers:
+    """Allocates the walkers' state, places them with FDG_CHAIN_INIT (twice where the reweight factors come from the first placement)
+    and takes ``gamma`` from the placed weights unless it was given.  ``step`` is the one place that issues a proposal and a step."""
+    import torch
+    handle, vmap, dmap, wgroups, coef, rho, gamma = p.handle, p.vmap, p.dmap, p.wgroups, p.coef, p.rho, p.gamma
+    R, B, N, D, DV = p.R, p.B, p.N, p.D, p.DV
     all_mask = (1 << D) - 1
-    with torch.cuda.device(device):
-        st = torch.cuda.current_stream(device).cuda_stream
-        f64 = dict(dtype=torch.float64, device=device)
-        x = _state(fx, B, device)
-        xp = torch.empty_like(x)
-        fac, facp = torch.ones((DV, B), **f64), torch.empty((DV, B), **f64)          # (row D: the discrete variable's 1 / p_j)
-        bins = binp = None
-        if dmap is not None:
-            bins, binp = (torch.zeros(B, dtype=torch.int32, device=device) for _ in range(2))
-        dv = _discrete(dmap, 0, bins, binp)
-        root, a = torch.zeros((R, B), **f64), torch.zeros(B, **f64)
-        total = torch.zeros((C + 1, B), **f64)
-        n_acc = torch.zeros(B, dtype=torch.int32, device=device)
+    f64 = dict(dtype=torch.float64, device=p.device)
+    x = _state(p.fx, B, p.device)
+    xp = torch.empty_like(x)
+    fac, facp = torch.ones((DV, B), **f64), torch.empty((DV, B), **f64)          # (row D: the discrete variable's 1 / p_j)
+    bins = binp = None
+    if dmap is not None:
+        bins, binp = (torch.zeros(B, dtype=torch.int32, device=p.device) for _ in range(2))
+    dv = _discrete(dmap, 0, bins, binp)
+    root, a = torch.zeros((R, B), **f64), torch.zeros(B, **f64)
+    total = torch.zeros((p.C + 1, B), **f64)
+    n_acc = torch.zeros(B, dtype=torch.int32, device=p.device)
 
-        def step(mask, off, g, flags, lmask=0):
-            grid = (vmap.d_grid.data_ptr(), D, G, col, n_col)
-            walk = (seed, off, x.data_ptr(), B, fac.data_ptr(), xp.data_ptr(), B, facp.data_ptr())
-            disc = (bool((mask >> D) & 1), dv.d_cdf, dv.n_bin, dv.d_ext, dv.ext_col, dv.d_bin, dv.d_binp)
-            if shift is not None:
-                capi.chain_propose_device_local(*grid, mask & all_mask, lmask, width, *walk, *disc, pgroups or (), B, st)
-            elif polar is not None:
-                capi.chain_propose_device_polar(*grid, mask & all_mask, *walk, *disc, pgroups, B, st)
-            elif dmap is None:
-                capi.chain_propose_device(*grid, mask, *walk, B, st)
-            else:
-                capi.chain_propose_device_discrete(*grid, mask & all_mask, *walk, *disc, B, st)
-            handle._chain_step(entry, mc, xp.data_ptr(), B, facp.data_ptr(), n_col, D, coef, g, seed, off, flags, x.data_ptr(), B,
-                               fac.data_ptr(), root.data_ptr(), a.data_ptr(), total.data_ptr(), n_acc.data_ptr(), B, st, desc, gdesc,
-                               None if dmap is None else (dv.n_bin, dv.d_binp, dv.d_bin))
+    def step(mask, off, g, flags, lmask=0):
+        grid = (vmap.d_grid.data_ptr(), D, p.G, p.col, p.n_col)
+        walk = (seed, off, x.data_ptr(), B, fac.data_ptr(), xp.data_ptr(), B, facp.data_ptr())
+        disc = (bool((mask >> D) & 1), dv.d_cdf, dv.n_bin, dv.d_ext, dv.ext_col, dv.d_bin, dv.d_binp)
+        if p.shift is not None:
+            capi.chain_propose_device_local(*grid, mask & all_mask, lmask, p.width, *walk, *disc, p.pgroups or (), B, st)
+        elif p.pgroups is not None:
+            capi.chain_propose_device_polar(*grid, mask & all_mask, *walk, *disc, p.pgroups, B, st)
+        elif dmap is None:
+            capi.chain_propose_device(*grid, mask, *walk, B, st)
+        else:
+            capi.chain_propose_device_discrete(*grid, mask & all_mask, *walk, *disc, B, st)
+        handle._chain_step(p.entry, p.mc, xp.data_ptr(), B, facp.data_ptr(), p.n_col, D, coef, g, seed, off, flags, x.data_ptr(), B,
+                           fac.data_ptr(), root.data_ptr(), a.data_ptr(), total.data_ptr(), n_acc.data_ptr(), B, st, p.desc, gdesc,
+                           None if dmap is None else (dv.n_bin, dv.d_binp, dv.d_bin))
 
-        entry = "_binned" if dmap is not None else "_grouped" if wgroups is not None else "_matsubara" if desc is not None else ""
-        mc = None if tables is None else (kF, beta, lam)
-        gdesc = None
-        if wgroups is not None:
-            gdesc, _gkeep = capi.make_chain_groups(wgroups.root_group, wgroups.var_sets, rho)
-        place = (1 << DV) - 1                                                            # every variable, the discrete one too
-        step(place, int(shard_start), 1.0, capi.FDG_CHAIN_INIT)                          # (gamma enters no result of the placement)
-        if wgroups is not None and rho is None:
-            # rho_g = 1 / mean_b |jac_g s_g| of the placement, then the placement again on the same counters with rho
-            from .nodetable import FDG_NO_ROOT
-            members = [[k for k in range(R) if int(handle.table.root_slot[k]) != FDG_NO_ROOT and int(wgroups.root_group[k]) == g]
-                       for g in range(NG)]
-            sg = torch.zeros(NG, **f64)
-            for g, ks in enumerate(members):
-                if ks:
-                    c = torch.ones(len(ks), **f64) if coef is None else torch.as_tensor(np.asarray(coef, dtype=np.float64)[ks], **f64)
-                    jg = fac[sorted(set(int(d) for d in wgroups.var_sets[g]))].prod(0)       # (an empty set: 1)
-                    if dmap is not None:
-                        jg = jg * fac[D]
-                    sg[g] = (jg * (c[:, None] * root[ks]).sum(0)).abs().sum()
-            if reduce is not None:
-                reduce(sg)
-            mean_g = sg.cpu().numpy() / N
-            rho = np.ones(NG)
-            for g, ks in enumerate(members):
-                if ks:
-                    if not (math.isfinite(mean_g[g]) and mean_g[g] > 0.0 and math.isfinite(1.0 / mean_g[g])):
-                        raise ValueError(f"the map's estimate of the integral of |s_g| of group {g} is not positive and finite: pass reweight")
-                    rho[g] = 1.0 / mean_g[g]
-            gdesc, _gkeep = capi.make_chain_groups(wgroups.root_group, wgroups.var_sets, rho)
-            step(place, int(shard_start), 1.0, capi.FDG_CHAIN_INIT)
-        if gamma is None:
-            sa = a.sum().reshape(1)
-            if reduce is not None:
-                reduce(sa)
-            gamma = float(gamma_rel) * float(sa.item()) / N
-            if not (math.isfinite(gamma) and gamma > 0.0):
-                raise ValueError("the map's estimate of the integral of |s| is not positive: pass gamma")
-        n_acc.zero_()
-
-        def accepted():                                       # the acceptances of all walkers so far: an integer, exact in fp64
-            s = n_acc.sum(dtype=torch.float64).reshape(1)
-            if reduce is not None:
-                reduce(s)
-            return float(s.item())
-
-        for t in range(n_step):
-            i = t % len(moves)
-            lm = 0 if lmoves is None else lmoves[i]
-            # tuning, in the discarded steps only: after a move that shifts exactly one variable and does nothing else
-            tuned = shift is not None and shift.tune and t < n_therm and moves[i] == 0 and lm != 0 and lm & (lm - 1) == 0
-            before = accepted() if tuned else 0.0
-            step(moves[i], (t + 1) * N + int(shard_start), float(gamma), capi.FDG_CHAIN_MEASURE if t >= n_therm else 0, lm)
-            if tuned:
-                d = lm.bit_length() - 1
-                width[d] = chain_tune_width(float(width[d]), accepted() - before, N, float(shift.target))
-        out = torch.zeros(3 * C + 2, **f64)
-        capi.chain_reduce_device(total.data_ptr(), C, B, out.data_ptr(), st)
-        acc_sum = n_acc.sum(dtype=torch.float64).reshape(1)
+    gdesc = gkeep = None
+    if wgroups is not None:
+        gdesc, gkeep = capi.make_chain_groups(wgroups.root_group, wgroups.var_sets, rho)
+    place = (1 << DV) - 1                                                            # every variable, the discrete one too
+    step(place, p.shard_start, 1.0, capi.FDG_CHAIN_INIT)                             # (gamma enters no result of the placement)
+    if wgroups is not None and rho is None:
+        # rho_g = 1 / mean_b |jac_g s_g| of the placement, then the placement again on the same counters with rho
+        from .nodetable import FDG_NO_ROOT
+        members = [[k for k in range(R) if int(handle.table.root_slot[k]) != FDG_NO_ROOT and int(wgroups.root_group[k]) == g]
+                   for g in range(p.NG)]
+        sg = torch.zeros(p.NG, **f64)
+        for g, ks in enumerate(members):
+            if ks:
+                c = torch.ones(len(ks), **f64) if coef is None else torch.as_tensor(np.asarray(coef, dtype=np.float64)[ks], **f64)
+                jg = fac[sorted(set(int(d) for d in wgroups.var_sets[g]))].prod(0)       # (an empty set: 1)
+                if dmap is not None:
+                    jg = jg * fac[D]
+                sg[g] = (jg * (c[:, None] * root[ks]).sum(0)).abs().sum()
         if reduce is not None:
-            reduce(out)
-            reduce(acc_sum)
-        # the observables: one call per block of the sums, behind the reduction and on its stream
-        osum = fsum = None
-        NB = max(n_bin, 1)
-        if ocoef is not None or frows is not None:
-            work = torch.empty(max(capi.chain_reduce_observables_work_bytes(c.shape[0], c.shape[1]) for c in (ocoef, frows) if c is not None),
-                               dtype=torch.uint8, device=device)
-            if ocoef is not None:
-                Mo = ocoef.shape[0]
-                osum = torch.zeros((NB, (Mo + 1) + (Mo + 1) * (Mo + 2) // 2), **f64)
-                for j in range(NB):
-                    capi.chain_reduce_observables_device(total.data_ptr(), B, j * R, R, C, ocoef, osum[j].data_ptr(), work.data_ptr(), st)
-                if reduce is not None:
-                    reduce(osum)
-            if frows is not None:
-                Mf = frows.shape[0]
-                fsum = torch.zeros((NB * F, (Mf + 1) + (Mf + 1) * (Mf + 2) // 2), **f64)
-                for jf in range(NB * F):
-                    capi.chain_reduce_observables_device(total.data_ptr(), B, 2 * jf * R, 2 * R, C, frows, fsum[jf].data_ptr(),
-                                                         work.data_ptr(), st)
-                if reduce is not None:
-                    reduce(fsum)
-        h = out.cpu().numpy()
-        osum, fsum = (None if v is None else v.cpu().numpy() for v in (osum, fsum))
+            reduce(sg)
+        mean_g = sg.cpu().numpy() / N
+        rho = np.ones(p.NG)
+        for g, ks in enumerate(members):
+            if ks:
+                if not (math.isfinite(mean_g[g]) and mean_g[g] > 0.0 and math.isfinite(1.0 / mean_g[g])):
+                    raise ValueError(f"the map's estimate of the integral of |s_g| of group {g} is not positive and finite: pass reweight")
+                rho[g] = 1.0 / mean_g[g]
+        gdesc, gkeep = capi.make_chain_groups(wgroups.root_group, wgroups.var_sets, rho)
+        step(place, p.shard_start, 1.0, capi.FDG_CHAIN_INIT)
+    if gamma is None:
+        sa = a.sum().reshape(1)
+        if reduce is not None:
+            reduce(sa)
+        gamma = float(p.gamma_rel) * float(sa.item()) / N
+        if not (math.isfinite(gamma) and gamma > 0.0):
+            raise ValueError("the map's estimate of the integral of |s| is not positive: pass gamma")
+    n_acc.zero_()
+    return _ChainWalkers(step, total, n_acc, float(gamma), rho, (gkeep, bins, binp))      # (``step`` holds ``dv``'s addresses, not the tensors)
+
+
+def _chain_walk(p: _ChainPlan, w: _ChainWalkers, *, reduce) -> None:
+    """The ``n_step`` steps, measuring from ``n_therm`` on; with ``shift.tune`` the widths ``p.width`` move in the discarded steps."""
+    import torch
+    shift, moves, lmoves, N = p.shift, p.moves, p.lmoves, p.N
+
+    def accepted():                                       # the acceptances of all walkers so far: an integer, exact in fp64
+        s = w.n_acc.sum(dtype=torch.float64).reshape(1)
+        if reduce is not None:
+            reduce(s)
+        return float(s.item())
+
+    for t in range(p.n_step):
+        i = t % len(moves)
+        lm = 0 if lmoves is None else lmoves[i]
+        # tuning, in the discarded steps only: after a move that shifts exactly one variable and does nothing else
+        tuned = shift is not None and shift.tune and t < p.n_therm and moves[i] == 0 and lm != 0 and lm & (lm - 1) == 0
+        before = accepted() if tuned else 0.0
+        w.step(moves[i], (t + 1) * N + p.shard_start, w.gamma, capi.FDG_CHAIN_MEASURE if t >= p.n_therm else 0, lm)
+        if tuned:
+            d = lm.bit_length() - 1
+            p.width[d] = chain_tune_width(float(p.width[d]), accepted() - before, N, float(shift.target))
+
+
+def _observable_estimates(sums: np.ndarray, M: int, N: int):
+    """:func:`chain_estimate_observables` on every block of raw sums ``[blocks, V]`` of ``M`` rows: ``(mean [blocks, M],
+    cov [blocks, M, M], stderr [blocks, M])``."""
+    est = [chain_estimate_observables(v[:M + 1], v[M + 1:], N) for v in sums]
+    return np.stack([m for m, _ in est]), np.stack([c for _, c in est]), np.sqrt(np.stack([np.diag(c) for _, c in est]))
+
+
+def _chain_results(p: _ChainPlan, w: _ChainWalkers, st, *, reduce, keep_sums) -> ChainResult:
+    """The reduction of the walkers' sums, one observables call per block of them behind it on its stream, and the estimates."""
+    import torch
+    R, F, C, B, N = p.R, p.F, p.C, p.B, p.N
+    f64 = dict(dtype=torch.float64, device=p.device)
+    out = torch.zeros(3 * C + 2, **f64)
+    capi.chain_reduce_device(w.total.data_ptr(), C, B, out.data_ptr(), st)
+    acc_sum = w.n_acc.sum(dtype=torch.float64).reshape(1)
+    if reduce is not None:
+        reduce(out)
+        reduce(acc_sum)
+
+    def block_sums(rows, n_block):                         # the raw sums of ``rows`` over each of the windows of their width
+        M, width = rows.shape
+        sums = torch.zeros((n_block, (M + 1) + (M + 1) * (M + 2) // 2), **f64)
+        for j in range(n_block):
+            capi.chain_reduce_observables_device(w.total.data_ptr(), B, j * width, width, C, rows, sums[j].data_ptr(), work.data_ptr(), st)
+        if reduce is not None:
+            reduce(sums)
+        return sums
+
+    NB = max(p.n_bin, 1)
+    rows = [c for c in (p.ocoef, p.frows) if c is not None]
+    if rows:
+        work = torch.empty(max(capi.chain_reduce_observables_work_bytes(*c.shape) for c in rows), dtype=torch.uint8, device=p.device)
+    osum = None if p.ocoef is None else block_sums(p.ocoef, NB)
+    fsum = None if p.frows is None else block_sums(p.frows, NB * F)
+    h = out.cpu().numpy()
+    osum, fsum = (None if v is None else v.cpu().numpy() for v in (osum, fsum))
     S, Q, X = h[:C + 1].copy(), h[C + 1:2 * C + 2].copy(), h[2 * C + 2:].copy()
     mean, err = chain_estimate(S, Q, X, N)                # (a root that does not exist has sums of 0: mean 0, stderr 0)
     if F:
-        mean, err = chain_complex(mean, max(n_bin, 1) * F, R), chain_complex(err, max(n_bin, 1) * F, R)
-    if dmap is not None:
-        mean, err = (v.reshape((n_bin, F, R) if F else (n_bin, R)) for v in (mean, err))
+        mean, err = chain_complex(mean, NB * F, R), chain_complex(err, NB * F, R)
+    if p.dmap is not None:
+        mean, err = (v.reshape((p.n_bin, F, R) if F else (p.n_bin, R)) for v in (mean, err))
     res = (ChainResult if osum is None and fsum is None else ChainObservablesResult)(
-        mean, err, float(acc_sum.item()) / (N * n_step), float(gamma), vmap, S, Q, X, shift_width=None if width is None else width.copy(),
-        reweight=rho)
+        mean, err, float(acc_sum.item()) / (N * p.n_step), w.gamma, p.vmap, S, Q, X, shift_width=None if p.width is None else p.width.copy(),
+        reweight=w.rho)
     if keep_sums:
-        res.walker_sums = total
-    lead = (n_bin,) if dmap is not None else ()
+        res.walker_sums = w.total
+    lead = (p.n_bin,) if p.dmap is not None else ()
     if osum is not None:
-        Mo = ocoef.shape[0]
-        est = [chain_estimate_observables(v[:Mo + 1], v[Mo + 1:], N) for v in osum]
-        res.obs_mean = np.stack([m for m, _ in est]).reshape(lead + (Mo,))
-        res.obs_cov = np.stack([c for _, c in est]).reshape(lead + (Mo, Mo))
-        res.obs_stderr = np.sqrt(np.stack([np.diag(c) for _, c in est])).reshape(lead + (Mo,))
+        Mo = p.ocoef.shape[0]
+        m, c, e = _observable_estimates(osum, Mo, N)
+        res.obs_mean, res.obs_cov, res.obs_stderr = m.reshape(lead + (Mo,)), c.reshape(lead + (Mo, Mo)), e.reshape(lead + (Mo,))
         res.obs_sums = osum.reshape(lead + osum.shape[1:])
     if fsum is not None:
-        Mf = frows.shape[0]
-        est = [chain_estimate_observables(v[:Mf + 1], v[Mf + 1:], N) for v in fsum]
-        res.fobs_mean = complex_components(np.stack([m for m, _ in est])).reshape(lead + (F, Mf // 2))
-        res.fobs_stderr = complex_components(np.sqrt(np.stack([np.diag(c) for _, c in est]))).reshape(lead + (F, Mf // 2))
-        res.fobs_cov = np.stack([c for _, c in est]).reshape(lead + (F, Mf, Mf))
+        Mf = p.frows.shape[0]
+        m, c, e = _observable_estimates(fsum, Mf, N)
+        res.fobs_mean, res.fobs_stderr = (complex_components(v).reshape(lead + (F, Mf // 2)) for v in (m, e))
+        res.fobs_cov = c.reshape(lead + (F, Mf, Mf))
         res.fobs_sums = fsum.reshape(lead + (F,) + fsum.shape[1:])
     return res
+
+
+def _chain(func_or_handle, tables, lo, hi, col, kF, beta, lam, *, n_warm_sample, alpha, seed, fixed, specialize_fused, n_total, shard_start, reduce,
+           floor=0.05, polar=None, keep_sums=False, **plan) -> ChainResult:
+    """The body of :func:`chain_integrate`, with ``wgroups`` of :func:`chain_integrate_grouped`, with ``dmap`` of
+    :func:`chain_integrate_binned`, with ``polar`` of :func:`chain_integrate_polar`, with ``shift`` of
+    :func:`chain_integrate_shift` (the moves are then its pairs, and ``moves`` is None), and with ``observables`` /
+    ``freq_observables`` of :func:`chain_integrate_observables` (calls behind the reduction; without them none is made).
+    Five stages: the plan, the warm-up, the placement, the walk, the results.  ``plan``: the keywords that only :func:`_chain_plan`
+    reads, which names them; the ones spelled out here are read by a later stage too."""
+    import torch
+    p = _chain_plan(func_or_handle, tables, lo, hi, col, kF, beta, lam, fixed=fixed, n_total=n_total, shard_start=shard_start, polar=polar, **plan)
+    _chain_warm(p, func_or_handle, tables, lo, hi, kF, beta, lam, n_warm_sample=n_warm_sample, alpha=alpha, floor=floor, seed=seed, fixed=fixed,
+                polar=polar, specialize_fused=specialize_fused, n_total=n_total, shard_start=shard_start, reduce=reduce)
+    with torch.cuda.device(p.device):
+        st = torch.cuda.current_stream(p.device).cuda_stream
+        w = _chain_place(p, st, seed=seed, reduce=reduce)
+        _chain_walk(p, w, reduce=reduce)
+        return _chain_results(p, w, st, reduce=reduce, keep_sums=keep_sums)
