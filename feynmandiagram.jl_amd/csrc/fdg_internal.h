@@ -92,15 +92,12 @@ struct fdg_ws_set {
 // What the launch path needs of a handle's options, parsed when the handle is created and whenever fdg_graph_set_option changes one: between an
 // evaluation entry point and hipModuleLaunchKernel nothing is looked up by name.
 struct fdg_launch_cfg {
-  bool no_rl = false, no_fused_acc = false, no_pool = false, pool_no_acc = false, no_streaming = false, no_w2 = false, no_coop = false, no_rm = false;
-  bool transpose_narrow = false;
+  bool no_rl = false, no_fused_acc = false, no_pool = false, no_streaming = false, no_coop = false, no_rm = false;
   uint32_t root_scratch_min = 16;          // roots from which row-major root matrices go through the column-major scratch (0: never)
   uint64_t root_scratch_mb = 256;
   int waves_per_cu = 0;                    // > 0: resident waves per CU forced (no oversubscription)
   int oversub = 0;                         // > 0: oversubscription factor forced
   long mem_waves = -1;                     // >= 0: resident waves per CU of memory-bound graphs (0: rule off); -1: the library's rule
-  long mem_oversub = 1;
-  double mem_ratio = 2.5;
   int tile_claim = -1;                     // memory-bound launches of the root-writing one-wave kernels: waves claim their next tiles from a counter (FDG_ISA_TILE_CLAIM):
                                            // 0 never, 1 always, -1 the library's rule: launches of 256 rounds and more
   uint64_t sm_chunk_bytes = 1ull << 29;    // row-major input without an in-place variant: bytes of leaves transposed per chunk
@@ -161,7 +158,7 @@ struct fdg_graph {
   uint64_t rl_valu = 0;            // FDG_K_RL: fold steps per evaluation
   bool coop_enabled = false;       // FDG_K_COOP: the tuner's verdict (a variant that is present but measured slower stays off)
   uint32_t coop_panel_wg = 0;      // FDG_K_COOP / FDG_K_POOL: bytes of spill panel per workgroup (the sum over its waves)
-  uint32_t pool_panel_wg = 0, pool_fetch = 0, pool_unit = 1;
+  uint32_t pool_panel_wg = 0, pool_fetch = 0;
   uint64_t pool_valu = 0;
   // companion HIP-source kernels of an ISA-specialised handle, used for sample-major input (FDG_SPEC_ROW_MAJOR_COMPANION)
   std::vector<char> alt_code;

@@ -346,7 +346,6 @@ struct Emit {
   int align = 1;              // option FDG_ISA_ALIGN: 0 print as rounds 1-4 did, 1 no 8-byte instruction straddles, 2 no fp64 / VOP3 one does
   bool pad_ok = true;         // false inside the cooperative / pooled kernels: their waves meet at barriers, and the pads cost gv_ver4_4's pooled kernel 12 %
                               // (profiles/r05_log_align_shift.txt)
-  int shift = 0;              // dev: FDG_ISA_SHIFT=n puts n s_nop at the head of every kernel (how much does the mere position matter?)
   uint64_t n_align_nop = 0;
   bool streaming = false;     // the kernel being printed is the variant for line-aligned batches: non-temporal leaf loads and root stores
   long nt_dist = -1;          // streaming kernels of long programs: a re-loaded leaf's earlier load is non-temporal too when the re-load is this many leaf loads away (-1: never)
@@ -484,27 +483,20 @@ static void rm_plan(const Lowered &p, const OptProgram &prog, uint32_t rm_bufs, 
                     std::vector<int> &rm_ld_buf) {
   const uint32_t rm_full = p.L / RM_CHUNK, rm_tail = (p.L % RM_CHUNK) ? 1u : 0u, n_chunk = rm_full + rm_tail;
   auto rm_chunk_of = [&](uint32_t leaf) { return leaf < rm_full * RM_CHUNK ? leaf / RM_CHUNK : rm_full; };
-  // Round 6 (OptParams::rm_pair, four buffers): chunks are fetched in PAIRS -- chunks 2u and 2u + 1 back to back into two adjacent buffers.  A
-  // 128-byte row segment of a row that is not a whole number of lines straddles two cache lines, and the line it shares with the next chunk is
-  // requested again when that chunk is fetched -- a chunk's worth of computing later, by which time the XCD's L2 has turned over for a quarter of
-  // them: the chunked variant moves 1.25 x the matrix, and its fetch stream ALONE runs at the memory system's ceiling for that traffic
-  // (profiles/r06_log_sweep_m.txt).  Fetched together, the two halves of a pair ask for their shared line within nanoseconds of each other.
-  const uint32_t G = (prog.params.rm_pair && rm_bufs >= 4 && rm_bufs % 2 == 0) ? 2u : 1u;
-  const uint32_t n_unit = (n_chunk + G - 1) / G, n_ubuf = rm_bufs / G;
   const size_t n_ops = prog.ops.size();
   rm_fetch.assign(n_ops + 1, {});
   rm_ld_buf.assign(n_ops, -1);
-  std::vector<std::vector<size_t>> uses(n_unit);
-  for (size_t q = 0; q < n_ops; ++q) if (prog.ops[q].kind == M_LD_LEAF) uses[rm_chunk_of(prog.ops[q].a) / G].push_back(q);
+  std::vector<std::vector<size_t>> uses(n_chunk);
+  for (size_t q = 0; q < n_ops; ++q) if (prog.ops[q].kind == M_LD_LEAF) uses[rm_chunk_of(prog.ops[q].a)].push_back(q);
   std::vector<size_t> cursor(uses.size(), 0);
-  std::vector<int64_t> resident(n_ubuf, -1);
-  std::vector<size_t> free_from(n_ubuf, 0);      // op index from which the buffer (pair) may be filled again
+  std::vector<int64_t> resident(rm_bufs, -1);
+  std::vector<size_t> free_from(rm_bufs, 0);     // op index from which the buffer may be filled again
   for (size_t q = 0; q < n_ops; ++q) {
     if (prog.ops[q].kind != M_LD_LEAF) continue;
-    const uint32_t c = rm_chunk_of(prog.ops[q].a), u = c / G;
+    const uint32_t u = rm_chunk_of(prog.ops[q].a);
     cursor[u]++;                                   // uses[u][cursor[u]..] are the later ones
     int b = -1;
-    for (uint32_t k = 0; k < n_ubuf; ++k) if (resident[k] == (int64_t)u) b = (int)k;
+    for (uint32_t k = 0; k < rm_bufs; ++k) if (resident[k] == (int64_t)u) b = (int)k;
     if (b < 0) {
       // a chunk is worth a buffer (and eight loads) when at least three of its leaves are read within the next
       // RM_WINDOW ops; stragglers -- a value used again long after its neighbours -- are gathered from memory
@@ -513,17 +505,16 @@ static void rm_plan(const Lowered &p, const OptProgram &prog, uint32_t rm_bufs, 
       if (soon < 3) continue;
       // victim: an empty buffer, else the resident chunk whose next use is farthest (none at all first)
       size_t far = 0;
-      for (uint32_t k = 0; k < n_ubuf; ++k) {
+      for (uint32_t k = 0; k < rm_bufs; ++k) {
         size_t nu;
         if (resident[k] < 0) nu = std::numeric_limits<size_t>::max();
         else { const auto &uu = uses[(size_t)resident[k]]; const size_t cu = cursor[(size_t)resident[k]]; nu = cu < uu.size() ? uu[cu] : std::numeric_limits<size_t>::max() - 1; }
         if (b < 0 || nu > far) { b = (int)k; far = nu; }
       }
-      for (uint32_t k = 0; k < G && G * u + k < n_chunk; ++k)
-        rm_fetch[std::min(free_from[(size_t)b], q)].push_back(RmFetch{G * u + k, G * (uint32_t)b + k});
+      rm_fetch[std::min(free_from[(size_t)b], q)].push_back(RmFetch{u, (uint32_t)b});
       resident[(size_t)b] = u;
     }
-    rm_ld_buf[q] = (int)(G * (uint32_t)b + c % G);
+    rm_ld_buf[q] = b;
     free_from[(size_t)b] = q + 1;
   }
 }
@@ -531,7 +522,7 @@ static void rm_plan(const Lowered &p, const OptProgram &prog, uint32_t rm_bufs, 
 // One wave's section of the cooperative kernel (emit_coop below): no kernel header or descriptor of its own; lane = thread id
 // & 63; private LDS slots behind the shared ones (addressed through their own base register); the wave's panel inside the
 // workgroup's; M_SEND / M_RECV / M_BARRIER.
-struct CoopSec { uint32_t wave, n_shared, priv_base_bytes, panel_wg_bytes, panel_prefix_bytes; bool pooled = false; uint32_t pool_unit = 1;
+struct CoopSec { uint32_t wave, n_shared, priv_base_bytes, panel_wg_bytes, panel_prefix_bytes; bool pooled = false;
                  uint32_t slack = 0, flag_base_bytes = 0, n_wave = 4; };     // slack > 0: progress words instead of s_barrier between the epochs of a tile (fdg_opt.h: CoopProgram::slack)
 // rl: the row-major variant for CONTIGUOUS rows (sample stride == L: compile_Python's [B, L] exactly) of graphs whose tile fits the LDS: a
 // tile's 64 rows are one block of 512 L bytes, streamed linearly into an LDS image by LDS-direct loads (1 KB per instruction, every cache
@@ -555,7 +546,6 @@ static KernelMeta emit_kernel(Emit &E, const Lowered &p, const OptProgram &prog,
     E.off = 0;
     E.klabel = kname;
     E.pad_ok = true;
-    for (int i = 0; i < E.shift; ++i) E.ins("s_nop 0");
   } else {
     os << ".Lsec" << sfx << ":\n";
   }
@@ -567,9 +557,7 @@ static KernelMeta emit_kernel(Emit &E, const Lowered &p, const OptProgram &prog,
   auto vall = [&](uint32_t r) { const int b = V_BASE + RW * r; return "v[" + std::to_string(b) + ":" + std::to_string(b + RW - 1) + "]"; };
   const std::string LD = W == 2 ? "global_load_dwordx4 " : "global_load_dwordx2 ";
   const std::string ST = W == 2 ? "global_store_dwordx4 " : "global_store_dwordx2 ";
-  // cache policy of the leaf stream (experiment knob): FDG_ISA_LEAF_POLICY="nt" / "sc1" / "sc0 sc1" ...
-  const std::string leaf_policy_env = fdg::knob("FDG_ISA_LEAF_POLICY") ? std::string(" ") + fdg::knob("FDG_ISA_LEAF_POLICY") : std::string();
-  const std::string root_policy = fdg::knob("FDG_ISA_ROOT_POLICY") ? std::string(" ") + fdg::knob("FDG_ISA_ROOT_POLICY") : std::string(E.streaming || (cs && cs->pooled) ? " nt" : "");
+  const std::string root_policy = E.streaming || (cs && cs->pooled) ? " nt" : "";
   // Streaming variant: a leaf's last load of the tile and the root stores are non-temporal -- the lines are not needed again, and
   // a read stream with a few stores in it runs 5-10 % faster that way (tools/ubench/tile_ahead.hip: 5.73 -> 6.32 TB/s).  Only for
   // batches whose tiles are whole cache lines (the runtime checks strides and bases): a line shared by two tiles would be
@@ -582,24 +570,22 @@ static KernelMeta emit_kernel(Emit &E, const Lowered &p, const OptProgram &prog,
   // 128 / 48, gv_sigma5 1.24 -> 1.27 / 1.29): last loads only for them.  profiles/r06_log_nt_sweep.txt, r06_log_sweep_c.txt, r06_log_sweep_d.txt.
   std::vector<uint8_t> final_load(prog.ops.size(), 0);
   if (E.streaming) {
-    const long nt_dist = fdg::knob("FDG_ISA_NT_DIST") ? std::atol(fdg::knob("FDG_ISA_NT_DIST")) : E.nt_dist;
     std::vector<long> next_at(p.L + 1, -1);     // ordinal (among the tile's leaf loads, counted from the end) of the leaf's next load
     long ord = 0;
     for (size_t i = prog.ops.size(); i-- > 0;)
       if ((prog.ops[i].kind == M_LD_LEAF || prog.ops[i].kind == M_LD_LEAF_ACC) && prog.ops[i].a < next_at.size()) {
         const uint32_t a = prog.ops[i].a;
-        if (next_at[a] < 0 || (nt_dist >= 0 && ord - next_at[a] > nt_dist)) final_load[i] = 1;
+        if (next_at[a] < 0 || (E.nt_dist >= 0 && ord - next_at[a] > E.nt_dist)) final_load[i] = 1;
         next_at[a] = ord++;
       }
   }
-  std::string leaf_policy = leaf_policy_env;
+  std::string leaf_policy;                     // cache policy of the next leaf load: " nt" for a streaming kernel's final loads
   const std::string DSR = W == 2 ? "ds_read_b128 " : "ds_read_b64 ";
   const std::string DSW = W == 2 ? "ds_write_b128 " : "ds_write_b64 ";
 
   const char *dbg = fdg::knob("FDG_ISA_DEBUG");
   const bool dbg_noleaf = dbg && std::strstr(dbg, "noleaf");
   const bool dbg_nolds = dbg && std::strstr(dbg, "nolds");
-  const bool use_ldexp = fdg::knob("FDG_ISA_NO_LDEXP") == nullptr;
   const bool dbg_novalu = dbg && std::strstr(dbg, "novalu");     // the memory stream of the program alone (waits included)
   const bool dbg_nopanel = dbg && std::strstr(dbg, "nopanel");   // no spill traffic to the HBM panel
   const bool dbg_norecv = dbg && std::strstr(dbg, "norecv");     // pooled / cooperative kernels without their reads of the shared LDS slots
@@ -984,7 +970,7 @@ static KernelMeta emit_kernel(Emit &E, const Lowered &p, const OptProgram &prog,
   std::vector<std::vector<RmFetch>> rm_fetch;       // [op index] fetches issued in front of that op
   std::vector<int> rm_ld_buf;                       // [op index] staging buffer an LD_LEAF reads, -1 = gathered from memory
   if (rm_bufs) rm_plan(p, prog, rm_bufs, rm_fetch, rm_ld_buf);
-  // Cache policy of the LDS-direct loads (experiment knob FDG_ISA_RM_POLICY="nt" ...).  Non-temporal loads stream 6.9 instead of
+  // Cache policy of the row-major chunks' LDS-direct loads: plain.  Non-temporal loads stream 6.9 instead of
   // 6.1 TB/s in a bare loop over rows that are whole cache lines (tools/ubench/rm_stream.hip), but a row of L doubles is not: the
   // 128-byte segments of consecutive chunks share lines, and a line fetched non-temporally is fetched again from memory for the
   // next chunk (measured: parquet_sigma4 6.2 -> 3.6e9 evals/s).  Plain loads it is.
@@ -992,11 +978,6 @@ static KernelMeta emit_kernel(Emit &E, const Lowered &p, const OptProgram &prog,
   // the caches, and a plain LDS-direct load costs the CU far more than a streaming one: gv_ver4_4 3.65 -> 3.06 ms per 524 288 samples, bit for
   // bit the same (profiles/r06_log_pool_sweep.txt; "sc1" / "sc0 sc1" change nothing, "sc0 sc1 nt" = "nt").  The fetches cost the same with one
   // or two waves per SIMD and whichever waves issue them -- a property of the CU's path to memory, not of the issuing wave.
-  // FDG_POOL_FETCH_POLICY="plain" / "sc1" / ... overrides.
-  const std::string panel_policy = fdg::knob("FDG_ISA_PANEL_POLICY") && fdg::knob("FDG_ISA_PANEL_POLICY")[0] ? std::string(" ") + fdg::knob("FDG_ISA_PANEL_POLICY") : std::string();   // (experiment)
-  const char *pool_policy_env = fdg::knob("FDG_POOL_FETCH_POLICY");
-  const std::string pool_policy = !pool_policy_env ? std::string(" nt") : (std::string(pool_policy_env) == "plain" || !pool_policy_env[0] ? std::string() : std::string(" ") + pool_policy_env);
-  const std::string rm_policy = fdg::knob("FDG_ISA_RM_POLICY") && fdg::knob("FDG_ISA_RM_POLICY")[0] ? std::string(" ") + fdg::knob("FDG_ISA_RM_POLICY") : std::string();
   std::vector<uint64_t> rm_ready(rm_bufs, 0);        // vm sequence number of the last load of the chunk in each buffer
   auto rm_emit_fetch = [&](const RmFetch &f) {
     // the buffer's previous readers have been issued; their data must have left the LDS before it is overwritten
@@ -1011,7 +992,7 @@ static KernelMeta emit_kernel(Emit &E, const Lowered &p, const OptProgram &prog,
         E.ins("s_add_u32 " + S(S_FA) + ", " + S(S_FA) + ", " + S(S_ROW8));
         E.ins("s_addc_u32 " + S(S_FA + 1) + ", " + S(S_FA + 1) + ", " + S(S_ROW8 + 1));
       }
-      E.ins("global_load_lds_dwordx4 v" + std::to_string((n & 1) ? rm0 + 9 : rm0) + ", " + S2(S_FA) + rm_policy);
+      E.ins("global_load_lds_dwordx4 v" + std::to_string((n & 1) ? rm0 + 9 : rm0) + ", " + S2(S_FA));
       ++E.vm_issued;
     }
     rm_ready[f.buf] = E.vm_issued;
@@ -1022,8 +1003,7 @@ static KernelMeta emit_kernel(Emit &E, const Lowered &p, const OptProgram &prog,
   // One s_waitcnt can serve several consumers: when an op has to wait for a load, the wait also covers what
   // the next few ops need of the loads issued so far (they complete in order and were issued long before,
   // so this costs nothing and saves issue slots).
-  const char *wl_env = fdg::knob("FDG_ISA_WAIT_LOOKAHEAD");
-  const size_t wait_look = wl_env ? (size_t)std::max(0, std::atoi(wl_env)) : 6;
+  const size_t wait_look = 6;
   auto vm_seq_needed = [&](const MOp &q) -> uint64_t {
     uint64_t sq = 0;
     auto use = [&](uint32_t r) { if (r < E.pend.size() && E.pend[r].first == 1) sq = std::max(sq, E.pend[r].second); };
@@ -1067,7 +1047,7 @@ static KernelMeta emit_kernel(Emit &E, const Lowered &p, const OptProgram &prog,
       case M_LD_LEAF:
         if (dbg_noleaf) break;   // timing experiments only (results are garbage)
         if (o.kind == M_LD_LEAF) E.wait_reg(o.d);
-        if (E.streaming && leaf_policy_env.empty()) leaf_policy = final_load[this_op] ? " nt" : "";
+        if (E.streaming) leaf_policy = final_load[this_op] ? " nt" : "";
         if (rl) {              // lane = row: image[row * 8 L + 8 leaf]
           E.wait_vm(rl_ready);
           E.ins("ds_read_b64 " + vall(o.d) + ", v" + std::to_string(rm0) + " offset:" + std::to_string(stage_base + o.a * 8u));
@@ -1140,7 +1120,7 @@ static KernelMeta emit_kernel(Emit &E, const Lowered &p, const OptProgram &prog,
         if (dbg_nopanel) break;
         E.wait_reg(o.d);
         const std::string opnd = panel_operand(o.a);
-        E.ins(LD + vall(o.d) + ", " + V(V_LANE8) + ", " + opnd + panel_policy);
+        E.ins(LD + vall(o.d) + ", " + V(V_LANE8) + ", " + opnd);
         E.pend[o.d] = {1, ++E.vm_issued};
         break;
       }
@@ -1148,7 +1128,7 @@ static KernelMeta emit_kernel(Emit &E, const Lowered &p, const OptProgram &prog,
         if (dbg_nopanel) break;
         E.wait_reg(o.a);
         const std::string opnd = panel_operand(o.d);
-        E.ins(ST + V(V_LANE8) + ", " + vall(o.a) + ", " + opnd + panel_policy);
+        E.ins(ST + V(V_LANE8) + ", " + vall(o.a) + ", " + opnd);
         ++E.vm_issued;
         break;
       }
@@ -1166,7 +1146,7 @@ static KernelMeta emit_kernel(Emit &E, const Lowered &p, const OptProgram &prog,
         break;
       case M_POOL_FETCH: {   // shared[d .. d + b - 1] = leaf[a .. a + b - 1]: 16 bytes per lane straight into the LDS slot(s), no register in between
         if (dbg_nofetch) break;
-        const bool pair = o.b == 2;          // 64 lanes: two leaves adjacent in the tile (leaf stride 64, checked at launch) into two adjacent slots
+        const bool pair = o.b == 2;          // 64 lanes: leaves a and c into two adjacent slots (FDG_POOL_PAIR)
         if (!pair && !pool_exec_low) { E.ins("s_mov_b64 exec, 0xffffffff"); pool_exec_low = true; }
         if (pair && pool_exec_low) { E.ins("s_mov_b64 exec, -1"); pool_exec_low = false; }
         // The tile's leaves lie within 2 GB of its first (checked at launch), so a leaf's place is a 32-bit offset from the tile's base: it goes
@@ -1176,7 +1156,7 @@ static KernelMeta emit_kernel(Emit &E, const Lowered &p, const OptProgram &prog,
         E.ins("s_mov_b32 m0, " + hex32(o.d * SLOT));
         std::string saddr = S2(S_LT);
         uint32_t off_reg = rm0 + 2;
-        if (pair && o.negc) {     // the upper half of the wave brings leaf c > a (any leaf): its lanes' offsets are (c - a) leaf strides further
+        if (pair) {               // the upper half of the wave brings leaf c > a (any leaf): its lanes' offsets are (c - a) leaf strides further
           if (o.a != 0) {
             E.ins("s_mul_i32 " + S(S_X) + ", " + S(S_LS8) + ", " + hex32(o.a));
             E.ins("s_add_u32 " + S(S_FA) + ", " + S(S_LT) + ", " + S(S_X));
@@ -1188,27 +1168,17 @@ static KernelMeta emit_kernel(Emit &E, const Lowered &p, const OptProgram &prog,
           E.ins("v_add_u32_e32 v" + std::to_string(rm0 + 3) + ", " + S(S_X) + ", v" + std::to_string(rm0 + 2));
           E.ins("v_cndmask_b32_e64 v" + std::to_string(rm0 + 3) + ", v" + std::to_string(rm0 + 2) + ", v" + std::to_string(rm0 + 3) + ", " + S2(S_DELTA + 4));
           off_reg = rm0 + 3;
-        } else if (o.a != 0 && !(fdg::knob("FDG_POOL_VADDR") && fdg::knob("FDG_POOL_VADDR")[0] == '1')) {
-          // (scalar address arithmetic: measured 1.5 % faster than one vector add into the offset register -- FDG_POOL_VADDR=1 -- although that is
-          //  two instructions fewer: the scalar unit's instructions cost a lone wave less than a vector one, profiles/r06_log_sweep_c.txt)
-          if (cs->pool_unit == 2) E.ins("s_add_u32 " + S(S_FA) + ", " + S(S_LT) + ", " + hex32(o.a * 512u));
-          else {
-            E.ins("s_mul_i32 " + S(S_X) + ", " + S(S_LS8) + ", " + hex32(o.a));
-            E.ins("s_add_u32 " + S(S_FA) + ", " + S(S_LT) + ", " + S(S_X));
-          }
+        } else if (o.a != 0) {
+          // (scalar address arithmetic: measured 1.5 % faster than one vector add into the offset register, although that is two
+          //  instructions fewer: the scalar unit's instructions cost a lone wave less than a vector one, profiles/r06_log_sweep_c.txt)
+          E.ins("s_mul_i32 " + S(S_X) + ", " + S(S_LS8) + ", " + hex32(o.a));
+          E.ins("s_add_u32 " + S(S_FA) + ", " + S(S_LT) + ", " + S(S_X));
           E.ins("s_addc_u32 " + S(S_FA + 1) + ", " + S(S_LT + 1) + ", 0");
           saddr = S2(S_FA);
-        } else if (o.a != 0) {
-          if (cs->pool_unit == 2) E.ins("v_add_u32_e32 v" + std::to_string(rm0 + 3) + ", " + hex32(o.a * 512u) + ", v" + std::to_string(rm0 + 2));
-          else {
-            E.ins("s_mul_i32 " + S(S_X) + ", " + S(S_LS8) + ", " + hex32(o.a));
-            E.ins("v_add_u32_e32 v" + std::to_string(rm0 + 3) + ", " + S(S_X) + ", v" + std::to_string(rm0 + 2));
-          }
-          off_reg = rm0 + 3;
         } else {
           E.ins("s_nop 0");       // (leaf 0: nothing to compute between the write of M0 and the load)
         }
-        E.ins("global_load_lds_dwordx4 v" + std::to_string(off_reg) + ", " + saddr + pool_policy);
+        E.ins("global_load_lds_dwordx4 v" + std::to_string(off_reg) + ", " + saddr + " nt");
         pool_pending.push_back({++E.vm_issued, (uint32_t)o.imm});
         const bool more = this_op + 1 < prog.ops.size() && prog.ops[this_op + 1].kind == M_POOL_FETCH;
         if (!more && pool_exec_low) { E.ins("s_mov_b64 exec, -1"); pool_exec_low = false; }
@@ -1292,10 +1262,10 @@ static KernelMeta emit_kernel(Emit &E, const Lowered &p, const OptProgram &prog,
         // A factor +-2^k (spin and symmetry factors mostly are: -2, 4, 0.5, ... -- 13 % of the executed ops of the GV 5-loop
         // self-energy): x * 2^k is v_ldexp_f64(x, k) bit for bit -- both are the exactly scaled value rounded once, denormal
         // results and overflow included -- and the sign rides on the source modifier.  The exponent adder instead of the
-        // multiplier array: the graphs that run against the power budget clock higher.  FDG_ISA_NO_LDEXP=1: v_mul_f64.
+        // multiplier array: the graphs that run against the power budget clock higher.
         int k2 = 0;
         const double m = std::frexp(std::fabs(o.imm), &k2);      // |imm| = m * 2^k2, m in [0.5, 1)
-        if (use_ldexp && !o.param && std::isfinite(o.imm) && o.imm != 0.0 && m == 0.5 && k2 - 1 >= -16 && k2 - 1 <= 64) {
+        if (!o.param && std::isfinite(o.imm) && o.imm != 0.0 && m == 0.5 && k2 - 1 >= -16 && k2 - 1 <= 64) {
           const bool neg = (o.nega != 0) != std::signbit(o.imm);
           E.ins("v_ldexp_f64 " + vlo(o.d) + ", " + (neg ? "-" : "") + vlo(o.a) + ", " + std::to_string(k2 - 1));
           if (W == 2) E.ins("v_ldexp_f64 " + vhi(o.d) + ", " + (neg ? "-" : "") + vhi(o.a) + ", " + std::to_string(k2 - 1));
@@ -1635,7 +1605,7 @@ static KernelMeta emit_coop(Emit &E, const Lowered &p, const CoopProgram &cp, co
   uint32_t accum = 0, n_agpr = 0;
   int n_sgpr = 0;
   for (uint32_t w = 0; w < cp.n_wave; ++w) {
-    const CoopSec cs{w, cp.n_shared, (cp.n_shared + w * cp.n_priv_lds) * 512u, panel_wg, prefix[w], cp.pooled, cp.pool_unit,
+    const CoopSec cs{w, cp.n_shared, (cp.n_shared + w * cp.n_priv_lds) * 512u, panel_wg, prefix[w], cp.pooled,
                      cp.pooled ? cp.slack : 0u, (cp.n_shared + cp.n_wave * cp.n_priv_lds) * 512u, cp.n_wave};
     E.hz.reset();
     const KernelMeta m = emit_kernel(E, p, cp.wave[w], kname + "_w" + std::to_string(w), 1, false, 0, &cs);
@@ -1716,7 +1686,6 @@ std::string emit_isa(const Lowered &p, const IsaPrograms &V, std::vector<IsaKern
   const uint32_t rm_bufs = V.rm_bufs;
   Emit E;
   { const char *a = fdg::knob("FDG_ISA_ALIGN"); E.align = a && a[0] >= '0' && a[0] <= '2' ? a[0] - '0' : 1; }
-  { const char *a = fdg::knob("FDG_ISA_SHIFT"); E.shift = a ? std::atoi(a) : 0; }
   E.check_off = fdg::knob("FDG_ISA_CHECK_OFF") != nullptr;
   E.os << "\t.amdgcn_target \"amdgcn-amd-amdhsa--gfx950\"\n\t.amdhsa_code_object_version 6\n";
   std::vector<KernelMeta> ks;
@@ -1751,7 +1720,7 @@ std::string emit_isa(const Lowered &p, const IsaPrograms &V, std::vector<IsaKern
   if (coop) { ks.push_back(emit_coop(E, p, *coop, kname + "_coop")); ks.back().wg = 64 * coop->n_wave; }
   if (pool) { ks.push_back(emit_coop(E, p, *pool, kname + "_pool")); ks.back().wg = 64 * pool->n_wave; }
   // The root-writing one-wave kernels once more with claimed tiles (see `claim` in emit_kernel), for the graphs a launch plan can find bound by
-  // memory (fdg_runtime.hip: IsaRun::shape; four times its default ratio leaves FDG_ISA_MEM_RATIO room).  Behind every other kernel: the text
+  // memory (fdg_runtime.hip: IsaRun::shape; four times its ratio, to be on the safe side).  Behind every other kernel: the text
   // in front of them is what it is without them.
   if (isa_has_claimed(p, prog)) {
     ks.push_back(emit_kernel(E, p, prog, kname + "_cl", 1, false, 0, nullptr, false, true));

@@ -65,14 +65,13 @@ struct Builder {
   std::unordered_map<uint64_t, std::vector<std::pair<double, uint32_t>>> vn_mulc;
   bool value_numbering = true;
   uint64_t vn_window = 0;        // reuse only results computed at most this many ops ago (0 = no limit)
-  std::vector<uint32_t> born;    // vid -> index of the op that produced it or (vn_touch) last read it
-  bool vn_touch = true;          // a value stays reusable while it keeps being read (it is live anyway)
+  std::vector<uint32_t> born;    // vid -> index of the op that produced it or last read it: a value stays reusable while it keeps being read (it is live anyway)
   bool fresh_enough(uint32_t ref) const {
     if (!vn_window) return true;
     const uint32_t v = ref >> 1;
     return v < born.size() && (uint64_t)u.size() - born[v] <= vn_window;
   }
-  void touch(uint32_t ref) { if (vn_touch) { const uint32_t v = ref >> 1; if (v < born.size()) born[v] = (uint32_t)u.size(); } }
+  void touch(uint32_t ref) { const uint32_t v = ref >> 1; if (v < born.size()) born[v] = (uint32_t)u.size(); }
   uint32_t fresh() { born.resize(next_vid + 1, 0); born[next_vid] = (uint32_t)u.size(); return next_vid++; }
   // Rematerialisation: the value of a cheap node (own fold of at most remat_cost steps) that has not been read for
   // remat_window ops is forgotten; its next consumer computes it again (the same IEEE operations on the same operands:
@@ -80,9 +79,7 @@ struct Builder {
   // come back through the HBM panel for every use; its operands -- lower-order sub-diagrams that many nodes keep reading --
   // usually are still on chip.  Roots are exempt.
   bool keep_root_order = false;
-  const std::vector<uint32_t> *root_rank = nullptr;  // pool programs (experiment FDG_POOL_SEED): [N] position of a root node in this wave's order of evaluation
   const std::vector<uint8_t> *root_mask = nullptr;   // pool programs: [R] the roots this wave computes and stores (others are not its business)
-  uint32_t term_window = 1, term_recent = 400;    // out-of-order evaluation of a wide node's terms (see build_uops)
   uint64_t remat_window = 0;
   uint32_t remat_cost = 8;
   std::vector<uint8_t> remat_ok;   // [N]
@@ -380,12 +377,10 @@ struct Frame { uint32_t n, i, acc; };
 // needs the most nodes, then always continue with the root whose cone is already computed to the
 // largest extent -- graphs that share most of their sub-expressions (Taylor coefficients of one
 // diagram, instant/dynamic parts, the rows of a vertex function) are finished while the shared values are still on chip.
-// (Bit sets: 180 roots x 45 000 nodes -- the 4-loop vertex function of example/benchmark.jl -- take 0.1 s.  With
-// FDG_ROOT_RECENT=w the overlap counts only the cones of the last w roots: what is likely to be on chip still.)
+// (Bit sets: 180 roots x 45 000 nodes -- the 4-loop vertex function of example/benchmark.jl -- take 0.1 s.)
 static void order_roots(const Lowered &p, std::vector<uint32_t> &tops) {
   const uint32_t L = p.L;
-  const size_t max_roots = fdg::knob("FDG_ROOT_ORDER_MAX") ? (size_t)std::atoi(fdg::knob("FDG_ROOT_ORDER_MAX")) : 1024;
-  if (tops.size() > 1 && tops.size() <= max_roots) {
+  if (tops.size() > 1 && tops.size() <= 1024) {
     const size_t R = tops.size(), W = (p.N + 63) / 64;
     std::vector<std::vector<uint64_t>> cone(R, std::vector<uint64_t>(W, 0));
     std::vector<uint64_t> csize(R, 0);
@@ -402,17 +397,10 @@ static void order_roots(const Lowered &p, std::vector<uint32_t> &tops) {
         }
       }
     }
-    const size_t recent = fdg::knob("FDG_ROOT_RECENT") ? (size_t)std::atoi(fdg::knob("FDG_ROOT_RECENT")) : 0;
     std::vector<uint64_t> done(W, 0);
     std::vector<uint8_t> used(R, 0);
     std::vector<uint32_t> ordered;
-    std::vector<size_t> order_idx;
     for (size_t k = 0; k < R; ++k) {
-      if (recent && k) {                       // only what the last `recent` roots touched
-        std::fill(done.begin(), done.end(), 0);
-        for (size_t q = order_idx.size() > recent ? order_idx.size() - recent : 0; q < order_idx.size(); ++q)
-          for (size_t w = 0; w < W; ++w) done[w] |= cone[order_idx[q]][w];
-      }
       size_t best = R; double best_score = -1.0;
       for (size_t r = 0; r < R; ++r) {
         if (used[r]) continue;
@@ -423,8 +411,7 @@ static void order_roots(const Lowered &p, std::vector<uint32_t> &tops) {
       }
       used[best] = 1;
       ordered.push_back(tops[best]);
-      order_idx.push_back(best);
-      if (!recent) for (size_t w = 0; w < W; ++w) done[w] |= cone[best][w];
+      for (size_t w = 0; w < W; ++w) done[w] |= cone[best][w];
     }
     tops.swap(ordered);
 }
@@ -451,8 +438,7 @@ void build_uops(Builder &B) {
   std::vector<uint32_t> tops;
   for (auto &rk : rootlist) if (rk.first >= L) tops.push_back(rk.first - L);
   tops.erase(std::unique(tops.begin(), tops.end()), tops.end());
-  if (B.root_rank) std::stable_sort(tops.begin(), tops.end(), [&](uint32_t x, uint32_t y) { return (*B.root_rank)[x] < (*B.root_rank)[y]; });
-  else if (!B.keep_root_order) order_roots(p, tops);
+  if (!B.keep_root_order) order_roots(p, tops);
   // One fold step of frame f (operand already computed).  Returns true when the node is finished.
   auto step = [&](Frame &f) -> bool {
     const uint32_t n = f.n, a = p.off[n], k = p.off[n + 1] - a;
@@ -492,35 +478,7 @@ void build_uops(Builder &B) {
       B.need(c);
       if (!B.available(c)) {
         if (B.ref_of[c] != NONE) B.n_remat++;
-        // Terms of a wide Sum / Prod may be COMPUTED out of order (their values wait for their turn in the left fold, which
-        // stays in order): among the next `term_window` terms the one that shares most operands with what was touched
-        // recently goes first, so that diagrams built from the same propagators are evaluated while those are on chip.
-        uint32_t pick = c;
-        const uint32_t k = p.off[f.n + 1] - p.off[f.n];
-        if (B.term_window > 1 && k >= 16 && B.ref_of[c] == NONE) {
-          double best = -1.0;
-          for (uint32_t j = f.i; j < k && j < f.i + B.term_window; ++j) {
-            const uint32_t cj = p.idx[p.off[f.n] + j];
-            if (cj < L || B.ref_of[cj] != NONE) continue;
-            uint32_t tot = 0, rec = 0;
-            auto look = [&](uint32_t v) {
-              tot++;
-              const uint32_t r = B.ref_of[v];
-              if (r == NONE) return;
-              const uint32_t vid = r >> 1;
-              if (vid < B.born.size() && B.born[vid] > 0 && (uint64_t)B.u.size() - B.born[vid] < B.term_recent) rec++;
-            };
-            const uint32_t nj = cj - L;
-            for (uint32_t e = p.off[nj]; e < p.off[nj + 1]; ++e) {
-              const uint32_t v = p.idx[e];
-              look(v);
-              if (v >= L && B.ref_of[v] == NONE) for (uint32_t e2 = p.off[v - L]; e2 < p.off[v - L + 1]; ++e2) look(p.idx[e2]);
-            }
-            const double score = tot ? (double)rec / tot : 0.0;
-            if (score > best + 1e-12) { best = score; pick = cj; }
-          }
-        }
-        st.push_back(Frame{pick - L, 0, NONE});
+        st.push_back(Frame{c - L, 0, NONE});
         continue;
       }
       if (step(st.back())) st.pop_back();
@@ -633,8 +591,7 @@ void fuse_fma(std::vector<UOp> &u, uint32_t n_value) {
       const uint8_t k = u[prod[v]].kind;
       // only a product computed just before: fusing moves the multiplication to the sum's position, and the
       // factors of an older product would have to stay in registers until then
-      const uint32_t reach = fdg::knob("FDG_FMA_REACH") ? (uint32_t)std::atoi(fdg::knob("FDG_FMA_REACH")) : 6u;
-      if (j - prod[v] > reach) return -1;
+      if (j - prod[v] > 6u) return -1;
       return (k == M_MUL || k == M_MULC) ? (int64_t)prod[v] : -1;
     };
     const int64_t pa = fusable(o.a), pb = (o.b >> 1) != (o.a >> 1) ? fusable(o.b) : -1;
@@ -679,9 +636,6 @@ struct Alloc {
   std::vector<uint32_t> free_land;
   uint32_t n_land = 0, n_acc_spill = 0;
   const int evict_cost = fdg::knob("FDG_EVICT_COST") ? std::atoi(fdg::knob("FDG_EVICT_COST")) : 2;    // read per program (see take_reg)
-  // pooled programs: a leaf comes back from the shared pool by an LDS read, so it is the cheapest thing to evict and is not parked anywhere
-  const double pool_leaf_cost = fdg::knob("FDG_POOL_LEAF_COST") ? std::atof(fdg::knob("FDG_POOL_LEAF_COST")) : 0.4;
-  const bool pool_nopark = fdg::knob("FDG_POOL_NOPARK") != nullptr;
   std::vector<MOp> out;
   OptProgram &prog;
 
@@ -755,7 +709,8 @@ struct Alloc {
         double score;
         if (nu == std::numeric_limits<uint32_t>::max()) score = 1e30;
         else {
-          const double c = home_kind[v] == 0 ? (double)evict_cost : (home_kind[v] == 1 || home_kind[v] == 4 ? 0.5 : (home_kind[v] == 3 && prm.pool_leaves ? pool_leaf_cost : 1.0));
+          // (pooled programs: a leaf comes back from the shared pool by an LDS read, so it is the cheapest thing to evict)
+          const double c = home_kind[v] == 0 ? (double)evict_cost : (home_kind[v] == 1 || home_kind[v] == 4 ? 0.5 : (home_kind[v] == 3 && prm.pool_leaves ? 0.4 : 1.0));
           score = (double)(nu - pos) / c;
         }
         if (score > best_score) { best_score = score; best = r; best_nu = nu; }
@@ -788,7 +743,7 @@ struct Alloc {
       // a leaf: re-loadable from its source; park it in LDS when there is room so
       // the next use does not go back to HBM
       uint32_t s;
-      if (next_use(v) != std::numeric_limits<uint32_t>::max() && !(prm.pool_leaves && pool_nopark)) {
+      if (next_use(v) != std::numeric_limits<uint32_t>::max()) {
         if (get_lds(s)) { out.push_back(MOp{M_ST_LDS, 0, 0, s, best, 0, 0.0}); home_kind[v] = 1; home_slot[v] = s; prog.n_st_lds++; }
         else if (get_acc(s)) { out.push_back(MOp{M_ST_ACC, 0, 0, s, best, 0, 0.0}); home_kind[v] = 4; home_slot[v] = s; prog.n_st_acc++; }
       }
@@ -1067,19 +1022,16 @@ void build_opt_program(const Lowered &p, const OptParams &prm, OptProgram &out) 
   Builder B0(p);
   B0.value_numbering = prm.vn_window != 1;     // 1 = off, 0 = unlimited, else window in ops
   B0.vn_window = prm.vn_window > 1 ? prm.vn_window : 0;
-  B0.vn_touch = fdg::knob("FDG_VN_BIRTH_WINDOW") == nullptr;   // default: the window counts from the last read
   B0.remat_window = prm.remat_window;
   B0.remat_cost = prm.remat_cost;
   B0.keep_root_order = prm.keep_root_order || fdg::knob("FDG_KEEP_ROOT_ORDER") != nullptr;     // (the environment switch is for experiments)
   if (const char *rw = fdg::knob("FDG_REMAT_WINDOW")) B0.remat_window = (uint64_t)std::atoll(rw);     // experiments
-  if (const char *tw = fdg::knob("FDG_TERM_WINDOW")) B0.term_window = (uint32_t)std::max(1, std::atoi(tw));
-  if (const char *tr = fdg::knob("FDG_TERM_RECENT")) B0.term_recent = (uint32_t)std::max(1, std::atoi(tr));
   build_uops(B0);
   Lowered plain;
   const bool retry = !B0.ok && B0.why == "inconsistent schedule groups";
   if (retry) { plain = p; plain.sched_group.clear(); }
   Builder B1(retry ? plain : p);
-  B1.value_numbering = B0.value_numbering; B1.vn_window = B0.vn_window; B1.vn_touch = B0.vn_touch;
+  B1.value_numbering = B0.value_numbering; B1.vn_window = B0.vn_window;
   B1.remat_window = B0.remat_window; B1.remat_cost = B0.remat_cost; B1.keep_root_order = B0.keep_root_order;
   if (retry) build_uops(B1);
   Builder &B = retry ? B1 : B0;
@@ -1133,7 +1085,6 @@ bool build_schedule(const Lowered &p, const OptParams &prm, std::vector<SchedOp>
   Builder B0(p);
   B0.value_numbering = prm.vn_window != 1;
   B0.vn_window = prm.vn_window > 1 ? prm.vn_window : 0;
-  B0.vn_touch = fdg::knob("FDG_VN_BIRTH_WINDOW") == nullptr;
   B0.keep_minus_one = prm.keep_minus_one;
   B0.mul_keeps_signs = prm.mul_keeps_signs;
   build_uops(B0);
@@ -1141,7 +1092,7 @@ bool build_schedule(const Lowered &p, const OptParams &prm, std::vector<SchedOp>
   const bool retry = !B0.ok && B0.why == "inconsistent schedule groups";
   if (retry) { plain = p; plain.sched_group.clear(); }
   Builder B1(retry ? plain : p);
-  B1.value_numbering = B0.value_numbering; B1.vn_window = B0.vn_window; B1.vn_touch = B0.vn_touch; B1.keep_minus_one = B0.keep_minus_one; B1.mul_keeps_signs = B0.mul_keeps_signs;
+  B1.value_numbering = B0.value_numbering; B1.vn_window = B0.vn_window; B1.keep_minus_one = B0.keep_minus_one; B1.mul_keeps_signs = B0.mul_keeps_signs;
   if (retry) build_uops(B1);
   Builder &B = retry ? B1 : B0;
   why = B.why;
@@ -1189,7 +1140,7 @@ struct CoopBuild {
   std::vector<std::pair<uint32_t, uint32_t>> rootlist;
   uint32_t cur_epoch = 0;
   uint64_t n_dup = 0;
-  uint32_t copy_window = 600;         // a received value not read for this many ops of its wave is received again when needed
+  static constexpr uint32_t copy_window = 600;   // a received value not read for this many ops of its wave is received again when needed
   bool ok = true;
   std::string why;
 
@@ -1321,8 +1272,6 @@ static void build_coop_once(const Lowered &p, const OptParams &prm, size_t budge
 
 // Shorter epochs keep fewer hand-overs in flight: when the shared slots run out the schedule is rebuilt with a smaller budget.
 void build_coop_program(const Lowered &p, const OptParams &prm, CoopProgram &out, uint32_t n_wave) {
-  const char *te = fdg::knob("FDG_COOP_EPOCH_OPS");
-  if (te) { const char *ge = fdg::knob("FDG_COOP_GAP"); build_coop_once(p, prm, (size_t)std::max(8, std::atoi(te)), ge ? (uint32_t)std::atoi(ge) : 2u, out, n_wave); return; }
   for (size_t budget : {192, 128, 96, 64, 48}) {
     build_coop_once(p, prm, budget, budget > 64 ? 2u : 1u, out, n_wave);
     if (out.supported || out.why != "shared LDS slots exhausted") return;
@@ -1334,7 +1283,6 @@ static void build_coop_once(const Lowered &p, const OptParams &prm, size_t budge
   out.n_wave = NW;
   const uint32_t L = p.L;
   CoopBuild C(p);
-  if (const char *e = fdg::knob("FDG_COOP_COPY_WINDOW")) C.copy_window = (uint32_t)std::max(1, std::atoi(e));
   for (uint32_t k = 0; k < p.R; ++k) if (p.root_slot[k] != FDG_NO_ROOT) C.rootlist.push_back({p.root_slot[k], k});
   std::sort(C.rootlist.begin(), C.rootlist.end());
   for (uint32_t w = 0; w < NW; ++w) {
@@ -1357,8 +1305,7 @@ static void build_coop_once(const Lowered &p, const OptParams &prm, size_t budge
   // on chip (order_roots); with a few roots the terms of each are dealt, a home wave folding them as they arrive.
   size_t n_wide = 0;
   for (uint32_t rn : root_nodes) n_wide += (p.off[rn + 1] - p.off[rn] >= 8 && p.op[rn] != FDG_OP_POWER);
-  const char *rte = fdg::knob("FDG_COOP_ROOT_TASKS");
-  const bool root_tasks = rte ? rte[0] == '1' : root_nodes.size() > 4 * (size_t)NW;
+  const bool root_tasks = root_nodes.size() > 4 * (size_t)NW;
   if (root_tasks) order_roots(p, root_nodes);
   std::vector<std::vector<uint32_t>> term_lists;
   for (uint32_t rn : root_nodes) {
@@ -1427,7 +1374,6 @@ static void build_coop_once(const Lowered &p, const OptParams &prm, size_t budge
   }
   // ---- publication intervals and shared slots ---------------------------------------------------------------------------
   out.n_priv_lds = NW == 4 ? 16 : (NW == 8 ? 8 : 4);
-  if (const char *e = fdg::knob("FDG_COOP_PRIV_LDS")) out.n_priv_lds = (uint32_t)std::max(1, std::min(70, std::atoi(e)));
   out.n_shared = std::min<uint32_t>(256, 312 - NW * out.n_priv_lds);   // (the emitter addresses shared slots as two banks of 128)
   struct Interval { uint32_t node, start, end, slot; };
   std::vector<Interval> ivs;
@@ -1470,17 +1416,6 @@ static void build_coop_once(const Lowered &p, const OptParams &prm, size_t budge
       free_at[best] = ivs[i].end + 1;
     }
   }
-  if (fdg::knob("FDG_COOP_DEBUG")) {
-    std::vector<uint32_t> occ(C.cur_epoch + 2, 0);
-    for (const Interval &iv : ivs) for (uint32_t e = iv.start; e <= iv.end && e < occ.size(); ++e) occ[e]++;
-    uint64_t sum = 0; uint32_t mx = 0;
-    for (uint32_t e = 0; e < C.cur_epoch; ++e) { sum += occ[e]; mx = std::max(mx, occ[e]); }
-    std::fprintf(stderr, "[coop] epochs %u intervals %zu copies %zu slot occupancy avg %.1f max %u of %u\n", C.cur_epoch, ivs.size(), C.copies.size(),
-                 (double)sum / std::max(1u, C.cur_epoch), mx, out.n_shared);
-    std::vector<uint32_t> len_hist(8, 0);
-    for (const Interval &iv : ivs) len_hist[std::min<uint32_t>(7, (iv.end - iv.start) / 4)]++;
-    for (uint32_t k = 0; k < 8; ++k) std::fprintf(stderr, "  interval length %u..%u epochs: %u\n", 4 * k, 4 * k + 3, len_hist[k]);
-  }
   out.n_transfer = C.copies.size();
   // ---- the waves' lists with their M_SEND ops, then the ordinary allocator ----------------------------------------------
   std::vector<std::vector<std::vector<UOp>>> sends(NW, std::vector<std::vector<UOp>>(C.cur_epoch));
@@ -1515,20 +1450,14 @@ static void build_coop_once(const Lowered &p, const OptParams &prm, size_t budge
 // =====================================================================================================================
 // Pooled cooperative variant (fdg_opt.h: build_pool_program).
 // =====================================================================================================================
-void build_pool_program(const Lowered &p, const OptParams &prm, CoopProgram &out, uint32_t NW, uint32_t epoch_ops, uint32_t ahead) {
-  const uint32_t unit_in = out.pool_unit;
+void build_pool_program(const Lowered &p, const OptParams &prm, CoopProgram &out, uint32_t NW, uint32_t epoch_ops) {
   out = CoopProgram();
   out.n_wave = NW;
   out.pooled = true;
-  out.pool_unit = unit_in == 2 ? 2 : 1;
-  if (const char *e = fdg::knob("FDG_POOL_UNIT")) out.pool_unit = std::atoi(e) == 2 ? 2 : 1;
   const uint32_t L = p.L;
   if (NW < 2 || NW > CoopProgram::MAXW) { out.why = "bad wave count"; return; }
   if (p.sched_group.size() == p.N && p.N) { out.why = "schedule groups are not part of the pooled variant"; return; }
-  if (const char *e = fdg::knob("FDG_POOL_EPOCH_OPS")) epoch_ops = (uint32_t)std::max(16, std::atoi(e));
-  if (const char *e = fdg::knob("FDG_POOL_AHEAD")) ahead = (uint32_t)std::max(1, std::atoi(e));
-  if (!epoch_ops) epoch_ops = 128;
-  if (!ahead) ahead = 8;
+  const uint32_t ahead = 8;       // epochs a fetch is issued before its first read, when a slot is free by then
   // synchronisation between the epochs of a tile: s_barrier (slack 0), or progress words with `slack` epochs of freedom (fdg_opt.h: CoopProgram::slack)
   uint32_t S = 0;
   if (const char *e = fdg::knob("FDG_POOL_SYNC")) if (std::string(e) == "flags") S = 2;
@@ -1567,35 +1496,14 @@ void build_pool_program(const Lowered &p, const OptParams &prm, CoopProgram &out
     }
   }
   // Largest cone first, each to the wave where load + affinity * (fold steps it adds there) is smallest: roots that share sub-expressions
-  // gather on one wave (what two waves both need is computed twice), and the waves finish together.  (FDG_POOL_DEAL=overlap deals in
-  // order_roots' order instead -- neighbours of that order on different waves at the same time: measured on the 4-loop GV vertex function
-  // that doubles the duplicated fold steps, 16 617 -> 67 062, and the pool traffic.)
+  // gather on one wave (what two waves both need is computed twice), and the waves finish together.
   std::vector<size_t> deal(root_nodes.size());
   for (size_t i = 0; i < deal.size(); ++i) deal[i] = i;
-  if (!(fdg::knob("FDG_POOL_DEAL") && std::string(fdg::knob("FDG_POOL_DEAL")) == "overlap")) {
-    std::sort(deal.begin(), deal.end(), [&](size_t a, size_t b) { return csize[a] > csize[b] || (csize[a] == csize[b] && a < b); });
-  } else {
-    std::vector<uint32_t> ordered = root_nodes;
-    order_roots(p, ordered);
-    std::vector<size_t> pos(p.N, 0);
-    for (size_t i = 0; i < root_nodes.size(); ++i) pos[root_nodes[i]] = i;
-    for (size_t i = 0; i < ordered.size(); ++i) deal[i] = pos[ordered[i]];
-  }
-  // (experiment FDG_POOL_SEED=n > 0: the dealing order and every wave's root order shuffled -- how much do the pool's fetches depend on which roots
-  //  run next to which?)
-  uint64_t pool_seed = fdg::knob("FDG_POOL_SEED") ? (uint64_t)std::atoll(fdg::knob("FDG_POOL_SEED")) : 0;
-  auto rnd = [&]() { pool_seed ^= pool_seed << 13; pool_seed ^= pool_seed >> 7; pool_seed ^= pool_seed << 17; return pool_seed; };
-  std::vector<uint32_t> root_rank;
-  if (pool_seed) {
-    pool_seed = pool_seed * 0x9E3779B97F4A7C15ull + 1;
-    for (size_t i = deal.size(); i > 1; --i) std::swap(deal[i - 1], deal[rnd() % i]);
-    root_rank.assign(p.N, 0);
-    for (size_t i = 0; i < root_nodes.size(); ++i) root_rank[root_nodes[i]] = (uint32_t)(rnd() & 0xffffff);
-  }
+  std::sort(deal.begin(), deal.end(), [&](size_t a, size_t b) { return csize[a] > csize[b] || (csize[a] == csize[b] && a < b); });
   std::vector<std::vector<uint64_t>> have(NW, std::vector<uint64_t>(W64, 0));
   std::vector<uint64_t> load(NW, 0);
   std::vector<uint32_t> wave_of_node(p.N, NONE);
-  const double affinity = fdg::knob("FDG_POOL_AFFINITY") ? std::atof(fdg::knob("FDG_POOL_AFFINITY")) : 2.0;
+  const double affinity = 2.0;
   for (size_t r : deal) {
     uint32_t best = 0; uint64_t best_load = ~0ull;
     std::vector<uint64_t> add(NW, 0);
@@ -1626,15 +1534,12 @@ void build_pool_program(const Lowered &p, const OptParams &prm, CoopProgram &out
     B[w]->value_numbering = prm.vn_window != 1;
     B[w]->vn_window = prm.vn_window > 1 ? prm.vn_window : 0;
     B[w]->root_mask = &mask[w];
-    if (!root_rank.empty()) B[w]->root_rank = &root_rank;
     build_uops(*B[w]);                 // (order_roots inside orders the wave's own roots by what they share)
     if (!B[w]->ok) { out.why = B[w]->why; return; }
   }
   // ---- registers per wave: leaves are re-loadable (from the pool: a short LDS read) ---------------------------------------------------------
   out.n_priv_lds = NW <= 4 ? 16 : (NW == 8 ? 8 : 4);
-  if (const char *e = fdg::knob("FDG_COOP_PRIV_LDS")) out.n_priv_lds = (uint32_t)std::max(1, std::min(70, std::atoi(e)));
   out.n_shared = std::min<uint32_t>(256, 312 - NW * out.n_priv_lds);
-  if (const char *e = fdg::knob("FDG_POOL_SLOTS")) out.n_shared = (uint32_t)std::max(8, std::min<int>((int)out.n_shared, std::atoi(e)));
   for (uint32_t w = 0; w < NW; ++w) {
     OptParams q = prm;
     q.n_lds = out.n_priv_lds;
@@ -1643,7 +1548,6 @@ void build_pool_program(const Lowered &p, const OptParams &prm, CoopProgram &out
     // a pool read is an LDS read -- of a pool all four waves and the fetches hammer: issued 96 fold steps ahead of its use (32, the
     // distance of a wave's private LDS slots: -10 %; 200: the landing registers are missed elsewhere, -4 %; profiles/r04_log_la_lds.txt)
     q.lookahead_leaf = 96;
-    if (const char *e = fdg::knob("FDG_POOL_READ_AHEAD")) q.lookahead_leaf = (uint32_t)std::max(1, std::atoi(e));
     q.reserve_pairs = std::max<uint32_t>(q.reserve_pairs, S ? 4u : 2u);      // (as in build_coop_program; three more registers for the progress words)
     if (!fit_registers(B[w]->u, q, out.wave[w])) { out.why = out.wave[w].why; return; }
     Alloc A(p, out.wave[w].params, B[w]->u, B[w]->next_vid, out.wave[w]);
@@ -1686,22 +1590,19 @@ void build_pool_program(const Lowered &p, const OptParams &prm, CoopProgram &out
   }
   out.n_epoch = n_epoch;
   // ---- the pool: which leaf sits in which slot during which epochs (offline Belady at epoch granularity over all waves' reads) -----------
-  // Unit of residency: one leaf (512 bytes of the tile), or -- `pool_unit` 2, tile-major batches only -- a PAIR of leaves 2u, 2u + 1, adjacent
-  // in the tile, brought by ONE 64-lane LDS-direct load into two adjacent slots (a fetch instruction costs the wave that issues it about a
-  // hundred cycles whatever it brings: tools/ubench/vmem_issue.hip; leaf numbers follow the first visit, so a leaf's neighbour is used near it).
-  const uint32_t U = out.pool_unit == 2 ? 2 : 1;
-  const uint32_t P = out.n_shared / U, LU = (L + U - 1) / U;
-  std::vector<std::vector<uint32_t>> read_ep(LU);           // [unit] epochs in which some wave reads it (ascending, unique)
+  // Unit of residency: one leaf (512 bytes of the tile) in one slot.
+  const uint32_t P = out.n_shared;
+  std::vector<std::vector<uint32_t>> read_ep(L);            // [leaf] epochs in which some wave reads it (ascending, unique)
   for (uint32_t w = 0; w < NW; ++w) {
     uint32_t e = 0;
     for (const MOp &o : out.wave[w].ops) {
       if (o.kind == M_BARRIER) { e++; continue; }
-      if (o.kind == M_LD_LEAF) read_ep[o.a / U].push_back(e);
+      if (o.kind == M_LD_LEAF) read_ep[o.a].push_back(e);
       if (o.kind == M_LD_LEAF_ACC) { out.why = "landing slots are not part of the pooled variant"; return; }
     }
   }
-  std::vector<std::vector<uint32_t>> need(n_epoch + 1);     // [epoch] units read in it
-  for (uint32_t l = 0; l < LU; ++l) {
+  std::vector<std::vector<uint32_t>> need(n_epoch + 1);     // [epoch] leaves read in it
+  for (uint32_t l = 0; l < L; ++l) {
     auto &v = read_ep[l];
     std::sort(v.begin(), v.end());
     v.erase(std::unique(v.begin(), v.end()), v.end());
@@ -1709,9 +1610,9 @@ void build_pool_program(const Lowered &p, const OptParams &prm, CoopProgram &out
   }
   struct Fetch { uint32_t unit, slot, issue, ready, unit2; };       // unit2 != NONE: a second, arbitrary leaf by the same instruction into slot + 1
   std::vector<Fetch> fetches;
-  std::vector<uint32_t> slot_of(LU, NONE);                  // resident unit -> unit slot
-  std::vector<uint32_t> in_slot(P, NONE), last_read(P, 0);  // slot -> unit; last epoch in which the slot's content is read (as planned so far)
-  std::vector<std::vector<std::pair<uint32_t, uint32_t>>> resid(LU);  // [unit] (first epoch readable, slot) per residency, ascending
+  std::vector<uint32_t> slot_of(L, NONE);                   // resident leaf -> slot
+  std::vector<uint32_t> in_slot(P, NONE), last_read(P, 0);  // slot -> leaf; last epoch in which the slot's content is read (as planned so far)
+  std::vector<std::vector<std::pair<uint32_t, uint32_t>>> resid(L);   // [leaf] (first epoch readable, slot) per residency, ascending
   auto next_read = [&](uint32_t l, uint32_t from) -> uint32_t {     // first read epoch >= from
     auto &v = read_ep[l];
     auto it = std::lower_bound(v.begin(), v.end(), from);
@@ -1723,8 +1624,8 @@ void build_pool_program(const Lowered &p, const OptParams &prm, CoopProgram &out
   // (an instruction costs the issuing wave about a hundred cycles whatever it brings).  MEASURED SLOWER, so off unless FDG_POOL_PAIR=1: on the
   // 4-loop GV vertex function 1 245 instead of 2 195 fetch instructions (+9 % leaves) run 4.16 ms against 3.70; with pairs only into slots whose
   // content is dead or 64 epochs from its next read 1 694 instructions, no extra leaf, 3.96 ms (profiles/r04_log_pool_anypair.txt).
-  const bool pairing = U == 1 && fdg::knob("FDG_POOL_PAIR") && fdg::knob("FDG_POOL_PAIR")[0] == '1';
-  const uint32_t far = fdg::knob("FDG_POOL_FAR") ? (uint32_t)std::atoi(fdg::knob("FDG_POOL_FAR")) : 64;
+  const bool pairing = fdg::knob("FDG_POOL_PAIR") && fdg::knob("FDG_POOL_PAIR")[0] == '1';
+  const uint32_t far = 64;
   const uint32_t INF = std::numeric_limits<uint32_t>::max();
   const uint32_t pair_far = fdg::knob("FDG_POOL_PAIR_FAR") ? (uint32_t)std::atoi(fdg::knob("FDG_POOL_PAIR_FAR")) : 32;
   // may slot s2 be given away at `issue` to content first read in epoch e?  key: how late its present content is needed again (0: no)
@@ -1742,8 +1643,7 @@ void build_pool_program(const Lowered &p, const OptParams &prm, CoopProgram &out
     in_slot[slot] = l; slot_of[l] = slot; last_read[slot] = e;
     resid[l].push_back({e, slot});
   };
-  uint64_t n_paired = 0;
-  for (uint32_t e = 1; e <= n_epoch; ++e) {                 // epoch whose reads must be resident
+  for (uint32_t e = 1; e <= n_epoch; ++e) {                // epoch whose reads must be resident
     // (flag synchronisation: a reader in epoch e only knows that the others have reached sync point max(1, e - S), so the fetch must have been
     //  confirmed by then: `rdy` takes the place of e as the epoch by which the leaf has landed)
     //  -- except in the first S + 1 epochs of a tile, whose sync points are strict: the pool starts empty, and everything the first epochs read
@@ -1781,7 +1681,6 @@ void build_pool_program(const Lowered &p, const OptParams &prm, CoopProgram &out
           install(la, best, e);
           install(lb, best + 1, e);
           fetches.push_back(Fetch{la, best, issue, rdy, lb});
-          n_paired++;
           i += 2;
           continue;
         }
@@ -1807,19 +1706,8 @@ void build_pool_program(const Lowered &p, const OptParams &prm, CoopProgram &out
       uint32_t b = 0;
       for (MOp &o : out.wave[w].ops) if (o.kind == M_BARRIER) { ++b; o.b = b; o.a = b == n_epoch ? 0u : (b <= S + 1 ? b : std::max<uint32_t>(S + 1, b - S)); }
     }
-  out.n_fetch = fetches.size();
   out.n_transfer = 0;                                       // leaves brought from memory per tile
-  for (const Fetch &f : fetches) out.n_transfer += f.unit2 != NONE ? 2 : std::min<uint32_t>(U, L - f.unit * U);
-  if (fdg::knob("FDG_POOL_DEBUG")) {
-    std::vector<uint32_t> hist(ahead + 2, 0);
-    uint64_t sum = 0;
-    for (const Fetch &f : fetches) { hist[std::min<uint32_t>(f.ready - f.issue, ahead + 1)]++; sum += f.ready - f.issue; }
-    std::fprintf(stderr, "[pool] %llu of the fetches bring two leaves; ", (unsigned long long)n_paired);
-    std::fprintf(stderr, "[pool] %zu fetches of %u leaves (%llu leaves in all), issued %.2f epochs of %u ops ahead on average;", fetches.size(), U, (unsigned long long)out.n_transfer,
-                 fetches.empty() ? 0.0 : (double)sum / (double)fetches.size(), epoch_ops);
-    for (uint32_t k = 1; k < hist.size(); ++k) std::fprintf(stderr, " %u:%u", k, hist[k]);
-    std::fprintf(stderr, "\n");
-  }
+  for (const Fetch &f : fetches) out.n_transfer += f.unit2 != NONE ? 2 : 1;
   // ---- fetch ops into the waves' lists (round robin, right after the barrier that opens the issue epoch); leaf reads become pool reads -----
   std::vector<std::vector<std::vector<Fetch>>> at(NW, std::vector<std::vector<Fetch>>(n_epoch + 1));
   {   // dealt epoch by epoch (an issue costs the wave about a hundred cycles: the waves of an epoch should issue equally many), the
@@ -1827,11 +1715,8 @@ void build_pool_program(const Lowered &p, const OptParams &prm, CoopProgram &out
     std::vector<std::vector<size_t>> by_issue(n_epoch + 1);
     for (size_t i = 0; i < fetches.size(); ++i) by_issue[fetches[i].issue].push_back(i);
     uint32_t turn = 0;
-    const bool global_rr = fdg::knob("FDG_POOL_DEAL_GLOBAL") != nullptr;      // (experiment: the round-3 dealing, by global index)
-    // (experiment FDG_POOL_FETCH_WAVES=n: only the first n waves issue fetches -- is what a fetch costs its wave a property of the wave or of the CU?)
-    const uint32_t NF = fdg::knob("FDG_POOL_FETCH_WAVES") ? (uint32_t)std::max(1, std::min<int>((int)NW, std::atoi(fdg::knob("FDG_POOL_FETCH_WAVES")))) : NW;
     for (uint32_t ep = 0; ep <= n_epoch; ++ep)
-      for (size_t i : by_issue[ep]) { at[global_rr ? i % NF : turn % NF][ep].push_back(fetches[i]); turn++; }
+      for (size_t i : by_issue[ep]) { at[turn % NW][ep].push_back(fetches[i]); turn++; }
   }
   for (uint32_t w = 0; w < NW; ++w) {
     std::vector<MOp> r;
@@ -1839,7 +1724,7 @@ void build_pool_program(const Lowered &p, const OptParams &prm, CoopProgram &out
     uint32_t e = 0;
     auto put_fetches = [&](uint32_t ep) {      // shared[d .. d + b - 1] = leaf[a .. a + b - 1]
       for (const Fetch &f : at[w][ep]) {
-        MOp m{M_POOL_FETCH, 0, 0, f.slot * U, f.unit * U, std::min<uint32_t>(U, L - f.unit * U), (double)f.ready};
+        MOp m{M_POOL_FETCH, 0, 0, f.slot, f.unit, 1, (double)f.ready};
         if (f.unit2 != NONE) { m.b = 2; m.c = f.unit2; m.negc = 1; }         // negc: the second leaf is c (any leaf), not a + 1
         r.push_back(m);
       }
@@ -1849,9 +1734,9 @@ void build_pool_program(const Lowered &p, const OptParams &prm, CoopProgram &out
       if (o.kind == M_BARRIER) { r.push_back(o); e++; if (e <= n_epoch) put_fetches(e); continue; }
       if (o.kind == M_LD_LEAF) {
         uint32_t slot = NONE;
-        for (const auto &pr : resid[o.a / U]) if (pr.first <= e) slot = pr.second;      // the residency that covers epoch e: the last one that started by then
+        for (const auto &pr : resid[o.a]) if (pr.first <= e) slot = pr.second;      // the residency that covers epoch e: the last one that started by then
         if (slot == NONE) { out.why = "internal: leaf read without a residency"; return; }
-        MOp m{M_RECV, 0, 0, o.d, slot * U + o.a % U, 0, 0.0};
+        MOp m{M_RECV, 0, 0, o.d, slot, 0, 0.0};
         r.push_back(m);
         out.wave[w].n_recv++;
         continue;

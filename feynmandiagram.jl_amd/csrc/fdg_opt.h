@@ -99,12 +99,11 @@ struct OptParams {
                                   // out -- ((-z) w) and -(z w) differ in the sign of a real part that cancels exactly
   bool acc_in_agpr = false;       // fused-accumulation kernels of graphs with 41 ... 124 roots: the per-lane accumulators live in AGPR pairs (above the
                                   // program's own), three VGPR pairs (weight, two temporaries) above the values; one wave per SIMD
-  bool pool_leaves = false;       // pooled cooperative programs: leaves are re-read from the shared LDS pool (cheap to evict, never parked)
+  bool pool_leaves = false;       // pooled cooperative programs: leaves are re-read from the shared LDS pool (cheap to evict)
   bool leaves_once = false;       // row-major programs (round 6): a leaf is loaded ONCE, while its 16-leaf chunk of the rows sits in a staging buffer, and is
                                   // from then on a value like any other -- evicted to an LDS slot, an AGPR pair or the panel (512 bytes, coalesced) instead of
                                   // being dropped and "re-loaded", which for a row-major matrix means fetching its whole chunk (8 KB) again or gathering
                                   // 64 cache lines for 64 doubles (parquet_sigma5 row-major: 33 chunk fetches + 13 gathers for 18 chunks)
-  bool rm_pair = false;           // row-major programs with four staging buffers: chunks are fetched in pairs (csrc/fdg_isa.cpp: rm_plan)
   uint32_t reserve_pairs = 0;     // VGPR pairs the kernel variant keeps above the values (accumulators, weight): the value budget shrinks
                                   // by this and by the temporaries the program's macro ops need, so that everything stays below v256
 };
@@ -157,25 +156,23 @@ struct CoopProgram {
   uint64_t n_duplicate = 0;    // fold steps computed by more than one wave
   bool pooled = false;         // build_pool_program: leaves come through the shared pool (M_POOL_FETCH / M_RECV); needs sample stride 1, leaf
                                // offsets below 2^31 bytes from the tile's base (tile-major batches) and full 64-sample tiles
-  uint32_t pool_unit = 1;      // pooled: leaves per fetch (in: set before build_pool_program; 2 = pairs of adjacent leaves, needs leaf stride 64: tile-major batches)
   uint32_t slack = 0;          // pooled, round 6 (FDG_POOL_SYNC=flags): > 0 = the waves do not meet at s_barrier between the epochs of a tile; every wave publishes
                                // the number of sync points it has reached in an LDS word of its own and passes sync point b when every other wave has reached
                                // b (the first slack + 1 sync points of a tile: strict) or max(slack + 1, b - slack) (M_BARRIER with a = that number, b = the
                                // sync's index; a = 0: a real s_barrier -- the last of a tile).  The
                                // planner keeps a leaf `slack` epochs longer on both sides: fetched so that it has landed `slack` epochs before its first read,
                                // its slot given away no earlier than `slack` epochs after its last
-  uint64_t n_fetch = 0;        // pooled: leaf fetches from memory per tile (>= the live leaves; what exceeds them was evicted from the pool and came again)
   bool supported = false;
   std::string why;
 };
 void build_coop_program(const Lowered &p, const OptParams &prm, CoopProgram &out, uint32_t n_wave = 4);
 // Pooled cooperative variant: whole roots are dealt to the waves of a CU (balanced by the fold steps each adds), every wave runs the ordinary
 // depth-first schedule on its roots, and NO wave loads a leaf from memory into a register: leaves are fetched into a shared LDS pool by
-// LDS-direct loads `ahead` epochs before their first reader needs them and stay there while any wave still reads them (offline Belady over
+// LDS-direct loads up to eight epochs before their first reader needs them and stay there while any wave still reads them (offline Belady over
 // the merged read sequence of all waves at epoch granularity).  The vertex functions of the reference's two benchmark programs re-read their
 // leaves 2-3 times in the one-wave kernels because 324 on-chip values per sample cannot hold their 1000-1500 leaves; a CU's eight waves and the
 // pool together hold 1200.
-void build_pool_program(const Lowered &p, const OptParams &prm, CoopProgram &out, uint32_t n_wave = 8, uint32_t epoch_ops = 0, uint32_t ahead = 0);
+void build_pool_program(const Lowered &p, const OptParams &prm, CoopProgram &out, uint32_t n_wave = 8, uint32_t epoch_ops = 128);
 
 // The programs of one code object, owned here except the main one.  emit_isa prints them as `kname`, `kname`_w2, _acc, _rm, _rm_acc, _rl, _rl_acc,
 // _coop, _pool (and the streaming copies _nt / _acc_nt where they pay); the accessors say which of them the code object gets.

@@ -630,19 +630,14 @@ void parse_launch_cfg(fdg_graph *g) {
   c.no_rl = get("FDG_ISA_NO_RL") != nullptr;
   c.no_fused_acc = get("FDG_ISA_NO_FUSED_ACC") != nullptr;
   c.no_pool = get("FDG_ISA_NO_POOL") != nullptr;
-  c.pool_no_acc = get("FDG_ISA_POOL_NO_ACC") != nullptr;
   c.no_streaming = get("FDG_ISA_NO_STREAMING") != nullptr;
-  c.no_w2 = get("FDG_ISA_NO_W2") != nullptr;
   c.no_coop = get("FDG_ISA_NO_COOP") != nullptr;
   c.no_rm = get("FDG_ISA_NO_RM") != nullptr;
-  c.transpose_narrow = get("FDG_TRANSPOSE_NARROW") != nullptr;
   if (const char *e = get("FDG_ROOT_SCRATCH_MIN")) c.root_scratch_min = (uint32_t)std::max(0, std::atoi(e));
   if (const char *e = get("FDG_ROOT_SCRATCH_MB")) c.root_scratch_mb = (uint64_t)std::max(1, std::atoi(e));
   if (const char *e = get("FDG_ISA_WAVES_PER_CU")) c.waves_per_cu = std::max(1, std::atoi(e));
   if (const char *e = get("FDG_ISA_OVERSUB")) c.oversub = std::max(1, std::atoi(e));
   if (const char *e = get("FDG_ISA_MEM_WAVES")) c.mem_waves = std::max(0l, std::atol(e));
-  if (const char *e = get("FDG_ISA_MEM_OVERSUB")) c.mem_oversub = std::max(1l, std::atol(e));
-  if (const char *e = get("FDG_ISA_MEM_RATIO")) c.mem_ratio = std::atof(e);
   if (const char *e = get("FDG_ISA_TILE_CLAIM")) c.tile_claim = e[0] != '0' ? 1 : 0;
   if (const char *e = get("FDG_SM_CHUNK_MB")) c.sm_chunk_bytes = (uint64_t)std::max(1, std::atoi(e)) << 20;
   if (const char *e = get("FDG_EVAL_CHUNK")) c.eval_chunk = std::atoll(e);
@@ -843,7 +838,7 @@ struct IsaRun {
   // Graphs bound by memory (fewer than 2.5 executed fold steps per algorithmic byte) stream faster from FEWER resident waves: four per CU
   // (one per SIMD) keep 4 x L x 512 bytes in flight per CU -- enough for the latency-bandwidth product -- and the memory system sees a
   // quarter of the concurrent streams (round 4, profiles/r04_log_waves.txt: headline +3-5 %, the 2-loop graph +6-15 %); the graphs at or
-  // above the ridge want every wave they can get.  Options FDG_ISA_MEM_WAVES / FDG_ISA_MEM_OVERSUB / FDG_ISA_MEM_RATIO override (0 waves = off).
+  // above the ridge want every wave they can get.  Option FDG_ISA_MEM_WAVES overrides (0 waves = off).
   // The claimed walk of the graphs with 24 leaves or more runs from THREE: its waves cannot drift apart, which is what a fourth wave was
   // covering for in the static walk, where three only equalled four (headline, one process, one allocation: 10.05 against 10.20 ms paired,
   // 10.54 against 10.82 ms plain, every alternation; two waves lose 3.5 %; profiles/log_tile_prefetch_bound*.txt).
@@ -851,7 +846,7 @@ struct IsaRun {
     return g->cfg.mem_waves >= 0 ? g->cfg.mem_waves : (p.L >= 24 ? (claimed ? 3 : 4) : (accumulating ? 8 : 5));
   }
   bool mem_bound(uint64_t valu, uint64_t bytes, const fdg_isa_kernel &k, bool accumulating) const {
-    return mem_waves_of(accumulating) > 0 && g->cfg.waves_per_cu <= 0 && g->cfg.oversub <= 0 && bytes && (double)valu < g->cfg.mem_ratio * (double)bytes &&
+    return mem_waves_of(accumulating) > 0 && g->cfg.waves_per_cu <= 0 && g->cfg.oversub <= 0 && bytes && (double)valu < 2.5 * (double)bytes &&
            (long)waves_per_cu(k) > mem_waves_of(accumulating);
   }
   long shape(uint64_t valu, uint64_t bytes, const fdg_isa_kernel &k, size_t bytes_per_wg, bool accumulating = false) const {
@@ -862,11 +857,7 @@ struct IsaRun {
     return oversub((long)g->n_cu * full, bytes_per_wg);
   }
   // the grid of a memory-bound launch with `mem_waves` resident waves per CU
-  long mem_grid(long mem_waves) const {
-    long f = g->cfg.mem_oversub;
-    while (f > 1 && ntiles < (long)g->n_cu * mem_waves * f * 4) f >>= 1;
-    return (long)g->n_cu * mem_waves * f;
-  }
+  long mem_grid(long mem_waves) const { return (long)g->n_cu * mem_waves; }
   // a matrix whose 64-sample tiles are whole 128-byte lines (samples of a column contiguous, column stride a multiple of 16
   // doubles, base on a line): the streaming variants may be used (non-temporal accesses would fetch a shared line twice)
   bool line_aligned(const void *base, long sample_stride, long col_stride) const {
@@ -881,11 +872,11 @@ struct IsaRun {
     const size_t panel = std::max((size_t)std::max<uint32_t>(ev.mem_slots, 1) * 512u * (size_t)grid,
                                   (size_t)std::max<uint32_t>(w2.mem_slots, 1) * 1024u * (size_t)grid2);
     // pooled cooperative variant: full tiles of batches whose samples of a leaf are contiguous and whose leaves lie within 2 GB of the tile's first
-    pool_ok = K(FDG_K_POOL).present && K(FDG_K_POOL).fn && a.ss == 1 && a.ls > 0 && (g->pool_unit == 1 || a.ls == 64) &&
+    pool_ok = K(FDG_K_POOL).present && K(FDG_K_POOL).fn && a.ss == 1 && a.ls > 0 &&
               (uint64_t)a.ls * 8u * (uint64_t)std::max<uint32_t>(p.L, 1) < (1ull << 31) && a.B >= 64 && !g->cfg.no_pool;
     // (a graph that has the pooled variant accumulates through it and the root scratch: its fused-accumulation program, with R + 2 fewer value
     //  registers and no pool, runs the 4-loop GV vertex function at 0.87e8 samples/s where the pooled evaluation + the weighted sum do 1.3e8)
-    fused_acc = a.mode == 1 && ac.present && !g->cfg.no_fused_acc && !(pool_ok && !g->cfg.pool_no_acc);
+    fused_acc = a.mode == 1 && ac.present && !g->cfg.no_fused_acc && !pool_ok;
     grid3 = ac.present ? shape(g->st_valu[1], 8ull * p.L, ac, ((size_t)ac.mem_slots + R) * 512u, true) : 0;
     const size_t panel3 = (size_t)std::max<uint32_t>(ac.mem_slots, 1) * 512u * (size_t)grid3;
     grid4 = rm.present ? (long)g->n_cu * waves_per_cu(rm) : 0;
@@ -942,7 +933,7 @@ struct IsaRun {
   // when there is one and the samples of a leaf are contiguous, the rest through the W = 1 kernel
   int launch_isa(const double *lf, long lss, long lls, double *rt, long rrs, long rrk, long n, long tls = 0, long trs = 0) {
     long done = 0;
-    if (K(FDG_K_W2).present && lss == 1 && n >= 128 && !tls && !trs && !g->cfg.no_w2) {
+    if (K(FDG_K_W2).present && lss == 1 && n >= 128 && !tls && !trs) {
       const long n2 = n & ~127l;
       const int rc = launch(FDG_K_W2, lf, lss, lls, rt, rrs, rrk, n2, std::min<long>(n2 / 128, grid2), nullptr, 128 * lss, 128 * rrs);
       if (rc) return rc;
@@ -1107,7 +1098,7 @@ struct IsaRun {
     HIP_TRY(hipStreamWaitEvent(s2, (hipEvent_t)g->ev_in, 0));
     auto transpose = [&](long c0, int buf) {
       const long n = std::min<long>(Bc, B - c0);
-      if (ls == 1 && (ss & 1) == 0 && ((uintptr_t)a.d_leaf & 15) == 0 && p.L >= 32 && !g->cfg.transpose_narrow) {
+      if (ls == 1 && (ss & 1) == 0 && ((uintptr_t)a.d_leaf & 15) == 0 && p.L >= 32) {
         const long ntile = ((n + 63) / 64) * ((p.L + 63) / 64);
         hipLaunchKernelGGL(fdg_transpose_rows_wide, dim3((unsigned)std::min<long>(ntile, (long)g->n_cu * 8)), dim3(256), 0, s2,
                            a.d_leaf + c0 * ss, (long)ss, (double *)((char *)g->d_ws3 + (size_t)buf * one), Bc, n, p.L);
@@ -1367,12 +1358,7 @@ int compile_hipcc(const std::string &src_path, const std::string &out_path, bool
 
 // LDS budget of the interpreter: enough slots for the whole live set when it
 // is small (8 blocks/CU), otherwise 40 slots = 80 KiB per block (2 blocks/CU)
-static uint32_t interp_lds_budget() {
-  uint32_t budget = 40;
-  const char *env = fdg::knob("FDG_LDS_SLOTS");
-  if (env) budget = (uint32_t)std::max(1, std::atoi(env));
-  return std::min(budget, 79u);
-}
+static constexpr uint32_t kInterpLdsBudget = 40;
 
 extern "C" {
 
@@ -1398,7 +1384,7 @@ int fdg_graph_create(const fdg_graph_desc *d, fdg_graph **out) {
   p.fac.assign(d->child_fac, d->child_fac + p.E);
   p.root_slot.assign(d->root_slot, d->root_slot + p.R);
   analyse(p);
-  build_interpreter_program(p, interp_lds_budget());
+  build_interpreter_program(p, kInterpLdsBudget);
   g->knobs = fdg::env_snapshot();
   parse_launch_cfg(g);
   *out = g;
@@ -1460,7 +1446,7 @@ int fdg_graph_set_association(fdg_graph *g, int assoc) {
     set_error("fdg_graph_set_association must be called before the handle is specialised"); return FDG_E_INVALID;
   }
   g->prog.assoc_interp = want;
-  build_interpreter_program(g->prog, interp_lds_budget());
+  build_interpreter_program(g->prog, kInterpLdsBudget);
   if (g->d_code) { hipDeviceSynchronize(); hipFree(g->d_code); g->d_code = nullptr; }      // (the stream is uploaded again on the next use)
   return FDG_OK;
 }
@@ -1613,7 +1599,6 @@ static fdg::OptParams pool_params(fdg::OptParams q, uint32_t nw) {
   q.n_acc = nw >= 8 ? 0 : 124;
   q.n_land = 0;
   q.lookahead_lds = 32;
-  if (const char *e = fdg::knob("FDG_POOL_LA_LDS")) q.lookahead_lds = (uint32_t)std::max(1, std::atoi(e));       // experiments
   return q;
 }
 
@@ -1621,7 +1606,7 @@ static int coop_program_out(const fdg::CoopProgram &cp, uint32_t wave, fdg_mop *
 // (shorter epochs read fewer leaves at a time: tried when the pool cannot hold what a window of epochs reads)
 static void build_pool_auto(const fdg::Lowered &p, const fdg::OptParams &q, fdg::CoopProgram &cp, uint32_t nw) {
   for (uint32_t ep : {128u, 64u, 32u, 16u}) {
-    fdg::build_pool_program(p, q, cp, nw, ep, 0);
+    fdg::build_pool_program(p, q, cp, nw, ep);
     if (cp.supported || cp.why != "leaf pool exhausted") break;
   }
 }
@@ -1758,7 +1743,6 @@ static void install_isa(fdg_graph *g, const fdg::IsaPrograms &V, std::vector<cha
   if (K[FDG_K_POOL].present) {
     g->pool_panel_wg = panel_bytes_per_wg(V.pool);
     g->pool_fetch = (uint32_t)V.pool.n_transfer;      // leaves brought from memory per tile
-    g->pool_unit = V.pool.pool_unit;
     g->pool_valu = 0;
     for (uint32_t w = 0; w < V.pool.n_wave; ++w) g->pool_valu += V.pool.wave[w].n_valu;
   }
@@ -1784,9 +1768,6 @@ static void install_isa(fdg_graph *g, const fdg::IsaPrograms &V, std::vector<cha
 // every program of a handle specialised with FDG_SPEC_FAST_MATH fuses products into sums (v_fma_f64)
 static void build_prog(const fdg_graph *g, fdg::OptParams prm, fdg::OptProgram &out) {
   prm.fma = prm.fma || g->isa_fma;
-  if (const char *e = fdg::knob("FDG_LA_LDS")) prm.lookahead_lds = (uint32_t)std::max(1, std::atoi(e));       // experiments
-  if (const char *e = fdg::knob("FDG_LA_LDS_B")) { if (prm.n_acc) prm.lookahead_lds = (uint32_t)std::max(1, std::atoi(e)); }   // ... one wave per SIMD only
-  if (fdg::knob("FDG_ROOTS_LAST") && !g->isa_fma) prm.roots_last = true;   // experiment: every program's root stores back to back at the tile's end (one block of a tile-major root batch)
   fdg::build_opt_program(g->prog, prm, out);
 }
 
@@ -1800,7 +1781,6 @@ static fdg::OptParams cfg_B() {
 // experiment switch: FDG_LAND=<n> AGPR landing slots for the leaf loads of the one-wave configuration (0 = none)
 static void apply_land_env(fdg::OptParams &q) {
   if (const char *e = fdg::knob("FDG_LAND")) q.n_land = q.n_acc ? std::min<uint32_t>((uint32_t)std::max(0, std::atoi(e)), q.n_acc / 2) : 0;
-  if (const char *e = fdg::knob("FDG_LAND_LA")) q.lookahead_land = (uint32_t)std::max(1, std::atoi(e));
 }
 
 static fdg::OptParams auto_program(const fdg_graph *g, fdg::OptProgram &prog) {
@@ -1869,7 +1849,7 @@ static bool build_acc_program(const fdg_graph *g, const fdg::OptParams &chosen, 
   //  accumulators would take more than a third of the value registers and the roots go through the column-major scratch)
   // (few roots: eight value registers next to the accumulators are enough -- the tiny-graph configuration of the 2-loop
   //  self-energies keeps 28; many roots must leave the values a working set worth having)
-  if (g->prog.R > 40 && g->prog.R <= 124 && chosen.n_reg >= 100 && !fdg::knob("FDG_ISA_NO_FUSED_ACC") && !fdg::knob("FDG_ISA_NO_AGPR_ACC")) {
+  if (g->prog.R > 40 && g->prog.R <= 124 && chosen.n_reg >= 100 && !fdg::knob("FDG_ISA_NO_FUSED_ACC")) {
     // 41 ... 124 roots (round 4): the accumulators in AGPR pairs -- the file a kernel launched with one wave per SIMD has to itself (the graphs
     // bound by memory are launched that way whatever their registers allow; the one-wave configuration uses it for spills and keeps what
     // the accumulators leave) -- instead of the detour through the root scratch, which cost the 84-root 3-loop vertex function a third.
@@ -1903,8 +1883,7 @@ static bool build_acc_program(const fdg_graph *g, const fdg::OptParams &chosen, 
 static uint32_t build_rm_program(const fdg_graph *g, const fdg::OptParams &chosen, fdg::OptProgram &pr, fdg::OptParams *qsel = nullptr) {
   if (g->prog.L < 16 || fdg::knob("FDG_ISA_NO_RM")) return 0;
   // (graphs in the tiny-graph configuration too, round 4: their contiguous rows take the linear variant, but rows with padding between them
-  //  had only the transposition pass left -- 0.2 of the HBM roof on the 3-loop self-energy; FDG_ISA_RM_TINY=0 restores that)
-  if (chosen.n_reg < 100 && fdg::knob("FDG_ISA_RM_TINY") && fdg::knob("FDG_ISA_RM_TINY")[0] == '0') return 0;
+  //  had only the transposition pass left -- 0.2 of the HBM roof on the 3-loop self-energy)
   // One wave per SIMD whatever the leaf-major kernel runs with: 40 KB of LDS per wave hold up to four staging buffers -- the
   // stream of first uses plus the few chunks a schedule keeps coming back to -- and the AGPR level makes up for the LDS
   // slots given away.  (Graphs that stream leaves are bound by latency, not by occupancy: DESIGN.md 6.)  The fewest
@@ -1912,7 +1891,6 @@ static uint32_t build_rm_program(const fdg_graph *g, const fdg::OptParams &chose
   // more waves per CU.  A program that would move more than 2.5x the matrix (leaves re-read all over a huge graph)
   // gets no such variant: the chunked transposition in front of the leaf-major kernel is cheaper there.
   const uint32_t n_chunk = (g->prog.L + 15) / 16;
-  const char *e = fdg::knob("FDG_ISA_RM_BUFS");
   // Two waves per SIMD when the program is small enough: the variant is bound by memory latency (one wave per SIMD spends
   // ~46 % of its cycles waiting for its chunks), and what hides latency is a second wave with its own two
   // buffers in flight.  Budget per wave: 256 registers (120 values + the nine address registers, no AGPR level) and
@@ -1920,38 +1898,29 @@ static uint32_t build_rm_program(const fdg_graph *g, const fdg::OptParams &chose
   // keep re-fetching within a quarter of the chunk count.
   // (Up to eight chunks -- 128 leaves: with longer rows the two buffers of a wave are too short a window; measured round 4,
   //  profiles/r04_log_rm_bufs.txt: 111 leaves +20 % over one wave per SIMD, 175 leaves -16 %.)
-  const char *ew = fdg::knob("FDG_ISA_RM_WAVES");
-  if (!(ew && std::atoi(ew) == 1) && !e && (n_chunk <= 8 || (ew && std::atoi(ew) == 2))) {
+  if (n_chunk <= 8) {
     // (both root orders are tried: in the reference's order the first uses of the leaves walk the row monotonically; round 6: also with
     //  the leaves loaded once and with shorter value-numbering windows, as in the one-wave search below)
-    const char *lo_env2 = fdg::knob("FDG_RM_LEAVES_ONCE"), *vn_env2 = fdg::knob("FDG_RM_VN");
     std::vector<uint32_t> windows2 = {chosen.vn_window};
-    if (vn_env2) windows2 = {(uint32_t)std::atoi(vn_env2)};
-    else if (g->prog.N <= 60000) for (uint32_t w : {1000u, 400u, 200u, 100u}) if (chosen.vn_window == 0 || w < chosen.vn_window) windows2.push_back(w);
-    const char *pp = fdg::knob("FDG_ISA_RM_PANEL_PCT");
-    const uint64_t panel_pct = pp ? (uint64_t)std::atoi(pp) : 0;
+    if (g->prog.N <= 60000) for (uint32_t w : {1000u, 400u, 200u, 100u}) if (chosen.vn_window == 0 || w < chosen.vn_window) windows2.push_back(w);
     double best2 = 1e300;
     fdg::OptProgram cand2;
     fdg::OptParams qbest;
     for (uint32_t vw : windows2)
     for (int variant = 0; variant < 4; ++variant) {
       const int keep = variant & 1, once = variant >> 1;
-      if (lo_env2 && (lo_env2[0] == '1') != (once != 0)) continue;
       fdg::OptParams q = cfg_A();
       q.vn_window = vw;
       q.n_lds = 8;
       q.reserve_pairs = 5;
       q.lookahead_leaf = 48;
-      if (const char *la = fdg::knob("FDG_ISA_RM_LA")) q.lookahead_leaf = (uint32_t)std::max(1, std::atoi(la));
       q.leaves_once = once != 0;
       q.keep_root_order = keep != 0;
       q.roots_last = true;             // the R stores of a row back to back: they share cache lines when the roots are row-major too (+7-11 %)
       build_prog(g, q, cand2);
-      if (!cand2.supported || (cand2.n_ld_mem + cand2.n_st_mem) * 100 > cand2.n_valu * panel_pct) continue;
+      if (!cand2.supported || cand2.n_ld_mem + cand2.n_st_mem != 0) continue;
       uint64_t fetches = 0, gathers = 0;
       fdg::rm_plan_stats(g->prog, cand2, 2, fetches, gathers);
-      if (fdg::knob("FDG_RM_DEBUG")) std::fprintf(stderr, "[rm] two waves per SIMD (root order %d, leaves once %d, vn %u): %u chunks, %llu fetches, %llu gathers with 2 buffers, %llu fold steps, %llu panel; lds slots %u\n", keep, once, vw, n_chunk,
-                                                  (unsigned long long)fetches, (unsigned long long)gathers, (unsigned long long)cand2.n_valu, (unsigned long long)(cand2.n_ld_mem + cand2.n_st_mem), cand2.n_lds_used);
       if (!(fetches * 4 <= (uint64_t)n_chunk * 5 + 4 && (fetches * 8192 + gathers * 2048) * 2 <= (uint64_t)g->prog.L * 512 * 5)) continue;
       const double cost = (double)cand2.n_valu * 4.5 + (double)fetches * 800.0 + (double)gathers * 400.0 + (double)(cand2.n_ld_mem + cand2.n_st_mem) * 60.0 + (double)(cand2.n_ld_lds + cand2.n_st_lds) * 8.0;
       if (cost < best2) { best2 = cost; pr = cand2; qbest = q; }
@@ -1961,59 +1930,47 @@ static uint32_t build_rm_program(const fdg_graph *g, const fdg::OptParams &chose
   // Four buffers first -- the deepest prefetch: +5-18 % on the graphs whose values then still fit the registers and AGPRs (no panel access
   // with the 14 LDS slots that remain) -- then the fewest buffers that keep re-fetching low (graphs that need their LDS slots:
   // four buffers -9 % on the 5-loop Parquet self-energy; profiles/r04_log_rm_bufs.txt).
-  const uint32_t first = e ? (uint32_t)std::max(1, std::min(4, std::atoi(e))) : 2u;
   // Round 6: per buffer count the candidates are {root order} x {leaves re-loadable | loaded once (fdg_opt.h: leaves_once)} x {value-numbering
   // window: the tile-major kernel's, and shorter ones -- a long window keeps values alive that the staging buffers' share of the LDS no longer
   // has room for}, compared by an estimate of what a tile costs its wave in cycles: a fold step 4.5, a chunk fetch 800 (eight LDS-direct loads),
   // a gathered leaf 400 (64 lines for 64 doubles), a panel access 60, an LDS move 8, an AGPR move 12.  (parquet_sigma5: 33 fetches + 13 gathers
   // + 231 panel accesses with re-loadable leaves and the tile-major window -> 17 fetches and a few dozen panel accesses; 0.22 -> 0.35 of the
-  // HBM roof with leaves_once alone, profiles/r06_log_sweep_d.txt.)  FDG_RM_LEAVES_ONCE=0 / 1, FDG_RM_VN=<window> force one form.
-  const char *lo_env = fdg::knob("FDG_RM_LEAVES_ONCE"), *vn_env = fdg::knob("FDG_RM_VN");
+  // HBM roof with leaves_once alone, profiles/r06_log_sweep_d.txt.)
   std::vector<uint32_t> windows = {chosen.vn_window};
-  if (vn_env) windows = {(uint32_t)std::atoi(vn_env)};
-  else if (g->prog.N <= 60000) for (uint32_t w : {2000u, 1000u, 400u, 200u}) if (chosen.vn_window == 0 || w < chosen.vn_window) windows.push_back(w);
+  if (g->prog.N <= 60000) for (uint32_t w : {2000u, 1000u, 400u, 200u}) if (chosen.vn_window == 0 || w < chosen.vn_window) windows.push_back(w);
   auto est_cycles = [](const fdg::OptProgram &c, uint64_t fetches, uint64_t gathers) {
     return (double)c.n_valu * 4.5 + (double)fetches * 800.0 + (double)gathers * 400.0 + (double)(c.n_ld_mem + c.n_st_mem) * 60.0 +
            (double)(c.n_ld_lds + c.n_st_lds) * 8.0 + (double)(c.n_ld_acc + c.n_st_acc) * 12.0;
   };
-  for (uint32_t pass = e ? 1u : 0u; pass < 2; ++pass)
-  for (uint32_t bufs = pass == 0 ? 4u : first; bufs <= 4; ++bufs) {
+  for (uint32_t pass = 0; pass < 2; ++pass)
+  for (uint32_t bufs = pass == 0 ? 4u : 2u; bufs <= 4; ++bufs) {
     double best_cost = 1e300; uint64_t best_fetches = 0, best_gathers = 0, best_panel = 0;
     bool any = false;
     fdg::OptProgram cand;
     for (uint32_t vw : windows)
     for (int variant = 0; variant < 4; ++variant) {
       const int keep = variant & 1, once = variant >> 1;
-      if (lo_env && (lo_env[0] == '1') != (once != 0)) continue;
       fdg::OptParams q = cfg_B();
       q.vn_window = vw;
       q.n_lds = 80u - bufs * 16u - 2u;                             // (two slots lost to the 1 KB alignment of the buffers)
       q.reserve_pairs = 5;
       q.lookahead_leaf = 48;
-      if (const char *la = fdg::knob("FDG_ISA_RM_LA")) q.lookahead_leaf = (uint32_t)std::max(1, std::atoi(la));
       q.leaves_once = once != 0;
       q.keep_root_order = keep != 0;
       q.roots_last = true;             // the R stores of a row back to back: they share cache lines when the roots are row-major too (+7-11 %)
-      q.rm_pair = bufs == 4 && fdg::knob("FDG_RM_PAIR") && fdg::knob("FDG_RM_PAIR")[0] == '1';
       build_prog(g, q, cand);
       if (!cand.supported) { if (!any && variant == 0 && vw == windows[0] && pass == 1) return 0; continue; }
       any = true;
       uint64_t fetches = 0, gathers = 0;
       fdg::rm_plan_stats(g->prog, cand, bufs, fetches, gathers);
       const double cost = est_cycles(cand, fetches, gathers);
-      if (fdg::knob("FDG_RM_DEBUG")) std::fprintf(stderr, "[rm] one wave per SIMD (root order %d, leaves once %d, vn %u): %u chunks, %llu fetches, %llu gathers with %u buffers, %llu fold steps, %llu panel accesses, %llu LDS and %llu AGPR moves: %.0f cycles\n", keep, once, vw, n_chunk,
-                                                  (unsigned long long)fetches, (unsigned long long)gathers, bufs, (unsigned long long)cand.n_valu, (unsigned long long)(cand.n_ld_mem + cand.n_st_mem),
-                                                  (unsigned long long)(cand.n_ld_lds + cand.n_st_lds), (unsigned long long)(cand.n_ld_acc + cand.n_st_acc), cost);
       if (cost < best_cost) { best_cost = cost; best_fetches = fetches; best_gathers = gathers; best_panel = cand.n_ld_mem + cand.n_st_mem; pr = std::move(cand); if (qsel) *qsel = q; }
     }
     if (best_cost == 1e300) { if (pass == 1) return 0; break; }      // (every candidate unsupported: no row-major program, not a count with `pr` unset)
     const bool cheap = best_fetches * 4 <= (uint64_t)n_chunk * 5 + 4;
     if (pass == 0) { if (best_cost < 1e300 && cheap && best_panel == 0) return 4; break; }
-    if (!cheap && bufs < 4 && !e) continue;
-    {   // (FDG_ISA_RM_MAX_TRAFFIC=<tenths>: the bound on what the variant may move, in tenths of the matrix; default 25)
-      const uint64_t tenths = fdg::knob("FDG_ISA_RM_MAX_TRAFFIC") ? (uint64_t)std::max(10, std::atoi(fdg::knob("FDG_ISA_RM_MAX_TRAFFIC"))) : 25;
-      if ((best_fetches * 8192 + best_gathers * 2048) * 10 > (uint64_t)g->prog.L * 512 * tenths) return 0;
-    }
+    if (!cheap && bufs < 4) continue;
+    if ((best_fetches * 8192 + best_gathers * 2048) * 10 > (uint64_t)g->prog.L * 512 * 25) return 0;      // more than 2.5 x the matrix
     return bufs;
   }
   return 0;
@@ -2027,9 +1984,6 @@ static void build_coop(const fdg_graph *g, const fdg::OptProgram &prog, fdg::Isa
   (void)prog;
   fdg::OptParams q = cfg_B();
   q.vn_window = 200;
-  if (const char *x = fdg::knob("FDG_COOP_LA_LEAF")) q.lookahead_leaf = (uint32_t)std::atoi(x);
-  if (const char *x = fdg::knob("FDG_COOP_LA_MEM")) q.lookahead_mem = (uint32_t)std::atoi(x);
-  if (const char *x = fdg::knob("FDG_COOP_LA_LDS")) q.lookahead_lds = (uint32_t)std::atoi(x);
   if (!(e && e[0] == '1')) {
     fdg::OptProgram ref;                      // the one-wave program without recomputation decides
     build_prog(g, q, ref);
@@ -2044,13 +1998,13 @@ static void build_coop(const fdg_graph *g, const fdg::OptProgram &prog, fdg::Isa
   }
 }
 static void build_variants(const fdg_graph *g, const fdg::OptParams &chosen, bool allow_w2, fdg::IsaPrograms &V) {
-  V.w2 = allow_w2 && !fdg::knob("FDG_ISA_NO_W2") && auto_program_w2(g, V.p2);
+  V.w2 = allow_w2 && auto_program_w2(g, V.p2);
   V.acc = build_acc_program(g, chosen, V.pa);
   fdg::OptParams qrm;
   V.rm_bufs = build_rm_program(g, chosen, V.pr, &qrm);
   // fused accumulation of row-major input: the row-major program once more with R + 2 fewer value registers
   V.rm_acc = false;
-  if (V.rm_bufs && V.acc && g->prog.R >= 1 && g->prog.R <= 40 && !fdg::knob("FDG_ISA_NO_RM_ACC")) {
+  if (V.rm_bufs && V.acc && g->prog.R >= 1 && g->prog.R <= 40) {
     qrm.reserve_pairs += g->prog.R + 2;
     qrm.roots_last = false;           // (accumulation: a root is consumed where it is finished)
     build_prog(g, qrm, V.pra);
@@ -2074,10 +2028,7 @@ static void build_pool(const fdg_graph *g, const fdg::OptProgram &prog, fdg::Isa
   const uint32_t nw = pool_waves();
   fdg::OptParams q = pool_params(cfg_B(), nw);
   q.vn_window = prog.params.vn_window;
-  if (const char *v = fdg::knob("FDG_POOL_VN")) q.vn_window = (uint32_t)std::max(0, std::atoi(v));      // (experiment: the pooled waves' own value-numbering window)
   build_pool_auto(g->prog, q, V.pool, nw);
-  if (fdg::knob("FDG_POOL_DEBUG")) std::fprintf(stderr, "[pool] %s: %u waves, %u epochs, %llu fetches for %u leaves, %llu duplicated fold steps (%s)\n", V.pool.supported ? "built" : "not built",
-                                                  V.pool.n_wave, V.pool.n_epoch, (unsigned long long)V.pool.n_fetch, g->prog.n_live_leaf, (unsigned long long)V.pool.n_duplicate, V.pool.why.c_str());
 }
 // The linear row-major variant (csrc/fdg_isa.cpp: `rl`): contiguous rows (sample stride == L) of graphs whose 64-row tile, 512 L bytes, leaves
 // room for two waves per CU or more.  One wave per SIMD at most, so the AGPR level is there; a leaf comes back from the image by an LDS read.
@@ -2086,22 +2037,21 @@ static void build_rl(const fdg_graph *g, const fdg::OptParams &chosen, fdg::IsaP
   const char *e = fdg::knob("FDG_ISA_RL");
   // Three waves per CU or more (image + eight LDS slots three times into 160 KB: up to 98 leaves): with two, a wave that waits for its
   // tile has one partner to cover it and the variant loses to the chunked one -- measured at 116 and 155 leaves: 2.26 vs 2.75e9 and
-  // 2.34 vs 2.72e9 evaluations/s; equal at 111 (profiles/r04_log_rl_big.txt).  FDG_ISA_RL_MAX_KB overrides the bound on the image.
-  const uint32_t rl_max_bytes = fdg::knob("FDG_ISA_RL_MAX_KB") ? (uint32_t)std::atoi(fdg::knob("FDG_ISA_RL_MAX_KB")) * 1024u : (160u * 1024u / 3u - 8u * 512u);
+  // 2.34 vs 2.72e9 evaluations/s; equal at 111 (profiles/r04_log_rl_big.txt).
+  const uint32_t rl_max_bytes = 160u * 1024u / 3u - 8u * 512u;
   if ((e && e[0] == '0') || g->prog.L < 2 || ((512u * g->prog.L + 1023u) & ~1023u) > rl_max_bytes || g->isa_fma) return;
   fdg::OptParams q = cfg_B();
   q.vn_window = chosen.vn_window;
   q.n_lds = 512u * g->prog.L > 72u * 1024u ? 0 : 8;
   q.reserve_pairs = 1;
   q.lookahead_leaf = 32;
-  q.pool_leaves = true;          // (an evicted leaf is read again from the image: cheap, and it is not parked anywhere)
+  q.pool_leaves = true;          // (an evicted leaf is read again from the image: cheap)
   q.roots_last = true;
-  if (const char *la = fdg::knob("FDG_ISA_RL_LA")) q.lookahead_leaf = (uint32_t)std::max(1, std::atoi(la));
   build_prog(g, q, V.prl);
   V.rl = V.prl.supported && V.prl.n_ld_mem + V.prl.n_st_mem == 0;
   // fused accumulation over the same rows: R accumulators, the weight and a temporary above the values
   V.rl_acc = false;
-  if (V.rl && V.acc && g->prog.R >= 1 && g->prog.R <= 40 && !fdg::knob("FDG_ISA_NO_RL_ACC")) {
+  if (V.rl && V.acc && g->prog.R >= 1 && g->prog.R <= 40) {
     q.reserve_pairs += g->prog.R + 2;
     q.n_reg = std::min<uint32_t>(q.n_reg, (256u - 6u - 2u * (g->prog.R + 2) - 2u - 8u) / 2u);
     q.roots_last = false;            // (a root is consumed where it is finished)
@@ -2370,9 +2320,6 @@ bool fdg_mc_isa_supported(fdg_graph *g, const fdg_leaf_tables *tab, std::string 
   // (measured: 5-loop self-energy, 13 000 ops, one kernel 1.67x faster; its Taylor expansion, 479 leaves and 79 000 ops, 0.9x;
   // the 4-loop vertex function of example/benchmark.jl, 984 leaves and 65 000 ops, 1.68x).  The other route writes and reads
   // 16 bytes per leaf and sample, which is worth some tens of fold steps: the budget grows with the number of leaves.
-  if (fdg::knob("FDG_MC_DEBUG"))
-    std::fprintf(stderr, "[mc] one-kernel program: valu %llu ld_leaf %llu ld_mem %llu st_mem %llu ld_lds %llu st_lds %llu\n", (unsigned long long)prog.n_valu,
-                 (unsigned long long)prog.n_ld_leaf, (unsigned long long)prog.n_ld_mem, (unsigned long long)prog.n_st_mem, (unsigned long long)prog.n_ld_lds, (unsigned long long)prog.n_st_lds);
   if (recommended) *recommended = prog.supported && prog.n_valu <= 40000 + 30ull * g->prog.L;
   return prog.supported;
 }

@@ -157,7 +157,7 @@ int fdg_graph_set_association(fdg_graph *g, int assoc);
  * fdg_graph_set_option changes one (value NULL: removes it) -- the same names, plus the variant selectors and tuning knobs the tests and dev
  * tools use (FDG_ISA_W2, FDG_ISA_COOP, FDG_COOP_WAVES, FDG_ISA_NO_FUSED_ACC, FDG_ROOT_SCRATCH_MB, ...).  Options that shape
  * a kernel must be set before the fdg_graph_specialize* call that builds it; options of the launch path (FDG_ISA_NO_*, FDG_*_CHUNK*,
- * FDG_ROOT_SCRATCH_*, FDG_ISA_WAVES_PER_CU, FDG_ISA_OVERSUB, FDG_ISA_MEM_*, FDG_ISA_TILE_CLAIM) take effect with the next call: they are
+ * FDG_ROOT_SCRATCH_*, FDG_ISA_WAVES_PER_CU, FDG_ISA_OVERSUB, FDG_ISA_MEM_WAVES, FDG_ISA_TILE_CLAIM) take effect with the next call: they are
  * parsed into the handle here, and between an evaluation entry point and hipModuleLaunchKernel nothing is looked up by name.
  * FDG_ISA_TILE_CLAIM = "1" / "0": launches of the root-writing one-wave kernels that the plan finds bound by memory always / never use
  * the twin whose waves claim their next run of tiles from a counter in the stream's workspace (fdg_isa_eval_cl / fdg_isa_eval_nt_cl: the

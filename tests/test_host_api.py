@@ -578,3 +578,29 @@ def test_handle_options_replace_the_environment(libfdg, monkeypatch):
     rt = open(os.path.join(src, "fdg_runtime.hip")).read()
     body = rt[rt.index("// The launch path."):rt.index("// JIT\n")]
     assert "knob(" not in body and "getenv" not in body
+
+
+def test_the_documented_options_are_the_ones_the_library_reads():
+    """INTEGRATION.md section 4 lists every option by name, supported and experiment together, and nothing else: the names the sources read
+    -- knob("FDG_...") anywhere in csrc/ outside a comment, get("FDG_...") in parse_launch_cfg -- are that set.  Left out of the documented
+    set: the names the section marks as read by the Python side only, and FDG_SPEC_*, which are flags of fdg_graph_specialize."""
+    import glob
+    src = os.path.join(os.path.dirname(capi.__file__), "csrc")
+    read = set()
+    for f in glob.glob(os.path.join(src, "*")):
+        code = "\n".join(line.split("//")[0] for line in open(f, errors="replace"))
+        read |= set(re.findall(r'\bknob\("(FDG_[A-Z0-9_]+)"\)', code))
+    rt = open(os.path.join(src, "fdg_runtime.hip")).read()
+    cfg = rt[rt.index("void parse_launch_cfg("):rt.index("// mode 0: roots -> d_root")]
+    in_cfg = set(re.findall(r'\bget\("(FDG_[A-Z0-9_]+)"\)', cfg))
+    assert len(in_cfg) >= 10
+    read |= in_cfg
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    sec = doc[doc.index("## 4. Options and the environment"):]
+    sec = sec[sec.index("**Supported**"):]
+    documented = set()
+    for line in sec.splitlines():
+        if not line.startswith("* Python side only"):
+            documented |= {n for n in re.findall(r"FDG_[A-Z0-9_]+", line) if not n.startswith("FDG_SPEC_")}
+    assert documented - read == set(), "documented, read by nothing"
+    assert read - documented == set(), "read by the library, not documented"
