@@ -33,7 +33,7 @@ FDG_TILE_SAMPLES = 64
 EXPORTS = [
     "fdg_last_error", "fdg_version", "fdg_graph_create", "fdg_graph_destroy", "fdg_graph_query",
     "fdg_graph_emit_source", "fdg_free", "fdg_graph_specialize", "fdg_eval_device", "fdg_eval",
-    "fdg_accumulate_device", "fdg_fill_uniform_device", "fdg_copy_device", "fdg_read_device", "fdg_clock_probe_device", "fdg_graph_specialize_typed", "fdg_eval_device_typed", "fdg_graph_create_complex_view", "fdg_isa_check_hazards", "fdg_graph_release_device", "fdg_powi",
+    "fdg_accumulate_device", "fdg_fill_uniform_device", "fdg_copy_device", "fdg_read_device", "fdg_clock_probe_device", "fdg_graph_specialize_typed", "fdg_eval_device_typed", "fdg_accumulate_device_typed", "fdg_graph_create_complex_view", "fdg_isa_check_hazards", "fdg_graph_release_device", "fdg_powi",
     "fdg_eval_strided", "fdg_graph_coop_program", "fdg_graph_set_opt_params", "fdg_graph_opt_program", "fdg_graph_set_schedule_groups", "fdg_leaf_eval_device", "fdg_leaf_eval_device_tiled",
     "fdg_comm_unique_id", "fdg_comm_create", "fdg_comm_destroy", "fdg_reduce_device",
     "fdg_graph_specialize_fused", "fdg_mc_eval_device", "fdg_mc_accumulate_device", "fdg_graph_mc_program",
@@ -240,6 +240,7 @@ def lib():
     L.fdg_clock_probe_device.argtypes = [C.c_double, vp, vp]
     L.fdg_graph_specialize_typed.argtypes = [vp, C.c_int, C.c_char_p, C.c_uint]
     L.fdg_eval_device_typed.argtypes = [vp, C.c_int, vp, i64, i64, vp, i64, i64, i64, vp]
+    L.fdg_accumulate_device_typed.argtypes = [vp, C.c_int, vp, i64, i64, vp, vp, vp, i64, vp]
     L.fdg_graph_create_complex_view.argtypes = [vp, C.POINTER(vp)]
     L.fdg_isa_check_hazards.argtypes = [C.c_char_p, C.POINTER(C.c_char_p)]
     L.fdg_graph_release_device.argtypes = [vp]
@@ -518,6 +519,10 @@ class GraphHandle:
 
     def eval_device_typed(self, dtype: int, d_leaf: int, ss: int, ls: int, d_root: int, rs: int, rk: int, B: int, stream: int = 0):
         check(lib().fdg_eval_device_typed(self._h, dtype, d_leaf, ss, ls, d_root, rs, rk, B, stream))
+
+    def accumulate_device_typed(self, dtype: int, d_leaf: int, ss: int, ls: int, d_weight: int, d_acc: int, d_acc2: int, B: int, stream: int = 0):
+        """``acc[k] += sum_b w[b] * root_k(b)`` for leaves of an element type FDG_DT_* (``d_acc2``: the squares as well; 0 = not wanted)."""
+        check(lib().fdg_accumulate_device_typed(self._h, dtype, d_leaf, ss, ls, d_weight or None, d_acc or None, d_acc2 or None, B, stream))
 
     # raw-pointer device entry points (ints are device addresses) ----------- #
     def eval_device(self, d_leaf: int, ss: int, ls: int, d_root: int, rs: int, rk: int, B: int, stream: int = 0):

@@ -601,10 +601,8 @@ class GraphFunc:
         root[:, live] = h[:, live]
         return root
 
-    def _call_torch_typed(self, root, leaf):
-        """Element types other than Float64: the generated function is generic in ``eltype(leafVal)`` (static.jl:98-133; the
-        types ``julia_to_C_typestr`` names, static.jl:135-153).  Float32, ComplexF64 and ComplexF32 tensors go through the
-        per-type kernel of ``fdg_graph_specialize_typed`` (compiled on first use); ``root`` has the leaves' type."""
+    def _typed_dtype(self, leaf) -> int:
+        """FDG_DT_* of a Float32 / ComplexF64 / ComplexF32 tensor; the type's kernels are compiled on first use."""
         import torch
         dt = {torch.float32: capi.FDG_DT_F32, torch.complex128: capi.FDG_DT_C64, torch.complex64: capi.FDG_DT_C32}.get(leaf.dtype)
         if dt is None:
@@ -617,6 +615,14 @@ class GraphFunc:
             isa = self._specialize in ("isa", "isa-autotune", "auto")
             self.handle.specialize_typed(dt, self._cache_dir, capi.FDG_SPEC_ISA if isa else 0)
             self._typed_ready.add(dt)
+        return dt
+
+    def _call_torch_typed(self, root, leaf):
+        """Element types other than Float64: the generated function is generic in ``eltype(leafVal)`` (static.jl:98-133; the
+        types ``julia_to_C_typestr`` names, static.jl:135-153).  Float32, ComplexF64 and ComplexF32 tensors go through the
+        per-type kernel of ``fdg_graph_specialize_typed`` (compiled on first use); ``root`` has the leaves' type."""
+        import torch
+        dt = self._typed_dtype(leaf)
         squeeze = leaf.dim() == 1
         if squeeze:
             leaf = leaf[None, :]
@@ -634,18 +640,31 @@ class GraphFunc:
         self.last_typed_kernel = self.handle.kernel_info()["last_kernel"]
         return root
 
-    def accumulate(self, leaf, weight=None, acc=None):
-        """``acc[k] += sum_b weight[b] * root_k(b)`` on device (torch tensors)."""
+    def accumulate(self, leaf, weight=None, acc=None, acc2=None):
+        """``acc[k] += sum_b weight[b] * root_k(b)`` on device (torch tensors).  ``leaf``: a float64, float32, complex128 or
+        complex64 ``[B, L]`` CUDA tensor of any strides; ``weight``: a float64 vector (None: weight 1).  ``acc`` is float64 ``[R]``
+        for real leaves and complex128 ``[R]`` for complex ones (the weights are real: real and imaginary parts are summed
+        separately), zeros when omitted, returned.  For the types other than float64 the roots are summed as the evaluator would
+        have stored them in the leaves' type, widened to double (fdg_accumulate_device_typed; ``last_typed_kernel`` names the
+        kernel), and ``acc2``, when given, receives ``sum_b (weight[b] * root_k(b))**2`` per component.  For float64 leaves
+        ``acc2`` is refused: :meth:`accumulate_moments` is that call."""
         import torch
-        if not leaf.is_cuda or leaf.dtype != torch.float64 or leaf.dim() != 2:
-            raise TypeError("leaf must be a float64 [B, L] CUDA tensor")
+        if not leaf.is_cuda or leaf.dim() != 2 or leaf.dtype not in (torch.float64, torch.float32, torch.complex128, torch.complex64):
+            raise TypeError("leaf must be a float64, float32, complex128 or complex64 [B, L] CUDA tensor")
         if leaf.shape[1] < self.n_leaf:
             raise IndexError("BoundsError: leafVal has fewer columns than the graph has leaves")
+        typed = leaf.dtype != torch.float64
+        if acc2 is not None and not typed:
+            raise ValueError("acc2 with float64 leaves: use accumulate_moments")
+        adt = torch.complex128 if leaf.dtype.is_complex else torch.float64
         if acc is None:
-            acc = torch.zeros(self.n_root, dtype=torch.float64, device=leaf.device)
-        if (not acc.is_cuda or acc.device != leaf.device or acc.dtype != torch.float64 or not acc.is_contiguous()
-                or acc.numel() < self.n_root):
-            raise ValueError("acc must be a contiguous float64 tensor of at least n_root elements on the leaves' device")
+            acc = torch.zeros(self.n_root, dtype=adt, device=leaf.device)
+        for name, a in (("acc", acc), ("acc2", acc2)):
+            if a is not None and (not _is_torch(a) or not a.is_cuda or a.device != leaf.device or a.dtype != adt or not a.is_contiguous()
+                                  or a.numel() < self.n_root):
+                raise ValueError(f"{name} must be a contiguous {adt} tensor of at least n_root elements on the leaves' device")
+        if acc2 is not None:
+            self._distinct("acc and acc2", acc, acc2)
         w = 0
         if weight is not None:
             if (not weight.is_cuda or weight.device != leaf.device or weight.dtype != torch.float64 or weight.dim() != 1
@@ -653,10 +672,16 @@ class GraphFunc:
                 raise ValueError("weight must be a float64 vector of at least B elements on the leaves' device")
             weight = weight.contiguous()
             w = weight.data_ptr()
+        dt = self._typed_dtype(leaf) if typed else capi.FDG_DT_F64
         st = torch.cuda.current_stream(leaf.device).cuda_stream
         with torch.cuda.device(leaf.device):
-            self.handle.accumulate_device(leaf.data_ptr(), leaf.stride(0), leaf.stride(1), w, acc.data_ptr(),
-                                          leaf.shape[0], st)
+            if typed:
+                self.handle.accumulate_device_typed(dt, leaf.data_ptr(), leaf.stride(0), leaf.stride(1), w, acc.data_ptr(),
+                                                    0 if acc2 is None else acc2.data_ptr(), leaf.shape[0], st)
+                self.last_typed_kernel = self.handle.kernel_info()["last_kernel"]
+            else:
+                self.handle.accumulate_device(leaf.data_ptr(), leaf.stride(0), leaf.stride(1), w, acc.data_ptr(),
+                                              leaf.shape[0], st)
         return acc
 
 

@@ -282,6 +282,60 @@ template <class T, class S> __device__ __forceinline__ T fdg_conv(S x) { return 
 template <class T, class S> __device__ __forceinline__ T fdg_conv_cx(fdg_cx<S> z) { T r; r.re = z.re; r.im = z.im; return r; }
 )SRC";
 
+// Fused weighted accumulation for these types (fdg_accumulate_device_typed): the body of fdg_spec_typed, then per existing root
+// x = the value fdg_spec_typed would have stored, widened to double, t = w * x, a += t and (want2) q += t * t -- per component
+// for the complex types, the weight being real.  The sums live in registers across the grid-stride loop; a lane past the end
+// skips its sample (a weight of 0 would make 0 * inf = NaN of an infinite root).  After the loop each component is summed over
+// the wave by a butterfly of shuffles, the four wave sums go through LDS and lane 0 adds them in wave order:
+// partial[blk * C + c] with C = C1 (want2: 2 C1), C1 = R (complex: 2 R, re and im interleaved as in a ComplexF64 vector), sums
+// first, squares behind them.  Components of roots that do not exist are not written; fdg_reduce_partials skips them.
+static const char *kTypedAccPrelude = R"SRC(
+__device__ __forceinline__ void fdg_block_store(double v, double *sh, double *dst) {
+  for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
+  if ((threadIdx.x & 63u) == 0u) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0u) *dst = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+  __syncthreads();
+}
+)SRC";
+
+static void emit_typed_acc(std::ostringstream &os, const Lowered &p, bool cx, const char *T, const std::string &body) {
+  const uint32_t nc = cx ? 2u : 1u, C1 = nc * p.R;
+  auto comp = [&](uint32_t k, uint32_t j) { return std::to_string(nc * k + j); };
+  os << kTypedAccPrelude;
+  os << "extern \"C\" __global__ void __launch_bounds__(256) fdg_spec_typed_acc(const " << T << " *__restrict__ leaf, long ss, long ls, "
+     << "const double *__restrict__ weight, double *__restrict__ partial, long B, int want2) {\n";
+  os << "  __shared__ double fdg_sh[4];\n";
+  for (uint32_t k = 0; k < p.R; ++k)
+    if (p.root_slot[k] != FDG_NO_ROOT)
+      for (uint32_t j = 0; j < nc; ++j) os << "  double a" << comp(k, j) << " = 0.0, q" << comp(k, j) << " = 0.0;\n";
+  os << "  const long nblk = (B + 255) / 256;\n  _Pragma(\"unroll 1\")\n  for (long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {\n";
+  os << "    const long b = blk * 256 + threadIdx.x;\n    if (b >= B) continue;\n";
+  os << "    const " << T << " *lp = leaf + b * ss;\n";
+  os << body;
+  os << "    const double w = weight ? weight[b] : 1.0;\n";
+  for (uint32_t k = 0; k < p.R; ++k) {
+    if (p.root_slot[k] == FDG_NO_ROOT) continue;
+    os << "    { const " << T << " x = " << (cx ? "fdg_conv_cx<" : "fdg_conv<") << T << ">(r" << k << ");";
+    for (uint32_t j = 0; j < nc; ++j) {
+      const std::string c = comp(k, j);
+      os << " { const double t = w * (double)" << (cx ? (j ? "x.im" : "x.re") : "x") << "; a" << c << " = a" << c << " + t; if (want2) q" << c
+         << " = q" << c << " + t * t; }";
+    }
+    os << " }\n";
+  }
+  os << "  }\n";
+  os << "  double *out = partial + (long)blockIdx.x * (want2 ? " << 2 * C1 << "l : " << C1 << "l);\n";
+  for (uint32_t k = 0; k < p.R; ++k)
+    if (p.root_slot[k] != FDG_NO_ROOT)
+      for (uint32_t j = 0; j < nc; ++j) os << "  fdg_block_store(a" << comp(k, j) << ", fdg_sh, out + " << comp(k, j) << ");\n";
+  os << "  if (want2) {\n";
+  for (uint32_t k = 0; k < p.R; ++k)
+    if (p.root_slot[k] != FDG_NO_ROOT)
+      for (uint32_t j = 0; j < nc; ++j) os << "    fdg_block_store(q" << comp(k, j) << ", fdg_sh, out + " << (C1 + nc * k + j) << ");\n";
+  os << "  }\n}\n";
+}
+
 std::string emit_hip_source_typed(const Lowered &p, int dtype, bool &ok, std::string &why) {
   ok = true;
   const bool cx = dtype == FDG_DT_C64 || dtype == FDG_DT_C32;
@@ -316,6 +370,7 @@ std::string emit_hip_source_typed(const Lowered &p, int dtype, bool &ok, std::st
     if (p.root_slot[k] != FDG_NO_ROOT)
       os << "    rp[" << k << "l * rk] = " << (cx ? "fdg_conv_cx<" : "fdg_conv<") << T << ">(r" << k << ");\n";      // setindex!: convert(eltype(root), g)
   os << "  }\n}\n";
+  emit_typed_acc(os, p, cx, T, body.str());
   return os.str();
 }
 

@@ -169,6 +169,8 @@ struct fdg_graph {
   // element types other than Float64 (fdg_graph_specialize_typed): one HIP-source kernel per type, [FDG_DT_*]
   std::vector<char> typed_code[4];
   void *typed_module[4] = {nullptr, nullptr, nullptr, nullptr}, *fn_typed[4] = {nullptr, nullptr, nullptr, nullptr};
+  void *fn_typed_acc[4] = {nullptr, nullptr, nullptr, nullptr};      // fdg_spec_typed_acc of the same module
+  std::string typed_route_name;    // storage of last_kernel when it names the twin's kernel "... (ComplexF64 rows)"
   // ComplexF64 rows through the Float64 assembly back end: the graph spelled out on real and imaginary parts (owned; may be null)
   fdg_graph *cx_twin = nullptr;
   bool cx_twin_tried = false;
@@ -240,7 +242,9 @@ int ensure_ws(fdg_graph *g, size_t bytes);       // grows the handle's device wo
 int fdg_run_locked(fdg_graph *g, int mode, const double *d_leaf, int64_t ss, int64_t ls, double *d_root, int64_t rs, int64_t rk,
                    const double *d_weight, double *d_acc, int64_t B, hipStream_t st,
                    int64_t lts = 0, int64_t rts = 0);   // caller holds g->mu; lts / rts != 0: tile strides of a tile-major batch (fdg.h)
-int launch_reduce_partials(const double *partial, uint32_t nblk, uint32_t R, double *acc, hipStream_t st);
+// acc[k] += the blocks' partial[blk * stride + k], k < R (stride 0: R); live: per-column mask, column k read at live[k >> live_shift]
+int launch_reduce_partials(const double *partial, uint32_t nblk, uint32_t R, double *acc, hipStream_t st, uint32_t stride = 0,
+                           const uint8_t *live = nullptr, uint32_t live_shift = 0);
 int ensure_root_scratch(fdg_graph *g, size_t need);   // grows d_ws2 of the bound stream's scratch set (caller holds g->mu)
 int root_live_mask(fdg_graph *g, const uint8_t **out);  // device mask of the roots that exist (null: all of them); caller holds g->mu
 // the Monte-Carlo step of fdg_mc_eval_device / fdg_mc_accumulate_device after the argument checks (fdg_leaf.hip): the caller holds g->mu,

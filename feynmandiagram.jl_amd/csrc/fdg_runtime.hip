@@ -167,20 +167,24 @@ fdg_interp(const uint32_t *code_, const double *__restrict__ leaf, long ss, long
 }
 
 // acc[k] += sum over blocks of partial[blk][k], fixed order (deterministic for
-// a given grid size)
+// a given grid size).  A block's partials are `stride` doubles apart (R when they are packed); with `live`, column k is added only
+// when live[k >> live_shift] is set (the typed accumulation: a root that does not exist has no partial, and acc[k] keeps its bits)
 __global__ void fdg_reduce_partials(const double *__restrict__ partial, uint32_t nblk, uint32_t R,
-                                    double *__restrict__ acc) {
+                                    double *__restrict__ acc, uint32_t stride, const uint8_t *__restrict__ live, uint32_t live_shift) {
   __shared__ double sh[256];
   for (uint32_t k = blockIdx.x; k < R; k += gridDim.x) {
+    if (live && !live[k >> live_shift]) continue;
     double s = 0.0;
-    for (uint32_t i = threadIdx.x; i < nblk; i += 256) s = s + partial[(size_t)i * R + k];
+    for (uint32_t i = threadIdx.x; i < nblk; i += 256) s = s + partial[(size_t)i * stride + k];
     s = fdg_block_sum256(s, sh);
     if (threadIdx.x == 0) acc[k] = acc[k] + s;
   }
 }
 
-int launch_reduce_partials(const double *partial, uint32_t nblk, uint32_t R, double *acc, hipStream_t st) {
-  hipLaunchKernelGGL(fdg_reduce_partials, dim3(std::min<uint32_t>(R, 64u)), dim3(256), 0, st, partial, nblk, R, acc);
+int launch_reduce_partials(const double *partial, uint32_t nblk, uint32_t R, double *acc, hipStream_t st, uint32_t stride, const uint8_t *live,
+                           uint32_t live_shift) {
+  hipLaunchKernelGGL(fdg_reduce_partials, dim3(std::min<uint32_t>(R, 64u)), dim3(256), 0, st, partial, nblk, R, acc, stride ? stride : R, live,
+                     live_shift);
   HIP_TRY(hipGetLastError());
   return FDG_OK;
 }
@@ -681,7 +685,7 @@ static int launch_hip_source(fdg_graph *g, hipFunction_t fn, int mode, const dou
   HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, 256, 1, 1, 0, st, args, nullptr));
   if (mode == 1) {
     hipLaunchKernelGGL(fdg_reduce_partials, dim3(std::min<uint32_t>(R, 64u)), dim3(256), 0, st, partial,
-                       (uint32_t)grid, R, d_acc);
+                       (uint32_t)grid, R, d_acc, R, nullptr, 0u);
     HIP_TRY(hipGetLastError());
   }
   return FDG_OK;
@@ -790,7 +794,7 @@ int run_interpreter(fdg_graph *g, const RunArgs &a) {
   HIP_TRY(hipGetLastError());
   if (mode == 1) {
     hipLaunchKernelGGL(fdg_reduce_partials, dim3(std::min<uint32_t>(R, 64u)), dim3(256), 0, a.st, partial,
-                       (uint32_t)grid, R, a.d_acc);
+                       (uint32_t)grid, R, a.d_acc, R, nullptr, 0u);
     HIP_TRY(hipGetLastError());
   }
   return FDG_OK;
@@ -966,7 +970,7 @@ struct IsaRun {
     const int rcl = root_live_mask(g, &live);
     if (rcl) return rcl;
     hipLaunchKernelGGL(fdg_weighted_partials, dim3(pb * R), dim3(256), 0, a.st, roots, a_rk, a.d_weight, (long)a.B, R, pb, partial, live);
-    hipLaunchKernelGGL(fdg_reduce_partials, dim3(std::min<uint32_t>(R, 64u)), dim3(256), 0, a.st, partial, pb, R, a.d_acc);
+    hipLaunchKernelGGL(fdg_reduce_partials, dim3(std::min<uint32_t>(R, 64u)), dim3(256), 0, a.st, partial, pb, R, a.d_acc, R, nullptr, 0u);
     HIP_TRY(hipGetLastError());
     return FDG_OK;
   }
@@ -1472,7 +1476,7 @@ int fdg_graph_release_device(fdg_graph *g) {
   if (g->alt_module) { hipModuleUnload((hipModule_t)g->alt_module); g->alt_module = nullptr; g->fn_alt_sm = g->fn_alt_gen = nullptr; }
   if (g->mc_module) { hipModuleUnload((hipModule_t)g->mc_module); g->mc_module = nullptr; forget_isa_kernels(g->mc_kern); }
   if (g->cx_twin) fdg_graph_release_device(g->cx_twin);
-  for (int t = 0; t < 4; ++t) if (g->typed_module[t]) { hipModuleUnload((hipModule_t)g->typed_module[t]); g->typed_module[t] = nullptr; g->fn_typed[t] = nullptr; }
+  for (int t = 0; t < 4; ++t) if (g->typed_module[t]) { hipModuleUnload((hipModule_t)g->typed_module[t]); g->typed_module[t] = nullptr; g->fn_typed[t] = g->fn_typed_acc[t] = nullptr; }
   return FDG_OK;
 }
 
@@ -2413,7 +2417,7 @@ int fdg_mc_isa_run(fdg_graph *g, int mode, const double *d_K, int64_t ks, int64_
     rc = root_live_mask(g, &live);
     if (rc) return rc;
     hipLaunchKernelGGL(fdg_weighted_partials, dim3(pb * R), dim3(256), 0, st, roots, (long)ld, d_weight, (long)B, R, pb, partial, live);
-    hipLaunchKernelGGL(fdg_reduce_partials, dim3(std::min<uint32_t>(R, 64u)), dim3(256), 0, st, partial, pb, R, d_acc);
+    hipLaunchKernelGGL(fdg_reduce_partials, dim3(std::min<uint32_t>(R, 64u)), dim3(256), 0, st, partial, pb, R, d_acc, R, nullptr, 0u);
     HIP_TRY(hipGetLastError());
     return FDG_OK;
   }
@@ -2609,8 +2613,21 @@ int fdg_graph_specialize_typed(fdg_graph *g, int dtype, const char *cache_dir, u
     }
   }
   if (flags & FDG_SPEC_KEEP_SOURCE) write_file(base + ".hip", src.c_str(), src.size());
-  if (g->typed_module[dtype]) { hipModuleUnload((hipModule_t)g->typed_module[dtype]); g->typed_module[dtype] = nullptr; g->fn_typed[dtype] = nullptr; }
+  if (g->typed_module[dtype]) { hipModuleUnload((hipModule_t)g->typed_module[dtype]); g->typed_module[dtype] = nullptr; g->fn_typed[dtype] = g->fn_typed_acc[dtype] = nullptr; }
   g->typed_code[dtype].swap(co);
+  return FDG_OK;
+}
+
+// binds the handle to the device and loads the type's code object: fdg_spec_typed and fdg_spec_typed_acc (caller holds g->mu)
+static int ensure_typed_module(fdg_graph *g, int dtype) {
+  const int rc = ensure_device(g);
+  if (rc || g->typed_module[dtype]) return rc;
+  hipModule_t m; hipFunction_t f, fa;
+  hipError_t e = hipModuleLoadData(&m, g->typed_code[dtype].data());
+  if (e != hipSuccess) { set_error("hipModuleLoadData failed: " + std::string(hipGetErrorString(e))); return FDG_E_JIT; }
+  HIP_TRY(hipModuleGetFunction(&f, m, "fdg_spec_typed"));
+  HIP_TRY(hipModuleGetFunction(&fa, m, "fdg_spec_typed_acc"));
+  g->typed_module[dtype] = m; g->fn_typed[dtype] = f; g->fn_typed_acc[dtype] = fa;
   return FDG_OK;
 }
 
@@ -2635,21 +2652,72 @@ int fdg_eval_device_typed(fdg_graph *g, int dtype, const void *d_leaf, int64_t s
     }
     if (rct != FDG_E_UNSUPPORTED) return rct;
   }
-  int rc = ensure_device(g);
+  int rc = ensure_typed_module(g, dtype);
   if (rc) return rc;
-  if (!g->typed_module[dtype]) {
-    hipModule_t m; hipFunction_t f;
-    hipError_t e = hipModuleLoadData(&m, g->typed_code[dtype].data());
-    if (e != hipSuccess) { set_error("hipModuleLoadData failed: " + std::string(hipGetErrorString(e))); return FDG_E_JIT; }
-    HIP_TRY(hipModuleGetFunction(&f, m, "fdg_spec_typed"));
-    g->typed_module[dtype] = m; g->fn_typed[dtype] = f;
-  }
   const long nblk = (long)((B + 255) / 256);
   const long grid = std::min<long>(nblk, (long)g->n_cu * 8);
   long a_ss = ss, a_ls = ls, a_rs = rs, a_rk = rk, a_B = B;
   void *args[] = {(void *)&d_leaf, &a_ss, &a_ls, (void *)&d_root, &a_rs, &a_rk, &a_B};
   HIP_TRY(hipModuleLaunchKernel((hipFunction_t)g->fn_typed[dtype], (unsigned)grid, 1, 1, 256, 1, 1, 0, (hipStream_t)stream, args, nullptr));
   static const char *names[] = {"", "fdg_spec_typed<Float32>", "fdg_spec_typed<ComplexF64>", "fdg_spec_typed<ComplexF32>"};
+  g->last_kernel = names[dtype];
+  return FDG_OK;
+}
+
+// acc[k] += sum_b w_b root_k(b) (and acc2[k] += sum_b (w_b root_k(b))^2) for the element types other than Float64: the roots are the
+// values fdg_eval_device_typed stores, widened to double; complex types accumulate (re, im) pairs with real weights.
+int fdg_accumulate_device_typed(fdg_graph *g, int dtype, const void *d_leaf, int64_t ss, int64_t ls, const double *d_weight, double *d_acc,
+                                double *d_acc2, int64_t B, void *stream) {
+  if (!g) { set_error("null handle"); return FDG_E_INVALID; }
+  if (dtype < 0 || dtype > FDG_DT_C32) { set_error("unknown element type"); return FDG_E_INVALID; }
+  if (B < 0) { set_error("n_sample < 0"); return FDG_E_INVALID; }
+  if (!d_acc) { set_error("null device buffer"); return FDG_E_INVALID; }
+  if (d_acc == d_acc2) { set_error("d_acc and d_acc2 are the same buffer"); return FDG_E_INVALID; }
+  if (dtype == FDG_DT_F64) {      // the ordinary entry points (they refuse a null leaf pointer themselves)
+    return d_acc2 ? fdg_accumulate_device_moments(g, (const double *)d_leaf, ss, ls, 0, nullptr, 0, 1, d_weight, d_acc, d_acc2, B, stream)
+                  : fdg_accumulate_device(g, (const double *)d_leaf, ss, ls, d_weight, d_acc, B, stream);
+  }
+  std::lock_guard<std::mutex> lk(g->mu);
+  fdg::KnobScope knob_scope(&g->knobs);
+  if (g->typed_code[dtype].empty()) { set_error("fdg_accumulate_device_typed: call fdg_graph_specialize_typed for this element type first"); return FDG_E_INVALID; }
+  if (g->prog.L && !d_leaf) { set_error("null device buffer"); return FDG_E_INVALID; }
+  if (B == 0 || g->prog.R == 0) return FDG_OK;
+  const uint32_t R = g->prog.R;
+  // ComplexF64 rows: the graph spelled out on real and imaginary parts (fdg_eval_device_typed's condition, without the root strides); its
+  // 2 R accumulators are the ComplexF64[R] vector
+  if (dtype == FDG_DT_C64 && g->cx_twin && ls == 1 && ss >= (int64_t)g->prog.L && B >= 64 && 2 * ss < (1ll << 23)) {
+    const int rct = d_acc2 ? fdg_accumulate_device_moments(g->cx_twin, (const double *)d_leaf, 2 * ss, 1, 0, nullptr, 0, 1, d_weight, d_acc, d_acc2, B, stream)
+                           : fdg_accumulate_device(g->cx_twin, (const double *)d_leaf, 2 * ss, 1, d_weight, d_acc, B, stream);
+    if (rct == FDG_OK) {
+      g->typed_route_name = std::string(g->cx_twin->last_kernel) + " (ComplexF64 rows)";
+      g->last_kernel = g->typed_route_name.c_str();
+      return rct;
+    }
+    if (rct != FDG_E_UNSUPPORTED) return rct;
+  }
+  int rc = ensure_typed_module(g, dtype);
+  if (rc) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  rc = fdg_bind_stream_ws(g, stream);
+  if (rc) return rc;
+  const bool cx = dtype != FDG_DT_F32;
+  const uint32_t C1 = cx ? 2 * R : R, C = d_acc2 ? 2 * C1 : C1;      // the layout of emit_typed_acc: sums, then squares
+  const long nblk = (long)((B + 255) / 256);
+  const long grid = std::min<long>(nblk, (long)g->n_cu * 8);
+  rc = ensure_ws(g, (size_t)grid * C * sizeof(double));
+  if (rc) return rc;
+  double *partial = (double *)g->d_ws;
+  const uint8_t *live = nullptr;
+  rc = root_live_mask(g, &live);
+  if (rc) return rc;
+  long a_ss = ss, a_ls = ls, a_B = B;
+  int want2 = d_acc2 ? 1 : 0;
+  void *args[] = {(void *)&d_leaf, &a_ss, &a_ls, (void *)&d_weight, (void *)&partial, &a_B, &want2};
+  HIP_TRY(hipModuleLaunchKernel((hipFunction_t)g->fn_typed_acc[dtype], (unsigned)grid, 1, 1, 256, 1, 1, 0, st, args, nullptr));
+  rc = launch_reduce_partials(partial, (uint32_t)grid, C1, d_acc, st, C, live, cx ? 1u : 0u);
+  if (!rc && d_acc2) rc = launch_reduce_partials(partial + C1, (uint32_t)grid, C1, d_acc2, st, C, live, cx ? 1u : 0u);
+  if (rc) return rc;
+  static const char *names[] = {"", "fdg_spec_typed_acc<Float32>", "fdg_spec_typed_acc<ComplexF64>", "fdg_spec_typed_acc<ComplexF32>"};
   g->last_kernel = names[dtype];
   return FDG_OK;
 }

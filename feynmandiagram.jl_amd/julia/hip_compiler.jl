@@ -223,6 +223,18 @@ function eval_device!(f::GraphFunc, d_root::Ptr{T}, d_leaf::Ptr{T}, B::Integer;
         (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Cvoid}),
         f.handle, dt, d_leaf, leaf_strides[1], leaf_strides[2], d_root, root_strides[1], root_strides[2], B, stream))
 end
+# The Monte-Carlo step for these types (include/fdg.h: fdg_accumulate_device_typed): d_acc[k] += sum_b w[b] * root_k(b) over the roots as
+# eval_device! would have stored them, widened to Float64.  d_acc (and d_acc2, the sums of squares; C_NULL: not wanted) is a Vector{Float64}
+# of length R for Float32 leaves and a Vector{ComplexF64} of length R for complex leaves; d_weight a Vector{Float64} or C_NULL (weight 1)
+function accumulate_device!(f::GraphFunc, d_acc::Ptr, d_leaf::Ptr{T}, d_weight::Ptr{Float64}, B::Integer;
+    d_acc2::Ptr=C_NULL, leaf_strides=(1, B), stream::Ptr{Cvoid}=C_NULL) where {T<:Union{Float32,ComplexF64,ComplexF32}}
+    dt = _FDG_DT[T]
+    cdir = isnothing(f.cache_dir) ? C_NULL : f.cache_dir
+    _fdg_check(ccall((:fdg_graph_specialize_typed, _libfdg), Cint, (Ptr{Cvoid}, Cint, Cstring, Cuint), f.handle, dt, cdir, Cuint(4)))
+    _fdg_check(ccall((:fdg_accumulate_device_typed, _libfdg), Cint,
+        (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}),
+        f.handle, dt, d_leaf, leaf_strides[1], leaf_strides[2], d_weight, d_acc, d_acc2, B, stream))
+end
 
 # Tile-major batches (include/fdg.h: fdg_eval_device_tiled): the leaves as an Array{Float64,3}(undef, 64, L, cld(B, 64)) -- sample in tile,
 # leaf, tile -- and the roots as (64, R, cld(B, 64)); what a Monte-Carlo driver that owns its sample batch should allocate: one

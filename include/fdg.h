@@ -283,9 +283,8 @@ int fdg_graph_pool_program(const fdg_graph *g, const fdg_opt_params *prm, uint32
  * promotion rules are C++'s here), products and sums of values of the type stay in the type, Complex * Complex is
  * (ar br - ai bi, ar bi + ai br) without contraction, Complex * Real scales both components (base/complex.jl), and a root is
  * converted to the element type when stored.  Covered: Sum, Prod, Power{2}, Power{3} (other literal powers take type-specific
- * paths through Base.power_by_squaring: FDG_E_UNSUPPORTED).  No fused accumulation, no ISA back end for these types: they go
- * through the compiler-scheduled kernel (every BASELINE configuration is Float64).  FDG_DT_F64 forwards to the ordinary entry
- * points. */
+ * paths through Base.power_by_squaring: FDG_E_UNSUPPORTED).  No ISA back end for these types: they go through the
+ * compiler-scheduled kernels (every BASELINE configuration is Float64).  FDG_DT_F64 forwards to the ordinary entry points. */
 #define FDG_DT_F64 0
 #define FDG_DT_F32 1
 #define FDG_DT_C64 2
@@ -303,6 +302,25 @@ int fdg_graph_specialize_typed(fdg_graph *g, int dtype, const char *cache_dir, u
 int fdg_graph_create_complex_view(const fdg_graph *g, fdg_graph **out);
 int fdg_eval_device_typed(fdg_graph *g, int dtype, const void *d_leaf, int64_t leaf_sample_stride, int64_t leaf_leaf_stride,
                           void *d_root, int64_t root_sample_stride, int64_t root_root_stride, int64_t n_sample, void *stream);
+/* The Monte-Carlo step for these types: the integrand's `sum weight * root over samples` around the generic eval_graph!, fused so that
+ * the roots never reach memory.  d_acc[k] += sum_b w_b x_k(b), where x_k(b) is the value fdg_eval_device_typed would have stored as
+ * root k of sample b -- converted to the element type first -- widened to Float64; with d_acc2 (optional, NULL: not wanted)
+ * d_acc2[k] += sum_b (w_b x_k(b))^2.  Float32: d_acc and d_acc2 hold R doubles.  ComplexF64 / ComplexF32: R (re, im) pairs of
+ * doubles, a ComplexF64[R]; the weights are real, so the sums run per component, and d_acc2[k] is (sum (w re)^2, sum (w im)^2).
+ * d_weight: Float64[n_sample], NULL = weight 1.  Both buffers are added to; entries of roots that do not exist (FDG_NO_ROOT) keep
+ * their bits (the sign of a zero included) on the per-type kernel's route.  A lane past the batch skips its sample (no weight-0 term: an infinite root gives an infinite sum, not NaN).
+ * The kernel, fdg_spec_typed_acc, has the body of fdg_spec_typed: Float64 sums in registers, a shuffle butterfly per wave, the four wave sums
+ * added in wave order, one partial per block and component; then fdg_reduce_partials in block order: no float atomics, bitwise
+ * reproducible for the same arguments on the same device.  ComplexF64 rows under fdg_eval_device_typed's condition (the view exists,
+ * leaf_leaf_stride == 1, leaf_sample_stride >= L, n_sample >= 64, the doubled stride addressable) go through the view's
+ * fdg_accumulate_device -- with d_acc2 its fdg_accumulate_device_moments, one bin.  fdg_kernel_info::last_kernel names the route:
+ * the view's kernel followed by " (ComplexF64 rows)", or fdg_spec_typed_acc<Float32 | ComplexF64 | ComplexF32>.  No promise of equal
+ * bits is made between the two routes, nor between calls with and without d_acc2.  FDG_DT_F64 forwards to fdg_accumulate_device,
+ * with d_acc2 to fdg_accumulate_device_moments with no bins, n_bin 1, tile stride 0.  FDG_E_INVALID before any device work: null
+ * handle, unknown dtype, n_sample < 0, a type fdg_graph_specialize_typed has not compiled, NULL d_acc, d_acc == d_acc2, NULL d_leaf
+ * when the graph has leaves.  n_sample == 0 or a graph without roots: FDG_OK, nothing touched. */
+int fdg_accumulate_device_typed(fdg_graph *g, int dtype, const void *d_leaf, int64_t leaf_sample_stride, int64_t leaf_leaf_stride,
+                                const double *d_weight, double *d_acc, double *d_acc2, int64_t n_sample, void *stream);
 
 /* Evaluate B samples, buffers in device memory.
  *   leaf value i of sample b : d_leaf[b*leaf_sample_stride + i*leaf_leaf_stride]
